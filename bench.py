@@ -6,11 +6,15 @@ GroupAdam-V4 apply over one batch of int64 ids, BASELINE.json config 2:
 One "step" = one lookup of the batch + one fused apply of the batch's gradients (dedup +
 segment-sum + row update).  Inputs (ids, grads) are resident in HBM before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W]           (N > 1: launched by torch.distributed.run)
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+                                                            (N > 1: launched by torch.distributed.run)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the dominant
-kernel (HIP events on the op's own stream, kv_profile_*) and `cpu_baseline` (the CPU oracle —
-a port of the reference algorithm — timed on this host on a bounded sample).
+Prints ONE JSON line on rank 0: the headline (`metric`, `value`, `unit`, `ms_per_step`, ...) of the K
+timed steps.  A plain run does only that: set-up, W warm-up steps, K timed steps.  `--full` adds
+everything else, measured after the timed region: `roofline` for the dominant kernel (HIP events on
+the op's own stream, kv_profile_*), the per-kernel table, the sub-records of `extras` and
+`cpu_baseline` (the CPU oracle — a port of the reference algorithm — timed on this host on a
+bounded sample).  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import ctypes
@@ -339,6 +343,33 @@ def extras(args, ops, L, _lib, var, slot, dev, pool, out, K, N, D, gen, state):
   return res
 
 
+DUMP_ROWS_BYTES = 32 << 20     # --dump-outputs: the sample of the lookup's output rows
+DUMP_STATE_BYTES = 16 << 20    # ... and of the var + slot rows of the batch's distinct ids
+
+
+def dump_outputs(dirname, out, ids, ops, var, slot):
+  """--dump-outputs: what the last timed step handed its caller, as float32 .npy files under `dirname` (48 MiB at most):
+  lookup_rows.npy, the lookup's output rows at a fixed, seeded sample of batch positions (all of them when they fit);
+  var_rows.npy / slot_rows.npy, the rows the step's apply left in the var and its slot table for a fixed, seeded sample
+  of the batch's distinct ids, in ascending id order (var None: the sharded path, whose tables hold a part of the keys
+  each).  The inputs are seeded, so the same arguments give the same positions and ids from run to run; the values agree
+  up to the order in which a repeated id's gradient rows are summed (not fixed outside deterministic mode: ~1e-6
+  absolute after a few hundred steps of the default workload)."""
+  os.makedirs(dirname, exist_ok=True)
+  rng = np.random.default_rng(SEED)
+  N, D = out.shape
+  n = min(N, DUMP_ROWS_BYTES // (4 * D))
+  pos = torch.from_numpy(np.sort(rng.choice(N, n, replace=False))).to(out.device)
+  np.save(os.path.join(dirname, "lookup_rows.npy"), out[pos].cpu().numpy().astype(np.float32))
+  if var is None:
+    return
+  u = torch.unique(ids)
+  n = min(u.numel(), DUMP_STATE_BYTES // (4 * 4 * D))         # var row (D) + slot row (3 D) per id
+  keys = u[torch.from_numpy(np.sort(rng.choice(u.numel(), n, replace=False))).to(u.device)]
+  np.save(os.path.join(dirname, "var_rows.npy"), ops.kv_variable_gather_or_zeros_v2(var, keys).cpu().numpy().astype(np.float32))
+  np.save(os.path.join(dirname, "slot_rows.npy"), ops.kv_variable_gather_or_zeros_v2(slot, keys).cpu().numpy().astype(np.float32))
+
+
 def exchange_block(world, cap, D, distinct_per_batch, lossless, staged):
   """The `exchange` object of a sharded line: what one rank puts on the wire per step.  Every peer gets one segment of
   peer_capacity + 1 records per exchange — (id, count) pairs out, rows back, summed gradient rows out — whatever the
@@ -361,16 +392,21 @@ def main():
   ap.add_argument("--dim", type=int, default=32)
   ap.add_argument("--zipf", type=float, default=1.2)
   ap.add_argument("--pool", type=int, default=8, help="distinct pre-generated batches cycled through")
+  ap.add_argument("--full", action="store_true",
+                  help="after the timed steps, measure everything besides the headline: roofline and per-kernel table, the "
+                       "sub-records of extras(), the CPU baseline (a plain run prints the headline only)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the last timed step computed to DIR/*.npy (float32; see dump_outputs)")
   ap.add_argument("--cpu-keys", type=int, default=50_000_000,
                   help="keys of the CPU baseline's table (BASELINE.md section 3: configs[1] = 50 M)")
   ap.add_argument("--cpu-build-budget", type=float, default=240.0,
                   help="seconds the CPU table build may take; when it runs out the baseline is timed on the keys inserted so far (and says so)")
   ap.add_argument("--cpu-steps", type=int, default=10)
   ap.add_argument("--no-extras", action="store_true",
-                  help="skip the measurements taken after the timed region (skew sweep, op boundary, no token, staged)")
-  ap.add_argument("--no-cpu-baseline", action="store_true")
+                  help="with --full: skip the measurements taken after the timed region (skew sweep, op boundary, no token, staged)")
+  ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
   ap.add_argument("--no-kernel-events", action="store_true",
-                  help="diagnostic: do not bracket kernels with HIP events in the timed region (no roofline)")
+                  help="diagnostic, with --full: do not bracket kernels with HIP events in the timed region (no roofline)")
   ap.add_argument("--no-token", action="store_true",
                   help="diagnostic: the apply rebuilds the batch index instead of taking over the lookup's")
   ap.add_argument("--deterministic", action="store_true",
@@ -385,6 +421,8 @@ def main():
   ap.add_argument("--force-sharded", action="store_true",
                   help="run the all_to_all exchange path even with one rank (exercises the N > 1 code on one GPU)")
   args = ap.parse_args()
+  if args.steps < 1:
+    ap.error("--steps must be at least 1")
 
   rank = int(os.environ.get("RANK", "0"))
   world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -483,16 +521,17 @@ def main():
     ids = splitmix64(z.sample(N, gen))
     grad = torch.randn(N, D, device=dev, generator=gen) * 1e-2
     U = int(torch.unique(ids).numel())
-    # entries of the batch = distinct (2048-id tile, id) pairs; S1 of them occur once in their tile (their gradient
-    # row goes straight to the apply, the others' rows are summed per tile first)
-    tl = torch.arange(N, device=dev, dtype=torch.int64) // 2048
-    _, ec = torch.unique(torch.stack([tl, ids], 1), dim=0, return_counts=True)
-    pool.append((ids, grad, U, int(ec.numel()), int((ec == 1).sum())))
-    del tl, ec
+    E = S1 = None
+    if args.full:
+      # entries of the batch = distinct (2048-id tile, id) pairs; S1 of them occur once in their tile (their gradient
+      # row goes straight to the apply, the others' rows are summed per tile first): the roofline's byte model
+      tl = torch.arange(N, device=dev, dtype=torch.int64) // 2048
+      _, ec = torch.unique(torch.stack([tl, ids], 1), dim=0, return_counts=True)
+      E, S1 = int(ec.numel()), int((ec == 1).sum())
+      del tl, ec
+    pool.append((ids, grad, U, E, S1))
   out = torch.empty((N, D), dtype=torch.float32, device=dev)
   U_mean = float(np.mean([p[2] for p in pool]))
-  E_mean = float(np.mean([p[3] for p in pool]))
-  S1_mean = float(np.mean([p[4] for p in pool]))
 
   state = {"b1p": np.float32(0.9), "b2p": np.float32(0.999)}
 
@@ -579,19 +618,24 @@ def main():
   # are ~16 % of this step), so only ONE kernel — the slowest one, found during the warm-up steps,
   # where every kernel is bracketed — carries events inside the timed region; that is the launch
   # `roofline` is computed from.  The per-kernel table (`kernels_ms`) comes from `steps` further
-  # fully bracketed steps after the clock has stopped.
-  ops.kv_profile_enable(var, 16 * args.warmup + 8)
+  # fully bracketed steps after the clock has stopped.  (--full only: a plain run brackets nothing.)
+  if args.full:
+    ops.kv_profile_enable(var, 16 * args.warmup + 8)
   for k in range(args.warmup):
     step(k)
   torch.cuda.synchronize()
   # the kernel to bracket in the timed region: the slowest one of three further untimed steps (the first warm-up
-  # steps still allocate and insert)
-  ops.kv_profile_enable(var, 64)
+  # steps still allocate and insert).  A plain run takes the same three steps, unbracketed: the timed steps start
+  # from the same state either way.
+  dom = sample_every = None
+  if args.full:
+    ops.kv_profile_enable(var, 64)
   for k in range(3):
     step(args.warmup + k)
   torch.cuda.synchronize()
-  warm = ops.kv_profile_read(var)
-  dom = max(warm, key=lambda k: warm[k][0] / max(warm[k][1], 1))
+  if args.full:
+    warm = ops.kv_profile_read(var)
+    dom = max(warm, key=lambda k: warm[k][0] / max(warm[k][1], 1))
   graphs = None
   if args.graph and not shard_path:
     # one graph per pooled batch: no launch gaps.  (The Adam powers b1p / b2p are arguments by value: a replay uses
@@ -609,10 +653,11 @@ def main():
     for g in graphs:           # untimed: every graph once
       g.replay()
     torch.cuda.synchronize()
-  ops.kv_profile_enable(var, 0 if (args.no_kernel_events or graphs) else args.steps + 8)
-  ops.kv_profile_select(var, [dom])
-  sample_every = SAMPLE_EVERY if SAMPLE_EVERY > 0 else (2 if args.steps <= 24 else 5 if args.steps <= 64 else 8)   # >= 8 launches timed
-  ops.kv_profile_sample(var, sample_every)     # a pair of event markers costs ~4 us of stream time per launch
+  if args.full:
+    ops.kv_profile_enable(var, 0 if (args.no_kernel_events or graphs) else args.steps + 8)
+    ops.kv_profile_select(var, [dom])
+    sample_every = SAMPLE_EVERY if SAMPLE_EVERY > 0 else (2 if args.steps <= 24 else 5 if args.steps <= 64 else 8)   # >= 8 launches timed
+    ops.kv_profile_sample(var, sample_every)     # a pair of event markers costs ~4 us of stream time per launch
   barrier()
   t0 = time.perf_counter()
   if graphs:
@@ -628,9 +673,43 @@ def main():
     tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if one_gpu_debug else dev)
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
-  timed = ops.kv_profile_read(var)
-  ops.kv_profile_select(var, None)
-  ops.kv_profile_sample(var, 1)
+  if args.full:
+    timed = ops.kv_profile_read(var)
+    ops.kv_profile_select(var, None)
+    ops.kv_profile_sample(var, 1)
+  if args.dump_outputs and rank == 0:     # before anything else runs on the tables
+    last = (args.warmup + args.steps - 1) % len(pool)
+    dump_outputs(args.dump_outputs, out, pool[last][0], ops, None if shard_path else var, slot)
+    torch.cuda.synchronize()
+
+  ms_per_step = dt / args.steps * 1e3
+  value = N * world / (dt / args.steps)
+  head = {
+      "metric": "lookups+GroupAdam-applies/sec and HBM GB/s, 1M int64 ids x dim32",
+      "value": value,
+      "unit": "ids/s (each id: 1 embedding lookup + 1 fused GroupAdam-V4 apply)",
+      "n_gpus": world,
+      "steps": args.steps,
+      "warmup": args.warmup,
+      "ms_per_step": ms_per_step,
+      "higher_is_better": True,
+      "scaling": "weak",
+      "vs_baseline": None,
+      "dtype": "f32",
+      "data": "synthetic",
+      "config": {"workload": "configs[1]: %dM-key KvVariable x dim%d per GPU, %d ids/batch per GPU Zipf(%.1f), "
+                             "lookup + sparse GroupAdam apply" % (args.keys // 1_000_000, D, N, args.zipf),
+                 "keys": K, "dim": D, "batch": N, "zipf": args.zipf, "global_batch": N * world, "unique_per_batch": U_mean,
+                 "parallelism": ("table sharded over %d GPUs by (mix64(id) >> 32) %% G, fixed-capacity id/row/grad exchange, "
+                                 "grouped ncclSend/ncclRecv over RCCL" % world) if world > 1 else "single GPU"},
+  }
+  if not args.full:
+    if rank == 0:
+      emit(json.dumps(head))
+    if shard_path:
+      teardown()
+    return
+
   prof = timed
   if not args.no_kernel_events:
     ops.kv_profile_enable(var, 8 * args.steps + 8)
@@ -669,8 +748,6 @@ def main():
     torch.cuda.synchronize()
     lookup_complete_ms = e0.elapsed_time(e1) / 12
 
-  ms_per_step = dt / args.steps * 1e3
-  value = N * world / (dt / args.steps)
   if args.no_kernel_events or graphs:
     if rank == 0:
       emit(json.dumps({"ms_per_step": ms_per_step, "value": value, "note": "diagnostic run without kernel events"}))
@@ -684,6 +761,8 @@ def main():
   # the partition pass (its gather blocks copy the rows); the apply reads every gradient row once and
   # reads + writes the optimizer state of every unique key in k_apply_sorted.
   Ub = U_mean
+  E_mean = float(np.mean([p[3] for p in pool]))
+  S1_mean = float(np.mean([p[4] for p in pool]))
   fused = prof["apply_tsum"][1] > 0 or prof["apply_tile"][1] > 0     # the entry-list pipeline ran (kv_fused.h)
   if fused:
     alg = {
@@ -737,25 +816,9 @@ def main():
   except (OSError, ValueError, KeyError):
     tj = None
 
-  res = {
-      "metric": "lookups+GroupAdam-applies/sec and HBM GB/s, 1M int64 ids x dim32",
-      "value": value,
-      "unit": "ids/s (each id: 1 embedding lookup + 1 fused GroupAdam-V4 apply)",
-      "n_gpus": world,
-      "steps": args.steps,
-      "warmup": args.warmup,
-      "ms_per_step": ms_per_step,
-      "higher_is_better": True,
-      "scaling": "weak",
-      "vs_baseline": None,
-      "dtype": "f32",
-      "data": "synthetic",
-      "config": {"workload": "configs[1]: %dM-key KvVariable x dim%d per GPU, %d ids/batch per GPU Zipf(%.1f), "
-                             "lookup + sparse GroupAdam apply" % (args.keys // 1_000_000, D, N, args.zipf),
-                 "keys": K, "dim": D, "batch": N, "zipf": args.zipf, "global_batch": N * world, "unique_per_batch": Ub,
-                 "tile_entries_per_batch": E_mean, "tile_entries_single": S1_mean,
-                 "parallelism": ("table sharded over %d GPUs by (mix64(id) >> 32) %% G, fixed-capacity id/row/grad exchange, "
-                                 "grouped ncclSend/ncclRecv over RCCL" % world) if world > 1 else "single GPU"},
+  res = dict(head)
+  res["config"].update({"tile_entries_per_batch": E_mean, "tile_entries_single": S1_mean})
+  res.update({
       "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_fetch_uncorrected": traffic_raw,
                    "traffic_source": traffic_src,
@@ -784,7 +847,7 @@ def main():
                                    "frac_of_peak": apply_bytes / (apply_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                    "applies_per_s": N / (apply_ms * 1e-3),
                                    "unique_applies_per_s": Ub / (apply_ms * 1e-3)}},
-  }
+  })
   if shard_path:
     # On the sharded path every rank runs the same kernels on what the exchange hands it (unique
     # ids per source rank; sizes change with every batch), so the per-launch byte model above does

@@ -26,3 +26,33 @@ def test_exchange_block_of_the_eight_gpu_line():
   # a world of one puts nothing on the wire; the rehearsal transport says what it is
   assert b.exchange_block(1, cap, D, distinct, True, False)["wire_bytes_per_rank_per_step"] == 0
   assert "staged" in b.exchange_block(2, cap, D, distinct, True, True)["transport"]
+
+
+def test_dump_outputs_samples_a_fixed_bounded_set_of_rows(tmp_path):
+  """--dump-outputs on the sharded path's form (lookup rows only), on host tensors: float32, within the byte budget, the
+  same seeded positions from call to call, the whole output when it fits."""
+  import numpy as np
+  import torch
+  b = _bench()
+  D = 32
+  out = torch.arange(300000 * D, dtype=torch.float32).reshape(300000, D)
+  for d in ("a", "b"):
+    b.dump_outputs(str(tmp_path / d), out, None, None, None, None)
+  assert sorted(os.listdir(tmp_path / "a")) == ["lookup_rows.npy"]
+  a, c = np.load(str(tmp_path / "a" / "lookup_rows.npy")), np.load(str(tmp_path / "b" / "lookup_rows.npy"))
+  assert a.dtype == np.float32 and a.nbytes <= b.DUMP_ROWS_BYTES and a.shape == (b.DUMP_ROWS_BYTES // (4 * D), D)
+  assert np.array_equal(a, c)
+  pos = a[:, 0] // D                                   # row r of `out` starts with r * D
+  assert np.array_equal(a, out.numpy()[pos.astype(np.int64)]) and (np.diff(pos) > 0).all()
+  small = out[:1000]
+  b.dump_outputs(str(tmp_path / "s"), small, None, None, None, None)
+  assert np.array_equal(np.load(str(tmp_path / "s" / "lookup_rows.npy")), small.numpy())
+
+
+def test_bench_options():
+  """--full (everything besides the headline) and --dump-outputs are on the command line."""
+  import subprocess
+  import sys
+  r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+  assert r.returncode == 0, r.stderr[-2000:]
+  assert "--full" in r.stdout and "--dump-outputs" in r.stdout

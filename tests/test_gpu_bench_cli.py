@@ -1,6 +1,6 @@
-"""bench.py's contract: the default single-GPU line carries every required key, and the N > 1
-control flow runs (two ranks on one GPU, collectives staged through gloo — a debugging mode of
-bench.py; real runs use RCCL with one rank per GPU)."""
+"""bench.py's contract: a plain run prints the headline of its timed steps and nothing else, and dumps what its last
+step computed; the --full single-GPU line carries every required key, and the N > 1 control flow runs (two ranks on one
+GPU, collectives staged through gloo — a debugging mode of bench.py; real runs use RCCL with one rank per GPU)."""
 import json
 import os
 import socket
@@ -21,12 +21,46 @@ def _line(out):
   return json.loads(rows[0])
 
 
+HEADLINE = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data", "config"}
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+  """No --full: the timed steps' headline only (no roofline, per-kernel table, sub-records or CPU baseline); --steps sets
+  the timed steps; --dump-outputs writes the last step's lookup rows and the state its apply left as float32 .npy, 64 MB
+  at most, and a second run with the same arguments computes the same (up to the order repeated ids are summed in)."""
+  if not torch.cuda.is_available():
+    pytest.skip("needs a GPU")
+  import numpy as np
+  N, D = 200000, 32
+  dumps = []
+  for run in ("a", "b"):
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "7", "--warmup", "2", "--keys", "2000000", "--batch", str(N),
+                        "--dump-outputs", str(tmp_path / run)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    assert set(d) == HEADLINE, sorted(set(d) ^ HEADLINE)
+    assert d["n_gpus"] == 1 and d["steps"] == 7 and d["warmup"] == 2 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and abs(d["value"] - N / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+    assert sorted(os.listdir(tmp_path / run)) == ["lookup_rows.npy", "slot_rows.npy", "var_rows.npy"]
+    z = {f[:-4]: np.load(str(tmp_path / run / f)) for f in os.listdir(tmp_path / run)}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in z.values())
+    assert sum(a.nbytes for a in z.values()) <= 64 * 10**6
+    assert z["lookup_rows"].shape == (N, D)                       # the whole output fits the budget at this size
+    assert z["var_rows"].shape[1] == D and z["slot_rows"].shape == (z["var_rows"].shape[0], 3 * D)
+    assert z["var_rows"].shape[0] > 1000 and (np.abs(z["var_rows"]).sum(1) > 0).all()     # keys of the batch: present
+    dumps.append(z)
+  for k in dumps[0]:
+    np.testing.assert_allclose(dumps[1][k], dumps[0][k], rtol=1e-3, atol=1e-6, err_msg=k)
+
+
 @pytest.mark.gpu
 def test_bench_single_gpu_line():
   if not torch.cuda.is_available():
     pytest.skip("needs a GPU")
-  r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--keys", "2000000", "--cpu-keys", "100000",
-                      "--cpu-steps", "1"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+  r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "2", "--keys", "2000000", "--cpu-keys",
+                      "100000", "--cpu-steps", "1"], cwd=ROOT, capture_output=True, text=True, timeout=600)
   assert r.returncode == 0, r.stderr[-2000:]
   d = _line(r.stdout)
   assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["value"] > 0
@@ -59,7 +93,7 @@ def test_bench_two_ranks_control_flow():
   s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
   env = dict(os.environ, KV_BENCH_ONE_GPU="1")
   r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                      "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1",
+                      "127.0.0.1", "--master-port", str(port), "bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
                       "--keys", "1000000", "--batch", "200000"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
   assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
   d = _line(r.stdout)
@@ -87,7 +121,7 @@ def test_forced_sharded_world_of_one_accounts_for_its_step():
   (the event markers cost stream time: the sum may run over ms_per_step, not under it)"""
   if not torch.cuda.is_available():
     pytest.skip("needs a GPU")
-  r = subprocess.run([sys.executable, "bench.py", "--force-sharded", "--steps", "8", "--warmup", "2", "--keys", "2000000",
+  r = subprocess.run([sys.executable, "bench.py", "--full", "--force-sharded", "--steps", "8", "--warmup", "2", "--keys", "2000000",
                       "--batch", "400000", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
   assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
   d = _line(r.stdout)
@@ -104,8 +138,8 @@ def test_bench_launches_its_own_ranks():
   env = dict(os.environ, KV_BENCH_ONE_GPU="1")
   for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
     env.pop(k, None)
-  r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--keys", "1000000",
-                      "--batch", "200000"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+  r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--keys",
+                      "1000000", "--batch", "200000"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
   assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
   d = _line(r.stdout)
   assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 400000 and d["value"] > 0
@@ -116,8 +150,9 @@ def _two_ranks(extra, timeout=600):
   env = dict(os.environ, KV_BENCH_ONE_GPU="1")
   for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
     env.pop(k, None)
-  return subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--keys", "1000000",
-                         "--batch", "200000"] + extra, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
+  return subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--keys",
+                         "1000000", "--batch", "200000"] + extra, cwd=ROOT, env=env, capture_output=True, text=True,
+                        timeout=timeout)
 
 
 @pytest.mark.gpu

@@ -1,9 +1,11 @@
 """The TF custom-op shim (tfplus_amd/tf_shim/kv_variable_ops_hip.cc) cannot be compiled in this image (no
 TensorFlow headers), so its op SCHEMAS — the drop-in interface: op name, inputs and outputs in order, attr names,
 types and defaults, statefulness — are checked here as text against the reference's own REGISTER_OP blocks
-(tfplus/kv_variable/ops/*.cc), read at test time; nothing of the reference is stored in this repository.
-Skipped where the reference tree is absent (the GPU box)."""
-import glob
+(tfplus/kv_variable/ops/*.cc) through tests/golden/tf_reference_ops.json: SHA-256 digests of the reference's schemas,
+op names and Python-layer calls (tests/golden/make_tf_reference_ops.py writes it from a reference checkout); nothing
+of the reference's text is stored in this repository."""
+import hashlib
+import json
 import os
 import re
 
@@ -11,7 +13,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "tfplus_amd", "tf_shim", "kv_variable_ops_hip.cc")
-REF_OPS = "/root/reference/tfplus/kv_variable/ops"
+REF_RECORD = os.path.join(ROOT, "tests", "golden", "tf_reference_ops.json")
 
 # every op of SURVEY.md §8(b), the "next" rows, and what the reference's Python layer needs to build a graph with a
 # Saver (KvVariableSaveable) and its hygiene calls
@@ -33,7 +35,6 @@ REQUIRED = ["KvVariable", "KvVariableV2", "KvVariableV3", "KvVariableV4", "InitK
 EXCLUDED = {"append_kv_variable_for_multi_hash", "kv_variable_export_for_multi_hash", "kv_variable_apply_snapshot",
             "kv_variable_apply_snapshot_v2", "kv_variable_dynamic_restore", "kv_variable_load_remote_table", "save_v3",
             "kv_variable_group_sparse_apply_adam_v2", "kv_variable_group_sparse_apply_adam_new_v2"}
-REF_PY = "/root/reference/tfplus/kv_variable/python"
 
 
 def _snake(name):
@@ -42,18 +43,23 @@ def _snake(name):
   return out
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PY), reason="reference tree not present")
+def _digest(x):
+  """SHA-256 of a name or a schema item list (the form tests/golden/tf_reference_ops.json records)."""
+  return hashlib.sha256(json.dumps(x, separators=(",", ":")).encode()).hexdigest()
+
+
+def _reference():
+  with open(REF_RECORD) as f:
+    return json.load(f)
+
+
 def test_required_covers_what_the_reference_python_layer_calls():
-  files = [os.path.join(REF_PY, "ops", f) for f in ("kv_variable_ops.py", "embedding_ops.py", "variable_scope.py")] + \
-          [os.path.join(REF_PY, "training", f) for f in ("group_adam.py", "adagrad.py", "sparse_group_ftrl.py", "adam.py",
-                                                         "gradient_descent.py")]
-  called = set()
-  for f in files:
-    if os.path.exists(f):
-      called |= set(re.findall(r"gen_kv_variable_ops\.([a-z_0-9]+)", open(f).read()))
-  have = {_snake(n) for n in REQUIRED}
-  missing = sorted(called - have - EXCLUDED)
-  assert not missing, missing
+  called = _reference()["python_layer_calls_sha256"]
+  assert len(called) >= len(REQUIRED) // 2
+  have = {_digest(n) for n in {_snake(n) for n in REQUIRED} | EXCLUDED}
+  missing = [h for h in called if h not in have]
+  assert not missing, ("%d wrapper(s) that the reference's Python layer calls are neither REQUIRED nor EXCLUDED "
+                       "(tests/golden/make_tf_reference_ops.py names them)" % len(missing))
 
 
 def _strip_comments(text):
@@ -209,16 +215,15 @@ def test_shim_registers_device_gpu_kernels():
     assert any('HostMemory("table_handle")' in r for r in gpu[op]), op
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_OPS), reason="reference tree not present")
 def test_shim_schemas_equal_the_reference():
-  ref = {}
-  for f in sorted(glob.glob(os.path.join(REF_OPS, "*.cc"))):
-    ref.update(_schemas(open(f).read()))
+  rec = _reference()
+  names, ref = set(rec["op_names_sha256"]), rec["schemas_sha256"]
   ours = _schemas(open(SHIM).read())
   assert len(ours) >= len(REQUIRED)
   for name, items in ours.items():
-    assert name in ref, "the reference registers no op named %s" % name
-    assert items == ref[name], "%s:\n  shim      %s\n  reference %s" % (name, items, ref[name])
+    assert _digest(name) in names, "the reference registers no op named %s" % name
+    assert name in ref, "%s: no recorded schema (rerun tests/golden/make_tf_reference_ops.py)" % name
+    assert _digest(items) == ref[name], "%s: the shim's schema differs from the reference's:\n  shim %s" % (name, items)
 
 
 def test_shim_type_checks_against_a_mock_of_the_tf_api():

@@ -1,5 +1,5 @@
 # usage: bash tools/ab_env.sh "ENV=1 ENV2=2" "..." : bench.py under each environment setting
-B="--steps 20 --warmup 3 --no-cpu-baseline --no-extras"
+B="--full --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
 i=0
 for e in "$@"; do
   i=$((i+1))

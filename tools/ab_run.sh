@@ -1,5 +1,5 @@
 # usage: bash tools/ab_run.sh "<env>" variant ... : bench.py with the product build, then with each build/ab/<variant>.so, under <env>
-B="--steps 20 --warmup 3 --no-cpu-baseline --no-extras"
+B="--full --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
 E="$1"; shift
 run() { tag=$1; shift; env $E "$@" > gpurun_out/ab_$tag.json 2> gpurun_out/ab_$tag.err; python3 - <<PY
 import json

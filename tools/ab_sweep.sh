@@ -1,5 +1,5 @@
 # usage: bash tools/ab_sweep.sh variant ... : bench.py's skew sweep / op-boundary records with the product build, then with each build/ab/<variant>.so
-B="--steps 20 --warmup 3 --no-cpu-baseline"
+B="--full --steps 20 --warmup 3 --no-cpu-baseline"
 run() { tag=$1; shift; "$@" > gpurun_out/abs_$tag.json 2> gpurun_out/abs_$tag.err; python3 - <<PY
 import json
 try:

@@ -2,7 +2,7 @@ cd /tmp && export TMPDIR=/tmp
 repo=${GRAFT_REPO_ROOT:-/root/repo}
 out=$repo/gpurun_out/prof_r04_sharded
 mkdir -p $out
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $repo/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --force-sharded > $out/bench.json 2> $out/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $repo/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras --force-sharded > $out/bench.json 2> $out/trace.err
 python3 - <<PY
 import csv,glob,collections
 f=glob.glob("$out/trace/*/*_kernel_trace.csv")[0]
