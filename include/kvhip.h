@@ -453,6 +453,10 @@ int kv_bucket_by_owner(kv_handle_t h, const void* ids, int64_t n, const int64_t*
 typedef struct kv_comm* kv_comm_t;
 int kv_comm_unique_id(void* id128);
 int kv_comm_create(int world, int rank, const void* id128, int device, kv_comm_t* out);
+/* on != 0: this rank's own segment of every exchange on `comm` goes through ncclSend / ncclRecv like a peer's, instead
+ * of staying in place or being a device copy (lets one GPU run the grouped send / recv code).  Off by default; this
+ * communicator only.  KV_INVALID_ARGUMENT on a communicator without RCCL (staged, or world 1 with id128 == NULL). */
+int kv_comm_set_self_via_rccl(kv_comm_t comm, int on);
 /* A communicator whose exchanges the CALLER makes on the host (a rehearsal of the N > 1 control flow where RCCL cannot
  * run: several ranks sharing one GPU, a CPU-side transport in a test).  Same ops, same agreement and failure protocol
  * as over RCCL; the library synchronises its stream, then calls
@@ -486,6 +490,7 @@ int kv_comm_all_to_all(kv_comm_t comm, const void* send, void* recv, int64_t byt
  * KV_FAILED_PRECONDITION).  A batch that needs more for one owner: its surplus ids read zeros and their gradients
  * are dropped; the next kv_shard_lookup / kv_shard_lookup_route returns KV_RESOURCE_EXHAUSTED AFTER queuing all its
  * own work (a rank that reports stays in step with its peers).  Raise peer_capacity on every rank.
+ * The table's dim: a multiple of 4 up to 256, its ids int64, not in occurrence-order mode (else KV_UNIMPLEMENTED).
  *
  * One training step per rank, all on the device, no host synchronisation, no size exchange:
  *   lookup  kv_shard_lookup_route   ids -> distinct ids + occurrence counts -> the owners' segments of send_pairs

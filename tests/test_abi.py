@@ -60,6 +60,14 @@ def test_product_never_imports_the_oracle():
   assert not bad, bad
 
 
+def test_library_reads_no_environment_variable():
+  """No code-path choice of libkvhip.so is left to a user-set variable: its sources never call getenv."""
+  csrc = os.path.join(ROOT, "tfplus_amd", "csrc")
+  bad = [f for f in sorted(os.listdir(csrc))
+         if f.endswith((".hip", ".h")) and "getenv" in open(os.path.join(csrc, f), errors="replace").read()]
+  assert not bad, bad
+
+
 @pytest.mark.gpu
 def test_c_host_program_over_the_abi(tmp_path):
   """A C++ program that includes only include/kvhip.h + HIP (no Python, no torch) drives the table."""

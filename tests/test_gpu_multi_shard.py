@@ -28,7 +28,6 @@ def test_multi_shard_ops_equal_the_per_table_sharded_ops():
     pytest.skip("needs a GPU")
   sys.path.insert(0, ROOT)
   from tfplus_amd.kv_variable.python.ops import gen_kv_variable_ops as ops
-  os.environ["KV_COMM_SELF_VIA_RCCL"] = "1"
   rng = np.random.default_rng(8)
   dims = [16, 32, 8, 64, 32]
   T = len(dims)
@@ -40,7 +39,7 @@ def test_multi_shard_ops_equal_the_per_table_sharded_ops():
       v = _table(ops, D, init, True); s = _table(ops, 3 * D, np.zeros((4, 3 * D), np.float32), True)
       vs.append(v); ss.append(s); shs.append(ops.KvShard(v, 1, 0, ops.KV_OWNER_HASH, max_ids=1 << 14))
     sets.append((vs, ss, shs))
-  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id())
+  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id(), self_via_rccl=True)
   for step in range(3):
     ids = [torch.from_numpy(rng.integers(0, 3000, 5000 + 777 * k)).cuda() for k in range(T)]
     if step == 2:
@@ -136,7 +135,6 @@ def test_multi_shard_lossless_tables_grow_together():
     pytest.skip("needs a GPU")
   sys.path.insert(0, ROOT)
   from tfplus_amd.kv_variable.python.ops import gen_kv_variable_ops as ops
-  os.environ["KV_COMM_SELF_VIA_RCCL"] = "1"
   rng = np.random.default_rng(12)
   D, T = 16, 3
   vs, ss, shs, v2, s2 = [], [], [], [], []
@@ -148,7 +146,7 @@ def test_multi_shard_lossless_tables_grow_together():
     sh.set_lossless(k != 1)                                                # table 1: default mode, roomy capacity
     shs.append(sh)
     v2.append(_table(ops, D, init, False)); s2.append(_table(ops, 3 * D, np.zeros((4, 3 * D), np.float32), False))
-  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id())
+  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id(), self_via_rccl=True)
   for step in range(2):
     ids = [torch.from_numpy(rng.choice(50000, 2500 + 500 * k, replace=False)).cuda() for k in range(T)]
     grads = [torch.from_numpy((rng.uniform(0.5, 1.5, (i.numel(), D)) * 1e-2).astype(np.float32)).cuda() for i in ids]

@@ -311,8 +311,7 @@ def test_native_shard_lossless_whole_op_through_rccl():
     ops.kv_set_clock_days(h, DAY); ops.kv_set_seed(h, 3); ops.init_kv_variable_v2(h, t)
   # (no set_lossless call: lossless is the library's DEFAULT — VERDICT r3 item 6 — a batch that overflows the capacity
   #  grows it on every rank and is routed again: no zero rows, no dropped gradients)
-  os.environ["KV_COMM_SELF_VIA_RCCL"] = "1"
-  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id())
+  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id(), self_via_rccl=True)
   hp = (0.1, 0.9, 0.999, 0.9, 0.999, 1e-8, 0, 0, 0)
   for step, n in enumerate((5000, 12000, 300)):
     ids = torch.from_numpy(rng.choice(100000, n, replace=False)).cuda()
@@ -342,8 +341,7 @@ def test_native_shard_lossy_mode_is_the_opt_in():
   table = np.ones((4, D), np.float32)
   ops, vars_, slots, shards = _native_setup(1, D, "hash", table, cap=16, max_ids=4096)
   shards[0].set_lossless(False)
-  os.environ["KV_COMM_SELF_VIA_RCCL"] = "1"
-  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id())
+  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id(), self_via_rccl=True)
   ids = torch.arange(0, 200, dtype=torch.int64).cuda()
   out = shards[0].lookup(comm, ids).cpu().numpy()
   assert np.count_nonzero(out.any(axis=1)) == 16 and shards[0].peer_capacity == 16
@@ -406,9 +404,8 @@ def test_native_shard_world_of_one_equals_the_unsharded_ops(with_rccl):
     ops.kv_set_deterministic(h, True)
   for h in (vars_[0], slots[0]):
     ops.kv_set_deterministic(h, True)
-  if with_rccl:   # the self segment through grouped ncclSend / ncclRecv as a peer's would go (read once, at the first exchange)
-    os.environ["KV_COMM_SELF_VIA_RCCL"] = "1"
-  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id() if with_rccl else None)
+  # with_rccl: the self segment through grouped ncclSend / ncclRecv as a peer's would go
+  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id() if with_rccl else None, self_via_rccl=with_rccl)
   for step in range(3):
     ids = torch.from_numpy(rng.integers(0, 5000, 20000)).cuda()
     g = torch.from_numpy((rng.standard_normal((20000, D)) * 1e-2).astype(np.float32)).cuda()
@@ -453,8 +450,7 @@ def test_native_shard_a_failing_rank_still_queues_its_exchanges():
   D = 16
   table = np.ones((4, D), np.float32)
   ops, vars_, slots, shards = _native_setup(1, D, "hash", table, max_ids=1024)
-  os.environ["KV_COMM_SELF_VIA_RCCL"] = "1"
-  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id())
+  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id(), self_via_rccl=True)
   good = torch.arange(100, dtype=torch.int64).cuda()
   out = shards[0].lookup(comm, good)
   assert torch.equal(out, torch.ones(100, D, device="cuda"))
@@ -469,6 +465,43 @@ def test_native_shard_a_failing_rank_still_queues_its_exchanges():
   shards[0].apply(comm, ops.OPT_GROUP_ADAM_V4, [slots[0]], torch.full((100, D), 0.5, device="cuda"), (0.1, 0.9, 0.999, 0.9, 0.999, 1e-8, 0, 0, 0))
   torch.cuda.synchronize()
   assert torch.equal(out, torch.ones(100, D, device="cuda")) and ops.kv_variable_size_v2(vars_[0]) == 100
+  del comm
+
+
+@pytest.mark.gpu
+def test_native_shard_refuses_a_dim_the_entry_list_kernels_do_not_serve():
+  """kv_shard_create takes the dims its route, finish and owner kernels serve — multiples of 4 up to 256 — and refuses
+  the rest with KV_UNIMPLEMENTED."""
+  if not torch.cuda.is_available():
+    pytest.skip("needs a GPU")
+  sys.path.insert(0, ROOT)
+  import ctypes
+  from tfplus_amd import _lib
+  from tfplus_amd.kv_variable.python.ops import gen_kv_variable_ops as ops
+  for D, ok in ((256, True), (260, False), (512, False)):
+    hv = ops.kv_variable([D])
+    ops.init_kv_variable_v2(hv, np.zeros((4, D), np.float32))
+    sh = ctypes.c_void_p()
+    rc = _lib.lib().kv_shard_create(hv.ptr, 2, 0, 0, 1 << 16, 0, ctypes.byref(sh))
+    if ok:
+      assert rc == 0, _lib.lib().kv_last_error()
+      assert _lib.lib().kv_shard_destroy(sh) == 0
+    else:
+      assert rc == _lib.KV_UNIMPLEMENTED and "up to 256" in _lib.lib().kv_last_error().decode(), (D, rc)
+
+
+@pytest.mark.gpu
+def test_comm_self_via_rccl_needs_an_rccl_communicator():
+  """kv_comm_set_self_via_rccl is a setting of one communicator: KV_INVALID_ARGUMENT on one without RCCL."""
+  if not torch.cuda.is_available():
+    pytest.skip("needs a GPU")
+  sys.path.insert(0, ROOT)
+  from tfplus_amd import _lib
+  from tfplus_amd.kv_variable.python.ops import gen_kv_variable_ops as ops
+  comm = ops.KvComm(1, 0, None)
+  assert _lib.lib().kv_comm_set_self_via_rccl(comm.ptr, 1) == _lib.KV_INVALID_ARGUMENT
+  with pytest.raises(Exception):
+    ops.KvComm(1, 0, None, self_via_rccl=True)
   del comm
 
 

@@ -76,6 +76,7 @@ SIGNATURES = {
     "kv_bucket_by_owner": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kv_comm_unique_id": (_i32, [_vp]),
     "kv_comm_create": (_i32, [_i32, _i32, _vp, _i32, _c.POINTER(_vp)]),
+    "kv_comm_set_self_via_rccl": (_i32, [_vp, _i32]),
     "kv_comm_create_staged": (_i32, [_i32, _i32, _vp, _vp, _vp, _i32, _c.POINTER(_vp)]),
     "kv_comm_destroy": (_i32, [_vp]),
     "kv_forget_stream": (_i32, [_vp]),

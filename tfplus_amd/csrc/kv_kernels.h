@@ -336,7 +336,7 @@ struct PartArgs {
   unsigned* route_overflow;        // pinned flag: a segment was too small
   unsigned* route_gcount;          // [MAXW + 1] records per owner so far; [MAXW]: blocks of the launch that are done
   unsigned* route_need;            // != nullptr: the LAST block of the launch writes the segments' headers, the largest segment
-                                   // wanted (here) and clears the counters — what k_seg_headers_take does in its own launch
+                                   // wanted (here) and clears the counters
   unsigned* route_uhint;           // pinned host word (may be null): the batch's distinct ids
   unsigned uniq_serial;            // k_uapply (kv_uapply.h): this launch's stamp (1 .. 65535)
   int use_mirror;                  // the lean update reads / writes the slot row's frequency word and flags in the var row's
@@ -1665,12 +1665,10 @@ __device__ __forceinline__ void apply_fin_body(const WsDev& w, const PartArgs& a
 // ------------------------------------------------------------------------------------------
 // VQ = float4 vectors per row (dim / 4) when > 0 (power of two); VQ = 0 -> generic dim
 // ORDER: the same pass files every position in the sorted list (order_pos): the training lookup's last kernel
-// the row a position reads: its entry's row, through w.row_map when the rows live in an exchange buffer (sharded
-// lookup: entry -> dense unique index -> the record the id was sent in); skipped records read the zero row
+// the row a position reads: its entry's row; skipped records read the zero row
 __device__ __forceinline__ unsigned gather_row(const WsDev& w, unsigned sr) {
   if (sr == 0xFFFFFFFFu) return 0u;
-  const unsigned r = w.ent_b[sr & SLOT_MASK];
-  return w.row_map ? (unsigned)w.row_map[r] : r;
+  return w.ent_b[sr & SLOT_MASK];
 }
 
 template <int VQ, bool ORDER = false>
@@ -2072,75 +2070,6 @@ __global__ void __launch_bounds__(TB) k_owner_scatter_fixed(const long long* __r
       }
     }
   }
-}
-// The same in two launches instead of four (hist + scan + scatter in one): a block counts its tile's ids per owner in LDS, takes
-// its place in every owner's segment with one atomic per owner, writes its records.  The order of the records
-// inside a segment then depends on block timing — it decides nothing but the owner's row numbering — so the
-// deterministic mode keeps the four-kernel version above.  gcount: [world] segment fill, zero between batches.
-__global__ void __launch_bounds__(TB) k_owner_route_fixed(const long long* __restrict__ ids, const int* __restrict__ cnts,
-                                                          long long n, int world, int rule, unsigned C,
-                                                          long long* __restrict__ seg, int* __restrict__ slot_of,
-                                                          unsigned* __restrict__ overflow, unsigned* __restrict__ gcount) {
-  __shared__ unsigned h[MAXW], base[MAXW];
-  if (threadIdx.x < MAXW) h[threadIdx.x] = 0;
-  __syncthreads();
-  const long long b0 = (long long)blockIdx.x * RT;
-  long long id[RT / TB];
-  unsigned d[RT / TB], r[RT / TB];
-  if (b0 < n) {
-#pragma unroll
-    for (int k = 0; k < RT / TB; ++k) {
-      const long long i = b0 + k * TB + threadIdx.x;
-      d[k] = 0xFFFFFFFFu;
-      if (i < n && cnts[i] > 0) {   // gaps of the sparse unique numbering carry a count of 0
-        id[k] = ids[i];
-        d[k] = owner_rank(id[k], world, rule);
-        r[k] = atomicAdd(&h[d[k]], 1u);
-      }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < world) base[threadIdx.x] = h[threadIdx.x] ? atomicAdd(&gcount[threadIdx.x], h[threadIdx.x]) : 0u;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < RT / TB; ++k) {
-      const long long i = b0 + k * TB + threadIdx.x;
-      if (d[k] != 0xFFFFFFFFu) {
-        const unsigned rr = base[d[k]] + r[k];
-        if (rr < C) {
-          const size_t slot = (size_t)d[k] * (C + 1) + 1 + rr;
-          seg[2 * slot] = id[k];
-          seg[2 * slot + 1] = (long long)cnts[i];
-          slot_of[i] = (int)slot;
-        } else {
-          slot_of[i] = 0;
-          atomicExch(overflow, 1u);
-        }
-      }
-    }
-  }
-}
-// ... and its headers, from the fill counters, which it zeroes for the next batch.  (A last-block-done epilogue in
-// the kernel above would need a device-scope release fence per block; on gfx950 that writes the XCD's L2 back and
-// cost 60 us behind the partition pass.)
-// need[0] (may be null) = the largest segment this batch WANTED, capped or not: what peer_capacity would have had to be
-// (one block: thread 0 clears it, every owner's thread raises it)
-// uhint (pinned host word, may be null) = the batch's distinct ids: the next route picks its partition count by it
-__global__ void k_seg_headers_take(unsigned* __restrict__ gcount, int world, unsigned C, long long* __restrict__ seg,
-                                   unsigned* __restrict__ need, unsigned* __restrict__ uhint) {
-  __shared__ unsigned tot;
-  const int d = threadIdx.x;
-  if (d == 0) { if (need) *need = 0u; tot = 0u; }
-  __syncthreads();
-  if (d < world) {
-    const unsigned c = gcount[d];
-    gcount[d] = 0;
-    seg[2 * (size_t)d * (C + 1)] = c < C ? c : C;
-    seg[2 * (size_t)d * (C + 1) + 1] = 0;
-    if (need) atomicMax(need, c);
-    atomicAdd(&tot, c);
-  }
-  __syncthreads();
-  if (d == 0 && uhint) __hip_atomic_store(uhint, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 // the segments' headers {records in the segment (at most C), 0}
 __global__ void k_seg_headers(const long long* __restrict__ counts, int world, unsigned C, long long* __restrict__ seg,

@@ -220,7 +220,7 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
     __syncthreads();
     if (UQ && a.route_world > 0) {
       // ---- the sharded route: every distinct id to its owner's segment of the send buffer.  The block counts its ids per
-      //      owner in LDS and reserves their records with ONE atomic per owner (what k_owner_route_fixed does per 1024 ids)
+      //      owner in LDS and reserves their records with ONE atomic per owner
       if (tid < MAXW) rh[tid] = 0;
       __syncthreads();
       unsigned rd[PERU], rr[PERU];
@@ -679,7 +679,7 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
 
 // The sharded route (PA_UNIQUE with route_need set): the block that finishes LAST writes every segment's header {records,
 // 0}, the largest segment any owner was asked for and the batch's distinct ids, and clears the counters for the next
-// launch — k_seg_headers_take without its launch.  Every block comes through here, whatever its partition held.
+// launch.  Every block comes through here, whatever its partition held.
 __device__ __forceinline__ void papply_route_tail(const PartArgs& a, const int mode_, const unsigned nblocks) {
   if ((mode_ & 0xFF) != PA_UNIQUE || a.route_world <= 0 || a.route_need == nullptr) return;   // (uniform over the launch)
   // No fence: the block's adds to the owners' counters are RETURNING device-scope atomics (their values place the

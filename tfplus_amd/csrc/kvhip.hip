@@ -647,8 +647,6 @@ unsigned pick_partitions(long long n, bool many_distinct = false) {
     const unsigned P0 = pick_partitions(n, false);
     return P0 < (unsigned)MAX_P ? P0 * 2u : P0;
   }
-  static const long long forced = [] { const char* e = getenv("KV_FORCE_P"); return e ? atoll(e) : 0ll; }();
-  if (forced > 0) return (unsigned)forced;  // diagnostic A/B only (tools/)
   unsigned long long want = std::min<unsigned long long>(1024, (unsigned long long)((n + 31) / 32));
   want = std::max<unsigned long long>(want, (unsigned long long)((n + 1023) / 1024));
   unsigned P = 1;
@@ -659,12 +657,7 @@ unsigned pick_partitions(long long n, bool many_distinct = false) {
 // the entry-list pipeline's partition count when nothing is known about the batch: about 384 ids per partition block
 // (k_part2 works on a tile's distinct keys, not on positions: fewer, fatter partitions than the sorted-position
 // pipeline wants), 64 .. 1024; never more than pick_partitions(n), so the workspace of either rule holds it
-long long forced_P() {   // KV_FORCE_P: diagnostic A/B only (tools/)
-  static const long long forced = [] { const char* e = getenv("KV_FORCE_P"); return e ? atoll(e) : 0ll; }();
-  return forced;
-}
 unsigned fused_default_P(long long n) {
-  if (forced_P() > 0) return (unsigned)forced_P();
   unsigned P = 64;
   while ((long long)P * 384 < n && P < 1024u) P <<= 1;
   return std::min(P, pick_partitions(n, false));
@@ -750,7 +743,6 @@ int ensure_workspace(kv_table* t, long long n, bool need_part, hipStream_t s) {
 }
 
 bool fused_ok(int D);
-bool fused_off();
 bool fused_tab(const kv_table* t);
 
 // The sharded owner ops (kv_shard_lookup_serve / kv_shard_apply_serve) read a rank's OWN exchange segment where it was
@@ -793,7 +785,6 @@ WsDev ws_view(kv_table* t, long long n) {
   d.P = pick_partitions(n);
   d.pshift = 64 - ilog2(d.P);
   d.seg_cap = 0;
-  d.row_map = nullptr;
   d.zero_counts = nullptr;
   d.dbg = w.dbg;
   // entry-list pipeline: mrow lives in slot_rank's storage
@@ -920,12 +911,8 @@ void launch_order(const TableDev& td, const WsDev& wd, long long n, hipStream_t 
 constexpr long long FUSED_MAX_N = 1ll << 23;
 // dims it serves: every multiple of 4 up to 256 (rows of dim / 4 float4; a row's lane group is the next power of two,
 // the lanes past the row's end masked: dims 12, 20, 100 ... run the same kernels as 16, 32, 128)
-bool fused_off() {
-  static const bool off = [] { const char* e = getenv("KV_NO_FUSED"); return e && atoi(e) != 0; }();   // A/B against the sorted-position pipeline
-  return off;
-}
 bool fused_ok(int D) {
-  if (fused_off() || (D & 3) != 0) return false;
+  if ((D & 3) != 0) return false;
   const int q = D / 4;
   return q >= 1 && q <= 64;
 }
@@ -1057,7 +1044,7 @@ int flush_part(kv_table* t, hipStream_t s);
 // change, the authoritative records; the keys' next lean apply finds no valid mirror, takes the general path once and
 // leaves a fresh clean copy (finish_key).  The ops that keep the epoch name their tables in tl_mirror_keep while they
 // enter: the training / inference lookups on the var (they touch var records and rows only), the GroupAdam and Adagrad
-// applies on (var, slot), single and batched, and the ops that only borrow a table's workspace.  KV_NO_MIRROR=1: never (A/B).
+// applies on (var, slot), single and batched, and the ops that only borrow a table's workspace.
 static thread_local kv_table* tl_mirror_keep[2] = {nullptr, nullptr};   // [0]: kept in its VAR role, [1]: kept in its SLOT role
 static thread_local kv_table* const* tl_mirror_keep_vars = nullptr;      // ... a batched op's tables in their VAR role
 static thread_local int tl_mirror_keep_nvars = 0;
@@ -1089,10 +1076,6 @@ static bool mirror_kept_as_slot(const kv_table* t) {
   for (int i = 0; i < tl_mirror_keep_nslots; ++i)
     if (tl_mirror_keep_slots[i] == t) return true;
   return false;
-}
-bool mirror_off() {
-  static const bool off = [] { const char* e = getenv("KV_NO_MIRROR"); return e && e[0] == '1'; }();
-  return off;
 }
 // held: the table of the pair whose lock the caller holds (the var itself, or its slot table): the views come from there
 void mirror_end_epoch(kv_table* var, hipStream_t s, const kv_table* held) {
@@ -1141,7 +1124,7 @@ void mirror_ban(kv_table* t, hipStream_t s) {
 }
 // (var, slot) become a mirror pair — or stay / become unpaired when the slot table already serves another var
 bool mirror_pair(kv_table* v, kv_table* sl, hipStream_t s) {
-  if (mirror_off() || sl->mirror_shared || v->mirror_banned || sl->mirror_banned) return false;
+  if (sl->mirror_shared || v->mirror_banned || sl->mirror_banned) return false;
   if (v->mirror_slot == sl && sl->mirror_var == v) return true;
   if (sl->mirror_var && sl->mirror_var != v) {   // a second var on one slot table: no mirrors for it at all
     mirror_unpair(sl->mirror_var, s, sl);
@@ -1299,7 +1282,7 @@ void choose_partitions(kv_table* t, WsDev& wd, long long n) {
     const unsigned u_prev = t->err_host ? reinterpret_cast<volatile unsigned*>(t->err_host)[1] : 0u;
     // (not in deterministic mode: the partitioning decides the order of a tile's entries, hence of the additions —
     // there it depends on the batch alone)
-    const bool hinted = !t->deterministic && t->batch_n_prev == n && u_prev > 0u && forced_P() <= 0;
+    const bool hinted = !t->deterministic && t->batch_n_prev == n && u_prev > 0u;
     t->batch_n_prev = n;
     if (hinted) {
       // about 384 distinct keys per partition block (the LDS hash of k_part2 holds 768 before a partition splits),
@@ -2853,7 +2836,7 @@ int kv_unique(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, 
     return KV_OK;
   }
   if (n < 0 || !ids || !uniq) return fail(KV_INVALID_ARGUMENT, "bad arguments");
-  if (n > (fused_off() ? (1ll << 21) : FUSED_MAX_N)) return fail(KV_UNIMPLEMENTED, "%lld ids in one call (limit 2^%d)", (long long)n, fused_off() ? 21 : 23);
+  if (n > FUSED_MAX_N) return fail(KV_UNIMPLEMENTED, "%lld ids in one call (limit 2^23)", (long long)n);
   DeviceGuard dg(t->device);
   std::lock_guard<std::mutex> l(t->mu);
   MirrorKeep mk(t, t);   // `t` lends its workspace: neither its rows nor any record is touched
@@ -2868,14 +2851,9 @@ int kv_unique(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, 
   pa.out_counts = uniq_counts;
   pa.det = det_mode(t);
   pa.n = n;
-  if (!fused_off()) {   // the entry-list kernels, whatever the table's dim (no row is touched)
-    if ((rc = fused_unique_pass(t, wd, pa, ids, counts, n, s))) return rc;
-    if (inverse) k_inverse_e<<<nblocks(n, TB, 2048), TB, 0, s>>>(t->ws.pos_ent, wd.ent_b, n, inverse);
-  } else {
-    launch_tile<false>(t, wd, ids, counts, n, s);   // ent_a = occurrences | saturating count per tile (and zeroes wd.ctr)
-    launch_part_keys<MODE_UNIQUE>(wd, pa, s);
-    if (inverse) k_dedup_inverse<<<nblocks(n, TB, 2048), TB, 0, s>>>(wd, n, inverse);
-  }
+  // the entry-list kernels, whatever the table's dim (no row is touched)
+  if ((rc = fused_unique_pass(t, wd, pa, ids, counts, n, s))) return rc;
+  if (inverse) k_inverse_e<<<nblocks(n, TB, 2048), TB, 0, s>>>(t->ws.pos_ent, wd.ent_b, n, inverse);
   if (num_unique_dev) k_store_count<<<1, 1, 0, s>>>(wd.ctr, (long long*)num_unique_dev);
   HIP_TRY(hipGetLastError());
   if (num_unique) {   // synchronous form
@@ -3486,6 +3464,7 @@ struct kv_comm {
   kv_comm_exchange_fn xfn = nullptr;
   kv_comm_max_fn mfn = nullptr;
   void* user = nullptr;
+  bool self_via_rccl = false;        // kv_comm_set_self_via_rccl: this rank's own segment goes through RCCL too
 };
 // the segments really travel (RCCL or the caller's transport); else: a world of one whose exchange is a device copy
 static inline bool wired(const kv_comm* c) { return c->comm != nullptr || c->xfn != nullptr; }
@@ -3505,7 +3484,7 @@ struct kv_shard {
   float* recv_rows = nullptr;
   long long* counts = nullptr;       // [world]
   unsigned* hist = nullptr;          // [world][tiles]
-  unsigned* gcount = nullptr;        // [MAXW + 1] k_owner_route_fixed's counters (zero between launches)
+  unsigned* gcount = nullptr;        // [MAXW + 1] the route's per-owner record counters (k_papply PA_UNIQUE; zero between launches)
   unsigned* overflow = nullptr;      // pinned, mapped: a segment was too small for a batch
   unsigned long long overflows = 0;  // batches reported so far
   unsigned* need = nullptr;          // device [2]: the largest segment the last routed batch wanted; the same over all ranks
@@ -3514,9 +3493,7 @@ struct kv_shard {
                                      // kv_shard_set_lossless(shard, 0) opts into the synchronisation-free mode
   unsigned long long grows = 0;      // times the capacity was raised
   long long n_last = 0;              // ids of the batch whose index `route` holds
-  bool ordered = false;              // ... and whether its positions are filed (order, work items) yet
   bool self_in_place = false;        // this rank's own segments are read from the send buffers (no device copy in the exchange)
-  bool route_fused = false;          // ... and whether it is an entry-list index (k_ltile<NOTABLE> + k_papply PA_UNIQUE), not a sorted position list
   const kv_comm* verified = nullptr; // the communicator whose ranks were seen to agree on world / capacity / dim
   uint64_t route_token = 0;
   kv_batch_token_t serve_token = 0;
@@ -3631,6 +3608,12 @@ int kv_comm_create_staged(int world, int rank, kv_comm_exchange_fn exchange, kv_
   return KV_OK;
 }
 
+int kv_comm_set_self_via_rccl(kv_comm_t c, int on) {
+  if (!c || !c->comm) return fail(KV_INVALID_ARGUMENT, "kv_comm_set_self_via_rccl: not an RCCL communicator");
+  c->self_via_rccl = on != 0;
+  return KV_OK;
+}
+
 int kv_comm_stream(kv_comm_t c, kv_stream_t* stream) {
   if (!c || !stream) return fail(KV_INVALID_ARGUMENT, "kv_comm_stream: null argument");
   *stream = (kv_stream_t)c->stream;
@@ -3683,10 +3666,9 @@ static int comm_exchange(kv_comm* c, int nseg, const void* const* sends, void* c
     HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_in, 0));
   }
   // this rank's own segment never meets RCCL: it stays in place (skip_self: the sharded whole ops read it in the send
-  // buffer) or is a device copy at HBM speed, queued in front of the group
-  // (KV_COMM_SELF_VIA_RCCL=1, a test switch: the self segment goes through ncclSend / ncclRecv like a peer's, which
-  // lets a single GPU exercise the grouped send / recv code)
-  static const bool self_rccl = [] { const char* e = getenv("KV_COMM_SELF_VIA_RCCL"); return e && e[0] == '1'; }();
+  // buffer) or is a device copy at HBM speed, queued in front of the group — unless kv_comm_set_self_via_rccl asked for
+  // it to go through ncclSend / ncclRecv like a peer's
+  const bool self_rccl = c->self_via_rccl;
   if (!self_rccl)
     for (int k = 0; k < nseg; ++k)
       if (!(skip_self && skip_self[k]))
@@ -3729,9 +3711,8 @@ int kv_shard_create(kv_handle_t local_table, int world, int rank, int owner_rule
   if (owner_rule != KV_OWNER_HASH && owner_rule != KV_OWNER_MOD) return fail(KV_INVALID_ARGUMENT, "owner_rule %d", owner_rule);
   if (max_ids < 1 || max_ids > (1ll << 21)) return fail(KV_INVALID_ARGUMENT, "max_ids %lld: 1 .. 2^21 ids per sharded batch", (long long)max_ids);
   if (local_table->key_dtype == KV_DT_INT32) return fail(KV_UNIMPLEMENTED, "sharded tables carry int64 ids");
-  if ((local_table->dim & 3) != 0) return fail(KV_UNIMPLEMENTED, "sharded tables: dim %d (multiples of 4)", local_table->dim);
-  if (fused_off())   // (the owners' serve side exists on the entry-list kernels alone)
-    return fail(KV_UNIMPLEMENTED, "KV_NO_FUSED=1 is an A/B switch of the single-table ops: no sharded tables under it");
+  if (!fused_ok(local_table->dim))   // (the route, the finish and the owners' serve side exist on the entry-list kernels alone)
+    return fail(KV_UNIMPLEMENTED, "sharded tables: dim %d (multiples of 4 up to 256)", local_table->dim);
   if (local_table->occurrence_order)
     return fail(KV_UNIMPLEMENTED, "sharded tables: occurrence-order mode is a single-table notion (senders pre-sum, owners add the senders' sums in rank order)");
   DeviceGuard dg(local_table->device);
@@ -3756,7 +3737,7 @@ int kv_shard_create(kv_handle_t local_table, int world, int rank, int owner_rule
       rc = fail(KV_RESOURCE_EXHAUSTED, "kv_shard_create: allocation failed");
       break;
     }
-    sh->overflow[0] = 0; sh->overflow[1] = 0;   // [1]: the last routed batch's distinct ids (k_seg_headers_take)
+    sh->overflow[0] = 0; sh->overflow[1] = 0;   // [1]: the last routed batch's distinct ids (k_papply PA_UNIQUE)
     if ((rc = shard_alloc_buffers(sh, (unsigned)C))) break;
   } while (0);
   if (rc) { kv_shard_destroy(sh); return rc; }
@@ -3814,12 +3795,12 @@ static int shard_late_report(kv_shard* sh, unsigned seen) {
 // The whole-op entry points (kv_shard_lookup / kv_shard_apply / kv_multi_shard_*) do the exchanges themselves, so they
 // leave this rank's own segments where they are: every kernel that reads a receive buffer downstream (the owner lookup's
 // tile pass, the finish, the owner apply's tile sums and k_papply) takes records [rank * (C + 1), +C + 1) from the send
-// buffer.  Only the entry-list kernels know how (other dims: the segment is copied like any peer's).
+// buffer.
 static bool shard_can_stay(const kv_shard* sh) {
-  return fused_ok(sh->table->dim) && (long long)sh->world * (sh->C + 1) <= FUSED_MAX_N;
+  return (long long)sh->world * (sh->C + 1) <= FUSED_MAX_N;
 }
 
-// ids -> local unique ids with counts -> the owners' segments of the send buffer.  4 launches, no host sync.
+// ids -> local unique ids with counts -> the owners' segments of the send buffer.  2 launches (deterministic mode: 6), no host sync.
 static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_stream_t stream) {
   if (!sh || (n > 0 && !ids) || n < 0 || n > sh->max_ids) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_route: n %lld (max %lld)", (long long)n, sh ? sh->max_ids : 0ll);
   DeviceGuard dg(sh->table->device);
@@ -3838,12 +3819,10 @@ static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_strea
   }
   if ((rc = ensure_workspace(rt, n, true, s))) return rc;
   WsDev wd = ws_view(rt, n);
-  // The route's index on the entry-list kernels (dims they do not serve: the sorted-position kernels):
+  // The route's index on the entry-list kernels:
   // a table-less tile pass (k_ltile<NOTABLE>: entries, mrow, every position's entry number) and k_papply in PA_UNIQUE
   // mode (the distinct ids numbered, uniq / ucnt written, every entry learns its id's number).  The finish then reads
   // position -> entry -> number -> record, the gradient pre-sum is k_tsum + k_papply PA_DEDUP.
-  const bool fused_route = fused_ok(rt->dim);
-  sh->route_fused = fused_route;
   PartArgs pa{};
   pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
   pa.out_keys = sh->uniq;
@@ -3851,62 +3830,37 @@ static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_strea
   pa.sparse_unique = 1;   // unique numbers with gaps: no counter to serialise on
   pa.det = sh->table->deterministic ? 1 : 0;
   pa.n = n;
-  if (fused_route) {
-    Workspace& ws = rt->ws;
-    if (ws.pos_cap < n) {
-      HIP_TRY(hipStreamSynchronize(s));
-      ws.pos_cap = 0;
-      if ((rc = regrow(&ws.pos_ent, (size_t)std::max<long long>(n, ws.cap_n)))) return rc;
-      ws.pos_cap = std::max<long long>(n, ws.cap_n);
-    }
-    rt->fused_index = true;
-    choose_partitions(rt, wd, n);   // (the distinct-id hint of the previous route of this length: k_papply publishes it)
-    WsDev wz = wd;
-    wz.zero_counts = sh->ucnt;
-    wz.pos_ent = ws.pos_ent;
-    launch_ltile_notable(rt, pa.tv, wz, ids, n, s);
-    pa.day_lk = pa.day;
-    if (!pa.det) {   // the numbered ids go straight to their owners' segments (the deterministic mode keeps the ordered scatter below)
-      pa.route_world = sh->world; pa.route_rule = sh->rule; pa.route_C = sh->C;
-      pa.route_seg = sh->send_pairs; pa.route_slot_of = sh->slot_of; pa.route_overflow = sh->overflow; pa.route_gcount = sh->gcount;
-      pa.route_need = sh->need; pa.route_uhint = sh->overflow + 1;   // (the launch's last block writes the headers: no k_seg_headers_take)
-    }
-    if ((rc = kvp_launch_papply_ud(&wd, &pa, PA_UNIQUE, (void*)s))) return fail(rc, "route: no kernel for dim %d", rt->dim);
-  } else {
-    {
-      // a skewed batch (the previous one of this length held at most n / 8 distinct ids; pinned word, no
-      // synchronisation): half the partitions, as in the unsharded index pass (fused_index_pass)
-      const unsigned u_prev = reinterpret_cast<volatile unsigned*>(sh->overflow)[1];
-      const bool few = !rt->deterministic && rt->batch_n_prev == n && u_prev > 0u && (long long)u_prev * 8 <= n && n >= (1ll << 18);
-      rt->batch_n_prev = n;
-      if (few) { wd.P = std::max(64u, wd.P / 2u); wd.pshift = 64 - ilog2(wd.P); }
-      rt->index_P = wd.P;
-    }
-    rt->fused_index = false;
-    // tile + partition passes only: kv_shard_lookup_finish's gather files the positions (order, work items) on its way
-    WsDev wz = wd;
-    wz.zero_counts = sh->ucnt;   // sparse unique numbers: the tile pass clears the counts, the partition pass sets the real ones
-    launch_tile<false>(rt, wz, ids, nullptr, n, s, 0);
-    launch_part_keys<MODE_UNIQUE>(wd, pa, s);
+  Workspace& ws = rt->ws;
+  if (ws.pos_cap < n) {
+    HIP_TRY(hipStreamSynchronize(s));
+    ws.pos_cap = 0;
+    if ((rc = regrow(&ws.pos_ent, (size_t)std::max<long long>(n, ws.cap_n)))) return rc;
+    ws.pos_cap = std::max<long long>(n, ws.cap_n);
   }
+  rt->fused_index = true;
+  choose_partitions(rt, wd, n);   // (the distinct-id hint of the previous route of this length: k_papply publishes it)
+  WsDev wz = wd;
+  wz.zero_counts = sh->ucnt;
+  wz.pos_ent = ws.pos_ent;
+  launch_ltile_notable(rt, pa.tv, wz, ids, n, s);
+  pa.day_lk = pa.day;
+  if (!pa.det) {   // the numbered ids go straight to their owners' segments (the deterministic mode keeps the ordered scatter below)
+    pa.route_world = sh->world; pa.route_rule = sh->rule; pa.route_C = sh->C;
+    pa.route_seg = sh->send_pairs; pa.route_slot_of = sh->slot_of; pa.route_overflow = sh->overflow; pa.route_gcount = sh->gcount;
+    pa.route_need = sh->need; pa.route_uhint = sh->overflow + 1;   // (the launch's last block writes the headers)
+  }
+  if ((rc = kvp_launch_papply_ud(&wd, &pa, PA_UNIQUE, (void*)s))) return fail(rc, "route: no kernel for dim %d", rt->dim);
   rt->batch_serial = ++g_serial;
   rt->batch_n = n;
   sh->route_token = rt->batch_serial;
-  sh->ordered = false;
-  const unsigned ntr = (unsigned)((n + RT - 1) / RT);
-  if (!pa.det) {
-    if (!fused_route)
-      k_owner_route_fixed<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, (long long)n, sh->world, sh->rule, sh->C, sh->send_pairs, sh->slot_of,
-                                             sh->overflow, sh->gcount);
-    if (!fused_route) k_seg_headers_take<<<1, MAXW, 0, s>>>(sh->gcount, sh->world, sh->C, sh->send_pairs, sh->need, sh->overflow + 1);
-    HIP_TRY(hipGetLastError());
-    return KV_OK;
+  if (pa.det) {   // the ordered owner scatter
+    const unsigned ntr = (unsigned)((n + RT - 1) / RT);
+    k_owner_hist_u32<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, (long long)n, sh->world, sh->rule, ntr, sh->hist);
+    k_owner_scan<<<1, 1024, 0, s>>>(sh->hist, ntr * sh->world, ntr, sh->world, sh->counts);
+    k_seg_headers<<<1, MAXW, 0, s>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
+    k_owner_scatter_fixed<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, (long long)n, sh->world, sh->rule, ntr, sh->hist, sh->C, sh->send_pairs,
+                                             sh->slot_of, sh->overflow);
   }
-  k_owner_hist_u32<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, (long long)n, sh->world, sh->rule, ntr, sh->hist);
-  k_owner_scan<<<1, 1024, 0, s>>>(sh->hist, ntr * sh->world, ntr, sh->world, sh->counts);
-  k_seg_headers<<<1, MAXW, 0, s>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
-  k_owner_scatter_fixed<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, (long long)n, sh->world, sh->rule, ntr, sh->hist, sh->C, sh->send_pairs,
-                                           sh->slot_of, sh->overflow);
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -3938,31 +3892,18 @@ int kv_shard_lookup_finish(kv_shard_t sh, float* out, kv_stream_t stream) {
   std::lock_guard<std::mutex> l(rt->mu);
   if (rt->batch_serial != sh->route_token || sh->route_token == 0) return fail(KV_FAILED_PRECONDITION, "kv_shard_lookup_finish without kv_shard_lookup_route");
   { int rc; if ((rc = hand_over(rt, (hipStream_t)stream))) return rc; }
-  // the training lookup's gather (k_gather<ORDER>) over the rows that came back: position -> entry -> dense unique
-  // index -> the record its id was sent in; the same pass files the positions for the gradient sum to come
-  if (sh->route_fused) {
-    const int q = row_lanes(rt->dim);
-    const int grid = nblocks(sh->n_last, TB, 8192);
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned slo = (unsigned)sh->rank * (sh->C + 1), slen = sh->self_in_place ? sh->C + 1 : 0u;
+  // over the rows that came back: position -> entry -> dense unique index -> the record its id was sent in
+  const int q = row_lanes(rt->dim);
+  const int grid = nblocks(sh->n_last, TB, 8192);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned slo = (unsigned)sh->rank * (sh->C + 1), slen = sh->self_in_place ? sh->C + 1 : 0u;
 #define KV_SF(VQ) k_shard_finish<VQ><<<grid, TB, 0, st>>>(rt->ws.pos_ent, rt->ws.ent_b, sh->slot_of, sh->recv_rows, out, sh->n_last, rt->dim, \
-                                                          sh->send_rows, slo, slen)
-    switch (q) {
-      case 1: KV_SF(1); break;   case 2: KV_SF(2); break;   case 4: KV_SF(4); break;   case 8: KV_SF(8); break;
-      case 16: KV_SF(16); break; case 32: KV_SF(32); break; default: KV_SF(64); break;
-    }
-#undef KV_SF
-    HIP_TRY(hipGetLastError());
-    return KV_OK;
+                                                        sh->send_rows, slo, slen)
+  switch (q) {
+    case 1: KV_SF(1); break;   case 2: KV_SF(2); break;   case 4: KV_SF(4); break;   case 8: KV_SF(8); break;
+    case 16: KV_SF(16); break; case 32: KV_SF(32); break; default: KV_SF(64); break;
   }
-  WsDev wd = ws_view(rt, sh->n_last);
-  if (rt->index_P) { wd.P = rt->index_P; wd.pshift = 64 - ilog2(wd.P); }   // the route's partitioning
-  wd.row_map = sh->slot_of;
-  TableDev rows = dev_view(rt);
-  rows.c0.rows = sh->recv_rows;
-  rows.chunk_bits = 31;
-  launch_gather(rows, wd, out, sh->n_last, (hipStream_t)stream, nullptr, 0, true);
-  sh->ordered = true;
+#undef KV_SF
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -3983,36 +3924,21 @@ int kv_shard_apply_route(kv_shard_t sh, const float* grad, kv_stream_t stream) {
   if ((rc = ensure_workspace(rt, sh->n_last, true, s))) return rc;
   WsDev wd = ws_view(rt, sh->n_last);
   if (rt->index_P) { wd.P = rt->index_P; wd.pshift = 64 - ilog2(wd.P); }   // the route's partitioning
-  if (sh->route_fused) {
-    // the tile sums of the ids repeated inside their tile, then the per-id sums straight into the records the ids were
-    // sent in (k_papply PA_DEDUP over the route's entries)
-    PartArgs pa{};
-    pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
-    pa.grad = grad;
-    pa.out_sum = sh->send_rows;
-    pa.out_map = sh->slot_of;
-    pa.det = rt->deterministic ? 1 : 0;
-    pa.n = sh->n_last;
-    pa.epart = wd.epart;
-    pa.day_lk = pa.day;
-    if ((rc = kvp_launch_tsum(&pa.tv, &wd, grad, (void*)s, nullptr, 0))) return fail(rc, "tile sums: no kernel for dim %d", rt->dim);
-    if ((rc = kvp_launch_papply_ud(&wd, &pa, PA_DEDUP, (void*)s))) return fail(rc, "gradient pre-sum: no kernel for dim %d", rt->dim);
-    HIP_TRY(hipGetLastError());
-    return KV_OK;
-  }
-  if (!sh->ordered) {   // a gradient for a batch whose rows were never fetched (kv_shard_lookup_finish skipped)
-    launch_order(dev_view(rt), wd, sh->n_last, s);
-    sh->ordered = true;
-  }
+  // the tile sums of the ids repeated inside their tile, then the per-id sums straight into the records the ids were
+  // sent in (k_papply PA_DEDUP over the route's entries)
   PartArgs pa{};
   pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
   pa.grad = grad;
   pa.out_sum = sh->send_rows;
   pa.out_map = sh->slot_of;
-  pa.fold_op = KV_SCATTER_ADD;
   pa.det = rt->deterministic ? 1 : 0;
   pa.n = sh->n_last;
-  return launch_apply<MODE_DEDUP, OPT_ADAGRAD>(rt, wd, pa, sh->n_last, s);
+  pa.epart = wd.epart;
+  pa.day_lk = pa.day;
+  if ((rc = kvp_launch_tsum(&pa.tv, &wd, grad, (void*)s, nullptr, 0))) return fail(rc, "tile sums: no kernel for dim %d", rt->dim);
+  if ((rc = kvp_launch_papply_ud(&wd, &pa, PA_DEDUP, (void*)s))) return fail(rc, "gradient pre-sum: no kernel for dim %d", rt->dim);
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
 }
 
 // the owner's half: recv_rows holds the peers' summed gradients, record for record as the lookup served them; the
@@ -4305,10 +4231,10 @@ static int multi_shard_check(const kv_shard_t* shards, int ntab, kv_comm_t comm,
 
 // ---- several sharded tables, one launch per phase -----------------------------------------------------
 // The route-side phases of kv_multi_shard_* run on the shards' private route tables; a table takes part in the batched
-// launches when its route is the entry-list one (not the deterministic mode, a dim the kernels serve, a batch that is
-// not empty); the others go through the per-table functions as before.
+// launches when its route is the entry-list one without the ordered owner scatter (not the deterministic mode, a batch
+// that is not empty); the others go through the per-table functions as before.
 static bool shard_batchable(const kv_shard* sh, int64_t n) {
-  return fused_ok(sh->table->dim) && !sh->table->deterministic && n > 0 && n <= sh->max_ids;
+  return !sh->table->deterministic && n > 0 && n <= sh->max_ids;
 }
 
 // route of the tables todo[0..m): the table-less tile pass of all of them (grid.y = table), then k_papply_multi in
@@ -4326,7 +4252,6 @@ static int multi_route_impl(const kv_shard_t* shards, const int* todo, int m, co
     rt->deterministic = false;
     sh->n_last = n[todo[j]];
     sh->route_token = 0;
-    sh->route_fused = true;
     if ((rc = ensure_workspace(rt, sh->n_last, true, s))) return rc;
     Workspace& ws = rt->ws;
     if (ws.pos_cap < sh->n_last) {
@@ -4381,7 +4306,6 @@ static int multi_route_impl(const kv_shard_t* shards, const int* todo, int m, co
     rt->batch_serial = ++g_serial;
     rt->batch_n = sh->n_last;
     sh->route_token = rt->batch_serial;
-    sh->ordered = false;
   }
   HIP_TRY(hipGetLastError());
   return KV_OK;
@@ -4561,7 +4485,7 @@ int kv_multi_shard_lookup(const kv_shard_t* shards, int ntab, kv_comm_t comm, co
     std::vector<int> dims;
     auto can = [&](int k) {
       const kv_shard* sh = shards[k];
-      return fused_ok(sh->table->dim) && sh->table->key_dtype == KV_DT_INT64 && (long long)sh->world * (sh->C + 1) <= (1ll << 21);
+      return sh->table->key_dtype == KV_DT_INT64 && (long long)sh->world * (sh->C + 1) <= (1ll << 21);
     };
     for (int k = 0; k < ntab; ++k)
         if (can(k)) dims.push_back(shards[k]->table->dim);
@@ -4599,12 +4523,12 @@ int kv_multi_shard_lookup(const kv_shard_t* shards, int ntab, kv_comm_t comm, co
   }
   if ((rc = comm_exchange(comm, ntab, sr.data(), rr.data(), rb.data(), w, stay.data()))) return rc;
   {
-    // finish: the tables of one row geometry whose route is an entry-list index in one launch
+    // finish: the tables of one row geometry in one launch
     std::vector<char> done(ntab, 0);
     for (int q : {1, 2, 4, 8, 16, 32, 64}) {
         std::vector<int> grp;
         for (int k = 0; k < ntab; ++k)
-          if (routed[k] && shards[k]->n_last > 0 && shards[k]->route_fused && row_lanes(shards[k]->table->dim) == q) grp.push_back(k);
+          if (routed[k] && shards[k]->n_last > 0 && row_lanes(shards[k]->table->dim) == q) grp.push_back(k);
         if (grp.size() < 2) continue;
         if (!note(multi_finish_impl(shards, grp.data(), (int)grp.size(), outs, w)))
           for (int k : grp) done[k] = 1;
@@ -4637,16 +4561,16 @@ int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int
   std::vector<char> stay(ntab, 0);
   std::vector<char> summed(ntab, 0);
   {
-    // gradient pre-sum: the tables of one dim whose route is an entry-list index in two launches
+    // gradient pre-sum: the tables of one dim whose route has no ordered owner scatter in two launches
     std::vector<int> dims;
     for (int k = 0; k < ntab; ++k)
-      if (shards[k]->n_last > 0 && shards[k]->route_fused && !shards[k]->table->deterministic) dims.push_back(shards[k]->table->dim);
+      if (shards[k]->n_last > 0 && !shards[k]->table->deterministic) dims.push_back(shards[k]->table->dim);
     std::sort(dims.begin(), dims.end());
     dims.erase(std::unique(dims.begin(), dims.end()), dims.end());
     for (int D : dims) {
       std::vector<int> grp;
       for (int k = 0; k < ntab; ++k)
-        if (shards[k]->n_last > 0 && shards[k]->route_fused && !shards[k]->table->deterministic && shards[k]->table->dim == D) grp.push_back(k);
+        if (shards[k]->n_last > 0 && !shards[k]->table->deterministic && shards[k]->table->dim == D) grp.push_back(k);
       if (grp.size() < 2) continue;
       if (!note(multi_presum_impl(shards, grp.data(), (int)grp.size(), grads, w)))
         for (int k : grp) summed[k] = 1;
@@ -4670,9 +4594,8 @@ int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int
     std::vector<int> dims;
     auto can = [&](int k) {
       const kv_shard* sh = shards[k];
-      return fused_ok(sh->table->dim) && sh->table->key_dtype == KV_DT_INT64 &&
-             (long long)sh->world * (sh->C + 1) <= (1ll << 21) && sh->serve_token != 0 && sh->serve_token == sh->table->batch_serial &&
-             sh->table->fused_index && slot0[k] != nullptr && (optimizer != 3 || (slot1 && slot1[k]));
+      return sh->table->key_dtype == KV_DT_INT64 && (long long)sh->world * (sh->C + 1) <= (1ll << 21) && sh->serve_token != 0 &&
+             sh->serve_token == sh->table->batch_serial && sh->table->fused_index && slot0[k] != nullptr && (optimizer != 3 || (slot1 && slot1[k]));
     };
     if (optimizer >= 0 && optimizer <= 3)
       for (int k = 0; k < ntab; ++k)

@@ -793,11 +793,14 @@ OPT_GROUP_ADAM_V4, OPT_GROUP_ADAM_V3, OPT_ADAGRAD, OPT_SPARSE_GROUP_FTRL = 0, 1,
 class KvComm(object):
   """RCCL communicator of the library (grouped ncclSend / ncclRecv on its own stream)."""
 
-  def __init__(self, world, rank, id128=None, device=0):
+  def __init__(self, world, rank, id128=None, device=0, self_via_rccl=False):
+    """self_via_rccl: this rank's own segment goes through ncclSend / ncclRecv too (kvhip.h kv_comm_set_self_via_rccl)."""
     self.ptr = ctypes.c_void_p()
     buf = None if id128 is None else ctypes.create_string_buffer(bytes(id128), 128)
     _lib.check(_lib.lib().kv_comm_create(int(world), int(rank), buf, int(device), ctypes.byref(self.ptr)))
     self.world, self.rank = world, rank
+    if self_via_rccl:
+      _lib.check(_lib.lib().kv_comm_set_self_via_rccl(self.ptr, 1))
 
   def stream(self):
     """The communicator's stream as a torch stream: work queued there reaches the sharded ops without an event hop."""
