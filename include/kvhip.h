@@ -406,6 +406,58 @@ int kv_multi_apply_sparse_group_ftrl_unique(int num_tables, const kv_handle_t* v
                                             const void* const* ids, const int64_t* ns, float lr, float l1, float l2,
                                             float l21, float l2_shrinkage, float lr_power, kv_stream_t stream);
 
+/* Per-coordinate FTRL-Proximal.  Replaces KvVariableSparseApplyFtrlOp<..., has_l2_shrinkage = true>::Compute
+ * (kernels/training_ops.cc:281-526; op KvVariableSparseApplyFtrlV2, ops/training_ops.cc:103-117).  Same tables as
+ * kv_apply_sparse_group_ftrl (accum and linear: dim-wide slot tables) and its argument order without l21.  The reference
+ * applies no CoverUpdate and no blacklist here: the var's flags are left to a later lookup (as kv_apply_adagrad).
+ * KV_INVALID_ARGUMENT for lr <= 0, l1 / l2 / l2_shrinkage < 0, lr_power > 0 or dims that differ; KV_FAILED_PRECONDITION
+ * for an uninitialised table.  _unique / _tok: the forms of kv_apply_sparse_group_ftrl_unique / _tok above. */
+int kv_apply_ftrl_v2(kv_handle_t var, kv_handle_t accum, kv_handle_t linear, const float* grad, const void* ids,
+                     int64_t n, float lr, float l1, float l2, float l2_shrinkage, float lr_power, kv_stream_t stream);
+int kv_apply_ftrl_v2_unique(kv_handle_t var, kv_handle_t accum, kv_handle_t linear, const float* grad, const void* ids,
+                            int64_t n, float lr, float l1, float l2, float l2_shrinkage, float lr_power, kv_stream_t stream);
+int kv_apply_ftrl_v2_tok(kv_handle_t var, kv_handle_t accum, kv_handle_t linear, const float* grad, const void* ids,
+                         int64_t n, float lr, float l1, float l2, float l2_shrinkage, float lr_power, kv_batch_token_t token,
+                         kv_stream_t stream);
+/* Group FTRL-V2.  Replaces KvVariableGroupSparseApplyFtrlOp<..., has_l2_shrinkage = true>::Compute
+ * (kernels/training_ops.cc:805-1059; op KvVariableGroupSparseApplyFtrlV2, ops/training_ops.cc:119-133): the FTRL linear
+ * update, then a group-lasso threshold l1 on the L2 norm of the whole linear row — the var is
+ * (l1 - norm) / ((sqrt(new_accum) / lr + 2 l2) norm) * linear (CoverUpdate), or blacklisted when norm <= l1.  Arguments,
+ * checks and forms as kv_apply_ftrl_v2. */
+int kv_apply_group_ftrl_v2(kv_handle_t var, kv_handle_t accum, kv_handle_t linear, const float* grad, const void* ids,
+                           int64_t n, float lr, float l1, float l2, float l2_shrinkage, float lr_power, kv_stream_t stream);
+int kv_apply_group_ftrl_v2_unique(kv_handle_t var, kv_handle_t accum, kv_handle_t linear, const float* grad, const void* ids,
+                                  int64_t n, float lr, float l1, float l2, float l2_shrinkage, float lr_power,
+                                  kv_stream_t stream);
+int kv_apply_group_ftrl_v2_tok(kv_handle_t var, kv_handle_t accum, kv_handle_t linear, const float* grad, const void* ids,
+                               int64_t n, float lr, float l1, float l2, float l2_shrinkage, float lr_power,
+                               kv_batch_token_t token, kv_stream_t stream);
+/* The two on many (var, accum, linear) triples of one dim, shaped like kv_multi_apply_sparse_group_ftrl[_tok|_unique]
+ * (occurrence-order tables are refused as there). */
+int kv_multi_apply_ftrl_v2(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, const kv_handle_t* linears,
+                           const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float l1, float l2,
+                           float l2_shrinkage, float lr_power, kv_stream_t stream);
+int kv_multi_apply_ftrl_v2_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, const kv_handle_t* linears,
+                               const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float l1,
+                               float l2, float l2_shrinkage, float lr_power, const kv_batch_token_t* tokens,
+                               kv_stream_t stream);
+int kv_multi_apply_ftrl_v2_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
+                                  const kv_handle_t* linears, const float* const* grads, const void* const* ids,
+                                  const int64_t* ns, float lr, float l1, float l2, float l2_shrinkage, float lr_power,
+                                  kv_stream_t stream);
+int kv_multi_apply_group_ftrl_v2(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
+                                 const kv_handle_t* linears, const float* const* grads, const void* const* ids,
+                                 const int64_t* ns, float lr, float l1, float l2, float l2_shrinkage, float lr_power,
+                                 kv_stream_t stream);
+int kv_multi_apply_group_ftrl_v2_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
+                                     const kv_handle_t* linears, const float* const* grads, const void* const* ids,
+                                     const int64_t* ns, float lr, float l1, float l2, float l2_shrinkage, float lr_power,
+                                     const kv_batch_token_t* tokens, kv_stream_t stream);
+int kv_multi_apply_group_ftrl_v2_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
+                                        const kv_handle_t* linears, const float* const* grads, const void* const* ids,
+                                        const int64_t* ns, float lr, float l1, float l2, float l2_shrinkage,
+                                        float lr_power, kv_stream_t stream);
+
 
 /* embedding_lookup_sparse on a KvVariable (python/ops/embedding_ops.py:279-441), fused: the
  * reference runs unique_with_counts -> GatherOrInsert[WithCounts] -> gather(idx) -> (x weights) ->
@@ -519,7 +571,8 @@ int kv_shard_lookup_serve(kv_shard_t shard, kv_stream_t stream);
 int kv_shard_lookup_finish(kv_shard_t shard, float* out, kv_stream_t stream);
 int kv_shard_apply_route(kv_shard_t shard, const float* grad, kv_stream_t stream);
 /* optimizer: 0 GroupAdam V4, 1 GroupAdam V3 (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21),
- * 2 Adagrad (hp = lr, update_slots), 3 SparseGroupFtrl (hp = lr, l1, l2, l21, l2_shrinkage, lr_power; slot1 = linear) */
+ * 2 Adagrad (hp = lr, update_slots), 3 SparseGroupFtrl (hp = lr, l1, l2, l21, l2_shrinkage, lr_power; slot1 = linear),
+ * 4 FTRL-V2, 5 group FTRL-V2 (hp = lr, l1, l2, l2_shrinkage, lr_power; slot1 = linear) */
 int kv_shard_apply_serve(kv_shard_t shard, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp,
                          kv_stream_t stream);
 int kv_shard_lookup(kv_shard_t shard, kv_comm_t comm, const void* ids, int64_t n, float* out, int join,

@@ -117,6 +117,18 @@ SIGNATURES = {
     "kv_multi_apply_group_adam_tok": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 9 + [_i32, _vp, _vp]),
     "kv_multi_apply_adagrad_tok": (_i32, [_i32, _vp, _vp, _c.c_float, _vp, _vp, _vp, _i32, _vp, _vp]),
     "kv_multi_apply_sparse_group_ftrl_tok": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 6 + [_vp, _vp]),
+    "kv_apply_ftrl_v2": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 5 + [_vp]),
+    "kv_apply_ftrl_v2_unique": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 5 + [_vp]),
+    "kv_apply_ftrl_v2_tok": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 5 + [_c.c_uint64, _vp]),
+    "kv_apply_group_ftrl_v2": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 5 + [_vp]),
+    "kv_apply_group_ftrl_v2_unique": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 5 + [_vp]),
+    "kv_apply_group_ftrl_v2_tok": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 5 + [_c.c_uint64, _vp]),
+    "kv_multi_apply_ftrl_v2": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp]),
+    "kv_multi_apply_ftrl_v2_unique": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp]),
+    "kv_multi_apply_ftrl_v2_tok": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp, _vp]),
+    "kv_multi_apply_group_ftrl_v2": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp]),
+    "kv_multi_apply_group_ftrl_v2_unique": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp]),
+    "kv_multi_apply_group_ftrl_v2_tok": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp, _vp]),
     "kv_lookup_sparse": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "kv_unsorted_segment_sum": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "kv_take_rows": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
@@ -160,7 +172,7 @@ def build(force=False):
   stale = (not os.path.exists(SO_PATH)
            or os.path.getmtime(SO_PATH) < max(os.path.getmtime(f) for f in srcs))
   if force or stale:
-    subprocess.check_call(["make", "-C", CSRC, "-s", "-j6"] + (["-B"] if force else []))
+    subprocess.check_call(["make", "-C", CSRC, "-s", "-j8"] + (["-B"] if force else []))
   return SO_PATH
 
 

@@ -44,7 +44,17 @@ constexpr int MAX_CHUNKS = 32768;   // 2^16-row chunks (no capacity hint) still 
 // index-pass modes (k_part_keys) and fold modes (k_apply_sorted)
 enum Mode { MODE_LOOKUP = 0, MODE_APPLY = 1, MODE_DEDUP = 2, MODE_SCATTER = 3, MODE_MARK = 4, MODE_UNIQUE = 5,
             MODE_APPLYIDX = 6 };
-enum Opt { OPT_ADAM_V4 = 0, OPT_ADAM_V3 = 1, OPT_ADAGRAD = 2, OPT_FTRL = 3 };
+enum Opt { OPT_ADAM_V4 = 0, OPT_ADAM_V3 = 1, OPT_ADAGRAD = 2, OPT_FTRL = 3, OPT_FTRL_V2 = 4, OPT_GROUP_FTRL_V2 = 5 };
+// What the pipelines ask of an optimizer, in one place (a new OPT_* must answer each of them):
+// GroupAdam: one slot table of three dim-wide blocks (m | v | z)
+constexpr bool group_adam(int opt) { return opt == OPT_ADAM_V4 || opt == OPT_ADAM_V3; }
+// a second slot table (accum + linear): rows probed and inserted in ts1, no slot-mirror lean path (the mirror stands for
+// ONE slot record)
+constexpr bool two_slots(int opt) { return opt == OPT_FTRL || opt == OPT_FTRL_V2 || opt == OPT_GROUP_FTRL_V2; }
+// no CoverUpdate of the var: its flags are read (blacklist lifted by RemoveBlacklistUnsafe) and left to a later lookup
+constexpr bool keeps_var_flags(int opt) { return opt == OPT_ADAGRAD || opt == OPT_FTRL_V2; }
+// dim-wide blocks of the first slot row
+constexpr int slot0_blocks(int opt) { return group_adam(opt) ? 3 : 1; }
 
 struct __attribute__((aligned(16))) Entry {
   long long key;
@@ -556,13 +566,17 @@ struct PreRows {
 // sin[0..2] = GroupAdam m | v | z, Adagrad accum, FTRL accum | linear.  Element e of a row lives at lane
 // (e / V) % LPR, step (e / V) / LPR.  All LPR lanes of every group of the wave call it (shuffles inside); `act`
 // masks groups without an update.  fvp / f0p / f1p = the flag bytes of the var / first / second slot row.
+// new1 = the second slot row was inserted now (its flags come from its values).
 // Restates the per-id body of KvVariableGroupSparseApplyAdamV4Op / V3Op / SparseApplyAdagradOp /
-// SparseGroupSparseApplyFtrlOp (training_ops.cc:7142-7197, 5871-5927, 1455-1486, 684-763).
+// SparseGroupSparseApplyFtrlOp / SparseApplyFtrlOp / GroupSparseApplyFtrlOp (training_ops.cc:7142-7197, 5871-5927,
+// 1455-1486, 684-763, 457-484, 977-1019).
 template <int OPT, int V, int LPR, int K>
 __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row, unsigned char* fvp, unsigned char* f0p,
                                          unsigned char* f1p, bool act, bool new0, int D, const float (&gv)[K][V],
-                                         const OptArgs& a, int lane, const float (&xin)[K][V], const float (&sin)[3][K][V]) {
-  if (OPT == OPT_ADAM_V4 || OPT == OPT_ADAM_V3) {
+                                         const OptArgs& a, int lane, const float (&xin)[K][V], const float (&sin)[3][K][V],
+                                         bool new1 = false) {
+  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_GROUP_FTRL_V2, "opt_core: unknown optimizer");
+  if (group_adam(OPT)) {
     // training_ops.cc:7166-7195 (V4) / :5895-5925 (V3); slot row = [m | v | z]
     float m[K][V], nv[K][V], sq[K][V], z[K][V], uu[K][V];
     float part = 0.f;
@@ -657,7 +671,7 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
       if (new0) *f0p = (unsigned char)((anys ? 0u : FLAG_UNDER) | (a.update_slots ? FLAG_DIRTY : 0u));
       else if (a.update_slots) *f0p |= (unsigned char)FLAG_DIRTY;
     }
-  } else {
+  } else if (OPT == OPT_FTRL) {
     // OPT_FTRL: training_ops.cc:713-751 with has_l2_shrinkage; slot 0 = accum, slot 1 = linear
     float x[K][V], ac[K][V], z[K][V], uu[K][V];
     float part = 0.f;
@@ -723,6 +737,113 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
       *f0p = (unsigned char)(anya ? 0u : FLAG_UNDER);
       *f1p = (unsigned char)(anyz ? 0u : FLAG_UNDER);
     }
+  } else if (OPT == OPT_FTRL_V2) {
+    // KvVariableSparseApplyFtrlV2, training_ops.cc:457-484 with has_l2_shrinkage; slot 0 = accum, slot 1 = linear.
+    // Element-wise FTRL-Proximal: no norm, no CoverUpdate and no blacklist (flags as the Adagrad branch treats them)
+    const bool half = a.lr_power == -0.5f;
+    const float two_l2s = 2.f * a.l2s, two_l2 = 2.f * a.l2;
+    const bool fm = KV_FASTM(a);
+    bool abig = false, zbig = false;   // the slot rows' values before the update: what a new row's flags come from
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      if (act && e0 < D) {
+        float xn[V], an[V], zn[V];
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+          const float xo = xin[k][c], ao = sin[0][k][c], zo = sin[1][k][c];
+          abig |= fabsf(ao) >= CUTOFF;
+          zbig |= fabsf(zo) >= CUTOFF;
+          const float gs = gv[k][c] + two_l2s * xo;
+          const float na = ao + gs * gs;
+          const float pn = half ? kv_sqrt(na, fm) : powf(na, -a.lr_power);
+          const float po = half ? kv_sqrt(ao, fm) : powf(ao, -a.lr_power);
+          zn[c] = zo + (gs - kv_div(pn - po, a.lr, fm) * xo);
+          const float adj = fmaxf(fminf(zn[c], a.l1), -a.l1);
+          xn[c] = kv_div(adj - zn[c], kv_div(pn, a.lr, fm) + two_l2, fm);
+          // accum += grad_to_use.square() re-evaluates the lazy expression with the updated var (:484)
+          const float gs2 = gv[k][c] + two_l2s * xn[c];
+          an[c] = ao + gs2 * gs2;
+        }
+        stv<V>(xrow + e0, xn);
+        stv<V>(s0row + e0, an);
+        stv<V>(s1row + e0, zn);
+      }
+    }
+    const bool anya = group_any<LPR>(abig), anyz = group_any<LPR>(zbig);
+    if (act && lane == 0) {
+      // the reference does not refresh under_threshold here; a later lookup does (FLAG_DIRTY)
+      *fvp |= (unsigned char)FLAG_DIRTY;
+      if (new0) *f0p = (unsigned char)((anya ? 0u : FLAG_UNDER) | FLAG_DIRTY);
+      else *f0p |= (unsigned char)FLAG_DIRTY;
+      if (new1) *f1p = (unsigned char)((anyz ? 0u : FLAG_UNDER) | FLAG_DIRTY);
+      else *f1p |= (unsigned char)FLAG_DIRTY;
+    }
+  } else {
+    // OPT_GROUP_FTRL_V2: KvVariableGroupSparseApplyFtrlV2, training_ops.cc:977-1019 with has_l2_shrinkage; slot 0 = accum,
+    // slot 1 = linear.  Group lasso with threshold l1 on the whole updated linear row
+    float z[K][V];
+    float part = 0.f;
+    const bool half = a.lr_power == -0.5f;
+    const float two_l2s = 2.f * a.l2s, two_l2 = 2.f * a.l2;
+    const bool fm = KV_FASTM(a);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      const bool valid = act && e0 < D;
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        const float xo = valid ? xin[k][c] : 0.f, ao = valid ? sin[0][k][c] : 0.f, zo = valid ? sin[1][k][c] : 0.f;
+        const float gs = gv[k][c] + two_l2s * xo;
+        const float na = ao + gs * gs;
+        const float pn = half ? kv_sqrt(na, fm) : powf(na, -a.lr_power);
+        const float po = half ? kv_sqrt(ao, fm) : powf(ao, -a.lr_power);
+        z[k][c] = zo + (gs - kv_div(pn - po, a.lr, fm) * xo);
+        if (valid) part += z[k][c] * z[k][c];
+      }
+    }
+    const float norm = kv_sqrt(group_sum<LPR>(part), fm);   // linear.square().sum().sqrt() (:994)
+    const bool upd = norm > a.l1;
+    const float l1mn = a.l1 - norm;
+    bool big = false, abig = false, zbig = false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      if (act && e0 < D) {
+        float xn[V], an[V];
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+          const float xo = xin[k][c], ao = sin[0][k][c];
+          xn[c] = 0.f;   // blacklist: the row reads as zeros (table_manager.h:335-357)
+          if (upd) {
+            const float gs = gv[k][c] + two_l2s * xo;
+            const float na = ao + gs * gs;
+            const float pn = half ? kv_sqrt(na, fm) : powf(na, -a.lr_power);
+            const float coef = kv_div(l1mn, (kv_div(pn, a.lr, fm) + two_l2) * norm, fm);
+            xn[c] = coef * z[k][c];
+          }
+          // accum += grad_to_use.square(), TWICE (:1015-1016), each re-evaluating the lazy expression with the updated
+          // var; on the blacklist branch we keep the pre-blacklist value like the SparseGroupFtrl branch above
+          const float xa = upd ? xn[c] : xo;
+          const float gs2 = gv[k][c] + two_l2s * xa;
+          const float g2 = gs2 * gs2;
+          an[c] = (ao + g2) + g2;
+          big |= fabsf(xn[c]) >= CUTOFF;
+          abig |= fabsf(an[c]) >= CUTOFF;
+          zbig |= fabsf(z[k][c]) >= CUTOFF;
+        }
+        stv<V>(xrow + e0, xn);
+        stv<V>(s0row + e0, an);
+        stv<V>(s1row + e0, z[k]);
+      }
+    }
+    const bool anyx = group_any<LPR>(big), anya = group_any<LPR>(abig), anyz = group_any<LPR>(zbig);
+    if (act && lane == 0) {
+      // CoverUpdateUnsafe or MarkBlacklistUnsafe on the var; CoverUpdateUnsafe on linear and accum (:1003-1021)
+      *fvp = (unsigned char)(upd ? (anyx ? 0u : FLAG_UNDER) : (FLAG_BLACK | FLAG_UNDER));
+      *f0p = (unsigned char)(anya ? 0u : FLAG_UNDER);
+      *f1p = (unsigned char)(anyz ? 0u : FLAG_UNDER);
+    }
   }
 }
 
@@ -738,11 +859,11 @@ __device__ __forceinline__ void opt_update_row(const TableDev& tv, const TableDe
   const int D = tv.dim;
   const bool skip = !live || (tag & ROW_FILTERED) || (tag & ROW_MASK) == 0u;  // training_ops.cc:7150-7152
   const unsigned rv = tag & ROW_MASK;
-  const bool act = !skip && r0 != 0 && (OPT != OPT_FTRL || r1 != 0);
+  const bool act = !skip && r0 != 0 && (!two_slots(OPT) || r1 != 0);
 
   float* xrow = row_ptr(tv, act ? rv : 0u);
   float* s0row = row_ptr(ts0, act ? r0 : 0u);
-  float* s1row = (OPT == OPT_FTRL) ? row_ptr(ts1, act ? r1 : 0u) : nullptr;
+  float* s1row = two_slots(OPT) ? row_ptr(ts1, act ? r1 : 0u) : nullptr;
 
   // new slot rows are initialised in registers with the slot table's init rule
   const float *ia0 = nullptr, *ib0 = nullptr, *ia1 = nullptr, *ib1 = nullptr;
@@ -751,7 +872,7 @@ __device__ __forceinline__ void opt_update_row(const TableDev& tv, const TableDe
     ia0 = ts0.init_table + (size_t)((unsigned)h % ts0.init_rows) * ts0.dim;
     ib0 = ts0.init_table + (size_t)((unsigned)(h >> 32) % ts0.init_rows) * ts0.dim;
   }
-  if (OPT == OPT_FTRL && act && new1) {
+  if (two_slots(OPT) && act && new1) {
     unsigned long long h = pick64((unsigned long long)key ^ (ts1.seed * 0x9E3779B97F4A7C15ULL));
     ia1 = ts1.init_table + (size_t)((unsigned)h % ts1.init_rows) * ts1.dim;
     ib1 = ts1.init_table + (size_t)((unsigned)(h >> 32) % ts1.init_rows) * ts1.dim;
@@ -770,20 +891,20 @@ __device__ __forceinline__ void opt_update_row(const TableDev& tv, const TableDe
       ldv<V>(xrow + e0, xin[k]);
     }
     if (pre && have_s && !new0) {
-      constexpr int NS0 = (OPT == OPT_ADAM_V4 || OPT == OPT_ADAM_V3) ? 3 : 1;
+      constexpr int NS0 = slot0_blocks(OPT);
 #pragma unroll
       for (int b3 = 0; b3 < NS0; ++b3)
 #pragma unroll
         for (int c = 0; c < V; ++c) sin[b3][k][c] = pre->s[b3][k][c];
     } else {
       ldslot<V>(s0row, ia0, ib0, new0, e0, sin[0][k]);
-      if (OPT == OPT_ADAM_V4 || OPT == OPT_ADAM_V3) {
+      if (group_adam(OPT)) {
         ldslot<V>(s0row, ia0, ib0, new0, e0 + D, sin[1][k]);
         ldslot<V>(s0row, ia0, ib0, new0, e0 + 2 * D, sin[2][k]);
       }
     }
-    if (OPT == OPT_FTRL) ldslot<V>(s1row, ia1, ib1, new1, e0, sin[1][k]);
+    if (two_slots(OPT)) ldslot<V>(s1row, ia1, ib1, new1, e0, sin[1][k]);
   }
   opt_core<OPT, V, LPR, K>(xrow, s0row, s1row, flags_ptr(tv, act ? rv : 0u), flags_ptr(ts0, act ? r0 : 0u),
-                           OPT == OPT_FTRL ? flags_ptr(ts1, act ? r1 : 0u) : nullptr, act, new0, D, gv, a, lane, xin, sin);
+                           two_slots(OPT) ? flags_ptr(ts1, act ? r1 : 0u) : nullptr, act, new0, D, gv, a, lane, xin, sin, new1);
 }

@@ -1214,7 +1214,7 @@ __device__ __forceinline__ RowsOf resolve_rows(const PartArgs& a, long long key,
   // the var record is only needed for the frequency filter: a blacklisted row is all zeros already
   // (RemoveBlacklistUnsafe hands out a zero row, table_manager.h:359-372) and the group optimizers
   // rewrite the flags after the update, so with enter_threshold == 0 they never read it
-  const bool need_vmeta = OPT == OPT_ADAGRAD || a.tv.enter_threshold != 0u;
+  const bool need_vmeta = keeps_var_flags(OPT) || a.tv.enter_threshold != 0u;
   if (need_vmeta && !vnew) {
     const uint2 mv = load_freq_flags(a.tv, rv);
     if ((mv.x & 0xFFFFu) < a.tv.enter_threshold) { o.tag = rv | ROW_FILTERED; return o; }  // kv_variable.h:910
@@ -1248,13 +1248,13 @@ __device__ __forceinline__ RowsOf resolve_rows(const PartArgs& a, long long key,
     return r;
   };
   bool new0 = false, new1 = false;
-  if (OPT == OPT_FTRL) o.r1 = slot_row(a.ts1, false, &new1);
+  if (two_slots(OPT)) o.r1 = slot_row(a.ts1, false, &new1);
   o.r0 = slot_row(a.ts0, a.use_hints != 0, &new0);
   // MarkAsDeltaListElements on every table of the op, for the keys the update reaches (training_ops.cc:7196-7201)
-  if (__builtin_expect(a.tv.track_delta | a.ts0.track_delta | (OPT == OPT_FTRL ? a.ts1.track_delta : 0u), 0)) {
+  if (__builtin_expect(a.tv.track_delta | a.ts0.track_delta | (two_slots(OPT) ? a.ts1.track_delta : 0u), 0)) {
     mark_delta(a.tv, rv);
     if (o.r0) mark_delta(a.ts0, o.r0);
-    if (OPT == OPT_FTRL && o.r1) mark_delta(a.ts1, o.r1);
+    if (two_slots(OPT) && o.r1) mark_delta(a.ts1, o.r1);
   }
   o.nb = (new0 ? 2u : 0u) | (new1 ? 4u : 0u) | (hinted ? 8u : 0u);
   return o;
@@ -1278,7 +1278,7 @@ __device__ __forceinline__ void prefetch_state(const PartArgs& a, const uint4& r
   }
   const float* xr = row_ptr(a.tv, ra.z & ROW_MASK);
   const float* sr = hok ? row_ptr(a.ts0, ra.w) : nullptr;
-  constexpr int NS0 = (OPT == OPT_ADAM_V4 || OPT == OPT_ADAM_V3) ? 3 : 1;
+  constexpr int NS0 = slot0_blocks(OPT);
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const int e0 = (lane + k * LPR) * V;
@@ -1314,7 +1314,7 @@ __device__ __forceinline__ void finish_key(const PartArgs& a, const uint4 hd, bo
                                    live, gv, a.opt, lane, pre, have_x, have_s && (ro.nb & 8u) != 0);
     // the key's slot record as this update left it goes into the var row's mirror (clean: the slot table's own record is
     // up to date), so that the key's NEXT apply takes the lean path without reading it
-    if (OPT != OPT_FTRL && a.use_mirror && live && lane == 0 && ro.r0 != 0u && (ro.tag & ROW_MASK) != 0u && !(ro.tag & ROW_FILTERED)) {
+    if (!two_slots(OPT) && a.use_mirror && live && lane == 0 && ro.r0 != 0u && (ro.tag & ROW_MASK) != 0u && !(ro.tag & ROW_FILTERED)) {
       const uint2 sm = load_freq_flags(a.ts0, ro.r0);
       SlotMirror nm;
       nm.srow = ro.r0; nm.freq = sm.x; nm.flags = (unsigned char)(sm.y & 0xFFu); nm.state = (unsigned char)MIRROR_CLEAN;

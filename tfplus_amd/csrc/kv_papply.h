@@ -327,16 +327,16 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
     for (int k = 0; k < K; ++k) { const int e0 = (lane + k * LPR) * V; evalid[k] = e0 < D; eoff[k] = evalid[k] ? e0 : 0; }
     // the lean update: single-chunk tables, hints, no delta lists — and the var rows carry mirrors of the slot records
     // (kv_device.h SlotMirror; the host's mirror_decide): any other launch or key goes through finish_key
-    const bool fast = (OPT != OPT_FTRL) && a.tv.single != 0u && a.ts0.single != 0u && a.use_hints != 0 &&
+    const bool fast = !two_slots(OPT) && a.tv.single != 0u && a.ts0.single != 0u && a.use_hints != 0 &&
                       (a.tv.track_delta | a.ts0.track_delta) == 0u && a.use_mirror != 0;
     float* const vrows = a.tv.c0.rows;
     RowMeta* const vmeta = a.tv.c0.meta;
     float* const srows = a.ts0.c0.rows;
     const int SD = a.ts0.dim;
     const unsigned smax = a.ts0.max_rows, thr = a.tv.enter_threshold;
-    const bool need_vmeta = OPT == OPT_ADAGRAD || thr != 0u;
+    const bool need_vmeta = keeps_var_flags(OPT) || thr != 0u;
     const unsigned mepoch = a.mirror_epoch & 0xFFFFu;
-    constexpr int NS0 = (OPT == OPT_ADAM_V4 || OPT == OPT_ADAM_V3) ? 3 : 1;
+    constexpr int NS0 = slot0_blocks(OPT);
 
     // ---- the apply: items = the round's hot keys (one per wave), then batches of G cold keys (one per lane group) -------
     const unsigned nbatch = (ncold + (unsigned)G - 1u) / (unsigned)G;

@@ -78,7 +78,7 @@ __device__ __forceinline__ unsigned uniq_insert(const TableDev& t, long long key
 template <int OPT, int V, int LPR, int K>
 __device__ __forceinline__ void uapply_body(const PartArgs& a, const void* __restrict__ ids, int ids32, long long n) {
   constexpr int G = 64 / LPR;
-  constexpr int NS0 = (OPT == OPT_ADAM_V4 || OPT == OPT_ADAM_V3) ? 3 : 1;
+  constexpr int NS0 = slot0_blocks(OPT);
   if (*reinterpret_cast<volatile unsigned*>(&a.tv.counters[1])) return;   // an earlier batch left the error flag up
   const int D = a.tv.dim;
   const int wl = threadIdx.x & 63, lane = wl % LPR, g = wl / LPR;
@@ -88,14 +88,14 @@ __device__ __forceinline__ void uapply_body(const PartArgs& a, const void* __res
   for (int k = 0; k < K; ++k) { const int e0 = (lane + k * LPR) * V; evalid[k] = e0 < D; eoff[k] = evalid[k] ? e0 : 0; }
   // the lean update: single-chunk tables, the var's index entries remember the slot rows, no delta lists (every pre-sized
   // training table); any other key or table goes through finish_key (kv_kernels.h)
-  const bool fast = (OPT != OPT_FTRL) && a.tv.single != 0u && a.ts0.single != 0u && a.use_hints != 0 &&
+  const bool fast = !two_slots(OPT) && a.tv.single != 0u && a.ts0.single != 0u && a.use_hints != 0 &&
                     (a.tv.track_delta | a.ts0.track_delta) == 0u && a.use_mirror != 0;   // ... and slot mirrors (kv_device.h)
   float* const vrows = a.tv.c0.rows;
   RowMeta* const vmeta = a.tv.c0.meta;
   float* const srows = a.ts0.c0.rows;
   const int SD = a.ts0.dim;
   const unsigned smax = a.ts0.max_rows, thr = a.tv.enter_threshold;
-  const bool need_vmeta = OPT == OPT_ADAGRAD || thr != 0u;
+  const bool need_vmeta = keeps_var_flags(OPT) || thr != 0u;
   const unsigned mepoch = a.mirror_epoch & 0xFFFFu;
   const unsigned serial = a.uniq_serial & 0xFFFFu;
   const float* const gbase = a.grad;

@@ -56,19 +56,25 @@ extern "C" int kvp_launch_apply_a(int mode, int opt, const void* wd, const void*
                                   unsigned nchunks, int span);
 extern "C" int kvp_launch_apply_b(int mode, int opt, const void* wd, const void* pa, void* stream, const void* md, int ntab,
                                   unsigned nchunks, int span);
+extern "C" int kvp_launch_apply_c(int mode, int opt, const void* wd, const void* pa, void* stream, const void* md, int ntab,
+                                  unsigned nchunks, int span);
 
 extern "C" int kvp_launch_tsum(const void* td, const void* wd, const float* grad, void* stream, const void* md, int ntab);
-// k_papply dispatch (kv_papply.h), two more translation units: a = GroupAdam V4 / V3, b = Adagrad / SparseGroupFtrl
+// k_papply dispatch (kv_papply.h), three more translation units: a = GroupAdam V4 / V3, b = Adagrad / SparseGroupFtrl,
+// d = FTRL-V2 / group FTRL-V2
 // k_ltsum dispatch (kv_fused.h: tile pass + tile sums), instantiated next to k_tsum; ids_kind 0 int64, 1 int32
 extern "C" int kvp_launch_ltsum(const void* td, const void* wd, const void* ids, int ids_kind, long long n, int det,
                                 const float* grad, void* stream);
 extern "C" int kvp_launch_papply_a(int opt, const void* wd, const void* pa, int mode, void* stream, const void* md = nullptr, int ntab = 0);
 extern "C" int kvp_launch_papply_b(int opt, const void* wd, const void* pa, int mode, void* stream, const void* md = nullptr, int ntab = 0);
+extern "C" int kvp_launch_papply_d(int opt, const void* wd, const void* pa, int mode, void* stream, const void* md = nullptr, int ntab = 0);
 extern "C" int kvp_launch_papply_ud(const void* wd, const void* pa, int mode, void* stream, const void* md = nullptr, int ntab = 0);   // PA_UNIQUE / PA_DEDUP
 // k_uapply dispatch (kv_uapply.h: the apply on unique ids), instantiated next to k_papply
 extern "C" int kvp_launch_uapply_a(int opt, const void* pa, const void* ids, int ids32, long long n, void* stream, const void* md = nullptr,
                                    int ntab = 0);
 extern "C" int kvp_launch_uapply_b(int opt, const void* pa, const void* ids, int ids32, long long n, void* stream, const void* md = nullptr,
+                                   int ntab = 0);
+extern "C" int kvp_launch_uapply_d(int opt, const void* pa, const void* ids, int ids32, long long n, void* stream, const void* md = nullptr,
                                    int ntab = 0);
 
 namespace {
@@ -77,6 +83,20 @@ namespace {
 #include "kv_kernels.h"
 #include "kv_fused.h"
 #include "kv_papply.h"
+
+// which translation unit instantiates an optimizer's apply kernels: a (GroupAdam), d / c (FTRL-V2, group FTRL-V2), else b
+constexpr bool ftrl_v2_unit(int opt) { return opt == OPT_FTRL_V2 || opt == OPT_GROUP_FTRL_V2; }
+int launch_papply_any(int opt, const void* wd, const void* pa, int mode, void* stream, const void* md = nullptr, int ntab = 0) {
+  if (group_adam(opt)) return kvp_launch_papply_a(opt, wd, pa, mode, stream, md, ntab);
+  if (ftrl_v2_unit(opt)) return kvp_launch_papply_d(opt, wd, pa, mode, stream, md, ntab);
+  return kvp_launch_papply_b(opt, wd, pa, mode, stream, md, ntab);
+}
+int launch_uapply_any(int opt, const void* pa, const void* ids, int ids32, long long n, void* stream, const void* md = nullptr,
+                      int ntab = 0) {
+  if (group_adam(opt)) return kvp_launch_uapply_a(opt, pa, ids, ids32, n, stream, md, ntab);
+  if (ftrl_v2_unit(opt)) return kvp_launch_uapply_d(opt, pa, ids, ids32, n, stream, md, ntab);
+  return kvp_launch_uapply_b(opt, pa, ids, ids32, n, stream, md, ntab);
+}
 
 // ------------------------------------------------------------------------------------------
 // maintenance kernels
@@ -977,7 +997,8 @@ int launch_apply(kv_table* prof_t, const WsDev& wd, const PartArgs& pa, long lon
   constexpr int gmax = 2048;
   const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(gmax, (nmax / 2 + chunk_cap(nmax)) / 4 + 1));
   const unsigned gfin = (unsigned)std::max<long long>(1, std::min<long long>(256, nmax / 4096 + 1));   // each block reads its share of the items at once
-  auto fn = (MODE == MODE_APPLY && (OPT == OPT_ADAM_V4 || OPT == OPT_ADAM_V3)) ? kvp_launch_apply_a : kvp_launch_apply_b;
+  auto fn = (MODE == MODE_APPLY && group_adam(OPT)) ? kvp_launch_apply_a
+            : (MODE == MODE_APPLY && ftrl_v2_unit(OPT)) ? kvp_launch_apply_c : kvp_launch_apply_b;
   int rc;
   if (pa.det == 2 && !md) {
     // occurrence order: the hot keys' chains first (k_occ_sum: one block per key, the sums to hpart), k_apply reads them
@@ -1151,7 +1172,7 @@ static int mirror_decide_rt(int opt, kv_table* v, kv_table* s0, PartArgs& pa, bo
   if ((v->mirror_slot || s0->mirror_var) && stream_is_capturing(s))
     return fail(KV_FAILED_PRECONDITION, "optimizer apply under stream capture on a (var, slot) pair with live slot mirrors: call "
                                         "kv_prepare_capture on both tables (outside the capture) first");
-  const bool eligible = opt != OPT_FTRL && lean && pa.use_hints != 0 && pa.tv.single != 0u && pa.ts0.single != 0u &&
+  const bool eligible = !two_slots(opt) && lean && pa.use_hints != 0 && pa.tv.single != 0u && pa.ts0.single != 0u &&
                         !v->track_delta && !s0->track_delta && !stream_is_capturing(s) && mirror_pair(v, s0, s);
   if (eligible) {
     pa.use_mirror = 1;
@@ -1345,8 +1366,7 @@ int fused_apply(kv_table* v, WsDev& wd, PartArgs& pa, long long n, hipStream_t s
     if (rc) return fail(rc, "tile sums: no kernel for dim %d", pa.tv.dim);
   }
   ProfScope ps(v, KV_PROF_APPLY_SORTED, s);
-  const int rc = (OPT == OPT_ADAM_V4 || OPT == OPT_ADAM_V3) ? kvp_launch_papply_a(OPT, &wd, &pa, pa_mode, (void*)s)
-                                                            : kvp_launch_papply_b(OPT, &wd, &pa, pa_mode, (void*)s);
+  const int rc = launch_papply_any(OPT, &wd, &pa, pa_mode, (void*)s);
   if (rc) return fail(rc, "partition + apply pass: no kernel for dim %d", pa.tv.dim);
   return KV_OK;
 }
@@ -2078,7 +2098,8 @@ static int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const vo
   return KV_OK;
 }
 
-// shared body of the batched optimizer ops: opt = OPT_*; slots1 only for FTRL (linear); slot_mult =
+static int check_ftrl_v2_hp(float lr, float l1, float l2, float l2s, float lr_power);
+// shared body of the batched optimizer ops: opt = OPT_*; slots1 only for the FTRL family (linear); slot_mult =
 // slot dim / var dim
 static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_handle_t* slots0,
                               const kv_handle_t* slots1, int slot_mult, const float* const* grads,
@@ -2116,7 +2137,7 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   MultiLock lock(all);
   // GroupAdam / Adagrad over pairs (var_i, slot_i): the lean update works on the var rows' slot mirrors (mirror_decide per
   // table below); FTRL reads and writes the slot tables' own records: its entry ends the tables' epochs
-  MirrorKeep mk(vars, opt != OPT_FTRL ? num_tables : 0, slots0, opt != OPT_FTRL ? num_tables : 0);
+  MirrorKeep mk(vars, !two_slots(opt) ? num_tables : 0, slots0, !two_slots(opt) ? num_tables : 0);
   if (tl_unique && fused_ok(D) && !stream_is_capturing(s)) {
     // The caller promises that no table's ids hold an id twice (kv_multi_apply_*_unique; kv_uapply.h): ONE launch for all
     // tables, one lane group per id (grid.y = table).  Pending lookup passes are settled first.
@@ -2157,8 +2178,7 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
     rel.launched = true;
     const int ids32 = vars[0]->key_dtype == KV_DT_INT32 ? 1 : 0;
     ProfScope ps(vars[0], KV_PROF_APPLY_UNIQUE, s);
-    rc = (opt == OPT_ADAM_V4 || opt == OPT_ADAM_V3) ? kvp_launch_uapply_a(opt, &hd[0].a, nullptr, ids32, nmax, (void*)s, sl->dev, num_tables)
-                                                    : kvp_launch_uapply_b(opt, &hd[0].a, nullptr, ids32, nmax, (void*)s, sl->dev, num_tables);
+    rc = launch_uapply_any(opt, &hd[0].a, nullptr, ids32, nmax, (void*)s, sl->dev, num_tables);
     if (rc) return fail(rc, "batched unique apply: no kernel for dim %d", D);
     HIP_TRY(hipGetLastError());
     return KV_OK;
@@ -2244,8 +2264,7 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
     }
     if ((rc = kvp_launch_tsum(&hd[0].a.tv, &wmax, nullptr, (void*)s, md, num_tables)))
       return fail(rc, "tile sums: no kernel for dim %d", D);
-    rc = (opt == OPT_ADAM_V4 || opt == OPT_ADAM_V3) ? kvp_launch_papply_a(opt, &wmax, &hd[0].a, pa_mode, (void*)s, md, num_tables)
-                                                    : kvp_launch_papply_b(opt, &wmax, &hd[0].a, pa_mode, (void*)s, md, num_tables);
+    rc = launch_papply_any(opt, &wmax, &hd[0].a, pa_mode, (void*)s, md, num_tables);
     if (rc) return fail(rc, "partition + apply pass: no kernel for dim %d", D);
     HIP_TRY(hipGetLastError());
     return KV_OK;
@@ -2258,6 +2277,8 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
     case OPT_ADAM_V4: rc = launch_apply<MODE_APPLY, OPT_ADAM_V4>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables); break;
     case OPT_ADAM_V3: rc = launch_apply<MODE_APPLY, OPT_ADAM_V3>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables); break;
     case OPT_ADAGRAD: rc = launch_apply<MODE_APPLY, OPT_ADAGRAD>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables); break;
+    case OPT_FTRL_V2: rc = launch_apply<MODE_APPLY, OPT_FTRL_V2>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables); break;
+    case OPT_GROUP_FTRL_V2: rc = launch_apply<MODE_APPLY, OPT_GROUP_FTRL_V2>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables); break;
     default: rc = launch_apply<MODE_APPLY, OPT_FTRL>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables); break;
   }
   if (rc) return rc;
@@ -2337,6 +2358,43 @@ int kv_multi_apply_sparse_group_ftrl_tok(int num_tables, const kv_handle_t* vars
   return multi_apply_common(num_tables, vars, accums, linears, 1, grads, ids, ns, a, OPT_FTRL, stream, tokens);
 }
 
+static int multi_apply_ftrl_v2_impl(int opt, int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
+                                    const kv_handle_t* linears, const float* const* grads, const void* const* ids,
+                                    const int64_t* ns, float lr, float l1, float l2, float l2s, float lr_power,
+                                    const kv_batch_token_t* tokens, kv_stream_t stream) {
+  int rc;
+  if ((rc = check_ftrl_v2_hp(lr, l1, l2, l2s, lr_power))) return rc;
+  if (num_tables < 1 || !vars || !vars[0] || !linears) return fail(KV_INVALID_ARGUMENT, "N must be >= 1");
+  OptArgs a{};
+  a.lr = lr; a.l1 = l1; a.l2 = l2; a.l2s = l2s; a.lr_power = lr_power;
+  return multi_apply_common(num_tables, vars, accums, linears, 1, grads, ids, ns, a, opt, stream, tokens);
+}
+int kv_multi_apply_ftrl_v2(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, const kv_handle_t* linears,
+                           const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float l1, float l2,
+                           float l2s, float lr_power, kv_stream_t stream) {
+  return multi_apply_ftrl_v2_impl(OPT_FTRL_V2, num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l2s, lr_power,
+                                  nullptr, stream);
+}
+int kv_multi_apply_ftrl_v2_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, const kv_handle_t* linears,
+                               const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float l1,
+                               float l2, float l2s, float lr_power, const kv_batch_token_t* tokens, kv_stream_t stream) {
+  return multi_apply_ftrl_v2_impl(OPT_FTRL_V2, num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l2s, lr_power,
+                                  tokens, stream);
+}
+int kv_multi_apply_group_ftrl_v2(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, const kv_handle_t* linears,
+                                 const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float l1,
+                                 float l2, float l2s, float lr_power, kv_stream_t stream) {
+  return multi_apply_ftrl_v2_impl(OPT_GROUP_FTRL_V2, num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l2s,
+                                  lr_power, nullptr, stream);
+}
+int kv_multi_apply_group_ftrl_v2_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
+                                     const kv_handle_t* linears, const float* const* grads, const void* const* ids,
+                                     const int64_t* ns, float lr, float l1, float l2, float l2s, float lr_power,
+                                     const kv_batch_token_t* tokens, kv_stream_t stream) {
+  return multi_apply_ftrl_v2_impl(OPT_GROUP_FTRL_V2, num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l2s,
+                                  lr_power, tokens, stream);
+}
+
 }  // extern "C"
 
 static bool claim_slot(kv_table* v, kv_table* sl, hipStream_t s);
@@ -2372,8 +2430,7 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
     if ((rc = mirror_decide<OPT>(v, s0, pa, true, s))) return rc;
     pa.uniq_serial = ++v->uniq_serial;
     ProfScope ps(v, KV_PROF_APPLY_UNIQUE, s);
-    rc = (OPT == OPT_ADAM_V4 || OPT == OPT_ADAM_V3) ? kvp_launch_uapply_a(OPT, &pa, ids, v->key_dtype == KV_DT_INT32 ? 1 : 0, n, (void*)s)
-                                                    : kvp_launch_uapply_b(OPT, &pa, ids, v->key_dtype == KV_DT_INT32 ? 1 : 0, n, (void*)s);
+    rc = launch_uapply_any(OPT, &pa, ids, v->key_dtype == KV_DT_INT32 ? 1 : 0, n, (void*)s);
     if (rc) return fail(rc, "unique apply: no kernel for dim %d", v->dim);
     HIP_TRY(hipGetLastError());
     return KV_OK;
@@ -2535,6 +2592,56 @@ int kv_apply_sparse_group_ftrl(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, 
   return kv_apply_sparse_group_ftrl_tok(v, acc, lin, grad, ids, n, lr, l1, l2, l21, l2s, lr_power, 0, stream);
 }
 
+// FTRL-V2 (opt = OPT_FTRL_V2) and group FTRL-V2 (OPT_GROUP_FTRL_V2): the checks of the reference's Compute
+// (training_ops.cc:281-440, 805-960), then the SparseGroupFtrl pipeline with the op's own row math
+static int check_ftrl_v2_hp(float lr, float l1, float l2, float l2s, float lr_power) {
+  if (!(lr > 0.f)) return fail(KV_INVALID_ARGUMENT, "lr is not a positive scalar: %g", lr);
+  if (!(l1 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l1 regularization strength is not a non-negative scalar: %g", l1);
+  if (!(l2 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l2 regularization strength is not a non-negative scalar: %g", l2);
+  if (!(lr_power <= 0.f)) return fail(KV_INVALID_ARGUMENT, "lr_power is not a non-positive scalar: %g", lr_power);
+  if (!(l2s >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l2 shrinkage regularization strength is not a non-negative scalar: %g", l2s);
+  return KV_OK;
+}
+static int apply_ftrl_v2_impl(int opt, kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids,
+                              int64_t n, float lr, float l1, float l2, float l2s, float lr_power, kv_batch_token_t token,
+                              kv_stream_t stream) {
+  int rc;
+  if ((rc = check_table(v)) || (rc = check_table(acc)) || (rc = check_table(lin))) return rc;
+  if (!v->initialized || !acc->initialized || !lin->initialized)
+    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables");
+  if ((rc = check_ftrl_v2_hp(lr, l1, l2, l2s, lr_power))) return rc;
+  if (acc->dim != v->dim) return fail(KV_INVALID_ARGUMENT, "kv_varaible and accum do not have the same shape [%d] [%d]", v->dim, acc->dim);
+  if (lin->dim != v->dim) return fail(KV_INVALID_ARGUMENT, "kv_variable and linear do not have the same shape [%d] [%d]", v->dim, lin->dim);
+  if (v->device != acc->device || v->device != lin->device || v == acc || v == lin || acc == lin)
+    return fail(KV_INVALID_ARGUMENT, "var, accum and linear must be distinct tables on one device");
+  if (n == 0) return KV_OK;
+  DeviceGuard dg(v->device);
+  MultiLock lk({v, acc, lin});
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = lk.enter(s, token != 0 && token == v->batch_serial ? v : nullptr))) return rc;
+  OptArgs a{};
+  a.lr = lr; a.l1 = l1; a.l2 = l2; a.l2s = l2s; a.lr_power = lr_power;
+  return opt == OPT_FTRL_V2 ? apply_common<OPT_FTRL_V2>(v, acc, lin, grad, ids, n, a, token, s)
+                            : apply_common<OPT_GROUP_FTRL_V2>(v, acc, lin, grad, ids, n, a, token, s);
+}
+int kv_apply_ftrl_v2_tok(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
+                         float lr, float l1, float l2, float l2s, float lr_power, kv_batch_token_t token, kv_stream_t stream) {
+  return apply_ftrl_v2_impl(OPT_FTRL_V2, v, acc, lin, grad, ids, n, lr, l1, l2, l2s, lr_power, token, stream);
+}
+int kv_apply_ftrl_v2(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
+                     float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
+  return apply_ftrl_v2_impl(OPT_FTRL_V2, v, acc, lin, grad, ids, n, lr, l1, l2, l2s, lr_power, 0, stream);
+}
+int kv_apply_group_ftrl_v2_tok(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
+                               float lr, float l1, float l2, float l2s, float lr_power, kv_batch_token_t token,
+                               kv_stream_t stream) {
+  return apply_ftrl_v2_impl(OPT_GROUP_FTRL_V2, v, acc, lin, grad, ids, n, lr, l1, l2, l2s, lr_power, token, stream);
+}
+int kv_apply_group_ftrl_v2(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
+                           float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
+  return apply_ftrl_v2_impl(OPT_GROUP_FTRL_V2, v, acc, lin, grad, ids, n, lr, l1, l2, l2s, lr_power, 0, stream);
+}
+
 // The same ops with the caller's promise that `ids` holds no id twice — what the reference's ops receive in an unchanged
 // TF graph (TF-core de-duplicates the IndexedSlices in front of them, variable_scope.py:1096-1106): kv_uapply.h
 struct UniqueScope { UniqueScope() { tl_unique = true; } ~UniqueScope() { tl_unique = false; } };
@@ -2576,6 +2683,30 @@ int kv_apply_sparse_group_ftrl_unique(kv_handle_t v, kv_handle_t acc, kv_handle_
                                       float l2s, float lr_power, kv_stream_t stream) {
   UniqueScope u;
   return kv_apply_sparse_group_ftrl_tok(v, acc, lin, grad, ids, n, lr, l1, l2, l21, l2s, lr_power, 0, stream);
+}
+int kv_apply_ftrl_v2_unique(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
+                            float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
+  UniqueScope u;
+  return apply_ftrl_v2_impl(OPT_FTRL_V2, v, acc, lin, grad, ids, n, lr, l1, l2, l2s, lr_power, 0, stream);
+}
+int kv_apply_group_ftrl_v2_unique(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids,
+                                  int64_t n, float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
+  UniqueScope u;
+  return apply_ftrl_v2_impl(OPT_GROUP_FTRL_V2, v, acc, lin, grad, ids, n, lr, l1, l2, l2s, lr_power, 0, stream);
+}
+int kv_multi_apply_ftrl_v2_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
+                                  const kv_handle_t* linears, const float* const* grads, const void* const* ids,
+                                  const int64_t* ns, float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
+  UniqueScope u;
+  return kv_multi_apply_ftrl_v2_tok(num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l2s, lr_power, nullptr, stream);
+}
+int kv_multi_apply_group_ftrl_v2_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
+                                        const kv_handle_t* linears, const float* const* grads, const void* const* ids,
+                                        const int64_t* ns, float lr, float l1, float l2, float l2s, float lr_power,
+                                        kv_stream_t stream) {
+  UniqueScope u;
+  return kv_multi_apply_group_ftrl_v2_tok(num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l2s, lr_power, nullptr,
+                                          stream);
 }
 
 // The slot table whose rows the var's index entries remember (Entry::hint): the first slot-0 table an
@@ -3944,7 +4075,8 @@ int kv_shard_apply_route(kv_shard_t sh, const float* grad, kv_stream_t stream) {
 // the owner's half: recv_rows holds the peers' summed gradients, record for record as the lookup served them; the
 // fused apply takes the index that lookup left in the table's workspace.  2 launches.
 // optimizer: 0 GroupAdam V4, 1 GroupAdam V3 (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21),
-// 2 Adagrad (hp = lr, update_slots), 3 SparseGroupFtrl (hp = lr, l1, l2, l21, l2_shrinkage, lr_power; slot1 = linear)
+// 2 Adagrad (hp = lr, update_slots), 3 SparseGroupFtrl (hp = lr, l1, l2, l21, l2_shrinkage, lr_power; slot1 = linear),
+// 4 FTRL-V2 / 5 group FTRL-V2 (hp = lr, l1, l2, l2_shrinkage, lr_power; slot1 = linear)
 int kv_shard_apply_serve(kv_shard_t sh, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp, kv_stream_t stream) {
   if (!sh || !hp) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_serve: bad arguments");
   if (sh->serve_token == 0 || sh->serve_token != sh->table->batch_serial)
@@ -3961,6 +4093,9 @@ int kv_shard_apply_serve(kv_shard_t sh, int optimizer, kv_handle_t slot0, kv_han
     case 3:
       return kv_apply_sparse_group_ftrl_tok(sh->table, slot0, slot1, sh->recv_rows, sh->recv_pairs, nrec, hp[0], hp[1], hp[2], hp[3],
                                             hp[4], hp[5], sh->serve_token, stream);
+    case 4: case 5:
+      return apply_ftrl_v2_impl(optimizer == 4 ? OPT_FTRL_V2 : OPT_GROUP_FTRL_V2, sh->table, slot0, slot1, sh->recv_rows,
+                                sh->recv_pairs, nrec, hp[0], hp[1], hp[2], hp[3], hp[4], sh->serve_token, stream);
     default:
       return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_serve: optimizer %d", optimizer);
   }
@@ -4543,7 +4678,7 @@ int kv_multi_shard_lookup(const kv_shard_t* shards, int ntab, kv_comm_t comm, co
   return KV_OK;
 }
 
-// slot0 / slot1: one handle per table (slot1 only for SparseGroupFtrl, else nullptr); hp as in kv_shard_apply_serve
+// slot0 / slot1: one handle per table (slot1 only for the FTRL family, else nullptr); hp as in kv_shard_apply_serve
 int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int optimizer, const kv_handle_t* slot0,
                          const kv_handle_t* slot1, const float* const* grads, const float* hp, int join, kv_stream_t stream) {
   int rc;
@@ -4595,9 +4730,9 @@ int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int
     auto can = [&](int k) {
       const kv_shard* sh = shards[k];
       return sh->table->key_dtype == KV_DT_INT64 && (long long)sh->world * (sh->C + 1) <= (1ll << 21) && sh->serve_token != 0 &&
-             sh->serve_token == sh->table->batch_serial && sh->table->fused_index && slot0[k] != nullptr && (optimizer != 3 || (slot1 && slot1[k]));
+             sh->serve_token == sh->table->batch_serial && sh->table->fused_index && slot0[k] != nullptr && (optimizer < 3 || (slot1 && slot1[k]));
     };
-    if (optimizer >= 0 && optimizer <= 3)
+    if (optimizer >= 0 && optimizer <= 5)
       for (int k = 0; k < ntab; ++k)
         if (can(k)) dims.push_back(shards[k]->table->dim);
     std::sort(dims.begin(), dims.end());
@@ -4629,6 +4764,10 @@ int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int
           break;
         case 2:
           r = kv_multi_apply_adagrad_tok(m, vs.data(), s0.data(), hp[0], gp.data(), ip.data(), nn.data(), hp[1] != 0.f, tok.data(), w);
+          break;
+        case 4: case 5:
+          r = multi_apply_ftrl_v2_impl(optimizer == 4 ? OPT_FTRL_V2 : OPT_GROUP_FTRL_V2, m, vs.data(), s0.data(), s1.data(), gp.data(),
+                                       ip.data(), nn.data(), hp[0], hp[1], hp[2], hp[3], hp[4], tok.data(), w);
           break;
         default:
           r = kv_multi_apply_sparse_group_ftrl_tok(m, vs.data(), s0.data(), s1.data(), gp.data(), ip.data(), nn.data(), hp[0], hp[1], hp[2],

@@ -275,6 +275,31 @@ def kv_variable_sparse_group_sparse_apply_ftrl_v2(var, accum, linear, grad, indi
       _scalar(l2), _scalar(l21), _scalar(l2_shrinkage), _scalar(lr_power), _token_for(var, ids), _stream(var)))
 
 
+def _ftrl_v2(fn, var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power, unique_indices):
+  g, ids = _grad_ids(var, grad, indices)
+  sc = (_scalar(lr), _scalar(l1), _scalar(l2), _scalar(l2_shrinkage), _scalar(lr_power))
+  lib = _lib.lib()
+  if unique_indices:
+    _lib.check(getattr(lib, fn + "_unique")(var.ptr, accum.ptr, linear.ptr, _p(g), _p(ids), ids.numel(), *sc, _stream(var)))
+    return
+  _lib.check(getattr(lib, fn + "_tok")(var.ptr, accum.ptr, linear.ptr, _p(g), _p(ids), ids.numel(), *sc,
+                                       _token_for(var, ids), _stream(var)))
+
+
+def kv_variable_sparse_apply_ftrl_v2(var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power,
+                                     use_locking=False, name=None, unique_indices=False):
+  """REGISTER_OP("KvVariableSparseApplyFtrlV2") ops/training_ops.cc:103-117: per-coordinate FTRL-Proximal
+  (kvhip.h kv_apply_ftrl_v2)."""
+  _ftrl_v2("kv_apply_ftrl_v2", var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power, unique_indices)
+
+
+def kv_variable_group_sparse_apply_ftrl_v2(var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power,
+                                           use_locking=False, name=None, unique_indices=False):
+  """REGISTER_OP("KvVariableGroupSparseApplyFtrlV2") ops/training_ops.cc:119-133: FTRL with a group-lasso threshold l1
+  on the whole linear row (kvhip.h kv_apply_group_ftrl_v2)."""
+  _ftrl_v2("kv_apply_group_ftrl_v2", var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power, unique_indices)
+
+
 def kv_dedup_segment_sum(table_handle, indices, grad):
   """tf.unique + tf.unsorted_segment_sum (TF-core _deduplicate_indexed_slices) on the GPU.
   Returns (unique_ids [U], summed [U, dim], inverse [n])."""
@@ -691,6 +716,36 @@ def kv_multi_sparse_group_sparse_apply_ftrl(var_handles, accum_handles, linear_h
                                                              toks, _stream(var_handles[0])))
 
 
+def _multi_ftrl_v2(fn, var_handles, accum_handles, linear_handles, grads, indices, lr, l1, l2, l2_shrinkage, lr_power,
+                   unique_indices):
+  n = len(var_handles)
+  if n < 1 or not (n == len(accum_handles) == len(linear_handles) == len(grads) == len(indices)):
+    raise _lib.InvalidArgumentError("vars, accums, linears, grads and indices must be equally long, N >= 1")
+  ids, gr, ns, toks = _multi_prep(var_handles, grads, indices)
+  vp = (ctypes.c_void_p * n)(*[h.ptr for h in var_handles]); ap = (ctypes.c_void_p * n)(*[h.ptr for h in accum_handles])
+  lp = (ctypes.c_void_p * n)(*[h.ptr for h in linear_handles])
+  sc = [ctypes.c_float(_scalar(x)) for x in (lr, l1, l2, l2_shrinkage, lr_power)]
+  lib = _lib.lib()
+  if unique_indices:
+    _lib.check(getattr(lib, fn + "_unique")(n, vp, ap, lp, _ptr_array(gr), _ptr_array(ids), ns, *sc, _stream(var_handles[0])))
+    return
+  _lib.check(getattr(lib, fn + "_tok")(n, vp, ap, lp, _ptr_array(gr), _ptr_array(ids), ns, *sc, toks, _stream(var_handles[0])))
+
+
+def kv_multi_sparse_apply_ftrl_v2(var_handles, accum_handles, linear_handles, grads, indices, lr, l1, l2, l2_shrinkage,
+                                  lr_power, unique_indices=False):
+  """KvVariableSparseApplyFtrlV2 on many (var, accum, linear) triples with two launches."""
+  _multi_ftrl_v2("kv_multi_apply_ftrl_v2", var_handles, accum_handles, linear_handles, grads, indices, lr, l1, l2,
+                 l2_shrinkage, lr_power, unique_indices)
+
+
+def kv_multi_group_sparse_apply_ftrl_v2(var_handles, accum_handles, linear_handles, grads, indices, lr, l1, l2,
+                                        l2_shrinkage, lr_power, unique_indices=False):
+  """KvVariableGroupSparseApplyFtrlV2 on many (var, accum, linear) triples with two launches."""
+  _multi_ftrl_v2("kv_multi_apply_group_ftrl_v2", var_handles, accum_handles, linear_handles, grads, indices, lr, l1, l2,
+                 l2_shrinkage, lr_power, unique_indices)
+
+
 _COMBINERS = {"sum": _lib.KV_COMBINER_SUM, "mean": _lib.KV_COMBINER_MEAN, "sqrtn": _lib.KV_COMBINER_SQRTN}
 
 
@@ -788,6 +843,7 @@ def kv_unique(table_handle, indices, counts=None, sync=True):
 # ---- sharded tables: the native path (kvhip.h kv_comm_* / kv_shard_*) -------------------------------------
 KV_OWNER_HASH, KV_OWNER_MOD = 0, 1
 OPT_GROUP_ADAM_V4, OPT_GROUP_ADAM_V3, OPT_ADAGRAD, OPT_SPARSE_GROUP_FTRL = 0, 1, 2, 3
+OPT_FTRL_V2, OPT_GROUP_FTRL_V2 = 4, 5   # hp = lr, l1, l2, l2_shrinkage, lr_power; slots = (accum, linear)
 
 
 class KvComm(object):
