@@ -295,8 +295,7 @@ __device__ __forceinline__ void tile_body(const WsDev& w, const IdT* __restrict_
 }
 
 // One op on one table (arguments by value) or the same op on many tables in one launch
-// (blockIdx.y = table; arguments from a descriptor array in device memory, see MultiDesc below).
-struct MultiDesc;
+// (blockIdx.y = table; arguments from a descriptor array in device memory, MultiDesc in kv_types.h).
 template <bool FIRST, typename IdT>
 __global__ void __launch_bounds__(TBT) k_tile(WsDev w, const IdT* __restrict__ ids,
                                              const int* __restrict__ counts, long long n, int det) {
@@ -306,44 +305,6 @@ __global__ void __launch_bounds__(TBT) k_tile(WsDev w, const IdT* __restrict__ i
 // ------------------------------------------------------------------------------------------
 // partition pass
 // ------------------------------------------------------------------------------------------
-struct PartArgs {
-  TableDev tv, ts0, ts1;      // var table; optimizer slot tables (apply)
-  OptArgs opt;
-  const float* grad;          // apply / dedup: input gradient rows; scatter: update rows
-  unsigned day;
-  int scatter_op, is_insert;  // MODE_SCATTER
-  int mark_what;              // MODE_MARK: 0 = blacklist, 1 = frequency words (in fvals)
-  const unsigned* fvals;
-  long long* out_keys;        // MODE_UNIQUE
-  float* out_sum;             // MODE_DEDUP fold: out_sum[row] = the key's sum
-  const int* out_map;         // ... or out_sum[out_map[row]] when given
-  int* out_counts;            // MODE_UNIQUE: occurrences (saturating) of each unique key
-  int count_once;             // MODE_LOOKUP: frequency += 1 per unique key instead of per occurrence
-  long long direct_rows;      // MODE_UNIQUE, > 0: keys ARE output row indices in [0, direct_rows)
-                              // (tf.unsorted_segment_sum): no key list, no counter
-  int use_hints;              // apply: ts0 is tv's attached slot table (Entry::hint names ts0's rows)
-  int fold_op;                // MODE_DEDUP fold: KV_SCATTER_ADD (sum) / MUL (product) / MIN / MAX / ASSIGN (last)
-  int det;                    // deterministic reduction mode
-  int sparse_unique;          // MODE_UNIQUE: unique numbers = sorted position of the partition + local number (with gaps)
-  long long n;                // ids in the batch
-  const float* epart;         // entry-list pipeline: list words tagged EP_TAG name rows of this array (tile sums), else of grad
-  unsigned day_lk;            // k_papply (kv_papply.h), PA_LOOKUP: the day stamp of the lookup whose bookkeeping it completes
-  // k_papply PA_UNIQUE with route_world > 0 (sharded lookup route): every distinct id goes straight to its owner's segment
-  int route_world, route_rule;     // owner_rank(id, world, rule)
-  unsigned route_C;                // records per segment (header not counted)
-  long long* route_seg;            // [world][C + 1][2] (id, count) records
-  int* route_slot_of;              // [number] the record the id went to (0: no room)
-  unsigned* route_overflow;        // pinned flag: a segment was too small
-  unsigned* route_gcount;          // [MAXW + 1] records per owner so far; [MAXW]: blocks of the launch that are done
-  unsigned* route_need;            // != nullptr: the LAST block of the launch writes the segments' headers, the largest segment
-                                   // wanted (here) and clears the counters
-  unsigned* route_uhint;           // pinned host word (may be null): the batch's distinct ids
-  unsigned uniq_serial;            // k_uapply (kv_uapply.h): this launch's stamp (1 .. 65535)
-  int use_mirror;                  // the lean update reads / writes the slot row's frequency word and flags in the var row's
-  unsigned mirror_epoch;           // SlotMirror (kv_device.h) when it is valid for this epoch; the host flushes (kvhip.hip mirror_*)
-  int dd_number;                   // k_papply PA_DEDUP: the pass numbers the distinct ids itself (dense, ctr[0]; out_keys[number] = id) —
-                                   // kv_dedup_segment_sum in one partition pass instead of PA_UNIQUE's and then this one
-};
 
 // round r of R keeps the keys whose sub-hash selects it (R = 1: everything)
 __device__ __forceinline__ bool in_round(long long key, unsigned R, unsigned round) {
@@ -428,7 +389,7 @@ __device__ __forceinline__ size_t seg_entry(const unsigned short* tpre, const un
   return (size_t)lo * TILE + tstart[lo] + (x - tpre[lo]);
 }
 
-// lanes that share one row in the apply kernels, by dim (kv_apply_launch.h dispatches on the same table);
+// lanes that share one row in the apply kernels, by dim (launch_apply_t below dispatches on the same table);
 // 64 / lanes keys ride side by side in a wave = the cold batch the partition pass forms
 __host__ __device__ inline int apply_lanes(int D) {
   if ((D & 3) == 0) {
@@ -1877,14 +1838,6 @@ __device__ __forceinline__ void goz_any(const TableDev& t, const void* __restric
 }
 
 // ---- kernel entry points: single table (by value) and many tables (descriptor array) ------------
-struct MultiDesc {
-  WsDev w;
-  PartArgs a;            // a.tv is the table of this entry (lookup) / the var table (apply)
-  const void* ids;
-  const int* counts;
-  float* out;            // lookup output rows
-  long long n;
-};
 
 template <int MODE>
 __global__ void __launch_bounds__(TBK, 4) k_part_keys(WsDev w, PartArgs a) { part_keys_body<MODE>(w, a); }
@@ -1930,6 +1883,61 @@ template <int VQ>
 __global__ void __launch_bounds__(TB) k_gather_multi(const MultiDesc* __restrict__ descs) {
   const MultiDesc& m = descs[blockIdx.y];
   gather_body<VQ>(m.a.tv, m.w, m.out, m.n);
+}
+
+// k_apply / k_apply_fin dispatch on the row geometry (kv_launch.h: launch_sorted_apply, launch_dedup_fold).
+// D % 4 == 0 -> float4 lanes, else scalar lanes.  md != nullptr: one launch over `ntab` tables (grid.y),
+// nchunks = blocks per table; only MODE_APPLY on float4 rows is instantiated for it.
+// span == 0: k_apply, span == 1: k_apply_fin.  Returns KV_OK, or KV_UNIMPLEMENTED for an unsupported dim.
+template <int MODE, int OPT>
+int launch_apply_t(const WsDev& wd, const PartArgs& pa, hipStream_t s, const MultiDesc* md, int ntab,
+                   unsigned nchunks, int span) {
+  const int D = pa.tv.dim;
+  int grid_ = (int)nchunks;
+#define KV_APPLY(V, LPR, K)                                                                        \
+  do {                                                                                             \
+    const size_t sh = span == 1 ? (size_t)(TBF / 64) * D * 4 + 16 : 0;                              \
+    if (span != 1) {  /* one resident generation of blocks: a second one would start when the first ends */  \
+      struct ApTag {};                                                                             \
+      const int resident = resident_blocks<ApTag>(k_apply<MODE, OPT, V, LPR, K>, TBS, 6, 4);   /* per device */ \
+      if ((int)nchunks > resident) grid_ = resident; else grid_ = (int)nchunks;                     \
+    }                                                                                              \
+    if constexpr (MODE == MODE_APPLY && V == 4) {                                                  \
+      if (md) {                                                                                    \
+        if (span) k_apply_fin_multi<MODE, OPT, V, LPR, K><<<dim3((unsigned)grid_, (unsigned)ntab), TBF, sh, s>>>(md);   \
+        else k_apply_multi<MODE, OPT, V, LPR, K><<<dim3((unsigned)grid_, (unsigned)ntab), TBS, sh, s>>>(md);      \
+        return KV_OK;                                                                              \
+      }                                                                                            \
+    }                                                                                              \
+    if (md) return KV_UNIMPLEMENTED;                                                               \
+    if (span) k_apply_fin<MODE, OPT, V, LPR, K><<<grid_, TBF, sh, s>>>(wd, pa);                     \
+    else k_apply<MODE, OPT, V, LPR, K><<<grid_, TBS, sh, s>>>(wd, pa);                        \
+    return KV_OK;                                                                                  \
+  } while (0)
+  if ((D & 3) == 0) {
+    const int q = D / 4;
+    if (q <= 1) KV_APPLY(4, 1, 1);
+    if (q <= 2) KV_APPLY(4, 2, 1);
+    if (q <= 4) KV_APPLY(4, 4, 1);
+    if (q <= 8) KV_APPLY(4, 8, 1);
+    if (q <= 16) KV_APPLY(4, 8, 2);    // dims 36..64: 8 lanes x 2 float4
+    if (q <= 32) KV_APPLY(4, 16, 2);   // dims 68..128: 16 lanes x 2 float4
+    if (q <= 64) KV_APPLY(4, 64, 1);
+    if (q <= 128) KV_APPLY(4, 64, 2);
+    if (q <= 256) KV_APPLY(4, 64, 4);
+  } else {
+    if (D <= 1) KV_APPLY(1, 1, 1);
+    if (D <= 2) KV_APPLY(1, 2, 1);
+    if (D <= 4) KV_APPLY(1, 4, 1);
+    if (D <= 8) KV_APPLY(1, 8, 1);
+    if (D <= 16) KV_APPLY(1, 16, 1);
+    if (D <= 32) KV_APPLY(1, 32, 1);
+    if (D <= 64) KV_APPLY(1, 64, 1);
+    if (D <= 128) KV_APPLY(1, 64, 2);
+    if (D <= 256) KV_APPLY(1, 64, 4);
+  }
+#undef KV_APPLY
+  return KV_UNIMPLEMENTED;
 }
 
 // BatchKvVariableGatherOrZerosV2 (kernels/kv_variable_ops.cc:431-470): N tables, N id lists, N

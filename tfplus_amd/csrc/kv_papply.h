@@ -761,7 +761,7 @@ template <int OPT>
 int launch_papply_t(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t s, const MultiDesc* md = nullptr, int ntab = 0) {
   const int D = pa.tv.dim;
   const size_t sh = (size_t)wd.ntiles * 4 + 32;
-  if ((D & 3) != 0 || (mode & 0xFF) > PA_NONE) return KV_UNIMPLEMENTED;   // (PA_UNIQUE / PA_DEDUP: launch_papply_ud_t)
+  if ((D & 3) != 0 || (mode & 0xFF) > PA_NONE) return KV_UNIMPLEMENTED;   // (PA_UNIQUE / PA_DEDUP: launch_papply_ud, kv_sums.hip)
 #define KV_PA(V, LPR, K)                                                     \
   do {                                                                       \
     if (md) k_papply_multi<OPT, V, LPR, K><<<dim3(wd.P, (unsigned)ntab), 256, sh, s>>>(md, mode);   \
@@ -778,41 +778,5 @@ int launch_papply_t(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t s
   if (q <= 32) KV_PA(4, 16, 2);
   if (q <= 64) KV_PA(4, 64, 1);
 #undef KV_PA
-  return KV_UNIMPLEMENTED;
-}
-
-// PA_UNIQUE (numbering only: one kernel whatever the dim) and PA_DEDUP (the per-id sums, by row geometry): their own
-// kernels, instantiated in their own translation unit (kv_papply_c.hip).  A template so that only that unit holds them.
-template <int UNIT>
-int launch_papply_ud_t(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t s, const MultiDesc* md = nullptr, int ntab = 0) {
-  const size_t sh = (size_t)wd.ntiles * 4 + 32;
-  if (mode == PA_UNIQUE) {
-    if (md) k_papply_uniq_multi<<<dim3(wd.P, (unsigned)ntab), 256, sh, s>>>(md, mode);
-    else if (wd.P <= 512u && !pa.det) k_papply_uniq<512><<<(int)wd.P, 512, sh, s>>>(wd, pa, mode);
-    else k_papply_uniq<256><<<(int)wd.P, 256, sh, s>>>(wd, pa, mode);
-    return KV_OK;
-  }
-  const int D = pa.tv.dim;
-  if (mode != PA_DEDUP || (D & 3) != 0) return KV_UNIMPLEMENTED;
-#define KV_PD(V, LPR, K)                                                     \
-  do {                                                                       \
-    if (md) k_papply_dedup_multi<V, LPR, K><<<dim3(wd.P, (unsigned)ntab), 256, sh, s>>>(md);   \
-    else if (pa.dd_number) {                                                 \
-      if (wd.P <= 512u && !pa.det) k_papply_dedup<V, LPR, K, 512, true><<<(int)wd.P, 512, sh, s>>>(wd, pa);   \
-      else k_papply_dedup<V, LPR, K, 256, true><<<(int)wd.P, 256, sh, s>>>(wd, pa);   \
-    }                                                                        \
-    else if (wd.P <= 512u && !pa.det) k_papply_dedup<V, LPR, K, 512><<<(int)wd.P, 512, sh, s>>>(wd, pa);   \
-    else k_papply_dedup<V, LPR, K, 256><<<(int)wd.P, 256, sh, s>>>(wd, pa);   \
-    return KV_OK;                                                            \
-  } while (0)
-  const int q = D / 4;
-  if (q <= 1) KV_PD(4, 1, 1);
-  if (q <= 2) KV_PD(4, 2, 1);
-  if (q <= 4) KV_PD(4, 4, 1);
-  if (q <= 8) KV_PD(4, 8, 1);
-  if (q <= 16) KV_PD(4, 8, 2);
-  if (q <= 32) KV_PD(4, 16, 2);
-  if (q <= 64) KV_PD(4, 64, 1);
-#undef KV_PD
   return KV_UNIMPLEMENTED;
 }

@@ -51,31 +51,10 @@
 
 #include "../../include/kvhip.h"
 
-// k_apply_sorted / k_apply_span dispatch, compiled in two other translation units (kv_apply_launch.h)
-extern "C" int kvp_launch_apply_a(int mode, int opt, const void* wd, const void* pa, void* stream, const void* md, int ntab,
-                                  unsigned nchunks, int span);
-extern "C" int kvp_launch_apply_b(int mode, int opt, const void* wd, const void* pa, void* stream, const void* md, int ntab,
-                                  unsigned nchunks, int span);
-extern "C" int kvp_launch_apply_c(int mode, int opt, const void* wd, const void* pa, void* stream, const void* md, int ntab,
-                                  unsigned nchunks, int span);
+// the kernels of the instantiation units (one per optimizer, one for the sums) are reached through kv_launch.h
+#include "kv_launch.h"
 
-extern "C" int kvp_launch_tsum(const void* td, const void* wd, const float* grad, void* stream, const void* md, int ntab);
-// k_papply dispatch (kv_papply.h), three more translation units: a = GroupAdam V4 / V3, b = Adagrad / SparseGroupFtrl,
-// d = FTRL-V2 / group FTRL-V2
-// k_ltsum dispatch (kv_fused.h: tile pass + tile sums), instantiated next to k_tsum; ids_kind 0 int64, 1 int32
-extern "C" int kvp_launch_ltsum(const void* td, const void* wd, const void* ids, int ids_kind, long long n, int det,
-                                const float* grad, void* stream);
-extern "C" int kvp_launch_papply_a(int opt, const void* wd, const void* pa, int mode, void* stream, const void* md = nullptr, int ntab = 0);
-extern "C" int kvp_launch_papply_b(int opt, const void* wd, const void* pa, int mode, void* stream, const void* md = nullptr, int ntab = 0);
-extern "C" int kvp_launch_papply_d(int opt, const void* wd, const void* pa, int mode, void* stream, const void* md = nullptr, int ntab = 0);
-extern "C" int kvp_launch_papply_ud(const void* wd, const void* pa, int mode, void* stream, const void* md = nullptr, int ntab = 0);   // PA_UNIQUE / PA_DEDUP
-// k_uapply dispatch (kv_uapply.h: the apply on unique ids), instantiated next to k_papply
-extern "C" int kvp_launch_uapply_a(int opt, const void* pa, const void* ids, int ids32, long long n, void* stream, const void* md = nullptr,
-                                   int ntab = 0);
-extern "C" int kvp_launch_uapply_b(int opt, const void* pa, const void* ids, int ids32, long long n, void* stream, const void* md = nullptr,
-                                   int ntab = 0);
-extern "C" int kvp_launch_uapply_d(int opt, const void* pa, const void* ids, int ids32, long long n, void* stream, const void* md = nullptr,
-                                   int ntab = 0);
+using namespace kvhip_internal;
 
 namespace {
 
@@ -83,20 +62,6 @@ namespace {
 #include "kv_kernels.h"
 #include "kv_fused.h"
 #include "kv_papply.h"
-
-// which translation unit instantiates an optimizer's apply kernels: a (GroupAdam), d / c (FTRL-V2, group FTRL-V2), else b
-constexpr bool ftrl_v2_unit(int opt) { return opt == OPT_FTRL_V2 || opt == OPT_GROUP_FTRL_V2; }
-int launch_papply_any(int opt, const void* wd, const void* pa, int mode, void* stream, const void* md = nullptr, int ntab = 0) {
-  if (group_adam(opt)) return kvp_launch_papply_a(opt, wd, pa, mode, stream, md, ntab);
-  if (ftrl_v2_unit(opt)) return kvp_launch_papply_d(opt, wd, pa, mode, stream, md, ntab);
-  return kvp_launch_papply_b(opt, wd, pa, mode, stream, md, ntab);
-}
-int launch_uapply_any(int opt, const void* pa, const void* ids, int ids32, long long n, void* stream, const void* md = nullptr,
-                      int ntab = 0) {
-  if (group_adam(opt)) return kvp_launch_uapply_a(opt, pa, ids, ids32, n, stream, md, ntab);
-  if (ftrl_v2_unit(opt)) return kvp_launch_uapply_d(opt, pa, ids, ids32, n, stream, md, ntab);
-  return kvp_launch_uapply_b(opt, pa, ids, ids32, n, stream, md, ntab);
-}
 
 // ------------------------------------------------------------------------------------------
 // maintenance kernels
@@ -769,11 +734,6 @@ bool fused_tab(const kv_table* t);
 // written: records [lo, lo + len) of the buffers the calling thread's next op on `table` reads come from `ids` / `grad`
 // (the send buffers) instead.  Per thread, so another thread's op on the same table sees nothing of it.
 struct SelfSegment { const kv_table* table = nullptr; unsigned lo = 0, len = 0; const void* ids = nullptr; const float* grad = nullptr; };
-static thread_local bool tl_unique = false;          // kv_apply_*_unique: the caller promises unique ids (apply_common takes the one-launch path)
-// The duplicate guard of the one-launch path stamps rows with a launch serial that lives on the HOST: a captured launch
-// would be replayed with the serial it was captured with and find its own stamps.  Under stream capture the unique forms
-// therefore run the batch pipeline (which needs no promise; same results, bit for bit): stream_is_capturing().
-static thread_local bool tl_require_reuse = false;   // the batched sharded apply: the tables must still hold their lookups' indexes
 static thread_local std::vector<SelfSegment> tl_selfs;   // (empty outside the sharded owner ops; several tables in the batched ones)
 struct SelfScope {
   size_t mark;
@@ -997,8 +957,10 @@ int launch_apply(kv_table* prof_t, const WsDev& wd, const PartArgs& pa, long lon
   constexpr int gmax = 2048;
   const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(gmax, (nmax / 2 + chunk_cap(nmax)) / 4 + 1));
   const unsigned gfin = (unsigned)std::max<long long>(1, std::min<long long>(256, nmax / 4096 + 1));   // each block reads its share of the items at once
-  auto fn = (MODE == MODE_APPLY && group_adam(OPT)) ? kvp_launch_apply_a
-            : (MODE == MODE_APPLY && ftrl_v2_unit(OPT)) ? kvp_launch_apply_c : kvp_launch_apply_b;
+  auto launch = [&](unsigned nchunks, int span) {
+    if constexpr (MODE == MODE_DEDUP) return launch_dedup_fold(wd, pa, s, md, ntab, nchunks, span);
+    else return launch_sorted_apply<OPT>(wd, pa, s, md, ntab, nchunks, span);
+  };
   int rc;
   if (pa.det == 2 && !md) {
     // occurrence order: the hot keys' chains first (k_occ_sum: one block per key, the sums to hpart), k_apply reads them
@@ -1020,17 +982,16 @@ int launch_apply(kv_table* prof_t, const WsDev& wd, const PartArgs& pa, long lon
   }
   {
     ProfScope ps(prof_t, KV_PROF_APPLY_SORTED, s);
-    rc = fn(MODE, OPT, &wd, &pa, (void*)s, md, ntab, grid, 0);
+    rc = launch(grid, 0);
   }
   if (rc == KV_OK && !skip_fin) {
     ProfScope ps(prof_t, KV_PROF_APPLY_SPAN, s);
-    rc = fn(MODE, OPT, &wd, &pa, (void*)s, md, ntab, gfin, 1);
+    rc = launch(gfin, 1);
   }
   if (rc == KV_UNIMPLEMENTED)
     return md ? fail(KV_UNIMPLEMENTED, "batched launch: embedding dim %d (multiples of 4 only)", D)
               : fail(KV_UNIMPLEMENTED, "embedding dim %d not supported by the fused kernels "
                      "(multiples of 4 up to 1024, any dim up to 256)", D);
-  if (rc) return fail(rc, "apply pass: no kernel for mode %d / optimizer %d", MODE, OPT);
   return KV_OK;
 }
 
@@ -1163,16 +1124,14 @@ bool mirror_pair(kv_table* v, kv_table* sl, hipStream_t s) {
 // Does this apply of (v, s0) work on the var rows' slot mirrors?  lean: the launch is k_papply / k_uapply (their lean
 // update is the only code that reads or writes a mirror).  Otherwise the apply reads and writes the slot table's own
 // records: the epoch ends first (the caller entered both tables under MirrorKeep, so nothing has ended it yet).
-static int mirror_decide_rt(int opt, kv_table* v, kv_table* s0, PartArgs& pa, bool lean, hipStream_t s);
 template <int OPT>
-static int mirror_decide(kv_table* v, kv_table* s0, PartArgs& pa, bool lean, hipStream_t s) { return mirror_decide_rt(OPT, v, s0, pa, lean, s); }
-static int mirror_decide_rt(int opt, kv_table* v, kv_table* s0, PartArgs& pa, bool lean, hipStream_t s) {
+static int mirror_decide(kv_table* v, kv_table* s0, PartArgs& pa, bool lean, hipStream_t s) {
   pa.use_mirror = 0; pa.mirror_epoch = 0u;
   // (a captured apply of a pair that still has mirrors: their flush would be recorded, not run — see mirror_on_entry)
   if ((v->mirror_slot || s0->mirror_var) && stream_is_capturing(s))
     return fail(KV_FAILED_PRECONDITION, "optimizer apply under stream capture on a (var, slot) pair with live slot mirrors: call "
                                         "kv_prepare_capture on both tables (outside the capture) first");
-  const bool eligible = !two_slots(opt) && lean && pa.use_hints != 0 && pa.tv.single != 0u && pa.ts0.single != 0u &&
+  const bool eligible = !two_slots(OPT) && lean && pa.use_hints != 0 && pa.tv.single != 0u && pa.ts0.single != 0u &&
                         !v->track_delta && !s0->track_delta && !stream_is_capturing(s) && mirror_pair(v, s0, s);
   if (eligible) {
     pa.use_mirror = 1;
@@ -1357,16 +1316,16 @@ int fused_apply(kv_table* v, WsDev& wd, PartArgs& pa, long long n, hipStream_t s
   pa.epart = wd.epart;
   if (tile_ids) {
     ProfScope ps(v, KV_PROF_APPLY_TILE, s);
-    const int rc = kvp_launch_ltsum(&pa.tv, &wd, tile_ids, v->key_dtype == KV_DT_INT32 ? 1 : 0, n, v->deterministic ? 1 : 0,
-                                    pa.grad, (void*)s);
+    const int rc = launch_ltsum(pa.tv, wd, tile_ids, v->key_dtype == KV_DT_INT32 ? 1 : 0, n, v->deterministic ? 1 : 0,
+                                pa.grad, s);
     if (rc) return fail(rc, "tile pass + tile sums: no kernel for dim %d", pa.tv.dim);
   } else {
     ProfScope ps(v, KV_PROF_APPLY_TSUM, s);
-    const int rc = kvp_launch_tsum(&pa.tv, &wd, pa.grad, (void*)s, nullptr, 0);
+    const int rc = launch_tsum(pa.tv, wd, pa.grad, s);
     if (rc) return fail(rc, "tile sums: no kernel for dim %d", pa.tv.dim);
   }
   ProfScope ps(v, KV_PROF_APPLY_SORTED, s);
-  const int rc = launch_papply_any(OPT, &wd, &pa, pa_mode, (void*)s);
+  const int rc = launch_papply<OPT>(wd, pa, pa_mode, s);
   if (rc) return fail(rc, "partition + apply pass: no kernel for dim %d", pa.tv.dim);
   return KV_OK;
 }
@@ -2098,13 +2057,16 @@ static int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const vo
   return KV_OK;
 }
 
-static int check_ftrl_v2_hp(float lr, float l1, float l2, float l2s, float lr_power);
-// shared body of the batched optimizer ops: opt = OPT_*; slots1 only for the FTRL family (linear); slot_mult =
-// slot dim / var dim
+}  // extern "C"
+
+// shared body of the batched optimizer ops: slots1 only for the FTRL family (linear); slot_mult = slot dim / var dim.
+// unique and the capture rule: as apply_common's.  require_reuse: the batched sharded apply — the tables must still hold
+// their lookups' indexes.
+template <int OPT>
 static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_handle_t* slots0,
                               const kv_handle_t* slots1, int slot_mult, const float* const* grads,
-                              const void* const* ids, const int64_t* ns, const OptArgs& a, int opt,
-                              kv_stream_t stream, const kv_batch_token_t* tokens = nullptr) {
+                              const void* const* ids, const int64_t* ns, const OptArgs& hp, kv_stream_t stream,
+                              const kv_batch_token_t* tokens, bool unique, bool require_reuse) {
   int rc;
   if ((rc = multi_common(num_tables, vars, ids, ns))) return rc;
   if ((rc = check_same_shape(num_tables, slots0, "slot tables"))) return rc;
@@ -2113,6 +2075,8 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   const int D = vars[0]->dim;
   if ((D & 3) != 0 || !dim_supported(D))
     return fail(KV_UNIMPLEMENTED, "batched optimizer op: embedding dim %d (multiples of 4 up to 1024)", D);
+  OptArgs a = hp;
+  a.l21_norm = a.l21 * std::sqrt((float)D);   // training_ops.cc:728
   std::vector<kv_table*> all;
   for (int i = 0; i < num_tables; ++i) {
     for (const kv_handle_t* sl : {slots0, slots1}) {
@@ -2137,8 +2101,8 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   MultiLock lock(all);
   // GroupAdam / Adagrad over pairs (var_i, slot_i): the lean update works on the var rows' slot mirrors (mirror_decide per
   // table below); FTRL reads and writes the slot tables' own records: its entry ends the tables' epochs
-  MirrorKeep mk(vars, !two_slots(opt) ? num_tables : 0, slots0, !two_slots(opt) ? num_tables : 0);
-  if (tl_unique && fused_ok(D) && !stream_is_capturing(s)) {
+  MirrorKeep mk(vars, !two_slots(OPT) ? num_tables : 0, slots0, !two_slots(OPT) ? num_tables : 0);
+  if (unique && fused_ok(D) && !stream_is_capturing(s)) {
     // The caller promises that no table's ids hold an id twice (kv_multi_apply_*_unique; kv_uapply.h): ONE launch for all
     // tables, one lane group per id (grid.y = table).  Pending lookup passes are settled first.
     long long nmax = 0;
@@ -2169,7 +2133,7 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
       d.a.opt.fast = fast_math_on(v) ? 1 : 0;
       d.a.n = ns[i];
       d.a.use_hints = claim_slot(v, slots0[i], s) ? 1 : 0;
-      if ((rc = mirror_decide_rt(opt, v, slots0[i], d.a, true, s))) return rc;
+      if ((rc = mirror_decide<OPT>(v, slots0[i], d.a, true, s))) return rc;
       d.a.uniq_serial = ns[i] > 0 ? ++v->uniq_serial : 0u;
       d.ids = ids[i];
       d.n = ns[i];
@@ -2178,7 +2142,7 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
     rel.launched = true;
     const int ids32 = vars[0]->key_dtype == KV_DT_INT32 ? 1 : 0;
     ProfScope ps(vars[0], KV_PROF_APPLY_UNIQUE, s);
-    rc = launch_uapply_any(opt, &hd[0].a, nullptr, ids32, nmax, (void*)s, sl->dev, num_tables);
+    rc = launch_uapply<OPT>(hd[0].a, nullptr, ids32, nmax, s, reinterpret_cast<const MultiDesc*>(sl->dev), num_tables);
     if (rc) return fail(rc, "batched unique apply: no kernel for dim %d", D);
     HIP_TRY(hipGetLastError());
     return KV_OK;
@@ -2205,7 +2169,7 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   }
   // (a table whose pass was pending while another's was not: hand_over has just settled it — the batch's entries stay valid)
   long long nmax = 0;
-  if (tl_require_reuse && !reuse)
+  if (require_reuse && !reuse)
     return fail(KV_FAILED_PRECONDITION, "batched sharded apply: another op used a table since this batch's lookup");
   for (int i = 0; i < num_tables; ++i) {
     if (!reuse) vars[i]->batch_serial = 0;
@@ -2233,7 +2197,7 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
     d.a.det = vars[i]->deterministic ? 1 : 0;
     d.a.n = ns[i];
     d.a.use_hints = claim_slot(vars[i], slots0[i], s) ? 1 : 0;
-    if ((rc = mirror_decide_rt(opt, vars[i], slots0[i], d.a, fz, s))) return rc;   // (fz: k_papply_multi; else the sorted-position kernels, no mirrors)
+    if ((rc = mirror_decide<OPT>(vars[i], slots0[i], d.a, fz, s))) return rc;   // (fz: k_papply_multi; else the sorted-position kernels, no mirrors)
     d.ids = ids[i];
     d.n = ns[i];
     if (ns[i] == 0) d.w.ntiles = 0;
@@ -2262,9 +2226,9 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
       for (int i = 0; i < num_tables; ++i)
         if (ns[i] > 0) { vars[i]->batch_serial = ++g_serial; vars[i]->batch_n = ns[i]; vars[i]->index_P = hd[i].w.P; }
     }
-    if ((rc = kvp_launch_tsum(&hd[0].a.tv, &wmax, nullptr, (void*)s, md, num_tables)))
+    if ((rc = launch_tsum(hd[0].a.tv, wmax, nullptr, s, md, num_tables)))
       return fail(rc, "tile sums: no kernel for dim %d", D);
-    rc = launch_papply_any(opt, &wmax, &hd[0].a, pa_mode, (void*)s, md, num_tables);
+    rc = launch_papply<OPT>(wmax, hd[0].a, pa_mode, s, md, num_tables);
     if (rc) return fail(rc, "partition + apply pass: no kernel for dim %d", D);
     HIP_TRY(hipGetLastError());
     return KV_OK;
@@ -2273,137 +2237,22 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   launch_tile<false>(vars[0], wmax, nullptr, nullptr, nmax, s, -1, md, num_tables, wmax.ntiles);
   launch_part_keys<MODE_APPLYIDX>(wmax, hd[0].a, s, md, num_tables);
   launch_order(hd[0].a.tv, wmax, nmax, s, md, num_tables);
-  switch (opt) {
-    case OPT_ADAM_V4: rc = launch_apply<MODE_APPLY, OPT_ADAM_V4>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables); break;
-    case OPT_ADAM_V3: rc = launch_apply<MODE_APPLY, OPT_ADAM_V3>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables); break;
-    case OPT_ADAGRAD: rc = launch_apply<MODE_APPLY, OPT_ADAGRAD>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables); break;
-    case OPT_FTRL_V2: rc = launch_apply<MODE_APPLY, OPT_FTRL_V2>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables); break;
-    case OPT_GROUP_FTRL_V2: rc = launch_apply<MODE_APPLY, OPT_GROUP_FTRL_V2>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables); break;
-    default: rc = launch_apply<MODE_APPLY, OPT_FTRL>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables); break;
-  }
-  if (rc) return rc;
+  if ((rc = launch_apply<MODE_APPLY, OPT>(vars[0], wmax, hd[0].a, nmax, s, md, num_tables))) return rc;
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
 
-int kv_multi_apply_group_adam(int num_tables, const kv_handle_t* vars, const kv_handle_t* slots,
-                              const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
-                              float b1p, float b2p, float b1, float b2, float eps, float l1, float l2, float l21,
-                              int version, kv_stream_t stream) {
-  return kv_multi_apply_group_adam_tok(num_tables, vars, slots, grads, ids, ns, lr, b1p, b2p, b1, b2, eps, l1, l2, l21, version,
-                                       nullptr, stream);
-}
-
-int kv_multi_apply_group_adam_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* slots,
-                                  const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
-                                  float b1p, float b2p, float b1, float b2, float eps, float l1, float l2, float l21,
-                                  int version, const kv_batch_token_t* tokens, kv_stream_t stream) {
-  if (version != 3 && version != 4) return fail(KV_INVALID_ARGUMENT, "GroupAdam version %d: 3 or 4", version);
-  if (!(lr > 0.f)) return fail(KV_INVALID_ARGUMENT, "lr is not a positive scalar: %g", lr);
-  if (!(l1 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l1 regularization strength is not a non-negative scalar: %g", l1);
-  if (!(l2 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l2 regularization strength is not a non-negative scalar: %g", l2);
-  if (!(l21 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l21 regularization strength is not a non-negative scalar: %g", l21);
-  if (num_tables < 1 || !vars || !vars[0]) return fail(KV_INVALID_ARGUMENT, "N must be >= 1");
-  OptArgs a{};
-  a.lr = lr; a.b1p = b1p; a.b2p = b2p; a.b1 = b1; a.b2 = b2; a.eps = eps;
-  if (version == 4) {  // training_ops.cc:7111-7120
-    a.l1 = l1 * lr; a.l2 = l2 * lr; a.l21 = l21 * lr;
-    a.alpha = lr * std::sqrt(1.f - b2p) / (1.f - b1p);
-  } else {             // :5840-5849
-    a.l1 = l1; a.l2 = l2; a.l21 = l21;
-    a.alpha = std::sqrt(1.f - b2p) / (1.f - b1p);
-  }
-  a.l21_norm = a.l21 * std::sqrt((float)vars[0]->dim);
-  return multi_apply_common(num_tables, vars, slots, nullptr, 3, grads, ids, ns, a,
-                            version == 4 ? OPT_ADAM_V4 : OPT_ADAM_V3, stream, tokens);
-}
-
-int kv_multi_apply_adagrad(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, float lr,
-                           const float* const* grads, const void* const* ids, const int64_t* ns,
-                           int update_slots, kv_stream_t stream) {
-  return kv_multi_apply_adagrad_tok(num_tables, vars, accums, lr, grads, ids, ns, update_slots, nullptr, stream);
-}
-
-int kv_multi_apply_adagrad_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, float lr,
-                               const float* const* grads, const void* const* ids, const int64_t* ns,
-                               int update_slots, const kv_batch_token_t* tokens, kv_stream_t stream) {
-  OptArgs a{};
-  a.lr = lr; a.update_slots = update_slots;
-  return multi_apply_common(num_tables, vars, accums, nullptr, 1, grads, ids, ns, a, OPT_ADAGRAD, stream, tokens);
-}
-
-int kv_multi_apply_sparse_group_ftrl(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
-                                     const kv_handle_t* linears, const float* const* grads,
-                                     const void* const* ids, const int64_t* ns, float lr, float l1, float l2,
-                                     float l21, float l2s, float lr_power, kv_stream_t stream) {
-  return kv_multi_apply_sparse_group_ftrl_tok(num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l21, l2s, lr_power,
-                                              nullptr, stream);
-}
-
-int kv_multi_apply_sparse_group_ftrl_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
-                                         const kv_handle_t* linears, const float* const* grads,
-                                         const void* const* ids, const int64_t* ns, float lr, float l1, float l2,
-                                         float l21, float l2s, float lr_power, const kv_batch_token_t* tokens,
-                                         kv_stream_t stream) {
-  if (!(lr > 0.f)) return fail(KV_INVALID_ARGUMENT, "lr is not a positive scalar: %g", lr);
-  if (!(l1 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l1 regularization strength is not a non-negative scalar: %g", l1);
-  if (!(l2 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l2 regularization strength is not a non-negative scalar: %g", l2);
-  if (!(l21 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l21 regularization strength is not a non-negative scalar: %g", l21);
-  if (!(lr_power <= 0.f)) return fail(KV_INVALID_ARGUMENT, "lr_power is not a non-positive scalar: %g", lr_power);
-  if (!(l2s >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l2 shrinkage regularization strength is not a non-negative scalar: %g", l2s);
-  if (num_tables < 1 || !vars || !vars[0] || !linears) return fail(KV_INVALID_ARGUMENT, "N must be >= 1");
-  OptArgs a{};
-  a.lr = lr; a.l1 = l1; a.l2 = l2; a.l21 = l21; a.l2s = l2s; a.lr_power = lr_power;
-  a.l21_norm = l21 * std::sqrt((float)vars[0]->dim);  // training_ops.cc:728
-  return multi_apply_common(num_tables, vars, accums, linears, 1, grads, ids, ns, a, OPT_FTRL, stream, tokens);
-}
-
-static int multi_apply_ftrl_v2_impl(int opt, int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
-                                    const kv_handle_t* linears, const float* const* grads, const void* const* ids,
-                                    const int64_t* ns, float lr, float l1, float l2, float l2s, float lr_power,
-                                    const kv_batch_token_t* tokens, kv_stream_t stream) {
-  int rc;
-  if ((rc = check_ftrl_v2_hp(lr, l1, l2, l2s, lr_power))) return rc;
-  if (num_tables < 1 || !vars || !vars[0] || !linears) return fail(KV_INVALID_ARGUMENT, "N must be >= 1");
-  OptArgs a{};
-  a.lr = lr; a.l1 = l1; a.l2 = l2; a.l2s = l2s; a.lr_power = lr_power;
-  return multi_apply_common(num_tables, vars, accums, linears, 1, grads, ids, ns, a, opt, stream, tokens);
-}
-int kv_multi_apply_ftrl_v2(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, const kv_handle_t* linears,
-                           const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float l1, float l2,
-                           float l2s, float lr_power, kv_stream_t stream) {
-  return multi_apply_ftrl_v2_impl(OPT_FTRL_V2, num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l2s, lr_power,
-                                  nullptr, stream);
-}
-int kv_multi_apply_ftrl_v2_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, const kv_handle_t* linears,
-                               const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float l1,
-                               float l2, float l2s, float lr_power, const kv_batch_token_t* tokens, kv_stream_t stream) {
-  return multi_apply_ftrl_v2_impl(OPT_FTRL_V2, num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l2s, lr_power,
-                                  tokens, stream);
-}
-int kv_multi_apply_group_ftrl_v2(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, const kv_handle_t* linears,
-                                 const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float l1,
-                                 float l2, float l2s, float lr_power, kv_stream_t stream) {
-  return multi_apply_ftrl_v2_impl(OPT_GROUP_FTRL_V2, num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l2s,
-                                  lr_power, nullptr, stream);
-}
-int kv_multi_apply_group_ftrl_v2_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
-                                     const kv_handle_t* linears, const float* const* grads, const void* const* ids,
-                                     const int64_t* ns, float lr, float l1, float l2, float l2s, float lr_power,
-                                     const kv_batch_token_t* tokens, kv_stream_t stream) {
-  return multi_apply_ftrl_v2_impl(OPT_GROUP_FTRL_V2, num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l2s,
-                                  lr_power, tokens, stream);
-}
-
-}  // extern "C"
-
 static bool claim_slot(kv_table* v, kv_table* sl, hipStream_t s);
 
 // shared body of the optimizer ops.  `token` names the batch index a lookup left in the var's workspace
-// (kv_gather_or_insert_tok): the same ids, so the index pass is skipped.  The caller holds the locks.
+// (kv_gather_or_insert_tok): the same ids, so the index pass is skipped.  unique: the caller promises unique ids
+// (kv_apply_*_unique), the one-launch path.  Its duplicate guard stamps rows with a launch serial that lives on the HOST: a
+// captured launch would be replayed with the serial it was captured with and find its own stamps.  Under stream capture the
+// unique forms therefore run the batch pipeline (which needs no promise; same results, bit for bit): stream_is_capturing().
+// The caller holds the locks.
 template <int OPT>
 static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* grad, const void* ids, int64_t n,
-                        const OptArgs& a, kv_batch_token_t token, hipStream_t s) {
+                        const OptArgs& a, kv_batch_token_t token, hipStream_t s, bool unique) {
   const long long nmax = fused_tab(v) ? FUSED_MAX_N : (1ll << 21);
   if (n < 0 || n > nmax)
     return fail(n < 0 ? KV_INVALID_ARGUMENT : KV_UNIMPLEMENTED,
@@ -2412,7 +2261,7 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
   if (!dim_supported(v->dim))
     return fail(KV_UNIMPLEMENTED, "embedding dim %d not supported by the fused kernels", v->dim);
   int rc;
-  if (tl_unique && fused_ok(v->dim) && !stream_is_capturing(s)) {
+  if (unique && fused_ok(v->dim) && !stream_is_capturing(s)) {
     // The caller promises unique ids (kv_apply_*_unique; kv_uapply.h): one launch, one lane group per id.  A pending
     // partition pass was settled by the caller's hand_over (no token is given).  Dims the kernel does not serve take the
     // batch pipeline below, which needs no promise.
@@ -2430,7 +2279,7 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
     if ((rc = mirror_decide<OPT>(v, s0, pa, true, s))) return rc;
     pa.uniq_serial = ++v->uniq_serial;
     ProfScope ps(v, KV_PROF_APPLY_UNIQUE, s);
-    rc = launch_uapply_any(OPT, &pa, ids, v->key_dtype == KV_DT_INT32 ? 1 : 0, n, (void*)s);
+    rc = launch_uapply<OPT>(pa, ids, v->key_dtype == KV_DT_INT32 ? 1 : 0, n, s);
     if (rc) return fail(rc, "unique apply: no kernel for dim %d", v->dim);
     HIP_TRY(hipGetLastError());
     return KV_OK;
@@ -2492,221 +2341,334 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
   return KV_OK;
 }
 
-extern "C" {
+// ---- the optimizer ops -----------------------------------------------------------------------------------------------
+// An optimizer op as the pipelines see it: which kernels (opt, an OPT_*), with which arguments, on slot tables of which
+// shape.  One parser per optimizer family fills it from the op's arguments; every entry point below is a parser and one of
+// two bodies: apply_one (one table) or multi_apply (many tables, one launch per stage).
+struct OptCall {
+  int opt = -1;          // OPT_*; -1: not known (a GroupAdam version other than 3 or 4, a sharded optimizer code)
+  OptArgs a{};           // without l21_norm, which the bodies derive from the var's dim
+  int slot_mult = 1;     // first slot table's dim / var dim; a second slot table (linear) iff two_slots(opt)
+  int status = KV_OK;    // the parser's verdict on the op's arguments; its message is the one fail() recorded last
+};
 
-int kv_apply_group_adam_tok(kv_handle_t v, kv_handle_t mvl, const float* grad, const void* ids, int64_t n,
-                            float lr, float b1p, float b2p, float b1, float b2, float eps, float l1,
-                            float l2, float l21, int version, kv_batch_token_t token, kv_stream_t stream) {
-  int rc;
-  if ((rc = check_table(v)) || (rc = check_table(mvl))) return rc;
-  if (version != 3 && version != 4) return fail(KV_INVALID_ARGUMENT, "GroupAdam version %d: 3 or 4", version);
-  // order and wording of training_ops.cc:7001-7103
-  if (!v->initialized || !mvl->initialized)
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: %s", !v->initialized ? "var" : "m_v_linear");
+// the hyperparameter checks the reference's ops share, in their order and wording (an op without l21 / lr_power / l2s
+// passes 0 for it)
+static int check_hp(float lr, float l1, float l2, float l21, float lr_power, float l2s) {
   if (!(lr > 0.f)) return fail(KV_INVALID_ARGUMENT, "lr is not a positive scalar: %g", lr);
   if (!(l1 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l1 regularization strength is not a non-negative scalar: %g", l1);
   if (!(l2 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l2 regularization strength is not a non-negative scalar: %g", l2);
   if (!(l21 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l21 regularization strength is not a non-negative scalar: %g", l21);
-  if (mvl->dim != 3 * v->dim)
-    return fail(KV_INVALID_ARGUMENT, "kv_variable and linear do not have the same shape [%d] [%d] (m_v_linear must be 3x)", v->dim, mvl->dim);
-  if (v->device != mvl->device) return fail(KV_INVALID_ARGUMENT, "var and slot live on different devices");
-  if (v == mvl) return fail(KV_INVALID_ARGUMENT, "var and m_v_linear are the same table");
-  if (n == 0) return KV_OK;
-  DeviceGuard dg(v->device);
-  MultiLock lk({v, mvl});
-  MirrorKeep mk(v, mvl);   // (apply_common decides whether this apply works on the mirrors: mirror_decide)
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = lk.enter(s, token != 0 && token == v->batch_serial ? v : nullptr))) return rc;
-  OptArgs a{};
+  if (!(lr_power <= 0.f)) return fail(KV_INVALID_ARGUMENT, "lr_power is not a non-positive scalar: %g", lr_power);
+  if (!(l2s >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l2 shrinkage regularization strength is not a non-negative scalar: %g", l2s);
+  return KV_OK;
+}
+
+// GroupAdam V4 / V3 (training_ops.cc:7001-7120, 5730-5849); slot row = m | v | z
+static OptCall group_adam_call(int version, float lr, float b1p, float b2p, float b1, float b2, float eps, float l1, float l2,
+                               float l21) {
+  OptCall c;
+  if (version != 3 && version != 4) {
+    c.status = fail(KV_INVALID_ARGUMENT, "GroupAdam version %d: 3 or 4", version);
+    return c;
+  }
+  c.opt = version == 4 ? OPT_ADAM_V4 : OPT_ADAM_V3;
+  c.slot_mult = 3;
+  if ((c.status = check_hp(lr, l1, l2, l21, 0.f, 0.f))) return c;
+  OptArgs& a = c.a;
   a.lr = lr; a.b1p = b1p; a.b2p = b2p; a.b1 = b1; a.b2 = b2; a.eps = eps;
-  if (version == 4) {  // :7111-7120
+  if (version == 4) {  // training_ops.cc:7111-7120
     a.l1 = l1 * lr; a.l2 = l2 * lr; a.l21 = l21 * lr;
     a.alpha = lr * std::sqrt(1.f - b2p) / (1.f - b1p);
   } else {             // :5840-5849
     a.l1 = l1; a.l2 = l2; a.l21 = l21;
     a.alpha = std::sqrt(1.f - b2p) / (1.f - b1p);
   }
-  a.l21_norm = a.l21 * std::sqrt((float)v->dim);
-  return version == 4 ? apply_common<OPT_ADAM_V4>(v, mvl, nullptr, grad, ids, n, a, token, s)
-                      : apply_common<OPT_ADAM_V3>(v, mvl, nullptr, grad, ids, n, a, token, s);
+  return c;
 }
-int kv_apply_group_adam(kv_handle_t v, kv_handle_t mvl, const float* grad, const void* ids, int64_t n,
-                        float lr, float b1p, float b2p, float b1, float b2, float eps, float l1,
-                        float l2, float l21, int version, kv_stream_t stream) {
-  return kv_apply_group_adam_tok(v, mvl, grad, ids, n, lr, b1p, b2p, b1, b2, eps, l1, l2, l21, version, 0, stream);
+// Adagrad (training_ops.cc:1372-1498): no checks of its own arguments
+static OptCall adagrad_call(float lr, int update_slots) {
+  OptCall c;
+  c.opt = OPT_ADAGRAD;
+  c.a.lr = lr; c.a.update_slots = update_slots;
+  return c;
 }
-
-int kv_apply_adagrad_tok(kv_handle_t v, kv_handle_t acc, float lr, const float* grad, const void* ids,
-                         int64_t n, int update_slots, kv_batch_token_t token, kv_stream_t stream) {
-  int rc;
-  if ((rc = check_table(v)) || (rc = check_table(acc))) return rc;
-  if (!v->initialized || !acc->initialized)
-    return fail(KV_FAILED_PRECONDITION, "Attempting to use uninitialized variables: %s", !v->initialized ? "var" : "accum");
-  if (acc->dim != v->dim) return fail(KV_INVALID_ARGUMENT, "var and accum do not have the same shape [%d] [%d]", v->dim, acc->dim);
-  if (v->device != acc->device || v == acc) return fail(KV_INVALID_ARGUMENT, "var and accum must be distinct tables on one device");
-  if (n == 0) return KV_OK;
-  DeviceGuard dg(v->device);
-  MultiLock lk({v, acc});
-  MirrorKeep mk(v, acc);   // (mirror_decide in apply_common)
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = lk.enter(s, token != 0 && token == v->batch_serial ? v : nullptr))) return rc;
-  OptArgs a{};
-  a.lr = lr; a.update_slots = update_slots;
-  return apply_common<OPT_ADAGRAD>(v, acc, nullptr, grad, ids, n, a, token, s);
+// SparseGroupFtrl (training_ops.cc:684-763); slots accum, linear
+static OptCall sparse_group_ftrl_call(float lr, float l1, float l2, float l21, float l2s, float lr_power) {
+  OptCall c;
+  c.opt = OPT_FTRL;
+  if ((c.status = check_hp(lr, l1, l2, l21, lr_power, l2s))) return c;
+  c.a.lr = lr; c.a.l1 = l1; c.a.l2 = l2; c.a.l21 = l21; c.a.l2s = l2s; c.a.lr_power = lr_power;
+  return c;
 }
-int kv_apply_adagrad(kv_handle_t v, kv_handle_t acc, float lr, const float* grad, const void* ids,
-                     int64_t n, int update_slots, kv_stream_t stream) {
-  return kv_apply_adagrad_tok(v, acc, lr, grad, ids, n, update_slots, 0, stream);
-}
-
-int kv_apply_sparse_group_ftrl_tok(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad,
-                                   const void* ids, int64_t n, float lr, float l1, float l2, float l21,
-                                   float l2s, float lr_power, kv_batch_token_t token, kv_stream_t stream) {
-  int rc;
-  if ((rc = check_table(v)) || (rc = check_table(acc)) || (rc = check_table(lin))) return rc;
-  if (!v->initialized || !acc->initialized || !lin->initialized)
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables");
-  if (!(lr > 0.f)) return fail(KV_INVALID_ARGUMENT, "lr is not a positive scalar: %g", lr);
-  if (!(l1 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l1 regularization strength is not a non-negative scalar: %g", l1);
-  if (!(l2 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l2 regularization strength is not a non-negative scalar: %g", l2);
-  if (!(l21 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l21 regularization strength is not a non-negative scalar: %g", l21);
-  if (!(lr_power <= 0.f)) return fail(KV_INVALID_ARGUMENT, "lr_power is not a non-positive scalar: %g", lr_power);
-  if (!(l2s >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l2 shrinkage regularization strength is not a non-negative scalar: %g", l2s);
-  if (acc->dim != v->dim) return fail(KV_INVALID_ARGUMENT, "kv_varaible and accum do not have the same shape [%d] [%d]", v->dim, acc->dim);
-  if (lin->dim != v->dim) return fail(KV_INVALID_ARGUMENT, "kv_variable and linear do not have the same shape [%d] [%d]", v->dim, lin->dim);
-  if (v->device != acc->device || v->device != lin->device || v == acc || v == lin || acc == lin)
-    return fail(KV_INVALID_ARGUMENT, "var, accum and linear must be distinct tables on one device");
-  if (n == 0) return KV_OK;
-  DeviceGuard dg(v->device);
-  MultiLock lk({v, acc, lin});
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = lk.enter(s, token != 0 && token == v->batch_serial ? v : nullptr))) return rc;
-  OptArgs a{};
-  a.lr = lr; a.l1 = l1; a.l2 = l2; a.l21 = l21; a.l2s = l2s; a.lr_power = lr_power;
-  a.l21_norm = l21 * std::sqrt((float)v->dim);  // :728
-  return apply_common<OPT_FTRL>(v, acc, lin, grad, ids, n, a, token, s);
-}
-int kv_apply_sparse_group_ftrl(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad,
-                               const void* ids, int64_t n, float lr, float l1, float l2, float l21,
-                               float l2s, float lr_power, kv_stream_t stream) {
-  return kv_apply_sparse_group_ftrl_tok(v, acc, lin, grad, ids, n, lr, l1, l2, l21, l2s, lr_power, 0, stream);
-}
-
 // FTRL-V2 (opt = OPT_FTRL_V2) and group FTRL-V2 (OPT_GROUP_FTRL_V2): the checks of the reference's Compute
 // (training_ops.cc:281-440, 805-960), then the SparseGroupFtrl pipeline with the op's own row math
-static int check_ftrl_v2_hp(float lr, float l1, float l2, float l2s, float lr_power) {
-  if (!(lr > 0.f)) return fail(KV_INVALID_ARGUMENT, "lr is not a positive scalar: %g", lr);
-  if (!(l1 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l1 regularization strength is not a non-negative scalar: %g", l1);
-  if (!(l2 >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l2 regularization strength is not a non-negative scalar: %g", l2);
-  if (!(lr_power <= 0.f)) return fail(KV_INVALID_ARGUMENT, "lr_power is not a non-positive scalar: %g", lr_power);
-  if (!(l2s >= 0.f)) return fail(KV_INVALID_ARGUMENT, "l2 shrinkage regularization strength is not a non-negative scalar: %g", l2s);
-  return KV_OK;
-}
-static int apply_ftrl_v2_impl(int opt, kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids,
-                              int64_t n, float lr, float l1, float l2, float l2s, float lr_power, kv_batch_token_t token,
-                              kv_stream_t stream) {
-  int rc;
-  if ((rc = check_table(v)) || (rc = check_table(acc)) || (rc = check_table(lin))) return rc;
-  if (!v->initialized || !acc->initialized || !lin->initialized)
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables");
-  if ((rc = check_ftrl_v2_hp(lr, l1, l2, l2s, lr_power))) return rc;
-  if (acc->dim != v->dim) return fail(KV_INVALID_ARGUMENT, "kv_varaible and accum do not have the same shape [%d] [%d]", v->dim, acc->dim);
-  if (lin->dim != v->dim) return fail(KV_INVALID_ARGUMENT, "kv_variable and linear do not have the same shape [%d] [%d]", v->dim, lin->dim);
-  if (v->device != acc->device || v->device != lin->device || v == acc || v == lin || acc == lin)
-    return fail(KV_INVALID_ARGUMENT, "var, accum and linear must be distinct tables on one device");
-  if (n == 0) return KV_OK;
-  DeviceGuard dg(v->device);
-  MultiLock lk({v, acc, lin});
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = lk.enter(s, token != 0 && token == v->batch_serial ? v : nullptr))) return rc;
-  OptArgs a{};
-  a.lr = lr; a.l1 = l1; a.l2 = l2; a.l2s = l2s; a.lr_power = lr_power;
-  return opt == OPT_FTRL_V2 ? apply_common<OPT_FTRL_V2>(v, acc, lin, grad, ids, n, a, token, s)
-                            : apply_common<OPT_GROUP_FTRL_V2>(v, acc, lin, grad, ids, n, a, token, s);
-}
-int kv_apply_ftrl_v2_tok(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
-                         float lr, float l1, float l2, float l2s, float lr_power, kv_batch_token_t token, kv_stream_t stream) {
-  return apply_ftrl_v2_impl(OPT_FTRL_V2, v, acc, lin, grad, ids, n, lr, l1, l2, l2s, lr_power, token, stream);
-}
-int kv_apply_ftrl_v2(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
-                     float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
-  return apply_ftrl_v2_impl(OPT_FTRL_V2, v, acc, lin, grad, ids, n, lr, l1, l2, l2s, lr_power, 0, stream);
-}
-int kv_apply_group_ftrl_v2_tok(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
-                               float lr, float l1, float l2, float l2s, float lr_power, kv_batch_token_t token,
-                               kv_stream_t stream) {
-  return apply_ftrl_v2_impl(OPT_GROUP_FTRL_V2, v, acc, lin, grad, ids, n, lr, l1, l2, l2s, lr_power, token, stream);
-}
-int kv_apply_group_ftrl_v2(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
-                           float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
-  return apply_ftrl_v2_impl(OPT_GROUP_FTRL_V2, v, acc, lin, grad, ids, n, lr, l1, l2, l2s, lr_power, 0, stream);
+static OptCall ftrl_v2_call(int opt, float lr, float l1, float l2, float l2s, float lr_power) {
+  OptCall c;
+  c.opt = opt;
+  if ((c.status = check_hp(lr, l1, l2, 0.f, lr_power, l2s))) return c;
+  c.a.lr = lr; c.a.l1 = l1; c.a.l2 = l2; c.a.l2s = l2s; c.a.lr_power = lr_power;
+  return c;
 }
 
-// The same ops with the caller's promise that `ids` holds no id twice — what the reference's ops receive in an unchanged
-// TF graph (TF-core de-duplicates the IndexedSlices in front of them, variable_scope.py:1096-1106): kv_uapply.h
-struct UniqueScope { UniqueScope() { tl_unique = true; } ~UniqueScope() { tl_unique = false; } };
-int kv_apply_group_adam_unique(kv_handle_t v, kv_handle_t mvl, const float* grad, const void* ids, int64_t n,
-                               float lr, float b1p, float b2p, float b1, float b2, float eps, float l1,
-                               float l2, float l21, int version, kv_stream_t stream) {
-  UniqueScope u;
-  return kv_apply_group_adam_tok(v, mvl, grad, ids, n, lr, b1p, b2p, b1, b2, eps, l1, l2, l21, version, 0, stream);
+// The sharded ops' `optimizer` code is the OPT_* value; their hp[] layout:
+// 0 GroupAdam V4, 1 GroupAdam V3 (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21),
+// 2 Adagrad (hp = lr, update_slots), 3 SparseGroupFtrl (hp = lr, l1, l2, l21, l2_shrinkage, lr_power; slot1 = linear),
+// 4 FTRL-V2 / 5 group FTRL-V2 (hp = lr, l1, l2, l2_shrinkage, lr_power; slot1 = linear)
+static OptCall shard_opt_call(int optimizer, const float* hp) {
+  switch (optimizer) {
+    case OPT_ADAM_V4: case OPT_ADAM_V3:
+      return group_adam_call(optimizer == OPT_ADAM_V4 ? 4 : 3, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8]);
+    case OPT_ADAGRAD: return adagrad_call(hp[0], hp[1] != 0.f);
+    case OPT_FTRL: return sparse_group_ftrl_call(hp[0], hp[1], hp[2], hp[3], hp[4], hp[5]);
+    case OPT_FTRL_V2: case OPT_GROUP_FTRL_V2: return ftrl_v2_call(optimizer, hp[0], hp[1], hp[2], hp[3], hp[4]);
+    default: return OptCall{};
+  }
+}
+
+// the one place where a runtime OPT_* becomes the template argument of the pipelines
+template <class F>
+static int with_opt(int opt, F&& f) {
+  switch (opt) {
+    case OPT_ADAM_V4: return f(std::integral_constant<int, OPT_ADAM_V4>());
+    case OPT_ADAM_V3: return f(std::integral_constant<int, OPT_ADAM_V3>());
+    case OPT_ADAGRAD: return f(std::integral_constant<int, OPT_ADAGRAD>());
+    case OPT_FTRL: return f(std::integral_constant<int, OPT_FTRL>());
+    case OPT_FTRL_V2: return f(std::integral_constant<int, OPT_FTRL_V2>());
+    case OPT_GROUP_FTRL_V2: return f(std::integral_constant<int, OPT_GROUP_FTRL_V2>());
+    default: return fail(KV_INTERNAL, "optimizer %d", opt);
+  }
+}
+
+// One table (s1: the linear table of the FTRL family).  The reference's single-table ops check, in this order: the handles,
+// the optimizer itself (GroupAdam version), the tables' initialisation, the hyperparameters, the shapes.  So c.status is
+// reported at its place in that order (nothing calls fail() before it unless it returns).  The batched ops report it first.
+static int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const float* grad, const void* ids, int64_t n,
+                     kv_batch_token_t token, kv_stream_t stream, bool unique) {
+  int rc;
+  const bool two = two_slots(c.opt);
+  if ((rc = check_table(v)) || (rc = check_table(s0)) || (two && (rc = check_table(s1)))) return rc;
+  if (c.status && c.opt < 0) return c.status;
+  if (group_adam(c.opt)) {   // order and wording of training_ops.cc:7001-7103
+    if (!v->initialized || !s0->initialized)
+      return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: %s", !v->initialized ? "var" : "m_v_linear");
+  } else if (!two) {
+    if (!v->initialized || !s0->initialized)
+      return fail(KV_FAILED_PRECONDITION, "Attempting to use uninitialized variables: %s", !v->initialized ? "var" : "accum");
+  } else if (!v->initialized || !s0->initialized || !s1->initialized) {
+    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables");
+  }
+  if (c.status) return c.status;
+  if (group_adam(c.opt)) {
+    if (s0->dim != c.slot_mult * v->dim)
+      return fail(KV_INVALID_ARGUMENT, "kv_variable and linear do not have the same shape [%d] [%d] (m_v_linear must be 3x)", v->dim, s0->dim);
+    if (v->device != s0->device) return fail(KV_INVALID_ARGUMENT, "var and slot live on different devices");
+    if (v == s0) return fail(KV_INVALID_ARGUMENT, "var and m_v_linear are the same table");
+  } else if (!two) {
+    if (s0->dim != v->dim) return fail(KV_INVALID_ARGUMENT, "var and accum do not have the same shape [%d] [%d]", v->dim, s0->dim);
+    if (v->device != s0->device || v == s0) return fail(KV_INVALID_ARGUMENT, "var and accum must be distinct tables on one device");
+  } else {
+    if (s0->dim != v->dim) return fail(KV_INVALID_ARGUMENT, "kv_varaible and accum do not have the same shape [%d] [%d]", v->dim, s0->dim);
+    if (s1->dim != v->dim) return fail(KV_INVALID_ARGUMENT, "kv_variable and linear do not have the same shape [%d] [%d]", v->dim, s1->dim);
+    if (v->device != s0->device || v->device != s1->device || v == s0 || v == s1 || s0 == s1)
+      return fail(KV_INVALID_ARGUMENT, "var, accum and linear must be distinct tables on one device");
+  }
+  if (n == 0) return KV_OK;
+  DeviceGuard dg(v->device);
+  MultiLock lk({v, s0, two ? s1 : s0});
+  // GroupAdam / Adagrad: apply_common decides whether this apply works on the mirrors (mirror_decide); the FTRL family reads
+  // and writes the slot tables' own records
+  MirrorKeep mk(two ? nullptr : v, two ? nullptr : s0);
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = lk.enter(s, token != 0 && token == v->batch_serial ? v : nullptr))) return rc;
+  OptArgs a = c.a;
+  a.l21_norm = a.l21 * std::sqrt((float)v->dim);   // training_ops.cc:728
+  return with_opt(c.opt, [&](auto o) { return apply_common<decltype(o)::value>(v, s0, two ? s1 : nullptr, grad, ids, n, a, token, s, unique); });
+}
+
+// Many tables.  After the parser's verdict the ops refuse a missing first table (and linears) — all but Adagrad, whose op
+// leaves that to multi_common — and multi_apply_common checks the tables, their initialisation included.
+static int multi_apply(const OptCall& c, int num_tables, const kv_handle_t* vars, const kv_handle_t* slots0,
+                       const kv_handle_t* slots1, const float* const* grads, const void* const* ids, const int64_t* ns,
+                       const kv_batch_token_t* tokens, kv_stream_t stream, bool unique, bool require_reuse = false) {
+  if (c.status) return c.status;
+  const bool two = two_slots(c.opt);
+  if (c.opt != OPT_ADAGRAD && (num_tables < 1 || !vars || !vars[0] || (two && !slots1)))
+    return fail(KV_INVALID_ARGUMENT, "N must be >= 1");
+  return with_opt(c.opt, [&](auto o) {
+    return multi_apply_common<decltype(o)::value>(num_tables, vars, slots0, two ? slots1 : nullptr, c.slot_mult, grads, ids, ns,
+                                                  c.a, stream, tokens, unique, require_reuse);
+  });
+}
+
+extern "C" {
+
+// ---- the entry points: plain / _tok / _unique, single table and batched ------------------------------------------------
+// The _unique forms carry the caller's promise that `ids` holds no id twice — what the reference's ops receive in an
+// unchanged TF graph (TF-core de-duplicates the IndexedSlices in front of them, variable_scope.py:1096-1106): kv_uapply.h
+int kv_apply_group_adam(kv_handle_t v, kv_handle_t mvl, const float* grad, const void* ids, int64_t n, float lr, float b1p,
+                        float b2p, float b1, float b2, float eps, float l1, float l2, float l21, int version, kv_stream_t stream) {
+  return apply_one(group_adam_call(version, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), v, mvl, nullptr, grad, ids, n, 0, stream, false);
+}
+int kv_apply_group_adam_tok(kv_handle_t v, kv_handle_t mvl, const float* grad, const void* ids, int64_t n, float lr, float b1p,
+                            float b2p, float b1, float b2, float eps, float l1, float l2, float l21, int version,
+                            kv_batch_token_t token, kv_stream_t stream) {
+  return apply_one(group_adam_call(version, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), v, mvl, nullptr, grad, ids, n, token, stream,
+                   false);
+}
+int kv_apply_group_adam_unique(kv_handle_t v, kv_handle_t mvl, const float* grad, const void* ids, int64_t n, float lr,
+                               float b1p, float b2p, float b1, float b2, float eps, float l1, float l2, float l21, int version,
+                               kv_stream_t stream) {
+  return apply_one(group_adam_call(version, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), v, mvl, nullptr, grad, ids, n, 0, stream, true);
+}
+int kv_multi_apply_group_adam(int num_tables, const kv_handle_t* vars, const kv_handle_t* slots, const float* const* grads,
+                              const void* const* ids, const int64_t* ns, float lr, float b1p, float b2p, float b1, float b2,
+                              float eps, float l1, float l2, float l21, int version, kv_stream_t stream) {
+  return multi_apply(group_adam_call(version, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), num_tables, vars, slots, nullptr, grads,
+                     ids, ns, nullptr, stream, false);
+}
+int kv_multi_apply_group_adam_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* slots, const float* const* grads,
+                                  const void* const* ids, const int64_t* ns, float lr, float b1p, float b2p, float b1, float b2,
+                                  float eps, float l1, float l2, float l21, int version, const kv_batch_token_t* tokens,
+                                  kv_stream_t stream) {
+  return multi_apply(group_adam_call(version, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), num_tables, vars, slots, nullptr, grads,
+                     ids, ns, tokens, stream, false);
 }
 int kv_multi_apply_group_adam_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* slots,
                                      const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
                                      float b1p, float b2p, float b1, float b2, float eps, float l1, float l2, float l21,
                                      int version, kv_stream_t stream) {
-  UniqueScope u;
-  return kv_multi_apply_group_adam_tok(num_tables, vars, slots, grads, ids, ns, lr, b1p, b2p, b1, b2, eps, l1, l2, l21, version,
-                                       nullptr, stream);
+  return multi_apply(group_adam_call(version, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), num_tables, vars, slots, nullptr, grads,
+                     ids, ns, nullptr, stream, true);
+}
+
+int kv_apply_adagrad(kv_handle_t v, kv_handle_t acc, float lr, const float* grad, const void* ids, int64_t n, int update_slots,
+                     kv_stream_t stream) {
+  return apply_one(adagrad_call(lr, update_slots), v, acc, nullptr, grad, ids, n, 0, stream, false);
+}
+int kv_apply_adagrad_tok(kv_handle_t v, kv_handle_t acc, float lr, const float* grad, const void* ids, int64_t n,
+                         int update_slots, kv_batch_token_t token, kv_stream_t stream) {
+  return apply_one(adagrad_call(lr, update_slots), v, acc, nullptr, grad, ids, n, token, stream, false);
+}
+int kv_apply_adagrad_unique(kv_handle_t v, kv_handle_t acc, float lr, const float* grad, const void* ids, int64_t n,
+                            int update_slots, kv_stream_t stream) {
+  return apply_one(adagrad_call(lr, update_slots), v, acc, nullptr, grad, ids, n, 0, stream, true);
+}
+int kv_multi_apply_adagrad(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, float lr,
+                           const float* const* grads, const void* const* ids, const int64_t* ns, int update_slots,
+                           kv_stream_t stream) {
+  return multi_apply(adagrad_call(lr, update_slots), num_tables, vars, accums, nullptr, grads, ids, ns, nullptr, stream, false);
+}
+int kv_multi_apply_adagrad_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, float lr,
+                               const float* const* grads, const void* const* ids, const int64_t* ns, int update_slots,
+                               const kv_batch_token_t* tokens, kv_stream_t stream) {
+  return multi_apply(adagrad_call(lr, update_slots), num_tables, vars, accums, nullptr, grads, ids, ns, tokens, stream, false);
 }
 int kv_multi_apply_adagrad_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, float lr,
                                   const float* const* grads, const void* const* ids, const int64_t* ns, int update_slots,
                                   kv_stream_t stream) {
-  UniqueScope u;
-  return kv_multi_apply_adagrad_tok(num_tables, vars, accums, lr, grads, ids, ns, update_slots, nullptr, stream);
+  return multi_apply(adagrad_call(lr, update_slots), num_tables, vars, accums, nullptr, grads, ids, ns, nullptr, stream, true);
+}
+
+int kv_apply_sparse_group_ftrl(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
+                               float lr, float l1, float l2, float l21, float l2s, float lr_power, kv_stream_t stream) {
+  return apply_one(sparse_group_ftrl_call(lr, l1, l2, l21, l2s, lr_power), v, acc, lin, grad, ids, n, 0, stream, false);
+}
+int kv_apply_sparse_group_ftrl_tok(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids,
+                                   int64_t n, float lr, float l1, float l2, float l21, float l2s, float lr_power,
+                                   kv_batch_token_t token, kv_stream_t stream) {
+  return apply_one(sparse_group_ftrl_call(lr, l1, l2, l21, l2s, lr_power), v, acc, lin, grad, ids, n, token, stream, false);
+}
+int kv_apply_sparse_group_ftrl_unique(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids,
+                                      int64_t n, float lr, float l1, float l2, float l21, float l2s, float lr_power,
+                                      kv_stream_t stream) {
+  return apply_one(sparse_group_ftrl_call(lr, l1, l2, l21, l2s, lr_power), v, acc, lin, grad, ids, n, 0, stream, true);
+}
+int kv_multi_apply_sparse_group_ftrl(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
+                                     const kv_handle_t* linears, const float* const* grads, const void* const* ids,
+                                     const int64_t* ns, float lr, float l1, float l2, float l21, float l2s, float lr_power,
+                                     kv_stream_t stream) {
+  return multi_apply(sparse_group_ftrl_call(lr, l1, l2, l21, l2s, lr_power), num_tables, vars, accums, linears, grads, ids, ns,
+                     nullptr, stream, false);
+}
+int kv_multi_apply_sparse_group_ftrl_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
+                                         const kv_handle_t* linears, const float* const* grads, const void* const* ids,
+                                         const int64_t* ns, float lr, float l1, float l2, float l21, float l2s,
+                                         float lr_power, const kv_batch_token_t* tokens, kv_stream_t stream) {
+  return multi_apply(sparse_group_ftrl_call(lr, l1, l2, l21, l2s, lr_power), num_tables, vars, accums, linears, grads, ids, ns,
+                     tokens, stream, false);
 }
 int kv_multi_apply_sparse_group_ftrl_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
                                             const kv_handle_t* linears, const float* const* grads, const void* const* ids,
                                             const int64_t* ns, float lr, float l1, float l2, float l21, float l2s,
                                             float lr_power, kv_stream_t stream) {
-  UniqueScope u;
-  return kv_multi_apply_sparse_group_ftrl_tok(num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l21, l2s, lr_power,
-                                              nullptr, stream);
+  return multi_apply(sparse_group_ftrl_call(lr, l1, l2, l21, l2s, lr_power), num_tables, vars, accums, linears, grads, ids, ns,
+                     nullptr, stream, true);
 }
-int kv_apply_adagrad_unique(kv_handle_t v, kv_handle_t acc, float lr, const float* grad, const void* ids,
-                            int64_t n, int update_slots, kv_stream_t stream) {
-  UniqueScope u;
-  return kv_apply_adagrad_tok(v, acc, lr, grad, ids, n, update_slots, 0, stream);
+
+int kv_apply_ftrl_v2(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
+                     float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
+  return apply_one(ftrl_v2_call(OPT_FTRL_V2, lr, l1, l2, l2s, lr_power), v, acc, lin, grad, ids, n, 0, stream, false);
 }
-int kv_apply_sparse_group_ftrl_unique(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad,
-                                      const void* ids, int64_t n, float lr, float l1, float l2, float l21,
-                                      float l2s, float lr_power, kv_stream_t stream) {
-  UniqueScope u;
-  return kv_apply_sparse_group_ftrl_tok(v, acc, lin, grad, ids, n, lr, l1, l2, l21, l2s, lr_power, 0, stream);
+int kv_apply_ftrl_v2_tok(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
+                         float lr, float l1, float l2, float l2s, float lr_power, kv_batch_token_t token, kv_stream_t stream) {
+  return apply_one(ftrl_v2_call(OPT_FTRL_V2, lr, l1, l2, l2s, lr_power), v, acc, lin, grad, ids, n, token, stream, false);
 }
 int kv_apply_ftrl_v2_unique(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
                             float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
-  UniqueScope u;
-  return apply_ftrl_v2_impl(OPT_FTRL_V2, v, acc, lin, grad, ids, n, lr, l1, l2, l2s, lr_power, 0, stream);
+  return apply_one(ftrl_v2_call(OPT_FTRL_V2, lr, l1, l2, l2s, lr_power), v, acc, lin, grad, ids, n, 0, stream, true);
 }
-int kv_apply_group_ftrl_v2_unique(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids,
-                                  int64_t n, float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
-  UniqueScope u;
-  return apply_ftrl_v2_impl(OPT_GROUP_FTRL_V2, v, acc, lin, grad, ids, n, lr, l1, l2, l2s, lr_power, 0, stream);
+int kv_multi_apply_ftrl_v2(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, const kv_handle_t* linears,
+                           const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float l1, float l2,
+                           float l2s, float lr_power, kv_stream_t stream) {
+  return multi_apply(ftrl_v2_call(OPT_FTRL_V2, lr, l1, l2, l2s, lr_power), num_tables, vars, accums, linears, grads, ids, ns,
+                     nullptr, stream, false);
+}
+int kv_multi_apply_ftrl_v2_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, const kv_handle_t* linears,
+                               const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float l1,
+                               float l2, float l2s, float lr_power, const kv_batch_token_t* tokens, kv_stream_t stream) {
+  return multi_apply(ftrl_v2_call(OPT_FTRL_V2, lr, l1, l2, l2s, lr_power), num_tables, vars, accums, linears, grads, ids, ns,
+                     tokens, stream, false);
 }
 int kv_multi_apply_ftrl_v2_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
                                   const kv_handle_t* linears, const float* const* grads, const void* const* ids,
                                   const int64_t* ns, float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
-  UniqueScope u;
-  return kv_multi_apply_ftrl_v2_tok(num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l2s, lr_power, nullptr, stream);
+  return multi_apply(ftrl_v2_call(OPT_FTRL_V2, lr, l1, l2, l2s, lr_power), num_tables, vars, accums, linears, grads, ids, ns,
+                     nullptr, stream, true);
+}
+
+int kv_apply_group_ftrl_v2(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
+                           float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
+  return apply_one(ftrl_v2_call(OPT_GROUP_FTRL_V2, lr, l1, l2, l2s, lr_power), v, acc, lin, grad, ids, n, 0, stream, false);
+}
+int kv_apply_group_ftrl_v2_tok(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids, int64_t n,
+                               float lr, float l1, float l2, float l2s, float lr_power, kv_batch_token_t token,
+                               kv_stream_t stream) {
+  return apply_one(ftrl_v2_call(OPT_GROUP_FTRL_V2, lr, l1, l2, l2s, lr_power), v, acc, lin, grad, ids, n, token, stream, false);
+}
+int kv_apply_group_ftrl_v2_unique(kv_handle_t v, kv_handle_t acc, kv_handle_t lin, const float* grad, const void* ids,
+                                  int64_t n, float lr, float l1, float l2, float l2s, float lr_power, kv_stream_t stream) {
+  return apply_one(ftrl_v2_call(OPT_GROUP_FTRL_V2, lr, l1, l2, l2s, lr_power), v, acc, lin, grad, ids, n, 0, stream, true);
+}
+int kv_multi_apply_group_ftrl_v2(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums, const kv_handle_t* linears,
+                                 const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float l1,
+                                 float l2, float l2s, float lr_power, kv_stream_t stream) {
+  return multi_apply(ftrl_v2_call(OPT_GROUP_FTRL_V2, lr, l1, l2, l2s, lr_power), num_tables, vars, accums, linears, grads, ids,
+                     ns, nullptr, stream, false);
+}
+int kv_multi_apply_group_ftrl_v2_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
+                                     const kv_handle_t* linears, const float* const* grads, const void* const* ids,
+                                     const int64_t* ns, float lr, float l1, float l2, float l2s, float lr_power,
+                                     const kv_batch_token_t* tokens, kv_stream_t stream) {
+  return multi_apply(ftrl_v2_call(OPT_GROUP_FTRL_V2, lr, l1, l2, l2s, lr_power), num_tables, vars, accums, linears, grads, ids,
+                     ns, tokens, stream, false);
 }
 int kv_multi_apply_group_ftrl_v2_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* accums,
                                         const kv_handle_t* linears, const float* const* grads, const void* const* ids,
                                         const int64_t* ns, float lr, float l1, float l2, float l2s, float lr_power,
                                         kv_stream_t stream) {
-  UniqueScope u;
-  return kv_multi_apply_group_ftrl_v2_tok(num_tables, vars, accums, linears, grads, ids, ns, lr, l1, l2, l2s, lr_power, nullptr,
-                                          stream);
+  return multi_apply(ftrl_v2_call(OPT_GROUP_FTRL_V2, lr, l1, l2, l2s, lr_power), num_tables, vars, accums, linears, grads, ids,
+                     ns, nullptr, stream, true);
 }
 
 // The slot table whose rows the var's index entries remember (Entry::hint): the first slot-0 table an
@@ -2836,7 +2798,7 @@ static int fused_unique_pass(kv_table* t, WsDev& wd, PartArgs& pa, const void* i
   int rc;
   if ((rc = unique_tile_pass(t, wd, pa, ids, counts, n, s))) return rc;
   // (k_papply_uniq: numbering only, nothing of the row geometry is touched — one kernel whatever the table's dim)
-  if ((rc = kvp_launch_papply_ud(&wd, &pa, PA_UNIQUE, (void*)s))) return fail(rc, "unique: no kernel");
+  if ((rc = launch_papply_ud(wd, pa, PA_UNIQUE, s))) return fail(rc, "unique: no kernel");
   return KV_OK;
 }
 
@@ -2876,8 +2838,8 @@ static int dedup_locked(kv_table* t, const void* ids, const float* grad, int64_t
     pa.dd_number = 1;
     pa.epart = wd.epart;
     pa.day_lk = pa.day;
-    if ((rc = kvp_launch_tsum(&pa.tv, &wd, grad, (void*)s, nullptr, 0))) return fail(rc, "tile sums: no kernel for dim %d", t->dim);
-    if ((rc = kvp_launch_papply_ud(&wd, &pa, PA_DEDUP, (void*)s))) return fail(rc, "per-id sums: no kernel for dim %d", t->dim);
+    if ((rc = launch_tsum(pa.tv, wd, grad, s))) return fail(rc, "tile sums: no kernel for dim %d", t->dim);
+    if ((rc = launch_papply_ud(wd, pa, PA_DEDUP, s))) return fail(rc, "per-id sums: no kernel for dim %d", t->dim);
     if (inverse) k_inverse_e<<<nblocks(n, TB, 2048), TB, 0, s>>>(t->ws.pos_ent, wd.ent_b, n, inverse);
   } else {
     index_pass<MODE_UNIQUE>(t, wd, pa, ids, nullptr, n, -1, nullptr, s);
@@ -2945,8 +2907,8 @@ int kv_unsorted_segment_sum(kv_handle_t t, const int32_t* segment_ids, const flo
     launch_ltile_notable(t, pa.tv, wd, segment_ids, n, s, nullptr, true);
     pa.epart = wd.epart;
     pa.day_lk = pa.day;
-    if ((rc = kvp_launch_tsum(&pa.tv, &wd, data, (void*)s, nullptr, 0))) return fail(rc, "tile sums: no kernel for dim %d", t->dim);
-    if ((rc = kvp_launch_papply_ud(&wd, &pa, PA_DEDUP, (void*)s))) return fail(rc, "segment sums: no kernel for dim %d", t->dim);
+    if ((rc = launch_tsum(pa.tv, wd, data, s))) return fail(rc, "tile sums: no kernel for dim %d", t->dim);
+    if ((rc = launch_papply_ud(wd, pa, PA_DEDUP, s))) return fail(rc, "segment sums: no kernel for dim %d", t->dim);
     HIP_TRY(hipGetLastError());
     return KV_OK;
   }
@@ -3980,7 +3942,7 @@ static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_strea
     pa.route_seg = sh->send_pairs; pa.route_slot_of = sh->slot_of; pa.route_overflow = sh->overflow; pa.route_gcount = sh->gcount;
     pa.route_need = sh->need; pa.route_uhint = sh->overflow + 1;   // (the launch's last block writes the headers)
   }
-  if ((rc = kvp_launch_papply_ud(&wd, &pa, PA_UNIQUE, (void*)s))) return fail(rc, "route: no kernel for dim %d", rt->dim);
+  if ((rc = launch_papply_ud(wd, pa, PA_UNIQUE, s))) return fail(rc, "route: no kernel for dim %d", rt->dim);
   rt->batch_serial = ++g_serial;
   rt->batch_n = n;
   sh->route_token = rt->batch_serial;
@@ -4066,17 +4028,14 @@ int kv_shard_apply_route(kv_shard_t sh, const float* grad, kv_stream_t stream) {
   pa.n = sh->n_last;
   pa.epart = wd.epart;
   pa.day_lk = pa.day;
-  if ((rc = kvp_launch_tsum(&pa.tv, &wd, grad, (void*)s, nullptr, 0))) return fail(rc, "tile sums: no kernel for dim %d", rt->dim);
-  if ((rc = kvp_launch_papply_ud(&wd, &pa, PA_DEDUP, (void*)s))) return fail(rc, "gradient pre-sum: no kernel for dim %d", rt->dim);
+  if ((rc = launch_tsum(pa.tv, wd, grad, s))) return fail(rc, "tile sums: no kernel for dim %d", rt->dim);
+  if ((rc = launch_papply_ud(wd, pa, PA_DEDUP, s))) return fail(rc, "gradient pre-sum: no kernel for dim %d", rt->dim);
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
 
 // the owner's half: recv_rows holds the peers' summed gradients, record for record as the lookup served them; the
-// fused apply takes the index that lookup left in the table's workspace.  2 launches.
-// optimizer: 0 GroupAdam V4, 1 GroupAdam V3 (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21),
-// 2 Adagrad (hp = lr, update_slots), 3 SparseGroupFtrl (hp = lr, l1, l2, l21, l2_shrinkage, lr_power; slot1 = linear),
-// 4 FTRL-V2 / 5 group FTRL-V2 (hp = lr, l1, l2, l2_shrinkage, lr_power; slot1 = linear)
+// fused apply takes the index that lookup left in the table's workspace.  2 launches.  optimizer / hp: shard_opt_call
 int kv_shard_apply_serve(kv_shard_t sh, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp, kv_stream_t stream) {
   if (!sh || !hp) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_serve: bad arguments");
   if (sh->serve_token == 0 || sh->serve_token != sh->table->batch_serial)
@@ -4084,21 +4043,9 @@ int kv_shard_apply_serve(kv_shard_t sh, int optimizer, kv_handle_t slot0, kv_han
                                         "(the sharded apply takes over the lookup's index)");
   const int64_t nrec = (int64_t)sh->world * (sh->C + 1);
   SelfScope self(sh->table, sh->self_in_place, (unsigned)sh->rank * (sh->C + 1), sh->C + 1, sh->send_pairs, sh->send_rows);
-  switch (optimizer) {
-    case 0: case 1:
-      return kv_apply_group_adam_tok(sh->table, slot0, sh->recv_rows, sh->recv_pairs, nrec, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5],
-                                     hp[6], hp[7], hp[8], optimizer == 0 ? 4 : 3, sh->serve_token, stream);
-    case 2:
-      return kv_apply_adagrad_tok(sh->table, slot0, hp[0], sh->recv_rows, sh->recv_pairs, nrec, hp[1] != 0.f, sh->serve_token, stream);
-    case 3:
-      return kv_apply_sparse_group_ftrl_tok(sh->table, slot0, slot1, sh->recv_rows, sh->recv_pairs, nrec, hp[0], hp[1], hp[2], hp[3],
-                                            hp[4], hp[5], sh->serve_token, stream);
-    case 4: case 5:
-      return apply_ftrl_v2_impl(optimizer == 4 ? OPT_FTRL_V2 : OPT_GROUP_FTRL_V2, sh->table, slot0, slot1, sh->recv_rows,
-                                sh->recv_pairs, nrec, hp[0], hp[1], hp[2], hp[3], hp[4], sh->serve_token, stream);
-    default:
-      return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_serve: optimizer %d", optimizer);
-  }
+  const OptCall c = shard_opt_call(optimizer, hp);
+  if (c.opt < 0) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_serve: optimizer %d", optimizer);
+  return apply_one(c, sh->table, slot0, slot1, sh->recv_rows, sh->recv_pairs, nrec, sh->serve_token, stream, false);
 }
 
 // whole ops: forked from `stream` onto the shard's own stream (the caller's stream is free for the dense tower);
@@ -4434,7 +4381,7 @@ static int multi_route_impl(const kv_shard_t* shards, const int* todo, int m, co
   // (PA_UNIQUE never reaches the code that depends on the row geometry: one variant serves every dim)
   PartArgs p0 = hd[0].a;
   p0.tv.dim = 4;
-  if ((rc = kvp_launch_papply_ud(&wmax, &p0, PA_UNIQUE, (void*)s, md, m))) return fail(rc, "route: no kernel");
+  if ((rc = launch_papply_ud(wmax, p0, PA_UNIQUE, s, md, m))) return fail(rc, "route: no kernel");
   for (int j = 0; j < m; ++j) {
     kv_shard* sh = shards[todo[j]];
     kv_table* rt = sh->route;
@@ -4533,8 +4480,8 @@ static int multi_presum_impl(const kv_shard_t* shards, const int* todo, int m, c
   HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, (size_t)m * sizeof(MultiDesc), hipMemcpyHostToDevice, s));
   rel.launched = true;
   const MultiDesc* md = reinterpret_cast<const MultiDesc*>(sl->dev);
-  if ((rc = kvp_launch_tsum(&hd[0].a.tv, &wmax, nullptr, (void*)s, md, m))) return fail(rc, "tile sums: no kernel for dim %d", hd[0].a.tv.dim);
-  if ((rc = kvp_launch_papply_ud(&wmax, &hd[0].a, PA_DEDUP, (void*)s, md, m))) return fail(rc, "gradient pre-sum: no kernel for dim %d", hd[0].a.tv.dim);
+  if ((rc = launch_tsum(hd[0].a.tv, wmax, nullptr, s, md, m))) return fail(rc, "tile sums: no kernel for dim %d", hd[0].a.tv.dim);
+  if ((rc = launch_papply_ud(wmax, hd[0].a, PA_DEDUP, s, md, m))) return fail(rc, "gradient pre-sum: no kernel for dim %d", hd[0].a.tv.dim);
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -4730,7 +4677,7 @@ int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int
     auto can = [&](int k) {
       const kv_shard* sh = shards[k];
       return sh->table->key_dtype == KV_DT_INT64 && (long long)sh->world * (sh->C + 1) <= (1ll << 21) && sh->serve_token != 0 &&
-             sh->serve_token == sh->table->batch_serial && sh->table->fused_index && slot0[k] != nullptr && (optimizer < 3 || (slot1 && slot1[k]));
+             sh->serve_token == sh->table->batch_serial && sh->table->fused_index && slot0[k] != nullptr && (!two_slots(optimizer) || (slot1 && slot1[k]));
     };
     if (optimizer >= 0 && optimizer <= 5)
       for (int k = 0; k < ntab; ++k)
@@ -4755,26 +4702,9 @@ int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int
         gp[j] = sh->recv_rows; ip[j] = sh->recv_pairs; nn[j] = (int64_t)sh->world * (sh->C + 1); tok[j] = sh->serve_token;
         self.add(sh->table, sh->self_in_place, (unsigned)sh->rank * (sh->C + 1), sh->C + 1, sh->send_pairs, sh->send_rows);
       }
-      tl_require_reuse = true;   // (the ids are (id, count) records: an apply that rebuilt its index from them would read them as plain ids)
-      int r;
-      switch (optimizer) {
-        case 0: case 1:
-          r = kv_multi_apply_group_adam_tok(m, vs.data(), s0.data(), gp.data(), ip.data(), nn.data(), hp[0], hp[1], hp[2], hp[3], hp[4], hp[5],
-                                            hp[6], hp[7], hp[8], optimizer == 0 ? 4 : 3, tok.data(), w);
-          break;
-        case 2:
-          r = kv_multi_apply_adagrad_tok(m, vs.data(), s0.data(), hp[0], gp.data(), ip.data(), nn.data(), hp[1] != 0.f, tok.data(), w);
-          break;
-        case 4: case 5:
-          r = multi_apply_ftrl_v2_impl(optimizer == 4 ? OPT_FTRL_V2 : OPT_GROUP_FTRL_V2, m, vs.data(), s0.data(), s1.data(), gp.data(),
-                                       ip.data(), nn.data(), hp[0], hp[1], hp[2], hp[3], hp[4], tok.data(), w);
-          break;
-        default:
-          r = kv_multi_apply_sparse_group_ftrl_tok(m, vs.data(), s0.data(), s1.data(), gp.data(), ip.data(), nn.data(), hp[0], hp[1], hp[2],
-                                                   hp[3], hp[4], hp[5], tok.data(), w);
-          break;
-      }
-      tl_require_reuse = false;
+      // (require_reuse: the ids are (id, count) records — an apply that rebuilt its index from them would read them as plain ids)
+      const int r = multi_apply(shard_opt_call(optimizer, hp), m, vs.data(), s0.data(), s1.data(), gp.data(), ip.data(), nn.data(),
+                                tok.data(), w, false, true);
       note(r);
       for (int k : grp) applied[k] = 1;
     }
