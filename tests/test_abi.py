@@ -68,6 +68,20 @@ def test_library_reads_no_environment_variable():
   assert not bad, bad
 
 
+def test_library_keeps_no_thread_local_op_state():
+  """What an op does is decided by its arguments, never by per-thread state another function set: the only thread_local
+  of libkvhip.so's sources is g_err, the per-thread error message the ABI documents (kv_last_error)."""
+  csrc = os.path.join(ROOT, "tfplus_amd", "csrc")
+  hits = []
+  for f in sorted(os.listdir(csrc)):
+    if f.endswith((".hip", ".h", ".cc", ".cpp")):
+      for line in open(os.path.join(csrc, f), errors="replace"):
+        if "thread_local" in line:
+          hits.append((f, line.strip()))
+  assert len(hits) == 1, hits
+  assert hits[0][0] == "kvhip.hip" and re.search(r"\bg_err\s*;", hits[0][1]), hits
+
+
 @pytest.mark.gpu
 def test_c_host_program_over_the_abi(tmp_path):
   """A C++ program that includes only include/kvhip.h + HIP (no Python, no torch) drives the table."""

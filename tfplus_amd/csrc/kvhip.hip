@@ -727,27 +727,13 @@ int ensure_workspace(kv_table* t, long long n, bool need_part, hipStream_t s) {
   return KV_OK;
 }
 
-bool fused_ok(int D);
-bool fused_tab(const kv_table* t);
+// The sharded owner ops read a rank's OWN exchange segment where it was written: records [lo, lo + len) of the buffers the
+// op reads come from `ids` / `grad` (the send buffers) instead.  Passed by kv_shard_lookup_serve / kv_shard_apply_serve and
+// the grouped serve blocks of kv_multi_shard_lookup / kv_multi_shard_apply (shard_self; one per table in the batched ones)
+// down to the ws_view of the lookup or apply that serves them; every other op passes none.  The default is "no segment".
+struct SelfSegment { unsigned lo = 0, len = 0; const void* ids = nullptr; const float* grad = nullptr; };
 
-// The sharded owner ops (kv_shard_lookup_serve / kv_shard_apply_serve) read a rank's OWN exchange segment where it was
-// written: records [lo, lo + len) of the buffers the calling thread's next op on `table` reads come from `ids` / `grad`
-// (the send buffers) instead.  Per thread, so another thread's op on the same table sees nothing of it.
-struct SelfSegment { const kv_table* table = nullptr; unsigned lo = 0, len = 0; const void* ids = nullptr; const float* grad = nullptr; };
-static thread_local std::vector<SelfSegment> tl_selfs;   // (empty outside the sharded owner ops; several tables in the batched ones)
-struct SelfScope {
-  size_t mark;
-  SelfScope() : mark(tl_selfs.size()) {}
-  SelfScope(const kv_table* t, bool on, unsigned lo, unsigned len, const void* ids, const float* grad) : mark(tl_selfs.size()) {
-    add(t, on, lo, len, ids, grad);
-  }
-  void add(const kv_table* t, bool on, unsigned lo, unsigned len, const void* ids, const float* grad) {
-    if (on) tl_selfs.push_back(SelfSegment{t, lo, len, ids, grad});
-  }
-  ~SelfScope() { tl_selfs.resize(mark); }
-};
-
-WsDev ws_view(kv_table* t, long long n) {
+WsDev ws_view(kv_table* t, long long n, const SelfSegment* self = nullptr) {
   Workspace& w = t->ws;
   WsDev d;
   d.ent_key = w.ent_key; d.ent_a = w.ent_a; d.ent_b = w.ent_b; d.ent_base = w.ent_base; d.ent_rec = w.ent_rec;
@@ -773,8 +759,7 @@ WsDev ws_view(kv_table* t, long long n) {
   d.epart = w.epart;
   d.pos_ent = nullptr;
   d.self_lo = d.self_len = 0; d.ids_self = nullptr; d.grad_self = nullptr;
-  for (const SelfSegment& x : tl_selfs)
-    if (x.table == t) { d.self_lo = x.lo; d.self_len = x.len; d.ids_self = x.ids; d.grad_self = x.grad; }
+  if (self) { d.self_lo = self->lo; d.self_len = self->len; d.ids_self = self->ids; d.grad_self = self->grad; }
   return d;
 }
 
@@ -1012,53 +997,37 @@ int report_deferred_error(kv_table* t, hipStream_t s) {
   return flagged_error(t, code, s);
 }
 
-// Ops of one table run in the order they were issued, whatever their streams: the per-table workspace
-// and the table itself are shared by every op (the reference's table locks cover execution, not just
-// enqueue, training_ops.cc:96-184).  Same stream as the last op: nothing to do.  Another stream: it first
-// waits for everything the previous stream had been given.
 // launches a lookup's pending partition pass (see kv_table::part_pending) on stream s
-int flush_part(kv_table* t, hipStream_t s);
+int flush_part(kv_table* t, hipStream_t s) {
+  if (!t->part_pending) return KV_OK;
+  t->part_pending = false;
+  WsDev wd; PartArgs pa;
+  std::memcpy(&wd, t->pend_wd, sizeof wd);
+  std::memcpy(&pa, t->pend_pa, sizeof pa);
+  ProfScope ps(t, KV_PROF_LOOKUP_PART, s);
+  // (k_part2 reads the tiles' entries alone — also behind a sharded owner lookup whose own segment stayed in the send
+  //  buffers; an apply that still comes with the batch's token runs k_papply PA_NONE over the same entries)
+  launch_part2(wd, pa, s);
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
 // ---- slot mirrors: the host side -------------------------------------------------------------------------------------
 // Invariant: the slot table's own records are up to date for every key whose var-row mirror is not (valid in the current
 // epoch AND dirty).  Mirrors are written only by the lean apply of (var, slot) — k_papply / k_uapply with use_mirror — and
 // read only by it.  EVERY other op that enters either table first ends the epoch (mirror_end_epoch: flush the dirty
 // copies, one kernel over the var's rows, then epoch + 1 — which invalidates every copy at once), so it sees, and may
 // change, the authoritative records; the keys' next lean apply finds no valid mirror, takes the general path once and
-// leaves a fresh clean copy (finish_key).  The ops that keep the epoch name their tables in tl_mirror_keep while they
-// enter: the training / inference lookups on the var (they touch var records and rows only), the GroupAdam and Adagrad
-// applies on (var, slot), single and batched, and the ops that only borrow a table's workspace.
-static thread_local kv_table* tl_mirror_keep[2] = {nullptr, nullptr};   // [0]: kept in its VAR role, [1]: kept in its SLOT role
-static thread_local kv_table* const* tl_mirror_keep_vars = nullptr;      // ... a batched op's tables in their VAR role
-static thread_local int tl_mirror_keep_nvars = 0;
-static thread_local kv_table* const* tl_mirror_keep_slots = nullptr;     // ... a batched apply's first slot tables, in their SLOT role
-static thread_local int tl_mirror_keep_nslots = 0;
-struct MirrorKeep {   // (scopes nest: the previous names come back)
-  kv_table* p0; kv_table* p1; kv_table* const* pv; int pn; kv_table* const* ps; int psn;
-  void save() {
-    p0 = tl_mirror_keep[0]; p1 = tl_mirror_keep[1]; pv = tl_mirror_keep_vars; pn = tl_mirror_keep_nvars;
-    ps = tl_mirror_keep_slots; psn = tl_mirror_keep_nslots;
-  }
-  explicit MirrorKeep(kv_table* as_var, kv_table* as_slot = nullptr) { save(); tl_mirror_keep[0] = as_var; tl_mirror_keep[1] = as_slot; }
-  MirrorKeep(kv_table* const* vars, int n, kv_table* const* slots = nullptr, int nslots = 0) {
-    save(); tl_mirror_keep_vars = vars; tl_mirror_keep_nvars = n; tl_mirror_keep_slots = slots; tl_mirror_keep_nslots = nslots;
-  }
-  ~MirrorKeep() {
-    tl_mirror_keep[0] = p0; tl_mirror_keep[1] = p1; tl_mirror_keep_vars = pv; tl_mirror_keep_nvars = pn;
-    tl_mirror_keep_slots = ps; tl_mirror_keep_nslots = psn;
-  }
+// leaves a fresh clean copy (finish_key).  An op that keeps the epoch says so where it enters the table (enter_op,
+// hand_over, MultiLock::enter), with the role(s) it keeps the table in; KEEP_NONE, the default, ends it.  The
+// keepers: the training / inference lookups on the var (they touch var records and rows only), the GroupAdam and Adagrad
+// applies on (var, slot), single and batched, and the ops that only borrow a table's workspace.  A role, not a table, is
+// kept: a var entered as KEEP_VAR that is also another var's slot table still ends that other pair's epoch.
+enum : unsigned {
+  KEEP_NONE = 0u,
+  KEEP_VAR = 1u,    // the table's own epoch (it is a pair's var) goes on
+  KEEP_SLOT = 2u,   // the epoch of the var this table is the slot table of goes on
 };
-static bool mirror_kept_as_var(const kv_table* t) {
-  if (t == tl_mirror_keep[0]) return true;
-  for (int i = 0; i < tl_mirror_keep_nvars; ++i)
-    if (tl_mirror_keep_vars[i] == t) return true;
-  return false;
-}
-static bool mirror_kept_as_slot(const kv_table* t) {
-  if (t == tl_mirror_keep[1]) return true;
-  for (int i = 0; i < tl_mirror_keep_nslots; ++i)
-    if (tl_mirror_keep_slots[i] == t) return true;
-  return false;
-}
 // held: the table of the pair whose lock the caller holds (the var itself, or its slot table): the views come from there
 void mirror_end_epoch(kv_table* var, hipStream_t s, const kv_table* held) {
   if (!var->mirror_slot) return;
@@ -1086,9 +1055,9 @@ static void mirror_snapshot(kv_table* v, kv_table* sl) {
 // the entry hook of hand_over / join_side.  Under a stream capture the flush would be RECORDED, not run, and a replay would
 // carry the epoch of its capture: a table that is captured gives up its mirrors beforehand (kv_prepare_capture ->
 // mirror_ban); an op that would have to end an epoch inside a capture is refused.
-int mirror_on_entry(kv_table* t, hipStream_t s) {
+int mirror_on_entry(kv_table* t, hipStream_t s, unsigned keep) {
   if (!t->mirror_var && !t->mirror_slot) return KV_OK;
-  const bool end_slot = t->mirror_var && !mirror_kept_as_slot(t), end_var = t->mirror_slot && !mirror_kept_as_var(t);
+  const bool end_slot = t->mirror_var && !(keep & KEEP_SLOT), end_var = t->mirror_slot && !(keep & KEEP_VAR);
   if ((end_slot || end_var) && stream_is_capturing(s))
     return fail(KV_FAILED_PRECONDITION, "this table is half of a (var, slot) pair whose optimizer applies keep the slot records' "
                                         "frequency words in the var's rows between ops; call kv_prepare_capture on it (outside the "
@@ -1123,7 +1092,7 @@ bool mirror_pair(kv_table* v, kv_table* sl, hipStream_t s) {
 
 // Does this apply of (v, s0) work on the var rows' slot mirrors?  lean: the launch is k_papply / k_uapply (their lean
 // update is the only code that reads or writes a mirror).  Otherwise the apply reads and writes the slot table's own
-// records: the epoch ends first (the caller entered both tables under MirrorKeep, so nothing has ended it yet).
+// records: the epoch ends first (the caller entered the var as KEEP_VAR and the slot as KEEP_SLOT, so nothing has ended it yet).
 template <int OPT>
 static int mirror_decide(kv_table* v, kv_table* s0, PartArgs& pa, bool lean, hipStream_t s) {
   pa.use_mirror = 0; pa.mirror_epoch = 0u;
@@ -1146,50 +1115,53 @@ static int mirror_decide(kv_table* v, kv_table* s0, PartArgs& pa, bool lean, hip
   return KV_OK;
 }
 
+// Ops of one table run in the order they were issued, whatever their streams: the per-table workspace
+// and the table itself are shared by every op (the reference's table locks cover execution, not just
+// enqueue, training_ops.cc:96-184).  Same stream as the last op: nothing to do.  Another stream: it first
+// waits for everything the previous stream had been given, and is the table's last stream from there on.
+static int hop_behind_last(kv_table* t, hipStream_t s) {
+  if (!t->has_last || t->last_stream == s) return KV_OK;
+  HIP_TRY(hipEventRecord(t->last_done, t->last_stream));
+  HIP_TRY(hipStreamWaitEvent(s, t->last_done, 0));
+  t->last_stream = s;
+  return KV_OK;
+}
+
+// keep: the mirror role(s) the op keeps the table in (KEEP_*; mirror_on_entry)
+// settle == false: the caller is the optimizer apply that takes the table's pending partition pass over
 // mutates == false: a read-only op (the inference gathers): ordered like any other op of the table — behind the table's
 // last op whatever its stream, and the next op behind it — but it does not move op_serial (a two-phase export may go on)
-// settle == false: the caller is the optimizer apply that takes the table's pending partition pass over
-int hand_over(kv_table* t, hipStream_t s, bool settle = true, bool mutates = true) {
+int hand_over(kv_table* t, hipStream_t s, unsigned keep = KEEP_NONE, bool settle = true, bool mutates = true) {
+  int rc;
   if (t->part_pending && settle) {   // (an apply that takes the batch over runs it itself, behind the stream hand-over below)
-    int rc;
-    if (t->has_last && t->last_stream != s) {
-      HIP_TRY(hipEventRecord(t->last_done, t->last_stream));
-      HIP_TRY(hipStreamWaitEvent(s, t->last_done, 0));
-      t->last_stream = s;
-    }
-    if ((rc = flush_part(t, s))) return rc;
+    if ((rc = hop_behind_last(t, s)) || (rc = flush_part(t, s))) return rc;
   }
-  if (t->has_last && t->last_stream != s) {
-    HIP_TRY(hipEventRecord(t->last_done, t->last_stream));
-    HIP_TRY(hipStreamWaitEvent(s, t->last_done, 0));
-  }
+  if ((rc = hop_behind_last(t, s))) return rc;
   t->last_stream = s;
   t->has_last = true;
   if (mutates) ++t->op_serial;
-  return mirror_on_entry(t, s);
+  return mirror_on_entry(t, s, keep);
 }
 
 // ops that read a table without the full hand_over (no workspace, no row-set change): the last lookup's pending
-// partition pass (it may still have rows to initialise) is settled first
+// partition pass (it may still have rows to initialise) is settled first.  None of them keeps a mirror epoch.
 int join_side(kv_table* t, hipStream_t s) {
+  int rc;
   if (t->part_pending) {
-    if (t->has_last && t->last_stream != s) {
-      HIP_TRY(hipEventRecord(t->last_done, t->last_stream));
-      HIP_TRY(hipStreamWaitEvent(s, t->last_done, 0));
-      t->last_stream = s;
-    }
-    const int rc = flush_part(t, s);
-    if (rc) return rc;
+    if ((rc = hop_behind_last(t, s)) || (rc = flush_part(t, s))) return rc;
   }
   // An epoch of slot mirrors that ends here flushes copies the last lean apply wrote — on the stream of t's last op (an apply
   // enters both tables; anything later on t has ended the epoch already): the flush must run behind it.  (A flush that
   // overtook the apply would miss its copies, and the epoch number that ends with it would orphan them for good.)
-  if ((t->mirror_var || t->mirror_slot) && t->has_last && t->last_stream != s) {
-    HIP_TRY(hipEventRecord(t->last_done, t->last_stream));
-    HIP_TRY(hipStreamWaitEvent(s, t->last_done, 0));
-    t->last_stream = s;
-  }
-  return mirror_on_entry(t, s);
+  if ((t->mirror_var || t->mirror_slot) && (rc = hop_behind_last(t, s))) return rc;
+  return mirror_on_entry(t, s, KEEP_NONE);
+}
+
+// How an op enters a table it holds the lock of: the deferred error of the table's last batch, then the hand-over.
+int enter_op(kv_table* t, hipStream_t s, unsigned keep = KEEP_NONE, bool settle = true, bool mutates = true) {
+  int rc;
+  if ((rc = report_deferred_error(t, s))) return rc;
+  return hand_over(t, s, keep, settle, mutates);
 }
 
 // locks tables in address order like MaybeLockVariableInputMutexesInOrder (training_ops.cc:96-184)
@@ -1202,20 +1174,17 @@ struct MultiLock {
     for (auto* t : ts) t->mu.lock();
   }
   ~MultiLock() { for (auto it = ts.rbegin(); it != ts.rend(); ++it) (*it)->mu.unlock(); }
+  // keep(t): the mirror role(s) table t is kept in (KEEP_*)
   // later: this table's pending partition pass is taken over by the caller (the optimizer apply of that batch)
-  int enter(hipStream_t s, kv_table* later = nullptr) {
+  template <class Keep>
+  int enter(hipStream_t s, Keep keep, kv_table* later = nullptr) {
     int rc;
     for (auto* t : ts)
-      if ((rc = report_deferred_error(t, s)) || (rc = hand_over(t, s, t != later))) return rc;
+      if ((rc = enter_op(t, s, keep(t), t != later))) return rc;
     return KV_OK;
   }
+  int enter(hipStream_t s) { return enter(s, [](const kv_table*) { return (unsigned)KEEP_NONE; }); }
 };
-// the same for ops on one table (the caller holds t->mu)
-int enter_op(kv_table* t, hipStream_t s) {
-  int rc;
-  if ((rc = report_deferred_error(t, s))) return rc;
-  return hand_over(t, s);
-}
 
 // The index of a batch (kv_kernels.h): tile pass, partition pass, sorted position list.
 //   MODE_LOOKUP   with out != nullptr: the training lookup (rows copied by the kernel that builds the list)
@@ -1238,20 +1207,6 @@ void index_pass(kv_table* t, const WsDev& wd, const PartArgs& pa, const void* id
   // plain gather, 36 instead of 48 us at configs[1]
   if (MODE == MODE_LOOKUP && out) launch_gather(pa.tv, wd, out, n, s, nullptr, 0, file_order);
   else launch_order(pa.tv, wd, n, s);
-}
-
-int flush_part(kv_table* t, hipStream_t s) {
-  if (!t->part_pending) return KV_OK;
-  t->part_pending = false;
-  WsDev wd; PartArgs pa;
-  std::memcpy(&wd, t->pend_wd, sizeof wd);
-  std::memcpy(&pa, t->pend_pa, sizeof pa);
-  ProfScope ps(t, KV_PROF_LOOKUP_PART, s);
-  // (k_part2 reads the tiles' entries alone — also behind a sharded owner lookup whose own segment stayed in the send
-  //  buffers; an apply that still comes with the batch's token runs k_papply PA_NONE over the same entries)
-  launch_part2(wd, pa, s);
-  HIP_TRY(hipGetLastError());
-  return KV_OK;
 }
 
 // partitions of an entry-list index pass over n ids (wd.P, wd.pshift; remembered in t->index_P)
@@ -1636,26 +1591,10 @@ int kv_get_meta(kv_handle_t t, const int64_t* ids, int64_t n, uint32_t* fw, uint
   return KV_OK;
 }
 
+// seg_cap + self: the (id, count) records of a sharded owner lookup, in fixed-capacity segments (kv_shard_lookup_serve)
 static int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, float* out,
-                                 kv_stream_t stream, int pairs, kv_batch_token_t* token, unsigned seg_cap = 0);
-
-int kv_gather_or_insert(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, float* out,
-                        kv_stream_t stream) {
-  return gather_or_insert_impl(t, ids, counts, n, out, stream, 0, nullptr);
-}
-int kv_gather_or_insert_tok(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, float* out,
-                            kv_batch_token_t* token, kv_stream_t stream) {
-  if (token) *token = 0;
-  return gather_or_insert_impl(t, ids, counts, n, out, stream, 0, token);
-}
-int kv_gather_or_insert_pairs(kv_handle_t t, const int64_t* id_count_pairs, int64_t n, float* out,
-                              kv_stream_t stream) {
-  if (t && t->key_dtype == KV_DT_INT32) return fail(KV_INVALID_ARGUMENT, "id/count pairs carry int64 ids");
-  return gather_or_insert_impl(t, id_count_pairs, nullptr, n, out, stream, 1, nullptr);
-}
-
-static int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, float* out,
-                                 kv_stream_t stream, int pairs, kv_batch_token_t* token, unsigned seg_cap) {
+                                 kv_stream_t stream, int pairs, kv_batch_token_t* token, unsigned seg_cap = 0,
+                                 const SelfSegment* self = nullptr) {
   int rc;
   if ((rc = check_table(t))) return rc;
   if (n == 0) return KV_OK;  // kv_variable_ops.cc:530-532
@@ -1665,9 +1604,8 @@ static int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* 
     return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
   DeviceGuard dg(t->device);
   std::lock_guard<std::mutex> l(t->mu);
-  MirrorKeep mk(t);   // a training lookup touches the var's rows and records, never a slot record or a mirror
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = enter_op(t, s))) return rc;
+  if ((rc = enter_op(t, s, KEEP_VAR))) return rc;   // a training lookup touches the var's rows and records, never a slot record or a mirror
   // any batch length: chunks of 2^21 ids are looked up one after another (same semantics as one
   // pass: the frequency adds saturate identically and rows are inserted by the first chunk)
   // the entry-list pipeline indexes a batch of up to FUSED_MAX_N ids in one pass; the sorted-position one 2^21
@@ -1682,7 +1620,7 @@ static int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* 
     if ((rc = ensure_capacity(t, m, s))) return rc;
     if ((rc = ensure_workspace(t, m, false, s))) return rc;
     const TableDev td = dev_view(t);
-    WsDev wd = ws_view(t, m);
+    WsDev wd = ws_view(t, m, self);
     wd.seg_cap = seg_cap;
     PartArgs pa{};
     pa.tv = td; pa.ts0 = td; pa.ts1 = td;
@@ -1700,6 +1638,21 @@ static int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* 
     if (token) *token = t->batch_serial;
   }
   return KV_OK;
+}
+
+int kv_gather_or_insert(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, float* out,
+                        kv_stream_t stream) {
+  return gather_or_insert_impl(t, ids, counts, n, out, stream, 0, nullptr);
+}
+int kv_gather_or_insert_tok(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, float* out,
+                            kv_batch_token_t* token, kv_stream_t stream) {
+  if (token) *token = 0;
+  return gather_or_insert_impl(t, ids, counts, n, out, stream, 0, token);
+}
+int kv_gather_or_insert_pairs(kv_handle_t t, const int64_t* id_count_pairs, int64_t n, float* out,
+                              kv_stream_t stream) {
+  if (t && t->key_dtype == KV_DT_INT32) return fail(KV_INVALID_ARGUMENT, "id/count pairs carry int64 ids");
+  return gather_or_insert_impl(t, id_count_pairs, nullptr, n, out, stream, 1, nullptr);
 }
 
 int kv_lookup_sparse(kv_handle_t t, const void* ids, const void* segment_ids, int segment_dtype,
@@ -1721,9 +1674,8 @@ int kv_lookup_sparse(kv_handle_t t, const void* ids, const void* segment_ids, in
     return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
   DeviceGuard dg(t->device);
   std::lock_guard<std::mutex> l(t->mu);
-  MirrorKeep mk(t);   // the table's own rows and records only
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = enter_op(t, s))) return rc;
+  if ((rc = enter_op(t, s, KEEP_VAR))) return rc;   // the table's own rows and records only
   const int D = t->dim;
   if (n == 0) {  // every segment is empty
     HIP_TRY(hipMemsetAsync(out, 0, (size_t)num_segments * D * sizeof(float), s));
@@ -1811,8 +1763,10 @@ int kv_gather_or_zeros(kv_handle_t t, const void* ids, int64_t n, float* out, kv
   DeviceGuard dg(t->device);
   std::lock_guard<std::mutex> l(t->mu);
   hipStream_t s = (hipStream_t)stream;
-  MirrorKeep mk(t);   // (the inference gather reads rows and flags of THIS table: as a var it leaves the mirrors alone)
-  if ((rc = hand_over(t, s, true, false))) return rc;   // a read: behind the table's last op on whatever stream, no serial bump
+  // a read: behind the table's last op on whatever stream, no serial bump.  It reads rows and flags of THIS table: as a var
+  // it leaves the mirrors alone.  (hand_over, not enter_op: unlike kv_batch_gather_or_zeros this op does not report the
+  // deferred error of the table's last batch — the next op that does will)
+  if ((rc = hand_over(t, s, KEEP_VAR, true, false))) return rc;
   const TableDev td = dev_view(t);
   const int q = t->dim / 4;
   const bool wave_shaped = (t->dim & 3) == 0 && q >= 1 && q <= 64 && (q & (q - 1)) == 0;
@@ -1908,11 +1862,10 @@ int kv_batch_gather_or_zeros(int num_tables, const kv_handle_t* tables, const vo
   DeviceGuard dg(device);
   hipStream_t s = (hipStream_t)stream;
   MultiLock lock(std::vector<kv_table*>(tables, tables + num_tables));
-  MirrorKeep mk(tables, num_tables);
   // every table is read on the op's stream: behind whatever its own last op queued on another stream (an optimizer
-  // apply that has not finished), and its next op behind this read
+  // apply that has not finished), and its next op behind this read (rows and flags only: as vars they keep their mirrors)
   for (kv_table* tb : lock.ts)
-    if ((rc = report_deferred_error(tb, s)) || (rc = hand_over(tb, s, true, false))) return rc;
+    if ((rc = enter_op(tb, s, KEEP_VAR, true, false))) return rc;
   BatchStage& st = g_stage[device][0];
   StageSlot* sl = nullptr;
   if ((rc = stage_acquire(st, (size_t)num_tables * sizeof(BatchGatherDesc), &sl))) return rc;
@@ -1937,8 +1890,6 @@ int kv_batch_gather_or_zeros(int num_tables, const kv_handle_t* tables, const vo
   return KV_OK;
 }
 
-static bool claim_slot(kv_table* v, kv_table* sl, hipStream_t s);
-
 // ---- many tables, one launch per pipeline stage (26-feature CTR step: 5 launches, not 130) ------
 // All tables: same device, same dim, same key dtype; each batch <= 2^21 ids.
 static int multi_common(int num_tables, const kv_handle_t* tables, const void* const* ids, const int64_t* ns) {
@@ -1962,24 +1913,12 @@ static int multi_common(int num_tables, const kv_handle_t* tables, const void* c
   return KV_OK;
 }
 
-int kv_multi_gather_or_insert(int num_tables, const kv_handle_t* tables, const void* const* ids,
-                              const int32_t* const* counts, const int64_t* ns, float* const* outs,
-                              kv_stream_t stream) {
-  return kv_multi_gather_or_insert_tok(num_tables, tables, ids, counts, ns, outs, nullptr, stream);
-}
-
-// ids_kind 2 + seg_caps: the (id, count) records of the sharded owner lookups, in fixed-capacity segments (kv_multi_shard_lookup)
+// ids_kind 2 + seg_caps + selfs (one per table): the (id, count) records of the sharded owner lookups, in fixed-capacity
+// segments (kv_multi_shard_lookup)
 static int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const void* const* ids,
                              const int32_t* const* counts, const int64_t* ns, float* const* outs,
-                             kv_batch_token_t* tokens, kv_stream_t stream, int ids_kind, const unsigned* seg_caps);
-int kv_multi_gather_or_insert_tok(int num_tables, const kv_handle_t* tables, const void* const* ids,
-                                  const int32_t* const* counts, const int64_t* ns, float* const* outs,
-                                  kv_batch_token_t* tokens, kv_stream_t stream) {
-  return multi_lookup_impl(num_tables, tables, ids, counts, ns, outs, tokens, stream, -1, nullptr);
-}
-static int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const void* const* ids,
-                             const int32_t* const* counts, const int64_t* ns, float* const* outs,
-                             kv_batch_token_t* tokens, kv_stream_t stream, int ids_kind, const unsigned* seg_caps) {
+                             kv_batch_token_t* tokens, kv_stream_t stream, int ids_kind, const unsigned* seg_caps,
+                             const SelfSegment* selfs) {
   int rc;
   if (tokens && num_tables > 0) std::memset(tokens, 0, (size_t)num_tables * sizeof(kv_batch_token_t));
   if ((rc = multi_common(num_tables, tables, ids, ns))) return rc;
@@ -1988,8 +1927,7 @@ static int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const vo
   DeviceGuard dg(device);
   hipStream_t s = (hipStream_t)stream;
   MultiLock lock(std::vector<kv_table*>(tables, tables + num_tables));
-  MirrorKeep mk(tables, num_tables);   // lookups: the tables' own rows and records only
-  if ((rc = lock.enter(s))) return rc;
+  if ((rc = lock.enter(s, [](const kv_table*) { return (unsigned)KEEP_VAR; }))) return rc;   // lookups: the tables' own rows and records only
   long long nmax = 0;
   for (int i = 0; i < num_tables; ++i) {
     tables[i]->batch_serial = 0;
@@ -2008,7 +1946,7 @@ static int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const vo
   for (int i = 0; i < num_tables; ++i) {
     MultiDesc& d = hd[i];
     std::memset(&d, 0, sizeof d);
-    d.w = ws_view(tables[i], std::max<long long>(ns[i], 1));
+    d.w = ws_view(tables[i], std::max<long long>(ns[i], 1), selfs ? &selfs[i] : nullptr);
     if (seg_caps) d.w.seg_cap = seg_caps[i];
     if (fused_tab(tables[i])) { d.w.P = fused_default_P(std::max<long long>(ns[i], 1)); d.w.pshift = 64 - ilog2(d.w.P); }
     d.a.tv = dev_view(tables[i]); d.a.ts0 = d.a.tv; d.a.ts1 = d.a.tv;
@@ -2056,17 +1994,40 @@ static int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const vo
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
+int kv_multi_gather_or_insert_tok(int num_tables, const kv_handle_t* tables, const void* const* ids,
+                                  const int32_t* const* counts, const int64_t* ns, float* const* outs,
+                                  kv_batch_token_t* tokens, kv_stream_t stream) {
+  return multi_lookup_impl(num_tables, tables, ids, counts, ns, outs, tokens, stream, -1, nullptr, nullptr);
+}
+int kv_multi_gather_or_insert(int num_tables, const kv_handle_t* tables, const void* const* ids,
+                              const int32_t* const* counts, const int64_t* ns, float* const* outs,
+                              kv_stream_t stream) {
+  return kv_multi_gather_or_insert_tok(num_tables, tables, ids, counts, ns, outs, nullptr, stream);
+}
 
 }  // extern "C"
 
+// The slot table whose rows the var's index entries remember (Entry::hint): the first slot-0 table an
+// optimizer uses with the var, or the one kv_attach_slot names.  Hints of a table that was cleared since
+// (import) mean nothing any more and are forgotten; another table simply goes without hints.
+static bool claim_slot(kv_table* v, kv_table* sl, hipStream_t s) {
+  if (v->slot_uid == sl->uid && v->slot_gen == sl->gen) return true;
+  if (v->slot_uid != 0 && v->slot_uid != sl->uid) return false;
+  if (v->slot_uid == sl->uid)   // same table, cleared since
+    k_clear_hints<<<nblocks((long long)v->cap + 1, TB, 8192), TB, 0, s>>>(v->entries, v->cap + 1);
+  v->slot_uid = sl->uid;
+  v->slot_gen = sl->gen;
+  return true;
+}
+
 // shared body of the batched optimizer ops: slots1 only for the FTRL family (linear); slot_mult = slot dim / var dim.
 // unique and the capture rule: as apply_common's.  require_reuse: the batched sharded apply — the tables must still hold
-// their lookups' indexes.
+// their lookups' indexes — and, selfs (one per table), read their ranks' own segments in place.
 template <int OPT>
 static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_handle_t* slots0,
                               const kv_handle_t* slots1, int slot_mult, const float* const* grads,
                               const void* const* ids, const int64_t* ns, const OptArgs& hp, kv_stream_t stream,
-                              const kv_batch_token_t* tokens, bool unique, bool require_reuse) {
+                              const kv_batch_token_t* tokens, bool unique, bool require_reuse, const SelfSegment* selfs) {
   int rc;
   if ((rc = multi_common(num_tables, vars, ids, ns))) return rc;
   if ((rc = check_same_shape(num_tables, slots0, "slot tables"))) return rc;
@@ -2101,13 +2062,17 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   MultiLock lock(all);
   // GroupAdam / Adagrad over pairs (var_i, slot_i): the lean update works on the var rows' slot mirrors (mirror_decide per
   // table below); FTRL reads and writes the slot tables' own records: its entry ends the tables' epochs
-  MirrorKeep mk(vars, !two_slots(OPT) ? num_tables : 0, slots0, !two_slots(OPT) ? num_tables : 0);
+  auto keep = [&](const kv_table* tb) -> unsigned {
+    unsigned k = KEEP_NONE;
+    if (!two_slots(OPT))
+      for (int i = 0; i < num_tables; ++i) k |= (vars[i] == tb ? KEEP_VAR : KEEP_NONE) | (slots0[i] == tb ? KEEP_SLOT : KEEP_NONE);
+    return k;
+  };
   if (unique && fused_ok(D) && !stream_is_capturing(s)) {
     // The caller promises that no table's ids hold an id twice (kv_multi_apply_*_unique; kv_uapply.h): ONE launch for all
     // tables, one lane group per id (grid.y = table).  Pending lookup passes are settled first.
     long long nmax = 0;
-    for (kv_table* tb : lock.ts)
-      if ((rc = report_deferred_error(tb, s)) || (rc = hand_over(tb, s))) return rc;
+    if ((rc = lock.enter(s, keep))) return rc;
     for (int i = 0; i < num_tables; ++i) {
       if ((rc = ensure_capacity(vars[i], ns[i], s)) || (rc = ensure_capacity(slots0[i], ns[i], s)) ||
           (slots1 && (rc = ensure_capacity(slots1[i], ns[i], s))))
@@ -2162,10 +2127,10 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
     }
   if (!reuse) pa_reuse = false;
   for (kv_table* tb : lock.ts) {
-    bool keep = false;
+    bool taken = false;   // this table's pending pass is taken over by k_papply_multi
     if (pa_reuse)
-      for (int i = 0; i < num_tables; ++i) keep = keep || (vars[i] == tb && ns[i] > 0);
-    if ((rc = report_deferred_error(tb, s)) || (rc = hand_over(tb, s, !keep))) return rc;
+      for (int i = 0; i < num_tables; ++i) taken = taken || (vars[i] == tb && ns[i] > 0);
+    if ((rc = enter_op(tb, s, keep(tb), !taken))) return rc;
   }
   // (a table whose pass was pending while another's was not: hand_over has just settled it — the batch's entries stay valid)
   long long nmax = 0;
@@ -2189,7 +2154,7 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   for (int i = 0; i < num_tables; ++i) {
     MultiDesc& d = hd[i];
     std::memset(&d, 0, sizeof d);
-    d.w = ws_view(vars[i], std::max<long long>(ns[i], 1));
+    d.w = ws_view(vars[i], std::max<long long>(ns[i], 1), selfs ? &selfs[i] : nullptr);
     d.a.tv = dev_view(vars[i]); d.a.ts0 = dev_view(slots0[i]); d.a.ts1 = slots1 ? dev_view(slots1[i]) : d.a.ts0;
     if (fz) { d.a.epart = d.w.epart; d.w.P = fused_default_P(std::max<long long>(ns[i], 1)); d.w.pshift = 64 - ilog2(d.w.P); }
     d.a.opt = a; d.a.grad = grads[i]; d.a.day = today(vars[i]);
@@ -2242,17 +2207,15 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   return KV_OK;
 }
 
-static bool claim_slot(kv_table* v, kv_table* sl, hipStream_t s);
-
 // shared body of the optimizer ops.  `token` names the batch index a lookup left in the var's workspace
 // (kv_gather_or_insert_tok): the same ids, so the index pass is skipped.  unique: the caller promises unique ids
 // (kv_apply_*_unique), the one-launch path.  Its duplicate guard stamps rows with a launch serial that lives on the HOST: a
 // captured launch would be replayed with the serial it was captured with and find its own stamps.  Under stream capture the
 // unique forms therefore run the batch pipeline (which needs no promise; same results, bit for bit): stream_is_capturing().
-// The caller holds the locks.
+// The caller holds the locks.  self: kv_shard_apply_serve's own segment, read in place.
 template <int OPT>
 static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* grad, const void* ids, int64_t n,
-                        const OptArgs& a, kv_batch_token_t token, hipStream_t s, bool unique) {
+                        const OptArgs& a, kv_batch_token_t token, hipStream_t s, bool unique, const SelfSegment* self) {
   const long long nmax = fused_tab(v) ? FUSED_MAX_N : (1ll << 21);
   if (n < 0 || n > nmax)
     return fail(n < 0 ? KV_INVALID_ARGUMENT : KV_UNIMPLEMENTED,
@@ -2307,7 +2270,7 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
   if ((rc = ensure_capacity(s0, n, s))) return rc;
   if (s1 && (rc = ensure_capacity(s1, n, s))) return rc;
   if ((rc = ensure_workspace(v, n, true, s))) return rc;
-  WsDev wd = ws_view(v, n);
+  WsDev wd = ws_view(v, n, self);
   PartArgs pa{};
   pa.tv = dev_view(v); pa.ts0 = dev_view(s0); pa.ts1 = s1 ? dev_view(s1) : pa.ts0;
   pa.opt = a; pa.grad = grad; pa.day = today(v);
@@ -2444,7 +2407,7 @@ static int with_opt(int opt, F&& f) {
 // the optimizer itself (GroupAdam version), the tables' initialisation, the hyperparameters, the shapes.  So c.status is
 // reported at its place in that order (nothing calls fail() before it unless it returns).  The batched ops report it first.
 static int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const float* grad, const void* ids, int64_t n,
-                     kv_batch_token_t token, kv_stream_t stream, bool unique) {
+                     kv_batch_token_t token, kv_stream_t stream, bool unique, const SelfSegment* self = nullptr) {
   int rc;
   const bool two = two_slots(c.opt);
   if ((rc = check_table(v)) || (rc = check_table(s0)) || (two && (rc = check_table(s1)))) return rc;
@@ -2477,27 +2440,28 @@ static int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, 
   DeviceGuard dg(v->device);
   MultiLock lk({v, s0, two ? s1 : s0});
   // GroupAdam / Adagrad: apply_common decides whether this apply works on the mirrors (mirror_decide); the FTRL family reads
-  // and writes the slot tables' own records
-  MirrorKeep mk(two ? nullptr : v, two ? nullptr : s0);
+  // and writes the slot tables' own records: its entry ends the tables' epochs
+  auto keep = [&](const kv_table* t) -> unsigned { return two ? KEEP_NONE : (t == v ? KEEP_VAR : KEEP_NONE) | (t == s0 ? KEEP_SLOT : KEEP_NONE); };
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = lk.enter(s, token != 0 && token == v->batch_serial ? v : nullptr))) return rc;
+  if ((rc = lk.enter(s, keep, token != 0 && token == v->batch_serial ? v : nullptr))) return rc;
   OptArgs a = c.a;
   a.l21_norm = a.l21 * std::sqrt((float)v->dim);   // training_ops.cc:728
-  return with_opt(c.opt, [&](auto o) { return apply_common<decltype(o)::value>(v, s0, two ? s1 : nullptr, grad, ids, n, a, token, s, unique); });
+  return with_opt(c.opt, [&](auto o) { return apply_common<decltype(o)::value>(v, s0, two ? s1 : nullptr, grad, ids, n, a, token, s, unique, self); });
 }
 
 // Many tables.  After the parser's verdict the ops refuse a missing first table (and linears) — all but Adagrad, whose op
 // leaves that to multi_common — and multi_apply_common checks the tables, their initialisation included.
 static int multi_apply(const OptCall& c, int num_tables, const kv_handle_t* vars, const kv_handle_t* slots0,
                        const kv_handle_t* slots1, const float* const* grads, const void* const* ids, const int64_t* ns,
-                       const kv_batch_token_t* tokens, kv_stream_t stream, bool unique, bool require_reuse = false) {
+                       const kv_batch_token_t* tokens, kv_stream_t stream, bool unique, bool require_reuse = false,
+                       const SelfSegment* selfs = nullptr) {
   if (c.status) return c.status;
   const bool two = two_slots(c.opt);
   if (c.opt != OPT_ADAGRAD && (num_tables < 1 || !vars || !vars[0] || (two && !slots1)))
     return fail(KV_INVALID_ARGUMENT, "N must be >= 1");
   return with_opt(c.opt, [&](auto o) {
     return multi_apply_common<decltype(o)::value>(num_tables, vars, slots0, two ? slots1 : nullptr, c.slot_mult, grads, ids, ns,
-                                                  c.a, stream, tokens, unique, require_reuse);
+                                                  c.a, stream, tokens, unique, require_reuse, selfs);
   });
 }
 
@@ -2669,19 +2633,6 @@ int kv_multi_apply_group_ftrl_v2_unique(int num_tables, const kv_handle_t* vars,
                                         kv_stream_t stream) {
   return multi_apply(ftrl_v2_call(OPT_GROUP_FTRL_V2, lr, l1, l2, l2s, lr_power), num_tables, vars, accums, linears, grads, ids,
                      ns, nullptr, stream, true);
-}
-
-// The slot table whose rows the var's index entries remember (Entry::hint): the first slot-0 table an
-// optimizer uses with the var, or the one kv_attach_slot names.  Hints of a table that was cleared since
-// (import) mean nothing any more and are forgotten; another table simply goes without hints.
-static bool claim_slot(kv_table* v, kv_table* sl, hipStream_t s) {
-  if (v->slot_uid == sl->uid && v->slot_gen == sl->gen) return true;
-  if (v->slot_uid != 0 && v->slot_uid != sl->uid) return false;
-  if (v->slot_uid == sl->uid)   // same table, cleared since
-    k_clear_hints<<<nblocks((long long)v->cap + 1, TB, 8192), TB, 0, s>>>(v->entries, v->cap + 1);
-  v->slot_uid = sl->uid;
-  v->slot_gen = sl->gen;
-  return true;
 }
 
 int kv_attach_slot(kv_handle_t v, kv_handle_t sl, kv_stream_t stream) {
@@ -2865,8 +2816,8 @@ int kv_dedup_segment_sum(kv_handle_t t, const void* ids, const float* grad, int6
   if (!dim_supported(t->dim)) return fail(KV_UNIMPLEMENTED, "embedding dim %d not supported", t->dim);
   DeviceGuard dg(t->device);
   std::lock_guard<std::mutex> l(t->mu);
-  MirrorKeep mk(t, t);   // `t` lends its workspace: neither its rows nor any record is touched
-  if ((rc = enter_op(t, (hipStream_t)stream))) return rc;
+  // `t` lends its workspace: neither its rows nor any record is touched
+  if ((rc = enter_op(t, (hipStream_t)stream, KEEP_VAR | KEEP_SLOT))) return rc;
   return dedup_locked(t, ids, grad, n, uniq, summed, inverse, num_unique, KV_SCATTER_ADD, (hipStream_t)stream);
 }
 
@@ -2883,9 +2834,9 @@ int kv_unsorted_segment_sum(kv_handle_t t, const int32_t* segment_ids, const flo
   if (num_segments == 0) return KV_OK;
   DeviceGuard dg(t->device);
   std::lock_guard<std::mutex> l(t->mu);
-  MirrorKeep mk(t, t);   // `t` lends its workspace: neither its rows nor any record is touched
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = enter_op(t, s))) return rc;
+  // `t` lends its workspace: neither its rows nor any record is touched
+  if ((rc = enter_op(t, s, KEEP_VAR | KEEP_SLOT))) return rc;
   HIP_TRY(hipMemsetAsync(out, 0, (size_t)num_segments * t->dim * sizeof(float), s));  // segments nobody names
   if (n == 0) return KV_OK;
   if ((rc = ensure_workspace(t, n, true, s))) return rc;
@@ -2932,9 +2883,9 @@ int kv_unique(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, 
   if (n > FUSED_MAX_N) return fail(KV_UNIMPLEMENTED, "%lld ids in one call (limit 2^23)", (long long)n);
   DeviceGuard dg(t->device);
   std::lock_guard<std::mutex> l(t->mu);
-  MirrorKeep mk(t, t);   // `t` lends its workspace: neither its rows nor any record is touched
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = enter_op(t, s))) return rc;
+  // `t` lends its workspace: neither its rows nor any record is touched
+  if ((rc = enter_op(t, s, KEEP_VAR | KEEP_SLOT))) return rc;
   if ((rc = ensure_workspace(t, n, false, s))) return rc;
   WsDev wd = ws_view(t, n);
   t->batch_serial = 0;
@@ -2969,7 +2920,6 @@ int kv_bucket_by_owner(kv_handle_t t, const void* ids, int64_t n, const int64_t*
     return fail(KV_INVALID_ARGUMENT, "bad arguments");
   DeviceGuard dg(t->device);
   std::lock_guard<std::mutex> l(t->mu);
-  MirrorKeep mk(t, t);   // `t` lends its workspace: neither its rows nor any record is touched
   hipStream_t s = (hipStream_t)stream;
   const unsigned ntiles = (unsigned)((n + RT - 1) / RT);
   const size_t need = (size_t)std::max(1u, ntiles) * world;
@@ -3892,6 +3842,11 @@ static int shard_late_report(kv_shard* sh, unsigned seen) {
 static bool shard_can_stay(const kv_shard* sh) {
   return (long long)sh->world * (sh->C + 1) <= FUSED_MAX_N;
 }
+// ... as the owner ops are told (ws_view): the (id, count) records, and for the apply (grad) the summed gradient rows
+static SelfSegment shard_self(const kv_shard* sh, bool grad) {
+  if (!sh->self_in_place) return SelfSegment{};
+  return SelfSegment{(unsigned)sh->rank * (sh->C + 1), sh->C + 1, sh->send_pairs, grad ? sh->send_rows : nullptr};
+}
 
 // ids -> local unique ids with counts -> the owners' segments of the send buffer.  2 launches (deterministic mode: 6), no host sync.
 static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_stream_t stream) {
@@ -3972,8 +3927,8 @@ int kv_shard_lookup_serve(kv_shard_t sh, kv_stream_t stream) {
   if (!sh) return fail(KV_INVALID_ARGUMENT, "null shard");
   const int64_t nrec = (int64_t)sh->world * (sh->C + 1);
   sh->serve_token = 0;
-  SelfScope self(sh->table, sh->self_in_place, (unsigned)sh->rank * (sh->C + 1), sh->C + 1, sh->send_pairs, nullptr);
-  return gather_or_insert_impl(sh->table, sh->recv_pairs, nullptr, nrec, sh->send_rows, stream, 1, &sh->serve_token, sh->C + 1);
+  const SelfSegment self = shard_self(sh, false);
+  return gather_or_insert_impl(sh->table, sh->recv_pairs, nullptr, nrec, sh->send_rows, stream, 1, &sh->serve_token, sh->C + 1, &self);
 }
 
 // out[i] = the row that came back for ids[i].  1 launch.
@@ -4042,10 +3997,10 @@ int kv_shard_apply_serve(kv_shard_t sh, int optimizer, kv_handle_t slot0, kv_han
     return fail(KV_FAILED_PRECONDITION, "kv_shard_apply_serve: another op used the table since this batch's lookup "
                                         "(the sharded apply takes over the lookup's index)");
   const int64_t nrec = (int64_t)sh->world * (sh->C + 1);
-  SelfScope self(sh->table, sh->self_in_place, (unsigned)sh->rank * (sh->C + 1), sh->C + 1, sh->send_pairs, sh->send_rows);
+  const SelfSegment self = shard_self(sh, true);
   const OptCall c = shard_opt_call(optimizer, hp);
   if (c.opt < 0) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_serve: optimizer %d", optimizer);
-  return apply_one(c, sh->table, slot0, slot1, sh->recv_rows, sh->recv_pairs, nrec, sh->serve_token, stream, false);
+  return apply_one(c, sh->table, slot0, slot1, sh->recv_rows, sh->recv_pairs, nrec, sh->serve_token, stream, false, &self);
 }
 
 // whole ops: forked from `stream` onto the shard's own stream (the caller's stream is free for the dense tower);
@@ -4585,14 +4540,14 @@ int kv_multi_shard_lookup(const kv_shard_t* shards, int ntab, kv_comm_t comm, co
       std::vector<float*> op(m);
       std::vector<kv_batch_token_t> tok(m, 0);
       std::vector<unsigned> caps(m);
-      SelfScope self;
+      std::vector<SelfSegment> selfs(m);
       for (int j = 0; j < m; ++j) {
         kv_shard* sh = shards[grp[j]];
         tb[j] = sh->table; ip[j] = sh->recv_pairs; nn[j] = (int64_t)sh->world * (sh->C + 1); op[j] = sh->send_rows; caps[j] = sh->C + 1;
         sh->serve_token = 0;
-        self.add(sh->table, sh->self_in_place, (unsigned)sh->rank * (sh->C + 1), sh->C + 1, sh->send_pairs, nullptr);
+        selfs[j] = shard_self(sh, false);
       }
-      if (note(multi_lookup_impl(m, tb.data(), ip.data(), nullptr, nn.data(), op.data(), tok.data(), w, 2, caps.data()))) {
+      if (note(multi_lookup_impl(m, tb.data(), ip.data(), nullptr, nn.data(), op.data(), tok.data(), w, 2, caps.data(), selfs.data()))) {
         for (int k : grp) HIP_TRY(hipMemsetAsync(shards[k]->send_rows, 0, (size_t)rb[k] * (wired(comm) ? shards[k]->world : 1), w));
       } else {
         for (int j = 0; j < m; ++j) shards[grp[j]]->serve_token = tok[j];
@@ -4695,16 +4650,16 @@ int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int
       std::vector<const void*> ip(m);
       std::vector<int64_t> nn(m);
       std::vector<kv_batch_token_t> tok(m);
-      SelfScope self;
+      std::vector<SelfSegment> selfs(m);
       for (int j = 0; j < m; ++j) {
         kv_shard* sh = shards[grp[j]];
         vs[j] = sh->table; s0[j] = slot0[grp[j]]; s1[j] = slot1 ? slot1[grp[j]] : nullptr;
         gp[j] = sh->recv_rows; ip[j] = sh->recv_pairs; nn[j] = (int64_t)sh->world * (sh->C + 1); tok[j] = sh->serve_token;
-        self.add(sh->table, sh->self_in_place, (unsigned)sh->rank * (sh->C + 1), sh->C + 1, sh->send_pairs, sh->send_rows);
+        selfs[j] = shard_self(sh, true);
       }
       // (require_reuse: the ids are (id, count) records — an apply that rebuilt its index from them would read them as plain ids)
       const int r = multi_apply(shard_opt_call(optimizer, hp), m, vs.data(), s0.data(), s1.data(), gp.data(), ip.data(), nn.data(),
-                                tok.data(), w, false, true);
+                                tok.data(), w, false, true, selfs.data());
       note(r);
       for (int k : grp) applied[k] = 1;
     }
