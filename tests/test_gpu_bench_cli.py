@@ -171,7 +171,7 @@ def test_bench_two_ranks_lossless_agreement():
 def test_bench_two_ranks_that_disagree_on_capacity_fail_fast():
   """Ranks created with different peer_capacity must not hang in an exchange of mismatched sizes nor read each other's
   padding: the first sharded op verifies {world, rank, capacity, dim, owner rule} across the ranks and every rank
-  fails with FAILED_PRECONDITION (kvhip.hip shard_verify)."""
+  fails with FAILED_PRECONDITION (kv_shard.hip shard_verify)."""
   if not torch.cuda.is_available():
     pytest.skip("needs a GPU")
   r = _two_ranks(["--debug-capacity-skew", "7"], timeout=300)

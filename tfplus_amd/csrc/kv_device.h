@@ -1,4 +1,5 @@
-// kv_device.h — device-side types and helpers of libkvhip (included by kvhip.hip only).
+// kv_device.h — device-side types and helpers of libkvhip (included into the anonymous namespace of every unit that has
+// device code or uses its constants; no kernel lives here).
 #pragma once
 
 // ------------------------------------------------------------------------------------------
@@ -408,7 +409,6 @@ __device__ __forceinline__ bool group_any(bool p) {
   return ((m >> (lane & ~(W - 1))) & gm) != 0;
 }
 
-
 // One unique key's fused optimizer update, executed by LPR cooperating lanes (lane = 0..LPR-1).
 // `tag` = var row id | ROW_FILTERED; gv = the key's summed gradient, element e at lane
 // (e / V) % LPR, step (e / V) / LPR.  All LPR lanes of every group in the wave must call it
@@ -768,4 +768,21 @@ __device__ __forceinline__ void opt_update_row(const TableDev& tv, const TableDe
   }
   opt_core<OPT, V, LPR, K>(xrow, s0row, s1row, flags_ptr(tv, act ? rv : 0u), flags_ptr(ts0, act ? r0 : 0u),
                            two_slots(OPT) ? flags_ptr(ts1, act ? r1 : 0u) : nullptr, act, new0, D, gv, a, lane, xin, sin, new1);
+}
+
+// ------------------------------------------------------------------------------------------
+// multi-GPU routing: stable-by-tile counting sort of ids by owner rank = floor_mod(id, world)
+// (kernels/utility.h:90-107).  world <= 64.  hist is [world][ntiles] (owner-major for the scan).
+// ------------------------------------------------------------------------------------------
+constexpr int RT = 1024;  // ids per routing tile (256 threads x 4)
+constexpr int MAXW = 64;
+
+// rule 0 (default): (mix64(id) >> 32) % world — balanced whatever the ids look like; rule 1: floor_mod(id, world), the
+// reference's `ids % num_shards` (python/ops/embedding_ops.py:121-127), for checkpoint compatibility
+__device__ __forceinline__ unsigned owner_rank(long long id, int world, int rule) {
+  // (the HIGH half of the hash: the index's home slot is mix64(key) & mask — with the low bits every key of a rank
+  // would share its low home-slot bits and the probe chains of a rank's table would cluster)
+  if (rule == 0) return (unsigned)((mix64((unsigned long long)id) >> 32) % (unsigned long long)world);
+  long long m = id % world;
+  return (unsigned)(m < 0 ? m + world : m);
 }

@@ -578,78 +578,6 @@ __global__ void __launch_bounds__(TBT, 4) k_ltile(TableDev t, WsDev w, const IdT
 }
 
 // ------------------------------------------------------------------------------------------
-// k_shard_finish: the sharded lookup's output rows from the records that came back
-// ------------------------------------------------------------------------------------------
-// out[i] = rows[slot_of[uniq_of_entry[tile * TILE + pos_ent[i]]]]: position -> its entry in the tile (k_ltile<NOTABLE>
-// filed it) -> the entry's distinct-id number (k_papply PA_UNIQUE wrote it to ent_b) -> the record the id was sent in
-// -> the row the owner returned.  A wave takes 64 positions, lane l resolves position l, the rows go VQ lanes per row
-// with streaming stores (the copy of goz_wave).
-template <int VQ, int CW = 4>
-__device__ __forceinline__ void shard_finish_body(const unsigned short* __restrict__ pos_ent, const unsigned* __restrict__ ent_u,
-                                                  const int* __restrict__ slot_of, const float* __restrict__ rows,
-                                                  float* __restrict__ out, long long n, int dim,
-                                                  const float* __restrict__ rows_self, unsigned self_lo, unsigned self_len) {
-  constexpr int RW = 64 / VQ;
-  const int lane = threadIdx.x & 63;
-  const int v = lane % VQ, sub = lane / VQ;
-  const int D4 = dim >> 2;   // float4 per row (<= VQ: lanes past it are masked)
-  const bool vlive = v < D4;
-  const int vv = vlive ? v : 0;
-  const long long nwaves = (long long)gridDim.x * (TB / 64);
-  for (long long r0 = ((long long)blockIdx.x * (TB / 64) + (threadIdx.x >> 6)) * 64; r0 < n; r0 += nwaves * 64) {
-    const long long i = r0 + lane;
-    unsigned rec = 0;   // record 0: a header's row (zeros) — positions past the end, ids that found no room in their segment
-    if (i < n) {
-      const unsigned e = pos_ent[i];
-      if (e != 0xFFFFu) rec = (unsigned)slot_of[ent_u[(size_t)(i / TILE) * TILE + e]];
-    }
-#pragma unroll
-    for (int j0 = 0; j0 < VQ; j0 += CW) {
-      float4 val[CW];
-      unsigned rj[CW];
-#pragma unroll
-      for (int j = 0; j < CW && j0 + j < VQ; ++j) rj[j] = __shfl(rec, (j0 + j) * RW + sub);
-#pragma unroll
-      for (int j = 0; j < CW && j0 + j < VQ; ++j)   // (records [self_lo, self_lo + self_len): this rank's own segment, read where the serve wrote it)
-        val[j] = reinterpret_cast<const float4*>((((unsigned)rj[j] - self_lo < self_len) ? rows_self : rows) + (size_t)rj[j] * dim)[vv];
-#pragma unroll
-      for (int j = 0; j < CW && j0 + j < VQ; ++j) {
-        const long long ii = r0 + (j0 + j) * RW + sub;
-        if (ii < n && vlive) {
-          float4* dst = reinterpret_cast<float4*>(out + (size_t)ii * dim) + v;
-          __builtin_nontemporal_store(val[j].x, &dst->x); __builtin_nontemporal_store(val[j].y, &dst->y);
-          __builtin_nontemporal_store(val[j].z, &dst->z); __builtin_nontemporal_store(val[j].w, &dst->w);
-        }
-      }
-    }
-  }
-}
-template <int VQ, int CW = 4>
-__global__ void __launch_bounds__(TB) k_shard_finish(const unsigned short* __restrict__ pos_ent, const unsigned* __restrict__ ent_u,
-                                                     const int* __restrict__ slot_of, const float* __restrict__ rows,
-                                                     float* __restrict__ out, long long n, int dim,
-                                                     const float* __restrict__ rows_self, unsigned self_lo, unsigned self_len) {
-  shard_finish_body<VQ, CW>(pos_ent, ent_u, slot_of, rows, out, n, dim, rows_self, self_lo, self_len);
-}
-// several tables of one row geometry in one launch (blockIdx.y = table)
-struct FinishDesc {
-  const unsigned short* pos_ent;
-  const unsigned* ent_u;
-  const int* slot_of;
-  const float* rows;
-  float* out;
-  long long n;
-  const float* rows_self;
-  unsigned self_lo, self_len;
-  int dim, pad;
-};
-template <int VQ, int CW = 4>
-__global__ void __launch_bounds__(TB) k_shard_finish_multi(const FinishDesc* __restrict__ descs) {
-  const FinishDesc d = descs[blockIdx.y];
-  shard_finish_body<VQ, CW>(d.pos_ent, d.ent_u, d.slot_of, d.rows, d.out, d.n, d.dim, d.rows_self, d.self_lo, d.self_len);
-}
-
-// ------------------------------------------------------------------------------------------
 // k_seg_combine_e: embedding_lookup_sparse's combiner over the tiles' entries
 // ------------------------------------------------------------------------------------------
 // out[s] = combine_j( w_j * rows[row(id_j)] ) over segment s's positions in position order (tf.segment_sum's order;

@@ -1,0 +1,328 @@
+// kv_host.h — what kv_shard.hip, the sharded layer, uses of the table and of the ops in kvhip.hip: the table's types and
+// the functions below, nothing else.  Everything sits in the hidden namespace of kv_types.h, so none of it is exported;
+// `struct kv_table` is the ABI's opaque handle and therefore global.  The functions are defined, and explained, in kvhip.hip.
+#pragma once
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/kvhip.h"
+#include "kv_launch.h"
+
+namespace __attribute__((visibility("hidden"))) kvhip_internal {
+
+int fail(int code, const char* fmt, ...);   // records the calling thread's message (kv_last_error), returns `code`
+
+#define HIP_TRY(expr)                                                                         \
+  do {                                                                                        \
+    hipError_t _e = (expr);                                                                   \
+    if (_e != hipSuccess)                                                                     \
+      return fail(_e == hipErrorOutOfMemory ? KV_RESOURCE_EXHAUSTED : KV_INTERNAL,            \
+                  "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+  } while (0)
+
+struct Workspace {
+  long long cap_n = 0;       // ids (multiple of TILE)
+  unsigned capP = 0;         // partitions toff was sized for
+  long long* ent_key = nullptr;
+  unsigned* ent_a = nullptr;
+  unsigned* ent_b = nullptr;
+  unsigned* ent_base = nullptr;
+  unsigned* ent_rec = nullptr;
+  unsigned* toff = nullptr;
+  unsigned* slot_rank = nullptr;
+  unsigned* order = nullptr;
+  uint4* coldlist = nullptr;   // [cap_n][2]
+  uint4* hotlist = nullptr;    // [cap_n][2]
+  uint4* litem = nullptr;      // [cap_n]
+  uint4* items = nullptr;      // [cap_n]
+  uint4* pmeta = nullptr;      // [capP]
+  float* hpart = nullptr;      // [chunk_cap(cap_n)][dim]
+  long long hpart_elems = 0;
+  unsigned* ctr = nullptr;
+  unsigned* mcount = nullptr;  // entry-list pipeline: [cap_n / TILE]
+  unsigned short* pos_ent = nullptr;   // [pos_cap] sharded route: every position's entry number in its tile
+  long long pos_cap = 0;
+  float* epart = nullptr;      // [cap_n / 2][dim] tile sums
+  long long epart_elems = 0;
+  long long* scat_keys = nullptr;  // kv_scatter_update on repeated ids: de-duplicated ids and combined updates
+  float* scat_sum = nullptr;
+  long long scat_cap = 0;          // rows
+  unsigned* seg_off = nullptr;   // kv_lookup_sparse: CSR offsets [seg_cap + 1]
+  long long seg_cap = 0;
+  unsigned long long* dbg = nullptr;
+};
+
+}  // namespace kvhip_internal
+
+using namespace kvhip_internal;   // (as every unit says: the handle's members name the internal types)
+
+struct kv_table {
+  // every op that may change which rows exist (or what the delta lists hold) advances op_serial; the two-phase
+  // calls (count, then fill into buffers the caller sized from the counts) refuse to fill once it has moved on
+  uint64_t op_serial = 1, export_serial = 0, delta_serial = 0, expire_serial = 0;
+  int device = 0;
+  int key_dtype = KV_DT_INT64;
+  int dim = 0;
+  unsigned enter_threshold = 0;
+  unsigned long long seed = 0;
+  int fixed_day = -1;
+  // index
+  Entry* entries = nullptr;
+  unsigned long long cap = 0;
+  // slab
+  int chunk_bits = 16;
+  std::vector<Chunk> chunks;
+  Chunk* d_chunks = nullptr;
+  unsigned* d_counters = nullptr;  // [0] next_row [1] error [2] rows on the free list
+  unsigned* free_rows = nullptr;   // rows released by Delete (device stack, rows_cap entries)
+  unsigned long long free_cap = 0;
+  long long free_known = 0;        // free-list length at the last sync (> 0: inserts pop from it)
+  unsigned long long idx_ub = 0;   // upper bound of claimed index entries (live keys + tombstones)
+  // exact claimed entries at a sync = idx_base + (next_row - bump_base) + free-list pops since the
+  // last index rebuild, pops = pushes_since - (free_now - free_base)   (revivals make it an upper bound)
+  unsigned long long idx_base = 0, bump_base = 1, pushes_since = 0;
+  long long free_base = 0;
+  unsigned long long rows_cap = 0;  // chunks.size() << chunk_bits
+  unsigned long long rows_ub = 1;   // upper bound of next_row
+  // init table
+  float* init_table = nullptr;
+  long long init_rows = 0;
+  bool initialized = false;
+  bool init_placeholder = false;   // init_table is the zero row an import put there, not a real init table
+  Workspace ws;
+  // the batch index the workspace holds: `batch_serial` names it (0 = none); an optimizer apply handed the
+  // same token takes the index over instead of rebuilding it
+  uint64_t batch_serial = 0;
+  long long batch_n = 0;
+  bool fused_index = false;        // the index is the tiles' entries (kv_fused.h: an apply of that batch goes through k_papply),
+                                   // not a sorted position list (kv_kernels.h)
+  long long batch_n_prev = 0;      // ids of the previous entry-list index pass (the distinct-count hint belongs to that size)
+  unsigned index_P = 0;            // partitions of the entry-list index the workspace holds
+  // A training lookup that hands out a batch token returns when its rows are written; its partition pass (frequency
+  // words, rows of new keys, the batch's key records and entry list) is PENDING: the optimizer apply of that batch
+  // runs it in front of its own kernels, any other op on the table runs it first thing (settle).  Same stream order
+  // as before, the rows just do not wait for it.
+  bool part_pending = false;
+  unsigned char pend_wd[sizeof(WsDev)], pend_pa[sizeof(PartArgs)];
+  // Slot mirrors (kv_device.h SlotMirror; mirror_* below): a var table paired with ONE slot table keeps, next to each row's
+  // record, a write-back copy of the slot row's frequency word and flags; the lean apply works on the copy alone.
+  long long stat_mirror_applies = 0;            // kv_get_stat
+  std::atomic<long long> stat_mirror_epochs{0}; // ... (an epoch of a var's mirrors may be ended under the slot table's lock)
+  // both tables of a mirror pair hold the pair's device views as the last lean apply (or the pairing) saw them — written with
+  // BOTH locks held.  An op that ends the epoch holds ONE of the two locks: it flushes through the copy in the table it
+  // holds and never reads the other table's host state (whose owner may be growing it on another thread).  What a dirty
+  // copy names — a var row and a slot row of the chunk-0 slabs — is inside these views whatever happened to the tables since.
+  TableDev mview_var{}, mview_slot{};
+  kv_table* mirror_slot = nullptr;          // var side: the slot table its mirrors stand for
+  std::atomic<unsigned> mirror_epoch{1};    // var side: generation of the copies (16 bits on the device)
+  std::atomic<bool> mirror_dirty{false};    // var side: a lean apply has written mirrors since the last flush
+  kv_table* mirror_var = nullptr;           // slot side: the var that holds this table's mirrors
+  bool mirror_banned = false;               // either side: the table is used under stream capture (kv_prepare_capture): no mirrors, ever
+  bool mirror_shared = false;               // slot side: a second var attached it — no mirrors for this table any more
+  unsigned uniq_serial = 0;        // stamp of the table's last kv_apply_*_unique launch (kv_uapply.h; wraps at 65535: stamps cleared)
+  bool deterministic = false;      // kv_set_deterministic
+  bool occurrence_order = false;   // kv_set_deterministic(h, 2): a repeated id's gradient rows are added one by one in input order
+                                   // (the sorted-position pipeline with one chain per key; implies deterministic)
+  std::atomic<int> shard_refs{0};  // kv_shard handles built on this table
+  bool fast_math = false;          // kv_set_fast_math: the optimizers' sqrt / division on v_sqrt_f32 / v_rcp_f32 (1 ulp) —
+                                   // never in deterministic mode, which keeps the IEEE sequences
+  uint64_t uid = 0;                // unique over the process: names the attached slot table safely
+  uint64_t slot_uid = 0;           // uid of the slot table the index entries' hints refer to (0 = none)
+  uint64_t slot_gen = 0;           // that table's `gen` when the hints were valid
+  uint64_t gen = 0;                // bumped when the table is cleared (import): hints into it die
+  unsigned* err_host = nullptr;    // pinned: the device error flag, copied back after every batch op
+  unsigned* cnt_host = nullptr;    // pinned: where the synchronous ops (kv_dedup_segment_sum, kv_unique) read their count back
+  hipStream_t last_stream = nullptr;  // stream of the table's last op; a different stream first waits for it
+  bool has_last = false;
+  hipEvent_t last_done = nullptr;
+  // delta lists (SUPPORT_DELTA_EXPORT / SUPPORT_PREDICTION_DELTA_EXPORT, kv_variable.h:100-111): live keys
+  // carry a byte in their RowMeta; keys recorded by Delete have no row and wait here
+  bool track_delta = false, track_pred = false;
+  std::vector<long long> del_train, del_pred;
+  unsigned long long* d_stat = nullptr;  // [4]
+  std::mutex mu;
+  unsigned* route_hist = nullptr;  // kv_bucket_by_owner scratch
+  size_t route_hist_cap = 0;
+  // optional per-kernel timing (kv_profile_*): event pairs recorded on the op's stream
+  bool prof = false;
+  unsigned prof_mask = 0xFFFFFFFFu;
+  std::vector<hipEvent_t> ev;
+  std::vector<int> ev_kind;
+  size_t ev_used = 0;
+  int prof_every = 1;                // bracket every prof_every-th launch of a kind (kv_profile_sample)
+  unsigned prof_seq[KV_PROF_KINDS] = {};
+};
+
+namespace __attribute__((visibility("hidden"))) kvhip_internal {
+
+// ---- small helpers -----------------------------------------------------------------------------------------------------
+inline unsigned long long pow2ceil(unsigned long long x) {
+  unsigned long long p = 1;
+  while (p < x) p <<= 1;
+  return p;
+}
+
+inline int ilog2(unsigned long long x) {
+  int l = 0;
+  while ((1ull << l) < x) ++l;
+  return l;
+}
+
+inline int nblocks(long long work, int per_block, int cap = 4096) {
+  long long b = (work + per_block - 1) / per_block;
+  if (b < 1) b = 1;
+  if (b > cap) b = cap;
+  return (int)b;
+}
+
+struct DeviceGuard {
+  int prev = 0;
+  explicit DeviceGuard(int d) { hipGetDevice(&prev); if (prev != d) hipSetDevice(d); cur = d; }
+  ~DeviceGuard() { if (prev != cur) hipSetDevice(prev); }
+  int cur;
+};
+
+inline int check_table(kv_handle_t h) {
+  if (!h) return fail(KV_INVALID_ARGUMENT, "null table handle");
+  return KV_OK;
+}
+
+// ---- the entry-list pipeline (kv_fused.h) ----
+// ids per index pass: positions and epart rows are 30-bit fields of the entry list's words, a partition block takes
+// up to 65535 entries; 2^23 ids (4096 tiles) stay well inside both
+constexpr long long FUSED_MAX_N = 1ll << 23;
+// dims it serves: every multiple of 4 up to 256 (rows of dim / 4 float4; a row's lane group is the next power of two,
+// the lanes past the row's end masked: dims 12, 20, 100 ... run the same kernels as 16, 32, 128)
+inline bool fused_ok(int D) {
+  if ((D & 3) != 0) return false;
+  const int q = D / 4;
+  return q >= 1 && q <= 64;
+}
+
+// lanes per row of the row-copy kernels: dim / 4 rounded up to a power of two
+inline int row_lanes(int D) { return (int)pow2ceil((unsigned long long)std::max(1, D / 4)); }
+
+// (re)allocation that leaves the old buffer in place when the new one cannot be had
+template <typename T>
+int regrow(T** p, size_t count) {
+  T* q = nullptr;
+  HIP_TRY(hipMalloc(&q, count * sizeof(T)));
+  if (*p) hipFree(*p);
+  *p = q;
+  return KV_OK;
+}
+
+bool stream_is_capturing(hipStream_t s);
+int ensure_workspace(kv_table* t, long long n, bool need_part, hipStream_t s);
+
+// ---- views -------------------------------------------------------------------------------------------------------------
+TableDev dev_view(const kv_table* t);
+
+// The sharded owner ops read a rank's OWN exchange segment where it was written: records [lo, lo + len) of the buffers the
+// op reads come from `ids` / `grad` (the send buffers) instead.  Passed by kv_shard_lookup_serve / kv_shard_apply_serve and
+// the grouped serve blocks of kv_multi_shard_lookup / kv_multi_shard_apply (shard_self; one per table in the batched ones)
+// down to the ws_view of the lookup or apply that serves them; every other op passes none.  The default is "no segment".
+struct SelfSegment { unsigned lo = 0, len = 0; const void* ids = nullptr; const float* grad = nullptr; };
+
+WsDev ws_view(kv_table* t, long long n, const SelfSegment* self = nullptr);
+
+// ---- kernel launchers (the pipelines' kernels are compiled into kvhip.hip alone) -----------------------------------------
+void launch_ltile_notable(kv_table* t, const TableDev& td, const WsDev& wd, const void* ids, long long n, hipStream_t s,
+                          const int* counts = nullptr, bool int32_ids = false);
+void launch_ltile_multi_notable(const WsDev& wmax, int ntab, const MultiDesc* md, hipStream_t s);
+
+// ---- entering a table --------------------------------------------------------------------------------------------------
+// the mirror role(s) an op keeps a table in where it enters it (kvhip.hip: slot mirrors, the host side)
+enum : unsigned {
+  KEEP_NONE = 0u,
+  KEEP_VAR = 1u,    // the table's own epoch (it is a pair's var) goes on
+  KEEP_SLOT = 2u,   // the epoch of the var this table is the slot table of goes on
+};
+
+int hand_over(kv_table* t, hipStream_t s, unsigned keep = KEEP_NONE, bool settle = true, bool mutates = true);
+int enter_op(kv_table* t, hipStream_t s, unsigned keep = KEEP_NONE, bool settle = true, bool mutates = true);
+
+// locks tables in address order like MaybeLockVariableInputMutexesInOrder (training_ops.cc:96-184)
+struct MultiLock {
+  std::vector<kv_table*> ts;
+  explicit MultiLock(std::initializer_list<kv_table*> l) : MultiLock(std::vector<kv_table*>(l)) {}
+  explicit MultiLock(std::vector<kv_table*> l) : ts(std::move(l)) {
+    std::sort(ts.begin(), ts.end());
+    ts.erase(std::unique(ts.begin(), ts.end()), ts.end());
+    for (auto* t : ts) t->mu.lock();
+  }
+  ~MultiLock() { for (auto it = ts.rbegin(); it != ts.rend(); ++it) (*it)->mu.unlock(); }
+  // keep(t): the mirror role(s) table t is kept in (KEEP_*)
+  // later: this table's pending partition pass is taken over by the caller (the optimizer apply of that batch)
+  template <class Keep>
+  int enter(hipStream_t s, Keep keep, kv_table* later = nullptr) {
+    int rc;
+    for (auto* t : ts)
+      if ((rc = enter_op(t, s, keep(t), t != later))) return rc;
+    return KV_OK;
+  }
+  int enter(hipStream_t s) { return enter(s, [](const kv_table*) { return (unsigned)KEEP_NONE; }); }
+};
+
+void retire_stream(hipStream_t dead);
+
+// ---- index passes ------------------------------------------------------------------------------------------------------
+extern std::atomic<uint64_t> g_serial;   // batch tokens
+void choose_partitions(kv_table* t, WsDev& wd, long long n);
+
+// ---- descriptor staging for the batched launches -----------------------------------------------------------------------
+struct StageSlot {
+  char* host = nullptr;   // pinned
+  char* dev = nullptr;
+  size_t cap = 0;
+  hipEvent_t consumed = nullptr;
+};
+struct BatchStage {       // a small ring, so the host can prepare call k+1 while call k still runs
+  std::mutex mu;
+  StageSlot slot[4];
+  unsigned cursor = 0;
+};
+extern BatchStage g_stage[64][2];   // [device][0 = inference gather, 1 = training ops]
+int stage_acquire(BatchStage& st, size_t bytes, StageSlot** out);
+struct StageRelease {   // unlocks (and marks the slot busy until the stream gets there) on scope exit
+  BatchStage& st; StageSlot* sl; hipStream_t s; bool launched = false;
+  ~StageRelease() { if (launched) hipEventRecord(sl->consumed, s); st.mu.unlock(); }
+};
+
+// ---- the ops the owner side of a sharded op runs -----------------------------------------------------------------------
+int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, float* out,
+                          kv_stream_t stream, int pairs, kv_batch_token_t* token, unsigned seg_cap = 0,
+                          const SelfSegment* self = nullptr);
+int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const void* const* ids,
+                      const int32_t* const* counts, const int64_t* ns, float* const* outs,
+                      kv_batch_token_t* tokens, kv_stream_t stream, int ids_kind, const unsigned* seg_caps,
+                      const SelfSegment* selfs);
+
+// An optimizer op as the pipelines see it: which kernels (opt, an OPT_*), with which arguments, on slot tables of which
+// shape.  One parser per optimizer family fills it from the op's arguments; every entry point below is a parser and one of
+// two bodies: apply_one (one table) or multi_apply (many tables, one launch per stage).
+struct OptCall {
+  int opt = -1;          // OPT_*; -1: not known (a GroupAdam version other than 3 or 4, a sharded optimizer code)
+  OptArgs a{};           // without l21_norm, which the bodies derive from the var's dim
+  int slot_mult = 1;     // first slot table's dim / var dim; a second slot table (linear) iff two_slots(opt)
+  int status = KV_OK;    // the parser's verdict on the op's arguments; its message is the one fail() recorded last
+};
+
+OptCall shard_opt_call(int optimizer, const float* hp);
+int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const float* grad, const void* ids, int64_t n,
+              kv_batch_token_t token, kv_stream_t stream, bool unique, const SelfSegment* self = nullptr);
+int multi_apply(const OptCall& c, int num_tables, const kv_handle_t* vars, const kv_handle_t* slots0,
+                const kv_handle_t* slots1, const float* const* grads, const void* const* ids, const int64_t* ns,
+                const kv_batch_token_t* tokens, kv_stream_t stream, bool unique, bool require_reuse = false,
+                const SelfSegment* selfs = nullptr);
+
+}  // namespace kvhip_internal

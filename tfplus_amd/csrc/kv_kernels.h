@@ -1160,7 +1160,6 @@ __device__ __forceinline__ void occ_sum_body(const WsDev& w, const PartArgs& a, 
 template <int NC>
 __global__ void __launch_bounds__(OCC_TB) k_occ_sum(WsDev w, PartArgs a, int fop) { occ_sum_body<NC>(w, a, fop); }
 
-
 // The slot-table rows of one key, resolved by the group leader.  FindOrInsertUnsafe(var, filter_out !=
 // nullptr) kv_variable.h:382-408 and FindOrInsertUnsafe(slot, nullptr) :409-414; FTRL probes linear
 // before accum (training_ops.cc:701-704).  `m0` is the record of the hinted slot row (requested early).
@@ -1964,148 +1963,6 @@ __global__ void k_dedup_inverse(WsDev w, long long n, int* inverse) {
     inverse[i] = (int)w.ent_b[w.slot_rank[i] & SLOT_MASK];
 }
 
-// ------------------------------------------------------------------------------------------
-// multi-GPU routing: stable-by-tile counting sort of ids by owner rank = floor_mod(id, world)
-// (kernels/utility.h:90-107).  world <= 64.  hist is [world][ntiles] (owner-major for the scan).
-// ------------------------------------------------------------------------------------------
-constexpr int RT = 1024;  // ids per routing tile (256 threads x 4)
-constexpr int MAXW = 64;
-
-// rule 0 (default): (mix64(id) >> 32) % world — balanced whatever the ids look like; rule 1: floor_mod(id, world), the
-// reference's `ids % num_shards` (python/ops/embedding_ops.py:121-127), for checkpoint compatibility
-__device__ __forceinline__ unsigned owner_rank(long long id, int world, int rule) {
-  // (the HIGH half of the hash: the index's home slot is mix64(key) & mask — with the low bits every key of a rank
-  // would share its low home-slot bits and the probe chains of a rank's table would cluster)
-  if (rule == 0) return (unsigned)((mix64((unsigned long long)id) >> 32) % (unsigned long long)world);
-  long long m = id % world;
-  return (unsigned)(m < 0 ? m + world : m);
-}
-
-template <typename IdT>
-__global__ void __launch_bounds__(TB) k_owner_hist(const IdT* __restrict__ ids, long long n, int world, int rule,
-                                                   unsigned ntiles, unsigned* __restrict__ hist,
-                                                   const long long* __restrict__ n_dev) {
-  if (n_dev) n = min(n, *n_dev);   // the list's length is still on the device (kv_unique without a sync)
-  __shared__ unsigned h[MAXW];
-  if (threadIdx.x < MAXW) h[threadIdx.x] = 0;
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * RT;
-#pragma unroll
-  for (int k = 0; k < RT / TB; ++k) {
-    const long long i = base + k * TB + threadIdx.x;
-    if (i < n) atomicAdd(&h[owner_rank(load_id(ids, (size_t)i), world, rule)], 1u);
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < world) hist[(size_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
-}
-
-// one block: exclusive scan of hist in (owner, tile) order -> base offsets; counts[w] = ids owned by w
-__global__ void __launch_bounds__(1024) k_owner_scan(unsigned* __restrict__ hist, unsigned total,
-                                                     unsigned ntiles, int world, long long* __restrict__ counts) {
-  __shared__ unsigned wtot[17];
-  const unsigned per = (total + 1023) / 1024;
-  const unsigned b0 = min(total, threadIdx.x * per), b1 = min(total, b0 + per);
-  unsigned sum = 0;
-  for (unsigned i = b0; i < b1; ++i) sum += hist[i];
-  unsigned tot;
-  unsigned run = block_excl_scan<16>(sum, wtot, &tot);
-  for (unsigned i = b0; i < b1; ++i) { const unsigned c = hist[i]; hist[i] = run; run += c; }
-  __syncthreads();
-  if ((int)threadIdx.x < world) {
-    const unsigned lo = hist[(size_t)threadIdx.x * ntiles];
-    const unsigned hi = ((int)threadIdx.x + 1 < world) ? hist[(size_t)(threadIdx.x + 1) * ntiles] : tot;
-    counts[threadIdx.x] = (long long)hi - (long long)lo;
-  }
-}
-
-template <typename IdT>
-__global__ void __launch_bounds__(TB) k_owner_scatter(const IdT* __restrict__ ids, long long n, int world, int rule,
-                                                      unsigned ntiles, const unsigned* __restrict__ base_off,
-                                                      long long* __restrict__ out_ids, int* __restrict__ perm,
-                                                      const long long* __restrict__ n_dev,
-                                                      const int* __restrict__ counts_in,
-                                                      long long* __restrict__ pairs_out, int* __restrict__ pos_out) {
-  if (n_dev) n = min(n, *n_dev);
-  __shared__ unsigned h[MAXW];
-  if ((int)threadIdx.x < world) h[threadIdx.x] = base_off[(size_t)threadIdx.x * ntiles + blockIdx.x];
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * RT;
-#pragma unroll
-  for (int k = 0; k < RT / TB; ++k) {
-    const long long i = base + k * TB + threadIdx.x;
-    if (i < n) {
-      const long long id = load_id(ids, (size_t)i);
-      const unsigned pos = atomicAdd(&h[owner_rank(id, world, rule)], 1u);
-      out_ids[pos] = id;
-      perm[pos] = (int)i;
-      // optional extras of the sharded lookup: the exchange payload (id, occurrence count) in
-      // bucket order, and where input position i went (the inverse of perm)
-      if (pairs_out) { pairs_out[2 * (size_t)pos] = id; pairs_out[2 * (size_t)pos + 1] = counts_in ? (long long)counts_in[i] : 1ll; }
-      if (pos_out) pos_out[i] = (int)pos;
-    }
-  }
-}
-// The sharded lookup's exchange payload in FIXED-CAPACITY segments (no size collective, no host sync): owner d's
-// segment is seg[d][0 .. C]: record 0 = header {pairs in the segment, 0}, records 1 .. = (id, occurrence count).
-// A record whose count is 0 is skipped by the owner's tile pass, so padding costs nothing but its bytes.  slot_of[u]
-// = where unique id u went (its row comes back at the same place).  More than C ids for one owner: the extra
-// ones are dropped and *overflow is raised (the host doubles C; hashed ownership keeps this from happening).
-__global__ void __launch_bounds__(TB) k_owner_scatter_fixed(const long long* __restrict__ ids, const int* __restrict__ cnts,
-                                                            long long n, int world, int rule,
-                                                            unsigned ntiles, const unsigned* __restrict__ base_off,
-                                                            unsigned C, long long* __restrict__ seg, int* __restrict__ slot_of,
-                                                            unsigned* __restrict__ overflow) {
-  __shared__ unsigned h[MAXW];
-  if ((int)threadIdx.x < world)   // rank inside the owner's bucket = global offset - the bucket's start
-    h[threadIdx.x] = base_off[(size_t)threadIdx.x * ntiles + blockIdx.x] - base_off[(size_t)threadIdx.x * ntiles];
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * RT;
-#pragma unroll
-  for (int k = 0; k < RT / TB; ++k) {
-    const long long i = base + k * TB + threadIdx.x;
-    if (i < n && cnts[i] > 0) {   // the list has gaps (sparse unique numbers): a count of 0 names no key
-      const long long id = ids[i];
-      const unsigned d = owner_rank(id, world, rule);
-      const unsigned r = atomicAdd(&h[d], 1u);
-      if (r < C) {
-        const size_t slot = (size_t)d * (C + 1) + 1 + r;
-        seg[2 * slot] = id;
-        seg[2 * slot + 1] = (long long)cnts[i];
-        slot_of[i] = (int)slot;
-      } else {
-        slot_of[i] = 0;        // record 0 is a header: its "row" is never a real one
-        atomicExch(overflow, 1u);
-      }
-    }
-  }
-}
-// the segments' headers {records in the segment (at most C), 0}
-__global__ void k_seg_headers(const long long* __restrict__ counts, int world, unsigned C, long long* __restrict__ seg,
-                              unsigned* __restrict__ need) {
-  const int d = threadIdx.x;
-  if (need && d == 0) *need = 0u;
-  __syncthreads();
-  if (d < world) {
-    seg[2 * (size_t)d * (C + 1)] = counts[d] < (long long)C ? counts[d] : (long long)C;
-    seg[2 * (size_t)d * (C + 1) + 1] = 0;
-    if (need) atomicMax(need, (unsigned)(counts[d] < 0x7FFFFFFFll ? counts[d] : 0x7FFFFFFFll));
-  }
-}
-// k_owner_hist over the sparse unique list of the sharded route (entries with a count of 0 name no key)
-__global__ void __launch_bounds__(TB) k_owner_hist_u32(const long long* __restrict__ ids, const int* __restrict__ cnts, long long n,
-                                                       int world, int rule, unsigned ntiles, unsigned* __restrict__ hist) {
-  __shared__ unsigned h[MAXW];
-  if (threadIdx.x < MAXW) h[threadIdx.x] = 0;
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * RT;
-#pragma unroll
-  for (int k = 0; k < RT / TB; ++k) {
-    const long long i = base + k * TB + threadIdx.x;
-    if (i < n && cnts[i] > 0) atomicAdd(&h[owner_rank(ids[i], world, rule)], 1u);
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < world) hist[(size_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
-}
 // ---------------------------------------------------------------------------------------------
 // embedding_lookup_sparse (python/ops/embedding_ops.py:279-441) fused behind the lookup index:
 //   k_seg_offsets   CSR offsets of the sorted segment ids: off[s] = first position of segment s
@@ -2208,4 +2065,3 @@ __global__ void __launch_bounds__(TB) k_take_rows(const U* __restrict__ src, con
     else out[x] = src[j * nu + e];
   }
 }
-

@@ -29,8 +29,6 @@
 //                   out_sum[out_map[number]] — the records the ids were sent in — instead of updating rows
 #pragma once
 
-enum PaMode { PA_LOOKUP = 0, PA_APPLYIDX = 1, PA_NONE = 2, PA_UNIQUE = 3, PA_DEDUP = 4,
-              PA_DEDUP_NUM = 5 };   // (a template constant only: PA_DEDUP that numbers the ids itself — kv_dedup_segment_sum)
 #ifndef KV_PA_WAVES
 #define KV_PA_WAVES 4      // waves per SIMD the register budget is set for (A/B knob: tools/mkvariant.sh)
 #endif

@@ -1,0 +1,206 @@
+// kv_route.h — the sharded layer's own kernels (included by kv_shard.hip only, after kv_device.h): the routing rule's
+// counting sort of ids by owner rank and the fixed-capacity exchange segments (k_owner_*, k_seg_headers), and the sharded
+// lookup's output rows from the records that came back (k_shard_finish).
+#pragma once
+
+// ------------------------------------------------------------------------------------------
+// multi-GPU routing: stable-by-tile counting sort of ids by owner rank (owner_rank, kv_device.h;
+// kernels/utility.h:90-107).  world <= 64.  hist is [world][ntiles] (owner-major for the scan).
+// ------------------------------------------------------------------------------------------
+template <typename IdT>
+__global__ void __launch_bounds__(TB) k_owner_hist(const IdT* __restrict__ ids, long long n, int world, int rule,
+                                                   unsigned ntiles, unsigned* __restrict__ hist,
+                                                   const long long* __restrict__ n_dev) {
+  if (n_dev) n = min(n, *n_dev);   // the list's length is still on the device (kv_unique without a sync)
+  __shared__ unsigned h[MAXW];
+  if (threadIdx.x < MAXW) h[threadIdx.x] = 0;
+  __syncthreads();
+  const long long base = (long long)blockIdx.x * RT;
+#pragma unroll
+  for (int k = 0; k < RT / TB; ++k) {
+    const long long i = base + k * TB + threadIdx.x;
+    if (i < n) atomicAdd(&h[owner_rank(load_id(ids, (size_t)i), world, rule)], 1u);
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < world) hist[(size_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
+}
+
+// one block: exclusive scan of hist in (owner, tile) order -> base offsets; counts[w] = ids owned by w
+__global__ void __launch_bounds__(1024) k_owner_scan(unsigned* __restrict__ hist, unsigned total,
+                                                     unsigned ntiles, int world, long long* __restrict__ counts) {
+  __shared__ unsigned wtot[17];
+  const unsigned per = (total + 1023) / 1024;
+  const unsigned b0 = min(total, threadIdx.x * per), b1 = min(total, b0 + per);
+  unsigned sum = 0;
+  for (unsigned i = b0; i < b1; ++i) sum += hist[i];
+  unsigned tot;
+  unsigned run = block_excl_scan<16>(sum, wtot, &tot);
+  for (unsigned i = b0; i < b1; ++i) { const unsigned c = hist[i]; hist[i] = run; run += c; }
+  __syncthreads();
+  if ((int)threadIdx.x < world) {
+    const unsigned lo = hist[(size_t)threadIdx.x * ntiles];
+    const unsigned hi = ((int)threadIdx.x + 1 < world) ? hist[(size_t)(threadIdx.x + 1) * ntiles] : tot;
+    counts[threadIdx.x] = (long long)hi - (long long)lo;
+  }
+}
+
+template <typename IdT>
+__global__ void __launch_bounds__(TB) k_owner_scatter(const IdT* __restrict__ ids, long long n, int world, int rule,
+                                                      unsigned ntiles, const unsigned* __restrict__ base_off,
+                                                      long long* __restrict__ out_ids, int* __restrict__ perm,
+                                                      const long long* __restrict__ n_dev,
+                                                      const int* __restrict__ counts_in,
+                                                      long long* __restrict__ pairs_out, int* __restrict__ pos_out) {
+  if (n_dev) n = min(n, *n_dev);
+  __shared__ unsigned h[MAXW];
+  if ((int)threadIdx.x < world) h[threadIdx.x] = base_off[(size_t)threadIdx.x * ntiles + blockIdx.x];
+  __syncthreads();
+  const long long base = (long long)blockIdx.x * RT;
+#pragma unroll
+  for (int k = 0; k < RT / TB; ++k) {
+    const long long i = base + k * TB + threadIdx.x;
+    if (i < n) {
+      const long long id = load_id(ids, (size_t)i);
+      const unsigned pos = atomicAdd(&h[owner_rank(id, world, rule)], 1u);
+      out_ids[pos] = id;
+      perm[pos] = (int)i;
+      // optional extras of the sharded lookup: the exchange payload (id, occurrence count) in
+      // bucket order, and where input position i went (the inverse of perm)
+      if (pairs_out) { pairs_out[2 * (size_t)pos] = id; pairs_out[2 * (size_t)pos + 1] = counts_in ? (long long)counts_in[i] : 1ll; }
+      if (pos_out) pos_out[i] = (int)pos;
+    }
+  }
+}
+// The sharded lookup's exchange payload in FIXED-CAPACITY segments (no size collective, no host sync): owner d's
+// segment is seg[d][0 .. C]: record 0 = header {pairs in the segment, 0}, records 1 .. = (id, occurrence count).
+// A record whose count is 0 is skipped by the owner's tile pass, so padding costs nothing but its bytes.  slot_of[u]
+// = where unique id u went (its row comes back at the same place).  More than C ids for one owner: the extra
+// ones are dropped and *overflow is raised (the host doubles C; hashed ownership keeps this from happening).
+__global__ void __launch_bounds__(TB) k_owner_scatter_fixed(const long long* __restrict__ ids, const int* __restrict__ cnts,
+                                                            long long n, int world, int rule,
+                                                            unsigned ntiles, const unsigned* __restrict__ base_off,
+                                                            unsigned C, long long* __restrict__ seg, int* __restrict__ slot_of,
+                                                            unsigned* __restrict__ overflow) {
+  __shared__ unsigned h[MAXW];
+  if ((int)threadIdx.x < world)   // rank inside the owner's bucket = global offset - the bucket's start
+    h[threadIdx.x] = base_off[(size_t)threadIdx.x * ntiles + blockIdx.x] - base_off[(size_t)threadIdx.x * ntiles];
+  __syncthreads();
+  const long long base = (long long)blockIdx.x * RT;
+#pragma unroll
+  for (int k = 0; k < RT / TB; ++k) {
+    const long long i = base + k * TB + threadIdx.x;
+    if (i < n && cnts[i] > 0) {   // the list has gaps (sparse unique numbers): a count of 0 names no key
+      const long long id = ids[i];
+      const unsigned d = owner_rank(id, world, rule);
+      const unsigned r = atomicAdd(&h[d], 1u);
+      if (r < C) {
+        const size_t slot = (size_t)d * (C + 1) + 1 + r;
+        seg[2 * slot] = id;
+        seg[2 * slot + 1] = (long long)cnts[i];
+        slot_of[i] = (int)slot;
+      } else {
+        slot_of[i] = 0;        // record 0 is a header: its "row" is never a real one
+        atomicExch(overflow, 1u);
+      }
+    }
+  }
+}
+// the segments' headers {records in the segment (at most C), 0}
+__global__ void k_seg_headers(const long long* __restrict__ counts, int world, unsigned C, long long* __restrict__ seg,
+                              unsigned* __restrict__ need) {
+  const int d = threadIdx.x;
+  if (need && d == 0) *need = 0u;
+  __syncthreads();
+  if (d < world) {
+    seg[2 * (size_t)d * (C + 1)] = counts[d] < (long long)C ? counts[d] : (long long)C;
+    seg[2 * (size_t)d * (C + 1) + 1] = 0;
+    if (need) atomicMax(need, (unsigned)(counts[d] < 0x7FFFFFFFll ? counts[d] : 0x7FFFFFFFll));
+  }
+}
+// k_owner_hist over the sparse unique list of the sharded route (entries with a count of 0 name no key)
+__global__ void __launch_bounds__(TB) k_owner_hist_u32(const long long* __restrict__ ids, const int* __restrict__ cnts, long long n,
+                                                       int world, int rule, unsigned ntiles, unsigned* __restrict__ hist) {
+  __shared__ unsigned h[MAXW];
+  if (threadIdx.x < MAXW) h[threadIdx.x] = 0;
+  __syncthreads();
+  const long long base = (long long)blockIdx.x * RT;
+#pragma unroll
+  for (int k = 0; k < RT / TB; ++k) {
+    const long long i = base + k * TB + threadIdx.x;
+    if (i < n && cnts[i] > 0) atomicAdd(&h[owner_rank(ids[i], world, rule)], 1u);
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < world) hist[(size_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
+}
+
+// ------------------------------------------------------------------------------------------
+// k_shard_finish: the sharded lookup's output rows from the records that came back
+// ------------------------------------------------------------------------------------------
+// out[i] = rows[slot_of[uniq_of_entry[tile * TILE + pos_ent[i]]]]: position -> its entry in the tile (k_ltile<NOTABLE>
+// filed it) -> the entry's distinct-id number (k_papply PA_UNIQUE wrote it to ent_b) -> the record the id was sent in
+// -> the row the owner returned.  A wave takes 64 positions, lane l resolves position l, the rows go VQ lanes per row
+// with streaming stores (the copy of goz_wave).
+template <int VQ, int CW = 4>
+__device__ __forceinline__ void shard_finish_body(const unsigned short* __restrict__ pos_ent, const unsigned* __restrict__ ent_u,
+                                                  const int* __restrict__ slot_of, const float* __restrict__ rows,
+                                                  float* __restrict__ out, long long n, int dim,
+                                                  const float* __restrict__ rows_self, unsigned self_lo, unsigned self_len) {
+  constexpr int RW = 64 / VQ;
+  const int lane = threadIdx.x & 63;
+  const int v = lane % VQ, sub = lane / VQ;
+  const int D4 = dim >> 2;   // float4 per row (<= VQ: lanes past it are masked)
+  const bool vlive = v < D4;
+  const int vv = vlive ? v : 0;
+  const long long nwaves = (long long)gridDim.x * (TB / 64);
+  for (long long r0 = ((long long)blockIdx.x * (TB / 64) + (threadIdx.x >> 6)) * 64; r0 < n; r0 += nwaves * 64) {
+    const long long i = r0 + lane;
+    unsigned rec = 0;   // record 0: a header's row (zeros) — positions past the end, ids that found no room in their segment
+    if (i < n) {
+      const unsigned e = pos_ent[i];
+      if (e != 0xFFFFu) rec = (unsigned)slot_of[ent_u[(size_t)(i / TILE) * TILE + e]];
+    }
+#pragma unroll
+    for (int j0 = 0; j0 < VQ; j0 += CW) {
+      float4 val[CW];
+      unsigned rj[CW];
+#pragma unroll
+      for (int j = 0; j < CW && j0 + j < VQ; ++j) rj[j] = __shfl(rec, (j0 + j) * RW + sub);
+#pragma unroll
+      for (int j = 0; j < CW && j0 + j < VQ; ++j)   // (records [self_lo, self_lo + self_len): this rank's own segment, read where the serve wrote it)
+        val[j] = reinterpret_cast<const float4*>((((unsigned)rj[j] - self_lo < self_len) ? rows_self : rows) + (size_t)rj[j] * dim)[vv];
+#pragma unroll
+      for (int j = 0; j < CW && j0 + j < VQ; ++j) {
+        const long long ii = r0 + (j0 + j) * RW + sub;
+        if (ii < n && vlive) {
+          float4* dst = reinterpret_cast<float4*>(out + (size_t)ii * dim) + v;
+          __builtin_nontemporal_store(val[j].x, &dst->x); __builtin_nontemporal_store(val[j].y, &dst->y);
+          __builtin_nontemporal_store(val[j].z, &dst->z); __builtin_nontemporal_store(val[j].w, &dst->w);
+        }
+      }
+    }
+  }
+}
+template <int VQ, int CW = 4>
+__global__ void __launch_bounds__(TB) k_shard_finish(const unsigned short* __restrict__ pos_ent, const unsigned* __restrict__ ent_u,
+                                                     const int* __restrict__ slot_of, const float* __restrict__ rows,
+                                                     float* __restrict__ out, long long n, int dim,
+                                                     const float* __restrict__ rows_self, unsigned self_lo, unsigned self_len) {
+  shard_finish_body<VQ, CW>(pos_ent, ent_u, slot_of, rows, out, n, dim, rows_self, self_lo, self_len);
+}
+// several tables of one row geometry in one launch (blockIdx.y = table)
+struct FinishDesc {
+  const unsigned short* pos_ent;
+  const unsigned* ent_u;
+  const int* slot_of;
+  const float* rows;
+  float* out;
+  long long n;
+  const float* rows_self;
+  unsigned self_lo, self_len;
+  int dim, pad;
+};
+template <int VQ, int CW = 4>
+__global__ void __launch_bounds__(TB) k_shard_finish_multi(const FinishDesc* __restrict__ descs) {
+  const FinishDesc d = descs[blockIdx.y];
+  shard_finish_body<VQ, CW>(d.pos_ent, d.ent_u, d.slot_of, d.rows, d.out, d.n, d.dim, d.rows_self, d.self_lo, d.self_len);
+}

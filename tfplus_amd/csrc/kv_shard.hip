@@ -1,0 +1,1313 @@
+// kv_shard.hip — sharded tables on the table core (kv_host.h): hashed ownership, fixed-capacity exchange, RCCL over xGMI
+// (SURVEY.md §8e).  kv_comm_* (RCCL by dlopen, grouped send / recv; or the caller's transport), kv_shard_* (route / serve /
+// finish phases and the whole ops), the batched kv_multi_shard_* ops, and kv_bucket_by_owner, the routing rule's
+// stand-alone form.  The only unit that knows RCCL; its own kernels are kv_route.h's.
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+#include <dlfcn.h>
+
+#include "kv_host.h"
+
+using namespace kvhip_internal;
+
+struct kv_comm {
+  ncclComm_t comm = nullptr;
+  int world = 1, rank = 0, device = 0;
+  hipStream_t stream = nullptr;      // the collectives' own stream
+  hipEvent_t ev_in = nullptr, ev_out = nullptr;
+  // host-staged transport (kv_comm_create_staged): the caller's callbacks move the segments
+  kv_comm_exchange_fn xfn = nullptr;
+  kv_comm_max_fn mfn = nullptr;
+  void* user = nullptr;
+  bool self_via_rccl = false;        // kv_comm_set_self_via_rccl: this rank's own segment goes through RCCL too
+};
+
+struct kv_shard {
+  kv_table* table = nullptr;         // this rank's share of the rows
+  kv_table* route = nullptr;         // owns the workspace of the local unique index (no rows of its own)
+  int world = 1, rank = 0, rule = KV_OWNER_HASH;
+  long long max_ids = 0;
+  unsigned C = 0;                    // (id, count) records per peer segment, header not counted
+  long long* uniq = nullptr;         // [max_ids]
+  int* ucnt = nullptr;               // [max_ids]
+  int* slot_of = nullptr;            // [max_ids] unique id -> record in the send buffer
+  long long* send_pairs = nullptr;   // [world][C + 1][2]
+  long long* recv_pairs = nullptr;
+  float* send_rows = nullptr;        // [world][C + 1][dim]
+  float* recv_rows = nullptr;
+  long long* counts = nullptr;       // [world]
+  unsigned* hist = nullptr;          // [world][tiles]
+  unsigned* gcount = nullptr;        // [MAXW + 1] the route's per-owner record counters (k_papply PA_UNIQUE; zero between launches)
+  unsigned* overflow = nullptr;      // pinned, mapped: a segment was too small for a batch
+  unsigned long long overflows = 0;  // batches reported so far
+  unsigned* need = nullptr;          // device [2]: the largest segment the last routed batch wanted; the same over all ranks
+  unsigned* need_host = nullptr;     // pinned copy of need[1]
+  bool lossless = true;              // ranks agree on the capacity before every exchange (the default: nothing can be lost);
+                                     // kv_shard_set_lossless(shard, 0) opts into the synchronisation-free mode
+  unsigned long long grows = 0;      // times the capacity was raised
+  long long n_last = 0;              // ids of the batch whose index `route` holds
+  bool self_in_place = false;        // this rank's own segments are read from the send buffers (no device copy in the exchange)
+  const kv_comm* verified = nullptr; // the communicator whose ranks were seen to agree on world / capacity / dim
+  uint64_t route_token = 0;
+  kv_batch_token_t serve_token = 0;
+  hipEvent_t ev_fork = nullptr, ev_done = nullptr;
+  int ranks_seen = 0;                // ranks whose handshake record arrived in the first exchange (shard_verify)
+  // per-phase timing of the whole ops (kv_shard_profile): events on the communicator's stream at the phase boundaries of
+  // every prof_every-th step; one sample in flight, collected by the next sampled call or by the read
+  int prof_every = 0;
+  unsigned prof_seq_l = 0, prof_seq_a = 0;
+  hipEvent_t pev[10] = {};           // lookup: [0..5] = 5 phases; apply: [6..9] = 3 phases
+  bool pend_l = false, pend_a = false;
+  double psum[KV_SHARD_PHASES] = {};
+  long long pcnt[KV_SHARD_PHASES] = {};
+};
+
+namespace {
+
+#include "kv_device.h"
+#include "kv_route.h"
+
+// RCCL is reached through dlopen: the copy the process already holds (PyTorch bundles one under the same soname)
+// is reused, so there is one RCCL per process; nothing links against it when the table is not sharded
+struct RcclApi {
+  void* lib = nullptr;
+  ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
+  ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
+  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
+  ncclResult_t (*GroupStart)() = nullptr;
+  ncclResult_t (*GroupEnd)() = nullptr;
+  ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
+  ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
+  ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;   // lossless mode only
+  const char* (*GetErrorString)(ncclResult_t) = nullptr;
+  bool ok = false;
+};
+
+RcclApi* rccl() {
+  static RcclApi api;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    // PyTorch's wheel carries its RCCL under the soname librccl.so, ROCm's own is librccl.so.1: whichever the process
+    // already holds wins, so that there is one RCCL (one set of xGMI channels) per process
+    for (const char* name : {"librccl.so", "librccl.so.1"})
+      if ((api.lib = dlopen(name, RTLD_NOW | RTLD_NOLOAD))) break;
+    if (!api.lib)
+      for (const char* name : {"librccl.so.1", "librccl.so"})
+        if ((api.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL))) break;
+    if (!api.lib) return;
+    auto sym = [&](const char* n) { return dlsym(api.lib, n); };
+    api.GetUniqueId = reinterpret_cast<decltype(api.GetUniqueId)>(sym("ncclGetUniqueId"));
+    api.CommInitRank = reinterpret_cast<decltype(api.CommInitRank)>(sym("ncclCommInitRank"));
+    api.CommDestroy = reinterpret_cast<decltype(api.CommDestroy)>(sym("ncclCommDestroy"));
+    api.GroupStart = reinterpret_cast<decltype(api.GroupStart)>(sym("ncclGroupStart"));
+    api.GroupEnd = reinterpret_cast<decltype(api.GroupEnd)>(sym("ncclGroupEnd"));
+    api.Send = reinterpret_cast<decltype(api.Send)>(sym("ncclSend"));
+    api.Recv = reinterpret_cast<decltype(api.Recv)>(sym("ncclRecv"));
+    api.AllReduce = reinterpret_cast<decltype(api.AllReduce)>(sym("ncclAllReduce"));
+    api.GetErrorString = reinterpret_cast<decltype(api.GetErrorString)>(sym("ncclGetErrorString"));
+    api.ok = api.GetUniqueId && api.CommInitRank && api.CommDestroy && api.GroupStart && api.GroupEnd && api.Send && api.Recv;
+  });
+  return &api;
+}
+
+#define NCCL_TRY(expr)                                                                                      \
+  do {                                                                                                      \
+    ncclResult_t _r = (expr);                                                                               \
+    if (_r != ncclSuccess)                                                                                  \
+      return fail(KV_INTERNAL, "%s failed: %s", #expr, rccl()->GetErrorString ? rccl()->GetErrorString(_r) : "?"); \
+  } while (0)
+
+// the segments really travel (RCCL or the caller's transport); else: a world of one whose exchange is a device copy
+static inline bool wired(const kv_comm* c) { return c->comm != nullptr || c->xfn != nullptr; }
+
+// phase timing of the whole sharded ops (kv_shard_profile): see kv_shard
+void shard_prof_collect(kv_shard* sh, bool lookup) {
+  bool& pend = lookup ? sh->pend_l : sh->pend_a;
+  if (!pend) return;
+  const int e0 = lookup ? 0 : 6, np = lookup ? 5 : 3, p0 = lookup ? 0 : 5;
+  if (hipEventSynchronize(sh->pev[e0 + np]) == hipSuccess)
+    for (int i = 0; i < np; ++i) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, sh->pev[e0 + i], sh->pev[e0 + i + 1]) == hipSuccess) { sh->psum[p0 + i] += ms; sh->pcnt[p0 + i] += 1; }
+    }
+  pend = false;
+}
+
+// does this call carry markers?  (collects the previous sample first: its events are about to be reused)
+bool shard_prof_begin(kv_shard* sh, bool lookup) {
+  if (sh->prof_every <= 0) return false;
+  unsigned& seq = lookup ? sh->prof_seq_l : sh->prof_seq_a;
+  if ((seq++ % (unsigned)sh->prof_every) != 0u) return false;
+  shard_prof_collect(sh, lookup);
+  for (hipEvent_t& e : sh->pev)
+    if (!e && hipEventCreate(&e) != hipSuccess) return false;
+  return true;
+}
+
+inline void shard_prof_mark(kv_shard* sh, bool on, int ev, hipStream_t w) { if (on) hipEventRecord(sh->pev[ev], w); }
+
+void shard_free_buffers(kv_shard* sh) {
+  hipFree(sh->send_pairs); hipFree(sh->recv_pairs); hipFree(sh->send_rows); hipFree(sh->recv_rows);
+  sh->send_pairs = sh->recv_pairs = nullptr; sh->send_rows = sh->recv_rows = nullptr;
+}
+
+int shard_alloc_buffers(kv_shard* sh, unsigned C) {
+  const size_t rec = (size_t)sh->world * (C + 1);
+  if (rec > (1ull << 21)) return fail(KV_INVALID_ARGUMENT, "peer_capacity %u x world %d exceeds 2^21 records per exchange", C, sh->world);
+  shard_free_buffers(sh);
+  HIP_TRY(hipMalloc(&sh->send_pairs, rec * 16));
+  HIP_TRY(hipMalloc(&sh->recv_pairs, rec * 16));
+  HIP_TRY(hipMalloc(&sh->send_rows, rec * sh->table->dim * sizeof(float)));
+  HIP_TRY(hipMalloc(&sh->recv_rows, rec * sh->table->dim * sizeof(float)));
+  HIP_TRY(hipMemset(sh->send_pairs, 0, rec * 16));
+  HIP_TRY(hipMemset(sh->recv_pairs, 0, rec * 16));
+  sh->C = C;
+  return KV_OK;
+}
+
+// bytes_per_peer bytes to / from every rank: grouped ncclSend / ncclRecv (xGMI is point to point: one pair per
+// link), on the communicator's own stream, behind everything `stream` was given and in front of what it gets next.
+// nseg buffers (the tables of a multi-table step) go out in ONE group: RCCL runs a group's sends and receives as one
+// launch, so 40 tables cost one exchange, not 40.
+// skip_self[k] (may be null): segment k of this rank is read from its send buffer by the kernels themselves
+static int comm_exchange(kv_comm* c, int nseg, const void* const* sends, void* const* recvs, const int64_t* bytes_per_peer, hipStream_t s,
+                         const char* skip_self = nullptr) {
+  if (c->xfn) {   // the caller's transport: everything queued so far has run, then the segments move on the host's clock
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int k = 0; k < nseg; ++k) {
+      const int r = c->xfn(c->user, sends[k], recvs[k], bytes_per_peer[k]);
+      if (r) return fail(KV_INTERNAL, "the staged exchange failed (callback returned %d)", r);
+    }
+    return KV_OK;
+  }
+  if (!c->comm) {   // world of one without RCCL
+    for (int k = 0; k < nseg; ++k)
+      if (!(skip_self && skip_self[k]))
+        HIP_TRY(hipMemcpyAsync(recvs[k], sends[k], (size_t)bytes_per_peer[k], hipMemcpyDeviceToDevice, s));
+    return KV_OK;
+  }
+  const bool hop = s != c->stream;   // the sharded ops run on the communicator's stream themselves: no hop
+  if (hop) {
+    HIP_TRY(hipEventRecord(c->ev_in, s));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_in, 0));
+  }
+  // this rank's own segment never meets RCCL: it stays in place (skip_self: the sharded whole ops read it in the send
+  // buffer) or is a device copy at HBM speed, queued in front of the group — unless kv_comm_set_self_via_rccl asked for
+  // it to go through ncclSend / ncclRecv like a peer's
+  const bool self_rccl = c->self_via_rccl;
+  if (!self_rccl)
+    for (int k = 0; k < nseg; ++k)
+      if (!(skip_self && skip_self[k]))
+        HIP_TRY(hipMemcpyAsync((char*)recvs[k] + (size_t)c->rank * bytes_per_peer[k], (const char*)sends[k] + (size_t)c->rank * bytes_per_peer[k],
+                             (size_t)bytes_per_peer[k], hipMemcpyDeviceToDevice, c->stream));
+  const bool grouped = c->world > 1 || self_rccl;
+  if (grouped) NCCL_TRY(rccl()->GroupStart());
+  ncclResult_t bad = ncclSuccess;   // a failed Send / Recv must not leave the group open on this communicator
+  for (int p = 0; p < c->world && bad == ncclSuccess; ++p) {
+    if (p == c->rank && !self_rccl) continue;
+    for (int k = 0; k < nseg && bad == ncclSuccess; ++k) {   // peer-major: both ends of a pair post the tables in the same order
+      const size_t b = (size_t)bytes_per_peer[k];
+      bad = rccl()->Send((const char*)sends[k] + (size_t)p * b, b, ncclChar, p, c->comm, c->stream);
+      if (bad == ncclSuccess) bad = rccl()->Recv((char*)recvs[k] + (size_t)p * b, b, ncclChar, p, c->comm, c->stream);
+    }
+  }
+  if (grouped) {
+    const ncclResult_t e = rccl()->GroupEnd();
+    if (bad == ncclSuccess) bad = e;
+  }
+  if (bad != ncclSuccess)
+    return fail(KV_INTERNAL, "grouped send / recv failed: %s", rccl()->GetErrorString ? rccl()->GetErrorString(bad) : "?");
+  if (hop) {
+    HIP_TRY(hipEventRecord(c->ev_out, c->stream));
+    HIP_TRY(hipStreamWaitEvent(s, c->ev_out, 0));
+  }
+  return KV_OK;
+}
+
+// A batch that sent one owner more than peer_capacity distinct ids raised the pinned flag (the surplus read zeros).
+// It is reported by the first call that ENDS after the flag landed — after that call has queued all its work, so a
+// rank that reports keeps step with its peers (an early return would leave them waiting in the exchange).  The
+// capacity is not changed here: it must change on every rank at once.
+// (`seen` is the flag as the call found it when it STARTED: a batch's own overflow is reported by the next call, never
+// by itself — which call reports does not depend on how fast the kernels ran.)
+static unsigned shard_take_flag(kv_shard* sh) {
+  return __atomic_exchange_n(sh->overflow, 0u, __ATOMIC_RELAXED);
+}
+
+static int shard_late_report(kv_shard* sh, unsigned seen) {
+  if (!seen) return KV_OK;
+  ++sh->overflows;
+  return fail(KV_RESOURCE_EXHAUSTED, "an earlier sharded batch sent one owner more than peer_capacity (%u) distinct ids: the surplus "
+                                     "ids read zeros and their gradients were dropped (this call itself was queued in full); "
+                                     "create the shards with a larger peer_capacity on every rank", sh->C);
+}
+
+// The whole-op entry points (kv_shard_lookup / kv_shard_apply / kv_multi_shard_*) do the exchanges themselves, so they
+// leave this rank's own segments where they are: every kernel that reads a receive buffer downstream (the owner lookup's
+// tile pass, the finish, the owner apply's tile sums and k_papply) takes records [rank * (C + 1), +C + 1) from the send
+// buffer.
+static bool shard_can_stay(const kv_shard* sh) {
+  return (long long)sh->world * (sh->C + 1) <= FUSED_MAX_N;
+}
+
+// ... as the owner ops are told (ws_view): the (id, count) records, and for the apply (grad) the summed gradient rows
+static SelfSegment shard_self(const kv_shard* sh, bool grad) {
+  if (!sh->self_in_place) return SelfSegment{};
+  return SelfSegment{(unsigned)sh->rank * (sh->C + 1), sh->C + 1, sh->send_pairs, grad ? sh->send_rows : nullptr};
+}
+
+// ids -> local unique ids with counts -> the owners' segments of the send buffer.  2 launches (deterministic mode: 6), no host sync.
+static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_stream_t stream) {
+  if (!sh || (n > 0 && !ids) || n < 0 || n > sh->max_ids) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_route: n %lld (max %lld)", (long long)n, sh ? sh->max_ids : 0ll);
+  DeviceGuard dg(sh->table->device);
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  kv_table* rt = sh->route;
+  std::lock_guard<std::mutex> l(rt->mu);
+  if ((rc = hand_over(rt, s))) return rc;   // the phases of one shard keep their order whatever streams they are given
+  rt->deterministic = sh->table->deterministic;   // the route index (tile pass, position order) follows the table's mode
+  sh->n_last = n;
+  sh->route_token = 0;
+  if (n == 0) {
+    HIP_TRY(hipMemsetAsync(sh->counts, 0, (size_t)sh->world * 8, s));
+    k_seg_headers<<<1, MAXW, 0, s>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
+    return KV_OK;
+  }
+  if ((rc = ensure_workspace(rt, n, true, s))) return rc;
+  WsDev wd = ws_view(rt, n);
+  // The route's index on the entry-list kernels:
+  // a table-less tile pass (k_ltile<NOTABLE>: entries, mrow, every position's entry number) and k_papply in PA_UNIQUE
+  // mode (the distinct ids numbered, uniq / ucnt written, every entry learns its id's number).  The finish then reads
+  // position -> entry -> number -> record, the gradient pre-sum is k_tsum + k_papply PA_DEDUP.
+  PartArgs pa{};
+  pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
+  pa.out_keys = sh->uniq;
+  pa.out_counts = sh->ucnt;
+  pa.sparse_unique = 1;   // unique numbers with gaps: no counter to serialise on
+  pa.det = sh->table->deterministic ? 1 : 0;
+  pa.n = n;
+  Workspace& ws = rt->ws;
+  if (ws.pos_cap < n) {
+    HIP_TRY(hipStreamSynchronize(s));
+    ws.pos_cap = 0;
+    if ((rc = regrow(&ws.pos_ent, (size_t)std::max<long long>(n, ws.cap_n)))) return rc;
+    ws.pos_cap = std::max<long long>(n, ws.cap_n);
+  }
+  rt->fused_index = true;
+  choose_partitions(rt, wd, n);   // (the distinct-id hint of the previous route of this length: k_papply publishes it)
+  WsDev wz = wd;
+  wz.zero_counts = sh->ucnt;
+  wz.pos_ent = ws.pos_ent;
+  launch_ltile_notable(rt, pa.tv, wz, ids, n, s);
+  pa.day_lk = pa.day;
+  if (!pa.det) {   // the numbered ids go straight to their owners' segments (the deterministic mode keeps the ordered scatter below)
+    pa.route_world = sh->world; pa.route_rule = sh->rule; pa.route_C = sh->C;
+    pa.route_seg = sh->send_pairs; pa.route_slot_of = sh->slot_of; pa.route_overflow = sh->overflow; pa.route_gcount = sh->gcount;
+    pa.route_need = sh->need; pa.route_uhint = sh->overflow + 1;   // (the launch's last block writes the headers)
+  }
+  if ((rc = launch_papply_ud(wd, pa, PA_UNIQUE, s))) return fail(rc, "route: no kernel for dim %d", rt->dim);
+  rt->batch_serial = ++g_serial;
+  rt->batch_n = n;
+  sh->route_token = rt->batch_serial;
+  if (pa.det) {   // the ordered owner scatter
+    const unsigned ntr = (unsigned)((n + RT - 1) / RT);
+    k_owner_hist_u32<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, (long long)n, sh->world, sh->rule, ntr, sh->hist);
+    k_owner_scan<<<1, 1024, 0, s>>>(sh->hist, ntr * sh->world, ntr, sh->world, sh->counts);
+    k_seg_headers<<<1, MAXW, 0, s>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
+    k_owner_scatter_fixed<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, (long long)n, sh->world, sh->rule, ntr, sh->hist, sh->C, sh->send_pairs,
+                                             sh->slot_of, sh->overflow);
+  }
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+static int shard_exchange_one(kv_comm* comm, const void* send, void* recv, int64_t bytes_per_peer, hipStream_t w, char stay) {
+  return comm_exchange(comm, 1, &send, &recv, &bytes_per_peer, w, &stay);
+}
+
+static int shard_fork(kv_shard* sh, hipStream_t s, hipStream_t work) {
+  if (s == work) return KV_OK;   // the caller works on the communicator's stream itself: one queue, no hops
+  HIP_TRY(hipEventRecord(sh->ev_fork, s));
+  HIP_TRY(hipStreamWaitEvent(work, sh->ev_fork, 0));
+  return KV_OK;
+}
+
+static int shard_done(kv_shard* sh, hipStream_t s, hipStream_t work, int join) {
+  HIP_TRY(hipEventRecord(sh->ev_done, work));
+  if (join && s != work) HIP_TRY(hipStreamWaitEvent(s, sh->ev_done, 0));
+  return KV_OK;
+}
+
+// Once per (shard, communicator): every rank tells every other its {world, rank, capacity, dim, owner rule}.  The
+// exchange has no size negotiation, so ranks that disagree would otherwise hang in RCCL or read each other's padding.
+static int shard_verify(kv_shard* sh, kv_comm* comm) {
+  if (sh->verified == comm) return KV_OK;
+  const int W = sh->world;
+  std::vector<long long> mine((size_t)W * 4), theirs((size_t)W * 4, 0);
+  for (int p = 0; p < W; ++p) {
+    mine[4 * p] = ((long long)W << 32) | (unsigned)sh->rank;
+    mine[4 * p + 1] = sh->C; mine[4 * p + 2] = sh->table->dim; mine[4 * p + 3] = sh->rule;
+  }
+  long long *ds = nullptr, *dr = nullptr;
+  HIP_TRY(hipMalloc(&ds, mine.size() * 8));
+  if (hipMalloc(&dr, mine.size() * 8) != hipSuccess) { hipFree(ds); return fail(KV_RESOURCE_EXHAUSTED, "kv_shard: out of memory"); }
+  int rc = KV_OK;
+  do {
+    if (hipMemcpy(ds, mine.data(), mine.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(KV_INTERNAL, "kv_shard: copy"); break; }
+    if ((rc = kv_comm_all_to_all(comm, ds, dr, wired(comm) ? 32 : 32 * W, comm->stream))) break;
+    if (hipStreamSynchronize(comm->stream) != hipSuccess || hipMemcpy(theirs.data(), dr, theirs.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+      rc = fail(KV_INTERNAL, "kv_shard: the first exchange failed");
+      break;
+    }
+    for (int p = 0; p < W && !rc; ++p) {
+      if ((theirs[4 * p] >> 32) != W || (int)(theirs[4 * p] & 0xFFFFFFFF) != (wired(comm) ? p : sh->rank))
+        rc = fail(KV_FAILED_PRECONDITION, "kv_shard: rank %d of the communicator is not shard %d of a world of %d", p, p, W);
+      else if (theirs[4 * p + 1] != (long long)sh->C || theirs[4 * p + 2] != sh->table->dim || theirs[4 * p + 3] != sh->rule)
+        rc = fail(KV_FAILED_PRECONDITION, "kv_shard: rank %d was created with peer_capacity %lld, dim %lld, owner rule %lld; this "
+                                          "rank with %u, %d, %d — they must be equal on every rank",
+                  p, theirs[4 * p + 1], theirs[4 * p + 2], theirs[4 * p + 3], sh->C, sh->table->dim, sh->rule);
+    }
+  } while (0);
+  hipFree(ds); hipFree(dr);
+  if (!rc) { sh->verified = comm; sh->ranks_seen = W; }
+  return rc;
+}
+
+// Lossless mode (kv_shard_set_lossless): before anything is exchanged every rank learns the largest segment ANY rank's
+// route wanted (one 4-byte all-reduce per table, one stream synchronisation for all tables) and, when that exceeds the
+// capacity, every rank raises its capacity to the same new value — they all computed it from the same number — and
+// routes the batch again.  grown[k] != 0: shards[k] must be routed again.  The price is the host round trip per lookup
+// that the default mode avoids; nothing is ever dropped.
+static int shard_agree_many(const kv_shard_t* shards, int ntab, kv_comm* comm, hipStream_t w, char* grown) {
+  bool any = false;
+  for (int k = 0; k < ntab; ++k) { grown[k] = 0; any = any || shards[k]->lossless; }
+  if (!any) return KV_OK;
+  if (comm->comm) {
+    if (!rccl()->AllReduce) return fail(KV_UNIMPLEMENTED, "lossless sharding needs ncclAllReduce");
+    NCCL_TRY(rccl()->GroupStart());
+    ncclResult_t bad = ncclSuccess;
+    for (int k = 0; k < ntab && bad == ncclSuccess; ++k)
+      if (shards[k]->lossless)
+        bad = rccl()->AllReduce(shards[k]->need, shards[k]->need + 1, 1, ncclUint32, ncclMax, comm->comm, w);
+    const ncclResult_t e = rccl()->GroupEnd();
+    if (bad == ncclSuccess) bad = e;
+    if (bad != ncclSuccess) return fail(KV_INTERNAL, "ncclAllReduce failed: %s", rccl()->GetErrorString ? rccl()->GetErrorString(bad) : "?");
+  }
+  for (int k = 0; k < ntab; ++k)
+    if (shards[k]->lossless)
+      HIP_TRY(hipMemcpyAsync(shards[k]->need_host, shards[k]->need + (comm->comm ? 1 : 0), sizeof(unsigned), hipMemcpyDeviceToHost, w));
+  HIP_TRY(hipStreamSynchronize(w));
+  if (comm->xfn && comm->world > 1) {   // the caller's transport: the maximum over the ranks, table by table
+    if (!comm->mfn) return fail(KV_UNIMPLEMENTED, "lossless sharding over a staged communicator needs its max_u32 callback");
+    for (int k = 0; k < ntab; ++k)
+      if (shards[k]->lossless) {
+        uint32_t v = *shards[k]->need_host;
+        const int r = comm->mfn(comm->user, &v);
+        if (r) return fail(KV_INTERNAL, "the staged agreement failed (callback returned %d)", r);
+        *shards[k]->need_host = v;
+      }
+  }
+  for (int k = 0; k < ntab; ++k) {
+    kv_shard* sh = shards[k];
+    if (!sh->lossless) continue;
+    const unsigned need = *sh->need_host;
+    if (need <= sh->C) continue;
+    const long long newC = std::min<long long>(sh->max_ids, (long long)need + need / 4 + 64);
+    int rc;
+    if ((rc = shard_alloc_buffers(sh, (unsigned)newC))) return rc;
+    *reinterpret_cast<volatile unsigned*>(sh->overflow) = 0;   // raised by the attempt that is now repeated
+    ++sh->grows;
+    grown[k] = 1;
+  }
+  return KV_OK;
+}
+
+// Several sharded tables in one step (the 40 embedding tables of a DCN): every table's route phase, then ONE grouped
+// exchange carrying all their segments, every table's serve phase, ONE exchange back, every table's finish — two
+// exchanges per lookup and one per apply whatever the number of tables.  Same results as the per-table ops.
+static int multi_shard_check(const kv_shard_t* shards, int ntab, kv_comm_t comm, const char* what) {
+  if (!shards || ntab < 1 || ntab > 4096 || !comm) return fail(KV_INVALID_ARGUMENT, "%s: bad arguments", what);
+  for (int k = 0; k < ntab; ++k) {
+    if (!shards[k] || shards[k]->world != comm->world || shards[k]->table->device != shards[0]->table->device)
+      return fail(KV_INVALID_ARGUMENT, "%s: shard %d / communicator mismatch", what, k);
+    for (int j = 0; j < k; ++j)
+      if (shards[j] == shards[k]) return fail(KV_INVALID_ARGUMENT, "%s: shard %d is listed twice", what, k);
+  }
+  return KV_OK;
+}
+
+// ---- several sharded tables, one launch per phase -----------------------------------------------------
+// The route-side phases of kv_multi_shard_* run on the shards' private route tables; a table takes part in the batched
+// launches when its route is the entry-list one without the ordered owner scatter (not the deterministic mode, a batch
+// that is not empty); the others go through the per-table functions as before.
+static bool shard_batchable(const kv_shard* sh, int64_t n) {
+  return !sh->table->deterministic && n > 0 && n <= sh->max_ids;
+}
+
+// route of the tables todo[0..m): the table-less tile pass of all of them (grid.y = table), then k_papply_multi in
+// PA_UNIQUE mode — numbering, the owners' segments, and each table's headers by its own last block.  2 launches.
+static int multi_route_impl(const kv_shard_t* shards, const int* todo, int m, const void* const* ids, const int64_t* n, hipStream_t s) {
+  int rc;
+  const int device = shards[todo[0]]->table->device;
+  std::vector<kv_table*> rts;
+  for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
+  MultiLock lock(rts);
+  for (int j = 0; j < m; ++j) {
+    kv_shard* sh = shards[todo[j]];
+    kv_table* rt = sh->route;
+    if ((rc = hand_over(rt, s))) return rc;
+    rt->deterministic = false;
+    sh->n_last = n[todo[j]];
+    sh->route_token = 0;
+    if ((rc = ensure_workspace(rt, sh->n_last, true, s))) return rc;
+    Workspace& ws = rt->ws;
+    if (ws.pos_cap < sh->n_last) {
+      HIP_TRY(hipStreamSynchronize(s));
+      ws.pos_cap = 0;
+      if ((rc = regrow(&ws.pos_ent, (size_t)std::max<long long>(sh->n_last, ws.cap_n)))) return rc;
+      ws.pos_cap = std::max<long long>(sh->n_last, ws.cap_n);
+    }
+  }
+  BatchStage& st = g_stage[device][1];
+  StageSlot* sl = nullptr;
+  if ((rc = stage_acquire(st, (size_t)m * sizeof(MultiDesc), &sl))) return rc;
+  StageRelease rel{st, sl, s};
+  MultiDesc* hd = reinterpret_cast<MultiDesc*>(sl->host);
+  WsDev wmax{};
+  for (int j = 0; j < m; ++j) {
+    kv_shard* sh = shards[todo[j]];
+    kv_table* rt = sh->route;
+    MultiDesc& d = hd[j];
+    std::memset(&d, 0, sizeof d);
+    d.w = ws_view(rt, sh->n_last);
+    rt->fused_index = true;
+    choose_partitions(rt, d.w, sh->n_last);
+    d.w.zero_counts = sh->ucnt;
+    d.w.pos_ent = rt->ws.pos_ent;
+    PartArgs& pa = d.a;
+    pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
+    pa.out_keys = sh->uniq; pa.out_counts = sh->ucnt;
+    pa.sparse_unique = 1;
+    pa.det = 0;
+    pa.n = sh->n_last;
+    pa.day_lk = pa.day;
+    pa.route_world = sh->world; pa.route_rule = sh->rule; pa.route_C = sh->C;
+    pa.route_seg = sh->send_pairs; pa.route_slot_of = sh->slot_of; pa.route_overflow = sh->overflow; pa.route_gcount = sh->gcount;
+    pa.route_need = sh->need; pa.route_uhint = sh->overflow + 1;
+    d.ids = ids[todo[j]];
+    d.n = sh->n_last;
+    wmax.ntiles = std::max(wmax.ntiles, d.w.ntiles);
+    wmax.P = std::max(wmax.P, d.w.P);
+  }
+  HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, (size_t)m * sizeof(MultiDesc), hipMemcpyHostToDevice, s));
+  rel.launched = true;
+  const MultiDesc* md = reinterpret_cast<const MultiDesc*>(sl->dev);
+  launch_ltile_multi_notable(wmax, m, md, s);
+  // (PA_UNIQUE never reaches the code that depends on the row geometry: one variant serves every dim)
+  PartArgs p0 = hd[0].a;
+  p0.tv.dim = 4;
+  if ((rc = launch_papply_ud(wmax, p0, PA_UNIQUE, s, md, m))) return fail(rc, "route: no kernel");
+  for (int j = 0; j < m; ++j) {
+    kv_shard* sh = shards[todo[j]];
+    kv_table* rt = sh->route;
+    rt->batch_serial = ++g_serial;
+    rt->batch_n = sh->n_last;
+    sh->route_token = rt->batch_serial;
+  }
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+// finish of the tables todo[0..m) — all of one row geometry (row_lanes(dim)): 1 launch
+static int multi_finish_impl(const kv_shard_t* shards, const int* todo, int m, float* const* outs, hipStream_t s) {
+  int rc;
+  const int device = shards[todo[0]]->table->device;
+  std::vector<kv_table*> rts;
+  for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
+  MultiLock lock(rts);
+  BatchStage& st = g_stage[device][1];
+  StageSlot* sl = nullptr;
+  if ((rc = stage_acquire(st, (size_t)m * sizeof(FinishDesc), &sl))) return rc;
+  StageRelease rel{st, sl, s};
+  FinishDesc* hd = reinterpret_cast<FinishDesc*>(sl->host);
+  long long nmax = 0;
+  for (int j = 0; j < m; ++j) {
+    kv_shard* sh = shards[todo[j]];
+    kv_table* rt = sh->route;
+    if (rt->batch_serial != sh->route_token || sh->route_token == 0) return fail(KV_FAILED_PRECONDITION, "kv_multi_shard_lookup: finish without route");
+    if (!outs[todo[j]]) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_lookup: output pointer is null");
+    if ((rc = hand_over(rt, s))) return rc;
+    FinishDesc& d = hd[j];
+    d.pos_ent = rt->ws.pos_ent; d.ent_u = rt->ws.ent_b; d.slot_of = sh->slot_of; d.rows = sh->recv_rows; d.out = outs[todo[j]];
+    d.n = sh->n_last; d.rows_self = sh->send_rows;
+    d.self_lo = (unsigned)sh->rank * (sh->C + 1); d.self_len = sh->self_in_place ? sh->C + 1 : 0u;
+    d.dim = rt->dim; d.pad = 0;
+    nmax = std::max<long long>(nmax, sh->n_last);
+  }
+  HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, (size_t)m * sizeof(FinishDesc), hipMemcpyHostToDevice, s));
+  rel.launched = true;
+  const FinishDesc* md = reinterpret_cast<const FinishDesc*>(sl->dev);
+  const dim3 grid((unsigned)nblocks(nmax, TB, 8192), (unsigned)m);
+#define KV_SFM(VQ) k_shard_finish_multi<VQ><<<grid, TB, 0, s>>>(md)
+  switch (row_lanes(shards[todo[0]]->table->dim)) {
+    case 1: KV_SFM(1); break;   case 2: KV_SFM(2); break;   case 4: KV_SFM(4); break;   case 8: KV_SFM(8); break;
+    case 16: KV_SFM(16); break; case 32: KV_SFM(32); break; default: KV_SFM(64); break;
+  }
+#undef KV_SFM
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+// gradient pre-sum of the tables todo[0..m) — all of one dim: the tile sums, then k_papply_multi PA_DEDUP.  2 launches.
+static int multi_presum_impl(const kv_shard_t* shards, const int* todo, int m, const float* const* grads, hipStream_t s) {
+  int rc;
+  const int device = shards[todo[0]]->table->device;
+  std::vector<kv_table*> rts;
+  for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
+  MultiLock lock(rts);
+  for (int j = 0; j < m; ++j) {
+    kv_shard* sh = shards[todo[j]];
+    kv_table* rt = sh->route;
+    if (rt->batch_serial != sh->route_token || sh->route_token == 0)
+      return fail(KV_FAILED_PRECONDITION, "kv_multi_shard_apply: the batch's lookup must come first");
+    if (!grads[todo[j]]) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_apply: grad pointer is null");
+    if ((rc = hand_over(rt, s))) return rc;
+    if ((rc = ensure_workspace(rt, sh->n_last, true, s))) return rc;
+  }
+  BatchStage& st = g_stage[device][1];
+  StageSlot* sl = nullptr;
+  if ((rc = stage_acquire(st, (size_t)m * sizeof(MultiDesc), &sl))) return rc;
+  StageRelease rel{st, sl, s};
+  MultiDesc* hd = reinterpret_cast<MultiDesc*>(sl->host);
+  WsDev wmax{};
+  long long nmax = 0;
+  for (int j = 0; j < m; ++j) {
+    kv_shard* sh = shards[todo[j]];
+    kv_table* rt = sh->route;
+    MultiDesc& d = hd[j];
+    std::memset(&d, 0, sizeof d);
+    d.w = ws_view(rt, sh->n_last);
+    if (rt->index_P) { d.w.P = rt->index_P; d.w.pshift = 64 - ilog2(d.w.P); }
+    PartArgs& pa = d.a;
+    pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
+    pa.grad = grads[todo[j]];
+    pa.out_sum = sh->send_rows;
+    pa.out_map = sh->slot_of;
+    pa.det = 0;
+    pa.n = sh->n_last;
+    pa.epart = d.w.epart;
+    pa.day_lk = pa.day;
+    d.n = sh->n_last;
+    wmax.ntiles = std::max(wmax.ntiles, d.w.ntiles);
+    wmax.P = std::max(wmax.P, d.w.P);
+    nmax = std::max<long long>(nmax, sh->n_last);
+  }
+  HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, (size_t)m * sizeof(MultiDesc), hipMemcpyHostToDevice, s));
+  rel.launched = true;
+  const MultiDesc* md = reinterpret_cast<const MultiDesc*>(sl->dev);
+  if ((rc = launch_tsum(hd[0].a.tv, wmax, nullptr, s, md, m))) return fail(rc, "tile sums: no kernel for dim %d", hd[0].a.tv.dim);
+  if ((rc = launch_papply_ud(wmax, hd[0].a, PA_DEDUP, s, md, m))) return fail(rc, "gradient pre-sum: no kernel for dim %d", hd[0].a.tv.dim);
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kv_bucket_by_owner(kv_handle_t t, const void* ids, int64_t n, const int64_t* n_dev, int world, int owner_rule, int64_t* out_ids,
+                       int32_t* perm, int64_t* counts_dev, const int32_t* id_counts, int64_t* pairs_out,
+                       int32_t* pos_out, kv_stream_t stream) {
+  int rc;
+  if ((rc = check_table(t))) return rc;
+  if (world < 1 || world > MAXW) return fail(KV_INVALID_ARGUMENT, "world %d: 1..%d ranks", world, MAXW);
+  if (owner_rule != KV_OWNER_HASH && owner_rule != KV_OWNER_MOD) return fail(KV_INVALID_ARGUMENT, "owner_rule %d", owner_rule);
+  if (n < 0 || n > (1ll << 31) - 1 || (n > 0 && (!ids || !out_ids || !perm)) || !counts_dev)
+    return fail(KV_INVALID_ARGUMENT, "bad arguments");
+  DeviceGuard dg(t->device);
+  std::lock_guard<std::mutex> l(t->mu);
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned ntiles = (unsigned)((n + RT - 1) / RT);
+  const size_t need = (size_t)std::max(1u, ntiles) * world;
+  if (t->route_hist_cap < need) {
+    HIP_TRY(hipStreamSynchronize(s));
+    hipFree(t->route_hist);
+    HIP_TRY(hipMalloc(&t->route_hist, need * sizeof(unsigned)));
+    t->route_hist_cap = need;
+  }
+  if (n == 0) {
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)world * sizeof(long long), s));
+    return KV_OK;
+  }
+  if (t->key_dtype == KV_DT_INT32) {
+    k_owner_hist<int><<<ntiles, TB, 0, s>>>((const int*)ids, n, world, owner_rule, ntiles, t->route_hist, (const long long*)n_dev);
+    k_owner_scan<<<1, 1024, 0, s>>>(t->route_hist, ntiles * world, ntiles, world, (long long*)counts_dev);
+    k_owner_scatter<int><<<ntiles, TB, 0, s>>>((const int*)ids, n, world, owner_rule, ntiles, t->route_hist, (long long*)out_ids, perm,
+                                               (const long long*)n_dev, id_counts, (long long*)pairs_out, pos_out);
+  } else {
+    k_owner_hist<long long><<<ntiles, TB, 0, s>>>((const long long*)ids, n, world, owner_rule, ntiles, t->route_hist,
+                                                  (const long long*)n_dev);
+    k_owner_scan<<<1, 1024, 0, s>>>(t->route_hist, ntiles * world, ntiles, world, (long long*)counts_dev);
+    k_owner_scatter<long long><<<ntiles, TB, 0, s>>>((const long long*)ids, n, world, owner_rule, ntiles, t->route_hist,
+                                                     (long long*)out_ids, perm, (const long long*)n_dev, id_counts,
+                                                     (long long*)pairs_out, pos_out);
+  }
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+int kv_comm_unique_id(void* id128) {
+  if (!id128) return fail(KV_INVALID_ARGUMENT, "id128 is null");
+  if (!rccl()->ok) return fail(KV_UNIMPLEMENTED, "librccl.so.1 could not be loaded");
+  static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId");
+  NCCL_TRY(rccl()->GetUniqueId(reinterpret_cast<ncclUniqueId*>(id128)));
+  return KV_OK;
+}
+
+int kv_comm_create(int world, int rank, const void* id128, int device, kv_comm_t* out) {
+  if (!out || world < 1 || world > MAXW || rank < 0 || rank >= world) return fail(KV_INVALID_ARGUMENT, "kv_comm_create: world %d rank %d", world, rank);
+  DeviceGuard dg(device);
+  kv_comm* c = new kv_comm();
+  c->world = world; c->rank = rank; c->device = device;
+  int rc = KV_OK;
+  do {
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming) != hipSuccess) {
+      rc = fail(KV_INTERNAL, "kv_comm_create: stream / events");
+      break;
+    }
+    if (world > 1 || id128) {   // a world of one needs no RCCL (the exchange is a device copy) unless asked for
+      if (!id128) { rc = fail(KV_INVALID_ARGUMENT, "kv_comm_create: unique id is null"); break; }
+      if (!rccl()->ok) { rc = fail(KV_UNIMPLEMENTED, "librccl.so.1 could not be loaded"); break; }
+      ncclUniqueId id;
+      std::memcpy(&id, id128, sizeof id);
+      ncclResult_t r = rccl()->CommInitRank(&c->comm, world, id, rank);
+      if (r != ncclSuccess) { rc = fail(KV_INTERNAL, "ncclCommInitRank: %s", rccl()->GetErrorString ? rccl()->GetErrorString(r) : "?"); break; }
+    }
+  } while (0);
+  if (rc) { kv_comm_destroy(c); return rc; }
+  *out = c;
+  return KV_OK;
+}
+
+int kv_comm_create_staged(int world, int rank, kv_comm_exchange_fn exchange, kv_comm_max_fn max_u32, void* user, int device,
+                          kv_comm_t* out) {
+  if (!out || !exchange || world < 1 || world > MAXW || rank < 0 || rank >= world)
+    return fail(KV_INVALID_ARGUMENT, "kv_comm_create_staged: world %d rank %d", world, rank);
+  DeviceGuard dg(device);
+  kv_comm* c = new kv_comm();
+  c->world = world; c->rank = rank; c->device = device;
+  c->xfn = exchange; c->mfn = max_u32; c->user = user;
+  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming) != hipSuccess) {
+    kv_comm_destroy(c);
+    return fail(KV_INTERNAL, "kv_comm_create_staged: stream / events");
+  }
+  *out = c;
+  return KV_OK;
+}
+
+int kv_comm_set_self_via_rccl(kv_comm_t c, int on) {
+  if (!c || !c->comm) return fail(KV_INVALID_ARGUMENT, "kv_comm_set_self_via_rccl: not an RCCL communicator");
+  c->self_via_rccl = on != 0;
+  return KV_OK;
+}
+
+int kv_comm_stream(kv_comm_t c, kv_stream_t* stream) {
+  if (!c || !stream) return fail(KV_INVALID_ARGUMENT, "kv_comm_stream: null argument");
+  *stream = (kv_stream_t)c->stream;
+  return KV_OK;
+}
+
+int kv_forget_stream(kv_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(KV_INVALID_ARGUMENT, "kv_forget_stream: the stream cannot be synchronised");
+  retire_stream(s);
+  return KV_OK;
+}
+
+int kv_comm_destroy(kv_comm_t c) {
+  if (!c) return KV_OK;
+  DeviceGuard dg(c->device);
+  if (c->stream) { hipStreamSynchronize(c->stream); retire_stream(c->stream); }   // no table keeps the stream as its last one
+  if (c->comm && rccl()->ok) rccl()->CommDestroy(c->comm);
+  if (c->ev_in) hipEventDestroy(c->ev_in);
+  if (c->ev_out) hipEventDestroy(c->ev_out);
+  if (c->stream) hipStreamDestroy(c->stream);
+  delete c;
+  return KV_OK;
+}
+
+int kv_comm_all_to_all(kv_comm_t c, const void* send, void* recv, int64_t bytes_per_peer, kv_stream_t stream) {
+  if (!c || !send || !recv || bytes_per_peer < 0) return fail(KV_INVALID_ARGUMENT, "kv_comm_all_to_all: bad arguments");
+  DeviceGuard dg(c->device);
+  return comm_exchange(c, 1, &send, &recv, &bytes_per_peer, (hipStream_t)stream);
+}
+
+int kv_shard_create(kv_handle_t local_table, int world, int rank, int owner_rule, int64_t max_ids, int64_t peer_capacity,
+                    kv_shard_t* out) {
+  int rc;
+  if ((rc = check_table(local_table))) return rc;
+  if (!out || world < 1 || world > MAXW || rank < 0 || rank >= world) return fail(KV_INVALID_ARGUMENT, "kv_shard_create: world %d rank %d", world, rank);
+  if (owner_rule != KV_OWNER_HASH && owner_rule != KV_OWNER_MOD) return fail(KV_INVALID_ARGUMENT, "owner_rule %d", owner_rule);
+  if (max_ids < 1 || max_ids > (1ll << 21)) return fail(KV_INVALID_ARGUMENT, "max_ids %lld: 1 .. 2^21 ids per sharded batch", (long long)max_ids);
+  if (local_table->key_dtype == KV_DT_INT32) return fail(KV_UNIMPLEMENTED, "sharded tables carry int64 ids");
+  if (!fused_ok(local_table->dim))   // (the route, the finish and the owners' serve side exist on the entry-list kernels alone)
+    return fail(KV_UNIMPLEMENTED, "sharded tables: dim %d (multiples of 4 up to 256)", local_table->dim);
+  if (local_table->occurrence_order)
+    return fail(KV_UNIMPLEMENTED, "sharded tables: occurrence-order mode is a single-table notion (senders pre-sum, owners add the senders' sums in rank order)");
+  DeviceGuard dg(local_table->device);
+  kv_shard* sh = new kv_shard();
+  sh->table = local_table; sh->world = world; sh->rank = rank; sh->rule = owner_rule; sh->max_ids = max_ids;
+  local_table->shard_refs.fetch_add(1);
+  do {
+    if ((rc = kv_create(KV_DT_INT64, KV_DT_FLOAT, local_table->dim, 0, 0, local_table->device, &sh->route))) break;
+    // default capacity: twice an even share of max_ids distinct ids (hashed ownership spreads them evenly), at least 1024
+    long long C = peer_capacity > 0 ? peer_capacity : std::max<long long>(1024, 2 * ((max_ids + world - 1) / world));
+    C = std::min<long long>(C, max_ids);
+    const unsigned ntr = (unsigned)((max_ids + RT - 1) / RT);
+    if (hipMalloc(&sh->uniq, (size_t)max_ids * 8) != hipSuccess || hipMalloc(&sh->ucnt, (size_t)max_ids * 4) != hipSuccess ||
+        hipMalloc(&sh->slot_of, (size_t)max_ids * 4) != hipSuccess || hipMalloc(&sh->counts, (size_t)world * 8) != hipSuccess ||
+        hipMalloc(&sh->hist, (size_t)ntr * world * 4) != hipSuccess ||
+        hipMalloc(&sh->gcount, (MAXW + 1) * 4) != hipSuccess || hipMemset(sh->gcount, 0, (MAXW + 1) * 4) != hipSuccess ||
+        hipHostMalloc(&sh->overflow, 2 * sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
+        hipMalloc(&sh->need, 2 * sizeof(unsigned)) != hipSuccess || hipMemset(sh->need, 0, 2 * sizeof(unsigned)) != hipSuccess ||
+        hipHostMalloc(&sh->need_host, sizeof(unsigned), hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&sh->ev_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&sh->ev_done, hipEventDisableTiming) != hipSuccess) {
+      rc = fail(KV_RESOURCE_EXHAUSTED, "kv_shard_create: allocation failed");
+      break;
+    }
+    sh->overflow[0] = 0; sh->overflow[1] = 0;   // [1]: the last routed batch's distinct ids (k_papply PA_UNIQUE)
+    if ((rc = shard_alloc_buffers(sh, (unsigned)C))) break;
+  } while (0);
+  if (rc) { kv_shard_destroy(sh); return rc; }
+  *out = sh;
+  return KV_OK;
+}
+
+int kv_shard_destroy(kv_shard_t sh) {
+  if (!sh) return KV_OK;
+  DeviceGuard dg(sh->table->device);
+  sh->table->shard_refs.fetch_sub(1);
+  hipDeviceSynchronize();
+  shard_free_buffers(sh);
+  hipFree(sh->uniq); hipFree(sh->ucnt); hipFree(sh->slot_of); hipFree(sh->counts); hipFree(sh->hist); hipFree(sh->gcount);
+  if (sh->overflow) hipHostFree(sh->overflow);
+  if (sh->need) hipFree(sh->need);
+  if (sh->need_host) hipHostFree(sh->need_host);
+  if (sh->ev_fork) hipEventDestroy(sh->ev_fork);
+  if (sh->ev_done) hipEventDestroy(sh->ev_done);
+  for (hipEvent_t e : sh->pev) if (e) hipEventDestroy(e);
+  if (sh->route) kv_destroy(sh->route);
+  delete sh;
+  return KV_OK;
+}
+
+int kv_shard_buffers(kv_shard_t sh, void** send_pairs, void** recv_pairs, void** send_rows, void** recv_rows,
+                     int64_t* pair_bytes_per_peer, int64_t* row_bytes_per_peer) {
+  if (!sh) return fail(KV_INVALID_ARGUMENT, "null shard");
+  if (send_pairs) *send_pairs = sh->send_pairs;
+  if (recv_pairs) *recv_pairs = sh->recv_pairs;
+  if (send_rows) *send_rows = sh->send_rows;
+  if (recv_rows) *recv_rows = sh->recv_rows;
+  if (pair_bytes_per_peer) *pair_bytes_per_peer = (int64_t)(sh->C + 1) * 16;
+  if (row_bytes_per_peer) *row_bytes_per_peer = (int64_t)(sh->C + 1) * sh->table->dim * (int64_t)sizeof(float);
+  return KV_OK;
+}
+
+int kv_shard_lookup_route(kv_shard_t sh, const void* ids, int64_t n, kv_stream_t stream) {
+  int rc;
+  const unsigned seen = sh ? shard_take_flag(sh) : 0u;
+  if (sh) sh->self_in_place = false;   // the caller makes the exchanges: all segments, its own included, arrive in the receive buffers
+  if ((rc = lookup_route_impl(sh, ids, n, stream))) return rc;
+  return shard_late_report(sh, seen);
+}
+
+// the owner's half: the ids the peers sent (recv_pairs) are looked up in this rank's table — frequency words count
+// every occurrence — and their rows go to send_rows, record for record.  3 launches.
+int kv_shard_lookup_serve(kv_shard_t sh, kv_stream_t stream) {
+  if (!sh) return fail(KV_INVALID_ARGUMENT, "null shard");
+  const int64_t nrec = (int64_t)sh->world * (sh->C + 1);
+  sh->serve_token = 0;
+  const SelfSegment self = shard_self(sh, false);
+  return gather_or_insert_impl(sh->table, sh->recv_pairs, nullptr, nrec, sh->send_rows, stream, 1, &sh->serve_token, sh->C + 1, &self);
+}
+
+// out[i] = the row that came back for ids[i].  1 launch.
+int kv_shard_lookup_finish(kv_shard_t sh, float* out, kv_stream_t stream) {
+  if (!sh || (sh->n_last > 0 && !out)) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_finish: output pointer is null");
+  if (sh->n_last == 0) return KV_OK;
+  DeviceGuard dg(sh->table->device);
+  kv_table* rt = sh->route;
+  std::lock_guard<std::mutex> l(rt->mu);
+  if (rt->batch_serial != sh->route_token || sh->route_token == 0) return fail(KV_FAILED_PRECONDITION, "kv_shard_lookup_finish without kv_shard_lookup_route");
+  { int rc; if ((rc = hand_over(rt, (hipStream_t)stream))) return rc; }
+  // over the rows that came back: position -> entry -> dense unique index -> the record its id was sent in
+  const int q = row_lanes(rt->dim);
+  const int grid = nblocks(sh->n_last, TB, 8192);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned slo = (unsigned)sh->rank * (sh->C + 1), slen = sh->self_in_place ? sh->C + 1 : 0u;
+#define KV_SF(VQ) k_shard_finish<VQ><<<grid, TB, 0, st>>>(rt->ws.pos_ent, rt->ws.ent_b, sh->slot_of, sh->recv_rows, out, sh->n_last, rt->dim, \
+                                                        sh->send_rows, slo, slen)
+  switch (q) {
+    case 1: KV_SF(1); break;   case 2: KV_SF(2); break;   case 4: KV_SF(4); break;   case 8: KV_SF(8); break;
+    case 16: KV_SF(16); break; case 32: KV_SF(32); break; default: KV_SF(64); break;
+  }
+#undef KV_SF
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+// backward: the gradient rows of the batch just looked up are summed per distinct id straight into the records their
+// ids were sent in (the route index is still there: no ids, no sizes, no sync).  2 launches.
+int kv_shard_apply_route(kv_shard_t sh, const float* grad, kv_stream_t stream) {
+  if (!sh || (sh->n_last > 0 && !grad)) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_route: grad pointer is null");
+  if (sh->n_last == 0) return KV_OK;
+  DeviceGuard dg(sh->table->device);
+  kv_table* rt = sh->route;
+  std::lock_guard<std::mutex> l(rt->mu);
+  if (rt->batch_serial != sh->route_token || sh->route_token == 0)
+    return fail(KV_FAILED_PRECONDITION, "kv_shard_apply_route: the batch's lookup must come first (kv_shard_lookup_route)");
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = hand_over(rt, s))) return rc;
+  if ((rc = ensure_workspace(rt, sh->n_last, true, s))) return rc;
+  WsDev wd = ws_view(rt, sh->n_last);
+  if (rt->index_P) { wd.P = rt->index_P; wd.pshift = 64 - ilog2(wd.P); }   // the route's partitioning
+  // the tile sums of the ids repeated inside their tile, then the per-id sums straight into the records the ids were
+  // sent in (k_papply PA_DEDUP over the route's entries)
+  PartArgs pa{};
+  pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
+  pa.grad = grad;
+  pa.out_sum = sh->send_rows;
+  pa.out_map = sh->slot_of;
+  pa.det = rt->deterministic ? 1 : 0;
+  pa.n = sh->n_last;
+  pa.epart = wd.epart;
+  pa.day_lk = pa.day;
+  if ((rc = launch_tsum(pa.tv, wd, grad, s))) return fail(rc, "tile sums: no kernel for dim %d", rt->dim);
+  if ((rc = launch_papply_ud(wd, pa, PA_DEDUP, s))) return fail(rc, "gradient pre-sum: no kernel for dim %d", rt->dim);
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+// the owner's half: recv_rows holds the peers' summed gradients, record for record as the lookup served them; the
+// fused apply takes the index that lookup left in the table's workspace.  2 launches.  optimizer / hp: shard_opt_call
+int kv_shard_apply_serve(kv_shard_t sh, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp, kv_stream_t stream) {
+  if (!sh || !hp) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_serve: bad arguments");
+  if (sh->serve_token == 0 || sh->serve_token != sh->table->batch_serial)
+    return fail(KV_FAILED_PRECONDITION, "kv_shard_apply_serve: another op used the table since this batch's lookup "
+                                        "(the sharded apply takes over the lookup's index)");
+  const int64_t nrec = (int64_t)sh->world * (sh->C + 1);
+  const SelfSegment self = shard_self(sh, true);
+  const OptCall c = shard_opt_call(optimizer, hp);
+  if (c.opt < 0) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_serve: optimizer %d", optimizer);
+  return apply_one(c, sh->table, slot0, slot1, sh->recv_rows, sh->recv_pairs, nrec, sh->serve_token, stream, false, &self);
+}
+
+// whole ops: forked from `stream` onto the shard's own stream (the caller's stream is free for the dense tower);
+// join != 0 makes `stream` wait for the result right away, else kv_shard_join does when the caller needs it
+int kv_shard_join(kv_shard_t sh, kv_stream_t stream) {
+  if (!sh) return fail(KV_INVALID_ARGUMENT, "null shard");
+  DeviceGuard dg(sh->table->device);
+  HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, sh->ev_done, 0));
+  return KV_OK;
+}
+
+int kv_shard_profile(kv_shard_t sh, int every) {
+  if (!sh) return fail(KV_INVALID_ARGUMENT, "null shard");
+  DeviceGuard dg(sh->table->device);
+  shard_prof_collect(sh, true); shard_prof_collect(sh, false);
+  sh->prof_every = every > 0 ? every : 0;
+  sh->prof_seq_l = sh->prof_seq_a = 0;
+  for (int i = 0; i < KV_SHARD_PHASES; ++i) { sh->psum[i] = 0.0; sh->pcnt[i] = 0; }
+  return KV_OK;
+}
+
+int kv_shard_profile_read(kv_shard_t sh, double* ms_sum, int64_t* samples, int n_phases, int64_t* info) {
+  if (!sh || !ms_sum || !samples || n_phases < KV_SHARD_PHASES) return fail(KV_INVALID_ARGUMENT, "kv_shard_profile_read: bad arguments");
+  DeviceGuard dg(sh->table->device);
+  shard_prof_collect(sh, true); shard_prof_collect(sh, false);
+  for (int i = 0; i < KV_SHARD_PHASES; ++i) { ms_sum[i] = sh->psum[i]; samples[i] = sh->pcnt[i]; }
+  if (info) { info[0] = sh->ranks_seen; info[1] = (int64_t)sh->C; info[2] = (int64_t)sh->grows; info[3] = (int64_t)sh->overflows; }
+  return KV_OK;
+}
+
+int kv_shard_set_lossless(kv_shard_t sh, int on) {
+  if (!sh) return fail(KV_INVALID_ARGUMENT, "null shard");
+  sh->lossless = on != 0;
+  return KV_OK;
+}
+
+// the same agreement between shards that live in ONE process (see kv_shard_exchange_local): call it after every
+// shard's kv_shard_lookup_route; *rerouted != 0 means the capacity was raised on all of them and the routes must run again
+int kv_shard_agree_local(const kv_shard_t* shards, int world, int* rerouted, kv_stream_t stream) {
+  if (!shards || world < 1 || !rerouted) return fail(KV_INVALID_ARGUMENT, "kv_shard_agree_local: bad arguments");
+  *rerouted = 0;
+  for (int p = 0; p < world; ++p)
+    if (!shards[p] || shards[p]->world != world || shards[p]->C != shards[0]->C)
+      return fail(KV_INVALID_ARGUMENT, "kv_shard_agree_local: shards differ in world / capacity");
+  DeviceGuard dg(shards[0]->table->device);
+  hipStream_t s = (hipStream_t)stream;
+  unsigned need = 0;
+  for (int p = 0; p < world; ++p)
+    HIP_TRY(hipMemcpyAsync(shards[p]->need_host, shards[p]->need, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int p = 0; p < world; ++p) need = std::max(need, *shards[p]->need_host);
+  if (need <= shards[0]->C) return KV_OK;
+  const long long newC = std::min<long long>(shards[0]->max_ids, (long long)need + need / 4 + 64);
+  for (int p = 0; p < world; ++p) {
+    int rc;
+    if ((rc = shard_alloc_buffers(shards[p], (unsigned)newC))) return rc;
+    *reinterpret_cast<volatile unsigned*>(shards[p]->overflow) = 0;
+    ++shards[p]->grows;
+  }
+  *rerouted = 1;
+  return KV_OK;
+}
+
+int kv_shard_lookup(kv_shard_t sh, kv_comm_t comm, const void* ids, int64_t n, float* out, int join, kv_stream_t stream) {
+  if (!sh || !comm || comm->world != sh->world) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup: shard / communicator mismatch");
+  DeviceGuard dg(sh->table->device);
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  // The lossless mode's agreement reads a device word on the host: one stream synchronisation, not allowed inside a stream
+  // capture.  Refused HERE, before the communicator's stream is forked into the capture and before anything is queued (a
+  // refusal behind the fork would leave the side stream unjoined and invalidate the caller's capture).
+  if (sh->lossless && (stream_is_capturing(s) || stream_is_capturing(comm->stream)))
+    return fail(KV_FAILED_PRECONDITION, "kv_shard_lookup under stream capture: the lossless mode (the default) synchronises once per "
+                                        "lookup; capture sharded steps with kv_shard_set_lossless(shard, 0) and a peer_capacity "
+                                        "sized for the workload");
+  if ((rc = shard_verify(sh, comm))) return rc;
+  const unsigned seen = shard_take_flag(sh);
+  hipStream_t w = comm->stream;   // phases and exchanges in one queue: no event hop between a kernel and its exchange
+  if ((rc = shard_fork(sh, s, w))) return rc;
+  int64_t pb = (int64_t)(sh->C + 1) * 16, rb = (int64_t)(sh->C + 1) * sh->table->dim * (int64_t)sizeof(float);
+  // A failure of THIS rank's phase (out of memory, a bad argument) must not leave the peers waiting in a grouped recv:
+  // the exchanges are queued all the same — void headers for a failed route, zero rows for a failed serve — and the
+  // first error is returned once everything is queued.  Only a failed exchange itself returns at once.
+  int first = KV_OK;
+  std::string first_msg;
+  auto note = [&](int r) { if (r && !first) { first = r; first_msg = kv_last_error(); } return r; };
+  sh->self_in_place = shard_can_stay(sh);
+  char stay = sh->self_in_place ? 1 : 0;
+  const bool pm = shard_prof_begin(sh, true);
+  shard_prof_mark(sh, pm, 0, w);
+  if (note(lookup_route_impl(sh, ids, n, w))) {
+    sh->n_last = 0; sh->route_token = 0;
+    HIP_TRY(hipMemsetAsync(sh->counts, 0, (size_t)sh->world * 8, w));
+    k_seg_headers<<<1, MAXW, 0, w>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
+  }
+  if (sh->lossless) {   // every rank takes part in the agreement, whatever its own route did
+    char grown = 0;
+    if ((rc = shard_agree_many(&sh, 1, comm, w, &grown))) return rc;
+    if (grown) {
+      pb = (int64_t)(sh->C + 1) * 16; rb = (int64_t)(sh->C + 1) * sh->table->dim * (int64_t)sizeof(float);
+      stay = (sh->self_in_place = shard_can_stay(sh)) ? 1 : 0;   // (the record count changed)
+      if (!first && note(lookup_route_impl(sh, ids, n, w))) { sh->n_last = 0; sh->route_token = 0; }
+      if (first) {   // this rank's batch was refused: its segments are void in the new buffers too
+        HIP_TRY(hipMemsetAsync(sh->counts, 0, (size_t)sh->world * 8, w));
+        k_seg_headers<<<1, MAXW, 0, w>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
+      }
+    }
+  }
+  shard_prof_mark(sh, pm, 1, w);
+  if ((rc = shard_exchange_one(comm, sh->send_pairs, sh->recv_pairs, wired(comm) ? pb : pb * sh->world, w, stay))) return rc;
+  shard_prof_mark(sh, pm, 2, w);
+  if (note(kv_shard_lookup_serve(sh, w)))
+    HIP_TRY(hipMemsetAsync(sh->send_rows, 0, (size_t)rb * sh->world, w));
+  shard_prof_mark(sh, pm, 3, w);
+  if ((rc = shard_exchange_one(comm, sh->send_rows, sh->recv_rows, wired(comm) ? rb : rb * sh->world, w, stay))) return rc;
+  shard_prof_mark(sh, pm, 4, w);
+  if (!first) note(kv_shard_lookup_finish(sh, out, w));
+  shard_prof_mark(sh, pm, 5, w);
+  if (pm) sh->pend_l = true;
+  if ((rc = shard_done(sh, s, w, join))) return rc;
+  if (first) return fail(first, "%s (this rank's exchanges were queued all the same)", first_msg.c_str());
+  return shard_late_report(sh, seen);
+}
+
+int kv_shard_apply(kv_shard_t sh, kv_comm_t comm, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* grad,
+                   const float* hp, int join, kv_stream_t stream) {
+  if (!sh || !comm || comm->world != sh->world) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply: shard / communicator mismatch");
+  DeviceGuard dg(sh->table->device);
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  hipStream_t w = comm->stream;
+  if ((rc = shard_fork(sh, s, w))) return rc;
+  const int64_t rb = (int64_t)(sh->C + 1) * sh->table->dim * (int64_t)sizeof(float);
+  // as in kv_shard_lookup: a rank whose route phase failed still takes part in the exchange (zero gradient rows)
+  int first = KV_OK;
+  std::string first_msg;
+  const bool pm = shard_prof_begin(sh, false);
+  shard_prof_mark(sh, pm, 6, w);
+  if ((first = kv_shard_apply_route(sh, grad, w))) {
+    first_msg = kv_last_error();
+    HIP_TRY(hipMemsetAsync(sh->send_rows, 0, (size_t)rb * sh->world, w));
+  }
+  shard_prof_mark(sh, pm, 7, w);
+  if ((rc = shard_exchange_one(comm, sh->send_rows, sh->recv_rows, wired(comm) ? rb : rb * sh->world, w, sh->self_in_place ? 1 : 0))) return rc;
+  shard_prof_mark(sh, pm, 8, w);
+  rc = kv_shard_apply_serve(sh, optimizer, slot0, slot1, hp, w);
+  shard_prof_mark(sh, pm, 9, w);
+  if (pm) sh->pend_a = true;
+  if (rc && !first) { first = rc; first_msg = kv_last_error(); }
+  if ((rc = shard_done(sh, s, w, join))) return rc;
+  if (first) return fail(first, "%s (this rank's exchange was queued all the same)", first_msg.c_str());
+  return KV_OK;
+}
+
+int kv_multi_shard_lookup(const kv_shard_t* shards, int ntab, kv_comm_t comm, const void* const* ids, const int64_t* n,
+                          float* const* outs, int join, kv_stream_t stream) {
+  int rc;
+  if ((rc = multi_shard_check(shards, ntab, comm, "kv_multi_shard_lookup"))) return rc;
+  if (!ids || !n || !outs) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_lookup: null argument list");
+  DeviceGuard dg(shards[0]->table->device);
+  hipStream_t s = (hipStream_t)stream, w = comm->stream;
+  {   // as in kv_shard_lookup: the lossless agreement's synchronisation is refused before the fork, not behind it
+    bool lossless = false;
+    for (int k = 0; k < ntab; ++k) lossless = lossless || shards[k]->lossless;
+    if (lossless && (stream_is_capturing(s) || stream_is_capturing(w)))
+      return fail(KV_FAILED_PRECONDITION, "kv_multi_shard_lookup under stream capture: the lossless mode (the default) synchronises once "
+                                          "per lookup; capture sharded steps with kv_shard_set_lossless(shard, 0)");
+  }
+  for (int k = 0; k < ntab; ++k)
+    if ((rc = shard_verify(shards[k], comm))) return rc;
+  std::vector<unsigned> seen(ntab);
+  for (int k = 0; k < ntab; ++k) seen[k] = shard_take_flag(shards[k]);
+  if ((rc = shard_fork(shards[0], s, w))) return rc;
+  int first = KV_OK;
+  std::string first_msg;
+  auto note = [&](int r) { if (r && !first) { first = r; first_msg = kv_last_error(); } return r; };
+  std::vector<const void*> sp(ntab), sr(ntab);
+  std::vector<void*> rp(ntab), rr(ntab);
+  std::vector<int64_t> pb(ntab), rb(ntab);
+  std::vector<char> routed(ntab, 1), stay(ntab, 0);
+  for (int k = 0; k < ntab; ++k) stay[k] = (shards[k]->self_in_place = shard_can_stay(shards[k])) ? 1 : 0;
+  auto buffers = [&](int k) {
+    kv_shard* sh = shards[k];
+    const int64_t mul = wired(comm) ? 1 : sh->world;
+    pb[k] = (int64_t)(sh->C + 1) * 16 * mul;
+    rb[k] = (int64_t)(sh->C + 1) * sh->table->dim * (int64_t)sizeof(float) * mul;
+    sp[k] = sh->send_pairs; rp[k] = sh->recv_pairs; sr[k] = sh->send_rows; rr[k] = sh->recv_rows;
+  };
+  auto route = [&](int k) -> int {
+    kv_shard* sh = shards[k];
+    if (routed[k] && note(lookup_route_impl(sh, ids[k], n[k], w))) routed[k] = 0;
+    if (!routed[k]) {   // as in kv_shard_lookup: void headers, the peers are not left waiting
+      sh->n_last = 0; sh->route_token = 0;
+      HIP_TRY(hipMemsetAsync(sh->counts, 0, (size_t)sh->world * 8, w));
+      k_seg_headers<<<1, MAXW, 0, w>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
+    }
+    return KV_OK;
+  };
+  {
+    // the tables whose route is the entry-list one go together: 2 launches for all of them
+    std::vector<int> todo;
+    std::vector<char> batched(ntab, 0);
+    for (int k = 0; k < ntab; ++k)
+        if (shard_batchable(shards[k], n[k])) todo.push_back(k);
+    if (todo.size() >= 2) {
+      for (int k : todo) batched[k] = 1;
+      if (note(multi_route_impl(shards, todo.data(), (int)todo.size(), ids, n, w)))
+        for (int k : todo) routed[k] = 0;   // (void headers below: the peers are not left waiting)
+    }
+    for (int k = 0; k < ntab; ++k) {
+      buffers(k);
+      if (batched[k] && routed[k]) continue;
+      if ((rc = route(k))) return rc;
+    }
+  }
+  {   // lossless tables: one agreement for all of them (see shard_agree_many), then the grown ones are routed again
+    std::vector<char> grown(ntab, 0);
+    bool any_lossless = false;
+    for (int k = 0; k < ntab; ++k) any_lossless = any_lossless || shards[k]->lossless;
+    if ((rc = shard_agree_many(shards, ntab, comm, w, grown.data()))) return rc;
+    for (int k = 0; k < ntab; ++k)
+      if (grown[k]) {
+        stay[k] = (shards[k]->self_in_place = shard_can_stay(shards[k])) ? 1 : 0;
+        buffers(k);
+        if ((rc = route(k))) return rc;
+      }
+  }
+  if ((rc = comm_exchange(comm, ntab, sp.data(), rp.data(), pb.data(), w, stay.data()))) return rc;
+  {
+    // the owners' lookups: the tables of one dim in one batched lookup over their receive buffers (tile pass of all of
+    // them in one launch; the partition passes stay pending for the batched apply)
+    std::vector<char> served(ntab, 0);
+    std::vector<int> dims;
+    auto can = [&](int k) {
+      const kv_shard* sh = shards[k];
+      return sh->table->key_dtype == KV_DT_INT64 && (long long)sh->world * (sh->C + 1) <= (1ll << 21);
+    };
+    for (int k = 0; k < ntab; ++k)
+        if (can(k)) dims.push_back(shards[k]->table->dim);
+    std::sort(dims.begin(), dims.end());
+    dims.erase(std::unique(dims.begin(), dims.end()), dims.end());
+    for (int D : dims) {
+      std::vector<int> grp;
+      for (int k = 0; k < ntab; ++k)
+        if (can(k) && shards[k]->table->dim == D) grp.push_back(k);
+      if (grp.size() < 2) continue;
+      const int m = (int)grp.size();
+      std::vector<kv_handle_t> tb(m);
+      std::vector<const void*> ip(m);
+      std::vector<int64_t> nn(m);
+      std::vector<float*> op(m);
+      std::vector<kv_batch_token_t> tok(m, 0);
+      std::vector<unsigned> caps(m);
+      std::vector<SelfSegment> selfs(m);
+      for (int j = 0; j < m; ++j) {
+        kv_shard* sh = shards[grp[j]];
+        tb[j] = sh->table; ip[j] = sh->recv_pairs; nn[j] = (int64_t)sh->world * (sh->C + 1); op[j] = sh->send_rows; caps[j] = sh->C + 1;
+        sh->serve_token = 0;
+        selfs[j] = shard_self(sh, false);
+      }
+      if (note(multi_lookup_impl(m, tb.data(), ip.data(), nullptr, nn.data(), op.data(), tok.data(), w, 2, caps.data(), selfs.data()))) {
+        for (int k : grp) HIP_TRY(hipMemsetAsync(shards[k]->send_rows, 0, (size_t)rb[k] * (wired(comm) ? shards[k]->world : 1), w));
+      } else {
+        for (int j = 0; j < m; ++j) shards[grp[j]]->serve_token = tok[j];
+      }
+      for (int k : grp) served[k] = 1;
+    }
+    for (int k = 0; k < ntab; ++k)
+      if (!served[k] && note(kv_shard_lookup_serve(shards[k], w)))
+        HIP_TRY(hipMemsetAsync(shards[k]->send_rows, 0, (size_t)rb[k] * (wired(comm) ? shards[k]->world : 1), w));
+  }
+  if ((rc = comm_exchange(comm, ntab, sr.data(), rr.data(), rb.data(), w, stay.data()))) return rc;
+  {
+    // finish: the tables of one row geometry in one launch
+    std::vector<char> done(ntab, 0);
+    for (int q : {1, 2, 4, 8, 16, 32, 64}) {
+        std::vector<int> grp;
+        for (int k = 0; k < ntab; ++k)
+          if (routed[k] && shards[k]->n_last > 0 && row_lanes(shards[k]->table->dim) == q) grp.push_back(k);
+        if (grp.size() < 2) continue;
+        if (!note(multi_finish_impl(shards, grp.data(), (int)grp.size(), outs, w)))
+          for (int k : grp) done[k] = 1;
+      }
+    for (int k = 0; k < ntab; ++k)
+      if (routed[k] && !done[k]) note(kv_shard_lookup_finish(shards[k], outs[k], w));
+  }
+  if ((rc = shard_done(shards[0], s, w, join))) return rc;
+  if (first) return fail(first, "%s (this rank's exchanges were queued all the same)", first_msg.c_str());
+  for (int k = 0; k < ntab; ++k)
+    if ((rc = shard_late_report(shards[k], seen[k]))) return rc;
+  return KV_OK;
+}
+
+// slot0 / slot1: one handle per table (slot1 only for the FTRL family, else nullptr); hp as in kv_shard_apply_serve
+int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int optimizer, const kv_handle_t* slot0,
+                         const kv_handle_t* slot1, const float* const* grads, const float* hp, int join, kv_stream_t stream) {
+  int rc;
+  if ((rc = multi_shard_check(shards, ntab, comm, "kv_multi_shard_apply"))) return rc;
+  if (!slot0 || !grads || !hp) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_apply: null argument list");
+  DeviceGuard dg(shards[0]->table->device);
+  hipStream_t s = (hipStream_t)stream, w = comm->stream;
+  if ((rc = shard_fork(shards[0], s, w))) return rc;
+  int first = KV_OK;
+  std::string first_msg;
+  auto note = [&](int r) { if (r && !first) { first = r; first_msg = kv_last_error(); } return r; };
+  std::vector<const void*> sr(ntab);
+  std::vector<void*> rr(ntab);
+  std::vector<int64_t> rb(ntab);
+  std::vector<char> stay(ntab, 0);
+  std::vector<char> summed(ntab, 0);
+  {
+    // gradient pre-sum: the tables of one dim whose route has no ordered owner scatter in two launches
+    std::vector<int> dims;
+    for (int k = 0; k < ntab; ++k)
+      if (shards[k]->n_last > 0 && !shards[k]->table->deterministic) dims.push_back(shards[k]->table->dim);
+    std::sort(dims.begin(), dims.end());
+    dims.erase(std::unique(dims.begin(), dims.end()), dims.end());
+    for (int D : dims) {
+      std::vector<int> grp;
+      for (int k = 0; k < ntab; ++k)
+        if (shards[k]->n_last > 0 && !shards[k]->table->deterministic && shards[k]->table->dim == D) grp.push_back(k);
+      if (grp.size() < 2) continue;
+      if (!note(multi_presum_impl(shards, grp.data(), (int)grp.size(), grads, w)))
+        for (int k : grp) summed[k] = 1;
+      else
+        for (int k : grp) summed[k] = 2;   // failed: zero gradient rows below
+    }
+  }
+  for (int k = 0; k < ntab; ++k) {
+    kv_shard* sh = shards[k];
+    stay[k] = sh->self_in_place ? 1 : 0;
+    rb[k] = (int64_t)(sh->C + 1) * sh->table->dim * (int64_t)sizeof(float) * (wired(comm) ? 1 : sh->world);
+    sr[k] = sh->send_rows; rr[k] = sh->recv_rows;
+    if (summed[k] == 1) continue;
+    if (summed[k] == 2 || note(kv_shard_apply_route(sh, grads[k], w)))
+      HIP_TRY(hipMemsetAsync(sh->send_rows, 0, (size_t)rb[k] * (wired(comm) ? sh->world : 1), w));
+  }
+  if ((rc = comm_exchange(comm, ntab, sr.data(), rr.data(), rb.data(), w, stay.data()))) return rc;
+  {
+    // the owners' applies: the tables of one dim whose serve lookups left their batch index in one batched apply
+    std::vector<char> applied(ntab, 0);
+    std::vector<int> dims;
+    auto can = [&](int k) {
+      const kv_shard* sh = shards[k];
+      return sh->table->key_dtype == KV_DT_INT64 && (long long)sh->world * (sh->C + 1) <= (1ll << 21) && sh->serve_token != 0 &&
+             sh->serve_token == sh->table->batch_serial && sh->table->fused_index && slot0[k] != nullptr && (!two_slots(optimizer) || (slot1 && slot1[k]));
+    };
+    if (optimizer >= 0 && optimizer <= 5)
+      for (int k = 0; k < ntab; ++k)
+        if (can(k)) dims.push_back(shards[k]->table->dim);
+    std::sort(dims.begin(), dims.end());
+    dims.erase(std::unique(dims.begin(), dims.end()), dims.end());
+    for (int D : dims) {
+      std::vector<int> grp;
+      for (int k = 0; k < ntab; ++k)
+        if (can(k) && shards[k]->table->dim == D) grp.push_back(k);
+      if (grp.size() < 2) continue;
+      const int m = (int)grp.size();
+      std::vector<kv_handle_t> vs(m), s0(m), s1(m);
+      std::vector<const float*> gp(m);
+      std::vector<const void*> ip(m);
+      std::vector<int64_t> nn(m);
+      std::vector<kv_batch_token_t> tok(m);
+      std::vector<SelfSegment> selfs(m);
+      for (int j = 0; j < m; ++j) {
+        kv_shard* sh = shards[grp[j]];
+        vs[j] = sh->table; s0[j] = slot0[grp[j]]; s1[j] = slot1 ? slot1[grp[j]] : nullptr;
+        gp[j] = sh->recv_rows; ip[j] = sh->recv_pairs; nn[j] = (int64_t)sh->world * (sh->C + 1); tok[j] = sh->serve_token;
+        selfs[j] = shard_self(sh, true);
+      }
+      // (require_reuse: the ids are (id, count) records — an apply that rebuilt its index from them would read them as plain ids)
+      const int r = multi_apply(shard_opt_call(optimizer, hp), m, vs.data(), s0.data(), s1.data(), gp.data(), ip.data(), nn.data(),
+                                tok.data(), w, false, true, selfs.data());
+      note(r);
+      for (int k : grp) applied[k] = 1;
+    }
+    for (int k = 0; k < ntab; ++k)
+      if (!applied[k]) note(kv_shard_apply_serve(shards[k], optimizer, slot0[k], slot1 ? slot1[k] : nullptr, hp, w));
+  }
+  if ((rc = shard_done(shards[0], s, w, join))) return rc;
+  if (first) return fail(first, "%s (this rank's exchange was queued all the same)", first_msg.c_str());
+  return KV_OK;
+}
+
+// The exchange between shards that live in ONE process (all on one device): segment r of shard p's send buffer to
+// segment p of shard r's receive buffer.  what: 0 = the (id, count) records, 1 = the rows.  This is how the
+// phases are exercised with several ranks on a single GPU (RCCL refuses two ranks on one device).
+int kv_shard_exchange_local(const kv_shard_t* shards, int world, int what, kv_stream_t stream) {
+  if (!shards || world < 1) return fail(KV_INVALID_ARGUMENT, "kv_shard_exchange_local: bad arguments");
+  for (int p = 0; p < world; ++p)
+    if (!shards[p] || shards[p]->world != world || shards[p]->C != shards[0]->C || shards[p]->table->dim != shards[0]->table->dim)
+      return fail(KV_INVALID_ARGUMENT, "kv_shard_exchange_local: shards differ in world / capacity / dim");
+  DeviceGuard dg(shards[0]->table->device);
+  const size_t rec = shards[0]->C + 1;
+  const size_t bytes = rec * (what == 0 ? 16 : (size_t)shards[0]->table->dim * sizeof(float));
+  for (int p = 0; p < world; ++p)
+    for (int r = 0; r < world; ++r) {
+      const char* src = what == 0 ? (const char*)shards[p]->send_pairs : (const char*)shards[p]->send_rows;
+      char* dst = what == 0 ? (char*)shards[r]->recv_pairs : (char*)shards[r]->recv_rows;
+      HIP_TRY(hipMemcpyAsync(dst + (size_t)p * bytes, src + (size_t)r * bytes, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
+  return KV_OK;
+}
+
+}  // extern "C"

@@ -196,5 +196,8 @@ struct MultiDesc {
   float* out;            // lookup output rows
   long long n;
 };
+// k_papply's modes (kv_papply.h explains them): the `mode` of launch_papply / launch_papply_ud
+enum PaMode { PA_LOOKUP = 0, PA_APPLYIDX = 1, PA_NONE = 2, PA_UNIQUE = 3, PA_DEDUP = 4,
+              PA_DEDUP_NUM = 5 };   // (a template constant only: PA_DEDUP that numbers the ids itself — kv_dedup_segment_sum)
 
 }  // namespace kvhip_internal
