@@ -1,6 +1,13 @@
-// kv_host.h — what kv_shard.hip, the sharded layer, uses of the table and of the ops in kvhip.hip: the table's types and
-// the functions below, nothing else.  Everything sits in the hidden namespace of kv_types.h, so none of it is exported;
-// `struct kv_table` is the ABI's opaque handle and therefore global.  The functions are defined, and explained, in kvhip.hip.
+// kv_host.h — the table core's internal interface: what the three units on top of kvhip.hip — kv_ops.hip (the table ops),
+// kv_apply.hip (the optimizer layer) and kv_shard.hip (the sharded layer) — use of a table: its types and the functions
+// below, nothing else.  Everything sits in the hidden namespace of kv_types.h, so none of it is exported; `struct kv_table`
+// is the ABI's opaque handle and therefore global.  The functions are defined, and explained, in kvhip.hip unless a section
+// names another unit.
+//
+// The boundary: no unit other than kvhip.hip names a mirror_*, mview_*, pend_wd or pend_pa member of kv_table — the slot
+// mirrors and the pending partition pass are reached through mirror_decide, set_pending_part, take_pending_part, flush_part and
+// launch_link_hints — and only kvhip.hip compiles the pipelines' kernels (kv_kernels.h, kv_fused.h, kv_papply.h), which the
+// other units reach through the launch_* functions.
 #pragma once
 
 #include <algorithm>
@@ -222,7 +229,18 @@ int regrow(T** p, size_t count) {
 }
 
 bool stream_is_capturing(hipStream_t s);
+int ws_sync(hipStream_t s);
+int ensure_capacity(kv_table* t, long long extra, hipStream_t s);
 int ensure_workspace(kv_table* t, long long n, bool need_part, hipStream_t s);
+unsigned fused_default_P(long long n);
+size_t chunk_cap(long long n);
+
+// ---- what a table's settings mean to an op -----------------------------------------------------------------------------
+bool fast_math_on(const kv_table* t);
+int det_mode(const kv_table* t);
+unsigned today(const kv_table* t);
+bool fused_tab(const kv_table* t);
+bool dim_supported(int D);
 
 // ---- views -------------------------------------------------------------------------------------------------------------
 TableDev dev_view(const kv_table* t);
@@ -235,7 +253,46 @@ struct SelfSegment { unsigned lo = 0, len = 0; const void* ids = nullptr; const 
 
 WsDev ws_view(kv_table* t, long long n, const SelfSegment* self = nullptr);
 
+// brackets one kernel launch with a pair of events when profiling is on
+struct ProfScope {
+  kv_table* t;
+  hipStream_t s;
+  bool on;
+  ProfScope(kv_table* t_, int kind, hipStream_t s_) : t(t_), s(s_), on(false) {
+    if (t->prof && ((t->prof_mask >> kind) & 1u) && t->ev_used + 2 <= t->ev.size() &&
+        (t->prof_every <= 1 || (t->prof_seq[kind]++ % (unsigned)t->prof_every) == 0u)) {
+      on = true;
+      t->ev_kind[t->ev_used / 2] = kind;
+      hipEventRecord(t->ev[t->ev_used], s);
+    }
+  }
+  ~ProfScope() {
+    if (on) {
+      hipEventRecord(t->ev[t->ev_used + 1], s);
+      t->ev_used += 2;
+    }
+  }
+};
+
 // ---- kernel launchers (the pipelines' kernels are compiled into kvhip.hip alone) -----------------------------------------
+// the templated ones are instantiated in kvhip.hip for the arguments named here
+template <bool FIRST>   // false, true
+void launch_tile(kv_table* t, const WsDev& wd, const void* ids, const int* counts, long long n, hipStream_t s,
+                 int ids_kind = -1, const MultiDesc* md = nullptr, int ntab = 0, unsigned gx = 0);
+template <int MODE>     // MODE_LOOKUP, MODE_APPLYIDX, MODE_UNIQUE, MODE_SCATTER, MODE_MARK
+void launch_part_keys(const WsDev& wd, const PartArgs& pa, hipStream_t s, const MultiDesc* md = nullptr, int ntab = 0);
+void launch_gather(const TableDev& td, const WsDev& wd, float* op, long long m, hipStream_t s,
+                   const MultiDesc* md = nullptr, int ntab = 0, bool order = false);
+void launch_order(const TableDev& td, const WsDev& wd, long long n, hipStream_t s,
+                  const MultiDesc* md = nullptr, int ntab = 0);
+void launch_ltile(kv_table* t, const TableDev& td, const WsDev& wd, const void* ids, const int* counts, long long n, float* out,
+                  hipStream_t s, int ids_kind = -1, const MultiDesc* md = nullptr, int ntab = 0, bool multi_rows = false);
+void launch_part2(const WsDev& wd, const PartArgs& pa, hipStream_t s, const MultiDesc* md = nullptr, int ntab = 0);
+int launch_occ_sum(const WsDev& wd, const PartArgs& pa, int fop, long long nmax, hipStream_t s);
+void launch_fill_entries(kv_table* t, hipStream_t s);
+void launch_clear_hints(kv_table* v, hipStream_t s);
+void launch_clear_stamps(kv_table* v, hipStream_t s);
+void launch_link_hints(kv_table* v, kv_table* sl, unsigned nrows, hipStream_t s);
 void launch_ltile_notable(kv_table* t, const TableDev& td, const WsDev& wd, const void* ids, long long n, hipStream_t s,
                           const int* counts = nullptr, bool int32_ids = false);
 void launch_ltile_multi_notable(const WsDev& wmax, int ntab, const MultiDesc* md, hipStream_t s);
@@ -250,6 +307,18 @@ enum : unsigned {
 
 int hand_over(kv_table* t, hipStream_t s, unsigned keep = KEEP_NONE, bool settle = true, bool mutates = true);
 int enter_op(kv_table* t, hipStream_t s, unsigned keep = KEEP_NONE, bool settle = true, bool mutates = true);
+int join_side(kv_table* t, hipStream_t s);
+int settle_pending(kv_table* t);
+int stats(kv_handle_t t, hipStream_t s, unsigned long long out[2], unsigned* nrows_out);
+
+// ---- the pending partition pass and the slot mirrors, as the ops see them ------------------------------------------------
+// a training lookup leaves its partition pass (wd, pa) pending on the table (kv_table::part_pending)
+void set_pending_part(kv_table* t, const WsDev& wd, const PartArgs& pa);
+// the optimizer apply of that batch takes it over: no longer pending; the lookup's own day stamp and counting rule come out
+void take_pending_part(kv_table* t, PartArgs* lookup);
+int flush_part(kv_table* t, hipStream_t s);
+// lean: the launch is k_papply / k_uapply AND the optimizer has one slot table (!two_slots(OPT))
+int mirror_decide(kv_table* v, kv_table* s0, PartArgs& pa, bool lean, hipStream_t s);
 
 // locks tables in address order like MaybeLockVariableInputMutexesInOrder (training_ops.cc:96-184)
 struct MultiLock {
@@ -278,6 +347,47 @@ void retire_stream(hipStream_t dead);
 // ---- index passes ------------------------------------------------------------------------------------------------------
 extern std::atomic<uint64_t> g_serial;   // batch tokens
 void choose_partitions(kv_table* t, WsDev& wd, long long n);
+template <int MODE>   // MODE_LOOKUP, MODE_APPLYIDX, MODE_UNIQUE
+void index_pass(kv_table* t, const WsDev& wd, const PartArgs& pa, const void* ids, const int* counts, long long n,
+                int ids_kind, float* out, hipStream_t s, bool file_order = true);
+int fused_lookup_pass(kv_table* t, WsDev& wd, const PartArgs& pa, const void* ids, const int* counts, long long n,
+                      int ids_kind, float* out, hipStream_t s, bool defer_part);
+// segmented fold over the sorted positions + fused update (k_apply_sorted), then the keys that cross chunk
+// boundaries (k_apply_span).  pa.n = ids of the batch (multi: nmax = the largest table's batch).  A host template that
+// launches through kv_launch.h and launch_occ_sum: kv_apply.hip uses it per OPT, kv_ops.hip for MODE_DEDUP.
+template <int MODE, int OPT>
+int launch_apply(kv_table* prof_t, const WsDev& wd, const PartArgs& pa, long long nmax, hipStream_t s,
+                 const MultiDesc* md = nullptr, int ntab = 0, bool skip_fin = false) {
+  const int D = pa.tv.dim;
+  // waves stride over the items (hot chunks, then cold batches of 64 / LPR keys); 8 blocks of 4 waves per CU
+  // is everything the chip holds at once, fewer for small batches
+  constexpr int gmax = 2048;
+  const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(gmax, (nmax / 2 + chunk_cap(nmax)) / 4 + 1));
+  const unsigned gfin = (unsigned)std::max<long long>(1, std::min<long long>(256, nmax / 4096 + 1));   // each block reads its share of the items at once
+  auto launch = [&](unsigned nchunks, int span) {
+    if constexpr (MODE == MODE_DEDUP) return launch_dedup_fold(wd, pa, s, md, ntab, nchunks, span);
+    else return launch_sorted_apply<OPT>(wd, pa, s, md, ntab, nchunks, span);
+  };
+  int rc;
+  if (pa.det == 2 && !md) {
+    // occurrence order: the hot keys' chains first (k_occ_sum: one block per key, the sums to hpart), k_apply reads them
+    const int fop = MODE == MODE_APPLY ? KV_SCATTER_ADD : pa.fold_op;
+    if ((rc = launch_occ_sum(wd, pa, fop, nmax, s))) return rc;
+  }
+  {
+    ProfScope ps(prof_t, KV_PROF_APPLY_SORTED, s);
+    rc = launch(grid, 0);
+  }
+  if (rc == KV_OK && !skip_fin) {
+    ProfScope ps(prof_t, KV_PROF_APPLY_SPAN, s);
+    rc = launch(gfin, 1);
+  }
+  if (rc == KV_UNIMPLEMENTED)
+    return md ? fail(KV_UNIMPLEMENTED, "batched launch: embedding dim %d (multiples of 4 only)", D)
+              : fail(KV_UNIMPLEMENTED, "embedding dim %d not supported by the fused kernels "
+                     "(multiples of 4 up to 1024, any dim up to 256)", D);
+  return KV_OK;
+}
 
 // ---- descriptor staging for the batched launches -----------------------------------------------------------------------
 struct StageSlot {
@@ -297,8 +407,12 @@ struct StageRelease {   // unlocks (and marks the slot busy until the stream get
   BatchStage& st; StageSlot* sl; hipStream_t s; bool launched = false;
   ~StageRelease() { if (launched) hipEventRecord(sl->consumed, s); st.mu.unlock(); }
 };
+int check_same_shape(int num_tables, const kv_handle_t* tables, const char* what);
 
-// ---- the ops the owner side of a sharded op runs -----------------------------------------------------------------------
+// ---- kv_ops.hip: the argument checks the batched lookups and the batched optimizer ops share ---------------------------
+int multi_common(int num_tables, const kv_handle_t* tables, const void* const* ids, const int64_t* ns);
+
+// ---- the ops the owner side of a sharded op runs (kv_ops.hip the lookups, kv_apply.hip the optimizer ops) --------------
 int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, float* out,
                           kv_stream_t stream, int pairs, kv_batch_token_t* token, unsigned seg_cap = 0,
                           const SelfSegment* self = nullptr);

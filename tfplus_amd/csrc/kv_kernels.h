@@ -1,4 +1,4 @@
-// kv_kernels.h — the batch pipeline (included by kvhip.hip and the kv_apply_*.hip units).
+// kv_kernels.h — the batch pipeline (included by kvhip.hip and the instantiation units: kv_opt_unit.h, kv_sums.hip).
 //
 // Why this shape.  A device-scope atomic on ONE address costs ~40 ns on MI355X and same-address
 // atomics serialise; a Zipf(1.2) batch of 1 M ids has ~100 keys that occur in (nearly) every tile, so
@@ -1716,126 +1716,6 @@ __device__ __forceinline__ void gather_body(const TableDev& t, const WsDev& w, f
   }
 }
 
-// KvVariableGatherOrZeros: read-only, no dedup needed (no writes, repeated keys hit cache).
-// FindOrZeros kv_variable.h:239-254 / BatchGetWithFn table_manager.h:112-154.
-template <typename IdT>
-__global__ void __launch_bounds__(TB) k_gather_or_zeros(TableDev t, const IdT* __restrict__ ids,
-                                                        float* __restrict__ out, long long n) {
-  const int D = t.dim;
-  const int lane8 = threadIdx.x & 7;
-  for (long long i = (long long)blockIdx.x * (TB / 8) + (threadIdx.x >> 3); i < n;
-       i += (long long)gridDim.x * (TB / 8)) {
-    const unsigned r = table_find(t, load_id(ids, (size_t)i));
-    const float* row = row_ptr(t, r);  // blacklisted rows are stored as zeros; row 0 is zeros
-    float* o = out + (size_t)i * D;
-    if ((D & 3) == 0) {
-      for (int q = lane8; q < (D >> 2); q += 8)
-        reinterpret_cast<float4*>(o)[q] = reinterpret_cast<const float4*>(row)[q];
-    } else {
-      for (int e = lane8; e < D; e += 8) o[e] = row[e];
-    }
-  }
-}
-
-// The same op for dims 4·VQ (VQ a power of two <= 64), wave-shaped like k_gather: one wave takes 64
-// consecutive ids per step, lane l probes id l (64 independent probes in flight per wave, none of them
-// repeated by neighbouring lanes), then the wave copies the rows VQ lanes per row, CH copy instructions
-// in flight, row ids handed over by shuffle, streaming stores (the output is not read again here).
-// ids_kind: 0 int64, 1 int32, 2 (id, count) int64 pairs.  `wave` of `nwaves` waves share the rows.
-// Software pipeline over the wave's steps: while step i copies its rows, the home index entries of step
-// i + 1 and the ids of step i + 2 are already in flight, so a step costs one round trip, not three — the
-// gather keeps the store bandwidth busy from a few waves per CU (it runs beside the partition pass).
-template <int VQ, int CWMAX = 4>
-__device__ __forceinline__ void goz_wave(const TableDev& t, const void* __restrict__ ids, int ids_kind,
-                                         float* __restrict__ out, long long n, long long wave, long long nwaves) {
-  constexpr int RW = 64 / VQ;            // rows per copy instruction
-  constexpr int CW = VQ < CWMAX ? VQ : CWMAX;    // copy instructions in flight (4 with many waves per CU: the probe hop
-                                                 // wants the occupancy; 8 for the few gather waves beside the partition pass)
-  const int lane = threadIdx.x & 63;
-  const int v = lane % VQ, sub = lane / VQ;
-  const long long stride = nwaves * 64;
-  auto load_key = [&](long long i) -> long long {
-    if (i >= n) return EMPTY_KEY;
-    return ids_kind == 1 ? (long long)reinterpret_cast<const int*>(ids)[i]
-                         : reinterpret_cast<const long long*>(ids)[i << (ids_kind == 2 ? 1 : 0)];
-  };
-  long long r0 = wave * 64;
-  if (r0 >= n) return;
-  long long k1 = load_key(r0 + lane);                  // step i + 1's key (first: step 0's)
-  long long k2 = load_key(r0 + stride + lane);         // step i + 2's
-  unsigned long long p1 = home_of(t, k1, mix64((unsigned long long)k1));
-  Entry e1 = load_entry(&t.entries[p1]);
-  for (; r0 < n; r0 += stride) {
-    // this step's rows: finish the probe started one step ago (row 0 reads zeros: misses, lanes past the end)
-    const unsigned rr = (r0 + lane < n) ? table_find_from(t, k1, p1, e1) : 0u;
-    // next step: its home entries leave now, the ids of the step after it too
-    k1 = k2;
-    p1 = home_of(t, k1, mix64((unsigned long long)k1));
-    if (r0 + stride < n) e1 = load_entry(&t.entries[p1]);
-    k2 = load_key(r0 + 2 * stride + lane);
-#pragma unroll
-    for (int j0 = 0; j0 < VQ; j0 += CW) {
-      float4 val[CW];
-      unsigned rj[CW];
-#pragma unroll
-      for (int j = 0; j < CW; ++j) rj[j] = __shfl(rr, (j0 + j) * RW + sub);
-#pragma unroll
-      for (int j = 0; j < CW; ++j) val[j] = reinterpret_cast<const float4*>(row_ptr(t, rj[j]))[v];
-#pragma unroll
-      for (int j = 0; j < CW; ++j) {
-        const long long ii = r0 + (j0 + j) * RW + sub;
-        if (ii < n) {
-          float4* dst = reinterpret_cast<float4*>(out + (size_t)ii * (VQ * 4)) + v;
-          __builtin_nontemporal_store(val[j].x, &dst->x); __builtin_nontemporal_store(val[j].y, &dst->y);
-          __builtin_nontemporal_store(val[j].z, &dst->z); __builtin_nontemporal_store(val[j].w, &dst->w);
-        }
-      }
-    }
-  }
-}
-template <typename IdT, int VQ>
-__global__ void __launch_bounds__(TB) k_gather_or_zeros_w(TableDev t, const IdT* __restrict__ ids,
-                                                          float* __restrict__ out, long long n) {
-  goz_wave<VQ>(t, ids, sizeof(IdT) == 4 ? 1 : 0, out, n, (long long)blockIdx.x * (TB / 64) + (threadIdx.x >> 6),
-               (long long)gridDim.x * (TB / 64));
-}
-
-// the gather for any dim behind one entry: wave-shaped for dims 4, 8, ..., 256, else 8 lanes per row
-template <int CWMAX = 4>
-__device__ __forceinline__ void goz_any(const TableDev& t, const void* __restrict__ ids, int ids_kind,
-                                        float* __restrict__ out, long long n, long long blk, long long nblk) {
-  const int D = t.dim;
-  const long long wave = blk * (blockDim.x / 64) + (threadIdx.x >> 6);
-  const long long nwaves = nblk * (blockDim.x / 64);
-  if ((D & 3) == 0) {  // block-uniform
-    switch (D >> 2) {
-      case 1: goz_wave<1, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
-      case 2: goz_wave<2, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
-      case 4: goz_wave<4, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
-      case 8: goz_wave<8, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
-      case 16: goz_wave<16, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
-      case 32: goz_wave<32, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
-      case 64: goz_wave<64, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
-      default: break;
-    }
-  }
-  const int lane8 = threadIdx.x & 7;
-  const long long gpb = blockDim.x / 8;
-  for (long long i = blk * gpb + (threadIdx.x >> 3); i < n; i += nblk * gpb) {
-    const long long key = ids_kind == 1 ? (long long)reinterpret_cast<const int*>(ids)[i]
-                                        : reinterpret_cast<const long long*>(ids)[i << (ids_kind == 2 ? 1 : 0)];
-    const unsigned r = table_find(t, key);
-    const float* row = row_ptr(t, r);
-    float* o = out + (size_t)i * D;
-    if ((D & 3) == 0) {
-      for (int q = lane8; q < (D >> 2); q += 8)
-        reinterpret_cast<float4*>(o)[q] = reinterpret_cast<const float4*>(row)[q];
-    } else {
-      for (int e = lane8; e < D; e += 8) o[e] = row[e];
-    }
-  }
-}
-
 // ---- kernel entry points: single table (by value) and many tables (descriptor array) ------------
 
 template <int MODE>
@@ -1937,131 +1817,4 @@ int launch_apply_t(const WsDev& wd, const PartArgs& pa, hipStream_t s, const Mul
   }
 #undef KV_APPLY
   return KV_UNIMPLEMENTED;
-}
-
-// BatchKvVariableGatherOrZerosV2 (kernels/kv_variable_ops.cc:431-470): N tables, N id lists, N
-// outputs — the reference loops over the tables; here ONE launch covers them all (blockIdx.y =
-// table, tables may differ in dim), which is what a 26-feature serving step needs.
-struct BatchGatherDesc {
-  TableDev t;
-  const void* ids;
-  float* out;
-  long long n;
-  int ids_int32;
-};
-__global__ void __launch_bounds__(TB) k_batch_gather_or_zeros(const BatchGatherDesc* __restrict__ descs) {
-  const BatchGatherDesc& d = descs[blockIdx.y];
-  goz_any(d.t, d.ids, d.ids_int32 ? 1 : 0, d.out, d.n, blockIdx.x, gridDim.x);
-}
-
-__global__ void k_store_count(const unsigned* ctr, long long* out) { *out = (long long)*ctr; }
-
-// kv_dedup_segment_sum: inverse[i] = dense unique index of input position i
-__global__ void k_dedup_inverse(WsDev w, long long n, int* inverse) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x)
-    inverse[i] = (int)w.ent_b[w.slot_rank[i] & SLOT_MASK];
-}
-
-// ---------------------------------------------------------------------------------------------
-// embedding_lookup_sparse (python/ops/embedding_ops.py:279-441) fused behind the lookup index:
-//   k_seg_offsets   CSR offsets of the sorted segment ids: off[s] = first position of segment s
-//   k_seg_combine   out[s] = combine_j( w_j * rows[row(id_j)] ) over the segment's positions, in
-//                   position order (tf.segment_sum order); mean: / sum w, sqrtn: / sqrt(sum w^2)
-// Segment ids outside [prev, num_segments) are clamped (memory safety only; TF rejects them).
-template <typename SegT>
-__global__ void __launch_bounds__(TB) k_seg_offsets(const SegT* __restrict__ seg, long long n, long long nseg,
-                                                    unsigned* __restrict__ off) {
-  for (long long i = (long long)blockIdx.x * TB + threadIdx.x; i <= n; i += (long long)gridDim.x * TB) {
-    long long prev = i > 0 ? (long long)seg[i - 1] : -1;
-    long long cur = i < n ? (long long)seg[i] : nseg;
-    prev = prev < -1 ? -1 : (prev > nseg ? nseg : prev);
-    cur = cur < 0 ? 0 : (cur > nseg ? nseg : cur);
-    for (long long sgi = prev + 1; sgi <= cur; ++sgi) off[sgi] = (unsigned)i;
-  }
-}
-
-// VQ = float4 lanes per row (dim / 4, power of two <= 64) or 0 = one thread per element.
-// has_w: sp_weights given (the reference multiplies, sums and divides by the weight sums);
-// otherwise tf.sparse_segment_{sum,mean,sqrt_n} (empty segment -> zeros).
-template <int VQ>
-__global__ void __launch_bounds__(TB) k_seg_combine(TableDev t, WsDev w, const unsigned* __restrict__ off,
-                                                    const float* __restrict__ wts, long long nseg,
-                                                    int combiner, float* __restrict__ out) {
-  const int D = t.dim;
-  constexpr int LPS = VQ > 0 ? VQ : 1;          // lanes per segment
-  const int v = threadIdx.x % LPS;
-  const long long g0 = ((long long)blockIdx.x * TB + threadIdx.x) / LPS;
-  const long long gstride = (long long)gridDim.x * TB / LPS;
-  for (long long sgi = g0; sgi < nseg; sgi += gstride) {
-    const unsigned lo = off[sgi], hi = off[sgi + 1];
-    float wsum = 0.f, w2 = 0.f;
-    if constexpr (VQ > 0) {
-      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      // SU ids of the segment at a time: their three dependent hops (slot -> row id -> row) overlap;
-      // the sums are still taken in id order
-      constexpr int SU = 4;
-      for (unsigned j = lo; j < hi; j += SU) {
-        unsigned sl[SU], r[SU];
-        float wj[SU];
-        float4 x[SU];
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          const bool ok = j + u < hi;
-          sl[u] = ok ? (w.slot_rank[j + u] & SLOT_MASK) : 0xFFFFFFFFu;
-          wj[u] = ok ? (wts ? wts[j + u] : 1.f) : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < SU; ++u) r[u] = sl[u] != 0xFFFFFFFFu ? w.ent_b[sl[u]] : 0u;
-#pragma unroll
-        for (int u = 0; u < SU; ++u) x[u] = reinterpret_cast<const float4*>(row_ptr(t, r[u]))[v];
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          if (sl[u] == 0xFFFFFFFFu) continue;
-          acc.x += x[u].x * wj[u]; acc.y += x[u].y * wj[u]; acc.z += x[u].z * wj[u]; acc.w += x[u].w * wj[u];
-          wsum += wj[u]; w2 += wj[u] * wj[u];
-        }
-      }
-      float den = 1.f;
-      if (combiner == 1) den = wsum; else if (combiner == 2) den = sqrtf(w2);
-      if (combiner != 0 && (wts || hi > lo)) { acc.x /= den; acc.y /= den; acc.z /= den; acc.w /= den; }
-      reinterpret_cast<float4*>(out + (size_t)sgi * D)[v] = acc;
-    } else {
-      for (int e = 0; e < D; ++e) {
-        float acc = 0.f;
-        wsum = 0.f; w2 = 0.f;
-        for (unsigned j = lo; j < hi; ++j) {
-          const unsigned r = w.ent_b[w.slot_rank[j] & SLOT_MASK];
-          const float wj = wts ? wts[j] : 1.f;
-          acc += row_ptr(t, r)[e] * wj;
-          wsum += wj; w2 += wj * wj;
-        }
-        float den = 1.f;
-        if (combiner == 1) den = wsum; else if (combiner == 2) den = sqrtf(w2);
-        if (combiner != 0 && (wts || hi > lo)) acc /= den;
-        out[(size_t)sgi * D + e] = acc;
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// k_take_rows: out[i] = src[idx[i]] (SCATTER = 0) or out[idx[i]] = src[i] (SCATTER = 1) over rows of
-// `nu` units of type U (float4 when the row is a multiple of 16 bytes).  The exchange's permute /
-// un-permute / expand steps of the sharded path.
-template <typename U, int SCATTER>
-__global__ void __launch_bounds__(TB) k_take_rows(const U* __restrict__ src, const int* __restrict__ idx,
-                                                  long long n, unsigned nu, int sh, U* __restrict__ out,
-                                                  const int* __restrict__ idx_outer = nullptr) {
-  const long long total = n * nu;
-  const long long stride = (long long)gridDim.x * TB;
-  for (long long x = (long long)blockIdx.x * TB + threadIdx.x; x < total; x += stride) {
-    long long i;
-    unsigned e;
-    if (sh >= 0) { i = x >> sh; e = (unsigned)(x & (nu - 1)); }
-    else { i = x / nu; e = (unsigned)(x - i * nu); }
-    const long long j = idx_outer ? idx[idx_outer[i]] : idx[i];   // two-level gather: src[idx[idx_outer[i]]]
-    if (SCATTER) out[j * nu + e] = src[x];
-    else out[x] = src[j * nu + e];
-  }
 }

@@ -1,0 +1,480 @@
+// kv_op_kernels.h — the small kernels only the table ops (kv_ops.hip) launch: point queries, delete, export / import /
+// delta, the inference gathers, unique / dedup helpers, the sparse lookup's combiners, kv_take_rows.  Included by kv_ops.hip
+// alone, behind kv_device.h, inside its anonymous namespace.
+#pragma once
+
+__global__ void k_fill_i64(long long* p, long long v, unsigned long long count) {
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < count;
+       i += (unsigned long long)gridDim.x * blockDim.x) p[i] = v;
+}
+// int64 list -> int32 list in place (one block: element i is read before any thread can overwrite
+// it, because writes land at half the byte offset and the loop is barrier-stepped)
+__global__ void k_narrow_keys(long long* keys, long long n) {
+  int* out = reinterpret_cast<int*>(keys);
+  for (long long base = 0; base < n; base += blockDim.x) {
+    const long long i = base + threadIdx.x;
+    const long long v = i < n ? keys[i] : 0;
+    __syncthreads();
+    if (i < n) out[i] = (int)v;
+    __syncthreads();
+  }
+}
+
+template <typename IdT>
+__global__ void k_get_meta(TableDev t, const IdT* ids, long long n, unsigned* fw, unsigned char* fl) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x) {
+    const unsigned r = table_find(t, load_id(ids, (size_t)i));
+    fw[i] = r ? *freq_ptr(t, r) : 0u;
+    fl[i] = r ? (unsigned char)(*flags_ptr(t, r) | 0x80u) : 0;
+  }
+}
+
+// GetCount kv_variable.h:503-524 (absent -> 0, else the low 16 bits) and GetTimeStamp :526-561
+// (absent -> today, else the high 16 bits = day stamp of the last training lookup)
+template <typename IdT>
+__global__ void k_get_count_ts(TableDev t, const IdT* ids, long long n, int what, unsigned today, unsigned* out) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x) {
+    const unsigned r = table_find(t, load_id(ids, (size_t)i));
+    const unsigned fw = r ? *freq_ptr(t, r) : 0u;
+    out[i] = what == 0 ? (r ? (fw & 0xFFFFu) : 0u) : (r ? (fw >> 16) : today);
+  }
+}
+
+// releases one key: its index entry becomes a tombstone, its row goes to the free list
+// (TableManager::DeleteKey table_manager.h:405-416: Evict + erase).  A key listed twice is
+// released once (the second probe finds the tombstone).
+__device__ __forceinline__ bool release_key(const TableDev& t, long long key, unsigned* free_rows) {
+  Entry* slot;
+  if (key == EMPTY_KEY) {
+    slot = &t.entries[t.mask + 1];
+    if (load_entry(slot).key != 0) return false;
+  } else {
+    unsigned long long p = mix64((unsigned long long)key) & t.mask;
+    for (;;) {
+      slot = &t.entries[p];
+      const Entry e = load_entry(slot);
+      if (e.key == key) break;
+      if (e.key == EMPTY_KEY) return false;
+      p = (p + 1) & t.mask;
+    }
+  }
+  const unsigned r = atomicExch(&slot->row, ROW_TOMB);   // duplicates of the key race here: one wins
+  if (r == ROW_TOMB || r == 0u) return false;
+  *flags_ptr(t, r) = (unsigned char)FLAG_FREE;
+  free_rows[atomicAdd(&t.counters[2], 1u)] = r;
+  return true;
+}
+template <typename IdT>
+__global__ void k_delete(TableDev t, const IdT* ids, long long n, unsigned* free_rows, unsigned long long* cnt) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x)
+    if (release_key(t, load_id(ids, (size_t)i), free_rows)) atomicAdd(&cnt[0], 1ull);
+}
+// DeleteWithTimestamp kv_variable.h:757-789: keys whose day stamp is > 0 and at least `threshold`
+// days old.  fill == 0 only counts; fill == 1 releases them and lists their keys.
+__global__ void k_delete_by_time(TableDev t, unsigned nrows, unsigned today, unsigned threshold, int fill,
+                                 unsigned* free_rows, unsigned long long* cnt, long long* out_keys) {
+  for (unsigned r = 1 + blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += gridDim.x * blockDim.x) {
+    if (*flags_ptr(t, r) & FLAG_FREE) continue;
+    const unsigned kt = *freq_ptr(t, r) >> 16;
+    if (kt == 0 || (int)today - (int)kt < (int)threshold) continue;
+    const long long key = *key_ptr(t, r);
+    if (!fill) { atomicAdd(&cnt[0], 1ull); continue; }
+    if (release_key(t, key, free_rows)) out_keys[atomicAdd(&cnt[0], 1ull)] = key;
+  }
+}
+
+// ExportValues dynamic_save.hpp:47-195.  cnt[0..2] = rows, blacklist, freq.  fill != 0 writes.
+__global__ void k_export(TableDev t, unsigned nrows, int first_n, int fill, unsigned long long* cnt,
+                         long long* keys, float* values, long long* blacklist, long long* fkeys,
+                         unsigned* fvals) {
+  const int D = t.dim;
+  for (unsigned r = 1 + blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += gridDim.x * blockDim.x) {
+    const unsigned fl = *flags_ptr(t, r);
+    const unsigned fw = *freq_ptr(t, r);
+    const long long key = *key_ptr(t, r);
+    if (fl & FLAG_FREE) continue;
+    if (fl & FLAG_BLACK) {
+      if (first_n > 3) {
+        unsigned long long p = atomicAdd(&cnt[1], 1ull);
+        if (fill && blacklist) blacklist[p] = key;
+      }
+    } else if ((first_n <= 3 || (fw & 0xFFFFu) >= t.enter_threshold) && !(fl & FLAG_UNDER)) {
+      unsigned long long p = atomicAdd(&cnt[0], 1ull);
+      if (fill) {
+        keys[p] = key;
+        const float* row = row_ptr(t, r);
+        for (int e = 0; e < D; ++e) values[p * D + e] = row[e];
+      }
+    }
+    if (first_n > 4) {
+      unsigned long long p = atomicAdd(&cnt[2], 1ull);
+      if (fill && fkeys) { fkeys[p] = key; fvals[p] = fw; }
+    }
+  }
+}
+
+// DeltaExport dynamic_save.hpp:198-451 over the rows whose delta bytes are set (train list, plus the
+// prediction list when first_n <= 3).  cnt[0] = update rows, [1] = blacklisted keys, [2] = all delta rows.
+// Order per key as in :231-248: low frequency -> only in the frequency list; blacklisted -> black list
+// (the caller hands the delete list as `black` when first_n <= 3, :345-351); else key + row.
+__global__ void k_export_delta(TableDev t, unsigned nrows, int first_n, int fill, unsigned long long* cnt,
+                               long long* keys, float* values, long long* black, long long* fkeys,
+                               unsigned* fvals) {
+  const int D = t.dim;
+  for (unsigned r = 1 + blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += gridDim.x * blockDim.x) {
+    const RowMeta m = *meta_ptr(t, r);
+    if (m.flags & FLAG_FREE) continue;
+    if (!((m.delta & DELTA_TRAIN) || (first_n <= 3 && (m.delta & DELTA_PRED)))) continue;
+    if (first_n > 4) {  // ExportFrequencyDelta kv_variable.h:937-957: the whole 32-bit word
+      unsigned long long p = atomicAdd(&cnt[2], 1ull);
+      if (fill && fkeys) { fkeys[p] = m.key; fvals[p] = m.freq; }
+    }
+    if ((m.freq & 0xFFFFu) < t.enter_threshold) continue;
+    if (m.flags & FLAG_BLACK) {
+      unsigned long long p = atomicAdd(&cnt[1], 1ull);
+      if (fill && black) black[p] = m.key;
+      continue;
+    }
+    unsigned long long p = atomicAdd(&cnt[0], 1ull);
+    if (fill) {
+      keys[p] = m.key;
+      const float* row = row_ptr(t, r);
+      for (int e = 0; e < D; ++e) values[p * D + e] = row[e];
+    }
+  }
+}
+// keys recorded by Delete: one that has a row again is a live member of the list (its row carries the
+// byte from here on), one without stays a "deleted" member.  which: 0 train list, 1 prediction list
+__global__ void k_delta_resolve(TableDev t, const long long* keys, long long n, int which, unsigned char* present) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x) {
+    const unsigned r = table_find(t, keys[i]);
+    present[i] = r ? 1 : 0;
+    if (r) meta_ptr(t, r)->delta |= (unsigned char)(which == 0 ? DELTA_TRAIN : DELTA_PRED);
+  }
+}
+// end of an export (dynamic_save.hpp:179-192, 432-443).  mode 0 (training export): the train list moves
+// to the prediction list (if kept) and empties; mode 1 (prediction export): the prediction list empties
+__global__ void k_delta_clear(TableDev t, unsigned nrows, int mode, int keep_pred) {
+  for (unsigned r = 1 + blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += gridDim.x * blockDim.x) {
+    RowMeta* m = meta_ptr(t, r);
+    const unsigned d = m->delta;
+    if (mode == 1) { if (d & DELTA_PRED) m->delta = (unsigned char)(d & ~DELTA_PRED); continue; }
+    if (d & DELTA_TRAIN) m->delta = (unsigned char)((d & ~DELTA_TRAIN) | (keep_pred ? DELTA_PRED : 0u));
+  }
+}
+
+// KvVariableGatherOrZeros: read-only, no dedup needed (no writes, repeated keys hit cache).
+// FindOrZeros kv_variable.h:239-254 / BatchGetWithFn table_manager.h:112-154.
+template <typename IdT>
+__global__ void __launch_bounds__(TB) k_gather_or_zeros(TableDev t, const IdT* __restrict__ ids,
+                                                        float* __restrict__ out, long long n) {
+  const int D = t.dim;
+  const int lane8 = threadIdx.x & 7;
+  for (long long i = (long long)blockIdx.x * (TB / 8) + (threadIdx.x >> 3); i < n;
+       i += (long long)gridDim.x * (TB / 8)) {
+    const unsigned r = table_find(t, load_id(ids, (size_t)i));
+    const float* row = row_ptr(t, r);  // blacklisted rows are stored as zeros; row 0 is zeros
+    float* o = out + (size_t)i * D;
+    if ((D & 3) == 0) {
+      for (int q = lane8; q < (D >> 2); q += 8)
+        reinterpret_cast<float4*>(o)[q] = reinterpret_cast<const float4*>(row)[q];
+    } else {
+      for (int e = lane8; e < D; e += 8) o[e] = row[e];
+    }
+  }
+}
+
+// The same op for dims 4·VQ (VQ a power of two <= 64), wave-shaped like k_gather: one wave takes 64
+// consecutive ids per step, lane l probes id l (64 independent probes in flight per wave, none of them
+// repeated by neighbouring lanes), then the wave copies the rows VQ lanes per row, CH copy instructions
+// in flight, row ids handed over by shuffle, streaming stores (the output is not read again here).
+// ids_kind: 0 int64, 1 int32, 2 (id, count) int64 pairs.  `wave` of `nwaves` waves share the rows.
+// Software pipeline over the wave's steps: while step i copies its rows, the home index entries of step
+// i + 1 and the ids of step i + 2 are already in flight, so a step costs one round trip, not three — the
+// gather keeps the store bandwidth busy from a few waves per CU (it runs beside the partition pass).
+template <int VQ, int CWMAX = 4>
+__device__ __forceinline__ void goz_wave(const TableDev& t, const void* __restrict__ ids, int ids_kind,
+                                         float* __restrict__ out, long long n, long long wave, long long nwaves) {
+  constexpr int RW = 64 / VQ;            // rows per copy instruction
+  constexpr int CW = VQ < CWMAX ? VQ : CWMAX;    // copy instructions in flight (4 with many waves per CU: the probe hop
+                                                 // wants the occupancy; 8 for the few gather waves beside the partition pass)
+  const int lane = threadIdx.x & 63;
+  const int v = lane % VQ, sub = lane / VQ;
+  const long long stride = nwaves * 64;
+  auto load_key = [&](long long i) -> long long {
+    if (i >= n) return EMPTY_KEY;
+    return ids_kind == 1 ? (long long)reinterpret_cast<const int*>(ids)[i]
+                         : reinterpret_cast<const long long*>(ids)[i << (ids_kind == 2 ? 1 : 0)];
+  };
+  long long r0 = wave * 64;
+  if (r0 >= n) return;
+  long long k1 = load_key(r0 + lane);                  // step i + 1's key (first: step 0's)
+  long long k2 = load_key(r0 + stride + lane);         // step i + 2's
+  unsigned long long p1 = home_of(t, k1, mix64((unsigned long long)k1));
+  Entry e1 = load_entry(&t.entries[p1]);
+  for (; r0 < n; r0 += stride) {
+    // this step's rows: finish the probe started one step ago (row 0 reads zeros: misses, lanes past the end)
+    const unsigned rr = (r0 + lane < n) ? table_find_from(t, k1, p1, e1) : 0u;
+    // next step: its home entries leave now, the ids of the step after it too
+    k1 = k2;
+    p1 = home_of(t, k1, mix64((unsigned long long)k1));
+    if (r0 + stride < n) e1 = load_entry(&t.entries[p1]);
+    k2 = load_key(r0 + 2 * stride + lane);
+#pragma unroll
+    for (int j0 = 0; j0 < VQ; j0 += CW) {
+      float4 val[CW];
+      unsigned rj[CW];
+#pragma unroll
+      for (int j = 0; j < CW; ++j) rj[j] = __shfl(rr, (j0 + j) * RW + sub);
+#pragma unroll
+      for (int j = 0; j < CW; ++j) val[j] = reinterpret_cast<const float4*>(row_ptr(t, rj[j]))[v];
+#pragma unroll
+      for (int j = 0; j < CW; ++j) {
+        const long long ii = r0 + (j0 + j) * RW + sub;
+        if (ii < n) {
+          float4* dst = reinterpret_cast<float4*>(out + (size_t)ii * (VQ * 4)) + v;
+          __builtin_nontemporal_store(val[j].x, &dst->x); __builtin_nontemporal_store(val[j].y, &dst->y);
+          __builtin_nontemporal_store(val[j].z, &dst->z); __builtin_nontemporal_store(val[j].w, &dst->w);
+        }
+      }
+    }
+  }
+}
+template <typename IdT, int VQ>
+__global__ void __launch_bounds__(TB) k_gather_or_zeros_w(TableDev t, const IdT* __restrict__ ids,
+                                                          float* __restrict__ out, long long n) {
+  goz_wave<VQ>(t, ids, sizeof(IdT) == 4 ? 1 : 0, out, n, (long long)blockIdx.x * (TB / 64) + (threadIdx.x >> 6),
+               (long long)gridDim.x * (TB / 64));
+}
+
+// the gather for any dim behind one entry: wave-shaped for dims 4, 8, ..., 256, else 8 lanes per row
+template <int CWMAX = 4>
+__device__ __forceinline__ void goz_any(const TableDev& t, const void* __restrict__ ids, int ids_kind,
+                                        float* __restrict__ out, long long n, long long blk, long long nblk) {
+  const int D = t.dim;
+  const long long wave = blk * (blockDim.x / 64) + (threadIdx.x >> 6);
+  const long long nwaves = nblk * (blockDim.x / 64);
+  if ((D & 3) == 0) {  // block-uniform
+    switch (D >> 2) {
+      case 1: goz_wave<1, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
+      case 2: goz_wave<2, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
+      case 4: goz_wave<4, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
+      case 8: goz_wave<8, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
+      case 16: goz_wave<16, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
+      case 32: goz_wave<32, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
+      case 64: goz_wave<64, CWMAX>(t, ids, ids_kind, out, n, wave, nwaves); return;
+      default: break;
+    }
+  }
+  const int lane8 = threadIdx.x & 7;
+  const long long gpb = blockDim.x / 8;
+  for (long long i = blk * gpb + (threadIdx.x >> 3); i < n; i += nblk * gpb) {
+    const long long key = ids_kind == 1 ? (long long)reinterpret_cast<const int*>(ids)[i]
+                                        : reinterpret_cast<const long long*>(ids)[i << (ids_kind == 2 ? 1 : 0)];
+    const unsigned r = table_find(t, key);
+    const float* row = row_ptr(t, r);
+    float* o = out + (size_t)i * D;
+    if ((D & 3) == 0) {
+      for (int q = lane8; q < (D >> 2); q += 8)
+        reinterpret_cast<float4*>(o)[q] = reinterpret_cast<const float4*>(row)[q];
+    } else {
+      for (int e = lane8; e < D; e += 8) o[e] = row[e];
+    }
+  }
+}
+
+// BatchKvVariableGatherOrZerosV2 (kernels/kv_variable_ops.cc:431-470): N tables, N id lists, N
+// outputs — the reference loops over the tables; here ONE launch covers them all (blockIdx.y =
+// table, tables may differ in dim), which is what a 26-feature serving step needs.
+struct BatchGatherDesc {
+  TableDev t;
+  const void* ids;
+  float* out;
+  long long n;
+  int ids_int32;
+};
+__global__ void __launch_bounds__(TB) k_batch_gather_or_zeros(const BatchGatherDesc* __restrict__ descs) {
+  const BatchGatherDesc& d = descs[blockIdx.y];
+  goz_any(d.t, d.ids, d.ids_int32 ? 1 : 0, d.out, d.n, blockIdx.x, gridDim.x);
+}
+
+__global__ void k_store_count(const unsigned* ctr, long long* out) { *out = (long long)*ctr; }
+
+// kv_dedup_segment_sum: inverse[i] = dense unique index of input position i
+__global__ void k_dedup_inverse(WsDev w, long long n, int* inverse) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x)
+    inverse[i] = (int)w.ent_b[w.slot_rank[i] & SLOT_MASK];
+}
+
+// ---------------------------------------------------------------------------------------------
+// embedding_lookup_sparse (python/ops/embedding_ops.py:279-441) fused behind the lookup index:
+//   k_seg_offsets   CSR offsets of the sorted segment ids: off[s] = first position of segment s
+//   k_seg_combine   out[s] = combine_j( w_j * rows[row(id_j)] ) over the segment's positions, in
+//                   position order (tf.segment_sum order); mean: / sum w, sqrtn: / sqrt(sum w^2)
+// Segment ids outside [prev, num_segments) are clamped (memory safety only; TF rejects them).
+template <typename SegT>
+__global__ void __launch_bounds__(TB) k_seg_offsets(const SegT* __restrict__ seg, long long n, long long nseg,
+                                                    unsigned* __restrict__ off) {
+  for (long long i = (long long)blockIdx.x * TB + threadIdx.x; i <= n; i += (long long)gridDim.x * TB) {
+    long long prev = i > 0 ? (long long)seg[i - 1] : -1;
+    long long cur = i < n ? (long long)seg[i] : nseg;
+    prev = prev < -1 ? -1 : (prev > nseg ? nseg : prev);
+    cur = cur < 0 ? 0 : (cur > nseg ? nseg : cur);
+    for (long long sgi = prev + 1; sgi <= cur; ++sgi) off[sgi] = (unsigned)i;
+  }
+}
+
+// VQ = float4 lanes per row (dim / 4, power of two <= 64) or 0 = one thread per element.
+// has_w: sp_weights given (the reference multiplies, sums and divides by the weight sums);
+// otherwise tf.sparse_segment_{sum,mean,sqrt_n} (empty segment -> zeros).
+template <int VQ>
+__global__ void __launch_bounds__(TB) k_seg_combine(TableDev t, WsDev w, const unsigned* __restrict__ off,
+                                                    const float* __restrict__ wts, long long nseg,
+                                                    int combiner, float* __restrict__ out) {
+  const int D = t.dim;
+  constexpr int LPS = VQ > 0 ? VQ : 1;          // lanes per segment
+  const int v = threadIdx.x % LPS;
+  const long long g0 = ((long long)blockIdx.x * TB + threadIdx.x) / LPS;
+  const long long gstride = (long long)gridDim.x * TB / LPS;
+  for (long long sgi = g0; sgi < nseg; sgi += gstride) {
+    const unsigned lo = off[sgi], hi = off[sgi + 1];
+    float wsum = 0.f, w2 = 0.f;
+    if constexpr (VQ > 0) {
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      // SU ids of the segment at a time: their three dependent hops (slot -> row id -> row) overlap;
+      // the sums are still taken in id order
+      constexpr int SU = 4;
+      for (unsigned j = lo; j < hi; j += SU) {
+        unsigned sl[SU], r[SU];
+        float wj[SU];
+        float4 x[SU];
+#pragma unroll
+        for (int u = 0; u < SU; ++u) {
+          const bool ok = j + u < hi;
+          sl[u] = ok ? (w.slot_rank[j + u] & SLOT_MASK) : 0xFFFFFFFFu;
+          wj[u] = ok ? (wts ? wts[j + u] : 1.f) : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < SU; ++u) r[u] = sl[u] != 0xFFFFFFFFu ? w.ent_b[sl[u]] : 0u;
+#pragma unroll
+        for (int u = 0; u < SU; ++u) x[u] = reinterpret_cast<const float4*>(row_ptr(t, r[u]))[v];
+#pragma unroll
+        for (int u = 0; u < SU; ++u) {
+          if (sl[u] == 0xFFFFFFFFu) continue;
+          acc.x += x[u].x * wj[u]; acc.y += x[u].y * wj[u]; acc.z += x[u].z * wj[u]; acc.w += x[u].w * wj[u];
+          wsum += wj[u]; w2 += wj[u] * wj[u];
+        }
+      }
+      float den = 1.f;
+      if (combiner == 1) den = wsum; else if (combiner == 2) den = sqrtf(w2);
+      if (combiner != 0 && (wts || hi > lo)) { acc.x /= den; acc.y /= den; acc.z /= den; acc.w /= den; }
+      reinterpret_cast<float4*>(out + (size_t)sgi * D)[v] = acc;
+    } else {
+      for (int e = 0; e < D; ++e) {
+        float acc = 0.f;
+        wsum = 0.f; w2 = 0.f;
+        for (unsigned j = lo; j < hi; ++j) {
+          const unsigned r = w.ent_b[w.slot_rank[j] & SLOT_MASK];
+          const float wj = wts ? wts[j] : 1.f;
+          acc += row_ptr(t, r)[e] * wj;
+          wsum += wj; w2 += wj * wj;
+        }
+        float den = 1.f;
+        if (combiner == 1) den = wsum; else if (combiner == 2) den = sqrtf(w2);
+        if (combiner != 0 && (wts || hi > lo)) acc /= den;
+        out[(size_t)sgi * D + e] = acc;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_take_rows: out[i] = src[idx[i]] (SCATTER = 0) or out[idx[i]] = src[i] (SCATTER = 1) over rows of
+// `nu` units of type U (float4 when the row is a multiple of 16 bytes).  The exchange's permute /
+// un-permute / expand steps of the sharded path.
+template <typename U, int SCATTER>
+__global__ void __launch_bounds__(TB) k_take_rows(const U* __restrict__ src, const int* __restrict__ idx,
+                                                  long long n, unsigned nu, int sh, U* __restrict__ out,
+                                                  const int* __restrict__ idx_outer = nullptr) {
+  const long long total = n * nu;
+  const long long stride = (long long)gridDim.x * TB;
+  for (long long x = (long long)blockIdx.x * TB + threadIdx.x; x < total; x += stride) {
+    long long i;
+    unsigned e;
+    if (sh >= 0) { i = x >> sh; e = (unsigned)(x & (nu - 1)); }
+    else { i = x / nu; e = (unsigned)(x - i * nu); }
+    const long long j = idx_outer ? idx[idx_outer[i]] : idx[i];   // two-level gather: src[idx[idx_outer[i]]]
+    if (SCATTER) out[j * nu + e] = src[x];
+    else out[x] = src[j * nu + e];
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_seg_combine_e: embedding_lookup_sparse's combiner over the tiles' entries
+// ------------------------------------------------------------------------------------------
+// out[s] = combine_j( w_j * rows[row(id_j)] ) over segment s's positions in position order (tf.segment_sum's order;
+// embedding_ops.py:395-441); position j -> its entry in its tile (pos_ent, filed by k_ltile) -> the entry's row word.  A
+// key this batch inserted in ANOTHER tile may not know its row yet (NEW_BIT, row part 0): it is probed — the partition
+// pass in front of this kernel has published every new row.  VQ lanes (power of two >= dim / 4) per segment, SU
+// positions of a segment in flight; the sums are taken in position order whatever SU is.
+template <int VQ>
+__global__ void __launch_bounds__(TB) k_seg_combine_e(TableDev t, const unsigned short* __restrict__ pos_ent,
+                                                      const unsigned* __restrict__ ent_b, const long long* __restrict__ ent_key,
+                                                      const unsigned* __restrict__ off, const float* __restrict__ wts,
+                                                      long long nseg, int combiner, float* __restrict__ out) {
+  const int D4 = t.dim >> 2;
+  const int v = threadIdx.x % VQ;
+  const bool vlive = v < D4;
+  const int vv = vlive ? v : 0;
+  const long long g0 = ((long long)blockIdx.x * TB + threadIdx.x) / VQ;
+  const long long gstride = (long long)gridDim.x * TB / VQ;
+  constexpr int SU = 4;
+  for (long long sgi = g0; sgi < nseg; sgi += gstride) {
+    const unsigned lo = off[sgi], hi = off[sgi + 1];
+    float wsum = 0.f, w2 = 0.f;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (unsigned j = lo; j < hi; j += SU) {
+      unsigned e[SU], r[SU];
+      float wj[SU];
+      float4 x[SU];
+#pragma unroll
+      for (int u = 0; u < SU; ++u) {
+        const bool ok = j + u < hi;
+        const unsigned pe = ok ? (unsigned)pos_ent[j + u] : 0xFFFFu;
+        e[u] = pe != 0xFFFFu ? ((j + u) / (unsigned)TILE) * (unsigned)TILE + pe : 0xFFFFFFFFu;
+        wj[u] = ok ? (wts ? wts[j + u] : 1.f) : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < SU; ++u) r[u] = e[u] != 0xFFFFFFFFu ? ent_b[e[u]] : 0u;
+#pragma unroll
+      for (int u = 0; u < SU; ++u) {
+        if (__builtin_expect((r[u] & NEW_BIT) != 0u && (r[u] & ROW_MASK) == 0u, 0)) r[u] = table_find(t, ent_key[e[u]]);
+        r[u] &= ROW_MASK;
+      }
+#pragma unroll
+      for (int u = 0; u < SU; ++u) x[u] = reinterpret_cast<const float4*>(row_ptr(t, r[u]))[vv];
+#pragma unroll
+      for (int u = 0; u < SU; ++u) {
+        if (!(j + u < hi)) continue;
+        acc.x += x[u].x * wj[u]; acc.y += x[u].y * wj[u]; acc.z += x[u].z * wj[u]; acc.w += x[u].w * wj[u];
+        wsum += wj[u]; w2 += wj[u] * wj[u];
+      }
+    }
+    float den = 1.f;
+    if (combiner == 1) den = wsum; else if (combiner == 2) den = sqrtf(w2);
+    if (combiner != 0 && (wts || hi > lo)) { acc.x /= den; acc.y /= den; acc.z /= den; acc.w /= den; }
+    if (vlive) reinterpret_cast<float4*>(out + (size_t)sgi * t.dim)[v] = acc;
+  }
+}
+
+// inverse[i] = the dense number of position i's id: position -> its entry in its tile -> the number k_papply PA_UNIQUE gave it
+__global__ void __launch_bounds__(TB) k_inverse_e(const unsigned short* __restrict__ pos_ent, const unsigned* __restrict__ ent_b,
+                                                  long long n, int* __restrict__ inverse) {
+  for (long long i = (long long)blockIdx.x * TB + threadIdx.x; i < n; i += (long long)gridDim.x * TB)
+    inverse[i] = (int)ent_b[(size_t)(i / TILE) * TILE + pos_ent[i]];
+}
