@@ -67,6 +67,57 @@ def test_multi_shard_ops_equal_the_per_table_sharded_ops():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("det", [True, False])
+@pytest.mark.parametrize("lossless", [True, False])
+def test_multi_shard_ops_of_one_table_are_the_single_sharded_ops(lossless, det):
+  """kv_multi_shard_lookup / kv_multi_shard_apply with ONE shard run what KvShard.lookup / .apply run (one body serves
+  both): rows, table contents and frequency sums are bit-identical to the single ops on a twin.  lossless (the default): a
+  capacity of 16 records, so the first step's agreement raises it — once — and routes the batch again; else the lossy mode
+  with the default capacity.  det: deterministic tables, ids repeat; the default mode's fp32 sums of a repeated id take no
+  fixed order, so there every batch holds distinct ids."""
+  if not torch.cuda.is_available():
+    pytest.skip("needs a GPU")
+  sys.path.insert(0, ROOT)
+  from tfplus_amd.kv_variable.python.ops import gen_kv_variable_ops as ops
+  rng = np.random.default_rng(31)
+  D = 32
+  init = np.random.default_rng(400).standard_normal((32, D)).astype(np.float32)
+  vs, ss, shs = [], [], []
+  for which in range(2):   # 0: driven by the multi ops, 1: by the single ops
+    v = _table(ops, D, init, det); s = _table(ops, 3 * D, np.zeros((4, 3 * D), np.float32), det)
+    sh = ops.KvShard(v, 1, 0, ops.KV_OWNER_HASH, max_ids=1 << 14, peer_capacity=16 if lossless else 0)
+    sh.set_lossless(lossless)
+    vs.append(v); ss.append(s); shs.append(sh)
+  comm = ops.KvComm(1, 0, ops.kv_comm_unique_id(), self_via_rccl=True)
+  caps = []
+  for step, n in enumerate((3000, 2500, 0, 2000)):
+    if det:
+      ids = torch.from_numpy(rng.integers(0, 4000, n)).cuda()
+    else:
+      ids = torch.from_numpy(rng.choice(50000, n, replace=False)).cuda()
+    grad = torch.from_numpy((rng.standard_normal((n, D)) * 1e-2).astype(np.float32)).cuda()
+    out, = ops.kv_multi_shard_lookup([shs[0]], comm, [ids], join=(step != 1))
+    if step == 1:
+      shs[0].join()
+    want = shs[1].lookup(comm, ids)
+    assert torch.equal(out, want), step
+    ops.kv_multi_shard_apply([shs[0]], comm, ops.OPT_GROUP_ADAM_V4, [[ss[0]]], [grad], HP)
+    shs[1].apply(comm, ops.OPT_GROUP_ADAM_V4, [ss[1]], grad, HP)
+    assert shs[0].peer_capacity == shs[1].peer_capacity
+    caps.append(shs[0].peer_capacity)
+  torch.cuda.synchronize()
+  if lossless:
+    assert caps[0] > 16 and caps == [caps[0]] * len(caps), caps     # one grow, in the first step
+  for a, b in ((vs[0], vs[1]), (ss[0], ss[1])):
+    ka, va = ops.read_kv_variable_op_v2(a); kb, vb = ops.read_kv_variable_op_v2(b)
+    oa, ob = torch.argsort(ka), torch.argsort(kb)
+    assert torch.equal(ka[oa], kb[ob]) and torch.equal(va[oa], vb[ob])
+    assert ops.kv_variable_frequency(a) == ops.kv_variable_frequency(b)
+  assert ops.kv_variable_frequency(vs[0]) > 0
+  del comm
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("opt", ["adam", "ftrl"])
 def test_multi_shard_batched_phases_equal_the_per_table_ops(opt):
   """The default (not deterministic) mode: kv_multi_shard_lookup / _apply run every phase of same-shaped tables in one

@@ -1,7 +1,7 @@
 // kv_apply.hip — the optimizer layer of the C ABI on the table core (kv_host.h): one parser per optimizer family, the two
-// bodies (apply_one: one table; multi_apply: many tables, one launch per stage), the 30 kv_apply_* / kv_multi_apply_*
-// entry points and kv_attach_slot.  It compiles no kernel: the optimizers' kernels are reached through the typed launchers
-// of kv_launch.h, the pipelines' through the core's.
+// bodies (apply_one: one table; multi_apply: many tables, one launch per stage; the PartArgs of all their launches start
+// from opt_part_args), the 30 kv_apply_* / kv_multi_apply_* entry points and kv_attach_slot.  It compiles no kernel: the
+// optimizers' kernels are reached through the typed launchers of kv_launch.h, the pipelines' through the core's.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -23,6 +23,26 @@ static bool claim_slot(kv_table* v, kv_table* sl, hipStream_t s) {
   v->slot_uid = sl->uid;
   v->slot_gen = sl->gen;
   return true;
+}
+
+// the 16-bit stamp of the unique-ids launches wraps (once per 65535 launches): every row back to "none", in front of the
+// launch that takes the next serial
+static void wrap_uniq_serial(kv_table* v, hipStream_t s) {
+  if (v->uniq_serial < 65535u) return;
+  launch_clear_stamps(v, s);
+  v->uniq_serial = 0;
+}
+
+// What the PartArgs of every optimizer launch starts from: the var's and slots' views, the hyperparameters with the var's
+// fast-math flag, the gradient rows, the day, the batch size and whether the var's hints name s0 (claim_slot: in front of
+// the site's mirror_decide).  det, day_lk / count_once, epart and uniq_serial are the sites' own.
+static void opt_part_args(PartArgs& pa, kv_table* v, kv_table* s0, kv_table* s1, const OptArgs& a, const float* grad, long long n,
+                          hipStream_t s) {
+  pa.tv = dev_view(v); pa.ts0 = dev_view(s0); pa.ts1 = s1 ? dev_view(s1) : pa.ts0;
+  pa.opt = a; pa.grad = grad; pa.day = today(v);
+  pa.opt.fast = fast_math_on(v) ? 1 : 0;
+  pa.n = n;
+  pa.use_hints = claim_slot(v, s0, s) ? 1 : 0;
 }
 
 // ... and the optimizer apply over the tiles' entries: the tile sums of the repeated ids (k_tsum; tile_ids != nullptr: the
@@ -107,34 +127,23 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
       nmax = std::max<long long>(nmax, ns[i]);
     }
     if (nmax == 0) return KV_OK;
-    BatchStage& st = g_stage[device][1];
-    StageSlot* sl = nullptr;
-    if ((rc = stage_acquire(st, (size_t)num_tables * sizeof(MultiDesc), &sl))) return rc;
-    StageRelease rel{st, sl, s};
-    MultiDesc* hd = reinterpret_cast<MultiDesc*>(sl->host);
+    Staged<MultiDesc> hd(device, 1, num_tables);
+    if (hd.rc) return hd.rc;
     for (int i = 0; i < num_tables; ++i) {
       kv_table* v = vars[i];
-      if (v->uniq_serial >= 65535u) {   // the 16-bit stamp wraps: every row back to "none"
-        launch_clear_stamps(v, s);
-        v->uniq_serial = 0;
-      }
+      wrap_uniq_serial(v, s);
       MultiDesc& d = hd[i];
-      std::memset(&d, 0, sizeof d);
-      d.a.tv = dev_view(v); d.a.ts0 = dev_view(slots0[i]); d.a.ts1 = slots1 ? dev_view(slots1[i]) : d.a.ts0;
-      d.a.opt = a; d.a.grad = grads[i]; d.a.day = today(v);
-      d.a.opt.fast = fast_math_on(v) ? 1 : 0;
-      d.a.n = ns[i];
-      d.a.use_hints = claim_slot(v, slots0[i], s) ? 1 : 0;
+      opt_part_args(d.a, v, slots0[i], slots1 ? slots1[i] : nullptr, a, grads[i], ns[i], s);
       if ((rc = mirror_decide(v, slots0[i], d.a, !two_slots(OPT), s))) return rc;
       d.a.uniq_serial = ns[i] > 0 ? ++v->uniq_serial : 0u;
       d.ids = ids[i];
       d.n = ns[i];
     }
-    HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, (size_t)num_tables * sizeof(MultiDesc), hipMemcpyHostToDevice, s));
-    rel.launched = true;
+    const MultiDesc* md;
+    if ((rc = hd.upload(s, &md))) return rc;
     const int ids32 = vars[0]->key_dtype == KV_DT_INT32 ? 1 : 0;
     ProfScope ps(vars[0], KV_PROF_APPLY_UNIQUE, s);
-    rc = launch_uapply<OPT>(hd[0].a, nullptr, ids32, nmax, s, reinterpret_cast<const MultiDesc*>(sl->dev), num_tables);
+    rc = launch_uapply<OPT>(hd[0].a, nullptr, ids32, nmax, s, md, num_tables);
     if (rc) return fail(rc, "batched unique apply: no kernel for dim %d", D);
     HIP_TRY(hipGetLastError());
     return KV_OK;
@@ -172,40 +181,30 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
     nmax = std::max<long long>(nmax, ns[i]);
   }
   if (nmax == 0) return KV_OK;
-  BatchStage& st = g_stage[device][1];
-  StageSlot* sl = nullptr;
-  if ((rc = stage_acquire(st, (size_t)num_tables * sizeof(MultiDesc), &sl))) return rc;
-  StageRelease rel{st, sl, s};
-  MultiDesc* hd = reinterpret_cast<MultiDesc*>(sl->host);
+  Staged<MultiDesc> hd(device, 1, num_tables);
+  if (hd.rc) return hd.rc;
   WsDev wmax{};
   for (int i = 0; i < num_tables; ++i) {
     MultiDesc& d = hd[i];
-    std::memset(&d, 0, sizeof d);
     d.w = ws_view(vars[i], std::max<long long>(ns[i], 1), selfs ? &selfs[i] : nullptr);
-    d.a.tv = dev_view(vars[i]); d.a.ts0 = dev_view(slots0[i]); d.a.ts1 = slots1 ? dev_view(slots1[i]) : d.a.ts0;
-    if (fz) { d.a.epart = d.w.epart; d.w.P = fused_default_P(std::max<long long>(ns[i], 1)); d.w.pshift = 64 - ilog2(d.w.P); }
-    d.a.opt = a; d.a.grad = grads[i]; d.a.day = today(vars[i]);
-    d.a.opt.fast = fast_math_on(vars[i]) ? 1 : 0;
+    if (fz) { d.a.epart = d.w.epart; use_partitions(d.w, fused_default_P(std::max<long long>(ns[i], 1))); }
+    opt_part_args(d.a, vars[i], slots0[i], slots1 ? slots1[i] : nullptr, a, grads[i], ns[i], s);
     d.a.det = vars[i]->deterministic ? 1 : 0;
-    d.a.n = ns[i];
-    d.a.use_hints = claim_slot(vars[i], slots0[i], s) ? 1 : 0;
     if ((rc = mirror_decide(vars[i], slots0[i], d.a, fz && !two_slots(OPT), s))) return rc;   // (fz: k_papply_multi; else the sorted-position kernels, no mirrors)
     d.ids = ids[i];
     d.n = ns[i];
     if (ns[i] == 0) d.w.ntiles = 0;
-    if (reuse && ns[i] > 0 && vars[i]->index_P) { d.w.P = vars[i]->index_P; d.w.pshift = 64 - ilog2(d.w.P); }   // the lookup's partitioning
+    if (reuse && ns[i] > 0 && vars[i]->index_P) use_partitions(d.w, vars[i]->index_P);   // the lookup's partitioning
     d.a.day_lk = d.a.day;
     if (pa_reuse && ns[i] > 0) {   // the pending lookup's own day stamp and counting rule
       PartArgs pend;
       take_pending_part(vars[i], &pend);
       d.a.day_lk = pend.day; d.a.count_once = pend.count_once;
     }
-    wmax.ntiles = std::max(wmax.ntiles, d.w.ntiles);
-    wmax.P = std::max(wmax.P, d.w.P);
+    widen(wmax, d.w);
   }
-  HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, (size_t)num_tables * sizeof(MultiDesc), hipMemcpyHostToDevice, s));
-  rel.launched = true;
-  const MultiDesc* md = reinterpret_cast<const MultiDesc*>(sl->dev);
+  const MultiDesc* md;
+  if ((rc = hd.upload(s, &md))) return rc;
   if (fz) {
     // partition pass + update in one launch (k_papply_multi) behind the tile sums; an optimizer that meets the ids first
     // runs the tile pass of all tables in front (PA_APPLYIDX)
@@ -255,16 +254,9 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
     // partition pass was settled by the caller's hand_over (no token is given).  Dims the kernel does not serve take the
     // batch pipeline below, which needs no promise.
     if ((rc = ensure_capacity(v, n, s)) || (rc = ensure_capacity(s0, n, s)) || (s1 && (rc = ensure_capacity(s1, n, s)))) return rc;
-    if (v->uniq_serial >= 65535u) {   // the 16-bit stamp wraps: every row back to "none" (once per 65535 launches)
-      launch_clear_stamps(v, s);
-      v->uniq_serial = 0;
-    }
+    wrap_uniq_serial(v, s);
     PartArgs pa{};
-    pa.tv = dev_view(v); pa.ts0 = dev_view(s0); pa.ts1 = s1 ? dev_view(s1) : pa.ts0;
-    pa.opt = a; pa.grad = grad; pa.day = today(v);
-    pa.opt.fast = fast_math_on(v) ? 1 : 0;
-    pa.n = n;
-    pa.use_hints = claim_slot(v, s0, s) ? 1 : 0;
+    opt_part_args(pa, v, s0, s1, a, grad, n, s);
     if ((rc = mirror_decide(v, s0, pa, !two_slots(OPT), s))) return rc;
     pa.uniq_serial = ++v->uniq_serial;
     ProfScope ps(v, KV_PROF_APPLY_UNIQUE, s);
@@ -297,12 +289,8 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
   if ((rc = ensure_workspace(v, n, true, s))) return rc;
   WsDev wd = ws_view(v, n, self);
   PartArgs pa{};
-  pa.tv = dev_view(v); pa.ts0 = dev_view(s0); pa.ts1 = s1 ? dev_view(s1) : pa.ts0;
-  pa.opt = a; pa.grad = grad; pa.day = today(v);
-  pa.opt.fast = fast_math_on(v) ? 1 : 0;
+  opt_part_args(pa, v, s0, s1, a, grad, n, s);
   pa.det = det_mode(v);
-  pa.n = n;
-  pa.use_hints = claim_slot(v, s0, s) ? 1 : 0;
   pa.day_lk = pa.day;
   if (pa_mode == PA_LOOKUP) { pa.day_lk = pend.day; pa.count_once = pend.count_once; }
   if (!reuse) {
@@ -320,7 +308,7 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
   } else if (pa_mode < 0 && v->fused_index) {
     pa_mode = PA_NONE;   // the tiles' entries of a batch whose bookkeeping is done
   }
-  if (v->fused_index && reuse && v->index_P) { wd.P = v->index_P; wd.pshift = 64 - ilog2(wd.P); }   // the lookup's partitioning
+  if (v->fused_index && reuse && v->index_P) use_partitions(wd, v->index_P);   // the lookup's partitioning
   if ((rc = mirror_decide(v, s0, pa, v->fused_index && !two_slots(OPT), s))) return rc;
   if (v->fused_index) rc = fused_apply<OPT>(v, wd, pa, n, s, pa_mode, tile_ids);
   else rc = launch_apply<MODE_APPLY, OPT>(v, wd, pa, n, s);

@@ -7,7 +7,8 @@
 // The boundary: no unit other than kvhip.hip names a mirror_*, mview_*, pend_wd or pend_pa member of kv_table — the slot
 // mirrors and the pending partition pass are reached through mirror_decide, set_pending_part, take_pending_part, flush_part and
 // launch_link_hints — and only kvhip.hip compiles the pipelines' kernels (kv_kernels.h, kv_fused.h, kv_papply.h), which the
-// other units reach through the launch_* functions.
+// other units reach through the launch_* functions.  The descriptors of a batched launch go to the device through
+// Staged<Desc> alone (the staging ring: acquire, fill, upload, busy until the stream has read them).
 #pragma once
 
 #include <algorithm>
@@ -402,11 +403,38 @@ struct BatchStage {       // a small ring, so the host can prepare call k+1 whil
   unsigned cursor = 0;
 };
 extern BatchStage g_stage[64][2];   // [device][0 = inference gather, 1 = training ops]
-int stage_acquire(BatchStage& st, size_t bytes, StageSlot** out);
-struct StageRelease {   // unlocks (and marks the slot busy until the stream gets there) on scope exit
-  BatchStage& st; StageSlot* sl; hipStream_t s; bool launched = false;
-  ~StageRelease() { if (launched) hipEventRecord(sl->consumed, s); st.mu.unlock(); }
+int stage_take(BatchStage& st, size_t bytes, StageSlot** out);   // the ring's next slot; st.mu is HELD where it succeeds
+// `count` descriptors of a batched launch on g_stage[device][ring]: zeroed host descriptors by index, then ONE upload,
+// which is the only way to the device pointer — so a slot a kernel may still read is always marked busy.  The ring stays
+// locked until scope exit.  Check rc before anything else.
+template <class Desc>   // MultiDesc, FinishDesc, BatchGatherDesc
+class Staged {
+  BatchStage& st;
+  StageSlot* sl = nullptr;
+  const size_t bytes;
+  hipStream_t s = nullptr;
+  bool launched = false;
+ public:
+  int rc;
+  Staged(int device, int ring, int count) : st(g_stage[device][ring]), bytes((size_t)count * sizeof(Desc)) {
+    if (!(rc = stage_take(st, bytes, &sl))) std::memset(sl->host, 0, bytes);
+  }
+  Staged(const Staged&) = delete;
+  ~Staged() {   // the slot is busy until the stream gets there
+    if (launched) hipEventRecord(sl->consumed, s);
+    if (sl) st.mu.unlock();
+  }
+  Desc& operator[](int i) { return reinterpret_cast<Desc*>(sl->host)[i]; }
+  int upload(hipStream_t stream, const Desc** dev) {
+    HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, bytes, hipMemcpyHostToDevice, stream));
+    launched = true; s = stream;
+    *dev = reinterpret_cast<const Desc*>(sl->dev);
+    return KV_OK;
+  }
 };
+// a batched launch's grid covers its largest table
+inline void widen(WsDev& wmax, const WsDev& w) { wmax.ntiles = std::max(wmax.ntiles, w.ntiles); wmax.P = std::max(wmax.P, w.P); }
+inline void use_partitions(WsDev& w, unsigned P) { w.P = P; w.pshift = 64 - ilog2(P); }
 int check_same_shape(int num_tables, const kv_handle_t* tables, const char* what);
 
 // ---- kv_ops.hip: the argument checks the batched lookups and the batched optimizer ops share ---------------------------

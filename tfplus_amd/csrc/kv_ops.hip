@@ -376,18 +376,14 @@ int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const void* con
     nmax = std::max<long long>(nmax, ns[i]);
   }
   if (nmax == 0) return KV_OK;
-  BatchStage& st = g_stage[device][1];
-  StageSlot* sl = nullptr;
-  if ((rc = stage_acquire(st, (size_t)num_tables * sizeof(MultiDesc), &sl))) return rc;
-  StageRelease rel{st, sl, s};
-  MultiDesc* hd = reinterpret_cast<MultiDesc*>(sl->host);
+  Staged<MultiDesc> hd(device, 1, num_tables);
+  if (hd.rc) return hd.rc;
   WsDev wmax{};
   for (int i = 0; i < num_tables; ++i) {
     MultiDesc& d = hd[i];
-    std::memset(&d, 0, sizeof d);
     d.w = ws_view(tables[i], std::max<long long>(ns[i], 1), selfs ? &selfs[i] : nullptr);
     if (seg_caps) d.w.seg_cap = seg_caps[i];
-    if (fused_tab(tables[i])) { d.w.P = fused_default_P(std::max<long long>(ns[i], 1)); d.w.pshift = 64 - ilog2(d.w.P); }
+    if (fused_tab(tables[i])) use_partitions(d.w, fused_default_P(std::max<long long>(ns[i], 1)));
     d.a.tv = dev_view(tables[i]); d.a.ts0 = d.a.tv; d.a.ts1 = d.a.tv;
     d.a.day = today(tables[i]);
     d.a.det = tables[i]->deterministic ? 1 : 0;
@@ -397,12 +393,10 @@ int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const void* con
     d.out = outs[i];
     d.n = ns[i];
     if (ns[i] == 0) d.w.ntiles = 0;
-    wmax.ntiles = std::max(wmax.ntiles, d.w.ntiles);
-    wmax.P = std::max(wmax.P, d.w.P);
+    widen(wmax, d.w);
   }
-  HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, (size_t)num_tables * sizeof(MultiDesc), hipMemcpyHostToDevice, s));
-  rel.launched = true;
-  const MultiDesc* md = reinterpret_cast<const MultiDesc*>(sl->dev);
+  const MultiDesc* md;
+  if ((rc = hd.upload(s, &md))) return rc;
   kv_table* t0 = tables[0];
   if (fused_tab(t0)) {
     for (int i = 0; i < num_tables; ++i) tables[i]->fused_index = true;
@@ -648,11 +642,8 @@ int kv_batch_gather_or_zeros(int num_tables, const kv_handle_t* tables, const vo
   // apply that has not finished), and its next op behind this read (rows and flags only: as vars they keep their mirrors)
   for (kv_table* tb : lock.ts)
     if ((rc = enter_op(tb, s, KEEP_VAR, true, false))) return rc;
-  BatchStage& st = g_stage[device][0];
-  StageSlot* sl = nullptr;
-  if ((rc = stage_acquire(st, (size_t)num_tables * sizeof(BatchGatherDesc), &sl))) return rc;
-  StageRelease rel{st, sl, s};
-  BatchGatherDesc* hd = reinterpret_cast<BatchGatherDesc*>(sl->host);
+  Staged<BatchGatherDesc> hd(device, 0, num_tables);
+  if (hd.rc) return hd.rc;
   long long nmax = 0;
   for (int i = 0; i < num_tables; ++i) {
     BatchGatherDesc& d = hd[i];
@@ -664,10 +655,10 @@ int kv_batch_gather_or_zeros(int num_tables, const kv_handle_t* tables, const vo
     nmax = std::max<long long>(nmax, ns[i]);
   }
   if (nmax == 0) return KV_OK;
-  HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, (size_t)num_tables * sizeof(BatchGatherDesc), hipMemcpyHostToDevice, s));
-  rel.launched = true;
+  const BatchGatherDesc* md;
+  if ((rc = hd.upload(s, &md))) return rc;
   dim3 grid((unsigned)nblocks(nmax, TB / 8, 2048), (unsigned)num_tables);
-  k_batch_gather_or_zeros<<<grid, TB, 0, s>>>(reinterpret_cast<const BatchGatherDesc*>(sl->dev));
+  k_batch_gather_or_zeros<<<grid, TB, 0, s>>>(md);
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }

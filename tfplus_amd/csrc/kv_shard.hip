@@ -2,6 +2,9 @@
 // (SURVEY.md §8e).  kv_comm_* (RCCL by dlopen, grouped send / recv; or the caller's transport), kv_shard_* (route / serve /
 // finish phases and the whole ops), the batched kv_multi_shard_* ops, and kv_bucket_by_owner, the routing rule's
 // stand-alone form.  The only unit that knows RCCL; its own kernels are kv_route.h's.
+// Each phase's arguments are built in one place (route_desc, presum_desc, finish_desc) for its single-table and its
+// batched launch; each whole op has one body (shards_lookup, shards_apply), of which the single forms are the one-table
+// case; segment sizes come from shard_bytes, batched groups from groups_of.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -169,21 +172,21 @@ int shard_alloc_buffers(kv_shard* sh, unsigned C) {
 // link), on the communicator's own stream, behind everything `stream` was given and in front of what it gets next.
 // nseg buffers (the tables of a multi-table step) go out in ONE group: RCCL runs a group's sends and receives as one
 // launch, so 40 tables cost one exchange, not 40.
-// skip_self[k] (may be null): segment k of this rank is read from its send buffer by the kernels themselves
-static int comm_exchange(kv_comm* c, int nseg, const void* const* sends, void* const* recvs, const int64_t* bytes_per_peer, hipStream_t s,
-                         const char* skip_self = nullptr) {
+// stay: this rank's own segment is read from the send buffer by the kernels themselves
+struct Seg { const void* send; void* recv; int64_t bytes_per_peer; bool stay; };
+static int comm_exchange(kv_comm* c, int nseg, const Seg* seg, hipStream_t s) {
   if (c->xfn) {   // the caller's transport: everything queued so far has run, then the segments move on the host's clock
     HIP_TRY(hipStreamSynchronize(s));
     for (int k = 0; k < nseg; ++k) {
-      const int r = c->xfn(c->user, sends[k], recvs[k], bytes_per_peer[k]);
+      const int r = c->xfn(c->user, seg[k].send, seg[k].recv, seg[k].bytes_per_peer);
       if (r) return fail(KV_INTERNAL, "the staged exchange failed (callback returned %d)", r);
     }
     return KV_OK;
   }
   if (!c->comm) {   // world of one without RCCL
     for (int k = 0; k < nseg; ++k)
-      if (!(skip_self && skip_self[k]))
-        HIP_TRY(hipMemcpyAsync(recvs[k], sends[k], (size_t)bytes_per_peer[k], hipMemcpyDeviceToDevice, s));
+      if (!seg[k].stay)
+        HIP_TRY(hipMemcpyAsync(seg[k].recv, seg[k].send, (size_t)seg[k].bytes_per_peer, hipMemcpyDeviceToDevice, s));
     return KV_OK;
   }
   const bool hop = s != c->stream;   // the sharded ops run on the communicator's stream themselves: no hop
@@ -191,24 +194,25 @@ static int comm_exchange(kv_comm* c, int nseg, const void* const* sends, void* c
     HIP_TRY(hipEventRecord(c->ev_in, s));
     HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_in, 0));
   }
-  // this rank's own segment never meets RCCL: it stays in place (skip_self: the sharded whole ops read it in the send
+  // this rank's own segment never meets RCCL: it stays in place (stay: the sharded whole ops read it in the send
   // buffer) or is a device copy at HBM speed, queued in front of the group — unless kv_comm_set_self_via_rccl asked for
   // it to go through ncclSend / ncclRecv like a peer's
   const bool self_rccl = c->self_via_rccl;
   if (!self_rccl)
     for (int k = 0; k < nseg; ++k)
-      if (!(skip_self && skip_self[k]))
-        HIP_TRY(hipMemcpyAsync((char*)recvs[k] + (size_t)c->rank * bytes_per_peer[k], (const char*)sends[k] + (size_t)c->rank * bytes_per_peer[k],
-                             (size_t)bytes_per_peer[k], hipMemcpyDeviceToDevice, c->stream));
+      if (!seg[k].stay) {
+        const size_t b = (size_t)seg[k].bytes_per_peer;
+        HIP_TRY(hipMemcpyAsync((char*)seg[k].recv + c->rank * b, (const char*)seg[k].send + c->rank * b, b, hipMemcpyDeviceToDevice, c->stream));
+      }
   const bool grouped = c->world > 1 || self_rccl;
   if (grouped) NCCL_TRY(rccl()->GroupStart());
   ncclResult_t bad = ncclSuccess;   // a failed Send / Recv must not leave the group open on this communicator
   for (int p = 0; p < c->world && bad == ncclSuccess; ++p) {
     if (p == c->rank && !self_rccl) continue;
     for (int k = 0; k < nseg && bad == ncclSuccess; ++k) {   // peer-major: both ends of a pair post the tables in the same order
-      const size_t b = (size_t)bytes_per_peer[k];
-      bad = rccl()->Send((const char*)sends[k] + (size_t)p * b, b, ncclChar, p, c->comm, c->stream);
-      if (bad == ncclSuccess) bad = rccl()->Recv((char*)recvs[k] + (size_t)p * b, b, ncclChar, p, c->comm, c->stream);
+      const size_t b = (size_t)seg[k].bytes_per_peer;
+      bad = rccl()->Send((const char*)seg[k].send + p * b, b, ncclChar, p, c->comm, c->stream);
+      if (bad == ncclSuccess) bad = rccl()->Recv((char*)seg[k].recv + p * b, b, ncclChar, p, c->comm, c->stream);
     }
   }
   if (grouped) {
@@ -256,6 +260,91 @@ static SelfSegment shard_self(const kv_shard* sh, bool grad) {
   return SelfSegment{(unsigned)sh->rank * (sh->C + 1), sh->C + 1, sh->send_pairs, grad ? sh->send_rows : nullptr};
 }
 
+// A shard's segment sizes in bytes, of the (id, count) records and of the rows: one peer's segment, or (whole) the buffer of
+// `world` segments.  Every memset and exchange of the whole ops takes its size from here (an exchange that is not wired is
+// one device copy of the whole buffer).
+struct SegBytes { int64_t pairs, rows; };
+static SegBytes shard_bytes(const kv_shard* sh, bool whole) {
+  const int64_t rec = (int64_t)(sh->C + 1) * (whole ? sh->world : 1);
+  return SegBytes{rec * 16, rec * sh->table->dim * (int64_t)sizeof(float)};
+}
+
+// a route table's pos_ent holds n positions
+static int route_ensure_pos(kv_table* rt, long long n, hipStream_t s) {
+  Workspace& ws = rt->ws;
+  if (ws.pos_cap >= n) return KV_OK;
+  int rc;
+  HIP_TRY(hipStreamSynchronize(s));
+  ws.pos_cap = 0;
+  if ((rc = regrow(&ws.pos_ent, (size_t)std::max<long long>(n, ws.cap_n)))) return rc;
+  ws.pos_cap = std::max<long long>(n, ws.cap_n);
+  return KV_OK;
+}
+
+// The arguments of a shard's route over n ids (d is zeroed) — the index on the entry-list kernels:
+// a table-less tile pass (k_ltile<NOTABLE>: entries, mrow, every position's entry number; d.w is ITS view) and k_papply in
+// PA_UNIQUE mode (the distinct ids numbered, uniq / ucnt written, every entry learns its id's number).  The finish then reads
+// position -> entry -> number -> record, the gradient pre-sum is k_tsum + k_papply PA_DEDUP.
+static void route_desc(kv_shard* sh, long long n, MultiDesc& d) {
+  kv_table* rt = sh->route;
+  d.w = ws_view(rt, n);
+  rt->fused_index = true;
+  choose_partitions(rt, d.w, n);   // (the distinct-id hint of the previous route of this length: k_papply publishes it)
+  d.w.zero_counts = sh->ucnt;
+  d.w.pos_ent = rt->ws.pos_ent;
+  PartArgs& pa = d.a;
+  pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
+  pa.out_keys = sh->uniq;
+  pa.out_counts = sh->ucnt;
+  pa.sparse_unique = 1;   // unique numbers with gaps: no counter to serialise on
+  pa.det = sh->table->deterministic ? 1 : 0;
+  pa.n = n;
+  pa.day_lk = pa.day;
+  if (!pa.det) {   // the numbered ids go straight to their owners' segments (the deterministic mode keeps the ordered scatter)
+    pa.route_world = sh->world; pa.route_rule = sh->rule; pa.route_C = sh->C;
+    pa.route_seg = sh->send_pairs; pa.route_slot_of = sh->slot_of; pa.route_overflow = sh->overflow; pa.route_gcount = sh->gcount;
+    pa.route_need = sh->need; pa.route_uhint = sh->overflow + 1;   // (the launch's last block writes the headers)
+  }
+}
+
+// ... of its gradient pre-sum (d is zeroed): the tile sums of the ids repeated inside their tile, then the per-id sums
+// straight into the records the ids were sent in (k_papply PA_DEDUP over the route's entries, in the route's partitioning)
+static void presum_desc(kv_shard* sh, const float* grad, MultiDesc& d) {
+  kv_table* rt = sh->route;
+  d.w = ws_view(rt, sh->n_last);
+  if (rt->index_P) use_partitions(d.w, rt->index_P);
+  PartArgs& pa = d.a;
+  pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
+  pa.grad = grad;
+  pa.out_sum = sh->send_rows;
+  pa.out_map = sh->slot_of;
+  pa.det = rt->deterministic ? 1 : 0;
+  pa.n = sh->n_last;
+  pa.epart = d.w.epart;
+  pa.day_lk = pa.day;
+}
+
+// ... and of its finish, over the rows that came back: position -> entry -> dense unique index -> the record its id was
+// sent in (this rank's own records, where they stayed in place, in the send buffer)
+static FinishDesc finish_desc(const kv_shard* sh, float* out) {
+  const kv_table* rt = sh->route;
+  FinishDesc d{};
+  d.pos_ent = rt->ws.pos_ent; d.ent_u = rt->ws.ent_b; d.slot_of = sh->slot_of; d.rows = sh->recv_rows; d.out = out;
+  d.n = sh->n_last; d.rows_self = sh->send_rows;
+  d.self_lo = (unsigned)sh->rank * (sh->C + 1); d.self_len = sh->self_in_place ? sh->C + 1 : 0u;
+  d.dim = rt->dim;
+  return d;
+}
+
+// a route with nothing to send — an empty batch, or one that failed or was refused: void headers in the send buffer, so that
+// the peers are not left waiting
+static int shard_void_route(kv_shard* sh, hipStream_t w) {
+  sh->n_last = 0; sh->route_token = 0;
+  HIP_TRY(hipMemsetAsync(sh->counts, 0, (size_t)sh->world * 8, w));
+  k_seg_headers<<<1, MAXW, 0, w>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
+  return KV_OK;
+}
+
 // ids -> local unique ids with counts -> the owners' segments of the send buffer.  2 launches (deterministic mode: 6), no host sync.
 static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_stream_t stream) {
   if (!sh || (n > 0 && !ids) || n < 0 || n > sh->max_ids) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_route: n %lld (max %lld)", (long long)n, sh ? sh->max_ids : 0ll);
@@ -268,48 +357,18 @@ static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_strea
   rt->deterministic = sh->table->deterministic;   // the route index (tile pass, position order) follows the table's mode
   sh->n_last = n;
   sh->route_token = 0;
-  if (n == 0) {
-    HIP_TRY(hipMemsetAsync(sh->counts, 0, (size_t)sh->world * 8, s));
-    k_seg_headers<<<1, MAXW, 0, s>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
-    return KV_OK;
-  }
-  if ((rc = ensure_workspace(rt, n, true, s))) return rc;
-  WsDev wd = ws_view(rt, n);
-  // The route's index on the entry-list kernels:
-  // a table-less tile pass (k_ltile<NOTABLE>: entries, mrow, every position's entry number) and k_papply in PA_UNIQUE
-  // mode (the distinct ids numbered, uniq / ucnt written, every entry learns its id's number).  The finish then reads
-  // position -> entry -> number -> record, the gradient pre-sum is k_tsum + k_papply PA_DEDUP.
-  PartArgs pa{};
-  pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
-  pa.out_keys = sh->uniq;
-  pa.out_counts = sh->ucnt;
-  pa.sparse_unique = 1;   // unique numbers with gaps: no counter to serialise on
-  pa.det = sh->table->deterministic ? 1 : 0;
-  pa.n = n;
-  Workspace& ws = rt->ws;
-  if (ws.pos_cap < n) {
-    HIP_TRY(hipStreamSynchronize(s));
-    ws.pos_cap = 0;
-    if ((rc = regrow(&ws.pos_ent, (size_t)std::max<long long>(n, ws.cap_n)))) return rc;
-    ws.pos_cap = std::max<long long>(n, ws.cap_n);
-  }
-  rt->fused_index = true;
-  choose_partitions(rt, wd, n);   // (the distinct-id hint of the previous route of this length: k_papply publishes it)
-  WsDev wz = wd;
-  wz.zero_counts = sh->ucnt;
-  wz.pos_ent = ws.pos_ent;
-  launch_ltile_notable(rt, pa.tv, wz, ids, n, s);
-  pa.day_lk = pa.day;
-  if (!pa.det) {   // the numbered ids go straight to their owners' segments (the deterministic mode keeps the ordered scatter below)
-    pa.route_world = sh->world; pa.route_rule = sh->rule; pa.route_C = sh->C;
-    pa.route_seg = sh->send_pairs; pa.route_slot_of = sh->slot_of; pa.route_overflow = sh->overflow; pa.route_gcount = sh->gcount;
-    pa.route_need = sh->need; pa.route_uhint = sh->overflow + 1;   // (the launch's last block writes the headers)
-  }
-  if ((rc = launch_papply_ud(wd, pa, PA_UNIQUE, s))) return fail(rc, "route: no kernel for dim %d", rt->dim);
+  if (n == 0) return shard_void_route(sh, s);   // an empty batch: void headers
+  if ((rc = ensure_workspace(rt, n, true, s)) || (rc = route_ensure_pos(rt, n, s))) return rc;
+  MultiDesc d{};
+  route_desc(sh, n, d);
+  launch_ltile_notable(rt, d.a.tv, d.w, ids, n, s);
+  WsDev wd = d.w;
+  wd.zero_counts = nullptr; wd.pos_ent = nullptr;   // (the tile pass alone files those)
+  if ((rc = launch_papply_ud(wd, d.a, PA_UNIQUE, s))) return fail(rc, "route: no kernel for dim %d", rt->dim);
   rt->batch_serial = ++g_serial;
   rt->batch_n = n;
   sh->route_token = rt->batch_serial;
-  if (pa.det) {   // the ordered owner scatter
+  if (d.a.det) {   // the ordered owner scatter
     const unsigned ntr = (unsigned)((n + RT - 1) / RT);
     k_owner_hist_u32<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, (long long)n, sh->world, sh->rule, ntr, sh->hist);
     k_owner_scan<<<1, 1024, 0, s>>>(sh->hist, ntr * sh->world, ntr, sh->world, sh->counts);
@@ -319,10 +378,6 @@ static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_strea
   }
   HIP_TRY(hipGetLastError());
   return KV_OK;
-}
-
-static int shard_exchange_one(kv_comm* comm, const void* send, void* recv, int64_t bytes_per_peer, hipStream_t w, char stay) {
-  return comm_exchange(comm, 1, &send, &recv, &bytes_per_peer, w, &stay);
 }
 
 static int shard_fork(kv_shard* sh, hipStream_t s, hipStream_t work) {
@@ -448,7 +503,6 @@ static bool shard_batchable(const kv_shard* sh, int64_t n) {
 // PA_UNIQUE mode — numbering, the owners' segments, and each table's headers by its own last block.  2 launches.
 static int multi_route_impl(const kv_shard_t* shards, const int* todo, int m, const void* const* ids, const int64_t* n, hipStream_t s) {
   int rc;
-  const int device = shards[todo[0]]->table->device;
   std::vector<kv_table*> rts;
   for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
   MultiLock lock(rts);
@@ -459,49 +513,20 @@ static int multi_route_impl(const kv_shard_t* shards, const int* todo, int m, co
     rt->deterministic = false;
     sh->n_last = n[todo[j]];
     sh->route_token = 0;
-    if ((rc = ensure_workspace(rt, sh->n_last, true, s))) return rc;
-    Workspace& ws = rt->ws;
-    if (ws.pos_cap < sh->n_last) {
-      HIP_TRY(hipStreamSynchronize(s));
-      ws.pos_cap = 0;
-      if ((rc = regrow(&ws.pos_ent, (size_t)std::max<long long>(sh->n_last, ws.cap_n)))) return rc;
-      ws.pos_cap = std::max<long long>(sh->n_last, ws.cap_n);
-    }
+    if ((rc = ensure_workspace(rt, sh->n_last, true, s)) || (rc = route_ensure_pos(rt, sh->n_last, s))) return rc;
   }
-  BatchStage& st = g_stage[device][1];
-  StageSlot* sl = nullptr;
-  if ((rc = stage_acquire(st, (size_t)m * sizeof(MultiDesc), &sl))) return rc;
-  StageRelease rel{st, sl, s};
-  MultiDesc* hd = reinterpret_cast<MultiDesc*>(sl->host);
+  Staged<MultiDesc> hd(shards[todo[0]]->table->device, 1, m);
+  if (hd.rc) return hd.rc;
   WsDev wmax{};
   for (int j = 0; j < m; ++j) {
     kv_shard* sh = shards[todo[j]];
-    kv_table* rt = sh->route;
-    MultiDesc& d = hd[j];
-    std::memset(&d, 0, sizeof d);
-    d.w = ws_view(rt, sh->n_last);
-    rt->fused_index = true;
-    choose_partitions(rt, d.w, sh->n_last);
-    d.w.zero_counts = sh->ucnt;
-    d.w.pos_ent = rt->ws.pos_ent;
-    PartArgs& pa = d.a;
-    pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
-    pa.out_keys = sh->uniq; pa.out_counts = sh->ucnt;
-    pa.sparse_unique = 1;
-    pa.det = 0;
-    pa.n = sh->n_last;
-    pa.day_lk = pa.day;
-    pa.route_world = sh->world; pa.route_rule = sh->rule; pa.route_C = sh->C;
-    pa.route_seg = sh->send_pairs; pa.route_slot_of = sh->slot_of; pa.route_overflow = sh->overflow; pa.route_gcount = sh->gcount;
-    pa.route_need = sh->need; pa.route_uhint = sh->overflow + 1;
-    d.ids = ids[todo[j]];
-    d.n = sh->n_last;
-    wmax.ntiles = std::max(wmax.ntiles, d.w.ntiles);
-    wmax.P = std::max(wmax.P, d.w.P);
+    route_desc(sh, sh->n_last, hd[j]);
+    hd[j].ids = ids[todo[j]];
+    hd[j].n = sh->n_last;
+    widen(wmax, hd[j].w);
   }
-  HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, (size_t)m * sizeof(MultiDesc), hipMemcpyHostToDevice, s));
-  rel.launched = true;
-  const MultiDesc* md = reinterpret_cast<const MultiDesc*>(sl->dev);
+  const MultiDesc* md;
+  if ((rc = hd.upload(s, &md))) return rc;
   launch_ltile_multi_notable(wmax, m, md, s);
   // (PA_UNIQUE never reaches the code that depends on the row geometry: one variant serves every dim)
   PartArgs p0 = hd[0].a;
@@ -521,15 +546,11 @@ static int multi_route_impl(const kv_shard_t* shards, const int* todo, int m, co
 // finish of the tables todo[0..m) — all of one row geometry (row_lanes(dim)): 1 launch
 static int multi_finish_impl(const kv_shard_t* shards, const int* todo, int m, float* const* outs, hipStream_t s) {
   int rc;
-  const int device = shards[todo[0]]->table->device;
   std::vector<kv_table*> rts;
   for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
   MultiLock lock(rts);
-  BatchStage& st = g_stage[device][1];
-  StageSlot* sl = nullptr;
-  if ((rc = stage_acquire(st, (size_t)m * sizeof(FinishDesc), &sl))) return rc;
-  StageRelease rel{st, sl, s};
-  FinishDesc* hd = reinterpret_cast<FinishDesc*>(sl->host);
+  Staged<FinishDesc> hd(shards[todo[0]]->table->device, 1, m);
+  if (hd.rc) return hd.rc;
   long long nmax = 0;
   for (int j = 0; j < m; ++j) {
     kv_shard* sh = shards[todo[j]];
@@ -537,16 +558,11 @@ static int multi_finish_impl(const kv_shard_t* shards, const int* todo, int m, f
     if (rt->batch_serial != sh->route_token || sh->route_token == 0) return fail(KV_FAILED_PRECONDITION, "kv_multi_shard_lookup: finish without route");
     if (!outs[todo[j]]) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_lookup: output pointer is null");
     if ((rc = hand_over(rt, s))) return rc;
-    FinishDesc& d = hd[j];
-    d.pos_ent = rt->ws.pos_ent; d.ent_u = rt->ws.ent_b; d.slot_of = sh->slot_of; d.rows = sh->recv_rows; d.out = outs[todo[j]];
-    d.n = sh->n_last; d.rows_self = sh->send_rows;
-    d.self_lo = (unsigned)sh->rank * (sh->C + 1); d.self_len = sh->self_in_place ? sh->C + 1 : 0u;
-    d.dim = rt->dim; d.pad = 0;
+    hd[j] = finish_desc(sh, outs[todo[j]]);
     nmax = std::max<long long>(nmax, sh->n_last);
   }
-  HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, (size_t)m * sizeof(FinishDesc), hipMemcpyHostToDevice, s));
-  rel.launched = true;
-  const FinishDesc* md = reinterpret_cast<const FinishDesc*>(sl->dev);
+  const FinishDesc* md;
+  if ((rc = hd.upload(s, &md))) return rc;
   const dim3 grid((unsigned)nblocks(nmax, TB, 8192), (unsigned)m);
 #define KV_SFM(VQ) k_shard_finish_multi<VQ><<<grid, TB, 0, s>>>(md)
   switch (row_lanes(shards[todo[0]]->table->dim)) {
@@ -558,10 +574,10 @@ static int multi_finish_impl(const kv_shard_t* shards, const int* todo, int m, f
   return KV_OK;
 }
 
-// gradient pre-sum of the tables todo[0..m) — all of one dim: the tile sums, then k_papply_multi PA_DEDUP.  2 launches.
+// gradient pre-sum of the tables todo[0..m) — all of one dim, none in deterministic mode: the tile sums, then k_papply_multi
+// PA_DEDUP.  2 launches.
 static int multi_presum_impl(const kv_shard_t* shards, const int* todo, int m, const float* const* grads, hipStream_t s) {
   int rc;
-  const int device = shards[todo[0]]->table->device;
   std::vector<kv_table*> rts;
   for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
   MultiLock lock(rts);
@@ -574,40 +590,231 @@ static int multi_presum_impl(const kv_shard_t* shards, const int* todo, int m, c
     if ((rc = hand_over(rt, s))) return rc;
     if ((rc = ensure_workspace(rt, sh->n_last, true, s))) return rc;
   }
-  BatchStage& st = g_stage[device][1];
-  StageSlot* sl = nullptr;
-  if ((rc = stage_acquire(st, (size_t)m * sizeof(MultiDesc), &sl))) return rc;
-  StageRelease rel{st, sl, s};
-  MultiDesc* hd = reinterpret_cast<MultiDesc*>(sl->host);
+  Staged<MultiDesc> hd(shards[todo[0]]->table->device, 1, m);
+  if (hd.rc) return hd.rc;
   WsDev wmax{};
-  long long nmax = 0;
   for (int j = 0; j < m; ++j) {
-    kv_shard* sh = shards[todo[j]];
-    kv_table* rt = sh->route;
-    MultiDesc& d = hd[j];
-    std::memset(&d, 0, sizeof d);
-    d.w = ws_view(rt, sh->n_last);
-    if (rt->index_P) { d.w.P = rt->index_P; d.w.pshift = 64 - ilog2(d.w.P); }
-    PartArgs& pa = d.a;
-    pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
-    pa.grad = grads[todo[j]];
-    pa.out_sum = sh->send_rows;
-    pa.out_map = sh->slot_of;
-    pa.det = 0;
-    pa.n = sh->n_last;
-    pa.epart = d.w.epart;
-    pa.day_lk = pa.day;
-    d.n = sh->n_last;
-    wmax.ntiles = std::max(wmax.ntiles, d.w.ntiles);
-    wmax.P = std::max(wmax.P, d.w.P);
-    nmax = std::max<long long>(nmax, sh->n_last);
+    presum_desc(shards[todo[j]], grads[todo[j]], hd[j]);
+    hd[j].a.det = 0;
+    hd[j].n = hd[j].a.n;
+    widen(wmax, hd[j].w);
   }
-  HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, (size_t)m * sizeof(MultiDesc), hipMemcpyHostToDevice, s));
-  rel.launched = true;
-  const MultiDesc* md = reinterpret_cast<const MultiDesc*>(sl->dev);
+  const MultiDesc* md;
+  if ((rc = hd.upload(s, &md))) return rc;
   if ((rc = launch_tsum(hd[0].a.tv, wmax, nullptr, s, md, m))) return fail(rc, "tile sums: no kernel for dim %d", hd[0].a.tv.dim);
   if ((rc = launch_papply_ud(wmax, hd[0].a, PA_DEDUP, s, md, m))) return fail(rc, "gradient pre-sum: no kernel for dim %d", hd[0].a.tv.dim);
   HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+// ---- the whole ops: kv_shard_lookup / kv_shard_apply are kv_multi_shard_lookup / kv_multi_shard_apply of one table -----------
+// A failure of THIS rank's phase (out of memory, a bad argument) must not leave the peers waiting in a grouped recv: the
+// exchanges are queued all the same — void headers for a failed route, zero rows for a failed serve or pre-sum — and the
+// first error is returned once everything is queued.  Only a failed exchange or agreement returns at once.
+struct FirstError {
+  int code = KV_OK;
+  std::string msg;
+  int operator()(int r) { if (r && !code) { code = r; msg = kv_last_error(); } return r; }
+};
+
+static int shard_zero_rows(kv_shard* sh, hipStream_t w) {
+  HIP_TRY(hipMemsetAsync(sh->send_rows, 0, (size_t)shard_bytes(sh, true).rows, w));
+  return KV_OK;
+}
+
+// one grouped exchange for all tables: their (id, count) segments, or (rows) their row segments
+static int shards_exchange(const kv_shard_t* shards, int ntab, kv_comm* comm, bool rows, hipStream_t w) {
+  std::vector<Seg> seg(ntab);
+  for (int k = 0; k < ntab; ++k) {
+    const kv_shard* sh = shards[k];
+    const SegBytes b = shard_bytes(sh, !wired(comm));
+    seg[k] = rows ? Seg{sh->send_rows, sh->recv_rows, b.rows, sh->self_in_place} : Seg{sh->send_pairs, sh->recv_pairs, b.pairs, sh->self_in_place};
+  }
+  return comm_exchange(comm, ntab, seg.data(), w);
+}
+
+// The tables [0, ntab) that take part in a batched launch, split by key(k) (negative: table k takes no part): the groups of at
+// least two tables, in ascending key order, each in table order.  The callers launch those and then, in table order, the
+// tables left over one by one.
+template <class Key>
+static std::vector<std::vector<int>> groups_of(int ntab, Key key) {
+  std::vector<std::vector<int>> out;
+  if (ntab < 2) return out;
+  std::vector<std::pair<int, int>> kk;
+  for (int k = 0; k < ntab; ++k) {
+    const int q = key(k);
+    if (q >= 0) kk.emplace_back(q, k);
+  }
+  std::sort(kk.begin(), kk.end());
+  for (size_t i = 0, j; i < kk.size(); i = j) {
+    for (j = i + 1; j < kk.size() && kk[j].first == kk[i].first;) ++j;
+    if (j - i < 2) continue;
+    out.emplace_back();
+    for (size_t e = i; e < j; ++e) out.back().push_back(kk[e].second);
+  }
+  return out;
+}
+
+// the owner side of a table can join a batched lookup / apply over the receive buffers
+static bool shard_owner_batchable(const kv_shard* sh) {
+  return sh->table->key_dtype == KV_DT_INT64 && (long long)sh->world * (sh->C + 1) <= (1ll << 21);
+}
+
+// Forked from `s` onto the communicator's stream (the caller's stream is free for the dense tower; phases and exchanges in
+// one queue: no event hop between a kernel and its exchange): verify, route, lossless agreement and the re-route of grown
+// tables, exchange, serve, exchange, finish.  single: kv_shard_lookup — the phase events of kv_shard_profile are its alone.
+static int shards_lookup(const char* what, bool single, const kv_shard_t* shards, int ntab, kv_comm* comm, const void* const* ids,
+                         const int64_t* n, float* const* outs, int join, hipStream_t s) {
+  int rc;
+  DeviceGuard dg(shards[0]->table->device);
+  hipStream_t w = comm->stream;
+  // The lossless mode's agreement reads a device word on the host: one stream synchronisation, not allowed inside a stream
+  // capture.  Refused HERE, before the communicator's stream is forked into the capture and before anything is queued (a
+  // refusal behind the fork would leave the side stream unjoined and invalidate the caller's capture; ADVICE r5).
+  bool lossless = false;
+  for (int k = 0; k < ntab; ++k) lossless = lossless || shards[k]->lossless;
+  if (lossless && (stream_is_capturing(s) || stream_is_capturing(w)))
+    return fail(KV_FAILED_PRECONDITION, "%s under stream capture: the lossless mode (the default) synchronises once per lookup; "
+                                        "capture sharded steps with kv_shard_set_lossless(shard, 0)%s",
+                what, single ? " and a peer_capacity sized for the workload" : "");
+  for (int k = 0; k < ntab; ++k)
+    if ((rc = shard_verify(shards[k], comm))) return rc;
+  std::vector<unsigned> seen(ntab);
+  for (int k = 0; k < ntab; ++k) seen[k] = shard_take_flag(shards[k]);
+  kv_shard* const sh0 = shards[0];
+  if ((rc = shard_fork(sh0, s, w))) return rc;
+  FirstError note;
+  std::vector<char> routed(ntab, 1), done(ntab, 0);
+  for (int k = 0; k < ntab; ++k) shards[k]->self_in_place = shard_can_stay(shards[k]);
+  const bool pm = single && shard_prof_begin(sh0, true);
+  shard_prof_mark(sh0, pm, 0, w);
+  auto route = [&](int k) -> int {
+    if (routed[k] && note(lookup_route_impl(shards[k], ids[k], n[k], w))) routed[k] = 0;
+    return routed[k] ? KV_OK : shard_void_route(shards[k], w);
+  };
+  // the tables whose route is the entry-list one go together: 2 launches for all of them
+  for (const auto& grp : groups_of(ntab, [&](int k) { return shard_batchable(shards[k], n[k]) ? 0 : -1; })) {
+    const bool ok = !note(multi_route_impl(shards, grp.data(), (int)grp.size(), ids, n, w));
+    for (int k : grp) { routed[k] = ok; done[k] = ok; }   // (failed: void headers below, the peers are not left waiting)
+  }
+  for (int k = 0; k < ntab; ++k)
+    if (!done[k] && (rc = route(k))) return rc;
+  {   // lossless tables: one agreement for all of them (every rank takes part, whatever its own route did), then the grown
+      // ones are routed again — or, where this rank's batch was refused, get void headers in the new buffers too
+    std::vector<char> grown(ntab, 0);
+    if ((rc = shard_agree_many(shards, ntab, comm, w, grown.data()))) return rc;
+    for (int k = 0; k < ntab; ++k)
+      if (grown[k]) {
+        shards[k]->self_in_place = shard_can_stay(shards[k]);   // (the record count changed)
+        if ((rc = route(k))) return rc;
+      }
+  }
+  shard_prof_mark(sh0, pm, 1, w);
+  if ((rc = shards_exchange(shards, ntab, comm, false, w))) return rc;
+  shard_prof_mark(sh0, pm, 2, w);
+  // the owners' lookups: the tables of one dim in one batched lookup over their receive buffers (tile pass of all of them
+  // in one launch; the partition passes stay pending for the batched apply)
+  done.assign(ntab, 0);
+  for (const auto& grp : groups_of(ntab, [&](int k) { return shard_owner_batchable(shards[k]) ? shards[k]->table->dim : -1; })) {
+    const int m = (int)grp.size();
+    std::vector<kv_handle_t> tb(m);
+    std::vector<const void*> ip(m);
+    std::vector<int64_t> nn(m);
+    std::vector<float*> op(m);
+    std::vector<kv_batch_token_t> tok(m, 0);
+    std::vector<unsigned> caps(m);
+    std::vector<SelfSegment> selfs(m);
+    for (int j = 0; j < m; ++j) {
+      kv_shard* sh = shards[grp[j]];
+      tb[j] = sh->table; ip[j] = sh->recv_pairs; nn[j] = (int64_t)sh->world * (sh->C + 1); op[j] = sh->send_rows; caps[j] = sh->C + 1;
+      sh->serve_token = 0;
+      selfs[j] = shard_self(sh, false);
+    }
+    if (note(multi_lookup_impl(m, tb.data(), ip.data(), nullptr, nn.data(), op.data(), tok.data(), w, 2, caps.data(), selfs.data()))) {
+      for (int k : grp)
+        if ((rc = shard_zero_rows(shards[k], w))) return rc;
+    } else {
+      for (int j = 0; j < m; ++j) shards[grp[j]]->serve_token = tok[j];
+    }
+    for (int k : grp) done[k] = 1;
+  }
+  for (int k = 0; k < ntab; ++k)
+    if (!done[k] && note(kv_shard_lookup_serve(shards[k], w)) && (rc = shard_zero_rows(shards[k], w))) return rc;
+  shard_prof_mark(sh0, pm, 3, w);
+  if ((rc = shards_exchange(shards, ntab, comm, true, w))) return rc;
+  shard_prof_mark(sh0, pm, 4, w);
+  // finish, of every table whose own route succeeded: the tables of one row geometry in one launch
+  done.assign(ntab, 0);
+  for (const auto& grp : groups_of(ntab, [&](int k) { return routed[k] && shards[k]->n_last > 0 ? row_lanes(shards[k]->table->dim) : -1; }))
+    if (!note(multi_finish_impl(shards, grp.data(), (int)grp.size(), outs, w)))
+      for (int k : grp) done[k] = 1;
+  for (int k = 0; k < ntab; ++k)
+    if (routed[k] && !done[k]) note(kv_shard_lookup_finish(shards[k], outs[k], w));
+  shard_prof_mark(sh0, pm, 5, w);
+  if (pm) sh0->pend_l = true;
+  if ((rc = shard_done(sh0, s, w, join))) return rc;
+  if (note.code) return fail(note.code, "%s (this rank's exchanges were queued all the same)", note.msg.c_str());
+  for (int k = 0; k < ntab; ++k)
+    if ((rc = shard_late_report(shards[k], seen[k]))) return rc;
+  return KV_OK;
+}
+
+// backward, as shards_lookup: the gradient pre-sum, ONE exchange, the owners' applies.  A rank whose pre-sum failed still
+// takes part in the exchange (zero gradient rows).  slot1 may be null (no table has a second slot table).
+static int shards_apply(bool single, const kv_shard_t* shards, int ntab, kv_comm* comm, int optimizer, const kv_handle_t* slot0,
+                        const kv_handle_t* slot1, const float* const* grads, const float* hp, int join, hipStream_t s) {
+  int rc;
+  DeviceGuard dg(shards[0]->table->device);
+  hipStream_t w = comm->stream;
+  kv_shard* const sh0 = shards[0];
+  if ((rc = shard_fork(sh0, s, w))) return rc;
+  FirstError note;
+  const bool pm = single && shard_prof_begin(sh0, false);
+  shard_prof_mark(sh0, pm, 6, w);
+  // gradient pre-sum: the tables of one dim whose route has no ordered owner scatter in two launches
+  std::vector<char> done(ntab, 0);   // 1: summed; 2: its group failed (zero gradient rows)
+  for (const auto& grp : groups_of(ntab, [&](int k) {
+         return shards[k]->n_last > 0 && !shards[k]->table->deterministic ? shards[k]->table->dim : -1; })) {
+    const char r = note(multi_presum_impl(shards, grp.data(), (int)grp.size(), grads, w)) ? 2 : 1;
+    for (int k : grp) done[k] = r;
+  }
+  for (int k = 0; k < ntab; ++k)
+    if (done[k] != 1 && (done[k] == 2 || note(kv_shard_apply_route(shards[k], grads[k], w))) && (rc = shard_zero_rows(shards[k], w))) return rc;
+  shard_prof_mark(sh0, pm, 7, w);
+  if ((rc = shards_exchange(shards, ntab, comm, true, w))) return rc;
+  shard_prof_mark(sh0, pm, 8, w);
+  // the owners' applies: the tables of one dim whose serve lookups left their batch index in one batched apply
+  done.assign(ntab, 0);
+  for (const auto& grp : groups_of(ntab, [&](int k) {
+         const kv_shard* sh = shards[k];
+         return optimizer >= 0 && optimizer <= 5 && shard_owner_batchable(sh) && sh->serve_token != 0 &&
+                        sh->serve_token == sh->table->batch_serial && sh->table->fused_index && slot0[k] != nullptr &&
+                        (!two_slots(optimizer) || (slot1 && slot1[k]))
+                    ? sh->table->dim : -1; })) {
+    const int m = (int)grp.size();
+    std::vector<kv_handle_t> vs(m), s0(m), s1(m);
+    std::vector<const float*> gp(m);
+    std::vector<const void*> ip(m);
+    std::vector<int64_t> nn(m);
+    std::vector<kv_batch_token_t> tok(m);
+    std::vector<SelfSegment> selfs(m);
+    for (int j = 0; j < m; ++j) {
+      kv_shard* sh = shards[grp[j]];
+      vs[j] = sh->table; s0[j] = slot0[grp[j]]; s1[j] = slot1 ? slot1[grp[j]] : nullptr;
+      gp[j] = sh->recv_rows; ip[j] = sh->recv_pairs; nn[j] = (int64_t)sh->world * (sh->C + 1); tok[j] = sh->serve_token;
+      selfs[j] = shard_self(sh, true);
+    }
+    // (require_reuse: the ids are (id, count) records — an apply that rebuilt its index from them would read them as plain ids)
+    note(multi_apply(shard_opt_call(optimizer, hp), m, vs.data(), s0.data(), s1.data(), gp.data(), ip.data(), nn.data(), tok.data(), w,
+                     false, true, selfs.data()));
+    for (int k : grp) done[k] = 1;
+  }
+  for (int k = 0; k < ntab; ++k)
+    if (!done[k]) note(kv_shard_apply_serve(shards[k], optimizer, slot0[k], slot1 ? slot1[k] : nullptr, hp, w));
+  shard_prof_mark(sh0, pm, 9, w);
+  if (pm) sh0->pend_a = true;
+  if ((rc = shard_done(sh0, s, w, join))) return rc;
+  if (note.code) return fail(note.code, "%s (this rank's exchange was queued all the same)", note.msg.c_str());
   return KV_OK;
 }
 
@@ -743,7 +950,8 @@ int kv_comm_destroy(kv_comm_t c) {
 int kv_comm_all_to_all(kv_comm_t c, const void* send, void* recv, int64_t bytes_per_peer, kv_stream_t stream) {
   if (!c || !send || !recv || bytes_per_peer < 0) return fail(KV_INVALID_ARGUMENT, "kv_comm_all_to_all: bad arguments");
   DeviceGuard dg(c->device);
-  return comm_exchange(c, 1, &send, &recv, &bytes_per_peer, (hipStream_t)stream);
+  const Seg all{send, recv, bytes_per_peer, false};
+  return comm_exchange(c, 1, &all, (hipStream_t)stream);
 }
 
 int kv_shard_create(kv_handle_t local_table, int world, int rank, int owner_rule, int64_t max_ids, int64_t peer_capacity,
@@ -813,8 +1021,8 @@ int kv_shard_buffers(kv_shard_t sh, void** send_pairs, void** recv_pairs, void**
   if (recv_pairs) *recv_pairs = sh->recv_pairs;
   if (send_rows) *send_rows = sh->send_rows;
   if (recv_rows) *recv_rows = sh->recv_rows;
-  if (pair_bytes_per_peer) *pair_bytes_per_peer = (int64_t)(sh->C + 1) * 16;
-  if (row_bytes_per_peer) *row_bytes_per_peer = (int64_t)(sh->C + 1) * sh->table->dim * (int64_t)sizeof(float);
+  if (pair_bytes_per_peer) *pair_bytes_per_peer = shard_bytes(sh, false).pairs;
+  if (row_bytes_per_peer) *row_bytes_per_peer = shard_bytes(sh, false).rows;
   return KV_OK;
 }
 
@@ -845,14 +1053,11 @@ int kv_shard_lookup_finish(kv_shard_t sh, float* out, kv_stream_t stream) {
   std::lock_guard<std::mutex> l(rt->mu);
   if (rt->batch_serial != sh->route_token || sh->route_token == 0) return fail(KV_FAILED_PRECONDITION, "kv_shard_lookup_finish without kv_shard_lookup_route");
   { int rc; if ((rc = hand_over(rt, (hipStream_t)stream))) return rc; }
-  // over the rows that came back: position -> entry -> dense unique index -> the record its id was sent in
-  const int q = row_lanes(rt->dim);
-  const int grid = nblocks(sh->n_last, TB, 8192);
+  const FinishDesc d = finish_desc(sh, out);
+  const int grid = nblocks(d.n, TB, 8192);
   hipStream_t st = (hipStream_t)stream;
-  const unsigned slo = (unsigned)sh->rank * (sh->C + 1), slen = sh->self_in_place ? sh->C + 1 : 0u;
-#define KV_SF(VQ) k_shard_finish<VQ><<<grid, TB, 0, st>>>(rt->ws.pos_ent, rt->ws.ent_b, sh->slot_of, sh->recv_rows, out, sh->n_last, rt->dim, \
-                                                        sh->send_rows, slo, slen)
-  switch (q) {
+#define KV_SF(VQ) k_shard_finish<VQ><<<grid, TB, 0, st>>>(d.pos_ent, d.ent_u, d.slot_of, d.rows, d.out, d.n, d.dim, d.rows_self, d.self_lo, d.self_len)
+  switch (row_lanes(d.dim)) {
     case 1: KV_SF(1); break;   case 2: KV_SF(2); break;   case 4: KV_SF(4); break;   case 8: KV_SF(8); break;
     case 16: KV_SF(16); break; case 32: KV_SF(32); break; default: KV_SF(64); break;
   }
@@ -875,21 +1080,10 @@ int kv_shard_apply_route(kv_shard_t sh, const float* grad, kv_stream_t stream) {
   int rc;
   if ((rc = hand_over(rt, s))) return rc;
   if ((rc = ensure_workspace(rt, sh->n_last, true, s))) return rc;
-  WsDev wd = ws_view(rt, sh->n_last);
-  if (rt->index_P) { wd.P = rt->index_P; wd.pshift = 64 - ilog2(wd.P); }   // the route's partitioning
-  // the tile sums of the ids repeated inside their tile, then the per-id sums straight into the records the ids were
-  // sent in (k_papply PA_DEDUP over the route's entries)
-  PartArgs pa{};
-  pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
-  pa.grad = grad;
-  pa.out_sum = sh->send_rows;
-  pa.out_map = sh->slot_of;
-  pa.det = rt->deterministic ? 1 : 0;
-  pa.n = sh->n_last;
-  pa.epart = wd.epart;
-  pa.day_lk = pa.day;
-  if ((rc = launch_tsum(pa.tv, wd, grad, s))) return fail(rc, "tile sums: no kernel for dim %d", rt->dim);
-  if ((rc = launch_papply_ud(wd, pa, PA_DEDUP, s))) return fail(rc, "gradient pre-sum: no kernel for dim %d", rt->dim);
+  MultiDesc d{};
+  presum_desc(sh, grad, d);
+  if ((rc = launch_tsum(d.a.tv, d.w, grad, s))) return fail(rc, "tile sums: no kernel for dim %d", rt->dim);
+  if ((rc = launch_papply_ud(d.w, d.a, PA_DEDUP, s))) return fail(rc, "gradient pre-sum: no kernel for dim %d", rt->dim);
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -971,93 +1165,13 @@ int kv_shard_agree_local(const kv_shard_t* shards, int world, int* rerouted, kv_
 
 int kv_shard_lookup(kv_shard_t sh, kv_comm_t comm, const void* ids, int64_t n, float* out, int join, kv_stream_t stream) {
   if (!sh || !comm || comm->world != sh->world) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup: shard / communicator mismatch");
-  DeviceGuard dg(sh->table->device);
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  // The lossless mode's agreement reads a device word on the host: one stream synchronisation, not allowed inside a stream
-  // capture.  Refused HERE, before the communicator's stream is forked into the capture and before anything is queued (a
-  // refusal behind the fork would leave the side stream unjoined and invalidate the caller's capture; ADVICE r5).
-  if (sh->lossless && (stream_is_capturing(s) || stream_is_capturing(comm->stream)))
-    return fail(KV_FAILED_PRECONDITION, "kv_shard_lookup under stream capture: the lossless mode (the default) synchronises once per "
-                                        "lookup; capture sharded steps with kv_shard_set_lossless(shard, 0) and a peer_capacity "
-                                        "sized for the workload");
-  if ((rc = shard_verify(sh, comm))) return rc;
-  const unsigned seen = shard_take_flag(sh);
-  hipStream_t w = comm->stream;   // phases and exchanges in one queue: no event hop between a kernel and its exchange
-  if ((rc = shard_fork(sh, s, w))) return rc;
-  int64_t pb = (int64_t)(sh->C + 1) * 16, rb = (int64_t)(sh->C + 1) * sh->table->dim * (int64_t)sizeof(float);
-  // A failure of THIS rank's phase (out of memory, a bad argument) must not leave the peers waiting in a grouped recv:
-  // the exchanges are queued all the same — void headers for a failed route, zero rows for a failed serve — and the
-  // first error is returned once everything is queued.  Only a failed exchange itself returns at once.
-  int first = KV_OK;
-  std::string first_msg;
-  auto note = [&](int r) { if (r && !first) { first = r; first_msg = kv_last_error(); } return r; };
-  sh->self_in_place = shard_can_stay(sh);
-  char stay = sh->self_in_place ? 1 : 0;
-  const bool pm = shard_prof_begin(sh, true);
-  shard_prof_mark(sh, pm, 0, w);
-  if (note(lookup_route_impl(sh, ids, n, w))) {
-    sh->n_last = 0; sh->route_token = 0;
-    HIP_TRY(hipMemsetAsync(sh->counts, 0, (size_t)sh->world * 8, w));
-    k_seg_headers<<<1, MAXW, 0, w>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
-  }
-  if (sh->lossless) {   // every rank takes part in the agreement, whatever its own route did
-    char grown = 0;
-    if ((rc = shard_agree_many(&sh, 1, comm, w, &grown))) return rc;
-    if (grown) {
-      pb = (int64_t)(sh->C + 1) * 16; rb = (int64_t)(sh->C + 1) * sh->table->dim * (int64_t)sizeof(float);
-      stay = (sh->self_in_place = shard_can_stay(sh)) ? 1 : 0;   // (the record count changed)
-      if (!first && note(lookup_route_impl(sh, ids, n, w))) { sh->n_last = 0; sh->route_token = 0; }
-      if (first) {   // this rank's batch was refused: its segments are void in the new buffers too
-        HIP_TRY(hipMemsetAsync(sh->counts, 0, (size_t)sh->world * 8, w));
-        k_seg_headers<<<1, MAXW, 0, w>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
-      }
-    }
-  }
-  shard_prof_mark(sh, pm, 1, w);
-  if ((rc = shard_exchange_one(comm, sh->send_pairs, sh->recv_pairs, wired(comm) ? pb : pb * sh->world, w, stay))) return rc;
-  shard_prof_mark(sh, pm, 2, w);
-  if (note(kv_shard_lookup_serve(sh, w)))
-    HIP_TRY(hipMemsetAsync(sh->send_rows, 0, (size_t)rb * sh->world, w));
-  shard_prof_mark(sh, pm, 3, w);
-  if ((rc = shard_exchange_one(comm, sh->send_rows, sh->recv_rows, wired(comm) ? rb : rb * sh->world, w, stay))) return rc;
-  shard_prof_mark(sh, pm, 4, w);
-  if (!first) note(kv_shard_lookup_finish(sh, out, w));
-  shard_prof_mark(sh, pm, 5, w);
-  if (pm) sh->pend_l = true;
-  if ((rc = shard_done(sh, s, w, join))) return rc;
-  if (first) return fail(first, "%s (this rank's exchanges were queued all the same)", first_msg.c_str());
-  return shard_late_report(sh, seen);
+  return shards_lookup("kv_shard_lookup", true, &sh, 1, comm, &ids, &n, &out, join, (hipStream_t)stream);
 }
 
 int kv_shard_apply(kv_shard_t sh, kv_comm_t comm, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* grad,
                    const float* hp, int join, kv_stream_t stream) {
   if (!sh || !comm || comm->world != sh->world) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply: shard / communicator mismatch");
-  DeviceGuard dg(sh->table->device);
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  hipStream_t w = comm->stream;
-  if ((rc = shard_fork(sh, s, w))) return rc;
-  const int64_t rb = (int64_t)(sh->C + 1) * sh->table->dim * (int64_t)sizeof(float);
-  // as in kv_shard_lookup: a rank whose route phase failed still takes part in the exchange (zero gradient rows)
-  int first = KV_OK;
-  std::string first_msg;
-  const bool pm = shard_prof_begin(sh, false);
-  shard_prof_mark(sh, pm, 6, w);
-  if ((first = kv_shard_apply_route(sh, grad, w))) {
-    first_msg = kv_last_error();
-    HIP_TRY(hipMemsetAsync(sh->send_rows, 0, (size_t)rb * sh->world, w));
-  }
-  shard_prof_mark(sh, pm, 7, w);
-  if ((rc = shard_exchange_one(comm, sh->send_rows, sh->recv_rows, wired(comm) ? rb : rb * sh->world, w, sh->self_in_place ? 1 : 0))) return rc;
-  shard_prof_mark(sh, pm, 8, w);
-  rc = kv_shard_apply_serve(sh, optimizer, slot0, slot1, hp, w);
-  shard_prof_mark(sh, pm, 9, w);
-  if (pm) sh->pend_a = true;
-  if (rc && !first) { first = rc; first_msg = kv_last_error(); }
-  if ((rc = shard_done(sh, s, w, join))) return rc;
-  if (first) return fail(first, "%s (this rank's exchange was queued all the same)", first_msg.c_str());
-  return KV_OK;
+  return shards_apply(true, &sh, 1, comm, optimizer, &slot0, &slot1, &grad, hp, join, (hipStream_t)stream);
 }
 
 int kv_multi_shard_lookup(const kv_shard_t* shards, int ntab, kv_comm_t comm, const void* const* ids, const int64_t* n,
@@ -1065,138 +1179,7 @@ int kv_multi_shard_lookup(const kv_shard_t* shards, int ntab, kv_comm_t comm, co
   int rc;
   if ((rc = multi_shard_check(shards, ntab, comm, "kv_multi_shard_lookup"))) return rc;
   if (!ids || !n || !outs) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_lookup: null argument list");
-  DeviceGuard dg(shards[0]->table->device);
-  hipStream_t s = (hipStream_t)stream, w = comm->stream;
-  {   // as in kv_shard_lookup: the lossless agreement's synchronisation is refused before the fork, not behind it
-    bool lossless = false;
-    for (int k = 0; k < ntab; ++k) lossless = lossless || shards[k]->lossless;
-    if (lossless && (stream_is_capturing(s) || stream_is_capturing(w)))
-      return fail(KV_FAILED_PRECONDITION, "kv_multi_shard_lookup under stream capture: the lossless mode (the default) synchronises once "
-                                          "per lookup; capture sharded steps with kv_shard_set_lossless(shard, 0)");
-  }
-  for (int k = 0; k < ntab; ++k)
-    if ((rc = shard_verify(shards[k], comm))) return rc;
-  std::vector<unsigned> seen(ntab);
-  for (int k = 0; k < ntab; ++k) seen[k] = shard_take_flag(shards[k]);
-  if ((rc = shard_fork(shards[0], s, w))) return rc;
-  int first = KV_OK;
-  std::string first_msg;
-  auto note = [&](int r) { if (r && !first) { first = r; first_msg = kv_last_error(); } return r; };
-  std::vector<const void*> sp(ntab), sr(ntab);
-  std::vector<void*> rp(ntab), rr(ntab);
-  std::vector<int64_t> pb(ntab), rb(ntab);
-  std::vector<char> routed(ntab, 1), stay(ntab, 0);
-  for (int k = 0; k < ntab; ++k) stay[k] = (shards[k]->self_in_place = shard_can_stay(shards[k])) ? 1 : 0;
-  auto buffers = [&](int k) {
-    kv_shard* sh = shards[k];
-    const int64_t mul = wired(comm) ? 1 : sh->world;
-    pb[k] = (int64_t)(sh->C + 1) * 16 * mul;
-    rb[k] = (int64_t)(sh->C + 1) * sh->table->dim * (int64_t)sizeof(float) * mul;
-    sp[k] = sh->send_pairs; rp[k] = sh->recv_pairs; sr[k] = sh->send_rows; rr[k] = sh->recv_rows;
-  };
-  auto route = [&](int k) -> int {
-    kv_shard* sh = shards[k];
-    if (routed[k] && note(lookup_route_impl(sh, ids[k], n[k], w))) routed[k] = 0;
-    if (!routed[k]) {   // as in kv_shard_lookup: void headers, the peers are not left waiting
-      sh->n_last = 0; sh->route_token = 0;
-      HIP_TRY(hipMemsetAsync(sh->counts, 0, (size_t)sh->world * 8, w));
-      k_seg_headers<<<1, MAXW, 0, w>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
-    }
-    return KV_OK;
-  };
-  {
-    // the tables whose route is the entry-list one go together: 2 launches for all of them
-    std::vector<int> todo;
-    std::vector<char> batched(ntab, 0);
-    for (int k = 0; k < ntab; ++k)
-        if (shard_batchable(shards[k], n[k])) todo.push_back(k);
-    if (todo.size() >= 2) {
-      for (int k : todo) batched[k] = 1;
-      if (note(multi_route_impl(shards, todo.data(), (int)todo.size(), ids, n, w)))
-        for (int k : todo) routed[k] = 0;   // (void headers below: the peers are not left waiting)
-    }
-    for (int k = 0; k < ntab; ++k) {
-      buffers(k);
-      if (batched[k] && routed[k]) continue;
-      if ((rc = route(k))) return rc;
-    }
-  }
-  {   // lossless tables: one agreement for all of them (see shard_agree_many), then the grown ones are routed again
-    std::vector<char> grown(ntab, 0);
-    bool any_lossless = false;
-    for (int k = 0; k < ntab; ++k) any_lossless = any_lossless || shards[k]->lossless;
-    if ((rc = shard_agree_many(shards, ntab, comm, w, grown.data()))) return rc;
-    for (int k = 0; k < ntab; ++k)
-      if (grown[k]) {
-        stay[k] = (shards[k]->self_in_place = shard_can_stay(shards[k])) ? 1 : 0;
-        buffers(k);
-        if ((rc = route(k))) return rc;
-      }
-  }
-  if ((rc = comm_exchange(comm, ntab, sp.data(), rp.data(), pb.data(), w, stay.data()))) return rc;
-  {
-    // the owners' lookups: the tables of one dim in one batched lookup over their receive buffers (tile pass of all of
-    // them in one launch; the partition passes stay pending for the batched apply)
-    std::vector<char> served(ntab, 0);
-    std::vector<int> dims;
-    auto can = [&](int k) {
-      const kv_shard* sh = shards[k];
-      return sh->table->key_dtype == KV_DT_INT64 && (long long)sh->world * (sh->C + 1) <= (1ll << 21);
-    };
-    for (int k = 0; k < ntab; ++k)
-        if (can(k)) dims.push_back(shards[k]->table->dim);
-    std::sort(dims.begin(), dims.end());
-    dims.erase(std::unique(dims.begin(), dims.end()), dims.end());
-    for (int D : dims) {
-      std::vector<int> grp;
-      for (int k = 0; k < ntab; ++k)
-        if (can(k) && shards[k]->table->dim == D) grp.push_back(k);
-      if (grp.size() < 2) continue;
-      const int m = (int)grp.size();
-      std::vector<kv_handle_t> tb(m);
-      std::vector<const void*> ip(m);
-      std::vector<int64_t> nn(m);
-      std::vector<float*> op(m);
-      std::vector<kv_batch_token_t> tok(m, 0);
-      std::vector<unsigned> caps(m);
-      std::vector<SelfSegment> selfs(m);
-      for (int j = 0; j < m; ++j) {
-        kv_shard* sh = shards[grp[j]];
-        tb[j] = sh->table; ip[j] = sh->recv_pairs; nn[j] = (int64_t)sh->world * (sh->C + 1); op[j] = sh->send_rows; caps[j] = sh->C + 1;
-        sh->serve_token = 0;
-        selfs[j] = shard_self(sh, false);
-      }
-      if (note(multi_lookup_impl(m, tb.data(), ip.data(), nullptr, nn.data(), op.data(), tok.data(), w, 2, caps.data(), selfs.data()))) {
-        for (int k : grp) HIP_TRY(hipMemsetAsync(shards[k]->send_rows, 0, (size_t)rb[k] * (wired(comm) ? shards[k]->world : 1), w));
-      } else {
-        for (int j = 0; j < m; ++j) shards[grp[j]]->serve_token = tok[j];
-      }
-      for (int k : grp) served[k] = 1;
-    }
-    for (int k = 0; k < ntab; ++k)
-      if (!served[k] && note(kv_shard_lookup_serve(shards[k], w)))
-        HIP_TRY(hipMemsetAsync(shards[k]->send_rows, 0, (size_t)rb[k] * (wired(comm) ? shards[k]->world : 1), w));
-  }
-  if ((rc = comm_exchange(comm, ntab, sr.data(), rr.data(), rb.data(), w, stay.data()))) return rc;
-  {
-    // finish: the tables of one row geometry in one launch
-    std::vector<char> done(ntab, 0);
-    for (int q : {1, 2, 4, 8, 16, 32, 64}) {
-        std::vector<int> grp;
-        for (int k = 0; k < ntab; ++k)
-          if (routed[k] && shards[k]->n_last > 0 && row_lanes(shards[k]->table->dim) == q) grp.push_back(k);
-        if (grp.size() < 2) continue;
-        if (!note(multi_finish_impl(shards, grp.data(), (int)grp.size(), outs, w)))
-          for (int k : grp) done[k] = 1;
-      }
-    for (int k = 0; k < ntab; ++k)
-      if (routed[k] && !done[k]) note(kv_shard_lookup_finish(shards[k], outs[k], w));
-  }
-  if ((rc = shard_done(shards[0], s, w, join))) return rc;
-  if (first) return fail(first, "%s (this rank's exchanges were queued all the same)", first_msg.c_str());
-  for (int k = 0; k < ntab; ++k)
-    if ((rc = shard_late_report(shards[k], seen[k]))) return rc;
-  return KV_OK;
+  return shards_lookup("kv_multi_shard_lookup", false, shards, ntab, comm, ids, n, outs, join, (hipStream_t)stream);
 }
 
 // slot0 / slot1: one handle per table (slot1 only for the FTRL family, else nullptr); hp as in kv_shard_apply_serve
@@ -1205,89 +1188,7 @@ int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int
   int rc;
   if ((rc = multi_shard_check(shards, ntab, comm, "kv_multi_shard_apply"))) return rc;
   if (!slot0 || !grads || !hp) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_apply: null argument list");
-  DeviceGuard dg(shards[0]->table->device);
-  hipStream_t s = (hipStream_t)stream, w = comm->stream;
-  if ((rc = shard_fork(shards[0], s, w))) return rc;
-  int first = KV_OK;
-  std::string first_msg;
-  auto note = [&](int r) { if (r && !first) { first = r; first_msg = kv_last_error(); } return r; };
-  std::vector<const void*> sr(ntab);
-  std::vector<void*> rr(ntab);
-  std::vector<int64_t> rb(ntab);
-  std::vector<char> stay(ntab, 0);
-  std::vector<char> summed(ntab, 0);
-  {
-    // gradient pre-sum: the tables of one dim whose route has no ordered owner scatter in two launches
-    std::vector<int> dims;
-    for (int k = 0; k < ntab; ++k)
-      if (shards[k]->n_last > 0 && !shards[k]->table->deterministic) dims.push_back(shards[k]->table->dim);
-    std::sort(dims.begin(), dims.end());
-    dims.erase(std::unique(dims.begin(), dims.end()), dims.end());
-    for (int D : dims) {
-      std::vector<int> grp;
-      for (int k = 0; k < ntab; ++k)
-        if (shards[k]->n_last > 0 && !shards[k]->table->deterministic && shards[k]->table->dim == D) grp.push_back(k);
-      if (grp.size() < 2) continue;
-      if (!note(multi_presum_impl(shards, grp.data(), (int)grp.size(), grads, w)))
-        for (int k : grp) summed[k] = 1;
-      else
-        for (int k : grp) summed[k] = 2;   // failed: zero gradient rows below
-    }
-  }
-  for (int k = 0; k < ntab; ++k) {
-    kv_shard* sh = shards[k];
-    stay[k] = sh->self_in_place ? 1 : 0;
-    rb[k] = (int64_t)(sh->C + 1) * sh->table->dim * (int64_t)sizeof(float) * (wired(comm) ? 1 : sh->world);
-    sr[k] = sh->send_rows; rr[k] = sh->recv_rows;
-    if (summed[k] == 1) continue;
-    if (summed[k] == 2 || note(kv_shard_apply_route(sh, grads[k], w)))
-      HIP_TRY(hipMemsetAsync(sh->send_rows, 0, (size_t)rb[k] * (wired(comm) ? sh->world : 1), w));
-  }
-  if ((rc = comm_exchange(comm, ntab, sr.data(), rr.data(), rb.data(), w, stay.data()))) return rc;
-  {
-    // the owners' applies: the tables of one dim whose serve lookups left their batch index in one batched apply
-    std::vector<char> applied(ntab, 0);
-    std::vector<int> dims;
-    auto can = [&](int k) {
-      const kv_shard* sh = shards[k];
-      return sh->table->key_dtype == KV_DT_INT64 && (long long)sh->world * (sh->C + 1) <= (1ll << 21) && sh->serve_token != 0 &&
-             sh->serve_token == sh->table->batch_serial && sh->table->fused_index && slot0[k] != nullptr && (!two_slots(optimizer) || (slot1 && slot1[k]));
-    };
-    if (optimizer >= 0 && optimizer <= 5)
-      for (int k = 0; k < ntab; ++k)
-        if (can(k)) dims.push_back(shards[k]->table->dim);
-    std::sort(dims.begin(), dims.end());
-    dims.erase(std::unique(dims.begin(), dims.end()), dims.end());
-    for (int D : dims) {
-      std::vector<int> grp;
-      for (int k = 0; k < ntab; ++k)
-        if (can(k) && shards[k]->table->dim == D) grp.push_back(k);
-      if (grp.size() < 2) continue;
-      const int m = (int)grp.size();
-      std::vector<kv_handle_t> vs(m), s0(m), s1(m);
-      std::vector<const float*> gp(m);
-      std::vector<const void*> ip(m);
-      std::vector<int64_t> nn(m);
-      std::vector<kv_batch_token_t> tok(m);
-      std::vector<SelfSegment> selfs(m);
-      for (int j = 0; j < m; ++j) {
-        kv_shard* sh = shards[grp[j]];
-        vs[j] = sh->table; s0[j] = slot0[grp[j]]; s1[j] = slot1 ? slot1[grp[j]] : nullptr;
-        gp[j] = sh->recv_rows; ip[j] = sh->recv_pairs; nn[j] = (int64_t)sh->world * (sh->C + 1); tok[j] = sh->serve_token;
-        selfs[j] = shard_self(sh, true);
-      }
-      // (require_reuse: the ids are (id, count) records — an apply that rebuilt its index from them would read them as plain ids)
-      const int r = multi_apply(shard_opt_call(optimizer, hp), m, vs.data(), s0.data(), s1.data(), gp.data(), ip.data(), nn.data(),
-                                tok.data(), w, false, true, selfs.data());
-      note(r);
-      for (int k : grp) applied[k] = 1;
-    }
-    for (int k = 0; k < ntab; ++k)
-      if (!applied[k]) note(kv_shard_apply_serve(shards[k], optimizer, slot0[k], slot1 ? slot1[k] : nullptr, hp, w));
-  }
-  if ((rc = shard_done(shards[0], s, w, join))) return rc;
-  if (first) return fail(first, "%s (this rank's exchange was queued all the same)", first_msg.c_str());
-  return KV_OK;
+  return shards_apply(false, shards, ntab, comm, optimizer, slot0, slot1, grads, hp, join, (hipStream_t)stream);
 }
 
 // The exchange between shards that live in ONE process (all on one device): segment r of shard p's send buffer to

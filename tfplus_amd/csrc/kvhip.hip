@@ -405,8 +405,7 @@ WsDev ws_view(kv_table* t, long long n, const SelfSegment* self) {
   d.hpart = w.hpart;
   d.ctr = w.ctr;
   d.ntiles = (unsigned)((n + TILE - 1) / TILE);
-  d.P = pick_partitions(n);
-  d.pshift = 64 - ilog2(d.P);
+  use_partitions(d, pick_partitions(n));
   d.seg_cap = 0;
   d.zero_counts = nullptr;
   d.dbg = w.dbg;
@@ -863,8 +862,8 @@ std::atomic<uint64_t> g_uid{0};
 // and descriptor kind; the next upload waits until the previous launch has consumed the buffer
 BatchStage g_stage[64][2];   // [device][0 = inference gather, 1 = training ops]
 
-// returns with st.mu HELD (released by StageRelease after `consumed` is recorded on the stream)
-int stage_acquire(BatchStage& st, size_t bytes, StageSlot** out) {
+// returns with st.mu HELD (released by ~Staged after `consumed` is recorded on the stream)
+int stage_take(BatchStage& st, size_t bytes, StageSlot** out) {
   st.mu.lock();
   StageSlot& sl = st.slot[st.cursor++ & 3u];
   if (sl.consumed && hipEventSynchronize(sl.consumed) != hipSuccess) {
