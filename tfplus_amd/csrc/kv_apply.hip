@@ -89,7 +89,7 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   for (int i = 0; i < num_tables; ++i) {
     for (const kv_handle_t* sl : {slots0, slots1}) {
       if (!sl) continue;
-      if (!sl[i]->initialized) return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: optimizer slot");
+      if ((rc = require_initialized(sl[i], "optimizer slot"))) return rc;
       if (sl[i]->dim != slot_mult * D || sl[i]->device != vars[0]->device || sl[i]->key_dtype != vars[0]->key_dtype)
         return fail(KV_INVALID_ARGUMENT, "var and slot do not have matching shapes (slot dim must be %d x var dim, same device / key dtype)", slot_mult);
       all.push_back(sl[i]);
@@ -420,13 +420,12 @@ int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const f
   if ((rc = check_table(v)) || (rc = check_table(s0)) || (two && (rc = check_table(s1)))) return rc;
   if (c.status && c.opt < 0) return c.status;
   if (group_adam(c.opt)) {   // order and wording of training_ops.cc:7001-7103
-    if (!v->initialized || !s0->initialized)
-      return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: %s", !v->initialized ? "var" : "m_v_linear");
+    if ((rc = require_initialized(v, "var")) || (rc = require_initialized(s0, "m_v_linear"))) return rc;
   } else if (!two) {
     if (!v->initialized || !s0->initialized)
       return fail(KV_FAILED_PRECONDITION, "Attempting to use uninitialized variables: %s", !v->initialized ? "var" : "accum");
-  } else if (!v->initialized || !s0->initialized || !s1->initialized) {
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables");
+  } else if ((rc = require_initialized(v, nullptr)) || (rc = require_initialized(s0, nullptr)) || (rc = require_initialized(s1, nullptr))) {
+    return rc;
   }
   if (c.status) return c.status;
   if (group_adam(c.opt)) {

@@ -9,6 +9,10 @@
 // launch_link_hints — and only kvhip.hip compiles the pipelines' kernels (kv_kernels.h, kv_fused.h, kv_papply.h), which the
 // other units reach through the launch_* functions.  The descriptors of a batched launch go to the device through
 // Staged<Desc> alone (the staging ring: acquire, fill, upload, busy until the stream has read them).
+//
+// What the entry points share: TableOp (device, lock and stream of a single-table op), require_initialized (the one
+// precondition message), with_lanes / with_id_type (a kernel's row-width and id-type template arguments from run-time
+// values), self_part_args (the PartArgs of an op on a table's own rows) and ensure_pos_ent (Workspace::pos_ent).
 #pragma once
 
 #include <algorithm>
@@ -20,6 +24,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/kvhip.h"
@@ -204,6 +209,43 @@ inline int check_table(kv_handle_t h) {
   return KV_OK;
 }
 
+// CheckInitializedInternal (kv_variable.h:242).  what: the words behind the colon (the optimizer ops name the table;
+// nullptr: none).  Each op calls it where the reference checks, between its own argument checks.
+inline int require_initialized(const kv_table* t, const char* what = "KvVariable init table not set") {
+  if (t->initialized) return KV_OK;
+  return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables%s%s", what ? ": " : "", what ? what : "");
+}
+
+// A single-table op from here to scope exit: the table's device current, its mutex held, s the op's stream.  Entering the
+// table stays the op's own call, because the ops differ in it: enter_op with its KEEP_* roles, hand_over, join_side, none.
+struct TableOp {
+  DeviceGuard dg;
+  std::lock_guard<std::mutex> lock;
+  hipStream_t s;
+  TableOp(kv_table* t, kv_stream_t stream) : dg(t->device), lock(t->mu), s((hipStream_t)stream) {}
+};
+
+// f(std::integral_constant<int, VQ>) for a row of `lanes` lanes (row_lanes: a power of two, 1 .. 64): the VQ template
+// argument of the row-copy kernels
+template <class F>
+auto with_lanes(int lanes, F&& f) {
+  switch (lanes) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    default: return f(std::integral_constant<int, 64>{});
+  }
+}
+// f(IdT{}) with the id type of a kernel: int or long long
+template <class F>
+auto with_id_type(bool int32_ids, F&& f) {
+  if (int32_ids) return f(int{});
+  return f((long long)0);
+}
+
 // ---- the entry-list pipeline (kv_fused.h) ----
 // ids per index pass: positions and epart rows are 30-bit fields of the entry list's words, a partition block takes
 // up to 65535 entries; 2^23 ids (4096 tiles) stay well inside both
@@ -233,6 +275,7 @@ bool stream_is_capturing(hipStream_t s);
 int ws_sync(hipStream_t s);
 int ensure_capacity(kv_table* t, long long extra, hipStream_t s);
 int ensure_workspace(kv_table* t, long long n, bool need_part, hipStream_t s);
+int ensure_pos_ent(kv_table* t, long long n, hipStream_t s);
 unsigned fused_default_P(long long n);
 size_t chunk_cap(long long n);
 
@@ -253,6 +296,15 @@ TableDev dev_view(const kv_table* t);
 struct SelfSegment { unsigned lo = 0, len = 0; const void* ids = nullptr; const float* grad = nullptr; };
 
 WsDev ws_view(kv_table* t, long long n, const SelfSegment* self = nullptr);
+
+// the PartArgs of an op of n ids on a table's own rows: its slot tables are the table itself
+inline PartArgs self_part_args(const kv_table* t, long long n) {
+  PartArgs pa{};
+  pa.tv = dev_view(t); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
+  pa.det = det_mode(t);
+  pa.n = n;
+  return pa;
+}
 
 // brackets one kernel launch with a pair of events when profiling is on
 struct ProfScope {

@@ -1,6 +1,11 @@
 // kv_ops.hip — the table ops of the C ABI on the table core (kv_host.h): the training and inference lookups,
 // kv_lookup_sparse, unique / dedup / segment sums, point queries, delete, export / import / delta, scatter.  Its own kernels
 // are kv_op_kernels.h's; the pipelines' kernels are reached through the core's launchers.
+//
+// An entry point reads as its checks — in the reference's order, which differs per op: where n == 0 returns and where
+// require_initialized stands is each op's own — then TableOp (device, lock, stream), how it enters the table, and what it
+// launches.  The bodies two ops share are in the unnamed namespace: tile_pass_notable and segment_sums (the distinct-id
+// ops), export_pass (the four export calls), read_figure (size / sum_freq / map size), scatter_like, delete_locked.
 #include <hip/hip_runtime.h>
 
 #include <iterator>
@@ -88,25 +93,22 @@ static int delta_after_export(kv_table* t, int first_n, unsigned nrows, hipStrea
 // tf.unique_with_counts on the entry-list kernels (any dim: no row is touched): a table-less tile pass (entries, every
 // position's entry) and k_papply PA_UNIQUE with dense numbers — uniq / uniq_counts written, every entry learns its id's
 // number, the count in wd.ctr[0].  The table's mutex is held by the caller.
-// the table-less tile pass of the distinct-id ops: entries, every position's entry number (pos_ent)
-static int unique_tile_pass(kv_table* t, WsDev& wd, PartArgs& pa, const void* ids, const int* counts, long long n, hipStream_t s) {
-  Workspace& ws = t->ws;
+// the table-less tile pass of the distinct-id ops: entries and, file_pos, every position's entry number (pos_ent)
+static int tile_pass_notable(kv_table* t, WsDev& wd, const PartArgs& pa, const void* ids, const int* counts, long long n,
+                             bool int32_ids, bool file_pos, hipStream_t s) {
   int rc;
-  if (ws.pos_cap < n) {
-    if ((rc = ws_sync(s))) return rc;   // (refused under a stream capture before anything is queued, like ensure_workspace)
-    ws.pos_cap = 0;
-    if ((rc = regrow(&ws.pos_ent, (size_t)std::max<long long>(n, ws.cap_n)))) return rc;
-    ws.pos_cap = std::max<long long>(n, ws.cap_n);
+  if (file_pos) {
+    if ((rc = ensure_pos_ent(t, n, s))) return rc;
+    wd.pos_ent = t->ws.pos_ent;
   }
   t->fused_index = true;
   choose_partitions(t, wd, n);
-  wd.pos_ent = ws.pos_ent;
-  launch_ltile_notable(t, pa.tv, wd, ids, n, s, counts, t->key_dtype == KV_DT_INT32);
+  launch_ltile_notable(t, pa.tv, wd, ids, n, s, counts, int32_ids);
   return KV_OK;
 }
 static int fused_unique_pass(kv_table* t, WsDev& wd, PartArgs& pa, const void* ids, const int* counts, long long n, hipStream_t s) {
   int rc;
-  if ((rc = unique_tile_pass(t, wd, pa, ids, counts, n, s))) return rc;
+  if ((rc = tile_pass_notable(t, wd, pa, ids, counts, n, t->key_dtype == KV_DT_INT32, true, s))) return rc;
   // (k_papply_uniq: numbering only, nothing of the row geometry is touched — one kernel whatever the table's dim)
   if ((rc = launch_papply_ud(wd, pa, PA_UNIQUE, s))) return fail(rc, "unique: no kernel");
   return KV_OK;
@@ -122,7 +124,29 @@ static int read_count(kv_table* t, const unsigned* dev, hipStream_t s, unsigned*
   return KV_OK;
 }
 
-// tf.unique + unsorted_segment_sum on the batch pipeline; the table's mutex is held by the caller.
+// The rows pa.grad of one id folded (pa.fold_op) into one output row, on the batch pipeline; the table's mutex is held by the
+// caller, which set the outputs in pa: out_keys + out_sum with dd_number (kv_dedup_segment_sum: the distinct ids numbered,
+// summed[number]) or out_sum with direct_rows (kv_unsorted_segment_sum: an id IS its output row).  Sums on a table of the
+// entry-list kernels' dims take those (t->fused_index says so afterwards): the table-less tile pass — file_pos: with every
+// position's entry, for an inverse — the tile sums of the ids repeated inside their tile (k_tsum), then ONE partition pass
+// (k_papply PA_DEDUP: the per-id sums over the tiles' entries; dd_number, which launch_papply_ud alone reads: it numbers
+// the ids it sums).  Everything else: the sorted positions (index_pass) and the segmented fold over them.
+static int segment_sums(kv_table* t, WsDev& wd, PartArgs& pa, const void* ids, long long n, bool int32_ids, bool file_pos,
+                        const char* what, hipStream_t s) {
+  int rc;
+  if (pa.fold_op != KV_SCATTER_ADD || !fused_tab(t)) {
+    index_pass<MODE_UNIQUE>(t, wd, pa, ids, nullptr, n, int32_ids ? 1 : 0, nullptr, s);
+    return launch_apply<MODE_DEDUP, OPT_ADAGRAD>(t, wd, pa, n, s);
+  }
+  if ((rc = tile_pass_notable(t, wd, pa, ids, nullptr, n, int32_ids, file_pos, s))) return rc;
+  pa.epart = wd.epart;
+  pa.day_lk = pa.day;
+  if ((rc = launch_tsum(pa.tv, wd, pa.grad, s))) return fail(rc, "tile sums: no kernel for dim %d", t->dim);
+  if ((rc = launch_papply_ud(wd, pa, PA_DEDUP, s))) return fail(rc, "%s: no kernel for dim %d", what, t->dim);
+  return KV_OK;
+}
+
+// tf.unique + unsorted_segment_sum; the table's mutex is held by the caller.
 // fold_op: how the rows of one id combine (KV_SCATTER_ADD = sum, MUL = product, MIN, MAX)
 static int dedup_locked(kv_table* t, const void* ids, const float* grad, int64_t n, int64_t* uniq,
                         float* summed, int32_t* inverse, int64_t* num_unique, int fold_op, hipStream_t s) {
@@ -130,32 +154,15 @@ static int dedup_locked(kv_table* t, const void* ids, const float* grad, int64_t
   if ((rc = ensure_workspace(t, n, true, s))) return rc;
   WsDev wd = ws_view(t, n);
   t->batch_serial = 0;
-  PartArgs pa{};
-  pa.tv = dev_view(t); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
+  PartArgs pa = self_part_args(t, n);
   pa.grad = grad;
   pa.out_keys = (long long*)uniq;
   pa.out_sum = summed;
   pa.fold_op = fold_op;
-  pa.det = det_mode(t);
-  pa.n = n;
-  if (fold_op == KV_SCATTER_ADD && fused_tab(t)) {
-    // the entry-list kernels: distinct ids numbered (fused_unique_pass), tile sums of the rows of ids repeated inside their
-    // tile (k_tsum), the per-id sums over the tiles' entries straight to summed[number] (k_papply PA_DEDUP)
-    // (round 6: ONE partition pass — k_papply PA_DEDUP numbers the ids it sums, dd_number — where PA_UNIQUE's numbering pass
-    //  ran in front of it: the table-less tile pass, the tile sums, the pass)
-    if ((rc = unique_tile_pass(t, wd, pa, ids, nullptr, n, s))) return rc;
-    pa.out_map = nullptr;
-    pa.dd_number = 1;
-    pa.epart = wd.epart;
-    pa.day_lk = pa.day;
-    if ((rc = launch_tsum(pa.tv, wd, grad, s))) return fail(rc, "tile sums: no kernel for dim %d", t->dim);
-    if ((rc = launch_papply_ud(wd, pa, PA_DEDUP, s))) return fail(rc, "per-id sums: no kernel for dim %d", t->dim);
-    if (inverse) k_inverse_e<<<nblocks(n, TB, 2048), TB, 0, s>>>(t->ws.pos_ent, wd.ent_b, n, inverse);
-  } else {
-    index_pass<MODE_UNIQUE>(t, wd, pa, ids, nullptr, n, -1, nullptr, s);
-    if ((rc = launch_apply<MODE_DEDUP, OPT_ADAGRAD>(t, wd, pa, n, s))) return rc;
-    if (inverse) k_dedup_inverse<<<nblocks(n, TB, 2048), TB, 0, s>>>(wd, n, inverse);
-  }
+  pa.dd_number = 1;
+  if ((rc = segment_sums(t, wd, pa, ids, n, t->key_dtype == KV_DT_INT32, true, "per-id sums", s))) return rc;
+  if (inverse && t->fused_index) k_inverse_e<<<nblocks(n, TB, 2048), TB, 0, s>>>(t->ws.pos_ent, wd.ent_b, n, inverse);
+  else if (inverse) k_dedup_inverse<<<nblocks(n, TB, 2048), TB, 0, s>>>(wd, n, inverse);
   unsigned U = 0;
   if ((rc = read_count(t, wd.ctr, s, &U))) return rc;
   *num_unique = U;
@@ -197,11 +204,10 @@ static int delete_locked(kv_table* t, const void* ids, int64_t n, int64_t* num_d
   t->batch_serial = 0;   // rows are released: an index of a batch that held them is void (its token goes stale)
   if ((rc = ensure_free_list(t, s))) return rc;
   HIP_TRY(hipMemsetAsync(t->d_stat, 0, 4 * sizeof(unsigned long long), s));
-  const TableDev td = dev_view(t);
-  if (t->key_dtype == KV_DT_INT32)
-    k_delete<int><<<nblocks(n, TB, 4096), TB, 0, s>>>(td, (const int*)ids, n, t->free_rows, t->d_stat);
-  else
-    k_delete<long long><<<nblocks(n, TB, 4096), TB, 0, s>>>(td, (const long long*)ids, n, t->free_rows, t->d_stat);
+  with_id_type(t->key_dtype == KV_DT_INT32, [&](auto id) {
+    using IDT = decltype(id);
+    k_delete<IDT><<<nblocks(n, TB, 4096), TB, 0, s>>>(dev_view(t), (const IDT*)ids, n, t->free_rows, t->d_stat);
+  });
   HIP_TRY(hipGetLastError());
   unsigned long long rel = 0;
   if ((rc = after_release(t, s, &rel))) return rc;
@@ -213,17 +219,14 @@ static int count_or_ts(kv_handle_t t, const void* ids, int64_t n, int what, uint
   int rc;
   if ((rc = check_table(t))) return rc;
   if (n < 0 || (n > 0 && (!ids || !out))) return fail(KV_INVALID_ARGUMENT, "indices / output pointer is null");
-  if (!t->initialized)
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
+  if ((rc = require_initialized(t))) return rc;
   if (n == 0) return KV_OK;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = join_side(t, s))) return rc;
-  if (t->key_dtype == KV_DT_INT32)
-    k_get_count_ts<int><<<nblocks(n, TB, 4096), TB, 0, s>>>(dev_view(t), (const int*)ids, n, what, today(t), out);
-  else
-    k_get_count_ts<long long><<<nblocks(n, TB, 4096), TB, 0, s>>>(dev_view(t), (const long long*)ids, n, what, today(t), out);
+  TableOp op(t, stream);
+  if ((rc = join_side(t, op.s))) return rc;
+  with_id_type(t->key_dtype == KV_DT_INT32, [&](auto id) {
+    using IDT = decltype(id);
+    k_get_count_ts<IDT><<<nblocks(n, TB, 4096), TB, 0, op.s>>>(dev_view(t), (const IDT*)ids, n, what, today(t), out);
+  });
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -234,8 +237,7 @@ static int scatter_like(kv_handle_t t, const void* ids, const float* vals, int64
   int rc;
   if (n == 0) return KV_OK;
   if (n < 0 || !ids || (!vals && mark < 0)) return fail(KV_INVALID_ARGUMENT, "bad arguments");
-  if (!t->initialized && !is_insert && mark < 0)
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
+  if (!is_insert && mark < 0 && (rc = require_initialized(t))) return rc;
   const long long CH = 1ll << 21;
   const size_t idsz = t->key_dtype == KV_DT_INT32 ? 4 : 8;
   for (long long off = 0; off < n; off += CH) {
@@ -243,14 +245,13 @@ static int scatter_like(kv_handle_t t, const void* ids, const float* vals, int64
     if ((rc = ensure_capacity(t, m, s))) return rc;
     if ((rc = ensure_workspace(t, m, false, s))) return rc;
     const WsDev wd = ws_view(t, m);
-    PartArgs pa{};
-    pa.tv = dev_view(t);
+    PartArgs pa = self_part_args(t, m);   // (neither k_part_keys<MODE_SCATTER> nor <MODE_MARK> reads det or n)
     if (!t->initialized) {
       // InsertOrUpdate / import never consult the init table; new rows start from the zero row
       pa.tv.init_table = t->chunks[0].rows;
       pa.tv.init_rows = 1;
+      pa.ts0 = pa.tv; pa.ts1 = pa.tv;
     }
-    pa.ts0 = pa.tv; pa.ts1 = pa.tv;
     pa.grad = vals ? vals + (size_t)off * t->dim : nullptr;
     pa.scatter_op = op; pa.is_insert = is_insert;
     pa.mark_what = mark; pa.fvals = fvals ? fvals + off : nullptr;
@@ -260,6 +261,35 @@ static int scatter_like(kv_handle_t t, const void* ids, const float* vals, int64
     else launch_part_keys<MODE_SCATTER>(wd, pa, s);
   }
   HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+// a figure of the table (kv_variable.h:139-175), which: 0 size(), 1 sum_freq(), 2 the map's rows (live keys, whatever
+// their frequency)
+static int read_figure(kv_handle_t t, int which, int64_t* out, kv_stream_t stream) {
+  int rc;
+  if ((rc = check_table(t))) return rc;
+  TableOp op(t, stream);
+  unsigned long long o[2];
+  unsigned nrows = 1;
+  if ((rc = stats(t, op.s, which < 2 ? o : nullptr, which < 2 ? nullptr : &nrows))) return rc;
+  *out = which < 2 ? (int64_t)o[which] : (int64_t)nrows - 1 - t->free_known;
+  return KV_OK;
+}
+
+// One export kernel (k_export, k_export_delta) over the table's rows: d_stat cleared, the launch — a fill with the buffers
+// it writes — and, c != nullptr, its three counters read back (synchronous).
+template <class Kernel>
+static int export_pass(kv_table* t, Kernel kernel, unsigned nrows, int first_n, unsigned long long* c, hipStream_t s,
+                       bool fill = false, int64_t* keys = nullptr, float* values = nullptr, int64_t* blacklist = nullptr,
+                       int64_t* fkeys = nullptr, uint32_t* fvals = nullptr) {
+  HIP_TRY(hipMemsetAsync(t->d_stat, 0, 4 * sizeof(unsigned long long), s));
+  kernel<<<nblocks(nrows, TB, 2048), TB, 0, s>>>(dev_view(t), nrows, first_n, fill ? 1 : 0, t->d_stat, (long long*)keys, values,
+                                                 (long long*)blacklist, (long long*)fkeys, fvals);
+  if (fill) HIP_TRY(hipGetLastError());
+  if (!c) return KV_OK;
+  HIP_TRY(hipMemcpyAsync(c, t->d_stat, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return KV_OK;
 }
 
@@ -295,8 +325,7 @@ int multi_common(int num_tables, const kv_handle_t* tables, const void* const* i
     if (ns[i] < 0 || ns[i] > (fused_tab(tables[0]) ? FUSED_MAX_N : (1ll << 21)))
       return fail(KV_INVALID_ARGUMENT, "indices: bad length %lld", (long long)ns[i]);
     if (ns[i] > 0 && !ids[i]) return fail(KV_INVALID_ARGUMENT, "indices pointer is null");
-    if (!tables[i]->initialized)
-      return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
+    if ((rc = require_initialized(tables[i]))) return rc;
     for (int j = 0; j < i; ++j)
       if (tables[j] == tables[i]) return fail(KV_INVALID_ARGUMENT, "batched op: table listed twice");
   }
@@ -312,11 +341,9 @@ int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* counts,
   if (n == 0) return KV_OK;  // kv_variable_ops.cc:530-532
   if (n < 0 || n > (1ll << 30)) return fail(KV_INVALID_ARGUMENT, "indices: bad length %lld", (long long)n);
   if (!ids || !out) return fail(KV_INVALID_ARGUMENT, "indices / output pointer is null");
-  if (!t->initialized)
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  if ((rc = require_initialized(t))) return rc;
+  TableOp tab(t, stream);
+  const hipStream_t s = tab.s;
   if ((rc = enter_op(t, s, KEEP_VAR))) return rc;   // a training lookup touches the var's rows and records, never a slot record or a mirror
   // any batch length: chunks of 2^21 ids are looked up one after another (same semantics as one
   // pass: the frequency adds saturate identically and rows are inserted by the first chunk)
@@ -331,14 +358,10 @@ int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* counts,
     float* op = out + (size_t)off * t->dim;
     if ((rc = ensure_capacity(t, m, s))) return rc;
     if ((rc = ensure_workspace(t, m, false, s))) return rc;
-    const TableDev td = dev_view(t);
     WsDev wd = ws_view(t, m, self);
     wd.seg_cap = seg_cap;
-    PartArgs pa{};
-    pa.tv = td; pa.ts0 = td; pa.ts1 = td;
+    PartArgs pa = self_part_args(t, m);
     pa.day = today(t);
-    pa.det = det_mode(t);
-    pa.n = m;
     const bool defer_part = token != nullptr && n <= CHK;   // a token is asked for: an apply of this batch follows
     if (fused_tab(t)) { if ((rc = fused_lookup_pass(t, wd, pa, idp, cp, m, pairs ? 2 : -1, op, s, defer_part))) return rc; }
     else index_pass<MODE_LOOKUP>(t, wd, pa, idp, cp, m, pairs ? 2 : -1, op, s, token != nullptr && n <= CHK);
@@ -384,10 +407,8 @@ int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const void* con
     d.w = ws_view(tables[i], std::max<long long>(ns[i], 1), selfs ? &selfs[i] : nullptr);
     if (seg_caps) d.w.seg_cap = seg_caps[i];
     if (fused_tab(tables[i])) use_partitions(d.w, fused_default_P(std::max<long long>(ns[i], 1)));
-    d.a.tv = dev_view(tables[i]); d.a.ts0 = d.a.tv; d.a.ts1 = d.a.tv;
+    d.a = self_part_args(tables[i], ns[i]);   // (det: multi_common refuses occurrence-order tables)
     d.a.day = today(tables[i]);
-    d.a.det = tables[i]->deterministic ? 1 : 0;
-    d.a.n = ns[i];
     d.ids = ids[i];
     d.counts = counts ? counts[i] : nullptr;
     d.out = outs[i];
@@ -430,45 +451,17 @@ int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const void* con
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
-int kv_size(kv_handle_t t, int64_t* out, kv_stream_t stream) {
-  int rc;
-  if ((rc = check_table(t))) return rc;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  unsigned long long o[2];
-  if ((rc = stats(t, (hipStream_t)stream, o, nullptr))) return rc;
-  *out = (int64_t)o[0];
-  return KV_OK;
-}
-int kv_sum_freq(kv_handle_t t, int64_t* out, kv_stream_t stream) {
-  int rc;
-  if ((rc = check_table(t))) return rc;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  unsigned long long o[2];
-  if ((rc = stats(t, (hipStream_t)stream, o, nullptr))) return rc;
-  *out = (int64_t)o[1];
-  return KV_OK;
-}
-int kv_map_size(kv_handle_t t, int64_t* out, kv_stream_t stream) {
-  int rc;
-  if ((rc = check_table(t))) return rc;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  unsigned nrows = 1;
-  if ((rc = stats(t, (hipStream_t)stream, nullptr, &nrows))) return rc;
-  *out = (int64_t)nrows - 1 - t->free_known;
-  return KV_OK;
-}
+int kv_size(kv_handle_t t, int64_t* out, kv_stream_t stream) { return read_figure(t, 0, out, stream); }
+int kv_sum_freq(kv_handle_t t, int64_t* out, kv_stream_t stream) { return read_figure(t, 1, out, stream); }
+int kv_map_size(kv_handle_t t, int64_t* out, kv_stream_t stream) { return read_figure(t, 2, out, stream); }
 
 int kv_get_meta(kv_handle_t t, const int64_t* ids, int64_t n, uint32_t* fw, uint8_t* fl, kv_stream_t stream) {
   int rc;
   if ((rc = check_table(t))) return rc;
   if (n <= 0) return KV_OK;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  if ((rc = join_side(t, (hipStream_t)stream))) return rc;
-  k_get_meta<long long><<<nblocks(n, TB), TB, 0, (hipStream_t)stream>>>(dev_view(t), (const long long*)ids, n, fw, fl);
+  TableOp op(t, stream);
+  if ((rc = join_side(t, op.s))) return rc;
+  k_get_meta<long long><<<nblocks(n, TB), TB, 0, op.s>>>(dev_view(t), (const long long*)ids, n, fw, fl);
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -503,11 +496,9 @@ int kv_lookup_sparse(kv_handle_t t, const void* ids, const void* segment_ids, in
   if (num_segments < 0 || num_segments > (1ll << 31) - 2) return fail(KV_INVALID_ARGUMENT, "bad num_segments");
   if (num_segments == 0) return KV_OK;
   if (!out || (n > 0 && (!ids || !segment_ids))) return fail(KV_INVALID_ARGUMENT, "ids / segment ids / output pointer is null");
-  if (!t->initialized)
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  if ((rc = require_initialized(t))) return rc;
+  TableOp op(t, stream);
+  const hipStream_t s = op.s;
   if ((rc = enter_op(t, s, KEEP_VAR))) return rc;   // the table's own rows and records only
   const int D = t->dim;
   if (n == 0) {  // every segment is empty
@@ -524,20 +515,13 @@ int kv_lookup_sparse(kv_handle_t t, const void* ids, const void* segment_ids, in
     if ((rc = regrow(&ws.seg_off, (size_t)(want + 1)))) return rc;
     ws.seg_cap = want;
   }
-  if (fused && ws.pos_cap < n) {   // every position's entry in its tile (k_ltile files it for the combiner)
-    if ((rc = ws_sync(s))) return rc;
-    ws.pos_cap = 0;
-    if ((rc = regrow(&ws.pos_ent, (size_t)std::max<long long>(n, ws.cap_n)))) return rc;
-    ws.pos_cap = std::max<long long>(n, ws.cap_n);
-  }
-  const TableDev td = dev_view(t);
+  // every position's entry in its tile (k_ltile files it for the combiner)
+  if (fused && (rc = ensure_pos_ent(t, n, s))) return rc;
   WsDev wd = ws_view(t, n);
-  PartArgs pa{};
-  pa.tv = td; pa.ts0 = td; pa.ts1 = td;
+  PartArgs pa = self_part_args(t, n);
+  const TableDev& td = pa.tv;
   pa.day = today(t);
   pa.count_once = count_occurrences ? 0 : 1;
-  pa.det = det_mode(t);
-  pa.n = n;
   t->batch_serial = 0;
   if (fused) {
     // the entry-list kernels: tile pass without rows (entries, every position's entry), the lookup's bookkeeping (which
@@ -553,35 +537,23 @@ int kv_lookup_sparse(kv_handle_t t, const void* ids, const void* segment_ids, in
     launch_part_keys<MODE_LOOKUP>(wd, pa, s);
   }
   ProfScope ps_gather(t, KV_PROF_LOOKUP_ORDER, s);
-  if (segment_dtype == KV_DT_INT32)
-    k_seg_offsets<int><<<nblocks(n + 1, TB, 2048), TB, 0, s>>>((const int*)segment_ids, n, num_segments, ws.seg_off);
-  else
-    k_seg_offsets<long long><<<nblocks(n + 1, TB, 2048), TB, 0, s>>>((const long long*)segment_ids, n, num_segments, ws.seg_off);
-  if (fused) {
-    const int ql = row_lanes(D);
-    const int grid = nblocks(num_segments * ql, TB, 8192);
-#define KV_SCE(VQ) k_seg_combine_e<VQ><<<grid, TB, 0, s>>>(td, ws.pos_ent, wd.ent_b, wd.ent_key, ws.seg_off, weights, num_segments, combiner, out)
-    switch (ql) {
-      case 1: KV_SCE(1); break;   case 2: KV_SCE(2); break;   case 4: KV_SCE(4); break;   case 8: KV_SCE(8); break;
-      case 16: KV_SCE(16); break; case 32: KV_SCE(32); break; default: KV_SCE(64); break;
-    }
-#undef KV_SCE
-    HIP_TRY(hipGetLastError());
-    return KV_OK;
-  }
+  with_id_type(segment_dtype == KV_DT_INT32, [&](auto id) {
+    using IDT = decltype(id);
+    k_seg_offsets<IDT><<<nblocks(n + 1, TB, 2048), TB, 0, s>>>((const IDT*)segment_ids, n, num_segments, ws.seg_off);
+  });
   const int q = (D % 4 == 0) ? D / 4 : 0;
-  const bool vec = q > 0 && (q & (q - 1)) == 0 && q <= 64;
-  const int grid = nblocks(num_segments * (vec ? q : 1), TB, 8192);
-  switch (vec ? q : 0) {
-    case 1: k_seg_combine<1><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out); break;
-    case 2: k_seg_combine<2><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out); break;
-    case 4: k_seg_combine<4><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out); break;
-    case 8: k_seg_combine<8><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out); break;
-    case 16: k_seg_combine<16><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out); break;
-    case 32: k_seg_combine<32><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out); break;
-    case 64: k_seg_combine<64><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out); break;
-    default: k_seg_combine<0><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out); break;
-  }
+  const bool vec = q > 0 && (q & (q - 1)) == 0 && q <= 64;   // the sorted-position combiner's rows: a power of two of float4, or <0>
+  const int grid = nblocks(num_segments * (fused ? row_lanes(D) : vec ? q : 1), TB, 8192);
+  if (fused)
+    with_lanes(row_lanes(D), [&](auto vq) {
+      k_seg_combine_e<decltype(vq)::value><<<grid, TB, 0, s>>>(td, ws.pos_ent, wd.ent_b, wd.ent_key, ws.seg_off, weights, num_segments, combiner, out);
+    });
+  else if (vec)
+    with_lanes(q, [&](auto vq) {
+      k_seg_combine<decltype(vq)::value><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out);
+    });
+  else
+    k_seg_combine<0><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out);
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -589,13 +561,11 @@ int kv_lookup_sparse(kv_handle_t t, const void* ids, const void* segment_ids, in
 int kv_gather_or_zeros(kv_handle_t t, const void* ids, int64_t n, float* out, kv_stream_t stream) {
   int rc;
   if ((rc = check_table(t))) return rc;
-  if (!t->initialized)   // FindOrZeros -> CheckInitializedInternal (kv_variable.h:242)
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
+  if ((rc = require_initialized(t))) return rc;   // FindOrZeros -> CheckInitializedInternal (kv_variable.h:242)
   if (n == 0) return KV_OK;
   if (n < 0 || !ids || !out) return fail(KV_INVALID_ARGUMENT, "indices / output pointer is null");
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  TableOp op(t, stream);
+  const hipStream_t s = op.s;
   // a read: behind the table's last op on whatever stream, no serial bump.  It reads rows and flags of THIS table: as a var
   // it leaves the mirrors alone.  (hand_over, not enter_op: unlike kv_batch_gather_or_zeros this op does not report the
   // deferred error of the table's last batch — the next op that does will)
@@ -604,22 +574,13 @@ int kv_gather_or_zeros(kv_handle_t t, const void* ids, int64_t n, float* out, kv
   const int q = t->dim / 4;
   const bool wave_shaped = (t->dim & 3) == 0 && q >= 1 && q <= 64 && (q & (q - 1)) == 0;
   const int gw = nblocks(n, TB, 8192);  // a 64-id step per wave at 1 M ids: residency hides the hops
-#define KV_GOZ(IDT, VQ) k_gather_or_zeros_w<IDT, VQ><<<gw, TB, 0, s>>>(td, (const IDT*)ids, out, n)
-#define KV_GOZ_ALL(IDT)                                                                        \
-  switch (q) {                                                                                 \
-    case 1: KV_GOZ(IDT, 1); break;   case 2: KV_GOZ(IDT, 2); break;   case 4: KV_GOZ(IDT, 4); break;    \
-    case 8: KV_GOZ(IDT, 8); break;   case 16: KV_GOZ(IDT, 16); break; case 32: KV_GOZ(IDT, 32); break;  \
-    default: KV_GOZ(IDT, 64); break;                                                           \
-  }
-  if (wave_shaped) {
-    if (t->key_dtype == KV_DT_INT32) { KV_GOZ_ALL(int) } else { KV_GOZ_ALL(long long) }
-  } else if (t->key_dtype == KV_DT_INT32) {
-    k_gather_or_zeros<int><<<nblocks(n, TB / 8, 8192), TB, 0, s>>>(td, (const int*)ids, out, n);
-  } else {
-    k_gather_or_zeros<long long><<<nblocks(n, TB / 8, 8192), TB, 0, s>>>(td, (const long long*)ids, out, n);
-  }
-#undef KV_GOZ_ALL
-#undef KV_GOZ
+  with_id_type(t->key_dtype == KV_DT_INT32, [&](auto id) {
+    using IDT = decltype(id);
+    if (wave_shaped)
+      with_lanes(q, [&](auto vq) { k_gather_or_zeros_w<IDT, decltype(vq)::value><<<gw, TB, 0, s>>>(td, (const IDT*)ids, out, n); });
+    else
+      k_gather_or_zeros<IDT><<<nblocks(n, TB / 8, 8192), TB, 0, s>>>(td, (const IDT*)ids, out, n);
+  });
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -631,8 +592,7 @@ int kv_batch_gather_or_zeros(int num_tables, const kv_handle_t* tables, const vo
   if (!ids || !ns || !outs) return fail(KV_INVALID_ARGUMENT, "null argument array");
   for (int i = 0; i < num_tables; ++i) {
     if (ns[i] < 0 || (ns[i] > 0 && (!ids[i] || !outs[i]))) return fail(KV_INVALID_ARGUMENT, "indices / output pointer is null");
-    if (!tables[i]->initialized)   // FindOrZeros -> CheckInitializedInternal (kv_variable.h:242)
-      return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
+    if ((rc = require_initialized(tables[i]))) return rc;   // FindOrZeros -> CheckInitializedInternal (kv_variable.h:242)
   }
   const int device = tables[0]->device;
   DeviceGuard dg(device);
@@ -685,11 +645,10 @@ int kv_dedup_segment_sum(kv_handle_t t, const void* ids, const float* grad, int6
   if (n > (fused_tab(t) ? FUSED_MAX_N : (1ll << 21)))
     return fail(KV_UNIMPLEMENTED, "%lld ids in one call (limit 2^%d)", (long long)n, fused_tab(t) ? 23 : 21);
   if (!dim_supported(t->dim)) return fail(KV_UNIMPLEMENTED, "embedding dim %d not supported", t->dim);
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
+  TableOp op(t, stream);
   // `t` lends its workspace: neither its rows nor any record is touched
-  if ((rc = enter_op(t, (hipStream_t)stream, KEEP_VAR | KEEP_SLOT))) return rc;
-  return dedup_locked(t, ids, grad, n, uniq, summed, inverse, num_unique, KV_SCATTER_ADD, (hipStream_t)stream);
+  if ((rc = enter_op(t, op.s, KEEP_VAR | KEEP_SLOT))) return rc;
+  return dedup_locked(t, ids, grad, n, uniq, summed, inverse, num_unique, KV_SCATTER_ADD, op.s);
 }
 
 int kv_unsorted_segment_sum(kv_handle_t t, const int32_t* segment_ids, const float* data, int64_t n,
@@ -703,9 +662,8 @@ int kv_unsorted_segment_sum(kv_handle_t t, const int32_t* segment_ids, const flo
     return fail(KV_UNIMPLEMENTED, "%lld rows in one call (limit 2^%d)", (long long)n, fused_tab(t) ? 23 : 21);
   if (!dim_supported(t->dim)) return fail(KV_UNIMPLEMENTED, "embedding dim %d not supported", t->dim);
   if (num_segments == 0) return KV_OK;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  TableOp op(t, stream);
+  const hipStream_t s = op.s;
   // `t` lends its workspace: neither its rows nor any record is touched
   if ((rc = enter_op(t, s, KEEP_VAR | KEEP_SLOT))) return rc;
   HIP_TRY(hipMemsetAsync(out, 0, (size_t)num_segments * t->dim * sizeof(float), s));  // segments nobody names
@@ -713,29 +671,12 @@ int kv_unsorted_segment_sum(kv_handle_t t, const int32_t* segment_ids, const flo
   if ((rc = ensure_workspace(t, n, true, s))) return rc;
   WsDev wd = ws_view(t, n);
   t->batch_serial = 0;
-  PartArgs pa{};
-  pa.tv = dev_view(t); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
+  PartArgs pa = self_part_args(t, n);
   pa.grad = data;
   pa.out_sum = out;
-  pa.direct_rows = num_segments;
+  pa.direct_rows = num_segments;   // no numbering: an id IS its output row
   pa.fold_op = KV_SCATTER_ADD;
-  pa.det = det_mode(t);
-  pa.n = n;
-  if (fused_tab(t)) {
-    // the entry-list kernels: the segment ids de-duplicated per tile (no numbering: an id IS its output row), the tile
-    // sums, the per-id sums over the tiles' entries straight to out[id]
-    t->fused_index = true;
-    choose_partitions(t, wd, n);
-    launch_ltile_notable(t, pa.tv, wd, segment_ids, n, s, nullptr, true);
-    pa.epart = wd.epart;
-    pa.day_lk = pa.day;
-    if ((rc = launch_tsum(pa.tv, wd, data, s))) return fail(rc, "tile sums: no kernel for dim %d", t->dim);
-    if ((rc = launch_papply_ud(wd, pa, PA_DEDUP, s))) return fail(rc, "segment sums: no kernel for dim %d", t->dim);
-    HIP_TRY(hipGetLastError());
-    return KV_OK;
-  }
-  index_pass<MODE_UNIQUE>(t, wd, pa, segment_ids, nullptr, n, 1, nullptr, s);
-  if ((rc = launch_apply<MODE_DEDUP, OPT_ADAGRAD>(t, wd, pa, n, s))) return rc;
+  if ((rc = segment_sums(t, wd, pa, segment_ids, n, true, false, "segment sums", s))) return rc;
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -752,20 +693,16 @@ int kv_unique(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, 
   }
   if (n < 0 || !ids || !uniq) return fail(KV_INVALID_ARGUMENT, "bad arguments");
   if (n > FUSED_MAX_N) return fail(KV_UNIMPLEMENTED, "%lld ids in one call (limit 2^23)", (long long)n);
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  TableOp op(t, stream);
+  const hipStream_t s = op.s;
   // `t` lends its workspace: neither its rows nor any record is touched
   if ((rc = enter_op(t, s, KEEP_VAR | KEEP_SLOT))) return rc;
   if ((rc = ensure_workspace(t, n, false, s))) return rc;
   WsDev wd = ws_view(t, n);
   t->batch_serial = 0;
-  PartArgs pa{};
-  pa.tv = dev_view(t); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
+  PartArgs pa = self_part_args(t, n);
   pa.out_keys = (long long*)uniq;
   pa.out_counts = uniq_counts;
-  pa.det = det_mode(t);
-  pa.n = n;
   // the entry-list kernels, whatever the table's dim (no row is touched)
   if ((rc = fused_unique_pass(t, wd, pa, ids, counts, n, s))) return rc;
   if (inverse) k_inverse_e<<<nblocks(n, TB, 2048), TB, 0, s>>>(t->ws.pos_ent, wd.ent_b, n, inverse);
@@ -773,8 +710,7 @@ int kv_unique(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, 
   HIP_TRY(hipGetLastError());
   if (num_unique) {   // synchronous form
     unsigned U = 0;
-    int rc2;
-    if ((rc2 = read_count(t, wd.ctr, s, &U))) return rc2;
+    if ((rc = read_count(t, wd.ctr, s, &U))) return rc;
     *num_unique = U;
   }
   return KV_OK;
@@ -785,13 +721,11 @@ int kv_delete(kv_handle_t t, const void* ids, int64_t n, int64_t* num_deleted, k
   if ((rc = check_table(t))) return rc;
   if (num_deleted) *num_deleted = 0;
   if (n < 0 || (n > 0 && !ids)) return fail(KV_INVALID_ARGUMENT, "indices pointer is null");
-  if (!t->initialized)
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
+  if ((rc = require_initialized(t))) return rc;
   if (n == 0) return KV_OK;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  if ((rc = record_deleted(t, ids, n, t->key_dtype == KV_DT_INT32, (hipStream_t)stream))) return rc;
-  return delete_locked(t, ids, n, num_deleted, (hipStream_t)stream);
+  TableOp op(t, stream);
+  if ((rc = record_deleted(t, ids, n, t->key_dtype == KV_DT_INT32, op.s))) return rc;
+  return delete_locked(t, ids, n, num_deleted, op.s);
 }
 
 int kv_delete_with_timestamp(kv_handle_t t, int threshold, int dry_run, int64_t* out_keys, int64_t* count,
@@ -799,11 +733,9 @@ int kv_delete_with_timestamp(kv_handle_t t, int threshold, int dry_run, int64_t*
   int rc;
   if ((rc = check_table(t))) return rc;
   if (!count || (!dry_run && !out_keys)) return fail(KV_INVALID_ARGUMENT, "count / delete_keys pointer is null");
-  if (!t->initialized)
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  if ((rc = require_initialized(t))) return rc;
+  TableOp op(t, stream);
+  const hipStream_t s = op.s;
   if (!dry_run) {   // out_keys was sized by a dry run: nothing may have touched the table (or its clock) since
     if (t->expire_serial != t->op_serial)
       return fail(KV_FAILED_PRECONDITION, "the table was used between the dry run and kv_delete_with_timestamp: the key "
@@ -866,17 +798,11 @@ int kv_take_rows(int device, const void* src, const int32_t* index, const int32_
 int kv_export_count(kv_handle_t t, int first_n, int64_t* counts, kv_stream_t stream) {
   int rc;
   if ((rc = check_table(t))) return rc;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  TableOp op(t, stream);
   unsigned nrows = 1;
-  if ((rc = stats(t, s, nullptr, &nrows))) return rc;
-  HIP_TRY(hipMemsetAsync(t->d_stat, 0, 4 * sizeof(unsigned long long), s));
-  k_export<<<nblocks(nrows, TB, 2048), TB, 0, s>>>(dev_view(t), nrows, first_n, 0, t->d_stat, nullptr,
-                                                   nullptr, nullptr, nullptr, nullptr);
+  if ((rc = stats(t, op.s, nullptr, &nrows))) return rc;
   unsigned long long c[3];
-  HIP_TRY(hipMemcpyAsync(c, t->d_stat, sizeof c, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  if ((rc = export_pass(t, k_export, nrows, first_n, c, op.s))) return rc;
   t->export_serial = t->op_serial;
   counts[0] = (int64_t)c[0]; counts[1] = (int64_t)c[1]; counts[2] = (int64_t)c[2];
   return KV_OK;
@@ -886,29 +812,22 @@ int kv_export_fill(kv_handle_t t, int first_n, int64_t* keys, float* values, int
                    int64_t* fkeys, uint32_t* fvals, kv_stream_t stream) {
   int rc;
   if ((rc = check_table(t))) return rc;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  TableOp op(t, stream);
   if (t->export_serial != t->op_serial)
     return fail(KV_FAILED_PRECONDITION, "the table was used between kv_export_count and kv_export_fill: the buffers sized "
                                         "from the counts may be too small; count again");
   ++t->op_serial;   // a fill ends the export (delta lists handed on): the next fill needs a new count
   unsigned nrows = 1;
-  if ((rc = stats(t, s, nullptr, &nrows))) return rc;
-  HIP_TRY(hipMemsetAsync(t->d_stat, 0, 4 * sizeof(unsigned long long), s));
-  k_export<<<nblocks(nrows, TB, 2048), TB, 0, s>>>(dev_view(t), nrows, first_n, 1, t->d_stat,
-                                                   (long long*)keys, values, (long long*)blacklist,
-                                                   (long long*)fkeys, fvals);
-  HIP_TRY(hipGetLastError());
-  if (first_n > 2 && (rc = delta_after_export(t, first_n, nrows, s))) return rc;  // dynamic_save.hpp:179-192
+  if ((rc = stats(t, op.s, nullptr, &nrows))) return rc;
+  if ((rc = export_pass(t, k_export, nrows, first_n, nullptr, op.s, true, keys, values, blacklist, fkeys, fvals))) return rc;
+  if (first_n > 2 && (rc = delta_after_export(t, first_n, nrows, op.s))) return rc;  // dynamic_save.hpp:179-192
   return KV_OK;
 }
 
 int kv_set_delta_tracking(kv_handle_t t, int support_delta_export, int support_prediction_delta_export) {
   int rc;
   if ((rc = check_table(t))) return rc;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
+  TableOp op(t, nullptr);
   if ((rc = settle_pending(t))) return rc;
   t->track_delta = support_delta_export != 0;
   t->track_pred = support_prediction_delta_export != 0;
@@ -919,21 +838,14 @@ int kv_export_delta_count(kv_handle_t t, int first_n, int64_t* counts, kv_stream
   int rc;
   if ((rc = check_table(t))) return rc;
   if (!counts) return fail(KV_INVALID_ARGUMENT, "counts pointer is null");
-  if (!t->initialized)
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  if ((rc = require_initialized(t))) return rc;
+  TableOp op(t, stream);
   unsigned nrows = 1;
-  if ((rc = stats(t, s, nullptr, &nrows))) return rc;
+  if ((rc = stats(t, op.s, nullptr, &nrows))) return rc;
   std::vector<long long> absent;
-  if ((rc = delta_prepare(t, first_n, s, &absent))) return rc;
-  HIP_TRY(hipMemsetAsync(t->d_stat, 0, 4 * sizeof(unsigned long long), s));
-  k_export_delta<<<nblocks(nrows, TB, 2048), TB, 0, s>>>(dev_view(t), nrows, first_n, 0, t->d_stat, nullptr,
-                                                         nullptr, nullptr, nullptr, nullptr);
+  if ((rc = delta_prepare(t, first_n, op.s, &absent))) return rc;
   unsigned long long c[3];
-  HIP_TRY(hipMemcpyAsync(c, t->d_stat, sizeof c, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  if ((rc = export_pass(t, k_export_delta, nrows, first_n, c, op.s))) return rc;
   counts[0] = (int64_t)c[0];
   counts[1] = first_n > 3 ? (int64_t)c[1] : 0;
   counts[2] = first_n > 4 ? (int64_t)(c[2] + absent.size()) : 0;
@@ -946,11 +858,9 @@ int kv_export_delta_fill(kv_handle_t t, int first_n, int64_t* keys, float* value
                          int64_t* fkeys, uint32_t* fvals, int64_t* delete_keys, kv_stream_t stream) {
   int rc;
   if ((rc = check_table(t))) return rc;
-  if (!t->initialized)
-    return fail(KV_FAILED_PRECONDITION, "Failed to use uninitialized variables: KvVariable init table not set");
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  if ((rc = require_initialized(t))) return rc;
+  TableOp op(t, stream);
+  const hipStream_t s = op.s;
   if (t->delta_serial != t->op_serial)
     return fail(KV_FAILED_PRECONDITION, "the table was used between kv_export_delta_count and kv_export_delta_fill: the "
                                         "buffers sized from the counts may be too small; count again");
@@ -959,15 +869,11 @@ int kv_export_delta_fill(kv_handle_t t, int first_n, int64_t* keys, float* value
   if ((rc = stats(t, s, nullptr, &nrows))) return rc;
   std::vector<long long> absent;
   if ((rc = delta_prepare(t, first_n, s, &absent))) return rc;
-  HIP_TRY(hipMemsetAsync(t->d_stat, 0, 4 * sizeof(unsigned long long), s));
   // prediction exports move the blacklisted keys to the delete list (dynamic_save.hpp:345-351)
-  k_export_delta<<<nblocks(nrows, TB, 2048), TB, 0, s>>>(dev_view(t), nrows, first_n, 1, t->d_stat, (long long*)keys,
-                                                         values, (long long*)(first_n > 3 ? blacklist : delete_keys),
-                                                         (long long*)fkeys, fvals);
-  HIP_TRY(hipGetLastError());
   unsigned long long c[3];
-  HIP_TRY(hipMemcpyAsync(c, t->d_stat, sizeof c, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  if ((rc = export_pass(t, k_export_delta, nrows, first_n, c, s, true, keys, values, first_n > 3 ? blacklist : delete_keys,
+                        fkeys, fvals)))
+    return rc;
   if (!absent.empty()) {  // keys without a row: deleted (:233-236), frequency 0 (kv_variable.h:950)
     if (!delete_keys) return fail(KV_INVALID_ARGUMENT, "delete_keys pointer is null");
     const size_t off = first_n > 3 ? 0 : (size_t)c[1];
@@ -984,10 +890,9 @@ int kv_export_delta_fill(kv_handle_t t, int first_n, int64_t* keys, float* value
 int kv_insert(kv_handle_t t, const void* ids, const float* values, int64_t n, kv_stream_t stream) {
   int rc;
   if ((rc = check_table(t))) return rc;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  if ((rc = enter_op(t, (hipStream_t)stream))) return rc;
-  return scatter_like(t, ids, values, n, KV_SCATTER_ASSIGN, 1, -1, nullptr, (hipStream_t)stream);
+  TableOp op(t, stream);
+  if ((rc = enter_op(t, op.s))) return rc;
+  return scatter_like(t, ids, values, n, KV_SCATTER_ASSIGN, 1, -1, nullptr, op.s);
 }
 
 int kv_scatter_update(kv_handle_t t, const void* ids, const float* updates, int64_t n, int op,
@@ -995,9 +900,8 @@ int kv_scatter_update(kv_handle_t t, const void* ids, const float* updates, int6
   int rc;
   if ((rc = check_table(t))) return rc;
   if (op < KV_SCATTER_ASSIGN || op > KV_SCATTER_MAX) return fail(KV_INVALID_ARGUMENT, "unsupported update operation %d", op);
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  TableOp tab(t, stream);
+  const hipStream_t s = tab.s;
   if ((rc = enter_op(t, s))) return rc;
   if (op != KV_SCATTER_ASSIGN && n > 1 && ids && updates && dim_supported(t->dim)) {
     // ScatterUpdate applies every occurrence of an id in turn (kv_variable.h:616-734): the update rows of a
@@ -1011,7 +915,7 @@ int kv_scatter_update(kv_handle_t t, const void* ids, const float* updates, int6
     Workspace& w = t->ws;
     const long long want = std::min<long long>(n, CHK);
     if (w.scat_cap < want) {
-      HIP_TRY(hipStreamSynchronize(s));
+      if ((rc = ws_sync(s))) return rc;
       const long long cap = std::max<long long>(want, std::min<long long>(w.scat_cap * 2, CHK));
       w.scat_cap = 0;
       if ((rc = regrow(&w.scat_keys, (size_t)cap)) || (rc = regrow(&w.scat_sum, (size_t)cap * t->dim))) return rc;
@@ -1039,9 +943,8 @@ int kv_import_delta(kv_handle_t t, const int64_t* keys, const float* values, int
                     const int64_t* delete_keys, int64_t n_delete, int first_n, kv_stream_t stream) {
   int rc;
   if ((rc = check_table(t))) return rc;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  TableOp op(t, stream);
+  const hipStream_t s = op.s;
   if (t->key_dtype == KV_DT_INT32) return fail(KV_UNIMPLEMENTED, "import with int32 keys");
   if ((rc = enter_op(t, s))) return rc;
   // Stage 1 (dynamic_restore.hpp:58-77): insert or overwrite, lift the blacklist, re-evaluate under_threshold
@@ -1069,9 +972,8 @@ int kv_import(kv_handle_t t, const int64_t* keys, const float* values, int64_t n
               kv_stream_t stream) {
   int rc;
   if ((rc = check_table(t))) return rc;
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  TableOp op(t, stream);
+  const hipStream_t s = op.s;
   if (t->key_dtype == KV_DT_INT32) return fail(KV_UNIMPLEMENTED, "import with int32 keys");
   if ((rc = enter_op(t, s))) return rc;
   // clear(): dynamic_restore.hpp:60-62

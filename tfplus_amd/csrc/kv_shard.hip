@@ -269,18 +269,6 @@ static SegBytes shard_bytes(const kv_shard* sh, bool whole) {
   return SegBytes{rec * 16, rec * sh->table->dim * (int64_t)sizeof(float)};
 }
 
-// a route table's pos_ent holds n positions
-static int route_ensure_pos(kv_table* rt, long long n, hipStream_t s) {
-  Workspace& ws = rt->ws;
-  if (ws.pos_cap >= n) return KV_OK;
-  int rc;
-  HIP_TRY(hipStreamSynchronize(s));
-  ws.pos_cap = 0;
-  if ((rc = regrow(&ws.pos_ent, (size_t)std::max<long long>(n, ws.cap_n)))) return rc;
-  ws.pos_cap = std::max<long long>(n, ws.cap_n);
-  return KV_OK;
-}
-
 // The arguments of a shard's route over n ids (d is zeroed) — the index on the entry-list kernels:
 // a table-less tile pass (k_ltile<NOTABLE>: entries, mrow, every position's entry number; d.w is ITS view) and k_papply in
 // PA_UNIQUE mode (the distinct ids numbered, uniq / ucnt written, every entry learns its id's number).  The finish then reads
@@ -293,12 +281,10 @@ static void route_desc(kv_shard* sh, long long n, MultiDesc& d) {
   d.w.zero_counts = sh->ucnt;
   d.w.pos_ent = rt->ws.pos_ent;
   PartArgs& pa = d.a;
-  pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
+  pa = self_part_args(rt, n);   // (det: the route table follows its table's mode and is never in occurrence order)
   pa.out_keys = sh->uniq;
   pa.out_counts = sh->ucnt;
   pa.sparse_unique = 1;   // unique numbers with gaps: no counter to serialise on
-  pa.det = sh->table->deterministic ? 1 : 0;
-  pa.n = n;
   pa.day_lk = pa.day;
   if (!pa.det) {   // the numbered ids go straight to their owners' segments (the deterministic mode keeps the ordered scatter)
     pa.route_world = sh->world; pa.route_rule = sh->rule; pa.route_C = sh->C;
@@ -314,12 +300,10 @@ static void presum_desc(kv_shard* sh, const float* grad, MultiDesc& d) {
   d.w = ws_view(rt, sh->n_last);
   if (rt->index_P) use_partitions(d.w, rt->index_P);
   PartArgs& pa = d.a;
-  pa.tv = dev_view(rt); pa.ts0 = pa.tv; pa.ts1 = pa.tv;
+  pa = self_part_args(rt, sh->n_last);
   pa.grad = grad;
   pa.out_sum = sh->send_rows;
   pa.out_map = sh->slot_of;
-  pa.det = rt->deterministic ? 1 : 0;
-  pa.n = sh->n_last;
   pa.epart = d.w.epart;
   pa.day_lk = pa.day;
 }
@@ -358,7 +342,7 @@ static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_strea
   sh->n_last = n;
   sh->route_token = 0;
   if (n == 0) return shard_void_route(sh, s);   // an empty batch: void headers
-  if ((rc = ensure_workspace(rt, n, true, s)) || (rc = route_ensure_pos(rt, n, s))) return rc;
+  if ((rc = ensure_workspace(rt, n, true, s)) || (rc = ensure_pos_ent(rt, n, s))) return rc;
   MultiDesc d{};
   route_desc(sh, n, d);
   launch_ltile_notable(rt, d.a.tv, d.w, ids, n, s);
@@ -513,7 +497,7 @@ static int multi_route_impl(const kv_shard_t* shards, const int* todo, int m, co
     rt->deterministic = false;
     sh->n_last = n[todo[j]];
     sh->route_token = 0;
-    if ((rc = ensure_workspace(rt, sh->n_last, true, s)) || (rc = route_ensure_pos(rt, sh->n_last, s))) return rc;
+    if ((rc = ensure_workspace(rt, sh->n_last, true, s)) || (rc = ensure_pos_ent(rt, sh->n_last, s))) return rc;
   }
   Staged<MultiDesc> hd(shards[todo[0]]->table->device, 1, m);
   if (hd.rc) return hd.rc;
@@ -564,12 +548,7 @@ static int multi_finish_impl(const kv_shard_t* shards, const int* todo, int m, f
   const FinishDesc* md;
   if ((rc = hd.upload(s, &md))) return rc;
   const dim3 grid((unsigned)nblocks(nmax, TB, 8192), (unsigned)m);
-#define KV_SFM(VQ) k_shard_finish_multi<VQ><<<grid, TB, 0, s>>>(md)
-  switch (row_lanes(shards[todo[0]]->table->dim)) {
-    case 1: KV_SFM(1); break;   case 2: KV_SFM(2); break;   case 4: KV_SFM(4); break;   case 8: KV_SFM(8); break;
-    case 16: KV_SFM(16); break; case 32: KV_SFM(32); break; default: KV_SFM(64); break;
-  }
-#undef KV_SFM
+  with_lanes(row_lanes(shards[todo[0]]->table->dim), [&](auto vq) { k_shard_finish_multi<decltype(vq)::value><<<grid, TB, 0, s>>>(md); });
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -1056,12 +1035,9 @@ int kv_shard_lookup_finish(kv_shard_t sh, float* out, kv_stream_t stream) {
   const FinishDesc d = finish_desc(sh, out);
   const int grid = nblocks(d.n, TB, 8192);
   hipStream_t st = (hipStream_t)stream;
-#define KV_SF(VQ) k_shard_finish<VQ><<<grid, TB, 0, st>>>(d.pos_ent, d.ent_u, d.slot_of, d.rows, d.out, d.n, d.dim, d.rows_self, d.self_lo, d.self_len)
-  switch (row_lanes(d.dim)) {
-    case 1: KV_SF(1); break;   case 2: KV_SF(2); break;   case 4: KV_SF(4); break;   case 8: KV_SF(8); break;
-    case 16: KV_SF(16); break; case 32: KV_SF(32); break; default: KV_SF(64); break;
-  }
-#undef KV_SF
+  with_lanes(row_lanes(d.dim), [&](auto vq) {
+    k_shard_finish<decltype(vq)::value><<<grid, TB, 0, st>>>(d.pos_ent, d.ent_u, d.slot_of, d.rows, d.out, d.n, d.dim, d.rows_self, d.self_lo, d.self_len);
+  });
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }

@@ -390,6 +390,20 @@ int ensure_workspace(kv_table* t, long long n, bool need_part, hipStream_t s) {
   return KV_OK;
 }
 
+// Workspace::pos_ent holds n positions (every position's entry number in its tile: the table-less tile pass of the
+// distinct-id ops and the sharded route, kv_lookup_sparse's combiner)
+int ensure_pos_ent(kv_table* t, long long n, hipStream_t s) {
+  Workspace& w = t->ws;
+  if (w.pos_cap >= n) return KV_OK;
+  int rc;
+  if ((rc = ws_sync(s))) return rc;
+  const long long cap = std::max<long long>(n, w.cap_n);
+  w.pos_cap = 0;
+  if ((rc = regrow(&w.pos_ent, (size_t)cap))) return rc;
+  w.pos_cap = cap;
+  return KV_OK;
+}
+
 WsDev ws_view(kv_table* t, long long n, const SelfSegment* self) {
   Workspace& w = t->ws;
   WsDev d;
@@ -517,35 +531,27 @@ void launch_ltile(kv_table* t, const TableDev& td, const WsDev& wd, const void* 
   const int grid = (int)wd.ntiles;
   const size_t sh = ltile_smem_bytes();
   const int det = det_mode(t);
-  const int q = row_lanes(td.dim);
-#define KV_LT2(IDT, VQ)                                                                                     \
-  do {                                                                                                      \
-    if (md && multi_rows) k_ltile_multi<IDT, VQ, true><<<dim3((unsigned)grid, (unsigned)ntab), TBT, sh, s>>>(md); \
-    else if (md) k_ltile_multi<IDT, 1, false><<<dim3((unsigned)grid, (unsigned)ntab), TBT, sh, s>>>(md);     \
-    else if (out) k_ltile<IDT, VQ, true><<<grid, TBT, sh, s>>>(td, wd, (const IDT*)ids, counts, n, det, out); \
-    else k_ltile<IDT, 1, false><<<grid, TBT, sh, s>>>(td, wd, (const IDT*)ids, counts, n, det, nullptr);     \
-  } while (0)
-#define KV_LT(IDT)                                                              \
-  do {                                                                          \
-    switch (q) {                                                                \
-      case 1: KV_LT2(IDT, 1); break;   case 2: KV_LT2(IDT, 2); break;           \
-      case 4: KV_LT2(IDT, 4); break;   case 8: KV_LT2(IDT, 8); break;           \
-      case 16: KV_LT2(IDT, 16); break; case 32: KV_LT2(IDT, 32); break;         \
-      default: KV_LT2(IDT, 64); break;                                          \
-    }                                                                           \
-  } while (0)
-  if (ids_kind == 2) KV_LT(IdCount);
-  else if (ids_kind == 1) KV_LT(int);
-  else KV_LT(long long);
-#undef KV_LT
-#undef KV_LT2
+  auto launch = [&](auto id) {
+    using IDT = decltype(id);
+    with_lanes(row_lanes(td.dim), [&](auto vq) {
+      constexpr int VQ = decltype(vq)::value;
+      if (md && multi_rows) k_ltile_multi<IDT, VQ, true><<<dim3((unsigned)grid, (unsigned)ntab), TBT, sh, s>>>(md);
+      else if (md) k_ltile_multi<IDT, 1, false><<<dim3((unsigned)grid, (unsigned)ntab), TBT, sh, s>>>(md);
+      else if (out) k_ltile<IDT, VQ, true><<<grid, TBT, sh, s>>>(td, wd, (const IDT*)ids, counts, n, det, out);
+      else k_ltile<IDT, 1, false><<<grid, TBT, sh, s>>>(td, wd, (const IDT*)ids, counts, n, det, nullptr);
+    });
+  };
+  if (ids_kind == 2) launch(IdCount{});
+  else if (ids_kind == 1) launch(int{});
+  else launch((long long)0);
 }
 // the table-less tile pass of the sharded route (int64 ids): entries, mrow, every position's entry number
 void launch_ltile_notable(kv_table* t, const TableDev& td, const WsDev& wd, const void* ids, long long n, hipStream_t s,
                           const int* counts, bool int32_ids) {
-  const int det = det_mode(t);
-  if (int32_ids) k_ltile<int, 1, false, true><<<(int)wd.ntiles, TBT, ltile_smem_bytes(), s>>>(td, wd, (const int*)ids, counts, n, det, nullptr);
-  else k_ltile<long long, 1, false, true><<<(int)wd.ntiles, TBT, ltile_smem_bytes(), s>>>(td, wd, (const long long*)ids, counts, n, det, nullptr);
+  with_id_type(int32_ids, [&](auto id) {
+    using IDT = decltype(id);
+    k_ltile<IDT, 1, false, true><<<(int)wd.ntiles, TBT, ltile_smem_bytes(), s>>>(td, wd, (const IDT*)ids, counts, n, det_mode(t), nullptr);
+  });
 }
 // ... of `ntab` sharded routes in one launch (wmax: the largest ntiles of the batch of tables)
 void launch_ltile_multi_notable(const WsDev& wmax, int ntab, const MultiDesc* md, hipStream_t s) {
@@ -1140,9 +1146,8 @@ int kv_prepare_capture(kv_handle_t t, int64_t max_new_ids, kv_stream_t stream) {
   int rc;
   if ((rc = check_table(t))) return rc;
   if (max_new_ids < 0) return fail(KV_INVALID_ARGUMENT, "max_new_ids < 0");
-  DeviceGuard dg(t->device);
-  std::lock_guard<std::mutex> l(t->mu);
-  hipStream_t s = (hipStream_t)stream;
+  TableOp op(t, stream);
+  hipStream_t s = op.s;
   if ((rc = enter_op(t, s))) return rc;
   mirror_ban(t, s);   // (a captured apply replays without host code: no slot mirrors for this table from here on)
   unsigned c[3];
