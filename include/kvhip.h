@@ -458,6 +458,52 @@ int kv_multi_apply_group_ftrl_v2_unique(int num_tables, const kv_handle_t* vars,
                                         const int64_t* ns, float lr, float l1, float l2, float l2_shrinkage,
                                         float lr_power, kv_stream_t stream);
 
+/* Group RectifiedAdam.  Replaces KvVariableGroupSparseApplyRectifiedAdamOp::Compute (kernels/training_ops.cc:6694-6978; op
+ * KvVariableGroupSparseApplyRectifiedAdam, ops/training_ops.cc:1194-1217).  `opt` is ONE slot table of dim 5 x the var's:
+ * [m | v | linear | vhat | vamsgrad].  Bookkeeping as kv_apply_group_adam version 3 (frequency filter on the var, slot row
+ * found or inserted, CoverUpdate / blacklist, delta lists).  Per id, with alpha = sqrt(1 - beta2_power) (:6883-6936):
+ *   m = beta1 m + (1 - beta1) g;  new_v = beta2 v + (1 - beta2) g^2;  use_nesterov: m = g (1 - beta1) + beta1 m (stored)
+ *   not tractable:  rm = m / (1 - beta1_power),        rv = 1 / lr
+ *   tractable:      rm = r_t m / (1 - beta1_power),    rv = (sqrt(amsgrad ? (vamsgrad = max(new_v, vamsgrad)) : new_v) / alpha
+ *                                                            + epsilon) / lr
+ *   linear += rm - (rv - vhat) var;  u = clamp(linear, -l1, l1) - linear;  norm = |u|_2
+ *   norm > l21 sqrt(dim): var = u (1 - l21 sqrt(dim) / norm) / (rv + 2 l2) (CoverUpdate), else the var is blacklisted
+ *   vhat = rv;  v = new_v (CoverUpdate of the slot row)
+ * r_t, tractable and the powers are the caller's (python: GroupRectifiedAdamOptimizer); tractable / amsgrad / use_nesterov
+ * are 0 or 1.  KV_INVALID_ARGUMENT for lr <= 0, l1 / l2 / l21 < 0 (:6742-6779) or an opt dim other than 5 x the var's (the
+ * reference's check, :6790-6805, also admits an opt dim equal to the var's and would read past the row: refused here);
+ * KV_FAILED_PRECONDITION for an uninitialised table (:6714-6721).  Dims, limits, graph capture, deterministic modes, fast
+ * math and delta tracking as kv_apply_group_adam.  _unique / _tok: the forms of kv_apply_group_adam_unique / _tok. */
+int kv_apply_group_rectified_adam(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                                  float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1,
+                                  float l2, float l21, float r_t, int tractable, int amsgrad, int use_nesterov,
+                                  kv_stream_t stream);
+int kv_apply_group_rectified_adam_tok(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                                      float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1,
+                                      float l2, float l21, float r_t, int tractable, int amsgrad, int use_nesterov,
+                                      kv_batch_token_t token, kv_stream_t stream);
+int kv_apply_group_rectified_adam_unique(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n,
+                                         float lr, float beta1_power, float beta2_power, float beta1, float beta2,
+                                         float epsilon, float l1, float l2, float l21, float r_t, int tractable, int amsgrad,
+                                         int use_nesterov, kv_stream_t stream);
+/* ... on many (var, opt) pairs of one dim (kernels/training_ops.cc:6694-6978 per pair), shaped like
+ * kv_multi_apply_group_adam[_tok|_unique]. */
+int kv_multi_apply_group_rectified_adam(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                        const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                        float beta1_power, float beta2_power, float beta1, float beta2, float epsilon,
+                                        float l1, float l2, float l21, float r_t, int tractable, int amsgrad,
+                                        int use_nesterov, kv_stream_t stream);
+int kv_multi_apply_group_rectified_adam_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                            const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                            float beta1_power, float beta2_power, float beta1, float beta2, float epsilon,
+                                            float l1, float l2, float l21, float r_t, int tractable, int amsgrad,
+                                            int use_nesterov, const kv_batch_token_t* tokens, kv_stream_t stream);
+int kv_multi_apply_group_rectified_adam_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                               const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                               float beta1_power, float beta2_power, float beta1, float beta2, float epsilon,
+                                               float l1, float l2, float l21, float r_t, int tractable, int amsgrad,
+                                               int use_nesterov, kv_stream_t stream);
+
 
 /* embedding_lookup_sparse on a KvVariable (python/ops/embedding_ops.py:279-441), fused: the
  * reference runs unique_with_counts -> GatherOrInsert[WithCounts] -> gather(idx) -> (x weights) ->
@@ -572,7 +618,9 @@ int kv_shard_lookup_finish(kv_shard_t shard, float* out, kv_stream_t stream);
 int kv_shard_apply_route(kv_shard_t shard, const float* grad, kv_stream_t stream);
 /* optimizer: 0 GroupAdam V4, 1 GroupAdam V3 (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21),
  * 2 Adagrad (hp = lr, update_slots), 3 SparseGroupFtrl (hp = lr, l1, l2, l21, l2_shrinkage, lr_power; slot1 = linear),
- * 4 FTRL-V2, 5 group FTRL-V2 (hp = lr, l1, l2, l2_shrinkage, lr_power; slot1 = linear) */
+ * 4 FTRL-V2, 5 group FTRL-V2 (hp = lr, l1, l2, l2_shrinkage, lr_power; slot1 = linear),
+ * 6 group RectifiedAdam (kernels/training_ops.cc:6694-6978; hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2,
+ * l21, r_t, tractable, amsgrad, use_nesterov — the three flags as 0 / 1; slot0 = opt, slot1 unused) */
 int kv_shard_apply_serve(kv_shard_t shard, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp,
                          kv_stream_t stream);
 int kv_shard_lookup(kv_shard_t shard, kv_comm_t comm, const void* ids, int64_t n, float* out, int join,

@@ -129,6 +129,12 @@ SIGNATURES = {
     "kv_multi_apply_group_ftrl_v2": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp]),
     "kv_multi_apply_group_ftrl_v2_unique": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp]),
     "kv_multi_apply_group_ftrl_v2_tok": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp, _vp]),
+    "kv_apply_group_rectified_adam": (_i32, [_vp, _vp, _vp, _vp, _i64] + [_f] * 10 + [_i32] * 3 + [_vp]),
+    "kv_apply_group_rectified_adam_unique": (_i32, [_vp, _vp, _vp, _vp, _i64] + [_f] * 10 + [_i32] * 3 + [_vp]),
+    "kv_apply_group_rectified_adam_tok": (_i32, [_vp, _vp, _vp, _vp, _i64] + [_f] * 10 + [_i32] * 3 + [_c.c_uint64, _vp]),
+    "kv_multi_apply_group_rectified_adam": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 10 + [_i32] * 3 + [_vp]),
+    "kv_multi_apply_group_rectified_adam_unique": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 10 + [_i32] * 3 + [_vp]),
+    "kv_multi_apply_group_rectified_adam_tok": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 10 + [_i32] * 3 + [_vp, _vp]),
     "kv_lookup_sparse": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "kv_unsorted_segment_sum": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "kv_take_rows": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),

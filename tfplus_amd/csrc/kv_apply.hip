@@ -1,6 +1,6 @@
 // kv_apply.hip — the optimizer layer of the C ABI on the table core (kv_host.h): one parser per optimizer family, the two
 // bodies (apply_one: one table; multi_apply: many tables, one launch per stage; the PartArgs of all their launches start
-// from opt_part_args), the 30 kv_apply_* / kv_multi_apply_* entry points and kv_attach_slot.  It compiles no kernel: the
+// from opt_part_args), the 36 kv_apply_* / kv_multi_apply_* entry points and kv_attach_slot.  It compiles no kernel: the
 // optimizers' kernels are reached through the typed launchers of kv_launch.h, the pipelines' through the core's.
 #include <hip/hip_runtime.h>
 
@@ -378,6 +378,24 @@ static OptCall ftrl_v2_call(int opt, float lr, float l1, float l2, float l2s, fl
   return c;
 }
 
+// Group RectifiedAdam (training_ops.cc:6714-6820; row math :6883-6936); slot row = m | v | linear | vhat | vamsgrad.
+// alpha = sqrt(1 - beta2_power) (:6884) and 1 - beta1_power (:6895) once, in fp32
+static OptCall group_radam_call(float lr, float b1p, float b2p, float b1, float b2, float eps, float l1, float l2, float l21,
+                                float r_t, int tractable, int amsgrad, int use_nesterov) {
+  OptCall c;
+  c.opt = OPT_GROUP_RADAM;
+  c.slot_mult = slot0_blocks(OPT_GROUP_RADAM);
+  if ((c.status = check_hp(lr, l1, l2, l21, 0.f, 0.f))) return c;
+  OptArgs& a = c.a;
+  a.lr = lr; a.b1p = b1p; a.b2p = b2p; a.b1 = b1; a.b2 = b2; a.eps = eps;
+  a.l1 = l1; a.l2 = l2; a.l21 = l21;
+  radam_r_t(a) = r_t;
+  radam_c1(a) = 1.f - b1p;
+  a.alpha = std::sqrt(1.f - b2p);
+  radam_flags(a) = (tractable ? RADAM_TRACTABLE : 0) | (amsgrad ? RADAM_AMSGRAD : 0) | (use_nesterov ? RADAM_NESTEROV : 0);
+  return c;
+}
+
 // the one place where a runtime OPT_* becomes the template argument of the pipelines
 template <class F>
 static int with_opt(int opt, F&& f) {
@@ -388,6 +406,7 @@ static int with_opt(int opt, F&& f) {
     case OPT_FTRL: return f(std::integral_constant<int, OPT_FTRL>());
     case OPT_FTRL_V2: return f(std::integral_constant<int, OPT_FTRL_V2>());
     case OPT_GROUP_FTRL_V2: return f(std::integral_constant<int, OPT_GROUP_FTRL_V2>());
+    case OPT_GROUP_RADAM: return f(std::integral_constant<int, OPT_GROUP_RADAM>());
     default: return fail(KV_INTERNAL, "optimizer %d", opt);
   }
 }
@@ -398,7 +417,9 @@ namespace __attribute__((visibility("hidden"))) kvhip_internal {
 // The sharded ops' `optimizer` code is the OPT_* value; their hp[] layout:
 // 0 GroupAdam V4, 1 GroupAdam V3 (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21),
 // 2 Adagrad (hp = lr, update_slots), 3 SparseGroupFtrl (hp = lr, l1, l2, l21, l2_shrinkage, lr_power; slot1 = linear),
-// 4 FTRL-V2 / 5 group FTRL-V2 (hp = lr, l1, l2, l2_shrinkage, lr_power; slot1 = linear)
+// 4 FTRL-V2 / 5 group FTRL-V2 (hp = lr, l1, l2, l2_shrinkage, lr_power; slot1 = linear),
+// 6 group RectifiedAdam (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad,
+// use_nesterov; the three flags as 0 / 1)
 OptCall shard_opt_call(int optimizer, const float* hp) {
   switch (optimizer) {
     case OPT_ADAM_V4: case OPT_ADAM_V3:
@@ -406,6 +427,9 @@ OptCall shard_opt_call(int optimizer, const float* hp) {
     case OPT_ADAGRAD: return adagrad_call(hp[0], hp[1] != 0.f);
     case OPT_FTRL: return sparse_group_ftrl_call(hp[0], hp[1], hp[2], hp[3], hp[4], hp[5]);
     case OPT_FTRL_V2: case OPT_GROUP_FTRL_V2: return ftrl_v2_call(optimizer, hp[0], hp[1], hp[2], hp[3], hp[4]);
+    case OPT_GROUP_RADAM:
+      return group_radam_call(hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8], hp[9], hp[10] != 0.f, hp[11] != 0.f,
+                              hp[12] != 0.f);
     default: return OptCall{};
   }
 }
@@ -419,8 +443,8 @@ int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const f
   const bool two = two_slots(c.opt);
   if ((rc = check_table(v)) || (rc = check_table(s0)) || (two && (rc = check_table(s1)))) return rc;
   if (c.status && c.opt < 0) return c.status;
-  if (group_adam(c.opt)) {   // order and wording of training_ops.cc:7001-7103
-    if ((rc = require_initialized(v, "var")) || (rc = require_initialized(s0, "m_v_linear"))) return rc;
+  if (wide_slot(c.opt)) {   // order and wording of training_ops.cc:7001-7103 (group RectifiedAdam: :6714-6721)
+    if ((rc = require_initialized(v, "var")) || (rc = require_initialized(s0, group_adam(c.opt) ? "m_v_linear" : "opt"))) return rc;
   } else if (!two) {
     if (!v->initialized || !s0->initialized)
       return fail(KV_FAILED_PRECONDITION, "Attempting to use uninitialized variables: %s", !v->initialized ? "var" : "accum");
@@ -428,11 +452,15 @@ int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const f
     return rc;
   }
   if (c.status) return c.status;
-  if (group_adam(c.opt)) {
+  if (wide_slot(c.opt)) {
+    // (group RectifiedAdam: the reference's check (:6790-6805) also lets an opt dim EQUAL to the var's through and would
+    // then read four blocks past the row; here only 5x passes)
     if (s0->dim != c.slot_mult * v->dim)
-      return fail(KV_INVALID_ARGUMENT, "kv_variable and linear do not have the same shape [%d] [%d] (m_v_linear must be 3x)", v->dim, s0->dim);
+      return group_adam(c.opt)
+                 ? fail(KV_INVALID_ARGUMENT, "kv_variable and linear do not have the same shape [%d] [%d] (m_v_linear must be 3x)", v->dim, s0->dim)
+                 : fail(KV_INVALID_ARGUMENT, "kv_variable and opt_shape do not have the same shape [%d] [%d] (opt must be 5x)", v->dim, s0->dim);
     if (v->device != s0->device) return fail(KV_INVALID_ARGUMENT, "var and slot live on different devices");
-    if (v == s0) return fail(KV_INVALID_ARGUMENT, "var and m_v_linear are the same table");
+    if (v == s0) return fail(KV_INVALID_ARGUMENT, "var and %s are the same table", group_adam(c.opt) ? "m_v_linear" : "opt");
   } else if (!two) {
     if (s0->dim != v->dim) return fail(KV_INVALID_ARGUMENT, "var and accum do not have the same shape [%d] [%d]", v->dim, s0->dim);
     if (v->device != s0->device || v == s0) return fail(KV_INVALID_ARGUMENT, "var and accum must be distinct tables on one device");
@@ -511,6 +539,49 @@ int kv_multi_apply_group_adam_unique(int num_tables, const kv_handle_t* vars, co
                                      int version, kv_stream_t stream) {
   return multi_apply(group_adam_call(version, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), num_tables, vars, slots, nullptr, grads,
                      ids, ns, nullptr, stream, true);
+}
+
+int kv_apply_group_rectified_adam(kv_handle_t v, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                                  float b1p, float b2p, float b1, float b2, float eps, float l1, float l2, float l21, float r_t,
+                                  int tractable, int amsgrad, int use_nesterov, kv_stream_t stream) {
+  return apply_one(group_radam_call(lr, b1p, b2p, b1, b2, eps, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov), v, opt, nullptr,
+                   grad, ids, n, 0, stream, false);
+}
+int kv_apply_group_rectified_adam_tok(kv_handle_t v, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                                      float b1p, float b2p, float b1, float b2, float eps, float l1, float l2, float l21,
+                                      float r_t, int tractable, int amsgrad, int use_nesterov, kv_batch_token_t token,
+                                      kv_stream_t stream) {
+  return apply_one(group_radam_call(lr, b1p, b2p, b1, b2, eps, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov), v, opt, nullptr,
+                   grad, ids, n, token, stream, false);
+}
+int kv_apply_group_rectified_adam_unique(kv_handle_t v, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                                         float b1p, float b2p, float b1, float b2, float eps, float l1, float l2, float l21,
+                                         float r_t, int tractable, int amsgrad, int use_nesterov, kv_stream_t stream) {
+  return apply_one(group_radam_call(lr, b1p, b2p, b1, b2, eps, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov), v, opt, nullptr,
+                   grad, ids, n, 0, stream, true);
+}
+int kv_multi_apply_group_rectified_adam(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                        const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float b1p,
+                                        float b2p, float b1, float b2, float eps, float l1, float l2, float l21, float r_t,
+                                        int tractable, int amsgrad, int use_nesterov, kv_stream_t stream) {
+  return multi_apply(group_radam_call(lr, b1p, b2p, b1, b2, eps, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov), num_tables,
+                     vars, opts, nullptr, grads, ids, ns, nullptr, stream, false);
+}
+int kv_multi_apply_group_rectified_adam_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                            const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                            float b1p, float b2p, float b1, float b2, float eps, float l1, float l2, float l21,
+                                            float r_t, int tractable, int amsgrad, int use_nesterov,
+                                            const kv_batch_token_t* tokens, kv_stream_t stream) {
+  return multi_apply(group_radam_call(lr, b1p, b2p, b1, b2, eps, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov), num_tables,
+                     vars, opts, nullptr, grads, ids, ns, tokens, stream, false);
+}
+int kv_multi_apply_group_rectified_adam_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                               const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                               float b1p, float b2p, float b1, float b2, float eps, float l1, float l2,
+                                               float l21, float r_t, int tractable, int amsgrad, int use_nesterov,
+                                               kv_stream_t stream) {
+  return multi_apply(group_radam_call(lr, b1p, b2p, b1, b2, eps, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov), num_tables,
+                     vars, opts, nullptr, grads, ids, ns, nullptr, stream, true);
 }
 
 int kv_apply_adagrad(kv_handle_t v, kv_handle_t acc, float lr, const float* grad, const void* ids, int64_t n, int update_slots,

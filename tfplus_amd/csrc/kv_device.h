@@ -417,26 +417,28 @@ __device__ __forceinline__ bool group_any(bool p) {
 // Restates the per-id body of KvVariableGroupSparseApplyAdamV4Op / V3Op / SparseApplyAdagradOp /
 // SparseGroupSparseApplyFtrlOp (training_ops.cc:7142-7197, 5871-5927, 1455-1486, 684-763).
 // State rows the caller already holds (requested together with the gradient rows, so the update needs no
-// second round trip): x = the var row; s[0..2] = the first slot table's row in blocks of dim floats
-// (GroupAdam m | v | z; Adagrad / FTRL accum in s[0]).  have_x / have_s say which of them are valid.
-template <int V, int K>
+// second round trip): x = the var row; s[0 .. slot0_blocks(OPT)) = the first slot table's row in blocks of dim floats
+// (GroupAdam m | v | z; group RectifiedAdam m | v | linear | vhat | vamsgrad; Adagrad / FTRL accum in s[0]).  have_x /
+// have_s say which of them are valid.  (s has opt_core's width, state_blocks(OPT): the lean paths hand it over as it is.)
+template <int OPT, int V, int K>
 struct PreRows {
-  float x[K][V], s[3][K][V];
+  float x[K][V], s[state_blocks(OPT)][K][V];
 };
 // The row math and the stores of one key's update, on values the caller already holds: xin = the var row;
-// sin[0..2] = GroupAdam m | v | z, Adagrad accum, FTRL accum | linear.  Element e of a row lives at lane
+// sin = GroupAdam m | v | z, group RectifiedAdam m | v | linear | vhat | vamsgrad, Adagrad accum, FTRL accum | linear.
+// Element e of a row lives at lane
 // (e / V) % LPR, step (e / V) / LPR.  All LPR lanes of every group of the wave call it (shuffles inside); `act`
 // masks groups without an update.  fvp / f0p / f1p = the flag bytes of the var / first / second slot row.
 // new1 = the second slot row was inserted now (its flags come from its values).
 // Restates the per-id body of KvVariableGroupSparseApplyAdamV4Op / V3Op / SparseApplyAdagradOp /
-// SparseGroupSparseApplyFtrlOp / SparseApplyFtrlOp / GroupSparseApplyFtrlOp (training_ops.cc:7142-7197, 5871-5927,
-// 1455-1486, 684-763, 457-484, 977-1019).
+// SparseGroupSparseApplyFtrlOp / SparseApplyFtrlOp / GroupSparseApplyFtrlOp / GroupSparseApplyRectifiedAdamOp
+// (training_ops.cc:7142-7197, 5871-5927, 1455-1486, 684-763, 457-484, 977-1019, 6883-6936).
 template <int OPT, int V, int LPR, int K>
 __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row, unsigned char* fvp, unsigned char* f0p,
                                          unsigned char* f1p, bool act, bool new0, int D, const float (&gv)[K][V],
-                                         const OptArgs& a, int lane, const float (&xin)[K][V], const float (&sin)[3][K][V],
-                                         bool new1 = false) {
-  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_GROUP_FTRL_V2, "opt_core: unknown optimizer");
+                                         const OptArgs& a, int lane, const float (&xin)[K][V],
+                                         const float (&sin)[state_blocks(OPT)][K][V], bool new1 = false) {
+  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_GROUP_RADAM, "opt_core: unknown optimizer");
   if (group_adam(OPT)) {
     // training_ops.cc:7166-7195 (V4) / :5895-5925 (V3); slot row = [m | v | z]
     float m[K][V], nv[K][V], sq[K][V], z[K][V], uu[K][V];
@@ -640,7 +642,7 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
       if (new1) *f1p = (unsigned char)((anyz ? 0u : FLAG_UNDER) | FLAG_DIRTY);
       else *f1p |= (unsigned char)FLAG_DIRTY;
     }
-  } else {
+  } else if (OPT == OPT_GROUP_FTRL_V2) {
     // OPT_GROUP_FTRL_V2: KvVariableGroupSparseApplyFtrlV2, training_ops.cc:977-1019 with has_l2_shrinkage; slot 0 = accum,
     // slot 1 = linear.  Group lasso with threshold l1 on the whole updated linear row
     float z[K][V];
@@ -705,6 +707,80 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
       *f0p = (unsigned char)(anya ? 0u : FLAG_UNDER);
       *f1p = (unsigned char)(anyz ? 0u : FLAG_UNDER);
     }
+  } else {
+    // OPT_GROUP_RADAM: KvVariableGroupSparseApplyRectifiedAdam, training_ops.cc:6883-6936; slot row =
+    // [m | v | linear | vhat | vamsgrad].  a.alpha = sqrt(1 - beta2_power), radam_c1(a) = 1 - beta1_power (host, fp32).
+    // m_corr is a copy of m's TensorMap (FlatVector, :195): the nesterov assignment writes m itself
+    constexpr int NB = slot0_blocks(OPT);
+    float m[K][V], nv[K][V], rv[K][V], z[K][V], uu[K][V], va[K][V];
+    float part = 0.f;
+    const float omb1 = 1.f - a.b1, omb2 = 1.f - a.b2;
+    const bool fm = KV_FASTM(a);
+    const bool tract = (radam_flags(a) & RADAM_TRACTABLE) != 0, ams = (radam_flags(a) & RADAM_AMSGRAD) != 0;
+    const bool nest = (radam_flags(a) & RADAM_NESTEROV) != 0;
+    const float inv_lr = kv_div(1.f, a.lr, fm);   // v.constant(1) / lr (:6896)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      const bool valid = act && e0 < D;
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        const float xo = valid ? xin[k][c] : 0.f, mo = valid ? sin[0][k][c] : 0.f, vo = valid ? sin[1][k][c] : 0.f;
+        const float zo = valid ? sin[2][k][c] : 0.f, vh = valid ? sin[3][k][c] : 0.f;
+        float vam = valid ? sin[4][k][c] : 0.f;
+        const float gg = gv[k][c];
+        float mn = a.b1 * mo + omb1 * gg;
+        const float vn = a.b2 * vo + omb2 * (gg * gg);
+        if (nest) mn = gg * omb1 + a.b1 * mn;
+        float rm, r;
+        if (!tract) {
+          rm = kv_div(mn, radam_c1(a), fm);
+          r = inv_lr;
+        } else {
+          if (ams) vam = fmaxf(vn, vam);
+          rm = kv_div(radam_r_t(a) * mn, radam_c1(a), fm);
+          r = kv_div(kv_div(kv_sqrt(ams ? vam : vn, fm), a.alpha, fm) + a.eps, a.lr, fm);
+        }
+        const float zn = zo + (rm - (r - vh) * xo);
+        const float adj = fmaxf(fminf(zn, a.l1), -a.l1);
+        const float uv = adj - zn;
+        m[k][c] = mn; nv[k][c] = vn; rv[k][c] = r; z[k][c] = zn; uu[k][c] = uv; va[k][c] = vam;
+        if (valid) part += uv * uv;
+      }
+    }
+    const float norm = kv_sqrt(group_sum<LPR>(part), fm);
+    const bool upd = norm > a.l21_norm;
+    const float scale = 1.f - kv_div(a.l21_norm, norm, fm);
+    const float two_l2 = 2.f * a.l2;
+    bool big = false, sbig = false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      if (act && e0 < D) {
+        float xn[V];
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+          xn[c] = 0.f;  // blacklist: the row reads as zeros (table_manager.h:335-357)
+          if (upd) xn[c] = kv_div(uu[k][c] * scale, rv[k][c] + two_l2, fm);
+          big |= fabsf(xn[c]) >= CUTOFF;
+          sbig |= fabsf(m[k][c]) >= CUTOFF || fabsf(nv[k][c]) >= CUTOFF || fabsf(z[k][c]) >= CUTOFF ||
+                  fabsf(rv[k][c]) >= CUTOFF || fabsf(va[k][c]) >= CUTOFF;
+        }
+        stv<V>(xrow + e0, xn);
+        stv<V>(s0row + e0, m[k]);
+        stv<V>(s0row + e0 + D, nv[k]);
+        stv<V>(s0row + e0 + 2 * D, z[k]);
+        stv<V>(s0row + e0 + 3 * D, rv[k]);
+        // vamsgrad is assigned in the amsgrad branch only (:6901); a row inserted now gets its init value written
+        if ((tract && ams) || new0) stv<V>(s0row + e0 + (NB - 1) * D, va[k]);
+      }
+    }
+    const bool anyx = group_any<LPR>(big), anys = group_any<LPR>(sbig);
+    if (act && lane == 0) {
+      // CoverUpdateUnsafe -> UpdateUnderThreshold, or MarkBlacklistUnsafe (:6923-6936)
+      *fvp = (unsigned char)(upd ? (anyx ? 0u : FLAG_UNDER) : (FLAG_BLACK | FLAG_UNDER));
+      *f0p = (unsigned char)(anys ? 0u : FLAG_UNDER);
+    }
   }
 }
 
@@ -715,7 +791,7 @@ __device__ __forceinline__ void opt_update_row(const TableDev& tv, const TableDe
                                                const TableDev& ts1, long long key, unsigned tag,
                                                unsigned r0, bool new0, unsigned r1, bool new1,
                                                bool live, const float (&gv)[K][V], const OptArgs& a,
-                                               int lane, const PreRows<V, K>* pre = nullptr, bool have_x = false,
+                                               int lane, const PreRows<OPT, V, K>* pre = nullptr, bool have_x = false,
                                                bool have_s = false) {
   const int D = tv.dim;
   const bool skip = !live || (tag & ROW_FILTERED) || (tag & ROW_MASK) == 0u;  // training_ops.cc:7150-7152
@@ -738,12 +814,18 @@ __device__ __forceinline__ void opt_update_row(const TableDev& tv, const TableDe
     ia1 = ts1.init_table + (size_t)((unsigned)h % ts1.init_rows) * ts1.dim;
     ib1 = ts1.init_table + (size_t)((unsigned)(h >> 32) % ts1.init_rows) * ts1.dim;
   }
-  float xin[K][V], sin[3][K][V];
+  constexpr int NS0 = slot0_blocks(OPT), NSB = state_blocks(OPT);
+  float xin[K][V], sin[NSB][K][V];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const int e0 = (lane + k * LPR) * V;
 #pragma unroll
-    for (int c = 0; c < V; ++c) xin[k][c] = sin[0][k][c] = sin[1][k][c] = sin[2][k][c] = 0.f;
+    for (int c = 0; c < V; ++c) {
+      // (blocks 0..2 in one statement, as they always were: the FTRL kernels' register allocation follows it — tools/kres.sh)
+      xin[k][c] = sin[0][k][c] = sin[1][k][c] = sin[2][k][c] = 0.f;
+#pragma unroll
+      for (int b3 = 3; b3 < NSB; ++b3) sin[b3][k][c] = 0.f;
+    }
     if (!(act && e0 < D)) continue;
     if (pre && have_x) {
 #pragma unroll
@@ -752,17 +834,20 @@ __device__ __forceinline__ void opt_update_row(const TableDev& tv, const TableDe
       ldv<V>(xrow + e0, xin[k]);
     }
     if (pre && have_s && !new0) {
-      constexpr int NS0 = slot0_blocks(OPT);
 #pragma unroll
       for (int b3 = 0; b3 < NS0; ++b3)
 #pragma unroll
         for (int c = 0; c < V; ++c) sin[b3][k][c] = pre->s[b3][k][c];
     } else {
+      // (blocks 0..2 as the statements they always were: one unrolled loop over all blocks gives the GroupAdam kernels
+      // another register allocation — tools/kres.sh)
       ldslot<V>(s0row, ia0, ib0, new0, e0, sin[0][k]);
-      if (group_adam(OPT)) {
+      if (NS0 > 1) {
         ldslot<V>(s0row, ia0, ib0, new0, e0 + D, sin[1][k]);
         ldslot<V>(s0row, ia0, ib0, new0, e0 + 2 * D, sin[2][k]);
       }
+#pragma unroll
+      for (int b3 = 3; b3 < NS0; ++b3) ldslot<V>(s0row, ia0, ib0, new0, e0 + b3 * D, sin[b3][k]);
     }
     if (two_slots(OPT)) ldslot<V>(s1row, ia1, ib1, new1, e0, sin[1][k]);
   }

@@ -1225,7 +1225,7 @@ __device__ __forceinline__ RowsOf resolve_rows(const PartArgs& a, long long key,
 // finish walks slot index -> slot record -> rows, three dependent hops.  Called by the LPR lanes of the key's group.
 template <int OPT, int V, int LPR, int K>
 __device__ __forceinline__ void prefetch_state(const PartArgs& a, const uint4& ra, bool live, int lane, int D, RowMeta& m0,
-                                               bool& hint_loaded, PreRows<V, K>& pre, bool& have_x, bool& have_s) {
+                                               bool& hint_loaded, PreRows<OPT, V, K>& pre, bool& have_x, bool& have_s) {
   hint_loaded = false; have_x = false; have_s = false;
   if (!live || (ra.z & ROW_MASK) == 0u) return;
   const bool hok = a.use_hints && ra.w != 0u && ra.w < a.ts0.max_rows;
@@ -1259,7 +1259,7 @@ __device__ __forceinline__ void prefetch_state(const PartArgs& a, const uint4& r
 template <int MODE, int OPT, int V, int LPR, int K>
 __device__ __forceinline__ void finish_key(const PartArgs& a, const uint4 hd, bool live, bool hint_loaded,
                                            const RowMeta& m0, float (&gv)[K][V], int lane,
-                                           const PreRows<V, K>* pre = nullptr, bool have_x = false, bool have_s = false) {
+                                           const PreRows<OPT, V, K>* pre = nullptr, bool have_x = false, bool have_s = false) {
   const int D = a.tv.dim;
   const long long key = (long long)(((unsigned long long)hd.y << 32) | hd.x);
   if (MODE == MODE_APPLY) {
@@ -1346,7 +1346,7 @@ __device__ __forceinline__ void apply_body(const WsDev& w, const PartArgs& a) {
     // the state of the key that gets finished here (prefetch_state): one set of registers for both kinds of item
     RowMeta m0{};
     bool hint_loaded = false, have_x = false, have_s = false;
-    PreRows<V, K> pre;
+    PreRows<OPT, V, K> pre;
     if (is_hot) {
       // ---- hot chunk: rows [lo, hi) of one key, G * RB of them per step ------------------------------------
       const unsigned hx = item.x & ~HEAD_BIT;
@@ -1569,7 +1569,7 @@ __device__ __forceinline__ void apply_fin_body(const WsDev& w, const PartArgs& a
     const uint4 ra = make_uint4(lkeys[q][3], lkeys[q][4], lkeys[q][5], lkeys[q][6]);
     RowMeta m0{};
     bool hl = false, hx = false, hs = false;
-    PreRows<V, K> pre;
+    PreRows<OPT, V, K> pre;
     if (MODE == MODE_APPLY) prefetch_state<OPT, V, LPR, K>(a, ra, g == 0, lane, D, m0, hl, pre, hx, hs);   // with the partials
     wave_sum(lkeys[q][1], 0u, lkeys[q][2], gv);
     finish_key<MODE, OPT, V, LPR, K>(a, ra, g == 0, hl, m0, gv, lane, &pre, hx, hs);
@@ -1585,7 +1585,7 @@ __device__ __forceinline__ void apply_fin_body(const WsDev& w, const PartArgs& a
     uint4 ra = make_uint4(0u, 0u, 0u, 0u);
     RowMeta m0{};
     bool hl = false, hx = false, hs = false;
-    PreRows<V, K> pre;
+    PreRows<OPT, V, K> pre;
     if (wv == 0) {
       ra = make_uint4(lkeys[q][3], lkeys[q][4], lkeys[q][5], lkeys[q][6]);
       if (MODE == MODE_APPLY) prefetch_state<OPT, V, LPR, K>(a, ra, g == 0, lane, D, m0, hl, pre, hx, hs);

@@ -412,7 +412,7 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
       uint2 vm = make_uint2(0u, 0u);
       uint4 mir = make_uint4(0u, 0u, 0u, 0u);   // {srow, freq, flags | state << 8 | epoch << 16, -}
       bool hint_loaded = false, have_x = false, have_s = false;
-      PreRows<V, K> pre;
+      PreRows<OPT, V, K> pre;
       const bool st_live = live && row != 0u;
       auto prefetch = [&]() {
         if (fast) {

@@ -766,7 +766,7 @@ static int shards_apply(bool single, const kv_shard_t* shards, int ntab, kv_comm
   done.assign(ntab, 0);
   for (const auto& grp : groups_of(ntab, [&](int k) {
          const kv_shard* sh = shards[k];
-         return optimizer >= 0 && optimizer <= 5 && shard_owner_batchable(sh) && sh->serve_token != 0 &&
+         return optimizer >= 0 && optimizer <= OPT_GROUP_RADAM && shard_owner_batchable(sh) && sh->serve_token != 0 &&
                         sh->serve_token == sh->table->batch_serial && sh->table->fused_index && slot0[k] != nullptr &&
                         (!two_slots(optimizer) || (slot1 && slot1[k]))
                     ? sh->table->dim : -1; })) {

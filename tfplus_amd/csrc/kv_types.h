@@ -11,7 +11,8 @@ namespace __attribute__((visibility("hidden"))) kvhip_internal {
 // index-pass modes (k_part_keys) and fold modes (k_apply_sorted)
 enum Mode { MODE_LOOKUP = 0, MODE_APPLY = 1, MODE_DEDUP = 2, MODE_SCATTER = 3, MODE_MARK = 4, MODE_UNIQUE = 5,
             MODE_APPLYIDX = 6 };
-enum Opt { OPT_ADAM_V4 = 0, OPT_ADAM_V3 = 1, OPT_ADAGRAD = 2, OPT_FTRL = 3, OPT_FTRL_V2 = 4, OPT_GROUP_FTRL_V2 = 5 };
+enum Opt { OPT_ADAM_V4 = 0, OPT_ADAM_V3 = 1, OPT_ADAGRAD = 2, OPT_FTRL = 3, OPT_FTRL_V2 = 4, OPT_GROUP_FTRL_V2 = 5,
+           OPT_GROUP_RADAM = 6 };
 // What the pipelines ask of an optimizer, in one place (a new OPT_* must answer each of them):
 // GroupAdam: one slot table of three dim-wide blocks (m | v | z)
 constexpr bool group_adam(int opt) { return opt == OPT_ADAM_V4 || opt == OPT_ADAM_V3; }
@@ -20,8 +21,14 @@ constexpr bool group_adam(int opt) { return opt == OPT_ADAM_V4 || opt == OPT_ADA
 constexpr bool two_slots(int opt) { return opt == OPT_FTRL || opt == OPT_FTRL_V2 || opt == OPT_GROUP_FTRL_V2; }
 // no CoverUpdate of the var: its flags are read (blacklist lifted by RemoveBlacklistUnsafe) and left to a later lookup
 constexpr bool keeps_var_flags(int opt) { return opt == OPT_ADAGRAD || opt == OPT_FTRL_V2; }
-// dim-wide blocks of the first slot row
-constexpr int slot0_blocks(int opt) { return group_adam(opt) ? 3 : 1; }
+// dim-wide blocks of the first slot row (group RectifiedAdam: m | v | linear | vhat | vamsgrad)
+constexpr int slot0_blocks(int opt) { return opt == OPT_GROUP_RADAM ? 5 : group_adam(opt) ? 3 : 1; }
+// one wide slot table whose dim is a multiple of the var's (what the ops' initialisation and shape checks ask)
+constexpr bool wide_slot(int opt) { return slot0_blocks(opt) > 1; }
+// dim-wide blocks of optimizer state a key's update holds besides the var row: the first slot row's (the FTRL family's
+// second slot table's row rides in block 1).  Three at the least: the existing optimizers' kernels keep the register
+// allocation they were tuned with
+constexpr int state_blocks(int opt) { return slot0_blocks(opt) > 3 ? slot0_blocks(opt) : 3; }
 
 struct __attribute__((aligned(16))) Entry {
   long long key;
@@ -141,10 +148,21 @@ struct WsDev {
 
 struct OptArgs {
   float lr, b1p, b2p, b1, b2, eps, l1, l2, l21, l2s, lr_power;
-  float alpha, l21_norm;  // host-precomputed in fp32 exactly as the reference does
+  float alpha, l21_norm;  // host-precomputed in fp32 exactly as the reference does (group RectifiedAdam: sqrt(1 - beta2_power))
   int update_slots;
   int fast;               // row math on the hardware's 1-ulp v_sqrt_f32 / v_rcp_f32 (kv_set_fast_math; 0: IEEE sequences)
 };
+
+// Group RectifiedAdam's own scalars ride in the fields its math has no use for.  OptArgs is part of every apply kernel's
+// argument block and the older optimizers' kernels are kept instruction for instruction (tools/kres.sh): the struct
+// stays as it is
+constexpr int RADAM_TRACTABLE = 1, RADAM_AMSGRAD = 2, RADAM_NESTEROV = 4;
+__host__ __device__ inline float& radam_r_t(OptArgs& a) { return a.l2s; }          // the rectification term r_t
+__host__ __device__ inline float radam_r_t(const OptArgs& a) { return a.l2s; }
+__host__ __device__ inline float& radam_c1(OptArgs& a) { return a.lr_power; }      // 1 - beta1_power
+__host__ __device__ inline float radam_c1(const OptArgs& a) { return a.lr_power; }
+__host__ __device__ inline int& radam_flags(OptArgs& a) { return a.update_slots; }  // RADAM_* bits
+__host__ __device__ inline int radam_flags(const OptArgs& a) { return a.update_slots; }
 
 // arguments of the index / partition pass and the optimizer apply (kv_kernels.h: partition pass)
 struct PartArgs {

@@ -152,7 +152,7 @@ __device__ __forceinline__ void uapply_body(const PartArgs& a, const void* __res
     uint2 vm = make_uint2(0u, 0u);
     uint4 mir = make_uint4(0u, 0u, 0u, 0u);   // {srow, freq, flags | state << 8 | epoch << 16, -}
     bool hint_loaded = false, have_x = false, have_s = false;
-    PreRows<V, K> pre;
+    PreRows<OPT, V, K> pre;
     if (fast) {
       const unsigned rr = st_live ? row : 0u;
       const unsigned hh = (st_live && hint < smax) ? hint : 0u;

@@ -300,6 +300,30 @@ def kv_variable_group_sparse_apply_ftrl_v2(var, accum, linear, grad, indices, lr
   _ftrl_v2("kv_apply_group_ftrl_v2", var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power, unique_indices)
 
 
+def _radam_scalars(lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov):
+  return ([_scalar(x) for x in (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t)],
+          [int(bool(x)) for x in (tractable, amsgrad, use_nesterov)])
+
+
+def kv_variable_group_sparse_apply_rectified_adam(var, opt, grad, indices, lr, beta1_power, beta2_power, beta1, beta2,
+                                                  epsilon, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov,
+                                                  use_locking=False, name=None, unique_indices=False, token=None):
+  """REGISTER_OP("KvVariableGroupSparseApplyRectifiedAdam") ops/training_ops.cc:1194-1217: `opt` is one slot table of
+  dim 5 x the var's, m | v | linear | vhat | vamsgrad (kvhip.h kv_apply_group_rectified_adam).  token: the batch token of
+  the lookup of the same ids (default: the one the var's last lookup of this very tensor left)."""
+  g, ids = _grad_ids(var, grad, indices)
+  fl, flags = _radam_scalars(lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad,
+                             use_nesterov)
+  lib = _lib.lib()
+  if unique_indices:
+    _lib.check(lib.kv_apply_group_rectified_adam_unique(var.ptr, opt.ptr, _p(g), _p(ids), ids.numel(), *fl, *flags,
+                                                        _stream(var)))
+    return
+  tok = _token_for(var, ids) if token is None else int(token)
+  _lib.check(lib.kv_apply_group_rectified_adam_tok(var.ptr, opt.ptr, _p(g), _p(ids), ids.numel(), *fl, *flags, tok,
+                                                   _stream(var)))
+
+
 def kv_dedup_segment_sum(table_handle, indices, grad):
   """tf.unique + tf.unsorted_segment_sum (TF-core _deduplicate_indexed_slices) on the GPU.
   Returns (unique_ids [U], summed [U, dim], inverse [n])."""
@@ -746,6 +770,27 @@ def kv_multi_group_sparse_apply_ftrl_v2(var_handles, accum_handles, linear_handl
                  l2_shrinkage, lr_power, unique_indices)
 
 
+def kv_multi_group_sparse_apply_rectified_adam(var_handles, opt_handles, grads, indices, lr, beta1_power, beta2_power, beta1,
+                                               beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov,
+                                               unique_indices=False):
+  """KvVariableGroupSparseApplyRectifiedAdam on many (var, opt) pairs with two kernel launches (one with unique_indices)."""
+  n = len(var_handles)
+  if n < 1 or not (n == len(opt_handles) == len(grads) == len(indices)):
+    raise _lib.InvalidArgumentError("vars, opts, grads and indices must be equally long, N >= 1")
+  ids, gr, ns, toks = _multi_prep(var_handles, grads, indices)
+  vp = (ctypes.c_void_p * n)(*[h.ptr for h in var_handles]); sp = (ctypes.c_void_p * n)(*[h.ptr for h in opt_handles])
+  fl, flags = _radam_scalars(lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad,
+                             use_nesterov)
+  sc = [ctypes.c_float(x) for x in fl]
+  lib = _lib.lib()
+  if unique_indices:
+    _lib.check(lib.kv_multi_apply_group_rectified_adam_unique(n, vp, sp, _ptr_array(gr), _ptr_array(ids), ns, *sc, *flags,
+                                                              _stream(var_handles[0])))
+    return
+  _lib.check(lib.kv_multi_apply_group_rectified_adam_tok(n, vp, sp, _ptr_array(gr), _ptr_array(ids), ns, *sc, *flags, toks,
+                                                         _stream(var_handles[0])))
+
+
 _COMBINERS = {"sum": _lib.KV_COMBINER_SUM, "mean": _lib.KV_COMBINER_MEAN, "sqrtn": _lib.KV_COMBINER_SQRTN}
 
 
@@ -844,6 +889,8 @@ def kv_unique(table_handle, indices, counts=None, sync=True):
 KV_OWNER_HASH, KV_OWNER_MOD = 0, 1
 OPT_GROUP_ADAM_V4, OPT_GROUP_ADAM_V3, OPT_ADAGRAD, OPT_SPARSE_GROUP_FTRL = 0, 1, 2, 3
 OPT_FTRL_V2, OPT_GROUP_FTRL_V2 = 4, 5   # hp = lr, l1, l2, l2_shrinkage, lr_power; slots = (accum, linear)
+# hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov (flags 0 / 1)
+OPT_GROUP_RADAM = 6
 
 
 class KvComm(object):

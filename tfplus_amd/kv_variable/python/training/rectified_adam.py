@@ -28,24 +28,28 @@ class RectifiedAdamOptimizer(Optimizer):
   def _get_beta_accumulators(self):
     return self._step, self._beta1_power, self._beta2_power
 
-  def _create_slots(self, var_list):
+  def _init_accumulators(self):
     if self._step is None:
       self._step, self._beta1_power, self._beta2_power = np.float32(1.0), np.float32(self._beta1), np.float32(self._beta2)
+
+  def _create_slots(self, var_list):
+    self._init_accumulators()
     for v in var_list:
       self._zeros_slot(v, "m", self._name + "/m")
       self._zeros_slot(v, "v", self._name + "/v")
       if self._amsgrad:
         self._zeros_slot(v, "vhat", self._name + "/vhat")
 
-  def _resource_apply_sparse(self, grad, var, indices):
+  def _step_scalars(self):
+    """The step's host scalars in float32 (the reference's rectified_adam.py:281-345): the warmed-up / decayed learning
+    rate, sma_inf, sma_t, tractable = sma_t >= sma_threshold and the rectification term r_t (0 while not tractable).
+    GroupRectifiedAdamOptimizer hands the same numbers to its fused op."""
     f = np.float32
-    D = var.embedding_dim
-    ids, g, _ = gen_kv_variable_ops.kv_dedup_segment_sum(var.handle, indices, grad.reshape(-1, D))
-    step, b1p, b2p = self._step, self._beta1_power, self._beta2_power
+    step, b2p = self._step, self._beta2_power
     lr_t = f(self._lr)
     if self._initial_decay > 0.0:
       lr_t = f(lr_t / (f(1.0) + f(self._initial_decay) * step))
-    b1, b2, eps = f(self._beta1), f(self._beta2), f(self._epsilon)
+    b2 = f(self._beta2)
     if self._total_steps > 0:
       total = f(self._total_steps)
       warm = f(total * f(self._warmup_proportion))
@@ -54,6 +58,20 @@ class RectifiedAdamOptimizer(Optimizer):
       lr_t = f(lr_t * (step / warm)) if step <= warm else f(lr_t + decay_rate * min(f(step - warm), decay_steps))
     sma_inf = f(f(2.0) / (f(1.0) - b2) - f(1.0))
     sma_t = f(sma_inf - f(2.0) * step * b2p / (f(1.0) - b2p))
+    tractable = bool(sma_t >= f(self._sma_threshold))
+    r_t = f(0.0)
+    if tractable:
+      with np.errstate(invalid="ignore"):
+        r_t = f(np.sqrt((sma_t - f(4)) / (sma_inf - f(4)) * (sma_t - f(2)) / (sma_inf - f(2)) * sma_inf / sma_t))
+    return lr_t, sma_inf, sma_t, tractable, r_t
+
+  def _resource_apply_sparse(self, grad, var, indices):
+    f = np.float32
+    D = var.embedding_dim
+    ids, g, _ = gen_kv_variable_ops.kv_dedup_segment_sum(var.handle, indices, grad.reshape(-1, D))
+    b1p, b2p = self._beta1_power, self._beta2_power
+    lr_t, _, _, tractable, r_t = self._step_scalars()
+    b1, b2, eps = f(self._beta1), f(self._beta2), f(self._epsilon)
     m_tab, v_tab = self.get_slot(var, "m"), self.get_slot(var, "v")
     m = float(b1) * gen_kv_variable_ops.kv_variable_gather_or_insert_v2(m_tab.handle, ids) + g * float(f(1) - b1)
     gen_kv_variable_ops.kv_variable_scatter_update_v2(m_tab.handle, ids, m)
@@ -69,9 +87,7 @@ class RectifiedAdamOptimizer(Optimizer):
       v_corr = torch.sqrt(vhat / float(f(1) - b2p))
     else:
       v_corr = torch.sqrt(v / float(f(1) - b2p))
-    if sma_t >= f(self._sma_threshold):
-      with np.errstate(invalid="ignore"):
-        r_t = f(np.sqrt((sma_t - f(4)) / (sma_inf - f(4)) * (sma_t - f(2)) / (sma_inf - f(2)) * sma_inf / sma_t))
+    if tractable:
       upd = float(r_t) * m_corr / (v_corr + float(eps))
     else:
       upd = m_corr
