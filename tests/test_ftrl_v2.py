@@ -97,20 +97,6 @@ def test_shim_gpu_registrations():
       assert 'HostMemory("grad")' not in r and 'HostMemory("indices")' not in r, r
 
 
-def _block(text, start, end):
-  a = text.index(start)
-  return text[a:text.index(end, a)]
-
-
-def test_shim_resource_class_is_the_one_of_the_main_shim():
-  """LookupResource finds the KvVariable resource by its type: the two translation units must define it identically."""
-  main = open(S.SHIM).read()
-  ours = open(SHIM).read()
-  for start, end in (("class StagingRing {", "\n};\n"), ("class KvHipResource : public ResourceBase {", "\n};\n"),
-                     ("static Status KeyTypeMatches(", "\n}\n")):
-    assert _block(ours, start, end) == _block(main, start, end), start
-
-
 def test_restatement_reproduces_A4(golden_dir):
   """test_training_ops.py:68-205's FTRL-V2 step, at tests/test_oracle_golden.py's bars for A4."""
   g = np.load(os.path.join(golden_dir, "A4_ftrl_v2.npz"))

@@ -97,20 +97,6 @@ def test_shim_gpu_registrations():
     assert 'HostMemory("grad")' not in r and 'HostMemory("indices")' not in r, r
 
 
-def _block(text, start, end):
-  a = text.index(start)
-  return text[a:text.index(end, a)]
-
-
-def test_shim_resource_class_is_the_one_of_the_main_shim():
-  """LookupResource finds the KvVariable resource by its type: the translation units must define it identically."""
-  main = open(S.SHIM).read()
-  ours = open(SHIM).read()
-  for start, end in (("class StagingRing {", "\n};\n"), ("class KvHipResource : public ResourceBase {", "\n};\n"),
-                     ("static Status KeyTypeMatches(", "\n}\n")):
-    assert _block(ours, start, end) == _block(main, start, end), start
-
-
 # ---- the restatement ---------------------------------------------------------------------------------------------------
 def _fresh(rng, U, D):
   return (rng.standard_normal((U, D)) * 0.3).astype(F), np.zeros((U, 5 * D), F), rng.normal(0, 0.1, (U, D)).astype(F)

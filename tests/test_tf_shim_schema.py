@@ -243,6 +243,48 @@ def test_shim_type_checks_against_a_mock_of_the_tf_api():
   assert r.returncode == 0, r.stderr[-3000:]
 
 
+SHIM_DIR = os.path.dirname(SHIM)
+UNITS = ["kv_variable_ops_hip.cc", "kv_ftrl_ops_hip.cc", "kv_radam_ops_hip.cc"]
+COMMON = "kv_shim_common.h"
+SHARED = ["class StagingRing", "class KvHipResource", "KeyTypeMatches(", "IndicesComeFromUnique(", "DeviceGradIds("]
+
+
+def test_shared_definitions_live_in_the_common_header_only():
+  """LookupResource finds the KvVariable resource by its type, so every translation unit of the plug-in must see the very
+  same class: it, and the helpers the optimizer kernels share, are defined once, in kv_shim_common.h, and each unit
+  includes that header."""
+  texts = {f: _strip_comments(open(os.path.join(SHIM_DIR, f)).read()) for f in sorted(os.listdir(SHIM_DIR))}
+  assert set(UNITS) | {COMMON} <= set(texts)
+  for what in SHARED:
+    if what.startswith("class "):
+      pat = r"^\s*%s\b[^;{]*\{" % what                            # a class definition (not a forward declaration)
+    else:
+      pat = r"^\s*(?:[\w:<>\*&]+\s+)+%s[^;{]*\{" % re.escape(what)    # a function definition (a call has no type in front)
+    where = [f for f, t in texts.items() for _ in re.finditer(pat, t, flags=re.M)]
+    assert where == [COMMON], (what, where)
+  for f in UNITS:
+    assert re.search(r'^#include "%s"' % re.escape(COMMON), texts[f], flags=re.M), f
+
+
+def test_shim_units_share_one_translation_unit_or_clash_only_on_registrations(tmp_path):
+  """The common header has include guards: the three units included into ONE translation unit meet its definitions once.
+  Against the mock that compiles; where it does not (the real REGISTER_OP statics may clash), no error is about a name
+  of the header.  Nothing needs this build — each unit compiles alone (the three mock checks)."""
+  import shutil
+  import subprocess
+  if shutil.which("g++") is None or not os.path.isdir("/opt/rocm/include/hip"):
+    pytest.skip("needs g++ and the HIP headers")
+  src = tmp_path / "all_units.cc"
+  src.write_text('#include "%s"\n' % COMMON + "".join('#include "%s"\n' % f for f in UNITS))
+  r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), "-I",
+                      os.path.join(ROOT, "tests", "tf_mock"), "-I", "/opt/rocm/include", "-D__HIP_PLATFORM_AMD__",
+                      "-I", SHIM_DIR, str(src)], capture_output=True, text=True, timeout=300)
+  names = "StagingRing|KvHipResource|KeyTypeMatches|IndicesComeFromUnique|DeviceGradIds|StageGradIds|ReleaseGradIds|GradIds|" \
+          "TfStream|FromKv|FromHip|Fingerprint|ApplyInputs|ApplyTables|ApplyOnDevice|ApplyStaged"
+  clashes = [l for l in r.stderr.splitlines() if re.search(r"error: .*\b(%s)\b" % names, l)]
+  assert r.returncode == 0 or (not clashes and "redefinition" in r.stderr), r.stderr[-3000:]
+
+
 def test_unique_producer_rule(tmp_path):
   """the shim takes the racy-unless-unique one-launch apply when `indices` is output 0 of a tf.unique
   node.  The rule (tfplus_amd/tf_shim/unique_input.h, plain strings) is compiled and run here: the exact leaf Unique /

@@ -48,15 +48,6 @@ SIGNATURES = {
     "kv_gather_or_insert": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "kv_gather_or_insert_tok": (_i32, [_vp, _vp, _vp, _i64, _vp, _c.POINTER(_c.c_uint64), _vp]),
     "kv_gather_or_zeros": (_i32, [_vp, _vp, _i64, _vp, _vp]),
-    "kv_apply_group_adam": (_i32, [_vp, _vp, _vp, _vp, _i64] + [_f] * 9 + [_i32, _vp]),
-    "kv_apply_adagrad": (_i32, [_vp, _vp, _f, _vp, _vp, _i64, _i32, _vp]),
-    "kv_apply_sparse_group_ftrl": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 6 + [_vp]),
-    "kv_apply_group_adam_unique": (_i32, [_vp, _vp, _vp, _vp, _i64] + [_f] * 9 + [_i32, _vp]),
-    "kv_apply_adagrad_unique": (_i32, [_vp, _vp, _f, _vp, _vp, _i64, _i32, _vp]),
-    "kv_apply_sparse_group_ftrl_unique": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 6 + [_vp]),
-    "kv_apply_group_adam_tok": (_i32, [_vp, _vp, _vp, _vp, _i64] + [_f] * 9 + [_i32, _c.c_uint64, _vp]),
-    "kv_apply_adagrad_tok": (_i32, [_vp, _vp, _f, _vp, _vp, _i64, _i32, _c.c_uint64, _vp]),
-    "kv_apply_sparse_group_ftrl_tok": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 6 + [_c.c_uint64, _vp]),
     "kv_attach_slot": (_i32, [_vp, _vp, _vp]),
     "kv_set_deterministic": (_i32, [_vp, _i32]),
     "kv_set_fast_math": (_i32, [_vp, _i32]),
@@ -107,34 +98,7 @@ SIGNATURES = {
     "kv_delete_with_timestamp": (_i32, [_vp, _i32, _i32, _vp, _c.POINTER(_i64), _vp]),
     "kv_batch_gather_or_zeros": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp]),
     "kv_multi_gather_or_insert": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "kv_multi_apply_group_adam": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 9 + [_i32, _vp]),
-    "kv_multi_apply_adagrad": (_i32, [_i32, _vp, _vp, _c.c_float, _vp, _vp, _vp, _i32, _vp]),
-    "kv_multi_apply_sparse_group_ftrl": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 6 + [_vp]),
     "kv_multi_gather_or_insert_tok": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "kv_multi_apply_group_adam_unique": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 9 + [_i32, _vp]),
-    "kv_multi_apply_adagrad_unique": (_i32, [_i32, _vp, _vp, _c.c_float, _vp, _vp, _vp, _i32, _vp]),
-    "kv_multi_apply_sparse_group_ftrl_unique": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 6 + [_vp]),
-    "kv_multi_apply_group_adam_tok": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 9 + [_i32, _vp, _vp]),
-    "kv_multi_apply_adagrad_tok": (_i32, [_i32, _vp, _vp, _c.c_float, _vp, _vp, _vp, _i32, _vp, _vp]),
-    "kv_multi_apply_sparse_group_ftrl_tok": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 6 + [_vp, _vp]),
-    "kv_apply_ftrl_v2": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 5 + [_vp]),
-    "kv_apply_ftrl_v2_unique": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 5 + [_vp]),
-    "kv_apply_ftrl_v2_tok": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 5 + [_c.c_uint64, _vp]),
-    "kv_apply_group_ftrl_v2": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 5 + [_vp]),
-    "kv_apply_group_ftrl_v2_unique": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 5 + [_vp]),
-    "kv_apply_group_ftrl_v2_tok": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64] + [_f] * 5 + [_c.c_uint64, _vp]),
-    "kv_multi_apply_ftrl_v2": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp]),
-    "kv_multi_apply_ftrl_v2_unique": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp]),
-    "kv_multi_apply_ftrl_v2_tok": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp, _vp]),
-    "kv_multi_apply_group_ftrl_v2": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp]),
-    "kv_multi_apply_group_ftrl_v2_unique": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp]),
-    "kv_multi_apply_group_ftrl_v2_tok": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 5 + [_vp, _vp]),
-    "kv_apply_group_rectified_adam": (_i32, [_vp, _vp, _vp, _vp, _i64] + [_f] * 10 + [_i32] * 3 + [_vp]),
-    "kv_apply_group_rectified_adam_unique": (_i32, [_vp, _vp, _vp, _vp, _i64] + [_f] * 10 + [_i32] * 3 + [_vp]),
-    "kv_apply_group_rectified_adam_tok": (_i32, [_vp, _vp, _vp, _vp, _i64] + [_f] * 10 + [_i32] * 3 + [_c.c_uint64, _vp]),
-    "kv_multi_apply_group_rectified_adam": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 10 + [_i32] * 3 + [_vp]),
-    "kv_multi_apply_group_rectified_adam_unique": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 10 + [_i32] * 3 + [_vp]),
-    "kv_multi_apply_group_rectified_adam_tok": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp] + [_c.c_float] * 10 + [_i32] * 3 + [_vp, _vp]),
     "kv_lookup_sparse": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "kv_unsorted_segment_sum": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "kv_take_rows": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
@@ -144,6 +108,27 @@ SIGNATURES = {
     "kv_profile_sample": (_i32, [_vp, _i32]),
     "kv_profile_read": (_i32, [_vp, _c.POINTER(_c.c_double), _c.POINTER(_i64), _i32]),
 }
+
+
+# One row per optimizer family: C stem -> (number of table handles, the arguments behind them in the C order).
+# g = grad, i = ids, n = the id count, f = a float scalar, b = an int scalar.  Every family has the entry points
+# kv_apply_<stem>[_unique|_tok] and kv_multi_apply_<stem>[_unique|_tok] (a table count in front; handles, grad, ids and
+# n become arrays); _tok takes the batch token (an array of them) in front of the stream.
+OPT_FAMILIES = {
+    "group_adam": (2, "gin" + "f" * 9 + "b"),                 # lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, version
+    "adagrad": (2, "fginb"),                                  # lr | update_slots
+    "sparse_group_ftrl": (3, "gin" + "f" * 6),                # lr, l1, l2, l21, l2_shrinkage, lr_power
+    "ftrl_v2": (3, "gin" + "f" * 5),                          # lr, l1, l2, l2_shrinkage, lr_power
+    "group_ftrl_v2": (3, "gin" + "f" * 5),
+    "group_rectified_adam": (2, "gin" + "f" * 10 + "bbb"),    # ... l21, r_t, tractable, amsgrad, use_nesterov
+}
+_ARG = {"g": _vp, "i": _vp, "f": _f, "b": _i32}
+for _stem, (_handles, _layout) in OPT_FAMILIES.items():
+  for _name, _lead, _n, _tok in (("kv_apply_" + _stem, [], _i64, _c.c_uint64), ("kv_multi_apply_" + _stem, [_i32], _vp, _vp)):
+    _args = _lead + [_vp] * _handles + [_n if c == "n" else _ARG[c] for c in _layout]
+    SIGNATURES[_name] = (_i32, _args + [_vp])
+    SIGNATURES[_name + "_unique"] = (_i32, _args + [_vp])
+    SIGNATURES[_name + "_tok"] = (_i32, _args + [_tok, _vp])
 
 
 class KvError(RuntimeError):

@@ -216,19 +216,29 @@ def _grad_ids(var, grad, indices):
   return g, ids
 
 
-def _group_adam(version, var, m_v_linear, grad, indices, lr, beta1_power, beta2_power, beat1, beta2,
-                epsilon, l1, l2, l21, use_locking, unique_indices=False):
+def _layout_args(stem, per, scalars):
+  """The arguments behind the table handles in the C order of the family's row (_lib.OPT_FAMILIES): `per` has grad, ids
+  and n; `scalars` are the family's float ("f") and int ("b") arguments in that order."""
+  sc = iter(scalars)
+  args = []
+  for c in _lib.OPT_FAMILIES[stem][1]:
+    if c in per:
+      args.append(per[c])
+    else:
+      args.append(_scalar(next(sc)) if c == "f" else int(next(sc)))
+  return args
+
+
+def _apply(stem, tables, grad, indices, scalars, unique_indices, token=None):
+  """One optimizer step on (var, slot tables...): kv_apply_<stem>_unique on the caller's promise that `indices` holds no id
+  twice (what TF-core's de-duplication guarantees in the reference's graph: kvhip.h), else kv_apply_<stem>_tok with the token
+  of the var's last lookup of this very tensor (or the caller's `token`)."""
+  var = tables[0]
   g, ids = _grad_ids(var, grad, indices)
-  if unique_indices:   # the caller's promise (what TF-core's de-duplication guarantees in the reference's graph): kvhip.h
-    _lib.check(_lib.lib().kv_apply_group_adam_unique(
-        var.ptr, m_v_linear.ptr, _p(g), _p(ids), ids.numel(), _scalar(lr), _scalar(beta1_power),
-        _scalar(beta2_power), _scalar(beat1), _scalar(beta2), _scalar(epsilon), _scalar(l1), _scalar(l2),
-        _scalar(l21), version, _stream(var)))
-    return
-  _lib.check(_lib.lib().kv_apply_group_adam_tok(
-      var.ptr, m_v_linear.ptr, _p(g), _p(ids), ids.numel(), _scalar(lr), _scalar(beta1_power),
-      _scalar(beta2_power), _scalar(beat1), _scalar(beta2), _scalar(epsilon), _scalar(l1), _scalar(l2),
-      _scalar(l21), version, _token_for(var, ids), _stream(var)))
+  args = [t.ptr for t in tables] + _layout_args(stem, {"g": _p(g), "i": _p(ids), "n": ids.numel()}, scalars)
+  if not unique_indices:
+    args.append(_token_for(var, ids) if token is None else int(token))
+  _lib.check(getattr(_lib.lib(), "kv_apply_%s_%s" % (stem, "unique" if unique_indices else "tok"))(*args, _stream(var)))
 
 
 def kv_variable_group_sparse_apply_adam_v4(var, m_v_linear, grad, indices, lr, beta1_power,
@@ -236,73 +246,43 @@ def kv_variable_group_sparse_apply_adam_v4(var, m_v_linear, grad, indices, lr, b
                                            use_locking=False, name=None, unique_indices=False):
   """REGISTER_OP("KvVariableGroupSparseApplyAdamV4") ops/training_ops.cc:1266-1285.
   unique_indices: the caller's promise that `indices` holds no id twice (kv_apply_group_adam_unique)."""
-  _group_adam(4, var, m_v_linear, grad, indices, lr, beta1_power, beta2_power, beat1, beta2, epsilon,
-              l1, l2, l21, use_locking, unique_indices)
+  _apply("group_adam", (var, m_v_linear), grad, indices,
+         (lr, beta1_power, beta2_power, beat1, beta2, epsilon, l1, l2, l21, 4), unique_indices)
 
 
 def kv_variable_group_sparse_apply_adam_v3(var, m_v_linear, grad, indices, lr, beta1_power,
                                            beta2_power, beat1, beta2, epsilon, l1, l2, l21,
                                            use_locking=False, name=None, unique_indices=False):
   """REGISTER_OP("KvVariableGroupSparseApplyAdamV3") ops/training_ops.cc:1086-1105."""
-  _group_adam(3, var, m_v_linear, grad, indices, lr, beta1_power, beta2_power, beat1, beta2, epsilon,
-              l1, l2, l21, use_locking, unique_indices)
+  _apply("group_adam", (var, m_v_linear), grad, indices,
+         (lr, beta1_power, beta2_power, beat1, beta2, epsilon, l1, l2, l21, 3), unique_indices)
 
 
 def kv_variable_sparse_apply_adagrad(var, accum, lr, grad, indices, use_locking=False,
                                      update_slots=True, name=None, unique_indices=False):
   """REGISTER_OP("KvVariableSparseApplyAdagrad") ops/training_ops.cc:214-226."""
-  g, ids = _grad_ids(var, grad, indices)
-  if unique_indices:
-    _lib.check(_lib.lib().kv_apply_adagrad_unique(var.ptr, accum.ptr, _scalar(lr), _p(g), _p(ids), ids.numel(),
-                                                  int(bool(update_slots)), _stream(var)))
-    return
-  _lib.check(_lib.lib().kv_apply_adagrad_tok(var.ptr, accum.ptr, _scalar(lr), _p(g), _p(ids), ids.numel(),
-                                             int(bool(update_slots)), _token_for(var, ids), _stream(var)))
+  _apply("adagrad", (var, accum), grad, indices, (lr, bool(update_slots)), unique_indices)
 
 
 def kv_variable_sparse_group_sparse_apply_ftrl_v2(var, accum, linear, grad, indices, lr, l1, l2, l21,
                                                   l2_shrinkage, lr_power, use_locking=False,
                                                   name=None, unique_indices=False):
   """REGISTER_OP("KvVariableSparseGroupSparseApplyFtrlV2") ops/training_ops.cc:135-150."""
-  g, ids = _grad_ids(var, grad, indices)
-  if unique_indices:
-    _lib.check(_lib.lib().kv_apply_sparse_group_ftrl_unique(
-        var.ptr, accum.ptr, linear.ptr, _p(g), _p(ids), ids.numel(), _scalar(lr), _scalar(l1),
-        _scalar(l2), _scalar(l21), _scalar(l2_shrinkage), _scalar(lr_power), _stream(var)))
-    return
-  _lib.check(_lib.lib().kv_apply_sparse_group_ftrl_tok(
-      var.ptr, accum.ptr, linear.ptr, _p(g), _p(ids), ids.numel(), _scalar(lr), _scalar(l1),
-      _scalar(l2), _scalar(l21), _scalar(l2_shrinkage), _scalar(lr_power), _token_for(var, ids), _stream(var)))
-
-
-def _ftrl_v2(fn, var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power, unique_indices):
-  g, ids = _grad_ids(var, grad, indices)
-  sc = (_scalar(lr), _scalar(l1), _scalar(l2), _scalar(l2_shrinkage), _scalar(lr_power))
-  lib = _lib.lib()
-  if unique_indices:
-    _lib.check(getattr(lib, fn + "_unique")(var.ptr, accum.ptr, linear.ptr, _p(g), _p(ids), ids.numel(), *sc, _stream(var)))
-    return
-  _lib.check(getattr(lib, fn + "_tok")(var.ptr, accum.ptr, linear.ptr, _p(g), _p(ids), ids.numel(), *sc,
-                                       _token_for(var, ids), _stream(var)))
+  _apply("sparse_group_ftrl", (var, accum, linear), grad, indices, (lr, l1, l2, l21, l2_shrinkage, lr_power), unique_indices)
 
 
 def kv_variable_sparse_apply_ftrl_v2(var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power,
                                      use_locking=False, name=None, unique_indices=False):
   """REGISTER_OP("KvVariableSparseApplyFtrlV2") ops/training_ops.cc:103-117: per-coordinate FTRL-Proximal
   (kvhip.h kv_apply_ftrl_v2)."""
-  _ftrl_v2("kv_apply_ftrl_v2", var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power, unique_indices)
+  _apply("ftrl_v2", (var, accum, linear), grad, indices, (lr, l1, l2, l2_shrinkage, lr_power), unique_indices)
 
 
 def kv_variable_group_sparse_apply_ftrl_v2(var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power,
                                            use_locking=False, name=None, unique_indices=False):
   """REGISTER_OP("KvVariableGroupSparseApplyFtrlV2") ops/training_ops.cc:119-133: FTRL with a group-lasso threshold l1
   on the whole linear row (kvhip.h kv_apply_group_ftrl_v2)."""
-  _ftrl_v2("kv_apply_group_ftrl_v2", var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power, unique_indices)
-
-
-def _radam_scalars(lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov):
-  return ([_scalar(x) for x in (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t)],
-          [int(bool(x)) for x in (tractable, amsgrad, use_nesterov)])
+  _apply("group_ftrl_v2", (var, accum, linear), grad, indices, (lr, l1, l2, l2_shrinkage, lr_power), unique_indices)
 
 
 def kv_variable_group_sparse_apply_rectified_adam(var, opt, grad, indices, lr, beta1_power, beta2_power, beta1, beta2,
@@ -311,17 +291,9 @@ def kv_variable_group_sparse_apply_rectified_adam(var, opt, grad, indices, lr, b
   """REGISTER_OP("KvVariableGroupSparseApplyRectifiedAdam") ops/training_ops.cc:1194-1217: `opt` is one slot table of
   dim 5 x the var's, m | v | linear | vhat | vamsgrad (kvhip.h kv_apply_group_rectified_adam).  token: the batch token of
   the lookup of the same ids (default: the one the var's last lookup of this very tensor left)."""
-  g, ids = _grad_ids(var, grad, indices)
-  fl, flags = _radam_scalars(lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad,
-                             use_nesterov)
-  lib = _lib.lib()
-  if unique_indices:
-    _lib.check(lib.kv_apply_group_rectified_adam_unique(var.ptr, opt.ptr, _p(g), _p(ids), ids.numel(), *fl, *flags,
-                                                        _stream(var)))
-    return
-  tok = _token_for(var, ids) if token is None else int(token)
-  _lib.check(lib.kv_apply_group_rectified_adam_tok(var.ptr, opt.ptr, _p(g), _p(ids), ids.numel(), *fl, *flags, tok,
-                                                   _stream(var)))
+  _apply("group_rectified_adam", (var, opt), grad, indices,
+         (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, bool(tractable), bool(amsgrad),
+          bool(use_nesterov)), unique_indices, token)
 
 
 def kv_dedup_segment_sum(table_handle, indices, grad):
@@ -673,122 +645,69 @@ def _multi_tokens(var_handles, indices):
   return [b.reshape(-1) for b in base], toks
 
 
+def _multi_apply(stem, words, tables, grads, indices, scalars, unique_indices):
+  """_apply on many table sets with the batched entry points: `tables` = (var handles, the handles of each slot role...),
+  `words` names the lists in the error message.  The tokens are those of a batched lookup over the very same tensors."""
+  var_handles = tables[0]
+  n = len(var_handles)
+  if n < 1 or not all(len(x) == n for x in tables[1:] + (grads, indices)):
+    raise _lib.InvalidArgumentError("%s must be equally long, N >= 1" % words)
+  ids, toks = _multi_tokens(var_handles, indices)
+  gr = [_f32(h, g).reshape(-1, h.dim) for h, g in zip(var_handles, grads)]
+  for g, i in zip(gr, ids):
+    if g.shape[0] != i.numel():
+      raise _lib.InvalidArgumentError("grad must be the same size as indices in the first dimension.")
+  args = [n] + [(ctypes.c_void_p * n)(*[h.ptr for h in hs]) for hs in tables]
+  args += _layout_args(stem, {"g": _ptr_array(gr), "i": _ptr_array(ids), "n": (ctypes.c_int64 * n)(*[i.numel() for i in ids])},
+                       scalars)
+  if not unique_indices:
+    args.append(toks)
+  _lib.check(getattr(_lib.lib(), "kv_multi_apply_%s_%s" % (stem, "unique" if unique_indices else "tok"))(
+      *args, _stream(var_handles[0])))
+
+
 def kv_multi_group_sparse_apply_adam(var_handles, m_v_linear_handles, grads, indices, lr, beta1_power, beta2_power,
                                      beat1, beta2, epsilon, l1, l2, l21, version=4, unique_indices=False):
   """KvVariableGroupSparseApplyAdamV4 (V3) on many (var, m_v_linear) pairs with two kernel launches (one with
   unique_indices: the caller's promise that no table's indices hold an id twice, kvhip.h kv_multi_apply_*_unique)."""
-  n = len(var_handles)
-  if n < 1 or not (n == len(m_v_linear_handles) == len(grads) == len(indices)):
-    raise _lib.InvalidArgumentError("vars, slots, grads and indices must be equally long, N >= 1")
-  ids, toks = _multi_tokens(var_handles, indices)
-  gr = [_f32(h, g).reshape(-1, h.dim) for h, g in zip(var_handles, grads)]
-  for g, i in zip(gr, ids):
-    if g.shape[0] != i.numel():
-      raise _lib.InvalidArgumentError("grad must be the same size as indices in the first dimension.")
-  vp = (ctypes.c_void_p * n)(*[h.ptr for h in var_handles])
-  sp = (ctypes.c_void_p * n)(*[h.ptr for h in m_v_linear_handles])
-  ns = (ctypes.c_int64 * n)(*[i.numel() for i in ids])
-  sc = [ctypes.c_float(_scalar(x)) for x in (lr, beta1_power, beta2_power, beat1, beta2, epsilon, l1, l2, l21)]
-  if unique_indices:
-    _lib.check(_lib.lib().kv_multi_apply_group_adam_unique(n, vp, sp, _ptr_array(gr), _ptr_array(ids), ns, *sc, int(version),
-                                                           _stream(var_handles[0])))
-    return
-  _lib.check(_lib.lib().kv_multi_apply_group_adam_tok(n, vp, sp, _ptr_array(gr), _ptr_array(ids), ns, *sc, int(version),
-                                                      toks, _stream(var_handles[0])))
-
-
-def _multi_prep(var_handles, grads, indices):
-  ids, toks = _multi_tokens(var_handles, indices)
-  gr = [_f32(h, g).reshape(-1, h.dim) for h, g in zip(var_handles, grads)]
-  for g, i in zip(gr, ids):
-    if g.shape[0] != i.numel():
-      raise _lib.InvalidArgumentError("grad must be the same size as indices in the first dimension.")
-  n = len(var_handles)
-  return ids, gr, (ctypes.c_int64 * n)(*[i.numel() for i in ids]), toks
+  _multi_apply("group_adam", "vars, slots, grads and indices", (var_handles, m_v_linear_handles), grads, indices,
+               (lr, beta1_power, beta2_power, beat1, beta2, epsilon, l1, l2, l21, version), unique_indices)
 
 
 def kv_multi_sparse_apply_adagrad(var_handles, accum_handles, lr, grads, indices, update_slots=True, unique_indices=False):
   """KvVariableSparseApplyAdagrad on many (var, accum) pairs with two kernel launches."""
-  n = len(var_handles)
-  if n < 1 or not (n == len(accum_handles) == len(grads) == len(indices)):
-    raise _lib.InvalidArgumentError("vars, accums, grads and indices must be equally long, N >= 1")
-  ids, gr, ns, toks = _multi_prep(var_handles, grads, indices)
-  vp = (ctypes.c_void_p * n)(*[h.ptr for h in var_handles]); ap = (ctypes.c_void_p * n)(*[h.ptr for h in accum_handles])
-  if unique_indices:
-    _lib.check(_lib.lib().kv_multi_apply_adagrad_unique(n, vp, ap, ctypes.c_float(_scalar(lr)), _ptr_array(gr), _ptr_array(ids), ns,
-                                                        int(bool(update_slots)), _stream(var_handles[0])))
-    return
-  _lib.check(_lib.lib().kv_multi_apply_adagrad_tok(n, vp, ap, ctypes.c_float(_scalar(lr)), _ptr_array(gr), _ptr_array(ids), ns,
-                                                   int(bool(update_slots)), toks, _stream(var_handles[0])))
+  _multi_apply("adagrad", "vars, accums, grads and indices", (var_handles, accum_handles), grads, indices,
+               (lr, bool(update_slots)), unique_indices)
 
 
 def kv_multi_sparse_group_sparse_apply_ftrl(var_handles, accum_handles, linear_handles, grads, indices, lr, l1, l2, l21,
                                             l2_shrinkage, lr_power, unique_indices=False):
   """KvVariableSparseGroupSparseApplyFtrlV2 on many (var, accum, linear) triples with two launches."""
-  n = len(var_handles)
-  if n < 1 or not (n == len(accum_handles) == len(linear_handles) == len(grads) == len(indices)):
-    raise _lib.InvalidArgumentError("vars, accums, linears, grads and indices must be equally long, N >= 1")
-  ids, gr, ns, toks = _multi_prep(var_handles, grads, indices)
-  vp = (ctypes.c_void_p * n)(*[h.ptr for h in var_handles]); ap = (ctypes.c_void_p * n)(*[h.ptr for h in accum_handles])
-  lp = (ctypes.c_void_p * n)(*[h.ptr for h in linear_handles])
-  sc = [ctypes.c_float(_scalar(x)) for x in (lr, l1, l2, l21, l2_shrinkage, lr_power)]
-  if unique_indices:
-    _lib.check(_lib.lib().kv_multi_apply_sparse_group_ftrl_unique(n, vp, ap, lp, _ptr_array(gr), _ptr_array(ids), ns, *sc,
-                                                                  _stream(var_handles[0])))
-    return
-  _lib.check(_lib.lib().kv_multi_apply_sparse_group_ftrl_tok(n, vp, ap, lp, _ptr_array(gr), _ptr_array(ids), ns, *sc,
-                                                             toks, _stream(var_handles[0])))
-
-
-def _multi_ftrl_v2(fn, var_handles, accum_handles, linear_handles, grads, indices, lr, l1, l2, l2_shrinkage, lr_power,
-                   unique_indices):
-  n = len(var_handles)
-  if n < 1 or not (n == len(accum_handles) == len(linear_handles) == len(grads) == len(indices)):
-    raise _lib.InvalidArgumentError("vars, accums, linears, grads and indices must be equally long, N >= 1")
-  ids, gr, ns, toks = _multi_prep(var_handles, grads, indices)
-  vp = (ctypes.c_void_p * n)(*[h.ptr for h in var_handles]); ap = (ctypes.c_void_p * n)(*[h.ptr for h in accum_handles])
-  lp = (ctypes.c_void_p * n)(*[h.ptr for h in linear_handles])
-  sc = [ctypes.c_float(_scalar(x)) for x in (lr, l1, l2, l2_shrinkage, lr_power)]
-  lib = _lib.lib()
-  if unique_indices:
-    _lib.check(getattr(lib, fn + "_unique")(n, vp, ap, lp, _ptr_array(gr), _ptr_array(ids), ns, *sc, _stream(var_handles[0])))
-    return
-  _lib.check(getattr(lib, fn + "_tok")(n, vp, ap, lp, _ptr_array(gr), _ptr_array(ids), ns, *sc, toks, _stream(var_handles[0])))
+  _multi_apply("sparse_group_ftrl", "vars, accums, linears, grads and indices", (var_handles, accum_handles, linear_handles),
+               grads, indices, (lr, l1, l2, l21, l2_shrinkage, lr_power), unique_indices)
 
 
 def kv_multi_sparse_apply_ftrl_v2(var_handles, accum_handles, linear_handles, grads, indices, lr, l1, l2, l2_shrinkage,
                                   lr_power, unique_indices=False):
   """KvVariableSparseApplyFtrlV2 on many (var, accum, linear) triples with two launches."""
-  _multi_ftrl_v2("kv_multi_apply_ftrl_v2", var_handles, accum_handles, linear_handles, grads, indices, lr, l1, l2,
-                 l2_shrinkage, lr_power, unique_indices)
+  _multi_apply("ftrl_v2", "vars, accums, linears, grads and indices", (var_handles, accum_handles, linear_handles),
+               grads, indices, (lr, l1, l2, l2_shrinkage, lr_power), unique_indices)
 
 
 def kv_multi_group_sparse_apply_ftrl_v2(var_handles, accum_handles, linear_handles, grads, indices, lr, l1, l2,
                                         l2_shrinkage, lr_power, unique_indices=False):
   """KvVariableGroupSparseApplyFtrlV2 on many (var, accum, linear) triples with two launches."""
-  _multi_ftrl_v2("kv_multi_apply_group_ftrl_v2", var_handles, accum_handles, linear_handles, grads, indices, lr, l1, l2,
-                 l2_shrinkage, lr_power, unique_indices)
+  _multi_apply("group_ftrl_v2", "vars, accums, linears, grads and indices", (var_handles, accum_handles, linear_handles),
+               grads, indices, (lr, l1, l2, l2_shrinkage, lr_power), unique_indices)
 
 
 def kv_multi_group_sparse_apply_rectified_adam(var_handles, opt_handles, grads, indices, lr, beta1_power, beta2_power, beta1,
                                                beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov,
                                                unique_indices=False):
   """KvVariableGroupSparseApplyRectifiedAdam on many (var, opt) pairs with two kernel launches (one with unique_indices)."""
-  n = len(var_handles)
-  if n < 1 or not (n == len(opt_handles) == len(grads) == len(indices)):
-    raise _lib.InvalidArgumentError("vars, opts, grads and indices must be equally long, N >= 1")
-  ids, gr, ns, toks = _multi_prep(var_handles, grads, indices)
-  vp = (ctypes.c_void_p * n)(*[h.ptr for h in var_handles]); sp = (ctypes.c_void_p * n)(*[h.ptr for h in opt_handles])
-  fl, flags = _radam_scalars(lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad,
-                             use_nesterov)
-  sc = [ctypes.c_float(x) for x in fl]
-  lib = _lib.lib()
-  if unique_indices:
-    _lib.check(lib.kv_multi_apply_group_rectified_adam_unique(n, vp, sp, _ptr_array(gr), _ptr_array(ids), ns, *sc, *flags,
-                                                              _stream(var_handles[0])))
-    return
-  _lib.check(lib.kv_multi_apply_group_rectified_adam_tok(n, vp, sp, _ptr_array(gr), _ptr_array(ids), ns, *sc, *flags, toks,
-                                                         _stream(var_handles[0])))
+  _multi_apply("group_rectified_adam", "vars, opts, grads and indices", (var_handles, opt_handles), grads, indices,
+               (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, bool(tractable), bool(amsgrad),
+                bool(use_nesterov)), unique_indices)
 
 
 _COMBINERS = {"sum": _lib.KV_COMBINER_SUM, "mean": _lib.KV_COMBINER_MEAN, "sqrtn": _lib.KV_COMBINER_SQRTN}

@@ -11,7 +11,8 @@
 // tensors.  tensorflow-cpu keeps tensors in host memory, so they cross PCIe through a per-resource ring of
 // pinned staging buffers (no allocation per call once warm; DESIGN.md §4 gives the PCIe bound): the DEVICE_CPU
 // kernels.  The DEVICE_GPU kernels at the end of the file (a TensorFlow-ROCm build) hand tensor.data() straight to the
-// C ABI on TF's stream: no staging, the measured path.
+// C ABI on TF's stream: no staging, the measured path.  The resource class these ops create (KvHipResource) and what the
+// optimizer kernels share live in kv_shim_common.h, which kv_ftrl_ops_hip.cc and kv_radam_ops_hip.cc include too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,8 +22,8 @@
 #include <string>
 #include <vector>
 
+#include "kv_shim_common.h"   // the resource class (KvHipResource), the status helpers, the optimizer ops' one sequence
 #include "kvhip.h"
-#include "unique_input.h"
 #include "tensorflow/core/framework/common_shape_fns.h"
 #include "tensorflow/core/framework/node_def.pb.h"
 #include "tensorflow/core/framework/op.h"
@@ -35,147 +36,6 @@ using namespace tensorflow;  // NOLINT
 using shape_inference::InferenceContext;
 using shape_inference::ShapeAndType;
 using shape_inference::ShapeHandle;
-
-static Status FromKv(int rc) {
-  if (rc == KV_OK) return OkStatus();
-  return Status(static_cast<tsl::error::Code>(rc), kv_last_error());
-}
-static Status FromHip(hipError_t e, const char* what) {
-  if (e == hipSuccess) return OkStatus();
-  return errors::Internal(what, ": ", hipGetErrorString(e));
-}
-#define HIP_OK(ctx, expr) OP_REQUIRES_OK(ctx, FromHip((expr), #expr))
-#define HIP_RET(expr)                                 \
-  do {                                                \
-    Status _s = FromHip((expr), #expr);               \
-    if (!_s.ok()) return _s;                          \
-  } while (0)
-
-// Ring of pinned host + device staging buffers.  A slot is reused only after the stream has passed the event
-// recorded behind its last use; buffers grow geometrically and are never freed before the resource dies.
-class StagingRing {
- public:
-  struct Slot {
-    char* host = nullptr;
-    char* dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;
-  };
-  ~StagingRing() {
-    for (Slot& s : slots_) {
-      if (s.done) { hipEventSynchronize(s.done); hipEventDestroy(s.done); }
-      if (s.host) hipHostFree(s.host);
-      if (s.dev) hipFree(s.dev);
-    }
-  }
-  // a slot with room for `bytes` on both sides (waits for the slot's previous user)
-  Status Acquire(size_t bytes, Slot** out) {
-    Slot& s = slots_[cursor_++ % kSlots];
-    if (s.done) HIP_RET(hipEventSynchronize(s.done));
-    if (s.cap < bytes) {
-      size_t cap = s.cap ? s.cap : (1u << 20);
-      while (cap < bytes) cap *= 2;
-      char *h = nullptr, *d = nullptr;
-      HIP_RET(hipHostMalloc(reinterpret_cast<void**>(&h), cap));
-      hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), cap);
-      if (e != hipSuccess) { hipHostFree(h); return FromHip(e, "hipMalloc(staging)"); }
-      if (s.host) hipHostFree(s.host);
-      if (s.dev) hipFree(s.dev);
-      s.host = h; s.dev = d; s.cap = cap;
-    }
-    if (!s.done) HIP_RET(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    *out = &s;
-    return OkStatus();
-  }
-  // host tensor -> device (asynchronous; the slot stays busy until Release)
-  static Status Upload(Slot* s, const void* src, size_t bytes, hipStream_t st) {
-    if (bytes == 0) return OkStatus();
-    std::memcpy(s->host, src, bytes);
-    HIP_RET(hipMemcpyAsync(s->dev, s->host, bytes, hipMemcpyHostToDevice, st));
-    return OkStatus();
-  }
-  // device -> host tensor (synchronous: the op's output must be complete when Compute returns)
-  static Status Download(Slot* s, void* dst, size_t bytes, hipStream_t st) {
-    if (bytes == 0) return OkStatus();
-    HIP_RET(hipMemcpyAsync(s->host, s->dev, bytes, hipMemcpyDeviceToHost, st));
-    HIP_RET(hipStreamSynchronize(st));
-    std::memcpy(dst, s->host, bytes);
-    return OkStatus();
-  }
-  static Status Release(Slot* s, hipStream_t st) { return FromHip(hipEventRecord(s->done, st), "hipEventRecord"); }
-
- private:
-  static constexpr int kSlots = 6;
-  Slot slots_[kSlots];
-  unsigned cursor_ = 0;
-};
-
-// The resource the handle points at: owns one kv_handle_t, its stream and its staging ring.
-class KvHipResource : public ResourceBase {
- public:
-  KvHipResource(kv_handle_t h, int dim, DataType key_dtype) : h_(h), dim_(dim), key_dtype_(key_dtype) {
-    hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking);
-  }
-  ~KvHipResource() override {
-    if (stream_) hipStreamSynchronize(stream_);
-    kv_destroy(h_);
-    if (stream_) hipStreamDestroy(stream_);
-  }
-  string DebugString() const override { return "KvHipResource"; }
-  kv_handle_t h() const { return h_; }
-  int dim() const { return dim_; }
-  DataType key_dtype() const { return key_dtype_; }
-  hipStream_t stream() const { return stream_; }
-  StagingRing* ring() { return &ring_; }
-  std::mutex* mu() { return &mu_; }
-  // the batch a training lookup left behind (kv_gather_or_insert_tok): token + what identified the ids
-  kv_batch_token_t token = 0;
-  const void* token_ids = nullptr;
-  int64_t token_n = 0;
-  uint64_t token_sum = 0;
-  Tensor token_keep;   // DEVICE_GPU: a reference to the lookup's ids tensor, held until the token is used or dropped — while
-                       // it is held the allocator cannot hand the buffer to another tensor, so "same address and length"
-                       // means "same tensor" (BFC readily reuses a freed buffer of the same size)
-  // the init table as the graph gave it (KvVariableExport returns it: dynamic_save.hpp:110-118)
-  std::vector<float> init_host;
-  int64_t init_rows = 0;
-
- private:
-  kv_handle_t h_;
-  int dim_;
-  DataType key_dtype_;
-  hipStream_t stream_ = nullptr;
-  StagingRing ring_;
-  std::mutex mu_;   // one Compute at a time moves data through this resource's ring
-};
-
-// content fingerprint of an ids tensor: EVERY byte takes part (the token is only passed on when the optimizer op
-// receives the very ids the lookup saw — kvhip.h promises a right result only then; a sampled hash would let two
-// batches that differ in an unsampled id share an index).  The ids are on the host here and about to be copied
-// anyway; one multiply-xor per 8 bytes is nothing next to the PCIe transfer.  TF-core's de-duplicated indices
-// never match and take the general path.
-static uint64_t Fingerprint(const void* p, size_t bytes) {
-  const unsigned char* c = static_cast<const unsigned char*>(p);
-  uint64_t h = 1469598103934665603ull ^ bytes;
-  size_t i = 0;
-  for (; i + 8 <= bytes; i += 8) {
-    uint64_t w;
-    std::memcpy(&w, c + i, 8);
-    h = (h ^ w) * 0x9E3779B97F4A7C15ull;
-    h ^= h >> 29;
-  }
-  for (; i < bytes; ++i) h = (h ^ c[i]) * 1099511628211ull;
-  return h;
-}
-
-static Status KeyTypeMatches(const KvHipResource* r, const Tensor& ids) {
-  const DataType t = ids.dtype();
-  const bool ok = (r->key_dtype() == DT_INT32 && t == DT_INT32) ||
-                  (r->key_dtype() != DT_INT32 && (t == DT_INT64 || t == DT_UINT64));
-  if (!ok) return errors::InvalidArgument("indices dtype ", DataTypeString(t), " does not match the table's key dtype ",
-                                          DataTypeString(r->key_dtype()));
-  return OkStatus();
-}
 
 // handle shape [?, value_shape...] and dtype on the resource output (ops/kv_variable_ops.cc:49-73)
 static Status KvVariableShapeFn(InferenceContext* c) {
@@ -321,12 +181,6 @@ REGISTER_KERNEL_BUILDER(Name("KvVariable").Device(DEVICE_CPU), CreateKvVariableH
 REGISTER_KERNEL_BUILDER(Name("KvVariableV2").Device(DEVICE_CPU), CreateKvVariableHipOp);
 REGISTER_KERNEL_BUILDER(Name("KvVariableV3").Device(DEVICE_CPU), CreateKvVariableHipOp);
 REGISTER_KERNEL_BUILDER(Name("KvVariableV4").Device(DEVICE_CPU), CreateKvVariableHipOp);
-
-// every kernel below starts the same way
-#define KV_RESOURCE(ctx, index, var)                                          \
-  KvHipResource* var = nullptr;                                               \
-  OP_REQUIRES_OK(ctx, LookupResource(ctx, HandleFromInput(ctx, index), &var)); \
-  core::ScopedUnref unref_##var(var)
 
 // ---- KvVariableShapeV2 : ops :203-210, kernels/kv_variable_ops.cc:159-177 -------------------------------
 REGISTER_OP("KvVariableShapeV2")
@@ -750,78 +604,29 @@ REGISTER_OP("KvVariableGroupSparseApplyAdamV4")
     .Attr("use_locking: bool = false")
     .SetShapeFn(shape_inference::NoOutputs);
 
-// Are the `indices` of this optimizer node unique?  In an UNCHANGED reference graph they are: the processor patch
-// (python/ops/variable_scope.py:1096-1106) sends the gradient through TF-core's _deduplicate_indexed_slices, whose
-// array_ops.unique produces the node ".../Unique" whose output 0 feeds input `input` here.  Then the op is ONE launch
-// (kv_apply_*_unique, include/kvhip.h).  The test is the producer's name and output slot (unique_input.h: the exact leaf
-// Unique / UniqueV2 with TensorFlow's _<n> suffix, slot 0 only — ":1" is the inverse index vector) — a heuristic; the
-// promise it makes is also guarded on the device (an id listed twice raises the table's error word: the next op on the
-// table fails with InvalidArgument).  TFPLUS_KV_UNIQUE_INDICES=0 never takes that path, =1 always does.
-static bool IndicesComeFromUnique(const NodeDef& def, int input) {
-  const char* e = std::getenv("TFPLUS_KV_UNIQUE_INDICES");
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '1') return true;
-  if (input >= def.input_size()) return false;
-  return kv_shim::InputIsUniqueValues(def.input(input));
+// The optimizer kernels, DEVICE_CPU (staged) and DEVICE_GPU, are a constructor and one call of the sequence in
+// kv_shim_common.h (ApplyStaged / ApplyOnDevice); what differs per op is where its inputs are (ApplyInputs: number of
+// tables, positions of grad and indices, first and last scalar input) and the C call.
+constexpr ApplyInputs kGroupAdamInputs = {2, 2, 3, 4, 12};   // scalars: kernels/training_ops.cc:7034-7068
+template <int VERSION>
+static int CallGroupAdam(OpKernelContext* ctx, const kv_handle_t* h, const float* grad, const void* ids, int64_t n,
+                         const kv_batch_token_t* token, hipStream_t st) {
+  auto f = [&](int i) { return ctx->input(i).scalar<float>()(); };   // host memory (the DEVICE_GPU registrations say so)
+  if (!token)
+    return kv_apply_group_adam_unique(h[0], h[1], grad, ids, n, f(4), f(5), f(6), f(7), f(8), f(9), f(10), f(11), f(12),
+                                      VERSION, st);
+  return kv_apply_group_adam_tok(h[0], h[1], grad, ids, n, f(4), f(5), f(6), f(7), f(8), f(9), f(10), f(11), f(12), VERSION,
+                                 *token, st);
 }
-
-// gradient + indices of an optimizer op on the var's ring; the var's stream carries the whole op
-struct GradIds {
-  StagingRing::Slot *sg = nullptr, *si = nullptr;
-  int64_t n = 0;
-  kv_batch_token_t token = 0;
-};
-static Status StageGradIds(OpKernelContext* ctx, KvHipResource* var, const Tensor& grad, const Tensor& ids, GradIds* g) {
-  if (!TensorShapeUtils::IsVector(ids.shape())) return errors::InvalidArgument("indices must be one-dimensional");
-  TF_RETURN_IF_ERROR(KeyTypeMatches(var, ids));
-  if (grad.dims() < 1 || grad.dim_size(0) != ids.dim_size(0))
-    return errors::InvalidArgument("grad must be the same size as indices in the first dimension.");
-  if (grad.NumElements() != ids.dim_size(0) * var->dim())
-    return errors::InvalidArgument("var and grad must match in dimension 1");
-  g->n = ids.dim_size(0);
-  if (g->n == 0) return OkStatus();
-  TF_RETURN_IF_ERROR(var->ring()->Acquire(grad.TotalBytes(), &g->sg));
-  TF_RETURN_IF_ERROR(var->ring()->Acquire(ids.TotalBytes(), &g->si));
-  TF_RETURN_IF_ERROR(StagingRing::Upload(g->sg, grad.data(), grad.TotalBytes(), var->stream()));
-  TF_RETURN_IF_ERROR(StagingRing::Upload(g->si, ids.data(), ids.TotalBytes(), var->stream()));
-  // the batch token of the forward lookup, when these are the very ids it saw (same length and content); TF-core's
-  // _deduplicate_indexed_slices hands over unique ids, which never match: those take the general path
-  if (var->token != 0 && var->token_n == g->n && var->token_sum == Fingerprint(ids.data(), ids.TotalBytes()))
-    g->token = var->token;
-  return OkStatus();
-}
-static Status ReleaseGradIds(KvHipResource* var, GradIds* g) {
-  if (g->sg) TF_RETURN_IF_ERROR(StagingRing::Release(g->sg, var->stream()));
-  if (g->si) TF_RETURN_IF_ERROR(StagingRing::Release(g->si, var->stream()));
-  return OkStatus();
-}
-// the slot resources' own streams must see the work the var's stream was given, and vice versa: the C ABI
-// orders ops of one table across streams itself (kvhip.h), so nothing to do here beyond using var's stream
 
 template <int VERSION>
 class KvGroupAdamHipOp : public OpKernel {
  public:
-  explicit KvGroupAdamHipOp(OpKernelConstruction* c) : OpKernel(c), unique_(IndicesComeFromUnique(c->def(), 3)) {}
+  explicit KvGroupAdamHipOp(OpKernelConstruction* c)
+      : OpKernel(c), unique_(IndicesComeFromUnique(c->def(), kGroupAdamInputs.indices)) {}
   void Compute(OpKernelContext* ctx) override {
-    KV_RESOURCE(ctx, 0, var);
-    KV_RESOURCE(ctx, 1, slot);
-    for (int i = 4; i <= 12; ++i)   // kernels/training_ops.cc:7034-7068
-      OP_REQUIRES(ctx, TensorShapeUtils::IsScalar(ctx->input(i).shape()),
-                  errors::InvalidArgument("input ", i, " is not a scalar: ", ctx->input(i).shape().DebugString()));
-    auto f = [&](int i) { return ctx->input(i).scalar<float>()(); };
-    std::lock_guard<std::mutex> l(*var->mu());
-    GradIds g;
-    OP_REQUIRES_OK(ctx, StageGradIds(ctx, var, ctx->input(2), ctx->input(3), &g));
-    if (g.n == 0) return;
-    if (g.token == 0 && unique_)
-      OP_REQUIRES_OK(ctx, FromKv(kv_apply_group_adam_unique(var->h(), slot->h(), reinterpret_cast<const float*>(g.sg->dev), g.si->dev,
-                                                            g.n, f(4), f(5), f(6), f(7), f(8), f(9), f(10), f(11), f(12), VERSION,
-                                                            var->stream())));
-    else
-      OP_REQUIRES_OK(ctx, FromKv(kv_apply_group_adam_tok(var->h(), slot->h(), reinterpret_cast<const float*>(g.sg->dev), g.si->dev,
-                                                         g.n, f(4), f(5), f(6), f(7), f(8), f(9), f(10), f(11), f(12), VERSION,
-                                                         g.token, var->stream())));
-    OP_REQUIRES_OK(ctx, ReleaseGradIds(var, &g));
+    OP_REQUIRES_OK(ctx, ApplyStaged(ctx, kGroupAdamInputs, unique_,
+                                    [ctx](auto... a) { return CallGroupAdam<VERSION>(ctx, a...); }));
   }
 
  private:
@@ -847,29 +652,23 @@ REGISTER_OP("KvVariableSparseApplyAdagrad")
     .Attr("update_slots: bool = true")
     .SetShapeFn(shape_inference::NoOutputs);
 
+constexpr ApplyInputs kAdagradInputs = {2, 3, 4, 2, 2, "lr"};
+static int CallAdagrad(OpKernelContext* ctx, bool update_slots, const kv_handle_t* h, const float* grad, const void* ids,
+                       int64_t n, const kv_batch_token_t* token, hipStream_t st) {
+  const float lr = ctx->input(2).scalar<float>()();
+  if (!token) return kv_apply_adagrad_unique(h[0], h[1], lr, grad, ids, n, update_slots ? 1 : 0, st);
+  return kv_apply_adagrad_tok(h[0], h[1], lr, grad, ids, n, update_slots ? 1 : 0, *token, st);
+}
+
 class KvAdagradHipOp : public OpKernel {
  public:
-  explicit KvAdagradHipOp(OpKernelConstruction* c) : OpKernel(c), unique_(IndicesComeFromUnique(c->def(), 4)) {
+  explicit KvAdagradHipOp(OpKernelConstruction* c)
+      : OpKernel(c), unique_(IndicesComeFromUnique(c->def(), kAdagradInputs.indices)) {
     OP_REQUIRES_OK(c, c->GetAttr("update_slots", &update_slots_));
   }
   void Compute(OpKernelContext* ctx) override {
-    KV_RESOURCE(ctx, 0, var);
-    KV_RESOURCE(ctx, 1, acc);
-    OP_REQUIRES(ctx, TensorShapeUtils::IsScalar(ctx->input(2).shape()),
-                errors::InvalidArgument("lr is not a scalar: ", ctx->input(2).shape().DebugString()));
-    std::lock_guard<std::mutex> l(*var->mu());
-    GradIds g;
-    OP_REQUIRES_OK(ctx, StageGradIds(ctx, var, ctx->input(3), ctx->input(4), &g));
-    if (g.n == 0) return;
-    if (g.token == 0 && unique_)
-      OP_REQUIRES_OK(ctx, FromKv(kv_apply_adagrad_unique(var->h(), acc->h(), ctx->input(2).scalar<float>()(),
-                                                         reinterpret_cast<const float*>(g.sg->dev), g.si->dev, g.n,
-                                                         update_slots_ ? 1 : 0, var->stream())));
-    else
-      OP_REQUIRES_OK(ctx, FromKv(kv_apply_adagrad_tok(var->h(), acc->h(), ctx->input(2).scalar<float>()(),
-                                                      reinterpret_cast<const float*>(g.sg->dev), g.si->dev, g.n,
-                                                      update_slots_ ? 1 : 0, g.token, var->stream())));
-    OP_REQUIRES_OK(ctx, ReleaseGradIds(var, &g));
+    OP_REQUIRES_OK(ctx, ApplyStaged(ctx, kAdagradInputs, unique_,
+                                    [&](auto... a) { return CallAdagrad(ctx, update_slots_, a...); }));
   }
 
  private:
@@ -896,31 +695,21 @@ REGISTER_OP("KvVariableSparseGroupSparseApplyFtrlV2")
     .Attr("use_locking: bool = false")
     .SetShapeFn(shape_inference::NoOutputs);
 
+constexpr ApplyInputs kGroupFtrlInputs = {3, 3, 4, 5, 10};
+static int CallGroupFtrl(OpKernelContext* ctx, const kv_handle_t* h, const float* grad, const void* ids, int64_t n,
+                         const kv_batch_token_t* token, hipStream_t st) {
+  auto f = [&](int i) { return ctx->input(i).scalar<float>()(); };
+  if (!token) return kv_apply_sparse_group_ftrl_unique(h[0], h[1], h[2], grad, ids, n, f(5), f(6), f(7), f(8), f(9), f(10), st);
+  return kv_apply_sparse_group_ftrl_tok(h[0], h[1], h[2], grad, ids, n, f(5), f(6), f(7), f(8), f(9), f(10), *token, st);
+}
+
 class KvGroupFtrlHipOp : public OpKernel {
  public:
-  explicit KvGroupFtrlHipOp(OpKernelConstruction* c) : OpKernel(c), unique_(IndicesComeFromUnique(c->def(), 4)) {}
+  explicit KvGroupFtrlHipOp(OpKernelConstruction* c)
+      : OpKernel(c), unique_(IndicesComeFromUnique(c->def(), kGroupFtrlInputs.indices)) {}
   void Compute(OpKernelContext* ctx) override {
-    KV_RESOURCE(ctx, 0, var);
-    KV_RESOURCE(ctx, 1, acc);
-    KV_RESOURCE(ctx, 2, lin);
-    for (int i = 5; i <= 10; ++i)
-      OP_REQUIRES(ctx, TensorShapeUtils::IsScalar(ctx->input(i).shape()),
-                  errors::InvalidArgument("input ", i, " is not a scalar: ", ctx->input(i).shape().DebugString()));
-    auto f = [&](int i) { return ctx->input(i).scalar<float>()(); };
-    std::lock_guard<std::mutex> l(*var->mu());
-    GradIds g;
-    OP_REQUIRES_OK(ctx, StageGradIds(ctx, var, ctx->input(3), ctx->input(4), &g));
-    if (g.n == 0) return;
-    if (g.token == 0 && unique_) {
-      OP_REQUIRES_OK(ctx, FromKv(kv_apply_sparse_group_ftrl_unique(var->h(), acc->h(), lin->h(), reinterpret_cast<const float*>(g.sg->dev),
-                                                                g.si->dev, g.n, f(5), f(6), f(7), f(8), f(9), f(10),
-                                                                var->stream())));
-    } else {
-      OP_REQUIRES_OK(ctx, FromKv(kv_apply_sparse_group_ftrl_tok(var->h(), acc->h(), lin->h(), reinterpret_cast<const float*>(g.sg->dev),
-                                                                g.si->dev, g.n, f(5), f(6), f(7), f(8), f(9), f(10), g.token,
-                                                                var->stream())));
-    }
-    OP_REQUIRES_OK(ctx, ReleaseGradIds(var, &g));
+    OP_REQUIRES_OK(ctx, ApplyStaged(ctx, kGroupFtrlInputs, unique_,
+                                    [ctx](auto... a) { return CallGroupFtrl(ctx, a...); }));
   }
 
  private:
@@ -1412,12 +1201,6 @@ REGISTER_KERNEL_BUILDER(Name("KvVariableFullOrDeltaImportV2").Device(DEVICE_CPU)
 // GPU-placed variable finds a kernel for each of them (a resource is only visible to kernels of its own device); those
 // run the kernel bodies above unchanged — they are savers, counters and maintenance, not the hot path.
 // =====================================================================================================================
-}  // namespace tfplus_hip
-#include "tensorflow/core/util/gpu_kernel_helper.h"   // GetGpuStream: gpuStream_t is hipStream_t under TENSORFLOW_USE_ROCM
-namespace tfplus_hip {
-
-static hipStream_t TfStream(OpKernelContext* ctx) { return GetGpuStream(ctx); }
-
 template <int MODE>
 class KvGatherGpuOp : public OpKernel {
  public:
@@ -1464,45 +1247,14 @@ KV_REGISTER_GATHER_GPU("KvVariableGatherOrZerosV2", 0);
 KV_REGISTER_GATHER_GPU("KvVariableGatherOrInsertV2", 1);
 KV_REGISTER_GATHER_GPU("KvVariableGatherOrInsertWithCounts", 2);
 
-// gradient + indices of an optimizer op, device-resident: shape checks, and the lookup's token when these are its ids
-static Status DeviceGradIds(KvHipResource* var, const Tensor& grad, const Tensor& ids, int64_t* n, kv_batch_token_t* token) {
-  if (!TensorShapeUtils::IsVector(ids.shape())) return errors::InvalidArgument("indices must be one-dimensional");
-  TF_RETURN_IF_ERROR(KeyTypeMatches(var, ids));
-  if (grad.dims() < 1 || grad.dim_size(0) != ids.dim_size(0))
-    return errors::InvalidArgument("grad must be the same size as indices in the first dimension.");
-  if (grad.NumElements() != ids.dim_size(0) * var->dim())
-    return errors::InvalidArgument("var and grad must match in dimension 1");
-  *n = ids.dim_size(0);
-  *token = (var->token != 0 && var->token_n == *n && var->token_ids == ids.data()) ? var->token : 0;
-  var->token = 0;   // one apply per lookup: a second optimizer op on the same ids rebuilds the index
-  var->token_keep = Tensor();
-  return OkStatus();
-}
-
 template <int VERSION>
 class KvGroupAdamGpuOp : public OpKernel {
  public:
-  explicit KvGroupAdamGpuOp(OpKernelConstruction* c) : OpKernel(c), unique_(IndicesComeFromUnique(c->def(), 3)) {}
+  explicit KvGroupAdamGpuOp(OpKernelConstruction* c)
+      : OpKernel(c), unique_(IndicesComeFromUnique(c->def(), kGroupAdamInputs.indices)) {}
   void Compute(OpKernelContext* ctx) override {
-    KV_RESOURCE(ctx, 0, var);
-    KV_RESOURCE(ctx, 1, slot);
-    for (int i = 4; i <= 12; ++i)   // kernels/training_ops.cc:7034-7068
-      OP_REQUIRES(ctx, TensorShapeUtils::IsScalar(ctx->input(i).shape()),
-                  errors::InvalidArgument("input ", i, " is not a scalar: ", ctx->input(i).shape().DebugString()));
-    auto f = [&](int i) { return ctx->input(i).scalar<float>()(); };   // host memory (registration below)
-    std::lock_guard<std::mutex> l(*var->mu());
-    int64_t n = 0;
-    kv_batch_token_t token = 0;
-    OP_REQUIRES_OK(ctx, DeviceGradIds(var, ctx->input(2), ctx->input(3), &n, &token));
-    if (n == 0) return;
-    if (token == 0 && unique_)
-      OP_REQUIRES_OK(ctx, FromKv(kv_apply_group_adam_unique(var->h(), slot->h(), static_cast<const float*>(ctx->input(2).data()),
-                                                            ctx->input(3).data(), n, f(4), f(5), f(6), f(7), f(8), f(9), f(10), f(11),
-                                                            f(12), VERSION, TfStream(ctx))));
-    else
-      OP_REQUIRES_OK(ctx, FromKv(kv_apply_group_adam_tok(var->h(), slot->h(), static_cast<const float*>(ctx->input(2).data()),
-                                                         ctx->input(3).data(), n, f(4), f(5), f(6), f(7), f(8), f(9), f(10), f(11),
-                                                         f(12), VERSION, token, TfStream(ctx))));
+    OP_REQUIRES_OK(ctx, ApplyOnDevice(ctx, kGroupAdamInputs, unique_,
+                                      [ctx](auto... a) { return CallGroupAdam<VERSION>(ctx, a...); }));
   }
 
  private:
@@ -1520,27 +1272,13 @@ KV_REGISTER_APPLY_GPU("KvVariableGroupSparseApplyAdamV4", KV_GPU_ADAM_HOST, KvGr
 
 class KvAdagradGpuOp : public OpKernel {
  public:
-  explicit KvAdagradGpuOp(OpKernelConstruction* c) : OpKernel(c), unique_(IndicesComeFromUnique(c->def(), 4)) {
+  explicit KvAdagradGpuOp(OpKernelConstruction* c)
+      : OpKernel(c), unique_(IndicesComeFromUnique(c->def(), kAdagradInputs.indices)) {
     OP_REQUIRES_OK(c, c->GetAttr("update_slots", &update_slots_));
   }
   void Compute(OpKernelContext* ctx) override {
-    KV_RESOURCE(ctx, 0, var);
-    KV_RESOURCE(ctx, 1, acc);
-    OP_REQUIRES(ctx, TensorShapeUtils::IsScalar(ctx->input(2).shape()),
-                errors::InvalidArgument("lr is not a scalar: ", ctx->input(2).shape().DebugString()));
-    std::lock_guard<std::mutex> l(*var->mu());
-    int64_t n = 0;
-    kv_batch_token_t token = 0;
-    OP_REQUIRES_OK(ctx, DeviceGradIds(var, ctx->input(3), ctx->input(4), &n, &token));
-    if (n == 0) return;
-    if (token == 0 && unique_)
-      OP_REQUIRES_OK(ctx, FromKv(kv_apply_adagrad_unique(var->h(), acc->h(), ctx->input(2).scalar<float>()(),
-                                                         static_cast<const float*>(ctx->input(3).data()), ctx->input(4).data(), n,
-                                                         update_slots_ ? 1 : 0, TfStream(ctx))));
-    else
-      OP_REQUIRES_OK(ctx, FromKv(kv_apply_adagrad_tok(var->h(), acc->h(), ctx->input(2).scalar<float>()(),
-                                                      static_cast<const float*>(ctx->input(3).data()), ctx->input(4).data(), n,
-                                                      update_slots_ ? 1 : 0, token, TfStream(ctx))));
+    OP_REQUIRES_OK(ctx, ApplyOnDevice(ctx, kAdagradInputs, unique_,
+                                      [&](auto... a) { return CallAdagrad(ctx, update_slots_, a...); }));
   }
 
  private:
@@ -1552,29 +1290,11 @@ KV_REGISTER_APPLY_GPU("KvVariableSparseApplyAdagrad", KV_GPU_ADAGRAD_HOST, KvAda
 
 class KvGroupFtrlGpuOp : public OpKernel {
  public:
-  explicit KvGroupFtrlGpuOp(OpKernelConstruction* c) : OpKernel(c), unique_(IndicesComeFromUnique(c->def(), 4)) {}
+  explicit KvGroupFtrlGpuOp(OpKernelConstruction* c)
+      : OpKernel(c), unique_(IndicesComeFromUnique(c->def(), kGroupFtrlInputs.indices)) {}
   void Compute(OpKernelContext* ctx) override {
-    KV_RESOURCE(ctx, 0, var);
-    KV_RESOURCE(ctx, 1, acc);
-    KV_RESOURCE(ctx, 2, lin);
-    for (int i = 5; i <= 10; ++i)
-      OP_REQUIRES(ctx, TensorShapeUtils::IsScalar(ctx->input(i).shape()),
-                  errors::InvalidArgument("input ", i, " is not a scalar: ", ctx->input(i).shape().DebugString()));
-    auto f = [&](int i) { return ctx->input(i).scalar<float>()(); };
-    std::lock_guard<std::mutex> l(*var->mu());
-    int64_t n = 0;
-    kv_batch_token_t token = 0;
-    OP_REQUIRES_OK(ctx, DeviceGradIds(var, ctx->input(3), ctx->input(4), &n, &token));
-    if (n == 0) return;
-    if (token == 0 && unique_) {
-      OP_REQUIRES_OK(ctx, FromKv(kv_apply_sparse_group_ftrl_unique(var->h(), acc->h(), lin->h(), static_cast<const float*>(ctx->input(3).data()),
-                                                                ctx->input(4).data(), n, f(5), f(6), f(7), f(8), f(9), f(10),
-                                                                TfStream(ctx))));
-    } else {
-      OP_REQUIRES_OK(ctx, FromKv(kv_apply_sparse_group_ftrl_tok(var->h(), acc->h(), lin->h(), static_cast<const float*>(ctx->input(3).data()),
-                                                                ctx->input(4).data(), n, f(5), f(6), f(7), f(8), f(9), f(10), token,
-                                                                TfStream(ctx))));
-    }
+    OP_REQUIRES_OK(ctx, ApplyOnDevice(ctx, kGroupFtrlInputs, unique_,
+                                      [ctx](auto... a) { return CallGroupFtrl(ctx, a...); }));
   }
 
  private:
