@@ -520,6 +520,42 @@ int kv_lookup_sparse(kv_handle_t h, const void* ids, const void* segment_ids, in
                      const float* weights, int64_t n, int64_t num_segments, int combiner,
                      int count_occurrences, float* out, kv_stream_t stream);
 
+/* The backward of kv_lookup_sparse: the `values` [n, dim] of the IndexedSlices whose indices are the lookup's ids,
+ *   values[j, :] = scale_j * seg_grad[segment_ids[j], :]
+ *   scale_j = w_j (sum), w_j / sum_s(w) (mean), w_j / sqrtf(sum_s(w^2)) (sqrtn); s = the segment of j, w_j = 1 for weights == NULL
+ * seg_grad [num_segments, dim] is the gradient of the lookup's output.  The result is defined bit for bit: a segment's
+ * denominator is summed in float32 from +0 in position order (the forward's own order, so both directions divide by the
+ * same number; unweighted it is the segment's length), the scale is one IEEE division, each element one multiply.  A zero
+ * denominator gives what IEEE gives (inf / nan).  Rows of seg_grad that belong to empty segments are never read; segment
+ * ids outside [0, num_segments) are clamped into it (memory safety only).  `h` supplies device, dim and workspace: no row
+ * and no record of the table is touched.  Any dim.  Checks, status codes and the per-call limit of n as kv_lookup_sparse;
+ * num_segments == 0 and n == 0 are no-ops.  Asynchronous; under a stream capture a call that would have to grow a
+ * workspace buffer is refused before anything is queued (run it once outside the capture first). */
+int kv_lookup_sparse_grad(kv_handle_t h, const float* seg_grad, const void* segment_ids, int segment_dtype,
+                          const float* weights, int64_t n, int64_t num_segments, int combiner,
+                          float* values, kv_stream_t stream);
+
+/* kv_lookup_sparse / kv_lookup_sparse_grad on many tables with one launch per stage: table i gets exactly what the
+ * single-table op would give it — the same output bits, rows, frequency words, flags and delta lists.  The tables follow
+ * the rules of the other batched ops: one device, dim and key dtype, each listed once, none in occurrence-order mode
+ * (KV_UNIMPLEMENTED).  One segment dtype and one combiner per call.  `weights` may be NULL, and so may weights[i];
+ * count_occurrences NULL means 0 for every table.  ns[i] == 0 yields zero rows for table i's segments (forward) and
+ * writes nothing (backward); a table with num_segments[i] == 0 is a no-op.
+ * Forward: four launches whatever num_tables is (tile pass, partition pass, offsets, combiner) for the dims the entry-list
+ * kernels serve — multiples of 4 up to 256.  Other dims run the single-table path table by table inside the call, under
+ * the same locks: the same result, no launch saved.  Backward: at most three launches (offsets, weighted denominators,
+ * expand), any dim.
+ * No batch tokens: the partition pass cannot be left pending for the optimizer apply, because the combiner reads the rows
+ * it publishes for new keys.  The apply that follows a sparse lookup builds its index as it does today. */
+int kv_multi_lookup_sparse(int num_tables, const kv_handle_t* tables, const void* const* ids,
+                           const void* const* segment_ids, int segment_dtype, const float* const* weights,
+                           const int64_t* ns, const int64_t* num_segments, int combiner,
+                           const int* count_occurrences, float* const* outs, kv_stream_t stream);
+int kv_multi_lookup_sparse_grad(int num_tables, const kv_handle_t* tables, const float* const* seg_grads,
+                                const void* const* segment_ids, int segment_dtype, const float* const* weights,
+                                const int64_t* ns, const int64_t* num_segments, int combiner,
+                                float* const* values, kv_stream_t stream);
+
 /* tf.unsorted_segment_sum(data [n, dim], segment_ids [n] int32, num_segments) on the batch pipeline
  * (no float atomics: a segment named by 100 000 rows costs the same as 100 000 segments): out
  * [num_segments, dim]; segments nobody names are zero rows, ids outside [0, num_segments) are

@@ -6,14 +6,15 @@ package itself imports on a machine without a GPU (the CPU test tier), but the f
 without the extension raises — there is no CPU path.
 """
 
-__all__ = ["get_kv_variable", "embedding_lookup", "embedding_lookup_sparse", "safe_embedding_lookup_sparse",
-           "KvVariable", "GroupAdamOptimizer", "AdagradOptimizer", "SparseGroupFtrlOptimizer"]
+__all__ = ["get_kv_variable", "embedding_lookup", "embedding_lookup_sparse", "embedding_lookup_sparse_multi",
+           "safe_embedding_lookup_sparse", "KvVariable", "GroupAdamOptimizer", "AdagradOptimizer", "SparseGroupFtrlOptimizer"]
 
 
 def __getattr__(name):
   if name in ("get_kv_variable",):
     from tfplus_amd.kv_variable.python.ops import variable_scope as m
-  elif name in ("embedding_lookup", "embedding_lookup_sparse", "safe_embedding_lookup_sparse"):
+  elif name in ("embedding_lookup", "embedding_lookup_sparse", "embedding_lookup_sparse_multi",
+                "safe_embedding_lookup_sparse"):
     from tfplus_amd.kv_variable.python.ops import embedding_ops as m
   elif name == "KvVariable":
     from tfplus_amd.kv_variable.python.ops import kv_variable_ops as m

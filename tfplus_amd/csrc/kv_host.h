@@ -69,8 +69,10 @@ struct Workspace {
   long long* scat_keys = nullptr;  // kv_scatter_update on repeated ids: de-duplicated ids and combined updates
   float* scat_sum = nullptr;
   long long scat_cap = 0;          // rows
-  unsigned* seg_off = nullptr;   // kv_lookup_sparse: CSR offsets [seg_cap + 1]
+  unsigned* seg_off = nullptr;   // kv_lookup_sparse and its backward: CSR offsets [seg_cap + 1]
   long long seg_cap = 0;
+  float* seg_den = nullptr;      // kv_lookup_sparse_grad: the segments' denominators [den_cap]
+  long long den_cap = 0;
   unsigned long long* dbg = nullptr;
 };
 
@@ -454,12 +456,12 @@ struct BatchStage {       // a small ring, so the host can prepare call k+1 whil
   StageSlot slot[4];
   unsigned cursor = 0;
 };
-extern BatchStage g_stage[64][2];   // [device][0 = inference gather, 1 = training ops]
+extern BatchStage g_stage[64][3];   // [device][0 = inference gather, 1 = training ops, 2 = the sparse lookups' own descriptors]
 int stage_take(BatchStage& st, size_t bytes, StageSlot** out);   // the ring's next slot; st.mu is HELD where it succeeds
 // `count` descriptors of a batched launch on g_stage[device][ring]: zeroed host descriptors by index, then ONE upload,
 // which is the only way to the device pointer — so a slot a kernel may still read is always marked busy.  The ring stays
 // locked until scope exit.  Check rc before anything else.
-template <class Desc>   // MultiDesc, FinishDesc, BatchGatherDesc
+template <class Desc>   // MultiDesc, FinishDesc, BatchGatherDesc, SparseDesc
 class Staged {
   BatchStage& st;
   StageSlot* sl = nullptr;

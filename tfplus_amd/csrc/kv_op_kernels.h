@@ -1,5 +1,6 @@
 // kv_op_kernels.h — the small kernels only the table ops (kv_ops.hip) launch: point queries, delete, export / import /
-// delta, the inference gathers, unique / dedup helpers, the sparse lookup's combiners, kv_take_rows.  Included by kv_ops.hip
+// delta, the inference gathers, unique / dedup helpers, the sparse lookup's combiners, its backward and their batched forms,
+// kv_take_rows.  Included by kv_ops.hip
 // alone, behind kv_device.h, inside its anonymous namespace.
 #pragma once
 
@@ -318,8 +319,8 @@ __global__ void k_dedup_inverse(WsDev w, long long n, int* inverse) {
 //                   position order (tf.segment_sum order); mean: / sum w, sqrtn: / sqrt(sum w^2)
 // Segment ids outside [prev, num_segments) are clamped (memory safety only; TF rejects them).
 template <typename SegT>
-__global__ void __launch_bounds__(TB) k_seg_offsets(const SegT* __restrict__ seg, long long n, long long nseg,
-                                                    unsigned* __restrict__ off) {
+__device__ __forceinline__ void seg_offsets_body(const SegT* __restrict__ seg, long long n, long long nseg,
+                                                 unsigned* __restrict__ off) {
   for (long long i = (long long)blockIdx.x * TB + threadIdx.x; i <= n; i += (long long)gridDim.x * TB) {
     long long prev = i > 0 ? (long long)seg[i - 1] : -1;
     long long cur = i < n ? (long long)seg[i] : nseg;
@@ -327,6 +328,11 @@ __global__ void __launch_bounds__(TB) k_seg_offsets(const SegT* __restrict__ seg
     cur = cur < 0 ? 0 : (cur > nseg ? nseg : cur);
     for (long long sgi = prev + 1; sgi <= cur; ++sgi) off[sgi] = (unsigned)i;
   }
+}
+template <typename SegT>
+__global__ void __launch_bounds__(TB) k_seg_offsets(const SegT* __restrict__ seg, long long n, long long nseg,
+                                                    unsigned* __restrict__ off) {
+  seg_offsets_body(seg, n, nseg, off);
 }
 
 // VQ = float4 lanes per row (dim / 4, power of two <= 64) or 0 = one thread per element.
@@ -423,10 +429,10 @@ __global__ void __launch_bounds__(TB) k_take_rows(const U* __restrict__ src, con
 // pass in front of this kernel has published every new row.  VQ lanes (power of two >= dim / 4) per segment, SU
 // positions of a segment in flight; the sums are taken in position order whatever SU is.
 template <int VQ>
-__global__ void __launch_bounds__(TB) k_seg_combine_e(TableDev t, const unsigned short* __restrict__ pos_ent,
-                                                      const unsigned* __restrict__ ent_b, const long long* __restrict__ ent_key,
-                                                      const unsigned* __restrict__ off, const float* __restrict__ wts,
-                                                      long long nseg, int combiner, float* __restrict__ out) {
+__device__ __forceinline__ void seg_combine_e_body(const TableDev& t, const unsigned short* __restrict__ pos_ent,
+                                                   const unsigned* __restrict__ ent_b, const long long* __restrict__ ent_key,
+                                                   const unsigned* __restrict__ off, const float* __restrict__ wts,
+                                                   long long nseg, int combiner, float* __restrict__ out) {
   const int D4 = t.dim >> 2;
   const int v = threadIdx.x % VQ;
   const bool vlive = v < D4;
@@ -471,10 +477,136 @@ __global__ void __launch_bounds__(TB) k_seg_combine_e(TableDev t, const unsigned
     if (vlive) reinterpret_cast<float4*>(out + (size_t)sgi * t.dim)[v] = acc;
   }
 }
+template <int VQ>
+__global__ void __launch_bounds__(TB) k_seg_combine_e(TableDev t, const unsigned short* __restrict__ pos_ent,
+                                                      const unsigned* __restrict__ ent_b, const long long* __restrict__ ent_key,
+                                                      const unsigned* __restrict__ off, const float* __restrict__ wts,
+                                                      long long nseg, int combiner, float* __restrict__ out) {
+  seg_combine_e_body<VQ>(t, pos_ent, ent_b, ent_key, off, wts, nseg, combiner, out);
+}
 
 // inverse[i] = the dense number of position i's id: position -> its entry in its tile -> the number k_papply PA_UNIQUE gave it
 __global__ void __launch_bounds__(TB) k_inverse_e(const unsigned short* __restrict__ pos_ent, const unsigned* __restrict__ ent_b,
                                                   long long n, int* __restrict__ inverse) {
   for (long long i = (long long)blockIdx.x * TB + threadIdx.x; i < n; i += (long long)gridDim.x * TB)
     inverse[i] = (int)ent_b[(size_t)(i / TILE) * TILE + pos_ent[i]];
+}
+
+// ---------------------------------------------------------------------------------------------
+// The backward of the sparse lookup: values[j] = scale_j * seg_grad[segment of j], scale_j = w_j (sum), w_j / sum_s(w)
+// (mean), w_j / sqrtf(sum_s(w^2)) (sqrtn); w_j = 1 without weights.  Defined bit for bit: a segment's denominator is summed
+// in float32 from +0 in position order (seg_combine_e_body's order and roundings), the scale is one IEEE division, each
+// element one multiply.
+//   k_seg_offsets   the CSR offsets, as in the forward
+//   k_seg_den       weighted mean / sqrtn: den[s], one thread per segment (unweighted: the segment's length, straight
+//                   from the offsets — no pass)
+//   k_seg_expand    one lane group (VQ float4 lanes; VQ = 0: one thread per element) per position: reads seg_grad,
+//                   writes each values row exactly once.  Rows of empty segments are never read: no position names them.
+// A segment id outside [0, nseg) is clamped into it (memory safety only, like k_seg_offsets).
+__device__ __forceinline__ void seg_den_body(const unsigned* __restrict__ off, const float* __restrict__ wts, long long nseg,
+                                             int combiner, float* __restrict__ den) {
+  for (long long sgi = (long long)blockIdx.x * TB + threadIdx.x; sgi < nseg; sgi += (long long)gridDim.x * TB) {
+    const unsigned lo = off[sgi], hi = off[sgi + 1];
+    float a = 0.f;
+    if (combiner == 1) for (unsigned j = lo; j < hi; ++j) a += wts[j];
+    else for (unsigned j = lo; j < hi; ++j) { const float wj = wts[j]; a += wj * wj; }
+    den[sgi] = combiner == 1 ? a : sqrtf(a);
+  }
+}
+__global__ void __launch_bounds__(TB) k_seg_den(const unsigned* __restrict__ off, const float* __restrict__ wts, long long nseg,
+                                                int combiner, float* __restrict__ den) {
+  seg_den_body(off, wts, nseg, combiner, den);
+}
+
+// the scale of position j in segment sg
+__device__ __forceinline__ float seg_scale(const unsigned* __restrict__ off, const float* __restrict__ den,
+                                           const float* __restrict__ wts, long long j, long long sg, int combiner) {
+  const float wj = wts ? wts[j] : 1.f;
+  if (combiner == 0) return wj;
+  float d;
+  if (wts) d = den[sg];
+  else { d = (float)(off[sg + 1] - off[sg]); if (combiner == 2) d = sqrtf(d); }
+  return wj / d;
+}
+template <typename SegT>
+__device__ __forceinline__ long long seg_of(const SegT* __restrict__ seg, long long j, long long nseg) {
+  const long long sg = (long long)seg[j];
+  return sg < 0 ? 0 : (sg >= nseg ? nseg - 1 : sg);
+}
+template <typename SegT, int VQ>
+__device__ __forceinline__ void seg_expand_body(const float* __restrict__ seg_grad, const SegT* __restrict__ seg,
+                                                const unsigned* __restrict__ off, const float* __restrict__ den,
+                                                const float* __restrict__ wts, long long n, long long nseg, int D, int combiner,
+                                                float* __restrict__ values) {
+  if constexpr (VQ > 0) {
+    const int D4 = D >> 2;
+    const int v = threadIdx.x % VQ;
+    const long long g0 = ((long long)blockIdx.x * TB + threadIdx.x) / VQ;
+    const long long gstride = (long long)gridDim.x * TB / VQ;
+    for (long long j = g0; j < n; j += gstride) {
+      const long long sg = seg_of(seg, j, nseg);
+      const float sc = seg_scale(off, den, wts, j, sg, combiner);
+      const float4* src = reinterpret_cast<const float4*>(seg_grad + (size_t)sg * D);
+      float4* dst = reinterpret_cast<float4*>(values + (size_t)j * D);
+      for (int q = v; q < D4; q += VQ) {   // (one round for dims up to 256; the lanes past the row's end take none)
+        const float4 g = src[q];
+        dst[q] = make_float4(g.x * sc, g.y * sc, g.z * sc, g.w * sc);
+      }
+    }
+  } else {
+    const long long total = n * D;
+    for (long long x = (long long)blockIdx.x * TB + threadIdx.x; x < total; x += (long long)gridDim.x * TB) {
+      const long long j = x / D;
+      const int e = (int)(x - j * D);
+      const long long sg = seg_of(seg, j, nseg);
+      values[x] = seg_grad[(size_t)sg * D + e] * seg_scale(off, den, wts, j, sg, combiner);
+    }
+  }
+}
+template <typename SegT, int VQ>
+__global__ void __launch_bounds__(TB) k_seg_expand(const float* __restrict__ seg_grad, const SegT* __restrict__ seg,
+                                                   const unsigned* __restrict__ off, const float* __restrict__ den,
+                                                   const float* __restrict__ wts, long long n, long long nseg, int D, int combiner,
+                                                   float* __restrict__ values) {
+  seg_expand_body<SegT, VQ>(seg_grad, seg, off, den, wts, n, nseg, D, combiner, values);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The sparse lookup and its backward over many tables in one launch per stage (blockIdx.y = table).  The per-table sparse
+// arguments travel in an array of these, next to the MultiDesc array the batched tile and partition passes read (which
+// stays as narrow as the hot batched kernels index it).  A table with nseg == 0 takes no part.
+struct SparseDesc {
+  const void* seg;         // [n] segment ids (one dtype for the whole call)
+  const float* wts;        // [n] or null
+  unsigned* off;           // [nseg + 1] the table's Workspace::seg_off
+  float* den;              // [nseg] the table's Workspace::seg_den (backward, weighted mean / sqrtn)
+  const float* seg_grad;   // backward: [nseg, dim]
+  float* out;              // forward: [nseg, dim]; backward: values [n, dim]
+  long long n, nseg;
+};
+template <typename SegT>
+__global__ void __launch_bounds__(TB) k_seg_offsets_multi(const SparseDesc* __restrict__ descs) {
+  const SparseDesc& d = descs[blockIdx.y];
+  if (d.nseg == 0) return;
+  seg_offsets_body(reinterpret_cast<const SegT*>(d.seg), d.n, d.nseg, d.off);
+}
+template <int VQ>
+__global__ void __launch_bounds__(TB) k_seg_combine_e_multi(const MultiDesc* __restrict__ mdescs,
+                                                            const SparseDesc* __restrict__ descs, int combiner) {
+  const MultiDesc& m = mdescs[blockIdx.y];
+  const SparseDesc& d = descs[blockIdx.y];
+  if (d.nseg == 0) return;
+  seg_combine_e_body<VQ>(m.a.tv, m.w.pos_ent, m.w.ent_b, m.w.ent_key, d.off, d.wts, d.nseg, combiner, d.out);
+}
+__global__ void __launch_bounds__(TB) k_seg_den_multi(const SparseDesc* __restrict__ descs, int combiner) {
+  const SparseDesc& d = descs[blockIdx.y];
+  if (d.nseg == 0 || !d.wts) return;
+  seg_den_body(d.off, d.wts, d.nseg, combiner, d.den);
+}
+template <typename SegT, int VQ>
+__global__ void __launch_bounds__(TB) k_seg_expand_multi(const SparseDesc* __restrict__ descs, int D, int combiner) {
+  const SparseDesc& d = descs[blockIdx.y];
+  if (d.nseg == 0) return;
+  seg_expand_body<SegT, VQ>(d.seg_grad, reinterpret_cast<const SegT*>(d.seg), d.off, d.den, d.wts, d.n, d.nseg, D, combiner,
+                            d.out);
 }

@@ -1,5 +1,5 @@
 // kv_ops.hip — the table ops of the C ABI on the table core (kv_host.h): the training and inference lookups,
-// kv_lookup_sparse, unique / dedup / segment sums, point queries, delete, export / import / delta, scatter.  Its own kernels
+// kv_lookup_sparse with its backward and their batched forms, unique / dedup / segment sums, point queries, delete, export / import / delta, scatter.  Its own kernels
 // are kv_op_kernels.h's; the pipelines' kernels are reached through the core's launchers.
 //
 // An entry point reads as its checks — in the reference's order, which differs per op: where n == 0 returns and where
@@ -307,6 +307,163 @@ static int ensure_init_placeholder(kv_table* t, hipStream_t s) {
   return KV_OK;
 }
 
+
+// the sparse lookups' segment buffers: Workspace::seg_off holds num_segments + 1 offsets and, need_den, Workspace::seg_den
+// num_segments denominators (grown behind ws_sync like the rest of the workspace)
+static int ensure_seg(kv_table* t, long long num_segments, bool need_den, hipStream_t s) {
+  int rc;
+  Workspace& ws = t->ws;
+  if (ws.seg_cap < num_segments) {
+    if ((rc = ws_sync(s))) return rc;
+    const long long want = std::max<long long>(num_segments, ws.seg_cap * 2);
+    ws.seg_cap = 0;
+    if ((rc = regrow(&ws.seg_off, (size_t)(want + 1)))) return rc;
+    ws.seg_cap = want;
+  }
+  if (need_den && ws.den_cap < num_segments) {
+    if ((rc = ws_sync(s))) return rc;
+    const long long want = std::max<long long>(num_segments, ws.den_cap * 2);
+    ws.den_cap = 0;
+    if ((rc = regrow(&ws.seg_den, (size_t)want))) return rc;
+    ws.den_cap = want;
+  }
+  return KV_OK;
+}
+
+// the argument checks kv_lookup_sparse, its backward and their batched forms share
+static int sparse_call_checks(int combiner, int segment_dtype) {
+  if (combiner < KV_COMBINER_SUM || combiner > KV_COMBINER_SQRTN)
+    return fail(KV_INVALID_ARGUMENT, "combiner must be one of 'mean', 'sqrtn' or 'sum'");  // embedding_ops.py:345
+  if (segment_dtype != KV_DT_INT32 && segment_dtype != KV_DT_INT64)
+    return fail(KV_INVALID_ARGUMENT, "segment ids must be int32 or int64");
+  return KV_OK;
+}
+static int sparse_size_checks(const kv_table* t, int64_t n, int64_t num_segments) {
+  const bool fused = fused_tab(t);   // (dim is fixed at creation: readable without the lock)
+  if (n < 0 || n > (fused ? FUSED_MAX_N : (1ll << 21)))
+    return fail(KV_INVALID_ARGUMENT, "sp_ids: %lld values (at most 2^%d per call)", (long long)n, fused ? 23 : 21);
+  if (num_segments < 0 || num_segments > (1ll << 31) - 2) return fail(KV_INVALID_ARGUMENT, "bad num_segments");
+  return KV_OK;
+}
+
+// kv_lookup_sparse behind its checks; the table's mutex is held by the caller, its device is current
+static int lookup_sparse_locked(kv_table* t, const void* ids, const void* segment_ids, int segment_dtype, const float* weights,
+                                int64_t n, int64_t num_segments, int combiner, int count_occurrences, float* out, hipStream_t s) {
+  int rc;
+  const bool fused = fused_tab(t);
+  if ((rc = enter_op(t, s, KEEP_VAR))) return rc;   // the table's own rows and records only
+  const int D = t->dim;
+  if (n == 0) {  // every segment is empty
+    HIP_TRY(hipMemsetAsync(out, 0, (size_t)num_segments * D * sizeof(float), s));
+    return KV_OK;
+  }
+  if ((rc = ensure_capacity(t, n, s))) return rc;
+  if ((rc = ensure_workspace(t, n, false, s))) return rc;
+  if ((rc = ensure_seg(t, num_segments, false, s))) return rc;
+  Workspace& ws = t->ws;
+  // every position's entry in its tile (k_ltile files it for the combiner)
+  if (fused && (rc = ensure_pos_ent(t, n, s))) return rc;
+  WsDev wd = ws_view(t, n);
+  PartArgs pa = self_part_args(t, n);
+  const TableDev& td = pa.tv;
+  pa.day = today(t);
+  pa.count_once = count_occurrences ? 0 : 1;
+  t->batch_serial = 0;
+  if (fused) {
+    // the entry-list kernels: tile pass without rows (entries, every position's entry), the lookup's bookkeeping (which
+    // also publishes the rows of new keys), then the combiner reads position -> entry -> row
+    wd.pos_ent = ws.pos_ent;
+    if ((rc = fused_lookup_pass(t, wd, pa, ids, nullptr, n, -1, nullptr, s, false))) return rc;
+  } else {
+    {
+      ProfScope ps(t, KV_PROF_LOOKUP_TILE, s);
+      launch_tile<false>(t, wd, ids, nullptr, n, s);
+    }
+    ProfScope ps(t, KV_PROF_LOOKUP_PART, s);
+    launch_part_keys<MODE_LOOKUP>(wd, pa, s);
+  }
+  ProfScope ps_gather(t, KV_PROF_LOOKUP_ORDER, s);
+  with_id_type(segment_dtype == KV_DT_INT32, [&](auto id) {
+    using IDT = decltype(id);
+    k_seg_offsets<IDT><<<nblocks(n + 1, TB, 2048), TB, 0, s>>>((const IDT*)segment_ids, n, num_segments, ws.seg_off);
+  });
+  const int q = (D % 4 == 0) ? D / 4 : 0;
+  const bool vec = q > 0 && (q & (q - 1)) == 0 && q <= 64;   // the sorted-position combiner's rows: a power of two of float4, or <0>
+  const int grid = nblocks(num_segments * (fused ? row_lanes(D) : vec ? q : 1), TB, 8192);
+  if (fused)
+    with_lanes(row_lanes(D), [&](auto vq) {
+      k_seg_combine_e<decltype(vq)::value><<<grid, TB, 0, s>>>(td, ws.pos_ent, wd.ent_b, wd.ent_key, ws.seg_off, weights, num_segments, combiner, out);
+    });
+  else if (vec)
+    with_lanes(q, [&](auto vq) {
+      k_seg_combine<decltype(vq)::value><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out);
+    });
+  else
+    k_seg_combine<0><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out);
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+// the expand kernels' lane group: float4 lanes for dims that are a multiple of 4 (64 at the most: wider rows take more
+// than one round), 0 = one thread per element
+static int expand_lanes(int D) { return D % 4 == 0 ? std::min(64, row_lanes(D)) : 0; }
+// f(SegT{}, integral_constant<VQ>) for the expand kernels' template arguments
+template <class F>
+static void with_expand_types(bool int32_seg, int lanes, F&& f) {
+  with_id_type(int32_seg, [&](auto id) {
+    if (lanes == 0) f(id, std::integral_constant<int, 0>{});
+    else with_lanes(lanes, [&](auto vq) { f(id, vq); });
+  });
+}
+
+// kv_lookup_sparse_grad behind its checks (n > 0, num_segments > 0); the table's mutex is held by the caller
+static int lookup_sparse_grad_locked(kv_table* t, const float* seg_grad, const void* segment_ids, int segment_dtype,
+                                     const float* weights, int64_t n, int64_t num_segments, int combiner, float* values,
+                                     hipStream_t s) {
+  int rc;
+  // `t` lends its workspace: neither its rows nor any record is touched
+  if ((rc = enter_op(t, s, KEEP_VAR | KEEP_SLOT))) return rc;
+  const bool need_den = weights != nullptr && combiner != KV_COMBINER_SUM;
+  if ((rc = ensure_seg(t, num_segments, need_den, s))) return rc;
+  Workspace& ws = t->ws;
+  const int D = t->dim;
+  const bool seg32 = segment_dtype == KV_DT_INT32;
+  with_id_type(seg32, [&](auto id) {
+    using IDT = decltype(id);
+    k_seg_offsets<IDT><<<nblocks(n + 1, TB, 2048), TB, 0, s>>>((const IDT*)segment_ids, n, num_segments, ws.seg_off);
+  });
+  if (need_den) k_seg_den<<<nblocks(num_segments, TB, 4096), TB, 0, s>>>(ws.seg_off, weights, num_segments, combiner, ws.seg_den);
+  const int lanes = expand_lanes(D);
+  const int grid = nblocks(n * (lanes ? lanes : D), TB, 16384);
+  with_expand_types(seg32, lanes, [&](auto id, auto vq) {
+    using IDT = decltype(id);
+    k_seg_expand<IDT, decltype(vq)::value><<<grid, TB, 0, s>>>(seg_grad, (const IDT*)segment_ids, ws.seg_off, ws.seg_den, weights, n,
+                                                               num_segments, D, combiner, values);
+  });
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+// what the batched sparse ops check of every table's sizes and pointers beyond multi_common (whose id lists are the ids —
+// forward — or the segment ids — backward).  rows: outs (forward: written whenever the table has segments) or values
+// (backward: written where it has positions too); src: the segment ids (forward) or the segments' gradients (backward).
+// en: the ids per table that take part — none for a table without segments, a no-op as in the single-table ops
+static int multi_sparse_checks(int num_tables, const kv_handle_t* tables, const int64_t* ns, const int64_t* num_segments,
+                               const void* const* rows, bool rows_without_ids, const void* const* src, std::vector<int64_t>* en) {
+  int rc;
+  if (num_tables < 1) return fail(KV_INVALID_ARGUMENT, "N must be >= 1");
+  if (!tables || !ns || !num_segments || !rows || !src) return fail(KV_INVALID_ARGUMENT, "null argument array");
+  en->resize((size_t)num_tables);
+  for (int i = 0; i < num_tables; ++i) {
+    if ((rc = check_table(tables[i]))) return rc;
+    if ((rc = sparse_size_checks(tables[i], ns[i], num_segments[i]))) return rc;
+    const int64_t m = num_segments[i] == 0 ? 0 : ns[i];
+    (*en)[(size_t)i] = m;
+    if ((m > 0 && (!src[i] || !rows[i])) || (rows_without_ids && num_segments[i] > 0 && !rows[i]))
+      return fail(KV_INVALID_ARGUMENT, "segment ids / gradient / output pointer is null");
+  }
+  return KV_OK;
+}
 }  // namespace
 
 namespace __attribute__((visibility("hidden"))) kvhip_internal {
@@ -486,74 +643,178 @@ int kv_lookup_sparse(kv_handle_t t, const void* ids, const void* segment_ids, in
                      float* out, kv_stream_t stream) {
   int rc;
   if ((rc = check_table(t))) return rc;
-  if (combiner < KV_COMBINER_SUM || combiner > KV_COMBINER_SQRTN)
-    return fail(KV_INVALID_ARGUMENT, "combiner must be one of 'mean', 'sqrtn' or 'sum'");  // embedding_ops.py:345
-  if (segment_dtype != KV_DT_INT32 && segment_dtype != KV_DT_INT64)
-    return fail(KV_INVALID_ARGUMENT, "segment ids must be int32 or int64");
-  const bool fused = fused_tab(t);   // (dim is fixed at creation: readable without the lock)
-  if (n < 0 || n > (fused ? FUSED_MAX_N : (1ll << 21)))
-    return fail(KV_INVALID_ARGUMENT, "sp_ids: %lld values (at most 2^%d per call)", (long long)n, fused ? 23 : 21);
-  if (num_segments < 0 || num_segments > (1ll << 31) - 2) return fail(KV_INVALID_ARGUMENT, "bad num_segments");
+  if ((rc = sparse_call_checks(combiner, segment_dtype))) return rc;
+  if ((rc = sparse_size_checks(t, n, num_segments))) return rc;
   if (num_segments == 0) return KV_OK;
   if (!out || (n > 0 && (!ids || !segment_ids))) return fail(KV_INVALID_ARGUMENT, "ids / segment ids / output pointer is null");
   if ((rc = require_initialized(t))) return rc;
   TableOp op(t, stream);
-  const hipStream_t s = op.s;
-  if ((rc = enter_op(t, s, KEEP_VAR))) return rc;   // the table's own rows and records only
-  const int D = t->dim;
-  if (n == 0) {  // every segment is empty
-    HIP_TRY(hipMemsetAsync(out, 0, (size_t)num_segments * D * sizeof(float), s));
+  return lookup_sparse_locked(t, ids, segment_ids, segment_dtype, weights, n, num_segments, combiner, count_occurrences, out, op.s);
+}
+
+int kv_lookup_sparse_grad(kv_handle_t t, const float* seg_grad, const void* segment_ids, int segment_dtype,
+                          const float* weights, int64_t n, int64_t num_segments, int combiner, float* values,
+                          kv_stream_t stream) {
+  int rc;
+  if ((rc = check_table(t))) return rc;
+  if ((rc = sparse_call_checks(combiner, segment_dtype))) return rc;
+  if ((rc = sparse_size_checks(t, n, num_segments))) return rc;
+  if (num_segments == 0 || n == 0) return KV_OK;
+  if (!seg_grad || !segment_ids || !values) return fail(KV_INVALID_ARGUMENT, "gradient / segment ids / output pointer is null");
+  if ((rc = require_initialized(t))) return rc;
+  TableOp op(t, stream);
+  return lookup_sparse_grad_locked(t, seg_grad, segment_ids, segment_dtype, weights, n, num_segments, combiner, values, op.s);
+}
+
+int kv_multi_lookup_sparse(int num_tables, const kv_handle_t* tables, const void* const* ids,
+                           const void* const* segment_ids, int segment_dtype, const float* const* weights,
+                           const int64_t* ns, const int64_t* num_segments, int combiner,
+                           const int* count_occurrences, float* const* outs, kv_stream_t stream) {
+  int rc;
+  if ((rc = sparse_call_checks(combiner, segment_dtype))) return rc;
+  std::vector<int64_t> en;   // ids per table that take part (0 for a table without segments)
+  if ((rc = multi_sparse_checks(num_tables, tables, ns, num_segments, (const void* const*)outs, true, segment_ids, &en))) return rc;
+  if ((rc = multi_common(num_tables, tables, ids, en.data()))) return rc;
+  const int device = tables[0]->device;
+  DeviceGuard dg(device);
+  hipStream_t s = (hipStream_t)stream;
+  MultiLock lock(std::vector<kv_table*>(tables, tables + num_tables));
+  auto wts = [&](int i) { return weights ? weights[i] : nullptr; };
+  auto occ = [&](int i) { return count_occurrences ? count_occurrences[i] : 0; };
+  kv_table* t0 = tables[0];
+  if (!fused_tab(t0)) {
+    // a dim the entry-list kernels do not serve: the single-table path, table by table, under the same locks
+    for (int i = 0; i < num_tables; ++i)
+      if (num_segments[i] > 0 &&
+          (rc = lookup_sparse_locked(tables[i], ids[i], segment_ids[i], segment_dtype, wts(i), ns[i], num_segments[i], combiner,
+                                     occ(i), outs[i], s)))
+        return rc;
     return KV_OK;
   }
-  if ((rc = ensure_capacity(t, n, s))) return rc;
-  if ((rc = ensure_workspace(t, n, false, s))) return rc;
-  Workspace& ws = t->ws;
-  if (ws.seg_cap < num_segments) {
-    if ((rc = ws_sync(s))) return rc;
-    const long long want = std::max<long long>(num_segments, ws.seg_cap * 2);
-    ws.seg_cap = 0;
-    if ((rc = regrow(&ws.seg_off, (size_t)(want + 1)))) return rc;
-    ws.seg_cap = want;
+  if ((rc = lock.enter(s, [](const kv_table*) { return (unsigned)KEEP_VAR; }))) return rc;   // the tables' own rows and records only
+  // every buffer that may have to grow, before anything is queued
+  long long nmax = 0, segmax = 0;
+  for (int i = 0; i < num_tables; ++i) {
+    kv_table* t = tables[i];
+    t->batch_serial = 0;
+    if (num_segments[i] == 0) continue;
+    if ((rc = ensure_capacity(t, en[i], s))) return rc;
+    if ((rc = ensure_workspace(t, std::max<long long>(en[i], 1), false, s))) return rc;
+    if ((rc = ensure_seg(t, num_segments[i], false, s))) return rc;
+    if ((rc = ensure_pos_ent(t, std::max<long long>(en[i], 1), s))) return rc;
+    nmax = std::max<long long>(nmax, en[i]);
+    segmax = std::max<long long>(segmax, num_segments[i]);
   }
-  // every position's entry in its tile (k_ltile files it for the combiner)
-  if (fused && (rc = ensure_pos_ent(t, n, s))) return rc;
-  WsDev wd = ws_view(t, n);
-  PartArgs pa = self_part_args(t, n);
-  const TableDev& td = pa.tv;
-  pa.day = today(t);
-  pa.count_once = count_occurrences ? 0 : 1;
-  t->batch_serial = 0;
-  if (fused) {
-    // the entry-list kernels: tile pass without rows (entries, every position's entry), the lookup's bookkeeping (which
-    // also publishes the rows of new keys), then the combiner reads position -> entry -> row
-    wd.pos_ent = ws.pos_ent;
-    if ((rc = fused_lookup_pass(t, wd, pa, ids, nullptr, n, -1, nullptr, s, false))) return rc;
-  } else {
-    {
-      ProfScope ps(t, KV_PROF_LOOKUP_TILE, s);
-      launch_tile<false>(t, wd, ids, nullptr, n, s);
-    }
-    ProfScope ps(t, KV_PROF_LOOKUP_PART, s);
-    launch_part_keys<MODE_LOOKUP>(wd, pa, s);
+  if (segmax == 0) return KV_OK;
+  Staged<MultiDesc> hd(device, 1, num_tables);
+  if (hd.rc) return hd.rc;
+  Staged<SparseDesc> sd(device, 2, num_tables);
+  if (sd.rc) return sd.rc;
+  WsDev wmax{};
+  for (int i = 0; i < num_tables; ++i) {
+    kv_table* t = tables[i];
+    MultiDesc& d = hd[i];
+    d.w = ws_view(t, std::max<long long>(en[i], 1));
+    use_partitions(d.w, fused_default_P(std::max<long long>(en[i], 1)));
+    d.w.pos_ent = t->ws.pos_ent;
+    d.a = self_part_args(t, en[i]);   // (det: multi_common refuses occurrence-order tables)
+    d.a.day = today(t);
+    d.a.count_once = occ(i) ? 0 : 1;
+    d.ids = ids[i];
+    d.n = en[i];
+    if (en[i] == 0) d.w.ntiles = 0;
+    widen(wmax, d.w);
+    SparseDesc& q = sd[i];
+    q.seg = segment_ids[i];
+    q.wts = en[i] > 0 ? wts(i) : nullptr;   // no ids: zero rows, whatever the weights would divide by
+    q.off = t->ws.seg_off;
+    q.out = outs[i];
+    q.n = en[i];
+    q.nseg = num_segments[i];
+    if (en[i] > 0) t->fused_index = true;
   }
-  ProfScope ps_gather(t, KV_PROF_LOOKUP_ORDER, s);
+  const MultiDesc* md;
+  const SparseDesc* sp;
+  if ((rc = hd.upload(s, &md))) return rc;
+  if ((rc = sd.upload(s, &sp))) return rc;
+  // four launches whatever num_tables is: the tile pass without rows (entries, every position's entry), the lookups'
+  // bookkeeping (which publishes the rows of new keys), the offsets, the combiner
+  if (nmax > 0) {
+    launch_ltile(t0, hd[0].a.tv, wmax, nullptr, nullptr, nmax, nullptr, s, -1, md, num_tables, false);
+    launch_part2(wmax, hd[0].a, s, md, num_tables);
+  }
   with_id_type(segment_dtype == KV_DT_INT32, [&](auto id) {
     using IDT = decltype(id);
-    k_seg_offsets<IDT><<<nblocks(n + 1, TB, 2048), TB, 0, s>>>((const IDT*)segment_ids, n, num_segments, ws.seg_off);
+    k_seg_offsets_multi<IDT><<<dim3((unsigned)nblocks(nmax + 1, TB, 2048), (unsigned)num_tables), TB, 0, s>>>(sp);
   });
-  const int q = (D % 4 == 0) ? D / 4 : 0;
-  const bool vec = q > 0 && (q & (q - 1)) == 0 && q <= 64;   // the sorted-position combiner's rows: a power of two of float4, or <0>
-  const int grid = nblocks(num_segments * (fused ? row_lanes(D) : vec ? q : 1), TB, 8192);
-  if (fused)
-    with_lanes(row_lanes(D), [&](auto vq) {
-      k_seg_combine_e<decltype(vq)::value><<<grid, TB, 0, s>>>(td, ws.pos_ent, wd.ent_b, wd.ent_key, ws.seg_off, weights, num_segments, combiner, out);
-    });
-  else if (vec)
-    with_lanes(q, [&](auto vq) {
-      k_seg_combine<decltype(vq)::value><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out);
-    });
-  else
-    k_seg_combine<0><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out);
+  const int lanes = row_lanes(t0->dim);
+  with_lanes(lanes, [&](auto vq) {
+    k_seg_combine_e_multi<decltype(vq)::value><<<dim3((unsigned)nblocks(segmax * lanes, TB, 8192), (unsigned)num_tables), TB, 0, s>>>(
+        md, sp, combiner);
+  });
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+int kv_multi_lookup_sparse_grad(int num_tables, const kv_handle_t* tables, const float* const* seg_grads,
+                                const void* const* segment_ids, int segment_dtype, const float* const* weights,
+                                const int64_t* ns, const int64_t* num_segments, int combiner,
+                                float* const* values, kv_stream_t stream) {
+  int rc;
+  if ((rc = sparse_call_checks(combiner, segment_dtype))) return rc;
+  std::vector<int64_t> en;
+  if ((rc = multi_sparse_checks(num_tables, tables, ns, num_segments, (const void* const*)values, false,
+                                (const void* const*)seg_grads, &en)))
+    return rc;
+  if (!segment_ids) return fail(KV_INVALID_ARGUMENT, "null argument array");
+  if ((rc = multi_common(num_tables, tables, segment_ids, en.data()))) return rc;   // (its id lists: the segment ids)
+  const int device = tables[0]->device;
+  DeviceGuard dg(device);
+  hipStream_t s = (hipStream_t)stream;
+  MultiLock lock(std::vector<kv_table*>(tables, tables + num_tables));
+  // the tables lend their workspaces: neither rows nor records are touched
+  if ((rc = lock.enter(s, [](const kv_table*) { return (unsigned)(KEEP_VAR | KEEP_SLOT); }))) return rc;
+  auto wts = [&](int i) { return weights ? weights[i] : nullptr; };
+  long long nmax = 0, segmax = 0;
+  bool any_den = false;
+  for (int i = 0; i < num_tables; ++i) {
+    if (en[i] == 0) continue;
+    const bool need_den = wts(i) != nullptr && combiner != KV_COMBINER_SUM;
+    if ((rc = ensure_seg(tables[i], num_segments[i], need_den, s))) return rc;
+    any_den |= need_den;
+    nmax = std::max<long long>(nmax, en[i]);
+    segmax = std::max<long long>(segmax, num_segments[i]);
+  }
+  if (nmax == 0) return KV_OK;
+  Staged<SparseDesc> sd(device, 2, num_tables);
+  if (sd.rc) return sd.rc;
+  for (int i = 0; i < num_tables; ++i) {
+    SparseDesc& q = sd[i];
+    if (en[i] == 0) continue;   // (zeroed: nseg == 0, no part in the launches)
+    q.seg = segment_ids[i];
+    q.wts = wts(i);
+    q.off = tables[i]->ws.seg_off;
+    q.den = tables[i]->ws.seg_den;
+    q.seg_grad = seg_grads[i];
+    q.out = values[i];
+    q.n = en[i];
+    q.nseg = num_segments[i];
+  }
+  const SparseDesc* sp;
+  if ((rc = sd.upload(s, &sp))) return rc;
+  // at most three launches: the offsets, the weighted denominators (if any table has them), the expand
+  const bool seg32 = segment_dtype == KV_DT_INT32;
+  const int D = tables[0]->dim;
+  with_id_type(seg32, [&](auto id) {
+    using IDT = decltype(id);
+    k_seg_offsets_multi<IDT><<<dim3((unsigned)nblocks(nmax + 1, TB, 2048), (unsigned)num_tables), TB, 0, s>>>(sp);
+  });
+  if (any_den) k_seg_den_multi<<<dim3((unsigned)nblocks(segmax, TB, 4096), (unsigned)num_tables), TB, 0, s>>>(sp, combiner);
+  const int lanes = expand_lanes(D);
+  const dim3 grid((unsigned)nblocks(nmax * (lanes ? lanes : D), TB, 16384), (unsigned)num_tables);
+  with_expand_types(seg32, lanes, [&](auto id, auto vq) {
+    k_seg_expand_multi<decltype(id), decltype(vq)::value><<<grid, TB, 0, s>>>(sp, D, combiner);
+  });
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }

@@ -866,7 +866,7 @@ std::atomic<uint64_t> g_uid{0};
 
 // descriptor staging for the batched launches: one pinned host buffer + device buffer per device
 // and descriptor kind; the next upload waits until the previous launch has consumed the buffer
-BatchStage g_stage[64][2];   // [device][0 = inference gather, 1 = training ops]
+BatchStage g_stage[64][3];   // [device][0 = inference gather, 1 = training ops, 2 = the sparse lookups' own descriptors]
 
 // returns with st.mu HELD (released by ~Staged after `consumed` is recorded on the stream)
 int stage_take(BatchStage& st, size_t bytes, StageSlot** out) {
@@ -1041,7 +1041,7 @@ int kv_destroy(kv_handle_t t) {
   hipFree(w.ent_key); hipFree(w.ent_a); hipFree(w.ent_b); hipFree(w.ent_base); hipFree(w.ent_rec); hipFree(w.toff); hipFree(w.slot_rank);
   hipFree(w.order); hipFree(w.coldlist); hipFree(w.hotlist); hipFree(w.litem); hipFree(w.items); hipFree(w.pmeta); hipFree(w.hpart);
   hipFree(w.mcount); hipFree(w.epart); hipFree(w.pos_ent);
-  hipFree(w.ctr); hipFree(w.dbg); hipFree(w.scat_keys); hipFree(w.scat_sum); hipFree(w.seg_off);
+  hipFree(w.ctr); hipFree(w.dbg); hipFree(w.scat_keys); hipFree(w.scat_sum); hipFree(w.seg_off); hipFree(w.seg_den);
   if (t->err_host) hipHostFree(t->err_host);
   if (t->cnt_host) hipHostFree(t->cnt_host);
   if (t->last_done) hipEventDestroy(t->last_done);

@@ -122,6 +122,50 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, partition_strategy="mod"
   return summed / torch.sqrt(_segment_sum(wts * wts, seg, nseg))
 
 
+def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None, combiner=None, max_norm=None):
+  """[embedding_lookup_sparse(p, i, w, combiner=combiner) for p, i, w in zip(...)] — one KvVariable per feature — with
+  the features that take the fused path grouped by (device, dim, key dtype): one batched forward per group
+  (kv_multi_lookup_sparse: four launches whatever the group's size) under one autograd function, whose backward is one
+  kv_multi_lookup_sparse_grad per group and files one IndexedSlices on each variable.  A feature the fused path does not
+  take — a partitioned variable, max_norm, inference mode, more ids than one call takes, a variable some earlier feature
+  of its group already uses — goes through embedding_lookup_sparse as it is."""
+  if combiner is None:
+    combiner = "mean"
+  if combiner not in ("mean", "sqrtn", "sum"):
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  nf = len(params_list)
+  if sp_weights_list is None:
+    sp_weights_list = [None] * nf
+  if nf != len(sp_ids_list) or nf != len(sp_weights_list):
+    raise ValueError("params_list, sp_ids_list (and sp_weights_list) must be equally long")
+  out = [None] * nf
+  groups = collections.OrderedDict()   # (device, dim, key dtype, takes gradients) -> [(feature, var, ids, seg, weights, nseg)]
+  for f, (params, sp_ids, sp_w) in enumerate(zip(params_list, sp_ids_list, sp_weights_list)):
+    plist = _as_list(params)
+    if not isinstance(sp_ids, SparseTensor):
+      raise TypeError("sp_ids must be SparseTensor")
+    if sp_w is not None and not isinstance(sp_w, SparseTensor):
+      raise TypeError("sp_weights must be either None or SparseTensor")
+    var = plist[0]
+    n = torch.as_tensor(sp_ids.values).numel()
+    fused = (len(plist) == 1 and max_norm is None and kv_variable_ops.IS_TRAINING and hasattr(var, "lookup_sparse")
+             and 0 < n <= (1 << 21))
+    key = (var.device, var.embedding_dim, var.key_dtype, var.trainable) if fused else None
+    if not fused or any(e[1] is var for e in groups.get(key, ())):
+      out[f] = embedding_lookup_sparse(plist, sp_ids, sp_w, combiner=combiner, max_norm=max_norm)
+      continue
+    seg = torch.as_tensor(sp_ids.indices).to(var.device)[:, 0].to(torch.int64)
+    groups.setdefault(key, []).append((f, var, torch.as_tensor(sp_ids.values).to(var.device), seg,
+                                       None if sp_w is None else sp_w.values, int(seg.max().item()) + 1))
+  for members in groups.values():
+    res = kv_variable_ops.lookup_sparse_multi([m[1] for m in members], [m[2] for m in members], [m[3] for m in members],
+                                              [m[4] for m in members], [m[5] for m in members], combiner,
+                                              [m[1].enter_threshold > 0 for m in members])
+    for m, r in zip(members, res):
+      out[m[0]] = r
+  return out
+
+
 def safe_embedding_lookup_sparse(embedding_weights, sparse_ids, sparse_weights=None, combiner=None,
                                  default_id=None, name=None, partition_strategy="mod", max_norm=None):
   """embedding_ops.py:444-628.  For KvVariables ids < 0 are ordinary keys and are NOT pruned

@@ -721,21 +721,99 @@ def kv_variable_lookup_sparse(table_handle, ids, segment_ids, weights, num_segme
   if combiner not in _COMBINERS:
     raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
   ids = _ids(table_handle, ids).reshape(-1)
+  seg, w = _sparse_args(table_handle, ids.numel(), segment_ids, weights)
+  out = torch.empty((int(num_segments), table_handle.dim), dtype=torch.float32, device=_dev(table_handle))
+  _lib.check(_lib.lib().kv_lookup_sparse(table_handle.ptr, _p(ids), _p(seg), _TORCH_KEY[seg.dtype], _p(w),
+                                         ids.numel(), int(num_segments), _COMBINERS[combiner],
+                                         int(bool(count_occurrences)), _p(out), _stream(table_handle)))
+  return out
+
+
+def _sparse_args(table_handle, n, segment_ids, weights):
+  """segment ids (int32 / int64, flat) and weights (fp32, flat, or None) of a sparse lookup over n ids, on the table's
+  device; the argument errors of kv_variable_lookup_sparse."""
   dev = _dev(table_handle)
   seg = torch.as_tensor(segment_ids).to(dev).reshape(-1)
   if seg.dtype not in _TORCH_KEY:
     seg = seg.to(torch.int64)
   seg = seg.contiguous()
-  if seg.numel() != ids.numel():
+  if seg.numel() != n:
     raise _lib.InvalidArgumentError("segment_ids and ids must have the same length")
   w = None if weights is None else _f32(table_handle, weights).reshape(-1)
-  if w is not None and w.numel() != ids.numel():
+  if w is not None and w.numel() != n:
     raise _lib.InvalidArgumentError("sp_weights and sp_ids must have the same number of values")
-  out = torch.empty((int(num_segments), table_handle.dim), dtype=torch.float32, device=dev)
-  _lib.check(_lib.lib().kv_lookup_sparse(table_handle.ptr, _p(ids), _p(seg), _TORCH_KEY[seg.dtype], _p(w),
-                                         ids.numel(), int(num_segments), _COMBINERS[combiner],
-                                         int(bool(count_occurrences)), _p(out), _stream(table_handle)))
+  return seg, w
+
+
+def kv_variable_lookup_sparse_grad(table_handle, seg_grad, segment_ids, weights, num_segments, combiner="mean"):
+  """The backward of kv_variable_lookup_sparse: values [n, dim] with values[j] = scale_j * seg_grad[segment_ids[j]]
+  (scale_j = w_j, w_j / sum_segment(w) or w_j / sqrt(sum_segment(w^2))) — the IndexedSlices values that go with the
+  lookup's ids.  seg_grad is [num_segments, dim]; one native call, defined bit for bit (kvhip.h kv_lookup_sparse_grad)."""
+  if combiner not in _COMBINERS:
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  n = torch.as_tensor(segment_ids).numel()
+  seg, w = _sparse_args(table_handle, n, segment_ids, weights)
+  g = _f32(table_handle, seg_grad).reshape(-1, table_handle.dim)
+  if g.shape[0] != int(num_segments):
+    raise _lib.InvalidArgumentError("seg_grad must have num_segments rows")
+  out = torch.empty((n, table_handle.dim), dtype=torch.float32, device=g.device)
+  _lib.check(_lib.lib().kv_lookup_sparse_grad(table_handle.ptr, _p(g), _p(seg), _TORCH_KEY[seg.dtype], _p(w), n,
+                                              int(num_segments), _COMBINERS[combiner], _p(out), _stream(table_handle)))
   return out
+
+
+def _multi_sparse_args(table_handles, ns, segment_ids, weights, num_segments, combiner):
+  """What the two batched sparse ops share: lengths, combiner, one segment dtype for the call, the C arrays."""
+  n = len(table_handles)
+  if combiner not in _COMBINERS:
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  if n < 1 or n != len(segment_ids) or n != len(num_segments) or n != len(ns) or (weights is not None and len(weights) != n):
+    raise _lib.InvalidArgumentError("table_handles, ids, segment_ids, num_segments (and weights) must be equally long, N >= 1")
+  sw = [_sparse_args(h, m, s, None if weights is None else weights[k])
+        for k, (h, m, s) in enumerate(zip(table_handles, ns, segment_ids))]
+  seg = [s for s, _ in sw]
+  if len({s.dtype for s in seg}) > 1:   # one dtype per call
+    seg = [s.to(torch.int64) for s in seg]
+  w = [x for _, x in sw]
+  hp = (ctypes.c_void_p * n)(*[h.ptr for h in table_handles])
+  return (seg, w, hp, _ptr_array(seg), _TORCH_KEY[seg[0].dtype], _ptr_array(w), (ctypes.c_int64 * n)(*ns),
+          (ctypes.c_int64 * n)(*[int(x) for x in num_segments]))
+
+
+def kv_multi_lookup_sparse(table_handles, ids, segment_ids, weights, num_segments, combiner="mean", count_occurrences=None):
+  """[kv_variable_lookup_sparse(t, i, s, w, n, combiner, c) for ...] with four kernel launches for all tables (same dim
+  and key dtype; other dims than the multiples of 4 up to 256 loop inside the call).  weights: None, or a list whose
+  entries may be None; count_occurrences: None (False for every table) or one flag per table.  Returns the list of
+  [num_segments[i], dim] outputs."""
+  n = len(table_handles)
+  if n != len(ids) or (count_occurrences is not None and len(count_occurrences) != n):
+    raise _lib.InvalidArgumentError("table_handles, ids (and count_occurrences) must be equally long, N >= 1")
+  idl = [_ids(h, i).reshape(-1) for h, i in zip(table_handles, ids)]
+  seg, w, hp, segp, segdt, wp, ns, nsegs = _multi_sparse_args(table_handles, [i.numel() for i in idl], segment_ids, weights,
+                                                            num_segments, combiner)
+  outs = [torch.empty((int(m), h.dim), dtype=torch.float32, device=_dev(h)) for h, m in zip(table_handles, num_segments)]
+  occ = None if count_occurrences is None else (ctypes.c_int * n)(*[int(bool(c)) for c in count_occurrences])
+  _lib.check(_lib.lib().kv_multi_lookup_sparse(n, hp, _ptr_array(idl), segp, segdt, wp, ns, nsegs, _COMBINERS[combiner], occ,
+                                               _ptr_array(outs), _stream(table_handles[0])))
+  return outs
+
+
+def kv_multi_lookup_sparse_grad(table_handles, seg_grads, segment_ids, weights, num_segments, combiner="mean"):
+  """[kv_variable_lookup_sparse_grad(t, g, s, w, n, combiner) for ...] with at most three kernel launches for all tables
+  (same dim and key dtype, any dim).  Returns the list of [n_i, dim] values."""
+  n = len(table_handles)
+  if n != len(seg_grads):
+    raise _lib.InvalidArgumentError("table_handles and seg_grads must be equally long, N >= 1")
+  lens = [torch.as_tensor(s).numel() for s in segment_ids]
+  seg, w, hp, segp, segdt, wp, ns, nsegs = _multi_sparse_args(table_handles, lens, segment_ids, weights, num_segments, combiner)
+  gr = [_f32(h, g).reshape(-1, h.dim) for h, g in zip(table_handles, seg_grads)]
+  for g, m in zip(gr, num_segments):
+    if g.shape[0] != int(m):
+      raise _lib.InvalidArgumentError("seg_grad must have num_segments rows")
+  outs = [torch.empty((m, h.dim), dtype=torch.float32, device=_dev(h)) for h, m in zip(table_handles, lens)]
+  _lib.check(_lib.lib().kv_multi_lookup_sparse_grad(n, hp, _ptr_array(gr), segp, segdt, wp, ns, nsegs, _COMBINERS[combiner],
+                                                    _ptr_array(outs), _stream(table_handles[0])))
+  return outs
 
 
 def kv_unsorted_segment_sum(table_handle, data, segment_ids, num_segments):

@@ -47,8 +47,9 @@ class _GatherGrad(torch.autograd.Function):
 class _SparseLookupGrad(torch.autograd.Function):
   """Fused embedding_lookup_sparse.  Gradient as TF builds it through gather / multiply /
   segment_sum: IndexedSlices(values[j] = scale_j * grad[segment_j], indices = ids) with scale_j =
-  w_j (sum), w_j / sum_segment(w) (mean), w_j / sqrt(sum_segment(w^2)) (sqrtn); no gradient flows
-  to sp_weights here."""
+  w_j (sum), w_j / sum_segment(w) (mean), w_j / sqrt(sum_segment(w^2)) (sqrtn), in one native call
+  (kv_lookup_sparse_grad: the denominators summed in position order like the forward's); no gradient
+  flows to sp_weights here."""
 
   @staticmethod
   def forward(ctx, anchor, var, ids, seg, weights, nseg, combiner, count_occurrences):
@@ -58,20 +59,46 @@ class _SparseLookupGrad(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, grad):
-    var, ids, seg, w = ctx.var, ctx.ids, ctx.seg.to(torch.int64), ctx.weights
-    n = ids.numel()
-    wj = torch.ones(n, dtype=grad.dtype, device=grad.device) if w is None else w.to(grad.dtype)
-    if ctx.combiner == "mean":
-      den = torch.zeros(ctx.nseg, dtype=grad.dtype, device=grad.device).index_add_(0, seg, wj)
-      scale = wj / den.index_select(0, seg)
-    elif ctx.combiner == "sqrtn":
-      den = torch.zeros(ctx.nseg, dtype=grad.dtype, device=grad.device).index_add_(0, seg, wj * wj).sqrt()
-      scale = wj / den.index_select(0, seg)
-    else:
-      scale = wj
-    vals = grad.reshape(ctx.nseg, -1).index_select(0, seg) * scale.unsqueeze(1)
-    var._pending_grads.append(IndexedSlices(vals.contiguous(), ids.reshape(-1), None))
+    var, ids = ctx.var, ctx.ids
+    vals = gen_kv_variable_ops.kv_variable_lookup_sparse_grad(var.handle, grad.reshape(ctx.nseg, -1), ctx.seg, ctx.weights,
+                                                              ctx.nseg, ctx.combiner)
+    var._pending_grads.append(IndexedSlices(vals, ids.reshape(-1), None))
     return None, None, None, None, None, None, None, None
+
+
+class _MultiSparseLookupGrad(torch.autograd.Function):
+  """_SparseLookupGrad over the KvVariables of one (device, dim, key dtype) group: the batched forward
+  (kv_multi_lookup_sparse), and ONE kv_multi_lookup_sparse_grad in the backward, which files one IndexedSlices on each
+  variable."""
+
+  @staticmethod
+  def forward(ctx, anchor, vars_, ids, segs, weights, nsegs, combiner, count_occurrences):
+    ctx.vars, ctx.ids, ctx.segs, ctx.weights, ctx.nsegs, ctx.combiner = vars_, ids, segs, weights, nsegs, combiner
+    return tuple(gen_kv_variable_ops.kv_multi_lookup_sparse([v.handle for v in vars_], ids, segs, weights, nsegs, combiner,
+                                                            count_occurrences))
+
+  @staticmethod
+  def backward(ctx, *grads):
+    vals = gen_kv_variable_ops.kv_multi_lookup_sparse_grad(
+        [v.handle for v in ctx.vars], [g.reshape(m, -1) for g, m in zip(grads, ctx.nsegs)], ctx.segs, ctx.weights, ctx.nsegs,
+        ctx.combiner)
+    for var, v, ids in zip(ctx.vars, vals, ctx.ids):
+      var._pending_grads.append(IndexedSlices(v, ids.reshape(-1), None))
+    return None, None, None, None, None, None, None, None
+
+
+def lookup_sparse_multi(vars_, ids, segment_ids, weights, num_segments, combiner, count_occurrences):
+  """KvVariable.lookup_sparse over KvVariables of one device, dim and key dtype (each listed once; training mode only):
+  the list of their [num_segments[i], dim] outputs."""
+  dev = vars_[0].device
+  ids = [torch.as_tensor(i).to(dev).reshape(-1) for i in ids]
+  segs = [torch.as_tensor(s).to(dev).reshape(-1) for s in segment_ids]
+  ws = [None if w is None else torch.as_tensor(w, dtype=torch.float32).to(dev).reshape(-1) for w in weights]
+  nsegs = [int(m) for m in num_segments]
+  occ = [bool(c) for c in count_occurrences]
+  if torch.is_grad_enabled() and all(v.trainable for v in vars_):
+    return list(_MultiSparseLookupGrad.apply(vars_[0]._anchor, list(vars_), ids, segs, ws, nsegs, combiner, occ))
+  return gen_kv_variable_ops.kv_multi_lookup_sparse([v.handle for v in vars_], ids, segs, ws, nsegs, combiner, occ)
 
 
 class KvVariable(object):
