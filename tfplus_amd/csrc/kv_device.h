@@ -265,13 +265,22 @@ claimed:
 
 // kv_variable.h:889-898 GenerateRandomInitialValue: row = 0.5 * (T[r1] + T[r2]).  The
 // reference draws r1, r2 from std::rand(); here they are a hash of (key, seed) so a run is
-// reproducible.  Executed by `lanes` cooperating lanes (lane = 0..lanes-1).  Returns
+// reproducible.  init_rule_rows: the two rows of the init table for `key`.
+// (D = t.dim, handed over by init_var_row, which holds it in a register as the apply bodies always did)
+__device__ __forceinline__ void init_rule_rows(const TableDev& t, long long key, const float** ia, const float** ib, int D) {
+  const unsigned long long h = pick64((unsigned long long)key ^ (t.seed * 0x9E3779B97F4A7C15ULL));
+  *ia = t.init_table + (size_t)((unsigned)h % t.init_rows) * D;
+  *ib = t.init_table + (size_t)((unsigned)(h >> 32) % t.init_rows) * D;
+}
+__device__ __forceinline__ void init_rule_rows(const TableDev& t, long long key, const float** ia, const float** ib) {
+  init_rule_rows(t, key, ia, ib, t.dim);
+}
+// The init rule's row written to dst by `lanes` cooperating lanes (lane = 0..lanes-1).  Returns
 // whether this lane saw any |x| >= CUTOFF.
 __device__ __forceinline__ bool init_row_coop(const TableDev& t, long long key, float* dst,
                                               int lane, int lanes) {
-  unsigned long long h = pick64((unsigned long long)key ^ (t.seed * 0x9E3779B97F4A7C15ULL));
-  const float* a = t.init_table + (size_t)((unsigned)h % t.init_rows) * t.dim;
-  const float* b = t.init_table + (size_t)((unsigned)(h >> 32) % t.init_rows) * t.dim;
+  const float *a, *b;
+  init_rule_rows(t, key, &a, &b);
   bool big = false;
   for (int e = lane; e < t.dim; e += lanes) {
     float v = (a[e] + b[e]) * 0.5f;
@@ -804,16 +813,8 @@ __device__ __forceinline__ void opt_update_row(const TableDev& tv, const TableDe
 
   // new slot rows are initialised in registers with the slot table's init rule
   const float *ia0 = nullptr, *ib0 = nullptr, *ia1 = nullptr, *ib1 = nullptr;
-  if (act && new0) {
-    unsigned long long h = pick64((unsigned long long)key ^ (ts0.seed * 0x9E3779B97F4A7C15ULL));
-    ia0 = ts0.init_table + (size_t)((unsigned)h % ts0.init_rows) * ts0.dim;
-    ib0 = ts0.init_table + (size_t)((unsigned)(h >> 32) % ts0.init_rows) * ts0.dim;
-  }
-  if (two_slots(OPT) && act && new1) {
-    unsigned long long h = pick64((unsigned long long)key ^ (ts1.seed * 0x9E3779B97F4A7C15ULL));
-    ia1 = ts1.init_table + (size_t)((unsigned)h % ts1.init_rows) * ts1.dim;
-    ib1 = ts1.init_table + (size_t)((unsigned)(h >> 32) % ts1.init_rows) * ts1.dim;
-  }
+  if (act && new0) init_rule_rows(ts0, key, &ia0, &ib0);
+  if (two_slots(OPT) && act && new1) init_rule_rows(ts1, key, &ia1, &ib1);
   constexpr int NS0 = slot0_blocks(OPT), NSB = state_blocks(OPT);
   float xin[K][V], sin[NSB][K][V];
 #pragma unroll

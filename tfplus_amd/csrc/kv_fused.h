@@ -289,9 +289,9 @@ __device__ __forceinline__ void ltile_body(const TableDev& t, const WsDev& w, co
               const unsigned rj = __shfl(rr[k], (j0 + j) * RW + sub);
               const long long kj = __shfl(kreg[k], (j0 + j) * RW + sub);
               if (rj & NEW_BIT) {
-                const unsigned long long h = pick64((unsigned long long)kj ^ (t.seed * 0x9E3779B97F4A7C15ULL));
-                const float4 a = reinterpret_cast<const float4*>(t.init_table + (size_t)((unsigned)h % t.init_rows) * t.dim)[vv];
-                const float4 b = reinterpret_cast<const float4*>(t.init_table + (size_t)((unsigned)(h >> 32) % t.init_rows) * t.dim)[vv];
+                const float *ia, *ib;
+                init_rule_rows(t, kj, &ia, &ib);
+                const float4 a = reinterpret_cast<const float4*>(ia)[vv], b = reinterpret_cast<const float4*>(ib)[vv];
                 val[j] = make_float4((a.x + b.x) * 0.5f, (a.y + b.y) * 0.5f, (a.z + b.z) * 0.5f, (a.w + b.w) * 0.5f);
               }
             }
@@ -738,9 +738,7 @@ __device__ __forceinline__ void part2_body(const WsDev& w, const PartArgs& a) {
         mark_delta(a.tv, r[k]);
         // find_func / insert_func (kv_variable.h:320-363)
         const unsigned cnt = a.count_once ? 1u : hval[s];
-        unsigned lo = (m[k].x & 0xFFFFu) + (cnt > 65535u ? 65535u : cnt);
-        if (lo > 65535u) lo = 65535u;
-        mp->freq = (a.day << 16) | lo;
+        mp->freq = (a.day << 16) | freq_add_sat(m[k].x, cnt);
         if (isnew[k]) mp->flags = (unsigned char)FLAG_DIRTY;
         if (m[k].y & FLAG_DIRTY) lnew[atomicAdd(&lnnew, 1u)] = (unsigned short)(s | (isnew[k] ? 0x8000u : 0u));
       }

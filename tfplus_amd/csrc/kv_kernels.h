@@ -1,4 +1,6 @@
-// kv_kernels.h — the batch pipeline (included by kvhip.hip and the instantiation units: kv_opt_unit.h, kv_sums.hip).
+// kv_kernels.h — the sorted-position batch pipeline, the one fallback, and nothing else (included by
+// kvhip.hip and the instantiation units: kv_opt_unit.h, kv_sums.hip).  What its apply kernels do to ONE key's state —
+// resolve_rows, prefetch_state, finish_key — is kv_key_update.h, included in front of this file.
 //
 // Why this shape.  A device-scope atomic on ONE address costs ~40 ns on MI355X and same-address
 // atomics serialise; a Zipf(1.2) batch of 1 M ids has ~100 keys that occur in (nearly) every tile, so
@@ -671,9 +673,7 @@ __device__ __forceinline__ void part_keys_body(const WsDev& w, const PartArgs& a
           // hi16 = today; UpdateUnderThreshold only has work to do when the row changed since the
           // flag was computed (FLAG_DIRTY) or the row is new — every other writer keeps it current
           const unsigned cnt = a.count_once ? 1u : hval[s];
-          unsigned lo = (m[k].x & 0xFFFFu) + (cnt > 65535u ? 65535u : cnt);
-          if (lo > 65535u) lo = 65535u;
-          mp->freq = (a.day << 16) | lo;
+          mp->freq = (a.day << 16) | freq_add_sat(m[k].x, cnt);
           if (isnew[k]) mp->flags = (unsigned char)FLAG_DIRTY;
           if (m[k].y & FLAG_DIRTY) lnew[atomicAdd(&lnnew, 1u)] = (unsigned short)(s | (isnew[k] ? 0x8000u : 0u));
         } else if (MODE == MODE_APPLYIDX) {
@@ -1159,137 +1159,6 @@ __device__ __forceinline__ void occ_sum_body(const WsDev& w, const PartArgs& a, 
 }
 template <int NC>
 __global__ void __launch_bounds__(OCC_TB) k_occ_sum(WsDev w, PartArgs a, int fop) { occ_sum_body<NC>(w, a, fop); }
-
-// The slot-table rows of one key, resolved by the group leader.  FindOrInsertUnsafe(var, filter_out !=
-// nullptr) kv_variable.h:382-408 and FindOrInsertUnsafe(slot, nullptr) :409-414; FTRL probes linear
-// before accum (training_ops.cc:701-704).  `m0` is the record of the hinted slot row (requested early).
-struct RowsOf { unsigned tag, r0, r1, nb; };   // nb: bit 1 / 2 = slot row 0 / 1 inserted now, bit 3 = slot row 0 is the hinted one
-template <int OPT>
-__device__ __forceinline__ RowsOf resolve_rows(const PartArgs& a, long long key, unsigned rvw, unsigned hint,
-                                               bool hint_loaded, const RowMeta& m0) {
-  const unsigned rv = rvw & ROW_MASK;
-  const bool vnew = (rvw >> 31) != 0u;   // inserted by this apply: not filtered (kv_variable.h:400-407, succ == false)
-  RowsOf o{rv, 0u, 0u, 0u};
-  if (rv == 0u) return o;
-  // the var record is only needed for the frequency filter: a blacklisted row is all zeros already
-  // (RemoveBlacklistUnsafe hands out a zero row, table_manager.h:359-372) and the group optimizers
-  // rewrite the flags after the update, so with enter_threshold == 0 they never read it
-  const bool need_vmeta = keeps_var_flags(OPT) || a.tv.enter_threshold != 0u;
-  if (need_vmeta && !vnew) {
-    const uint2 mv = load_freq_flags(a.tv, rv);
-    if ((mv.x & 0xFFFFu) < a.tv.enter_threshold) { o.tag = rv | ROW_FILTERED; return o; }  // kv_variable.h:910
-    if (mv.y & FLAG_BLACK) meta_ptr(a.tv, rv)->flags = FLAG_UNDER;   // RemoveBlacklistUnsafe: fresh zero row (ours already is)
-  }
-  // slot rows are only created for keys the update will touch (filtered keys returned above)
-  bool hinted = false;
-  auto slot_row = [&](const TableDev& t, bool use_hint, bool* isnew) -> unsigned {
-    *isnew = false;
-    unsigned r = 0, f = 0;
-    if (use_hint && hint_loaded && m0.key == key && !(m0.flags & FLAG_FREE)) {
-      r = hint; f = m0.freq; hinted = true;
-    } else {
-      r = table_find(t, key);
-      if (__builtin_expect(r == 0u, 0)) {
-        r = table_find_or_insert(t, key, isnew);
-        if (r && *isnew) { RowMeta* m = meta_ptr(t, r); m->freq = 1u; m->flags = 0; }
-      }
-      if (r && !*isnew) f = meta_ptr(t, r)->freq;
-      if (use_hint && r) {   // remember it in the var's index entry
-        Entry* e = table_entry_of(a.tv, key);
-        if (e) e->hint = r;
-      }
-    }
-    // AddFrequency(1, today) on a slot row that already existed (kv_variable.h:409-414); a new one keeps word 1
-    if (r && !*isnew) {
-      unsigned lo = (f & 0xFFFFu) + 1u;
-      if (lo > 65535u) lo = 65535u;
-      *freq_ptr(t, r) = (a.day << 16) | lo;
-    }
-    return r;
-  };
-  bool new0 = false, new1 = false;
-  if (two_slots(OPT)) o.r1 = slot_row(a.ts1, false, &new1);
-  o.r0 = slot_row(a.ts0, a.use_hints != 0, &new0);
-  // MarkAsDeltaListElements on every table of the op, for the keys the update reaches (training_ops.cc:7196-7201)
-  if (__builtin_expect(a.tv.track_delta | a.ts0.track_delta | (two_slots(OPT) ? a.ts1.track_delta : 0u), 0)) {
-    mark_delta(a.tv, rv);
-    if (o.r0) mark_delta(a.ts0, o.r0);
-    if (two_slots(OPT) && o.r1) mark_delta(a.ts1, o.r1);
-  }
-  o.nb = (new0 ? 2u : 0u) | (new1 ? 4u : 0u) | (hinted ? 8u : 0u);
-  return o;
-}
-
-// Everything the update of one key needs besides its gradient, requested in ONE round trip: the var row, the
-// hinted slot row and that row's own record (the hint is validated against it in resolve_rows).  Without this the
-// finish walks slot index -> slot record -> rows, three dependent hops.  Called by the LPR lanes of the key's group.
-template <int OPT, int V, int LPR, int K>
-__device__ __forceinline__ void prefetch_state(const PartArgs& a, const uint4& ra, bool live, int lane, int D, RowMeta& m0,
-                                               bool& hint_loaded, PreRows<OPT, V, K>& pre, bool& have_x, bool& have_s) {
-  hint_loaded = false; have_x = false; have_s = false;
-  if (!live || (ra.z & ROW_MASK) == 0u) return;
-  const bool hok = a.use_hints && ra.w != 0u && ra.w < a.ts0.max_rows;
-  if (lane == 0 && hok) {
-    const uint4 mm = *reinterpret_cast<const uint4*>(meta_ptr(a.ts0, ra.w));
-    m0.key = (long long)(((unsigned long long)mm.y << 32) | mm.x);
-    m0.freq = mm.z;
-    m0.flags = (unsigned char)(mm.w & 0xFFu);
-    hint_loaded = true;
-  }
-  const float* xr = row_ptr(a.tv, ra.z & ROW_MASK);
-  const float* sr = hok ? row_ptr(a.ts0, ra.w) : nullptr;
-  constexpr int NS0 = slot0_blocks(OPT);
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const int e0 = (lane + k * LPR) * V;
-    if (e0 < D) {
-      ldv<V>(xr + e0, pre.x[k]);
-      if (hok) {
-#pragma unroll
-        for (int b3 = 0; b3 < NS0; ++b3) ldv<V>(sr + e0 + b3 * D, pre.s[b3][k]);
-      }
-    }
-  }
-  have_x = true; have_s = hok;
-}
-
-// finish one key whose combined gradient is in gv: optimizer update (MODE_APPLY) or emit (MODE_DEDUP).
-// All LPR lanes of every group of the wave call it (shuffles inside); `live` masks groups without a key.
-// hd = {key lo, key hi, row word, slot-row hint}
-template <int MODE, int OPT, int V, int LPR, int K>
-__device__ __forceinline__ void finish_key(const PartArgs& a, const uint4 hd, bool live, bool hint_loaded,
-                                           const RowMeta& m0, float (&gv)[K][V], int lane,
-                                           const PreRows<OPT, V, K>* pre = nullptr, bool have_x = false, bool have_s = false) {
-  const int D = a.tv.dim;
-  const long long key = (long long)(((unsigned long long)hd.y << 32) | hd.x);
-  if (MODE == MODE_APPLY) {
-    RowsOf ro{0u, 0u, 0u, 0u};
-    if (live && lane == 0) ro = resolve_rows<OPT>(a, key, hd.z, hd.w, hint_loaded, m0);
-    if (LPR > 1) {
-      ro.tag = __shfl(ro.tag, 0, LPR); ro.r0 = __shfl(ro.r0, 0, LPR);
-      ro.r1 = __shfl(ro.r1, 0, LPR); ro.nb = __shfl(ro.nb, 0, LPR);
-    }
-    // the slot rows in `pre` are those of the hinted row: good only if the hint stood up
-    opt_update_row<OPT, V, LPR, K>(a.tv, a.ts0, a.ts1, key, ro.tag, ro.r0, (ro.nb & 2u) != 0, ro.r1, (ro.nb & 4u) != 0,
-                                   live, gv, a.opt, lane, pre, have_x, have_s && (ro.nb & 8u) != 0);
-    // the key's slot record as this update left it goes into the var row's mirror (clean: the slot table's own record is
-    // up to date), so that the key's NEXT apply takes the lean path without reading it
-    if (!two_slots(OPT) && a.use_mirror && live && lane == 0 && ro.r0 != 0u && (ro.tag & ROW_MASK) != 0u && !(ro.tag & ROW_FILTERED)) {
-      const uint2 sm = load_freq_flags(a.ts0, ro.r0);
-      SlotMirror nm;
-      nm.srow = ro.r0; nm.freq = sm.x; nm.flags = (unsigned char)(sm.y & 0xFFu); nm.state = (unsigned char)MIRROR_CLEAN;
-      nm.epoch = (unsigned short)a.mirror_epoch; nm.pad = 0u;
-      *mirror_ptr(a.tv, ro.tag & ROW_MASK) = nm;
-    }
-  } else if (live && hd.z != ROW_MASK) {
-    const size_t orow = a.out_map ? (size_t)a.out_map[hd.z] : (size_t)hd.z;   // sharded apply: the unique id's exchange slot
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const int e0 = (lane + k * LPR) * V;
-      if (e0 < D) stv<V>(a.out_sum + orow * D + e0, gv[k]);
-    }
-  }
-}
 
 template <int MODE, int OPT, int V, int LPR, int K>
 __device__ __forceinline__ void apply_body(const WsDev& w, const PartArgs& a) {

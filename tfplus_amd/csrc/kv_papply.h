@@ -35,6 +35,9 @@
 #ifndef KV_PA_HOTRB
 #define KV_PA_HOTRB 8      // a hot key's sources in flight per lane group and step
 #endif
+#ifndef KV_PA_RC
+#define KV_PA_RC 4         // further sources of a cold key in flight per lane group and step
+#endif
 // Two block shapes (A/B at configs[1], 109 k keys: 256 threads x 1024 partitions 64.7 us, 512 x 512 60 us, 1024 x 256
 // 75 us; at 773 k keys 512-thread blocks lose: four generations of blocks instead of two):
 //   TBP = 512: 2048 hash slots, 2048 sources in LDS — chosen when the batch has at most 512 partitions (one resident
@@ -323,26 +326,14 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
     bool evalid[K];
   #pragma unroll
     for (int k = 0; k < K; ++k) { const int e0 = (lane + k * LPR) * V; evalid[k] = e0 < D; eoff[k] = evalid[k] ? e0 : 0; }
-    // the lean update: single-chunk tables, hints, no delta lists — and the var rows carry mirrors of the slot records
-    // (kv_device.h SlotMirror; the host's mirror_decide): any other launch or key goes through finish_key
-    const bool fast = !two_slots(OPT) && a.tv.single != 0u && a.ts0.single != 0u && a.use_hints != 0 &&
-                      (a.tv.track_delta | a.ts0.track_delta) == 0u && a.use_mirror != 0;
-    float* const vrows = a.tv.c0.rows;
-    RowMeta* const vmeta = a.tv.c0.meta;
-    float* const srows = a.ts0.c0.rows;
-    const int SD = a.ts0.dim;
-    const unsigned smax = a.ts0.max_rows, thr = a.tv.enter_threshold;
-    const bool need_vmeta = keeps_var_flags(OPT) || thr != 0u;
-    const unsigned mepoch = a.mirror_epoch & 0xFFFFu;
+    // the lean update for every key whose slot mirror stands; any other launch or key goes through finish_key (kv_key_update.h)
+    const LeanCtx lc = lean_ctx<OPT>(a);
     constexpr int NS0 = slot0_blocks(OPT);
 
     // ---- the apply: items = the round's hot keys (one per wave), then batches of G cold keys (one per lane group) -------
     const unsigned nbatch = (ncold + (unsigned)G - 1u) / (unsigned)G;
     const unsigned nitems = nhot + nbatch;
     KV_STAMPPV(6, E); KV_STAMPPV(7, nu); KV_STAMPPV(8, nhot);
-#ifdef KV_PA_X_NOAPPLY
-    return false;
-#endif
     if (UQ) return false;   // (block-uniform) numbering only
 #ifdef KV_STAMPS
     unsigned long long st_t0 = wall_clock64(), st_hot = 0, st_cold = 0, st_nh = 0, st_nc = 0;
@@ -370,11 +361,7 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
 #pragma unroll
         for (int k = 0; k < K; ++k) ldv_stream<V>(src + eo[k], dst[k]);
       };
-#ifdef KV_PA_X_NOHOT
-      const bool is_hot = false;
-#else
       const bool is_hot = it < nhot;
-#endif
       // the key of this lane group (hot: every group the same key, group 0 finishes it)
       const unsigned kr = is_hot ? it : nhot + (it - nhot) * (unsigned)G + (unsigned)g;
       const bool have = is_hot || kr < nu;
@@ -414,15 +401,16 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
       bool hint_loaded = false, have_x = false, have_s = false;
       PreRows<OPT, V, K> pre;
       const bool st_live = live && row != 0u;
+      // (the same loads as uapply_body's prefetch, kv_uapply.h: keep the two in step — kv_key_update.h says why they are two)
       auto prefetch = [&]() {
-        if (fast) {
+        if (lc.fast) {
           const unsigned rr = st_live ? row : 0u;
-          const unsigned hh = (st_live && hint < smax) ? hint : 0u;
-          const RowMeta* const vrec = vmeta + (size_t)rr * META_STRIDE;
+          const unsigned hh = (st_live && hint < lc.smax) ? hint : 0u;
+          const RowMeta* const vrec = lc.vmeta + (size_t)rr * META_STRIDE;
           mir = *reinterpret_cast<const uint4*>(vrec + 1);   // the slot record's copy, in the var record's own line
           vm = *reinterpret_cast<const uint2*>(&vrec->freq);
-          const float* xr = vrows + (size_t)rr * D;
-          const float* sr = srows + (size_t)hh * SD;
+          const float* xr = lc.vrows + (size_t)rr * D;
+          const float* sr = lc.srows + (size_t)hh * lc.SD;
 #pragma unroll
           for (int k = 0; k < K; ++k) {
             ldv<V>(xr + eo[k], pre.x[k]);
@@ -495,9 +483,6 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
 #pragma unroll
             for (int cc = 0; cc < V; ++cc) gv[k][cc] += (cnt >= 2u) ? g2[k][cc] : 0.f;
         }
-#ifndef KV_PA_RC
-#define KV_PA_RC 4
-#endif
         constexpr int RC = (KV_PA_RC / K) > 0 ? (KV_PA_RC / K) : 1;
         for (unsigned j0 = 2; __ballot(live && j0 < cnt) != 0ull; j0 += RC) {
           float val[RC][K][V];
@@ -535,22 +520,9 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
       if (mode != PA_NONE) {
         const bool nk = st_live && isnew;
         if (__builtin_expect(__ballot(nk) != 0ull, 0)) {
-          if (nk) {   // the init rule's value (kv_variable.h:889-898): the row the update starts from, and what the table holds if it does not act
-            const unsigned long long h = pick64((unsigned long long)key ^ (a.tv.seed * 0x9E3779B97F4A7C15ULL));
-            const float* ia = a.tv.init_table + (size_t)((unsigned)h % a.tv.init_rows) * D;
-            const float* ib = a.tv.init_table + (size_t)((unsigned)(h >> 32) % a.tv.init_rows) * D;
-            float* xrow = row_ptr(a.tv, row);
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-              float va_[V], vb_[V];
-              ldv<V>(ia + eo[k], va_);
-              ldv<V>(ib + eo[k], vb_);
-#pragma unroll
-              for (int cc = 0; cc < V; ++cc) pre.x[k][cc] = (va_[cc] + vb_[cc]) * 0.5f;
-              if (evalid[k]) stv<V>(xrow + eo[k], pre.x[k]);
-            }
-            have_x = true;
-          }
+          // the init rule's value: the row the update starts from, and what the table holds if it does not act
+          (void)init_var_row<V, LPR, K>(a.tv, key, row, nk, D, eo, evalid, pre.x);
+          if (nk) have_x = true;
         }
         const unsigned oflags = nk ? (unsigned)FLAG_DIRTY : (vm.y & 0xFFu);
         const bool recompute = st_live && (mode == PA_LOOKUP ? (oflags & FLAG_DIRTY) != 0u : nk);
@@ -602,37 +574,10 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
       // ---- the update (one copy for both kinds of item) ------------------------------------------------------------------
       const bool fin_live = live && errflag == 0u;
       const uint4 ra = make_uint4((unsigned)key, (unsigned)((unsigned long long)key >> 32), row | (vnew ? NEW_BIT : 0u), hint);
-      bool general = fin_live;
-      if (fast) {
-        const unsigned hh = hint < smax ? hint : 0u;
-        // the hint stands up: the slot row carries this key and is not released (what resolve_rows checks)
-        // ... or, with mirrors: the var row's mirror stands for exactly that slot row in this epoch (established by the
-        // general path below or by kv_attach_slot; kv_device.h SlotMirror)
-        const bool ok = fin_live && row != 0u && hh != 0u && ((mir.z >> 8) & 0xFFu) != MIRROR_INVALID && (mir.z >> 16) == mepoch &&
-                        mir.x == hh;
-        const unsigned sfreq = mir.y;   // the slot row's frequency word
-        bool act = ok;
-        if (need_vmeta && ok && !vnew) {   // frequency filter / un-blacklisting (resolve_rows; kv_variable.h:910)
-          if ((vm.x & 0xFFFFu) < thr) act = false;
-          else if ((vm.y & FLAG_BLACK) && lane == 0) vmeta[(size_t)row * META_STRIDE].flags = FLAG_UNDER;
-        }
-        const unsigned rr = act ? row : 0u, h2 = act ? hh : 0u;
-        SlotMirror* const mp = reinterpret_cast<SlotMirror*>(vmeta + (size_t)rr * META_STRIDE + 1);
-        if (act && lane == 0) {   // AddFrequency(1, today) on the slot row (kv_variable.h:409-414)
-          unsigned lo16 = (sfreq & 0xFFFFu) + 1u;
-          if (lo16 > 65535u) lo16 = 65535u;
-          mp->freq = (a.day << 16) | lo16;
-          mp->state = (unsigned char)MIRROR_DIRTY;
-        }
-        opt_core<OPT, V, LPR, K>(vrows + (size_t)rr * D, srows + (size_t)h2 * SD, nullptr, &vmeta[(size_t)rr * META_STRIDE].flags,
-                                 &mp->flags, nullptr, act, false, D, gv, a.opt, lane_i, pre.x, pre.s);
-        general = fin_live && !ok;
-      }
-#ifndef KV_PA_X_NOGENERAL
-      if (!fast || __ballot(general) != 0ull)
+      const bool general = key_update<OPT, V, LPR, K>(a, lc, row, hint, vnew, fin_live, lane_i, D, gv, vm, mir, pre);
+      if (!lc.fast || __ballot(general) != 0ull)
         finish_key<MODE_APPLY, OPT, V, LPR, K>(a, ra, general, hint_loaded && general, m0, gv, lane_i, &pre, have_x && general,
                                                have_s && general);
-#endif
 #ifdef KV_STAMPS
       {
         const unsigned long long now = wall_clock64();

@@ -78,7 +78,6 @@ __device__ __forceinline__ unsigned uniq_insert(const TableDev& t, long long key
 template <int OPT, int V, int LPR, int K>
 __device__ __forceinline__ void uapply_body(const PartArgs& a, const void* __restrict__ ids, int ids32, long long n) {
   constexpr int G = 64 / LPR;
-  constexpr int NS0 = slot0_blocks(OPT);
   if (*reinterpret_cast<volatile unsigned*>(&a.tv.counters[1])) return;   // an earlier batch left the error flag up
   const int D = a.tv.dim;
   const int wl = threadIdx.x & 63, lane = wl % LPR, g = wl / LPR;
@@ -86,17 +85,8 @@ __device__ __forceinline__ void uapply_body(const PartArgs& a, const void* __res
   bool evalid[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) { const int e0 = (lane + k * LPR) * V; evalid[k] = e0 < D; eoff[k] = evalid[k] ? e0 : 0; }
-  // the lean update: single-chunk tables, the var's index entries remember the slot rows, no delta lists (every pre-sized
-  // training table); any other key or table goes through finish_key (kv_kernels.h)
-  const bool fast = !two_slots(OPT) && a.tv.single != 0u && a.ts0.single != 0u && a.use_hints != 0 &&
-                    (a.tv.track_delta | a.ts0.track_delta) == 0u && a.use_mirror != 0;   // ... and slot mirrors (kv_device.h)
-  float* const vrows = a.tv.c0.rows;
-  RowMeta* const vmeta = a.tv.c0.meta;
-  float* const srows = a.ts0.c0.rows;
-  const int SD = a.ts0.dim;
-  const unsigned smax = a.ts0.max_rows, thr = a.tv.enter_threshold;
-  const bool need_vmeta = keeps_var_flags(OPT) || thr != 0u;
-  const unsigned mepoch = a.mirror_epoch & 0xFFFFu;
+  // the lean update for every key whose slot mirror stands; any other key or table goes through finish_key (kv_key_update.h)
+  const LeanCtx lc = lean_ctx<OPT>(a);
   const unsigned serial = a.uniq_serial & 0xFFFFu;
   const float* const gbase = a.grad;
   const long long nbatch = (n + G - 1) / G;
@@ -150,17 +140,19 @@ __device__ __forceinline__ void uapply_body(const PartArgs& a, const void* __res
     }
     RowMeta m0{};
     uint2 vm = make_uint2(0u, 0u);
-    uint4 mir = make_uint4(0u, 0u, 0u, 0u);   // {srow, freq, flags | state << 8 | epoch << 16, -}
+    uint4 mir = make_uint4(0u, 0u, 0u, 0u);
     bool hint_loaded = false, have_x = false, have_s = false;
     PreRows<OPT, V, K> pre;
-    if (fast) {
+    // (the same loads as papply_body's prefetch lambda, kv_papply.h: keep the two in step — kv_key_update.h says why they are two)
+    if (lc.fast) {
+      constexpr int NS0 = slot0_blocks(OPT);
       const unsigned rr = st_live ? row : 0u;
-      const unsigned hh = (st_live && hint < smax) ? hint : 0u;
-      const RowMeta* const vrec = vmeta + (size_t)rr * META_STRIDE;
+      const unsigned hh = (st_live && hint < lc.smax) ? hint : 0u;
+      const RowMeta* const vrec = lc.vmeta + (size_t)rr * META_STRIDE;
       mir = *reinterpret_cast<const uint4*>(vrec + 1);   // the slot record's copy, in the var record's own line
       vm = *reinterpret_cast<const uint2*>(&vrec->freq);
-      const float* xr = vrows + (size_t)rr * D;
-      const float* sr = srows + (size_t)hh * SD;
+      const float* xr = lc.vrows + (size_t)rr * D;
+      const float* sr = lc.srows + (size_t)hh * lc.SD;
 #pragma unroll
       for (int k = 0; k < K; ++k) {
         ldv<V>(xr + eoff[k], pre.x[k]);
@@ -196,27 +188,7 @@ __device__ __forceinline__ void uapply_body(const PartArgs& a, const void* __res
     {
       const bool nk = go && st_live && isnew;
       if (__builtin_expect(__ballot(nk) != 0ull, 0)) {
-        bool big = false;
-        if (nk) {
-          const unsigned long long h = pick64((unsigned long long)key ^ (a.tv.seed * 0x9E3779B97F4A7C15ULL));
-          const float* ia = a.tv.init_table + (size_t)((unsigned)h % a.tv.init_rows) * D;
-          const float* ib = a.tv.init_table + (size_t)((unsigned)(h >> 32) % a.tv.init_rows) * D;
-          float* xrow = row_ptr(a.tv, row);
-#pragma unroll
-          for (int k = 0; k < K; ++k) {
-            float va_[V], vb_[V];
-            ldv<V>(ia + eoff[k], va_);
-            ldv<V>(ib + eoff[k], vb_);
-#pragma unroll
-            for (int cc = 0; cc < V; ++cc) {
-              pre.x[k][cc] = (va_[cc] + vb_[cc]) * 0.5f;
-              big |= evalid[k] && fabsf(pre.x[k][cc]) >= CUTOFF;
-            }
-            if (evalid[k]) stv<V>(xrow + eoff[k], pre.x[k]);
-          }
-          have_x = true;
-        }
-        const bool any = group_any<LPR>(big);
+        const bool any = init_var_row<V, LPR, K>(a.tv, key, row, nk, D, eoff, evalid, pre.x);
         if (nk) {
           const unsigned nfl = any ? 0u : (unsigned)FLAG_UNDER;
           if (lane == 0) {
@@ -224,6 +196,7 @@ __device__ __forceinline__ void uapply_body(const PartArgs& a, const void* __res
             *meta_ptr(a.tv, row) = nm;
           }
           vm.x = 1u; vm.y = nfl | (serial << 16);
+          have_x = true;
           vnew = true;
         }
       }
@@ -231,31 +204,8 @@ __device__ __forceinline__ void uapply_body(const PartArgs& a, const void* __res
 
     // ---- the update ----------------------------------------------------------------------------------------------------------
     const uint4 ra = make_uint4((unsigned)key, (unsigned)((unsigned long long)key >> 32), row | (vnew ? NEW_BIT : 0u), hint);
-    bool general = go;
-    if (fast) {
-      const unsigned hh = hint < smax ? hint : 0u;
-      // the hint stands up: the slot row carries this key and is not released (what resolve_rows checks)
-      // ... or, with mirrors: the var row's mirror stands for exactly that slot row in this epoch (kv_device.h SlotMirror)
-      const bool ok = go && row != 0u && hh != 0u && ((mir.z >> 8) & 0xFFu) != MIRROR_INVALID && (mir.z >> 16) == mepoch && mir.x == hh;
-      const unsigned sfreq = mir.y;   // the slot row's frequency word
-      bool act = ok;
-      if (need_vmeta && ok && !vnew) {   // frequency filter / un-blacklisting (resolve_rows; kv_variable.h:910)
-        if ((vm.x & 0xFFFFu) < thr) act = false;
-        else if ((vm.y & FLAG_BLACK) && lane == 0) vmeta[(size_t)row * META_STRIDE].flags = FLAG_UNDER;
-      }
-      const unsigned rr = act ? row : 0u, h2 = act ? hh : 0u;
-      SlotMirror* const mp = reinterpret_cast<SlotMirror*>(vmeta + (size_t)rr * META_STRIDE + 1);
-      if (act && lane == 0) {   // AddFrequency(1, today) on the slot row (kv_variable.h:409-414)
-        unsigned lo16 = (sfreq & 0xFFFFu) + 1u;
-        if (lo16 > 65535u) lo16 = 65535u;
-        mp->freq = (a.day << 16) | lo16;
-        mp->state = (unsigned char)MIRROR_DIRTY;
-      }
-      opt_core<OPT, V, LPR, K>(vrows + (size_t)rr * D, srows + (size_t)h2 * SD, nullptr, &vmeta[(size_t)rr * META_STRIDE].flags,
-                               &mp->flags, nullptr, act, false, D, gv, a.opt, lane, pre.x, pre.s);
-      general = go && !ok;
-    }
-    if (!fast || __ballot(general) != 0ull)
+    const bool general = key_update<OPT, V, LPR, K>(a, lc, row, hint, vnew, go, lane, D, gv, vm, mir, pre);
+    if (!lc.fast || __ballot(general) != 0ull)
       finish_key<MODE_APPLY, OPT, V, LPR, K>(a, ra, general, hint_loaded && general, m0, gv, lane, &pre, have_x && general,
                                              have_s && general);
     // ---- what the XOR found -----------------------------------------------------------------------------------------------------

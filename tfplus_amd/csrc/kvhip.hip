@@ -57,6 +57,7 @@ using namespace kvhip_internal;
 namespace {
 
 #include "kv_device.h"
+#include "kv_key_update.h"
 #include "kv_kernels.h"
 #include "kv_fused.h"
 #include "kv_papply.h"
