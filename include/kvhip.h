@@ -249,6 +249,34 @@ int kv_prepare_capture(kv_handle_t h, int64_t max_new_ids, kv_stream_t stream);
 int kv_dedup_segment_sum(kv_handle_t h, const void* ids, const float* grad, int64_t n,
                          int64_t* uniq_ids, float* summed, int32_t* inverse, int64_t* num_unique,
                          kv_stream_t stream);
+/* The same work and the same outputs with the count left on the DEVICE: *num_unique_dev (int64, device memory) is
+ * written behind the sums on `stream`, nothing is synchronised and no blocking copy is made, so the host runs ahead and
+ * the calls of an unchanged graph's step — lookup, this, kv_apply_unique_counted — queue without a host round trip.
+ * uniq_ids / summed / inverse are as above, valid for the first *num_unique_dev entries once the stream gets there.
+ * n == 0 sets the word to 0 (a hipMemsetAsync).  (The table's batch workspace still grows behind a synchronisation the
+ * first time a batch length is seen.) */
+int kv_dedup_segment_sum_dev(kv_handle_t h, const void* ids, const float* grad, int64_t n,
+                             int64_t* uniq_ids, float* summed, int32_t* inverse, int64_t* num_unique_dev,
+                             kv_stream_t stream);
+
+/* kv_apply_<optimizer>_unique with the id count taken from the DEVICE: the op is applied to the first
+ * min(n_max, *n_dev) ids and gradient rows, *n_dev (int64, device memory — kv_dedup_segment_sum_dev's or kv_unique's
+ * num_unique_dev) being read by the kernel when it runs.  `optimizer`, `hp` and `slot1` are kv_shard_apply_serve's
+ * codes and layouts (0 .. 6, below).  The same promise of unique ids, the same duplicate guard, checks, results and slot
+ * mirror handling as the _unique ops: the same bits.  `ids` [n_max] are KV_DT_INT64 or KV_DT_INT32 (ids_dtype) whatever
+ * the table's key dtype — the dedup writes int64 ids for every table.  `grad` is [n_max, dim].
+ * The host sizes everything by n_max: the tables' capacity (their row bounds advance by n_max per call, so a table
+ * within n_max rows of its capacity refreshes its counts — one synchronisation — more often than with the exact form),
+ * the 0 .. 2^23 range check and the grid.
+ * A count that is negative or above n_max applies NOTHING and is not clamped: it raises the table's error word and the
+ * next call on the table returns KV_INVALID_ARGUMENT naming this op.
+ * KV_UNIMPLEMENTED, before anything is queued: for embedding dims the one-launch kernel does not serve (not a multiple
+ * of 4, or above 256 — the batch pipeline the exact forms fall back to needs a host count), and under stream capture
+ * (the duplicate guard's launch serial lives on the host and a replay would meet its own stamps; a serial kept on the
+ * device is future work). */
+int kv_apply_unique_counted(kv_handle_t var, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp,
+                            const float* grad, const void* ids, int ids_dtype, int64_t n_max, const int64_t* n_dev,
+                            kv_stream_t stream);
 
 /* ---- export / import ("next" rows) -------------------------------------------
  * Replaces ReadKvVariableOp / KvVariableExport (kernels/kv_variable_ops.cc:325-346, 779-860) ->

@@ -54,6 +54,8 @@ SIGNATURES = {
     "kv_get_stat": (_i32, [_vp, _i32, _c.POINTER(_i64)]),
     "kv_prepare_capture": (_i32, [_vp, _i64, _vp]),
     "kv_dedup_segment_sum": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _c.POINTER(_i64), _vp]),
+    "kv_dedup_segment_sum_dev": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "kv_apply_unique_counted": (_i32, [_vp, _i32, _vp, _vp, _c.POINTER(_f), _vp, _vp, _i32, _i64, _vp, _vp]),
     "kv_export_count": (_i32, [_vp, _i32, _c.POINTER(_i64), _vp]),
     "kv_export_fill": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kv_set_delta_tracking": (_i32, [_vp, _i32, _i32]),

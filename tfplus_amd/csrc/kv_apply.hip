@@ -237,10 +237,13 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
 // (kv_apply_*_unique), the one-launch path.  Its duplicate guard stamps rows with a launch serial that lives on the HOST: a
 // captured launch would be replayed with the serial it was captured with and find its own stamps.  Under stream capture the
 // unique forms therefore run the batch pipeline (which needs no promise; same results, bit for bit): stream_is_capturing().
-// The caller holds the locks.  self: kv_shard_apply_serve's own segment, read in place.
+// The caller holds the locks.  self: kv_shard_apply_serve's own segment, read in place.  counted (kv_apply_unique_counted,
+// with unique): n bounds the batch, the kernel reads the count from the device; apply_one has refused what only the batch
+// pipeline serves.
 template <int OPT>
 static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* grad, const void* ids, int64_t n,
-                        const OptArgs& a, kv_batch_token_t token, hipStream_t s, bool unique, const SelfSegment* self) {
+                        const OptArgs& a, kv_batch_token_t token, hipStream_t s, bool unique, const SelfSegment* self,
+                        const DevCount* counted) {
   const long long nmax = fused_tab(v) ? FUSED_MAX_N : (1ll << 21);
   if (n < 0 || n > nmax)
     return fail(n < 0 ? KV_INVALID_ARGUMENT : KV_UNIMPLEMENTED,
@@ -249,6 +252,8 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
   if (!dim_supported(v->dim))
     return fail(KV_UNIMPLEMENTED, "embedding dim %d not supported by the fused kernels", v->dim);
   int rc;
+  if (counted && (!unique || !fused_ok(v->dim) || stream_is_capturing(s)))
+    return fail(KV_INTERNAL, "counted apply off the one-launch path");
   if (unique && fused_ok(v->dim) && !stream_is_capturing(s)) {
     // The caller promises unique ids (kv_apply_*_unique; kv_uapply.h): one launch, one lane group per id.  A pending
     // partition pass was settled by the caller's hand_over (no token is given).  Dims the kernel does not serve take the
@@ -260,7 +265,8 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
     if ((rc = mirror_decide(v, s0, pa, !two_slots(OPT), s))) return rc;
     pa.uniq_serial = ++v->uniq_serial;
     ProfScope ps(v, KV_PROF_APPLY_UNIQUE, s);
-    rc = launch_uapply<OPT>(pa, ids, v->key_dtype == KV_DT_INT32 ? 1 : 0, n, s);
+    if (counted) rc = launch_uapply<OPT>(pa, ids, counted->ids32, n, s, nullptr, 0, counted->n_dev);
+    else rc = launch_uapply<OPT>(pa, ids, v->key_dtype == KV_DT_INT32 ? 1 : 0, n, s);
     if (rc) return fail(rc, "unique apply: no kernel for dim %d", v->dim);
     HIP_TRY(hipGetLastError());
     return KV_OK;
@@ -438,7 +444,7 @@ OptCall shard_opt_call(int optimizer, const float* hp) {
 // the optimizer itself (GroupAdam version), the tables' initialisation, the hyperparameters, the shapes.  So c.status is
 // reported at its place in that order (nothing calls fail() before it unless it returns).  The batched ops report it first.
 int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const float* grad, const void* ids, int64_t n,
-              kv_batch_token_t token, kv_stream_t stream, bool unique, const SelfSegment* self) {
+              kv_batch_token_t token, kv_stream_t stream, bool unique, const SelfSegment* self, const DevCount* counted) {
   int rc;
   const bool two = two_slots(c.opt);
   if ((rc = check_table(v)) || (rc = check_table(s0)) || (two && (rc = check_table(s1)))) return rc;
@@ -470,6 +476,15 @@ int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const f
     if (v->device != s0->device || v->device != s1->device || v == s0 || v == s1 || s0 == s1)
       return fail(KV_INVALID_ARGUMENT, "var, accum and linear must be distinct tables on one device");
   }
+  if (counted) {   // what only the batch pipeline serves needs a host count: refused before anything is queued
+    if (!fused_ok(v->dim))
+      return fail(KV_UNIMPLEMENTED, "kv_apply_unique_counted: embedding dim %d (multiples of 4 up to 256; other dims take the batch "
+                                    "pipeline, which needs the count on the host: kv_apply_*_unique)", v->dim);
+    DeviceGuard dgc(v->device);
+    if (stream_is_capturing((hipStream_t)stream))
+      return fail(KV_UNIMPLEMENTED, "kv_apply_unique_counted under stream capture: the duplicate guard's launch serial lives on "
+                                    "the host (kv_apply_*_unique takes the batch pipeline there)");
+  }
   if (n == 0) return KV_OK;
   DeviceGuard dg(v->device);
   MultiLock lk({v, s0, two ? s1 : s0});
@@ -480,7 +495,7 @@ int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const f
   if ((rc = lk.enter(s, keep, token != 0 && token == v->batch_serial ? v : nullptr))) return rc;
   OptArgs a = c.a;
   a.l21_norm = a.l21 * std::sqrt((float)v->dim);   // training_ops.cc:728
-  return with_opt(c.opt, [&](auto o) { return apply_common<decltype(o)::value>(v, s0, two ? s1 : nullptr, grad, ids, n, a, token, s, unique, self); });
+  return with_opt(c.opt, [&](auto o) { return apply_common<decltype(o)::value>(v, s0, two ? s1 : nullptr, grad, ids, n, a, token, s, unique, self, counted); });
 }
 
 // Many tables.  After the parser's verdict the ops refuse a missing first table (and linears) — all but Adagrad, whose op
@@ -711,6 +726,21 @@ int kv_multi_apply_group_ftrl_v2_unique(int num_tables, const kv_handle_t* vars,
                                         kv_stream_t stream) {
   return multi_apply(ftrl_v2_call(OPT_GROUP_FTRL_V2, lr, l1, l2, l2s, lr_power), num_tables, vars, accums, linears, grads, ids,
                      ns, nullptr, stream, true);
+}
+
+// the _unique op of optimizer code `optimizer` (shard_opt_call) with the id count on the device: kv_uapply.h k_uapply_counted
+int kv_apply_unique_counted(kv_handle_t v, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp, const float* grad,
+                            const void* ids, int ids_dtype, int64_t n_max, const int64_t* n_dev, kv_stream_t stream) {
+  if (!hp) return fail(KV_INVALID_ARGUMENT, "kv_apply_unique_counted: hp is null");
+  if (ids_dtype != KV_DT_INT64 && ids_dtype != KV_DT_INT32)
+    return fail(KV_INVALID_ARGUMENT, "kv_apply_unique_counted: ids_dtype %d (KV_DT_INT64 or KV_DT_INT32)", ids_dtype);
+  if (!n_dev) return fail(KV_INVALID_ARGUMENT, "kv_apply_unique_counted: n_dev is null");
+  const OptCall c = shard_opt_call(optimizer, hp);
+  if (c.opt < 0) return fail(KV_INVALID_ARGUMENT, "kv_apply_unique_counted: optimizer %d", optimizer);
+  DevCount dc;
+  dc.n_dev = reinterpret_cast<const long long*>(n_dev);
+  dc.ids32 = ids_dtype == KV_DT_INT32 ? 1 : 0;
+  return apply_one(c, v, slot0, slot1, grad, ids, n_max, 0, stream, true, nullptr, &dc);
 }
 
 int kv_attach_slot(kv_handle_t v, kv_handle_t sl, kv_stream_t stream) {

@@ -514,8 +514,12 @@ struct OptCall {
 };
 
 OptCall shard_opt_call(int optimizer, const float* hp);
+// kv_apply_unique_counted: the unique apply whose id count is a device word (n of apply_one is then the most ids the call
+// may hold) and whose ids have a dtype of their own
+struct DevCount { const long long* n_dev = nullptr; int ids32 = 0; };
 int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const float* grad, const void* ids, int64_t n,
-              kv_batch_token_t token, kv_stream_t stream, bool unique, const SelfSegment* self = nullptr);
+              kv_batch_token_t token, kv_stream_t stream, bool unique, const SelfSegment* self = nullptr,
+              const DevCount* counted = nullptr);
 int multi_apply(const OptCall& c, int num_tables, const kv_handle_t* vars, const kv_handle_t* slots0,
                 const kv_handle_t* slots1, const float* const* grads, const void* const* ids, const int64_t* ns,
                 const kv_batch_token_t* tokens, kv_stream_t stream, bool unique, bool require_reuse = false,

@@ -17,15 +17,17 @@ int launch_sorted_apply(const WsDev& wd, const PartArgs& pa, hipStream_t s, cons
 // k_papply (kv_papply.h): partition pass + update in one launch; mode = PA_LOOKUP / PA_APPLYIDX / PA_NONE
 template <int OPT>
 int launch_papply(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t s, const MultiDesc* md = nullptr, int ntab = 0);
-// k_uapply (kv_uapply.h): the apply on unique ids and pre-summed rows, one launch
+// k_uapply (kv_uapply.h): the apply on unique ids and pre-summed rows, one launch.  n_dev != nullptr (one table): n bounds
+// the batch and the kernel reads the id count from the device word (k_uapply_counted)
 template <int OPT>
 int launch_uapply(const PartArgs& pa, const void* ids, int ids32, long long n, hipStream_t s, const MultiDesc* md = nullptr,
-                  int ntab = 0);
+                  int ntab = 0, const long long* n_dev = nullptr);
 
 #define KV_OPT_LAUNCHERS(OPT)                                                                                                \
   template <> int launch_sorted_apply<OPT>(const WsDev&, const PartArgs&, hipStream_t, const MultiDesc*, int, unsigned, int); \
   template <> int launch_papply<OPT>(const WsDev&, const PartArgs&, int, hipStream_t, const MultiDesc*, int);                 \
-  template <> int launch_uapply<OPT>(const PartArgs&, const void*, int, long long, hipStream_t, const MultiDesc*, int)
+  template <> int launch_uapply<OPT>(const PartArgs&, const void*, int, long long, hipStream_t, const MultiDesc*, int, \
+                                     const long long*)
 KV_OPT_LAUNCHERS(OPT_ADAM_V4);         // kv_opt_adam_v4.hip
 KV_OPT_LAUNCHERS(OPT_ADAM_V3);         // kv_opt_adam_v3.hip
 KV_OPT_LAUNCHERS(OPT_ADAGRAD);         // kv_opt_adagrad.hip

@@ -148,8 +148,11 @@ static int segment_sums(kv_table* t, WsDev& wd, PartArgs& pa, const void* ids, l
 
 // tf.unique + unsorted_segment_sum; the table's mutex is held by the caller.
 // fold_op: how the rows of one id combine (KV_SCATTER_ADD = sum, MUL = product, MIN, MAX)
+// The count goes to num_unique (host: the call synchronises, read_count) and / or to num_unique_dev (a device word, written
+// by k_store_count behind the sums: nothing is synchronised), as kv_unique's.
 static int dedup_locked(kv_table* t, const void* ids, const float* grad, int64_t n, int64_t* uniq,
-                        float* summed, int32_t* inverse, int64_t* num_unique, int fold_op, hipStream_t s) {
+                        float* summed, int32_t* inverse, int64_t* num_unique, int64_t* num_unique_dev, int fold_op,
+                        hipStream_t s) {
   int rc;
   if ((rc = ensure_workspace(t, n, true, s))) return rc;
   WsDev wd = ws_view(t, n);
@@ -163,9 +166,15 @@ static int dedup_locked(kv_table* t, const void* ids, const float* grad, int64_t
   if ((rc = segment_sums(t, wd, pa, ids, n, t->key_dtype == KV_DT_INT32, true, "per-id sums", s))) return rc;
   if (inverse && t->fused_index) k_inverse_e<<<nblocks(n, TB, 2048), TB, 0, s>>>(t->ws.pos_ent, wd.ent_b, n, inverse);
   else if (inverse) k_dedup_inverse<<<nblocks(n, TB, 2048), TB, 0, s>>>(wd, n, inverse);
-  unsigned U = 0;
-  if ((rc = read_count(t, wd.ctr, s, &U))) return rc;
-  *num_unique = U;
+  if (num_unique_dev) {
+    k_store_count<<<1, 1, 0, s>>>(wd.ctr, (long long*)num_unique_dev);
+    HIP_TRY(hipGetLastError());
+  }
+  if (num_unique) {   // synchronous form
+    unsigned U = 0;
+    if ((rc = read_count(t, wd.ctr, s, &U))) return rc;
+    *num_unique = U;
+  }
   return KV_OK;
 }
 
@@ -909,7 +918,28 @@ int kv_dedup_segment_sum(kv_handle_t t, const void* ids, const float* grad, int6
   TableOp op(t, stream);
   // `t` lends its workspace: neither its rows nor any record is touched
   if ((rc = enter_op(t, op.s, KEEP_VAR | KEEP_SLOT))) return rc;
-  return dedup_locked(t, ids, grad, n, uniq, summed, inverse, num_unique, KV_SCATTER_ADD, op.s);
+  return dedup_locked(t, ids, grad, n, uniq, summed, inverse, num_unique, nullptr, KV_SCATTER_ADD, op.s);
+}
+
+// ... with the count left on the device: no synchronisation, no blocking copy (the checks are the synchronous form's)
+int kv_dedup_segment_sum_dev(kv_handle_t t, const void* ids, const float* grad, int64_t n, int64_t* uniq,
+                             float* summed, int32_t* inverse, int64_t* num_unique_dev, kv_stream_t stream) {
+  int rc;
+  if ((rc = check_table(t))) return rc;
+  if (!num_unique_dev) return fail(KV_INVALID_ARGUMENT, "num_unique_dev is null");
+  if (n == 0) {
+    DeviceGuard dg(t->device);
+    HIP_TRY(hipMemsetAsync(num_unique_dev, 0, sizeof(int64_t), (hipStream_t)stream));
+    return KV_OK;
+  }
+  if (n < 0 || !ids || !grad || !uniq || !summed) return fail(KV_INVALID_ARGUMENT, "bad arguments");
+  if (n > (fused_tab(t) ? FUSED_MAX_N : (1ll << 21)))
+    return fail(KV_UNIMPLEMENTED, "%lld ids in one call (limit 2^%d)", (long long)n, fused_tab(t) ? 23 : 21);
+  if (!dim_supported(t->dim)) return fail(KV_UNIMPLEMENTED, "embedding dim %d not supported", t->dim);
+  TableOp op(t, stream);
+  // `t` lends its workspace: neither its rows nor any record is touched
+  if ((rc = enter_op(t, op.s, KEEP_VAR | KEEP_SLOT))) return rc;
+  return dedup_locked(t, ids, grad, n, uniq, summed, inverse, nullptr, num_unique_dev, KV_SCATTER_ADD, op.s);
 }
 
 int kv_unsorted_segment_sum(kv_handle_t t, const int32_t* segment_ids, const float* data, int64_t n,
@@ -1186,7 +1216,7 @@ int kv_scatter_update(kv_handle_t t, const void* ids, const float* updates, int6
       const long long m = std::min(CHK, (long long)n - off);
       int64_t U = 0;
       if ((rc = dedup_locked(t, (const char*)ids + (size_t)off * idsz, updates + (size_t)off * t->dim, m,
-                             (int64_t*)w.scat_keys, w.scat_sum, nullptr, &U, fold, s)))
+                             (int64_t*)w.scat_keys, w.scat_sum, nullptr, &U, nullptr, fold, s)))
         return rc;
       if (t->key_dtype == KV_DT_INT32 && U > 0)   // the unique list is int64; the table's ops take its own key type
         k_narrow_keys<<<1, 1024, 0, s>>>(w.scat_keys, U);

@@ -33,7 +33,7 @@ int launch_papply<KV_OPT>(const WsDev& wd, const PartArgs& pa, int mode, hipStre
 }
 template <>
 int launch_uapply<KV_OPT>(const PartArgs& pa, const void* ids, int ids32, long long n, hipStream_t s, const MultiDesc* md,
-                          int ntab) {
-  return launch_uapply_t<KV_OPT>(pa, ids, ids32, n, s, md, ntab);
+                          int ntab, const long long* n_dev) {
+  return launch_uapply_t<KV_OPT>(pa, ids, ids32, n, s, md, ntab, n_dev);
 }
 }  // namespace kvhip_internal

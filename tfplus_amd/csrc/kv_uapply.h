@@ -229,12 +229,29 @@ __global__ void __launch_bounds__(256, (K == 1 ? 4 : 2)) k_uapply_multi(const Mu
   uapply_body<OPT, V, LPR, K>(m.a, m.ids, ids32, m.n);
 }
 
+// the id count from the device (kv_apply_unique_counted): *n_dev is the number of ids and gradient rows that are valid, at
+// most the n_max the host sized the launch for.  One load of a uniform address (a scalar load: every wave gets the word
+// once), then the check: a count outside 0 .. n_max raises the table's error word (code 5) and nothing is applied; with 0 ids
+// nothing is read at all (uapply_body's id_at clamps to n - 1).
+template <int OPT, int V, int LPR, int K>
+__global__ void __launch_bounds__(256, (K == 1 ? 4 : 2)) k_uapply_counted(PartArgs a, const void* __restrict__ ids, int ids32,
+                                                                           long long n_max, const long long* __restrict__ n_dev) {
+  const long long n = *n_dev;
+  if (n < 0 || n > n_max) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) raise_error(a.tv, 5u);
+    return;
+  }
+  if (n == 0) return;
+  uapply_body<OPT, V, LPR, K>(a, ids, ids32, n);
+}
+
 // dispatch on the row geometry (as k_papply: float4 rows, a power-of-two lane count).  KV_UNIMPLEMENTED for other dims:
 // the caller falls back to the batch pipeline, which serves them.  md != nullptr: `ntab` tables in one launch (n = the
-// largest table's ids, pa = any table's arguments: only the dim is read)
+// largest table's ids, pa = any table's arguments: only the dim is read).  n_dev != nullptr (single table only): n is the
+// most ids the call may hold — the grid is sized from it — and the kernel takes the count from *n_dev (k_uapply_counted)
 template <int OPT>
 int launch_uapply_t(const PartArgs& pa, const void* ids, int ids32, long long n, hipStream_t s, const MultiDesc* md = nullptr,
-                    int ntab = 0) {
+                    int ntab = 0, const long long* n_dev = nullptr) {
   const int D = pa.tv.dim;
   if ((D & 3) != 0) return KV_UNIMPLEMENTED;
 #define KV_UA(V, LPR, K)                                                                                        \
@@ -248,6 +265,8 @@ int launch_uapply_t(const PartArgs& pa, const void* ids, int ids32, long long n,
     if (md) {   /* all tables' blocks are one resident generation */                                            \
       if (ntab > 0 && (long long)grid * ntab > resident) grid = resident / ntab > 1 ? resident / ntab : 1;       \
       k_uapply_multi<OPT, V, LPR, K><<<dim3((unsigned)grid, (unsigned)ntab), 256, 0, s>>>(md, ids32);            \
+    } else if (n_dev) {                                                                                         \
+      k_uapply_counted<OPT, V, LPR, K><<<grid, 256, 0, s>>>(pa, ids, ids32, n, n_dev);                           \
     } else {                                                                                                    \
       k_uapply<OPT, V, LPR, K><<<grid, 256, 0, s>>>(pa, ids, ids32, n);                                          \
     }                                                                                                           \

@@ -245,6 +245,9 @@ int flagged_error(kv_table* t, unsigned code, hipStream_t s) {
     return fail(KV_INVALID_ARGUMENT, "kv_apply_*_unique: the ids of an earlier call were NOT unique (an id was listed twice): that "
                                      "batch was not applied as the reference applies repeated ids; pass such batches to "
                                      "kv_apply_* (which sums repeated ids) instead");
+  if (code == 5)
+    return fail(KV_INVALID_ARGUMENT, "kv_apply_unique_counted: the device count of an earlier call was negative or above its n_max: "
+                                     "that batch was not applied (the count is not clamped)");
   return fail(KV_INTERNAL, code == 2 ? "a hash partition received more than 65535 entries in one batch "
                                        "(key set crafted against the partition hash); that batch was not applied"
                                      : "row slab overflow detected on device");

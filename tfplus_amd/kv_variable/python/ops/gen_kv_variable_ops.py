@@ -204,8 +204,8 @@ kv_variable_gather_v2 = kv_variable_gather_or_zeros_v2
 
 
 # ---- optimizers ---------------------------------------------------------------------------------
-def _grad_ids(var, grad, indices):
-  ids = _ids(var, indices)
+def _grad_ids(var, grad, indices, keep_dtype=False):
+  ids = indices if keep_dtype else _ids(var, indices)
   if ids.dim() != 1:
     raise _lib.InvalidArgumentError("indices must be one-dimensional")
   g = _f32(var, grad)
@@ -229,10 +229,52 @@ def _layout_args(stem, per, scalars):
   return args
 
 
-def _apply(stem, tables, grad, indices, scalars, unique_indices, token=None):
+def _hp_array(hp):
+  """The float vector of hyperparameters the generic entry points take (kvhip.h kv_shard_apply_serve: one layout per
+  optimizer code), each rounded to fp32 once."""
+  return (ctypes.c_float * len(hp))(*[float(np.float32(x)) for x in hp])
+
+
+# stem of an optimizer family + its scalars (the order of _lib.OPT_FAMILIES) -> the optimizer code and hp vector of the
+# generic entry points (the OPT_* codes below; GroupAdam's trailing scalar is its version)
+_COUNTED_CODE = {"adagrad": 2, "sparse_group_ftrl": 3, "ftrl_v2": 4, "group_ftrl_v2": 5, "group_rectified_adam": 6}
+
+
+def _code_and_hp(stem, scalars):
+  sc = [_scalar(x) for x in scalars]
+  if stem == "group_adam":
+    if int(scalars[-1]) not in (3, 4):
+      raise _lib.InvalidArgumentError("GroupAdam version %d: 3 or 4" % int(scalars[-1]))
+    return (0 if int(scalars[-1]) == 4 else 1), sc[:-1]
+  return _COUNTED_CODE[stem], sc
+
+
+def _apply_counted(stem, tables, grad, indices, scalars, unique_count):
+  """kv_apply_unique_counted (kvhip.h): the _unique op on the first `unique_count` ids and gradient rows, the count (a
+  1-element int64 tensor on the table's device — kv_dedup_segment_sum(sync=False)'s or kv_unique(sync=False)'s) being read
+  on the device: nothing waits for the stream.  `indices` keep their own dtype (int64 or int32)."""
+  var = tables[0]
+  dev = _dev(var)
+  if not (isinstance(unique_count, torch.Tensor) and unique_count.dtype == torch.int64 and unique_count.numel() == 1
+          and unique_count.device == dev):
+    raise _lib.InvalidArgumentError("unique_count must be a 1-element int64 tensor on the table's device")
+  ids = torch.as_tensor(indices)
+  if ids.dtype not in _TORCH_KEY:
+    ids = ids.to(torch.int64)
+  g, ids = _grad_ids(var, grad, ids.to(dev).contiguous(), keep_dtype=True)
+  code, hp = _code_and_hp(stem, scalars)
+  _lib.check(_lib.lib().kv_apply_unique_counted(var.ptr, code, tables[1].ptr, tables[2].ptr if len(tables) > 2 else None,
+                                                _hp_array(hp), _p(g), _p(ids), _TORCH_KEY[ids.dtype], ids.numel(),
+                                                _p(unique_count), _stream(var)))
+
+
+def _apply(stem, tables, grad, indices, scalars, unique_indices, token=None, unique_count=None):
   """One optimizer step on (var, slot tables...): kv_apply_<stem>_unique on the caller's promise that `indices` holds no id
   twice (what TF-core's de-duplication guarantees in the reference's graph: kvhip.h), else kv_apply_<stem>_tok with the token
-  of the var's last lookup of this very tensor (or the caller's `token`)."""
+  of the var's last lookup of this very tensor (or the caller's `token`).  unique_count (a device tensor): the same promise
+  for the first unique_count ids, the count staying on the device (_apply_counted)."""
+  if unique_count is not None:
+    return _apply_counted(stem, tables, grad, indices, scalars, unique_count)
   var = tables[0]
   g, ids = _grad_ids(var, grad, indices)
   args = [t.ptr for t in tables] + _layout_args(stem, {"g": _p(g), "i": _p(ids), "n": ids.numel()}, scalars)
@@ -243,68 +285,81 @@ def _apply(stem, tables, grad, indices, scalars, unique_indices, token=None):
 
 def kv_variable_group_sparse_apply_adam_v4(var, m_v_linear, grad, indices, lr, beta1_power,
                                            beta2_power, beat1, beta2, epsilon, l1, l2, l21,
-                                           use_locking=False, name=None, unique_indices=False):
+                                           use_locking=False, name=None, unique_indices=False, unique_count=None):
   """REGISTER_OP("KvVariableGroupSparseApplyAdamV4") ops/training_ops.cc:1266-1285.
-  unique_indices: the caller's promise that `indices` holds no id twice (kv_apply_group_adam_unique)."""
+  unique_indices: the caller's promise that `indices` holds no id twice (kv_apply_group_adam_unique).
+  unique_count: a 1-element int64 device tensor — the same promise for the first unique_count ids, the count read on the
+  device (kv_apply_unique_counted; every optimizer wrapper below takes it)."""
   _apply("group_adam", (var, m_v_linear), grad, indices,
-         (lr, beta1_power, beta2_power, beat1, beta2, epsilon, l1, l2, l21, 4), unique_indices)
+         (lr, beta1_power, beta2_power, beat1, beta2, epsilon, l1, l2, l21, 4), unique_indices, unique_count=unique_count)
 
 
 def kv_variable_group_sparse_apply_adam_v3(var, m_v_linear, grad, indices, lr, beta1_power,
                                            beta2_power, beat1, beta2, epsilon, l1, l2, l21,
-                                           use_locking=False, name=None, unique_indices=False):
+                                           use_locking=False, name=None, unique_indices=False, unique_count=None):
   """REGISTER_OP("KvVariableGroupSparseApplyAdamV3") ops/training_ops.cc:1086-1105."""
   _apply("group_adam", (var, m_v_linear), grad, indices,
-         (lr, beta1_power, beta2_power, beat1, beta2, epsilon, l1, l2, l21, 3), unique_indices)
+         (lr, beta1_power, beta2_power, beat1, beta2, epsilon, l1, l2, l21, 3), unique_indices, unique_count=unique_count)
 
 
 def kv_variable_sparse_apply_adagrad(var, accum, lr, grad, indices, use_locking=False,
-                                     update_slots=True, name=None, unique_indices=False):
+                                     update_slots=True, name=None, unique_indices=False, unique_count=None):
   """REGISTER_OP("KvVariableSparseApplyAdagrad") ops/training_ops.cc:214-226."""
-  _apply("adagrad", (var, accum), grad, indices, (lr, bool(update_slots)), unique_indices)
+  _apply("adagrad", (var, accum), grad, indices, (lr, bool(update_slots)), unique_indices, unique_count=unique_count)
 
 
 def kv_variable_sparse_group_sparse_apply_ftrl_v2(var, accum, linear, grad, indices, lr, l1, l2, l21,
                                                   l2_shrinkage, lr_power, use_locking=False,
-                                                  name=None, unique_indices=False):
+                                                  name=None, unique_indices=False, unique_count=None):
   """REGISTER_OP("KvVariableSparseGroupSparseApplyFtrlV2") ops/training_ops.cc:135-150."""
-  _apply("sparse_group_ftrl", (var, accum, linear), grad, indices, (lr, l1, l2, l21, l2_shrinkage, lr_power), unique_indices)
+  _apply("sparse_group_ftrl", (var, accum, linear), grad, indices, (lr, l1, l2, l21, l2_shrinkage, lr_power), unique_indices,
+         unique_count=unique_count)
 
 
 def kv_variable_sparse_apply_ftrl_v2(var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power,
-                                     use_locking=False, name=None, unique_indices=False):
+                                     use_locking=False, name=None, unique_indices=False, unique_count=None):
   """REGISTER_OP("KvVariableSparseApplyFtrlV2") ops/training_ops.cc:103-117: per-coordinate FTRL-Proximal
   (kvhip.h kv_apply_ftrl_v2)."""
-  _apply("ftrl_v2", (var, accum, linear), grad, indices, (lr, l1, l2, l2_shrinkage, lr_power), unique_indices)
+  _apply("ftrl_v2", (var, accum, linear), grad, indices, (lr, l1, l2, l2_shrinkage, lr_power), unique_indices,
+         unique_count=unique_count)
 
 
 def kv_variable_group_sparse_apply_ftrl_v2(var, accum, linear, grad, indices, lr, l1, l2, l2_shrinkage, lr_power,
-                                           use_locking=False, name=None, unique_indices=False):
+                                           use_locking=False, name=None, unique_indices=False, unique_count=None):
   """REGISTER_OP("KvVariableGroupSparseApplyFtrlV2") ops/training_ops.cc:119-133: FTRL with a group-lasso threshold l1
   on the whole linear row (kvhip.h kv_apply_group_ftrl_v2)."""
-  _apply("group_ftrl_v2", (var, accum, linear), grad, indices, (lr, l1, l2, l2_shrinkage, lr_power), unique_indices)
+  _apply("group_ftrl_v2", (var, accum, linear), grad, indices, (lr, l1, l2, l2_shrinkage, lr_power), unique_indices,
+         unique_count=unique_count)
 
 
 def kv_variable_group_sparse_apply_rectified_adam(var, opt, grad, indices, lr, beta1_power, beta2_power, beta1, beta2,
                                                   epsilon, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov,
-                                                  use_locking=False, name=None, unique_indices=False, token=None):
+                                                  use_locking=False, name=None, unique_indices=False, token=None,
+                                                  unique_count=None):
   """REGISTER_OP("KvVariableGroupSparseApplyRectifiedAdam") ops/training_ops.cc:1194-1217: `opt` is one slot table of
   dim 5 x the var's, m | v | linear | vhat | vamsgrad (kvhip.h kv_apply_group_rectified_adam).  token: the batch token of
   the lookup of the same ids (default: the one the var's last lookup of this very tensor left)."""
   _apply("group_rectified_adam", (var, opt), grad, indices,
          (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, bool(tractable), bool(amsgrad),
-          bool(use_nesterov)), unique_indices, token)
+          bool(use_nesterov)), unique_indices, token, unique_count)
 
 
-def kv_dedup_segment_sum(table_handle, indices, grad):
+def kv_dedup_segment_sum(table_handle, indices, grad, sync=True):
   """tf.unique + tf.unsorted_segment_sum (TF-core _deduplicate_indexed_slices) on the GPU.
-  Returns (unique_ids [U], summed [U, dim], inverse [n])."""
+  Returns (unique_ids [U], summed [U, dim], inverse [n]).  sync=False leaves U on the device (kv_dedup_segment_sum_dev):
+  returns (ids [n] of which the first U are valid, summed [n, dim], inverse [n], U as a 1-element int64 device tensor)
+  without waiting for the stream — what the optimizer wrappers take as unique_count."""
   g, ids = _grad_ids(table_handle, grad, indices)
   n = ids.numel()
   dev = _dev(table_handle)
   uniq = torch.empty(n, dtype=torch.int64, device=dev)
   summed = torch.empty((n, table_handle.dim), dtype=torch.float32, device=dev)
   inv = torch.empty(n, dtype=torch.int32, device=dev)
+  if not sync:
+    nu_dev = torch.empty(1, dtype=torch.int64, device=dev)
+    _lib.check(_lib.lib().kv_dedup_segment_sum_dev(table_handle.ptr, _p(ids), _p(g), n, _p(uniq), _p(summed), _p(inv),
+                                                   _p(nu_dev), _stream(table_handle)))
+    return uniq, summed, inv, nu_dev
   nu = ctypes.c_int64()
   _lib.check(_lib.lib().kv_dedup_segment_sum(table_handle.ptr, _p(ids), _p(g), n, _p(uniq), _p(summed),
                                              _p(inv), ctypes.byref(nu), _stream(table_handle)))
@@ -1088,7 +1143,7 @@ class KvShard(object):
 
   def apply(self, comm, optimizer, slots, grad, hp, join=True):
     g = _f32(self.table, grad)
-    arr = (ctypes.c_float * len(hp))(*[float(np.float32(x)) for x in hp])
+    arr = _hp_array(hp)
     s0 = slots[0].ptr
     s1 = slots[1].ptr if len(slots) > 1 else None
     _lib.check(_lib.lib().kv_shard_apply(self.ptr, comm.ptr, int(optimizer), s0, s1, _p(g), arr, int(bool(join)), _stream(self.table)))
@@ -1117,7 +1172,7 @@ class KvShard(object):
     self._keep_g = g
 
   def apply_serve(self, optimizer, slots, hp):
-    arr = (ctypes.c_float * len(hp))(*[float(np.float32(x)) for x in hp])
+    arr = _hp_array(hp)
     s1 = slots[1].ptr if len(slots) > 1 else None
     _lib.check(_lib.lib().kv_shard_apply_serve(self.ptr, int(optimizer), slots[0].ptr, s1, arr, _stream(self.table)))
 
@@ -1148,7 +1203,7 @@ def kv_multi_shard_apply(shards, comm, optimizer, slots_list, grads, hp, join=Tr
   two = all(len(sl) > 1 for sl in slots_list)
   s1 = (ctypes.c_void_p * T)(*[sl[1].ptr for sl in slots_list]) if two else None
   gp = (ctypes.c_void_p * T)(*[_p(g) for g in gs])
-  hpa = (ctypes.c_float * len(hp))(*[float(np.float32(x)) for x in hp])
+  hpa = _hp_array(hp)
   _lib.check(_lib.lib().kv_multi_shard_apply(arr, T, comm.ptr, int(optimizer), s0, s1, gp, hpa, int(bool(join)), _stream(shards[0].table)))
   for sh, g in zip(shards, gs):
     sh._keep_g = g
