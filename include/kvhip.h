@@ -584,6 +584,44 @@ int kv_multi_lookup_sparse_grad(int num_tables, const kv_handle_t* tables, const
                                 const int64_t* ns, const int64_t* num_segments, int combiner,
                                 float* const* values, kv_stream_t stream);
 
+/* embedding_lookup_sparse on a KvVariable OUTSIDE training, in one launch.  The reference runs unique ->
+ * KvVariableGatherOrZerosV2 (python/ops/kv_variable_ops.py:1072-1080, 1105-1113) -> gather(idx) -> (x weights) ->
+ * segment_sum / sparse_segment_{sum,mean,sqrt_n} (python/ops/embedding_ops.py:359-441).  Arguments as kv_lookup_sparse.
+ * Result: out[s, :] = the combiner over the positions j of segment s, in position order, of w_j * row(ids[j]), where
+ * row() is exactly what kv_gather_or_zeros returns for that id: zeros for a missing key, a blacklisted key and a key under
+ * the enter threshold.  The accumulator starts at +0 in float32; one multiply-add per position and element (the compiler
+ * may fuse it).  mean divides by the float32 sum of w_j, sqrtn by sqrtf of the float32 sum of w_j * w_j, both taken from
+ * +0 in position order; weights == NULL means w_j = 1.  Zero rows of missing keys count in the denominators, as in the
+ * reference's chain.
+ * Empty segments follow kv_lookup_sparse: unweighted a zero row, weighted mean / sqrtn 0/0 as IEEE gives it.  n == 0 with
+ * num_segments > 0 writes every segment by that rule (weights == NULL is accepted); num_segments == 0 is a no-op.
+ * segment_ids are ascending, int32 or int64.  Ids outside [0, num_segments) are clamped the way kv_lookup_sparse clamps
+ * them (negative ids count towards segment 0, ids >= num_segments towards none) — memory safety only.  A list that is not
+ * ascending gives unspecified values, never a read or write outside the caller's buffers.
+ * No side effects: no insert, no frequency / day / flag / delta-list change, no batch token touched, no workspace taken
+ * from the table; slot mirrors stay as they are.  Any dim the library supports; 0 <= n < 2^31 (there is no workspace, so
+ * the limits of the index pipelines do not apply) and 0 <= num_segments <= 2^31 - 2, as in kv_lookup_sparse; ids are int32
+ * for KV_DT_INT32 tables, int64 otherwise.  Checks, in order, before anything is queued: the handle,
+ * KV_FAILED_PRECONDITION for an uninitialised table, null pointers, sizes outside those ranges, a segment dtype other than
+ * int32 / int64, a combiner other than 0 / 1 / 2 (all KV_INVALID_ARGUMENT), then KV_UNIMPLEMENTED for a table whose dim the
+ * library does not serve (a multiple of 4 above 1024, any other dim above 256).
+ * Asynchronous.  Only the kernel is queued: the call is capturable in a HIP graph with no precondition.  Tables in
+ * occurrence-order mode are served like any other (the mode is about gradient sums).
+ * Not a reference op: the Python mirror calls it; a TF graph needs the rewrite the training sparse lookup needs. */
+int kv_lookup_sparse_zeros(kv_handle_t h, const void* ids, const void* segment_ids, int segment_dtype,
+                           const float* weights, int64_t n, int64_t num_segments, int combiner,
+                           float* out, kv_stream_t stream);
+/* kv_lookup_sparse_zeros on many tables with ONE kernel launch whatever num_tables is: table i gets exactly the bits the
+ * single-table op gives it.  One device; the tables are free to differ in dim and key dtype, as in
+ * kv_batch_gather_or_zeros, and the same table may be listed more than once (it is only read).  One segment dtype and one
+ * combiner per call.  `weights` may be NULL, and so may weights[i].  The tables are entered as kv_batch_gather_or_zeros
+ * enters them: a table's deferred error is reported here.  num_tables < 1 and null argument arrays are
+ * KV_INVALID_ARGUMENT; every table's arguments are checked as above before anything is queued. */
+int kv_batch_lookup_sparse_zeros(int num_tables, const kv_handle_t* tables, const void* const* ids,
+                                 const void* const* segment_ids, int segment_dtype, const float* const* weights,
+                                 const int64_t* ns, const int64_t* num_segments, int combiner,
+                                 float* const* outs, kv_stream_t stream);
+
 /* tf.unsorted_segment_sum(data [n, dim], segment_ids [n] int32, num_segments) on the batch pipeline
  * (no float atomics: a segment named by 100 000 rows costs the same as 100 000 segments): out
  * [num_segments, dim]; segments nobody names are zero rows, ids outside [0, num_segments) are

@@ -105,6 +105,8 @@ SIGNATURES = {
     "kv_lookup_sparse_grad": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _vp, _vp]),
     "kv_multi_lookup_sparse": (_i32, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "kv_multi_lookup_sparse_grad": (_i32, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "kv_lookup_sparse_zeros": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _vp, _vp]),
+    "kv_batch_lookup_sparse_zeros": (_i32, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "kv_unsorted_segment_sum": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "kv_take_rows": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "kv_gather_or_insert_pairs": (_i32, [_vp, _vp, _i64, _vp, _vp]),

@@ -1,5 +1,6 @@
 // kv_op_kernels.h — the small kernels only the table ops (kv_ops.hip) launch: point queries, delete, export / import /
-// delta, the inference gathers, unique / dedup helpers, the sparse lookup's combiners, its backward and their batched forms,
+// delta, the inference gathers, unique / dedup helpers, the sparse lookup's combiners, its backward and their batched forms, the
+// serving-mode sparse lookup (kv_lookup_sparse_zeros),
 // kv_take_rows.  Included by kv_ops.hip
 // alone, behind kv_device.h, inside its anonymous namespace.
 #pragma once
@@ -397,6 +398,190 @@ __global__ void __launch_bounds__(TB) k_seg_combine(TableDev t, WsDev w, const u
       }
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// kv_lookup_sparse_zeros: embedding_lookup_sparse outside training (python/ops/kv_variable_ops.py:1072-1080, 1105-1113:
+// unique -> KvVariableGatherOrZerosV2; embedding_ops.py:359-441: gather(idx) -> (x weights) -> segment_sum /
+// sparse_segment_{sum,mean,sqrt_n}) in ONE launch, read-only: no dedup, no offsets pass, no workspace.
+//   out[s] = combine_j( w_j * row(id_j) ) over the segment's positions in position order, row() = what
+//   k_gather_or_zeros reads (row 0, the zero row, for a key the index does not hold)
+// A group of LPS lanes owns a segment (VQ lanes, one float4 each, for dims 4 * VQ; VQ == 0: the whole wave, lane v owns
+// elements v, v + 64, ... of any dim up to 1024).  Two things differ from k_seg_combine:
+//  * segment bounds: lo(s) = lower_bound(segment_ids, s), searched by the group's lane 0; hi(s) = lo(s + 1) comes from
+//    the next group of the wave by shuffle, and the wave's last bound is searched by the last group's lane 1 in the same
+//    loop (VQ == 1 has no such lane: there lane 63 searches twice).  Clamped like seg_offsets_body: lo(s <= 0) = 0,
+//    lo(s >= nseg) = lower_bound(nseg), so every position is in [0, n] whatever the list holds.
+//    Cost, DERIVED and not measured: at most log2(n) dependent loads per bound, L2-resident after the first waves
+//    (~200 cycles an L2 hit), i.e. 11-18 hops = 1-1.5 us at serving sizes (2 k - 200 k ids), all groups' searches in
+//    flight together — below the ~6 us of the launch boundary a separate offsets kernel would add, and without the
+//    workspace bookkeeping that would bar graph capture.
+//  * row lookup: there is no entry list.  Lane u of the group probes position pos + u (LPS probes of a group in flight,
+//    none repeated by a neighbour), the row numbers and weights go round by shuffle, SU rows in flight per lane; the
+//    additions stay in position order.  Rows are plain loads (repeated keys hit L2), out is written once, streaming.
+//    The probe is NOT software-pipelined across chunks as goz_wave's is: a chunk of LPS positions pays id -> entry -> row
+//    before the next chunk's probe starts, so with small groups (dim 4 / 8: LPS 1 / 2) a long segment advances one or two
+//    positions per three hops.  At serving shapes (1-8 ids per segment, dims 64 / 128) a segment is one chunk; measured
+//    there (profiles/serving_sparse.txt) the batched launch takes 2.3-3.3x the plain batched gather of the same ids: the
+//    bound search and the probe are one dependent chain per wave step.  Pipelining both across a wave's steps, as
+//    goz_wave does, is the next step for this kernel.
+// No LDS, no atomics, no float reduction across lanes.
+__device__ __forceinline__ int lsz_lower_bound(const void* __restrict__ seg, int seg32, int n, long long s) {
+  int a = 0, b = n;
+  while (a < b) {
+    const int m = a + ((b - a) >> 1);
+    const long long x = seg32 ? (long long)reinterpret_cast<const int*>(seg)[m] : reinterpret_cast<const long long*>(seg)[m];
+    if (x < s) a = m + 1; else b = m;
+  }
+  return a;
+}
+__device__ __forceinline__ int lsz_bound(const void* __restrict__ seg, int seg32, int n, long long nseg, long long s) {
+  return s <= 0 ? 0 : lsz_lower_bound(seg, seg32, n, s < nseg ? s : nseg);
+}
+
+template <int VQ>
+__device__ __forceinline__ void lsz_body(const TableDev& t, const void* __restrict__ ids, int ids32,
+                                         const void* __restrict__ seg, int seg32, const float* __restrict__ wts,
+                                         int n, long long nseg, int combiner, float* __restrict__ out,
+                                         long long blk, long long nblk) {
+  constexpr int LPS = VQ > 0 ? VQ : 64;     // lanes per segment
+  constexpr int G = 64 / LPS;               // segments per wave and step
+  constexpr int SU = LPS < 4 ? LPS : 4;     // rows in flight per lane
+  constexpr int NE = 16;                    // VQ == 0: elements per lane at the most (dim <= 1024)
+  const int D = t.dim;
+  const int lane = threadIdx.x & 63;
+  const int v = lane % LPS, sub = lane / LPS, gbase = sub * LPS;
+  const int kmax = VQ > 0 ? 0 : (D + 63) >> 6;
+  const long long wave = blk * (blockDim.x / 64) + (threadIdx.x >> 6);
+  const long long nwaves = nblk * (blockDim.x / 64);
+  for (long long base = wave * G; base < nseg; base += nwaves * G) {   // wave-uniform
+    const long long sgi = base + sub;
+    // the bounds: lane 0 of each group its segment's first position, the wave's last bound beside them
+    int b0 = 0, b1 = 0;
+    if (v == 0) b0 = lsz_bound(seg, seg32, n, nseg, sgi);
+    else if (LPS > 1 && lane == 64 - LPS + 1) b0 = lsz_bound(seg, seg32, n, nseg, base + G);
+    if (LPS == 1 && lane == 63) b1 = lsz_bound(seg, seg32, n, nseg, base + G);
+    const int lo = __shfl(b0, gbase);
+    const int hi_next = __shfl(b0, sub < G - 1 ? gbase + LPS : gbase);
+    const int hi_last = LPS > 1 ? __shfl(b0, 64 - LPS + 1) : __shfl(b1, 63);
+    const int hi = sub < G - 1 ? hi_next : hi_last;
+    const int len = sgi < nseg && hi > lo ? hi - lo : 0;   // (a list that is not ascending may give hi < lo: nothing is read)
+    float wsum = 0.f, w2 = 0.f;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    float accs[VQ > 0 ? 1 : NE];
+    if constexpr (VQ == 0) {
+#pragma unroll
+      for (int k = 0; k < NE; ++k) accs[k] = 0.f;
+    }
+    unsigned pos = (unsigned)lo;   // the chunk's first position; rem: the segment's positions from there on
+    for (int rem = len; __any(rem > 0); rem -= LPS, pos += LPS) {
+      // lane v: the probe of position pos + v (row 0, weight 0 past the segment's end)
+      const bool live = v < rem;
+      unsigned r = 0u;
+      float wv = 0.f;
+      if (live) {
+        const unsigned p = pos + v;
+        const long long key = ids32 ? (long long)reinterpret_cast<const int*>(ids)[p] : reinterpret_cast<const long long*>(ids)[p];
+        wv = wts ? wts[p] : 1.f;
+        r = table_find(t, key);
+      }
+      for (int u0 = 0; u0 < LPS && __any(u0 < rem); u0 += SU) {
+        unsigned ru[SU];
+        float wu[SU];
+#pragma unroll
+        for (int u = 0; u < SU; ++u) { ru[u] = __shfl(r, gbase + u0 + u); wu[u] = __shfl(wv, gbase + u0 + u); }
+        if constexpr (VQ > 0) {
+          float4 x[SU];
+#pragma unroll
+          for (int u = 0; u < SU; ++u) x[u] = reinterpret_cast<const float4*>(row_ptr(t, ru[u]))[v];
+#pragma unroll
+          for (int u = 0; u < SU; ++u) {
+            if (u0 + u >= rem) continue;
+            acc.x += x[u].x * wu[u]; acc.y += x[u].y * wu[u]; acc.z += x[u].z * wu[u]; acc.w += x[u].w * wu[u];
+            wsum += wu[u]; w2 += wu[u] * wu[u];
+          }
+        } else {
+          const float* rowp[SU];
+#pragma unroll
+          for (int u = 0; u < SU; ++u) rowp[u] = row_ptr(t, ru[u]);
+#pragma unroll
+          for (int k = 0; k < NE; ++k) {
+            if (k < kmax) {   // wave-uniform
+              const int e = v + (k << 6);
+              float x[SU];
+#pragma unroll
+              for (int u = 0; u < SU; ++u) x[u] = e < D ? rowp[u][e] : 0.f;
+#pragma unroll
+              for (int u = 0; u < SU; ++u)
+                if (u0 + u < rem) accs[k] += x[u] * wu[u];
+            }
+          }
+#pragma unroll
+          for (int u = 0; u < SU; ++u)
+            if (u0 + u < rem) { wsum += wu[u]; w2 += wu[u] * wu[u]; }
+        }
+      }
+    }
+    if (sgi >= nseg) continue;
+    float den = 1.f;
+    if (combiner == 1) den = wsum; else if (combiner == 2) den = sqrtf(w2);
+    const bool divide = combiner != 0 && (wts || len > 0);
+    if constexpr (VQ > 0) {
+      if (divide) { acc.x /= den; acc.y /= den; acc.z /= den; acc.w /= den; }
+      float4* dst = reinterpret_cast<float4*>(out + (size_t)sgi * D) + v;
+      __builtin_nontemporal_store(acc.x, &dst->x); __builtin_nontemporal_store(acc.y, &dst->y);
+      __builtin_nontemporal_store(acc.z, &dst->z); __builtin_nontemporal_store(acc.w, &dst->w);
+    } else {
+#pragma unroll
+      for (int k = 0; k < NE; ++k) {
+        const int e = v + (k << 6);
+        if (e < D) __builtin_nontemporal_store(divide ? accs[k] / den : accs[k], out + (size_t)sgi * D + e);
+      }
+    }
+  }
+}
+// the lookup for any dim behind one entry, as goz_any: VQ lanes per segment for dims 4, 8, ..., 256, else the whole wave
+__device__ __forceinline__ void lsz_any(const TableDev& t, const void* __restrict__ ids, int ids32,
+                                        const void* __restrict__ seg, int seg32, const float* __restrict__ wts, int n,
+                                        long long nseg, int combiner, float* __restrict__ out, long long blk, long long nblk) {
+  const int D = t.dim;
+  if ((D & 3) == 0) {  // block-uniform
+    switch (D >> 2) {
+      case 1: lsz_body<1>(t, ids, ids32, seg, seg32, wts, n, nseg, combiner, out, blk, nblk); return;
+      case 2: lsz_body<2>(t, ids, ids32, seg, seg32, wts, n, nseg, combiner, out, blk, nblk); return;
+      case 4: lsz_body<4>(t, ids, ids32, seg, seg32, wts, n, nseg, combiner, out, blk, nblk); return;
+      case 8: lsz_body<8>(t, ids, ids32, seg, seg32, wts, n, nseg, combiner, out, blk, nblk); return;
+      case 16: lsz_body<16>(t, ids, ids32, seg, seg32, wts, n, nseg, combiner, out, blk, nblk); return;
+      case 32: lsz_body<32>(t, ids, ids32, seg, seg32, wts, n, nseg, combiner, out, blk, nblk); return;
+      case 64: lsz_body<64>(t, ids, ids32, seg, seg32, wts, n, nseg, combiner, out, blk, nblk); return;
+      default: break;
+    }
+  }
+  lsz_body<0>(t, ids, ids32, seg, seg32, wts, n, nseg, combiner, out, blk, nblk);
+}
+template <int VQ>
+__global__ void __launch_bounds__(TB) k_lookup_sparse_zeros(TableDev t, const void* __restrict__ ids, int ids32,
+                                                            const void* __restrict__ seg, int seg32,
+                                                            const float* __restrict__ wts, int n, long long nseg,
+                                                            int combiner, float* __restrict__ out) {
+  lsz_body<VQ>(t, ids, ids32, seg, seg32, wts, n, nseg, combiner, out, blockIdx.x, gridDim.x);
+}
+// the batched form: blockIdx.y = table, tables free to differ in dim and key dtype; a table's blocks past its own
+// segments leave at once
+struct BatchSparseZerosDesc {
+  TableDev t;
+  const void* ids;
+  const void* seg;
+  const float* wts;
+  float* out;
+  long long nseg;
+  int n;
+  int ids_int32;
+};
+__global__ void __launch_bounds__(TB) k_batch_lookup_sparse_zeros(const BatchSparseZerosDesc* __restrict__ descs,
+                                                                  int seg32, int combiner) {
+  const BatchSparseZerosDesc& d = descs[blockIdx.y];
+  lsz_any(d.t, d.ids, d.ids_int32, d.seg, seg32, d.wts, d.n, d.nseg, combiner, d.out, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -473,6 +473,28 @@ static int multi_sparse_checks(int num_tables, const kv_handle_t* tables, const 
   }
   return KV_OK;
 }
+
+// kv_lookup_sparse_zeros / kv_batch_lookup_sparse_zeros: the checks of one table's arguments, in the order of the header
+static int sparse_zeros_checks(const kv_table* t, const void* ids, const void* segment_ids, int segment_dtype, int64_t n,
+                               int64_t num_segments, int combiner, const float* out) {
+  int rc;
+  if ((rc = require_initialized(t))) return rc;   // FindOrZeros -> CheckInitializedInternal (kv_variable.h:242)
+  if (num_segments > 0 && (!out || (n > 0 && (!ids || !segment_ids))))
+    return fail(KV_INVALID_ARGUMENT, "ids / segment ids / output pointer is null");
+  if (n < 0 || n >= (1ll << 31)) return fail(KV_INVALID_ARGUMENT, "sp_ids: %lld values (fewer than 2^31 per call)", (long long)n);
+  if (num_segments < 0 || num_segments > (1ll << 31) - 2) return fail(KV_INVALID_ARGUMENT, "bad num_segments");
+  if (segment_dtype != KV_DT_INT32 && segment_dtype != KV_DT_INT64)
+    return fail(KV_INVALID_ARGUMENT, "segment ids must be int32 or int64");
+  if (combiner < KV_COMBINER_SUM || combiner > KV_COMBINER_SQRTN)
+    return fail(KV_INVALID_ARGUMENT, "combiner must be one of 'mean', 'sqrtn' or 'sum'");  // embedding_ops.py:345
+  if (!dim_supported(t->dim)) return fail(KV_UNIMPLEMENTED, "embedding dim %d not supported", t->dim);
+  return KV_OK;
+}
+// lanes of a segment's group in lsz_body: dim / 4 for the dims 4, 8, ..., 256, else (0) the whole wave
+static int sparse_zeros_lanes(int D) {
+  const int q = D / 4;
+  return ((D & 3) == 0 && q >= 1 && q <= 64 && (q & (q - 1)) == 0) ? q : 0;
+}
 }  // namespace
 
 namespace __attribute__((visibility("hidden"))) kvhip_internal {
@@ -889,6 +911,75 @@ int kv_batch_gather_or_zeros(int num_tables, const kv_handle_t* tables, const vo
   if ((rc = hd.upload(s, &md))) return rc;
   dim3 grid((unsigned)nblocks(nmax, TB / 8, 2048), (unsigned)num_tables);
   k_batch_gather_or_zeros<<<grid, TB, 0, s>>>(md);
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+int kv_lookup_sparse_zeros(kv_handle_t t, const void* ids, const void* segment_ids, int segment_dtype,
+                           const float* weights, int64_t n, int64_t num_segments, int combiner, float* out,
+                           kv_stream_t stream) {
+  int rc;
+  if ((rc = check_table(t))) return rc;
+  if ((rc = sparse_zeros_checks(t, ids, segment_ids, segment_dtype, n, num_segments, combiner, out))) return rc;
+  if (num_segments == 0) return KV_OK;
+  TableOp op(t, stream);
+  const hipStream_t s = op.s;
+  // a read, entered like kv_gather_or_zeros: behind the table's last op on whatever stream, no serial bump, no workspace;
+  // as a var the table keeps its mirrors.  Only the kernel is queued: capturable with no precondition
+  if ((rc = hand_over(t, s, KEEP_VAR, true, false))) return rc;
+  const TableDev td = dev_view(t);
+  const int q = sparse_zeros_lanes(t->dim);
+  const int grid = nblocks(num_segments * (q ? q : 64), TB, 8192);
+  const int ids32 = t->key_dtype == KV_DT_INT32, seg32 = segment_dtype == KV_DT_INT32;
+  if (q)
+    with_lanes(q, [&](auto vq) {
+      k_lookup_sparse_zeros<decltype(vq)::value><<<grid, TB, 0, s>>>(td, ids, ids32, segment_ids, seg32, weights, (int)n,
+                                                                    num_segments, combiner, out);
+    });
+  else
+    k_lookup_sparse_zeros<0><<<grid, TB, 0, s>>>(td, ids, ids32, segment_ids, seg32, weights, (int)n, num_segments, combiner, out);
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+int kv_batch_lookup_sparse_zeros(int num_tables, const kv_handle_t* tables, const void* const* ids,
+                                 const void* const* segment_ids, int segment_dtype, const float* const* weights,
+                                 const int64_t* ns, const int64_t* num_segments, int combiner,
+                                 float* const* outs, kv_stream_t stream) {
+  int rc;
+  if ((rc = check_same_shape(num_tables, tables, "tables"))) return rc;
+  if (!ids || !segment_ids || !ns || !num_segments || !outs) return fail(KV_INVALID_ARGUMENT, "null argument array");
+  for (int i = 0; i < num_tables; ++i)
+    if ((rc = sparse_zeros_checks(tables[i], ids[i], segment_ids[i], segment_dtype, ns[i], num_segments[i], combiner, outs[i])))
+      return rc;
+  const int device = tables[0]->device;
+  DeviceGuard dg(device);
+  hipStream_t s = (hipStream_t)stream;
+  MultiLock lock(std::vector<kv_table*>(tables, tables + num_tables));   // (a table listed twice is locked and entered once)
+  // entered like kv_batch_gather_or_zeros: every table is read on the op's stream, and reports its deferred error
+  for (kv_table* tb : lock.ts)
+    if ((rc = enter_op(tb, s, KEEP_VAR, true, false))) return rc;
+  Staged<BatchSparseZerosDesc> hd(device, 0, num_tables);
+  if (hd.rc) return hd.rc;
+  long long work = 0;   // lanes of the table with the most of them
+  for (int i = 0; i < num_tables; ++i) {
+    BatchSparseZerosDesc& d = hd[i];
+    const int q = sparse_zeros_lanes(tables[i]->dim);
+    d.t = dev_view(tables[i]);
+    d.ids = ids[i];
+    d.seg = segment_ids[i];
+    d.wts = weights ? weights[i] : nullptr;
+    d.out = outs[i];
+    d.nseg = num_segments[i];
+    d.n = (int)ns[i];
+    d.ids_int32 = tables[i]->key_dtype == KV_DT_INT32;
+    work = std::max<long long>(work, num_segments[i] * (q ? q : 64));
+  }
+  if (work == 0) return KV_OK;
+  const BatchSparseZerosDesc* md;
+  if ((rc = hd.upload(s, &md))) return rc;
+  dim3 grid((unsigned)nblocks(work, TB, 4096), (unsigned)num_tables);
+  k_batch_lookup_sparse_zeros<<<grid, TB, 0, s>>>(md, segment_dtype == KV_DT_INT32, combiner);
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }

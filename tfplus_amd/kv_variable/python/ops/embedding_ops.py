@@ -84,9 +84,31 @@ def _segment_sum(data, segment_ids, n):
   return out.index_add(0, segment_ids, data)
 
 
+def _num_segments(indices_list):
+  """last segment id + 1 of each sp_ids.indices (0 for an empty one).  Indices that live on the host are read there; those
+  on a device cost ONE device-to-host copy for the whole list, not one per feature."""
+  out, on_dev = [0] * len(indices_list), []
+  for k, ind in enumerate(indices_list):
+    if isinstance(ind, torch.Tensor) and ind.is_cuda:
+      if ind.shape[0]:
+        on_dev.append((k, ind[:, 0].max()))
+    else:
+      t = torch.as_tensor(ind)
+      out[k] = int(t[:, 0].max()) + 1 if t.shape[0] else 0
+  if on_dev:
+    dev = on_dev[0][1].device
+    for (k, _), m in zip(on_dev, torch.stack([m.to(dev).to(torch.int64) for _, m in on_dev]).tolist()):
+      out[k] = int(m) + 1
+  return out
+
+
 def embedding_lookup_sparse(params, sp_ids, sp_weights, partition_strategy="mod", name=None,
                             combiner=None, max_norm=None):
-  """embedding_ops.py:279-441: unique ids -> lookup -> (weighted) segment sum / mean / sqrtn."""
+  """embedding_ops.py:279-441: unique ids -> lookup -> (weighted) segment sum / mean / sqrtn.  One KvVariable without
+  max_norm takes one fused native call: kv_lookup_sparse when training (up to 2^21 ids), kv_lookup_sparse_zeros in
+  inference mode (read-only, one launch, any number of ids).  Partitioned variables and max_norm take the op chain.
+  The segment count is the last segment id + 1, as in the reference: sp_ids.indices on the host cost nothing, indices on
+  a device cost one device-to-host copy in front of the call (embedding_lookup_sparse_multi pays it once for all features)."""
   if combiner is None:
     combiner = "mean"
   if combiner not in ("mean", "sqrtn", "sum"):
@@ -100,10 +122,11 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, partition_strategy="mod"
   seg = torch.as_tensor(sp_ids.indices).to(dev)[:, 0].to(torch.int64)
   ids = torch.as_tensor(sp_ids.values).to(dev)
   need_counts = plist[0].enter_threshold > 0
-  nseg = int(seg.max().item()) + 1 if seg.numel() else 0
-  if (len(plist) == 1 and max_norm is None and kv_variable_ops.IS_TRAINING and hasattr(plist[0], "lookup_sparse")
-      and 0 < ids.numel() <= (1 << 21)):
-    # one table, training: the whole chain is one fused call (dedup + lookup + combine on the GPU)
+  nseg = _num_segments([sp_ids.indices])[0]
+  if (len(plist) == 1 and max_norm is None and hasattr(plist[0], "lookup_sparse")
+      and 0 < ids.numel() and (not kv_variable_ops.IS_TRAINING or ids.numel() <= (1 << 21))):
+    # one table: the whole chain is one fused call (training: dedup + lookup + combine; inference: probe + combine, and
+    # the training pipeline's bound on the ids does not apply)
     return plist[0].lookup_sparse(ids, seg, None if sp_weights is None else sp_weights.values, nseg, combiner,
                                   need_counts)
   uniq, idx, cnt = torch.unique(ids, return_inverse=True, return_counts=True)
@@ -126,9 +149,12 @@ def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None
   """[embedding_lookup_sparse(p, i, w, combiner=combiner) for p, i, w in zip(...)] — one KvVariable per feature — with
   the features that take the fused path grouped by (device, dim, key dtype): one batched forward per group
   (kv_multi_lookup_sparse: four launches whatever the group's size) under one autograd function, whose backward is one
-  kv_multi_lookup_sparse_grad per group and files one IndexedSlices on each variable.  A feature the fused path does not
-  take — a partitioned variable, max_norm, inference mode, more ids than one call takes, a variable some earlier feature
-  of its group already uses — goes through embedding_lookup_sparse as it is."""
+  kv_multi_lookup_sparse_grad per group and files one IndexedSlices on each variable.  In inference mode the groups are
+  the devices — dims and key dtypes may differ, a variable may serve several features — and a group is ONE read-only
+  launch (kv_batch_lookup_sparse_zeros).  The segment counts of all fused features are read in one go (_num_segments: at
+  most one device-to-host copy per call, none for indices on the host).  A feature the fused path does not take — a
+  partitioned variable, max_norm, in training mode more ids than one call takes or a variable some earlier feature of its
+  group already uses — goes through embedding_lookup_sparse as it is."""
   if combiner is None:
     combiner = "mean"
   if combiner not in ("mean", "sqrtn", "sum"):
@@ -139,7 +165,7 @@ def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None
   if nf != len(sp_ids_list) or nf != len(sp_weights_list):
     raise ValueError("params_list, sp_ids_list (and sp_weights_list) must be equally long")
   out = [None] * nf
-  groups = collections.OrderedDict()   # (device, dim, key dtype, takes gradients) -> [(feature, var, ids, seg, weights, nseg)]
+  groups = collections.OrderedDict()   # (device, dim, key dtype, takes gradients) or, in inference mode, (device,) -> [(feature, var, ids, seg, weights, nseg)]
   for f, (params, sp_ids, sp_w) in enumerate(zip(params_list, sp_ids_list, sp_weights_list)):
     plist = _as_list(params)
     if not isinstance(sp_ids, SparseTensor):
@@ -148,15 +174,19 @@ def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None
       raise TypeError("sp_weights must be either None or SparseTensor")
     var = plist[0]
     n = torch.as_tensor(sp_ids.values).numel()
-    fused = (len(plist) == 1 and max_norm is None and kv_variable_ops.IS_TRAINING and hasattr(var, "lookup_sparse")
-             and 0 < n <= (1 << 21))
-    key = (var.device, var.embedding_dim, var.key_dtype, var.trainable) if fused else None
-    if not fused or any(e[1] is var for e in groups.get(key, ())):
+    training = kv_variable_ops.IS_TRAINING
+    fused = (len(plist) == 1 and max_norm is None and hasattr(var, "lookup_sparse")
+             and 0 < n and (not training or n <= (1 << 21)))
+    key = None if not fused else (var.device, var.embedding_dim, var.key_dtype, var.trainable) if training else (var.device,)
+    if not fused or (training and any(e[1] is var for e in groups.get(key, ()))):
       out[f] = embedding_lookup_sparse(plist, sp_ids, sp_w, combiner=combiner, max_norm=max_norm)
       continue
     seg = torch.as_tensor(sp_ids.indices).to(var.device)[:, 0].to(torch.int64)
-    groups.setdefault(key, []).append((f, var, torch.as_tensor(sp_ids.values).to(var.device), seg,
-                                       None if sp_w is None else sp_w.values, int(seg.max().item()) + 1))
+    groups.setdefault(key, []).append([f, var, torch.as_tensor(sp_ids.values).to(var.device), seg,
+                                       None if sp_w is None else sp_w.values, sp_ids.indices])
+  fused_members = [m for members in groups.values() for m in members]
+  for m, nseg in zip(fused_members, _num_segments([m[5] for m in fused_members])):   # one host read for all features
+    m[5] = nseg
   for members in groups.values():
     res = kv_variable_ops.lookup_sparse_multi([m[1] for m in members], [m[2] for m in members], [m[3] for m in members],
                                               [m[4] for m in members], [m[5] for m in members], combiner,

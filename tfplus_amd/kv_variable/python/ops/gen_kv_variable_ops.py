@@ -871,6 +871,37 @@ def kv_multi_lookup_sparse_grad(table_handles, seg_grads, segment_ids, weights, 
   return outs
 
 
+def kv_variable_lookup_sparse_zeros(table_handle, ids, segment_ids, weights, num_segments, combiner="mean"):
+  """embedding_lookup_sparse on one KvVariable outside training, in one kernel launch: GatherOrZeros rows (missing,
+  blacklisted and under-threshold keys read zeros) -> weighted segment sum / mean / sqrtn in position order.  Read-only:
+  nothing is inserted or counted.  segment_ids ascending; returns [num_segments, dim] (kvhip.h kv_lookup_sparse_zeros)."""
+  if combiner not in _COMBINERS:
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  ids = _ids(table_handle, ids).reshape(-1)
+  seg, w = _sparse_args(table_handle, ids.numel(), segment_ids, weights)
+  out = torch.empty((int(num_segments), table_handle.dim), dtype=torch.float32, device=_dev(table_handle))
+  _lib.check(_lib.lib().kv_lookup_sparse_zeros(table_handle.ptr, _p(ids), _p(seg), _TORCH_KEY[seg.dtype], _p(w),
+                                               ids.numel(), int(num_segments), _COMBINERS[combiner], _p(out),
+                                               _stream(table_handle)))
+  return out
+
+
+def batch_kv_variable_lookup_sparse_zeros(table_handles, ids, segment_ids, weights, num_segments, combiner="mean"):
+  """[kv_variable_lookup_sparse_zeros(t, i, s, w, n, combiner) for ...] with one kernel launch for all tables (one device;
+  dims and key dtypes free to differ; a table may be listed more than once).  weights: None, or a list whose entries may
+  be None.  Returns the list of [num_segments[i], dim_i] outputs."""
+  n = len(table_handles)
+  if n != len(ids):
+    raise _lib.InvalidArgumentError("table_handles and ids must be equally long, N >= 1")
+  idl = [_ids(h, i).reshape(-1) for h, i in zip(table_handles, ids)]
+  seg, w, hp, segp, segdt, wp, ns, nsegs = _multi_sparse_args(table_handles, [i.numel() for i in idl], segment_ids, weights,
+                                                            num_segments, combiner)
+  outs = [torch.empty((int(m), h.dim), dtype=torch.float32, device=_dev(h)) for h, m in zip(table_handles, num_segments)]
+  _lib.check(_lib.lib().kv_batch_lookup_sparse_zeros(n, hp, _ptr_array(idl), segp, segdt, wp, ns, nsegs,
+                                                     _COMBINERS[combiner], _ptr_array(outs), _stream(table_handles[0])))
+  return outs
+
+
 def kv_unsorted_segment_sum(table_handle, data, segment_ids, num_segments):
   """tf.unsorted_segment_sum on the GPU batch pipeline: [num_segments, dim] fp32."""
   d = _f32(table_handle, data).reshape(-1, table_handle.dim)

@@ -88,13 +88,17 @@ class _MultiSparseLookupGrad(torch.autograd.Function):
 
 
 def lookup_sparse_multi(vars_, ids, segment_ids, weights, num_segments, combiner, count_occurrences):
-  """KvVariable.lookup_sparse over KvVariables of one device, dim and key dtype (each listed once; training mode only):
-  the list of their [num_segments[i], dim] outputs."""
+  """KvVariable.lookup_sparse over KvVariables of one device: the list of their [num_segments[i], dim_i] outputs.  In
+  training mode the variables share dim and key dtype and each is listed once (kv_multi_lookup_sparse, one autograd
+  node); in inference mode they are free to differ and to repeat, and the call is one read-only launch
+  (kv_batch_lookup_sparse_zeros: nothing inserted or counted, no autograd node, no pending gradient)."""
   dev = vars_[0].device
   ids = [torch.as_tensor(i).to(dev).reshape(-1) for i in ids]
   segs = [torch.as_tensor(s).to(dev).reshape(-1) for s in segment_ids]
   ws = [None if w is None else torch.as_tensor(w, dtype=torch.float32).to(dev).reshape(-1) for w in weights]
   nsegs = [int(m) for m in num_segments]
+  if not IS_TRAINING:
+    return gen_kv_variable_ops.batch_kv_variable_lookup_sparse_zeros([v.handle for v in vars_], ids, segs, ws, nsegs, combiner)
   occ = [bool(c) for c in count_occurrences]
   if torch.is_grad_enabled() and all(v.trainable for v in vars_):
     return list(_MultiSparseLookupGrad.apply(vars_[0]._anchor, list(vars_), ids, segs, ws, nsegs, combiner, occ))
@@ -208,10 +212,14 @@ class KvVariable(object):
     return gen_kv_variable_ops.kv_variable_gather_or_insert_v2(self._handle, ids)
 
   def lookup_sparse(self, ids, segment_ids, weights, num_segments, combiner, count_occurrences):
-    """embedding_lookup_sparse on this table in one fused call (training mode only)."""
+    """embedding_lookup_sparse on this table in one fused call: kv_lookup_sparse when training (missing keys are
+    inserted, the gradient is filed on the variable), kv_lookup_sparse_zeros else (GatherOrZeros rows, read-only, no
+    autograd node and no pending gradient; count_occurrences has no meaning there)."""
     ids = torch.as_tensor(ids).to(self._device).reshape(-1)
     seg = torch.as_tensor(segment_ids).to(self._device).reshape(-1)
     w = None if weights is None else torch.as_tensor(weights, dtype=torch.float32).to(self._device).reshape(-1)
+    if not IS_TRAINING:
+      return gen_kv_variable_ops.kv_variable_lookup_sparse_zeros(self._handle, ids, seg, w, num_segments, combiner)
     if self._trainable and torch.is_grad_enabled():
       return _SparseLookupGrad.apply(self._anchor, self, ids, seg, w, int(num_segments), combiner,
                                      bool(count_occurrences))
