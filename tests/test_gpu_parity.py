@@ -416,6 +416,85 @@ def test_two_optimizer_steps_on_one_lookup_token(ops):
     _assert_same_table(ops, hs, os_, ids_np, rtol=2e-5, atol=1e-7)
 
 
+def _repeated_grad(rng, ids_np, D):
+  """one gradient row per id, repeated for every occurrence (the sum then hardly depends on its order)"""
+  u = np.unique(ids_np)
+  return rng.normal(0, 1e-2, (u.size, D)).astype(np.float32)[np.searchsorted(u, ids_np)]
+
+
+@pytest.mark.parametrize("D", [8, 6])      # on the entry-list kernels; off them (the sorted positions)
+def test_apply_with_the_token_of_the_lookup_before_last(ops, D):
+  """token lookup(A) -> token lookup(B) of the same length on the same table -> apply(A's ids and gradients, A's token): the
+  token is stale by its serial alone (the sizes are equal), so the apply indexes A again instead of taking B's index over.
+  The state equals the oracle's for lookup A, lookup B, apply A.  3000 ids of 200 keys: more than one tile."""
+  from tfplus_amd import _lib
+  import ctypes
+  L = _lib.lib()
+  st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+  rng = np.random.default_rng(4321 + D)
+  hv, ov = _pair(ops, D, seed=6, rng=rng)
+  ha, oa = _const(ops, D, 0.1)
+  n = 3000
+  a_np = rng.integers(0, 200, n).astype(np.int64)
+  b_np = rng.integers(100, 300, n).astype(np.int64)
+  toks = []
+  for ids_np in (a_np, b_np):
+    ids = torch.from_numpy(ids_np).cuda()
+    out = torch.empty((n, D), device="cuda")
+    tok = ctypes.c_uint64(0)
+    _lib.check(L.kv_gather_or_insert_tok(hv.ptr, ids.data_ptr(), None, n, out.data_ptr(), ctypes.byref(tok), st))
+    np.testing.assert_array_equal(_np(out), ov.gather_or_insert(ids_np))
+    toks.append(tok.value)
+  assert toks[0] != 0 and toks[1] != 0 and toks[0] != toks[1]
+  g_np = _repeated_grad(rng, a_np, D)
+  ids, grad = torch.from_numpy(a_np).cuda(), torch.from_numpy(g_np).cuda()
+  _lib.check(L.kv_apply_adagrad_tok(hv.ptr, ha.ptr, 0.05, grad.data_ptr(), ids.data_ptr(), n, 1, toks[0], st))
+  uu, gs, _ = ko.dedup_segment_sum(a_np, g_np)
+  ko.apply_adagrad(ov, oa, 0.05, gs, uu)
+  keys = np.concatenate([a_np, b_np])
+  _assert_same_table(ops, hv, ov, keys, rtol=2e-5, atol=1e-7)      # repeated ids: summation order (tests/_reorder.py has the bound)
+  _assert_same_table(ops, ha, oa, a_np, rtol=2e-5, atol=1e-7)
+
+
+def test_batched_apply_with_one_stale_token_indexes_every_table_again(ops):
+  """kv_multi_gather_or_insert_tok on three tables -> a plain lookup on the middle one alone (it settles that table's pending
+  partition pass and replaces its index) -> kv_multi_apply_adagrad_tok with all three tokens: one stale token, and every
+  table is indexed again.  Every table's state equals the oracle's."""
+  from tfplus_amd import _lib
+  import ctypes
+  L = _lib.lib()
+  st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+  D, T, n = 8, 3, 3000
+  rng = np.random.default_rng(8642)
+  var = [_pair(ops, D, seed=7 + j, rng=rng) for j in range(T)]
+  acc = [_const(ops, D, 0.1) for _ in range(T)]
+  ids_np = [rng.integers(0, 200, n).astype(np.int64) for _ in range(T)]
+  ids = [torch.from_numpy(i).cuda() for i in ids_np]
+  outs = [torch.empty((n, D), device="cuda") for _ in range(T)]
+  arr = lambda ts: (ctypes.c_void_p * T)(*[t.data_ptr() for t in ts])
+  hv = (ctypes.c_void_p * T)(*[v[0].ptr for v in var])
+  hacc = (ctypes.c_void_p * T)(*[a[0].ptr for a in acc])
+  ns = (ctypes.c_int64 * T)(*([n] * T))
+  toks = (ctypes.c_uint64 * T)()
+  _lib.check(L.kv_multi_gather_or_insert_tok(T, hv, arr(ids), None, ns, arr(outs), toks, st))
+  for j in range(T):
+    assert toks[j] != 0
+    np.testing.assert_array_equal(_np(outs[j]), var[j][1].gather_or_insert(ids_np[j]))
+  other_np = rng.integers(100, 300, n).astype(np.int64)
+  other, out = torch.from_numpy(other_np).cuda(), torch.empty((n, D), device="cuda")
+  _lib.check(L.kv_gather_or_insert(var[1][0].ptr, other.data_ptr(), None, n, out.data_ptr(), st))
+  np.testing.assert_array_equal(_np(out), var[1][1].gather_or_insert(other_np))
+  g_np = [_repeated_grad(rng, i, D) for i in ids_np]
+  grads = [torch.from_numpy(g).cuda() for g in g_np]
+  _lib.check(L.kv_multi_apply_adagrad_tok(T, hv, hacc, 0.05, arr(grads), arr(ids), ns, 1, toks, st))
+  for j in range(T):
+    uu, gs, _ = ko.dedup_segment_sum(ids_np[j], g_np[j])
+    ko.apply_adagrad(var[j][1], acc[j][1], 0.05, gs, uu)
+    keys = np.concatenate([ids_np[j], other_np]) if j == 1 else ids_np[j]
+    _assert_same_table(ops, var[j][0], var[j][1], keys, rtol=2e-5, atol=1e-7)      # repeated ids: summation order, as above
+    _assert_same_table(ops, acc[j][0], acc[j][1], ids_np[j], rtol=2e-5, atol=1e-7)
+
+
 def test_group_adam_parity_with_regularizers_and_blacklist(ops):
   rng = np.random.default_rng(31)
   D = 32

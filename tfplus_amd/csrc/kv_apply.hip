@@ -157,9 +157,9 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   bool pa_reuse = reuse;                      // ... and its partition pass is still pending
   for (int i = 0; i < num_tables && reuse; ++i)
     if (ns[i] > 0) {
-      const bool held = tokens[i] != 0 && tokens[i] == vars[i]->batch_serial && ns[i] == vars[i]->batch_n && vars[i]->fused_index;
-      if (!held) reuse = false;
-      if (!held || !vars[i]->part_pending) pa_reuse = false;
+      const BatchIndex::Plan p = vars[i]->batch.plan(tokens[i], ns[i], fz);
+      if (!BatchIndex::takes_entries(p)) reuse = false;
+      if (p != BatchIndex::TAKE_PENDING) pa_reuse = false;
     }
   if (!reuse) pa_reuse = false;
   for (kv_table* tb : lock.ts) {
@@ -173,7 +173,7 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   if (require_reuse && !reuse)
     return fail(KV_FAILED_PRECONDITION, "batched sharded apply: another op used a table since this batch's lookup");
   for (int i = 0; i < num_tables; ++i) {
-    if (!reuse) vars[i]->batch_serial = 0;
+    if (!reuse) vars[i]->batch.drop();
     if (!reuse && (rc = ensure_capacity(vars[i], ns[i], s))) return rc;
     if ((rc = ensure_capacity(slots0[i], ns[i], s))) return rc;
     if (slots1 && (rc = ensure_capacity(slots1[i], ns[i], s))) return rc;
@@ -194,7 +194,7 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
     d.ids = ids[i];
     d.n = ns[i];
     if (ns[i] == 0) d.w.ntiles = 0;
-    if (reuse && ns[i] > 0 && vars[i]->index_P) use_partitions(d.w, vars[i]->index_P);   // the lookup's partitioning
+    if (reuse && ns[i] > 0 && vars[i]->batch.P()) use_partitions(d.w, vars[i]->batch.P());   // the lookup's partitioning
     d.a.day_lk = d.a.day;
     if (pa_reuse && ns[i] > 0) {   // the pending lookup's own day stamp and counting rule
       PartArgs pend;
@@ -210,11 +210,10 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
     // runs the tile pass of all tables in front (PA_APPLYIDX)
     int pa_mode = pa_reuse ? PA_LOOKUP : PA_NONE;
     if (!reuse) {
-      for (int i = 0; i < num_tables; ++i) vars[i]->fused_index = true;
       launch_ltile(vars[0], hd[0].a.tv, wmax, nullptr, nullptr, nmax, nullptr, s, -1, md, num_tables, false);
       pa_mode = PA_APPLYIDX;
       for (int i = 0; i < num_tables; ++i)
-        if (ns[i] > 0) { vars[i]->batch_serial = ++g_serial; vars[i]->batch_n = ns[i]; vars[i]->index_P = hd[i].w.P; }
+        if (ns[i] > 0) vars[i]->batch.publish(++g_serial, ns[i], BatchIndex::ENTRIES, hd[i].w.P);
     }
     if ((rc = launch_tsum(hd[0].a.tv, wmax, nullptr, s, md, num_tables)))
       return fail(rc, "tile sums: no kernel for dim %d", D);
@@ -223,7 +222,6 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
     HIP_TRY(hipGetLastError());
     return KV_OK;
   }
-  for (int i = 0; i < num_tables; ++i) vars[i]->fused_index = false;
   launch_tile<false>(vars[0], wmax, nullptr, nullptr, nmax, s, -1, md, num_tables, wmax.ntiles);
   launch_part_keys<MODE_APPLYIDX>(wmax, hd[0].a, s, md, num_tables);
   launch_order(hd[0].a.tv, wmax, nmax, s, md, num_tables);
@@ -271,24 +269,20 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
     HIP_TRY(hipGetLastError());
     return KV_OK;
   }
-  const bool reuse = token != 0 && token == v->batch_serial && n == v->batch_n;
-  // The entry-list kernels serve this dim (pa_route): the tile sums, then k_papply — the partition pass and the update in
-  // one launch — in the mode the batch's state asks for:
-  //   PA_LOOKUP    the token names the lookup whose partition pass is still pending: k_papply completes its bookkeeping too
-  //   PA_NONE      the token names a batch whose bookkeeping is done (a second optimizer on the token; a pass another op settled)
-  //   PA_APPLYIDX  no (valid) token: the optimizer meets the ids first — the tile pass runs with the tile sums (k_ltsum)
-  const bool pa_route = fused_tab(v);
-  int pa_mode = -1;
+  // What the token is worth (BatchIndex::plan), and with it the apply's kernels.  The entry-list ones: the tile sums, then
+  // k_papply — the partition pass and the update in one launch — in the mode the batch's state asks for:
+  //   PA_LOOKUP    TAKE_PENDING: the token names the lookup whose partition pass is still pending: k_papply completes its bookkeeping too
+  //   PA_NONE      TAKE_DONE: the token names a batch whose bookkeeping is done (a second optimizer on the token; a pass another op settled)
+  //   PA_APPLYIDX  REBUILD on a table of their dims: the optimizer meets the ids first — the tile pass runs with the tile sums (k_ltsum)
+  // TAKE_SORTED, and REBUILD on any other table: the sorted positions and the segmented fold over them (launch_apply).
+  const BatchIndex::Plan plan = v->batch.plan(token, n, fused_tab(v));
+  const bool reuse = plan != BatchIndex::REBUILD;
+  const bool entries = reuse ? BatchIndex::takes_entries(plan) : fused_tab(v);
+  const int pa_mode = plan == BatchIndex::TAKE_PENDING ? PA_LOOKUP : reuse ? PA_NONE : PA_APPLYIDX;
   PartArgs pend{};
   const void* tile_ids = nullptr;   // != nullptr: the batch's tile pass runs in front of the apply (k_ltsum)
-  if (v->part_pending) {
-    if (reuse && pa_route && v->fused_index) {
-      take_pending_part(v, &pend);
-      pa_mode = PA_LOOKUP;
-    } else if ((rc = flush_part(v, s))) {
-      return rc;
-    }
-  }
+  if (plan == BatchIndex::TAKE_PENDING) take_pending_part(v, &pend);
+  else if ((rc = flush_part(v, s))) return rc;   // (a pass nobody takes over; the caller's entry left it only to a token of this batch)
   if (!reuse && (rc = ensure_capacity(v, n, s))) return rc;
   if ((rc = ensure_capacity(s0, n, s))) return rc;
   if (s1 && (rc = ensure_capacity(s1, n, s))) return rc;
@@ -300,23 +294,19 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
   pa.day_lk = pa.day;
   if (pa_mode == PA_LOOKUP) { pa.day_lk = pend.day; pa.count_once = pend.count_once; }
   if (!reuse) {
-    v->batch_serial = 0;
-    if (pa_route) {   // tile pass + tile sums in one launch, then partition pass + update in one launch
-      v->fused_index = true;
+    if (entries) {   // tile pass + tile sums in one launch, then partition pass + update in one launch
       choose_partitions(v, wd, n);
       tile_ids = ids;
-      pa_mode = PA_APPLYIDX;
     } else {
       index_pass<MODE_APPLYIDX>(v, wd, pa, ids, nullptr, n, -1, nullptr, s);
     }
-    v->batch_serial = ++g_serial;   // the index stays valid for this batch (e.g. a second optimizer on the same ids)
-    v->batch_n = n;
-  } else if (pa_mode < 0 && v->fused_index) {
-    pa_mode = PA_NONE;   // the tiles' entries of a batch whose bookkeeping is done
+    // the index stays valid for this batch (e.g. a second optimizer on the same ids)
+    v->batch.publish(++g_serial, n, entries ? BatchIndex::ENTRIES : BatchIndex::SORTED, wd.P);
+  } else if (entries && v->batch.P()) {
+    use_partitions(wd, v->batch.P());   // the lookup's partitioning
   }
-  if (v->fused_index && reuse && v->index_P) use_partitions(wd, v->index_P);   // the lookup's partitioning
-  if ((rc = mirror_decide(v, s0, pa, v->fused_index && !two_slots(OPT), s))) return rc;
-  if (v->fused_index) rc = fused_apply<OPT>(v, wd, pa, n, s, pa_mode, tile_ids);
+  if ((rc = mirror_decide(v, s0, pa, entries && !two_slots(OPT), s))) return rc;
+  if (entries) rc = fused_apply<OPT>(v, wd, pa, n, s, pa_mode, tile_ids);
   else rc = launch_apply<MODE_APPLY, OPT>(v, wd, pa, n, s);
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
@@ -492,7 +482,7 @@ int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const f
   // and writes the slot tables' own records: its entry ends the tables' epochs
   auto keep = [&](const kv_table* t) -> unsigned { return two ? KEEP_NONE : (t == v ? KEEP_VAR : KEEP_NONE) | (t == s0 ? KEEP_SLOT : KEEP_NONE); };
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = lk.enter(s, keep, token != 0 && token == v->batch_serial ? v : nullptr))) return rc;
+  if ((rc = lk.enter(s, keep, v->batch.holds(token, n) ? v : nullptr))) return rc;
   OptArgs a = c.a;
   a.l21_norm = a.l21 * std::sqrt((float)v->dim);   // training_ops.cc:728
   return with_opt(c.opt, [&](auto o) { return apply_common<decltype(o)::value>(v, s0, two ? s1 : nullptr, grad, ids, n, a, token, s, unique, self, counted); });
@@ -758,7 +748,7 @@ int kv_attach_slot(kv_handle_t v, kv_handle_t sl, kv_stream_t stream) {
     launch_clear_hints(v, s);
   v->slot_uid = sl->uid;
   v->slot_gen = sl->gen;
-  v->batch_serial = 0;
+  v->batch.drop();
   // (the entry above ended any running epoch of either table; a pair of single-chunk tables gets its mirrors filled here)
   launch_link_hints(v, sl, nrows, s);
   HIP_TRY(hipGetLastError());

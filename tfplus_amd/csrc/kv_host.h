@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/kvhip.h"
+#include "kv_batch_index.h"
 #include "kv_launch.h"
 
 namespace __attribute__((visibility("hidden"))) kvhip_internal {
@@ -114,19 +115,14 @@ struct kv_table {
   bool initialized = false;
   bool init_placeholder = false;   // init_table is the zero row an import put there, not a real init table
   Workspace ws;
-  // the batch index the workspace holds: `batch_serial` names it (0 = none); an optimizer apply handed the
-  // same token takes the index over instead of rebuilding it
-  uint64_t batch_serial = 0;
-  long long batch_n = 0;
-  bool fused_index = false;        // the index is the tiles' entries (kv_fused.h: an apply of that batch goes through k_papply),
-                                   // not a sorted position list (kv_kernels.h)
-  long long batch_n_prev = 0;      // ids of the previous entry-list index pass (the distinct-count hint belongs to that size)
-  unsigned index_P = 0;            // partitions of the entry-list index the workspace holds
+  // the index of the table's last batch, as far as the workspace still holds it, and whether that lookup's partition pass
+  // is still pending: one record, written only through its transitions (kv_batch_index.h states the invariants)
+  BatchIndex batch;
+  long long batch_n_prev = 0;      // ids of the previous entry-list index pass (choose_partitions: the distinct-count hint belongs to that size)
   // A training lookup that hands out a batch token returns when its rows are written; its partition pass (frequency
-  // words, rows of new keys, the batch's key records and entry list) is PENDING: the optimizer apply of that batch
-  // runs it in front of its own kernels, any other op on the table runs it first thing (settle).  Same stream order
-  // as before, the rows just do not wait for it.
-  bool part_pending = false;
+  // words, rows of new keys, the batch's key records and entry list) is PENDING (batch.part_pending()): the optimizer apply
+  // of that batch runs it in front of its own kernels, any other op on the table runs it first thing (settle).  Same stream
+  // order as before, the rows just do not wait for it.  The pass's arguments, as byte images (their types are the device's):
   unsigned char pend_wd[sizeof(WsDev)], pend_pa[sizeof(PartArgs)];
   // Slot mirrors (kv_device.h SlotMirror; mirror_* below): a var table paired with ONE slot table keeps, next to each row's
   // record, a write-back copy of the slot row's frequency word and flags; the lean apply works on the copy alone.
@@ -367,7 +363,7 @@ int settle_pending(kv_table* t);
 int stats(kv_handle_t t, hipStream_t s, unsigned long long out[2], unsigned* nrows_out);
 
 // ---- the pending partition pass and the slot mirrors, as the ops see them ------------------------------------------------
-// a training lookup leaves its partition pass (wd, pa) pending on the table (kv_table::part_pending)
+// a training lookup leaves its partition pass (wd, pa) pending on the table (BatchIndex::defer_part)
 void set_pending_part(kv_table* t, const WsDev& wd, const PartArgs& pa);
 // the optimizer apply of that batch takes it over: no longer pending; the lookup's own day stamp and counting rule come out
 void take_pending_part(kv_table* t, PartArgs* lookup);
@@ -401,7 +397,7 @@ void retire_stream(hipStream_t dead);
 
 // ---- index passes ------------------------------------------------------------------------------------------------------
 extern std::atomic<uint64_t> g_serial;   // batch tokens
-void choose_partitions(kv_table* t, WsDev& wd, long long n);
+void choose_partitions(kv_table* t, WsDev& wd, long long n);   // wd.P, wd.pshift: whoever publishes the index hands P on
 template <int MODE>   // MODE_LOOKUP, MODE_APPLYIDX, MODE_UNIQUE
 void index_pass(kv_table* t, const WsDev& wd, const PartArgs& pa, const void* ids, const int* counts, long long n,
                 int ids_kind, float* out, hipStream_t s, bool file_order = true);

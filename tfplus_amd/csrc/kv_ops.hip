@@ -101,7 +101,6 @@ static int tile_pass_notable(kv_table* t, WsDev& wd, const PartArgs& pa, const v
     if ((rc = ensure_pos_ent(t, n, s))) return rc;
     wd.pos_ent = t->ws.pos_ent;
   }
-  t->fused_index = true;
   choose_partitions(t, wd, n);
   launch_ltile_notable(t, pa.tv, wd, ids, n, s, counts, int32_ids);
   return KV_OK;
@@ -127,14 +126,15 @@ static int read_count(kv_table* t, const unsigned* dev, hipStream_t s, unsigned*
 // The rows pa.grad of one id folded (pa.fold_op) into one output row, on the batch pipeline; the table's mutex is held by the
 // caller, which set the outputs in pa: out_keys + out_sum with dd_number (kv_dedup_segment_sum: the distinct ids numbered,
 // summed[number]) or out_sum with direct_rows (kv_unsorted_segment_sum: an id IS its output row).  Sums on a table of the
-// entry-list kernels' dims take those (t->fused_index says so afterwards): the table-less tile pass — file_pos: with every
+// entry-list kernels' dims take those (sums_on_entries): the table-less tile pass — file_pos: with every
 // position's entry, for an inverse — the tile sums of the ids repeated inside their tile (k_tsum), then ONE partition pass
 // (k_papply PA_DEDUP: the per-id sums over the tiles' entries; dd_number, which launch_papply_ud alone reads: it numbers
 // the ids it sums).  Everything else: the sorted positions (index_pass) and the segmented fold over them.
+static bool sums_on_entries(const kv_table* t, int fold_op) { return fold_op == KV_SCATTER_ADD && fused_tab(t); }
 static int segment_sums(kv_table* t, WsDev& wd, PartArgs& pa, const void* ids, long long n, bool int32_ids, bool file_pos,
                         const char* what, hipStream_t s) {
   int rc;
-  if (pa.fold_op != KV_SCATTER_ADD || !fused_tab(t)) {
+  if (!sums_on_entries(t, pa.fold_op)) {
     index_pass<MODE_UNIQUE>(t, wd, pa, ids, nullptr, n, int32_ids ? 1 : 0, nullptr, s);
     return launch_apply<MODE_DEDUP, OPT_ADAGRAD>(t, wd, pa, n, s);
   }
@@ -156,7 +156,7 @@ static int dedup_locked(kv_table* t, const void* ids, const float* grad, int64_t
   int rc;
   if ((rc = ensure_workspace(t, n, true, s))) return rc;
   WsDev wd = ws_view(t, n);
-  t->batch_serial = 0;
+  t->batch.drop();
   PartArgs pa = self_part_args(t, n);
   pa.grad = grad;
   pa.out_keys = (long long*)uniq;
@@ -164,7 +164,7 @@ static int dedup_locked(kv_table* t, const void* ids, const float* grad, int64_t
   pa.fold_op = fold_op;
   pa.dd_number = 1;
   if ((rc = segment_sums(t, wd, pa, ids, n, t->key_dtype == KV_DT_INT32, true, "per-id sums", s))) return rc;
-  if (inverse && t->fused_index) k_inverse_e<<<nblocks(n, TB, 2048), TB, 0, s>>>(t->ws.pos_ent, wd.ent_b, n, inverse);
+  if (inverse && sums_on_entries(t, fold_op)) k_inverse_e<<<nblocks(n, TB, 2048), TB, 0, s>>>(t->ws.pos_ent, wd.ent_b, n, inverse);
   else if (inverse) k_dedup_inverse<<<nblocks(n, TB, 2048), TB, 0, s>>>(wd, n, inverse);
   if (num_unique_dev) {
     k_store_count<<<1, 1, 0, s>>>(wd.ctr, (long long*)num_unique_dev);
@@ -210,7 +210,7 @@ static int after_release(kv_table* t, hipStream_t s, unsigned long long* release
 static int delete_locked(kv_table* t, const void* ids, int64_t n, int64_t* num_deleted, hipStream_t s) {
   int rc;
   if ((rc = enter_op(t, s))) return rc;
-  t->batch_serial = 0;   // rows are released: an index of a batch that held them is void (its token goes stale)
+  t->batch.drop();   // rows are released: an index of a batch that held them is void (its token goes stale)
   if ((rc = ensure_free_list(t, s))) return rc;
   HIP_TRY(hipMemsetAsync(t->d_stat, 0, 4 * sizeof(unsigned long long), s));
   with_id_type(t->key_dtype == KV_DT_INT32, [&](auto id) {
@@ -264,7 +264,7 @@ static int scatter_like(kv_handle_t t, const void* ids, const float* vals, int64
     pa.grad = vals ? vals + (size_t)off * t->dim : nullptr;
     pa.scatter_op = op; pa.is_insert = is_insert;
     pa.mark_what = mark; pa.fvals = fvals ? fvals + off : nullptr;
-    t->batch_serial = 0;
+    t->batch.drop();
     launch_tile<true>(t, wd, (const char*)ids + (size_t)off * idsz, nullptr, m, s);
     if (mark >= 0) launch_part_keys<MODE_MARK>(wd, pa, s);
     else launch_part_keys<MODE_SCATTER>(wd, pa, s);
@@ -377,7 +377,7 @@ static int lookup_sparse_locked(kv_table* t, const void* ids, const void* segmen
   const TableDev& td = pa.tv;
   pa.day = today(t);
   pa.count_once = count_occurrences ? 0 : 1;
-  t->batch_serial = 0;
+  t->batch.drop();
   if (fused) {
     // the entry-list kernels: tile pass without rows (entries, every position's entry), the lookup's bookkeeping (which
     // also publishes the rows of new keys), then the combiner reads position -> entry -> row
@@ -538,7 +538,9 @@ int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* counts,
   // the entry-list pipeline indexes a batch of up to FUSED_MAX_N ids in one pass; the sorted-position one 2^21
   const long long CHK = fused_tab(t) ? FUSED_MAX_N : (1ll << 21);
   const size_t idsz = pairs ? 16 : (t->key_dtype == KV_DT_INT32 ? 4 : 8);
-  t->batch_serial = 0;
+  t->batch.drop();
+  const bool tok = token != nullptr && n <= CHK;   // a token is asked for, one pass indexes the batch: an apply of it follows
+  unsigned P = 0;
   for (long long off = 0; off < n; off += CHK) {
     const long long m = std::min(CHK, (long long)n - off);
     const void* idp = (const char*)ids + (size_t)off * idsz;
@@ -550,16 +552,13 @@ int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* counts,
     wd.seg_cap = seg_cap;
     PartArgs pa = self_part_args(t, m);
     pa.day = today(t);
-    const bool defer_part = token != nullptr && n <= CHK;   // a token is asked for: an apply of this batch follows
-    if (fused_tab(t)) { if ((rc = fused_lookup_pass(t, wd, pa, idp, cp, m, pairs ? 2 : -1, op, s, defer_part))) return rc; }
-    else index_pass<MODE_LOOKUP>(t, wd, pa, idp, cp, m, pairs ? 2 : -1, op, s, token != nullptr && n <= CHK);
+    if (fused_tab(t)) { if ((rc = fused_lookup_pass(t, wd, pa, idp, cp, m, pairs ? 2 : -1, op, s, tok))) return rc; }
+    else index_pass<MODE_LOOKUP>(t, wd, pa, idp, cp, m, pairs ? 2 : -1, op, s, tok);
+    P = wd.P;
   }
   HIP_TRY(hipGetLastError());
-  if (token && n <= CHK) {   // the workspace now holds the index of exactly this batch, positions filed
-    t->batch_serial = ++g_serial;
-    t->batch_n = n;
-    if (token) *token = t->batch_serial;
-  }
+  // the workspace now holds the index of exactly this batch, positions filed
+  if (tok) *token = t->batch.publish(++g_serial, n, fused_tab(t) ? BatchIndex::ENTRIES : BatchIndex::SORTED, P);
   return KV_OK;
 }
 
@@ -580,7 +579,7 @@ int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const void* con
   if ((rc = lock.enter(s, [](const kv_table*) { return (unsigned)KEEP_VAR; }))) return rc;   // lookups: the tables' own rows and records only
   long long nmax = 0;
   for (int i = 0; i < num_tables; ++i) {
-    tables[i]->batch_serial = 0;
+    tables[i]->batch.drop();
     if (ns[i] > 0 && !outs[i]) return fail(KV_INVALID_ARGUMENT, "output pointer is null");
     if ((rc = ensure_capacity(tables[i], ns[i], s))) return rc;
     if ((rc = ensure_workspace(tables[i], std::max<long long>(ns[i], 1), false, s))) return rc;
@@ -608,7 +607,6 @@ int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const void* con
   if ((rc = hd.upload(s, &md))) return rc;
   kv_table* t0 = tables[0];
   if (fused_tab(t0)) {
-    for (int i = 0; i < num_tables; ++i) tables[i]->fused_index = true;
     launch_ltile(t0, hd[0].a.tv, wmax, nullptr, nullptr, nmax, nullptr, s, ids_kind, md, num_tables, true);
     // tokens asked for: an optimizer apply of these batches follows — every table's partition pass stays pending
     // (kv_multi_apply_*_tok completes it inside k_papply_multi; any other op on a table settles that table first)
@@ -617,14 +615,10 @@ int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const void* con
     if (tokens)   // every table's workspace now holds the index of exactly its batch (kv_multi_apply_*_tok takes it over)
       for (int i = 0; i < num_tables; ++i) {
         if (ns[i] <= 0) continue;
-        tables[i]->batch_serial = ++g_serial;
-        tables[i]->batch_n = ns[i];
-        tables[i]->index_P = hd[i].w.P;
-        tokens[i] = tables[i]->batch_serial;
+        tokens[i] = tables[i]->batch.publish(++g_serial, ns[i], BatchIndex::ENTRIES, hd[i].w.P);
         if (defer) set_pending_part(tables[i], hd[i].w, hd[i].a);
       }
   } else {
-    for (int i = 0; i < num_tables; ++i) tables[i]->fused_index = false;
     launch_tile<false>(t0, wmax, nullptr, nullptr, nmax, s, -1, md, num_tables, wmax.ntiles);
     launch_part_keys<MODE_LOOKUP>(wmax, hd[0].a, s, md, num_tables);
     launch_gather(hd[0].a.tv, wmax, nullptr, nmax, s, md, num_tables);
@@ -727,7 +721,7 @@ int kv_multi_lookup_sparse(int num_tables, const kv_handle_t* tables, const void
   long long nmax = 0, segmax = 0;
   for (int i = 0; i < num_tables; ++i) {
     kv_table* t = tables[i];
-    t->batch_serial = 0;
+    t->batch.drop();
     if (num_segments[i] == 0) continue;
     if ((rc = ensure_capacity(t, en[i], s))) return rc;
     if ((rc = ensure_workspace(t, std::max<long long>(en[i], 1), false, s))) return rc;
@@ -762,7 +756,6 @@ int kv_multi_lookup_sparse(int num_tables, const kv_handle_t* tables, const void
     q.out = outs[i];
     q.n = en[i];
     q.nseg = num_segments[i];
-    if (en[i] > 0) t->fused_index = true;
   }
   const MultiDesc* md;
   const SparseDesc* sp;
@@ -1052,7 +1045,7 @@ int kv_unsorted_segment_sum(kv_handle_t t, const int32_t* segment_ids, const flo
   if (n == 0) return KV_OK;
   if ((rc = ensure_workspace(t, n, true, s))) return rc;
   WsDev wd = ws_view(t, n);
-  t->batch_serial = 0;
+  t->batch.drop();
   PartArgs pa = self_part_args(t, n);
   pa.grad = data;
   pa.out_sum = out;
@@ -1081,7 +1074,7 @@ int kv_unique(kv_handle_t t, const void* ids, const int32_t* counts, int64_t n, 
   if ((rc = enter_op(t, s, KEEP_VAR | KEEP_SLOT))) return rc;
   if ((rc = ensure_workspace(t, n, false, s))) return rc;
   WsDev wd = ws_view(t, n);
-  t->batch_serial = 0;
+  t->batch.drop();
   PartArgs pa = self_part_args(t, n);
   pa.out_keys = (long long*)uniq;
   pa.out_counts = uniq_counts;
@@ -1123,7 +1116,7 @@ int kv_delete_with_timestamp(kv_handle_t t, int threshold, int dry_run, int64_t*
       return fail(KV_FAILED_PRECONDITION, "the table was used between the dry run and kv_delete_with_timestamp: the key "
                                           "buffer sized from the count may be too small; count again");
     ++t->op_serial;
-    t->batch_serial = 0;   // rows are released: an index of a batch that held them is void
+    t->batch.drop();   // rows are released: an index of a batch that held them is void (a pending pass: stats settles it below)
   }
   unsigned nrows = 1;
   if ((rc = stats(t, s, nullptr, &nrows))) return rc;
@@ -1362,7 +1355,7 @@ int kv_import(kv_handle_t t, const int64_t* keys, const float* values, int64_t n
   HIP_TRY(hipStreamSynchronize(s));
   t->gen += 1;            // row ids start over: slot-row hints into this table are void
   t->slot_uid = 0;        // and the fresh index carries none of its own
-  t->batch_serial = 0;
+  t->batch.drop();
   unsigned init[3] = {1, 0, 0};
   HIP_TRY(hipMemcpy(t->d_counters, init, sizeof init, hipMemcpyHostToDevice));  // stack source: synchronous
   launch_fill_entries(t, s);

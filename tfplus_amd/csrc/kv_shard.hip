@@ -276,7 +276,6 @@ static SegBytes shard_bytes(const kv_shard* sh, bool whole) {
 static void route_desc(kv_shard* sh, long long n, MultiDesc& d) {
   kv_table* rt = sh->route;
   d.w = ws_view(rt, n);
-  rt->fused_index = true;
   choose_partitions(rt, d.w, n);   // (the distinct-id hint of the previous route of this length: k_papply publishes it)
   d.w.zero_counts = sh->ucnt;
   d.w.pos_ent = rt->ws.pos_ent;
@@ -298,7 +297,7 @@ static void route_desc(kv_shard* sh, long long n, MultiDesc& d) {
 static void presum_desc(kv_shard* sh, const float* grad, MultiDesc& d) {
   kv_table* rt = sh->route;
   d.w = ws_view(rt, sh->n_last);
-  if (rt->index_P) use_partitions(d.w, rt->index_P);
+  if (rt->batch.P()) use_partitions(d.w, rt->batch.P());
   PartArgs& pa = d.a;
   pa = self_part_args(rt, sh->n_last);
   pa.grad = grad;
@@ -349,9 +348,7 @@ static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_strea
   WsDev wd = d.w;
   wd.zero_counts = nullptr; wd.pos_ent = nullptr;   // (the tile pass alone files those)
   if ((rc = launch_papply_ud(wd, d.a, PA_UNIQUE, s))) return fail(rc, "route: no kernel for dim %d", rt->dim);
-  rt->batch_serial = ++g_serial;
-  rt->batch_n = n;
-  sh->route_token = rt->batch_serial;
+  sh->route_token = rt->batch.publish(++g_serial, n, BatchIndex::ENTRIES, d.w.P);
   if (d.a.det) {   // the ordered owner scatter
     const unsigned ntr = (unsigned)((n + RT - 1) / RT);
     k_owner_hist_u32<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, (long long)n, sh->world, sh->rule, ntr, sh->hist);
@@ -519,9 +516,7 @@ static int multi_route_impl(const kv_shard_t* shards, const int* todo, int m, co
   for (int j = 0; j < m; ++j) {
     kv_shard* sh = shards[todo[j]];
     kv_table* rt = sh->route;
-    rt->batch_serial = ++g_serial;
-    rt->batch_n = sh->n_last;
-    sh->route_token = rt->batch_serial;
+    sh->route_token = rt->batch.publish(++g_serial, sh->n_last, BatchIndex::ENTRIES, hd[j].w.P);
   }
   HIP_TRY(hipGetLastError());
   return KV_OK;
@@ -539,7 +534,7 @@ static int multi_finish_impl(const kv_shard_t* shards, const int* todo, int m, f
   for (int j = 0; j < m; ++j) {
     kv_shard* sh = shards[todo[j]];
     kv_table* rt = sh->route;
-    if (rt->batch_serial != sh->route_token || sh->route_token == 0) return fail(KV_FAILED_PRECONDITION, "kv_multi_shard_lookup: finish without route");
+    if (!rt->batch.holds(sh->route_token, sh->n_last)) return fail(KV_FAILED_PRECONDITION, "kv_multi_shard_lookup: finish without route");
     if (!outs[todo[j]]) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_lookup: output pointer is null");
     if ((rc = hand_over(rt, s))) return rc;
     hd[j] = finish_desc(sh, outs[todo[j]]);
@@ -563,7 +558,7 @@ static int multi_presum_impl(const kv_shard_t* shards, const int* todo, int m, c
   for (int j = 0; j < m; ++j) {
     kv_shard* sh = shards[todo[j]];
     kv_table* rt = sh->route;
-    if (rt->batch_serial != sh->route_token || sh->route_token == 0)
+    if (!rt->batch.holds(sh->route_token, sh->n_last))
       return fail(KV_FAILED_PRECONDITION, "kv_multi_shard_apply: the batch's lookup must come first");
     if (!grads[todo[j]]) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_apply: grad pointer is null");
     if ((rc = hand_over(rt, s))) return rc;
@@ -766,8 +761,8 @@ static int shards_apply(bool single, const kv_shard_t* shards, int ntab, kv_comm
   done.assign(ntab, 0);
   for (const auto& grp : groups_of(ntab, [&](int k) {
          const kv_shard* sh = shards[k];
-         return optimizer >= 0 && optimizer <= OPT_GROUP_RADAM && shard_owner_batchable(sh) && sh->serve_token != 0 &&
-                        sh->serve_token == sh->table->batch_serial && sh->table->fused_index && slot0[k] != nullptr &&
+         const BatchIndex::Plan served = sh->table->batch.plan(sh->serve_token, (long long)sh->world * (sh->C + 1), fused_tab(sh->table));
+         return optimizer >= 0 && optimizer <= OPT_GROUP_RADAM && shard_owner_batchable(sh) && BatchIndex::takes_entries(served) && slot0[k] != nullptr &&
                         (!two_slots(optimizer) || (slot1 && slot1[k]))
                     ? sh->table->dim : -1; })) {
     const int m = (int)grp.size();
@@ -1030,7 +1025,7 @@ int kv_shard_lookup_finish(kv_shard_t sh, float* out, kv_stream_t stream) {
   DeviceGuard dg(sh->table->device);
   kv_table* rt = sh->route;
   std::lock_guard<std::mutex> l(rt->mu);
-  if (rt->batch_serial != sh->route_token || sh->route_token == 0) return fail(KV_FAILED_PRECONDITION, "kv_shard_lookup_finish without kv_shard_lookup_route");
+  if (!rt->batch.holds(sh->route_token, sh->n_last)) return fail(KV_FAILED_PRECONDITION, "kv_shard_lookup_finish without kv_shard_lookup_route");
   { int rc; if ((rc = hand_over(rt, (hipStream_t)stream))) return rc; }
   const FinishDesc d = finish_desc(sh, out);
   const int grid = nblocks(d.n, TB, 8192);
@@ -1050,7 +1045,7 @@ int kv_shard_apply_route(kv_shard_t sh, const float* grad, kv_stream_t stream) {
   DeviceGuard dg(sh->table->device);
   kv_table* rt = sh->route;
   std::lock_guard<std::mutex> l(rt->mu);
-  if (rt->batch_serial != sh->route_token || sh->route_token == 0)
+  if (!rt->batch.holds(sh->route_token, sh->n_last))
     return fail(KV_FAILED_PRECONDITION, "kv_shard_apply_route: the batch's lookup must come first (kv_shard_lookup_route)");
   hipStream_t s = (hipStream_t)stream;
   int rc;
@@ -1068,10 +1063,10 @@ int kv_shard_apply_route(kv_shard_t sh, const float* grad, kv_stream_t stream) {
 // fused apply takes the index that lookup left in the table's workspace.  2 launches.  optimizer / hp: shard_opt_call
 int kv_shard_apply_serve(kv_shard_t sh, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp, kv_stream_t stream) {
   if (!sh || !hp) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_serve: bad arguments");
-  if (sh->serve_token == 0 || sh->serve_token != sh->table->batch_serial)
+  const int64_t nrec = (int64_t)sh->world * (sh->C + 1);
+  if (!sh->table->batch.holds(sh->serve_token, nrec))
     return fail(KV_FAILED_PRECONDITION, "kv_shard_apply_serve: another op used the table since this batch's lookup "
                                         "(the sharded apply takes over the lookup's index)");
-  const int64_t nrec = (int64_t)sh->world * (sh->C + 1);
   const SelfSegment self = shard_self(sh, true);
   const OptCall c = shard_opt_call(optimizer, hp);
   if (c.opt < 0) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_serve: optimizer %d", optimizer);

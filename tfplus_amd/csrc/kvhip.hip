@@ -240,7 +240,7 @@ int flagged_error(kv_table* t, unsigned code, hipStream_t s) {
   hipMemsetAsync(t->d_counters + 1, 0, sizeof(unsigned), s);
   hipStreamSynchronize(s);
   if (t->err_host) *reinterpret_cast<volatile unsigned*>(t->err_host) = 0u;
-  t->batch_serial = 0;
+  t->batch.drop();   // (from report_deferred_error: ahead of the settle — a pending pass stays for the table's next op)
   if (code == 4)
     return fail(KV_INVALID_ARGUMENT, "kv_apply_*_unique: the ids of an earlier call were NOT unique (an id was listed twice): that "
                                      "batch was not applied as the reference applies repeated ids; pass such batches to "
@@ -354,7 +354,7 @@ int ensure_workspace(kv_table* t, long long n, bool need_part, hipStream_t s) {
     const size_t nt = (size_t)(cap / TILE);
     // every buffer is replaced only once its successor exists; a failure leaves the old sizes in force
     w.cap_n = 0; w.capP = 0; w.hpart_elems = 0; w.epart_elems = 0;
-    t->batch_serial = 0;
+    t->batch.drop();
     if ((rc = regrow(&w.ent_key, (size_t)cap)) || (rc = regrow(&w.ent_a, (size_t)cap)) ||
         (rc = regrow(&w.ent_b, (size_t)cap)) || (rc = regrow(&w.ent_base, (size_t)cap)) || (rc = regrow(&w.ent_rec, (size_t)cap)) ||
         (rc = regrow(&w.toff, nt * (capP + 1))) || (rc = regrow(&w.slot_rank, (size_t)cap)) ||
@@ -600,22 +600,22 @@ int report_deferred_error(kv_table* t, hipStream_t s) {
   return flagged_error(t, code, s);
 }
 
-// a lookup's partition pass (wd, pa) stays pending on the table (see kv_table::part_pending)
+// a lookup's partition pass (wd, pa) stays pending on the table (BatchIndex::defer_part)
 void set_pending_part(kv_table* t, const WsDev& wd, const PartArgs& pa) {
   std::memcpy(t->pend_wd, &wd, sizeof wd);
   std::memcpy(t->pend_pa, &pa, sizeof pa);
-  t->part_pending = true;
+  t->batch.defer_part();
 }
 // ... and is taken over by the optimizer apply of that batch (k_papply PA_LOOKUP completes it): not pending any more;
 // *lookup = the pending lookup's own arguments (the apply wants its day stamp and counting rule)
 void take_pending_part(kv_table* t, PartArgs* lookup) {
   std::memcpy(lookup, t->pend_pa, sizeof *lookup);
-  t->part_pending = false;
+  t->batch.part_taken();
 }
-// launches a lookup's pending partition pass (see kv_table::part_pending) on stream s
+// launches a lookup's pending partition pass (BatchIndex::defer_part) on stream s
 int flush_part(kv_table* t, hipStream_t s) {
-  if (!t->part_pending) return KV_OK;
-  t->part_pending = false;
+  if (!t->batch.part_pending()) return KV_OK;
+  t->batch.part_flushed();
   WsDev wd; PartArgs pa;
   std::memcpy(&wd, t->pend_wd, sizeof wd);
   std::memcpy(&pa, t->pend_pa, sizeof pa);
@@ -743,7 +743,7 @@ static int hop_behind_last(kv_table* t, hipStream_t s) {
 // last op whatever its stream, and the next op behind it — but it does not move op_serial (a two-phase export may go on)
 int hand_over(kv_table* t, hipStream_t s, unsigned keep, bool settle, bool mutates) {
   int rc;
-  if (t->part_pending && settle) {   // (an apply that takes the batch over runs it itself, behind the stream hand-over below)
+  if (t->batch.part_pending() && settle) {   // (an apply that takes the batch over runs it itself, behind the stream hand-over below)
     if ((rc = hop_behind_last(t, s)) || (rc = flush_part(t, s))) return rc;
   }
   if ((rc = hop_behind_last(t, s))) return rc;
@@ -757,7 +757,7 @@ int hand_over(kv_table* t, hipStream_t s, unsigned keep, bool settle, bool mutat
 // partition pass (it may still have rows to initialise) is settled first.  None of them keeps a mirror epoch.
 int join_side(kv_table* t, hipStream_t s) {
   int rc;
-  if (t->part_pending) {
+  if (t->batch.part_pending()) {
     if ((rc = hop_behind_last(t, s)) || (rc = flush_part(t, s))) return rc;
   }
   // An epoch of slot mirrors that ends here flushes copies the last lean apply wrote — on the stream of t's last op (an apply
@@ -781,7 +781,6 @@ int enter_op(kv_table* t, hipStream_t s, unsigned keep, bool settle, bool mutate
 template <int MODE>
 void index_pass(kv_table* t, const WsDev& wd, const PartArgs& pa, const void* ids, const int* counts, long long n,
                 int ids_kind, float* out, hipStream_t s, bool file_order) {
-  t->fused_index = false;
   {
     ProfScope ps(t, MODE == MODE_LOOKUP ? KV_PROF_LOOKUP_TILE : KV_PROF_INDEX, s);
     launch_tile<false>(t, wd, ids, counts, n, s, ids_kind);
@@ -797,7 +796,7 @@ void index_pass(kv_table* t, const WsDev& wd, const PartArgs& pa, const void* id
   else launch_order(pa.tv, wd, n, s);
 }
 
-// partitions of an entry-list index pass over n ids (wd.P, wd.pshift; remembered in t->index_P)
+// partitions of an entry-list index pass over n ids (wd.P, wd.pshift; whoever publishes the index hands P to BatchIndex::publish)
 void choose_partitions(kv_table* t, WsDev& wd, long long n) {
   {
     // the distinct ids of the batch before the last one (the tile pass hands the partition pass's count to the host
@@ -826,7 +825,6 @@ void choose_partitions(kv_table* t, WsDev& wd, long long n) {
       wd.P = fused_default_P(n);
     }
     wd.pshift = 64 - ilog2(wd.P);
-    t->index_P = wd.P;
   }
 }
 
@@ -835,7 +833,6 @@ void choose_partitions(kv_table* t, WsDev& wd, long long n) {
 // in the same pass as the update) or for whatever op the table sees next (flush_part)
 int fused_lookup_pass(kv_table* t, WsDev& wd, const PartArgs& pa, const void* ids, const int* counts, long long n,
                       int ids_kind, float* out, hipStream_t s, bool defer_part) {
-  t->fused_index = true;
   choose_partitions(t, wd, n);
   {
     ProfScope ps(t, KV_PROF_LOOKUP_TILE, s);
@@ -912,7 +909,7 @@ int check_same_shape(int num_tables, const kv_handle_t* tables, const char* what
 // changes what the passes would compute (seed, deterministic order), first lets them run — on the stream of the
 // table's last op — and waits for them.
 int settle_pending(kv_table* t) {
-  if (!t->part_pending) return KV_OK;
+  if (!t->batch.part_pending()) return KV_OK;
   hipStream_t s = t->has_last ? t->last_stream : nullptr;
   int rc;
   if ((rc = join_side(t, s))) return rc;
@@ -1123,8 +1120,7 @@ int kv_set_deterministic(kv_handle_t t, int on) {
     return fail(KV_UNIMPLEMENTED, "kv_set_deterministic(h, 2): the table serves a kv_shard (occurrence order is a single-table notion)");
   t->deterministic = on != 0;
   t->occurrence_order = on == 2;
-  t->batch_serial = 0;      // the index a lookup left was built by the other pipeline's rules
-  t->fused_index = false;
+  t->batch.drop();   // the index a lookup left was built by the other pipeline's rules
   return KV_OK;
 }
 
