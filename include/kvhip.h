@@ -262,7 +262,7 @@ int kv_dedup_segment_sum_dev(kv_handle_t h, const void* ids, const float* grad, 
 /* kv_apply_<optimizer>_unique with the id count taken from the DEVICE: the op is applied to the first
  * min(n_max, *n_dev) ids and gradient rows, *n_dev (int64, device memory — kv_dedup_segment_sum_dev's or kv_unique's
  * num_unique_dev) being read by the kernel when it runs.  `optimizer`, `hp` and `slot1` are kv_shard_apply_serve's
- * codes and layouts (0 .. 6, below).  The same promise of unique ids, the same duplicate guard, checks, results and slot
+ * codes and layouts (0 .. 7, below).  The same promise of unique ids, the same duplicate guard, checks, results and slot
  * mirror handling as the _unique ops: the same bits.  `ids` [n_max] are KV_DT_INT64 or KV_DT_INT32 (ids_dtype) whatever
  * the table's key dtype — the dedup writes int64 ids for every table.  `grad` is [n_max, dim].
  * The host sizes everything by n_max: the tables' capacity (their row bounds advance by n_max per call, so a table
@@ -532,6 +532,44 @@ int kv_multi_apply_group_rectified_adam_unique(int num_tables, const kv_handle_t
                                                float l1, float l2, float l21, float r_t, int tractable, int amsgrad,
                                                int use_nesterov, kv_stream_t stream);
 
+/* Plain Adam, one op.  The reference has no kernel for it: its AdamOptimizer composes the sparse step from generic ops
+ * (python/training/adam.py:93-163: TF-core's de-duplication, gather on the slot, the moment arithmetic, scatter_update on
+ * the slot, scatter_sub on the var).  This op leaves what that chain leaves.  `m_v` is ONE slot table of dim 2 x the var's:
+ * [m | v].  Per distinct id, g = the id's summed gradient row, every operation one fp32 rounding:
+ *   m = beta1 m + g (1 - beta1);  v = beta2 v + (g g) (1 - beta2);  slot row = [m | v]
+ *   var = var - (lr_t m) / (epsilon + sqrt(v)),  lr_t = (lr sqrt(1 - beta2_power)) / (1 - beta1_power)
+ * (lr_t, 1 - beta1 and 1 - beta2 once on the host, in fp32.)  Bookkeeping is the chain's (GatherOrInsert kv_variable.h:263-380,
+ * ScatterUpdate :616-734), NOT the group ops':
+ *   slot table: the row is found, or inserted with the init rule; its frequency word gets one hit per distinct id and the
+ *     day stamp (a row inserted now: day << 16 | 1 — the group ops leave 1); a blacklisted row reads as zeros and is left
+ *     unwritten; flags from the row written (UpdateUnderThreshold);
+ *   var table: the row is found, or inserted with the init rule and frequency word 1; an existing row's frequency word and
+ *     day are untouched; NO enter-threshold filter and NO CoverUpdate — a key below the threshold is updated, a
+ *     blacklisted row is neither written nor un-blacklisted (the group ops filter, lift the blacklist and may set it);
+ *     flags from the row written;
+ *   delta lists: every id is marked in both tables.
+ * KV_INVALID_ARGUMENT for lr <= 0, beta1_power >= 1 or beta2_power >= 1 (lr_t would be inf or nan), var == m_v, an m_v
+ * dim other than 2 x the var's ("m_v must be 2x") and tables on different devices; KV_FAILED_PRECONDITION for an
+ * uninitialised table.  Dims, limits, graph capture, deterministic modes, fast math and delta tracking as
+ * kv_apply_group_adam.  _unique / _tok: the forms of kv_apply_group_adam_unique / _tok. */
+int kv_apply_adam(kv_handle_t var, kv_handle_t m_v, const float* grad, const void* ids, int64_t n, float lr, float beta1_power,
+                  float beta2_power, float beta1, float beta2, float epsilon, kv_stream_t stream);
+int kv_apply_adam_tok(kv_handle_t var, kv_handle_t m_v, const float* grad, const void* ids, int64_t n, float lr,
+                      float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, kv_batch_token_t token,
+                      kv_stream_t stream);
+int kv_apply_adam_unique(kv_handle_t var, kv_handle_t m_v, const float* grad, const void* ids, int64_t n, float lr,
+                         float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, kv_stream_t stream);
+/* ... on many (var, m_v) pairs of one dim, shaped like kv_multi_apply_group_adam[_tok|_unique]. */
+int kv_multi_apply_adam(int num_tables, const kv_handle_t* vars, const kv_handle_t* m_vs, const float* const* grads,
+                        const void* const* ids, const int64_t* ns, float lr, float beta1_power, float beta2_power, float beta1,
+                        float beta2, float epsilon, kv_stream_t stream);
+int kv_multi_apply_adam_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* m_vs, const float* const* grads,
+                            const void* const* ids, const int64_t* ns, float lr, float beta1_power, float beta2_power,
+                            float beta1, float beta2, float epsilon, const kv_batch_token_t* tokens, kv_stream_t stream);
+int kv_multi_apply_adam_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* m_vs, const float* const* grads,
+                               const void* const* ids, const int64_t* ns, float lr, float beta1_power, float beta2_power,
+                               float beta1, float beta2, float epsilon, kv_stream_t stream);
+
 
 /* embedding_lookup_sparse on a KvVariable (python/ops/embedding_ops.py:279-441), fused: the
  * reference runs unique_with_counts -> GatherOrInsert[WithCounts] -> gather(idx) -> (x weights) ->
@@ -722,7 +760,8 @@ int kv_shard_apply_route(kv_shard_t shard, const float* grad, kv_stream_t stream
  * 2 Adagrad (hp = lr, update_slots), 3 SparseGroupFtrl (hp = lr, l1, l2, l21, l2_shrinkage, lr_power; slot1 = linear),
  * 4 FTRL-V2, 5 group FTRL-V2 (hp = lr, l1, l2, l2_shrinkage, lr_power; slot1 = linear),
  * 6 group RectifiedAdam (kernels/training_ops.cc:6694-6978; hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2,
- * l21, r_t, tractable, amsgrad, use_nesterov — the three flags as 0 / 1; slot0 = opt, slot1 unused) */
+ * l21, r_t, tractable, amsgrad, use_nesterov — the three flags as 0 / 1; slot0 = opt, slot1 unused),
+ * 7 Adam (kv_apply_adam; hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon; slot0 = m_v, slot1 unused) */
 int kv_shard_apply_serve(kv_shard_t shard, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp,
                          kv_stream_t stream);
 int kv_shard_lookup(kv_shard_t shard, kv_comm_t comm, const void* ids, int64_t n, float* out, int join,

@@ -128,6 +128,7 @@ OPT_FAMILIES = {
     "ftrl_v2": (3, "gin" + "f" * 5),                          # lr, l1, l2, l2_shrinkage, lr_power
     "group_ftrl_v2": (3, "gin" + "f" * 5),
     "group_rectified_adam": (2, "gin" + "f" * 10 + "bbb"),    # ... l21, r_t, tractable, amsgrad, use_nesterov
+    "adam": (2, "gin" + "f" * 6),                             # lr, beta1_power, beta2_power, beta1, beta2, epsilon
 }
 _ARG = {"g": _vp, "i": _vp, "f": _f, "b": _i32}
 for _stem, (_handles, _layout) in OPT_FAMILIES.items():

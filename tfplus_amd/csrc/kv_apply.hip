@@ -1,6 +1,6 @@
 // kv_apply.hip — the optimizer layer of the C ABI on the table core (kv_host.h): one parser per optimizer family, the two
 // bodies (apply_one: one table; multi_apply: many tables, one launch per stage; the PartArgs of all their launches start
-// from opt_part_args), the 36 kv_apply_* / kv_multi_apply_* entry points and kv_attach_slot.  It compiles no kernel: the
+// from opt_part_args), the 42 kv_apply_* / kv_multi_apply_* entry points and kv_attach_slot.  It compiles no kernel: the
 // optimizers' kernels are reached through the typed launchers of kv_launch.h, the pipelines' through the core's.
 #include <hip/hip_runtime.h>
 
@@ -67,6 +67,22 @@ int fused_apply(kv_table* v, WsDev& wd, PartArgs& pa, long long n, hipStream_t s
   return KV_OK;
 }
 
+// What the wide-slot ops call their slot table and say about its shape (the reference's wording where it has an op), one
+// row per optimizer, for apply_one and the batched body alike: a new wide-slot OPT_* gets the neutral row until it has its
+// own.  same_first: the same-table test comes in front of the shape test.  (Behind it the test is never reached — a table
+// never has a multiple of its own dim; the older ops keep their order and answer var == slot with the shape message.)
+struct WideSlotWords { const char* slot; const char* shape; const char* mult; bool same_first; };
+static WideSlotWords wide_slot_words(int opt) {
+  switch (opt) {
+    case OPT_ADAM_V4: case OPT_ADAM_V3:
+      return {"m_v_linear", "kv_variable and linear do not have the same shape [%d] [%d] (m_v_linear must be 3x)", "", false};
+    case OPT_GROUP_RADAM:
+      return {"opt", "kv_variable and opt_shape do not have the same shape [%d] [%d] (opt must be 5x)", "", false};
+    case OPT_ADAM: return {"m_v", "var and m_v do not have matching shapes [%d] [%d] (m_v must be 2x)", ": m_v must be 2x", true};
+    default: return {"slot", "var and slot do not have matching shapes [%d] [%d]", "", false};
+  }
+}
+
 // shared body of the batched optimizer ops: slots1 only for the FTRL family (linear); slot_mult = slot dim / var dim.
 // unique and the capture rule: as apply_common's.  require_reuse: the batched sharded apply — the tables must still hold
 // their lookups' indexes — and, selfs (one per table), read their ranks' own segments in place.
@@ -91,7 +107,8 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
       if (!sl) continue;
       if ((rc = require_initialized(sl[i], "optimizer slot"))) return rc;
       if (sl[i]->dim != slot_mult * D || sl[i]->device != vars[0]->device || sl[i]->key_dtype != vars[0]->key_dtype)
-        return fail(KV_INVALID_ARGUMENT, "var and slot do not have matching shapes (slot dim must be %d x var dim, same device / key dtype)", slot_mult);
+        return fail(KV_INVALID_ARGUMENT, "var and slot do not have matching shapes (slot dim must be %d x var dim, same device / key dtype)%s",
+                    slot_mult, wide_slot_words(OPT).mult);
       all.push_back(sl[i]);
     }
     if (ns[i] > 0 && !grads[i]) return fail(KV_INVALID_ARGUMENT, "grad pointer is null");
@@ -392,6 +409,24 @@ static OptCall group_radam_call(float lr, float b1p, float b2p, float b1, float 
   return c;
 }
 
+// Plain Adam: the reference composes it from generic ops (python/training/adam.py:93-163), so the checks are this
+// library's own.  slot row = m | v.  lr_t (adam.py:142-144) in fp32 in the composition's order; a power at or above 1 would
+// make it inf or nan
+static OptCall adam_call(float lr, float b1p, float b2p, float b1, float b2, float eps) {
+  OptCall c;
+  c.opt = OPT_ADAM;
+  c.slot_mult = slot0_blocks(OPT_ADAM);
+  if (!(lr > 0.f)) { c.status = fail(KV_INVALID_ARGUMENT, "lr is not a positive scalar: %g", lr); return c; }
+  if (!(b1p < 1.f)) { c.status = fail(KV_INVALID_ARGUMENT, "beta1_power is not below 1: %g", b1p); return c; }
+  if (!(b2p < 1.f)) { c.status = fail(KV_INVALID_ARGUMENT, "beta2_power is not below 1: %g", b2p); return c; }
+  OptArgs& a = c.a;
+  a.lr = lr; a.b1p = b1p; a.b2p = b2p; a.b1 = b1; a.b2 = b2; a.eps = eps;
+  a.alpha = (lr * std::sqrt(1.f - b2p)) / (1.f - b1p);
+  adam_omb1(a) = 1.f - b1;
+  adam_omb2(a) = 1.f - b2;
+  return c;
+}
+
 // the one place where a runtime OPT_* becomes the template argument of the pipelines
 template <class F>
 static int with_opt(int opt, F&& f) {
@@ -403,6 +438,7 @@ static int with_opt(int opt, F&& f) {
     case OPT_FTRL_V2: return f(std::integral_constant<int, OPT_FTRL_V2>());
     case OPT_GROUP_FTRL_V2: return f(std::integral_constant<int, OPT_GROUP_FTRL_V2>());
     case OPT_GROUP_RADAM: return f(std::integral_constant<int, OPT_GROUP_RADAM>());
+    case OPT_ADAM: return f(std::integral_constant<int, OPT_ADAM>());
     default: return fail(KV_INTERNAL, "optimizer %d", opt);
   }
 }
@@ -415,7 +451,8 @@ namespace __attribute__((visibility("hidden"))) kvhip_internal {
 // 2 Adagrad (hp = lr, update_slots), 3 SparseGroupFtrl (hp = lr, l1, l2, l21, l2_shrinkage, lr_power; slot1 = linear),
 // 4 FTRL-V2 / 5 group FTRL-V2 (hp = lr, l1, l2, l2_shrinkage, lr_power; slot1 = linear),
 // 6 group RectifiedAdam (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad,
-// use_nesterov; the three flags as 0 / 1)
+// use_nesterov; the three flags as 0 / 1),
+// 7 Adam (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon; slot0 = m_v)
 OptCall shard_opt_call(int optimizer, const float* hp) {
   switch (optimizer) {
     case OPT_ADAM_V4: case OPT_ADAM_V3:
@@ -426,6 +463,7 @@ OptCall shard_opt_call(int optimizer, const float* hp) {
     case OPT_GROUP_RADAM:
       return group_radam_call(hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8], hp[9], hp[10] != 0.f, hp[11] != 0.f,
                               hp[12] != 0.f);
+    case OPT_ADAM: return adam_call(hp[0], hp[1], hp[2], hp[3], hp[4], hp[5]);
     default: return OptCall{};
   }
 }
@@ -439,8 +477,9 @@ int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const f
   const bool two = two_slots(c.opt);
   if ((rc = check_table(v)) || (rc = check_table(s0)) || (two && (rc = check_table(s1)))) return rc;
   if (c.status && c.opt < 0) return c.status;
+  const WideSlotWords ww = wide_slot_words(c.opt);
   if (wide_slot(c.opt)) {   // order and wording of training_ops.cc:7001-7103 (group RectifiedAdam: :6714-6721)
-    if ((rc = require_initialized(v, "var")) || (rc = require_initialized(s0, group_adam(c.opt) ? "m_v_linear" : "opt"))) return rc;
+    if ((rc = require_initialized(v, "var")) || (rc = require_initialized(s0, ww.slot))) return rc;
   } else if (!two) {
     if (!v->initialized || !s0->initialized)
       return fail(KV_FAILED_PRECONDITION, "Attempting to use uninitialized variables: %s", !v->initialized ? "var" : "accum");
@@ -449,14 +488,12 @@ int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const f
   }
   if (c.status) return c.status;
   if (wide_slot(c.opt)) {
-    // (group RectifiedAdam: the reference's check (:6790-6805) also lets an opt dim EQUAL to the var's through and would
-    // then read four blocks past the row; here only 5x passes)
-    if (s0->dim != c.slot_mult * v->dim)
-      return group_adam(c.opt)
-                 ? fail(KV_INVALID_ARGUMENT, "kv_variable and linear do not have the same shape [%d] [%d] (m_v_linear must be 3x)", v->dim, s0->dim)
-                 : fail(KV_INVALID_ARGUMENT, "kv_variable and opt_shape do not have the same shape [%d] [%d] (opt must be 5x)", v->dim, s0->dim);
+    // (group RectifiedAdam: the reference's shape check (:6790-6805) also lets an opt dim EQUAL to the var's through and
+    // would then read four blocks past the row; here only 5x passes)
+    if (ww.same_first && v == s0) return fail(KV_INVALID_ARGUMENT, "var and %s are the same table", ww.slot);
+    if (s0->dim != c.slot_mult * v->dim) return fail(KV_INVALID_ARGUMENT, ww.shape, v->dim, s0->dim);
     if (v->device != s0->device) return fail(KV_INVALID_ARGUMENT, "var and slot live on different devices");
-    if (v == s0) return fail(KV_INVALID_ARGUMENT, "var and %s are the same table", group_adam(c.opt) ? "m_v_linear" : "opt");
+    if (v == s0) return fail(KV_INVALID_ARGUMENT, "var and %s are the same table", ww.slot);
   } else if (!two) {
     if (s0->dim != v->dim) return fail(KV_INVALID_ARGUMENT, "var and accum do not have the same shape [%d] [%d]", v->dim, s0->dim);
     if (v->device != s0->device || v == s0) return fail(KV_INVALID_ARGUMENT, "var and accum must be distinct tables on one device");
@@ -587,6 +624,34 @@ int kv_multi_apply_group_rectified_adam_unique(int num_tables, const kv_handle_t
                                                kv_stream_t stream) {
   return multi_apply(group_radam_call(lr, b1p, b2p, b1, b2, eps, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov), num_tables,
                      vars, opts, nullptr, grads, ids, ns, nullptr, stream, true);
+}
+
+int kv_apply_adam(kv_handle_t v, kv_handle_t mv, const float* grad, const void* ids, int64_t n, float lr, float b1p, float b2p,
+                  float b1, float b2, float eps, kv_stream_t stream) {
+  return apply_one(adam_call(lr, b1p, b2p, b1, b2, eps), v, mv, nullptr, grad, ids, n, 0, stream, false);
+}
+int kv_apply_adam_tok(kv_handle_t v, kv_handle_t mv, const float* grad, const void* ids, int64_t n, float lr, float b1p,
+                      float b2p, float b1, float b2, float eps, kv_batch_token_t token, kv_stream_t stream) {
+  return apply_one(adam_call(lr, b1p, b2p, b1, b2, eps), v, mv, nullptr, grad, ids, n, token, stream, false);
+}
+int kv_apply_adam_unique(kv_handle_t v, kv_handle_t mv, const float* grad, const void* ids, int64_t n, float lr, float b1p,
+                         float b2p, float b1, float b2, float eps, kv_stream_t stream) {
+  return apply_one(adam_call(lr, b1p, b2p, b1, b2, eps), v, mv, nullptr, grad, ids, n, 0, stream, true);
+}
+int kv_multi_apply_adam(int num_tables, const kv_handle_t* vars, const kv_handle_t* mvs, const float* const* grads,
+                        const void* const* ids, const int64_t* ns, float lr, float b1p, float b2p, float b1, float b2, float eps,
+                        kv_stream_t stream) {
+  return multi_apply(adam_call(lr, b1p, b2p, b1, b2, eps), num_tables, vars, mvs, nullptr, grads, ids, ns, nullptr, stream, false);
+}
+int kv_multi_apply_adam_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* mvs, const float* const* grads,
+                            const void* const* ids, const int64_t* ns, float lr, float b1p, float b2p, float b1, float b2,
+                            float eps, const kv_batch_token_t* tokens, kv_stream_t stream) {
+  return multi_apply(adam_call(lr, b1p, b2p, b1, b2, eps), num_tables, vars, mvs, nullptr, grads, ids, ns, tokens, stream, false);
+}
+int kv_multi_apply_adam_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* mvs, const float* const* grads,
+                               const void* const* ids, const int64_t* ns, float lr, float b1p, float b2p, float b1, float b2,
+                               float eps, kv_stream_t stream) {
+  return multi_apply(adam_call(lr, b1p, b2p, b1, b2, eps), num_tables, vars, mvs, nullptr, grads, ids, ns, nullptr, stream, true);
 }
 
 int kv_apply_adagrad(kv_handle_t v, kv_handle_t acc, float lr, const float* grad, const void* ids, int64_t n, int update_slots,

@@ -427,27 +427,30 @@ __device__ __forceinline__ bool group_any(bool p) {
 // SparseGroupSparseApplyFtrlOp (training_ops.cc:7142-7197, 5871-5927, 1455-1486, 684-763).
 // State rows the caller already holds (requested together with the gradient rows, so the update needs no
 // second round trip): x = the var row; s[0 .. slot0_blocks(OPT)) = the first slot table's row in blocks of dim floats
-// (GroupAdam m | v | z; group RectifiedAdam m | v | linear | vhat | vamsgrad; Adagrad / FTRL accum in s[0]).  have_x /
+// (GroupAdam m | v | z; group RectifiedAdam m | v | linear | vhat | vamsgrad; Adam m | v; Adagrad / FTRL accum in s[0]).  have_x /
 // have_s say which of them are valid.  (s has opt_core's width, state_blocks(OPT): the lean paths hand it over as it is.)
 template <int OPT, int V, int K>
 struct PreRows {
   float x[K][V], s[state_blocks(OPT)][K][V];
 };
 // The row math and the stores of one key's update, on values the caller already holds: xin = the var row;
-// sin = GroupAdam m | v | z, group RectifiedAdam m | v | linear | vhat | vamsgrad, Adagrad accum, FTRL accum | linear.
+// sin = GroupAdam m | v | z, group RectifiedAdam m | v | linear | vhat | vamsgrad, Adam m | v, Adagrad accum, FTRL accum | linear.
 // Element e of a row lives at lane
 // (e / V) % LPR, step (e / V) / LPR.  All LPR lanes of every group of the wave call it (shuffles inside); `act`
 // masks groups without an update.  fvp / f0p / f1p = the flag bytes of the var / first / second slot row.
-// new1 = the second slot row was inserted now (its flags come from its values).
+// new1 = the second slot row was inserted now (its flags come from its values).  vblack / sblack (scatter_chain(OPT)
+// only): the var / slot row is blacklisted — it reads as zeros where it is read and is left as it is.
 // Restates the per-id body of KvVariableGroupSparseApplyAdamV4Op / V3Op / SparseApplyAdagradOp /
 // SparseGroupSparseApplyFtrlOp / SparseApplyFtrlOp / GroupSparseApplyFtrlOp / GroupSparseApplyRectifiedAdamOp
-// (training_ops.cc:7142-7197, 5871-5927, 1455-1486, 684-763, 457-484, 977-1019, 6883-6936).
+// (training_ops.cc:7142-7197, 5871-5927, 1455-1486, 684-763, 457-484, 977-1019, 6883-6936) and, for Adam, the row
+// arithmetic of the reference's Python composition (python/training/adam.py:93-163).
 template <int OPT, int V, int LPR, int K>
 __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row, unsigned char* fvp, unsigned char* f0p,
                                          unsigned char* f1p, bool act, bool new0, int D, const float (&gv)[K][V],
                                          const OptArgs& a, int lane, const float (&xin)[K][V],
-                                         const float (&sin)[state_blocks(OPT)][K][V], bool new1 = false) {
-  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_GROUP_RADAM, "opt_core: unknown optimizer");
+                                         const float (&sin)[state_blocks(OPT)][K][V], bool new1 = false, bool vblack = false,
+                                         bool sblack = false) {
+  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_ADAM, "opt_core: unknown optimizer");
   if (group_adam(OPT)) {
     // training_ops.cc:7166-7195 (V4) / :5895-5925 (V3); slot row = [m | v | z]
     float m[K][V], nv[K][V], sq[K][V], z[K][V], uu[K][V];
@@ -716,7 +719,7 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
       *f0p = (unsigned char)(anya ? 0u : FLAG_UNDER);
       *f1p = (unsigned char)(anyz ? 0u : FLAG_UNDER);
     }
-  } else {
+  } else if (OPT == OPT_GROUP_RADAM) {
     // OPT_GROUP_RADAM: KvVariableGroupSparseApplyRectifiedAdam, training_ops.cc:6883-6936; slot row =
     // [m | v | linear | vhat | vamsgrad].  a.alpha = sqrt(1 - beta2_power), radam_c1(a) = 1 - beta1_power (host, fp32).
     // m_corr is a copy of m's TensorMap (FlatVector, :195): the nesterov assignment writes m itself
@@ -790,6 +793,42 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
       *fvp = (unsigned char)(upd ? (anyx ? 0u : FLAG_UNDER) : (FLAG_BLACK | FLAG_UNDER));
       *f0p = (unsigned char)(anys ? 0u : FLAG_UNDER);
     }
+  } else {
+    // OPT_ADAM: python/training/adam.py:93-163 on one de-duplicated id; slot row = [m | v].  a.alpha = lr_t =
+    // lr sqrt(1 - beta2_power) / (1 - beta1_power), adam_omb1 / adam_omb2 = 1 - beta1 / 1 - beta2 (host, fp32).  One pass:
+    // nothing couples the elements of a row, so no value outlives its element block.  The gather hands a blacklisted slot
+    // row over as zeros (table_manager.h:224-226) and neither scatter writes a blacklisted row (kv_variable.h:700-712)
+    bool big = false, sbig = false;
+    const bool fm = KV_FASTM(a);
+    const float omb1 = adam_omb1(a), omb2 = adam_omb2(a);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      if (act && e0 < D) {
+        float xn[V], mn[V], vn[V];
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+          const float mo = sblack ? 0.f : sin[0][k][c], vo = sblack ? 0.f : sin[1][k][c];
+          const float gg = gv[k][c];
+          mn[c] = a.b1 * mo + gg * omb1;
+          vn[c] = a.b2 * vo + (gg * gg) * omb2;
+          xn[c] = xin[k][c] - kv_div(a.alpha * mn[c], a.eps + kv_sqrt(vn[c], fm), fm);
+          big |= fabsf(xn[c]) >= CUTOFF;
+          sbig |= fabsf(mn[c]) >= CUTOFF || fabsf(vn[c]) >= CUTOFF;
+        }
+        if (!vblack) stv<V>(xrow + e0, xn);
+        if (!sblack) {
+          stv<V>(s0row + e0, mn);
+          stv<V>(s0row + e0 + D, vn);
+        }
+      }
+    }
+    const bool anyx = group_any<LPR>(big), anys = group_any<LPR>(sbig);
+    if (act && lane == 0) {
+      // UpdateUnderThreshold on the rows written (kv_variable.h:706, 837-861); a blacklisted row keeps its flags
+      if (!vblack) *fvp = (unsigned char)(anyx ? 0u : FLAG_UNDER);
+      if (!sblack) *f0p = (unsigned char)(anys ? 0u : FLAG_UNDER);
+    }
   }
 }
 
@@ -801,7 +840,7 @@ __device__ __forceinline__ void opt_update_row(const TableDev& tv, const TableDe
                                                unsigned r0, bool new0, unsigned r1, bool new1,
                                                bool live, const float (&gv)[K][V], const OptArgs& a,
                                                int lane, const PreRows<OPT, V, K>* pre = nullptr, bool have_x = false,
-                                               bool have_s = false) {
+                                               bool have_s = false, bool vblack = false, bool sblack = false) {
   const int D = tv.dim;
   const bool skip = !live || (tag & ROW_FILTERED) || (tag & ROW_MASK) == 0u;  // training_ops.cc:7150-7152
   const unsigned rv = tag & ROW_MASK;
@@ -845,7 +884,7 @@ __device__ __forceinline__ void opt_update_row(const TableDev& tv, const TableDe
       ldslot<V>(s0row, ia0, ib0, new0, e0, sin[0][k]);
       if (NS0 > 1) {
         ldslot<V>(s0row, ia0, ib0, new0, e0 + D, sin[1][k]);
-        ldslot<V>(s0row, ia0, ib0, new0, e0 + 2 * D, sin[2][k]);
+        if (NS0 > 2) ldslot<V>(s0row, ia0, ib0, new0, e0 + 2 * D, sin[2][k]);   // (Adam's row ends after two blocks)
       }
 #pragma unroll
       for (int b3 = 3; b3 < NS0; ++b3) ldslot<V>(s0row, ia0, ib0, new0, e0 + b3 * D, sin[b3][k]);
@@ -853,7 +892,8 @@ __device__ __forceinline__ void opt_update_row(const TableDev& tv, const TableDe
     if (two_slots(OPT)) ldslot<V>(s1row, ia1, ib1, new1, e0, sin[1][k]);
   }
   opt_core<OPT, V, LPR, K>(xrow, s0row, s1row, flags_ptr(tv, act ? rv : 0u), flags_ptr(ts0, act ? r0 : 0u),
-                           two_slots(OPT) ? flags_ptr(ts1, act ? r1 : 0u) : nullptr, act, new0, D, gv, a, lane, xin, sin, new1);
+                           two_slots(OPT) ? flags_ptr(ts1, act ? r1 : 0u) : nullptr, act, new0, D, gv, a, lane, xin, sin, new1, vblack,
+                           sblack);
 }
 
 // ------------------------------------------------------------------------------------------

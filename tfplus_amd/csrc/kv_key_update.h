@@ -15,7 +15,8 @@ __device__ __forceinline__ unsigned freq_add_sat(unsigned word, unsigned count) 
 // The slot-table rows of one key, resolved by the group leader.  FindOrInsertUnsafe(var, filter_out !=
 // nullptr) kv_variable.h:382-408 and FindOrInsertUnsafe(slot, nullptr) :409-414; FTRL probes linear
 // before accum (training_ops.cc:701-704).  `m0` is the record of the hinted slot row (requested early).
-struct RowsOf { unsigned tag, r0, r1, nb; };   // nb: bit 1 / 2 = slot row 0 / 1 inserted now, bit 3 = slot row 0 is the hinted one
+struct RowsOf { unsigned tag, r0, r1, nb; };   // nb: bit 1 / 2 = slot row 0 / 1 inserted now, bit 3 = slot row 0 is the hinted one,
+                                               // bit 4 / 5 (scatter_chain(OPT)) = the var / slot row is blacklisted
 template <int OPT>
 __device__ __forceinline__ RowsOf resolve_rows(const PartArgs& a, long long key, unsigned rvw, unsigned hint,
                                                bool hint_loaded, const RowMeta& m0) {
@@ -27,7 +28,10 @@ __device__ __forceinline__ RowsOf resolve_rows(const PartArgs& a, long long key,
   // (RemoveBlacklistUnsafe hands out a zero row, table_manager.h:359-372) and the group optimizers
   // rewrite the flags after the update, so with enter_threshold == 0 they never read it
   const bool need_vmeta = keeps_var_flags(OPT) || a.tv.enter_threshold != 0u;
-  if (need_vmeta && !vnew) {
+  bool vblack = false, sblack = false;
+  if (scatter_chain(OPT)) {   // ScatterSub (kv_variable.h:616-734): no filter; a blacklisted row is skipped, not lifted
+    if (!vnew) vblack = (load_freq_flags(a.tv, rv).y & FLAG_BLACK) != 0u;
+  } else if (need_vmeta && !vnew) {
     const uint2 mv = load_freq_flags(a.tv, rv);
     if ((mv.x & 0xFFFFu) < a.tv.enter_threshold) { o.tag = rv | ROW_FILTERED; return o; }  // kv_variable.h:910
     if (mv.y & FLAG_BLACK) meta_ptr(a.tv, rv)->flags = FLAG_UNDER;   // RemoveBlacklistUnsafe: fresh zero row (ours already is)
@@ -39,13 +43,17 @@ __device__ __forceinline__ RowsOf resolve_rows(const PartArgs& a, long long key,
     unsigned r = 0, f = 0;
     if (use_hint && hint_loaded && m0.key == key && !(m0.flags & FLAG_FREE)) {
       r = hint; f = m0.freq; hinted = true;
+      if (scatter_chain(OPT)) sblack = (m0.flags & FLAG_BLACK) != 0u;
     } else {
       r = table_find(t, key);
       if (__builtin_expect(r == 0u, 0)) {
         r = table_find_or_insert(t, key, isnew);
-        if (r && *isnew) { RowMeta* m = meta_ptr(t, r); m->freq = 1u; m->flags = 0; }
+        // (scatter_chain: GatherOrInsert's insert_func stamps the day, kv_variable.h:339-363; FindOrInsertUnsafe's does not)
+        if (r && *isnew) { RowMeta* m = meta_ptr(t, r); m->freq = scatter_chain(OPT) ? ((a.day << 16) | 1u) : 1u; m->flags = 0; }
       }
-      if (r && !*isnew) f = meta_ptr(t, r)->freq;
+      if (scatter_chain(OPT)) {
+        if (r && !*isnew) { const uint2 ff = load_freq_flags(t, r); f = ff.x; sblack = (ff.y & FLAG_BLACK) != 0u; }
+      } else if (r && !*isnew) f = meta_ptr(t, r)->freq;
       if (use_hint && r) {   // remember it in the var's index entry
         Entry* e = table_entry_of(a.tv, key);
         if (e) e->hint = r;
@@ -65,6 +73,7 @@ __device__ __forceinline__ RowsOf resolve_rows(const PartArgs& a, long long key,
     if (two_slots(OPT) && o.r1) mark_delta(a.ts1, o.r1);
   }
   o.nb = (new0 ? 2u : 0u) | (new1 ? 4u : 0u) | (hinted ? 8u : 0u);
+  if (scatter_chain(OPT)) o.nb |= (vblack ? 16u : 0u) | (sblack ? 32u : 0u);
   return o;
 }
 
@@ -119,7 +128,8 @@ __device__ __forceinline__ void finish_key(const PartArgs& a, const uint4 hd, bo
     }
     // the slot rows in `pre` are those of the hinted row: good only if the hint stood up
     opt_update_row<OPT, V, LPR, K>(a.tv, a.ts0, a.ts1, key, ro.tag, ro.r0, (ro.nb & 2u) != 0, ro.r1, (ro.nb & 4u) != 0,
-                                   live, gv, a.opt, lane, pre, have_x, have_s && (ro.nb & 8u) != 0);
+                                   live, gv, a.opt, lane, pre, have_x, have_s && (ro.nb & 8u) != 0,
+                                   scatter_chain(OPT) && (ro.nb & 16u) != 0, scatter_chain(OPT) && (ro.nb & 32u) != 0);
     // the key's slot record as this update left it goes into the var row's mirror (clean: the slot table's own record is
     // up to date), so that the key's NEXT apply takes the lean path without reading it
     if (!two_slots(OPT) && a.use_mirror && live && lane == 0 && ro.r0 != 0u && (ro.tag & ROW_MASK) != 0u && !(ro.tag & ROW_FILTERED)) {
@@ -214,7 +224,11 @@ __device__ __forceinline__ bool key_update(const PartArgs& a, const LeanCtx& c, 
                   mir.x == hh;
   const unsigned sfreq = mir.y;   // the slot row's frequency word
   bool act = ok;
-  if (c.need_vmeta && ok && !vnew) {   // frequency filter / un-blacklisting (resolve_rows; kv_variable.h:910)
+  bool vblack = false, sblack = false;
+  if (scatter_chain(OPT)) {   // no filter; blacklisted rows stay as they are (resolve_rows)
+    vblack = ok && !vnew && (vm.y & FLAG_BLACK) != 0u;
+    sblack = ok && (mir.z & FLAG_BLACK) != 0u;
+  } else if (c.need_vmeta && ok && !vnew) {   // frequency filter / un-blacklisting (resolve_rows; kv_variable.h:910)
     if ((vm.x & 0xFFFFu) < c.thr) act = false;
     else if ((vm.y & FLAG_BLACK) && lane == 0) c.vmeta[(size_t)row * META_STRIDE].flags = FLAG_UNDER;
   }
@@ -225,6 +239,6 @@ __device__ __forceinline__ bool key_update(const PartArgs& a, const LeanCtx& c, 
     mp->state = (unsigned char)MIRROR_DIRTY;
   }
   opt_core<OPT, V, LPR, K>(c.vrows + (size_t)rr * D, c.srows + (size_t)h2 * c.SD, nullptr, &c.vmeta[(size_t)rr * META_STRIDE].flags,
-                           &mp->flags, nullptr, act, false, D, gv, a.opt, lane, pre.x, pre.s);
+                           &mp->flags, nullptr, act, false, D, gv, a.opt, lane, pre.x, pre.s, false, vblack, sblack);
   return go && !ok;
 }

@@ -35,6 +35,7 @@ KV_OPT_LAUNCHERS(OPT_FTRL);            // kv_opt_ftrl.hip
 KV_OPT_LAUNCHERS(OPT_FTRL_V2);         // kv_opt_ftrl_v2.hip
 KV_OPT_LAUNCHERS(OPT_GROUP_FTRL_V2);   // kv_opt_group_ftrl_v2.hip
 KV_OPT_LAUNCHERS(OPT_GROUP_RADAM);     // kv_opt_group_radam.hip
+KV_OPT_LAUNCHERS(OPT_ADAM);            // kv_opt_adam.hip
 
 // ---- optimizer-free (kv_sums.hip) --------------------------------------------------------------------------------------
 // k_tsum (kv_fused.h): the tile sums in front of k_papply

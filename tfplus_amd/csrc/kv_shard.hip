@@ -762,7 +762,7 @@ static int shards_apply(bool single, const kv_shard_t* shards, int ntab, kv_comm
   for (const auto& grp : groups_of(ntab, [&](int k) {
          const kv_shard* sh = shards[k];
          const BatchIndex::Plan served = sh->table->batch.plan(sh->serve_token, (long long)sh->world * (sh->C + 1), fused_tab(sh->table));
-         return optimizer >= 0 && optimizer <= OPT_GROUP_RADAM && shard_owner_batchable(sh) && BatchIndex::takes_entries(served) && slot0[k] != nullptr &&
+         return optimizer >= 0 && optimizer <= OPT_ADAM && shard_owner_batchable(sh) && BatchIndex::takes_entries(served) && slot0[k] != nullptr &&
                         (!two_slots(optimizer) || (slot1 && slot1[k]))
                     ? sh->table->dim : -1; })) {
     const int m = (int)grp.size();

@@ -12,7 +12,7 @@ namespace __attribute__((visibility("hidden"))) kvhip_internal {
 enum Mode { MODE_LOOKUP = 0, MODE_APPLY = 1, MODE_DEDUP = 2, MODE_SCATTER = 3, MODE_MARK = 4, MODE_UNIQUE = 5,
             MODE_APPLYIDX = 6 };
 enum Opt { OPT_ADAM_V4 = 0, OPT_ADAM_V3 = 1, OPT_ADAGRAD = 2, OPT_FTRL = 3, OPT_FTRL_V2 = 4, OPT_GROUP_FTRL_V2 = 5,
-           OPT_GROUP_RADAM = 6 };
+           OPT_GROUP_RADAM = 6, OPT_ADAM = 7 };
 // What the pipelines ask of an optimizer, in one place (a new OPT_* must answer each of them):
 // GroupAdam: one slot table of three dim-wide blocks (m | v | z)
 constexpr bool group_adam(int opt) { return opt == OPT_ADAM_V4 || opt == OPT_ADAM_V3; }
@@ -21,8 +21,14 @@ constexpr bool group_adam(int opt) { return opt == OPT_ADAM_V4 || opt == OPT_ADA
 constexpr bool two_slots(int opt) { return opt == OPT_FTRL || opt == OPT_FTRL_V2 || opt == OPT_GROUP_FTRL_V2; }
 // no CoverUpdate of the var: its flags are read (blacklist lifted by RemoveBlacklistUnsafe) and left to a later lookup
 constexpr bool keeps_var_flags(int opt) { return opt == OPT_ADAGRAD || opt == OPT_FTRL_V2; }
-// dim-wide blocks of the first slot row (group RectifiedAdam: m | v | linear | vhat | vamsgrad)
-constexpr int slot0_blocks(int opt) { return opt == OPT_GROUP_RADAM ? 5 : group_adam(opt) ? 3 : 1; }
+// plain Adam: the bookkeeping of the generic ops its reference composes (python/training/adam.py:93-163), GatherOrInsert
+// and ScatterUpdate on the slot row, ScatterSub on the var (kv_variable.h:263-380, 616-734), not a training op's.  The var
+// has no frequency filter and no CoverUpdate: a blacklisted row stays blacklisted and unwritten, any other row's flags are
+// recomputed from the row written.  A slot row inserted now carries the day stamp (insert_func); a blacklisted one reads
+// as zeros and is left unwritten
+constexpr bool scatter_chain(int opt) { return opt == OPT_ADAM; }
+// dim-wide blocks of the first slot row (group RectifiedAdam: m | v | linear | vhat | vamsgrad; Adam: m | v)
+constexpr int slot0_blocks(int opt) { return opt == OPT_GROUP_RADAM ? 5 : group_adam(opt) ? 3 : opt == OPT_ADAM ? 2 : 1; }
 // one wide slot table whose dim is a multiple of the var's (what the ops' initialisation and shape checks ask)
 constexpr bool wide_slot(int opt) { return slot0_blocks(opt) > 1; }
 // dim-wide blocks of optimizer state a key's update holds besides the var row: the first slot row's (the FTRL family's
@@ -146,9 +152,11 @@ struct WsDev {
                            // position -> entry -> record); nullptr: not filed
 };
 
+// (Fields an optimizer's math has no use for carry that optimizer's own host scalars — the radam_* / adam_* accessors below:
+// read l2s, lr_power and update_slots per optimizer, never for all of them.)
 struct OptArgs {
   float lr, b1p, b2p, b1, b2, eps, l1, l2, l21, l2s, lr_power;
-  float alpha, l21_norm;  // host-precomputed in fp32 exactly as the reference does (group RectifiedAdam: sqrt(1 - beta2_power))
+  float alpha, l21_norm;  // host-precomputed in fp32 exactly as the reference does (group RectifiedAdam: sqrt(1 - beta2_power); Adam: lr_t)
   int update_slots;
   int fast;               // row math on the hardware's 1-ulp v_sqrt_f32 / v_rcp_f32 (kv_set_fast_math; 0: IEEE sequences)
 };
@@ -163,6 +171,11 @@ __host__ __device__ inline float& radam_c1(OptArgs& a) { return a.lr_power; }   
 __host__ __device__ inline float radam_c1(const OptArgs& a) { return a.lr_power; }
 __host__ __device__ inline int& radam_flags(OptArgs& a) { return a.update_slots; }  // RADAM_* bits
 __host__ __device__ inline int radam_flags(const OptArgs& a) { return a.update_slots; }
+// ... and plain Adam's: alpha carries lr_t = lr sqrt(1 - beta2_power) / (1 - beta1_power); 1 - beta1 and 1 - beta2 (host, fp32)
+__host__ __device__ inline float& adam_omb1(OptArgs& a) { return a.l2s; }
+__host__ __device__ inline float adam_omb1(const OptArgs& a) { return a.l2s; }
+__host__ __device__ inline float& adam_omb2(OptArgs& a) { return a.lr_power; }
+__host__ __device__ inline float adam_omb2(const OptArgs& a) { return a.lr_power; }
 
 // arguments of the index / partition pass and the optimizer apply (kv_kernels.h: partition pass)
 struct PartArgs {

@@ -237,7 +237,8 @@ def _hp_array(hp):
 
 # stem of an optimizer family + its scalars (the order of _lib.OPT_FAMILIES) -> the optimizer code and hp vector of the
 # generic entry points (the OPT_* codes below; GroupAdam's trailing scalar is its version)
-_COUNTED_CODE = {"adagrad": 2, "sparse_group_ftrl": 3, "ftrl_v2": 4, "group_ftrl_v2": 5, "group_rectified_adam": 6}
+_COUNTED_CODE = {"adagrad": 2, "sparse_group_ftrl": 3, "ftrl_v2": 4, "group_ftrl_v2": 5, "group_rectified_adam": 6,
+                 "adam": 7}
 
 
 def _code_and_hp(stem, scalars):
@@ -342,6 +343,17 @@ def kv_variable_group_sparse_apply_rectified_adam(var, opt, grad, indices, lr, b
   _apply("group_rectified_adam", (var, opt), grad, indices,
          (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, bool(tractable), bool(amsgrad),
           bool(use_nesterov)), unique_indices, token, unique_count)
+
+
+def kv_variable_sparse_apply_adam(var, m_v, grad, indices, lr, beta1_power, beta2_power, beta1, beta2, epsilon,
+                                  use_locking=False, name=None, unique_indices=False, unique_count=None, token=None):
+  """Plain Adam's sparse step as ONE op (kvhip.h kv_apply_adam).  The reference has no op for it: its AdamOptimizer
+  composes gather -> moment arithmetic -> scatter_update -> scatter_sub (python/training/adam.py:93-163), and this op
+  leaves what that chain leaves on de-duplicated ids.  `m_v` is one slot table of dim 2 x the var's, m | v.  The duplicate
+  sum is inside the op.  token: the batch token of the lookup of the same ids (default: the one the var's last lookup of
+  this very tensor left)."""
+  _apply("adam", (var, m_v), grad, indices, (lr, beta1_power, beta2_power, beta1, beta2, epsilon), unique_indices, token,
+         unique_count)
 
 
 def kv_dedup_segment_sum(table_handle, indices, grad, sync=True):
@@ -765,6 +777,13 @@ def kv_multi_group_sparse_apply_rectified_adam(var_handles, opt_handles, grads, 
                 bool(use_nesterov)), unique_indices)
 
 
+def kv_multi_sparse_apply_adam(var_handles, m_v_handles, grads, indices, lr, beta1_power, beta2_power, beta1, beta2,
+                               epsilon, unique_indices=False):
+  """kv_variable_sparse_apply_adam on many (var, m_v) pairs with two kernel launches (one with unique_indices)."""
+  _multi_apply("adam", "vars, m_vs, grads and indices", (var_handles, m_v_handles), grads, indices,
+               (lr, beta1_power, beta2_power, beta1, beta2, epsilon), unique_indices)
+
+
 _COMBINERS = {"sum": _lib.KV_COMBINER_SUM, "mean": _lib.KV_COMBINER_MEAN, "sqrtn": _lib.KV_COMBINER_SQRTN}
 
 
@@ -974,6 +993,7 @@ OPT_GROUP_ADAM_V4, OPT_GROUP_ADAM_V3, OPT_ADAGRAD, OPT_SPARSE_GROUP_FTRL = 0, 1,
 OPT_FTRL_V2, OPT_GROUP_FTRL_V2 = 4, 5   # hp = lr, l1, l2, l2_shrinkage, lr_power; slots = (accum, linear)
 # hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov (flags 0 / 1)
 OPT_GROUP_RADAM = 6
+OPT_ADAM = 7   # hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon; slots = (m_v,)
 
 
 class KvComm(object):
