@@ -47,22 +47,27 @@ def ftrl_v2(x, a, z, g, lr, l1, l2, l2_shrinkage, lr_power):
   return x1.astype(F), a1.astype(F), z1.astype(F)
 
 
-def group_ftrl_v2(x, a, z, g, lr, l1, l2, l2_shrinkage, lr_power):
+def group_ftrl_v2(x, a, z, g, lr, l1, l2, l2_shrinkage, lr_power, dtype=F):
   """-> (var, accum, linear, updated) after one KvVariableGroupSparseApplyFtrlV2 step; updated[i] is False where row i
-  was blacklisted (its var reads as zeros)."""
-  x, a, z, g = (np.asarray(t, F) for t in (x, a, z, g))
-  lr, l1, two_l2, two_l2s, lrp = _hp(lr, l1, l2, l2_shrinkage, lr_power)
+  was blacklisted (its var reads as zeros).  dtype = np.float64: the same step in double precision (the hyperparameters
+  still start from their float32 values)."""
+  T = dtype
+  x, a, z, g = (np.asarray(t, T) for t in (x, a, z, g))
+  lr, l1, two_l2, two_l2s, lrp = (T(v) for v in _hp(lr, l1, l2, l2_shrinkage, lr_power))
   with np.errstate(all="ignore"):
-    pn, z1 = _linear(x, a, z, g, lr, two_l2s, lrp)
-    norm = np.sqrt((z1 * z1).sum(axis=1, dtype=F)).astype(F)[:, None]
+    gs = g + two_l2s * x
+    na = a + gs * gs
+    pn, po = (np.sqrt(v) if lrp == T(-0.5) else np.power(v, -lrp).astype(T) for v in (na, a))
+    z1 = z + (gs - ((pn - po) / lr) * x)
+    norm = np.sqrt((z1 * z1).sum(axis=1, dtype=T)).astype(T)[:, None]
     upd = norm > l1
     coef = (l1 - norm) / ((pn / lr + two_l2) * norm)
-    x1 = np.where(upd, coef * z1, F(0))
+    x1 = np.where(upd, coef * z1, T(0))
     xa = np.where(upd, x1, x)
     gs2 = g + two_l2s * xa
     g2 = gs2 * gs2
     a1 = (a + g2) + g2
-  return x1.astype(F), a1.astype(F), z1.astype(F), upd[:, 0]
+  return x1.astype(T), a1.astype(T), z1.astype(T), upd[:, 0]
 
 
 def under_threshold(rows):

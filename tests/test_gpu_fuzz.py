@@ -4,7 +4,11 @@ exactly; rows and optimizer state to north_star's 1e-6 relative.  The optimizer 
 ops get — unique ids and TF-core's occurrence-ordered segment sums (variable_scope.py:1096-1106 runs
 tf.unique + unsorted_segment_sum in front of them) — so no summation-order allowance is needed here; the
 fused segment reduction of repeated ids is bounded per element in test_gpu_config_sizes.py,
-test_gpu_parity.py::test_full_size_batch_properties and test_large_batches_match_oracle below."""
+test_gpu_parity.py::test_full_size_batch_properties and test_large_batches_match_oracle below.
+
+The programs drive the optimizers the oracle restates: GroupAdam V4, Adagrad and SparseGroupFtrl.  FTRL-V2, group FTRL-V2,
+group RectifiedAdam and plain Adam run their random programs in tests/test_gpu_fuzz_optimizers.py, against the host model
+of tests/_kv_model.py."""
 RTOL, ATOL = 1e-6, 1e-7      # ATOL: FTRL rebuilds the row from a linear slot that is a difference of O(1) terms
 import numpy as np
 import pytest
