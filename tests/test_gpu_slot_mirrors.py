@@ -30,13 +30,18 @@ def ops():
 def _mk(ops, name, D, seed, cap=200_000):
   rng = np.random.default_rng(seed)
   hv, ov = _pair(ops, D, seed=seed, rng=rng, cap=cap)
+  hs, os_ = _mk_slot(ops, name, D, cap)
+  return (hv, hs), (ov, os_)
+
+
+def _mk_slot(ops, name, D, cap=200_000):
   val = 0.0 if name.startswith("adam") else 0.1
   mult = 3 if name.startswith("adam") else 1
   table = np.full((16, mult * D), val, np.float32)
   hs = ops.kv_variable([mult * D], capacity_hint=cap)
   ops.kv_set_clock_days(hs, DAY); ops.kv_set_seed(hs, 0); ops.init_kv_variable_v2(hs, table)
   os_ = ko.OracleKv(mult * D, 0, table, day=DAY, picker=1, seed=0)
-  return (hv, hs), (ov, os_)
+  return hs, os_
 
 
 def _step(ops, name, hs, os_, rng, t, ids, unique=False):
@@ -343,3 +348,126 @@ def test_slot_queries_from_another_thread_while_the_var_grows(ops):
     os_[0].gather_or_insert(batches[t])
     ko.apply_group_adam(os_[0], os_[1], grads[t], batches[t], 0.05, b1p, b2p, 0.9, 0.999, 1e-8)
   _check(ops, hs, os_, np.unique(np.concatenate(batches)))
+
+
+def test_epoch_ended_from_both_sides_at_once(ops):
+  """three host threads, a stream each: the stepper (lookup + apply), one asker that ends the epoch from the VAR's side under
+  the var's lock (a size query), one that ends it from the SLOT's side under the slot table's lock (a point query on its
+  records).  The pair's record has a lock of its own: one end decides, flushes with the number the dirty copies carry and
+  bumps, the other one waits for that flush before it reads; no step's frequency words or flags are lost"""
+  import threading
+  name, D = "adam4", 16
+  rng = np.random.default_rng(37)
+  hs, os_ = _mk(ops, name, D, seed=37, cap=60_000)
+  ids = np.arange(20_000, dtype=np.int64) - 1000
+  STEPS = 25
+  grads = [rng.normal(0, 1e-2, (ids.size, D)).astype(np.float32) for _ in range(STEPS)]
+  errs, stop, calls = [], threading.Event(), {"var": 0, "slot": 0}
+
+  def stepper():
+    try:
+      with torch.cuda.stream(torch.cuda.Stream()):
+        dids = torch.from_numpy(ids).cuda()
+        for t in range(STEPS):
+          b1p, b2p = _beta_pows(t)
+          ops.kv_variable_gather_or_insert_v2(hs[0], dids)
+          ops.kv_variable_group_sparse_apply_adam_v4(hs[0], hs[1], torch.from_numpy(grads[t]).cuda(), dids, 0.05, b1p, b2p, 0.9, 0.999,
+                                                     1e-8, 0.0, 0.0, 0.0, unique_indices=(t % 2 == 0))
+        torch.cuda.current_stream().synchronize()
+    except Exception as e:  # pragma: no cover
+      errs.append(repr(e))
+    finally:
+      stop.set()
+
+  def asker(side):
+    try:
+      with torch.cuda.stream(torch.cuda.Stream()):
+        q = torch.from_numpy(ids[::97].copy()).cuda()
+        while True:
+          if side == "var":
+            ops.kv_variable_size_v2(hs[0])          # ends the running epoch under the var's lock
+          else:
+            ops.kv_get_meta(hs[1], q)               # ... under the slot table's lock
+          calls[side] += 1
+          if stop.is_set():
+            break
+    except Exception as e:  # pragma: no cover
+      errs.append(repr(e))
+
+  th = [threading.Thread(target=stepper), threading.Thread(target=asker, args=("var",)), threading.Thread(target=asker, args=("slot",))]
+  for t in th:
+    t.start()
+  for t in th:
+    t.join()
+  torch.cuda.synchronize()
+  assert not errs, errs
+  assert calls["var"] >= 1 and calls["slot"] >= 1, calls
+  for t in range(STEPS):
+    b1p, b2p = _beta_pows(t)
+    os_[0].gather_or_insert(ids)
+    ko.apply_group_adam(os_[0], os_[1], grads[t], ids, 0.05, b1p, b2p, 0.9, 0.999, 1e-8)
+  _check(ops, hs, os_, ids)
+  assert ops.kv_get_stat(hs[0], ops.KV_STAT_MIRROR_EPOCHS) > 2
+
+
+def _two_lean_applies(ops, hs, os_, rng, ids):
+  """the first apply of the keys leaves clean copies, the second one works on them: dirty copies nobody has asked for yet.
+  Returns the launcher — the ids and gradients are on the device before it is called, so it only queues — and the oracle's turn"""
+  D = hs[0].dim
+  grads = [rng.normal(0, 1e-2, (ids.size, D)).astype(np.float32) for _ in range(2)]
+  dids, dgrads = torch.from_numpy(ids).cuda(), [torch.from_numpy(g).cuda() for g in grads]
+  torch.cuda.current_stream().synchronize()
+
+  def launch():
+    for t in range(2):
+      b1p, b2p = _beta_pows(t)
+      ops.kv_variable_group_sparse_apply_adam_v4(hs[0], hs[1], dgrads[t], dids, 0.05, b1p, b2p, 0.9, 0.999, 1e-8, 0.0, 0.0, 0.0,
+                                                 unique_indices=True)
+
+  def oracle():
+    for t in range(2):
+      b1p, b2p = _beta_pows(t)
+      ko.apply_group_adam(os_[0], os_[1], grads[t], ids, 0.05, b1p, b2p, 0.9, 0.999, 1e-8)
+  return launch, oracle
+
+
+def test_var_destroyed_behind_a_queued_lean_apply(ops):
+  """the var is destroyed while its last lean apply is still queued on a non-default stream, behind a few milliseconds of other
+  work: the dirty copies go back on THAT stream, behind the apply that writes them — the slot table ends up the oracle's"""
+  name, D = "adam4", 16
+  rng = np.random.default_rng(41)
+  hs, os_ = _mk(ops, name, D, seed=41, cap=60_000)
+  ids = np.arange(20_000, dtype=np.int64) - 1000
+  with torch.cuda.stream(torch.cuda.Stream()):
+    launch, oracle = _two_lean_applies(ops, hs, os_, rng, ids)
+    a = torch.randn(4096, 4096, device="cuda")
+    for _ in range(6):
+      a = (a @ a) * 1e-3
+    launch()
+    assert ops.kv_get_stat(hs[0], ops.KV_STAT_MIRROR_APPLIES) == 2
+    ops.destroy_kv_variable_op_v2(hs[0])
+  torch.cuda.synchronize()
+  oracle()
+  np.testing.assert_array_equal(_np(ops.kv_variable_get_count_v2(hs[1], ids)), os_[1].get_count(ids))
+  _check(ops, hs[1:], os_[1:], ids)     # rows, frequency words, flags (kv_get_meta), sizes
+
+
+def test_slot_destroyed_first(ops):
+  """the slot table goes first, dirty copies outstanding: the var finds the pair dissolved at its next op and goes on alone;
+  with a new slot table it pairs again, in an epoch none of the old copies carries"""
+  name, D = "adam4", 16
+  rng = np.random.default_rng(43)
+  hs, os_ = _mk(ops, name, D, seed=43, cap=60_000)
+  ids = np.arange(20_000, dtype=np.int64) - 1000
+  launch, oracle = _two_lean_applies(ops, hs, os_, rng, ids)
+  launch(); oracle()
+  ops.destroy_kv_variable_op_v2(hs[1])
+  assert ops.kv_variable_size_v2(hs[0]) == os_[0].size()
+  np.testing.assert_allclose(_np(ops.kv_variable_gather_or_zeros_v2(hs[0], ids)), os_[0].gather_or_zeros(ids), rtol=RTOL, atol=1e-7)
+  assert ops.kv_get_stat(hs[0], ops.KV_STAT_MIRROR_APPLIES) == 2
+  _check(ops, hs[:1], os_[:1], ids)
+  hs2, os2 = _mk_slot(ops, name, D, cap=60_000)              # (the oracle's new slot table starts fresh, too)
+  hs, os_ = (hs[0], hs2), (os_[0], os2)
+  _step(ops, name, hs, os_, rng, 2, ids, unique=True)
+  _check(ops, hs, os_, ids)
+  ops.destroy_kv_variable_op_v2(hs[0])

@@ -4,9 +4,9 @@
 // is the ABI's opaque handle and therefore global.  The functions are defined, and explained, in kvhip.hip unless a section
 // names another unit.
 //
-// The boundary: no unit other than kvhip.hip names a mirror_*, mview_*, pend_wd or pend_pa member of kv_table — the slot
-// mirrors and the pending partition pass are reached through mirror_decide, set_pending_part, take_pending_part, flush_part and
-// launch_link_hints — and only kvhip.hip compiles the pipelines' kernels (kv_kernels.h, kv_fused.h, kv_papply.h), which the
+// The boundary: no unit other than kvhip.hip names a pair_*, mirror_*, pend_wd or pend_pa member of kv_table, or a MirrorPair
+// — the slot mirrors and the pending partition pass are reached through mirror_decide, set_pending_part, take_pending_part,
+// flush_part and launch_link_hints — and only kvhip.hip compiles the pipelines' kernels (kv_kernels.h, kv_fused.h, kv_papply.h), which the
 // other units reach through the launch_* functions.  The descriptors of a batched launch go to the device through
 // Staged<Desc> alone (the staging ring: acquire, fill, upload, busy until the stream has read them).
 //
@@ -22,6 +22,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -30,6 +31,7 @@
 #include "../../include/kvhip.h"
 #include "kv_batch_index.h"
 #include "kv_launch.h"
+#include "kv_mirror_epoch.h"
 
 namespace __attribute__((visibility("hidden"))) kvhip_internal {
 
@@ -75,6 +77,22 @@ struct Workspace {
   float* seg_den = nullptr;      // kv_lookup_sparse_grad: the segments' denominators [den_cap]
   long long den_cap = 0;
   unsigned long long* dbg = nullptr;
+};
+
+// The slot mirrors of one (var, slot) pair (kv_device.h SlotMirror; kvhip.hip "slot mirrors: the host side"): ONE record that
+// the two tables share, each through a reference of its own (kv_table::pair_var / pair_slot), either of which may go first.
+// Everything in it is read and written under `mu` alone — the innermost lock: taken with one or both table locks held, never
+// the other way round.
+struct MirrorPair {
+  std::mutex mu;
+  MirrorEpoch epoch;
+  // the pair's device views as the last lean apply (or the pairing) saw them.  What a dirty copy names — a var row and a
+  // slot row of the chunk-0 slabs — is inside these views whatever happened to the tables since: an epoch end launches
+  // through them and never reads the other table's host state (whose owner may be growing it on another thread)
+  TableDev view_var{}, view_slot{};
+  bool dissolved = false;        // a table has left: no epoch, no copies any more; the other one drops its reference when it next looks
+  hipEvent_t flushed = nullptr;  // recorded behind the last write-back, on the stream that ran it
+  ~MirrorPair() { if (flushed) hipEventDestroy(flushed); }
 };
 
 }  // namespace kvhip_internal
@@ -124,21 +142,14 @@ struct kv_table {
   // of that batch runs it in front of its own kernels, any other op on the table runs it first thing (settle).  Same stream
   // order as before, the rows just do not wait for it.  The pass's arguments, as byte images (their types are the device's):
   unsigned char pend_wd[sizeof(WsDev)], pend_pa[sizeof(PartArgs)];
-  // Slot mirrors (kv_device.h SlotMirror; mirror_* below): a var table paired with ONE slot table keeps, next to each row's
-  // record, a write-back copy of the slot row's frequency word and flags; the lean apply works on the copy alone.
-  long long stat_mirror_applies = 0;            // kv_get_stat
-  std::atomic<long long> stat_mirror_epochs{0}; // ... (an epoch of a var's mirrors may be ended under the slot table's lock)
-  // both tables of a mirror pair hold the pair's device views as the last lean apply (or the pairing) saw them — written with
-  // BOTH locks held.  An op that ends the epoch holds ONE of the two locks: it flushes through the copy in the table it
-  // holds and never reads the other table's host state (whose owner may be growing it on another thread).  What a dirty
-  // copy names — a var row and a slot row of the chunk-0 slabs — is inside these views whatever happened to the tables since.
-  TableDev mview_var{}, mview_slot{};
-  kv_table* mirror_slot = nullptr;          // var side: the slot table its mirrors stand for
-  std::atomic<unsigned> mirror_epoch{1};    // var side: generation of the copies (16 bits on the device)
-  std::atomic<bool> mirror_dirty{false};    // var side: a lean apply has written mirrors since the last flush
-  kv_table* mirror_var = nullptr;           // slot side: the var that holds this table's mirrors
-  bool mirror_banned = false;               // either side: the table is used under stream capture (kv_prepare_capture): no mirrors, ever
-  bool mirror_shared = false;               // slot side: a second var attached it — no mirrors for this table any more
+  // Slot mirrors: the table's references to the pair records it is half of — as a var (its rows hold the copies) and as a slot
+  // table (another table's rows hold copies of its records); a table can be both.  Read and written under the table's own
+  // `mu`, never by the partner.  The rest are the table's own facts, under `mu` like everything else.
+  std::shared_ptr<MirrorPair> pair_var, pair_slot;
+  unsigned mirror_next = 1u;       // var side: the first epoch of its next pair — where the last pair it left stopped
+  long long stat_mirror_applies = 0, stat_mirror_epochs = 0;   // kv_get_stat (epochs: ended in the pairs it has left as their var)
+  bool mirror_banned = false;      // either side: the table is used under stream capture (kv_prepare_capture): no mirrors, ever
+  bool mirror_shared = false;      // slot side: a second var attached it — no mirrors for this table any more
   unsigned uniq_serial = 0;        // stamp of the table's last kv_apply_*_unique launch (kv_uapply.h; wraps at 65535: stamps cleared)
   bool deterministic = false;      // kv_set_deterministic
   bool occurrence_order = false;   // kv_set_deterministic(h, 2): a repeated id's gradient rows are added one by one in input order

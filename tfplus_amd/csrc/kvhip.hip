@@ -630,73 +630,86 @@ int flush_part(kv_table* t, hipStream_t s) {
 // ---- slot mirrors: the host side -------------------------------------------------------------------------------------
 // Invariant: the slot table's own records are up to date for every key whose var-row mirror is not (valid in the current
 // epoch AND dirty).  Mirrors are written only by the lean apply of (var, slot) — k_papply / k_uapply with use_mirror — and
-// read only by it.  EVERY other op that enters either table first ends the epoch (mirror_end_epoch: flush the dirty
-// copies, one kernel over the var's rows, then epoch + 1 — which invalidates every copy at once), so it sees, and may
-// change, the authoritative records; the keys' next lean apply finds no valid mirror, takes the general path once and
-// leaves a fresh clean copy (finish_key).  An op that keeps the epoch says so where it enters the table (enter_op,
-// hand_over, MultiLock::enter), with the role(s) it keeps the table in; KEEP_NONE, the default, ends it.  The
-// keepers: the training / inference lookups on the var (they touch var records and rows only), the GroupAdam and Adagrad
-// applies on (var, slot), single and batched, and the ops that only borrow a table's workspace.  A role, not a table, is
-// kept: a var entered as KEEP_VAR that is also another var's slot table still ends that other pair's epoch.
-// held: the table of the pair whose lock the caller holds (the var itself, or its slot table): the views come from there
-void mirror_end_epoch(kv_table* var, hipStream_t s, const kv_table* held) {
-  if (!var->mirror_slot) return;
-  var->stat_mirror_epochs.fetch_add(1);
-  const TableDev& tv = held->mview_var;
-  const long long rows = (long long)tv.max_rows + 1;
-  if (var->mirror_dirty.exchange(false))
-    k_flush_mirrors<<<nblocks(rows, TB, 8192), TB, 0, s>>>(tv, held->mview_slot, var->mirror_epoch.load() & 0xFFFFu);
-  if ((var->mirror_epoch.fetch_add(1) + 1u) > 0xFFFFu) {
-    k_clear_mirrors<<<nblocks(rows, TB, 8192), TB, 0, s>>>(tv);
-    var->mirror_epoch.store(1);
+// read only by it.  EVERY other op that enters either table first ends the epoch (flush the dirty copies, one kernel over
+// the var's rows, then epoch + 1 — which invalidates every copy at once), so it sees, and may change, the authoritative
+// records; the keys' next lean apply finds no valid mirror, takes the general path once and leaves a fresh clean copy
+// (finish_key).  An op that keeps the epoch says so where it enters the table, with the role(s) it keeps the table in
+// (KEEP_*, kv_host.h).  A role, not a table, is kept: a var entered as KEEP_VAR that is also another var's slot table still
+// ends that other pair's epoch.
+// The locks: a pair is ONE record (MirrorPair, kv_host.h).  A table's reference to it (pair_var, pair_slot) is read and
+// written under that table's own mu, never by the partner.  What is in the record is read and written under the record's
+// mu, the innermost lock: mirror_visit and the lean apply (mirror_decide) take it once and are the transitions.
+
+// ends p's epoch (p.mu held) on s: the write-back with the number the dirty copies carry, the clearing on wrap.  The event
+// stands behind the last write-back; a call that launched none (the pair's other side may just have, on its own stream)
+// waits for it before its op reads a slot record.  write_back == false: the slot table is going, its records with it
+static void pair_end_epoch(MirrorPair& p, hipStream_t s, bool write_back) {
+  const MirrorEpoch::End e = p.epoch.end();
+  const long long rows = (long long)p.view_var.max_rows + 1;
+  const bool flush = e.flush && write_back;
+  if (flush) k_flush_mirrors<<<nblocks(rows, TB, 8192), TB, 0, s>>>(p.view_var, p.view_slot, e.flush_epoch16);
+  if (e.clear_all) k_clear_mirrors<<<nblocks(rows, TB, 8192), TB, 0, s>>>(p.view_var);
+  if (flush || e.clear_all) hipEventRecord(p.flushed, s);
+  else hipStreamWaitEvent(s, p.flushed, 0);
+}
+// What table t (t->mu held) does to the pair behind `ref`, one of its own two references, on stream s.  A table that leaves
+// dissolves the pair (the dirty copies go back); its partner, whose lock the leaver need not hold, finds the record
+// dissolved whatever it came for, and leaves too, behind the leaver's write-back.  A var that leaves keeps the record's next
+// epoch: its rows still hold the copies, and only a number none of them carries makes them void in its next pair.
+// Under a stream capture the flush would be RECORDED, not run, and a replay would carry the epoch of its capture: a table
+// that is captured gives up its mirrors beforehand (kv_prepare_capture); an op that would end an epoch in a capture is refused.
+enum MirrorVisit { LOOK, END_EPOCH, LEAVE, LEAVE_NO_FLUSH };
+static int mirror_visit(kv_table* t, std::shared_ptr<MirrorPair>& ref, hipStream_t s, MirrorVisit what) {
+  if (!ref) return KV_OK;
+  {
+    std::lock_guard<std::mutex> l(ref->mu);
+    if (!ref->dissolved) {
+      if (what == LOOK) return KV_OK;
+      if (what == END_EPOCH && stream_is_capturing(s))
+        return fail(KV_FAILED_PRECONDITION, "this table is half of a (var, slot) pair whose optimizer applies keep the slot records' "
+                                            "frequency words in the var's rows between ops; call kv_prepare_capture on it (outside the "
+                                            "capture) before capturing ops on it");
+      pair_end_epoch(*ref, s, what != LEAVE_NO_FLUSH);
+      if (what == END_EPOCH) return KV_OK;
+      ref->dissolved = true;
+    } else if (!stream_is_capturing(s)) hipStreamWaitEvent(s, ref->flushed, 0);
+    if (&ref == &t->pair_var) { t->mirror_next = ref->epoch.epoch16(); t->stat_mirror_epochs = ref->epoch.ended(); }
   }
-}
-void mirror_unpair(kv_table* var, hipStream_t s, const kv_table* held) {
-  if (!var->mirror_slot) return;
-  mirror_end_epoch(var, s, held);
-  var->mirror_slot->mirror_var = nullptr;
-  var->mirror_slot = nullptr;
-}
-// (both locks held)
-static void mirror_snapshot(kv_table* v, kv_table* sl) {
-  v->mview_var = sl->mview_var = dev_view(v);
-  v->mview_slot = sl->mview_slot = dev_view(sl);
-}
-// the entry hook of hand_over / join_side.  Under a stream capture the flush would be RECORDED, not run, and a replay would
-// carry the epoch of its capture: a table that is captured gives up its mirrors beforehand (kv_prepare_capture ->
-// mirror_ban); an op that would have to end an epoch inside a capture is refused.
-int mirror_on_entry(kv_table* t, hipStream_t s, unsigned keep) {
-  if (!t->mirror_var && !t->mirror_slot) return KV_OK;
-  const bool end_slot = t->mirror_var && !(keep & KEEP_SLOT), end_var = t->mirror_slot && !(keep & KEEP_VAR);
-  if ((end_slot || end_var) && stream_is_capturing(s))
-    return fail(KV_FAILED_PRECONDITION, "this table is half of a (var, slot) pair whose optimizer applies keep the slot records' "
-                                        "frequency words in the var's rows between ops; call kv_prepare_capture on it (outside the "
-                                        "capture) before capturing ops on it");
-  if (end_slot) mirror_end_epoch(t->mirror_var, s, t);   // t is a slot table: its records are about to be read or written
-  if (end_var) mirror_end_epoch(t, s, t);                // t is a var: its rows may be released, moved or read back
+  ref.reset();
   return KV_OK;
 }
-// kv_prepare_capture: the table's ops are about to be captured and replayed — no host code runs at a replay, so nothing
-// could flush or re-validate a mirror: the pair is dissolved now (the dirty copies go back) and never forms again
+// ... LOOK: is there a live pair behind ref?
+static bool mirror_live(kv_table* t, std::shared_ptr<MirrorPair>& ref, hipStream_t s) { mirror_visit(t, ref, s, LOOK); return ref != nullptr; }
+// the entry hook of hand_over / join_side: a role the op does not keep the table in ends its pair's epoch
+int mirror_on_entry(kv_table* t, hipStream_t s, unsigned keep) {
+  int rc = KV_OK;
+  if (!(keep & KEEP_SLOT)) rc = mirror_visit(t, t->pair_slot, s, END_EPOCH);         // its records are about to be read or written
+  if (!rc && !(keep & KEEP_VAR)) rc = mirror_visit(t, t->pair_var, s, END_EPOCH);    // its rows may be released, moved or read back
+  return rc;
+}
+// kv_prepare_capture: no host code runs at a replay, so nothing could flush or re-validate a mirror: no pair, now or ever
 void mirror_ban(kv_table* t, hipStream_t s) {
-  if (t->mirror_slot) mirror_unpair(t, s, t);
-  if (t->mirror_var) mirror_unpair(t->mirror_var, s, t);
+  mirror_visit(t, t->pair_var, s, LEAVE);
+  mirror_visit(t, t->pair_slot, s, LEAVE);
   t->mirror_banned = true;
 }
-// (var, slot) become a mirror pair — or stay / become unpaired when the slot table already serves another var
+// (var, slot) become a mirror pair — or stay / become unpaired when the slot table already serves another var (both locks held)
 bool mirror_pair(kv_table* v, kv_table* sl, hipStream_t s) {
   if (sl->mirror_shared || v->mirror_banned || sl->mirror_banned) return false;
-  if (v->mirror_slot == sl && sl->mirror_var == v) return true;
-  if (sl->mirror_var && sl->mirror_var != v) {   // a second var on one slot table: no mirrors for it at all
-    mirror_unpair(sl->mirror_var, s, sl);
+  // (one record in both tables' hands is live: whoever dissolves it holds one of the two locks and drops its reference at once)
+  if (v->pair_var && v->pair_var == sl->pair_slot) return true;
+  if (mirror_live(sl, sl->pair_slot, s)) {   // a second var on one slot table: no mirrors for it at all
+    mirror_visit(sl, sl->pair_slot, s, LEAVE);
     sl->mirror_shared = true;
     return false;
   }
-  if (v->mirror_slot && v->mirror_slot != sl) mirror_unpair(v, s, v);
-  v->mirror_slot = sl;
-  sl->mirror_var = v;
-  mirror_snapshot(v, sl);
-  mirror_end_epoch(v, s, v);   // a fresh epoch: whatever bytes the rows' mirror units hold are void
+  mirror_visit(v, v->pair_var, s, LEAVE);   // a change of slot table
+  auto p = std::make_shared<MirrorPair>();
+  if (hipEventCreateWithFlags(&p->flushed, hipEventDisableTiming) != hipSuccess) return false;
+  p->epoch = MirrorEpoch(v->mirror_next, v->stat_mirror_epochs);
+  p->view_var = dev_view(v); p->view_slot = dev_view(sl);
+  v->pair_var = sl->pair_slot = p;
+  mirror_visit(v, v->pair_var, s, END_EPOCH);   // a fresh epoch: whatever bytes the rows' mirror units hold are void
   return true;
 }
 
@@ -706,23 +719,24 @@ bool mirror_pair(kv_table* v, kv_table* sl, hipStream_t s) {
 // (lean is false for an optimizer with two slot tables: the caller passes lean && !two_slots(OPT))
 int mirror_decide(kv_table* v, kv_table* s0, PartArgs& pa, bool lean, hipStream_t s) {
   pa.use_mirror = 0; pa.mirror_epoch = 0u;
-  // (a captured apply of a pair that still has mirrors: their flush would be recorded, not run — see mirror_on_entry)
-  if ((v->mirror_slot || s0->mirror_var) && stream_is_capturing(s))
+  // (a captured apply of a pair that still has mirrors: their flush would be recorded, not run — see mirror_visit)
+  if ((v->pair_var || s0->pair_slot) && stream_is_capturing(s) && (mirror_live(v, v->pair_var, s) || mirror_live(s0, s0->pair_slot, s)))
     return fail(KV_FAILED_PRECONDITION, "optimizer apply under stream capture on a (var, slot) pair with live slot mirrors: call "
                                         "kv_prepare_capture on both tables (outside the capture) first");
   const bool eligible = lean && pa.use_hints != 0 && pa.tv.single != 0u && pa.ts0.single != 0u &&
                         !v->track_delta && !s0->track_delta && !stream_is_capturing(s) && mirror_pair(v, s0, s);
   if (eligible) {
+    MirrorPair& p = *v->pair_var;
+    std::lock_guard<std::mutex> l(p.mu);
+    p.view_var = dev_view(v); p.view_slot = dev_view(s0);   // what this apply's dirty copies name is inside these views
     pa.use_mirror = 1;
-    pa.mirror_epoch = v->mirror_epoch.load() & 0xFFFFu;
-    mirror_snapshot(v, s0);   // what this apply's dirty copies name is inside these views
-    v->mirror_dirty.store(true);
+    pa.mirror_epoch = p.epoch.lean_apply();
     ++v->stat_mirror_applies;
-  } else {
-    if (v->mirror_slot) mirror_end_epoch(v, s, v);
-    if (s0->mirror_var && s0->mirror_var != v) mirror_end_epoch(s0->mirror_var, s, s0);
+    return KV_OK;
   }
-  return KV_OK;
+  int rc = mirror_visit(v, v->pair_var, s, END_EPOCH);
+  if (!rc && s0->pair_slot != v->pair_var) rc = mirror_visit(s0, s0->pair_slot, s, END_EPOCH);
+  return rc;
 }
 
 // Ops of one table run in the order they were issued, whatever their streams: the per-table workspace
@@ -763,7 +777,7 @@ int join_side(kv_table* t, hipStream_t s) {
   // An epoch of slot mirrors that ends here flushes copies the last lean apply wrote — on the stream of t's last op (an apply
   // enters both tables; anything later on t has ended the epoch already): the flush must run behind it.  (A flush that
   // overtook the apply would miss its copies, and the epoch number that ends with it would orphan them for good.)
-  if ((t->mirror_var || t->mirror_slot) && (rc = hop_behind_last(t, s))) return rc;
+  if ((t->pair_var || t->pair_slot) && (rc = hop_behind_last(t, s))) return rc;
   return mirror_on_entry(t, s, KEEP_NONE);
 }
 
@@ -950,8 +964,10 @@ void launch_clear_stamps(kv_table* v, hipStream_t s) {
 // filled with the hints
 void launch_link_hints(kv_table* v, kv_table* sl, unsigned nrows, hipStream_t s) {
   const bool mir = v->chunks.size() == 1 && sl->chunks.size() == 1 && !v->track_delta && !sl->track_delta && mirror_pair(v, sl, s);
-  if (nrows > 1)
-    k_link_hints<<<nblocks(nrows, TB, 8192), TB, 0, s>>>(dev_view(v), dev_view(sl), nrows, v->mirror_epoch.load() & 0xFFFFu, mir ? 1 : 0);
+  if (nrows <= 1) return;
+  unsigned epoch = 0u;   // (the copies' stamp: not looked at without mirrors)
+  if (mir) { std::lock_guard<std::mutex> l(v->pair_var->mu); epoch = v->pair_var->epoch.epoch16(); }
+  k_link_hints<<<nblocks(nrows, TB, 8192), TB, 0, s>>>(dev_view(v), dev_view(sl), nrows, epoch, mir ? 1 : 0);
 }
 
 // the templated launchers, for the arguments the units on top use (kv_host.h)
@@ -1026,12 +1042,14 @@ int kv_create(int key_dtype, int value_dtype, int dim, int enter_threshold, int6
 int kv_destroy(kv_handle_t t) {
   if (!t) return KV_OK;
   { std::lock_guard<std::mutex> l(g_tables_mu); g_tables.erase(t); }
-  {   // slot mirrors: a var hands its dirty copies back before it goes; a slot table takes its var's pairing with it
-    DeviceGuard dgm(t->device);
-    if (t->mirror_slot) mirror_unpair(t, nullptr, t);
-    if (t->mirror_var) { t->mirror_var->mirror_dirty.store(false); t->mirror_var->mirror_slot = nullptr; t->mirror_var = nullptr; }
-  }
   DeviceGuard dg(t->device);
+  {   // slot mirrors: a var hands its dirty copies back before it goes — on the stream of its last op, where the lean apply
+      // that wrote them was queued; a slot table's records go with it: nothing to write back
+    std::lock_guard<std::mutex> l(t->mu);
+    hipStream_t s = t->has_last ? t->last_stream : nullptr;
+    mirror_visit(t, t->pair_var, s, LEAVE);
+    mirror_visit(t, t->pair_slot, s, LEAVE_NO_FLUSH);
+  }
   hipDeviceSynchronize();
   for (auto& c : t->chunks) { hipFree(c.rows); hipFree(c.meta); }
   hipFree(t->entries); hipFree(t->d_chunks); hipFree(t->d_counters); hipFree(t->d_stat); hipFree(t->free_rows);
@@ -1138,7 +1156,11 @@ int kv_get_stat(kv_handle_t t, int which, int64_t* value) {
   if (!value) return fail(KV_INVALID_ARGUMENT, "kv_get_stat: null value");
   std::lock_guard<std::mutex> l(t->mu);
   if (which == KV_STAT_MIRROR_APPLIES) { *value = t->stat_mirror_applies; return KV_OK; }
-  if (which == KV_STAT_MIRROR_EPOCHS) { *value = t->stat_mirror_epochs.load(); return KV_OK; }
+  if (which == KV_STAT_MIRROR_EPOCHS) {   // (of the pairs the table has been the var of)
+    *value = t->stat_mirror_epochs;
+    if (t->pair_var) { std::lock_guard<std::mutex> lp(t->pair_var->mu); *value = t->pair_var->epoch.ended(); }
+    return KV_OK;
+  }
   return fail(KV_INVALID_ARGUMENT, "kv_get_stat: unknown counter %d", which);
 }
 

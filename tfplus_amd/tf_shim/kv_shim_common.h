@@ -106,6 +106,7 @@ class KvHipResource : public ResourceBase {
   ~KvHipResource() override {
     if (stream_) hipStreamSynchronize(stream_);
     kv_destroy(h_);
+    if (stream_) kv_forget_stream(stream_);   // an optimizer op on this stream left it as the slot tables' last one
     if (stream_) hipStreamDestroy(stream_);
   }
   string DebugString() const override { return "KvHipResource"; }
