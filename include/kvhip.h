@@ -50,6 +50,35 @@ typedef void* kv_stream_t;            /* hipStream_t */
 
 const char* kv_last_error(void);
 
+/* The refused batch (deferred, KV_INTERNAL).  Every batch op that indexes its ids — the lookups, the optimizer applies,
+ * kv_unique, kv_dedup_segment_sum, inserts and scatters — spreads them over hash partitions by the top bits of one 64-bit
+ * hash of the key, and one block works through a partition's distinct keys in classes of further hash bits.  Two key sets
+ * are refused instead of processed; neither occurs with ids that were not computed from the hash:
+ *   - one partition receives more than 65535 (tile, key) entries of one batch;
+ *   - one partition holds more distinct keys than its block's key table (768 to 1023, by the kernel) whose hashes agree in
+ *     so many of the bits 20 .. 43 that 23 successive halvings of the class leave them together (the classes' work list is
+ *     24 deep).  Keys that agree in fewer of those bits, or whose halvings leave no sibling class waiting, are handled.
+ * When: the kernel that meets such a partition raises the table's error word and every later kernel of that op does
+ * nothing; the call that queued it returns KV_OK (nothing waits for the device) unless it synchronises itself.  The error is
+ * returned by the NEXT call on that table at the latest — for a training lookup whose partition pass is deferred to the op
+ * behind it (kv_gather_or_insert_tok), by the call behind that op, or by that op itself if it waits for the device
+ * (kv_size, kv_map_size, kv_sum_freq, the exports) — once, as KV_INTERNAL with a message that names both causes; the
+ * call after it proceeds normally.  The single-table reads kv_gather_or_zeros, kv_lookup_sparse_zeros, kv_get_count,
+ * kv_get_timestamp and kv_get_meta never report a deferred error (they queue one kernel and read no error word): they do
+ * not count as that next call, and what they read of the refused batch's new keys before the report is unspecified.
+ * What the refused batch did.  A partition with more than 65535 entries is refused before its block touches anything.
+ * A partition refused for its inseparable keys is refused LATE: its block works through the classes one by one, so every
+ * class it finished before it met the inseparable one, and every sibling class still on its work list afterwards (the
+ * block goes on with them), is processed by that kernel — those keys may be inserted, counted (lookups) or updated (applies).
+ * What is guaranteed: for the keys of the class that could not be separated, and for every key of a partition refused
+ * for its entry count, NOTHING happens — no row, slot row, frequency, day stamp or delta mark of a key the table held
+ * changes, and the keys the batch would have inserted are not in the table afterwards: the report removes the index
+ * entries and rows the first pass had claimed for them (they read as absent; kv_size, kv_map_size, kv_sum_freq and the
+ * exports do not see them; a later batch inserts them as new).  A lookup's output rows and kv_unique's outputs for a
+ * refused batch are unspecified.  Other partitions of the SAME batch may have been processed before the flag went up,
+ * like the other classes of the refused one: a refused batch is not atomic, neither across partitions nor inside the
+ * partition that was refused for inseparable keys.  Feed such ids in smaller batches. */
+
 /* ---- lifecycle ------------------------------------------------------------------------- */
 
 /* Replaces CreateKvVariableOp::Compute (kernels/kv_variable_ops.cc:58-116) + KvVariable ctor

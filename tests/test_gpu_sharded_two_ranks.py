@@ -594,6 +594,7 @@ def test_whole_ops_with_ranks_as_threads_match_one_unsharded_table(world, D, los
   sys.path.insert(0, ROOT)
   from oracle import kv_oracle as ko
   from tfplus_amd.kv_variable.python.ops import sharded
+  import _hash_keys as hk
   rng = np.random.default_rng(31 + world)
   table = rng.standard_normal((64, D)).astype(np.float32)
   ops, vars_, slots, shards = _native_setup(world, D, "hash", table, cap=cap, max_ids=1 << 14)
@@ -632,10 +633,18 @@ def test_whole_ops_with_ranks_as_threads_match_one_unsharded_table(world, D, los
   comms = [make_comm(r) for r in range(world)]
   b1p, b2p = np.float32(0.9), np.float32(0.999)
   hp = (0.1, b1p, b2p, 0.9, 0.999, 1e-8, 0, 0, 0)
-  for step in range(3):
+  for step in range(4):
     batches = [rng.integers(-300, 300, 2500 + 411 * r) for r in range(world)]
     if step == 2:
       batches[0] = batches[0][:0]                                           # a rank with an empty batch
+    if step == 3:
+      # keys crafted against the owner hash (tests/_hash_keys.py): rank 0's whole batch — 1500 keys, the edge keys INT64_MIN
+      # (the index's sentinel: the route_seg .. EMPTY_KEY records of kv_papply.h), INT64_MAX, 0 and -1, with repeats —
+      # belongs to ONE owner, the last rank (the edge keys to whoever owns them); rank 1 sends the sentinel key as well
+      crafted = hk.case("D_w%d" % world)
+      batches[0] = rng.permutation(np.concatenate([crafted, crafted[rng.integers(0, crafted.size, 700)],
+                                                   np.repeat(np.array(hk.EDGE_KEYS, np.int64), 3)]))
+      batches[1] = rng.permutation(np.concatenate([batches[1], np.full(3, hk.INT64_MIN, np.int64)]))
     sign = rng.choice([-1.0, 1.0], (1, D))
     grads = [(rng.uniform(0.5, 1.5, (b.size, D)) * 1e-2 * sign).astype(np.float32) for b in batches]
     outs, errs = [None] * world, []
@@ -684,7 +693,7 @@ def test_whole_ops_with_ranks_as_threads_match_one_unsharded_table(world, D, los
   if lossless and cap:
     assert all(sh.peer_capacity > cap for sh in shards)                     # grown, on every rank alike
     assert len({sh.peer_capacity for sh in shards}) == 1
-  assert all(c.exchanges >= 9 for c in comms)
+  assert all(c.exchanges >= 12 for c in comms)
   del comms
 
 

@@ -17,7 +17,8 @@ namespace __attribute__((visibility("hidden"))) kvhip_internal {
 //   - A pending partition pass belongs to a held ENTRIES index: it is the bookkeeping of the lookup that published it.
 //     Nothing here launches, so the ops keep that: an op drops only a table it entered with settle (or after
 //     settle_pending), and a lookup that defers its pass publishes in the same op.  (The report of a deferred device error
-//     drops before it settles: the pass then stays pending for the table's next op, which no token reaches any more.)
+//     drops before it settles: the pass then stays pending for the table's next op, which no token reaches any more —
+//     except the report of a refused batch, code 2, which launches the pass before it sweeps: kvhip.hip rollback_refused.)
 class BatchIndex {
  public:
   enum Kind : unsigned char { ENTRIES, SORTED };

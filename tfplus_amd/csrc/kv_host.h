@@ -283,6 +283,7 @@ int regrow(T** p, size_t count) {
 bool stream_is_capturing(hipStream_t s);
 int ws_sync(hipStream_t s);
 int ensure_capacity(kv_table* t, long long extra, hipStream_t s);
+int ensure_free_list(kv_table* t, hipStream_t s);   // the free-list stack holds every row of the slab (before a kernel that releases rows)
 int ensure_workspace(kv_table* t, long long n, bool need_part, hipStream_t s);
 int ensure_pos_ent(kv_table* t, long long n, hipStream_t s);
 unsigned fused_default_P(long long n);

@@ -444,7 +444,7 @@ __device__ __forceinline__ void part_keys_body(const WsDev& w, const PartArgs& a
   __shared__ unsigned lbig[16][3];   // keys of the class with more than 16 chunks: {hot list index, first chunk, chunks}
   if (ORD && E == 0) { if (tid == 0) w.pmeta[p] = make_uint4(0u, 0u, pbase, 0u); }
   if (E == 0) return;
-  const bool wide = E > 65535u;  // needs a key set crafted against the partition hash; guarded, not handled
+  const bool wide = E > 65535u;  // needs a key set crafted against the partition hash; refused (include/kvhip.h "The refused batch")
 
   // work list of (R, round) sub-hash classes; an overflowing class is split in two and each
   // class is processed exactly once (block-uniform control flow)
@@ -513,7 +513,7 @@ __device__ __forceinline__ void part_keys_body(const WsDev& w, const PartArgs& a
           stkR[sp] = 2 * R; stkr[sp] = round; ++sp;
           stkR[sp] = 2 * R; stkr[sp] = round + R; ++sp;
         } else {
-          raise_error(a.tv, 2u);   // keys that no sub-hash separates: reported, not applied
+          raise_error(a.tv, 2u);   // keys that no sub-hash separates: reported, THIS class not applied (the classes still listed are)
         }
       }
       __syncthreads();

@@ -178,21 +178,6 @@ static int dedup_locked(kv_table* t, const void* ids, const float* grad, int64_t
   return KV_OK;
 }
 
-// the free-list stack must hold every row of the slab
-static int ensure_free_list(kv_table* t, hipStream_t s) {
-  if (t->free_cap >= t->rows_cap) return KV_OK;
-  unsigned* nf = nullptr;
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipMalloc(&nf, (size_t)t->rows_cap * sizeof(unsigned)));
-  if (t->free_rows) {
-    HIP_TRY(hipMemcpy(nf, t->free_rows, (size_t)t->free_cap * sizeof(unsigned), hipMemcpyDeviceToDevice));
-    hipFree(t->free_rows);
-  }
-  t->free_rows = nf;
-  t->free_cap = t->rows_cap;
-  return KV_OK;
-}
-
 // after a kernel that pushed rows: read the counters, account the pushes (synchronous)
 static int after_release(kv_table* t, hipStream_t s, unsigned long long* released) {
   unsigned c[3];

@@ -94,6 +94,27 @@ __global__ void k_rehash(TableDev t, TableDev told, unsigned nrows) {
     }
   }
 }
+// A batch the partition pass refused (device error 2) after the entry-list tile pass (kv_fused.h tile_insert) had inserted
+// its new keys: their index entries are {key, row, HINT_NEW} and their rows have no record yet (no key, no frequency word,
+// no contents — the partition pass writes all three).  Every reader that walks the rows (k_stats, k_export, k_rehash,
+// k_delete_by_time) would take such a row for a live key 0.  So the report of the error takes them out again: the entry
+// becomes a tombstone (probe chains through it stay intact; the same key revives it), the row goes back to the free list.
+// One thread per index entry, the sentinel key's entry[mask + 1] included; a row is named by one entry, so it is pushed once.
+__global__ void k_rollback_new(TableDev t, unsigned* free_rows, unsigned long long* cnt) {
+  const unsigned long long count = t.mask + 2ull;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < count;
+       i += (unsigned long long)gridDim.x * blockDim.x) {
+    Entry* s = &t.entries[i];
+    const Entry e = load_entry(s);
+    if (e.key == EMPTY_KEY || e.hint != HINT_NEW) continue;
+    s->hint = 0u;
+    s->row = ROW_TOMB;
+    if (e.row == 0u || e.row == ROW_TOMB || e.row >= t.max_rows) continue;   // (claimed, but the slab was full: no row)
+    *flags_ptr(t, e.row) = (unsigned char)FLAG_FREE;
+    free_rows[atomicAdd(&t.counters[2], 1u)] = e.row;
+    atomicAdd(&cnt[0], 1ull);
+  }
+}
 // kv_uapply.h: the 16-bit launch serial wrapped — every row's stamp back to "none"
 __global__ void k_clear_stamps(TableDev t, unsigned nrows) {
   for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += gridDim.x * blockDim.x) meta_ptr(t, r)->stamp = 0;
@@ -234,13 +255,57 @@ int build_index(kv_table* t, unsigned long long newcap, unsigned nrows, hipStrea
   return KV_OK;
 }
 
+// the free-list stack must hold every row of the slab
+int ensure_free_list(kv_table* t, hipStream_t s) {
+  if (t->free_cap >= t->rows_cap) return KV_OK;
+  unsigned* nf = nullptr;
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMalloc(&nf, (size_t)t->rows_cap * sizeof(unsigned)));
+  if (t->free_rows) {
+    HIP_TRY(hipMemcpy(nf, t->free_rows, (size_t)t->free_cap * sizeof(unsigned), hipMemcpyDeviceToDevice));
+    hipFree(t->free_rows);
+  }
+  t->free_rows = nf;
+  t->free_cap = t->rows_cap;
+  return KV_OK;
+}
+
+static int hop_behind_last(kv_table* t, hipStream_t s);
+
+// The report of a refused batch (code 2) takes the keys its tile pass inserted out of the table again (k_rollback_new).
+// A LATER lookup's partition pass may still be pending (the refusal was raised while that lookup's entry settled the
+// refused batch's pass): its new keys carry HINT_NEW too and are its own, so it runs first — and if it refuses its batch
+// as well, that one's keys go with the same sweep and the flag is cleared once more.
+static int rollback_refused(kv_table* t, hipStream_t s) {
+  int rc;
+  if ((rc = hop_behind_last(t, s)) || (rc = flush_part(t, s)) || (rc = ensure_free_list(t, s))) return rc;
+  HIP_TRY(hipMemsetAsync(t->d_stat, 0, 4 * sizeof(unsigned long long), s));
+  k_rollback_new<<<nblocks((long long)t->cap + 1, TB, 8192), TB, 0, s>>>(dev_view(t), t->free_rows, t->d_stat);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemsetAsync(t->d_counters + 1, 0, sizeof(unsigned), s));
+  unsigned c[3];
+  unsigned long long n = 0;
+  HIP_TRY(hipMemcpyAsync(&n, t->d_stat, sizeof n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(c, t->d_counters, sizeof c, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  t->pushes_since += n;   // (as after a Delete: kv_ops.hip after_release)
+  t->free_known = std::max(0, (int)c[2]);
+  t->rows_ub = c[0];
+  return KV_OK;
+}
+
 // the device error flag was found set at a synchronous point: report once, then clear it so the table
-// stays usable (the batch that raised it had no effect beyond rows it may have inserted)
+// stays usable (the batch that raised it had no effect beyond rows it may have inserted; a refused batch's — code 2 —
+// are taken out again)
 int flagged_error(kv_table* t, unsigned code, hipStream_t s) {
   hipMemsetAsync(t->d_counters + 1, 0, sizeof(unsigned), s);
+  if (code == 2) {
+    const int rc = rollback_refused(t, s);
+    if (rc) return rc;
+  }
   hipStreamSynchronize(s);
   if (t->err_host) *reinterpret_cast<volatile unsigned*>(t->err_host) = 0u;
-  t->batch.drop();   // (from report_deferred_error: ahead of the settle — a pending pass stays for the table's next op)
+  t->batch.drop();   // (from report_deferred_error: ahead of the settle — a pending pass stays for the table's next op; code 2 has run it)
   if (code == 4)
     return fail(KV_INVALID_ARGUMENT, "kv_apply_*_unique: the ids of an earlier call were NOT unique (an id was listed twice): that "
                                      "batch was not applied as the reference applies repeated ids; pass such batches to "
@@ -248,8 +313,10 @@ int flagged_error(kv_table* t, unsigned code, hipStream_t s) {
   if (code == 5)
     return fail(KV_INVALID_ARGUMENT, "kv_apply_unique_counted: the device count of an earlier call was negative or above its n_max: "
                                      "that batch was not applied (the count is not clamped)");
-  return fail(KV_INTERNAL, code == 2 ? "a hash partition received more than 65535 entries in one batch "
-                                       "(key set crafted against the partition hash); that batch was not applied"
+  return fail(KV_INTERNAL, code == 2 ? "an earlier batch was refused: one hash partition received more than 65535 entries, or more "
+                                       "distinct keys than a partition block holds that no sub-hash separates (a key set crafted "
+                                       "against the hash); those keys were not applied and the ones the batch had inserted were removed again "
+                                       "(other keys of that batch may have been: include/kvhip.h, The refused batch)"
                                      : "row slab overflow detected on device");
 }
 
