@@ -798,6 +798,32 @@ int kv_shard_lookup(kv_shard_t shard, kv_comm_t comm, const void* ids, int64_t n
 int kv_shard_apply(kv_shard_t shard, kv_comm_t comm, int optimizer, kv_handle_t slot0, kv_handle_t slot1,
                    const float* grad, const float* hp, int join, kv_stream_t stream);
 int kv_shard_join(kv_shard_t shard, kv_stream_t stream);
+/* The READ-ONLY sharded lookup: evaluation and serving of a table that only fits sharded.  The reference's partitioned
+ * lookup (python/ops/embedding_ops.py:115-204) is the same graph in both modes; outside training its per-shard op is
+ * KvVariableGatherOrZerosV2 instead of KvVariableGatherOrInsertV2 (python/ops/kv_variable_ops.py:1082-1113).  Here:
+ *   kv_shard_lookup_serve_zeros   the owner's phase for a caller with its own exchange, between kv_shard_lookup_route /
+ *                                 the exchange of the records and the exchange of the rows / kv_shard_lookup_finish:
+ *                                 one launch over the live records it received -> send_rows, record for record
+ *   kv_shard_lookup_zeros         the whole op: kv_shard_lookup with that serve (same route, lossless agreement and
+ *   kv_multi_shard_lookup_zeros   re-route, same two grouped exchanges, same finish, join and late overflow report; a
+ *                                 rank whose phase failed still takes part in the exchanges); the serve is one launch per
+ *                                 group of tables that share a row geometry
+ * Result: out[i] is what kv_gather_or_zeros on the table of ids[i]'s owner returns — the row, or zeros for a key that table
+ * does not hold, a blacklisted key and a key under the enter threshold; in lossy mode the surplus ids of an overflowing
+ * segment read zeros as ever.  An uninitialised table: KV_FAILED_PRECONDITION.
+ * No side effects on the tables: nothing is inserted, no frequency word, day stamp, flag or delta mark changes, no slot
+ * mirror is touched.  The tables are entered as kv_batch_gather_or_zeros enters them: the read runs behind a table's last
+ * op on any stream, a pending lookup pass is settled first, the table's deferred error is reported here.
+ * A pending training batch: the route of a read-only lookup overwrites the shard's route index, so the batch looked up
+ * BEFORE it can no longer be applied — kv_shard_apply_route, kv_shard_apply and kv_multi_shard_apply return
+ * KV_FAILED_PRECONDITION before anything is queued (on every rank alike: they all made the same calls), and
+ * kv_shard_apply_serve refuses as its serve token is void.  Apply a training batch before evaluating; the next training
+ * lookup (kv_shard_lookup, kv_shard_lookup_route ...) makes the shard trainable again.
+ * Stream capture: as for kv_shard_lookup — in lossless mode the whole ops are refused (KV_FAILED_PRECONDITION) before
+ * anything is queued.  kv_shard_profile does not sample read-only lookups: its sums and counts stay as they are. */
+int kv_shard_lookup_serve_zeros(kv_shard_t shard, kv_stream_t stream);
+int kv_shard_lookup_zeros(kv_shard_t shard, kv_comm_t comm, const void* ids, int64_t n, float* out, int join,
+                          kv_stream_t stream);
 /* Lossless mode — ON by default since round 4: a sharded lookup can lose nothing, like the reference's capacity-free
  * partitioned lookup (embedding_ops.py:115-204).  kv_shard_lookup / kv_multi_shard_lookup first agree on the largest
  * segment any rank's route produced (one 4-byte ncclAllReduce per table and ONE stream synchronisation per call); when
@@ -839,6 +865,9 @@ int kv_shard_agree_local(const kv_shard_t* shards, int world, int* rerouted, kv_
  * kv_shard_join(shards[0], stream). */
 int kv_multi_shard_lookup(const kv_shard_t* shards, int ntab, kv_comm_t comm, const void* const* ids, const int64_t* n,
                           float* const* outs, int join, kv_stream_t stream);
+/* the read-only form (see kv_shard_lookup_zeros) */
+int kv_multi_shard_lookup_zeros(const kv_shard_t* shards, int ntab, kv_comm_t comm, const void* const* ids,
+                                const int64_t* n, float* const* outs, int join, kv_stream_t stream);
 int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int optimizer, const kv_handle_t* slot0,
                          const kv_handle_t* slot1, const float* const* grads, const float* hp, int join,
                          kv_stream_t stream);

@@ -1,6 +1,7 @@
 // kv_route.h — the sharded layer's own kernels (included by kv_shard.hip only, after kv_device.h): the routing rule's
 // counting sort of ids by owner rank and the fixed-capacity exchange segments (k_owner_*, k_seg_headers), and the sharded
-// lookup's output rows from the records that came back (k_shard_finish).
+// lookup's output rows from the records that came back (k_shard_finish), and the owner's read-only serve of the records it
+// received (k_shard_serve_zeros).
 #pragma once
 
 // ------------------------------------------------------------------------------------------
@@ -203,4 +204,120 @@ template <int VQ, int CW = 4>
 __global__ void __launch_bounds__(TB) k_shard_finish_multi(const FinishDesc* __restrict__ descs) {
   const FinishDesc d = descs[blockIdx.y];
   shard_finish_body<VQ, CW>(d.pos_ent, d.ent_u, d.slot_of, d.rows, d.out, d.n, d.dim, d.rows_self, d.self_lo, d.self_len);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_shard_serve_zeros: the owner's READ-ONLY serve (kv_shard_lookup_serve_zeros) — rows[record] = the table's row of the
+// record's id, or zeros where k_gather_or_zeros reads zeros (row 0: a key the index does not hold; a blacklisted key and one
+// under the enter threshold are stored as zeros).  Nothing of the table is written: no insert, no frequency word, no stamp.
+// ------------------------------------------------------------------------------------------
+// The records are `world` segments of C + 1 (id, count) pairs (k_owner_scatter_fixed / k_papply PA_UNIQUE wrote them, the
+// exchange moved them): record 0 of a segment is its header {records in the segment, 0}, records 1 .. cnt are live, the rest
+// is padding.  Segment `self_seg` is read from pairs_self (this rank's own segment where it stayed in the send buffer), the
+// others from pairs.  The work follows the LIVE records: the header counts (clamped to 0 .. C — nothing else of a peer's
+// segment is trusted, and a count is only ever a loop bound) and their prefix sums sit in LDS, a dense index q walks the live
+// records, q -> its segment by a search over the prefix, its record = q - prefix[segment] + 1.  Padding is neither probed
+// nor written; the counts of the records are not read.  A wave step is goz_wave's (kv_op_kernels.h): lane l probes live
+// record l, the home entries of the next step and the ids of the step after it are in flight, the rows go VQ lanes per row
+// with the row and record numbers handed over by shuffle — with plain stores: the rows are read again at once, by the exchange
+// and by this rank's own finish (as the training serve's, kv_fused.h).  Every segment's header row is written as zeros:
+// k_shard_finish reads record 0 for an id that found no room in its segment.
+struct ServeZerosDesc {
+  TableDev t;
+  const long long* pairs;        // [world][C + 1][2]
+  const long long* pairs_self;   // segment self_seg is read here
+  float* rows;                   // [world][C + 1][dim]
+  unsigned C;
+  int world;
+  int self_seg;                  // -1: every segment is read from pairs
+  int pad;
+};
+template <int VQ, int CWMAX = 4>
+__device__ __forceinline__ void shard_serve_zeros_body(const ServeZerosDesc& d) {
+  constexpr int RW = 64 / VQ;
+  constexpr int CW = VQ < CWMAX ? VQ : CWMAX;
+  const TableDev& t = d.t;
+  const int lane = threadIdx.x & 63;
+  const int v = lane % VQ, sub = lane / VQ;
+  const int D4 = t.dim >> 2;   // float4 per row (<= VQ: lanes past it are masked)
+  const bool vlive = v < D4;
+  const int vv = vlive ? v : 0;
+  const unsigned C = d.C, S = C + 1;
+  const int world = d.world;
+  auto seg_pairs = [&](int p) { return (p == d.self_seg ? d.pairs_self : d.pairs) + 2 * (size_t)p * S; };
+  // pre[p] = live records in front of segment p; pre[MAXW] = all of them (segments past `world` hold none)
+  __shared__ unsigned pre[MAXW + 1];
+  if (threadIdx.x < 64) {
+    long long c = lane < world ? seg_pairs(lane)[0] : 0ll;
+    c = c < 0 ? 0ll : (c > (long long)C ? (long long)C : c);
+    unsigned x = (unsigned)c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned y = __shfl_up(x, o);
+      if (lane >= o) x += y;
+    }
+    pre[lane + 1] = x;
+    if (lane == 0) pre[0] = 0u;
+  }
+  // the headers' rows: zeros (world * D4 float4, the first block's)
+  if (blockIdx.x == 0)
+    for (int i = threadIdx.x; i < world * D4; i += TB)
+      reinterpret_cast<float4*>(d.rows + (size_t)(i / D4) * S * t.dim)[i % D4] = make_float4(0.f, 0.f, 0.f, 0.f);
+  __syncthreads();
+  const long long total = pre[MAXW];
+  // live record q -> its id; *g = its record number in the buffers (0 past the end: never written)
+  auto load_rec = [&](long long q, unsigned* g) -> long long {
+    *g = 0u;
+    if (q >= total) return EMPTY_KEY;
+    int p = 0;   // the last segment whose prefix is <= q (empty segments in front of it share that prefix: skipped)
+#pragma unroll
+    for (int step = MAXW / 2; step > 0; step >>= 1)
+      if (pre[p + step] <= (unsigned)q) p += step;
+    const unsigned rec = (unsigned)q - pre[p] + 1u;   // 1 .. count of segment p <= C
+    *g = (unsigned)p * S + rec;
+    return seg_pairs(p)[2 * (size_t)rec];
+  };
+  const long long nwaves = (long long)gridDim.x * (TB / 64);
+  const long long stride = nwaves * 64;
+  long long q0 = ((long long)blockIdx.x * (TB / 64) + (threadIdx.x >> 6)) * 64;
+  if (q0 >= total) return;
+  unsigned g1, g2;
+  long long k1 = load_rec(q0 + lane, &g1);            // step i + 1's id (first: step 0's)
+  long long k2 = load_rec(q0 + stride + lane, &g2);   // step i + 2's
+  unsigned long long p1 = home_of(t, k1, mix64((unsigned long long)k1));
+  Entry e1 = load_entry(&t.entries[p1]);
+  for (; q0 < total; q0 += stride) {
+    // this step's rows: finish the probe started one step ago (row 0 reads zeros: misses, lanes past the end)
+    const unsigned rr = (q0 + lane < total) ? table_find_from(t, k1, p1, e1) : 0u;
+    const unsigned gg = g1;
+    // next step: its home entries leave now, the ids of the step after it too
+    k1 = k2; g1 = g2;
+    p1 = home_of(t, k1, mix64((unsigned long long)k1));
+    if (q0 + stride < total) e1 = load_entry(&t.entries[p1]);
+    k2 = load_rec(q0 + 2 * stride + lane, &g2);
+#pragma unroll
+    for (int j0 = 0; j0 < VQ; j0 += CW) {
+      float4 val[CW];
+      unsigned rj[CW], gj[CW];
+#pragma unroll
+      for (int j = 0; j < CW; ++j) { rj[j] = __shfl(rr, (j0 + j) * RW + sub); gj[j] = __shfl(gg, (j0 + j) * RW + sub); }
+#pragma unroll
+      for (int j = 0; j < CW; ++j) val[j] = reinterpret_cast<const float4*>(row_ptr(t, rj[j]))[vv];
+#pragma unroll
+      for (int j = 0; j < CW; ++j) {
+        const long long qq = q0 + (j0 + j) * RW + sub;
+        if (qq < total && vlive) {
+          float4* dst = reinterpret_cast<float4*>(d.rows + (size_t)gj[j] * t.dim) + v;
+          // (by component — still one 16-byte store: a whole-struct copy out of val[] keeps the array in memory, 16 KiB of LDS per block)
+          dst->x = val[j].x; dst->y = val[j].y; dst->z = val[j].z; dst->w = val[j].w;
+        }
+      }
+    }
+  }
+}
+// several tables of one row geometry in one launch (blockIdx.y = table); a single table is the one-table case
+template <int VQ>
+__global__ void __launch_bounds__(TB) k_shard_serve_zeros(const ServeZerosDesc* __restrict__ descs) {
+  const ServeZerosDesc d = descs[blockIdx.y];
+  shard_serve_zeros_body<VQ>(d);
 }

@@ -1,7 +1,7 @@
 // kv_shard.hip — sharded tables on the table core (kv_host.h): hashed ownership, fixed-capacity exchange, RCCL over xGMI
 // (SURVEY.md §8e).  kv_comm_* (RCCL by dlopen, grouped send / recv; or the caller's transport), kv_shard_* (route / serve /
-// finish phases and the whole ops), the batched kv_multi_shard_* ops, and kv_bucket_by_owner, the routing rule's
-// stand-alone form.  The only unit that knows RCCL; its own kernels are kv_route.h's.
+// finish phases and the whole ops; the read-only lookup is the training one with another serve: serve_zeros_impl), the
+// batched kv_multi_shard_* ops, and kv_bucket_by_owner, the routing rule's stand-alone form.  The only unit that knows RCCL; its own kernels are kv_route.h's.
 // Each phase's arguments are built in one place (route_desc, presum_desc, finish_desc) for its single-table and its
 // batched launch; each whole op has one body (shards_lookup, shards_apply), of which the single forms are the one-table
 // case; segment sizes come from shard_bytes, batched groups from groups_of.
@@ -53,6 +53,7 @@ struct kv_shard {
   const kv_comm* verified = nullptr; // the communicator whose ranks were seen to agree on world / capacity / dim
   uint64_t route_token = 0;
   kv_batch_token_t serve_token = 0;
+  bool read_only_last = false;       // the last served batch was a read-only one (kv_shard_lookup_serve_zeros): no apply may follow it
   hipEvent_t ev_fork = nullptr, ev_done = nullptr;
   int ranks_seen = 0;                // ranks whose handshake record arrived in the first exchange (shard_verify)
   // per-phase timing of the whole ops (kv_shard_profile): events on the communicator's stream at the phase boundaries of
@@ -322,7 +323,7 @@ static FinishDesc finish_desc(const kv_shard* sh, float* out) {
 // a route with nothing to send — an empty batch, or one that failed or was refused: void headers in the send buffer, so that
 // the peers are not left waiting
 static int shard_void_route(kv_shard* sh, hipStream_t w) {
-  sh->n_last = 0; sh->route_token = 0;
+  sh->n_last = 0; sh->route_token = 0; sh->read_only_last = false;
   HIP_TRY(hipMemsetAsync(sh->counts, 0, (size_t)sh->world * 8, w));
   k_seg_headers<<<1, MAXW, 0, w>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
   return KV_OK;
@@ -340,6 +341,7 @@ static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_strea
   rt->deterministic = sh->table->deterministic;   // the route index (tile pass, position order) follows the table's mode
   sh->n_last = n;
   sh->route_token = 0;
+  sh->read_only_last = false;   // a new batch: whoever serves it says what it is
   if (n == 0) return shard_void_route(sh, s);   // an empty batch: void headers
   if ((rc = ensure_workspace(rt, n, true, s)) || (rc = ensure_pos_ent(rt, n, s))) return rc;
   MultiDesc d{};
@@ -494,6 +496,7 @@ static int multi_route_impl(const kv_shard_t* shards, const int* todo, int m, co
     rt->deterministic = false;
     sh->n_last = n[todo[j]];
     sh->route_token = 0;
+    sh->read_only_last = false;
     if ((rc = ensure_workspace(rt, sh->n_last, true, s)) || (rc = ensure_pos_ent(rt, sh->n_last, s))) return rc;
   }
   Staged<MultiDesc> hd(shards[todo[0]]->table->device, 1, m);
@@ -546,6 +549,56 @@ static int multi_finish_impl(const kv_shard_t* shards, const int* todo, int m, f
   with_lanes(row_lanes(shards[todo[0]]->table->dim), [&](auto vq) { k_shard_finish_multi<decltype(vq)::value><<<grid, TB, 0, s>>>(md); });
   HIP_TRY(hipGetLastError());
   return KV_OK;
+}
+
+// The owner's READ-ONLY serve of the tables todo[0..m) — all of one row geometry (row_lanes(dim)): 1 launch
+// (k_shard_serve_zeros, kv_route.h).  The tables are entered as kv_batch_gather_or_zeros enters them: behind their last op on
+// whatever stream, a pending lookup pass settled, the deferred error reported, as vars they keep their mirrors; no serial bump,
+// no workspace, no batch index — the shard's serve token is void, and its last served batch is marked read-only whatever
+// happens below (its route has overwritten the route index of the batch before it: shard_refuse_apply).
+static int serve_zeros_impl(const kv_shard_t* shards, const int* todo, int m, hipStream_t s) {
+  int rc;
+  std::vector<kv_table*> tbs;
+  unsigned gx = 1;
+  for (int j = 0; j < m; ++j) {
+    kv_shard* sh = shards[todo[j]];
+    sh->serve_token = 0;
+    sh->read_only_last = true;
+    tbs.push_back(sh->table);
+  }
+  for (int j = 0; j < m; ++j)
+    if ((rc = require_initialized(shards[todo[j]]->table))) return rc;   // FindOrZeros -> CheckInitializedInternal (kv_variable.h:242)
+  MultiLock lock(tbs);
+  for (kv_table* tb : lock.ts)
+    if ((rc = enter_op(tb, s, KEEP_VAR, true, false))) return rc;
+  Staged<ServeZerosDesc> hd(shards[todo[0]]->table->device, 0, m);
+  if (hd.rc) return hd.rc;
+  for (int j = 0; j < m; ++j) {
+    const kv_shard* sh = shards[todo[j]];
+    ServeZerosDesc& d = hd[j];
+    d.t = dev_view(sh->table);
+    d.pairs = sh->recv_pairs; d.pairs_self = sh->send_pairs; d.rows = sh->send_rows;
+    d.C = sh->C; d.world = sh->world;
+    d.self_seg = sh->self_in_place ? sh->rank : -1;
+    // one 64-record step per wave were every segment full (the waves past the live records leave at once)
+    gx = std::max(gx, (unsigned)nblocks((long long)sh->world * sh->C, TB, 8192));
+  }
+  const ServeZerosDesc* md;
+  if ((rc = hd.upload(s, &md))) return rc;
+  const dim3 grid(gx, (unsigned)m);
+  with_lanes(row_lanes(shards[todo[0]]->table->dim), [&](auto vq) { k_shard_serve_zeros<decltype(vq)::value><<<grid, TB, 0, s>>>(md); });
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+// A read-only lookup's route overwrote the route index of the batch before it: a training apply behind it would pre-sum its
+// gradients into the wrong records.  Refused before anything is queued — every rank made the same calls, so every rank
+// refuses alike and no peer is left waiting in a grouped recv.
+static int shard_refuse_apply(const kv_shard* sh, const char* what) {
+  if (!sh->read_only_last) return KV_OK;
+  return fail(KV_FAILED_PRECONDITION, "%s: the shard's last served batch was a read-only lookup (kv_shard_lookup_zeros / "
+                                      "kv_shard_lookup_serve_zeros), which leaves nothing to apply — nothing was queued; run the "
+                                      "training lookup of the batch first", what);
 }
 
 // gradient pre-sum of the tables todo[0..m) — all of one dim, none in deterministic mode: the tile sums, then k_papply_multi
@@ -637,7 +690,9 @@ static bool shard_owner_batchable(const kv_shard* sh) {
 // Forked from `s` onto the communicator's stream (the caller's stream is free for the dense tower; phases and exchanges in
 // one queue: no event hop between a kernel and its exchange): verify, route, lossless agreement and the re-route of grown
 // tables, exchange, serve, exchange, finish.  single: kv_shard_lookup — the phase events of kv_shard_profile are its alone.
-static int shards_lookup(const char* what, bool single, const kv_shard_t* shards, int ntab, kv_comm* comm, const void* const* ids,
+// read_only: kv_shard_lookup_zeros / kv_multi_shard_lookup_zeros — the same op but for the serve (serve_zeros_impl, one launch
+// per row geometry: the owners' tables are read, never written) and the profile, which does not sample it.
+static int shards_lookup(const char* what, bool single, bool read_only, const kv_shard_t* shards, int ntab, kv_comm* comm, const void* const* ids,
                          const int64_t* n, float* const* outs, int join, hipStream_t s) {
   int rc;
   DeviceGuard dg(shards[0]->table->device);
@@ -660,7 +715,7 @@ static int shards_lookup(const char* what, bool single, const kv_shard_t* shards
   FirstError note;
   std::vector<char> routed(ntab, 1), done(ntab, 0);
   for (int k = 0; k < ntab; ++k) shards[k]->self_in_place = shard_can_stay(shards[k]);
-  const bool pm = single && shard_prof_begin(sh0, true);
+  const bool pm = single && !read_only && shard_prof_begin(sh0, true);
   shard_prof_mark(sh0, pm, 0, w);
   auto route = [&](int k) -> int {
     if (routed[k] && note(lookup_route_impl(shards[k], ids[k], n[k], w))) routed[k] = 0;
@@ -689,7 +744,20 @@ static int shards_lookup(const char* what, bool single, const kv_shard_t* shards
   // the owners' lookups: the tables of one dim in one batched lookup over their receive buffers (tile pass of all of them
   // in one launch; the partition passes stay pending for the batched apply)
   done.assign(ntab, 0);
-  for (const auto& grp : groups_of(ntab, [&](int k) { return shard_owner_batchable(shards[k]) ? shards[k]->table->dim : -1; })) {
+  if (read_only) {   // the read-only serve instead: the tables of one row geometry in one launch, then the tables left over, one launch each
+    auto serve = [&](const int* todo, int m) -> int {
+      if (note(serve_zeros_impl(shards, todo, m, w)))
+        for (int j = 0; j < m; ++j)
+          if ((rc = shard_zero_rows(shards[todo[j]], w))) return rc;
+      for (int j = 0; j < m; ++j) done[todo[j]] = 1;
+      return KV_OK;
+    };
+    for (const auto& grp : groups_of(ntab, [&](int k) { return row_lanes(shards[k]->table->dim); }))
+      if ((rc = serve(grp.data(), (int)grp.size()))) return rc;
+    for (int k = 0; k < ntab; ++k)
+      if (!done[k] && (rc = serve(&k, 1))) return rc;
+  }
+  for (const auto& grp : groups_of(ntab, [&](int k) { return !read_only && shard_owner_batchable(shards[k]) ? shards[k]->table->dim : -1; })) {
     const int m = (int)grp.size();
     std::vector<kv_handle_t> tb(m);
     std::vector<const void*> ip(m);
@@ -741,6 +809,8 @@ static int shards_apply(bool single, const kv_shard_t* shards, int ntab, kv_comm
   DeviceGuard dg(shards[0]->table->device);
   hipStream_t w = comm->stream;
   kv_shard* const sh0 = shards[0];
+  for (int k = 0; k < ntab; ++k)
+    if ((rc = shard_refuse_apply(shards[k], single ? "kv_shard_apply" : "kv_multi_shard_apply"))) return rc;
   if ((rc = shard_fork(sh0, s, w))) return rc;
   FirstError note;
   const bool pm = single && shard_prof_begin(sh0, false);
@@ -1018,6 +1088,16 @@ int kv_shard_lookup_serve(kv_shard_t sh, kv_stream_t stream) {
   return gather_or_insert_impl(sh->table, sh->recv_pairs, nullptr, nrec, sh->send_rows, stream, 1, &sh->serve_token, sh->C + 1, &self);
 }
 
+// the owner's half of a READ-ONLY lookup: the rows of the ids the peers sent as kv_gather_or_zeros reads them (zeros for a
+// key the table does not hold, a blacklisted one, one under the enter threshold) to send_rows, record for record; the table
+// is not changed in any way.  1 launch.
+int kv_shard_lookup_serve_zeros(kv_shard_t sh, kv_stream_t stream) {
+  if (!sh) return fail(KV_INVALID_ARGUMENT, "null shard");
+  DeviceGuard dg(sh->table->device);
+  const int one = 0;
+  return serve_zeros_impl(&sh, &one, 1, (hipStream_t)stream);
+}
+
 // out[i] = the row that came back for ids[i].  1 launch.
 int kv_shard_lookup_finish(kv_shard_t sh, float* out, kv_stream_t stream) {
   if (!sh || (sh->n_last > 0 && !out)) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_finish: output pointer is null");
@@ -1041,6 +1121,7 @@ int kv_shard_lookup_finish(kv_shard_t sh, float* out, kv_stream_t stream) {
 // ids were sent in (the route index is still there: no ids, no sizes, no sync).  2 launches.
 int kv_shard_apply_route(kv_shard_t sh, const float* grad, kv_stream_t stream) {
   if (!sh || (sh->n_last > 0 && !grad)) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_route: grad pointer is null");
+  { int rc; if ((rc = shard_refuse_apply(sh, "kv_shard_apply_route"))) return rc; }
   if (sh->n_last == 0) return KV_OK;
   DeviceGuard dg(sh->table->device);
   kv_table* rt = sh->route;
@@ -1136,7 +1217,12 @@ int kv_shard_agree_local(const kv_shard_t* shards, int world, int* rerouted, kv_
 
 int kv_shard_lookup(kv_shard_t sh, kv_comm_t comm, const void* ids, int64_t n, float* out, int join, kv_stream_t stream) {
   if (!sh || !comm || comm->world != sh->world) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup: shard / communicator mismatch");
-  return shards_lookup("kv_shard_lookup", true, &sh, 1, comm, &ids, &n, &out, join, (hipStream_t)stream);
+  return shards_lookup("kv_shard_lookup", true, false, &sh, 1, comm, &ids, &n, &out, join, (hipStream_t)stream);
+}
+
+int kv_shard_lookup_zeros(kv_shard_t sh, kv_comm_t comm, const void* ids, int64_t n, float* out, int join, kv_stream_t stream) {
+  if (!sh || !comm || comm->world != sh->world) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_zeros: shard / communicator mismatch");
+  return shards_lookup("kv_shard_lookup_zeros", true, true, &sh, 1, comm, &ids, &n, &out, join, (hipStream_t)stream);
 }
 
 int kv_shard_apply(kv_shard_t sh, kv_comm_t comm, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* grad,
@@ -1150,7 +1236,15 @@ int kv_multi_shard_lookup(const kv_shard_t* shards, int ntab, kv_comm_t comm, co
   int rc;
   if ((rc = multi_shard_check(shards, ntab, comm, "kv_multi_shard_lookup"))) return rc;
   if (!ids || !n || !outs) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_lookup: null argument list");
-  return shards_lookup("kv_multi_shard_lookup", false, shards, ntab, comm, ids, n, outs, join, (hipStream_t)stream);
+  return shards_lookup("kv_multi_shard_lookup", false, false, shards, ntab, comm, ids, n, outs, join, (hipStream_t)stream);
+}
+
+int kv_multi_shard_lookup_zeros(const kv_shard_t* shards, int ntab, kv_comm_t comm, const void* const* ids, const int64_t* n,
+                                float* const* outs, int join, kv_stream_t stream) {
+  int rc;
+  if ((rc = multi_shard_check(shards, ntab, comm, "kv_multi_shard_lookup_zeros"))) return rc;
+  if (!ids || !n || !outs) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_lookup_zeros: null argument list");
+  return shards_lookup("kv_multi_shard_lookup_zeros", false, true, shards, ntab, comm, ids, n, outs, join, (hipStream_t)stream);
 }
 
 // slot0 / slot1: one handle per table (slot1 only for the FTRL family, else nullptr); hp as in kv_shard_apply_serve

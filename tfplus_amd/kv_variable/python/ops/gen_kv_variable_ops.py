@@ -1192,6 +1192,15 @@ class KvShard(object):
     self._keep = (ids, out)     # the shard's stream may still be reading / writing them
     return out
 
+  def lookup_zeros(self, comm, indices, join=True):
+    """The read-only lookup (kvhip.h kv_shard_lookup_zeros): every owner reads as kv_variable_gather_or_zeros_v2 does, no
+    table changes.  The batch looked up before it can no longer be applied: apply first, or look it up again."""
+    ids = _ids(self.table, indices)
+    out = _gather_out(self.table, ids)
+    _lib.check(_lib.lib().kv_shard_lookup_zeros(self.ptr, comm.ptr, _p(ids), ids.numel(), _p(out), int(bool(join)), _stream(self.table)))
+    self._keep = (ids, out)     # the shard's stream may still be reading / writing them
+    return out
+
   def apply(self, comm, optimizer, slots, grad, hp, join=True):
     g = _f32(self.table, grad)
     arr = _hp_array(hp)
@@ -1212,6 +1221,10 @@ class KvShard(object):
   def lookup_serve(self):
     _lib.check(_lib.lib().kv_shard_lookup_serve(self.ptr, _stream(self.table)))
 
+  def lookup_serve_zeros(self):
+    """The owner's phase of the read-only lookup, between lookup_route / lookup_finish and the caller's exchanges."""
+    _lib.check(_lib.lib().kv_shard_lookup_serve_zeros(self.ptr, _stream(self.table)))
+
   def lookup_finish(self):
     out = _gather_out(self.table, self._ids)
     _lib.check(_lib.lib().kv_shard_lookup_finish(self.ptr, _p(out), _stream(self.table)))
@@ -1231,6 +1244,16 @@ class KvShard(object):
 def kv_multi_shard_lookup(shards, comm, indices_list, join=True):
   """Sharded lookup of several tables in one step: two grouped exchanges whatever len(shards) is (kvhip.h
   kv_multi_shard_lookup).  Returns one [n_k, dim_k] tensor per table."""
+  return _multi_shard_lookup(_lib.lib().kv_multi_shard_lookup, shards, comm, indices_list, join)
+
+
+def kv_multi_shard_lookup_zeros(shards, comm, indices_list, join=True):
+  """The read-only form (kvhip.h kv_multi_shard_lookup_zeros): the owners read as kv_variable_gather_or_zeros_v2 does, one
+  serve launch per group of tables that share a row geometry.  Returns one [n_k, dim_k] tensor per table."""
+  return _multi_shard_lookup(_lib.lib().kv_multi_shard_lookup_zeros, shards, comm, indices_list, join)
+
+
+def _multi_shard_lookup(fn, shards, comm, indices_list, join):
   T = len(shards)
   ids = [_ids(sh.table, x) for sh, x in zip(shards, indices_list)]
   outs = [_gather_out(sh.table, i) for sh, i in zip(shards, ids)]
@@ -1238,7 +1261,7 @@ def kv_multi_shard_lookup(shards, comm, indices_list, join=True):
   ip = (ctypes.c_void_p * T)(*[_p(i) for i in ids])
   nn = (ctypes.c_int64 * T)(*[i.numel() for i in ids])
   op = (ctypes.c_void_p * T)(*[_p(o) for o in outs])
-  _lib.check(_lib.lib().kv_multi_shard_lookup(arr, T, comm.ptr, ip, nn, op, int(bool(join)), _stream(shards[0].table)))
+  _lib.check(fn(arr, T, comm.ptr, ip, nn, op, int(bool(join)), _stream(shards[0].table)))
   for sh, i, o in zip(shards, ids, outs):
     sh._keep = (i, o)
   return outs

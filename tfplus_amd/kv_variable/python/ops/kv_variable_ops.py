@@ -211,6 +211,11 @@ class KvVariable(object):
       return gen_kv_variable_ops.kv_variable_gather_or_insert_with_counts(self._handle, ids, counts)
     return gen_kv_variable_ops.kv_variable_gather_or_insert_v2(self._handle, ids)
 
+  def gather_or_zeros(self, indices):
+    """GatherOrZeros whatever the mode (kv_variable_ops.py:1097-1113 is its IS_TRAINING == False branch): read-only, zeros
+    for a key the table does not hold.  The owner's read of sharded.ShardedKvVariable.lookup_zeros."""
+    return gen_kv_variable_ops.kv_variable_gather_or_zeros_v2(self._handle, torch.as_tensor(indices).to(self._device))
+
   def lookup_sparse(self, ids, segment_ids, weights, num_segments, combiner, count_occurrences):
     """embedding_lookup_sparse on this table in one fused call: kv_lookup_sparse when training (missing keys are
     inserted, the gradient is filed on the variable), kv_lookup_sparse_zeros else (GatherOrZeros rows, read-only, no

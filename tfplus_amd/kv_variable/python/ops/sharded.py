@@ -217,6 +217,22 @@ class ShardedKvVariable(object):
     out = _take(back, where, self.take_fn)
     return out.reshape(tuple(ids.shape) + tuple(out.shape[1:]))
 
+  def lookup_zeros(self, ids):
+    """The read-only lookup (evaluation, serving): the same graph with GatherOrZeros at the owner, as the reference's
+    partitioned lookup outside training (python/ops/embedding_ops.py:115-204 over kv_variable_ops.py:1082-1113).  Unique
+    ids travel (no counts: nothing is counted), the owner reads shard.gather_or_zeros(served) — zeros for a key it does
+    not hold, nothing inserted — and the rows come back and are expanded.  Leaves nothing for a backward pass: a following
+    apply_gradients takes the long path, never the stale short one.  (The native form: KvShard.lookup_zeros.)"""
+    flat = ids.reshape(-1)
+    uniq, inv = torch.unique(flat, return_inverse=True)
+    rt = route(uniq, self.group, self.bucket_fn, rule=self.owner_rule)
+    served = exchange(rt, uniq, group=self.group, presorted=rt.bucketed_ids, take_fn=self.take_fn)
+    rows = self.shard.gather_or_zeros(served)
+    back = exchange(rt, rows, reverse=True, group=self.group, take_fn=self.take_fn)   # in the order of uniq
+    self._last = None
+    out = _take(back, inv, self.take_fn)
+    return out.reshape(tuple(ids.shape) + tuple(out.shape[1:]))
+
   def apply_gradients(self, apply_fn, grad, ids):
     """Sends one summed gradient row per unique id to its owner; each owner runs
     apply_fn(shard, grad, ids) once — its fused dedup + segment-sum + row update."""
