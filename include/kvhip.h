@@ -86,7 +86,16 @@ const char* kv_last_error(void);
  * clamped to uint16 like SaturateMaxFrequency.  `capacity_hint` pre-sizes the HBM hash index
  * and row slab for that many keys (0 = small default; both grow on demand).  Keys of every
  * supported key_dtype are handled as their 64-bit two's-complement pattern; `ids` buffers are
- * int64 (KV_DT_INT64 / KV_DT_UINT64) or int32 (KV_DT_INT32). */
+ * int64 (KV_DT_INT64 / KV_DT_UINT64) or int32 (KV_DT_INT32).
+ * Any positive `dim` is accepted.  The fused kernels serve the multiples of 4 up to 1024 and every dim up to 256; on a
+ * table of another dim (257, 258, 1028, 2048 ...) the lookups (kv_gather_or_insert*, kv_gather_or_zeros,
+ * kv_batch_gather_or_zeros, kv_lookup_sparse and its _grad), kv_insert, kv_scatter_update with ASSIGN (or with one id),
+ * the exports, the imports and the figures still work, while every optimizer op (_tok, _unique, kv_multi_*),
+ * kv_scatter_update with any other operation on more than one id, kv_dedup_segment_sum[_dev], kv_unsorted_segment_sum and
+ * kv_[batch_]lookup_sparse_zeros return KV_UNIMPLEMENTED from their host-side checks, with nothing queued and the table
+ * unchanged.  The batched optimizer ops
+ * take the multiples of 4 only, kv_apply_unique_counted the multiples of 4 up to 256
+ * (tests/test_gpu_row_geometry.py holds this list op by op). */
 int kv_create(int key_dtype, int value_dtype, int dim, int enter_threshold, int64_t capacity_hint,
               int device, kv_handle_t* out);
 /* Replaces DestroyKvVariableOp (kernels/kv_variable_ops.cc:295-323). Synchronous. */

@@ -449,6 +449,8 @@ int launch_apply(kv_table* prof_t, const WsDev& wd, const PartArgs& pa, long lon
     return md ? fail(KV_UNIMPLEMENTED, "batched launch: embedding dim %d (multiples of 4 only)", D)
               : fail(KV_UNIMPLEMENTED, "embedding dim %d not supported by the fused kernels "
                      "(multiples of 4 up to 1024, any dim up to 256)", D);
+  if (rc)   // (today the one such step is k_apply_fin's request for its LDS, dims 576 and up: launch_apply_t)
+    return fail(rc, "sorted-position apply at embedding dim %d: setting up a kernel launch failed (code %d)", D, rc);
   return KV_OK;
 }
 

@@ -1352,6 +1352,12 @@ __device__ __forceinline__ void apply_body(const WsDev& w, const PartArgs& a) {
 // its share of the item directory at once (a key's first chunk item names the key); keys of up to 64 chunks
 // go one to a wave, bigger ones to the whole block.  The order of the additions depends on nothing but the key.
 constexpr int TBF = 1024;
+// LDS of a k_apply_fin block: the key directory and its count (static), and one partial row per wave (dynamic).  Above
+// LDS_NO_ASK — what a launch gets without asking; from dim 576 up — launch_apply_t asks for the dynamic part, as
+// launch_occ_sum does; at dim 1024 the block holds 28 688 + 65 552 bytes of the CU's 160 KB.
+constexpr size_t FIN_STATIC_LDS = (size_t)TBF * 7 * 4 + 16;
+constexpr size_t LDS_NO_ASK = 64 * 1024;
+__host__ __device__ inline size_t fin_dyn_lds(int D) { return (size_t)(TBF / 64) * D * 4 + 16; }
 template <int MODE, int OPT, int V, int LPR, int K>
 __device__ __forceinline__ void apply_fin_body(const WsDev& w, const PartArgs& a) {
   const unsigned errflag = *reinterpret_cast<volatile unsigned*>(&a.tv.counters[1]);
@@ -1633,6 +1639,15 @@ __global__ void __launch_bounds__(TB) k_gather_multi(const MultiDesc* __restrict
   gather_body<VQ>(m.a.tv, m.w, m.out, m.n);
 }
 
+// the k_apply_fin entry point launch_apply_t launches (multi: the descriptor-array form, float4 optimizer rows only)
+template <int MODE, int OPT, int V, int LPR, int K>
+const void* fin_kernel(bool multi) {
+  if constexpr (MODE == MODE_APPLY && V == 4) {
+    if (multi) return (const void*)k_apply_fin_multi<MODE, OPT, V, LPR, K>;
+  }
+  return (const void*)k_apply_fin<MODE, OPT, V, LPR, K>;
+}
+
 // k_apply / k_apply_fin dispatch on the row geometry (kv_launch.h: launch_sorted_apply, launch_dedup_fold).
 // D % 4 == 0 -> float4 lanes, else scalar lanes.  md != nullptr: one launch over `ntab` tables (grid.y),
 // nchunks = blocks per table; only MODE_APPLY on float4 rows is instantiated for it.
@@ -1644,7 +1659,12 @@ int launch_apply_t(const WsDev& wd, const PartArgs& pa, hipStream_t s, const Mul
   int grid_ = (int)nchunks;
 #define KV_APPLY(V, LPR, K)                                                                        \
   do {                                                                                             \
-    const size_t sh = span == 1 ? (size_t)(TBF / 64) * D * 4 + 16 : 0;                              \
+    const size_t sh = span == 1 ? fin_dyn_lds(D) : 0;                                              \
+    if (span == 1 && sh + FIN_STATIC_LDS > LDS_NO_ASK) {  /* wide rows (dims 576..1024): per device, so asked at every launch */ \
+      if (hipFuncSetAttribute(fin_kernel<MODE, OPT, V, LPR, K>(md != nullptr), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                              (int)sh) != hipSuccess)                                               \
+        return KV_INTERNAL;                                                                        \
+    }                                                                                              \
     if (span != 1) {  /* one resident generation of blocks: a second one would start when the first ends */  \
       struct ApTag {};                                                                             \
       const int resident = resident_blocks<ApTag>(k_apply<MODE, OPT, V, LPR, K>, TBS, 6, 4);   /* per device */ \

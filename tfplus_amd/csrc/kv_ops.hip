@@ -1260,6 +1260,11 @@ int kv_scatter_update(kv_handle_t t, const void* ids, const float* updates, int6
   int rc;
   if ((rc = check_table(t))) return rc;
   if (op < KV_SCATTER_ASSIGN || op > KV_SCATTER_MAX) return fail(KV_INVALID_ARGUMENT, "unsupported update operation %d", op);
+  // a folding operation counts every occurrence of a repeated id: the de-duplication below does that, and it runs on the dims
+  // of the fused kernels only.  The per-position path would keep ONE occurrence: refused, before anything is queued
+  if (op != KV_SCATTER_ASSIGN && n > 1 && !dim_supported(t->dim))
+    return fail(KV_UNIMPLEMENTED, "kv_scatter_update: operation %d on more than one id at embedding dim %d (multiples of 4 up to "
+                                  "1024, any dim up to 256; assign, or one id per call, works at every dim)", op, t->dim);
   TableOp tab(t, stream);
   const hipStream_t s = tab.s;
   if ((rc = enter_op(t, s))) return rc;
@@ -1294,7 +1299,7 @@ int kv_scatter_update(kv_handle_t t, const void* ids, const float* updates, int6
     return KV_OK;
   }
   // assign: one of the occurrences of a repeated id stays (the reference's result depends on its thread
-  // interleaving there); dims outside the fused kernels' range take this path for every operation
+  // interleaving there); a single id of any operation, at any dim
   return scatter_like(t, ids, updates, n, op, 0, -1, nullptr, s);
 }
 
