@@ -1,14 +1,15 @@
 """The row geometry of every kernel family, restated: which instantiation a dim runs in each pipeline, the committed
 list of dims that reaches every one of them at its edges, and the one batch the row-geometry tests run on.
 
-  class_of(pipeline, D)   the instantiation dim D takes in `pipeline`, restated from the dispatch tables in the sources
-                          (tests/test_row_geometry.py parses those tables and holds this restatement against them):
-      "sorted"        (V, LPR, K) of k_apply / k_apply_fin            kv_kernels.h   launch_apply_t
-      "entry"         (V, LPR, K) of k_papply / k_uapply, or None     kv_papply.h    launch_papply_t, kv_uapply.h launch_uapply_t
-      "row_copy"      lanes per row of the row-copy kernels, or None  kv_host.h      row_lanes / with_lanes
-      "gather"        VQ of k_gather (0: the generic body)            kvhip.hip      launch_gather
-      "gather_zeros"  q of k_gather_or_zeros_w, or 0 (8-lane kernel)  kv_ops.hip     kv_gather_or_zeros
-      "sparse_zeros"  VQ of lsz_body (0: the whole wave)              kv_ops.hip     sparse_zeros_lanes
+  class_of(pipeline, D)   the instantiation dim D takes in `pipeline`, restated from the one dispatch table in the sources,
+                          kv_row_geom.h (tests/test_row_geometry.py holds this restatement, for every dim, against what
+                          that header selects, and the launchers below against the header):
+      "sorted"        (V, LPR, K) of k_apply / k_apply_fin            with_row_geom<SORTED_MAX_Q, true>   kv_kernels.h launch_apply_t
+      "entry"         (V, LPR, K) of k_papply / k_uapply, or None     with_row_geom<ENTRY_MAX_Q>          kv_papply.h, kv_uapply.h, kv_sums.hip
+      "row_copy"      lanes per row of the row-copy kernels, or None  row_lanes / with_lanes
+      "gather"        VQ of k_gather (0: the generic body)            pow2_vectors(D, 256)                kvhip.hip launch_gather
+      "gather_zeros"  q of k_gather_or_zeros_w, or 0 (8-lane kernel)  pow2_vectors(D, 64)                 kv_ops.hip kv_gather_or_zeros
+      "sparse_zeros"  VQ of lsz_body (0: the whole wave)              pow2_vectors(D, 64)                 kv_ops.hip sparse_zeros_lanes
       "occ_sum"       NC of k_occ_sum                                 kvhip.hip      launch_occ_sum
   DIMS                for every class of every pipeline its smallest dim, its largest dim and, where the class has one,
                       a dim whose last lane or k vector is partly masked
@@ -29,13 +30,13 @@ LDS_PER_CU = 160 * 1024         # gfx950
 
 PIPELINES = ("sorted", "entry", "row_copy", "gather", "gather_zeros", "sparse_zeros", "occ_sum")
 
-# (largest q = D / 4, (V, LPR, K)): launch_apply_t's float4 rows; the entry-list kernels stop at q = 64
+# (largest q = D / 4, (V, LPR, K)): kv_row_geom.h Float4Ladder, launch_apply_t's float4 rows; the entry-list kernels stop at q = 64
 _F4 = [(1, (4, 1, 1)), (2, (4, 2, 1)), (4, (4, 4, 1)), (8, (4, 8, 1)), (16, (4, 8, 2)), (32, (4, 16, 2)), (64, (4, 64, 1)),
        (128, (4, 64, 2)), (256, (4, 64, 4))]
-# (largest D, (V, LPR, K)): launch_apply_t's scalar rows
+# (largest D, (V, LPR, K)): kv_row_geom.h ScalarLadder, launch_apply_t's scalar rows
 _SC = [(1, (1, 1, 1)), (2, (1, 2, 1)), (4, (1, 4, 1)), (8, (1, 8, 1)), (16, (1, 16, 1)), (32, (1, 32, 1)), (64, (1, 64, 1)),
        (128, (1, 64, 2)), (256, (1, 64, 4))]
-_ENTRY_Q = 64                   # kv_host.h fused_ok
+_ENTRY_Q = 64                   # kv_row_geom.h ENTRY_MAX_Q (fused_ok)
 _OCC = [1, 2, 4, 8, 16]         # launch_occ_sum: nc = ceil(D / 64) -> the first NC that holds it
 
 

@@ -1,9 +1,12 @@
-"""The row-geometry restatement (tests/_row_geometry.py) against the sources, on the CPU: class_of agrees with the
-dispatch tables parsed out of the headers, DIMS reaches every class of every pipeline at its edges, draw_batch meets its
-occurrence plan for the seeds the GPU module uses, and the LDS a k_apply_fin block needs is within what its launcher
-provides at every dim.  A later change to a table fails here until the restatement and the dim list follow."""
+"""The row-geometry restatement (tests/_row_geometry.py) against the sources, on the CPU: class_of agrees, for every dim,
+with what the one dispatch table (tfplus_amd/csrc/kv_row_geom.h) selects — printed by a stand-alone program that includes
+the header alone — and every launcher goes through that table; DIMS reaches every class of every pipeline at its edges,
+draw_batch meets its occurrence plan for the seeds the GPU module uses, and the LDS a k_apply_fin block needs is within
+what its launcher provides at every dim.  A later change to a table fails here until the restatement and the dim list follow."""
 import os
 import re
+import shutil
+import subprocess
 import sys
 
 import numpy as np
@@ -28,10 +31,36 @@ def _const(text, name):
   return int(m.group(1))
 
 
-def _ladder(text, var, macro):
-  """[(top, (V, LPR, K))] of the `if (var <= top) MACRO(V, LPR, K);` lines, in source order."""
-  return [(int(t), (int(v), int(l), int(k)))
-          for t, v, l, k in re.findall(r"if \(%s <= (\d+)\) %s\((\d+), (\d+), (\d+)\);" % (var, macro), text)]
+def _function(text, head):
+  """The definition that starts with `head`, up to its closing brace in column 0."""
+  at = text.index(head)
+  return text[at:text.index("\n}\n", at) + 3]
+
+
+@pytest.fixture(scope="module")
+def selected(tmp_path_factory):
+  """{D: what kv_row_geom.h selects for dim D}, D in 0..1028, as tests/c_abi/row_geom_check.cc prints it: the program
+  includes the header alone, is built with the host compiler under AddressSanitizer and UBSan and run directly (no GPU,
+  nothing loaded into Python).  "sorted" / "entry": the (V, LPR, K) with_row_geom hands the launcher's lambda, or None."""
+  src = os.path.join(HERE, "c_abi", "row_geom_check.cc")
+  exe = str(tmp_path_factory.mktemp("row_geom") / "row_geom_check")
+  if shutil.which("g++"):
+    cmd = ["g++", "-std=c++17", "-fsanitize=address,undefined"]
+  else:   # the compiler the library itself needs
+    cmd = [shutil.which("hipcc") or "/opt/rocm/bin/hipcc", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined"]
+  subprocess.check_call(cmd + ["-Wall", "-Werror", "-I", CSRC, "-o", exe, src])
+  r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+  assert r.returncode == 0, r.stdout + r.stderr
+  lines = r.stdout.strip().split("\n")
+  assert lines[-1] == "ok" and len(lines) == 1030, r.stdout[-2000:] + r.stderr
+  cls = lambda w: None if w == "-" else tuple(int(x) for x in w.split(","))
+  out = {}
+  for D, line in enumerate(lines[:-1]):
+    w = line.split()
+    assert int(w[0]) == D and len(w) == 9, line
+    out[D] = dict(sorted=cls(w[1]), entry=cls(w[2]), fused_ok=bool(int(w[3])), row_lanes=int(w[4]), lanes=int(w[5]),
+                  lanes256=int(w[6]), pow2_64=int(w[7]), pow2_256=int(w[8]))
+  return out
 
 
 def test_constants_match_the_headers():
@@ -44,59 +73,96 @@ def test_constants_match_the_headers():
   assert all(G.dim_supported(D) for D in G.DIMS) and not any(G.dim_supported(D) for D in G.REFUSED)
 
 
-def test_class_of_matches_the_sorted_apply_table():
-  ker = _src("kv_kernels.h")
-  body = ker[ker.index("int launch_apply_t("):]
-  f4, sc = _ladder(body, "q", "KV_APPLY"), _ladder(body, "D", "KV_APPLY")
-  assert f4 == G._F4 and sc == G._SC
-  assert re.search(r"if \(\(D & 3\) == 0\) \{\s*const int q = D / 4;", body)
+def test_class_of_matches_the_sorted_apply_table(selected):
+  for D in range(1, 1025):
+    assert G.class_of("sorted", D) == selected[D]["sorted"], D
+    assert (selected[D]["sorted"] is not None) == G.dim_supported(D), D
   for D in SUPPORTED:
-    want = next(c for t, c in (f4 if D % 4 == 0 else sc) if (D // 4 if D % 4 == 0 else D) <= t)
-    assert G.class_of("sorted", D) == want, D
-    v, lpr, k = want
-    assert D <= v * lpr * k, D          # the class holds the whole row
-  # apply_lanes (the cold batch the partition pass forms) states the same lane counts
-  m = re.search(r"return q <= 1 \? 1 : q <= 2 \? 2 : q <= 4 \? 4 : q <= 16 \? 8 : q <= 32 \? 16 : 64;", ker)
-  assert m
+    if selected[D]["sorted"]:
+      v, lpr, k = selected[D]["sorted"]
+      assert D <= v * lpr * k, D          # the class holds the whole row
+  assert all(selected[D]["sorted"] is None for D in (0, 257, 258, 1025, 1028))
+  body = _function(_src("kv_kernels.h"), "int launch_apply_t(")
+  assert re.search(r"return with_row_geom<SORTED_MAX_Q, true>\(D, \[&\]\(auto g\) -> int \{", body)
+  geom = _src("kv_row_geom.h")
+  assert _const(geom, "SORTED_MAX_Q") == G._F4[-1][0] and _const(geom, "SCALAR_MAX_D") == G._SC[-1][0]
+  # apply_lanes (the cold batch the partition pass forms) states the same lane counts: restated for the device, and held
+  # against the table by the compiler
+  assert re.search(r"return q <= 1 \? 1 : q <= 2 \? 2 : q <= 4 \? 4 : q <= 16 \? 8 : q <= 32 \? 16 : 64;", geom)
+  assert re.search(r"if \(!row_class\(D\)\.none\(\) && apply_lanes\(D\) != row_class\(D\)\.LPR\) return false;", geom)
+  assert re.search(r"static_assert\(apply_lanes_match_the_ladders\(\),", geom)
+  assert "apply_lanes(a.tv.dim)" in _src("kv_kernels.h")
 
 
-@pytest.mark.parametrize("name,macro,fn", [("kv_papply.h", "KV_PA", "launch_papply_t"), ("kv_uapply.h", "KV_UA", "launch_uapply_t")])
-def test_class_of_matches_the_entry_list_tables(name, macro, fn):
-  text = _src(name)
-  body = text[text.index("int %s(" % fn):]
-  lad = _ladder(body, "q", macro)
-  assert lad == [e for e in G._F4 if e[0] <= G._ENTRY_Q]
-  assert re.search(r"if \(\(D & 3\) != 0", body)
-  host = _src("kv_host.h")
-  assert re.search(r"inline bool fused_ok\(int D\) \{\s*if \(\(D & 3\) != 0\) return false;\s*const int q = D / 4;\s*"
-                   r"return q >= 1 && q <= 64;", host)
+ENTRY_LAUNCHERS = [("kv_papply.h", "int launch_papply_t("), ("kv_uapply.h", "int launch_uapply_t("),
+                   ("kv_sums.hip", "int launch_tsum("), ("kv_sums.hip", "static int launch_ltsum_t("),
+                   ("kv_sums.hip", "int launch_papply_ud(")]
+
+
+@pytest.mark.parametrize("name,head", ENTRY_LAUNCHERS, ids=[h.split()[-1][:-1] for _, h in ENTRY_LAUNCHERS])
+def test_class_of_matches_the_entry_list_tables(name, head, selected):
+  body = _function(_src(name), head)
+  calls = re.findall(r"with_row_geom<([^>]*)>\(", body)
+  assert calls == ["ENTRY_MAX_Q"], (head, calls)
+  assert _const(_src("kv_row_geom.h"), "ENTRY_MAX_Q") == G._ENTRY_Q
+  assert "constexpr bool fused_ok(int D) { return !row_class(D, ENTRY_MAX_Q, false).none(); }" in _src("kv_row_geom.h")
+  for D in range(1, 1025):
+    assert G.class_of("entry", D) == selected[D]["entry"], D
+    assert selected[D]["fused_ok"] == (selected[D]["entry"] is not None) == (D % 4 == 0 and D // 4 <= G._ENTRY_Q), D
+    if selected[D]["entry"]:
+      assert selected[D]["entry"] == selected[D]["sorted"], D      # one table: the entry family is its float4 rungs to q = 64
+
+
+def test_no_hand_written_ladder_remains():
+  """The table is stated once: no `if (q <= N) KV_XX(V, LPR, K);` ladder, no per-expansion tag struct, no rung outside
+  kv_row_geom.h; every rung of the restatement is there once."""
+  for name in sorted(os.listdir(CSRC)):
+    if not name.endswith((".h", ".hip")):
+      continue
+    text = _src(name)
+    assert not re.search(r"if \((?:q|D) <= \d+\) KV_\w+\(", text), name      # (nc: the occ-sum table, another rule)
+    assert not re.search(r"struct \w*Tag \{\}", text), name
+    assert ("Rung<" in text) == (name == "kv_row_geom.h"), name
+  rungs = [(int(t), (int(v), int(l), int(k)))
+           for t, v, l, k in re.findall(r"\bRung<(\d+), (\d+), (\d+), (\d+)>", _src("kv_row_geom.h"))]
+  assert rungs == G._F4 + G._SC
+
+
+def test_class_of_matches_the_row_copy_lanes(selected):
   for D in range(1, 1025):
     q = D // 4
-    want = next(c for t, c in lad if q <= t) if D % 4 == 0 and q <= lad[-1][0] else None
-    assert G.class_of("entry", D) == want, D
-
-
-def test_class_of_matches_the_row_copy_lanes():
-  host = _src("kv_host.h")
-  assert re.search(r"inline int row_lanes\(int D\) \{ return \(int\)pow2ceil\(\(unsigned long long\)std::max\(1, D / 4\)\); \}", host)
-  body = host[host.index("auto with_lanes("):host.index("auto with_id_type(")]
-  cases = [int(c) for c in re.findall(r"case (\d+): return f\(std::integral_constant<int, \1>", body)]
-  assert cases == [1, 2, 4, 8, 16, 32] and re.search(r"default: return f\(std::integral_constant<int, 64>", body)
-  assert sorted({G.class_of("row_copy", D) for D in SUPPORTED if D % 4 == 0}) == cases + [64]
+    assert selected[D]["row_lanes"] == G._pow2ceil(max(1, q)), D
+    assert selected[D]["lanes"] == min(64, selected[D]["row_lanes"]) and selected[D]["lanes256"] == min(256, selected[D]["row_lanes"]), D
+    if D % 4 == 0:
+      assert G.class_of("row_copy", D) == selected[D]["lanes"], D
+  assert sorted({G.class_of("row_copy", D) for D in SUPPORTED if D % 4 == 0}) == [1, 2, 4, 8, 16, 32, 64]
   # dim 36: 16 lanes in the row copies, 8 lanes x 2 vectors in the apply
   assert G.class_of("row_copy", 36) == 16 and G.class_of("entry", 36) == (4, 8, 2)
+  # the default cap adds no instantiation to the callers that name none
+  assert re.search(r"template <int CAP = 64, int L = 1, class F>\s*auto with_lanes\(int lanes, F&& f\)", _src("kv_row_geom.h"))
+  for name in ("kvhip.hip", "kv_ops.hip", "kv_shard.hip"):
+    assert set(re.findall(r"\bwith_lanes(<\w+>)?\(", _src(name))) <= ({"", "<TB>"} if name == "kvhip.hip" else {""}), name
 
 
-def test_class_of_matches_the_gather_tables():
+def test_class_of_matches_the_gather_tables(selected):
   hip, ops = _src("kvhip.hip"), _src("kv_ops.hip")
-  body = hip[hip.index("void launch_gather("):hip.index("#undef KV_GATHER")]
-  cases = [(int(a), int(b)) for a, b in re.findall(r"case (\d+): KV_GATHER\((\d+)\);", body)]
-  assert cases == [(v, v) for v in (1, 2, 4, 8, 16, 32, 64, 128, 256)] and "default: KV_GATHER(0);" in body
-  assert "const bool vec = q > 0 && (q & (q - 1)) == 0 && q <= TB;" in body and _const(_src("kv_device.h"), "TB") == 256
-  assert sorted({G.class_of("gather", D) for D in SUPPORTED}) == [0] + [v for v, _ in cases]
-  cond = "(D & 3) == 0 && q >= 1 && q <= 64 && (q & (q - 1)) == 0) ? q : 0;"
-  assert cond in ops[ops.index("static int sparse_zeros_lanes("):]
-  assert "const bool wave_shaped = (t->dim & 3) == 0 && q >= 1 && q <= 64 && (q & (q - 1)) == 0;" in ops
+  body = _function(hip, "void launch_gather(")
+  assert "const int q = pow2_vectors(D, TB);" in body and _const(_src("kv_device.h"), "TB") == 256
+  # a power-of-two q takes its own VQ, every other dim the generic body <0>
+  assert re.search(r"if \(q\) with_lanes<TB>\(q, launch\);\s*else launch\(std::integral_constant<int, 0>\{\}\);", body)
+  assert "static int sparse_zeros_lanes(int D) { return pow2_vectors(D, 64); }" in ops
+  gz = _function(ops, "int kv_gather_or_zeros(")
+  assert "const int q = pow2_vectors(t->dim, 64);" in gz
+  assert re.search(r"if \(q\)\s*with_lanes\(q, \[&\]\(auto vq\) \{ k_gather_or_zeros_w<", gz)
+  for D in range(1, 1025):
+    assert G.class_of("gather", D) == selected[D]["pow2_256"], D
+    if selected[D]["pow2_256"]:
+      assert selected[D]["lanes256"] == selected[D]["pow2_256"], D       # with_lanes<256> hands q itself over
+    for p in ("gather_zeros", "sparse_zeros"):
+      assert G.class_of(p, D) == selected[D]["pow2_64"], (p, D)
+    if selected[D]["pow2_64"]:
+      assert selected[D]["lanes"] == selected[D]["pow2_64"], D
+  assert sorted({G.class_of("gather", D) for D in SUPPORTED}) == [0, 1, 2, 4, 8, 16, 32, 64, 128, 256]
   for p in ("gather_zeros", "sparse_zeros"):
     assert sorted({G.class_of(p, D) for D in SUPPORTED}) == [0, 1, 2, 4, 8, 16, 32, 64]
 

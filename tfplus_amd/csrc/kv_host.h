@@ -11,8 +11,9 @@
 // Staged<Desc> alone (the staging ring: acquire, fill, upload, busy until the stream has read them).
 //
 // What the entry points share: TableOp (device, lock and stream of a single-table op), require_initialized (the one
-// precondition message), with_lanes / with_id_type (a kernel's row-width and id-type template arguments from run-time
-// values), self_part_args (the PartArgs of an op on a table's own rows) and ensure_pos_ent (Workspace::pos_ent).
+// precondition message), with_id_type (a kernel's id-type template argument from a run-time value; the row-width ones come
+// from kv_row_geom.h, the one statement of the row geometry: with_lanes, with_row_geom), self_part_args (the PartArgs of an
+// op on a table's own rows) and ensure_pos_ent (Workspace::pos_ent).
 #pragma once
 
 #include <algorithm>
@@ -234,20 +235,6 @@ struct TableOp {
   TableOp(kv_table* t, kv_stream_t stream) : dg(t->device), lock(t->mu), s((hipStream_t)stream) {}
 };
 
-// f(std::integral_constant<int, VQ>) for a row of `lanes` lanes (row_lanes: a power of two, 1 .. 64): the VQ template
-// argument of the row-copy kernels
-template <class F>
-auto with_lanes(int lanes, F&& f) {
-  switch (lanes) {
-    case 1: return f(std::integral_constant<int, 1>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 8: return f(std::integral_constant<int, 8>{});
-    case 16: return f(std::integral_constant<int, 16>{});
-    case 32: return f(std::integral_constant<int, 32>{});
-    default: return f(std::integral_constant<int, 64>{});
-  }
-}
 // f(IdT{}) with the id type of a kernel: int or long long
 template <class F>
 auto with_id_type(bool int32_ids, F&& f) {
@@ -258,17 +245,7 @@ auto with_id_type(bool int32_ids, F&& f) {
 // ---- the entry-list pipeline (kv_fused.h) ----
 // ids per index pass: positions and epart rows are 30-bit fields of the entry list's words, a partition block takes
 // up to 65535 entries; 2^23 ids (4096 tiles) stay well inside both
-constexpr long long FUSED_MAX_N = 1ll << 23;
-// dims it serves: every multiple of 4 up to 256 (rows of dim / 4 float4; a row's lane group is the next power of two,
-// the lanes past the row's end masked: dims 12, 20, 100 ... run the same kernels as 16, 32, 128)
-inline bool fused_ok(int D) {
-  if ((D & 3) != 0) return false;
-  const int q = D / 4;
-  return q >= 1 && q <= 64;
-}
-
-// lanes per row of the row-copy kernels: dim / 4 rounded up to a power of two
-inline int row_lanes(int D) { return (int)pow2ceil((unsigned long long)std::max(1, D / 4)); }
+constexpr long long FUSED_MAX_N = 1ll << 23;   // (the dims it serves: fused_ok, kv_row_geom.h)
 
 // (re)allocation that leaves the old buffer in place when the new one cannot be had
 template <typename T>

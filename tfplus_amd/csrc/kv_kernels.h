@@ -391,16 +391,6 @@ __device__ __forceinline__ size_t seg_entry(const unsigned short* tpre, const un
   return (size_t)lo * TILE + tstart[lo] + (x - tpre[lo]);
 }
 
-// lanes that share one row in the apply kernels, by dim (launch_apply_t below dispatches on the same table);
-// 64 / lanes keys ride side by side in a wave = the cold batch the partition pass forms
-__host__ __device__ inline int apply_lanes(int D) {
-  if ((D & 3) == 0) {
-    const int q = D / 4;
-    return q <= 1 ? 1 : q <= 2 ? 2 : q <= 4 ? 4 : q <= 16 ? 8 : q <= 32 ? 16 : 64;
-  }
-  return D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : D <= 32 ? 32 : 64;
-}
-
 // chunk geometry of a hot key: HC rows per chunk — about what a batch of cold keys costs, so every work item
 // of the apply weighs the same and a round-robin hand-out is balanced.  Occurrence order (det == 2): one chunk, the
 // whole key — a sum taken one row at a time in list order is one chain.
@@ -1648,62 +1638,37 @@ const void* fin_kernel(bool multi) {
   return (const void*)k_apply_fin<MODE, OPT, V, LPR, K>;
 }
 
-// k_apply / k_apply_fin dispatch on the row geometry (kv_launch.h: launch_sorted_apply, launch_dedup_fold).
-// D % 4 == 0 -> float4 lanes, else scalar lanes.  md != nullptr: one launch over `ntab` tables (grid.y),
+// k_apply / k_apply_fin dispatch on the row geometry (kv_launch.h: launch_sorted_apply, launch_dedup_fold; kv_row_geom.h:
+// the whole table, D % 4 == 0 -> float4 lanes, else scalar lanes).  md != nullptr: one launch over `ntab` tables (grid.y),
 // nchunks = blocks per table; only MODE_APPLY on float4 rows is instantiated for it.
 // span == 0: k_apply, span == 1: k_apply_fin.  Returns KV_OK, or KV_UNIMPLEMENTED for an unsupported dim.
 template <int MODE, int OPT>
 int launch_apply_t(const WsDev& wd, const PartArgs& pa, hipStream_t s, const MultiDesc* md, int ntab,
                    unsigned nchunks, int span) {
   const int D = pa.tv.dim;
-  int grid_ = (int)nchunks;
-#define KV_APPLY(V, LPR, K)                                                                        \
-  do {                                                                                             \
-    const size_t sh = span == 1 ? fin_dyn_lds(D) : 0;                                              \
-    if (span == 1 && sh + FIN_STATIC_LDS > LDS_NO_ASK) {  /* wide rows (dims 576..1024): per device, so asked at every launch */ \
-      if (hipFuncSetAttribute(fin_kernel<MODE, OPT, V, LPR, K>(md != nullptr), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)sh) != hipSuccess)                                               \
-        return KV_INTERNAL;                                                                        \
-    }                                                                                              \
-    if (span != 1) {  /* one resident generation of blocks: a second one would start when the first ends */  \
-      struct ApTag {};                                                                             \
-      const int resident = resident_blocks<ApTag>(k_apply<MODE, OPT, V, LPR, K>, TBS, 6, 4);   /* per device */ \
-      if ((int)nchunks > resident) grid_ = resident; else grid_ = (int)nchunks;                     \
-    }                                                                                              \
-    if constexpr (MODE == MODE_APPLY && V == 4) {                                                  \
-      if (md) {                                                                                    \
-        if (span) k_apply_fin_multi<MODE, OPT, V, LPR, K><<<dim3((unsigned)grid_, (unsigned)ntab), TBF, sh, s>>>(md);   \
-        else k_apply_multi<MODE, OPT, V, LPR, K><<<dim3((unsigned)grid_, (unsigned)ntab), TBS, sh, s>>>(md);      \
-        return KV_OK;                                                                              \
-      }                                                                                            \
-    }                                                                                              \
-    if (md) return KV_UNIMPLEMENTED;                                                               \
-    if (span) k_apply_fin<MODE, OPT, V, LPR, K><<<grid_, TBF, sh, s>>>(wd, pa);                     \
-    else k_apply<MODE, OPT, V, LPR, K><<<grid_, TBS, sh, s>>>(wd, pa);                        \
-    return KV_OK;                                                                                  \
-  } while (0)
-  if ((D & 3) == 0) {
-    const int q = D / 4;
-    if (q <= 1) KV_APPLY(4, 1, 1);
-    if (q <= 2) KV_APPLY(4, 2, 1);
-    if (q <= 4) KV_APPLY(4, 4, 1);
-    if (q <= 8) KV_APPLY(4, 8, 1);
-    if (q <= 16) KV_APPLY(4, 8, 2);    // dims 36..64: 8 lanes x 2 float4
-    if (q <= 32) KV_APPLY(4, 16, 2);   // dims 68..128: 16 lanes x 2 float4
-    if (q <= 64) KV_APPLY(4, 64, 1);
-    if (q <= 128) KV_APPLY(4, 64, 2);
-    if (q <= 256) KV_APPLY(4, 64, 4);
-  } else {
-    if (D <= 1) KV_APPLY(1, 1, 1);
-    if (D <= 2) KV_APPLY(1, 2, 1);
-    if (D <= 4) KV_APPLY(1, 4, 1);
-    if (D <= 8) KV_APPLY(1, 8, 1);
-    if (D <= 16) KV_APPLY(1, 16, 1);
-    if (D <= 32) KV_APPLY(1, 32, 1);
-    if (D <= 64) KV_APPLY(1, 64, 1);
-    if (D <= 128) KV_APPLY(1, 64, 2);
-    if (D <= 256) KV_APPLY(1, 64, 4);
-  }
-#undef KV_APPLY
-  return KV_UNIMPLEMENTED;
+  return with_row_geom<SORTED_MAX_Q, true>(D, [&](auto g) -> int {
+    constexpr int V = decltype(g)::V, LPR = decltype(g)::LPR, K = decltype(g)::K;
+    int grid_ = (int)nchunks;
+    const size_t sh = span == 1 ? fin_dyn_lds(D) : 0;
+    if (span == 1 && sh + FIN_STATIC_LDS > LDS_NO_ASK) {  // wide rows (dims 576..1024): per device, so asked at every launch
+      if (hipFuncSetAttribute(fin_kernel<MODE, OPT, V, LPR, K>(md != nullptr), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)sh) != hipSuccess)
+        return KV_INTERNAL;
+    }
+    if (span != 1) {  // one resident generation of blocks: a second one would start when the first ends
+      const int resident = resident_blocks<k_apply<MODE, OPT, V, LPR, K>>(TBS, 6, 4);   // per device
+      if ((int)nchunks > resident) grid_ = resident;
+    }
+    if constexpr (MODE == MODE_APPLY && V == 4) {
+      if (md) {
+        if (span) k_apply_fin_multi<MODE, OPT, V, LPR, K><<<dim3((unsigned)grid_, (unsigned)ntab), TBF, sh, s>>>(md);
+        else k_apply_multi<MODE, OPT, V, LPR, K><<<dim3((unsigned)grid_, (unsigned)ntab), TBS, sh, s>>>(md);
+        return KV_OK;
+      }
+    }
+    if (md) return KV_UNIMPLEMENTED;
+    if (span) k_apply_fin<MODE, OPT, V, LPR, K><<<grid_, TBF, sh, s>>>(wd, pa);
+    else k_apply<MODE, OPT, V, LPR, K><<<grid_, TBS, sh, s>>>(wd, pa);
+    return KV_OK;
+  });
 }

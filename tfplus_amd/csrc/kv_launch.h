@@ -1,10 +1,12 @@
 // kv_launch.h — the launchers kvhip.hip, kv_ops.hip and kv_apply.hip call and the translation unit that defines each.  The optimizer apply kernels are
 // instantiated once per OPT_*, in kv_opt_<name>.hip (kv_opt_unit.h); the optimizer-free sums in kv_sums.hip.  A launcher
-// dispatches on the row geometry and returns KV_OK, or KV_UNIMPLEMENTED for a dim its kernels do not serve.
+// dispatches on the row geometry — the one table of kv_row_geom.h, through with_row_geom — and returns KV_OK, or
+// KV_UNIMPLEMENTED for a dim its kernels do not serve.
 // md != nullptr: `ntab` tables in one launch (wd / n: the largest table's; pa: the first table's, only its dim is read).
 #pragma once
 
 #include "kv_types.h"
+#include "kv_row_geom.h"
 
 namespace __attribute__((visibility("hidden"))) kvhip_internal {
 

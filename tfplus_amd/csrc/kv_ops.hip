@@ -381,14 +381,13 @@ static int lookup_sparse_locked(kv_table* t, const void* ids, const void* segmen
     using IDT = decltype(id);
     k_seg_offsets<IDT><<<nblocks(n + 1, TB, 2048), TB, 0, s>>>((const IDT*)segment_ids, n, num_segments, ws.seg_off);
   });
-  const int q = (D % 4 == 0) ? D / 4 : 0;
-  const bool vec = q > 0 && (q & (q - 1)) == 0 && q <= 64;   // the sorted-position combiner's rows: a power of two of float4, or <0>
-  const int grid = nblocks(num_segments * (fused ? row_lanes(D) : vec ? q : 1), TB, 8192);
+  const int q = pow2_vectors(D, 64);   // the sorted-position combiner's rows: a power of two of float4, or <0>
+  const int grid = nblocks(num_segments * (fused ? row_lanes(D) : q ? q : 1), TB, 8192);
   if (fused)
     with_lanes(row_lanes(D), [&](auto vq) {
       k_seg_combine_e<decltype(vq)::value><<<grid, TB, 0, s>>>(td, ws.pos_ent, wd.ent_b, wd.ent_key, ws.seg_off, weights, num_segments, combiner, out);
     });
-  else if (vec)
+  else if (q)
     with_lanes(q, [&](auto vq) {
       k_seg_combine<decltype(vq)::value><<<grid, TB, 0, s>>>(td, wd, ws.seg_off, weights, num_segments, combiner, out);
     });
@@ -476,10 +475,7 @@ static int sparse_zeros_checks(const kv_table* t, const void* ids, const void* s
   return KV_OK;
 }
 // lanes of a segment's group in lsz_body: dim / 4 for the dims 4, 8, ..., 256, else (0) the whole wave
-static int sparse_zeros_lanes(int D) {
-  const int q = D / 4;
-  return ((D & 3) == 0 && q >= 1 && q <= 64 && (q & (q - 1)) == 0) ? q : 0;
-}
+static int sparse_zeros_lanes(int D) { return pow2_vectors(D, 64); }
 }  // namespace
 
 namespace __attribute__((visibility("hidden"))) kvhip_internal {
@@ -841,12 +837,11 @@ int kv_gather_or_zeros(kv_handle_t t, const void* ids, int64_t n, float* out, kv
   // deferred error of the table's last batch — the next op that does will)
   if ((rc = hand_over(t, s, KEEP_VAR, true, false))) return rc;
   const TableDev td = dev_view(t);
-  const int q = t->dim / 4;
-  const bool wave_shaped = (t->dim & 3) == 0 && q >= 1 && q <= 64 && (q & (q - 1)) == 0;
+  const int q = pow2_vectors(t->dim, 64);   // a wave of whole rows (k_gather_or_zeros_w); 0: the 8-lane kernel
   const int gw = nblocks(n, TB, 8192);  // a 64-id step per wave at 1 M ids: residency hides the hops
   with_id_type(t->key_dtype == KV_DT_INT32, [&](auto id) {
     using IDT = decltype(id);
-    if (wave_shaped)
+    if (q)
       with_lanes(q, [&](auto vq) { k_gather_or_zeros_w<IDT, decltype(vq)::value><<<gw, TB, 0, s>>>(td, (const IDT*)ids, out, n); });
     else
       k_gather_or_zeros<IDT><<<nblocks(n, TB / 8, 8192), TB, 0, s>>>(td, (const IDT*)ids, out, n);

@@ -697,29 +697,18 @@ __global__ void __launch_bounds__(256, KV_PA_WAVES) k_papply_multi(const MultiDe
   papply_body<OPT, V, LPR, K, 256>(m.w, m.a, mode);
 }
 
-// dispatch on the row geometry (the dims fused_ok() admits: float4 rows, a power-of-two lane count); one block per
+// dispatch on the row geometry (kv_row_geom.h: the float4 rungs up to ENTRY_MAX_Q, the dims fused_ok() admits); one block per
 // partition.  Returns KV_OK, or KV_UNIMPLEMENTED for a dim the entry-list pipeline does not serve.
 // md != nullptr: `ntab` tables in one launch (wd = the largest ntiles / P of the batch of tables)
 template <int OPT>
 int launch_papply_t(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t s, const MultiDesc* md = nullptr, int ntab = 0) {
-  const int D = pa.tv.dim;
   const size_t sh = (size_t)wd.ntiles * 4 + 32;
-  if ((D & 3) != 0 || (mode & 0xFF) > PA_NONE) return KV_UNIMPLEMENTED;   // (PA_UNIQUE / PA_DEDUP: launch_papply_ud, kv_sums.hip)
-#define KV_PA(V, LPR, K)                                                     \
-  do {                                                                       \
-    if (md) k_papply_multi<OPT, V, LPR, K><<<dim3(wd.P, (unsigned)ntab), 256, sh, s>>>(md, mode);   \
-    else if (wd.P <= 512u && !pa.det) k_papply<OPT, V, LPR, K, 512><<<(int)wd.P, 512, sh, s>>>(wd, pa, mode);   \
-    else k_papply<OPT, V, LPR, K, 256><<<(int)wd.P, 256, sh, s>>>(wd, pa, mode);       \
-    return KV_OK;                                                            \
-  } while (0)
-  const int q = D / 4;
-  if (q <= 1) KV_PA(4, 1, 1);
-  if (q <= 2) KV_PA(4, 2, 1);
-  if (q <= 4) KV_PA(4, 4, 1);
-  if (q <= 8) KV_PA(4, 8, 1);   // (dim 32 with 4 lanes x 2 vectors or 2 x 4 per key — 16 / 32 keys per wave and step: 102 / 177 us against 62.7)
-  if (q <= 16) KV_PA(4, 8, 2);
-  if (q <= 32) KV_PA(4, 16, 2);
-  if (q <= 64) KV_PA(4, 64, 1);
-#undef KV_PA
-  return KV_UNIMPLEMENTED;
+  if ((mode & 0xFF) > PA_NONE) return KV_UNIMPLEMENTED;   // (PA_UNIQUE / PA_DEDUP: launch_papply_ud, kv_sums.hip)
+  return with_row_geom<ENTRY_MAX_Q>(pa.tv.dim, [&](auto g) -> int {
+    constexpr int V = decltype(g)::V, LPR = decltype(g)::LPR, K = decltype(g)::K;
+    if (md) k_papply_multi<OPT, V, LPR, K><<<dim3(wd.P, (unsigned)ntab), 256, sh, s>>>(md, mode);
+    else if (wd.P <= 512u && !pa.det) k_papply<OPT, V, LPR, K, 512><<<(int)wd.P, 512, sh, s>>>(wd, pa, mode);
+    else k_papply<OPT, V, LPR, K, 256><<<(int)wd.P, 256, sh, s>>>(wd, pa, mode);
+    return KV_OK;
+  });
 }

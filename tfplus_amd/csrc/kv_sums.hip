@@ -2,6 +2,7 @@
 // table-less forms of its partition pass (k_papply_uniq: the distinct ids of a batch numbered — the sharded route, kv_unique,
 // kv_dedup_segment_sum; k_papply_dedup: the gradient rows summed per distinct id) and the plain segment fold of the
 // sorted-position pipeline (k_apply in MODE_DEDUP).  A translation unit of its own, next to the optimizers' (kv_opt_unit.h).
+// Each launcher takes its kernel's row geometry from the one table of kv_row_geom.h (with_row_geom).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -23,50 +24,26 @@ namespace {
 
 namespace kvhip_internal {
 
-// k_tsum: same row geometry as k_apply.  grid = ntiles blocks of TBC threads.  md: wd = the largest ntiles.
+// k_tsum: same row geometry as k_papply.  grid = ntiles blocks of TBC threads.  md: wd = the largest ntiles.
 int launch_tsum(const TableDev& td, const WsDev& wd, const float* grad, hipStream_t s, const MultiDesc* md, int ntab) {
-  const int D = td.dim;
-#define KV_TSUM(V, LPR, K)                                                                              \
-  do {                                                                                                  \
-    if (md) k_tsum_multi<V, LPR, K><<<dim3(wd.ntiles, (unsigned)ntab), TBC, 0, s>>>(md);                 \
-    else k_tsum<V, LPR, K><<<wd.ntiles, TBC, (size_t)TILE * 4, s>>>(td, wd, grad);                       \
-    return KV_OK;                                                                                       \
-  } while (0)
-  if ((D & 3) != 0) return KV_UNIMPLEMENTED;
-  const int q = D / 4;
-  if (q <= 1) KV_TSUM(4, 1, 1);
-  if (q <= 2) KV_TSUM(4, 2, 1);
-  if (q <= 4) KV_TSUM(4, 4, 1);
-  if (q <= 8) KV_TSUM(4, 8, 1);
-  if (q <= 16) KV_TSUM(4, 8, 2);
-  if (q <= 32) KV_TSUM(4, 16, 2);
-  if (q <= 64) KV_TSUM(4, 64, 1);
-#undef KV_TSUM
-  return KV_UNIMPLEMENTED;
+  return with_row_geom<ENTRY_MAX_Q>(td.dim, [&](auto g) -> int {
+    constexpr int V = decltype(g)::V, LPR = decltype(g)::LPR, K = decltype(g)::K;
+    if (md) k_tsum_multi<V, LPR, K><<<dim3(wd.ntiles, (unsigned)ntab), TBC, 0, s>>>(md);
+    else k_tsum<V, LPR, K><<<wd.ntiles, TBC, (size_t)TILE * 4, s>>>(td, wd, grad);
+    return KV_OK;
+  });
 }
 
 // k_ltsum: one block per tile
 template <typename IdT>
 static int launch_ltsum_t(const TableDev& td, const WsDev& wd, const IdT* ids, long long n, int det, const float* grad,
                           hipStream_t s) {
-  const int D = td.dim;
   const size_t sh = ltile_smem_bytes();
-#define KV_LTSUM(V, LPR, K)                                                                              \
-  do {                                                                                                   \
-    k_ltsum<IdT, V, LPR, K><<<(int)wd.ntiles, TBT, sh, s>>>(td, wd, ids, nullptr, n, det, grad);           \
-    return KV_OK;                                                                                        \
-  } while (0)
-  if ((D & 3) != 0) return KV_UNIMPLEMENTED;
-  const int q = D / 4;
-  if (q <= 1) KV_LTSUM(4, 1, 1);
-  if (q <= 2) KV_LTSUM(4, 2, 1);
-  if (q <= 4) KV_LTSUM(4, 4, 1);
-  if (q <= 8) KV_LTSUM(4, 8, 1);
-  if (q <= 16) KV_LTSUM(4, 8, 2);
-  if (q <= 32) KV_LTSUM(4, 16, 2);
-  if (q <= 64) KV_LTSUM(4, 64, 1);
-#undef KV_LTSUM
-  return KV_UNIMPLEMENTED;
+  return with_row_geom<ENTRY_MAX_Q>(td.dim, [&](auto g) -> int {
+    constexpr int V = decltype(g)::V, LPR = decltype(g)::LPR, K = decltype(g)::K;
+    k_ltsum<IdT, V, LPR, K><<<(int)wd.ntiles, TBT, sh, s>>>(td, wd, ids, nullptr, n, det, grad);
+    return KV_OK;
+  });
 }
 int launch_ltsum(const TableDev& td, const WsDev& wd, const void* ids, int ids_kind, long long n, int det, const float* grad,
                  hipStream_t s) {
@@ -83,29 +60,18 @@ int launch_papply_ud(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t 
     else k_papply_uniq<256><<<(int)wd.P, 256, sh, s>>>(wd, pa, mode);
     return KV_OK;
   }
-  const int D = pa.tv.dim;
-  if (mode != PA_DEDUP || (D & 3) != 0) return KV_UNIMPLEMENTED;
-#define KV_PD(V, LPR, K)                                                     \
-  do {                                                                       \
-    if (md) k_papply_dedup_multi<V, LPR, K><<<dim3(wd.P, (unsigned)ntab), 256, sh, s>>>(md);   \
-    else if (pa.dd_number) {                                                 \
-      if (wd.P <= 512u && !pa.det) k_papply_dedup<V, LPR, K, 512, true><<<(int)wd.P, 512, sh, s>>>(wd, pa);   \
-      else k_papply_dedup<V, LPR, K, 256, true><<<(int)wd.P, 256, sh, s>>>(wd, pa);   \
-    }                                                                        \
-    else if (wd.P <= 512u && !pa.det) k_papply_dedup<V, LPR, K, 512><<<(int)wd.P, 512, sh, s>>>(wd, pa);   \
-    else k_papply_dedup<V, LPR, K, 256><<<(int)wd.P, 256, sh, s>>>(wd, pa);   \
-    return KV_OK;                                                            \
-  } while (0)
-  const int q = D / 4;
-  if (q <= 1) KV_PD(4, 1, 1);
-  if (q <= 2) KV_PD(4, 2, 1);
-  if (q <= 4) KV_PD(4, 4, 1);
-  if (q <= 8) KV_PD(4, 8, 1);
-  if (q <= 16) KV_PD(4, 8, 2);
-  if (q <= 32) KV_PD(4, 16, 2);
-  if (q <= 64) KV_PD(4, 64, 1);
-#undef KV_PD
-  return KV_UNIMPLEMENTED;
+  if (mode != PA_DEDUP) return KV_UNIMPLEMENTED;
+  return with_row_geom<ENTRY_MAX_Q>(pa.tv.dim, [&](auto g) -> int {
+    constexpr int V = decltype(g)::V, LPR = decltype(g)::LPR, K = decltype(g)::K;
+    if (md) k_papply_dedup_multi<V, LPR, K><<<dim3(wd.P, (unsigned)ntab), 256, sh, s>>>(md);
+    else if (pa.dd_number) {
+      if (wd.P <= 512u && !pa.det) k_papply_dedup<V, LPR, K, 512, true><<<(int)wd.P, 512, sh, s>>>(wd, pa);
+      else k_papply_dedup<V, LPR, K, 256, true><<<(int)wd.P, 256, sh, s>>>(wd, pa);
+    }
+    else if (wd.P <= 512u && !pa.det) k_papply_dedup<V, LPR, K, 512><<<(int)wd.P, 512, sh, s>>>(wd, pa);
+    else k_papply_dedup<V, LPR, K, 256><<<(int)wd.P, 256, sh, s>>>(wd, pa);
+    return KV_OK;
+  });
 }
 
 int launch_dedup_fold(const WsDev& wd, const PartArgs& pa, hipStream_t s, const MultiDesc* md, int ntab, unsigned nchunks,

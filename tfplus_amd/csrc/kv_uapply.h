@@ -245,41 +245,28 @@ __global__ void __launch_bounds__(256, (K == 1 ? 4 : 2)) k_uapply_counted(PartAr
   uapply_body<OPT, V, LPR, K>(a, ids, ids32, n);
 }
 
-// dispatch on the row geometry (as k_papply: float4 rows, a power-of-two lane count).  KV_UNIMPLEMENTED for other dims:
-// the caller falls back to the batch pipeline, which serves them.  md != nullptr: `ntab` tables in one launch (n = the
+// dispatch on the row geometry (as k_papply: kv_row_geom.h, the float4 rungs up to ENTRY_MAX_Q).  KV_UNIMPLEMENTED for other
+// dims: the caller falls back to the batch pipeline, which serves them.  md != nullptr: `ntab` tables in one launch (n = the
 // largest table's ids, pa = any table's arguments: only the dim is read).  n_dev != nullptr (single table only): n is the
 // most ids the call may hold — the grid is sized from it — and the kernel takes the count from *n_dev (k_uapply_counted)
 template <int OPT>
 int launch_uapply_t(const PartArgs& pa, const void* ids, int ids32, long long n, hipStream_t s, const MultiDesc* md = nullptr,
                     int ntab = 0, const long long* n_dev = nullptr) {
-  const int D = pa.tv.dim;
-  if ((D & 3) != 0) return KV_UNIMPLEMENTED;
-#define KV_UA(V, LPR, K)                                                                                        \
-  do {                                                                                                          \
-    constexpr int G = 64 / LPR;                                                                                 \
-    struct UaTag {};                                                                                            \
-    const int resident = resident_blocks<UaTag>(k_uapply<OPT, V, LPR, K>, 256, 6, 2);   /* per device */          \
-    const long long nbatch = (n + G - 1) / G;                                                                   \
-    const long long want = (nbatch + 3) / 4;                                                                    \
-    int grid = (int)(want < 1 ? 1 : want > resident ? resident : want);                                         \
-    if (md) {   /* all tables' blocks are one resident generation */                                            \
-      if (ntab > 0 && (long long)grid * ntab > resident) grid = resident / ntab > 1 ? resident / ntab : 1;       \
-      k_uapply_multi<OPT, V, LPR, K><<<dim3((unsigned)grid, (unsigned)ntab), 256, 0, s>>>(md, ids32);            \
-    } else if (n_dev) {                                                                                         \
-      k_uapply_counted<OPT, V, LPR, K><<<grid, 256, 0, s>>>(pa, ids, ids32, n, n_dev);                           \
-    } else {                                                                                                    \
-      k_uapply<OPT, V, LPR, K><<<grid, 256, 0, s>>>(pa, ids, ids32, n);                                          \
-    }                                                                                                           \
-    return KV_OK;                                                                                               \
-  } while (0)
-  const int q = D / 4;
-  if (q <= 1) KV_UA(4, 1, 1);
-  if (q <= 2) KV_UA(4, 2, 1);
-  if (q <= 4) KV_UA(4, 4, 1);
-  if (q <= 8) KV_UA(4, 8, 1);
-  if (q <= 16) KV_UA(4, 8, 2);
-  if (q <= 32) KV_UA(4, 16, 2);
-  if (q <= 64) KV_UA(4, 64, 1);
-#undef KV_UA
-  return KV_UNIMPLEMENTED;
+  return with_row_geom<ENTRY_MAX_Q>(pa.tv.dim, [&](auto g) -> int {
+    constexpr int V = decltype(g)::V, LPR = decltype(g)::LPR, K = decltype(g)::K;
+    constexpr int G = 64 / LPR;
+    const int resident = resident_blocks<k_uapply<OPT, V, LPR, K>>(256, 6, 2);   // per device
+    const long long nbatch = (n + G - 1) / G;
+    const long long want = (nbatch + 3) / 4;
+    int grid = (int)(want < 1 ? 1 : want > resident ? resident : want);
+    if (md) {   // all tables' blocks are one resident generation
+      if (ntab > 0 && (long long)grid * ntab > resident) grid = resident / ntab > 1 ? resident / ntab : 1;
+      k_uapply_multi<OPT, V, LPR, K><<<dim3((unsigned)grid, (unsigned)ntab), 256, 0, s>>>(md, ids32);
+    } else if (n_dev) {
+      k_uapply_counted<OPT, V, LPR, K><<<grid, 256, 0, s>>>(pa, ids, ids32, n, n_dev);
+    } else {
+      k_uapply<OPT, V, LPR, K><<<grid, 256, 0, s>>>(pa, ids, ids32, n);
+    }
+    return KV_OK;
+  });
 }

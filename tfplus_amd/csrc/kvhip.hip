@@ -543,30 +543,17 @@ void launch_tile(kv_table* t, const WsDev& wd, const void* ids, const int* count
 void launch_gather(const TableDev& td, const WsDev& wd, float* op, long long m, hipStream_t s,
                    const MultiDesc* md, int ntab, bool order) {
   const int D = td.dim;
-  const int q = (D % 4 == 0) ? D / 4 : 0;
-  const bool vec = q > 0 && (q & (q - 1)) == 0 && q <= TB;
-  const long long rows_per_block = vec ? TB / q : 1;
+  const int q = pow2_vectors(D, TB);   // a lane group per row; 0: the generic body, one thread per element
   constexpr int gcap = 8192;  // one 64-row step per wave at 1M rows: residency, not a loop, hides the hops
-  const int grid = vec ? nblocks(m, q <= 64 ? TB : (int)rows_per_block, gcap) : nblocks(m * D, TB, 4096);
-#define KV_GATHER(VQ)                                                                        \
-  do {                                                                                       \
-    if (md) k_gather_multi<VQ><<<dim3((unsigned)grid, (unsigned)ntab), TB, 0, s>>>(md);       \
-    else if (order) k_gather<VQ, true><<<grid + ITEM_BLOCKS, TB, 0, s>>>(td, wd, op, m);      \
-    else k_gather<VQ, false><<<grid, TB, 0, s>>>(td, wd, op, m);                              \
-  } while (0)
-  switch (vec ? q : 0) {
-    case 1: KV_GATHER(1); break;
-    case 2: KV_GATHER(2); break;
-    case 4: KV_GATHER(4); break;
-    case 8: KV_GATHER(8); break;
-    case 16: KV_GATHER(16); break;
-    case 32: KV_GATHER(32); break;
-    case 64: KV_GATHER(64); break;
-    case 128: KV_GATHER(128); break;
-    case 256: KV_GATHER(256); break;
-    default: KV_GATHER(0); break;
-  }
-#undef KV_GATHER
+  const int grid = q ? nblocks(m, q <= 64 ? TB : TB / q, gcap) : nblocks(m * D, TB, 4096);   // (q > 64: TB / q rows per block)
+  auto launch = [&](auto vq) {
+    constexpr int VQ = decltype(vq)::value;
+    if (md) k_gather_multi<VQ><<<dim3((unsigned)grid, (unsigned)ntab), TB, 0, s>>>(md);
+    else if (order) k_gather<VQ, true><<<grid + ITEM_BLOCKS, TB, 0, s>>>(td, wd, op, m);
+    else k_gather<VQ, false><<<grid, TB, 0, s>>>(td, wd, op, m);
+  };
+  if (q) with_lanes<TB>(q, launch);
+  else launch(std::integral_constant<int, 0>{});
 }
 
 // partition pass.  multi (md != nullptr): wd carries the LARGEST ntiles / P of the batch of tables (LDS
@@ -593,7 +580,6 @@ void launch_order(const TableDev& td, const WsDev& wd, long long n, hipStream_t 
 // ... and tables: one in occurrence-order mode takes the sorted-position pipeline for every op, like a dim the entry-list
 // kernels do not serve (its sums are one chain per key there; the entry lists sum tile by tile)
 bool fused_tab(const kv_table* t) { return fused_ok(t->dim) && !t->occurrence_order; }
-bool pow2_rows(int D) { return (D & 3) == 0 && row_lanes(D) == D / 4; }
 // tile pass: dedup, index probes / inserts, entries, tile-local order and (out != nullptr) the output rows
 // md != nullptr: `ntab` tables in one launch (grid.y), arguments from the descriptor array; multi_rows: with rows
 void launch_ltile(kv_table* t, const TableDev& td, const WsDev& wd, const void* ids, const int* counts, long long n, float* out,
