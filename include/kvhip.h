@@ -877,6 +877,56 @@ int kv_multi_shard_lookup(const kv_shard_t* shards, int ntab, kv_comm_t comm, co
 /* the read-only form (see kv_shard_lookup_zeros) */
 int kv_multi_shard_lookup_zeros(const kv_shard_t* shards, int ntab, kv_comm_t comm, const void* const* ids,
                                 const int64_t* n, float* const* outs, int join, kv_stream_t stream);
+/* embedding_lookup_sparse on SHARDED tables: the finish phase combines into segments.  The reference sends a partitioned
+ * variable's multi-hot feature down its op chain (python/ops/embedding_ops.py:279-441 over :115-204); here the rows a
+ * combine needs already sit in the shard's receive buffer when the finish runs, so one launch walks the segments and
+ * writes [num_segments, dim] once — the [n, dim] rows are never written or read back.
+ *   kv_shard_lookup_finish_sparse        the phase, for a caller with its own exchange: it stands where
+ *                                        kv_shard_lookup_finish stands, with its preconditions — the batch's
+ *                                        kv_shard_lookup_route must be the shard's last (else KV_FAILED_PRECONDITION), n is
+ *                                        that batch's length
+ *   kv_shard_lookup_sparse               kv_shard_lookup / kv_shard_lookup_zeros / kv_multi_shard_lookup[_zeros] with that
+ *   kv_shard_lookup_sparse_zeros         finish.  Everything up to the finish is those ops', their effects on the owners'
+ *   kv_multi_shard_lookup_sparse[_zeros] tables included: the training form inserts, counts every occurrence and leaves the
+ *                                        shard trainable (kv_shard_apply of values [n, dim], e.g. kv_lookup_sparse_grad's);
+ *                                        the read-only form changes nothing and voids a pending batch for the apply, as
+ *                                        documented for kv_shard_lookup_zeros.  kv_shard_profile samples the combining
+ *                                        finish of kv_shard_lookup_sparse as phase 4 (finish).
+ * Result: out[s, :] = the combiner over the positions j of segment s, in position order, of w_j * row_j, where row_j is
+ * bit for bit what the plain sharded lookup of the same kind returns for ids[j]: the owner's row; zeros where
+ * kv_gather_or_zeros reads zeros, in the read-only form; zeros for the surplus ids of an overflowing segment in lossy mode.
+ * Accumulator, denominators, empty segments, n == 0, num_segments == 0, the clamping of segment ids and a list that is not
+ * ascending: as kv_lookup_sparse_zeros (float32 from +0, one multiply-add per position and element; mean divides by the
+ * float32 sum of w_j, sqrtn by sqrtf of the sum of w_j * w_j, both in position order; zero rows count in the
+ * denominators).  n == 0 with num_segments > 0 still writes every segment — the plain finish is skipped for an empty batch,
+ * this one is not.  0 <= num_segments <= 2^31 - 2; n <= the shard's max_ids; segment_ids [n] int32 or int64, weights [n] or
+ * NULL.
+ * The multi forms: one segment dtype and one combiner per call; `weights` may be NULL, and so may weights[k];
+ * segment_ids[k] == NULL means table k is finished plainly into outs[k] [n_k, dim_k] — a model with one-hot and multi-hot
+ * features still pays two exchanges per step.  The combining finish is one launch per group of sparse tables that share a
+ * row geometry.
+ * Argument errors, all KV_INVALID_ARGUMENT: a null segment_ids (n > 0, num_segments > 0; the single forms) or out
+ * (num_segments > 0), a segment dtype other than int32 / int64, a combiner outside 0 .. 2, num_segments out of range.  The
+ * phase form reports them before anything is queued.  The whole ops handle them like a failed route of that table: void
+ * headers go out, the rank takes part in both exchanges (its peers are never left waiting), out is not written, the error
+ * is returned at the end.
+ * Stream capture: as kv_shard_lookup.  The finish itself takes no workspace and allocates nothing. */
+int kv_shard_lookup_finish_sparse(kv_shard_t shard, const void* segment_ids, int segment_dtype, const float* weights,
+                                  int64_t num_segments, int combiner, float* out, kv_stream_t stream);
+int kv_shard_lookup_sparse(kv_shard_t shard, kv_comm_t comm, const void* ids, const void* segment_ids, int segment_dtype,
+                           const float* weights, int64_t n, int64_t num_segments, int combiner, float* out, int join,
+                           kv_stream_t stream);
+int kv_shard_lookup_sparse_zeros(kv_shard_t shard, kv_comm_t comm, const void* ids, const void* segment_ids,
+                                 int segment_dtype, const float* weights, int64_t n, int64_t num_segments, int combiner,
+                                 float* out, int join, kv_stream_t stream);
+int kv_multi_shard_lookup_sparse(const kv_shard_t* shards, int ntab, kv_comm_t comm, const void* const* ids,
+                                 const void* const* segment_ids, int segment_dtype, const float* const* weights,
+                                 const int64_t* n, const int64_t* num_segments, int combiner, float* const* outs,
+                                 int join, kv_stream_t stream);
+int kv_multi_shard_lookup_sparse_zeros(const kv_shard_t* shards, int ntab, kv_comm_t comm, const void* const* ids,
+                                       const void* const* segment_ids, int segment_dtype, const float* const* weights,
+                                       const int64_t* n, const int64_t* num_segments, int combiner, float* const* outs,
+                                       int join, kv_stream_t stream);
 int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int optimizer, const kv_handle_t* slot0,
                          const kv_handle_t* slot1, const float* const* grads, const float* hp, int join,
                          kv_stream_t stream);

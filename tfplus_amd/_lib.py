@@ -93,6 +93,13 @@ SIGNATURES = {
     "kv_shard_agree_local": (_i32, [_c.POINTER(_vp), _i32, _c.POINTER(_i32), _vp]),
     "kv_multi_shard_lookup": (_i32, [_c.POINTER(_vp), _i32, _vp, _c.POINTER(_vp), _c.POINTER(_c.c_int64), _c.POINTER(_vp), _i32, _vp]),
     "kv_multi_shard_lookup_zeros": (_i32, [_c.POINTER(_vp), _i32, _vp, _c.POINTER(_vp), _c.POINTER(_c.c_int64), _c.POINTER(_vp), _i32, _vp]),
+    "kv_shard_lookup_finish_sparse": (_i32, [_vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp]),
+    "kv_shard_lookup_sparse": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _vp]),
+    "kv_shard_lookup_sparse_zeros": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _vp]),
+    "kv_multi_shard_lookup_sparse": (_i32, [_c.POINTER(_vp), _i32, _vp, _c.POINTER(_vp), _c.POINTER(_vp), _i32, _c.POINTER(_vp),
+                                     _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _i32, _c.POINTER(_vp), _i32, _vp]),
+    "kv_multi_shard_lookup_sparse_zeros": (_i32, [_c.POINTER(_vp), _i32, _vp, _c.POINTER(_vp), _c.POINTER(_vp), _i32, _c.POINTER(_vp),
+                                           _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _i32, _c.POINTER(_vp), _i32, _vp]),
     "kv_multi_shard_apply": (_i32, [_c.POINTER(_vp), _i32, _vp, _i32, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp),
                              _c.POINTER(_f), _i32, _vp]),
     "kv_shard_join": (_i32, [_vp, _vp]),

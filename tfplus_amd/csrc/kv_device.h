@@ -913,3 +913,22 @@ __device__ __forceinline__ unsigned owner_rank(long long id, int world, int rule
   long long m = id % world;
   return (unsigned)(m < 0 ? m + world : m);
 }
+
+// ------------------------------------------------------------------------------------------
+// segment bounds of an ascending segment-id list, for the kernels that walk segments without an offsets pass (lsz_body,
+// kv_op_kernels.h; shard_finish_sparse_body, kv_route.h): lo(s) = lower_bound(segment_ids, s), clamped like
+// seg_offsets_body — lo(s <= 0) = 0, lo(s >= nseg) = lower_bound(nseg) — so every position is in [0, n] whatever the list
+// holds.  At most log2(n) dependent loads per bound, L2-resident after the first waves.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ int lsz_lower_bound(const void* __restrict__ seg, int seg32, int n, long long s) {
+  int a = 0, b = n;
+  while (a < b) {
+    const int m = a + ((b - a) >> 1);
+    const long long x = seg32 ? (long long)reinterpret_cast<const int*>(seg)[m] : reinterpret_cast<const long long*>(seg)[m];
+    if (x < s) a = m + 1; else b = m;
+  }
+  return a;
+}
+__device__ __forceinline__ int lsz_bound(const void* __restrict__ seg, int seg32, int n, long long nseg, long long s) {
+  return s <= 0 ? 0 : lsz_lower_bound(seg, seg32, n, s < nseg ? s : nseg);
+}

@@ -437,6 +437,10 @@ struct StageSlot {
   char* dev = nullptr;
   size_t cap = 0;
   hipEvent_t consumed = nullptr;
+  // where `consumed` was recorded, and whether the stream may not have got there yet (retire_stream clears it for a stream
+  // that was drained and is about to go away: an event is not waited on once its stream is gone)
+  hipStream_t last = nullptr;
+  bool busy = false;
 };
 struct BatchStage {       // a small ring, so the host can prepare call k+1 while call k still runs
   std::mutex mu;
@@ -462,7 +466,7 @@ class Staged {
   }
   Staged(const Staged&) = delete;
   ~Staged() {   // the slot is busy until the stream gets there
-    if (launched) hipEventRecord(sl->consumed, s);
+    if (launched) { hipEventRecord(sl->consumed, s); sl->last = s; sl->busy = true; }
     if (sl) st.mu.unlock();
   }
   Desc& operator[](int i) { return reinterpret_cast<Desc*>(sl->host)[i]; }

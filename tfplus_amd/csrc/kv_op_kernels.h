@@ -425,20 +425,8 @@ __global__ void __launch_bounds__(TB) k_seg_combine(TableDev t, WsDev w, const u
 //    there (profiles/serving_sparse.txt) the batched launch takes 2.3-3.3x the plain batched gather of the same ids: the
 //    bound search and the probe are one dependent chain per wave step.  Pipelining both across a wave's steps, as
 //    goz_wave does, is the next step for this kernel.
-// No LDS, no atomics, no float reduction across lanes.
-__device__ __forceinline__ int lsz_lower_bound(const void* __restrict__ seg, int seg32, int n, long long s) {
-  int a = 0, b = n;
-  while (a < b) {
-    const int m = a + ((b - a) >> 1);
-    const long long x = seg32 ? (long long)reinterpret_cast<const int*>(seg)[m] : reinterpret_cast<const long long*>(seg)[m];
-    if (x < s) a = m + 1; else b = m;
-  }
-  return a;
-}
-__device__ __forceinline__ int lsz_bound(const void* __restrict__ seg, int seg32, int n, long long nseg, long long s) {
-  return s <= 0 ? 0 : lsz_lower_bound(seg, seg32, n, s < nseg ? s : nseg);
-}
-
+// No LDS, no atomics, no float reduction across lanes.  (lsz_bound: kv_device.h — the sharded combining finish walks
+// its segments the same way.)
 template <int VQ>
 __device__ __forceinline__ void lsz_body(const TableDev& t, const void* __restrict__ ids, int ids32,
                                          const void* __restrict__ seg, int seg32, const float* __restrict__ wts,

@@ -1,7 +1,7 @@
 // kv_route.h — the sharded layer's own kernels (included by kv_shard.hip only, after kv_device.h): the routing rule's
 // counting sort of ids by owner rank and the fixed-capacity exchange segments (k_owner_*, k_seg_headers), and the sharded
-// lookup's output rows from the records that came back (k_shard_finish), and the owner's read-only serve of the records it
-// received (k_shard_serve_zeros).
+// lookup's output rows from the records that came back (k_shard_finish) or their combination into segments
+// (k_shard_finish_sparse), and the owner's read-only serve of the records it received (k_shard_serve_zeros).
 #pragma once
 
 // ------------------------------------------------------------------------------------------
@@ -204,6 +204,110 @@ template <int VQ, int CW = 4>
 __global__ void __launch_bounds__(TB) k_shard_finish_multi(const FinishDesc* __restrict__ descs) {
   const FinishDesc d = descs[blockIdx.y];
   shard_finish_body<VQ, CW>(d.pos_ent, d.ent_u, d.slot_of, d.rows, d.out, d.n, d.dim, d.rows_self, d.self_lo, d.self_len);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_shard_finish_sparse: the COMBINING finish (kv_shard_lookup_finish_sparse and the sparse whole ops) —
+//   out[s] = combine_j( w_j * row_j ) over the positions j of segment s, in position order,
+// row_j = the row k_shard_finish writes for position j, read where that kernel reads it.  The [n, dim] rows are never
+// written: the records' rows already sit in the receive buffer (this rank's own in the send buffer), one launch walks the
+// segments and writes [num_segments, dim] once.
+//  * the segment walk is lsz_body's (kv_op_kernels.h): a group of VQ lanes owns a segment, 64 / VQ segments per wave step,
+//    the bounds from lsz_bound (kv_device.h) by the group's lane 0, the neighbour's bound by shuffle, the wave's last bound
+//    searched beside them.  No LDS, no atomics, no float reduction across lanes; out is written once, streaming.
+//  * the row fetch is shard_finish_body's: lane u of the group resolves position pos + u (pos_ent -> 0xFFFF: record 0, else
+//    slot_of[ent_u[tile base + entry]]), records and weights go round the group by shuffle, up to 4 rows in flight per lane
+//    (float4 loads from rows, or rows_self for this rank's own in-place segment); the additions stay in position order.
+//  * VQ = row_lanes(dim): dims that are not a power of two times 4 (12, 20, 100 ...) run the next instantiation with the
+//    lanes v >= dim / 4 masked.  A masked lane still resolves its position — the chunk is VQ positions whatever the dim —
+//    and reads float4 0 of the rows it is handed; it accumulates into registers nobody stores.
+// A chunk pays four dependent loads (pos_ent -> ent_u -> slot_of -> row) where lsz_body pays three (id -> entry -> row),
+// and is not pipelined across chunks either: see DESIGN.md §4 for what was measured.
+// ------------------------------------------------------------------------------------------
+struct FinishSparseDesc {
+  FinishDesc f;          // f.out: [nseg, dim]; f.n: the routed batch's length (0: every segment is empty)
+  const void* seg;       // [n] ascending, int32 or int64
+  const float* wts;      // [n] or null
+  long long nseg;
+};
+template <int VQ>
+__device__ __forceinline__ void shard_finish_sparse_body(const FinishSparseDesc& d, int seg32, int combiner) {
+  constexpr int G = 64 / VQ;                // segments per wave and step
+  constexpr int SU = VQ < 4 ? VQ : 4;       // rows in flight per lane
+  const FinishDesc& f = d.f;
+  const void* __restrict__ seg = d.seg;
+  const float* __restrict__ wts = d.wts;
+  const unsigned short* __restrict__ pos_ent = f.pos_ent;
+  const unsigned* __restrict__ ent_u = f.ent_u;
+  const int* __restrict__ slot_of = f.slot_of;
+  const int dim = f.dim, n = (int)f.n;
+  const long long nseg = d.nseg;
+  const int lane = threadIdx.x & 63;
+  const int v = lane % VQ, sub = lane / VQ, gbase = sub * VQ;
+  const bool vlive = v < (dim >> 2);        // float4 per row <= VQ: lanes past it are masked
+  const int vv = vlive ? v : 0;
+  const long long wave = (long long)blockIdx.x * (TB / 64) + (threadIdx.x >> 6);
+  const long long nwaves = (long long)gridDim.x * (TB / 64);
+  for (long long base = wave * G; base < nseg; base += nwaves * G) {   // wave-uniform
+    const long long sgi = base + sub;
+    // the bounds: lane 0 of each group its segment's first position, the wave's last bound beside them
+    int b0 = 0, b1 = 0;
+    if (v == 0) b0 = lsz_bound(seg, seg32, n, nseg, sgi);
+    else if (VQ > 1 && lane == 64 - VQ + 1) b0 = lsz_bound(seg, seg32, n, nseg, base + G);
+    if (VQ == 1 && lane == 63) b1 = lsz_bound(seg, seg32, n, nseg, base + G);
+    const int lo = __shfl(b0, gbase);
+    const int hi_next = __shfl(b0, sub < G - 1 ? gbase + VQ : gbase);
+    const int hi_last = VQ > 1 ? __shfl(b0, 64 - VQ + 1) : __shfl(b1, 63);
+    const int hi = sub < G - 1 ? hi_next : hi_last;
+    const int len = sgi < nseg && hi > lo ? hi - lo : 0;   // (a list that is not ascending may give hi < lo: nothing is read)
+    float wsum = 0.f, w2 = 0.f;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    unsigned pos = (unsigned)lo;   // the chunk's first position; rem: the segment's positions from there on
+    for (int rem = len; __any(rem > 0); rem -= VQ, pos += VQ) {
+      // lane v: the record of position pos + v (record 0, weight 0 past the segment's end)
+      unsigned rec = 0u;
+      float wv = 0.f;
+      if (v < rem) {
+        const unsigned p = pos + v;
+        wv = wts ? wts[p] : 1.f;
+        const unsigned e = pos_ent[p];
+        if (e != 0xFFFFu) rec = (unsigned)slot_of[ent_u[(size_t)(p / TILE) * TILE + e]];
+      }
+      for (int u0 = 0; u0 < VQ && __any(u0 < rem); u0 += SU) {
+        unsigned ru[SU];
+        float wu[SU];
+        float4 x[SU];
+#pragma unroll
+        for (int u = 0; u < SU; ++u) { ru[u] = __shfl(rec, gbase + u0 + u); wu[u] = __shfl(wv, gbase + u0 + u); }
+#pragma unroll
+        for (int u = 0; u < SU; ++u)   // (records [self_lo, self_lo + self_len): this rank's own segment, read where the serve wrote it)
+          x[u] = reinterpret_cast<const float4*>(((ru[u] - f.self_lo < f.self_len) ? f.rows_self : f.rows) + (size_t)ru[u] * dim)[vv];
+#pragma unroll
+        for (int u = 0; u < SU; ++u) {
+          if (u0 + u >= rem) continue;
+          acc.x += x[u].x * wu[u]; acc.y += x[u].y * wu[u]; acc.z += x[u].z * wu[u]; acc.w += x[u].w * wu[u];
+          wsum += wu[u]; w2 += wu[u] * wu[u];
+        }
+      }
+    }
+    if (sgi >= nseg || !vlive) continue;
+    float den = 1.f;
+    if (combiner == 1) den = wsum; else if (combiner == 2) den = sqrtf(w2);
+    if (combiner != 0 && (wts || len > 0)) { acc.x /= den; acc.y /= den; acc.z /= den; acc.w /= den; }
+    float4* dst = reinterpret_cast<float4*>(f.out + (size_t)sgi * dim) + v;
+    __builtin_nontemporal_store(acc.x, &dst->x); __builtin_nontemporal_store(acc.y, &dst->y);
+    __builtin_nontemporal_store(acc.z, &dst->z); __builtin_nontemporal_store(acc.w, &dst->w);
+  }
+}
+template <int VQ>
+__global__ void __launch_bounds__(TB) k_shard_finish_sparse(FinishSparseDesc d, int seg32, int combiner) {
+  shard_finish_sparse_body<VQ>(d, seg32, combiner);
+}
+// several tables of one row geometry in one launch (blockIdx.y = table); a table's blocks past its own segments leave at once
+template <int VQ>
+__global__ void __launch_bounds__(TB) k_shard_finish_sparse_multi(const FinishSparseDesc* __restrict__ descs, int seg32, int combiner) {
+  const FinishSparseDesc d = descs[blockIdx.y];
+  shard_finish_sparse_body<VQ>(d, seg32, combiner);
 }
 
 // ------------------------------------------------------------------------------------------

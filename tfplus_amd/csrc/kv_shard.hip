@@ -2,9 +2,10 @@
 // (SURVEY.md §8e).  kv_comm_* (RCCL by dlopen, grouped send / recv; or the caller's transport), kv_shard_* (route / serve /
 // finish phases and the whole ops; the read-only lookup is the training one with another serve: serve_zeros_impl), the
 // batched kv_multi_shard_* ops, and kv_bucket_by_owner, the routing rule's stand-alone form.  The only unit that knows RCCL; its own kernels are kv_route.h's.
-// Each phase's arguments are built in one place (route_desc, presum_desc, finish_desc) for its single-table and its
-// batched launch; each whole op has one body (shards_lookup, shards_apply), of which the single forms are the one-table
-// case; segment sizes come from shard_bytes, batched groups from groups_of.
+// Each phase's arguments are built in one place (route_desc, presum_desc, finish_desc, finish_sparse_desc) for its
+// single-table and its batched launch; each whole op has one body (shards_lookup, shards_apply), of which the single forms
+// are the one-table case and the sparse lookups the ones with the combining finish (SparseArgs); segment sizes come from
+// shard_bytes, batched groups from groups_of.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -52,6 +53,7 @@ struct kv_shard {
   bool self_in_place = false;        // this rank's own segments are read from the send buffers (no device copy in the exchange)
   const kv_comm* verified = nullptr; // the communicator whose ranks were seen to agree on world / capacity / dim
   uint64_t route_token = 0;
+  bool empty_routed = false;         // the last route was of an EMPTY batch (n_last == 0, no token: shard_route_holds)
   kv_batch_token_t serve_token = 0;
   bool read_only_last = false;       // the last served batch was a read-only one (kv_shard_lookup_serve_zeros): no apply may follow it
   hipEvent_t ev_fork = nullptr, ev_done = nullptr;
@@ -320,10 +322,46 @@ static FinishDesc finish_desc(const kv_shard* sh, float* out) {
   return d;
 }
 
+// ... and of its COMBINING finish: the same rows, walked segment by segment (k_shard_finish_sparse, kv_route.h)
+static FinishSparseDesc finish_sparse_desc(const kv_shard* sh, const void* seg, const float* wts, int64_t nseg, float* out) {
+  FinishSparseDesc d{};
+  d.f = finish_desc(sh, out);
+  d.seg = seg; d.wts = wts; d.nseg = nseg;
+  return d;
+}
+
+// The segments of the sparse lookups' combining finish, per table of the call.  all: every table is combined (the single
+// forms: segment_ids may be null where the batch is empty); else seg[k] == nullptr means table k is finished plainly.
+struct SparseArgs {
+  const void* const* seg;
+  int seg_dtype;
+  const float* const* wts;   // may be null, and so may wts[k]
+  const int64_t* nseg;
+  int combiner;
+  bool all;
+  bool sparse(int k) const { return all || seg[k] != nullptr; }
+  const float* w(int k) const { return wts ? wts[k] : nullptr; }
+};
+
+// the argument errors of a combining finish over a batch of n ids (kvhip.h kv_shard_lookup_finish_sparse)
+static int sparse_finish_check(const char* what, const void* seg, int seg_dtype, int64_t n, int64_t nseg, int combiner, const float* out) {
+  if (nseg < 0 || nseg > (1ll << 31) - 2) return fail(KV_INVALID_ARGUMENT, "%s: bad num_segments", what);
+  if (nseg > 0 && (!out || (n > 0 && !seg))) return fail(KV_INVALID_ARGUMENT, "%s: segment ids / output pointer is null", what);
+  if (seg_dtype != KV_DT_INT32 && seg_dtype != KV_DT_INT64) return fail(KV_INVALID_ARGUMENT, "%s: segment ids must be int32 or int64", what);
+  if (combiner < KV_COMBINER_SUM || combiner > KV_COMBINER_SQRTN)
+    return fail(KV_INVALID_ARGUMENT, "%s: combiner must be one of 'mean', 'sqrtn' or 'sum'", what);
+  return KV_OK;
+}
+
+// the shard's route index is the one of the batch it last routed (an empty batch leaves no index and no token)
+static bool shard_route_holds(const kv_shard* sh) {
+  return sh->n_last > 0 ? sh->route->batch.holds(sh->route_token, sh->n_last) : sh->empty_routed;
+}
+
 // a route with nothing to send — an empty batch, or one that failed or was refused: void headers in the send buffer, so that
 // the peers are not left waiting
 static int shard_void_route(kv_shard* sh, hipStream_t w) {
-  sh->n_last = 0; sh->route_token = 0; sh->read_only_last = false;
+  sh->n_last = 0; sh->route_token = 0; sh->empty_routed = false; sh->read_only_last = false;
   HIP_TRY(hipMemsetAsync(sh->counts, 0, (size_t)sh->world * 8, w));
   k_seg_headers<<<1, MAXW, 0, w>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
   return KV_OK;
@@ -341,8 +379,13 @@ static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_strea
   rt->deterministic = sh->table->deterministic;   // the route index (tile pass, position order) follows the table's mode
   sh->n_last = n;
   sh->route_token = 0;
+  sh->empty_routed = false;
   sh->read_only_last = false;   // a new batch: whoever serves it says what it is
-  if (n == 0) return shard_void_route(sh, s);   // an empty batch: void headers
+  if (n == 0) {   // an empty batch: void headers
+    if ((rc = shard_void_route(sh, s))) return rc;
+    sh->empty_routed = true;
+    return KV_OK;
+  }
   if ((rc = ensure_workspace(rt, n, true, s)) || (rc = ensure_pos_ent(rt, n, s))) return rc;
   MultiDesc d{};
   route_desc(sh, n, d);
@@ -496,6 +539,7 @@ static int multi_route_impl(const kv_shard_t* shards, const int* todo, int m, co
     rt->deterministic = false;
     sh->n_last = n[todo[j]];
     sh->route_token = 0;
+    sh->empty_routed = false;
     sh->read_only_last = false;
     if ((rc = ensure_workspace(rt, sh->n_last, true, s)) || (rc = ensure_pos_ent(rt, sh->n_last, s))) return rc;
   }
@@ -547,6 +591,44 @@ static int multi_finish_impl(const kv_shard_t* shards, const int* todo, int m, f
   if ((rc = hd.upload(s, &md))) return rc;
   const dim3 grid((unsigned)nblocks(nmax, TB, 8192), (unsigned)m);
   with_lanes(row_lanes(shards[todo[0]]->table->dim), [&](auto vq) { k_shard_finish_multi<decltype(vq)::value><<<grid, TB, 0, s>>>(md); });
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
+// the COMBINING finish of the tables todo[0..m) — all of one row geometry (row_lanes(dim)), their arguments checked
+// (sparse_finish_check): 1 launch.  One table takes its descriptor by value: nothing is staged, nothing allocated.
+static int finish_sparse_impl(const char* what, const kv_shard_t* shards, const int* todo, int m, const SparseArgs& sp,
+                              float* const* outs, hipStream_t s) {
+  int rc;
+  std::vector<kv_table*> rts;
+  for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
+  MultiLock lock(rts);
+  const int q = row_lanes(shards[todo[0]]->table->dim);
+  std::vector<FinishSparseDesc> ds(m);
+  long long work = 0;   // lanes of the table with the most of them
+  for (int j = 0; j < m; ++j) {
+    const int k = todo[j];
+    kv_shard* sh = shards[k];
+    if (!shard_route_holds(sh)) return fail(KV_FAILED_PRECONDITION, "%s: finish without kv_shard_lookup_route", what);
+    if ((rc = hand_over(sh->route, s))) return rc;
+    ds[j] = finish_sparse_desc(sh, sp.seg[k], sp.w(k), sp.nseg[k], outs[k]);
+    work = std::max<long long>(work, sp.nseg[k] * q);
+  }
+  if (work == 0) return KV_OK;
+  const int seg32 = sp.seg_dtype == KV_DT_INT32, combiner = sp.combiner;
+  const unsigned gx = (unsigned)nblocks(work, TB, 8192);
+  if (m == 1) {
+    const FinishSparseDesc d = ds[0];
+    with_lanes(q, [&](auto vq) { k_shard_finish_sparse<decltype(vq)::value><<<gx, TB, 0, s>>>(d, seg32, combiner); });
+  } else {
+    Staged<FinishSparseDesc> hd(shards[todo[0]]->table->device, 1, m);
+    if (hd.rc) return hd.rc;
+    for (int j = 0; j < m; ++j) hd[j] = ds[j];
+    const FinishSparseDesc* md;
+    if ((rc = hd.upload(s, &md))) return rc;
+    const dim3 grid(gx, (unsigned)m);
+    with_lanes(q, [&](auto vq) { k_shard_finish_sparse_multi<decltype(vq)::value><<<grid, TB, 0, s>>>(md, seg32, combiner); });
+  }
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -692,8 +774,11 @@ static bool shard_owner_batchable(const kv_shard* sh) {
 // tables, exchange, serve, exchange, finish.  single: kv_shard_lookup — the phase events of kv_shard_profile are its alone.
 // read_only: kv_shard_lookup_zeros / kv_multi_shard_lookup_zeros — the same op but for the serve (serve_zeros_impl, one launch
 // per row geometry: the owners' tables are read, never written) and the profile, which does not sample it.
+// sp: the sparse lookups — the same op but for the finish of the tables sp->sparse(k), which combines the rows into segments
+// (finish_sparse_impl, one launch per row geometry; sampled as `finish`).  A table whose sparse arguments are wrong is
+// treated as one whose route failed: void headers, both exchanges, its output untouched, the error at the end.
 static int shards_lookup(const char* what, bool single, bool read_only, const kv_shard_t* shards, int ntab, kv_comm* comm, const void* const* ids,
-                         const int64_t* n, float* const* outs, int join, hipStream_t s) {
+                         const int64_t* n, float* const* outs, int join, hipStream_t s, const SparseArgs* sp = nullptr) {
   int rc;
   DeviceGuard dg(shards[0]->table->device);
   hipStream_t w = comm->stream;
@@ -714,6 +799,9 @@ static int shards_lookup(const char* what, bool single, bool read_only, const kv
   if ((rc = shard_fork(sh0, s, w))) return rc;
   FirstError note;
   std::vector<char> routed(ntab, 1), done(ntab, 0);
+  auto sparse = [&](int k) { return sp && sp->sparse(k); };
+  for (int k = 0; k < ntab; ++k)
+    if (sparse(k) && note(sparse_finish_check(what, sp->seg[k], sp->seg_dtype, n[k], sp->nseg[k], sp->combiner, outs[k]))) routed[k] = 0;
   for (int k = 0; k < ntab; ++k) shards[k]->self_in_place = shard_can_stay(shards[k]);
   const bool pm = single && !read_only && shard_prof_begin(sh0, true);
   shard_prof_mark(sh0, pm, 0, w);
@@ -722,7 +810,7 @@ static int shards_lookup(const char* what, bool single, bool read_only, const kv
     return routed[k] ? KV_OK : shard_void_route(shards[k], w);
   };
   // the tables whose route is the entry-list one go together: 2 launches for all of them
-  for (const auto& grp : groups_of(ntab, [&](int k) { return shard_batchable(shards[k], n[k]) ? 0 : -1; })) {
+  for (const auto& grp : groups_of(ntab, [&](int k) { return routed[k] && shard_batchable(shards[k], n[k]) ? 0 : -1; })) {
     const bool ok = !note(multi_route_impl(shards, grp.data(), (int)grp.size(), ids, n, w));
     for (int k : grp) { routed[k] = ok; done[k] = ok; }   // (failed: void headers below, the peers are not left waiting)
   }
@@ -785,13 +873,20 @@ static int shards_lookup(const char* what, bool single, bool read_only, const kv
   shard_prof_mark(sh0, pm, 3, w);
   if ((rc = shards_exchange(shards, ntab, comm, true, w))) return rc;
   shard_prof_mark(sh0, pm, 4, w);
-  // finish, of every table whose own route succeeded: the tables of one row geometry in one launch
+  // finish, of every table whose own route succeeded: the tables of one row geometry in one launch — the plain ones, then
+  // the combining ones (an empty batch still writes its segments)
   done.assign(ntab, 0);
-  for (const auto& grp : groups_of(ntab, [&](int k) { return routed[k] && shards[k]->n_last > 0 ? row_lanes(shards[k]->table->dim) : -1; }))
+  for (const auto& grp : groups_of(ntab, [&](int k) { return routed[k] && !sparse(k) && shards[k]->n_last > 0 ? row_lanes(shards[k]->table->dim) : -1; }))
     if (!note(multi_finish_impl(shards, grp.data(), (int)grp.size(), outs, w)))
       for (int k : grp) done[k] = 1;
   for (int k = 0; k < ntab; ++k)
-    if (routed[k] && !done[k]) note(kv_shard_lookup_finish(shards[k], outs[k], w));
+    if (routed[k] && !done[k] && !sparse(k)) note(kv_shard_lookup_finish(shards[k], outs[k], w));
+  for (const auto& grp : groups_of(ntab, [&](int k) { return routed[k] && sparse(k) && sp->nseg[k] > 0 ? row_lanes(shards[k]->table->dim) : -1; })) {
+    note(finish_sparse_impl(what, shards, grp.data(), (int)grp.size(), *sp, outs, w));
+    for (int k : grp) done[k] = 1;
+  }
+  for (int k = 0; k < ntab; ++k)
+    if (routed[k] && !done[k] && sparse(k) && sp->nseg[k] > 0) note(finish_sparse_impl(what, shards, &k, 1, *sp, outs, w));
   shard_prof_mark(sh0, pm, 5, w);
   if (pm) sh0->pend_l = true;
   if ((rc = shard_done(sh0, s, w, join))) return rc;
@@ -860,6 +955,26 @@ static int shards_apply(bool single, const kv_shard_t* shards, int ntab, kv_comm
   if ((rc = shard_done(sh0, s, w, join))) return rc;
   if (note.code) return fail(note.code, "%s (this rank's exchange was queued all the same)", note.msg.c_str());
   return KV_OK;
+}
+
+// the sparse whole ops: shards_lookup with the combining finish
+static int shard_lookup_sparse(const char* what, bool read_only, kv_shard_t sh, kv_comm_t comm, const void* ids, const void* segment_ids,
+                               int segment_dtype, const float* weights, int64_t n, int64_t num_segments, int combiner, float* out, int join,
+                               kv_stream_t stream) {
+  if (!sh || !comm || comm->world != sh->world) return fail(KV_INVALID_ARGUMENT, "%s: shard / communicator mismatch", what);
+  const SparseArgs sp{&segment_ids, segment_dtype, &weights, &num_segments, combiner, true};
+  return shards_lookup(what, true, read_only, &sh, 1, comm, &ids, &n, &out, join, (hipStream_t)stream, &sp);
+}
+
+static int multi_shard_lookup_sparse(const char* what, bool read_only, const kv_shard_t* shards, int ntab, kv_comm_t comm,
+                                     const void* const* ids, const void* const* segment_ids, int segment_dtype,
+                                     const float* const* weights, const int64_t* n, const int64_t* num_segments, int combiner,
+                                     float* const* outs, int join, kv_stream_t stream) {
+  int rc;
+  if ((rc = multi_shard_check(shards, ntab, comm, what))) return rc;
+  if (!ids || !segment_ids || !n || !num_segments || !outs) return fail(KV_INVALID_ARGUMENT, "%s: null argument list", what);
+  const SparseArgs sp{segment_ids, segment_dtype, weights, num_segments, combiner, false};
+  return shards_lookup(what, false, read_only, shards, ntab, comm, ids, n, outs, join, (hipStream_t)stream, &sp);
 }
 
 }  // namespace
@@ -1117,6 +1232,20 @@ int kv_shard_lookup_finish(kv_shard_t sh, float* out, kv_stream_t stream) {
   return KV_OK;
 }
 
+// out[s] = the combiner over segment s of w_j * (the row that came back for ids[j]), in position order.  1 launch; an empty
+// batch still writes its segments.
+int kv_shard_lookup_finish_sparse(kv_shard_t sh, const void* segment_ids, int segment_dtype, const float* weights,
+                                  int64_t num_segments, int combiner, float* out, kv_stream_t stream) {
+  if (!sh) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_finish_sparse: null shard");
+  int rc;
+  if ((rc = sparse_finish_check("kv_shard_lookup_finish_sparse", segment_ids, segment_dtype, sh->n_last, num_segments, combiner, out)))
+    return rc;
+  DeviceGuard dg(sh->table->device);
+  const SparseArgs sp{&segment_ids, segment_dtype, &weights, &num_segments, combiner, true};
+  const int one = 0;
+  return finish_sparse_impl("kv_shard_lookup_finish_sparse", &sh, &one, 1, sp, &out, (hipStream_t)stream);
+}
+
 // backward: the gradient rows of the batch just looked up are summed per distinct id straight into the records their
 // ids were sent in (the route index is still there: no ids, no sizes, no sync).  2 launches.
 int kv_shard_apply_route(kv_shard_t sh, const float* grad, kv_stream_t stream) {
@@ -1223,6 +1352,36 @@ int kv_shard_lookup(kv_shard_t sh, kv_comm_t comm, const void* ids, int64_t n, f
 int kv_shard_lookup_zeros(kv_shard_t sh, kv_comm_t comm, const void* ids, int64_t n, float* out, int join, kv_stream_t stream) {
   if (!sh || !comm || comm->world != sh->world) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_zeros: shard / communicator mismatch");
   return shards_lookup("kv_shard_lookup_zeros", true, true, &sh, 1, comm, &ids, &n, &out, join, (hipStream_t)stream);
+}
+
+int kv_shard_lookup_sparse(kv_shard_t sh, kv_comm_t comm, const void* ids, const void* segment_ids, int segment_dtype,
+                           const float* weights, int64_t n, int64_t num_segments, int combiner, float* out, int join,
+                           kv_stream_t stream) {
+  return shard_lookup_sparse("kv_shard_lookup_sparse", false, sh, comm, ids, segment_ids, segment_dtype, weights, n, num_segments, combiner,
+                             out, join, stream);
+}
+
+int kv_shard_lookup_sparse_zeros(kv_shard_t sh, kv_comm_t comm, const void* ids, const void* segment_ids, int segment_dtype,
+                                 const float* weights, int64_t n, int64_t num_segments, int combiner, float* out, int join,
+                                 kv_stream_t stream) {
+  return shard_lookup_sparse("kv_shard_lookup_sparse_zeros", true, sh, comm, ids, segment_ids, segment_dtype, weights, n, num_segments,
+                             combiner, out, join, stream);
+}
+
+int kv_multi_shard_lookup_sparse(const kv_shard_t* shards, int ntab, kv_comm_t comm, const void* const* ids,
+                                 const void* const* segment_ids, int segment_dtype, const float* const* weights,
+                                 const int64_t* n, const int64_t* num_segments, int combiner, float* const* outs,
+                                 int join, kv_stream_t stream) {
+  return multi_shard_lookup_sparse("kv_multi_shard_lookup_sparse", false, shards, ntab, comm, ids, segment_ids, segment_dtype, weights, n,
+                                   num_segments, combiner, outs, join, stream);
+}
+
+int kv_multi_shard_lookup_sparse_zeros(const kv_shard_t* shards, int ntab, kv_comm_t comm, const void* const* ids,
+                                       const void* const* segment_ids, int segment_dtype, const float* const* weights,
+                                       const int64_t* n, const int64_t* num_segments, int combiner, float* const* outs,
+                                       int join, kv_stream_t stream) {
+  return multi_shard_lookup_sparse("kv_multi_shard_lookup_sparse_zeros", true, shards, ntab, comm, ids, segment_ids, segment_dtype, weights,
+                                   n, num_segments, combiner, outs, join, stream);
 }
 
 int kv_shard_apply(kv_shard_t sh, kv_comm_t comm, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* grad,

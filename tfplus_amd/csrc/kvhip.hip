@@ -922,11 +922,20 @@ int fused_lookup_pass(kv_table* t, WsDev& wd, const PartArgs& pa, const void* id
 std::mutex g_tables_mu;
 std::unordered_set<kv_table*> g_tables;
 void retire_stream(hipStream_t dead) {   // `dead` is drained (the caller synchronised it)
-  std::lock_guard<std::mutex> l(g_tables_mu);
-  for (kv_table* t : g_tables) {
-    std::lock_guard<std::mutex> lt(t->mu);
-    if (t->has_last && t->last_stream == dead) { t->has_last = false; t->last_stream = nullptr; }
+  {
+    std::lock_guard<std::mutex> l(g_tables_mu);
+    for (kv_table* t : g_tables) {
+      std::lock_guard<std::mutex> lt(t->mu);
+      if (t->has_last && t->last_stream == dead) { t->has_last = false; t->last_stream = nullptr; }
+    }
   }
+  // ... and the staging slots whose last launch ran there have been read: their events are not waited on again
+  for (auto& dev : g_stage)
+    for (BatchStage& st : dev) {
+      std::lock_guard<std::mutex> l(st.mu);
+      for (StageSlot& sl : st.slot)
+        if (sl.busy && sl.last == dead) sl.busy = false;
+    }
 }
 
 std::atomic<uint64_t> g_serial{0};   // batch tokens
@@ -940,10 +949,12 @@ BatchStage g_stage[64][3];   // [device][0 = inference gather, 1 = training ops,
 int stage_take(BatchStage& st, size_t bytes, StageSlot** out) {
   st.mu.lock();
   StageSlot& sl = st.slot[st.cursor++ & 3u];
-  if (sl.consumed && hipEventSynchronize(sl.consumed) != hipSuccess) {
+  const hipError_t busy = sl.busy ? hipEventSynchronize(sl.consumed) : hipSuccess;
+  if (busy != hipSuccess) {
     st.mu.unlock();
-    return fail(KV_INTERNAL, "descriptor staging: event sync failed");
+    return fail(KV_INTERNAL, "descriptor staging: event sync failed (%s)", hipGetErrorString(busy));
   }
+  sl.busy = false;
   if (sl.cap < bytes) {
     if (sl.host) hipHostFree(sl.host);
     if (sl.dev) hipFree(sl.dev);

@@ -1209,6 +1209,34 @@ class KvShard(object):
     _lib.check(_lib.lib().kv_shard_apply(self.ptr, comm.ptr, int(optimizer), s0, s1, _p(g), arr, int(bool(join)), _stream(self.table)))
     self._keep_g = g
 
+  def _lookup_sparse(self, fn, comm, indices, segment_ids, weights, num_segments, combiner, join):
+    if combiner not in _COMBINERS:
+      raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+    ids = _ids(self.table, indices).reshape(-1)
+    seg, w = _sparse_args(self.table, ids.numel(), segment_ids, weights)
+    out = torch.empty((int(num_segments), self.table.dim), dtype=torch.float32, device=_dev(self.table))
+    _lib.check(fn(self.ptr, comm.ptr, _p(ids), _p(seg), _TORCH_KEY[seg.dtype], _p(w), ids.numel(), int(num_segments),
+                  _COMBINERS[combiner], _p(out), int(bool(join)), _stream(self.table)))
+    self._keep = (ids, seg, w, out)     # the shard's stream may still be reading / writing them
+    return out
+
+  def lookup_sparse(self, comm, indices, segment_ids, weights, num_segments, combiner="mean", join=True):
+    """embedding_lookup_sparse on the sharded table, training form (kvhip.h kv_shard_lookup_sparse): lookup() whose finish
+    combines the rows into segments — [num_segments, dim], the [n, dim] rows are never written.  The owners insert and count
+    as for lookup(); apply_sparse (or apply with values [n, dim]) is its backward."""
+    return self._lookup_sparse(_lib.lib().kv_shard_lookup_sparse, comm, indices, segment_ids, weights, num_segments, combiner, join)
+
+  def lookup_sparse_zeros(self, comm, indices, segment_ids, weights, num_segments, combiner="mean", join=True):
+    """The read-only form (kvhip.h kv_shard_lookup_sparse_zeros): lookup_zeros() with the combining finish."""
+    return self._lookup_sparse(_lib.lib().kv_shard_lookup_sparse_zeros, comm, indices, segment_ids, weights, num_segments, combiner,
+                               join)
+
+  def apply_sparse(self, comm, optimizer, slots, seg_grad, segment_ids, weights, num_segments, combiner, hp, join=True):
+    """The backward of lookup_sparse, a composition: kv_variable_lookup_sparse_grad on the shard's table expands the segment
+    gradients [num_segments, dim] into the values [n, dim] of the batch, apply() sums and sends them."""
+    values = kv_variable_lookup_sparse_grad(self.table, seg_grad, segment_ids, weights, num_segments, combiner)
+    self.apply(comm, optimizer, slots, values, hp, join)
+
   def join(self):
     _lib.check(_lib.lib().kv_shard_join(self.ptr, _stream(self.table)))
 
@@ -1228,6 +1256,19 @@ class KvShard(object):
   def lookup_finish(self):
     out = _gather_out(self.table, self._ids)
     _lib.check(_lib.lib().kv_shard_lookup_finish(self.ptr, _p(out), _stream(self.table)))
+    return out
+
+  def lookup_finish_sparse(self, segment_ids, weights, num_segments, combiner="mean"):
+    """The combining finish (kvhip.h kv_shard_lookup_finish_sparse), where lookup_finish stands: [num_segments, dim] from
+    the rows that came back for the batch lookup_route saw, combined per segment in position order."""
+    if combiner not in _COMBINERS:
+      raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+    routed = getattr(self, "_ids", None)   # (never routed: the library refuses; else the lists must be as long as the batch)
+    n = torch.as_tensor(segment_ids).numel() if routed is None else routed.numel()
+    seg, w = _sparse_args(self.table, n, segment_ids, weights)
+    out = torch.empty((int(num_segments), self.table.dim), dtype=torch.float32, device=_dev(self.table))
+    _lib.check(_lib.lib().kv_shard_lookup_finish_sparse(self.ptr, _p(seg), _TORCH_KEY[seg.dtype], _p(w), int(num_segments),
+                                                        _COMBINERS[combiner], _p(out), _stream(self.table)))
     return out
 
   def apply_route(self, grad):
@@ -1264,6 +1305,57 @@ def _multi_shard_lookup(fn, shards, comm, indices_list, join):
   _lib.check(fn(arr, T, comm.ptr, ip, nn, op, int(bool(join)), _stream(shards[0].table)))
   for sh, i, o in zip(shards, ids, outs):
     sh._keep = (i, o)
+  return outs
+
+
+def kv_multi_shard_lookup_sparse(shards, comm, indices_list, segment_ids_list, weights_list, num_segments_list, combiner="mean",
+                                 join=True):
+  """Sharded sparse lookup of several tables in one step, training form (kvhip.h kv_multi_shard_lookup_sparse): two grouped
+  exchanges whatever len(shards) is, one combining finish per group of tables that share a row geometry.  An entry of
+  segment_ids_list may be None: that table is looked up plainly ([n_k, dim_k]); weights_list may be None, and so may its
+  entries.  Returns one [num_segments_k, dim_k] (or [n_k, dim_k]) tensor per table."""
+  return _multi_shard_lookup_sparse(_lib.lib().kv_multi_shard_lookup_sparse, shards, comm, indices_list, segment_ids_list,
+                                    weights_list, num_segments_list, combiner, join)
+
+
+def kv_multi_shard_lookup_sparse_zeros(shards, comm, indices_list, segment_ids_list, weights_list, num_segments_list,
+                                       combiner="mean", join=True):
+  """The read-only form (kvhip.h kv_multi_shard_lookup_sparse_zeros)."""
+  return _multi_shard_lookup_sparse(_lib.lib().kv_multi_shard_lookup_sparse_zeros, shards, comm, indices_list, segment_ids_list,
+                                    weights_list, num_segments_list, combiner, join)
+
+
+def _multi_shard_lookup_sparse(fn, shards, comm, indices_list, segment_ids_list, weights_list, num_segments_list, combiner, join):
+  T = len(shards)
+  if combiner not in _COMBINERS:
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  if T < 1 or len(indices_list) != T or len(segment_ids_list) != T or len(num_segments_list) != T or \
+      (weights_list is not None and len(weights_list) != T):
+    raise _lib.InvalidArgumentError("shards, indices, segment_ids, num_segments (and weights) must be equally long, N >= 1")
+  ids, segs, ws, outs = [], [], [], []
+  for k, sh in enumerate(shards):
+    sparse = segment_ids_list[k] is not None
+    i = _ids(sh.table, indices_list[k])
+    i = i.reshape(-1) if sparse else i
+    s = w = None
+    if sparse:
+      s, w = _sparse_args(sh.table, i.numel(), segment_ids_list[k], None if weights_list is None else weights_list[k])
+      outs.append(torch.empty((int(num_segments_list[k]), sh.table.dim), dtype=torch.float32, device=_dev(sh.table)))
+    else:
+      outs.append(_gather_out(sh.table, i))
+    ids.append(i); segs.append(s); ws.append(w)
+  if len({s.dtype for s in segs if s is not None}) > 1:   # one dtype per call
+    segs = [None if s is None else s.to(torch.int64) for s in segs]
+  dts = [s.dtype for s in segs if s is not None]
+  # (a sparse table whose batch is empty still names a list: a null entry would mean a plain finish)
+  segs = [torch.zeros(1, dtype=s.dtype, device=s.device) if s is not None and s.numel() == 0 else s for s in segs]
+  arr = (ctypes.c_void_p * T)(*[sh.ptr for sh in shards])
+  nn = (ctypes.c_int64 * T)(*[i.numel() for i in ids])
+  ns = (ctypes.c_int64 * T)(*[0 if s is None else int(m) for s, m in zip(segs, num_segments_list)])
+  _lib.check(fn(arr, T, comm.ptr, _ptr_array(ids), _ptr_array(segs), _TORCH_KEY[dts[0] if dts else torch.int64], _ptr_array(ws),
+                nn, ns, _COMBINERS[combiner], _ptr_array(outs), int(bool(join)), _stream(shards[0].table)))
+  for sh, i, s, w, o in zip(shards, ids, segs, ws, outs):
+    sh._keep = (i, s, w, o)
   return outs
 
 

@@ -233,6 +233,40 @@ class ShardedKvVariable(object):
     out = _take(back, inv, self.take_fn)
     return out.reshape(tuple(ids.shape) + tuple(out.shape[1:]))
 
+  def lookup_sparse(self, ids, segment_ids, weights, num_segments, combiner="mean", training=True):
+    """embedding_lookup_sparse over the sharded table, stated in torch: lookup (training) or lookup_zeros (read-only) of
+    the ids, then the combine of python/ops/embedding_ops.py:359-441 — out[s] = the combiner over the positions j of
+    segment s, in position order, of w_j * row_j, float32; mean divides by sum w_j, sqrtn by sqrt(sum w_j^2); an empty
+    segment is a zero row without weights and 0/0 with them (mean / sqrtn); segment ids below 0 count towards segment 0,
+    ids >= num_segments towards none.  segment_ids ascending; returns [num_segments, dim].  This is the statement of the
+    semantics (CPU tests); the native form combines in the finish phase and never writes the [n, dim] rows:
+    KvShard.lookup_sparse / lookup_sparse_zeros."""
+    if combiner not in ("sum", "mean", "sqrtn"):
+      raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+    rows = self.lookup(ids) if training else self.lookup_zeros(ids)
+    n = ids.numel()
+    rows = rows.reshape(n, rows.shape[-1]).to(torch.float32)
+    seg = torch.as_tensor(segment_ids).reshape(-1).to(torch.int64).to(rows.device)
+    if seg.numel() != n:
+      raise ValueError("segment_ids and ids must have the same length")
+    w = torch.ones(n, dtype=torch.float32, device=rows.device) if weights is None else \
+        torch.as_tensor(weights, dtype=torch.float32).reshape(-1).to(rows.device)
+    if w.numel() != n:
+      raise ValueError("sp_weights and sp_ids must have the same number of values")
+    nseg = int(num_segments)
+    s = seg.clamp(min=0)
+    keep = s < nseg
+    s, x, w = s[keep], rows[keep], w[keep]
+    out = torch.zeros((nseg, rows.shape[1]), dtype=torch.float32, device=rows.device).index_add_(0, s, x * w[:, None])
+    if combiner == "sum":
+      return out
+    den = torch.zeros(nseg, dtype=torch.float32, device=rows.device).index_add_(0, s, w if combiner == "mean" else w * w)
+    if combiner == "sqrtn":
+      den = den.sqrt()
+    if weights is None:   # an empty segment stays a zero row
+      den = torch.where(torch.bincount(s, minlength=nseg) > 0, den, torch.ones_like(den))
+    return out / den[:, None]
+
   def apply_gradients(self, apply_fn, grad, ids):
     """Sends one summed gradient row per unique id to its owner; each owner runs
     apply_fn(shard, grad, ids) once — its fused dedup + segment-sum + row update."""
