@@ -9,7 +9,6 @@ import ctypes
 import functools
 import os
 import sys
-import threading
 
 import numpy as np
 import pytest
@@ -18,6 +17,9 @@ torch = pytest.importorskip("torch")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _ranks import Ranks as _Ranks  # noqa: E402  (ranks as threads, shared with tests/test_gpu_fuzz_sharded.py)
+
 DAY, THR = 20000, 3
 RTOL, ATOL = 2e-5, 2e-6
 pytestmark = pytest.mark.gpu
@@ -313,62 +315,7 @@ def test_lossy_overflow_reads_zeros_for_the_surplus_and_reports_once(ops):
   shards[1].lookup_route(torch.from_numpy(many[:0]).cuda())       # shard 1's own batch fitted: nothing to report
 
 
-# ---- cases 5 and 6: the whole ops, ranks as threads over KvCommStaged ------------------------------------------------------
-class _Ranks(object):
-  """`world` staged communicators whose callbacks move the segments between the ranks' buffers on the device (the transport
-  of test_whole_ops_with_ranks_as_threads_match_one_unsharded_table: a rank's own segment is never delivered)."""
-
-  def __init__(self, ops, world, timeout=60):
-    self.ops, self.world = ops, world
-    self.bar = threading.Barrier(world, timeout=timeout)
-    sent, vals, dev = [None] * world, [0] * world, torch.device("cuda", 0)
-
-    def make(r):
-      def exchange(send, recv, per_peer):
-        n = per_peer * world
-        sent[r] = ops.KvCommStaged.raw(send, n, dev)
-        torch.cuda.synchronize()
-        self.bar.wait()
-        dst = ops.KvCommStaged.raw(recv, n, dev)
-        for p in range(world):
-          if p == r and per_peer != 32:
-            dst[p * per_peer:(p + 1) * per_peer].fill_(0xA5)
-          else:
-            dst[p * per_peer:(p + 1) * per_peer].copy_(sent[p][r * per_peer:(r + 1) * per_peer])
-        torch.cuda.synchronize()
-        self.bar.wait()
-
-      def max_u32(v):
-        vals[r] = v
-        self.bar.wait()
-        m = max(vals)
-        self.bar.wait()
-        return m
-      return ops.KvCommStaged(0, world=world, rank=r, exchange=exchange, max_u32=max_u32)
-    self.comms = [make(r) for r in range(world)]
-
-  def run(self, fn):
-    """fn(rank, comm) on every rank at once; the results by rank"""
-    outs, errs = [None] * self.world, []
-
-    def body(r):
-      try:
-        torch.cuda.set_device(0)
-        outs[r] = fn(r, self.comms[r])
-        torch.cuda.synchronize()
-      except Exception as e:   # a rank that fails breaks the barrier: the others fail too instead of waiting
-        errs.append((r, repr(e)))
-        self.bar.abort()
-    ts = [threading.Thread(target=body, args=(r,)) for r in range(self.world)]
-    for t in ts:
-      t.start()
-    for t in ts:
-      t.join()
-    assert not errs, errs
-    self.bar.reset()
-    return outs
-
-
+# ---- cases 5 and 6: the whole ops, ranks as threads over KvCommStaged (tests/_ranks.py) -----------------------------------
 def test_whole_ops_single_and_multi_table(ops):
   """kv_shard_lookup_zeros, lossless with a capacity of 48 that must grow once, and kv_multi_shard_lookup_zeros over tables
   of dims 8, 8 and 32 (two row geometries: one grouped serve launch and one single); world 3"""
@@ -397,7 +344,7 @@ def test_whole_ops_single_and_multi_table(ops):
     for o in range(world):
       assert ops.kv_variable_frequency(tabs[t][0][o]) == int(np.sum(_owner(keys, world, rule) == o))
       assert ops.kv_variable_size_v2(tabs[t][0][o]) == int(np.sum(_owner(keys, world, rule) == o))
-  del ranks
+  ranks.close()
 
 
 def test_whole_op_at_world_one_equals_gather_or_zeros(ops):
@@ -482,7 +429,7 @@ def test_pending_batches_and_the_refused_apply(ops):
   for r in range(world):
     _check_rows(after[r], _owner_reads(ops, vars_, batches[r], world, rule), ref.gather_or_zeros(batches[r]), trained=True)
     assert np.all(np.any(after[r] != before[r], axis=1))            # every row moved (lr 0.1, gradients away from zero)
-  del ranks
+  ranks.close()
 
 
 # ---- case 7: errors ----------------------------------------------------------------------------------------------------

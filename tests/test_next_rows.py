@@ -161,6 +161,32 @@ def test_import_export_parity(ops):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("D", [8, 50])                                # the entry-list kernels and the sorted-position ones
+def test_the_lookup_after_an_import_evaluates_under_threshold(ops, D):
+  """ImportValues leaves under_threshold unevaluated (false), also on a key the blacklist inserts; the next lookup that finds
+  the key evaluates it (find_func: UpdateUnderThreshold): true for a row of zeros and for a blacklisted key.  A key no lookup
+  finds keeps the flag the import left."""
+  rng = np.random.default_rng(80 + D)
+  h, o = _pair(ops, D)
+  keys, black = np.arange(0, 40, dtype=np.int64), np.arange(100, 110, dtype=np.int64)
+  vals = rng.standard_normal((keys.size, D)).astype(np.float32)
+  vals[::3] = 0.0
+  fk = np.concatenate([keys, black])
+  fv = np.full(fk.size, (DAY << 16) | 3, np.uint32)
+  ops.kv_variable_import(h, keys, vals, black, fk, fv)
+  o.import_(keys, vals, black, fk, fv)
+  _same(ops, h, o, fk)
+  assert not any(m["under_threshold"] for m in ops.kv_get_meta(h, fk))
+  looked = np.concatenate([keys[:30], black[:6], keys[:9]])           # the rest is never looked up
+  np.testing.assert_array_equal(ops.kv_variable_gather_or_insert_v2(h, looked).cpu().numpy(), o.gather_or_insert(looked))
+  _same(ops, h, o, fk)
+  assert sum(m["under_threshold"] for m in ops.kv_get_meta(h, fk)) == 10 + 6
+  k2, _, b2, _, _ = [x.cpu().numpy() for x in ops.kv_variable_export(h, first_n=6)]
+  ok2, _, ob2, _, _ = o.export(first_n=6)
+  assert sorted(k2) == sorted(ok2) and sorted(b2) == sorted(ob2)      # the rows of zeros that were looked up are no longer exported
+
+
+@pytest.mark.gpu
 def test_I1_import_v2_known_answer_gpu(ops, golden_dir):
   """The reference's own KAT for import / export (py_ut/tests/test_kv_variable_ops.py:345-435), on the GPU
   table and against the oracle for the contents the reference does not assert."""

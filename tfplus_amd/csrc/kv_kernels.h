@@ -764,10 +764,12 @@ __device__ __forceinline__ void part_keys_body(const WsDev& w, const PartArgs& a
             *fp = (unsigned char)(any ? 0u : FLAG_UNDER);
           } else if (MODE == MODE_MARK) {
             // a key first seen by the blacklist is inserted blacklisted with under_threshold
-            // still false (EmbeddingValue(nullptr, true, 1, ...), table_manager.h:343-346)
-            if (a.mark_what == 0) *fp = (unsigned char)(isnew ? FLAG_BLACK : (FLAG_BLACK | FLAG_UNDER));
+            // still false (EmbeddingValue(nullptr, true, 1, ...), table_manager.h:343-346); the flag was never evaluated:
+            // FLAG_DIRTY, so the key's next lookup evaluates it as find_func does (kv_variable.h:320-332)
+            if (a.mark_what == 0) *fp = (unsigned char)(isnew ? (FLAG_BLACK | FLAG_DIRTY) : (FLAG_BLACK | FLAG_UNDER));
           } else if (a.is_insert == 2) {
-            if (isnew) *fp = 0;  // ImportValues does not evaluate under_threshold (dynamic_restore.hpp:183-194)
+            // ImportValues does not evaluate under_threshold (dynamic_restore.hpp:183-194): it reads false and is stale
+            if (isnew) *fp = (unsigned char)FLAG_DIRTY;
           } else if (a.is_insert == 3) {
             *fp = (unsigned char)(any ? 0u : FLAG_UNDER);  // RemoveBlacklist + UpdateUnderThreshold
           } else if (touch || isnew) {

@@ -1249,8 +1249,10 @@ int kv_shard_lookup_finish_sparse(kv_shard_t sh, const void* segment_ids, int se
 // backward: the gradient rows of the batch just looked up are summed per distinct id straight into the records their
 // ids were sent in (the route index is still there: no ids, no sizes, no sync).  2 launches.
 int kv_shard_apply_route(kv_shard_t sh, const float* grad, kv_stream_t stream) {
-  if (!sh || (sh->n_last > 0 && !grad)) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_route: grad pointer is null");
+  if (!sh) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_route: null shard");
+  // (the refusal first: n_last is the read-only batch's, and a rank whose voided training batch was empty has no gradient to name)
   { int rc; if ((rc = shard_refuse_apply(sh, "kv_shard_apply_route"))) return rc; }
+  if (sh->n_last > 0 && !grad) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_route: grad pointer is null");
   if (sh->n_last == 0) return KV_OK;
   DeviceGuard dg(sh->table->device);
   kv_table* rt = sh->route;
