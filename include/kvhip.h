@@ -129,6 +129,21 @@ int kv_sum_freq(kv_handle_t h, int64_t* out, kv_stream_t stream);
 int kv_get_meta(kv_handle_t h, const int64_t* ids, int64_t n, uint32_t* freq_words, uint8_t* flags,
                 kv_stream_t stream);
 
+/* ---- batch lengths --------------------------------------------------------------------------
+ * One index pass takes 2^23 ids on a table whose dim the entry-list kernels serve (the multiples of 4 up to 256) and
+ * 2^21 ids on a table of any other dim.  What a longer call does depends on the op:
+ *   kv_gather_or_insert[_tok|_pairs]            up to 2^30 ids, looked up pass by pass with the result of one pass (the
+ *                                               frequency adds saturate alike, a key is inserted by the first pass that
+ *                                               meets it); *token stays 0 when more than one pass was needed
+ *   kv_insert, kv_scatter_update, kv_import,    any length, in chunks of 2^21 ids; a folding update's later chunk meets
+ *   kv_import_delta                             the row the earlier chunk left
+ *   kv_gather_or_zeros, kv_batch_gather_or_zeros, kv_get_count, kv_get_timestamp, kv_export_*: any length
+ *   kv_apply_* (single-table forms), kv_dedup_segment_sum[_dev], kv_unsorted_segment_sum: one pass at the most, and
+ *   kv_unique (2^23 ids at every dim)           a longer call returns KV_UNIMPLEMENTED before anything is queued
+ *   kv_lookup_sparse, kv_lookup_sparse_grad and every kv_multi_* op: one pass at the most per table, a longer list
+ *                                               returns KV_INVALID_ARGUMENT before anything is queued
+ * Row buffers (out, grad, values, summed) may hold 2^31 elements and more: rows are addressed in 64 bits throughout. */
+
 /* ---- lookup (HOT LOOP 1) ------------------------------------------------------------------ */
 
 /* Replaces KvVariableGatherOrInsertOp / ...WithCountsOp::Compute
@@ -147,9 +162,10 @@ int kv_gather_or_insert(kv_handle_t h, const void* ids, const int32_t* counts, i
 int kv_gather_or_insert_pairs(kv_handle_t h, const int64_t* id_count_pairs, int64_t n, float* out,
                               kv_stream_t stream);
 
-/* The same lookup, additionally naming the batch: *token (never 0 on success for n <= 2^21) identifies the
- * index of `ids` that the lookup leaves in the table's workspace — the input positions sorted by key, each
- * key's row.  A kv_apply_*_tok call on the same table with the same ids, n and token takes that index over
+/* The same lookup, additionally naming the batch: *token (never 0 on success when one index pass
+ * takes n: see "batch lengths") identifies the index of `ids` that the lookup leaves in the table's
+ * workspace — the input positions sorted by key, each key's row.  A kv_apply_*_tok call on the same
+ * table with the same ids, n and token takes that index over
  * instead of rebuilding it (a training step applies the ids it has just looked up: the TF shim threads the
  * token from the forward op to the optimizer op).  Any other batch op on the table in between simply makes
  * the token stale; a stale or zero token means "build the index", never a wrong result.  The caller
