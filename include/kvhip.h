@@ -946,6 +946,50 @@ int kv_multi_shard_lookup_sparse_zeros(const kv_shard_t* shards, int ntab, kv_co
 int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int optimizer, const kv_handle_t* slot0,
                          const kv_handle_t* slot1, const float* const* grads, const float* hp, int join,
                          kv_stream_t stream);
+/* The backward of the sharded sparse lookup, fused: the gradient pre-sum takes the SEGMENT gradients [num_segments, dim].
+ * The composition — kv_lookup_sparse_grad expands them into [n, dim] values, kv_shard_apply_route reads those back to sum
+ * them per distinct id — writes and reads n * dim * 4 bytes that carry no information; here the two sum launches fetch a
+ * position's row from the segment gradients themselves, through per-position records (segment, scale: 8 bytes a position)
+ * that a small pre-pass leaves in the route table's workspace.
+ *   kv_shard_apply_route_sparse   the phase, for a caller with its own exchange: it stands where kv_shard_apply_route stands,
+ *                                 with its preconditions and codes (the refusal after a read-only lookup, the route token of
+ *                                 the batch last routed); n is that batch's length, as in kv_shard_lookup_finish_sparse.  It
+ *                                 writes what kv_shard_apply_route writes: the per-distinct-id sums in send_rows, in the
+ *                                 records the ids were sent in.  seg_grad [num_segments, dim], segment_ids [n] int32 or
+ *                                 int64, weights [n] or NULL.  n == 0: a no-op, KV_OK.
+ *   kv_shard_apply_sparse         kv_shard_apply with that pre-sum.  The exchange, the owner's kv_shard_apply_serve, the
+ *                                 fork / join and the late overflow report are kv_shard_apply's; kv_shard_profile samples the
+ *                                 pre-sum as phase 5 (presum).
+ *   kv_multi_shard_apply_sparse   kv_multi_shard_apply where, for a table k with segment_ids[k] != NULL, grads[k] holds that
+ *                                 table's segment gradients [num_segments[k], dim_k]; a table with segment_ids[k] == NULL
+ *                                 passes plain [n_k, dim_k] values — the mixed form of kv_multi_shard_lookup_sparse.  One
+ *                                 exchange per apply whatever the mix; one segment dtype and one combiner per call; weights
+ *                                 may be NULL, and so may weights[k].
+ * Result: the record of a distinct id receives the sum, over the id's positions j, of term_j = fl(scale_j * seg_grad[s_j, :]),
+ * with s_j and scale_j exactly kv_lookup_sparse_grad's — the segment id clamped into [0, num_segments), the denominator summed
+ * in float32 from +0 in position order, the scale one IEEE division, each element one multiply (rounded before any add: no
+ * contraction) — so each term is bit for bit the row the expansion would have written.  The terms are added in the order
+ * kv_shard_apply_route adds rows: the same row lists, entries, partitions and source lists drive it.  In deterministic mode
+ * send_rows is therefore bit for bit what kv_lookup_sparse_grad + kv_shard_apply_route leave; in the default mode it is the
+ * same multiset of terms per id, in whatever order the source filing gives.  Rows of seg_grad that belong to empty segments
+ * are never read; zero denominators give what IEEE gives; the surplus ids of an overflowing segment (lossy mode) and void
+ * entries are treated as kv_shard_apply_route treats them.
+ * Checks, in this order, the phase form's all before anything is queued: a null shard; kv_shard_apply_route's refusals;
+ * KV_INVALID_ARGUMENT for a null seg_grad or segment_ids (n > 0), a segment dtype other than int32 / int64, a combiner
+ * outside 0 .. 2, num_segments outside [1, 2^31 - 2] (n > 0: there is no gradient to expand).  The whole ops treat a failed
+ * sparse pre-sum like any failed pre-sum: zero rows go out, the rank takes part in the exchange, the first error is returned
+ * at the end.
+ * Stream capture: the position records and the segment offsets live in the route table's workspace; a call that would have
+ * to grow a buffer is refused (KV_FAILED_PRECONDITION) before anything is queued — run the shapes once outside the capture. */
+int kv_shard_apply_route_sparse(kv_shard_t shard, const float* seg_grad, const void* segment_ids, int segment_dtype,
+                                const float* weights, int64_t num_segments, int combiner, kv_stream_t stream);
+int kv_shard_apply_sparse(kv_shard_t shard, kv_comm_t comm, int optimizer, kv_handle_t slot0, kv_handle_t slot1,
+                          const float* seg_grad, const void* segment_ids, int segment_dtype, const float* weights,
+                          int64_t num_segments, int combiner, const float* hp, int join, kv_stream_t stream);
+int kv_multi_shard_apply_sparse(const kv_shard_t* shards, int ntab, kv_comm_t comm, int optimizer,
+                                const kv_handle_t* slot0, const kv_handle_t* slot1, const float* const* grads,
+                                const void* const* segment_ids, int segment_dtype, const float* const* weights,
+                                const int64_t* num_segments, int combiner, const float* hp, int join, kv_stream_t stream);
 /* the exchange between shards of ONE process on one device (segment r of shard p's send buffer -> segment p of
  * shard r's receive buffer; what: 0 records, 1 rows): several ranks on a single GPU, where RCCL cannot be used */
 int kv_shard_exchange_local(const kv_shard_t* shards, int world, int what, kv_stream_t stream);

@@ -102,6 +102,11 @@ SIGNATURES = {
                                            _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _i32, _c.POINTER(_vp), _i32, _vp]),
     "kv_multi_shard_apply": (_i32, [_c.POINTER(_vp), _i32, _vp, _i32, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp),
                              _c.POINTER(_f), _i32, _vp]),
+    "kv_shard_apply_route_sparse": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp]),
+    "kv_shard_apply_sparse": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _c.POINTER(_f), _i32, _vp]),
+    "kv_multi_shard_apply_sparse": (_i32, [_c.POINTER(_vp), _i32, _vp, _i32, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp),
+                                    _c.POINTER(_vp), _i32, _c.POINTER(_vp), _c.POINTER(_c.c_int64), _i32, _c.POINTER(_f), _i32,
+                                    _vp]),
     "kv_shard_join": (_i32, [_vp, _vp]),
     "kv_shard_exchange_local": (_i32, [_c.POINTER(_vp), _i32, _i32, _vp]),
     "kv_get_count": (_i32, [_vp, _vp, _i64, _vp, _vp]),

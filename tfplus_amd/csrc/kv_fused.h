@@ -803,9 +803,13 @@ constexpr int TBC = TBT;
 static_assert(TBC == TBT, "k_ltsum: the tile pass and the tile sums share one block");
 // FROM_LDS: the tile's mrow image is read from LDS at mrow_l — the tile pass's own image (k_ltsum: LtSmem::mr), or the
 // copy k_tsum stages while the count is still on its way (one round trip in front of the rows instead of two); mc_l = mcount[tile]
-template <int V, int LPR, int K, bool FROM_LDS = false>
+// SEG: the row of a position comes from the segments' gradients (kv_types.h SegSrc; k_tsum_seg, the sharded sparse apply):
+// sg.pscale[p] * sg.seg_grad[sg.pseg[p], :], each element one multiply — `grad` is not read.  The position records of the
+// next step are requested with its mrow words, behind this step's rows; the rows themselves are re-read by neighbouring
+// positions, so they are ordinary cached loads.  (The route table has no self range.)
+template <int V, int LPR, int K, bool FROM_LDS = false, bool SEG = false>
 __device__ __forceinline__ void tsum_body(const WsDev& w, const float* __restrict__ grad, int D, unsigned tile,
-                                          const unsigned* mrow_l = nullptr, unsigned mc_l = 0u) {
+                                          const unsigned* mrow_l = nullptr, unsigned mc_l = 0u, const SegSrc sg = SegSrc{}) {
   constexpr int G = 64 / LPR;
   constexpr int RB = (8 / K) > 0 ? (8 / K) : 1;
   constexpr int RS = G * RB;            // rows per wave and step
@@ -851,16 +855,39 @@ __device__ __forceinline__ void tsum_body(const WsDev& w, const float* __restric
       if constexpr (FROM_LDS) m[i] = mrow_l[rc]; else m[i] = mrow_g[rc];
     }
   };
-  if (r0 < r1) ldm(r0, mw);
+  int pw[SEG ? RB : 1], pn[SEG ? RB : 1];       // SEG: the rows' segments and scales, a step ahead like their mrow words
+  float sw[SEG ? RB : 1], sn[SEG ? RB : 1];
+  auto ldrec = [&](const unsigned (&m)[RB], int (&ps)[SEG ? RB : 1], float (&sc)[SEG ? RB : 1]) {
+    if constexpr (SEG) {
+#pragma unroll
+      for (int i = 0; i < RB; ++i) { const unsigned p = tbase + (m[i] & 0x7FFu); ps[i] = sg.pseg[p]; sc[i] = sg.pscale[p]; }
+    }
+  };
+  if (r0 < r1) { ldm(r0, mw); ldrec(mw, pw, sw); }
   for (unsigned rb = r0; rb < r1; rb += RS) {   // wave-uniform
     float val[RB][K][V];
 #pragma unroll
     for (int i = 0; i < RB; ++i) {
-      const float* src = ((tbase + (mw[i] & 0x7FFu) - w.self_lo < w.self_len) ? g0s : g0) + (size_t)(mw[i] & 0x7FFu) * D;
+      if constexpr (SEG) {
+        const float* src = sg.seg_grad + (size_t)pw[i] * D;
 #pragma unroll
-      for (int k = 0; k < K; ++k) ldv_stream<V>(src + eoff[k], val[i][k]);
+        for (int k = 0; k < K; ++k) ldv<V>(src + eoff[k], val[i][k]);
+      } else {
+        const float* src = ((tbase + (mw[i] & 0x7FFu) - w.self_lo < w.self_len) ? g0s : g0) + (size_t)(mw[i] & 0x7FFu) * D;
+#pragma unroll
+        for (int k = 0; k < K; ++k) ldv_stream<V>(src + eoff[k], val[i][k]);
+      }
     }
     ldm(rb + RS, mn);
+    if constexpr (SEG) {
+      ldrec(mn, pn, sn);
+#pragma unroll
+      for (int i = 0; i < RB; ++i)
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+          for (int cc = 0; cc < V; ++cc) val[i][k][cc] *= sw[i];
+    }
     // ---- inside the group: runs in row order ----
     float acc[K][V], pfx[K][V];
 #pragma unroll
@@ -976,6 +1003,10 @@ __device__ __forceinline__ void tsum_body(const WsDev& w, const float* __restric
     }
 #pragma unroll
     for (int i = 0; i < RB; ++i) mw[i] = mn[i];
+    if constexpr (SEG) {
+#pragma unroll
+      for (int i = 0; i < RB; ++i) { pw[i] = pn[i]; sw[i] = sn[i]; }
+    }
   }
   // ---- the wave's ends meet in LDS ----
   if (g == 0) {
@@ -1085,4 +1116,36 @@ __global__ void __launch_bounds__(TBC) k_tsum_multi(const MultiDesc* __restrict_
   if (*reinterpret_cast<volatile unsigned*>(&m.a.tv.counters[1])) return;
   if (blockIdx.x >= m.w.ntiles) return;
   tsum_body<V, LPR, K>(m.w, m.a.grad, m.a.tv.dim, blockIdx.x);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_tsum_seg / k_tsum_seg_multi: the tile sums where the gradient arrives per segment (kv_sums_seg.hip)
+// ------------------------------------------------------------------------------------------
+// k_tsum with the row fetch replaced (tsum_body<SEG>); both forms stage the tile's mrow image in LDS, so that the position
+// records of the next step hang off an LDS read, not off a second global round trip.
+template <int V, int LPR, int K>
+__global__ void __launch_bounds__(TBC) k_tsum_seg(TableDev t, WsDev w, SegSrc sg) {
+  if (*reinterpret_cast<volatile unsigned*>(&t.counters[1])) return;   // the index pass gave up on this batch
+  extern __shared__ __attribute__((aligned(16))) char ts_smem_raw[];
+  const unsigned tile = blockIdx.x;
+  const uint4 img = reinterpret_cast<const uint4*>(w.mrow + (size_t)tile * TILE)[threadIdx.x];
+  const unsigned mc = w.mcount[tile];
+  reinterpret_cast<uint4*>(ts_smem_raw)[threadIdx.x] = img;
+  __syncthreads();
+  tsum_body<V, LPR, K, true, true>(w, nullptr, t.dim, tile, reinterpret_cast<const unsigned*>(ts_smem_raw), mc, sg);
+}
+template <int V, int LPR, int K>
+__global__ void __launch_bounds__(TBC) k_tsum_seg_multi(const MultiDesc* __restrict__ descs, const SegDesc* __restrict__ segs) {
+  const MultiDesc& m = descs[blockIdx.y];
+  if (m.n == 0) return;
+  if (*reinterpret_cast<volatile unsigned*>(&m.a.tv.counters[1])) return;
+  if (blockIdx.x >= m.w.ntiles) return;
+  extern __shared__ __attribute__((aligned(16))) char ts_smem_raw[];
+  const unsigned tile = blockIdx.x;
+  const uint4 img = reinterpret_cast<const uint4*>(m.w.mrow + (size_t)tile * TILE)[threadIdx.x];
+  const unsigned mc = m.w.mcount[tile];
+  reinterpret_cast<uint4*>(ts_smem_raw)[threadIdx.x] = img;
+  __syncthreads();
+  tsum_body<V, LPR, K, true, true>(m.w, nullptr, m.a.tv.dim, tile, reinterpret_cast<const unsigned*>(ts_smem_raw), mc,
+                                   segs[blockIdx.y].src);
 }

@@ -77,6 +77,9 @@ struct Workspace {
   long long seg_cap = 0;
   float* seg_den = nullptr;      // kv_lookup_sparse_grad: the segments' denominators [den_cap]
   long long den_cap = 0;
+  int* pseg = nullptr;           // sharded sparse apply (a route table): every position's clamped segment [prec_cap]
+  float* pscale = nullptr;       // ... and its scale [prec_cap]
+  long long prec_cap = 0;
   unsigned long long* dbg = nullptr;
 };
 
@@ -263,6 +266,13 @@ int ensure_capacity(kv_table* t, long long extra, hipStream_t s);
 int ensure_free_list(kv_table* t, hipStream_t s);   // the free-list stack holds every row of the slab (before a kernel that releases rows)
 int ensure_workspace(kv_table* t, long long n, bool need_part, hipStream_t s);
 int ensure_pos_ent(kv_table* t, long long n, hipStream_t s);
+int ensure_pos_records(kv_table* t, long long n, hipStream_t s);   // Workspace::pseg / pscale hold n positions
+// kv_ops.hip: Workspace::seg_off holds num_segments + 1 offsets and, need_den, Workspace::seg_den num_segments denominators
+int ensure_seg(kv_table* t, long long num_segments, bool need_den, hipStream_t s);
+// kv_ops.hip: the position records of the sharded sparse apply (kv_types.h SegDesc; kv_lookup_sparse_grad's offsets,
+// denominators and scales, per position instead of per values row).  m tables; m > 1: `dev` is the staged copy of `host`.
+// At most 3 launches whatever m is.
+int launch_pos_records(int m, const SegDesc* host, const SegDesc* dev, int seg32, int combiner, hipStream_t s);
 unsigned fused_default_P(long long n);
 size_t chunk_cap(long long n);
 
@@ -452,7 +462,7 @@ int stage_take(BatchStage& st, size_t bytes, StageSlot** out);   // the ring's n
 // `count` descriptors of a batched launch on g_stage[device][ring]: zeroed host descriptors by index, then ONE upload,
 // which is the only way to the device pointer — so a slot a kernel may still read is always marked busy.  The ring stays
 // locked until scope exit.  Check rc before anything else.
-template <class Desc>   // MultiDesc, FinishDesc, BatchGatherDesc, SparseDesc
+template <class Desc>   // MultiDesc, FinishDesc, BatchGatherDesc, SparseDesc, SegDesc
 class Staged {
   BatchStage& st;
   StageSlot* sl = nullptr;

@@ -1,5 +1,6 @@
 // kv_launch.h — the launchers kvhip.hip, kv_ops.hip and kv_apply.hip call and the translation unit that defines each.  The optimizer apply kernels are
-// instantiated once per OPT_*, in kv_opt_<name>.hip (kv_opt_unit.h); the optimizer-free sums in kv_sums.hip.  A launcher
+// instantiated once per OPT_*, in kv_opt_<name>.hip (kv_opt_unit.h); the optimizer-free sums in kv_sums.hip and, where the
+// gradient arrives per segment, kv_sums_seg.hip.  A launcher
 // dispatches on the row geometry — the one table of kv_row_geom.h, through with_row_geom — and returns KV_OK, or
 // KV_UNIMPLEMENTED for a dim its kernels do not serve.
 // md != nullptr: `ntab` tables in one launch (wd / n: the largest table's; pa: the first table's, only its dim is read).
@@ -52,5 +53,13 @@ int launch_papply_ud(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t 
 // k_apply / k_apply_fin in MODE_DEDUP: the plain segment fold (sorted positions), as launch_sorted_apply; no md form
 int launch_dedup_fold(const WsDev& wd, const PartArgs& pa, hipStream_t s, const MultiDesc* md, int ntab, unsigned nchunks,
                       int span);
+
+// ---- optimizer-free, the gradient per segment (kv_sums_seg.hip; kv_types.h SegSrc) ---------------------------------------
+// k_tsum_seg / k_papply_dedup_seg: launch_tsum and launch_papply_ud's PA_DEDUP where the row of a position is
+// sg.pscale[p] * sg.seg_grad[sg.pseg[p], :].  md != nullptr: sd is the tables' SegDesc array next to it (sg is not read)
+int launch_tsum_seg(const TableDev& td, const WsDev& wd, const SegSrc& sg, hipStream_t s, const MultiDesc* md = nullptr,
+                    const SegDesc* sd = nullptr, int ntab = 0);
+int launch_papply_dedup_seg(const WsDev& wd, const PartArgs& pa, const SegSrc& sg, hipStream_t s, const MultiDesc* md = nullptr,
+                            const SegDesc* sd = nullptr, int ntab = 0);
 
 }  // namespace kvhip_internal

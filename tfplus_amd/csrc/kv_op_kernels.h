@@ -783,3 +783,40 @@ __global__ void __launch_bounds__(TB) k_seg_expand_multi(const SparseDesc* __res
   seg_expand_body<SegT, VQ>(d.seg_grad, reinterpret_cast<const SegT*>(d.seg), d.off, d.den, d.wts, d.n, d.nseg, D, combiner,
                             d.out);
 }
+
+// ---------------------------------------------------------------------------------------------
+// The position records of the sharded sparse apply (kv_types.h SegSrc / SegDesc; kv_sums_seg.hip sums from them): what
+// k_seg_expand computes per values row, kept per POSITION instead — pseg[j] = the clamped segment (seg_of), pscale[j] =
+// seg_scale(j).  The offsets and denominators in front of it are the backward's own bodies, so a scale is the same bits as
+// the one kv_lookup_sparse_grad multiplies by.  The batched forms read a SegDesc array (blockIdx.y = table; n == 0: no part).
+template <typename SegT>
+__device__ __forceinline__ void pos_records_body(const SegT* __restrict__ seg, const unsigned* __restrict__ off,
+                                                 const float* __restrict__ den, const float* __restrict__ wts, long long n,
+                                                 long long nseg, int combiner, int* __restrict__ pseg, float* __restrict__ pscale) {
+  for (long long j = (long long)blockIdx.x * TB + threadIdx.x; j < n; j += (long long)gridDim.x * TB) {
+    const long long sg = seg_of(seg, j, nseg);
+    pseg[j] = (int)sg;
+    pscale[j] = seg_scale(off, den, wts, j, sg, combiner);
+  }
+}
+template <typename SegT>
+__global__ void __launch_bounds__(TB) k_pos_records(SegDesc d, int combiner) {
+  pos_records_body(reinterpret_cast<const SegT*>(d.seg), d.off, d.den, d.wts, d.n, d.nseg, combiner, d.pseg, d.pscale);
+}
+template <typename SegT>
+__global__ void __launch_bounds__(TB) k_pos_offsets_multi(const SegDesc* __restrict__ descs) {
+  const SegDesc& d = descs[blockIdx.y];
+  if (d.n == 0) return;
+  seg_offsets_body(reinterpret_cast<const SegT*>(d.seg), d.n, d.nseg, d.off);
+}
+__global__ void __launch_bounds__(TB) k_pos_den_multi(const SegDesc* __restrict__ descs, int combiner) {
+  const SegDesc& d = descs[blockIdx.y];
+  if (d.n == 0 || !d.den) return;   // (den: named where the table has weights and the combiner divides)
+  seg_den_body(d.off, d.wts, d.nseg, combiner, d.den);
+}
+template <typename SegT>
+__global__ void __launch_bounds__(TB) k_pos_records_multi(const SegDesc* __restrict__ descs, int combiner) {
+  const SegDesc& d = descs[blockIdx.y];
+  if (d.n == 0) return;
+  pos_records_body(reinterpret_cast<const SegT*>(d.seg), d.off, d.den, d.wts, d.n, d.nseg, combiner, d.pseg, d.pscale);
+}

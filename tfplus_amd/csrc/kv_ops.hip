@@ -302,28 +302,6 @@ static int ensure_init_placeholder(kv_table* t, hipStream_t s) {
 }
 
 
-// the sparse lookups' segment buffers: Workspace::seg_off holds num_segments + 1 offsets and, need_den, Workspace::seg_den
-// num_segments denominators (grown behind ws_sync like the rest of the workspace)
-static int ensure_seg(kv_table* t, long long num_segments, bool need_den, hipStream_t s) {
-  int rc;
-  Workspace& ws = t->ws;
-  if (ws.seg_cap < num_segments) {
-    if ((rc = ws_sync(s))) return rc;
-    const long long want = std::max<long long>(num_segments, ws.seg_cap * 2);
-    ws.seg_cap = 0;
-    if ((rc = regrow(&ws.seg_off, (size_t)(want + 1)))) return rc;
-    ws.seg_cap = want;
-  }
-  if (need_den && ws.den_cap < num_segments) {
-    if ((rc = ws_sync(s))) return rc;
-    const long long want = std::max<long long>(num_segments, ws.den_cap * 2);
-    ws.den_cap = 0;
-    if ((rc = regrow(&ws.seg_den, (size_t)want))) return rc;
-    ws.den_cap = want;
-  }
-  return KV_OK;
-}
-
 // the argument checks kv_lookup_sparse, its backward and their batched forms share
 static int sparse_call_checks(int combiner, int segment_dtype) {
   if (combiner < KV_COMBINER_SUM || combiner > KV_COMBINER_SQRTN)
@@ -479,6 +457,59 @@ static int sparse_zeros_lanes(int D) { return pow2_vectors(D, 64); }
 }  // namespace
 
 namespace __attribute__((visibility("hidden"))) kvhip_internal {
+
+// the sparse lookups' segment buffers: Workspace::seg_off holds num_segments + 1 offsets and, need_den, Workspace::seg_den
+// num_segments denominators (grown behind ws_sync like the rest of the workspace)
+int ensure_seg(kv_table* t, long long num_segments, bool need_den, hipStream_t s) {
+  int rc;
+  Workspace& ws = t->ws;
+  if (ws.seg_cap < num_segments) {
+    if ((rc = ws_sync(s))) return rc;
+    const long long want = std::max<long long>(num_segments, ws.seg_cap * 2);
+    ws.seg_cap = 0;
+    if ((rc = regrow(&ws.seg_off, (size_t)(want + 1)))) return rc;
+    ws.seg_cap = want;
+  }
+  if (need_den && ws.den_cap < num_segments) {
+    if ((rc = ws_sync(s))) return rc;
+    const long long want = std::max<long long>(num_segments, ws.den_cap * 2);
+    ws.den_cap = 0;
+    if ((rc = regrow(&ws.seg_den, (size_t)want))) return rc;
+    ws.den_cap = want;
+  }
+  return KV_OK;
+}
+
+// the position records of the sharded sparse apply (kv_host.h; the kernels: kv_op_kernels.h).  The tables' buffers are
+// sized by the caller (ensure_seg, ensure_pos_records); a descriptor with n == 0 takes no part.
+int launch_pos_records(int m, const SegDesc* host, const SegDesc* dev, int seg32, int combiner, hipStream_t s) {
+  long long nmax = 0, segmax = 0;
+  bool any_den = false;
+  for (int j = 0; j < m; ++j) {
+    if (host[j].n == 0) continue;
+    nmax = std::max(nmax, host[j].n);
+    segmax = std::max(segmax, host[j].nseg);
+    any_den |= host[j].den != nullptr;
+  }
+  if (nmax == 0) return KV_OK;
+  const unsigned go = (unsigned)nblocks(nmax + 1, TB, 2048), gd = (unsigned)nblocks(segmax, TB, 4096), gr = (unsigned)nblocks(nmax, TB, 2048);
+  with_id_type(seg32 != 0, [&](auto id) {
+    using IDT = decltype(id);
+    if (m == 1) {
+      const SegDesc d = host[0];
+      k_seg_offsets<IDT><<<go, TB, 0, s>>>((const IDT*)d.seg, d.n, d.nseg, d.off);
+      if (any_den) k_seg_den<<<gd, TB, 0, s>>>(d.off, d.wts, d.nseg, combiner, d.den);
+      k_pos_records<IDT><<<gr, TB, 0, s>>>(d, combiner);
+    } else {
+      k_pos_offsets_multi<IDT><<<dim3(go, (unsigned)m), TB, 0, s>>>(dev);
+      if (any_den) k_pos_den_multi<<<dim3(gd, (unsigned)m), TB, 0, s>>>(dev, combiner);
+      k_pos_records_multi<IDT><<<dim3(gr, (unsigned)m), TB, 0, s>>>(dev, combiner);
+    }
+  });
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
 // ---- many tables, one launch per pipeline stage (26-feature CTR step: 5 launches, not 130) ------
 // All tables: same device, same dim, same key dtype; each batch <= 2^21 ids.
 int multi_common(int num_tables, const kv_handle_t* tables, const void* const* ids, const int64_t* ns) {

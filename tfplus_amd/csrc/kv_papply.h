@@ -48,8 +48,12 @@ template <int TBP> struct PaShape { static constexpr int HSK = TBP >= 512 ? 2048
 // FM: the mode when the kernel is compiled for one — PA_UNIQUE (k_papply_uniq: numbering only, no row geometry, none of
 // the apply's registers) and PA_DEDUP (k_papply_dedup: sources summed and stored, no state, no optimizer) have their own
 // kernels and the kernels of the table modes carry none of their code; -1: PA_LOOKUP / PA_APPLYIDX / PA_NONE, an argument
-template <int OPT, int V, int LPR, int K, int TBP, int FM = -1>
-__device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, const int mode_) {
+// SEG (PA_DEDUP only; k_papply_dedup_seg, the sharded sparse apply): a source that is an input position p is the row
+// sg.pscale[p] * sg.seg_grad[sg.pseg[p], :] (kv_types.h SegSrc), each element one multiply; a source tagged EP_TAG is a tile
+// sum in epart, as ever.  a.grad is not read.
+template <int OPT, int V, int LPR, int K, int TBP, int FM = -1, bool SEG = false>
+__device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, const int mode_, const SegSrc sg = SegSrc{}) {
+  static_assert(!SEG || FM == PA_DEDUP, "the segment source serves the gradient pre-sum alone");
   constexpr bool UQ = FM == PA_UNIQUE, DN = FM == PA_DEDUP_NUM, DD = FM == PA_DEDUP || DN;
   const int mode = FM >= 0 ? (DN ? (int)PA_DEDUP : FM) : (mode_ & 0xFF);
   constexpr int HSK = PaShape<TBP>::HSK;
@@ -355,11 +359,33 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
       for (int k = 0; k < K; ++k) { eo[k] = eoff[k]; asm volatile("" : "+v"(eo[k])); }
       int lane_i = lane;   // (opt_core / finish_key / prefetch_state derive their own offsets from the lane: the same move)
       asm volatile("" : "+v"(lane_i));
-      auto load_row = [&](unsigned pos, float (&dst)[K][V]) {
-        const float* base = (pos & EP_TAG) ? ebase : (pos - w.self_lo < w.self_len) ? gself : gbase;
-        const float* src = base + (size_t)(pos & ~EP_TAG) * D;
+      // SEG: the position records of a batch of sources are requested together (load_rec), then their rows (load_row): one
+      // round trip more than the plain form in front of a key's first rows, none per source
+      struct Rec { int ps; float sc; };
+      auto load_rec = [&](unsigned pos) -> Rec {
+        Rec r{0, 1.f};
+        if constexpr (SEG) {
+          const unsigned ix = (pos & EP_TAG) ? 0u : pos;   // (a tile sum has no record: position 0's is read and not used)
+          r.ps = sg.pseg[ix]; r.sc = sg.pscale[ix];
+        }
+        return r;
+      };
+      auto load_row = [&](unsigned pos, float (&dst)[K][V], const Rec rec = Rec{0, 1.f}) {
+        if constexpr (SEG) {
+          const bool tsum = (pos & EP_TAG) != 0u;
+          const float* src = tsum ? ebase + (size_t)(pos & ~EP_TAG) * D : sg.seg_grad + (size_t)rec.ps * D;
 #pragma unroll
-        for (int k = 0; k < K; ++k) ldv_stream<V>(src + eo[k], dst[k]);
+          for (int k = 0; k < K; ++k) {
+            ldv<V>(src + eo[k], dst[k]);
+#pragma unroll
+            for (int cc = 0; cc < V; ++cc) dst[k][cc] = tsum ? dst[k][cc] : dst[k][cc] * rec.sc;
+          }
+        } else {
+          const float* base = (pos & EP_TAG) ? ebase : (pos - w.self_lo < w.self_len) ? gself : gbase;
+          const float* src = base + (size_t)(pos & ~EP_TAG) * D;
+#pragma unroll
+          for (int k = 0; k < K; ++k) ldv_stream<V>(src + eo[k], dst[k]);
+        }
       };
       const bool is_hot = it < nhot;
       // the key of this lane group (hot: every group the same key, group 0 finishes it)
@@ -444,13 +470,24 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
           }
         };
         unsigned pa_[RB], pb_[RB];
+        Rec ra_[SEG ? RB : 1], rb_[SEG ? RB : 1];   // SEG: the sources' records, a step ahead like the sources themselves
         float va[RB][K][V];
         ldpos(0, pa_);
+        if constexpr (SEG) {
+#pragma unroll
+          for (int j = 0; j < RB; ++j) ra_[j] = load_rec(pa_[j]);
+        }
         if (!dedup) prefetch();
         for (unsigned stp = 0; stp < nst; ++stp) {
 #pragma unroll
-          for (int j = 0; j < RB; ++j) load_row(pa_[j], va[j]);
+          for (int j = 0; j < RB; ++j) {
+            if constexpr (SEG) load_row(pa_[j], va[j], ra_[j]); else load_row(pa_[j], va[j]);
+          }
           ldpos(stp + 1, pb_);
+          if constexpr (SEG) {
+#pragma unroll
+            for (int j = 0; j < RB; ++j) rb_[j] = load_rec(pb_[j]);
+          }
 #pragma unroll
           for (int j = 0; j < RB; ++j) {
             const bool ok = lo + stp * SR + j * G + g < hi;
@@ -459,6 +496,7 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
 #pragma unroll
               for (int cc = 0; cc < V; ++cc) gv[k][cc] += ok ? va[j][k][cc] : 0.f;
             pa_[j] = pb_[j];
+            if constexpr (SEG) ra_[j] = rb_[j];
           }
         }
 #pragma unroll
@@ -474,8 +512,14 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
         const unsigned p0 = src_at(st < E ? st : 0u);
         const bool two = __ballot(live && cnt >= 2u) != 0ull;
         const unsigned p1 = src_at((cnt >= 2u ? st + 1u : st) < E ? (cnt >= 2u ? st + 1u : st) : 0u);
-        load_row(p0, gv);
-        if (two) load_row(p1, g2);   // uniform over the wave
+        if constexpr (SEG) {
+          const Rec q0 = load_rec(p0), q1 = load_rec(p1);
+          load_row(p0, gv, q0);
+          if (two) load_row(p1, g2, q1);
+        } else {
+          load_row(p0, gv);
+          if (two) load_row(p1, g2);   // uniform over the wave
+        }
         if (!dedup) prefetch();
         if (two) {
 #pragma unroll
@@ -489,8 +533,16 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
           unsigned pj[RC];
 #pragma unroll
           for (int j = 0; j < RC; ++j) pj[j] = src_at(j0 + j < cnt ? st + j0 + j : (st < E ? st : 0u));
+          if constexpr (SEG) {
+            Rec qj[RC];
 #pragma unroll
-          for (int j = 0; j < RC; ++j) load_row(pj[j], val[j]);
+            for (int j = 0; j < RC; ++j) qj[j] = load_rec(pj[j]);
+#pragma unroll
+            for (int j = 0; j < RC; ++j) load_row(pj[j], val[j], qj[j]);
+          } else {
+#pragma unroll
+            for (int j = 0; j < RC; ++j) load_row(pj[j], val[j]);
+          }
 #pragma unroll
           for (int j = 0; j < RC; ++j) {
             const bool okj = j0 + j < cnt;
@@ -683,6 +735,19 @@ __global__ void __launch_bounds__(256, KV_PA_WAVES) k_papply_dedup_multi(const M
   const MultiDesc& m = descs[blockIdx.y];
   if (blockIdx.x >= m.w.P || m.n == 0) return;
   papply_body<OPT_ADAGRAD, V, LPR, K, 256, PA_DEDUP>(m.w, m.a, PA_DEDUP);
+}
+// PA_DEDUP where the gradient arrives per segment (the sharded sparse apply's pre-sum, kv_sums_seg.hip): both block shapes
+// of k_papply_dedup, and the batched form with its SegDesc array next to the MultiDesc array
+template <int V, int LPR, int K, int TBP>
+__global__ void __launch_bounds__(TBP, TBP >= 512 ? KV_PD_WAVES : KV_PA_WAVES) k_papply_dedup_seg(WsDev w, PartArgs a, SegSrc sg) {
+  papply_body<OPT_ADAGRAD, V, LPR, K, TBP, PA_DEDUP, true>(w, a, PA_DEDUP, sg);
+}
+template <int V, int LPR, int K>
+__global__ void __launch_bounds__(256, KV_PA_WAVES) k_papply_dedup_seg_multi(const MultiDesc* __restrict__ descs,
+                                                                            const SegDesc* __restrict__ segs) {
+  const MultiDesc& m = descs[blockIdx.y];
+  if (blockIdx.x >= m.w.P || m.n == 0) return;
+  papply_body<OPT_ADAGRAD, V, LPR, K, 256, PA_DEDUP, true>(m.w, m.a, PA_DEDUP, segs[blockIdx.y].src);
 }
 __global__ void __launch_bounds__(256, KV_PA_WAVES) k_papply_uniq_multi(const MultiDesc* __restrict__ descs, int mode) {
   const MultiDesc& m = descs[blockIdx.y];

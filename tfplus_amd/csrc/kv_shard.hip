@@ -3,9 +3,10 @@
 // finish phases and the whole ops; the read-only lookup is the training one with another serve: serve_zeros_impl), the
 // batched kv_multi_shard_* ops, and kv_bucket_by_owner, the routing rule's stand-alone form.  The only unit that knows RCCL; its own kernels are kv_route.h's.
 // Each phase's arguments are built in one place (route_desc, presum_desc, finish_desc, finish_sparse_desc) for its
-// single-table and its batched launch; each whole op has one body (shards_lookup, shards_apply), of which the single forms
-// are the one-table case and the sparse lookups the ones with the combining finish (SparseArgs); segment sizes come from
-// shard_bytes, batched groups from groups_of.
+// single-table and its batched launch (the sparse pre-sum, presum_sparse_impl, adds the position records to presum_desc);
+// each whole op has one body (shards_lookup, shards_apply), of which the single forms are the one-table case, the sparse
+// lookups the ones with the combining finish and the sparse applies the ones whose pre-sum reads segment gradients
+// (SparseArgs); segment sizes come from shard_bytes, batched groups from groups_of.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -350,6 +351,17 @@ static int sparse_finish_check(const char* what, const void* seg, int seg_dtype,
   if (seg_dtype != KV_DT_INT32 && seg_dtype != KV_DT_INT64) return fail(KV_INVALID_ARGUMENT, "%s: segment ids must be int32 or int64", what);
   if (combiner < KV_COMBINER_SUM || combiner > KV_COMBINER_SQRTN)
     return fail(KV_INVALID_ARGUMENT, "%s: combiner must be one of 'mean', 'sqrtn' or 'sum'", what);
+  return KV_OK;
+}
+
+// the argument errors of a sparse gradient pre-sum over a batch of n ids (kvhip.h kv_shard_apply_route_sparse): with n > 0
+// there is a gradient to expand, so there must be segments
+static int sparse_presum_check(const char* what, const float* seg_grad, const void* seg, int seg_dtype, int64_t n, int64_t nseg, int combiner) {
+  if (n > 0 && (!seg_grad || !seg)) return fail(KV_INVALID_ARGUMENT, "%s: segment gradients / segment ids pointer is null", what);
+  if (seg_dtype != KV_DT_INT32 && seg_dtype != KV_DT_INT64) return fail(KV_INVALID_ARGUMENT, "%s: segment ids must be int32 or int64", what);
+  if (combiner < KV_COMBINER_SUM || combiner > KV_COMBINER_SQRTN)
+    return fail(KV_INVALID_ARGUMENT, "%s: combiner must be one of 'mean', 'sqrtn' or 'sum'", what);
+  if (n > 0 && (nseg < 1 || nseg > (1ll << 31) - 2)) return fail(KV_INVALID_ARGUMENT, "%s: bad num_segments", what);
   return KV_OK;
 }
 
@@ -716,6 +728,72 @@ static int multi_presum_impl(const kv_shard_t* shards, const int* todo, int m, c
   return KV_OK;
 }
 
+// The SPARSE gradient pre-sum of the tables todo[0..m) — all of one dim, and where m > 1 none in deterministic mode: grads[k]
+// holds table k's SEGMENT gradients [nseg, dim].  The position records first (launch_pos_records: every position's clamped
+// segment and scale, kv_lookup_sparse_grad's own), then the two launches of the plain pre-sum in their per-segment forms
+// (kv_sums_seg.hip): the [n, dim] values are neither written nor read.  Every check and every buffer that may have to grow
+// comes before the first launch.  One table takes its arguments by value: nothing is staged.
+static int presum_sparse_impl(const char* what, const kv_shard_t* shards, const int* todo, int m, const float* const* grads,
+                              const SparseArgs& sp, hipStream_t s) {
+  int rc;
+  std::vector<kv_table*> rts;
+  for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
+  MultiLock lock(rts);
+  for (int j = 0; j < m; ++j) {
+    const int k = todo[j];
+    kv_shard* sh = shards[k];
+    if (!sh->route->batch.holds(sh->route_token, sh->n_last))
+      return fail(KV_FAILED_PRECONDITION, "%s: the batch's lookup must come first (kv_shard_lookup_route)", what);
+    if ((rc = sparse_presum_check(what, grads[k], sp.seg[k], sp.seg_dtype, sh->n_last, sp.nseg[k], sp.combiner))) return rc;
+  }
+  std::vector<SegDesc> sd(m);
+  for (int j = 0; j < m; ++j) {
+    const int k = todo[j];
+    kv_shard* sh = shards[k];
+    kv_table* rt = sh->route;
+    const bool need_den = sp.w(k) != nullptr && sp.combiner != KV_COMBINER_SUM;
+    if ((rc = hand_over(rt, s))) return rc;
+    if ((rc = ensure_workspace(rt, sh->n_last, true, s)) || (rc = ensure_seg(rt, sp.nseg[k], need_den, s)) ||
+        (rc = ensure_pos_records(rt, sh->n_last, s)))
+      return rc;
+    SegDesc& q = sd[j];
+    q.seg = sp.seg[k]; q.wts = sp.w(k); q.off = rt->ws.seg_off; q.den = need_den ? rt->ws.seg_den : nullptr;
+    q.pseg = rt->ws.pseg; q.pscale = rt->ws.pscale; q.n = sh->n_last; q.nseg = sp.nseg[k];
+    q.src = SegSrc{grads[k], rt->ws.pseg, rt->ws.pscale};
+  }
+  const int seg32 = sp.seg_dtype == KV_DT_INT32;
+  if (m == 1) {
+    MultiDesc d{};
+    presum_desc(shards[todo[0]], nullptr, d);
+    if ((rc = launch_pos_records(1, sd.data(), nullptr, seg32, sp.combiner, s))) return rc;
+    if ((rc = launch_tsum_seg(d.a.tv, d.w, sd[0].src, s))) return fail(rc, "tile sums: no kernel for dim %d", d.a.tv.dim);
+    if ((rc = launch_papply_dedup_seg(d.w, d.a, sd[0].src, s))) return fail(rc, "gradient pre-sum: no kernel for dim %d", d.a.tv.dim);
+    HIP_TRY(hipGetLastError());
+    return KV_OK;
+  }
+  const int device = shards[todo[0]]->table->device;
+  Staged<MultiDesc> hd(device, 1, m);
+  if (hd.rc) return hd.rc;
+  Staged<SegDesc> hs(device, 2, m);
+  if (hs.rc) return hs.rc;
+  WsDev wmax{};
+  for (int j = 0; j < m; ++j) {
+    presum_desc(shards[todo[j]], nullptr, hd[j]);
+    hd[j].a.det = 0;
+    hd[j].n = hd[j].a.n;
+    widen(wmax, hd[j].w);
+    hs[j] = sd[j];
+  }
+  const MultiDesc* md;
+  const SegDesc* sdev;
+  if ((rc = hd.upload(s, &md)) || (rc = hs.upload(s, &sdev))) return rc;
+  if ((rc = launch_pos_records(m, sd.data(), sdev, seg32, sp.combiner, s))) return rc;
+  if ((rc = launch_tsum_seg(hd[0].a.tv, wmax, SegSrc{}, s, md, sdev, m))) return fail(rc, "tile sums: no kernel for dim %d", hd[0].a.tv.dim);
+  if ((rc = launch_papply_dedup_seg(wmax, hd[0].a, SegSrc{}, s, md, sdev, m))) return fail(rc, "gradient pre-sum: no kernel for dim %d", hd[0].a.tv.dim);
+  HIP_TRY(hipGetLastError());
+  return KV_OK;
+}
+
 // ---- the whole ops: kv_shard_lookup / kv_shard_apply are kv_multi_shard_lookup / kv_multi_shard_apply of one table -----------
 // A failure of THIS rank's phase (out of memory, a bad argument) must not leave the peers waiting in a grouped recv: the
 // exchanges are queued all the same — void headers for a failed route, zero rows for a failed serve or pre-sum — and the
@@ -898,14 +976,18 @@ static int shards_lookup(const char* what, bool single, bool read_only, const kv
 
 // backward, as shards_lookup: the gradient pre-sum, ONE exchange, the owners' applies.  A rank whose pre-sum failed still
 // takes part in the exchange (zero gradient rows).  slot1 may be null (no table has a second slot table).
-static int shards_apply(bool single, const kv_shard_t* shards, int ntab, kv_comm* comm, int optimizer, const kv_handle_t* slot0,
-                        const kv_handle_t* slot1, const float* const* grads, const float* hp, int join, hipStream_t s) {
+// sp != nullptr (the sparse applies): grads[k] of a table with segments holds its SEGMENT gradients, and its pre-sum is the
+// sparse one (presum_sparse_impl) — in groups of its own, by dim; the exchange and the owners' side know no difference.
+static int shards_apply(const char* what, bool single, const kv_shard_t* shards, int ntab, kv_comm* comm, int optimizer,
+                        const kv_handle_t* slot0, const kv_handle_t* slot1, const float* const* grads, const float* hp, int join,
+                        hipStream_t s, const SparseArgs* sp = nullptr) {
   int rc;
   DeviceGuard dg(shards[0]->table->device);
   hipStream_t w = comm->stream;
   kv_shard* const sh0 = shards[0];
+  auto sparse = [&](int k) { return sp != nullptr && sp->sparse(k); };
   for (int k = 0; k < ntab; ++k)
-    if ((rc = shard_refuse_apply(shards[k], single ? "kv_shard_apply" : "kv_multi_shard_apply"))) return rc;
+    if ((rc = shard_refuse_apply(shards[k], what))) return rc;
   if ((rc = shard_fork(sh0, s, w))) return rc;
   FirstError note;
   const bool pm = single && shard_prof_begin(sh0, false);
@@ -913,12 +995,17 @@ static int shards_apply(bool single, const kv_shard_t* shards, int ntab, kv_comm
   // gradient pre-sum: the tables of one dim whose route has no ordered owner scatter in two launches
   std::vector<char> done(ntab, 0);   // 1: summed; 2: its group failed (zero gradient rows)
   for (const auto& grp : groups_of(ntab, [&](int k) {
-         return shards[k]->n_last > 0 && !shards[k]->table->deterministic ? shards[k]->table->dim : -1; })) {
-    const char r = note(multi_presum_impl(shards, grp.data(), (int)grp.size(), grads, w)) ? 2 : 1;
+         return shards[k]->n_last > 0 && !shards[k]->table->deterministic ? shards[k]->table->dim * 2 + (sparse(k) ? 1 : 0) : -1; })) {
+    const char r = note(sparse(grp[0]) ? presum_sparse_impl(what, shards, grp.data(), (int)grp.size(), grads, *sp, w)
+                                       : multi_presum_impl(shards, grp.data(), (int)grp.size(), grads, w)) ? 2 : 1;
     for (int k : grp) done[k] = r;
   }
+  auto presum_one = [&](int k) {
+    return sparse(k) ? kv_shard_apply_route_sparse(shards[k], grads[k], sp->seg[k], sp->seg_dtype, sp->w(k), sp->nseg[k], sp->combiner, w)
+                     : kv_shard_apply_route(shards[k], grads[k], w);
+  };
   for (int k = 0; k < ntab; ++k)
-    if (done[k] != 1 && (done[k] == 2 || note(kv_shard_apply_route(shards[k], grads[k], w))) && (rc = shard_zero_rows(shards[k], w))) return rc;
+    if (done[k] != 1 && (done[k] == 2 || note(presum_one(k))) && (rc = shard_zero_rows(shards[k], w))) return rc;
   shard_prof_mark(sh0, pm, 7, w);
   if ((rc = shards_exchange(shards, ntab, comm, true, w))) return rc;
   shard_prof_mark(sh0, pm, 8, w);
@@ -1271,6 +1358,21 @@ int kv_shard_apply_route(kv_shard_t sh, const float* grad, kv_stream_t stream) {
   return KV_OK;
 }
 
+// ... from the SEGMENT gradients of the batch's sparse lookup: the record of a distinct id receives the sum over its
+// positions j of scale_j * seg_grad[segment of j] — each term the row kv_lookup_sparse_grad would have written, added in the
+// order kv_shard_apply_route adds rows; the [n, dim] values never exist.  3 launches for the position records (2 without
+// weighted denominators), then the 2 of the pre-sum.
+int kv_shard_apply_route_sparse(kv_shard_t sh, const float* seg_grad, const void* segment_ids, int segment_dtype,
+                                const float* weights, int64_t num_segments, int combiner, kv_stream_t stream) {
+  if (!sh) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_route_sparse: null shard");
+  { int rc; if ((rc = shard_refuse_apply(sh, "kv_shard_apply_route_sparse"))) return rc; }
+  if (sh->n_last == 0) return KV_OK;
+  DeviceGuard dg(sh->table->device);
+  const SparseArgs sp{&segment_ids, segment_dtype, &weights, &num_segments, combiner, true};
+  const int one = 0;
+  return presum_sparse_impl("kv_shard_apply_route_sparse", &sh, &one, 1, &seg_grad, sp, (hipStream_t)stream);
+}
+
 // the owner's half: recv_rows holds the peers' summed gradients, record for record as the lookup served them; the
 // fused apply takes the index that lookup left in the table's workspace.  2 launches.  optimizer / hp: shard_opt_call
 int kv_shard_apply_serve(kv_shard_t sh, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp, kv_stream_t stream) {
@@ -1389,7 +1491,17 @@ int kv_multi_shard_lookup_sparse_zeros(const kv_shard_t* shards, int ntab, kv_co
 int kv_shard_apply(kv_shard_t sh, kv_comm_t comm, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* grad,
                    const float* hp, int join, kv_stream_t stream) {
   if (!sh || !comm || comm->world != sh->world) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply: shard / communicator mismatch");
-  return shards_apply(true, &sh, 1, comm, optimizer, &slot0, &slot1, &grad, hp, join, (hipStream_t)stream);
+  return shards_apply("kv_shard_apply", true, &sh, 1, comm, optimizer, &slot0, &slot1, &grad, hp, join, (hipStream_t)stream);
+}
+
+// kv_shard_apply whose pre-sum takes the SEGMENT gradients of the batch's sparse lookup (kv_shard_apply_route_sparse)
+int kv_shard_apply_sparse(kv_shard_t sh, kv_comm_t comm, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* seg_grad,
+                          const void* segment_ids, int segment_dtype, const float* weights, int64_t num_segments, int combiner,
+                          const float* hp, int join, kv_stream_t stream) {
+  if (!sh || !comm || comm->world != sh->world) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_sparse: shard / communicator mismatch");
+  const SparseArgs sp{&segment_ids, segment_dtype, &weights, &num_segments, combiner, true};
+  return shards_apply("kv_shard_apply_sparse", true, &sh, 1, comm, optimizer, &slot0, &slot1, &seg_grad, hp, join, (hipStream_t)stream,
+                      &sp);
 }
 
 int kv_multi_shard_lookup(const kv_shard_t* shards, int ntab, kv_comm_t comm, const void* const* ids, const int64_t* n,
@@ -1414,7 +1526,22 @@ int kv_multi_shard_apply(const kv_shard_t* shards, int ntab, kv_comm_t comm, int
   int rc;
   if ((rc = multi_shard_check(shards, ntab, comm, "kv_multi_shard_apply"))) return rc;
   if (!slot0 || !grads || !hp) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_apply: null argument list");
-  return shards_apply(false, shards, ntab, comm, optimizer, slot0, slot1, grads, hp, join, (hipStream_t)stream);
+  return shards_apply("kv_multi_shard_apply", false, shards, ntab, comm, optimizer, slot0, slot1, grads, hp, join, (hipStream_t)stream);
+}
+
+// kv_multi_shard_apply where grads[k] of a table with segment_ids[k] != nullptr holds its SEGMENT gradients
+// [num_segments[k], dim_k] (the mixed form of kv_multi_shard_lookup_sparse); one exchange whatever the mix
+int kv_multi_shard_apply_sparse(const kv_shard_t* shards, int ntab, kv_comm_t comm, int optimizer, const kv_handle_t* slot0,
+                                const kv_handle_t* slot1, const float* const* grads, const void* const* segment_ids,
+                                int segment_dtype, const float* const* weights, const int64_t* num_segments, int combiner,
+                                const float* hp, int join, kv_stream_t stream) {
+  int rc;
+  if ((rc = multi_shard_check(shards, ntab, comm, "kv_multi_shard_apply_sparse"))) return rc;
+  if (!slot0 || !grads || !hp || !segment_ids || !num_segments)
+    return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_apply_sparse: null argument list");
+  const SparseArgs sp{segment_ids, segment_dtype, weights, num_segments, combiner, false};
+  return shards_apply("kv_multi_shard_apply_sparse", false, shards, ntab, comm, optimizer, slot0, slot1, grads, hp, join,
+                      (hipStream_t)stream, &sp);
 }
 
 // The exchange between shards that live in ONE process (all on one device): segment r of shard p's send buffer to

@@ -227,6 +227,28 @@ struct MultiDesc {
   float* out;            // lookup output rows
   long long n;
 };
+// The sharded sparse apply's pre-sum (kv_sums_seg.hip): the gradient arrives per SEGMENT, and the row of input position p is
+// pscale[p] * seg_grad[pseg[p], :] — each element one multiply, the row kv_lookup_sparse_grad would have written.  The sum
+// kernels' *_seg forms take this as an extra argument; WsDev, PartArgs and MultiDesc stay as the training step's kernels
+// index them.
+struct SegSrc {
+  const float* seg_grad;   // [nseg, dim]
+  const int* pseg;         // [n] the position's segment, clamped into [0, nseg)
+  const float* pscale;     // [n] its scale (kv_op_kernels.h seg_scale)
+};
+// ... and per table of a batched launch, next to the MultiDesc array (as SparseDesc sits next to it in the sparse lookups):
+// what the sum kernels read (src) and what the pre-pass that writes the position records reads and writes
+struct SegDesc {
+  SegSrc src;
+  const void* seg;         // [n] segment ids (one dtype for the whole call)
+  const float* wts;        // [n] or null
+  unsigned* off;           // [nseg + 1] the route table's Workspace::seg_off
+  float* den;              // [nseg] its Workspace::seg_den (weighted mean / sqrtn)
+  int* pseg;               // [n] OUT: Workspace::pseg
+  float* pscale;           // [n] OUT: Workspace::pscale
+  long long n, nseg;
+};
+
 // k_papply's modes (kv_papply.h explains them): the `mode` of launch_papply / launch_papply_ud
 enum PaMode { PA_LOOKUP = 0, PA_APPLYIDX = 1, PA_NONE = 2, PA_UNIQUE = 3, PA_DEDUP = 4,
               PA_DEDUP_NUM = 5 };   // (a template constant only: PA_DEDUP that numbers the ids itself — kv_dedup_segment_sum)

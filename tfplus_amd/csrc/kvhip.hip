@@ -475,6 +475,19 @@ int ensure_pos_ent(kv_table* t, long long n, hipStream_t s) {
   return KV_OK;
 }
 
+// Workspace::pseg / pscale hold n positions (the sharded sparse apply's position records, on the route table)
+int ensure_pos_records(kv_table* t, long long n, hipStream_t s) {
+  Workspace& w = t->ws;
+  if (w.prec_cap >= n) return KV_OK;
+  int rc;
+  if ((rc = ws_sync(s))) return rc;
+  const long long cap = std::max<long long>(n, w.cap_n);
+  w.prec_cap = 0;
+  if ((rc = regrow(&w.pseg, (size_t)cap)) || (rc = regrow(&w.pscale, (size_t)cap))) return rc;
+  w.prec_cap = cap;
+  return KV_OK;
+}
+
 WsDev ws_view(kv_table* t, long long n, const SelfSegment* self) {
   Workspace& w = t->ws;
   WsDev d;
@@ -1124,7 +1137,7 @@ int kv_destroy(kv_handle_t t) {
   hipFree(w.ent_key); hipFree(w.ent_a); hipFree(w.ent_b); hipFree(w.ent_base); hipFree(w.ent_rec); hipFree(w.toff); hipFree(w.slot_rank);
   hipFree(w.order); hipFree(w.coldlist); hipFree(w.hotlist); hipFree(w.litem); hipFree(w.items); hipFree(w.pmeta); hipFree(w.hpart);
   hipFree(w.mcount); hipFree(w.epart); hipFree(w.pos_ent);
-  hipFree(w.ctr); hipFree(w.dbg); hipFree(w.scat_keys); hipFree(w.scat_sum); hipFree(w.seg_off); hipFree(w.seg_den);
+  hipFree(w.ctr); hipFree(w.dbg); hipFree(w.scat_keys); hipFree(w.scat_sum); hipFree(w.seg_off); hipFree(w.seg_den); hipFree(w.pseg); hipFree(w.pscale);
   if (t->err_host) hipHostFree(t->err_host);
   if (t->cnt_host) hipHostFree(t->cnt_host);
   if (t->last_done) hipEventDestroy(t->last_done);

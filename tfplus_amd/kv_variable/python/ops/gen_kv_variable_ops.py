@@ -1190,6 +1190,7 @@ class KvShard(object):
     out = _gather_out(self.table, ids)
     _lib.check(_lib.lib().kv_shard_lookup(self.ptr, comm.ptr, _p(ids), ids.numel(), _p(out), int(bool(join)), _stream(self.table)))
     self._keep = (ids, out)     # the shard's stream may still be reading / writing them
+    self._n_routed = ids.numel()
     return out
 
   def lookup_zeros(self, comm, indices, join=True):
@@ -1199,6 +1200,7 @@ class KvShard(object):
     out = _gather_out(self.table, ids)
     _lib.check(_lib.lib().kv_shard_lookup_zeros(self.ptr, comm.ptr, _p(ids), ids.numel(), _p(out), int(bool(join)), _stream(self.table)))
     self._keep = (ids, out)     # the shard's stream may still be reading / writing them
+    self._n_routed = ids.numel()
     return out
 
   def apply(self, comm, optimizer, slots, grad, hp, join=True):
@@ -1218,6 +1220,7 @@ class KvShard(object):
     _lib.check(fn(self.ptr, comm.ptr, _p(ids), _p(seg), _TORCH_KEY[seg.dtype], _p(w), ids.numel(), int(num_segments),
                   _COMBINERS[combiner], _p(out), int(bool(join)), _stream(self.table)))
     self._keep = (ids, seg, w, out)     # the shard's stream may still be reading / writing them
+    self._n_routed = ids.numel()
     return out
 
   def lookup_sparse(self, comm, indices, segment_ids, weights, num_segments, combiner="mean", join=True):
@@ -1231,11 +1234,29 @@ class KvShard(object):
     return self._lookup_sparse(_lib.lib().kv_shard_lookup_sparse_zeros, comm, indices, segment_ids, weights, num_segments, combiner,
                                join)
 
+  def _sparse_grad_args(self, seg_grad, segment_ids, weights, num_segments, combiner):
+    """(seg_grad [num_segments, dim] float32, segment ids, weights or None) on the table's device, for the batch last routed."""
+    if combiner not in _COMBINERS:
+      raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+    g = _f32(self.table, seg_grad)
+    if g.dim() != 2 or g.shape[0] != int(num_segments) or g.shape[1] != self.table.dim:
+      raise _lib.InvalidArgumentError("seg_grad must be [num_segments, dim] = [%d, %d], got %s"
+                                      % (int(num_segments), self.table.dim, tuple(g.shape)))
+    routed = getattr(self, "_n_routed", None)   # (never routed: the library refuses; else the lists must be as long as the batch)
+    seg, w = _sparse_args(self.table, torch.as_tensor(segment_ids).numel() if routed is None else routed, segment_ids, weights)
+    return g, seg, w
+
   def apply_sparse(self, comm, optimizer, slots, seg_grad, segment_ids, weights, num_segments, combiner, hp, join=True):
-    """The backward of lookup_sparse, a composition: kv_variable_lookup_sparse_grad on the shard's table expands the segment
-    gradients [num_segments, dim] into the values [n, dim] of the batch, apply() sums and sends them."""
-    values = kv_variable_lookup_sparse_grad(self.table, seg_grad, segment_ids, weights, num_segments, combiner)
-    self.apply(comm, optimizer, slots, values, hp, join)
+    """The backward of lookup_sparse, fused (kvhip.h kv_shard_apply_sparse): apply() whose gradient pre-sum reads the segment
+    gradients [num_segments, dim] themselves — the values [n, dim] kv_variable_lookup_sparse_grad would expand them into are
+    neither written nor read.  Bit for bit that composition in deterministic mode; the same terms per id in the default mode."""
+    g, seg, w = self._sparse_grad_args(seg_grad, segment_ids, weights, num_segments, combiner)
+    arr = _hp_array(hp)
+    s1 = slots[1].ptr if len(slots) > 1 else None
+    _lib.check(_lib.lib().kv_shard_apply_sparse(self.ptr, comm.ptr, int(optimizer), slots[0].ptr, s1, _p(g), _p(seg),
+                                                _TORCH_KEY[seg.dtype], _p(w), int(num_segments), _COMBINERS[combiner], arr,
+                                                int(bool(join)), _stream(self.table)))
+    self._keep_g = (g, seg, w)
 
   def join(self):
     _lib.check(_lib.lib().kv_shard_join(self.ptr, _stream(self.table)))
@@ -1244,6 +1265,7 @@ class KvShard(object):
   def lookup_route(self, indices):
     ids = _ids(self.table, indices)
     self._ids = ids    # first: a late report of an earlier batch's overflow (raised below) leaves this batch routed
+    self._n_routed = ids.numel()
     _lib.check(_lib.lib().kv_shard_lookup_route(self.ptr, _p(ids), ids.numel(), _stream(self.table)))
 
   def lookup_serve(self):
@@ -1276,6 +1298,14 @@ class KvShard(object):
     _lib.check(_lib.lib().kv_shard_apply_route(self.ptr, _p(g), _stream(self.table)))
     self._keep_g = g
 
+  def apply_route_sparse(self, seg_grad, segment_ids, weights, num_segments, combiner="mean"):
+    """The gradient pre-sum from the segment gradients [num_segments, dim] of the batch lookup_route saw (kvhip.h
+    kv_shard_apply_route_sparse), where apply_route stands: the same sums in send_rows, no [n, dim] values in between."""
+    g, seg, w = self._sparse_grad_args(seg_grad, segment_ids, weights, num_segments, combiner)
+    _lib.check(_lib.lib().kv_shard_apply_route_sparse(self.ptr, _p(g), _p(seg), _TORCH_KEY[seg.dtype], _p(w), int(num_segments),
+                                                      _COMBINERS[combiner], _stream(self.table)))
+    self._keep_g = (g, seg, w)
+
   def apply_serve(self, optimizer, slots, hp):
     arr = _hp_array(hp)
     s1 = slots[1].ptr if len(slots) > 1 else None
@@ -1305,6 +1335,7 @@ def _multi_shard_lookup(fn, shards, comm, indices_list, join):
   _lib.check(fn(arr, T, comm.ptr, ip, nn, op, int(bool(join)), _stream(shards[0].table)))
   for sh, i, o in zip(shards, ids, outs):
     sh._keep = (i, o)
+    sh._n_routed = i.numel()
   return outs
 
 
@@ -1356,6 +1387,7 @@ def _multi_shard_lookup_sparse(fn, shards, comm, indices_list, segment_ids_list,
                 nn, ns, _COMBINERS[combiner], _ptr_array(outs), int(bool(join)), _stream(shards[0].table)))
   for sh, i, s, w, o in zip(shards, ids, segs, ws, outs):
     sh._keep = (i, s, w, o)
+    sh._n_routed = i.numel()
   return outs
 
 
@@ -1373,6 +1405,43 @@ def kv_multi_shard_apply(shards, comm, optimizer, slots_list, grads, hp, join=Tr
   _lib.check(_lib.lib().kv_multi_shard_apply(arr, T, comm.ptr, int(optimizer), s0, s1, gp, hpa, int(bool(join)), _stream(shards[0].table)))
   for sh, g in zip(shards, gs):
     sh._keep_g = g
+
+
+def kv_multi_shard_apply_sparse(shards, comm, optimizer, slots_list, grads, segment_ids_list, weights_list, num_segments_list,
+                                combiner, hp, join=True):
+  """kv_multi_shard_apply whose pre-sum takes segment gradients (kvhip.h kv_multi_shard_apply_sparse): for a table k with
+  segment_ids_list[k] not None, grads[k] is [num_segments_k, dim_k]; a table with None passes plain [n_k, dim_k] values.
+  weights_list may be None, and so may its entries.  One grouped exchange whatever the mix."""
+  T = len(shards)
+  if combiner not in _COMBINERS:
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  if T < 1 or len(slots_list) != T or len(grads) != T or len(segment_ids_list) != T or len(num_segments_list) != T or \
+      (weights_list is not None and len(weights_list) != T):
+    raise _lib.InvalidArgumentError("shards, slots, grads, segment_ids, num_segments (and weights) must be equally long, N >= 1")
+  gs, segs, ws = [], [], []
+  for k, sh in enumerate(shards):
+    if segment_ids_list[k] is None:
+      gs.append(_f32(sh.table, grads[k])); segs.append(None); ws.append(None)
+    else:
+      g, s, w = sh._sparse_grad_args(grads[k], segment_ids_list[k], None if weights_list is None else weights_list[k],
+                                     num_segments_list[k], combiner)
+      gs.append(g); segs.append(s); ws.append(w)
+  if len({s.dtype for s in segs if s is not None}) > 1:   # one dtype per call
+    segs = [None if s is None else s.to(torch.int64) for s in segs]
+  dts = [s.dtype for s in segs if s is not None]
+  # (a sparse table whose batch is empty still names a list: a null entry would mean plain values)
+  segs = [torch.zeros(1, dtype=s.dtype, device=s.device) if s is not None and s.numel() == 0 else s for s in segs]
+  arr = (ctypes.c_void_p * T)(*[sh.ptr for sh in shards])
+  s0 = (ctypes.c_void_p * T)(*[sl[0].ptr for sl in slots_list])
+  two = all(len(sl) > 1 for sl in slots_list)
+  s1 = (ctypes.c_void_p * T)(*[sl[1].ptr for sl in slots_list]) if two else None
+  ns = (ctypes.c_int64 * T)(*[0 if s is None else int(m) for s, m in zip(segs, num_segments_list)])
+  hpa = _hp_array(hp)
+  _lib.check(_lib.lib().kv_multi_shard_apply_sparse(arr, T, comm.ptr, int(optimizer), s0, s1, _ptr_array(gs), _ptr_array(segs),
+                                                    _TORCH_KEY[dts[0] if dts else torch.int64], _ptr_array(ws), ns,
+                                                    _COMBINERS[combiner], hpa, int(bool(join)), _stream(shards[0].table)))
+  for sh, g, s, w in zip(shards, gs, segs, ws):
+    sh._keep_g = (g, s, w)
 
 
 def kv_shard_agree_local(shards):
