@@ -144,6 +144,23 @@ int kv_get_meta(kv_handle_t h, const int64_t* ids, int64_t n, uint32_t* freq_wor
  *                                               returns KV_INVALID_ARGUMENT before anything is queued
  * Row buffers (out, grad, values, summed) may hold 2^31 elements and more: rows are addressed in 64 bits throughout. */
 
+/* ---- buffers ---------------------------------------------------------------------------------
+ * Alignment.  Every pointer is aligned to its element type: 4 bytes for float, int32 and uint32 buffers (weights, counts,
+ * id_counts, int32 ids and segment ids, inverse, perm, pos_out, frequency words), 8 bytes for int64 buffers (ids, keys,
+ * segment ids, the (id, count) pairs — read as two int64 each — and the device count words); the kernels read and write
+ * those one element at a time.  The ROW buffers — every float buffer shaped [rows, dim] of a table's dim: out / outs[i] of
+ * the lookups, grad / grads[i], values (kv_insert, the imports, the exports, kv_lookup_sparse_grad), updates, summed, data,
+ * seg_grad, the init table — are aligned to 16 bytes when dim is a multiple of 4: the kernels move such rows as float4
+ * (16-byte loads and stores; rows are contiguous, so every row then starts on 16 bytes).  At other dims 4 bytes suffice.
+ * Other alignments are not supported and not checked: a row buffer off 16 bytes is undefined behaviour, not an error code.
+ * The one exception is kv_take_rows, which looks at src and out and moves rows 4 bytes at a time when either is off 16
+ * bytes or row_bytes is not a multiple of 16.  (Allocators of device memory return far stricter alignment; the case is a
+ * view into a larger buffer at an odd element offset.  The Python binding copies such a view before the call.)
+ * Extents.  An op writes the extent its comment defines and nothing else of the caller's memory: no byte in front of a
+ * buffer or behind it, and of the buffers whose filled length the op reports (uniq / summed / uniq_counts, the export
+ * lists, delete_keys, out_ids / perm under n_dev) nothing outside [0, n).  Buffers declared const are never written
+ * (tests/test_gpu_buffer_extents.py holds both, op by op, behind guard bands). */
+
 /* ---- lookup (HOT LOOP 1) ------------------------------------------------------------------ */
 
 /* Replaces KvVariableGatherOrInsertOp / ...WithCountsOp::Compute
@@ -632,7 +649,9 @@ int kv_multi_apply_adam_unique(int num_tables, const kv_handle_t* vars, const kv
  * or NULL.  out [num_segments, dim]; a segment without ids is a zero row (weighted: 0/0 as in the
  * reference).  Missing keys are inserted; count_occurrences != 0 adds every occurrence of a key to
  * its frequency (the WithCounts path taken when enter_threshold > 0, embedding_ops.py:373-382),
- * 0 adds 1 per distinct key.  n <= 2^21 per call. */
+ * 0 adds 1 per distinct key.  n <= 2^21 per call.  n == 0 writes zero rows for every segment whatever `weights` is
+ * (there are no weights to divide by; kv_multi_lookup_sparse does the same for a table with ns[i] == 0), and
+ * num_segments == 0 writes nothing. */
 #define KV_COMBINER_SUM 0
 #define KV_COMBINER_MEAN 1
 #define KV_COMBINER_SQRTN 2

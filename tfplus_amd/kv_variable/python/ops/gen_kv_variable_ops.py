@@ -70,7 +70,10 @@ def _token_for(handle, ids):
 
 
 def _f32(handle, x):
-  return torch.as_tensor(x, dtype=torch.float32).to(_dev(handle)).contiguous()
+  """A float buffer as the C ABI takes it (kvhip.h "Buffers"): contiguous and on 16 bytes.  .contiguous() keeps a view's
+  storage offset, so a view that starts off a 16-byte boundary is copied; the outputs are fresh allocations."""
+  t = torch.as_tensor(x, dtype=torch.float32).to(_dev(handle)).contiguous()
+  return t.clone() if t.data_ptr() % 16 else t
 
 
 def _p(t):
