@@ -309,7 +309,31 @@ int kv_get_stat(kv_handle_t h, int which, int64_t* value);
  * synchronisation is not allowed.  KV_RESOURCE_EXHAUSTED when the table would have to grow for that many ids (it
  * grows here, outside the capture, if it can).  The table's batch workspace is sized by the calls themselves: issue the
  * op once with the batch length outside the capture; a captured call that would have to grow it returns
- * KV_FAILED_PRECONDITION before it queues anything (the capture stays valid). */
+ * KV_FAILED_PRECONDITION before it queues anything (the capture stays valid).
+ *
+ * The capture contract.  A replay runs no host code, so everything the host decided at the capture travels into every
+ * replay BY VALUE: the table view (entry array, mask, chunk pointers, the end of the slab), the partition count and the
+ * many-distinct choice, whether the free list is handed to the kernels (only if the host knew of released rows at the
+ * capture: a graph captured before any delete takes fresh rows whatever is released later, one captured after a delete
+ * pops the list until it is empty and then takes fresh rows), the clock day (a replay stamps the day of its capture,
+ * whatever kv_set_clock_days has set since — as it applies the Adam powers of its capture), the hyperparameters, and the
+ * batch index a token names.  What a replay reads afresh is what the captured pointers point to: ids, counts, gradient rows,
+ * the table itself.  A lookup captured under a token runs its own bookkeeping pass in the graph (outside a capture that
+ * pass may wait for the apply of the batch).  A batched call (kv_multi_*, kv_batch_*) uploads one descriptor per table: a
+ * captured one keeps those bytes, host and device, for every replay, out of room that kv_prepare_capture sets aside per
+ * device (256 KiB free after each call of it; never reused); without that room it is refused with KV_FAILED_PRECONDITION.
+ *
+ * max_new_ids must cover every id of every captured call (each takes its whole length from the host's bounds once, at the
+ * capture) and every key the replays can insert: for R replays of one step on n ids, R n plus the ids of the calls
+ * captured.  A captured call for which the bounds have no room left is refused with KV_FAILED_PRECONDITION before anything
+ * is queued — making room would synchronise the stream, and growing would move the table under the graphs that hold its
+ * pointers; the capture stays valid, and nothing was changed.
+ * No op may grow or rebuild the table between a capture and its last replay (a lookup or apply of new ids beyond the
+ * prepared room, kv_reserve, an import): the graph holds the table's pointers by value.  The prepared room covers that —
+ * size it for the eager calls in between as well.  Deletes, scatters, figure calls and ops on present keys are free.
+ * Behind the first captured call the device's counters move without the host (by whatever the replays insert), so from
+ * then on every inserting call outside a capture reads them back first (one stream synchronisation per call): the host
+ * never sizes the table from a bound the replays have outrun. */
 int kv_prepare_capture(kv_handle_t h, int64_t max_new_ids, kv_stream_t stream);
 
 /* The TF-core step on its own (for callers that want the [U, dim] IndexedSlices):

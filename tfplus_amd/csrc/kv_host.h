@@ -131,6 +131,10 @@ struct kv_table {
   long long free_base = 0;
   unsigned long long rows_cap = 0;  // chunks.size() << chunk_bits
   unsigned long long rows_ub = 1;   // upper bound of next_row
+  // stream capture (kvhip.hip ensure_capacity): kv_prepare_capture was called; a call on the table was recorded into a
+  // capture since — replays move the device's counters without the host, so rows_ub / idx_ub are refreshed by every call
+  // outside a capture from then on
+  bool capture_prepared = false, captured_calls = false;
   // init table
   float* init_table = nullptr;
   long long init_rows = 0;
@@ -459,6 +463,15 @@ struct BatchStage {       // a small ring, so the host can prepare call k+1 whil
 };
 extern BatchStage g_stage[64][3];   // [device][0 = inference gather, 1 = training ops, 2 = the sparse lookups' own descriptors]
 int stage_take(BatchStage& st, size_t bytes, StageSlot** out);   // the ring's next slot; st.mu is HELD where it succeeds
+// Under a stream capture the upload is RECORDED: every replay copies whatever the host buffer holds then into a device
+// buffer that later calls write too, and a ring slot is handed out again four calls on — a replayed batched op would run on
+// another call's descriptors.  A captured batched call therefore takes the host and device bytes of its descriptors from an
+// arena whose bytes are handed out once and never again (graphs may be replayed for as long as the process lives).  The arena
+// grows outside captures only: kv_prepare_capture tops it up to CAPTURE_STAGE_ROOM free bytes (capture_stage_reserve);
+// capture_stage_take refuses with KV_FAILED_PRECONDITION where it has no room.
+constexpr size_t CAPTURE_STAGE_ROOM = 256 * 1024;
+int capture_stage_reserve(int device);
+int capture_stage_take(int device, size_t bytes, char** host, char** dev);
 // `count` descriptors of a batched launch on g_stage[device][ring]: zeroed host descriptors by index, then ONE upload,
 // which is the only way to the device pointer — so a slot a kernel may still read is always marked busy.  The ring stays
 // locked until scope exit.  Check rc before anything else.
@@ -469,9 +482,10 @@ class Staged {
   const size_t bytes;
   hipStream_t s = nullptr;
   bool launched = false;
+  const int device;
  public:
   int rc;
-  Staged(int device, int ring, int count) : st(g_stage[device][ring]), bytes((size_t)count * sizeof(Desc)) {
+  Staged(int device, int ring, int count) : st(g_stage[device][ring]), bytes((size_t)count * sizeof(Desc)), device(device) {
     if (!(rc = stage_take(st, bytes, &sl))) std::memset(sl->host, 0, bytes);
   }
   Staged(const Staged&) = delete;
@@ -481,6 +495,15 @@ class Staged {
   }
   Desc& operator[](int i) { return reinterpret_cast<Desc*>(sl->host)[i]; }
   int upload(hipStream_t stream, const Desc** dev) {
+    if (stream_is_capturing(stream)) {   // bytes of its own, for every replay (the ring slot never reaches the stream: not busy)
+      char *h, *d;
+      const int rc_take = capture_stage_take(device, bytes, &h, &d);
+      if (rc_take) return rc_take;
+      std::memcpy(h, sl->host, bytes);
+      HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, stream));
+      *dev = reinterpret_cast<const Desc*>(d);
+      return KV_OK;
+    }
     HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, bytes, hipMemcpyHostToDevice, stream));
     launched = true; s = stream;
     *dev = reinterpret_cast<const Desc*>(sl->dev);

@@ -552,6 +552,10 @@ int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* counts,
   const size_t idsz = pairs ? 16 : (t->key_dtype == KV_DT_INT32 ? 4 : 8);
   t->batch.drop();
   const bool tok = token != nullptr && n <= CHK;   // a token is asked for, one pass indexes the batch: an apply of it follows
+  // ... and takes the lookup's partition pass with it — but not under a stream capture: a pass still pending when the capture
+  // ends would be launched by the table's next op, outside the graph, and no replay would do the lookup's bookkeeping
+  // (frequency words, the rows of new keys).  A captured lookup runs its pass itself; the apply takes the entries (TAKE_DONE).
+  const bool defer = tok && !stream_is_capturing(s);
   unsigned P = 0;
   for (long long off = 0; off < n; off += CHK) {
     const long long m = std::min(CHK, (long long)n - off);
@@ -564,7 +568,7 @@ int gather_or_insert_impl(kv_handle_t t, const void* ids, const int32_t* counts,
     wd.seg_cap = seg_cap;
     PartArgs pa = self_part_args(t, m);
     pa.day = today(t);
-    if (fused_tab(t)) { if ((rc = fused_lookup_pass(t, wd, pa, idp, cp, m, pairs ? 2 : -1, op, s, tok))) return rc; }
+    if (fused_tab(t)) { if ((rc = fused_lookup_pass(t, wd, pa, idp, cp, m, pairs ? 2 : -1, op, s, defer))) return rc; }
     else index_pass<MODE_LOOKUP>(t, wd, pa, idp, cp, m, pairs ? 2 : -1, op, s, tok);
     P = wd.P;
   }
@@ -622,7 +626,8 @@ int multi_lookup_impl(int num_tables, const kv_handle_t* tables, const void* con
     launch_ltile(t0, hd[0].a.tv, wmax, nullptr, nullptr, nmax, nullptr, s, ids_kind, md, num_tables, true);
     // tokens asked for: an optimizer apply of these batches follows — every table's partition pass stays pending
     // (kv_multi_apply_*_tok completes it inside k_papply_multi; any other op on a table settles that table first)
-    const bool defer = tokens != nullptr;
+    // (not under a stream capture: gather_or_insert_impl)
+    const bool defer = tokens != nullptr && !stream_is_capturing(s);
     if (!defer) launch_part2(wmax, hd[0].a, s, md, num_tables);
     if (tokens)   // every table's workspace now holds the index of exactly its batch (kv_multi_apply_*_tok takes it over)
       for (int i = 0; i < num_tables; ++i) {

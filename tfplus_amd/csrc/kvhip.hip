@@ -323,10 +323,25 @@ int flagged_error(kv_table* t, unsigned code, hipStream_t s) {
 // make room for `extra` more keys (worst case: every id of the batch is new).  rows_ub bounds the
 // bump allocator, idx_ub the claimed index entries (a key inserted into a row taken from the free
 // list claims a new entry while the deleted key's tombstone stays until the next rebuild).
+//
+// Stream capture.  A captured call takes its ids from the bounds once, at the capture; every replay inserts on the device
+// again, without the host.  From the first captured call on (captured_calls: set here, behind kv_prepare_capture, and
+// never cleared — a graph can be replayed at any time) the device may be ahead of both bounds by whatever the replays
+// inserted, so every call outside a capture refreshes them from the device before it decides anything: a bound that lags
+// would let the device reach the end of the slab first (table_find_or_insert's trap) or fill the index past one half.
+// A captured call that finds no room left within the bounds cannot refresh or grow (both synchronise): it is refused
+// before anything is queued, as ws_sync refuses a workspace that would have to grow, and the capture stays valid.
 int ensure_capacity(kv_table* t, long long extra, hipStream_t s) {
+  const bool capturing = t->capture_prepared && stream_is_capturing(s);
+  if (capturing) t->captured_calls = true;
   unsigned long long need = t->rows_ub + (unsigned long long)extra;
   unsigned long long need_idx = t->idx_ub + (unsigned long long)extra;
-  if (need > t->rows_cap || need_idx * 2 > t->cap) {
+  if ((t->captured_calls && !capturing) || need > t->rows_cap || need_idx * 2 > t->cap) {
+    if (capturing || stream_is_capturing(s))
+      return fail(KV_FAILED_PRECONDITION, "the table has no room left for the %lld ids of this call within what kv_prepare_capture "
+                                          "settled (making room synchronises the stream and may move the table): call "
+                                          "kv_prepare_capture outside the stream capture with max_new_ids covering every captured "
+                                          "call and every replay", extra);
     // refresh the exact counts before deciding to grow
     unsigned c[3];
     HIP_TRY(hipMemcpyAsync(c, t->d_counters, sizeof c, hipMemcpyDeviceToHost, s));
@@ -984,6 +999,45 @@ int stage_take(BatchStage& st, size_t bytes, StageSlot** out) {
   return KV_OK;
 }
 
+// the descriptors of captured batched calls (kv_host.h): blocks of pinned host + device memory, filled front to back, never
+// handed out twice and never freed
+struct CaptureStage {
+  struct Block { char* host; char* dev; size_t used; };
+  std::mutex mu;
+  std::vector<Block> blocks;
+};
+static CaptureStage g_capture_stage[64];
+int capture_stage_reserve(int device) {
+  if (device < 0 || device >= 64) return fail(KV_INVALID_ARGUMENT, "device index");
+  CaptureStage& a = g_capture_stage[device];
+  std::lock_guard<std::mutex> l(a.mu);
+  if (!a.blocks.empty() && a.blocks.back().used == 0) return KV_OK;   // a whole block is free
+  CaptureStage::Block b{nullptr, nullptr, 0};
+  if (hipHostMalloc(&b.host, CAPTURE_STAGE_ROOM) != hipSuccess) return fail(KV_RESOURCE_EXHAUSTED, "capture staging: allocation failed");
+  if (hipMalloc(&b.dev, CAPTURE_STAGE_ROOM) != hipSuccess) {
+    hipHostFree(b.host);
+    return fail(KV_RESOURCE_EXHAUSTED, "capture staging: allocation failed");
+  }
+  // (an earlier block keeps what is left of it: the next take may still fit there)
+  a.blocks.push_back(b);
+  return KV_OK;
+}
+int capture_stage_take(int device, size_t bytes, char** host, char** dev) {
+  bytes = (bytes + 255) & ~(size_t)255;
+  CaptureStage& a = g_capture_stage[device];
+  std::lock_guard<std::mutex> l(a.mu);
+  for (CaptureStage::Block& b : a.blocks)
+    if (CAPTURE_STAGE_ROOM - b.used >= bytes) {
+      *host = b.host + b.used;
+      *dev = b.dev + b.used;
+      b.used += bytes;
+      return KV_OK;
+    }
+  return fail(KV_FAILED_PRECONDITION, "a batched call under stream capture keeps its %zu bytes of descriptors for every replay, and "
+                                      "the room kv_prepare_capture sets aside for them is used up (or was never made): call "
+                                      "kv_prepare_capture on a table of this device outside the stream capture first", bytes);
+}
+
 int check_same_shape(int num_tables, const kv_handle_t* tables, const char* what) {
   int rc;
   if (num_tables < 1) return fail(KV_INVALID_ARGUMENT, "N must be >= 1");
@@ -1034,8 +1088,10 @@ void launch_fill_entries(kv_table* t, hipStream_t s) {
 void launch_clear_hints(kv_table* v, hipStream_t s) {
   k_clear_hints<<<nblocks((long long)v->cap + 1, TB, 8192), TB, 0, s>>>(v->entries, v->cap + 1);
 }
+// (every row in use: behind captured calls rows_ub may lag the device — ensure_capacity — so there the whole slab is cleared)
 void launch_clear_stamps(kv_table* v, hipStream_t s) {
-  k_clear_stamps<<<nblocks((long long)v->rows_ub, TB, 4096), TB, 0, s>>>(dev_view(v), (unsigned)v->rows_ub);
+  const unsigned long long nrows = v->captured_calls ? v->rows_cap : v->rows_ub;
+  k_clear_stamps<<<nblocks((long long)nrows, TB, 4096), TB, 0, s>>>(dev_view(v), (unsigned)nrows);
 }
 // kv_attach_slot (both locks held, any running epoch of either table ended): a pair of single-chunk tables gets its mirrors
 // filled with the hints
@@ -1249,6 +1305,8 @@ int kv_prepare_capture(kv_handle_t t, int64_t max_new_ids, kv_stream_t stream) {
   hipStream_t s = op.s;
   if ((rc = enter_op(t, s))) return rc;
   mirror_ban(t, s);   // (a captured apply replays without host code: no slot mirrors for this table from here on)
+  t->capture_prepared = true;   // (ensure_capacity: captured calls on this table are told from the others from here on)
+  if ((rc = capture_stage_reserve(t->device))) return rc;   // (the descriptors of captured batched calls: kv_host.h)
   unsigned c[3];
   HIP_TRY(hipMemcpyAsync(c, t->d_counters, sizeof c, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
