@@ -121,7 +121,7 @@ def test_multi_shard_ops_of_one_table_are_the_single_sharded_ops(lossless, det):
 @pytest.mark.parametrize("opt", ["adam", "ftrl"])
 def test_multi_shard_batched_phases_equal_the_per_table_ops(opt):
   """The default (not deterministic) mode: kv_multi_shard_lookup / _apply run every phase of same-shaped tables in one
-  launch (route, owner lookup, finish, gradient pre-sum, owner apply: kv_shard.hip multi_*_impl).  Against the per-table
+  launch (route, owner lookup, finish, gradient pre-sum, owner apply: the m > 1 arms of kv_shard.hip's *_impl).  Against the per-table
   sharded ops on twin tables: the rows a lookup returns are bit-equal, the tables hold the same keys and — the fp32
   sums of repeated ids being taken in another order — the same values within the summation tolerance.  One table is
   read between its lookup and its apply (its pending pass is settled: it leaves the batched apply for the per-table

@@ -377,13 +377,18 @@ int mirror_decide(kv_table* v, kv_table* s0, PartArgs& pa, bool lean, hipStream_
 // locks tables in address order like MaybeLockVariableInputMutexesInOrder (training_ops.cc:96-184)
 struct MultiLock {
   std::vector<kv_table*> ts;
+  kv_table* one = nullptr;   // the single-table form: one mutex, nothing allocated (ts stays empty)
+  explicit MultiLock(kv_table* t) : one(t) { t->mu.lock(); }
   explicit MultiLock(std::initializer_list<kv_table*> l) : MultiLock(std::vector<kv_table*>(l)) {}
   explicit MultiLock(std::vector<kv_table*> l) : ts(std::move(l)) {
     std::sort(ts.begin(), ts.end());
     ts.erase(std::unique(ts.begin(), ts.end()), ts.end());
     for (auto* t : ts) t->mu.lock();
   }
-  ~MultiLock() { for (auto it = ts.rbegin(); it != ts.rend(); ++it) (*it)->mu.unlock(); }
+  ~MultiLock() {
+    for (auto it = ts.rbegin(); it != ts.rend(); ++it) (*it)->mu.unlock();
+    if (one) one->mu.unlock();
+  }
   // keep(t): the mirror role(s) table t is kept in (KEEP_*)
   // later: this table's pending partition pass is taken over by the caller (the optimizer apply of that batch)
   template <class Keep>
@@ -391,7 +396,7 @@ struct MultiLock {
     int rc;
     for (auto* t : ts)
       if ((rc = enter_op(t, s, keep(t), t != later))) return rc;
-    return KV_OK;
+    return one ? enter_op(one, s, keep(one), one != later) : KV_OK;
   }
   int enter(hipStream_t s) { return enter(s, [](const kv_table*) { return (unsigned)KEEP_NONE; }); }
 };

@@ -2,16 +2,17 @@
 // (SURVEY.md §8e).  kv_comm_* (RCCL by dlopen, grouped send / recv; or the caller's transport), kv_shard_* (route / serve /
 // finish phases and the whole ops; the read-only lookup is the training one with another serve: serve_zeros_impl), the
 // batched kv_multi_shard_* ops, and kv_bucket_by_owner, the routing rule's stand-alone form.  The only unit that knows RCCL; its own kernels are kv_route.h's.
-// Each phase's arguments are built in one place (route_desc, presum_desc, finish_desc, finish_sparse_desc) for its
-// single-table and its batched launch (the sparse pre-sum, presum_sparse_impl, adds the position records to presum_desc);
-// each whole op has one body (shards_lookup, shards_apply), of which the single forms are the one-table case, the sparse
-// lookups the ones with the combining finish and the sparse applies the ones whose pre-sum reads segment gradients
-// (SparseArgs); segment sizes come from shard_bytes, batched groups from groups_of.
+// One body per phase over the tables todo[0..m), whose one-table case (descriptor by value, nothing staged) is the phase's C entry
+// point: route_impl, serve_zeros_impl, finish_impl, finish_sparse_impl, presum_impl, presum_sparse_impl (arguments: *_desc); the
+// training serve and the owner's apply are the table ops' own.  One body per whole op (shards_lookup, shards_apply): the single
+// forms are its one-table case, the sparse lookups those with the combining finish, the sparse applies those whose pre-sum reads
+// segment gradients (SparseArgs); segment sizes: shard_bytes, batched groups: groups_of.  A shard's last batch: kv_shard_batch.h.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 
 #include "kv_host.h"
+#include "kv_shard_batch.h"
 
 using namespace kvhip_internal;
 
@@ -50,13 +51,8 @@ struct kv_shard {
   bool lossless = true;              // ranks agree on the capacity before every exchange (the default: nothing can be lost);
                                      // kv_shard_set_lossless(shard, 0) opts into the synchronisation-free mode
   unsigned long long grows = 0;      // times the capacity was raised
-  long long n_last = 0;              // ids of the batch whose index `route` holds
-  bool self_in_place = false;        // this rank's own segments are read from the send buffers (no device copy in the exchange)
+  ShardBatch batch;                  // the batch last routed and served: written only through its transitions (kv_shard_batch.h)
   const kv_comm* verified = nullptr; // the communicator whose ranks were seen to agree on world / capacity / dim
-  uint64_t route_token = 0;
-  bool empty_routed = false;         // the last route was of an EMPTY batch (n_last == 0, no token: shard_route_holds)
-  kv_batch_token_t serve_token = 0;
-  bool read_only_last = false;       // the last served batch was a read-only one (kv_shard_lookup_serve_zeros): no apply may follow it
   hipEvent_t ev_fork = nullptr, ev_done = nullptr;
   int ranks_seen = 0;                // ranks whose handshake record arrived in the first exchange (shard_verify)
   // per-phase timing of the whole ops (kv_shard_profile): events on the communicator's stream at the phase boundaries of
@@ -117,12 +113,20 @@ RcclApi* rccl() {
   return &api;
 }
 
-#define NCCL_TRY(expr)                                                                                      \
-  do {                                                                                                      \
-    ncclResult_t _r = (expr);                                                                               \
-    if (_r != ncclSuccess)                                                                                  \
-      return fail(KV_INTERNAL, "%s failed: %s", #expr, rccl()->GetErrorString ? rccl()->GetErrorString(_r) : "?"); \
+static const char* nccl_err(ncclResult_t r) { return rccl()->GetErrorString ? rccl()->GetErrorString(r) : "?"; }
+#define NCCL_TRY(expr)                                                                \
+  do {                                                                                \
+    ncclResult_t _r = (expr);                                                         \
+    if (_r != ncclSuccess) return fail(KV_INTERNAL, "%s failed: %s", #expr, nccl_err(_r)); \
   } while (0)
+
+// a new communicator's fields, its own stream and events (its device is current); false: they could not be created
+static bool comm_init(kv_comm* c, int world, int rank, int device) {
+  c->world = world; c->rank = rank; c->device = device;
+  return hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
+         hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming) == hipSuccess;
+}
 
 // the segments really travel (RCCL or the caller's transport); else: a world of one whose exchange is a device copy
 static inline bool wired(const kv_comm* c) { return c->comm != nullptr || c->xfn != nullptr; }
@@ -158,6 +162,8 @@ void shard_free_buffers(kv_shard* sh) {
   sh->send_pairs = sh->recv_pairs = nullptr; sh->send_rows = sh->recv_rows = nullptr;
 }
 
+static int64_t shard_nrec(const kv_shard* sh) { return (int64_t)sh->world * (sh->C + 1); }   // the records of a send or receive buffer
+
 int shard_alloc_buffers(kv_shard* sh, unsigned C) {
   const size_t rec = (size_t)sh->world * (C + 1);
   if (rec > (1ull << 21)) return fail(KV_INVALID_ARGUMENT, "peer_capacity %u x world %d exceeds 2^21 records per exchange", C, sh->world);
@@ -169,6 +175,14 @@ int shard_alloc_buffers(kv_shard* sh, unsigned C) {
   HIP_TRY(hipMemset(sh->send_pairs, 0, rec * 16));
   HIP_TRY(hipMemset(sh->recv_pairs, 0, rec * 16));
   sh->C = C;
+  return KV_OK;
+}
+
+// the lossless agreements' grow step: a route wanted `need` records in one segment, more than C (every rank saw that number)
+static int shard_grow(kv_shard* sh, unsigned need, long long max_ids) {
+  if (int rc = shard_alloc_buffers(sh, (unsigned)std::min<long long>(max_ids, (long long)need + need / 4 + 64))) return rc;
+  *reinterpret_cast<volatile unsigned*>(sh->overflow) = 0;   // raised by the attempt that is now repeated
+  ++sh->grows;
   return KV_OK;
 }
 
@@ -223,8 +237,7 @@ static int comm_exchange(kv_comm* c, int nseg, const Seg* seg, hipStream_t s) {
     const ncclResult_t e = rccl()->GroupEnd();
     if (bad == ncclSuccess) bad = e;
   }
-  if (bad != ncclSuccess)
-    return fail(KV_INTERNAL, "grouped send / recv failed: %s", rccl()->GetErrorString ? rccl()->GetErrorString(bad) : "?");
+  if (bad != ncclSuccess) return fail(KV_INTERNAL, "grouped send / recv failed: %s", nccl_err(bad));
   if (hop) {
     HIP_TRY(hipEventRecord(c->ev_out, c->stream));
     HIP_TRY(hipStreamWaitEvent(s, c->ev_out, 0));
@@ -255,12 +268,12 @@ static int shard_late_report(kv_shard* sh, unsigned seen) {
 // tile pass, the finish, the owner apply's tile sums and k_papply) takes records [rank * (C + 1), +C + 1) from the send
 // buffer.
 static bool shard_can_stay(const kv_shard* sh) {
-  return (long long)sh->world * (sh->C + 1) <= FUSED_MAX_N;
+  return shard_nrec(sh) <= FUSED_MAX_N;
 }
 
 // ... as the owner ops are told (ws_view): the (id, count) records, and for the apply (grad) the summed gradient rows
 static SelfSegment shard_self(const kv_shard* sh, bool grad) {
-  if (!sh->self_in_place) return SelfSegment{};
+  if (!sh->batch.own_segment_stays()) return SelfSegment{};
   return SelfSegment{(unsigned)sh->rank * (sh->C + 1), sh->C + 1, sh->send_pairs, grad ? sh->send_rows : nullptr};
 }
 
@@ -300,10 +313,10 @@ static void route_desc(kv_shard* sh, long long n, MultiDesc& d) {
 // straight into the records the ids were sent in (k_papply PA_DEDUP over the route's entries, in the route's partitioning)
 static void presum_desc(kv_shard* sh, const float* grad, MultiDesc& d) {
   kv_table* rt = sh->route;
-  d.w = ws_view(rt, sh->n_last);
+  d.w = ws_view(rt, sh->batch.n());
   if (rt->batch.P()) use_partitions(d.w, rt->batch.P());
   PartArgs& pa = d.a;
-  pa = self_part_args(rt, sh->n_last);
+  pa = self_part_args(rt, sh->batch.n());
   pa.grad = grad;
   pa.out_sum = sh->send_rows;
   pa.out_map = sh->slot_of;
@@ -317,8 +330,8 @@ static FinishDesc finish_desc(const kv_shard* sh, float* out) {
   const kv_table* rt = sh->route;
   FinishDesc d{};
   d.pos_ent = rt->ws.pos_ent; d.ent_u = rt->ws.ent_b; d.slot_of = sh->slot_of; d.rows = sh->recv_rows; d.out = out;
-  d.n = sh->n_last; d.rows_self = sh->send_rows;
-  d.self_lo = (unsigned)sh->rank * (sh->C + 1); d.self_len = sh->self_in_place ? sh->C + 1 : 0u;
+  d.n = sh->batch.n(); d.rows_self = sh->send_rows;
+  d.self_lo = (unsigned)sh->rank * (sh->C + 1); d.self_len = sh->batch.own_segment_stays() ? sh->C + 1 : 0u;
   d.dim = rt->dim;
   return d;
 }
@@ -365,57 +378,22 @@ static int sparse_presum_check(const char* what, const float* seg_grad, const vo
   return KV_OK;
 }
 
-// the shard's route index is the one of the batch it last routed (an empty batch leaves no index and no token)
-static bool shard_route_holds(const kv_shard* sh) {
-  return sh->n_last > 0 ? sh->route->batch.holds(sh->route_token, sh->n_last) : sh->empty_routed;
-}
-
 // a route with nothing to send — an empty batch, or one that failed or was refused: void headers in the send buffer, so that
 // the peers are not left waiting
 static int shard_void_route(kv_shard* sh, hipStream_t w) {
-  sh->n_last = 0; sh->route_token = 0; sh->empty_routed = false; sh->read_only_last = false;
+  sh->batch.route_voided();
   HIP_TRY(hipMemsetAsync(sh->counts, 0, (size_t)sh->world * 8, w));
   k_seg_headers<<<1, MAXW, 0, w>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
   return KV_OK;
 }
 
-// ids -> local unique ids with counts -> the owners' segments of the send buffer.  2 launches (deterministic mode: 6), no host sync.
-static int lookup_route_impl(kv_shard_t sh, const void* ids, int64_t n, kv_stream_t stream) {
-  if (!sh || (n > 0 && !ids) || n < 0 || n > sh->max_ids) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_route: n %lld (max %lld)", (long long)n, sh ? sh->max_ids : 0ll);
-  DeviceGuard dg(sh->table->device);
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  kv_table* rt = sh->route;
-  std::lock_guard<std::mutex> l(rt->mu);
-  if ((rc = hand_over(rt, s))) return rc;   // the phases of one shard keep their order whatever streams they are given
-  rt->deterministic = sh->table->deterministic;   // the route index (tile pass, position order) follows the table's mode
-  sh->n_last = n;
-  sh->route_token = 0;
-  sh->empty_routed = false;
-  sh->read_only_last = false;   // a new batch: whoever serves it says what it is
-  if (n == 0) {   // an empty batch: void headers
-    if ((rc = shard_void_route(sh, s))) return rc;
-    sh->empty_routed = true;
-    return KV_OK;
-  }
-  if ((rc = ensure_workspace(rt, n, true, s)) || (rc = ensure_pos_ent(rt, n, s))) return rc;
-  MultiDesc d{};
-  route_desc(sh, n, d);
-  launch_ltile_notable(rt, d.a.tv, d.w, ids, n, s);
-  WsDev wd = d.w;
-  wd.zero_counts = nullptr; wd.pos_ent = nullptr;   // (the tile pass alone files those)
-  if ((rc = launch_papply_ud(wd, d.a, PA_UNIQUE, s))) return fail(rc, "route: no kernel for dim %d", rt->dim);
-  sh->route_token = rt->batch.publish(++g_serial, n, BatchIndex::ENTRIES, d.w.P);
-  if (d.a.det) {   // the ordered owner scatter
-    const unsigned ntr = (unsigned)((n + RT - 1) / RT);
-    k_owner_hist_u32<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, (long long)n, sh->world, sh->rule, ntr, sh->hist);
-    k_owner_scan<<<1, 1024, 0, s>>>(sh->hist, ntr * sh->world, ntr, sh->world, sh->counts);
-    k_seg_headers<<<1, MAXW, 0, s>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
-    k_owner_scatter_fixed<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, (long long)n, sh->world, sh->rule, ntr, sh->hist, sh->C, sh->send_pairs,
-                                             sh->slot_of, sh->overflow);
-  }
-  HIP_TRY(hipGetLastError());
-  return KV_OK;
+static const int ONLY = 0;   // the todo list of a one-table call: shards[0]
+// the shards' route tables, locked: every route-side phase holds them from its checks to its last launch
+static MultiLock route_locks(const kv_shard_t* shards, const int* todo, int m) {
+  if (m == 1) return MultiLock(shards[todo[0]]->route);   // (one mutex, nothing allocated)
+  std::vector<kv_table*> rts;
+  for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
+  return MultiLock(std::move(rts));
 }
 
 static int shard_fork(kv_shard* sh, hipStream_t s, hipStream_t work) {
@@ -484,7 +462,7 @@ static int shard_agree_many(const kv_shard_t* shards, int ntab, kv_comm* comm, h
         bad = rccl()->AllReduce(shards[k]->need, shards[k]->need + 1, 1, ncclUint32, ncclMax, comm->comm, w);
     const ncclResult_t e = rccl()->GroupEnd();
     if (bad == ncclSuccess) bad = e;
-    if (bad != ncclSuccess) return fail(KV_INTERNAL, "ncclAllReduce failed: %s", rccl()->GetErrorString ? rccl()->GetErrorString(bad) : "?");
+    if (bad != ncclSuccess) return fail(KV_INTERNAL, "ncclAllReduce failed: %s", nccl_err(bad));
   }
   for (int k = 0; k < ntab; ++k)
     if (shards[k]->lossless)
@@ -502,14 +480,8 @@ static int shard_agree_many(const kv_shard_t* shards, int ntab, kv_comm* comm, h
   }
   for (int k = 0; k < ntab; ++k) {
     kv_shard* sh = shards[k];
-    if (!sh->lossless) continue;
-    const unsigned need = *sh->need_host;
-    if (need <= sh->C) continue;
-    const long long newC = std::min<long long>(sh->max_ids, (long long)need + need / 4 + 64);
-    int rc;
-    if ((rc = shard_alloc_buffers(sh, (unsigned)newC))) return rc;
-    *reinterpret_cast<volatile unsigned*>(sh->overflow) = 0;   // raised by the attempt that is now repeated
-    ++sh->grows;
+    if (!sh->lossless || *sh->need_host <= sh->C) continue;
+    if (int rc = shard_grow(sh, *sh->need_host, sh->max_ids)) return rc;
     grown[k] = 1;
   }
   return KV_OK;
@@ -529,80 +501,103 @@ static int multi_shard_check(const kv_shard_t* shards, int ntab, kv_comm_t comm,
   return KV_OK;
 }
 
-// ---- several sharded tables, one launch per phase -----------------------------------------------------
-// The route-side phases of kv_multi_shard_* run on the shards' private route tables; a table takes part in the batched
-// launches when its route is the entry-list one without the ordered owner scatter (not the deterministic mode, a batch
-// that is not empty); the others go through the per-table functions as before.
+// ---- the route-side phases, each over the tables todo[0..m) --------------------------------------------
+// On the shards' private route tables; every check and every buffer that may have to grow comes before the first launch.  m > 1:
+// one launch for all tables, their descriptors staged; m == 1: the single-table kernels, the descriptor by value, nothing staged.
+// A table joins a batched ROUTE when it has no ordered owner scatter (not the deterministic mode) and its batch is not empty.
 static bool shard_batchable(const kv_shard* sh, int64_t n) {
   return !sh->table->deterministic && n > 0 && n <= sh->max_ids;
 }
 
-// route of the tables todo[0..m): the table-less tile pass of all of them (grid.y = table), then k_papply_multi in
-// PA_UNIQUE mode — numbering, the owners' segments, and each table's headers by its own last block.  2 launches.
-static int multi_route_impl(const kv_shard_t* shards, const int* todo, int m, const void* const* ids, const int64_t* n, hipStream_t s) {
+// route: the table-less tile pass (m > 1: grid.y = table), then k_papply in PA_UNIQUE mode — numbering, the owners' segments, each
+// table's headers by its own last block.  m == 1 alone: the deterministic mode's ordered owner scatter, an empty batch's void route.
+static int route_impl(const char* what, const kv_shard_t* shards, const int* todo, int m, const void* const* ids, const int64_t* n, hipStream_t s) {
   int rc;
-  std::vector<kv_table*> rts;
-  for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
-  MultiLock lock(rts);
+  for (int j = 0; j < m; ++j)
+    if (const int k = todo[j]; (n[k] > 0 && !ids[k]) || n[k] < 0 || n[k] > shards[k]->max_ids)
+      return fail(KV_INVALID_ARGUMENT, "%s: n %lld (max %lld)", what, (long long)n[k], shards[k]->max_ids);
+  MultiLock lock = route_locks(shards, todo, m);
   for (int j = 0; j < m; ++j) {
     kv_shard* sh = shards[todo[j]];
     kv_table* rt = sh->route;
-    if ((rc = hand_over(rt, s))) return rc;
-    rt->deterministic = false;
-    sh->n_last = n[todo[j]];
-    sh->route_token = 0;
-    sh->empty_routed = false;
-    sh->read_only_last = false;
-    if ((rc = ensure_workspace(rt, sh->n_last, true, s)) || (rc = ensure_pos_ent(rt, sh->n_last, s))) return rc;
+    if ((rc = hand_over(rt, s))) return rc;   // the phases of one shard keep their order whatever streams they are given
+    rt->deterministic = sh->table->deterministic;   // the route index (tile pass, position order) follows the table's mode
+    sh->batch.begin_route(n[todo[j]]);
+    if (sh->batch.n() > 0 && ((rc = ensure_workspace(rt, sh->batch.n(), true, s)) || (rc = ensure_pos_ent(rt, sh->batch.n(), s)))) return rc;
   }
-  Staged<MultiDesc> hd(shards[todo[0]]->table->device, 1, m);
-  if (hd.rc) return hd.rc;
-  WsDev wmax{};
-  for (int j = 0; j < m; ++j) {
-    kv_shard* sh = shards[todo[j]];
-    route_desc(sh, sh->n_last, hd[j]);
-    hd[j].ids = ids[todo[j]];
-    hd[j].n = sh->n_last;
-    widen(wmax, hd[j].w);
-  }
-  const MultiDesc* md;
-  if ((rc = hd.upload(s, &md))) return rc;
-  launch_ltile_multi_notable(wmax, m, md, s);
-  // (PA_UNIQUE never reaches the code that depends on the row geometry: one variant serves every dim)
-  PartArgs p0 = hd[0].a;
-  p0.tv.dim = 4;
-  if ((rc = launch_papply_ud(wmax, p0, PA_UNIQUE, s, md, m))) return fail(rc, "route: no kernel");
-  for (int j = 0; j < m; ++j) {
-    kv_shard* sh = shards[todo[j]];
-    kv_table* rt = sh->route;
-    sh->route_token = rt->batch.publish(++g_serial, sh->n_last, BatchIndex::ENTRIES, hd[j].w.P);
+  if (m == 1) {
+    kv_shard* sh = shards[todo[0]];
+    const long long n0 = sh->batch.n();
+    if (n0 == 0) {   // an empty batch: void headers
+      if ((rc = shard_void_route(sh, s))) return rc;
+      sh->batch.routed_empty();
+      return KV_OK;
+    }
+    MultiDesc d{};
+    route_desc(sh, n0, d);
+    launch_ltile_notable(sh->route, d.a.tv, d.w, ids[todo[0]], n0, s);
+    WsDev wd = d.w;
+    wd.zero_counts = nullptr; wd.pos_ent = nullptr;   // (the tile pass alone files those)
+    if ((rc = launch_papply_ud(wd, d.a, PA_UNIQUE, s))) return fail(rc, "route: no kernel for dim %d", d.a.tv.dim);
+    sh->batch.route_published(sh->route->batch.publish(++g_serial, n0, BatchIndex::ENTRIES, d.w.P));
+    if (d.a.det) {   // the ordered owner scatter
+      const unsigned ntr = (unsigned)((n0 + RT - 1) / RT);
+      k_owner_hist_u32<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, n0, sh->world, sh->rule, ntr, sh->hist);
+      k_owner_scan<<<1, 1024, 0, s>>>(sh->hist, ntr * sh->world, ntr, sh->world, sh->counts);
+      k_seg_headers<<<1, MAXW, 0, s>>>(sh->counts, sh->world, sh->C, sh->send_pairs, sh->need);
+      k_owner_scatter_fixed<<<ntr, TB, 0, s>>>(sh->uniq, sh->ucnt, n0, sh->world, sh->rule, ntr, sh->hist, sh->C, sh->send_pairs, sh->slot_of, sh->overflow);
+    }
+  } else {
+    Staged<MultiDesc> hd(shards[todo[0]]->table->device, 1, m);
+    if (hd.rc) return hd.rc;
+    WsDev wmax{};
+    for (int j = 0; j < m; ++j) {
+      kv_shard* sh = shards[todo[j]];
+      route_desc(sh, sh->batch.n(), hd[j]);
+      hd[j].ids = ids[todo[j]]; hd[j].n = sh->batch.n();
+      widen(wmax, hd[j].w);
+    }
+    const MultiDesc* md;
+    if ((rc = hd.upload(s, &md))) return rc;
+    launch_ltile_multi_notable(wmax, m, md, s);
+    // (PA_UNIQUE never reaches the code that depends on the row geometry: one variant serves every dim)
+    PartArgs p0 = hd[0].a;
+    p0.tv.dim = 4;
+    if ((rc = launch_papply_ud(wmax, p0, PA_UNIQUE, s, md, m))) return fail(rc, "route: no kernel for dim %d", hd[0].a.tv.dim);
+    for (int j = 0; j < m; ++j)
+      shards[todo[j]]->batch.route_published(shards[todo[j]]->route->batch.publish(++g_serial, hd[j].n, BatchIndex::ENTRIES, hd[j].w.P));
   }
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
 
-// finish of the tables todo[0..m) — all of one row geometry (row_lanes(dim)): 1 launch
-static int multi_finish_impl(const kv_shard_t* shards, const int* todo, int m, float* const* outs, hipStream_t s) {
+// finish, out[i] = the row that came back for ids[i]: tables of one row geometry (row_lanes(dim)), no empty batch.  1 launch
+static int finish_impl(const char* what, const kv_shard_t* shards, const int* todo, int m, float* const* outs, hipStream_t s) {
   int rc;
-  std::vector<kv_table*> rts;
-  for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
-  MultiLock lock(rts);
-  Staged<FinishDesc> hd(shards[todo[0]]->table->device, 1, m);
-  if (hd.rc) return hd.rc;
+  MultiLock lock = route_locks(shards, todo, m);
   long long nmax = 0;
   for (int j = 0; j < m; ++j) {
     kv_shard* sh = shards[todo[j]];
-    kv_table* rt = sh->route;
-    if (!rt->batch.holds(sh->route_token, sh->n_last)) return fail(KV_FAILED_PRECONDITION, "kv_multi_shard_lookup: finish without route");
-    if (!outs[todo[j]]) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_lookup: output pointer is null");
-    if ((rc = hand_over(rt, s))) return rc;
-    hd[j] = finish_desc(sh, outs[todo[j]]);
-    nmax = std::max<long long>(nmax, sh->n_last);
+    if (!sh->batch.route_holds_ids(sh->route->batch)) return fail(KV_FAILED_PRECONDITION, "%s: finish without kv_shard_lookup_route", what);
+    if (!outs[todo[j]]) return fail(KV_INVALID_ARGUMENT, "%s: output pointer is null", what);
+    if ((rc = hand_over(sh->route, s))) return rc;
+    nmax = std::max(nmax, sh->batch.n());
   }
-  const FinishDesc* md;
-  if ((rc = hd.upload(s, &md))) return rc;
-  const dim3 grid((unsigned)nblocks(nmax, TB, 8192), (unsigned)m);
-  with_lanes(row_lanes(shards[todo[0]]->table->dim), [&](auto vq) { k_shard_finish_multi<decltype(vq)::value><<<grid, TB, 0, s>>>(md); });
+  const unsigned gx = (unsigned)nblocks(nmax, TB, 8192);
+  const int q = row_lanes(shards[todo[0]]->table->dim);
+  if (m == 1) {
+    const FinishDesc d = finish_desc(shards[todo[0]], outs[todo[0]]);
+    with_lanes(q, [&](auto vq) {
+      k_shard_finish<decltype(vq)::value><<<gx, TB, 0, s>>>(d.pos_ent, d.ent_u, d.slot_of, d.rows, d.out, d.n, d.dim, d.rows_self, d.self_lo, d.self_len);
+    });
+  } else {
+    Staged<FinishDesc> hd(shards[todo[0]]->table->device, 1, m);
+    if (hd.rc) return hd.rc;
+    for (int j = 0; j < m; ++j) hd[j] = finish_desc(shards[todo[j]], outs[todo[j]]);
+    const FinishDesc* md;
+    if ((rc = hd.upload(s, &md))) return rc;
+    with_lanes(q, [&](auto vq) { k_shard_finish_multi<decltype(vq)::value><<<dim3(gx, (unsigned)m), TB, 0, s>>>(md); });
+  }
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -612,16 +607,14 @@ static int multi_finish_impl(const kv_shard_t* shards, const int* todo, int m, f
 static int finish_sparse_impl(const char* what, const kv_shard_t* shards, const int* todo, int m, const SparseArgs& sp,
                               float* const* outs, hipStream_t s) {
   int rc;
-  std::vector<kv_table*> rts;
-  for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
-  MultiLock lock(rts);
+  MultiLock lock = route_locks(shards, todo, m);
   const int q = row_lanes(shards[todo[0]]->table->dim);
   std::vector<FinishSparseDesc> ds(m);
   long long work = 0;   // lanes of the table with the most of them
   for (int j = 0; j < m; ++j) {
     const int k = todo[j];
     kv_shard* sh = shards[k];
-    if (!shard_route_holds(sh)) return fail(KV_FAILED_PRECONDITION, "%s: finish without kv_shard_lookup_route", what);
+    if (!sh->batch.route_holds(sh->route->batch)) return fail(KV_FAILED_PRECONDITION, "%s: finish without kv_shard_lookup_route", what);
     if ((rc = hand_over(sh->route, s))) return rc;
     ds[j] = finish_sparse_desc(sh, sp.seg[k], sp.w(k), sp.nseg[k], outs[k]);
     work = std::max<long long>(work, sp.nseg[k] * q);
@@ -656,8 +649,7 @@ static int serve_zeros_impl(const kv_shard_t* shards, const int* todo, int m, hi
   unsigned gx = 1;
   for (int j = 0; j < m; ++j) {
     kv_shard* sh = shards[todo[j]];
-    sh->serve_token = 0;
-    sh->read_only_last = true;
+    sh->batch.served_read_only();
     tbs.push_back(sh->table);
   }
   for (int j = 0; j < m; ++j)
@@ -673,7 +665,7 @@ static int serve_zeros_impl(const kv_shard_t* shards, const int* todo, int m, hi
     d.t = dev_view(sh->table);
     d.pairs = sh->recv_pairs; d.pairs_self = sh->send_pairs; d.rows = sh->send_rows;
     d.C = sh->C; d.world = sh->world;
-    d.self_seg = sh->self_in_place ? sh->rank : -1;
+    d.self_seg = sh->batch.own_segment_stays() ? sh->rank : -1;
     // one 64-record step per wave were every segment full (the waves past the live records leave at once)
     gx = std::max(gx, (unsigned)nblocks((long long)sh->world * sh->C, TB, 8192));
   }
@@ -689,41 +681,42 @@ static int serve_zeros_impl(const kv_shard_t* shards, const int* todo, int m, hi
 // gradients into the wrong records.  Refused before anything is queued — every rank made the same calls, so every rank
 // refuses alike and no peer is left waiting in a grouped recv.
 static int shard_refuse_apply(const kv_shard* sh, const char* what) {
-  if (!sh->read_only_last) return KV_OK;
+  if (sh->batch.may_apply()) return KV_OK;
   return fail(KV_FAILED_PRECONDITION, "%s: the shard's last served batch was a read-only lookup (kv_shard_lookup_zeros / "
                                       "kv_shard_lookup_serve_zeros), which leaves nothing to apply — nothing was queued; run the "
                                       "training lookup of the batch first", what);
 }
 
-// gradient pre-sum of the tables todo[0..m) — all of one dim, none in deterministic mode: the tile sums, then k_papply_multi
-// PA_DEDUP.  2 launches.
-static int multi_presum_impl(const kv_shard_t* shards, const int* todo, int m, const float* const* grads, hipStream_t s) {
+// gradient pre-sum (tables of one dim, no empty batch; m > 1: none in deterministic mode): the tile sums, then k_papply PA_DEDUP
+static int presum_impl(const char* what, const kv_shard_t* shards, const int* todo, int m, const float* const* grads, hipStream_t s) {
   int rc;
-  std::vector<kv_table*> rts;
-  for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
-  MultiLock lock(rts);
+  MultiLock lock = route_locks(shards, todo, m);
   for (int j = 0; j < m; ++j) {
     kv_shard* sh = shards[todo[j]];
-    kv_table* rt = sh->route;
-    if (!rt->batch.holds(sh->route_token, sh->n_last))
-      return fail(KV_FAILED_PRECONDITION, "kv_multi_shard_apply: the batch's lookup must come first");
-    if (!grads[todo[j]]) return fail(KV_INVALID_ARGUMENT, "kv_multi_shard_apply: grad pointer is null");
-    if ((rc = hand_over(rt, s))) return rc;
-    if ((rc = ensure_workspace(rt, sh->n_last, true, s))) return rc;
+    if (!sh->batch.route_holds_ids(sh->route->batch)) return fail(KV_FAILED_PRECONDITION, "%s: the batch's lookup must come first (kv_shard_lookup_route)", what);
+    if (!grads[todo[j]]) return fail(KV_INVALID_ARGUMENT, "%s: grad pointer is null", what);
+    if ((rc = hand_over(sh->route, s))) return rc;
+    if ((rc = ensure_workspace(sh->route, sh->batch.n(), true, s))) return rc;
   }
-  Staged<MultiDesc> hd(shards[todo[0]]->table->device, 1, m);
-  if (hd.rc) return hd.rc;
-  WsDev wmax{};
-  for (int j = 0; j < m; ++j) {
-    presum_desc(shards[todo[j]], grads[todo[j]], hd[j]);
-    hd[j].a.det = 0;
-    hd[j].n = hd[j].a.n;
-    widen(wmax, hd[j].w);
+  if (m == 1) {
+    MultiDesc d{};
+    presum_desc(shards[todo[0]], grads[todo[0]], d);
+    if ((rc = launch_tsum(d.a.tv, d.w, d.a.grad, s))) return fail(rc, "tile sums: no kernel for dim %d", d.a.tv.dim);
+    if ((rc = launch_papply_ud(d.w, d.a, PA_DEDUP, s))) return fail(rc, "gradient pre-sum: no kernel for dim %d", d.a.tv.dim);
+  } else {
+    Staged<MultiDesc> hd(shards[todo[0]]->table->device, 1, m);
+    if (hd.rc) return hd.rc;
+    WsDev wmax{};
+    for (int j = 0; j < m; ++j) {
+      presum_desc(shards[todo[j]], grads[todo[j]], hd[j]);
+      hd[j].a.det = 0; hd[j].n = hd[j].a.n;
+      widen(wmax, hd[j].w);
+    }
+    const MultiDesc* md;
+    if ((rc = hd.upload(s, &md))) return rc;
+    if ((rc = launch_tsum(hd[0].a.tv, wmax, nullptr, s, md, m))) return fail(rc, "tile sums: no kernel for dim %d", hd[0].a.tv.dim);
+    if ((rc = launch_papply_ud(wmax, hd[0].a, PA_DEDUP, s, md, m))) return fail(rc, "gradient pre-sum: no kernel for dim %d", hd[0].a.tv.dim);
   }
-  const MultiDesc* md;
-  if ((rc = hd.upload(s, &md))) return rc;
-  if ((rc = launch_tsum(hd[0].a.tv, wmax, nullptr, s, md, m))) return fail(rc, "tile sums: no kernel for dim %d", hd[0].a.tv.dim);
-  if ((rc = launch_papply_ud(wmax, hd[0].a, PA_DEDUP, s, md, m))) return fail(rc, "gradient pre-sum: no kernel for dim %d", hd[0].a.tv.dim);
   HIP_TRY(hipGetLastError());
   return KV_OK;
 }
@@ -736,15 +729,13 @@ static int multi_presum_impl(const kv_shard_t* shards, const int* todo, int m, c
 static int presum_sparse_impl(const char* what, const kv_shard_t* shards, const int* todo, int m, const float* const* grads,
                               const SparseArgs& sp, hipStream_t s) {
   int rc;
-  std::vector<kv_table*> rts;
-  for (int j = 0; j < m; ++j) rts.push_back(shards[todo[j]]->route);
-  MultiLock lock(rts);
+  MultiLock lock = route_locks(shards, todo, m);
   for (int j = 0; j < m; ++j) {
     const int k = todo[j];
     kv_shard* sh = shards[k];
-    if (!sh->route->batch.holds(sh->route_token, sh->n_last))
+    if (!sh->batch.route_holds_ids(sh->route->batch))
       return fail(KV_FAILED_PRECONDITION, "%s: the batch's lookup must come first (kv_shard_lookup_route)", what);
-    if ((rc = sparse_presum_check(what, grads[k], sp.seg[k], sp.seg_dtype, sh->n_last, sp.nseg[k], sp.combiner))) return rc;
+    if ((rc = sparse_presum_check(what, grads[k], sp.seg[k], sp.seg_dtype, sh->batch.n(), sp.nseg[k], sp.combiner))) return rc;
   }
   std::vector<SegDesc> sd(m);
   for (int j = 0; j < m; ++j) {
@@ -753,12 +744,12 @@ static int presum_sparse_impl(const char* what, const kv_shard_t* shards, const 
     kv_table* rt = sh->route;
     const bool need_den = sp.w(k) != nullptr && sp.combiner != KV_COMBINER_SUM;
     if ((rc = hand_over(rt, s))) return rc;
-    if ((rc = ensure_workspace(rt, sh->n_last, true, s)) || (rc = ensure_seg(rt, sp.nseg[k], need_den, s)) ||
-        (rc = ensure_pos_records(rt, sh->n_last, s)))
+    if ((rc = ensure_workspace(rt, sh->batch.n(), true, s)) || (rc = ensure_seg(rt, sp.nseg[k], need_den, s)) ||
+        (rc = ensure_pos_records(rt, sh->batch.n(), s)))
       return rc;
     SegDesc& q = sd[j];
     q.seg = sp.seg[k]; q.wts = sp.w(k); q.off = rt->ws.seg_off; q.den = need_den ? rt->ws.seg_den : nullptr;
-    q.pseg = rt->ws.pseg; q.pscale = rt->ws.pscale; q.n = sh->n_last; q.nseg = sp.nseg[k];
+    q.pseg = rt->ws.pseg; q.pscale = rt->ws.pscale; q.n = sh->batch.n(); q.nseg = sp.nseg[k];
     q.src = SegSrc{grads[k], rt->ws.pseg, rt->ws.pscale};
   }
   const int seg32 = sp.seg_dtype == KV_DT_INT32;
@@ -815,7 +806,8 @@ static int shards_exchange(const kv_shard_t* shards, int ntab, kv_comm* comm, bo
   for (int k = 0; k < ntab; ++k) {
     const kv_shard* sh = shards[k];
     const SegBytes b = shard_bytes(sh, !wired(comm));
-    seg[k] = rows ? Seg{sh->send_rows, sh->recv_rows, b.rows, sh->self_in_place} : Seg{sh->send_pairs, sh->recv_pairs, b.pairs, sh->self_in_place};
+    const bool stay = sh->batch.own_segment_stays();
+    seg[k] = rows ? Seg{sh->send_rows, sh->recv_rows, b.rows, stay} : Seg{sh->send_pairs, sh->recv_pairs, b.pairs, stay};
   }
   return comm_exchange(comm, ntab, seg.data(), w);
 }
@@ -844,7 +836,7 @@ static std::vector<std::vector<int>> groups_of(int ntab, Key key) {
 
 // the owner side of a table can join a batched lookup / apply over the receive buffers
 static bool shard_owner_batchable(const kv_shard* sh) {
-  return sh->table->key_dtype == KV_DT_INT64 && (long long)sh->world * (sh->C + 1) <= (1ll << 21);
+  return sh->table->key_dtype == KV_DT_INT64 && shard_nrec(sh) <= (1ll << 21);
 }
 
 // Forked from `s` onto the communicator's stream (the caller's stream is free for the dense tower; phases and exchanges in
@@ -880,28 +872,28 @@ static int shards_lookup(const char* what, bool single, bool read_only, const kv
   auto sparse = [&](int k) { return sp && sp->sparse(k); };
   for (int k = 0; k < ntab; ++k)
     if (sparse(k) && note(sparse_finish_check(what, sp->seg[k], sp->seg_dtype, n[k], sp->nseg[k], sp->combiner, outs[k]))) routed[k] = 0;
-  for (int k = 0; k < ntab; ++k) shards[k]->self_in_place = shard_can_stay(shards[k]);
+  for (int k = 0; k < ntab; ++k) shards[k]->batch.exchanged_by_library(shard_can_stay(shards[k]));
   const bool pm = single && !read_only && shard_prof_begin(sh0, true);
   shard_prof_mark(sh0, pm, 0, w);
-  auto route = [&](int k) -> int {
-    if (routed[k] && note(lookup_route_impl(shards[k], ids[k], n[k], w))) routed[k] = 0;
-    return routed[k] ? KV_OK : shard_void_route(shards[k], w);
+  auto route = [&](const int* todo, int m) {   // false: refused or failed — void headers are due, the peers are not left waiting
+    const bool ok = routed[todo[0]] && !note(route_impl(what, shards, todo, m, ids, n, w));
+    for (int j = 0; j < m; ++j) routed[todo[j]] = ok;
+    return ok;
   };
-  // the tables whose route is the entry-list one go together: 2 launches for all of them
-  for (const auto& grp : groups_of(ntab, [&](int k) { return routed[k] && shard_batchable(shards[k], n[k]) ? 0 : -1; })) {
-    const bool ok = !note(multi_route_impl(shards, grp.data(), (int)grp.size(), ids, n, w));
-    for (int k : grp) { routed[k] = ok; done[k] = ok; }   // (failed: void headers below, the peers are not left waiting)
-  }
+  // the tables whose route is the entry-list one go together: 2 launches for all of them; then the others, one by one
+  for (const auto& grp : groups_of(ntab, [&](int k) { return routed[k] && shard_batchable(shards[k], n[k]) ? 0 : -1; }))
+    if (route(grp.data(), (int)grp.size()))
+      for (int k : grp) done[k] = 1;
   for (int k = 0; k < ntab; ++k)
-    if (!done[k] && (rc = route(k))) return rc;
+    if (!done[k] && !route(&k, 1) && (rc = shard_void_route(shards[k], w))) return rc;
   {   // lossless tables: one agreement for all of them (every rank takes part, whatever its own route did), then the grown
       // ones are routed again — or, where this rank's batch was refused, get void headers in the new buffers too
     std::vector<char> grown(ntab, 0);
     if ((rc = shard_agree_many(shards, ntab, comm, w, grown.data()))) return rc;
     for (int k = 0; k < ntab; ++k)
       if (grown[k]) {
-        shards[k]->self_in_place = shard_can_stay(shards[k]);   // (the record count changed)
-        if ((rc = route(k))) return rc;
+        shards[k]->batch.exchanged_by_library(shard_can_stay(shards[k]));   // (the record count changed)
+        if (!route(&k, 1) && (rc = shard_void_route(shards[k], w))) return rc;
       }
   }
   shard_prof_mark(sh0, pm, 1, w);
@@ -934,15 +926,15 @@ static int shards_lookup(const char* what, bool single, bool read_only, const kv
     std::vector<SelfSegment> selfs(m);
     for (int j = 0; j < m; ++j) {
       kv_shard* sh = shards[grp[j]];
-      tb[j] = sh->table; ip[j] = sh->recv_pairs; nn[j] = (int64_t)sh->world * (sh->C + 1); op[j] = sh->send_rows; caps[j] = sh->C + 1;
-      sh->serve_token = 0;
+      tb[j] = sh->table; ip[j] = sh->recv_pairs; nn[j] = shard_nrec(sh); op[j] = sh->send_rows; caps[j] = sh->C + 1;
+      sh->batch.serve_begins();
       selfs[j] = shard_self(sh, false);
     }
     if (note(multi_lookup_impl(m, tb.data(), ip.data(), nullptr, nn.data(), op.data(), tok.data(), w, 2, caps.data(), selfs.data()))) {
       for (int k : grp)
         if ((rc = shard_zero_rows(shards[k], w))) return rc;
     } else {
-      for (int j = 0; j < m; ++j) shards[grp[j]]->serve_token = tok[j];
+      for (int j = 0; j < m; ++j) shards[grp[j]]->batch.served(tok[j]);
     }
     for (int k : grp) done[k] = 1;
   }
@@ -954,11 +946,12 @@ static int shards_lookup(const char* what, bool single, bool read_only, const kv
   // finish, of every table whose own route succeeded: the tables of one row geometry in one launch — the plain ones, then
   // the combining ones (an empty batch still writes its segments)
   done.assign(ntab, 0);
-  for (const auto& grp : groups_of(ntab, [&](int k) { return routed[k] && !sparse(k) && shards[k]->n_last > 0 ? row_lanes(shards[k]->table->dim) : -1; }))
-    if (!note(multi_finish_impl(shards, grp.data(), (int)grp.size(), outs, w)))
+  auto plain = [&](int k) { return routed[k] && !sparse(k) && shards[k]->batch.n() > 0; };
+  for (const auto& grp : groups_of(ntab, [&](int k) { return plain(k) ? row_lanes(shards[k]->table->dim) : -1; }))
+    if (!note(finish_impl(what, shards, grp.data(), (int)grp.size(), outs, w)))
       for (int k : grp) done[k] = 1;
   for (int k = 0; k < ntab; ++k)
-    if (routed[k] && !done[k] && !sparse(k)) note(kv_shard_lookup_finish(shards[k], outs[k], w));
+    if (plain(k) && !done[k]) note(finish_impl(what, shards, &k, 1, outs, w));
   for (const auto& grp : groups_of(ntab, [&](int k) { return routed[k] && sparse(k) && sp->nseg[k] > 0 ? row_lanes(shards[k]->table->dim) : -1; })) {
     note(finish_sparse_impl(what, shards, grp.data(), (int)grp.size(), *sp, outs, w));
     for (int k : grp) done[k] = 1;
@@ -994,18 +987,16 @@ static int shards_apply(const char* what, bool single, const kv_shard_t* shards,
   shard_prof_mark(sh0, pm, 6, w);
   // gradient pre-sum: the tables of one dim whose route has no ordered owner scatter in two launches
   std::vector<char> done(ntab, 0);   // 1: summed; 2: its group failed (zero gradient rows)
+  auto presum = [&](const int* todo, int m) {   // (a group is all sparse or all plain)
+    return sparse(todo[0]) ? presum_sparse_impl(what, shards, todo, m, grads, *sp, w) : presum_impl(what, shards, todo, m, grads, w);
+  };
   for (const auto& grp : groups_of(ntab, [&](int k) {
-         return shards[k]->n_last > 0 && !shards[k]->table->deterministic ? shards[k]->table->dim * 2 + (sparse(k) ? 1 : 0) : -1; })) {
-    const char r = note(sparse(grp[0]) ? presum_sparse_impl(what, shards, grp.data(), (int)grp.size(), grads, *sp, w)
-                                       : multi_presum_impl(shards, grp.data(), (int)grp.size(), grads, w)) ? 2 : 1;
+         return shards[k]->batch.n() > 0 && !shards[k]->table->deterministic ? shards[k]->table->dim * 2 + (sparse(k) ? 1 : 0) : -1; })) {
+    const char r = note(presum(grp.data(), (int)grp.size())) ? 2 : 1;
     for (int k : grp) done[k] = r;
   }
-  auto presum_one = [&](int k) {
-    return sparse(k) ? kv_shard_apply_route_sparse(shards[k], grads[k], sp->seg[k], sp->seg_dtype, sp->w(k), sp->nseg[k], sp->combiner, w)
-                     : kv_shard_apply_route(shards[k], grads[k], w);
-  };
-  for (int k = 0; k < ntab; ++k)
-    if (done[k] != 1 && (done[k] == 2 || note(presum_one(k))) && (rc = shard_zero_rows(shards[k], w))) return rc;
+  for (int k = 0; k < ntab; ++k)   // the others one by one (an empty batch has nothing to sum)
+    if (done[k] != 1 && (done[k] == 2 || (shards[k]->batch.n() > 0 && note(presum(&k, 1)))) && (rc = shard_zero_rows(shards[k], w))) return rc;
   shard_prof_mark(sh0, pm, 7, w);
   if ((rc = shards_exchange(shards, ntab, comm, true, w))) return rc;
   shard_prof_mark(sh0, pm, 8, w);
@@ -1013,7 +1004,7 @@ static int shards_apply(const char* what, bool single, const kv_shard_t* shards,
   done.assign(ntab, 0);
   for (const auto& grp : groups_of(ntab, [&](int k) {
          const kv_shard* sh = shards[k];
-         const BatchIndex::Plan served = sh->table->batch.plan(sh->serve_token, (long long)sh->world * (sh->C + 1), fused_tab(sh->table));
+         const BatchIndex::Plan served = sh->table->batch.plan(sh->batch.serve_token(), shard_nrec(sh), fused_tab(sh->table));
          return optimizer >= 0 && optimizer <= OPT_ADAM && shard_owner_batchable(sh) && BatchIndex::takes_entries(served) && slot0[k] != nullptr &&
                         (!two_slots(optimizer) || (slot1 && slot1[k]))
                     ? sh->table->dim : -1; })) {
@@ -1027,7 +1018,7 @@ static int shards_apply(const char* what, bool single, const kv_shard_t* shards,
     for (int j = 0; j < m; ++j) {
       kv_shard* sh = shards[grp[j]];
       vs[j] = sh->table; s0[j] = slot0[grp[j]]; s1[j] = slot1 ? slot1[grp[j]] : nullptr;
-      gp[j] = sh->recv_rows; ip[j] = sh->recv_pairs; nn[j] = (int64_t)sh->world * (sh->C + 1); tok[j] = sh->serve_token;
+      gp[j] = sh->recv_rows; ip[j] = sh->recv_pairs; nn[j] = shard_nrec(sh); tok[j] = sh->batch.serve_token();
       selfs[j] = shard_self(sh, true);
     }
     // (require_reuse: the ids are (id, count) records — an apply that rebuilt its index from them would read them as plain ids)
@@ -1121,22 +1112,16 @@ int kv_comm_create(int world, int rank, const void* id128, int device, kv_comm_t
   if (!out || world < 1 || world > MAXW || rank < 0 || rank >= world) return fail(KV_INVALID_ARGUMENT, "kv_comm_create: world %d rank %d", world, rank);
   DeviceGuard dg(device);
   kv_comm* c = new kv_comm();
-  c->world = world; c->rank = rank; c->device = device;
   int rc = KV_OK;
   do {
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming) != hipSuccess) {
-      rc = fail(KV_INTERNAL, "kv_comm_create: stream / events");
-      break;
-    }
+    if (!comm_init(c, world, rank, device)) { rc = fail(KV_INTERNAL, "kv_comm_create: stream / events"); break; }
     if (world > 1 || id128) {   // a world of one needs no RCCL (the exchange is a device copy) unless asked for
       if (!id128) { rc = fail(KV_INVALID_ARGUMENT, "kv_comm_create: unique id is null"); break; }
       if (!rccl()->ok) { rc = fail(KV_UNIMPLEMENTED, "librccl.so.1 could not be loaded"); break; }
       ncclUniqueId id;
       std::memcpy(&id, id128, sizeof id);
       ncclResult_t r = rccl()->CommInitRank(&c->comm, world, id, rank);
-      if (r != ncclSuccess) { rc = fail(KV_INTERNAL, "ncclCommInitRank: %s", rccl()->GetErrorString ? rccl()->GetErrorString(r) : "?"); break; }
+      if (r != ncclSuccess) { rc = fail(KV_INTERNAL, "ncclCommInitRank: %s", nccl_err(r)); break; }
     }
   } while (0);
   if (rc) { kv_comm_destroy(c); return rc; }
@@ -1150,14 +1135,8 @@ int kv_comm_create_staged(int world, int rank, kv_comm_exchange_fn exchange, kv_
     return fail(KV_INVALID_ARGUMENT, "kv_comm_create_staged: world %d rank %d", world, rank);
   DeviceGuard dg(device);
   kv_comm* c = new kv_comm();
-  c->world = world; c->rank = rank; c->device = device;
   c->xfn = exchange; c->mfn = max_u32; c->user = user;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming) != hipSuccess) {
-    kv_comm_destroy(c);
-    return fail(KV_INTERNAL, "kv_comm_create_staged: stream / events");
-  }
+  if (!comm_init(c, world, rank, device)) { kv_comm_destroy(c); return fail(KV_INTERNAL, "kv_comm_create_staged: stream / events"); }
   *out = c;
   return KV_OK;
 }
@@ -1272,11 +1251,13 @@ int kv_shard_buffers(kv_shard_t sh, void** send_pairs, void** recv_pairs, void**
   return KV_OK;
 }
 
+// ids -> local unique ids with counts -> the owners' segments of the send buffer.  2 launches (deterministic mode: 6), no host sync.
 int kv_shard_lookup_route(kv_shard_t sh, const void* ids, int64_t n, kv_stream_t stream) {
-  int rc;
-  const unsigned seen = sh ? shard_take_flag(sh) : 0u;
-  if (sh) sh->self_in_place = false;   // the caller makes the exchanges: all segments, its own included, arrive in the receive buffers
-  if ((rc = lookup_route_impl(sh, ids, n, stream))) return rc;
+  if (!sh) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_route: n %lld (max %lld)", (long long)n, 0ll);
+  const unsigned seen = shard_take_flag(sh);
+  sh->batch.exchanged_by_caller();   // all segments, this rank's own included, arrive in the receive buffers
+  DeviceGuard dg(sh->table->device);
+  if (int rc = route_impl("kv_shard_lookup_route", &sh, &ONLY, 1, &ids, &n, (hipStream_t)stream)) return rc;
   return shard_late_report(sh, seen);
 }
 
@@ -1284,10 +1265,12 @@ int kv_shard_lookup_route(kv_shard_t sh, const void* ids, int64_t n, kv_stream_t
 // every occurrence — and their rows go to send_rows, record for record.  3 launches.
 int kv_shard_lookup_serve(kv_shard_t sh, kv_stream_t stream) {
   if (!sh) return fail(KV_INVALID_ARGUMENT, "null shard");
-  const int64_t nrec = (int64_t)sh->world * (sh->C + 1);
-  sh->serve_token = 0;
+  sh->batch.serve_begins();
   const SelfSegment self = shard_self(sh, false);
-  return gather_or_insert_impl(sh->table, sh->recv_pairs, nullptr, nrec, sh->send_rows, stream, 1, &sh->serve_token, sh->C + 1, &self);
+  kv_batch_token_t token = 0;   // (stays 0 where the lookup publishes nothing)
+  const int rc = gather_or_insert_impl(sh->table, sh->recv_pairs, nullptr, shard_nrec(sh), sh->send_rows, stream, 1, &token, sh->C + 1, &self);
+  sh->batch.served(token);
+  return rc;
 }
 
 // the owner's half of a READ-ONLY lookup: the rows of the ids the peers sent as kv_gather_or_zeros reads them (zeros for a
@@ -1296,27 +1279,15 @@ int kv_shard_lookup_serve(kv_shard_t sh, kv_stream_t stream) {
 int kv_shard_lookup_serve_zeros(kv_shard_t sh, kv_stream_t stream) {
   if (!sh) return fail(KV_INVALID_ARGUMENT, "null shard");
   DeviceGuard dg(sh->table->device);
-  const int one = 0;
-  return serve_zeros_impl(&sh, &one, 1, (hipStream_t)stream);
+  return serve_zeros_impl(&sh, &ONLY, 1, (hipStream_t)stream);
 }
 
 // out[i] = the row that came back for ids[i].  1 launch.
 int kv_shard_lookup_finish(kv_shard_t sh, float* out, kv_stream_t stream) {
-  if (!sh || (sh->n_last > 0 && !out)) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_finish: output pointer is null");
-  if (sh->n_last == 0) return KV_OK;
+  if (!sh || (sh->batch.n() > 0 && !out)) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_finish: output pointer is null");
+  if (sh->batch.n() == 0) return KV_OK;
   DeviceGuard dg(sh->table->device);
-  kv_table* rt = sh->route;
-  std::lock_guard<std::mutex> l(rt->mu);
-  if (!rt->batch.holds(sh->route_token, sh->n_last)) return fail(KV_FAILED_PRECONDITION, "kv_shard_lookup_finish without kv_shard_lookup_route");
-  { int rc; if ((rc = hand_over(rt, (hipStream_t)stream))) return rc; }
-  const FinishDesc d = finish_desc(sh, out);
-  const int grid = nblocks(d.n, TB, 8192);
-  hipStream_t st = (hipStream_t)stream;
-  with_lanes(row_lanes(d.dim), [&](auto vq) {
-    k_shard_finish<decltype(vq)::value><<<grid, TB, 0, st>>>(d.pos_ent, d.ent_u, d.slot_of, d.rows, d.out, d.n, d.dim, d.rows_self, d.self_lo, d.self_len);
-  });
-  HIP_TRY(hipGetLastError());
-  return KV_OK;
+  return finish_impl("kv_shard_lookup_finish", &sh, &ONLY, 1, &out, (hipStream_t)stream);
 }
 
 // out[s] = the combiner over segment s of w_j * (the row that came back for ids[j]), in position order.  1 launch; an empty
@@ -1325,37 +1296,23 @@ int kv_shard_lookup_finish_sparse(kv_shard_t sh, const void* segment_ids, int se
                                   int64_t num_segments, int combiner, float* out, kv_stream_t stream) {
   if (!sh) return fail(KV_INVALID_ARGUMENT, "kv_shard_lookup_finish_sparse: null shard");
   int rc;
-  if ((rc = sparse_finish_check("kv_shard_lookup_finish_sparse", segment_ids, segment_dtype, sh->n_last, num_segments, combiner, out)))
+  if ((rc = sparse_finish_check("kv_shard_lookup_finish_sparse", segment_ids, segment_dtype, sh->batch.n(), num_segments, combiner, out)))
     return rc;
   DeviceGuard dg(sh->table->device);
   const SparseArgs sp{&segment_ids, segment_dtype, &weights, &num_segments, combiner, true};
-  const int one = 0;
-  return finish_sparse_impl("kv_shard_lookup_finish_sparse", &sh, &one, 1, sp, &out, (hipStream_t)stream);
+  return finish_sparse_impl("kv_shard_lookup_finish_sparse", &sh, &ONLY, 1, sp, &out, (hipStream_t)stream);
 }
 
 // backward: the gradient rows of the batch just looked up are summed per distinct id straight into the records their
 // ids were sent in (the route index is still there: no ids, no sizes, no sync).  2 launches.
 int kv_shard_apply_route(kv_shard_t sh, const float* grad, kv_stream_t stream) {
   if (!sh) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_route: null shard");
-  // (the refusal first: n_last is the read-only batch's, and a rank whose voided training batch was empty has no gradient to name)
+  // (the refusal first: n is the read-only batch's, and a rank whose voided training batch was empty has no gradient to name)
   { int rc; if ((rc = shard_refuse_apply(sh, "kv_shard_apply_route"))) return rc; }
-  if (sh->n_last > 0 && !grad) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_route: grad pointer is null");
-  if (sh->n_last == 0) return KV_OK;
+  if (sh->batch.n() > 0 && !grad) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_route: grad pointer is null");
+  if (sh->batch.n() == 0) return KV_OK;
   DeviceGuard dg(sh->table->device);
-  kv_table* rt = sh->route;
-  std::lock_guard<std::mutex> l(rt->mu);
-  if (!rt->batch.holds(sh->route_token, sh->n_last))
-    return fail(KV_FAILED_PRECONDITION, "kv_shard_apply_route: the batch's lookup must come first (kv_shard_lookup_route)");
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if ((rc = hand_over(rt, s))) return rc;
-  if ((rc = ensure_workspace(rt, sh->n_last, true, s))) return rc;
-  MultiDesc d{};
-  presum_desc(sh, grad, d);
-  if ((rc = launch_tsum(d.a.tv, d.w, grad, s))) return fail(rc, "tile sums: no kernel for dim %d", rt->dim);
-  if ((rc = launch_papply_ud(d.w, d.a, PA_DEDUP, s))) return fail(rc, "gradient pre-sum: no kernel for dim %d", rt->dim);
-  HIP_TRY(hipGetLastError());
-  return KV_OK;
+  return presum_impl("kv_shard_apply_route", &sh, &ONLY, 1, &grad, (hipStream_t)stream);
 }
 
 // ... from the SEGMENT gradients of the batch's sparse lookup: the record of a distinct id receives the sum over its
@@ -1366,25 +1323,24 @@ int kv_shard_apply_route_sparse(kv_shard_t sh, const float* seg_grad, const void
                                 const float* weights, int64_t num_segments, int combiner, kv_stream_t stream) {
   if (!sh) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_route_sparse: null shard");
   { int rc; if ((rc = shard_refuse_apply(sh, "kv_shard_apply_route_sparse"))) return rc; }
-  if (sh->n_last == 0) return KV_OK;
+  if (sh->batch.n() == 0) return KV_OK;
   DeviceGuard dg(sh->table->device);
   const SparseArgs sp{&segment_ids, segment_dtype, &weights, &num_segments, combiner, true};
-  const int one = 0;
-  return presum_sparse_impl("kv_shard_apply_route_sparse", &sh, &one, 1, &seg_grad, sp, (hipStream_t)stream);
+  return presum_sparse_impl("kv_shard_apply_route_sparse", &sh, &ONLY, 1, &seg_grad, sp, (hipStream_t)stream);
 }
 
 // the owner's half: recv_rows holds the peers' summed gradients, record for record as the lookup served them; the
 // fused apply takes the index that lookup left in the table's workspace.  2 launches.  optimizer / hp: shard_opt_call
 int kv_shard_apply_serve(kv_shard_t sh, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp, kv_stream_t stream) {
   if (!sh || !hp) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_serve: bad arguments");
-  const int64_t nrec = (int64_t)sh->world * (sh->C + 1);
-  if (!sh->table->batch.holds(sh->serve_token, nrec))
+  const int64_t nrec = shard_nrec(sh);
+  if (!sh->table->batch.holds(sh->batch.serve_token(), nrec))
     return fail(KV_FAILED_PRECONDITION, "kv_shard_apply_serve: another op used the table since this batch's lookup "
                                         "(the sharded apply takes over the lookup's index)");
   const SelfSegment self = shard_self(sh, true);
   const OptCall c = shard_opt_call(optimizer, hp);
   if (c.opt < 0) return fail(KV_INVALID_ARGUMENT, "kv_shard_apply_serve: optimizer %d", optimizer);
-  return apply_one(c, sh->table, slot0, slot1, sh->recv_rows, sh->recv_pairs, nrec, sh->serve_token, stream, false, &self);
+  return apply_one(c, sh->table, slot0, slot1, sh->recv_rows, sh->recv_pairs, nrec, sh->batch.serve_token(), stream, false, &self);
 }
 
 // whole ops: forked from `stream` onto the shard's own stream (the caller's stream is free for the dense tower);
@@ -1437,13 +1393,8 @@ int kv_shard_agree_local(const kv_shard_t* shards, int world, int* rerouted, kv_
   HIP_TRY(hipStreamSynchronize(s));
   for (int p = 0; p < world; ++p) need = std::max(need, *shards[p]->need_host);
   if (need <= shards[0]->C) return KV_OK;
-  const long long newC = std::min<long long>(shards[0]->max_ids, (long long)need + need / 4 + 64);
-  for (int p = 0; p < world; ++p) {
-    int rc;
-    if ((rc = shard_alloc_buffers(shards[p], (unsigned)newC))) return rc;
-    *reinterpret_cast<volatile unsigned*>(shards[p]->overflow) = 0;
-    ++shards[p]->grows;
-  }
+  for (int p = 0; p < world; ++p)
+    if (int rc = shard_grow(shards[p], need, shards[0]->max_ids)) return rc;   // (one capacity for all of them)
   *rerouted = 1;
   return KV_OK;
 }
