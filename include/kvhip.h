@@ -757,6 +757,59 @@ int kv_batch_lookup_sparse_zeros(int num_tables, const kv_handle_t* tables, cons
                                  const int64_t* ns, const int64_t* num_segments, int combiner,
                                  float* const* outs, kv_stream_t stream);
 
+/* embedding_lookup_sparse(..., max_norm = c) on one KvVariable, fused: the clip of the reference's chain (tf
+ * embedding_ops._clip = clip_by_norm over the embedding axis, between the lookup and the weights) inside the kernels of
+ * kv_lookup_sparse, kv_lookup_sparse_grad and kv_lookup_sparse_zeros.  Arguments as their unclipped siblings, plus max_norm.
+ * The clip rule, for a row x of the table:
+ *   q = sum_e x_e^2 (float32),  norm = sqrtf(q),  s = norm > max_norm ? max_norm / norm : 1.0f
+ * with the IEEE square root and one IEEE division whatever kv_set_fast_math says; a zero row has s = 1 (there is no 0/0).
+ * Position j contributes x * (w_j * s_j): the factor is one multiply, then the multiply-add of the unclipped op.  The
+ * denominators stay the sums of w_j and w_j^2: the clip is on the embeddings, not on the weights.  q is summed inside the
+ * lane group that combines the segment — each lane its own elements in element order, then a butterfly over the group's
+ * lanes — so its rounding depends on the dim alone, never on the launch; a key that repeats has its norm recomputed per
+ * occurrence.  A row that is not clipped has w_j * 1.0f == w_j: a call in which no row exceeds max_norm (max_norm = +inf
+ * included) gives the bits, and in the training form the side effects, of the unclipped op.
+ * max_norm must be > 0 and not NaN (KV_INVALID_ARGUMENT).
+ *
+ * kv_lookup_sparse_clip: the training forward.  Pipeline, checks, limits on n, n == 0 / num_segments == 0 behaviour,
+ * count_occurrences, deferred errors and capture rules are kv_lookup_sparse's.  Served dims: the entry-list dims only —
+ * multiples of 4 up to 256, table not in occurrence-order mode; any other table is KV_UNIMPLEMENTED from the host-side
+ * checks, with nothing queued.  `saved`, when not NULL, receives n records of KV_SPARSE_CLIP_RECORD_BYTES (8) bytes, one
+ * per position, for the backward: their content is opaque (the row the combiner read and the factor it used).  They are
+ * valid until the next call that can insert into, delete from, import into or rebuild this table.  (That is the contract, and
+ * it is conservative: today rows stay where they are when keys are inserted or the index is rebuilt, so only a delete or an
+ * import can hand a saved row number to another key.)
+ *
+ * kv_lookup_sparse_clip_grad: the backward.  With g = seg_grad[segment of j], scale_j exactly kv_lookup_sparse_grad's
+ * (same offsets, same denominator pass, same roundings), x the row `saved[j]` names and s_j its saved factor:
+ *   s_j == 1:  values[j] = scale_j * g                                 (the bits of kv_lookup_sparse_grad)
+ *   s_j <  1:  values[j] = (scale_j * s_j) * (g - x * ((x . g) / q))   q = sum_e x_e^2 recomputed, x . g summed like q
+ * The branch is the saved factor's: the two directions cannot disagree about a row at the threshold.  The table is read,
+ * never written: no record, frequency word or slot mirror changes.  A row number from `saved` is clamped into the
+ * table's slab before use — memory safety only: a stale record gives unspecified values, never an access outside it.
+ * `saved` must not be NULL when there is work.  Dims, checks and limits as the forward; num_segments == 0 and n == 0 are
+ * no-ops; capture rules as kv_lookup_sparse_grad.
+ *
+ * kv_lookup_sparse_zeros_clip: the serving form, one launch, every dim kv_lookup_sparse_zeros serves (dims that are not
+ * 4, 8, 16, ..., 256 run the whole-wave form: lane v squares elements v, v + 64, ... and the butterfly spans the wave).
+ * row() stays the gather-or-zeros row: a missing, blacklisted or under-threshold key is a zero row with s = 1.  No side
+ * effects, no workspace; checks, ranges and capturability exactly as kv_lookup_sparse_zeros.
+ *
+ * Out of scope: there is no batched (kv_batch_... / kv_multi_...) and no sharded form of these three; a caller with many
+ * tables calls them table by table.  The dense embedding_lookup(max_norm =) is not covered either.
+ * Not reference ops: the Python mirror calls them (fused_max_norm = True); a TF graph needs the rewrite the unclipped
+ * sparse lookups need. */
+#define KV_SPARSE_CLIP_RECORD_BYTES 8
+int kv_lookup_sparse_clip(kv_handle_t h, const void* ids, const void* segment_ids, int segment_dtype,
+                          const float* weights, int64_t n, int64_t num_segments, int combiner,
+                          int count_occurrences, float max_norm, float* out, void* saved, kv_stream_t stream);
+int kv_lookup_sparse_clip_grad(kv_handle_t h, const float* seg_grad, const void* segment_ids, int segment_dtype,
+                               const float* weights, const void* saved, int64_t n, int64_t num_segments,
+                               int combiner, float max_norm, float* values, kv_stream_t stream);
+int kv_lookup_sparse_zeros_clip(kv_handle_t h, const void* ids, const void* segment_ids, int segment_dtype,
+                                const float* weights, int64_t n, int64_t num_segments, int combiner,
+                                float max_norm, float* out, kv_stream_t stream);
+
 /* tf.unsorted_segment_sum(data [n, dim], segment_ids [n] int32, num_segments) on the batch pipeline
  * (no float atomics: a segment named by 100 000 rows costs the same as 100 000 segments): out
  * [num_segments, dim]; segments nobody names are zero rows, ids outside [0, num_segments) are

@@ -1,6 +1,7 @@
 // kv_op_kernels.h — the small kernels only the table ops (kv_ops.hip) launch: point queries, delete, export / import /
 // delta, the inference gathers, unique / dedup helpers, the sparse lookup's combiners, its backward and their batched forms, the
-// serving-mode sparse lookup (kv_lookup_sparse_zeros),
+// serving-mode sparse lookup (kv_lookup_sparse_zeros), the max_norm variants of the three sparse-lookup kernels
+// (kv_lookup_sparse_clip, kv_lookup_sparse_clip_grad, kv_lookup_sparse_zeros_clip),
 // kv_take_rows.  Included by kv_ops.hip
 // alone, behind kv_device.h, inside its anonymous namespace.
 #pragma once
@@ -401,6 +402,59 @@ __global__ void __launch_bounds__(TB) k_seg_combine(TableDev t, WsDev w, const u
 }
 
 // ---------------------------------------------------------------------------------------------
+// The max_norm clip of embedding_lookup_sparse (tf embedding_ops._clip = clip_by_norm over the embedding axis) inside the
+// sparse lookups' own kernels: kv_lookup_sparse_clip, kv_lookup_sparse_clip_grad, kv_lookup_sparse_zeros_clip.
+//   q = sum_e x_e^2, norm = sqrtf(q), s = norm > max_norm ? max_norm / norm : 1.0f   (IEEE sqrt and division; a zero row: 1)
+//   position j contributes x * (w_j * s_j): one more multiply in front of the multiply-add of the unclipped kernels, so a
+//   row that is not clipped (w_j * 1.0f == w_j) contributes the unclipped bits.  The denominators stay the sums of w_j.
+// The norm is taken where the row already is — in the registers of the segment's lane group, right behind the load: each
+// lane squares and adds its own elements in element order, then an xor butterfly over the group's lanes (group_sum,
+// kv_device.h) leaves the same bits in every lane: at each distance the two partners add the same two numbers.  No LDS,
+// no atomics, no launch and no pass over the rows of its own; a repeated key's norm is recomputed per occurrence (the row
+// is an L2 hit).  A group's lanes walk the segment together, so all of them are in the butterfly whatever the other
+// groups of the wave do.
+// The bodies below take a clip policy as their last template argument: NoClip (the unclipped ops — nothing is computed,
+// passed or stored: their kernels are what they were) or one of the two records.
+struct NoClip {};
+struct ClipFwd {          // the two forwards
+  float max_norm;
+  uint2* saved;           // training form: [n] records {row read, bits of s_j}, or null; serving form: null
+};
+struct ClipBwd {          // the backward
+  TableDev t;
+  const uint2* saved;     // the forward's records
+  unsigned last_row;      // the slab's last row: a record's row number is clamped to it before use
+};
+template <class C> constexpr bool clips = !std::is_same<C, NoClip>::value;
+// "Nothing clips => the unclipped bits" holds across two compilations of the shared bodies because neither may fuse or
+// reassociate: the library is built with -ffp-contract=off, so every multiply and every add is its own IEEE operation in
+// both, and a packed v_pk_mul_f32 / v_pk_add_f32 rounds each half exactly as the scalar instruction does — which form the
+// compiler picks cannot change a bit.  tests/test_gpu_lookup_sparse_clip.py checks the equality per instantiation.
+// Apart from that, the clip kernels are compiled to the scalar forms only: a precaution for new code that costs nothing
+// here (they wait on dependent loads, not on the ALU) — the kernels were never run in the packed form, so nothing is
+// claimed about it.  (The attribute names a device feature: the host pass does not know it.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define KV_SCALAR_FP32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define KV_SCALAR_FP32
+#endif
+
+__device__ __forceinline__ float sq4(const float4& x) {
+  float p = x.x * x.x;
+  p += x.y * x.y; p += x.z * x.z; p += x.w * x.w;
+  return p;
+}
+__device__ __forceinline__ float dot4(const float4& x, const float4& g) {
+  float p = x.x * g.x;
+  p += x.y * g.y; p += x.z * g.z; p += x.w * g.w;
+  return p;
+}
+__device__ __forceinline__ float clip_factor(float q, float max_norm) {
+  const float norm = sqrtf(q);
+  return norm > max_norm ? max_norm / norm : 1.f;
+}
+
+// ---------------------------------------------------------------------------------------------
 // kv_lookup_sparse_zeros: embedding_lookup_sparse outside training (python/ops/kv_variable_ops.py:1072-1080, 1105-1113:
 // unique -> KvVariableGatherOrZerosV2; embedding_ops.py:359-441: gather(idx) -> (x weights) -> segment_sum /
 // sparse_segment_{sum,mean,sqrt_n}) in ONE launch, read-only: no dedup, no offsets pass, no workspace.
@@ -425,13 +479,18 @@ __global__ void __launch_bounds__(TB) k_seg_combine(TableDev t, WsDev w, const u
 //    there (profiles/serving_sparse.txt) the batched launch takes 2.3-3.3x the plain batched gather of the same ids: the
 //    bound search and the probe are one dependent chain per wave step.  Pipelining both across a wave's steps, as
 //    goz_wave does, is the next step for this kernel.
-// No LDS, no atomics, no float reduction across lanes.  (lsz_bound: kv_device.h — the sharded combining finish walks
-// its segments the same way.)
-template <int VQ>
+// No LDS, no atomics, and — but for the clip below — no float reduction across lanes.  (lsz_bound: kv_device.h — the
+// sharded combining finish walks its segments the same way.)
+// C = ClipFwd: kv_lookup_sparse_zeros_clip.  The chunk loops below are wave-uniform (__any), so every lane of a group is
+// in the row-norm butterfly.  VQ > 0: the group holds the SU rows in its float4s — SU independent butterflies over LPS
+// lanes.  VQ == 0: lane v squares its elements v, v + 64, ... in a loop of its own (the row is read again by the
+// multiply-adds behind it, from L1 / L2), and the butterfly spans the wave.  A key the index does not hold is row 0, the
+// zero row: s = 1.
+template <int VQ, class C = NoClip>
 __device__ __forceinline__ void lsz_body(const TableDev& t, const void* __restrict__ ids, int ids32,
                                          const void* __restrict__ seg, int seg32, const float* __restrict__ wts,
                                          int n, long long nseg, int combiner, float* __restrict__ out,
-                                         long long blk, long long nblk) {
+                                         long long blk, long long nblk, C clip = C{}) {
   constexpr int LPS = VQ > 0 ? VQ : 64;     // lanes per segment
   constexpr int G = 64 / LPS;               // segments per wave and step
   constexpr int SU = LPS < 4 ? LPS : 4;     // rows in flight per lane
@@ -482,16 +541,43 @@ __device__ __forceinline__ void lsz_body(const TableDev& t, const void* __restri
           float4 x[SU];
 #pragma unroll
           for (int u = 0; u < SU; ++u) x[u] = reinterpret_cast<const float4*>(row_ptr(t, ru[u]))[v];
+          float fu[SU];   // the rows' factors: w_j, clipped w_j * s_j
+#pragma unroll
+          for (int u = 0; u < SU; ++u) {
+            if constexpr (clips<C>) fu[u] = wu[u] * clip_factor(group_sum<LPS>(sq4(x[u])), clip.max_norm);
+            else fu[u] = wu[u];
+          }
 #pragma unroll
           for (int u = 0; u < SU; ++u) {
             if (u0 + u >= rem) continue;
-            acc.x += x[u].x * wu[u]; acc.y += x[u].y * wu[u]; acc.z += x[u].z * wu[u]; acc.w += x[u].w * wu[u];
+            acc.x += x[u].x * fu[u]; acc.y += x[u].y * fu[u]; acc.z += x[u].z * fu[u]; acc.w += x[u].w * fu[u];
             wsum += wu[u]; w2 += wu[u] * wu[u];
           }
         } else {
           const float* rowp[SU];
 #pragma unroll
           for (int u = 0; u < SU; ++u) rowp[u] = row_ptr(t, ru[u]);
+          float fu[SU];
+#pragma unroll
+          for (int u = 0; u < SU; ++u) fu[u] = wu[u];
+          if constexpr (clips<C>) {
+            float q[SU];
+#pragma unroll
+            for (int u = 0; u < SU; ++u) q[u] = 0.f;
+#pragma unroll
+            for (int k = 0; k < NE; ++k) {
+              if (k < kmax) {   // wave-uniform
+                const int e = v + (k << 6);
+#pragma unroll
+                for (int u = 0; u < SU; ++u) {
+                  const float xe = e < D ? rowp[u][e] : 0.f;
+                  q[u] += xe * xe;
+                }
+              }
+            }
+#pragma unroll
+            for (int u = 0; u < SU; ++u) fu[u] = wu[u] * clip_factor(group_sum<64>(q[u]), clip.max_norm);
+          }
 #pragma unroll
           for (int k = 0; k < NE; ++k) {
             if (k < kmax) {   // wave-uniform
@@ -501,7 +587,7 @@ __device__ __forceinline__ void lsz_body(const TableDev& t, const void* __restri
               for (int u = 0; u < SU; ++u) x[u] = e < D ? rowp[u][e] : 0.f;
 #pragma unroll
               for (int u = 0; u < SU; ++u)
-                if (u0 + u < rem) accs[k] += x[u] * wu[u];
+                if (u0 + u < rem) accs[k] += x[u] * fu[u];
             }
           }
 #pragma unroll
@@ -554,6 +640,13 @@ __global__ void __launch_bounds__(TB) k_lookup_sparse_zeros(TableDev t, const vo
                                                             int combiner, float* __restrict__ out) {
   lsz_body<VQ>(t, ids, ids32, seg, seg32, wts, n, nseg, combiner, out, blockIdx.x, gridDim.x);
 }
+template <int VQ>
+__global__ void KV_SCALAR_FP32 __launch_bounds__(TB) k_lookup_sparse_zeros_clip(TableDev t, const void* __restrict__ ids, int ids32,
+                                                                 const void* __restrict__ seg, int seg32,
+                                                                 const float* __restrict__ wts, int n, long long nseg,
+                                                                 int combiner, float* __restrict__ out, ClipFwd clip) {
+  lsz_body<VQ, ClipFwd>(t, ids, ids32, seg, seg32, wts, n, nseg, combiner, out, blockIdx.x, gridDim.x, clip);
+}
 // the batched form: blockIdx.y = table, tables free to differ in dim and key dtype; a table's blocks past its own
 // segments leave at once
 struct BatchSparseZerosDesc {
@@ -601,11 +694,14 @@ __global__ void __launch_bounds__(TB) k_take_rows(const U* __restrict__ src, con
 // key this batch inserted in ANOTHER tile may not know its row yet (NEW_BIT, row part 0): it is probed — the partition
 // pass in front of this kernel has published every new row.  VQ lanes (power of two >= dim / 4) per segment, SU
 // positions of a segment in flight; the sums are taken in position order whatever SU is.
-template <int VQ>
+// C = ClipFwd: kv_lookup_sparse_clip.  The SU rows in flight get SU independent butterflies over the group's VQ lanes (a
+// lane past the row's end — dim 12: VQ 4, three float4s — adds +0); the segment loop is the group's own, so its lanes are
+// all there.  Lane 0 files the position's record {row read, bits of s_j} for the backward.
+template <int VQ, class C = NoClip>
 __device__ __forceinline__ void seg_combine_e_body(const TableDev& t, const unsigned short* __restrict__ pos_ent,
                                                    const unsigned* __restrict__ ent_b, const long long* __restrict__ ent_key,
                                                    const unsigned* __restrict__ off, const float* __restrict__ wts,
-                                                   long long nseg, int combiner, float* __restrict__ out) {
+                                                   long long nseg, int combiner, float* __restrict__ out, C clip = C{}) {
   const int D4 = t.dim >> 2;
   const int v = threadIdx.x % VQ;
   const bool vlive = v < D4;
@@ -637,10 +733,21 @@ __device__ __forceinline__ void seg_combine_e_body(const TableDev& t, const unsi
       }
 #pragma unroll
       for (int u = 0; u < SU; ++u) x[u] = reinterpret_cast<const float4*>(row_ptr(t, r[u]))[vv];
+      float fj[SU];   // the rows' factors: w_j, clipped w_j * s_j
+#pragma unroll
+      for (int u = 0; u < SU; ++u) {
+        if constexpr (clips<C>) {
+          const float sj = clip_factor(group_sum<VQ>(vlive ? sq4(x[u]) : 0.f), clip.max_norm);
+          fj[u] = wj[u] * sj;
+          if (clip.saved && v == 0 && j + u < hi) clip.saved[j + u] = make_uint2(r[u], __float_as_uint(sj));
+        } else {
+          fj[u] = wj[u];
+        }
+      }
 #pragma unroll
       for (int u = 0; u < SU; ++u) {
         if (!(j + u < hi)) continue;
-        acc.x += x[u].x * wj[u]; acc.y += x[u].y * wj[u]; acc.z += x[u].z * wj[u]; acc.w += x[u].w * wj[u];
+        acc.x += x[u].x * fj[u]; acc.y += x[u].y * fj[u]; acc.z += x[u].z * fj[u]; acc.w += x[u].w * fj[u];
         wsum += wj[u]; w2 += wj[u] * wj[u];
       }
     }
@@ -656,6 +763,13 @@ __global__ void __launch_bounds__(TB) k_seg_combine_e(TableDev t, const unsigned
                                                       const unsigned* __restrict__ off, const float* __restrict__ wts,
                                                       long long nseg, int combiner, float* __restrict__ out) {
   seg_combine_e_body<VQ>(t, pos_ent, ent_b, ent_key, off, wts, nseg, combiner, out);
+}
+template <int VQ>
+__global__ void KV_SCALAR_FP32 __launch_bounds__(TB) k_seg_combine_e_clip(TableDev t, const unsigned short* __restrict__ pos_ent,
+                                                           const unsigned* __restrict__ ent_b, const long long* __restrict__ ent_key,
+                                                           const unsigned* __restrict__ off, const float* __restrict__ wts,
+                                                           long long nseg, int combiner, float* __restrict__ out, ClipFwd clip) {
+  seg_combine_e_body<VQ, ClipFwd>(t, pos_ent, ent_b, ent_key, off, wts, nseg, combiner, out, clip);
 }
 
 // inverse[i] = the dense number of position i's id: position -> its entry in its tile -> the number k_papply PA_UNIQUE gave it
@@ -706,11 +820,19 @@ __device__ __forceinline__ long long seg_of(const SegT* __restrict__ seg, long l
   const long long sg = (long long)seg[j];
   return sg < 0 ? 0 : (sg >= nseg ? nseg - 1 : sg);
 }
-template <typename SegT, int VQ>
+// C = ClipBwd: kv_lookup_sparse_clip_grad (rows of at most VQ float4s).  With g = seg_grad[segment of j], x = the row the
+// forward read for position j and s_j its saved factor:
+//   s_j == 1:  values[j] = scale_j * g                                    — the unclipped lines below, the same bits
+//   s_j <  1:  values[j] = (scale_j * s_j) * (g - x * ((x . g) / q))      q = sum_e x_e^2, recomputed
+// the Jacobian of x * max_norm / |x| applied to g.  x . g and q are lane partials in element order and the forward's
+// butterfly; the branch is the saved factor's, so the two directions cannot disagree about which rows were clipped.  The
+// group's lanes read the same record: the branch is the group's, and its lanes are all in the butterflies.
+template <typename SegT, int VQ, class C = NoClip>
 __device__ __forceinline__ void seg_expand_body(const float* __restrict__ seg_grad, const SegT* __restrict__ seg,
                                                 const unsigned* __restrict__ off, const float* __restrict__ den,
                                                 const float* __restrict__ wts, long long n, long long nseg, int D, int combiner,
-                                                float* __restrict__ values) {
+                                                float* __restrict__ values, C clip = C{}) {
+  static_assert(VQ > 0 || !clips<C>, "the clipped backward runs on a lane group per position");
   if constexpr (VQ > 0) {
     const int D4 = D >> 2;
     const int v = threadIdx.x % VQ;
@@ -721,6 +843,23 @@ __device__ __forceinline__ void seg_expand_body(const float* __restrict__ seg_gr
       const float sc = seg_scale(off, den, wts, j, sg, combiner);
       const float4* src = reinterpret_cast<const float4*>(seg_grad + (size_t)sg * D);
       float4* dst = reinterpret_cast<float4*>(values + (size_t)j * D);
+      if constexpr (clips<C>) {
+        const uint2 rec = clip.saved[j];
+        const float sj = __uint_as_float(rec.y);
+        if (sj < 1.f) {
+          const unsigned r = rec.x < clip.last_row ? rec.x : clip.last_row;   // a stale record stays inside the slab
+          const bool vlive = v < D4;
+          const int vv = vlive ? v : 0;
+          const float4 x = reinterpret_cast<const float4*>(row_ptr(clip.t, r))[vv];
+          const float4 g = src[vv];
+          const float q = group_sum<VQ>(vlive ? sq4(x) : 0.f);
+          const float xg = group_sum<VQ>(vlive ? dot4(x, g) : 0.f);
+          const float c = xg / q;
+          const float f = sc * sj;
+          if (vlive) dst[v] = make_float4((g.x - x.x * c) * f, (g.y - x.y * c) * f, (g.z - x.z * c) * f, (g.w - x.w * c) * f);
+          continue;
+        }
+      }
       for (int q = v; q < D4; q += VQ) {   // (one round for dims up to 256; the lanes past the row's end take none)
         const float4 g = src[q];
         dst[q] = make_float4(g.x * sc, g.y * sc, g.z * sc, g.w * sc);
@@ -742,6 +881,13 @@ __global__ void __launch_bounds__(TB) k_seg_expand(const float* __restrict__ seg
                                                    const float* __restrict__ wts, long long n, long long nseg, int D, int combiner,
                                                    float* __restrict__ values) {
   seg_expand_body<SegT, VQ>(seg_grad, seg, off, den, wts, n, nseg, D, combiner, values);
+}
+template <typename SegT, int VQ>
+__global__ void KV_SCALAR_FP32 __launch_bounds__(TB) k_seg_expand_clip(const float* __restrict__ seg_grad, const SegT* __restrict__ seg,
+                                                        const unsigned* __restrict__ off, const float* __restrict__ den,
+                                                        const float* __restrict__ wts, long long n, long long nseg, int D,
+                                                        int combiner, float* __restrict__ values, ClipBwd clip) {
+  seg_expand_body<SegT, VQ, ClipBwd>(seg_grad, seg, off, den, wts, n, nseg, D, combiner, values, clip);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -318,11 +318,24 @@ static int sparse_size_checks(const kv_table* t, int64_t n, int64_t num_segments
   return KV_OK;
 }
 
+// what the three max_norm ops check beyond their unclipped siblings; the training pair serves the entry-list dims only
+static int clip_checks(const kv_table* t, float max_norm, bool training) {
+  if (!(max_norm > 0.f)) return fail(KV_INVALID_ARGUMENT, "max_norm must be > 0 (and not NaN)");
+  if (training && !fused_tab(t))
+    return fail(KV_UNIMPLEMENTED, "the max_norm sparse lookup and its backward serve dims that are multiples of 4 up to 256, "
+                                  "outside occurrence-order mode (dim %d)", t->dim);
+  return KV_OK;
+}
+
 // kv_lookup_sparse behind its checks; the table's mutex is held by the caller, its device is current
+// clip: kv_lookup_sparse_clip (an entry-list table: clip_checks) — the same pipeline, the combiner's clip variant
 static int lookup_sparse_locked(kv_table* t, const void* ids, const void* segment_ids, int segment_dtype, const float* weights,
-                                int64_t n, int64_t num_segments, int combiner, int count_occurrences, float* out, hipStream_t s) {
+                                int64_t n, int64_t num_segments, int combiner, int count_occurrences, float* out, hipStream_t s,
+                                const ClipFwd* clip = nullptr) {
   int rc;
   const bool fused = fused_tab(t);
+  // (clip_checks ran before the lock was taken; kv_set_deterministic may have moved the table off the entry-list kernels since)
+  if (clip && (rc = clip_checks(t, clip->max_norm, true))) return rc;
   if ((rc = enter_op(t, s, KEEP_VAR))) return rc;   // the table's own rows and records only
   const int D = t->dim;
   if (n == 0) {  // every segment is empty
@@ -363,7 +376,11 @@ static int lookup_sparse_locked(kv_table* t, const void* ids, const void* segmen
   const int grid = nblocks(num_segments * (fused ? row_lanes(D) : q ? q : 1), TB, 8192);
   if (fused)
     with_lanes(row_lanes(D), [&](auto vq) {
-      k_seg_combine_e<decltype(vq)::value><<<grid, TB, 0, s>>>(td, ws.pos_ent, wd.ent_b, wd.ent_key, ws.seg_off, weights, num_segments, combiner, out);
+      if (clip)
+        k_seg_combine_e_clip<decltype(vq)::value><<<grid, TB, 0, s>>>(td, ws.pos_ent, wd.ent_b, wd.ent_key, ws.seg_off, weights, num_segments,
+                                                                     combiner, out, *clip);
+      else
+        k_seg_combine_e<decltype(vq)::value><<<grid, TB, 0, s>>>(td, ws.pos_ent, wd.ent_b, wd.ent_key, ws.seg_off, weights, num_segments, combiner, out);
     });
   else if (q)
     with_lanes(q, [&](auto vq) {
@@ -390,9 +407,16 @@ static void with_expand_types(bool int32_seg, int lanes, F&& f) {
 // kv_lookup_sparse_grad behind its checks (n > 0, num_segments > 0); the table's mutex is held by the caller
 static int lookup_sparse_grad_locked(kv_table* t, const float* seg_grad, const void* segment_ids, int segment_dtype,
                                      const float* weights, int64_t n, int64_t num_segments, int combiner, float* values,
-                                     hipStream_t s) {
+                                     hipStream_t s, const uint2* saved = nullptr) {
   int rc;
-  // `t` lends its workspace: neither its rows nor any record is touched
+  // `t` lends its workspace: neither its rows nor any record is touched.  saved (kv_lookup_sparse_clip_grad, an
+  // entry-list table: clip_checks): the clipped positions' rows are READ as well, by the row numbers the forward saved —
+  // the rows' floats only, no index entry, frequency word or flag.  A slot mirror is a copy of a slot record's frequency
+  // word and flags kept beside a var row's record: nothing this op reads or writes, so both roles keep their epoch.  The
+  // hand-over settles a pending partition pass first, as for every op: the rows it initialises are final before they are read.
+  if (saved && !fused_tab(t))   // (the mode may have changed between the entry's checks and the lock)
+    return fail(KV_UNIMPLEMENTED, "the max_norm sparse lookup's backward: the table left the entry-list kernels (occurrence-order mode)");
+  if (saved && t->rows_cap == 0) return fail(KV_FAILED_PRECONDITION, "the table has no rows: the saved records are not this table's");
   if ((rc = enter_op(t, s, KEEP_VAR | KEEP_SLOT))) return rc;
   const bool need_den = weights != nullptr && combiner != KV_COMBINER_SUM;
   if ((rc = ensure_seg(t, num_segments, need_den, s))) return rc;
@@ -408,8 +432,17 @@ static int lookup_sparse_grad_locked(kv_table* t, const float* seg_grad, const v
   const int grid = nblocks(n * (lanes ? lanes : D), TB, 16384);
   with_expand_types(seg32, lanes, [&](auto id, auto vq) {
     using IDT = decltype(id);
-    k_seg_expand<IDT, decltype(vq)::value><<<grid, TB, 0, s>>>(seg_grad, (const IDT*)segment_ids, ws.seg_off, ws.seg_den, weights, n,
-                                                               num_segments, D, combiner, values);
+    constexpr int VQ = decltype(vq)::value;
+    if constexpr (VQ > 0) {
+      if (saved) {
+        const TableDev td = dev_view(t);
+        k_seg_expand_clip<IDT, VQ><<<grid, TB, 0, s>>>(seg_grad, (const IDT*)segment_ids, ws.seg_off, ws.seg_den, weights, n, num_segments,
+                                                       D, combiner, values, ClipBwd{td, saved, td.max_rows - 1u});
+        return;
+      }
+    }
+    k_seg_expand<IDT, VQ><<<grid, TB, 0, s>>>(seg_grad, (const IDT*)segment_ids, ws.seg_off, ws.seg_den, weights, n,
+                                              num_segments, D, combiner, values);
   });
   HIP_TRY(hipGetLastError());
   return KV_OK;
@@ -708,6 +741,39 @@ int kv_lookup_sparse_grad(kv_handle_t t, const float* seg_grad, const void* segm
   return lookup_sparse_grad_locked(t, seg_grad, segment_ids, segment_dtype, weights, n, num_segments, combiner, values, op.s);
 }
 
+int kv_lookup_sparse_clip(kv_handle_t t, const void* ids, const void* segment_ids, int segment_dtype,
+                          const float* weights, int64_t n, int64_t num_segments, int combiner, int count_occurrences,
+                          float max_norm, float* out, void* saved, kv_stream_t stream) {
+  int rc;
+  if ((rc = check_table(t))) return rc;
+  if ((rc = sparse_call_checks(combiner, segment_dtype))) return rc;
+  if ((rc = sparse_size_checks(t, n, num_segments))) return rc;
+  if ((rc = clip_checks(t, max_norm, true))) return rc;
+  if (num_segments == 0) return KV_OK;
+  if (!out || (n > 0 && (!ids || !segment_ids))) return fail(KV_INVALID_ARGUMENT, "ids / segment ids / output pointer is null");
+  if ((rc = require_initialized(t))) return rc;
+  TableOp op(t, stream);
+  const ClipFwd clip{max_norm, static_cast<uint2*>(saved)};
+  return lookup_sparse_locked(t, ids, segment_ids, segment_dtype, weights, n, num_segments, combiner, count_occurrences, out, op.s, &clip);
+}
+
+int kv_lookup_sparse_clip_grad(kv_handle_t t, const float* seg_grad, const void* segment_ids, int segment_dtype,
+                               const float* weights, const void* saved, int64_t n, int64_t num_segments, int combiner,
+                               float max_norm, float* values, kv_stream_t stream) {
+  int rc;
+  if ((rc = check_table(t))) return rc;
+  if ((rc = sparse_call_checks(combiner, segment_dtype))) return rc;
+  if ((rc = sparse_size_checks(t, n, num_segments))) return rc;
+  if ((rc = clip_checks(t, max_norm, true))) return rc;
+  if (num_segments == 0 || n == 0) return KV_OK;
+  if (!seg_grad || !segment_ids || !values || !saved)
+    return fail(KV_INVALID_ARGUMENT, "gradient / segment ids / saved records / output pointer is null");
+  if ((rc = require_initialized(t))) return rc;
+  TableOp op(t, stream);
+  return lookup_sparse_grad_locked(t, seg_grad, segment_ids, segment_dtype, weights, n, num_segments, combiner, values, op.s,
+                                   static_cast<const uint2*>(saved));
+}
+
 int kv_multi_lookup_sparse(int num_tables, const kv_handle_t* tables, const void* const* ids,
                            const void* const* segment_ids, int segment_dtype, const float* const* weights,
                            const int64_t* ns, const int64_t* num_segments, int combiner,
@@ -924,12 +990,14 @@ int kv_batch_gather_or_zeros(int num_tables, const kv_handle_t* tables, const vo
   return KV_OK;
 }
 
-int kv_lookup_sparse_zeros(kv_handle_t t, const void* ids, const void* segment_ids, int segment_dtype,
-                           const float* weights, int64_t n, int64_t num_segments, int combiner, float* out,
-                           kv_stream_t stream) {
+// kv_lookup_sparse_zeros and (clip) kv_lookup_sparse_zeros_clip: the same entry, the same launch, the body's clip variant
+static int lookup_sparse_zeros_impl(kv_handle_t t, const void* ids, const void* segment_ids, int segment_dtype,
+                                    const float* weights, int64_t n, int64_t num_segments, int combiner, float* out,
+                                    kv_stream_t stream, const ClipFwd* clip) {
   int rc;
   if ((rc = check_table(t))) return rc;
   if ((rc = sparse_zeros_checks(t, ids, segment_ids, segment_dtype, n, num_segments, combiner, out))) return rc;
+  if (clip && (rc = clip_checks(t, clip->max_norm, false))) return rc;
   if (num_segments == 0) return KV_OK;
   TableOp op(t, stream);
   const hipStream_t s = op.s;
@@ -940,15 +1008,30 @@ int kv_lookup_sparse_zeros(kv_handle_t t, const void* ids, const void* segment_i
   const int q = sparse_zeros_lanes(t->dim);
   const int grid = nblocks(num_segments * (q ? q : 64), TB, 8192);
   const int ids32 = t->key_dtype == KV_DT_INT32, seg32 = segment_dtype == KV_DT_INT32;
-  if (q)
-    with_lanes(q, [&](auto vq) {
-      k_lookup_sparse_zeros<decltype(vq)::value><<<grid, TB, 0, s>>>(td, ids, ids32, segment_ids, seg32, weights, (int)n,
-                                                                    num_segments, combiner, out);
-    });
-  else
-    k_lookup_sparse_zeros<0><<<grid, TB, 0, s>>>(td, ids, ids32, segment_ids, seg32, weights, (int)n, num_segments, combiner, out);
+  auto launch = [&](auto vq) {
+    constexpr int VQ = decltype(vq)::value;
+    if (clip)
+      k_lookup_sparse_zeros_clip<VQ><<<grid, TB, 0, s>>>(td, ids, ids32, segment_ids, seg32, weights, (int)n, num_segments, combiner, out, *clip);
+    else
+      k_lookup_sparse_zeros<VQ><<<grid, TB, 0, s>>>(td, ids, ids32, segment_ids, seg32, weights, (int)n, num_segments, combiner, out);
+  };
+  if (q) with_lanes(q, launch);
+  else launch(std::integral_constant<int, 0>{});
   HIP_TRY(hipGetLastError());
   return KV_OK;
+}
+
+int kv_lookup_sparse_zeros(kv_handle_t t, const void* ids, const void* segment_ids, int segment_dtype,
+                           const float* weights, int64_t n, int64_t num_segments, int combiner, float* out,
+                           kv_stream_t stream) {
+  return lookup_sparse_zeros_impl(t, ids, segment_ids, segment_dtype, weights, n, num_segments, combiner, out, stream, nullptr);
+}
+
+int kv_lookup_sparse_zeros_clip(kv_handle_t t, const void* ids, const void* segment_ids, int segment_dtype,
+                                const float* weights, int64_t n, int64_t num_segments, int combiner, float max_norm,
+                                float* out, kv_stream_t stream) {
+  const ClipFwd clip{max_norm, nullptr};
+  return lookup_sparse_zeros_impl(t, ids, segment_ids, segment_dtype, weights, n, num_segments, combiner, out, stream, &clip);
 }
 
 int kv_batch_lookup_sparse_zeros(int num_tables, const kv_handle_t* tables, const void* const* ids,

@@ -11,6 +11,7 @@ import re
 
 import torch
 
+from tfplus_amd import _lib
 from tfplus_amd.kv_variable.python.ops import kv_variable_ops
 from tfplus_amd.kv_variable.python.ops.variable_scope import PartitionedKvVariable
 
@@ -102,11 +103,21 @@ def _num_segments(indices_list):
   return out
 
 
+def _fused_norm_ok(var, max_norm, fused_max_norm):
+  """May the fused sparse lookup serve this call's max_norm?  None always; a value only on request and where the native
+  clip serves the table (KvVariable.serves_max_norm)."""
+  return max_norm is None or (bool(fused_max_norm) and hasattr(var, "serves_max_norm") and var.serves_max_norm())
+
+
 def embedding_lookup_sparse(params, sp_ids, sp_weights, partition_strategy="mod", name=None,
-                            combiner=None, max_norm=None):
+                            combiner=None, max_norm=None, fused_max_norm=False):
   """embedding_ops.py:279-441: unique ids -> lookup -> (weighted) segment sum / mean / sqrtn.  One KvVariable without
   max_norm takes one fused native call: kv_lookup_sparse when training (up to 2^21 ids), kv_lookup_sparse_zeros in
   inference mode (read-only, one launch, any number of ids).  Partitioned variables and max_norm take the op chain.
+  fused_max_norm=True: one KvVariable with a max_norm takes the fused call too, the clip inside the same kernels
+  (kv_lookup_sparse_clip and its backward when training, for dims that are multiples of 4 up to 256;
+  kv_lookup_sparse_zeros_clip in inference mode, any dim); other dims and partitioned variables keep the chain.  Opt-in,
+  like AdamOptimizer(fused=True): the fused result differs from the chain's in rounding.
   The segment count is the last segment id + 1, as in the reference: sp_ids.indices on the host cost nothing, indices on
   a device cost one device-to-host copy in front of the call (embedding_lookup_sparse_multi pays it once for all features)."""
   if combiner is None:
@@ -123,12 +134,18 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, partition_strategy="mod"
   ids = torch.as_tensor(sp_ids.values).to(dev)
   need_counts = plist[0].enter_threshold > 0
   nseg = _num_segments([sp_ids.indices])[0]
-  if (len(plist) == 1 and max_norm is None and hasattr(plist[0], "lookup_sparse")
+  if (len(plist) == 1 and _fused_norm_ok(plist[0], max_norm, fused_max_norm) and hasattr(plist[0], "lookup_sparse")
       and 0 < ids.numel() and (not kv_variable_ops.IS_TRAINING or ids.numel() <= (1 << 21))):
     # one table: the whole chain is one fused call (training: dedup + lookup + combine; inference: probe + combine, and
     # the training pipeline's bound on the ids does not apply)
-    return plist[0].lookup_sparse(ids, seg, None if sp_weights is None else sp_weights.values, nseg, combiner,
-                                  need_counts)
+    try:
+      return plist[0].lookup_sparse(ids, seg, None if sp_weights is None else sp_weights.values, nseg, combiner,
+                                    need_counts, max_norm)
+    except _lib.UnimplementedError:
+      # a table the native clip does not serve although its dim would do (occurrence-order mode, set on the handle): the
+      # refusal comes from the host-side checks with nothing queued, and the call keeps the chain like any other such table
+      if max_norm is None:
+        raise
   uniq, idx, cnt = torch.unique(ids, return_inverse=True, return_counts=True)
   emb = _embedding_lookup_and_transform(plist, uniq, partition_strategy, max_norm=max_norm,
                                         counts=cnt.to(torch.int32) if need_counts else None)
@@ -145,7 +162,8 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, partition_strategy="mod"
   return summed / torch.sqrt(_segment_sum(wts * wts, seg, nseg))
 
 
-def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None, combiner=None, max_norm=None):
+def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None, combiner=None, max_norm=None,
+                                  fused_max_norm=False):
   """[embedding_lookup_sparse(p, i, w, combiner=combiner) for p, i, w in zip(...)] — one KvVariable per feature — with
   the features that take the fused path grouped by (device, dim, key dtype): one batched forward per group
   (kv_multi_lookup_sparse: four launches whatever the group's size) under one autograd function, whose backward is one
@@ -154,7 +172,8 @@ def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None
   launch (kv_batch_lookup_sparse_zeros).  The segment counts of all fused features are read in one go (_num_segments: at
   most one device-to-host copy per call, none for indices on the host).  A feature the fused path does not take — a
   partitioned variable, max_norm, in training mode more ids than one call takes or a variable some earlier feature of its
-  group already uses — goes through embedding_lookup_sparse as it is."""
+  group already uses — goes through embedding_lookup_sparse as it is.  So does every feature of a call with max_norm:
+  with fused_max_norm=True through the single-table fused clip ops (there is no batched form of them), else the chain."""
   if combiner is None:
     combiner = "mean"
   if combiner not in ("mean", "sqrtn", "sum"):
@@ -179,7 +198,8 @@ def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None
              and 0 < n and (not training or n <= (1 << 21)))
     key = None if not fused else (var.device, var.embedding_dim, var.key_dtype, var.trainable) if training else (var.device,)
     if not fused or (training and any(e[1] is var for e in groups.get(key, ()))):
-      out[f] = embedding_lookup_sparse(plist, sp_ids, sp_w, combiner=combiner, max_norm=max_norm)
+      out[f] = embedding_lookup_sparse(plist, sp_ids, sp_w, combiner=combiner, max_norm=max_norm,
+                                       fused_max_norm=fused_max_norm)
       continue
     seg = torch.as_tensor(sp_ids.indices).to(var.device)[:, 0].to(torch.int64)
     groups.setdefault(key, []).append([f, var, torch.as_tensor(sp_ids.values).to(var.device), seg,
@@ -197,7 +217,8 @@ def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None
 
 
 def safe_embedding_lookup_sparse(embedding_weights, sparse_ids, sparse_weights=None, combiner=None,
-                                 default_id=None, name=None, partition_strategy="mod", max_norm=None):
+                                 default_id=None, name=None, partition_strategy="mod", max_norm=None,
+                                 fused_max_norm=False):
   """embedding_ops.py:444-628.  For KvVariables ids < 0 are ordinary keys and are NOT pruned
   (:552-556); non-positive weights are pruned unless combiner == "sum" (:557-560); empty rows are
   filled with default_id (or read as zeros); the leading shape is restored."""
@@ -234,7 +255,7 @@ def safe_embedding_lookup_sparse(embedding_weights, sparse_ids, sparse_weights=N
   ind2 = torch.stack([row, torch.zeros_like(row)], 1)
   res = embedding_lookup_sparse(plist, SparseTensor(ind2, vals, [rows, shape[-1]]),
                                 None if w is None else SparseTensor(ind2, w, [rows, shape[-1]]),
-                                partition_strategy, name, combiner, max_norm)
+                                partition_strategy, name, combiner, max_norm, fused_max_norm)
   if res.shape[0] < rows:
     res = torch.cat([res, torch.zeros((rows - res.shape[0],) + tuple(res.shape[1:]), device=dev)])
   if default_id is None and empty.numel():

@@ -908,6 +908,61 @@ def kv_variable_lookup_sparse_zeros(table_handle, ids, segment_ids, weights, num
   return out
 
 
+def kv_variable_lookup_sparse_clip(table_handle, ids, segment_ids, weights, num_segments, combiner="mean",
+                                   count_occurrences=False, max_norm=None, save=True):
+  """kv_variable_lookup_sparse with the reference's max_norm clip (clip_by_norm of every looked-up row, before the
+  weights) inside the combiner: one call, dims that are multiples of 4 up to 256 (kvhip.h kv_lookup_sparse_clip).  Returns
+  (out [num_segments, dim], saved): saved is the opaque per-position record kv_variable_lookup_sparse_clip_grad reads
+  ([n, 2] int32; None with save=False), valid until the table's next insert, delete, import or rebuild."""
+  if combiner not in _COMBINERS:
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  ids = _ids(table_handle, ids).reshape(-1)
+  seg, w = _sparse_args(table_handle, ids.numel(), segment_ids, weights)
+  dev = _dev(table_handle)
+  out = torch.empty((int(num_segments), table_handle.dim), dtype=torch.float32, device=dev)
+  saved = torch.empty((ids.numel(), 2), dtype=torch.int32, device=dev) if save else None
+  _lib.check(_lib.lib().kv_lookup_sparse_clip(table_handle.ptr, _p(ids), _p(seg), _TORCH_KEY[seg.dtype], _p(w), ids.numel(),
+                                              int(num_segments), _COMBINERS[combiner], int(bool(count_occurrences)),
+                                              float(max_norm), _p(out), _p(saved), _stream(table_handle)))
+  return out, saved
+
+
+def kv_variable_lookup_sparse_clip_grad(table_handle, seg_grad, segment_ids, weights, saved, num_segments, combiner="mean",
+                                        max_norm=None):
+  """The backward of kv_variable_lookup_sparse_clip: values [n, dim]; a position whose row was not clipped gets
+  kv_variable_lookup_sparse_grad's row, a clipped one (scale_j * s_j) * (g - x * (x . g) / |x|^2) with x read from the
+  table through `saved` (kvhip.h kv_lookup_sparse_clip_grad).  The table is only read."""
+  if combiner not in _COMBINERS:
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  n = torch.as_tensor(segment_ids).numel()
+  seg, w = _sparse_args(table_handle, n, segment_ids, weights)
+  g = _f32(table_handle, seg_grad).reshape(-1, table_handle.dim)
+  if g.shape[0] != int(num_segments):
+    raise _lib.InvalidArgumentError("seg_grad must have num_segments rows")
+  if saved is None or saved.dtype != torch.int32 or saved.numel() != 2 * n or saved.device != g.device:
+    raise _lib.InvalidArgumentError("saved must be the record kv_variable_lookup_sparse_clip returned for these positions")
+  saved = saved.contiguous()
+  out = torch.empty((n, table_handle.dim), dtype=torch.float32, device=g.device)
+  _lib.check(_lib.lib().kv_lookup_sparse_clip_grad(table_handle.ptr, _p(g), _p(seg), _TORCH_KEY[seg.dtype], _p(w), _p(saved), n,
+                                                   int(num_segments), _COMBINERS[combiner], float(max_norm), _p(out),
+                                                   _stream(table_handle)))
+  return out
+
+
+def kv_variable_lookup_sparse_zeros_clip(table_handle, ids, segment_ids, weights, num_segments, combiner="mean", max_norm=None):
+  """kv_variable_lookup_sparse_zeros with the max_norm clip inside its one launch; every dim that op serves.  Read-only:
+  a key that reads zeros stays zeros (kvhip.h kv_lookup_sparse_zeros_clip)."""
+  if combiner not in _COMBINERS:
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  ids = _ids(table_handle, ids).reshape(-1)
+  seg, w = _sparse_args(table_handle, ids.numel(), segment_ids, weights)
+  out = torch.empty((int(num_segments), table_handle.dim), dtype=torch.float32, device=_dev(table_handle))
+  _lib.check(_lib.lib().kv_lookup_sparse_zeros_clip(table_handle.ptr, _p(ids), _p(seg), _TORCH_KEY[seg.dtype], _p(w),
+                                                    ids.numel(), int(num_segments), _COMBINERS[combiner], float(max_norm),
+                                                    _p(out), _stream(table_handle)))
+  return out
+
+
 def batch_kv_variable_lookup_sparse_zeros(table_handles, ids, segment_ids, weights, num_segments, combiner="mean"):
   """[kv_variable_lookup_sparse_zeros(t, i, s, w, n, combiner) for ...] with one kernel launch for all tables (one device;
   dims and key dtypes free to differ; a table may be listed more than once).  weights: None, or a list whose entries may

@@ -66,6 +66,30 @@ class _SparseLookupGrad(torch.autograd.Function):
     return None, None, None, None, None, None, None, None
 
 
+class _SparseLookupClipGrad(torch.autograd.Function):
+  """_SparseLookupGrad with the max_norm clip fused into both directions (kv_lookup_sparse_clip and its _grad).  The
+  forward keeps the op's per-position record; the backward reads the clipped rows through it, so by the op's contract it
+  has to run before the table's next insert, delete, import or rebuild — the order of a training step (lookup, backward,
+  apply).  Nothing here enforces that.  What can actually re-assign a saved row is a delete or an import in between (rows stay
+  in place under inserts — a second feature's lookup on the same variable included — and index rebuilds): the gradient of the
+  clipped positions is then unspecified, never an access outside the table."""
+
+  @staticmethod
+  def forward(ctx, anchor, var, ids, seg, weights, nseg, combiner, count_occurrences, max_norm):
+    ctx.var, ctx.ids, ctx.seg, ctx.weights, ctx.nseg, ctx.combiner, ctx.max_norm = var, ids, seg, weights, nseg, combiner, max_norm
+    out, ctx.saved = gen_kv_variable_ops.kv_variable_lookup_sparse_clip(var.handle, ids, seg, weights, nseg, combiner,
+                                                                        count_occurrences, max_norm)
+    return out
+
+  @staticmethod
+  def backward(ctx, grad):
+    var, ids = ctx.var, ctx.ids
+    vals = gen_kv_variable_ops.kv_variable_lookup_sparse_clip_grad(var.handle, grad.reshape(ctx.nseg, -1), ctx.seg, ctx.weights,
+                                                                   ctx.saved, ctx.nseg, ctx.combiner, ctx.max_norm)
+    var._pending_grads.append(IndexedSlices(vals, ids.reshape(-1), None))
+    return None, None, None, None, None, None, None, None, None
+
+
 class _MultiSparseLookupGrad(torch.autograd.Function):
   """_SparseLookupGrad over the KvVariables of one (device, dim, key dtype) group: the batched forward
   (kv_multi_lookup_sparse), and ONE kv_multi_lookup_sparse_grad in the backward, which files one IndexedSlices on each
@@ -216,13 +240,28 @@ class KvVariable(object):
     for a key the table does not hold.  The owner's read of sharded.ShardedKvVariable.lookup_zeros."""
     return gen_kv_variable_ops.kv_variable_gather_or_zeros_v2(self._handle, torch.as_tensor(indices).to(self._device))
 
-  def lookup_sparse(self, ids, segment_ids, weights, num_segments, combiner, count_occurrences):
+  def serves_max_norm(self):
+    """Does lookup_sparse(max_norm=) serve this table in the current mode?  Inference: every dim; training: the
+    multiples of 4 up to 256 (kvhip.h kv_lookup_sparse_clip).  By dim only: a table in occurrence-order mode is refused by the
+    op itself, and embedding_lookup_sparse then keeps the chain."""
+    return not IS_TRAINING or (self._embedding_dim % 4 == 0 and self._embedding_dim <= 256)
+
+  def lookup_sparse(self, ids, segment_ids, weights, num_segments, combiner, count_occurrences, max_norm=None):
     """embedding_lookup_sparse on this table in one fused call: kv_lookup_sparse when training (missing keys are
     inserted, the gradient is filed on the variable), kv_lookup_sparse_zeros else (GatherOrZeros rows, read-only, no
-    autograd node and no pending gradient; count_occurrences has no meaning there)."""
+    autograd node and no pending gradient; count_occurrences has no meaning there).  max_norm: every looked-up row is
+    clipped to that norm inside the same kernels (kv_lookup_sparse_clip, its _grad, kv_lookup_sparse_zeros_clip)."""
     ids = torch.as_tensor(ids).to(self._device).reshape(-1)
     seg = torch.as_tensor(segment_ids).to(self._device).reshape(-1)
     w = None if weights is None else torch.as_tensor(weights, dtype=torch.float32).to(self._device).reshape(-1)
+    if max_norm is not None:
+      if not IS_TRAINING:
+        return gen_kv_variable_ops.kv_variable_lookup_sparse_zeros_clip(self._handle, ids, seg, w, num_segments, combiner, max_norm)
+      if self._trainable and torch.is_grad_enabled():
+        return _SparseLookupClipGrad.apply(self._anchor, self, ids, seg, w, int(num_segments), combiner,
+                                           bool(count_occurrences), float(max_norm))
+      return gen_kv_variable_ops.kv_variable_lookup_sparse_clip(self._handle, ids, seg, w, num_segments, combiner,
+                                                                count_occurrences, max_norm, save=False)[0]
     if not IS_TRAINING:
       return gen_kv_variable_ops.kv_variable_lookup_sparse_zeros(self._handle, ids, seg, w, num_segments, combiner)
     if self._trainable and torch.is_grad_enabled():
