@@ -373,6 +373,51 @@ int kv_apply_unique_counted(kv_handle_t var, int optimizer, kv_handle_t slot0, k
                             const float* grad, const void* ids, int ids_dtype, int64_t n_max, const int64_t* n_dev,
                             kv_stream_t stream);
 
+/* The backward of kv_lookup_sparse on a plain table, fused: the optimizer apply takes the SEGMENT gradients
+ * [num_segments, dim].  The composition — kv_lookup_sparse_grad expands them into [n, dim] values, kv_apply_<optimizer> reads
+ * those back to sum them per distinct id — writes and reads n * dim * 4 bytes that carry no information; here the tile sums and
+ * the partition pass + update fetch a position's row from the segment gradients themselves, through per-position records
+ * (segment, scale: 8 bytes a position) that a small pre-pass leaves in the var table's workspace.  The values buffer is never
+ * allocated.  `optimizer`, `slot0`, `slot1` and `hp` are kv_shard_apply_serve's codes and layouts (0 .. 7, below), validated as
+ * kv_apply_unique_counted validates them: the hyperparameter checks, their order and their wording are the named ops'.
+ *   kv_apply_sparse        seg_grad [num_segments, dim], ids [n] of the table's key dtype, segment_ids [n] int32 or int64,
+ *                          weights [n] or NULL: kv_lookup_sparse's arguments of the batch.  n == 0: a no-op, KV_OK.
+ *   kv_multi_apply_sparse  the batched form, by multi_apply's rules (one device, one dim, one key dtype, each table listed
+ *                          once; one launch per stage whatever num_tables is; the 256-thread blocks): for a table k with
+ *                          segment_ids[k] != NULL, grads[k] holds that table's segment gradients [num_segments[k], dim]; a
+ *                          table with segment_ids[k] == NULL passes plain [ns[k], dim] values — the mixed form of
+ *                          kv_multi_shard_apply_sparse, for a model that mixes dense and sparse lookups of same-shaped
+ *                          tables.  One segment dtype and one combiner per call; weights may be NULL, and so may weights[k].
+ *                          Table k ends bit for bit as its single-table call would leave it, for the same block shape.
+ * Result: what kv_lookup_sparse_grad followed by the plain kv_apply_<optimizer> (no token) on (ids, values) leaves in the var
+ * and slot tables — rows, frequency words, day stamps, flags, blacklist transitions, delta lists, slot-mirror handling.  A
+ * distinct id receives the sum, over its positions j, of term_j = fl(scale_j * seg_grad[s_j, :]), with s_j and scale_j exactly
+ * kv_lookup_sparse_grad's — the segment id clamped into [0, num_segments), the denominator summed in float32 from +0 in
+ * position order, the scale one IEEE division, each element one multiply (rounded before any add: no contraction) — so each
+ * term is bit for bit the row the expansion would have written.  The terms are added in the order the plain apply adds rows:
+ * the same row lists, entries, partitions and source lists drive it.  In deterministic mode (kv_set_deterministic(h, 1)) the
+ * tables are therefore bit for bit the composition's; in the default mode each id receives the same multiset of terms, in
+ * whatever order the source filing gives.  Rows of seg_grad that belong to empty segments are never read.
+ * The table side is the plain apply's: the per-call limit of n (2^23), capacity growth, a pending partition pass of another
+ * batch settled first, and the batch index the call builds and publishes.  There is no _tok form — the training sparse lookup
+ * leaves no token (kv_lookup_sparse drops the batch record) — and no _unique form: sparse ids repeat.
+ * Checks, in this order, all before anything is queued: the handles; uninitialised tables (KV_FAILED_PRECONDITION);
+ * KV_INVALID_ARGUMENT for a null seg_grad / ids / segment_ids (n > 0), a segment dtype other than int32 / int64, a combiner
+ * outside 0 .. 2, num_segments outside [1, 2^31 - 2] (n > 0) and the optimizer's own argument errors; KV_UNIMPLEMENTED for a
+ * table off the entry-list kernels — an embedding dim that is not a multiple of 4 up to 256, or occurrence-order mode
+ * (kv_set_deterministic(h, 2)): expand and apply the values there.  The mode is checked again under the table's lock.
+ * Stream capture: the position records, segment offsets and denominators live in the var table's workspace; a call that would
+ * have to grow one of them is refused (KV_FAILED_PRECONDITION) before anything is queued — run the shapes once outside the
+ * capture. */
+int kv_apply_sparse(kv_handle_t var, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp,
+                    const float* seg_grad, const void* ids, const void* segment_ids, int segment_dtype,
+                    const float* weights, int64_t n, int64_t num_segments, int combiner, kv_stream_t stream);
+int kv_multi_apply_sparse(int num_tables, const kv_handle_t* vars, int optimizer, const kv_handle_t* slot0,
+                          const kv_handle_t* slot1, const float* hp, const float* const* grads,
+                          const void* const* ids, const void* const* segment_ids, int segment_dtype,
+                          const float* const* weights, const int64_t* ns, const int64_t* num_segments,
+                          int combiner, kv_stream_t stream);
+
 /* ---- export / import ("next" rows) -------------------------------------------
  * Replaces ReadKvVariableOp / KvVariableExport (kernels/kv_variable_ops.cc:325-346, 779-860) ->
  * ExportValues (kernels/dynamic_save.hpp:47-195).  Two-phase: kv_export_count fills

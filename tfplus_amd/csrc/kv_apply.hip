@@ -1,6 +1,7 @@
 // kv_apply.hip — the optimizer layer of the C ABI on the table core (kv_host.h): one parser per optimizer family, the two
 // bodies (apply_one: one table; multi_apply: many tables, one launch per stage; the PartArgs of all their launches start
-// from opt_part_args), the 42 kv_apply_* / kv_multi_apply_* entry points and kv_attach_slot.  It compiles no kernel: the
+// from opt_part_args), the 42 kv_apply_* / kv_multi_apply_* entry points, kv_[multi_]apply_sparse (the same bodies fed from
+// segment gradients) and kv_attach_slot.  It compiles no kernel: the
 // optimizers' kernels are reached through the typed launchers of kv_launch.h, the pipelines' through the core's.
 #include <hip/hip_runtime.h>
 
@@ -67,6 +68,68 @@ int fused_apply(kv_table* v, WsDev& wd, PartArgs& pa, long long n, hipStream_t s
   return KV_OK;
 }
 
+// ---- the sparse apply (kv_apply_sparse / kv_multi_apply_sparse; kv_host.h SparseGrads) -----------------------------------
+// the tables it serves: the entry-list kernels' (checked before the lock and again under it: kv_set_deterministic(h, 2) may
+// have moved the table off them in between)
+static int sparse_apply_serves(const kv_table* v) {
+  if (fused_tab(v)) return KV_OK;
+  return fail(KV_UNIMPLEMENTED, "the sparse apply serves dims that are multiples of 4 up to 256, outside occurrence-order mode "
+                                "(dim %d): expand with kv_lookup_sparse_grad and apply the values", v->dim);
+}
+// table k's sparse arguments (n ids): KV_INVALID_ARGUMENT, the wording of the sparse lookups' checks
+static int sparse_apply_args(const float* grad, const void* ids, const SparseGrads& sp, int k, int64_t n, bool plain_ok) {
+  if (sp.combiner < KV_COMBINER_SUM || sp.combiner > KV_COMBINER_SQRTN)
+    return fail(KV_INVALID_ARGUMENT, "combiner must be one of 'mean', 'sqrtn' or 'sum'");
+  if (sp.seg_dtype != KV_DT_INT32 && sp.seg_dtype != KV_DT_INT64) return fail(KV_INVALID_ARGUMENT, "segment ids must be int32 or int64");
+  if (n <= 0 || (plain_ok && !sp.seg[k])) return KV_OK;   // (a plain table of the batched form: multi_apply_common checks its pointers)
+  if (!grad || !ids || !sp.seg[k]) return fail(KV_INVALID_ARGUMENT, "seg_grad / ids / segment ids pointer is null");
+  if (sp.nseg[k] < 1 || sp.nseg[k] > (1ll << 31) - 2)
+    return fail(KV_INVALID_ARGUMENT, "bad num_segments %lld (1 .. 2^31 - 2: there is no gradient to expand)", (long long)sp.nseg[k]);
+  return KV_OK;
+}
+// the position records, segment offsets and denominators of table k live in the var's workspace; a call under stream capture
+// that would have to grow one of them is refused before the tables are entered, with nothing queued
+static int sparse_apply_capture_check(const kv_table* v, const SparseGrads& sp, int k, long long n, hipStream_t s) {
+  const Workspace& w = v->ws;
+  const long long nseg = sp.seg[k] ? sp.nseg[k] : 0;
+  if (n == 0 || (w.prec_cap >= n && w.seg_cap >= nseg && (!sp.need_den(k) || w.den_cap >= nseg)) || !stream_is_capturing(s)) return KV_OK;
+  return fail(KV_FAILED_PRECONDITION, "the sparse apply's position records or segment buffers have to grow for this call, which needs "
+                                      "a stream synchronisation: run the op once with these lengths outside the stream capture first");
+}
+// ... grown, and described: what the pre-pass (launch_pos_records) reads and writes, what the sum kernels read
+static int sparse_apply_desc(kv_table* v, const SparseGrads& sp, int k, const float* grad, long long n, hipStream_t s, SegDesc& q) {
+  int rc;
+  const long long nseg = sp.seg[k] ? sp.nseg[k] : 0;
+  if ((rc = ensure_seg(v, nseg, sp.need_den(k), s)) || (rc = ensure_pos_records(v, n, s))) return rc;
+  Workspace& w = v->ws;
+  q.seg = sp.seg[k]; q.wts = sp.w(k); q.off = w.seg_off; q.den = sp.need_den(k) ? w.seg_den : nullptr;
+  q.pseg = w.pseg; q.pscale = w.pscale; q.n = n; q.nseg = nseg;
+  q.src = SegSrc{grad, w.pseg, w.pscale};
+  return KV_OK;
+}
+// fused_apply of a batch the optimizer meets first (PA_APPLYIDX) with the gradient per segment: the position records, the
+// rows-free tile pass, then k_tsum_seg and k_papply_seg.  The tile pass and the tile sums are two launches here where
+// fused_apply has one (k_ltsum): both run tsum_body over the same mrow image, so the sums' term order is the same, and no
+// kernel is added for it.
+template <int OPT>
+static int fused_apply_sparse(kv_table* v, WsDev& wd, PartArgs& pa, long long n, hipStream_t s, const void* ids, const SegDesc& sd,
+                              const SparseGrads& sp) {
+  int rc;
+  pa.epart = wd.epart;
+  if ((rc = launch_pos_records(1, &sd, nullptr, sp.seg_dtype == KV_DT_INT32, sp.combiner, s))) return rc;
+  {
+    ProfScope ps(v, KV_PROF_APPLY_TILE, s);
+    launch_ltile(v, pa.tv, wd, ids, nullptr, n, nullptr, s);
+  }
+  {
+    ProfScope ps(v, KV_PROF_APPLY_TSUM, s);
+    if ((rc = launch_tsum_seg(pa.tv, wd, sd.src, s))) return fail(rc, "tile sums: no kernel for dim %d", pa.tv.dim);
+  }
+  ProfScope ps(v, KV_PROF_APPLY_SORTED, s);
+  if ((rc = launch_papply_seg<OPT>(wd, pa, PA_APPLYIDX, s, sd.src))) return fail(rc, "partition + apply pass: no kernel for dim %d", pa.tv.dim);
+  return KV_OK;
+}
+
 // What the wide-slot ops call their slot table and say about its shape (the reference's wording where it has an op), one
 // row per optimizer, for apply_one and the batched body alike: a new wide-slot OPT_* gets the neutral row until it has its
 // own.  same_first: the same-table test comes in front of the shape test.  (Behind it the test is never reached — a table
@@ -90,8 +153,10 @@ template <int OPT>
 static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_handle_t* slots0,
                               const kv_handle_t* slots1, int slot_mult, const float* const* grads,
                               const void* const* ids, const int64_t* ns, const OptArgs& hp, kv_stream_t stream,
-                              const kv_batch_token_t* tokens, bool unique, bool require_reuse, const SelfSegment* selfs) {
+                              const kv_batch_token_t* tokens, bool unique, bool require_reuse, const SelfSegment* selfs,
+                              const SparseGrads* sp) {
   int rc;
+  if (sp && (tokens || unique || require_reuse || selfs)) return fail(KV_INTERNAL, "sparse apply off the plain path");
   if ((rc = multi_common(num_tables, vars, ids, ns))) return rc;
   if ((rc = check_same_shape(num_tables, slots0, "slot tables"))) return rc;
   if (slots1 && (rc = check_same_shape(num_tables, slots1, "slot tables"))) return rc;
@@ -120,10 +185,18 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
     if (std::adjacent_find(u.begin(), u.end()) != u.end())
       return fail(KV_INVALID_ARGUMENT, "batched op: a table is listed twice (var or slot)");
   }
+  if (sp) {
+    for (int i = 0; i < num_tables; ++i)
+      if ((rc = sparse_apply_args(grads[i], ids[i], *sp, i, ns[i], true))) return rc;
+    if ((rc = sparse_apply_serves(vars[0]))) return rc;   // (one dim; multi_common has refused occurrence-order tables)
+  }
   const int device = vars[0]->device;
   DeviceGuard dg(device);
   hipStream_t s = (hipStream_t)stream;
   MultiLock lock(all);
+  if (sp)   // (the tables' mode again, under the locks: kv_set_deterministic(h, 2) may have moved one off the entry-list kernels)
+    for (int i = 0; i < num_tables; ++i)
+      if ((rc = sparse_apply_serves(vars[i])) || (rc = sparse_apply_capture_check(vars[i], *sp, i, ns[i], s))) return rc;
   // GroupAdam / Adagrad over pairs (var_i, slot_i): the lean update works on the var rows' slot mirrors (mirror_decide per
   // table below); FTRL reads and writes the slot tables' own records: its entry ends the tables' epochs
   auto keep = [&](const kv_table* tb) -> unsigned {
@@ -189,12 +262,14 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   long long nmax = 0;
   if (require_reuse && !reuse)
     return fail(KV_FAILED_PRECONDITION, "batched sharded apply: another op used a table since this batch's lookup");
+  std::vector<SegDesc> sd(sp ? (size_t)num_tables : 0);
   for (int i = 0; i < num_tables; ++i) {
     if (!reuse) vars[i]->batch.drop();
     if (!reuse && (rc = ensure_capacity(vars[i], ns[i], s))) return rc;
     if ((rc = ensure_capacity(slots0[i], ns[i], s))) return rc;
     if (slots1 && (rc = ensure_capacity(slots1[i], ns[i], s))) return rc;
     if ((rc = ensure_workspace(vars[i], std::max<long long>(ns[i], 1), true, s))) return rc;
+    if (sp && (rc = sparse_apply_desc(vars[i], *sp, i, grads[i], ns[i], s, sd[(size_t)i]))) return rc;
     nmax = std::max<long long>(nmax, ns[i]);
   }
   if (nmax == 0) return KV_OK;
@@ -205,7 +280,7 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
     MultiDesc& d = hd[i];
     d.w = ws_view(vars[i], std::max<long long>(ns[i], 1), selfs ? &selfs[i] : nullptr);
     if (fz) { d.a.epart = d.w.epart; use_partitions(d.w, fused_default_P(std::max<long long>(ns[i], 1))); }
-    opt_part_args(d.a, vars[i], slots0[i], slots1 ? slots1[i] : nullptr, a, grads[i], ns[i], s);
+    opt_part_args(d.a, vars[i], slots0[i], slots1 ? slots1[i] : nullptr, a, sp ? nullptr : grads[i], ns[i], s);
     d.a.det = vars[i]->deterministic ? 1 : 0;
     if ((rc = mirror_decide(vars[i], slots0[i], d.a, fz && !two_slots(OPT), s))) return rc;   // (fz: k_papply_multi; else the sorted-position kernels, no mirrors)
     d.ids = ids[i];
@@ -222,6 +297,25 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
   }
   const MultiDesc* md;
   if ((rc = hd.upload(s, &md))) return rc;
+  if (sp) {
+    // the sparse apply (fz, no token): the position records of all tables — a plain table's name its own values rows — the
+    // tile pass, then the tile sums and the partition pass + update in their per-segment forms: one launch per stage
+    Staged<SegDesc> hs(device, 2, num_tables);
+    if (hs.rc) return hs.rc;
+    for (int i = 0; i < num_tables; ++i) hs[i] = sd[(size_t)i];
+    const SegDesc* sdev;
+    if ((rc = hs.upload(s, &sdev))) return rc;
+    if (num_tables == 1 && !sd[0].seg) return fail(KV_INTERNAL, "sparse apply of one plain table");   // (multi_apply hands those to the plain op)
+    if ((rc = launch_pos_records(num_tables, sd.data(), sdev, sp->seg_dtype == KV_DT_INT32, sp->combiner, s))) return rc;
+    launch_ltile(vars[0], hd[0].a.tv, wmax, nullptr, nullptr, nmax, nullptr, s, -1, md, num_tables, false);
+    for (int i = 0; i < num_tables; ++i)
+      if (ns[i] > 0) vars[i]->batch.publish(++g_serial, ns[i], BatchIndex::ENTRIES, hd[i].w.P);
+    if ((rc = launch_tsum_seg(hd[0].a.tv, wmax, SegSrc{}, s, md, sdev, num_tables))) return fail(rc, "tile sums: no kernel for dim %d", D);
+    if ((rc = launch_papply_seg<OPT>(wmax, hd[0].a, PA_APPLYIDX, s, SegSrc{}, md, sdev, num_tables)))
+      return fail(rc, "partition + apply pass: no kernel for dim %d", D);
+    HIP_TRY(hipGetLastError());
+    return KV_OK;
+  }
   if (fz) {
     // partition pass + update in one launch (k_papply_multi) behind the tile sums; an optimizer that meets the ids first
     // runs the tile pass of all tables in front (PA_APPLYIDX)
@@ -258,7 +352,8 @@ static int multi_apply_common(int num_tables, const kv_handle_t* vars, const kv_
 template <int OPT>
 static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* grad, const void* ids, int64_t n,
                         const OptArgs& a, kv_batch_token_t token, hipStream_t s, bool unique, const SelfSegment* self,
-                        const DevCount* counted) {
+                        const DevCount* counted, const SparseGrads* sp) {
+  if (sp && (token != 0 || unique || self)) return fail(KV_INTERNAL, "sparse apply off the plain path");
   const long long nmax = fused_tab(v) ? FUSED_MAX_N : (1ll << 21);
   if (n < 0 || n > nmax)
     return fail(n < 0 ? KV_INVALID_ARGUMENT : KV_UNIMPLEMENTED,
@@ -304,9 +399,11 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
   if ((rc = ensure_capacity(s0, n, s))) return rc;
   if (s1 && (rc = ensure_capacity(s1, n, s))) return rc;
   if ((rc = ensure_workspace(v, n, true, s))) return rc;
+  SegDesc sd{};   // sp: the segments' gradients are fetched through position records; no [n, dim] values exist (pa.grad stays null)
+  if (sp && (rc = sparse_apply_desc(v, *sp, 0, grad, n, s, sd))) return rc;
   WsDev wd = ws_view(v, n, self);
   PartArgs pa{};
-  opt_part_args(pa, v, s0, s1, a, grad, n, s);
+  opt_part_args(pa, v, s0, s1, a, sp ? nullptr : grad, n, s);
   pa.det = det_mode(v);
   pa.day_lk = pa.day;
   if (pa_mode == PA_LOOKUP) { pa.day_lk = pend.day; pa.count_once = pend.count_once; }
@@ -323,7 +420,8 @@ static int apply_common(kv_table* v, kv_table* s0, kv_table* s1, const float* gr
     use_partitions(wd, v->batch.P());   // the lookup's partitioning
   }
   if ((rc = mirror_decide(v, s0, pa, entries && !two_slots(OPT), s))) return rc;
-  if (entries) rc = fused_apply<OPT>(v, wd, pa, n, s, pa_mode, tile_ids);
+  if (sp) rc = fused_apply_sparse<OPT>(v, wd, pa, n, s, ids, sd, *sp);   // (REBUILD on an entry-list table: PA_APPLYIDX)
+  else if (entries) rc = fused_apply<OPT>(v, wd, pa, n, s, pa_mode, tile_ids);
   else rc = launch_apply<MODE_APPLY, OPT>(v, wd, pa, n, s);
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
@@ -472,7 +570,8 @@ OptCall shard_opt_call(int optimizer, const float* hp) {
 // the optimizer itself (GroupAdam version), the tables' initialisation, the hyperparameters, the shapes.  So c.status is
 // reported at its place in that order (nothing calls fail() before it unless it returns).  The batched ops report it first.
 int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const float* grad, const void* ids, int64_t n,
-              kv_batch_token_t token, kv_stream_t stream, bool unique, const SelfSegment* self, const DevCount* counted) {
+              kv_batch_token_t token, kv_stream_t stream, bool unique, const SelfSegment* self, const DevCount* counted,
+              const SparseGrads* sp) {
   int rc;
   const bool two = two_slots(c.opt);
   if ((rc = check_table(v)) || (rc = check_table(s0)) || (two && (rc = check_table(s1)))) return rc;
@@ -486,6 +585,7 @@ int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const f
   } else if ((rc = require_initialized(v, nullptr)) || (rc = require_initialized(s0, nullptr)) || (rc = require_initialized(s1, nullptr))) {
     return rc;
   }
+  if (sp && (rc = sparse_apply_args(grad, ids, *sp, 0, n, false))) return rc;
   if (c.status) return c.status;
   if (wide_slot(c.opt)) {
     // (group RectifiedAdam: the reference's shape check (:6790-6805) also lets an opt dim EQUAL to the var's through and
@@ -513,16 +613,19 @@ int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const f
                                     "the host (kv_apply_*_unique takes the batch pipeline there)");
   }
   if (n == 0) return KV_OK;
+  if (sp && (rc = sparse_apply_serves(v))) return rc;
   DeviceGuard dg(v->device);
   MultiLock lk({v, s0, two ? s1 : s0});
   // GroupAdam / Adagrad: apply_common decides whether this apply works on the mirrors (mirror_decide); the FTRL family reads
   // and writes the slot tables' own records: its entry ends the tables' epochs
   auto keep = [&](const kv_table* t) -> unsigned { return two ? KEEP_NONE : (t == v ? KEEP_VAR : KEEP_NONE) | (t == s0 ? KEEP_SLOT : KEEP_NONE); };
   hipStream_t s = (hipStream_t)stream;
+  // (the table's mode again, under the lock: kv_set_deterministic(h, 2) may have moved it off the entry-list kernels)
+  if (sp && ((rc = sparse_apply_serves(v)) || (rc = sparse_apply_capture_check(v, *sp, 0, n, s)))) return rc;
   if ((rc = lk.enter(s, keep, v->batch.holds(token, n) ? v : nullptr))) return rc;
   OptArgs a = c.a;
   a.l21_norm = a.l21 * std::sqrt((float)v->dim);   // training_ops.cc:728
-  return with_opt(c.opt, [&](auto o) { return apply_common<decltype(o)::value>(v, s0, two ? s1 : nullptr, grad, ids, n, a, token, s, unique, self, counted); });
+  return with_opt(c.opt, [&](auto o) { return apply_common<decltype(o)::value>(v, s0, two ? s1 : nullptr, grad, ids, n, a, token, s, unique, self, counted, sp); });
 }
 
 // Many tables.  After the parser's verdict the ops refuse a missing first table (and linears) — all but Adagrad, whose op
@@ -530,14 +633,14 @@ int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const f
 int multi_apply(const OptCall& c, int num_tables, const kv_handle_t* vars, const kv_handle_t* slots0,
                 const kv_handle_t* slots1, const float* const* grads, const void* const* ids, const int64_t* ns,
                 const kv_batch_token_t* tokens, kv_stream_t stream, bool unique, bool require_reuse,
-                const SelfSegment* selfs) {
+                const SelfSegment* selfs, const SparseGrads* sp) {
   if (c.status) return c.status;
   const bool two = two_slots(c.opt);
   if (c.opt != OPT_ADAGRAD && (num_tables < 1 || !vars || !vars[0] || (two && !slots1)))
     return fail(KV_INVALID_ARGUMENT, "N must be >= 1");
   return with_opt(c.opt, [&](auto o) {
     return multi_apply_common<decltype(o)::value>(num_tables, vars, slots0, two ? slots1 : nullptr, c.slot_mult, grads, ids, ns,
-                                                  c.a, stream, tokens, unique, require_reuse, selfs);
+                                                  c.a, stream, tokens, unique, require_reuse, selfs, sp);
   });
 }
 }  // namespace kvhip_internal
@@ -796,6 +899,38 @@ int kv_apply_unique_counted(kv_handle_t v, int optimizer, kv_handle_t slot0, kv_
   dc.n_dev = reinterpret_cast<const long long*>(n_dev);
   dc.ids32 = ids_dtype == KV_DT_INT32 ? 1 : 0;
   return apply_one(c, v, slot0, slot1, grad, ids, n_max, 0, stream, true, nullptr, &dc);
+}
+
+// the plain op of optimizer code `optimizer` with the gradient per segment (kv_host.h SparseGrads): the fused backward of
+// kv_lookup_sparse / kv_multi_lookup_sparse on plain tables
+int kv_apply_sparse(kv_handle_t v, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp, const float* seg_grad,
+                    const void* ids, const void* segment_ids, int segment_dtype, const float* weights, int64_t n,
+                    int64_t num_segments, int combiner, kv_stream_t stream) {
+  int rc;
+  if ((rc = check_table(v)) || (rc = check_table(slot0))) return rc;   // the handles first (slot1: apply_one, where the family needs it)
+  if (!hp) return fail(KV_INVALID_ARGUMENT, "kv_apply_sparse: hp is null");
+  const OptCall c = shard_opt_call(optimizer, hp);
+  if (c.opt < 0) return fail(KV_INVALID_ARGUMENT, "kv_apply_sparse: optimizer %d", optimizer);
+  const SparseGrads sp{&segment_ids, &weights, &num_segments, segment_dtype, combiner};
+  return apply_one(c, v, slot0, slot1, seg_grad, ids, n, 0, stream, false, nullptr, nullptr, &sp);
+}
+int kv_multi_apply_sparse(int num_tables, const kv_handle_t* vars, int optimizer, const kv_handle_t* slot0,
+                          const kv_handle_t* slot1, const float* hp, const float* const* grads, const void* const* ids,
+                          const void* const* segment_ids, int segment_dtype, const float* const* weights, const int64_t* ns,
+                          const int64_t* num_segments, int combiner, kv_stream_t stream) {
+  int rc;
+  if (num_tables < 1 || !vars || !slot0) return fail(KV_INVALID_ARGUMENT, "kv_multi_apply_sparse: N must be >= 1, null argument array");
+  for (int k = 0; k < num_tables; ++k)
+    if ((rc = check_table(vars[k])) || (rc = check_table(slot0[k]))) return rc;   // the handles first
+  if (!hp) return fail(KV_INVALID_ARGUMENT, "kv_multi_apply_sparse: hp is null");
+  const OptCall c = shard_opt_call(optimizer, hp);
+  if (c.opt < 0) return fail(KV_INVALID_ARGUMENT, "kv_multi_apply_sparse: optimizer %d", optimizer);
+  if (num_tables < 1 || !segment_ids || !num_segments) return fail(KV_INVALID_ARGUMENT, "kv_multi_apply_sparse: N must be >= 1, null argument array");
+  bool any = false;
+  for (int k = 0; k < num_tables; ++k) any = any || segment_ids[k] != nullptr;
+  const SparseGrads sp{segment_ids, weights, num_segments, segment_dtype, combiner};
+  // (no table passes segments: the plain batched op, which serves every dim it serves)
+  return multi_apply(c, num_tables, vars, slot0, slot1, grads, ids, ns, nullptr, stream, false, false, nullptr, any ? &sp : nullptr);
 }
 
 int kv_attach_slot(kv_handle_t v, kv_handle_t sl, kv_stream_t stream) {

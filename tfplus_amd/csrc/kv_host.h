@@ -546,12 +546,23 @@ OptCall shard_opt_call(int optimizer, const float* hp);
 // kv_apply_unique_counted: the unique apply whose id count is a device word (n of apply_one is then the most ids the call
 // may hold) and whose ids have a dtype of their own
 struct DevCount { const long long* n_dev = nullptr; int ids32 = 0; };
+// kv_apply_sparse / kv_multi_apply_sparse: the gradient arrives per SEGMENT — grad / grads[k] is [nseg[k], dim] and the row of
+// position j is kv_lookup_sparse_grad's scale_j * grad[s_j, :], fetched through position records in the var's workspace
+// (kv_types.h SegSrc).  One entry per table; seg[k] == nullptr (batched form only): table k passes plain [n, dim] values.
+struct SparseGrads {
+  const void* const* seg;      // [n_k] segment ids, one dtype for the call
+  const float* const* wts;     // may be null, and so may wts[k]
+  const int64_t* nseg;
+  int seg_dtype, combiner;
+  const float* w(int k) const { return wts ? wts[k] : nullptr; }
+  bool need_den(int k) const { return seg[k] && w(k) && combiner != KV_COMBINER_SUM; }
+};
 int apply_one(const OptCall& c, kv_table* v, kv_table* s0, kv_table* s1, const float* grad, const void* ids, int64_t n,
               kv_batch_token_t token, kv_stream_t stream, bool unique, const SelfSegment* self = nullptr,
-              const DevCount* counted = nullptr);
+              const DevCount* counted = nullptr, const SparseGrads* sp = nullptr);
 int multi_apply(const OptCall& c, int num_tables, const kv_handle_t* vars, const kv_handle_t* slots0,
                 const kv_handle_t* slots1, const float* const* grads, const void* const* ids, const int64_t* ns,
                 const kv_batch_token_t* tokens, kv_stream_t stream, bool unique, bool require_reuse = false,
-                const SelfSegment* selfs = nullptr);
+                const SelfSegment* selfs = nullptr, const SparseGrads* sp = nullptr);
 
 }  // namespace kvhip_internal

@@ -20,6 +20,11 @@ int launch_sorted_apply(const WsDev& wd, const PartArgs& pa, hipStream_t s, cons
 // k_papply (kv_papply.h): partition pass + update in one launch; mode = PA_LOOKUP / PA_APPLYIDX / PA_NONE
 template <int OPT>
 int launch_papply(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t s, const MultiDesc* md = nullptr, int ntab = 0);
+// k_papply_seg (kv_papply.h): launch_papply where the row of an input position is sg.pscale[p] * sg.seg_grad[sg.pseg[p], :]
+// (kv_types.h SegSrc; the tile sums in front: launch_tsum_seg).  md != nullptr: sd is the tables' SegDesc array (sg is not read)
+template <int OPT>
+int launch_papply_seg(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t s, const SegSrc& sg, const MultiDesc* md = nullptr,
+                      const SegDesc* sd = nullptr, int ntab = 0);
 // k_uapply (kv_uapply.h): the apply on unique ids and pre-summed rows, one launch.  n_dev != nullptr (one table): n bounds
 // the batch and the kernel reads the id count from the device word (k_uapply_counted)
 template <int OPT>
@@ -29,6 +34,8 @@ int launch_uapply(const PartArgs& pa, const void* ids, int ids32, long long n, h
 #define KV_OPT_LAUNCHERS(OPT)                                                                                                \
   template <> int launch_sorted_apply<OPT>(const WsDev&, const PartArgs&, hipStream_t, const MultiDesc*, int, unsigned, int); \
   template <> int launch_papply<OPT>(const WsDev&, const PartArgs&, int, hipStream_t, const MultiDesc*, int);                 \
+  template <> int launch_papply_seg<OPT>(const WsDev&, const PartArgs&, int, hipStream_t, const SegSrc&, const MultiDesc*,    \
+                                         const SegDesc*, int);                                                                \
   template <> int launch_uapply<OPT>(const PartArgs&, const void*, int, long long, hipStream_t, const MultiDesc*, int, \
                                      const long long*)
 KV_OPT_LAUNCHERS(OPT_ADAM_V4);         // kv_opt_adam_v4.hip

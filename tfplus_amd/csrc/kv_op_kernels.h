@@ -952,7 +952,7 @@ __global__ void __launch_bounds__(TB) k_pos_records(SegDesc d, int combiner) {
 template <typename SegT>
 __global__ void __launch_bounds__(TB) k_pos_offsets_multi(const SegDesc* __restrict__ descs) {
   const SegDesc& d = descs[blockIdx.y];
-  if (d.n == 0) return;
+  if (d.n == 0 || !d.seg) return;
   seg_offsets_body(reinterpret_cast<const SegT*>(d.seg), d.n, d.nseg, d.off);
 }
 __global__ void __launch_bounds__(TB) k_pos_den_multi(const SegDesc* __restrict__ descs, int combiner) {
@@ -964,5 +964,10 @@ template <typename SegT>
 __global__ void __launch_bounds__(TB) k_pos_records_multi(const SegDesc* __restrict__ descs, int combiner) {
   const SegDesc& d = descs[blockIdx.y];
   if (d.n == 0) return;
+  if (!d.seg) {   // plain [n, dim] values in src.seg_grad (kv_multi_apply_sparse's mixed form): position j is its own segment,
+                  // and fl(1 * x) is x — the sum kernels read the values' own bits through the records
+    for (long long j = (long long)blockIdx.x * TB + threadIdx.x; j < d.n; j += (long long)gridDim.x * TB) { d.pseg[j] = (int)j; d.pscale[j] = 1.f; }
+    return;
+  }
   pos_records_body(reinterpret_cast<const SegT*>(d.seg), d.off, d.den, d.wts, d.n, d.nseg, combiner, d.pseg, d.pscale);
 }

@@ -1,5 +1,5 @@
 // kv_opt_unit.h — the body of an optimizer's instantiation unit, kv_opt_<name>.hip, which defines KV_OPT (an OPT_*) and
-// includes this: the optimizer's sorted-position (k_apply / k_apply_fin), entry-list (k_papply) and unique-ids (k_uapply)
+// includes this: the optimizer's sorted-position (k_apply / k_apply_fin), entry-list (k_papply, k_papply_seg) and unique-ids (k_uapply)
 // apply kernels behind the launchers of kv_launch.h.  One unit per optimizer, so that `make -j` builds them side by side.
 #include <hip/hip_runtime.h>
 
@@ -30,6 +30,11 @@ int launch_sorted_apply<KV_OPT>(const WsDev& wd, const PartArgs& pa, hipStream_t
 template <>
 int launch_papply<KV_OPT>(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t s, const MultiDesc* md, int ntab) {
   return launch_papply_t<KV_OPT>(wd, pa, mode, s, md, ntab);
+}
+template <>
+int launch_papply_seg<KV_OPT>(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t s, const SegSrc& sg, const MultiDesc* md,
+                              const SegDesc* sd, int ntab) {
+  return launch_papply_seg_t<KV_OPT>(wd, pa, mode, s, sg, md, sd, ntab);
 }
 template <>
 int launch_uapply<KV_OPT>(const PartArgs& pa, const void* ids, int ids32, long long n, hipStream_t s, const MultiDesc* md,

@@ -48,12 +48,16 @@ template <int TBP> struct PaShape { static constexpr int HSK = TBP >= 512 ? 2048
 // FM: the mode when the kernel is compiled for one — PA_UNIQUE (k_papply_uniq: numbering only, no row geometry, none of
 // the apply's registers) and PA_DEDUP (k_papply_dedup: sources summed and stored, no state, no optimizer) have their own
 // kernels and the kernels of the table modes carry none of their code; -1: PA_LOOKUP / PA_APPLYIDX / PA_NONE, an argument
-// SEG (PA_DEDUP only; k_papply_dedup_seg, the sharded sparse apply): a source that is an input position p is the row
-// sg.pscale[p] * sg.seg_grad[sg.pseg[p], :] (kv_types.h SegSrc), each element one multiply; a source tagged EP_TAG is a tile
-// sum in epart, as ever.  a.grad is not read.
+// SEG (PA_DEDUP: k_papply_dedup_seg, the sharded sparse apply; the table modes: k_papply_seg, kv_apply_sparse): a source that
+// is an input position p is the row sg.pscale[p] * sg.seg_grad[sg.pseg[p], :] (kv_types.h SegSrc); a source tagged EP_TAG is a
+// tile sum in epart, as ever.  a.grad is not read.  Each element of such a row is ONE multiply, rounded before any add: load_row
+// writes the product to the source's registers and the sums add those registers, and the library is built with
+// -ffp-contract=off, so the multiply cannot contract into the accumulation — the term is bit for bit the row
+// kv_lookup_sparse_grad would have written.  Nothing but the row fetch differs from the plain form: the same entries,
+// partitions, source lists and hot / cold split add a key's terms in the same order.
 template <int OPT, int V, int LPR, int K, int TBP, int FM = -1, bool SEG = false>
 __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, const int mode_, const SegSrc sg = SegSrc{}) {
-  static_assert(!SEG || FM == PA_DEDUP, "the segment source serves the gradient pre-sum alone");
+  static_assert(!SEG || FM == PA_DEDUP || FM == -1, "the segment source serves the gradient pre-sum and the table modes");
   constexpr bool UQ = FM == PA_UNIQUE, DN = FM == PA_DEDUP_NUM, DD = FM == PA_DEDUP || DN;
   const int mode = FM >= 0 ? (DN ? (int)PA_DEDUP : FM) : (mode_ & 0xFF);
   constexpr int HSK = PaShape<TBP>::HSK;
@@ -761,6 +765,28 @@ __global__ void __launch_bounds__(256, KV_PA_WAVES) k_papply_multi(const MultiDe
   if (blockIdx.x >= m.w.P || m.n == 0) return;
   papply_body<OPT, V, LPR, K, 256>(m.w, m.a, mode);
 }
+// k_papply where the gradient arrives per segment (kv_apply_sparse / kv_multi_apply_sparse): the table modes with the SEG row
+// fetch, in k_papply's block shapes and its batched form (the SegDesc array next to the MultiDesc array).  Kernels of their
+// own names: the training step's k_papply stays instruction for instruction what it was.  Compiled to the scalar fp32 forms
+// only, like the clip kernels (kv_op_kernels.h says why that cannot change a bit: -ffp-contract=off).
+#ifndef KV_SCALAR_FP32
+#if defined(__HIP_DEVICE_COMPILE__)
+#define KV_SCALAR_FP32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define KV_SCALAR_FP32
+#endif
+#endif
+template <int OPT, int V, int LPR, int K, int TBP>
+__global__ void KV_SCALAR_FP32 __launch_bounds__(TBP, KV_PA_WAVES) k_papply_seg(WsDev w, PartArgs a, int mode, SegSrc sg) {
+  papply_body<OPT, V, LPR, K, TBP, -1, true>(w, a, mode, sg);
+}
+template <int OPT, int V, int LPR, int K>
+__global__ void KV_SCALAR_FP32 __launch_bounds__(256, KV_PA_WAVES) k_papply_seg_multi(const MultiDesc* __restrict__ descs,
+                                                                      const SegDesc* __restrict__ segs, int mode) {
+  const MultiDesc& m = descs[blockIdx.y];
+  if (blockIdx.x >= m.w.P || m.n == 0) return;
+  papply_body<OPT, V, LPR, K, 256, -1, true>(m.w, m.a, mode, segs[blockIdx.y].src);
+}
 
 // dispatch on the row geometry (kv_row_geom.h: the float4 rungs up to ENTRY_MAX_Q, the dims fused_ok() admits); one block per
 // partition.  Returns KV_OK, or KV_UNIMPLEMENTED for a dim the entry-list pipeline does not serve.
@@ -774,6 +800,20 @@ int launch_papply_t(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t s
     if (md) k_papply_multi<OPT, V, LPR, K><<<dim3(wd.P, (unsigned)ntab), 256, sh, s>>>(md, mode);
     else if (wd.P <= 512u && !pa.det) k_papply<OPT, V, LPR, K, 512><<<(int)wd.P, 512, sh, s>>>(wd, pa, mode);
     else k_papply<OPT, V, LPR, K, 256><<<(int)wd.P, 256, sh, s>>>(wd, pa, mode);
+    return KV_OK;
+  });
+}
+// ... of k_papply_seg: launch_papply_t's grid, block shapes and choice rule; md: sd is the tables' SegDesc array (sg is not read)
+template <int OPT>
+int launch_papply_seg_t(const WsDev& wd, const PartArgs& pa, int mode, hipStream_t s, const SegSrc& sg, const MultiDesc* md = nullptr,
+                        const SegDesc* sd = nullptr, int ntab = 0) {
+  const size_t sh = (size_t)wd.ntiles * 4 + 32;
+  if ((mode & 0xFF) > PA_NONE) return KV_UNIMPLEMENTED;   // (PA_DEDUP: launch_papply_dedup_seg, kv_sums_seg.hip)
+  return with_row_geom<ENTRY_MAX_Q>(pa.tv.dim, [&](auto g) -> int {
+    constexpr int V = decltype(g)::V, LPR = decltype(g)::LPR, K = decltype(g)::K;
+    if (md) k_papply_seg_multi<OPT, V, LPR, K><<<dim3(wd.P, (unsigned)ntab), 256, sh, s>>>(md, sd, mode);
+    else if (wd.P <= 512u && !pa.det) k_papply_seg<OPT, V, LPR, K, 512><<<(int)wd.P, 512, sh, s>>>(wd, pa, mode, sg);
+    else k_papply_seg<OPT, V, LPR, K, 256><<<(int)wd.P, 256, sh, s>>>(wd, pa, mode, sg);
     return KV_OK;
   });
 }

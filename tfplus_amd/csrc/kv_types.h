@@ -240,7 +240,8 @@ struct SegSrc {
 // what the sum kernels read (src) and what the pre-pass that writes the position records reads and writes
 struct SegDesc {
   SegSrc src;
-  const void* seg;         // [n] segment ids (one dtype for the whole call)
+  const void* seg;         // [n] segment ids (one dtype for the whole call); null (kv_multi_apply_sparse's plain tables, batched
+                           // pre-pass only): src.seg_grad holds [n, dim] values and the records name them one to one
   const float* wts;        // [n] or null
   unsigned* off;           // [nseg + 1] the route table's Workspace::seg_off
   float* den;              // [nseg] its Workspace::seg_den (weighted mean / sqrtn)

@@ -110,7 +110,7 @@ def _fused_norm_ok(var, max_norm, fused_max_norm):
 
 
 def embedding_lookup_sparse(params, sp_ids, sp_weights, partition_strategy="mod", name=None,
-                            combiner=None, max_norm=None, fused_max_norm=False):
+                            combiner=None, max_norm=None, fused_max_norm=False, fused_backward=False):
   """embedding_ops.py:279-441: unique ids -> lookup -> (weighted) segment sum / mean / sqrtn.  One KvVariable without
   max_norm takes one fused native call: kv_lookup_sparse when training (up to 2^21 ids), kv_lookup_sparse_zeros in
   inference mode (read-only, one launch, any number of ids).  Partitioned variables and max_norm take the op chain.
@@ -119,7 +119,11 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, partition_strategy="mod"
   kv_lookup_sparse_zeros_clip in inference mode, any dim); other dims and partitioned variables keep the chain.  Opt-in,
   like AdamOptimizer(fused=True): the fused result differs from the chain's in rounding.
   The segment count is the last segment id + 1, as in the reference: sp_ids.indices on the host cost nothing, indices on
-  a device cost one device-to-host copy in front of the call (embedding_lookup_sparse_multi pays it once for all features)."""
+  a device cost one device-to-host copy in front of the call (embedding_lookup_sparse_multi pays it once for all features).
+  fused_backward=True (opt-in; the fused training call without max_norm only): the backward leaves the segments'
+  gradients unexpanded on the variable and an optimizer of a native family applies them in one call (kv_apply_sparse: the
+  [n, dim] IndexedSlices values are never built); pop_gradients() and every other consumer expand them on demand.  The
+  clipped lookups keep their own backward."""
   if combiner is None:
     combiner = "mean"
   if combiner not in ("mean", "sqrtn", "sum"):
@@ -140,7 +144,7 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, partition_strategy="mod"
     # the training pipeline's bound on the ids does not apply)
     try:
       return plist[0].lookup_sparse(ids, seg, None if sp_weights is None else sp_weights.values, nseg, combiner,
-                                    need_counts, max_norm)
+                                    need_counts, max_norm, fused_backward=bool(fused_backward) and max_norm is None)
     except _lib.UnimplementedError:
       # a table the native clip does not serve although its dim would do (occurrence-order mode, set on the handle): the
       # refusal comes from the host-side checks with nothing queued, and the call keeps the chain like any other such table
@@ -163,7 +167,7 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, partition_strategy="mod"
 
 
 def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None, combiner=None, max_norm=None,
-                                  fused_max_norm=False):
+                                  fused_max_norm=False, fused_backward=False):
   """[embedding_lookup_sparse(p, i, w, combiner=combiner) for p, i, w in zip(...)] — one KvVariable per feature — with
   the features that take the fused path grouped by (device, dim, key dtype): one batched forward per group
   (kv_multi_lookup_sparse: four launches whatever the group's size) under one autograd function, whose backward is one
@@ -173,7 +177,9 @@ def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None
   most one device-to-host copy per call, none for indices on the host).  A feature the fused path does not take — a
   partitioned variable, max_norm, in training mode more ids than one call takes or a variable some earlier feature of its
   group already uses — goes through embedding_lookup_sparse as it is.  So does every feature of a call with max_norm:
-  with fused_max_norm=True through the single-table fused clip ops (there is no batched form of them), else the chain."""
+  with fused_max_norm=True through the single-table fused clip ops (there is no batched form of them), else the chain.
+  fused_backward: as embedding_lookup_sparse's — the groups' backward files one unexpanded gradient per variable, and the
+  optimizer applies the variables of a group in one kv_multi_apply_sparse."""
   if combiner is None:
     combiner = "mean"
   if combiner not in ("mean", "sqrtn", "sum"):
@@ -199,7 +205,7 @@ def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None
     key = None if not fused else (var.device, var.embedding_dim, var.key_dtype, var.trainable) if training else (var.device,)
     if not fused or (training and any(e[1] is var for e in groups.get(key, ()))):
       out[f] = embedding_lookup_sparse(plist, sp_ids, sp_w, combiner=combiner, max_norm=max_norm,
-                                       fused_max_norm=fused_max_norm)
+                                       fused_max_norm=fused_max_norm, fused_backward=fused_backward)
       continue
     seg = torch.as_tensor(sp_ids.indices).to(var.device)[:, 0].to(torch.int64)
     groups.setdefault(key, []).append([f, var, torch.as_tensor(sp_ids.values).to(var.device), seg,
@@ -210,7 +216,7 @@ def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None
   for members in groups.values():
     res = kv_variable_ops.lookup_sparse_multi([m[1] for m in members], [m[2] for m in members], [m[3] for m in members],
                                               [m[4] for m in members], [m[5] for m in members], combiner,
-                                              [m[1].enter_threshold > 0 for m in members])
+                                              [m[1].enter_threshold > 0 for m in members], fused_backward=fused_backward)
     for m, r in zip(members, res):
       out[m[0]] = r
   return out
@@ -218,10 +224,11 @@ def embedding_lookup_sparse_multi(params_list, sp_ids_list, sp_weights_list=None
 
 def safe_embedding_lookup_sparse(embedding_weights, sparse_ids, sparse_weights=None, combiner=None,
                                  default_id=None, name=None, partition_strategy="mod", max_norm=None,
-                                 fused_max_norm=False):
+                                 fused_max_norm=False, fused_backward=False):
   """embedding_ops.py:444-628.  For KvVariables ids < 0 are ordinary keys and are NOT pruned
   (:552-556); non-positive weights are pruned unless combiner == "sum" (:557-560); empty rows are
-  filled with default_id (or read as zeros); the leading shape is restored."""
+  filled with default_id (or read as zeros); the leading shape is restored.  fused_backward: handed to
+  embedding_lookup_sparse."""
   plist = _as_list(embedding_weights)
   dev = plist[0].device
   idx = torch.as_tensor(sparse_ids.indices).to(dev)
@@ -255,7 +262,7 @@ def safe_embedding_lookup_sparse(embedding_weights, sparse_ids, sparse_weights=N
   ind2 = torch.stack([row, torch.zeros_like(row)], 1)
   res = embedding_lookup_sparse(plist, SparseTensor(ind2, vals, [rows, shape[-1]]),
                                 None if w is None else SparseTensor(ind2, w, [rows, shape[-1]]),
-                                partition_strategy, name, combiner, max_norm, fused_max_norm)
+                                partition_strategy, name, combiner, max_norm, fused_max_norm, fused_backward)
   if res.shape[0] < rows:
     res = torch.cat([res, torch.zeros((rows - res.shape[0],) + tuple(res.shape[1:]), device=dev)])
   if default_id is None and empty.numel():

@@ -30,6 +30,7 @@ class KvHandle(object):
     self.enter_threshold = enter_threshold
     self.name = name
     self.batch = None   # (token, ids data_ptr, n, ids version) of the last training lookup
+    self.order = 0      # kv_set_deterministic's last value (KV_ORDER_*)
 
   def __del__(self):
     try:
@@ -556,6 +557,7 @@ def kv_set_deterministic(table_handle, on=True):
   positions (bit-reproducible); 2 (KV_ORDER_OCCURRENCE): one by one in input order, the sum TF-core's unsorted_segment_sum
   takes on the CPU — bit for bit (include/kvhip.h kv_set_deterministic)."""
   _lib.check(_lib.lib().kv_set_deterministic(table_handle.ptr, int(on)))
+  table_handle.order = int(on)
 
 
 def kv_set_fast_math(table_handle, on=True):
@@ -891,6 +893,57 @@ def kv_multi_lookup_sparse_grad(table_handles, seg_grads, segment_ids, weights, 
   _lib.check(_lib.lib().kv_multi_lookup_sparse_grad(n, hp, _ptr_array(gr), segp, segdt, wp, ns, nsegs, _COMBINERS[combiner],
                                                     _ptr_array(outs), _stream(table_handles[0])))
   return outs
+
+
+def kv_variable_apply_sparse(stem, tables, scalars, seg_grad, ids, segment_ids, weights, num_segments, combiner="mean"):
+  """The optimizer step of family `stem` (a row of _lib.OPT_FAMILIES; `scalars` in that row's order) on tables = (var, slot
+  tables...) straight from the SEGMENT gradients of kv_variable_lookup_sparse: what kv_variable_lookup_sparse_grad followed by
+  the family's plain op leaves, without the [n, dim] values (kvhip.h kv_apply_sparse).  Dims that are multiples of 4 up to
+  256, outside occurrence-order mode."""
+  if combiner not in _COMBINERS:
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  var = tables[0]
+  idl = _ids(var, ids).reshape(-1)
+  seg, w = _sparse_args(var, idl.numel(), segment_ids, weights)
+  g = _f32(var, seg_grad).reshape(-1, var.dim)
+  if g.shape[0] != int(num_segments):
+    raise _lib.InvalidArgumentError("seg_grad must have num_segments rows")
+  code, hp = _code_and_hp(stem, scalars)
+  _lib.check(_lib.lib().kv_apply_sparse(var.ptr, code, tables[1].ptr, tables[2].ptr if len(tables) > 2 else None, _hp_array(hp),
+                                        _p(g), _p(idl), _p(seg), _TORCH_KEY[seg.dtype], _p(w), idl.numel(), int(num_segments),
+                                        _COMBINERS[combiner], _stream(var)))
+
+
+def kv_multi_apply_sparse(stem, tables, scalars, grads, ids, segment_ids, weights, num_segments, combiner="mean"):
+  """kv_variable_apply_sparse on many table sets with one launch per stage: tables = (var handles, the handles of each slot
+  role...), same device, dim and key dtype.  A table k with segment_ids[k] None passes plain [n_k, dim] values in grads[k]
+  (num_segments[k] is not read).  weights: None, or a list whose entries may be None (kvhip.h kv_multi_apply_sparse)."""
+  if combiner not in _COMBINERS:
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  vars_ = tables[0]
+  n = len(vars_)
+  if n < 1 or not all(len(x) == n for x in tuple(tables[1:]) + (grads, ids, segment_ids, num_segments)) or \
+      (weights is not None and len(weights) != n):
+    raise _lib.InvalidArgumentError("tables, grads, ids, segment_ids, num_segments (and weights) must be equally long, N >= 1")
+  idl = [_ids(h, i).reshape(-1) for h, i in zip(vars_, ids)]
+  sw = [(None, None) if s is None else _sparse_args(h, i.numel(), s, None if weights is None else weights[k])
+        for k, (h, i, s) in enumerate(zip(vars_, idl, segment_ids))]
+  seg = [s for s, _ in sw]
+  if len({s.dtype for s in seg if s is not None}) > 1:   # one dtype per call
+    seg = [None if s is None else s.to(torch.int64) for s in seg]
+  segdt = next((_TORCH_KEY[s.dtype] for s in seg if s is not None), _lib.KV_DT_INT64)
+  w = [x for _, x in sw]
+  gr = [_f32(h, g).reshape(-1, h.dim) for h, g in zip(vars_, grads)]
+  for g, i, s, m in zip(gr, idl, seg, num_segments):
+    if g.shape[0] != (i.numel() if s is None else int(m)):
+      raise _lib.InvalidArgumentError("grads[k] must have num_segments[k] rows (len(ids[k]) rows for a plain table)")
+  code, hp = _code_and_hp(stem, scalars)
+  handles = [(ctypes.c_void_p * n)(*[h.ptr for h in hs]) for hs in tables]
+  _lib.check(_lib.lib().kv_multi_apply_sparse(
+      n, handles[0], code, handles[1], handles[2] if len(handles) > 2 else None, _hp_array(hp), _ptr_array(gr), _ptr_array(idl),
+      _ptr_array(seg), segdt, _ptr_array(w), (ctypes.c_int64 * n)(*[i.numel() for i in idl]),
+      (ctypes.c_int64 * n)(*[0 if s is None else int(m) for s, m in zip(seg, num_segments)]), _COMBINERS[combiner],
+      _stream(vars_[0])))
 
 
 def kv_variable_lookup_sparse_zeros(table_handle, ids, segment_ids, weights, num_segments, combiner="mean"):

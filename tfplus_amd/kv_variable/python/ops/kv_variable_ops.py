@@ -18,6 +18,20 @@ from tfplus_amd.kv_variable.python.ops import gen_kv_variable_ops
 IS_TRAINING = True  # kv_variable_ops.py:95
 
 IndexedSlices = collections.namedtuple("IndexedSlices", ["values", "indices", "dense_shape"])
+# The gradient of a fused sparse lookup (fused_backward=True) before its expansion: the segments' gradients and the lookup's
+# own arguments.  An optimizer of a native family applies it as it is (kv_apply_sparse: the [n, dim] values are never
+# built); everything else sees the IndexedSlices expand_deferred makes of it — exactly what the default backward files.
+DeferredSparseGrad = collections.namedtuple("DeferredSparseGrad",
+                                            ["seg_grad", "indices", "segment_ids", "weights", "num_segments", "combiner"])
+
+
+def expand_deferred(var, g):
+  """The IndexedSlices of a gradient record of `var` (a DeferredSparseGrad through kv_lookup_sparse_grad)."""
+  if not isinstance(g, DeferredSparseGrad):
+    return g
+  vals = gen_kv_variable_ops.kv_variable_lookup_sparse_grad(var.handle, g.seg_grad, g.segment_ids, g.weights, g.num_segments,
+                                                            g.combiner)
+  return IndexedSlices(vals, g.indices, None)
 
 
 def set_training(flag):
@@ -49,21 +63,21 @@ class _SparseLookupGrad(torch.autograd.Function):
   segment_sum: IndexedSlices(values[j] = scale_j * grad[segment_j], indices = ids) with scale_j =
   w_j (sum), w_j / sum_segment(w) (mean), w_j / sqrt(sum_segment(w^2)) (sqrtn), in one native call
   (kv_lookup_sparse_grad: the denominators summed in position order like the forward's); no gradient
-  flows to sp_weights here."""
+  flows to sp_weights here.  fused_backward: the backward files the segments' gradients themselves (DeferredSparseGrad)."""
 
   @staticmethod
-  def forward(ctx, anchor, var, ids, seg, weights, nseg, combiner, count_occurrences):
+  def forward(ctx, anchor, var, ids, seg, weights, nseg, combiner, count_occurrences, fused_backward):
     ctx.var, ctx.ids, ctx.seg, ctx.weights, ctx.nseg, ctx.combiner = var, ids, seg, weights, nseg, combiner
+    ctx.fused_backward = fused_backward
     return gen_kv_variable_ops.kv_variable_lookup_sparse(var.handle, ids, seg, weights, nseg, combiner,
                                                          count_occurrences)
 
   @staticmethod
   def backward(ctx, grad):
-    var, ids = ctx.var, ctx.ids
-    vals = gen_kv_variable_ops.kv_variable_lookup_sparse_grad(var.handle, grad.reshape(ctx.nseg, -1), ctx.seg, ctx.weights,
-                                                              ctx.nseg, ctx.combiner)
-    var._pending_grads.append(IndexedSlices(vals, ids.reshape(-1), None))
-    return None, None, None, None, None, None, None, None
+    var = ctx.var
+    g = DeferredSparseGrad(grad.reshape(ctx.nseg, -1).contiguous(), ctx.ids.reshape(-1), ctx.seg, ctx.weights, ctx.nseg, ctx.combiner)
+    var._pending_grads.append(g if ctx.fused_backward else expand_deferred(var, g))
+    return None, None, None, None, None, None, None, None, None
 
 
 class _SparseLookupClipGrad(torch.autograd.Function):
@@ -93,25 +107,30 @@ class _SparseLookupClipGrad(torch.autograd.Function):
 class _MultiSparseLookupGrad(torch.autograd.Function):
   """_SparseLookupGrad over the KvVariables of one (device, dim, key dtype) group: the batched forward
   (kv_multi_lookup_sparse), and ONE kv_multi_lookup_sparse_grad in the backward, which files one IndexedSlices on each
-  variable."""
+  variable.  fused_backward: no expansion — one DeferredSparseGrad on each variable."""
 
   @staticmethod
-  def forward(ctx, anchor, vars_, ids, segs, weights, nsegs, combiner, count_occurrences):
+  def forward(ctx, anchor, vars_, ids, segs, weights, nsegs, combiner, count_occurrences, fused_backward):
     ctx.vars, ctx.ids, ctx.segs, ctx.weights, ctx.nsegs, ctx.combiner = vars_, ids, segs, weights, nsegs, combiner
+    ctx.fused_backward = fused_backward
     return tuple(gen_kv_variable_ops.kv_multi_lookup_sparse([v.handle for v in vars_], ids, segs, weights, nsegs, combiner,
                                                             count_occurrences))
 
   @staticmethod
   def backward(ctx, *grads):
+    if ctx.fused_backward:
+      for var, g, ids, seg, w, m in zip(ctx.vars, grads, ctx.ids, ctx.segs, ctx.weights, ctx.nsegs):
+        var._pending_grads.append(DeferredSparseGrad(g.reshape(m, -1).contiguous(), ids.reshape(-1), seg, w, m, ctx.combiner))
+      return None, None, None, None, None, None, None, None, None
     vals = gen_kv_variable_ops.kv_multi_lookup_sparse_grad(
         [v.handle for v in ctx.vars], [g.reshape(m, -1) for g, m in zip(grads, ctx.nsegs)], ctx.segs, ctx.weights, ctx.nsegs,
         ctx.combiner)
     for var, v, ids in zip(ctx.vars, vals, ctx.ids):
       var._pending_grads.append(IndexedSlices(v, ids.reshape(-1), None))
-    return None, None, None, None, None, None, None, None
+    return None, None, None, None, None, None, None, None, None
 
 
-def lookup_sparse_multi(vars_, ids, segment_ids, weights, num_segments, combiner, count_occurrences):
+def lookup_sparse_multi(vars_, ids, segment_ids, weights, num_segments, combiner, count_occurrences, fused_backward=False):
   """KvVariable.lookup_sparse over KvVariables of one device: the list of their [num_segments[i], dim_i] outputs.  In
   training mode the variables share dim and key dtype and each is listed once (kv_multi_lookup_sparse, one autograd
   node); in inference mode they are free to differ and to repeat, and the call is one read-only launch
@@ -125,7 +144,8 @@ def lookup_sparse_multi(vars_, ids, segment_ids, weights, num_segments, combiner
     return gen_kv_variable_ops.batch_kv_variable_lookup_sparse_zeros([v.handle for v in vars_], ids, segs, ws, nsegs, combiner)
   occ = [bool(c) for c in count_occurrences]
   if torch.is_grad_enabled() and all(v.trainable for v in vars_):
-    return list(_MultiSparseLookupGrad.apply(vars_[0]._anchor, list(vars_), ids, segs, ws, nsegs, combiner, occ))
+    return list(_MultiSparseLookupGrad.apply(vars_[0]._anchor, list(vars_), ids, segs, ws, nsegs, combiner, occ,
+                                             bool(fused_backward)))
   return gen_kv_variable_ops.kv_multi_lookup_sparse([v.handle for v in vars_], ids, segs, ws, nsegs, combiner, occ)
 
 
@@ -246,11 +266,14 @@ class KvVariable(object):
     op itself, and embedding_lookup_sparse then keeps the chain."""
     return not IS_TRAINING or (self._embedding_dim % 4 == 0 and self._embedding_dim <= 256)
 
-  def lookup_sparse(self, ids, segment_ids, weights, num_segments, combiner, count_occurrences, max_norm=None):
+  def lookup_sparse(self, ids, segment_ids, weights, num_segments, combiner, count_occurrences, max_norm=None,
+                    fused_backward=False):
     """embedding_lookup_sparse on this table in one fused call: kv_lookup_sparse when training (missing keys are
     inserted, the gradient is filed on the variable), kv_lookup_sparse_zeros else (GatherOrZeros rows, read-only, no
     autograd node and no pending gradient; count_occurrences has no meaning there).  max_norm: every looked-up row is
-    clipped to that norm inside the same kernels (kv_lookup_sparse_clip, its _grad, kv_lookup_sparse_zeros_clip)."""
+    clipped to that norm inside the same kernels (kv_lookup_sparse_clip, its _grad, kv_lookup_sparse_zeros_clip).
+    fused_backward (training, no max_norm — the clip's gradient is not a scaled segment row): the backward files the
+    segments' gradients unexpanded, for the optimizer's kv_apply_sparse (DeferredSparseGrad)."""
     ids = torch.as_tensor(ids).to(self._device).reshape(-1)
     seg = torch.as_tensor(segment_ids).to(self._device).reshape(-1)
     w = None if weights is None else torch.as_tensor(weights, dtype=torch.float32).to(self._device).reshape(-1)
@@ -266,7 +289,7 @@ class KvVariable(object):
       return gen_kv_variable_ops.kv_variable_lookup_sparse_zeros(self._handle, ids, seg, w, num_segments, combiner)
     if self._trainable and torch.is_grad_enabled():
       return _SparseLookupGrad.apply(self._anchor, self, ids, seg, w, int(num_segments), combiner,
-                                     bool(count_occurrences))
+                                     bool(count_occurrences), bool(fused_backward))
     return gen_kv_variable_ops.kv_variable_lookup_sparse(self._handle, ids, seg, w, num_segments, combiner,
                                                          count_occurrences)
 
@@ -384,11 +407,21 @@ class KvVariable(object):
   def delete_with_timestamp(self, threshold, name=None):
     return gen_kv_variable_ops.kv_variable_delete_with_timestamp(self._handle, threshold)
 
-  def pop_gradients(self):
-    """All IndexedSlices produced by backward passes since the last call, concatenated."""
+  def serves_apply_sparse(self):
+    """Does kv_apply_sparse serve this table?  Dims that are multiples of 4 up to 256, outside occurrence-order mode
+    (kvhip.h)."""
+    return self._embedding_dim % 4 == 0 and self._embedding_dim <= 256 and self._handle.order != 2
+
+  def pop_gradients(self, deferred=False):
+    """All IndexedSlices produced by backward passes since the last call, concatenated.  deferred=True (the optimizers): a
+    pending gradient that is exactly one DeferredSparseGrad comes back as it is; in every other case, and for every caller
+    that does not ask, deferred records are expanded first — today's IndexedSlices."""
     g, self._pending_grads = self._pending_grads, []
     if not g:
       return None
+    if deferred and len(g) == 1 and isinstance(g[0], DeferredSparseGrad):
+      return g[0]
+    g = [expand_deferred(self, x) for x in g]
     return IndexedSlices(torch.cat([x.values for x in g]), torch.cat([x.indices for x in g]), None)
 
   # -- scatter family (kv_variable_ops.py:1263-1338) ----------------------------------------------------

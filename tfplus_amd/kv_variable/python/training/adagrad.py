@@ -22,3 +22,6 @@ class AdagradOptimizer(Optimizer):
     acc = self.get_slot(var, "accumulator")
     return gen_kv_variable_ops.kv_variable_sparse_apply_adagrad(
         var.handle, acc.handle, self._learning_rate, grad, indices, use_locking=True)
+
+  def _native_step(self, var):
+    return "adagrad", (self.get_slot(var, "accumulator"),), (self._learning_rate, True)

@@ -56,6 +56,12 @@ class AdamOptimizer(Optimizer):
     upd = float(lr) * m / (float(np.float32(self._epsilon)) + torch.sqrt(v))
     return gen_kv_variable_ops.kv_variable_scatter_sub_v2(var.handle, ids, upd)
 
+  def _native_step(self, var):
+    if not self._fused:
+      return None
+    return ("adam", (self.get_slot(var, "m_v"),),
+            (self._lr, self._beta1_power, self._beta2_power, self._beta1, self._beta2, self._epsilon))
+
   def _finish(self):
     self._beta1_power = np.float32(self._beta1_power * np.float32(self._beta1))
     self._beta2_power = np.float32(self._beta2_power * np.float32(self._beta2))

@@ -48,11 +48,18 @@ class FtrlOptimizer(Optimizer):
     return self._apply_op(var.handle, accum.handle, linear.handle, grad, indices, self._learning_rate, self._l1,
                           self._adjusted_l2(), self._l2_shrinkage, self._learning_rate_power, use_locking=True)
 
+  _stem = "ftrl_v2"
+
+  def _native_step(self, var):
+    return (self._stem, (self.get_slot(var, "accum"), self.get_slot(var, "linear")),
+            (self._learning_rate, self._l1, self._adjusted_l2(), self._l2_shrinkage, self._learning_rate_power))
+
 
 class GroupFtrlOptimizer(FtrlOptimizer):
   """FTRL with a group-lasso threshold l1 on each key's whole linear row (kvhip.h kv_apply_group_ftrl_v2)."""
 
   _apply_op = staticmethod(gen_kv_variable_ops.kv_variable_group_sparse_apply_ftrl_v2)
+  _stem = "group_ftrl_v2"
 
   def __init__(self, learning_rate, learning_rate_power=-0.5, initial_accumulator_value=0.1,
                l1_regularization_strength=0.0, l2_regularization_strength=0.0, use_locking=False, name="GroupFtrl",

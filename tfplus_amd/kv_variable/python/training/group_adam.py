@@ -53,6 +53,11 @@ class GroupAdamOptimizer(Optimizer):
     return fn(var.handle, slot.handle, grad, indices, self._lr, self._beta1_power, self._beta2_power,
               self._beta1, self._beta2, self._epsilon, self._l1, self._l2, self._l21, use_locking=False)
 
+  def _native_step(self, var):
+    return ("group_adam", (self.get_slot(var, "m_v_linear"),),
+            (self._lr, self._beta1_power, self._beta2_power, self._beta1, self._beta2, self._epsilon, self._l1, self._l2,
+             self._l21, 4 if self._version == 4 else 3))
+
   def _finish(self):
     self._beta1_power = np.float32(self._beta1_power * np.float32(self._beta1))
     self._beta2_power = np.float32(self._beta2_power * np.float32(self._beta2))

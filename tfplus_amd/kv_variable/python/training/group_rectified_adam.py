@@ -43,3 +43,9 @@ class GroupRectifiedAdamOptimizer(RectifiedAdamOptimizer):
         var.handle, self.get_slot(var, "opt").handle, grad, indices, lr_t, self._beta1_power, self._beta2_power,
         self._beta1, self._beta2, self._epsilon, self._l1, self._l2, self._l21, r_t, tractable, self._amsgrad,
         self._use_nesterov, use_locking=False)
+
+  def _native_step(self, var):
+    lr_t, _, _, tractable, r_t = self._step_scalars()
+    return ("group_rectified_adam", (self.get_slot(var, "opt"),),
+            (lr_t, self._beta1_power, self._beta2_power, self._beta1, self._beta2, self._epsilon, self._l1, self._l2, self._l21,
+             r_t, bool(tractable), bool(self._amsgrad), bool(self._use_nesterov)))

@@ -10,8 +10,9 @@ to the op, which does that step on the GPU (include/kvhip.h, "sparse optimizer a
 """
 import torch
 
-from tfplus_amd.kv_variable.python.ops import variable_scope
-from tfplus_amd.kv_variable.python.ops.kv_variable_ops import IndexedSlices, KvVariable
+from tfplus_amd import _lib
+from tfplus_amd.kv_variable.python.ops import gen_kv_variable_ops, variable_scope
+from tfplus_amd.kv_variable.python.ops.kv_variable_ops import DeferredSparseGrad, IndexedSlices, KvVariable, expand_deferred
 from tfplus_amd.kv_variable.python.ops.variable_scope import PartitionedKvVariable
 
 
@@ -81,7 +82,33 @@ class Optimizer(object):
     for v in vs:
       v.pop_gradients()
     loss.backward()
-    return [(v.pop_gradients(), v) for v in vs]
+    return [(v.pop_gradients(deferred=True), v) for v in vs]
+
+  def _native_step(self, var):
+    """(family stem of _lib.OPT_FAMILIES, the var's slot variables, the family's scalars) where this optimizer's step on
+    `var` is one native op, else None: what lets apply_gradients hand a DeferredSparseGrad to kv_apply_sparse."""
+    return None
+
+  def _apply_deferred(self, grads_and_vars):
+    """The fused sparse applies: the vars of one (device, dim, key dtype, combiner) in one kv_multi_apply_sparse.  A group
+    the op does not serve after all (a table moved to occurrence-order mode behind the Python handle: refused by the
+    host-side checks with nothing queued) is expanded and applied as today."""
+    groups = {}
+    for g, v in grads_and_vars:
+      groups.setdefault((v.device.index, v.embedding_dim, v.key_dtype, g.combiner), []).append((g, v))
+    for members in groups.values():
+      steps = [self._native_step(v) for _, v in members]
+      stem, scalars = steps[0][0], steps[0][2]
+      tables = ([v.handle for _, v in members],) + tuple([st[1][r].handle for st in steps] for r in range(len(steps[0][1])))
+      gs = [g for g, _ in members]
+      try:
+        gen_kv_variable_ops.kv_multi_apply_sparse(stem, tables, scalars, [g.seg_grad for g in gs], [g.indices for g in gs],
+                                                  [g.segment_ids for g in gs], [g.weights for g in gs],
+                                                  [g.num_segments for g in gs], gs[0].combiner)
+      except _lib.UnimplementedError:
+        for g, v in members:
+          e = expand_deferred(v, g)
+          self._resource_apply_sparse(e.values, v, e.indices)
 
   def apply_gradients(self, grads_and_vars, global_step=None, name=None):
     grads_and_vars = [(g, v) for g, v in grads_and_vars if g is not None]
@@ -90,12 +117,19 @@ class Optimizer(object):
     for g, v in grads_and_vars:
       if not isinstance(v, KvVariable):
         raise TypeError("only KvVariables are handled here, got %r" % (v,))
-      if not isinstance(g, IndexedSlices):
+      if not isinstance(g, (IndexedSlices, DeferredSparseGrad)):
         raise TypeError("Gradient must be IndexedSlices for a KvVariable: %r" % (g,))
     self._create_slots([v for _, v in grads_and_vars])
     self._prepare()
+    # a deferred sparse gradient goes to the fused call where the step is one native op and the op serves the var (its
+    # dim, and not occurrence-order mode); every other one is expanded into the IndexedSlices the default backward files
+    fused = [(g, v) for g, v in grads_and_vars
+             if isinstance(g, DeferredSparseGrad) and v.serves_apply_sparse() and self._native_step(v) is not None]
+    self._apply_deferred(fused)
     for g, v in grads_and_vars:
-      self._resource_apply_sparse(g.values, v, g.indices)
+      if not any(g is f for f, _ in fused):
+        g = expand_deferred(v, g)
+        self._resource_apply_sparse(g.values, v, g.indices)
     self._finish()
 
   def minimize(self, loss, var_list=None, global_step=None):

@@ -42,3 +42,7 @@ class SparseGroupFtrlOptimizer(Optimizer):
     return gen_kv_variable_ops.kv_variable_sparse_group_sparse_apply_ftrl_v2(
         var.handle, accum.handle, linear.handle, grad, indices, self._learning_rate, self._l1, self._l2,
         self._l21, self._l2_shrinkage, self._learning_rate_power, use_locking=True)
+
+  def _native_step(self, var):
+    return ("sparse_group_ftrl", (self.get_slot(var, "accum"), self.get_slot(var, "linear")),
+            (self._learning_rate, self._l1, self._l2, self._l21, self._l2_shrinkage, self._learning_rate_power))
