@@ -357,7 +357,7 @@ int kv_dedup_segment_sum_dev(kv_handle_t h, const void* ids, const float* grad, 
 /* kv_apply_<optimizer>_unique with the id count taken from the DEVICE: the op is applied to the first
  * min(n_max, *n_dev) ids and gradient rows, *n_dev (int64, device memory — kv_dedup_segment_sum_dev's or kv_unique's
  * num_unique_dev) being read by the kernel when it runs.  `optimizer`, `hp` and `slot1` are kv_shard_apply_serve's
- * codes and layouts (0 .. 7, below).  The same promise of unique ids, the same duplicate guard, checks, results and slot
+ * codes and layouts (0 .. 8, below).  The same promise of unique ids, the same duplicate guard, checks, results and slot
  * mirror handling as the _unique ops: the same bits.  `ids` [n_max] are KV_DT_INT64 or KV_DT_INT32 (ids_dtype) whatever
  * the table's key dtype — the dedup writes int64 ids for every table.  `grad` is [n_max, dim].
  * The host sizes everything by n_max: the tables' capacity (their row bounds advance by n_max per call, so a table
@@ -378,7 +378,7 @@ int kv_apply_unique_counted(kv_handle_t var, int optimizer, kv_handle_t slot0, k
  * those back to sum them per distinct id — writes and reads n * dim * 4 bytes that carry no information; here the tile sums and
  * the partition pass + update fetch a position's row from the segment gradients themselves, through per-position records
  * (segment, scale: 8 bytes a position) that a small pre-pass leaves in the var table's workspace.  The values buffer is never
- * allocated.  `optimizer`, `slot0`, `slot1` and `hp` are kv_shard_apply_serve's codes and layouts (0 .. 7, below), validated as
+ * allocated.  `optimizer`, `slot0`, `slot1` and `hp` are kv_shard_apply_serve's codes and layouts (0 .. 8, below), validated as
  * kv_apply_unique_counted validates them: the hyperparameter checks, their order and their wording are the named ops'.
  *   kv_apply_sparse        seg_grad [num_segments, dim], ids [n] of the table's key dtype, segment_ids [n] int32 or int64,
  *                          weights [n] or NULL: kv_lookup_sparse's arguments of the batch.  n == 0: a no-op, KV_OK.
@@ -710,6 +710,55 @@ int kv_multi_apply_adam_unique(int num_tables, const kv_handle_t* vars, const kv
                                const void* const* ids, const int64_t* ns, float lr, float beta1_power, float beta2_power,
                                float beta1, float beta2, float epsilon, kv_stream_t stream);
 
+/* Plain RectifiedAdam (RAdam), one op.  The reference has no kernel for it: its RectifiedAdamOptimizer composes the sparse
+ * step from generic ops (python/training/rectified_adam.py:68-96: the de-duplication, gather_or_insert and scatter_update
+ * on m, v and, for amsgrad, vhat, an optional gather_or_insert on the var for the weight decay, scatter_sub on the var).
+ * This op leaves what that chain leaves.  `opt` is ONE slot table of dim 3 x the var's: [m | v | vhat]; the vhat block is
+ * read and written only with amsgrad == 1 — otherwise it keeps what it holds, and a row inserted now gets its init value.
+ * Per distinct id, g = the id's summed gradient row, every operation one fp32 rounding, in this order (:76-96):
+ *   m = beta1 m + g (1 - beta1);  mu = use_nesterov ? g (1 - beta1) + beta1 m : m;  mc = mu / (1 - beta1_power)
+ *   v = beta2 v + (g g) (1 - beta2)
+ *   amsgrad: vhat = max(v, vhat), vc = sqrt(vhat / (1 - beta2_power));  else vc = sqrt(v / (1 - beta2_power))
+ *   upd = tractable ? (r_t mc) / (vc + epsilon) : mc;  weight_decay > 0: upd = upd + weight_decay var
+ *   var = var - upd lr_t
+ * lr_t (warmed up / decayed), r_t, tractable and the powers are the caller's (:281-345); 1 - beta1, 1 - beta2,
+ * 1 - beta1_power and 1 - beta2_power are computed once on the host, in fp32.  Bookkeeping is the chain's, as kv_apply_adam's
+ * above (slot row found or inserted with the day stamp, one hit per distinct id, a blacklisted row read as zeros and left
+ * unwritten; var row found or inserted, its frequency word and day untouched, no enter-threshold filter, no CoverUpdate, a
+ * blacklisted row not written; flags from the rows written; every id marked in both delta lists).  With weight_decay > 0
+ * the chain also runs GatherOrInsert on the var (:95), so then, and only then, the var's record gets one hit per distinct
+ * id and the day stamp as well (a row inserted now: day << 16 | 1).
+ * KV_INVALID_ARGUMENT for lr_t <= 0, beta1_power >= 1 or beta2_power >= 1, weight_decay < 0, a flag other than 0 or 1,
+ * var == opt, an opt dim other than 3 x the var's ("opt must be 3x") and tables on different devices;
+ * KV_FAILED_PRECONDITION for an uninitialised table.  Dims, limits, graph capture, deterministic modes, fast math and delta
+ * tracking as kv_apply_adam.  _unique / _tok: the forms of kv_apply_group_adam_unique / _tok. */
+int kv_apply_rectified_adam(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr_t,
+                            float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float weight_decay,
+                            float r_t, int tractable, int amsgrad, int use_nesterov, kv_stream_t stream);
+int kv_apply_rectified_adam_tok(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr_t,
+                                float beta1_power, float beta2_power, float beta1, float beta2, float epsilon,
+                                float weight_decay, float r_t, int tractable, int amsgrad, int use_nesterov,
+                                kv_batch_token_t token, kv_stream_t stream);
+int kv_apply_rectified_adam_unique(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr_t,
+                                   float beta1_power, float beta2_power, float beta1, float beta2, float epsilon,
+                                   float weight_decay, float r_t, int tractable, int amsgrad, int use_nesterov,
+                                   kv_stream_t stream);
+/* ... on many (var, opt) pairs of one dim, shaped like kv_multi_apply_adam[_tok|_unique]. */
+int kv_multi_apply_rectified_adam(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts, const float* const* grads,
+                                  const void* const* ids, const int64_t* ns, float lr_t, float beta1_power, float beta2_power,
+                                  float beta1, float beta2, float epsilon, float weight_decay, float r_t, int tractable,
+                                  int amsgrad, int use_nesterov, kv_stream_t stream);
+int kv_multi_apply_rectified_adam_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                      const float* const* grads, const void* const* ids, const int64_t* ns, float lr_t,
+                                      float beta1_power, float beta2_power, float beta1, float beta2, float epsilon,
+                                      float weight_decay, float r_t, int tractable, int amsgrad, int use_nesterov,
+                                      const kv_batch_token_t* tokens, kv_stream_t stream);
+int kv_multi_apply_rectified_adam_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                         const float* const* grads, const void* const* ids, const int64_t* ns, float lr_t,
+                                         float beta1_power, float beta2_power, float beta1, float beta2, float epsilon,
+                                         float weight_decay, float r_t, int tractable, int amsgrad, int use_nesterov,
+                                         kv_stream_t stream);
+
 
 /* embedding_lookup_sparse on a KvVariable (python/ops/embedding_ops.py:279-441), fused: the
  * reference runs unique_with_counts -> GatherOrInsert[WithCounts] -> gather(idx) -> (x weights) ->
@@ -956,7 +1005,9 @@ int kv_shard_apply_route(kv_shard_t shard, const float* grad, kv_stream_t stream
  * 4 FTRL-V2, 5 group FTRL-V2 (hp = lr, l1, l2, l2_shrinkage, lr_power; slot1 = linear),
  * 6 group RectifiedAdam (kernels/training_ops.cc:6694-6978; hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2,
  * l21, r_t, tractable, amsgrad, use_nesterov — the three flags as 0 / 1; slot0 = opt, slot1 unused),
- * 7 Adam (kv_apply_adam; hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon; slot0 = m_v, slot1 unused) */
+ * 7 Adam (kv_apply_adam; hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon; slot0 = m_v, slot1 unused),
+ * 8 RectifiedAdam (kv_apply_rectified_adam; hp = lr_t, beta1_power, beta2_power, beta1, beta2, epsilon, weight_decay, r_t,
+ * tractable, amsgrad, use_nesterov — the three flags as 0 / 1; slot0 = opt, slot1 unused) */
 int kv_shard_apply_serve(kv_shard_t shard, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp,
                          kv_stream_t stream);
 int kv_shard_lookup(kv_shard_t shard, kv_comm_t comm, const void* ids, int64_t n, float* out, int join,

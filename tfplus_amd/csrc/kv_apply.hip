@@ -1,6 +1,6 @@
 // kv_apply.hip — the optimizer layer of the C ABI on the table core (kv_host.h): one parser per optimizer family, the two
 // bodies (apply_one: one table; multi_apply: many tables, one launch per stage; the PartArgs of all their launches start
-// from opt_part_args), the 42 kv_apply_* / kv_multi_apply_* entry points, kv_[multi_]apply_sparse (the same bodies fed from
+// from opt_part_args), the 48 kv_apply_* / kv_multi_apply_* entry points, kv_[multi_]apply_sparse (the same bodies fed from
 // segment gradients) and kv_attach_slot.  It compiles no kernel: the
 // optimizers' kernels are reached through the typed launchers of kv_launch.h, the pipelines' through the core's.
 #include <hip/hip_runtime.h>
@@ -142,6 +142,7 @@ static WideSlotWords wide_slot_words(int opt) {
     case OPT_GROUP_RADAM:
       return {"opt", "kv_variable and opt_shape do not have the same shape [%d] [%d] (opt must be 5x)", "", false};
     case OPT_ADAM: return {"m_v", "var and m_v do not have matching shapes [%d] [%d] (m_v must be 2x)", ": m_v must be 2x", true};
+    case OPT_RADAM: return {"opt", "var and opt do not have matching shapes [%d] [%d] (opt must be 3x)", ": opt must be 3x", true};
     default: return {"slot", "var and slot do not have matching shapes [%d] [%d]", "", false};
   }
 }
@@ -525,6 +526,35 @@ static OptCall adam_call(float lr, float b1p, float b2p, float b1, float b2, flo
   return c;
 }
 
+// Plain RectifiedAdam: the reference composes it from generic ops (python/training/rectified_adam.py:68-96), so the checks
+// are this library's own.  slot row = m | v | vhat.  lr_t, r_t, tractable and the powers are the caller's
+// (RectifiedAdamOptimizer._step_scalars); the four differences from 1 once, in fp32.  A power at or above 1 would divide by
+// zero or take a negative root
+static OptCall radam_call(float lr_t, float b1p, float b2p, float b1, float b2, float eps, float wd, float r_t, int tractable,
+                          int amsgrad, int use_nesterov) {
+  OptCall c;
+  c.opt = OPT_RADAM;
+  c.slot_mult = slot0_blocks(OPT_RADAM);
+  if (!(lr_t > 0.f)) { c.status = fail(KV_INVALID_ARGUMENT, "lr_t is not a positive scalar: %g", lr_t); return c; }
+  if (!(b1p < 1.f)) { c.status = fail(KV_INVALID_ARGUMENT, "beta1_power is not below 1: %g", b1p); return c; }
+  if (!(b2p < 1.f)) { c.status = fail(KV_INVALID_ARGUMENT, "beta2_power is not below 1: %g", b2p); return c; }
+  if (!(wd >= 0.f)) { c.status = fail(KV_INVALID_ARGUMENT, "weight_decay is negative: %g", wd); return c; }
+  for (int f : {tractable, amsgrad, use_nesterov})
+    if (f != 0 && f != 1) { c.status = fail(KV_INVALID_ARGUMENT, "tractable, amsgrad and use_nesterov are 0 or 1: %d", f); return c; }
+  OptArgs& a = c.a;
+  a.lr = lr_t; a.b1p = b1p; a.b2p = b2p; a.b1 = b1; a.b2 = b2; a.eps = eps;
+  radam_omb1(a) = 1.f - b1;
+  radam_omb2(a) = 1.f - b2;
+  radam_c1(a) = 1.f - b1p;
+  radam_c2(a) = 1.f - b2p;
+  radam_wd(a) = wd;
+  radam_r_t(a) = r_t;
+  radam_flags(a) = (tractable ? RADAM_TRACTABLE : 0) | (amsgrad ? RADAM_AMSGRAD : 0) | (use_nesterov ? RADAM_NESTEROV : 0);
+  return c;
+}
+// a flag in the generic entries' float vector: 0 or 1; anything else goes on as -1, which radam_call refuses
+static int hp_flag(float f) { return f == 0.f ? 0 : f == 1.f ? 1 : -1; }
+
 // the one place where a runtime OPT_* becomes the template argument of the pipelines
 template <class F>
 static int with_opt(int opt, F&& f) {
@@ -537,6 +567,7 @@ static int with_opt(int opt, F&& f) {
     case OPT_GROUP_FTRL_V2: return f(std::integral_constant<int, OPT_GROUP_FTRL_V2>());
     case OPT_GROUP_RADAM: return f(std::integral_constant<int, OPT_GROUP_RADAM>());
     case OPT_ADAM: return f(std::integral_constant<int, OPT_ADAM>());
+    case OPT_RADAM: return f(std::integral_constant<int, OPT_RADAM>());
     default: return fail(KV_INTERNAL, "optimizer %d", opt);
   }
 }
@@ -550,7 +581,9 @@ namespace __attribute__((visibility("hidden"))) kvhip_internal {
 // 4 FTRL-V2 / 5 group FTRL-V2 (hp = lr, l1, l2, l2_shrinkage, lr_power; slot1 = linear),
 // 6 group RectifiedAdam (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad,
 // use_nesterov; the three flags as 0 / 1),
-// 7 Adam (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon; slot0 = m_v)
+// 7 Adam (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon; slot0 = m_v),
+// 8 RectifiedAdam (hp = lr_t, beta1_power, beta2_power, beta1, beta2, epsilon, weight_decay, r_t, tractable, amsgrad,
+// use_nesterov; the three flags as 0 / 1; slot0 = opt)
 OptCall shard_opt_call(int optimizer, const float* hp) {
   switch (optimizer) {
     case OPT_ADAM_V4: case OPT_ADAM_V3:
@@ -562,6 +595,8 @@ OptCall shard_opt_call(int optimizer, const float* hp) {
       return group_radam_call(hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8], hp[9], hp[10] != 0.f, hp[11] != 0.f,
                               hp[12] != 0.f);
     case OPT_ADAM: return adam_call(hp[0], hp[1], hp[2], hp[3], hp[4], hp[5]);
+    case OPT_RADAM:
+      return radam_call(hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp_flag(hp[8]), hp_flag(hp[9]), hp_flag(hp[10]));
     default: return OptCall{};
   }
 }
@@ -756,6 +791,38 @@ int kv_multi_apply_adam_unique(int num_tables, const kv_handle_t* vars, const kv
                                float eps, kv_stream_t stream) {
   return multi_apply(adam_call(lr, b1p, b2p, b1, b2, eps), num_tables, vars, mvs, nullptr, grads, ids, ns, nullptr, stream, true);
 }
+
+#define KV_RADAM_PARAMS float lr_t, float b1p, float b2p, float b1, float b2, float eps, float wd, float r_t, int tractable, \
+                        int amsgrad, int use_nesterov
+#define KV_RADAM_CALL radam_call(lr_t, b1p, b2p, b1, b2, eps, wd, r_t, tractable, amsgrad, use_nesterov)
+int kv_apply_rectified_adam(kv_handle_t v, kv_handle_t opt, const float* grad, const void* ids, int64_t n, KV_RADAM_PARAMS,
+                            kv_stream_t stream) {
+  return apply_one(KV_RADAM_CALL, v, opt, nullptr, grad, ids, n, 0, stream, false);
+}
+int kv_apply_rectified_adam_tok(kv_handle_t v, kv_handle_t opt, const float* grad, const void* ids, int64_t n, KV_RADAM_PARAMS,
+                                kv_batch_token_t token, kv_stream_t stream) {
+  return apply_one(KV_RADAM_CALL, v, opt, nullptr, grad, ids, n, token, stream, false);
+}
+int kv_apply_rectified_adam_unique(kv_handle_t v, kv_handle_t opt, const float* grad, const void* ids, int64_t n, KV_RADAM_PARAMS,
+                                   kv_stream_t stream) {
+  return apply_one(KV_RADAM_CALL, v, opt, nullptr, grad, ids, n, 0, stream, true);
+}
+int kv_multi_apply_rectified_adam(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts, const float* const* grads,
+                                  const void* const* ids, const int64_t* ns, KV_RADAM_PARAMS, kv_stream_t stream) {
+  return multi_apply(KV_RADAM_CALL, num_tables, vars, opts, nullptr, grads, ids, ns, nullptr, stream, false);
+}
+int kv_multi_apply_rectified_adam_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts, const float* const* grads,
+                                      const void* const* ids, const int64_t* ns, KV_RADAM_PARAMS, const kv_batch_token_t* tokens,
+                                      kv_stream_t stream) {
+  return multi_apply(KV_RADAM_CALL, num_tables, vars, opts, nullptr, grads, ids, ns, tokens, stream, false);
+}
+int kv_multi_apply_rectified_adam_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                         const float* const* grads, const void* const* ids, const int64_t* ns, KV_RADAM_PARAMS,
+                                         kv_stream_t stream) {
+  return multi_apply(KV_RADAM_CALL, num_tables, vars, opts, nullptr, grads, ids, ns, nullptr, stream, true);
+}
+#undef KV_RADAM_PARAMS
+#undef KV_RADAM_CALL
 
 int kv_apply_adagrad(kv_handle_t v, kv_handle_t acc, float lr, const float* grad, const void* ids, int64_t n, int update_slots,
                      kv_stream_t stream) {

@@ -428,7 +428,8 @@ __device__ __forceinline__ bool group_any(bool p) {
 // SparseGroupSparseApplyFtrlOp (training_ops.cc:7142-7197, 5871-5927, 1455-1486, 684-763).
 // State rows the caller already holds (requested together with the gradient rows, so the update needs no
 // second round trip): x = the var row; s[0 .. slot0_blocks(OPT)) = the first slot table's row in blocks of dim floats
-// (GroupAdam m | v | z; group RectifiedAdam m | v | linear | vhat | vamsgrad; Adam m | v; Adagrad / FTRL accum in s[0]).  have_x /
+// (GroupAdam m | v | z; group RectifiedAdam m | v | linear | vhat | vamsgrad; Adam m | v; RectifiedAdam m | v | vhat;
+// Adagrad / FTRL accum in s[0]).  have_x /
 // have_s say which of them are valid.  (s has opt_core's width, state_blocks(OPT): the lean paths hand it over as it is.)
 template <int OPT, int V, int K>
 struct PreRows {
@@ -444,14 +445,14 @@ struct PreRows {
 // Restates the per-id body of KvVariableGroupSparseApplyAdamV4Op / V3Op / SparseApplyAdagradOp /
 // SparseGroupSparseApplyFtrlOp / SparseApplyFtrlOp / GroupSparseApplyFtrlOp / GroupSparseApplyRectifiedAdamOp
 // (training_ops.cc:7142-7197, 5871-5927, 1455-1486, 684-763, 457-484, 977-1019, 6883-6936) and, for Adam, the row
-// arithmetic of the reference's Python composition (python/training/adam.py:93-163).
+// arithmetic of the reference's Python compositions (python/training/adam.py:93-163, rectified_adam.py:76-96).
 template <int OPT, int V, int LPR, int K>
 __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row, unsigned char* fvp, unsigned char* f0p,
                                          unsigned char* f1p, bool act, bool new0, int D, const float (&gv)[K][V],
                                          const OptArgs& a, int lane, const float (&xin)[K][V],
                                          const float (&sin)[state_blocks(OPT)][K][V], bool new1 = false, bool vblack = false,
                                          bool sblack = false) {
-  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_ADAM, "opt_core: unknown optimizer");
+  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_RADAM, "opt_core: unknown optimizer");
   if (group_adam(OPT)) {
     // training_ops.cc:7166-7195 (V4) / :5895-5925 (V3); slot row = [m | v | z]
     float m[K][V], nv[K][V], sq[K][V], z[K][V], uu[K][V];
@@ -794,7 +795,7 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
       *fvp = (unsigned char)(upd ? (anyx ? 0u : FLAG_UNDER) : (FLAG_BLACK | FLAG_UNDER));
       *f0p = (unsigned char)(anys ? 0u : FLAG_UNDER);
     }
-  } else {
+  } else if (OPT == OPT_ADAM) {
     // OPT_ADAM: python/training/adam.py:93-163 on one de-duplicated id; slot row = [m | v].  a.alpha = lr_t =
     // lr sqrt(1 - beta2_power) / (1 - beta1_power), adam_omb1 / adam_omb2 = 1 - beta1 / 1 - beta2 (host, fp32).  One pass:
     // nothing couples the elements of a row, so no value outlives its element block.  The gather hands a blacklisted slot
@@ -825,6 +826,82 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
       }
     }
     const bool anyx = group_any<LPR>(big), anys = group_any<LPR>(sbig);
+    if (act && lane == 0) {
+      // UpdateUnderThreshold on the rows written (kv_variable.h:706, 837-861); a blacklisted row keeps its flags
+      if (!vblack) *fvp = (unsigned char)(anyx ? 0u : FLAG_UNDER);
+      if (!sblack) *f0p = (unsigned char)(anys ? 0u : FLAG_UNDER);
+    }
+  } else {
+    // OPT_RADAM: python/training/rectified_adam.py:76-96 on one de-duplicated id; slot row = [m | v | vhat].  a.lr = the
+    // caller's lr_t; radam_omb1 / radam_omb2 / radam_c1 / radam_c2 = 1 - beta1 / 1 - beta2 / 1 - beta1_power /
+    // 1 - beta2_power (host, fp32).  One pass, as Adam's: the nesterov look-ahead, the two bias corrections, the amsgrad
+    // maximum and the decay term are all per element, so no value outlives its element block and the three flags are
+    // wave-uniform selects inside it.  The vhat block is held, compared and stored under amsgrad only (slot_block_used:
+    // the callers did not load it otherwise); a row inserted now gets its init value written, as every block of a new row.
+    // Blacklisted rows as in Adam's chain: the slot row reads as zeros and neither row is written (the decay term of a
+    // blacklisted var row goes nowhere)
+    bool big = false, sbig = false;
+    const bool fm = KV_FASTM(a);
+    const int fl = radam_flags(a);
+    const bool tract = (fl & RADAM_TRACTABLE) != 0, ams = (fl & RADAM_AMSGRAD) != 0, nest = (fl & RADAM_NESTEROV) != 0;
+    const float omb1 = radam_omb1(a), omb2 = radam_omb2(a), c1 = radam_c1(a), c2 = radam_c2(a), rt = radam_r_t(a);
+    const float wd = radam_wd(a);
+    const bool decay = wd > 0.f;
+    const bool keep_vhat = ams || new0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      if (act && e0 < D) {
+        float xn[V], mn[V], vn[V], hn[V];
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+          const float mo = sblack ? 0.f : sin[0][k][c], vo = sblack ? 0.f : sin[1][k][c];
+          const float gg = gv[k][c], xo = xin[k][c];
+          mn[c] = a.b1 * mo + gg * omb1;
+          const float mu = nest ? gg * omb1 + a.b1 * mn[c] : mn[c];
+          const float mc = kv_div(mu, c1, fm);
+          vn[c] = a.b2 * vo + (gg * gg) * omb2;
+          float vh = vn[c];
+          hn[c] = 0.f;
+          if (keep_vhat) {
+            const float ho = sblack ? 0.f : sin[2][k][c];
+            // torch.maximum: a NaN on either side comes through
+            hn[c] = !ams ? ho : (vn[c] > ho || vn[c] != vn[c]) ? vn[c] : ho;
+            if (ams) vh = hn[c];
+          }
+          const float vc = kv_sqrt(kv_div(vh, c2, fm), fm);
+          float upd = tract ? kv_div(rt * mc, vc + a.eps, fm) : mc;
+          if (decay) upd = upd + wd * xo;
+          xn[c] = xo - upd * a.lr;
+          big |= fabsf(xn[c]) >= CUTOFF;
+          sbig |= fabsf(mn[c]) >= CUTOFF || fabsf(vn[c]) >= CUTOFF || (keep_vhat && fabsf(hn[c]) >= CUTOFF);
+        }
+        if (!vblack) stv<V>(xrow + e0, xn);
+        if (!sblack) {
+          stv<V>(s0row + e0, mn);
+          stv<V>(s0row + e0 + D, vn);
+          if (keep_vhat) stv<V>(s0row + e0 + 2 * D, hn);
+        }
+      }
+    }
+    const bool anyx = group_any<LPR>(big);
+    bool anys = group_any<LPR>(sbig);
+    // the row ScatterUpdate leaves still holds the vhat block this step did not touch: a row whose m and v are all below
+    // the cutoff (rare: the branch is per group) needs that block for its flag after all
+    if (act && !sblack && !keep_vhat && !anys) {
+      bool hbig = false;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int e0 = (lane + k * LPR) * V;
+        if (e0 < D) {
+          float ho[V];
+          ldv<V>(s0row + e0 + 2 * D, ho);
+#pragma unroll
+          for (int c = 0; c < V; ++c) hbig |= fabsf(ho[c]) >= CUTOFF;
+        }
+      }
+      anys = group_any<LPR>(hbig);
+    }
     if (act && lane == 0) {
       // UpdateUnderThreshold on the rows written (kv_variable.h:706, 837-861); a blacklisted row keeps its flags
       if (!vblack) *fvp = (unsigned char)(anyx ? 0u : FLAG_UNDER);
@@ -878,14 +955,15 @@ __device__ __forceinline__ void opt_update_row(const TableDev& tv, const TableDe
 #pragma unroll
       for (int b3 = 0; b3 < NS0; ++b3)
 #pragma unroll
-        for (int c = 0; c < V; ++c) sin[b3][k][c] = pre->s[b3][k][c];
+        for (int c = 0; c < V; ++c) sin[b3][k][c] = pre->s[b3][k][c];   // (a block the prefetch skipped is not read either)
     } else {
       // (blocks 0..2 as the statements they always were: one unrolled loop over all blocks gives the GroupAdam kernels
       // another register allocation — tools/kres.sh)
       ldslot<V>(s0row, ia0, ib0, new0, e0, sin[0][k]);
       if (NS0 > 1) {
         ldslot<V>(s0row, ia0, ib0, new0, e0 + D, sin[1][k]);
-        if (NS0 > 2) ldslot<V>(s0row, ia0, ib0, new0, e0 + 2 * D, sin[2][k]);   // (Adam's row ends after two blocks)
+        // (Adam's row ends after two blocks; RectifiedAdam's third is read under amsgrad, or for a new row's init value)
+        if (NS0 > 2 && (slot_block_used<OPT>(a, 2) || new0)) ldslot<V>(s0row, ia0, ib0, new0, e0 + 2 * D, sin[2][k]);
       }
 #pragma unroll
       for (int b3 = 3; b3 < NS0; ++b3) ldslot<V>(s0row, ia0, ib0, new0, e0 + b3 * D, sin[b3][k]);

@@ -30,7 +30,15 @@ __device__ __forceinline__ RowsOf resolve_rows(const PartArgs& a, long long key,
   const bool need_vmeta = keeps_var_flags(OPT) || a.tv.enter_threshold != 0u;
   bool vblack = false, sblack = false;
   if (scatter_chain(OPT)) {   // ScatterSub (kv_variable.h:616-734): no filter; a blacklisted row is skipped, not lifted
-    if (!vnew) vblack = (load_freq_flags(a.tv, rv).y & FLAG_BLACK) != 0u;
+    // RectifiedAdam with weight decay: GatherOrInsert on the var comes first (:263-380) — one hit and the day on a row that
+    // was there, blacklisted or not; a row inserted now carries insert_func's word
+    if constexpr (chain_gathers_var(OPT)) {
+      uint2 mv = make_uint2(0u, 0u);
+      if (!vnew) { mv = load_freq_flags(a.tv, rv); vblack = (mv.y & FLAG_BLACK) != 0u; }
+      if (var_gather<OPT>(a.opt)) *freq_ptr(a.tv, rv) = (a.day << 16) | (vnew ? 1u : freq_add_sat(mv.x, 1u));
+    } else if (!vnew) {
+      vblack = (load_freq_flags(a.tv, rv).y & FLAG_BLACK) != 0u;
+    }
   } else if (need_vmeta && !vnew) {
     const uint2 mv = load_freq_flags(a.tv, rv);
     if ((mv.x & 0xFFFFu) < a.tv.enter_threshold) { o.tag = rv | ROW_FILTERED; return o; }  // kv_variable.h:910
@@ -103,7 +111,8 @@ __device__ __forceinline__ void prefetch_state(const PartArgs& a, const uint4& r
       ldv<V>(xr + e0, pre.x[k]);
       if (hok) {
 #pragma unroll
-        for (int b3 = 0; b3 < NS0; ++b3) ldv<V>(sr + e0 + b3 * D, pre.s[b3][k]);
+        for (int b3 = 0; b3 < NS0; ++b3)
+          if (slot_block_used<OPT>(a.opt, b3)) ldv<V>(sr + e0 + b3 * D, pre.s[b3][k]);
       }
     }
   }
@@ -228,6 +237,10 @@ __device__ __forceinline__ bool key_update(const PartArgs& a, const LeanCtx& c, 
   if (scatter_chain(OPT)) {   // no filter; blacklisted rows stay as they are (resolve_rows)
     vblack = ok && !vnew && (vm.y & FLAG_BLACK) != 0u;
     sblack = ok && (mir.z & FLAG_BLACK) != 0u;
+    if constexpr (chain_gathers_var(OPT)) {   // the var's own GatherOrInsert (resolve_rows)
+      if (var_gather<OPT>(a.opt) && ok && lane == 0)
+        c.vmeta[(size_t)row * META_STRIDE].freq = (a.day << 16) | (vnew ? 1u : freq_add_sat(vm.x, 1u));
+    }
   } else if (c.need_vmeta && ok && !vnew) {   // frequency filter / un-blacklisting (resolve_rows; kv_variable.h:910)
     if ((vm.x & 0xFFFFu) < c.thr) act = false;
     else if ((vm.y & FLAG_BLACK) && lane == 0) c.vmeta[(size_t)row * META_STRIDE].flags = FLAG_UNDER;

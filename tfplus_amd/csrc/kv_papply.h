@@ -445,7 +445,8 @@ __device__ __forceinline__ void papply_body(const WsDev& w, const PartArgs& a, c
           for (int k = 0; k < K; ++k) {
             ldv<V>(xr + eo[k], pre.x[k]);
 #pragma unroll
-            for (int b3 = 0; b3 < NS0; ++b3) ldv<V>(sr + b3 * D + eo[k], pre.s[b3][k]);
+            for (int b3 = 0; b3 < NS0; ++b3)
+              if (slot_block_used<OPT>(a.opt, b3)) ldv<V>(sr + b3 * D + eo[k], pre.s[b3][k]);
           }
           hint_loaded = false; have_x = true; have_s = hh != 0u;   // (the general path reads the slot record itself)
         } else {

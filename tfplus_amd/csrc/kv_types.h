@@ -12,7 +12,7 @@ namespace __attribute__((visibility("hidden"))) kvhip_internal {
 enum Mode { MODE_LOOKUP = 0, MODE_APPLY = 1, MODE_DEDUP = 2, MODE_SCATTER = 3, MODE_MARK = 4, MODE_UNIQUE = 5,
             MODE_APPLYIDX = 6 };
 enum Opt { OPT_ADAM_V4 = 0, OPT_ADAM_V3 = 1, OPT_ADAGRAD = 2, OPT_FTRL = 3, OPT_FTRL_V2 = 4, OPT_GROUP_FTRL_V2 = 5,
-           OPT_GROUP_RADAM = 6, OPT_ADAM = 7 };
+           OPT_GROUP_RADAM = 6, OPT_ADAM = 7, OPT_RADAM = 8 };
 // What the pipelines ask of an optimizer, in one place (a new OPT_* must answer each of them):
 // GroupAdam: one slot table of three dim-wide blocks (m | v | z)
 constexpr bool group_adam(int opt) { return opt == OPT_ADAM_V4 || opt == OPT_ADAM_V3; }
@@ -26,9 +26,16 @@ constexpr bool keeps_var_flags(int opt) { return opt == OPT_ADAGRAD || opt == OP
 // has no frequency filter and no CoverUpdate: a blacklisted row stays blacklisted and unwritten, any other row's flags are
 // recomputed from the row written.  A slot row inserted now carries the day stamp (insert_func); a blacklisted one reads
 // as zeros and is left unwritten
-constexpr bool scatter_chain(int opt) { return opt == OPT_ADAM; }
-// dim-wide blocks of the first slot row (group RectifiedAdam: m | v | linear | vhat | vamsgrad; Adam: m | v)
-constexpr int slot0_blocks(int opt) { return opt == OPT_GROUP_RADAM ? 5 : group_adam(opt) ? 3 : opt == OPT_ADAM ? 2 : 1; }
+// (plain RectifiedAdam, python/training/rectified_adam.py:68-96, is the same kind of chain)
+constexpr bool scatter_chain(int opt) { return opt == OPT_ADAM || opt == OPT_RADAM; }
+// ... whose chain, with weight_decay > 0 (a run-time scalar: var_gather() below), also runs one GatherOrInsert on the VAR:
+// its record then gets one hit per distinct id and the day stamp, a row inserted now the word day << 16 | 1
+constexpr bool chain_gathers_var(int opt) { return opt == OPT_RADAM; }
+// dim-wide blocks of the first slot row (group RectifiedAdam: m | v | linear | vhat | vamsgrad; Adam: m | v; RectifiedAdam:
+// m | v | vhat)
+constexpr int slot0_blocks(int opt) {
+  return opt == OPT_GROUP_RADAM ? 5 : (group_adam(opt) || opt == OPT_RADAM) ? 3 : opt == OPT_ADAM ? 2 : 1;
+}
 // one wide slot table whose dim is a multiple of the var's (what the ops' initialisation and shape checks ask)
 constexpr bool wide_slot(int opt) { return slot0_blocks(opt) > 1; }
 // dim-wide blocks of optimizer state a key's update holds besides the var row: the first slot row's (the FTRL family's
@@ -153,7 +160,7 @@ struct WsDev {
 };
 
 // (Fields an optimizer's math has no use for carry that optimizer's own host scalars — the radam_* / adam_* accessors below:
-// read l2s, lr_power and update_slots per optimizer, never for all of them.)
+// read l1, l2, l21, l2s, lr_power, alpha and update_slots per optimizer, never for all of them.)
 struct OptArgs {
   float lr, b1p, b2p, b1, b2, eps, l1, l2, l21, l2s, lr_power;
   float alpha, l21_norm;  // host-precomputed in fp32 exactly as the reference does (group RectifiedAdam: sqrt(1 - beta2_power); Adam: lr_t)
@@ -176,6 +183,26 @@ __host__ __device__ inline float& adam_omb1(OptArgs& a) { return a.l2s; }
 __host__ __device__ inline float adam_omb1(const OptArgs& a) { return a.l2s; }
 __host__ __device__ inline float& adam_omb2(OptArgs& a) { return a.lr_power; }
 __host__ __device__ inline float adam_omb2(const OptArgs& a) { return a.lr_power; }
+// ... and plain RectifiedAdam's (radam_r_t, radam_c1 = 1 - beta1_power and radam_flags as above; lr carries the caller's lr_t):
+// 1 - beta1, 1 - beta2, 1 - beta2_power (host, fp32) and weight_decay
+__host__ __device__ inline float& radam_omb1(OptArgs& a) { return a.l1; }
+__host__ __device__ inline float radam_omb1(const OptArgs& a) { return a.l1; }
+__host__ __device__ inline float& radam_omb2(OptArgs& a) { return a.l2; }
+__host__ __device__ inline float radam_omb2(const OptArgs& a) { return a.l2; }
+__host__ __device__ inline float& radam_c2(OptArgs& a) { return a.alpha; }
+__host__ __device__ inline float radam_c2(const OptArgs& a) { return a.alpha; }
+__host__ __device__ inline float& radam_wd(OptArgs& a) { return a.l21; }
+__host__ __device__ inline float radam_wd(const OptArgs& a) { return a.l21; }
+// The vhat block (2) of RectifiedAdam's slot row takes part under amsgrad only: a wave-uniform test in front of its loads
+// and stores, so that the step without amsgrad moves two slot blocks.  Every other optimizer: all of its blocks, always
+// (the test folds away)
+template <int OPT>
+__host__ __device__ inline bool slot_block_used(const OptArgs& a, int b) {
+  return OPT != OPT_RADAM || b < 2 || (radam_flags(a) & RADAM_AMSGRAD) != 0;
+}
+// the chain of this call gathers the var (chain_gathers_var, weight_decay > 0)
+template <int OPT>
+__host__ __device__ inline bool var_gather(const OptArgs& a) { return chain_gathers_var(OPT) && radam_wd(a) > 0.f; }
 
 // arguments of the index / partition pass and the optimizer apply (kv_kernels.h: partition pass)
 struct PartArgs {

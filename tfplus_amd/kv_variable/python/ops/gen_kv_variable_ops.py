@@ -233,16 +233,24 @@ def _layout_args(stem, per, scalars):
   return args
 
 
-def _hp_array(hp):
+# floats the library reads from hp per optimizer code (kvhip.h kv_shard_apply_serve).  The C ABI takes a bare pointer, so the
+# length is checked here, where it is known: a vector in another family's layout is refused, not read past its end
+_HP_LEN = {0: 9, 1: 9, 2: 2, 3: 6, 4: 5, 5: 5, 6: 13, 7: 6, 8: 11}
+
+
+def _hp_array(hp, optimizer=None):
   """The float vector of hyperparameters the generic entry points take (kvhip.h kv_shard_apply_serve: one layout per
-  optimizer code), each rounded to fp32 once."""
+  optimizer code), each rounded to fp32 once.  (A code the table does not know goes on: the library refuses it unread.)"""
+  need = 0 if optimizer is None else _HP_LEN.get(int(optimizer), 0)
+  if len(hp) < need:
+    raise _lib.InvalidArgumentError("optimizer %d reads %d hyperparameters, hp has %d" % (int(optimizer), need, len(hp)))
   return (ctypes.c_float * len(hp))(*[float(np.float32(x)) for x in hp])
 
 
 # stem of an optimizer family + its scalars (the order of _lib.OPT_FAMILIES) -> the optimizer code and hp vector of the
 # generic entry points (the OPT_* codes below; GroupAdam's trailing scalar is its version)
 _COUNTED_CODE = {"adagrad": 2, "sparse_group_ftrl": 3, "ftrl_v2": 4, "group_ftrl_v2": 5, "group_rectified_adam": 6,
-                 "adam": 7}
+                 "adam": 7, "rectified_adam": 8, "radam": 8}       # ("radam": the short name of OPT_RADAM's family)
 
 
 def _code_and_hp(stem, scalars):
@@ -269,7 +277,7 @@ def _apply_counted(stem, tables, grad, indices, scalars, unique_count):
   g, ids = _grad_ids(var, grad, ids.to(dev).contiguous(), keep_dtype=True)
   code, hp = _code_and_hp(stem, scalars)
   _lib.check(_lib.lib().kv_apply_unique_counted(var.ptr, code, tables[1].ptr, tables[2].ptr if len(tables) > 2 else None,
-                                                _hp_array(hp), _p(g), _p(ids), _TORCH_KEY[ids.dtype], ids.numel(),
+                                                _hp_array(hp, code), _p(g), _p(ids), _TORCH_KEY[ids.dtype], ids.numel(),
                                                 _p(unique_count), _stream(var)))
 
 
@@ -358,6 +366,20 @@ def kv_variable_sparse_apply_adam(var, m_v, grad, indices, lr, beta1_power, beta
   this very tensor left)."""
   _apply("adam", (var, m_v), grad, indices, (lr, beta1_power, beta2_power, beta1, beta2, epsilon), unique_indices, token,
          unique_count)
+
+
+def kv_variable_sparse_apply_rectified_adam(var, opt, grad, indices, lr_t, beta1_power, beta2_power, beta1, beta2, epsilon,
+                                            weight_decay, r_t, tractable, amsgrad, use_nesterov, use_locking=False, name=None,
+                                            unique_indices=False, unique_count=None, token=None):
+  """Plain RectifiedAdam's sparse step as ONE op (kvhip.h kv_apply_rectified_adam).  The reference has no op for it: its
+  RectifiedAdamOptimizer composes gathers, the moment arithmetic, scatter_updates and a scatter_sub
+  (python/training/rectified_adam.py:68-96), and this op leaves what that chain leaves on de-duplicated ids.  `opt` is one
+  slot table of dim 3 x the var's, m | v | vhat (vhat touched under amsgrad only).  lr_t, r_t and tractable are the step's
+  host scalars (RectifiedAdamOptimizer._step_scalars).  The duplicate sum is inside the op.  token: as
+  kv_variable_sparse_apply_adam's."""
+  _apply("rectified_adam", (var, opt), grad, indices,
+         (lr_t, beta1_power, beta2_power, beta1, beta2, epsilon, weight_decay, r_t, tractable, amsgrad, use_nesterov),
+         unique_indices, token, unique_count)
 
 
 def kv_dedup_segment_sum(table_handle, indices, grad, sync=True):
@@ -789,6 +811,15 @@ def kv_multi_sparse_apply_adam(var_handles, m_v_handles, grads, indices, lr, bet
                (lr, beta1_power, beta2_power, beta1, beta2, epsilon), unique_indices)
 
 
+def kv_multi_sparse_apply_rectified_adam(var_handles, opt_handles, grads, indices, lr_t, beta1_power, beta2_power, beta1,
+                                         beta2, epsilon, weight_decay, r_t, tractable, amsgrad, use_nesterov,
+                                         unique_indices=False):
+  """kv_variable_sparse_apply_rectified_adam on many (var, opt) pairs with two kernel launches (one with unique_indices)."""
+  _multi_apply("rectified_adam", "vars, opts, grads and indices", (var_handles, opt_handles), grads, indices,
+               (lr_t, beta1_power, beta2_power, beta1, beta2, epsilon, weight_decay, r_t, tractable, amsgrad, use_nesterov),
+               unique_indices)
+
+
 _COMBINERS = {"sum": _lib.KV_COMBINER_SUM, "mean": _lib.KV_COMBINER_MEAN, "sqrtn": _lib.KV_COMBINER_SQRTN}
 
 
@@ -909,7 +940,7 @@ def kv_variable_apply_sparse(stem, tables, scalars, seg_grad, ids, segment_ids, 
   if g.shape[0] != int(num_segments):
     raise _lib.InvalidArgumentError("seg_grad must have num_segments rows")
   code, hp = _code_and_hp(stem, scalars)
-  _lib.check(_lib.lib().kv_apply_sparse(var.ptr, code, tables[1].ptr, tables[2].ptr if len(tables) > 2 else None, _hp_array(hp),
+  _lib.check(_lib.lib().kv_apply_sparse(var.ptr, code, tables[1].ptr, tables[2].ptr if len(tables) > 2 else None, _hp_array(hp, code),
                                         _p(g), _p(idl), _p(seg), _TORCH_KEY[seg.dtype], _p(w), idl.numel(), int(num_segments),
                                         _COMBINERS[combiner], _stream(var)))
 
@@ -940,7 +971,7 @@ def kv_multi_apply_sparse(stem, tables, scalars, grads, ids, segment_ids, weight
   code, hp = _code_and_hp(stem, scalars)
   handles = [(ctypes.c_void_p * n)(*[h.ptr for h in hs]) for hs in tables]
   _lib.check(_lib.lib().kv_multi_apply_sparse(
-      n, handles[0], code, handles[1], handles[2] if len(handles) > 2 else None, _hp_array(hp), _ptr_array(gr), _ptr_array(idl),
+      n, handles[0], code, handles[1], handles[2] if len(handles) > 2 else None, _hp_array(hp, code), _ptr_array(gr), _ptr_array(idl),
       _ptr_array(seg), segdt, _ptr_array(w), (ctypes.c_int64 * n)(*[i.numel() for i in idl]),
       (ctypes.c_int64 * n)(*[0 if s is None else int(m) for s, m in zip(seg, num_segments)]), _COMBINERS[combiner],
       _stream(vars_[0])))
@@ -1105,6 +1136,8 @@ OPT_FTRL_V2, OPT_GROUP_FTRL_V2 = 4, 5   # hp = lr, l1, l2, l2_shrinkage, lr_powe
 # hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, tractable, amsgrad, use_nesterov (flags 0 / 1)
 OPT_GROUP_RADAM = 6
 OPT_ADAM = 7   # hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon; slots = (m_v,)
+# hp = lr_t, beta1_power, beta2_power, beta1, beta2, epsilon, weight_decay, r_t, tractable, amsgrad, use_nesterov (flags 0 / 1)
+OPT_RADAM = 8  # slots = (opt,): m | v | vhat
 
 
 class KvComm(object):
@@ -1316,7 +1349,7 @@ class KvShard(object):
 
   def apply(self, comm, optimizer, slots, grad, hp, join=True):
     g = _f32(self.table, grad)
-    arr = _hp_array(hp)
+    arr = _hp_array(hp, optimizer)
     s0 = slots[0].ptr
     s1 = slots[1].ptr if len(slots) > 1 else None
     _lib.check(_lib.lib().kv_shard_apply(self.ptr, comm.ptr, int(optimizer), s0, s1, _p(g), arr, int(bool(join)), _stream(self.table)))
@@ -1362,7 +1395,7 @@ class KvShard(object):
     gradients [num_segments, dim] themselves — the values [n, dim] kv_variable_lookup_sparse_grad would expand them into are
     neither written nor read.  Bit for bit that composition in deterministic mode; the same terms per id in the default mode."""
     g, seg, w = self._sparse_grad_args(seg_grad, segment_ids, weights, num_segments, combiner)
-    arr = _hp_array(hp)
+    arr = _hp_array(hp, optimizer)
     s1 = slots[1].ptr if len(slots) > 1 else None
     _lib.check(_lib.lib().kv_shard_apply_sparse(self.ptr, comm.ptr, int(optimizer), slots[0].ptr, s1, _p(g), _p(seg),
                                                 _TORCH_KEY[seg.dtype], _p(w), int(num_segments), _COMBINERS[combiner], arr,
@@ -1418,7 +1451,7 @@ class KvShard(object):
     self._keep_g = (g, seg, w)
 
   def apply_serve(self, optimizer, slots, hp):
-    arr = _hp_array(hp)
+    arr = _hp_array(hp, optimizer)
     s1 = slots[1].ptr if len(slots) > 1 else None
     _lib.check(_lib.lib().kv_shard_apply_serve(self.ptr, int(optimizer), slots[0].ptr, s1, arr, _stream(self.table)))
 
@@ -1512,7 +1545,7 @@ def kv_multi_shard_apply(shards, comm, optimizer, slots_list, grads, hp, join=Tr
   two = all(len(sl) > 1 for sl in slots_list)
   s1 = (ctypes.c_void_p * T)(*[sl[1].ptr for sl in slots_list]) if two else None
   gp = (ctypes.c_void_p * T)(*[_p(g) for g in gs])
-  hpa = _hp_array(hp)
+  hpa = _hp_array(hp, optimizer)
   _lib.check(_lib.lib().kv_multi_shard_apply(arr, T, comm.ptr, int(optimizer), s0, s1, gp, hpa, int(bool(join)), _stream(shards[0].table)))
   for sh, g in zip(shards, gs):
     sh._keep_g = g
@@ -1547,7 +1580,7 @@ def kv_multi_shard_apply_sparse(shards, comm, optimizer, slots_list, grads, segm
   two = all(len(sl) > 1 for sl in slots_list)
   s1 = (ctypes.c_void_p * T)(*[sl[1].ptr for sl in slots_list]) if two else None
   ns = (ctypes.c_int64 * T)(*[0 if s is None else int(m) for s, m in zip(segs, num_segments_list)])
-  hpa = _hp_array(hp)
+  hpa = _hp_array(hp, optimizer)
   _lib.check(_lib.lib().kv_multi_shard_apply_sparse(arr, T, comm.ptr, int(optimizer), s0, s1, _ptr_array(gs), _ptr_array(segs),
                                                     _TORCH_KEY[dts[0] if dts else torch.int64], _ptr_array(ws), ns,
                                                     _COMBINERS[combiner], hpa, int(bool(join)), _stream(shards[0].table)))

@@ -4,7 +4,15 @@ Like the reference it is a composition of the generic ops: gather(m), gather(v) 
 rectification term r_t, optional warm-up / decay of the learning rate, nesterov and weight decay.
 Slots are separate tables "m", "v" (and "vhat") of the variable's dim (the reference inherits
 TF-core Adam's _create_slots); step, beta1_power, beta2_power are fp32 scalars advanced in _finish.
-The IndexedSlices are de-duplicated first, as TF-core does before _resource_apply_sparse."""
+The IndexedSlices are de-duplicated first, as TF-core does before _resource_apply_sparse.
+
+fused=True runs the same step as ONE native op, kv_variable_sparse_apply_rectified_adam (kvhip.h kv_apply_rectified_adam):
+the raw indices and gradient go in, the duplicate sum happens inside, the var's last lookup token is taken as
+AdamOptimizer's op takes it, and _native_step lets fused_backward=True and the sharded wrappers reach it.  _step_scalars
+and _finish are shared.  The STATE LAYOUT DIFFERS: fused=True keeps ONE slot table "m_v_vhat" of dim 3*D
+(num_concat_opt_vars = 3; m | v | vhat, the vhat block untouched without amsgrad) where the composition keeps separate
+"m", "v" (and "vhat") tables of dim D, so checkpoints are NOT interchangeable between the two settings.  The default stays
+the composition."""
 import numpy as np
 import torch
 
@@ -16,13 +24,14 @@ class RectifiedAdamOptimizer(Optimizer):
 
   def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-7, decay=0.0, weight_decay=0.0,
                amsgrad=False, sma_threshold=5.0, total_steps=0, warmup_proportion=0.1, min_lr=0.0,
-               use_locking=False, use_nesterov=False, name="RectifiedAdam"):
+               use_locking=False, use_nesterov=False, name="RectifiedAdam", fused=False):
     super(RectifiedAdamOptimizer, self).__init__(use_locking, name)
     self._lr, self._beta1, self._beta2, self._epsilon = learning_rate, beta1, beta2, epsilon
     self._initial_decay, self._weight_decay = decay, weight_decay
     self._amsgrad, self._sma_threshold = amsgrad, sma_threshold
     self._total_steps, self._warmup_proportion, self._min_lr = float(total_steps), warmup_proportion, min_lr
     self._use_nesterov = use_nesterov
+    self._fused = bool(fused)
     self._step = self._beta1_power = self._beta2_power = None
 
   def _get_beta_accumulators(self):
@@ -35,6 +44,10 @@ class RectifiedAdamOptimizer(Optimizer):
   def _create_slots(self, var_list):
     self._init_accumulators()
     for v in var_list:
+      if self._fused:
+        v.num_concat_opt_vars = 3
+        self._zeros_slot(v, "m_v_vhat", self._name + "_3")
+        continue
       self._zeros_slot(v, "m", self._name + "/m")
       self._zeros_slot(v, "v", self._name + "/v")
       if self._amsgrad:
@@ -65,7 +78,19 @@ class RectifiedAdamOptimizer(Optimizer):
         r_t = f(np.sqrt((sma_t - f(4)) / (sma_inf - f(4)) * (sma_t - f(2)) / (sma_inf - f(2)) * sma_inf / sma_t))
     return lr_t, sma_inf, sma_t, tractable, r_t
 
+  def _native_step(self, var):
+    if not self._fused:
+      return None
+    lr_t, _, _, tractable, r_t = self._step_scalars()
+    return ("rectified_adam", (self.get_slot(var, "m_v_vhat"),),
+            (lr_t, self._beta1_power, self._beta2_power, self._beta1, self._beta2, self._epsilon, self._weight_decay, r_t,
+             bool(tractable), bool(self._amsgrad), bool(self._use_nesterov)))
+
   def _resource_apply_sparse(self, grad, var, indices):
+    if self._fused:
+      _, slots, scalars = self._native_step(var)
+      return gen_kv_variable_ops.kv_variable_sparse_apply_rectified_adam(var.handle, slots[0].handle, grad, indices, *scalars,
+                                                                         use_locking=False)
     f = np.float32
     D = var.embedding_dim
     ids, g, _ = gen_kv_variable_ops.kv_dedup_segment_sum(var.handle, indices, grad.reshape(-1, D))
