@@ -357,7 +357,7 @@ int kv_dedup_segment_sum_dev(kv_handle_t h, const void* ids, const float* grad, 
 /* kv_apply_<optimizer>_unique with the id count taken from the DEVICE: the op is applied to the first
  * min(n_max, *n_dev) ids and gradient rows, *n_dev (int64, device memory — kv_dedup_segment_sum_dev's or kv_unique's
  * num_unique_dev) being read by the kernel when it runs.  `optimizer`, `hp` and `slot1` are kv_shard_apply_serve's
- * codes and layouts (0 .. 8, below).  The same promise of unique ids, the same duplicate guard, checks, results and slot
+ * codes and layouts (0 .. 9, below).  The same promise of unique ids, the same duplicate guard, checks, results and slot
  * mirror handling as the _unique ops: the same bits.  `ids` [n_max] are KV_DT_INT64 or KV_DT_INT32 (ids_dtype) whatever
  * the table's key dtype — the dedup writes int64 ids for every table.  `grad` is [n_max, dim].
  * The host sizes everything by n_max: the tables' capacity (their row bounds advance by n_max per call, so a table
@@ -378,7 +378,7 @@ int kv_apply_unique_counted(kv_handle_t var, int optimizer, kv_handle_t slot0, k
  * those back to sum them per distinct id — writes and reads n * dim * 4 bytes that carry no information; here the tile sums and
  * the partition pass + update fetch a position's row from the segment gradients themselves, through per-position records
  * (segment, scale: 8 bytes a position) that a small pre-pass leaves in the var table's workspace.  The values buffer is never
- * allocated.  `optimizer`, `slot0`, `slot1` and `hp` are kv_shard_apply_serve's codes and layouts (0 .. 8, below), validated as
+ * allocated.  `optimizer`, `slot0`, `slot1` and `hp` are kv_shard_apply_serve's codes and layouts (0 .. 9, below), validated as
  * kv_apply_unique_counted validates them: the hyperparameter checks, their order and their wording are the named ops'.
  *   kv_apply_sparse        seg_grad [num_segments, dim], ids [n] of the table's key dtype, segment_ids [n] int32 or int64,
  *                          weights [n] or NULL: kv_lookup_sparse's arguments of the batch.  n == 0: a no-op, KV_OK.
@@ -759,6 +759,72 @@ int kv_multi_apply_rectified_adam_unique(int num_tables, const kv_handle_t* vars
                                          float weight_decay, float r_t, int tractable, int amsgrad, int use_nesterov,
                                          kv_stream_t stream);
 
+/* Group AMSGrad: KvVariableGroupSparseApplyAMSGrad (kernels/training_ops.cc:1523-1805; row math :1742-1775).  The reference
+ * keeps four slot variables beside the var; here `opt` is ONE slot table of dim 4 x the var's: [m | v | linear | vhat], a
+ * row of zeros at first (the optimizer's slot initialiser).  Per distinct id, g = the id's summed gradient row, every
+ * operation one fp32 rounding, in the reference's order:
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) (g g)
+ *   new_vhat = max(vhat, v / (1 - beta2_power))
+ *   linear = linear + (m / (1 - beta1_power) - ((sqrt(new_vhat) - sqrt(vhat)) / lr) var)
+ *   u = clamp(linear, -l1, l1) - linear;  norm = sqrt(sum u u)
+ *   norm > l21 sqrt(dim):  var = (u (1 - l21 sqrt(dim) / norm)) / ((sqrt(new_vhat) + epsilon) / lr + 2 l2), CoverUpdate
+ *   else:                  the var is blacklisted (MarkBlacklist): it reads as zeros
+ *   vhat = new_vhat;  all four blocks are written on either branch
+ * 1 - beta1_power and 1 - beta2_power are computed once on the host, in fp32.  Bookkeeping as kv_apply_group_rectified_adam:
+ * the var's enter-threshold filter, FindOrInsert on the slot row, CoverUpdate flags of the slot row from all four blocks,
+ * every id marked in both delta lists.
+ * KV_INVALID_ARGUMENT for lr <= 0, negative l1 / l2 / l21, a beta power outside [0, 1), var == opt, an opt dim other than
+ * 4 x the var's ("opt must be 4x") and tables on different devices; KV_FAILED_PRECONDITION for an uninitialised table.
+ * Dims, limits, graph capture, deterministic modes, fast math and delta tracking as kv_apply_group_adam.
+ * _unique / _tok: the forms of kv_apply_group_adam_unique / _tok. */
+int kv_apply_group_amsgrad(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                           float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1, float l2,
+                           float l21, kv_stream_t stream);
+int kv_apply_group_amsgrad_tok(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                               float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1, float l2,
+                               float l21, kv_batch_token_t token, kv_stream_t stream);
+int kv_apply_group_amsgrad_unique(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                                  float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1,
+                                  float l2, float l21, kv_stream_t stream);
+/* ... on many (var, opt) pairs of one dim, shaped like kv_multi_apply_group_rectified_adam[_tok|_unique]. */
+int kv_multi_apply_group_amsgrad(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts, const float* const* grads,
+                                 const void* const* ids, const int64_t* ns, float lr, float beta1_power, float beta2_power,
+                                 float beta1, float beta2, float epsilon, float l1, float l2, float l21, kv_stream_t stream);
+int kv_multi_apply_group_amsgrad_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                     const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                     float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1,
+                                     float l2, float l21, const kv_batch_token_t* tokens, kv_stream_t stream);
+int kv_multi_apply_group_amsgrad_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                        const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                        float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1,
+                                        float l2, float l21, kv_stream_t stream);
+
+/* Group AdaBelief: KvVariableGroupSparseApplyAdaBelief (kernels/training_ops.cc:2982-3251; row math :3189-3222).  The same
+ * kernels as kv_apply_group_amsgrad's, a run-time flag apart; `opt` = [m | v | linear | accum].  Two expressions differ:
+ *   v = beta2 v + (1 - beta2) ((g - m) (g - m)), m being the NEW m (:3190 assigns it before :3192 reads it)
+ *   new_accum = v / (1 - beta2_power): no maximum
+ * Everything else — the linear update, the l1 / l21 tail, bookkeeping, checks, forms — as kv_apply_group_amsgrad. */
+int kv_apply_group_adabelief(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                             float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1, float l2,
+                             float l21, kv_stream_t stream);
+int kv_apply_group_adabelief_tok(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                                 float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1,
+                                 float l2, float l21, kv_batch_token_t token, kv_stream_t stream);
+int kv_apply_group_adabelief_unique(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                                    float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1,
+                                    float l2, float l21, kv_stream_t stream);
+int kv_multi_apply_group_adabelief(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts, const float* const* grads,
+                                   const void* const* ids, const int64_t* ns, float lr, float beta1_power, float beta2_power,
+                                   float beta1, float beta2, float epsilon, float l1, float l2, float l21, kv_stream_t stream);
+int kv_multi_apply_group_adabelief_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                       const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                       float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1,
+                                       float l2, float l21, const kv_batch_token_t* tokens, kv_stream_t stream);
+int kv_multi_apply_group_adabelief_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                          const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                          float beta1_power, float beta2_power, float beta1, float beta2, float epsilon,
+                                          float l1, float l2, float l21, kv_stream_t stream);
+
 
 /* embedding_lookup_sparse on a KvVariable (python/ops/embedding_ops.py:279-441), fused: the
  * reference runs unique_with_counts -> GatherOrInsert[WithCounts] -> gather(idx) -> (x weights) ->
@@ -1007,7 +1073,10 @@ int kv_shard_apply_route(kv_shard_t shard, const float* grad, kv_stream_t stream
  * l21, r_t, tractable, amsgrad, use_nesterov — the three flags as 0 / 1; slot0 = opt, slot1 unused),
  * 7 Adam (kv_apply_adam; hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon; slot0 = m_v, slot1 unused),
  * 8 RectifiedAdam (kv_apply_rectified_adam; hp = lr_t, beta1_power, beta2_power, beta1, beta2, epsilon, weight_decay, r_t,
- * tractable, amsgrad, use_nesterov — the three flags as 0 / 1; slot0 = opt, slot1 unused) */
+ * tractable, amsgrad, use_nesterov — the three flags as 0 / 1; slot0 = opt, slot1 unused),
+ * 9 group AMSGrad / group AdaBelief (kv_apply_group_amsgrad / kv_apply_group_adabelief; hp = lr, beta1_power, beta2_power,
+ * beta1, beta2, epsilon, l1, l2, l21, variant — 0 AMSGrad, 1 AdaBelief, anything else KV_INVALID_ARGUMENT; slot0 = opt,
+ * slot1 unused) */
 int kv_shard_apply_serve(kv_shard_t shard, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp,
                          kv_stream_t stream);
 int kv_shard_lookup(kv_shard_t shard, kv_comm_t comm, const void* ids, int64_t n, float* out, int join,

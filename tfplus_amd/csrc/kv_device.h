@@ -429,14 +429,15 @@ __device__ __forceinline__ bool group_any(bool p) {
 // State rows the caller already holds (requested together with the gradient rows, so the update needs no
 // second round trip): x = the var row; s[0 .. slot0_blocks(OPT)) = the first slot table's row in blocks of dim floats
 // (GroupAdam m | v | z; group RectifiedAdam m | v | linear | vhat | vamsgrad; Adam m | v; RectifiedAdam m | v | vhat;
-// Adagrad / FTRL accum in s[0]).  have_x /
+// group AMSGrad / AdaBelief m | v | linear | acc; Adagrad / FTRL accum in s[0]).  have_x /
 // have_s say which of them are valid.  (s has opt_core's width, state_blocks(OPT): the lean paths hand it over as it is.)
 template <int OPT, int V, int K>
 struct PreRows {
   float x[K][V], s[state_blocks(OPT)][K][V];
 };
 // The row math and the stores of one key's update, on values the caller already holds: xin = the var row;
-// sin = GroupAdam m | v | z, group RectifiedAdam m | v | linear | vhat | vamsgrad, Adam m | v, Adagrad accum, FTRL accum | linear.
+// sin = GroupAdam m | v | z, group RectifiedAdam m | v | linear | vhat | vamsgrad, Adam m | v, Adagrad accum, FTRL accum | linear,
+// group AMSGrad / group AdaBelief m | v | linear | acc.
 // Element e of a row lives at lane
 // (e / V) % LPR, step (e / V) / LPR.  All LPR lanes of every group of the wave call it (shuffles inside); `act`
 // masks groups without an update.  fvp / f0p / f1p = the flag bytes of the var / first / second slot row.
@@ -444,7 +445,8 @@ struct PreRows {
 // only): the var / slot row is blacklisted — it reads as zeros where it is read and is left as it is.
 // Restates the per-id body of KvVariableGroupSparseApplyAdamV4Op / V3Op / SparseApplyAdagradOp /
 // SparseGroupSparseApplyFtrlOp / SparseApplyFtrlOp / GroupSparseApplyFtrlOp / GroupSparseApplyRectifiedAdamOp
-// (training_ops.cc:7142-7197, 5871-5927, 1455-1486, 684-763, 457-484, 977-1019, 6883-6936) and, for Adam, the row
+// / GroupSparseApplyAMSGradOp / GroupSparseApplyAdaBeliefOp
+// (training_ops.cc:7142-7197, 5871-5927, 1455-1486, 684-763, 457-484, 977-1019, 6883-6936, 1742-1775, 3189-3222) and, for Adam, the row
 // arithmetic of the reference's Python compositions (python/training/adam.py:93-163, rectified_adam.py:76-96).
 template <int OPT, int V, int LPR, int K>
 __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row, unsigned char* fvp, unsigned char* f0p,
@@ -452,7 +454,7 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
                                          const OptArgs& a, int lane, const float (&xin)[K][V],
                                          const float (&sin)[state_blocks(OPT)][K][V], bool new1 = false, bool vblack = false,
                                          bool sblack = false) {
-  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_RADAM, "opt_core: unknown optimizer");
+  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_GROUP_ADAM4, "opt_core: unknown optimizer");
   if (group_adam(OPT)) {
     // training_ops.cc:7166-7195 (V4) / :5895-5925 (V3); slot row = [m | v | z]
     float m[K][V], nv[K][V], sq[K][V], z[K][V], uu[K][V];
@@ -792,6 +794,76 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
     const bool anyx = group_any<LPR>(big), anys = group_any<LPR>(sbig);
     if (act && lane == 0) {
       // CoverUpdateUnsafe -> UpdateUnderThreshold, or MarkBlacklistUnsafe (:6923-6936)
+      *fvp = (unsigned char)(upd ? (anyx ? 0u : FLAG_UNDER) : (FLAG_BLACK | FLAG_UNDER));
+      *f0p = (unsigned char)(anys ? 0u : FLAG_UNDER);
+    }
+  } else if (OPT == OPT_GROUP_ADAM4) {
+    // OPT_GROUP_ADAM4: KvVariableGroupSparseApplyAMSGrad (training_ops.cc:1742-1775) and ...AdaBelief (:3189-3222), one
+    // family: slot row = [m | v | linear | acc], acc = vhat / accum.  They differ in two expressions, both behind the
+    // wave-uniform ga4_variant(a): what v's second term squares (g, or g - m with m already assigned) and whether acc takes
+    // the maximum with its old value.  ga4_c1 / ga4_c2 = 1 - beta1_power / 1 - beta2_power (host, fp32).
+    // Two passes around the row norm.  None of the four slot blocks depends on the norm (the reference writes them on both
+    // branches), so the first pass stores them as it forms them and only the var's numerator and denominator, u and y,
+    // stay in registers across the group_sum: 2 K V values where group RectifiedAdam holds 6 K V
+    float uu[K][V], yy[K][V];
+    float part = 0.f;
+    const float omb1 = 1.f - a.b1, omb2 = 1.f - a.b2, c1 = ga4_c1(a), c2 = ga4_c2(a);
+    const float two_l2 = 2.f * a.l2;
+    const bool fm = KV_FASTM(a);
+    const bool belief = ga4_variant(a) == GA4_ADABELIEF;
+    bool big = false, sbig = false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      const bool valid = act && e0 < D;
+      float mn[V], vn[V], zn[V], an[V];
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        const float xo = valid ? xin[k][c] : 0.f, mo = valid ? sin[0][k][c] : 0.f, vo = valid ? sin[1][k][c] : 0.f;
+        const float zo = valid ? sin[2][k][c] : 0.f, ao = valid ? sin[3][k][c] : 0.f;
+        const float gg = gv[k][c];
+        mn[c] = a.b1 * mo + omb1 * gg;
+        const float d = belief ? gg - mn[c] : gg;
+        vn[c] = a.b2 * vo + omb2 * (d * d);
+        const float vc = kv_div(vn[c], c2, fm);
+        an[c] = belief ? vc : fmaxf(ao, vc);
+        const float sq = kv_sqrt(an[c], fm);
+        zn[c] = zo + (kv_div(mn[c], c1, fm) - kv_div(sq - kv_sqrt(ao, fm), a.lr, fm) * xo);
+        const float adj = fmaxf(fminf(zn[c], a.l1), -a.l1);
+        uu[k][c] = adj - zn[c];
+        yy[k][c] = kv_div(sq + a.eps, a.lr, fm) + two_l2;
+        if (valid) {   // (a masked lane adds nothing)
+          part += uu[k][c] * uu[k][c];
+          sbig |= fabsf(mn[c]) >= CUTOFF || fabsf(vn[c]) >= CUTOFF || fabsf(zn[c]) >= CUTOFF || fabsf(an[c]) >= CUTOFF;
+        }
+      }
+      if (valid) {
+        stv<V>(s0row + e0, mn);
+        stv<V>(s0row + e0 + D, vn);
+        stv<V>(s0row + e0 + 2 * D, zn);
+        stv<V>(s0row + e0 + 3 * D, an);
+      }
+    }
+    const float norm = kv_sqrt(group_sum<LPR>(part), fm);
+    const bool upd = norm > a.l21_norm;
+    const float scale = 1.f - kv_div(a.l21_norm, norm, fm);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      if (act && e0 < D) {
+        float xn[V];
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+          xn[c] = 0.f;  // blacklist: the row reads as zeros (table_manager.h:335-357)
+          if (upd) xn[c] = kv_div(uu[k][c] * scale, yy[k][c], fm);
+          big |= fabsf(xn[c]) >= CUTOFF;
+        }
+        stv<V>(xrow + e0, xn);
+      }
+    }
+    const bool anyx = group_any<LPR>(big), anys = group_any<LPR>(sbig);
+    if (act && lane == 0) {
+      // CoverUpdateUnsafe -> UpdateUnderThreshold, or MarkBlacklistUnsafe (:1755-1766 / :3202-3213)
       *fvp = (unsigned char)(upd ? (anyx ? 0u : FLAG_UNDER) : (FLAG_BLACK | FLAG_UNDER));
       *f0p = (unsigned char)(anys ? 0u : FLAG_UNDER);
     }

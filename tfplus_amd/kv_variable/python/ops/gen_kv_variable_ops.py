@@ -235,7 +235,7 @@ def _layout_args(stem, per, scalars):
 
 # floats the library reads from hp per optimizer code (kvhip.h kv_shard_apply_serve).  The C ABI takes a bare pointer, so the
 # length is checked here, where it is known: a vector in another family's layout is refused, not read past its end
-_HP_LEN = {0: 9, 1: 9, 2: 2, 3: 6, 4: 5, 5: 5, 6: 13, 7: 6, 8: 11}
+_HP_LEN = {0: 9, 1: 9, 2: 2, 3: 6, 4: 5, 5: 5, 6: 13, 7: 6, 8: 11, 9: 10}
 
 
 def _hp_array(hp, optimizer=None):
@@ -251,6 +251,8 @@ def _hp_array(hp, optimizer=None):
 # generic entry points (the OPT_* codes below; GroupAdam's trailing scalar is its version)
 _COUNTED_CODE = {"adagrad": 2, "sparse_group_ftrl": 3, "ftrl_v2": 4, "group_ftrl_v2": 5, "group_rectified_adam": 6,
                  "adam": 7, "rectified_adam": 8, "radam": 8}       # ("radam": the short name of OPT_RADAM's family)
+# OPT_GROUP_ADAM4's two stems share code 9: the stem becomes the variant, the last float of hp
+_GROUP_ADAM4_VARIANT = {"group_amsgrad": 0, "group_adabelief": 1}
 
 
 def _code_and_hp(stem, scalars):
@@ -259,6 +261,8 @@ def _code_and_hp(stem, scalars):
     if int(scalars[-1]) not in (3, 4):
       raise _lib.InvalidArgumentError("GroupAdam version %d: 3 or 4" % int(scalars[-1]))
     return (0 if int(scalars[-1]) == 4 else 1), sc[:-1]
+  if stem in _GROUP_ADAM4_VARIANT:
+    return 9, sc + [float(_GROUP_ADAM4_VARIANT[stem])]
   return _COUNTED_CODE[stem], sc
 
 
@@ -355,6 +359,25 @@ def kv_variable_group_sparse_apply_rectified_adam(var, opt, grad, indices, lr, b
   _apply("group_rectified_adam", (var, opt), grad, indices,
          (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, r_t, bool(tractable), bool(amsgrad),
           bool(use_nesterov)), unique_indices, token, unique_count)
+
+
+def kv_variable_group_sparse_apply_amsgrad(var, opt, grad, indices, lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1,
+                                           l2, l21, use_locking=False, name=None, unique_indices=False, token=None,
+                                           unique_count=None):
+  """REGISTER_OP("KvVariableGroupSparseApplyAMSGrad") (kernels/training_ops.cc:1523-1805): the reference's four slot
+  variables are ONE slot table `opt` of dim 4 x the var's, m | v | linear | vhat (kvhip.h kv_apply_group_amsgrad).  token:
+  as kv_variable_group_sparse_apply_rectified_adam's."""
+  _apply("group_amsgrad", (var, opt), grad, indices, (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21),
+         unique_indices, token, unique_count)
+
+
+def kv_variable_group_sparse_apply_adabelief(var, opt, grad, indices, lr, beta1_power, beta2_power, beta1, beta2, epsilon,
+                                             l1, l2, l21, use_locking=False, name=None, unique_indices=False, token=None,
+                                             unique_count=None):
+  """REGISTER_OP("KvVariableGroupSparseApplyAdaBelief") (kernels/training_ops.cc:2982-3251): `opt` is one slot table of dim
+  4 x the var's, m | v | linear | accum (kvhip.h kv_apply_group_adabelief: group AMSGrad's kernels, a run-time flag apart)."""
+  _apply("group_adabelief", (var, opt), grad, indices, (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21),
+         unique_indices, token, unique_count)
 
 
 def kv_variable_sparse_apply_adam(var, m_v, grad, indices, lr, beta1_power, beta2_power, beta1, beta2, epsilon,
@@ -804,6 +827,20 @@ def kv_multi_group_sparse_apply_rectified_adam(var_handles, opt_handles, grads, 
                 bool(use_nesterov)), unique_indices)
 
 
+def kv_multi_group_sparse_apply_amsgrad(var_handles, opt_handles, grads, indices, lr, beta1_power, beta2_power, beta1, beta2,
+                                        epsilon, l1, l2, l21, unique_indices=False):
+  """KvVariableGroupSparseApplyAMSGrad on many (var, opt) pairs with two kernel launches (one with unique_indices)."""
+  _multi_apply("group_amsgrad", "vars, opts, grads and indices", (var_handles, opt_handles), grads, indices,
+               (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21), unique_indices)
+
+
+def kv_multi_group_sparse_apply_adabelief(var_handles, opt_handles, grads, indices, lr, beta1_power, beta2_power, beta1,
+                                          beta2, epsilon, l1, l2, l21, unique_indices=False):
+  """KvVariableGroupSparseApplyAdaBelief on many (var, opt) pairs with two kernel launches (one with unique_indices)."""
+  _multi_apply("group_adabelief", "vars, opts, grads and indices", (var_handles, opt_handles), grads, indices,
+               (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21), unique_indices)
+
+
 def kv_multi_sparse_apply_adam(var_handles, m_v_handles, grads, indices, lr, beta1_power, beta2_power, beta1, beta2,
                                epsilon, unique_indices=False):
   """kv_variable_sparse_apply_adam on many (var, m_v) pairs with two kernel launches (one with unique_indices)."""
@@ -1138,6 +1175,9 @@ OPT_GROUP_RADAM = 6
 OPT_ADAM = 7   # hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon; slots = (m_v,)
 # hp = lr_t, beta1_power, beta2_power, beta1, beta2, epsilon, weight_decay, r_t, tractable, amsgrad, use_nesterov (flags 0 / 1)
 OPT_RADAM = 8  # slots = (opt,): m | v | vhat
+# group AMSGrad / group AdaBelief: hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, variant (0 AMSGrad,
+# 1 AdaBelief); slots = (opt,): m | v | linear | acc
+OPT_GROUP_ADAM4 = 9
 
 
 class KvComm(object):
