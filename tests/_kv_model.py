@@ -6,7 +6,9 @@ restate: what a whole random program is carried with, without asking the device 
   apply_step     the bookkeeping of one step of ftrl_v2 / group_ftrl_v2 / group_radam / adam on unique ids and their summed
                  gradient rows, stated ONCE: the enter-threshold filter, which slot rows are created or hit, when a var is
                  blacklisted or lifted, which under_threshold flags are recomputed.  The row arithmetic is that of
-                 tests/_ftrl_ref.py, tests/_radam_ref.py and tests/_adam_ref.py, called on all of a step's rows at once;
+                 tests/_ftrl_ref.py, tests/_radam_ref.py and tests/_adam_ref.py, called on all of a step's rows at once
+                 (also group_amsgrad / group_adabelief, GROUP_ADAM4 below: group RAdam's bookkeeping on the row math of
+                 tests/_group_adam4_ref.py, for the row-geometry matrix; no random program runs them);
   Program        the random-program generator shared by tests/test_kv_model.py (conditions, on the model alone) and
                  tests/test_gpu_fuzz_optimizers.py (the same programs side by side with the GPU tables).
 
@@ -25,6 +27,7 @@ scatter_update op 0 and blacklisting put exact values: the allowance goes back t
 import numpy as np
 
 import _ftrl_ref as RF
+import _group_adam4_ref as R4
 import _radam_ref as RR
 
 F = np.float32
@@ -217,10 +220,15 @@ class Table(object):
 FAMILIES = ("ftrl_v2", "group_ftrl_v2", "group_radam", "adam")
 FTRL_BAR = (1e-5, 1e-7)          # tests/test_gpu_ftrl_v2.py test_parity_unique_ids, the group op at lr_power -0.5
 RADAM_BAR = (1e-6, 1e-9)         # tests/test_gpu_group_radam.py _lasso_tol: RTOL / scale of the value + 1e-9
+# Group AMSGrad / group AdaBelief (kvhip.h kv_apply_group_amsgrad: group RAdam's bookkeeping, the row math of
+# tests/_group_adam4_ref.py): apply_step takes the two names -> the restatement's variant.  They are in no random program
+# (FAMILIES, SEEDS, Program) and carry no allowance: bar=True is not for them.
+GROUP_ADAM4 = {"group_amsgrad": "amsgrad", "group_adabelief": "adabelief"}
 
 
 def slot_dims(family, D):
-  return {"ftrl_v2": [D, D], "group_ftrl_v2": [D, D], "group_radam": [5 * D], "adam": [2 * D]}[family]
+  return {"ftrl_v2": [D, D], "group_ftrl_v2": [D, D], "group_radam": [5 * D], "adam": [2 * D], "group_amsgrad": [4 * D],
+          "group_adabelief": [4 * D]}[family]
 
 
 def linear_norms(family, x, srows, g, hp):
@@ -231,6 +239,11 @@ def linear_norms(family, x, srows, g, hp):
     z1 = RF._linear(x, srows[0], srows[1], g, lr, two_l2s, lrp)[1].astype(F)
     return np.sqrt((z1.astype(np.float64) ** 2).sum(axis=1)), z1
   D = x.shape[1]
+  if family in GROUP_ADAM4:      # |clamp(linear', -l1, l1) - linear'|_2, as group RAdam's
+    z1 = R4.step(GROUP_ADAM4[family], x, srows[0], g, hp, F)[1][:, 2 * D:3 * D].astype(F)
+    z64, l1 = z1.astype(np.float64), float(F(hp[6]))
+    u = np.clip(z64, -l1, l1) - z64
+    return np.sqrt((u * u).sum(axis=1)), z1
   z1 = RR.group_radam(x, srows[0], g, *hp)[1][:, 2 * D:3 * D]
   return RR.row_norms(x, srows[0], g, *hp), z1
 
@@ -300,7 +313,7 @@ def resolve_step(family, var, slots, uniq_ids, summed_grad):
   """The first half of a step, which does not depend on the op's scalars: the filter, the lifting, the slot rows created or
   hit (apply_step's docstring).  -> the context finish_step takes; ctx["x"], ctx["srows"], ctx["g"] are the rows the step
   starts from (the keys that pass the filter, in the order of uniq_ids)."""
-  assert family in FAMILIES
+  assert family in FAMILIES or family in GROUP_ADAM4
   D = var.dim
   uniq = [int(k) for k in np.asarray(uniq_ids).reshape(-1)]
   g_all = np.asarray(summed_grad, F).reshape(len(uniq), D)
@@ -372,6 +385,12 @@ def finish_step(family, var, slots, ctx, hp, bar=False):
     x1, a1, z1, upd = RF.group_ftrl_v2(x, srows[0], srows[1], g, *hp)
     new = [x1, a1, z1]
     thr = float(F(hp[1]))
+  elif family in GROUP_ADAM4:
+    assert not bar, "step_allowance does not know %s" % family
+    x1, s1, upd, _ = R4.step(GROUP_ADAM4[family], x, srows[0], g, hp, F)
+    new = [x1.astype(F), s1.astype(F)]
+    x1 = new[0]
+    thr = float(F(hp[8])) * float(np.sqrt(F(D)))
   else:
     x1, s1, upd = RR.group_radam(x, srows[0], g, *hp)
     new = [x1, s1]

@@ -11,6 +11,11 @@ gates the update, and every output is the kernel's bit for bit.
 
 Rows are [U, D] float32 arrays: x = var, g = the summed gradient rows; the slot row is [U, 5 D] = m | v | linear | vhat |
 vamsgrad.
+
+  radam_ref, chain  PLAIN RectifiedAdam, which the reference has no kernel for: the arithmetic of the chain its
+                    RectifiedAdamOptimizer composes (python/training/rectified_adam.py:76-96), and one step of that chain
+                    on the table models of tests/_kv_model.py: the yardstick of tests/test_gpu_radam.py and of the
+                    row-geometry matrix (tests/_row_geometry.py).
 """
 import numpy as np
 
@@ -117,3 +122,40 @@ def composite_step_tolerance(x, x_new, rv, vhat):
   x, so an earlier difference is carried, not amplified."""
   x, x_new, rv, vhat = (np.asarray(t, np.float64) for t in (x, x_new, rv, vhat))
   return COMPOSITE_ROUNDINGS * 2.0 ** -24 * (np.maximum(rv, vhat) * np.abs(x) / rv + np.abs(x_new - x))
+
+
+# ---- plain RectifiedAdam (kvhip.h kv_apply_rectified_adam) -------------------------------------------------------------------
+# lr_t, beta1_power, beta2_power, beta1, beta2, epsilon, weight_decay, r_t, tractable, amsgrad, use_nesterov
+HP = (0.05, 0.81, 0.998, 0.9, 0.999, 1e-7, 0.01, 0.4, 1, 1, 1)
+
+
+def radam_ref(x, s, g, hp, dt):
+  """rectified_adam.py:76-96 on rows (x var, read for the decay term only; s slot = m | v | vhat; g the summed gradient), every
+  operation one rounding of dtype dt, the scalars the caller's float32 values.  -> (what scatter_sub takes off the var, slot rows)"""
+  lr_t, b1p, b2p, b1, b2, eps, wd, r_t, tract, ams, nest = [dt(F(v)) for v in hp]
+  D, one = g.shape[1], dt(1)
+  omb1, omb2, c1, c2 = one - b1, one - b2, one - b1p, one - b2p
+  x, g, m, v, h = [a.astype(dt) for a in (x, g, s[:, :D], s[:, D:2 * D], s[:, 2 * D:])]
+  with np.errstate(all="ignore"):
+    m1 = b1 * m + g * omb1
+    mu = g * omb1 + b1 * m1 if nest else m1
+    mc = mu / c1
+    v1 = b2 * v + (g * g) * omb2
+    h1 = np.maximum(v1, h) if ams else h
+    vc = np.sqrt((h1 if ams else v1) / c2)
+    upd = (r_t * mc) / (vc + eps) if tract else mc
+    if wd > 0:
+      upd = upd + wd * x
+    return upd * lr_t, np.concatenate([m1, v1, h1], axis=1)
+
+
+def chain(var, slot, ids, g, hp):
+  """One float32 step of the reference's chain on the models.  -> the (var, slot) rows it started from, their float64 step's"""
+  x0, s0 = [np.stack([t.rows[k].row if k in t.rows else t.init_row(k) for k in ids.tolist()]) for t in (var, slot)]
+  sg = slot.gather_or_insert(ids)                                 # (a blacklisted row: zeros)
+  xg = var.gather_or_insert(ids) if hp[6] > 0 else x0
+  step, s1 = radam_ref(xg, sg, g, hp, F)
+  slot.scatter_update(ids, s1, 0)
+  var.scatter_update(ids, step, 2)
+  step64, s64 = radam_ref(xg, sg, g, hp, np.float64)
+  return x0, s0, x0 - step64, s64

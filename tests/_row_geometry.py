@@ -175,9 +175,22 @@ def draw_grads(rng, batch, D, scale=1e-2):
 # The var of a group step is held against the same step in float64 from the reference's float32 inputs, within
 # max(bar, 4 x the float32 reference's own distance from that float64 result): the reference and the kernel are two float32
 # orders of one D-term sum.
+#
+# NEW_FAMILIES, on tests/_kv_model.py tables.  radam: the float32 chain of tests/_radam_ref.py, whose bits the rows must hold
+# (repeated ids carry gradients every order sums exactly), steps with RADAM_FLAGS.  group_amsgrad / group_adabelief: the row
+# math of tests/_group_adam4_ref.py with group RAdam's bookkeeping (_kv_model.GROUP_ADAM4), l1 = 1e-3, l2 = 0.01, epsilon =
+# 1e-7, lr = 0.05, l21 from lasso_threshold; var AND slot rows against the float64 step at tests/test_gpu_group_adam4.py's bar.
 FAMILIES = ("group_adam_v4", "group_adam_v3", "adagrad", "sparse_group_ftrl", "ftrl_v2", "group_ftrl_v2", "group_radam", "adam")
 ORACLE_FAMILIES = FAMILIES[:4]
-GROUP_FAMILIES = ("group_adam_v4", "group_adam_v3", "sparse_group_ftrl", "group_ftrl_v2", "group_radam")
+# FAMILIES stays as it is: tests/_capture_cases.py, tests/test_gpu_capture_replay.py and tests/test_gpu_apply_sparse.py build
+# their cases from it and seed generators with its indices.  The later families stand beside it.
+NEW_FAMILIES = ("radam", "group_amsgrad", "group_adabelief")
+ALL_FAMILIES = FAMILIES + NEW_FAMILIES
+ADAM4_FAMILIES = NEW_FAMILIES[1:]                 # optimizer code 9: one kernel family, a run-time variant flag
+GROUP_FAMILIES = ("group_adam_v4", "group_adam_v3", "sparse_group_ftrl", "group_ftrl_v2", "group_radam") + ADAM4_FAMILIES
+# families whose step reads the var through a coefficient that differences two square roots: the rows are set to the
+# reference's bits between two steps (tests/test_gpu_row_geometry.py _align)
+ALIGNED_FAMILIES = ("group_adam_v4", "group_adam_v3") + ADAM4_FAMILIES
 OPT_SEED = SEEDS[0]
 STEPS = 3
 DAY = 20000
@@ -187,12 +200,19 @@ SKIP_BELOW = 1e-4               # rows whose scale lies this close to the thresh
 # (atol of the var, atol of each slot table): tests/test_gpu_parity.py for the oracle's families, test_gpu_ftrl_v2.py
 # _check, test_gpu_adam.py _assert_twins
 ATOL = {"group_adam_v4": (1e-9, [1e-10]), "group_adam_v3": (1e-9, [1e-10]), "adagrad": (1e-9, [0.0]),
-        "sparse_group_ftrl": (1e-8, [0.0, 1e-8]), "ftrl_v2": (1e-9, [1e-9, 1e-9]), "adam": (1e-9, [1e-9])}
+        "sparse_group_ftrl": (1e-8, [0.0, 1e-8]), "ftrl_v2": (1e-9, [1e-9, 1e-9]), "adam": (1e-9, [1e-9]),
+        # radam: the float32 chain's bits (tests/test_gpu_radam.py test_unique_ids), so no tolerance at all; code 9:
+        # tests/test_gpu_group_adam4.py _bar, against the float64 step, the var and all four slot blocks
+        "radam": (0.0, [0.0]), "group_amsgrad": (1e-7, [1e-7]), "group_adabelief": (1e-7, [1e-7])}
+# radam's steps: (weight_decay, tractable, amsgrad, use_nesterov) — every flag both ways, the var-record hit that only
+# weight decay causes on and off
+RADAM_FLAGS = [(0.0, 0, 0, 0), (0.01, 1, 0, 1), (0.01, 1, 1, 0)]
 
 
 def slot_dims(family, D):
   return {"group_adam_v4": [3 * D], "group_adam_v3": [3 * D], "adagrad": [D], "sparse_group_ftrl": [D, D], "ftrl_v2": [D, D],
-          "group_ftrl_v2": [D, D], "group_radam": [5 * D], "adam": [2 * D]}[family]
+          "group_ftrl_v2": [D, D], "group_radam": [5 * D], "adam": [2 * D], "radam": [3 * D], "group_amsgrad": [4 * D],
+          "group_adabelief": [4 * D]}[family]
 
 
 def beta_pows(t):
@@ -208,6 +228,9 @@ def inits(family, D, rng):
     v = rng.uniform(0.5, 1.0, (32, D)) * 0.05
     v[::2] *= 1e-3
     v = v.astype(F)
+  elif family in NEW_FAMILIES:      # tests/test_gpu_radam.py, tests/test_gpu_group_adam4.py: uniform rows; radam's slot 1e-4
+    v = rng.uniform(-0.5, 0.5, (64 if family == "radam" else 32, D)).astype(F)
+    return v, [np.full((16 if family == "radam" else 4, d), 1e-4 if family == "radam" else 0.0, F) for d in slot_dims(family, D)]
   else:
     v = (rng.standard_normal((32, D)) * 0.1).astype(F)
   const = {"adagrad": [0.1], "sparse_group_ftrl": [0.1, 0.0], "ftrl_v2": [0.1, 0.0], "group_ftrl_v2": [0.1, 0.0]}.get(family, [0.0])
@@ -357,12 +380,14 @@ def trajectory(family, D, seed=OPT_SEED):
   Cached: every apply form of a (family, dim) runs the same trajectory."""
   key = (family, int(D), int(seed))
   if key not in _CACHE:
-    _CACHE[key] = _oracle_trajectory(*key) if family in ORACLE_FAMILIES else _model_trajectory(*key)
+    fn = _oracle_trajectory if family in ORACLE_FAMILIES else _radam_trajectory if family == "radam" else \
+        _adam4_trajectory if family in ADAM4_FAMILIES else _model_trajectory
+    _CACHE[key] = fn(*key)
   return _CACHE[key]
 
 
 def _setup(family, D, seed):
-  rng = np.random.default_rng([seed, D, FAMILIES.index(family)])
+  rng = np.random.default_rng([seed, D, ALL_FAMILIES.index(family)])
   batch = draw_batch(np.random.default_rng(seed))
   vinit, sinits = inits(family, D, rng)
   grads = [step_grads(rng, batch, D) for _ in range(STEPS)]
@@ -524,3 +549,124 @@ def _model_trajectory(family, D, seed):
                   "tables": [{"rows": rows[j].copy(), "rows32": new[j].astype(np.float64), "tol": np.array(tol[j], np.float64),
                               "metas": side.metas(j, keys), "counters": side.counters(j)} for j in range(len(side.tables))]})
   return {"batch": batch, "vinit": vinit, "sinits": sinits, "steps": steps}
+
+
+def _radam_trajectory(family, D, seed):
+  """Plain RectifiedAdam: the float32 chain of tests/_radam_ref.py on the table models, bit for bit (tol 0, rows = rows32).
+  Beyond the common record: per step "pre_metas" (the var's records after the step's lookup, before the step), per table
+  "rows64" (the chain's float64 step from the float32 inputs); "f64_dist", the largest |float32 - float64| over the steps'
+  var and slot rows: what the GPU test doubles (tests/test_gpu_radam.py F64_BOUND's rule)."""
+  import _radam_ref as RR
+  rng, batch, vinit, sinits, grads = _setup(family, D, seed)
+  keys, ids = batch["keys"], batch["ids"]
+  side = _ModelSide(family, D, seed, vinit, sinits)
+  var, slot = side.tables
+  side.lookup(batch["pre"])
+  nk = keys.size
+  steps, dist = [], 0.0
+  for t in range(STEPS):
+    side.lookup(ids)
+    pre_metas = side.metas(0, keys)
+    u, s = _dedup(ids, grads[t])
+    at = np.array([int(np.flatnonzero(u == k)[0]) for k in keys])
+    b1p, b2p = beta_pows(t)
+    hp = (0.05, b1p, b2p, 0.9, 0.999, 1e-7) + RADAM_FLAGS[t][:1] + (0.4,) + RADAM_FLAGS[t][1:]
+    w64 = [w[at] for w in RR.chain(var, slot, u, s, hp)[2:]]
+    new = [side.rows(j, keys) for j in range(2)]
+    dist = max([dist] + [float(np.abs(a.astype(np.float64) - b).max()) for a, b in zip(new, w64)])
+    steps.append({"ids": ids, "grad": grads[t], "u": u, "s": s, "hp": hp, "clear": np.ones(nk, bool), "widen": np.ones((nk, 1)),
+                  "ref_err": 0.0, "black": np.zeros(nk, bool), "live": np.ones(nk, bool), "zeros": None, "pre_metas": pre_metas,
+                  "tables": [{"rows": new[j].astype(np.float64), "rows32": new[j].astype(np.float64), "rows64": w64[j],
+                              "tol": np.zeros(new[j].shape), "metas": side.metas(j, keys), "counters": side.counters(j)}
+                             for j in range(2)]})
+  return {"batch": batch, "vinit": vinit, "sinits": sinits, "steps": steps, "f64_dist": dist}
+
+
+def _adam4_trajectory(family, D, seed):
+  """Group AMSGrad / group AdaBelief: the float32 restatement of tests/_group_adam4_ref.py with tests/_kv_model.py's
+  bookkeeping carries the state; every step's var AND slot rows are held against the float64 step from the float32 inputs at
+  tests/test_gpu_group_adam4.py's bar (rtol 1e-6, the var's over scale; atol 1e-7).  l21: _kv_model.lasso_threshold on the
+  step's own row norms.  Per step also "slot_err": the float32 restatement's distance on the slot rows, in units of the bar."""
+  import _group_adam4_ref as R4
+  import _kv_model as M
+  rng, batch, vinit, sinits, grads = _setup(family, D, seed)
+  keys, ids = batch["keys"], batch["ids"]
+  side = _ModelSide(family, D, seed, vinit, sinits)
+  var, slots = side.tables[0], side.tables[1:]
+  side.lookup(batch["pre"])
+  nk = keys.size
+  pos = {int(k): i for i, k in enumerate(keys.tolist())}
+  rows = [side.rows(j, keys).astype(np.float64) for j in range(2)]
+  tol = [np.zeros_like(r) for r in rows]
+  clear = np.ones(nk, bool)
+  av, aslots = ATOL[family]
+  steps = []
+  for t in range(STEPS):
+    side.lookup(ids)
+    u, s = _dedup(ids, grads[t])
+    b1p, b2p = beta_pows(t)
+    seen = {}
+
+    def hp_fn(x, srows, g):
+      hp0 = (0.05, b1p, b2p, 0.9, 0.999, 1e-7, 1e-3, 0.01, 0.0)
+      seen.update(x=x, s=srows[0], g=g)
+      return hp0[:8] + (M.lasso_threshold(M.linear_norms(family, x, srows, g, hp0)[0], rng) / float(np.sqrt(D)),)
+
+    res = M.apply_step(family, var, slots, u, s, hp_fn)
+    hp = res["hp"]
+    li = np.array([pos[k] for k in res["keys"]], np.int64)
+    live = np.zeros(nk, bool)
+    live[li] = True
+    new = [side.rows(j, keys) for j in range(2)]
+    with np.errstate(all="ignore"):
+      scale = 1.0 - 1.0 / res["ratio"]
+    c = np.abs(scale) > SKIP_BELOW
+    clear[li] &= c
+    black = np.zeros(nk, bool)
+    black[li] = ~res["updated"]
+    x64, s64, upd, _ = R4.step(M.GROUP_ADAM4[family], seen["x"], seen["s"], seen["g"], hp)
+    assert np.array_equal(upd[c], res["updated"][c]), (family, D, t)
+    bar = RTOL / np.maximum(scale, SKIP_BELOW)[:, None] * np.abs(x64) + av
+    sbar = RTOL * np.abs(s64) + aslots[0]
+    err = (np.abs(new[0][li].astype(np.float64) - x64) / bar).max(axis=1)      # per row, in units of its bar
+    ref_err = float(err[c].max())
+    widen = np.ones((nk, 1))
+    widen[li] = np.maximum(1.0, 4.0 * np.where(c, err, 0.0))[:, None]
+    rows[0][li], tol[0][li] = x64, bar
+    rows[1][li], tol[1][li] = s64, sbar
+    steps.append({"ids": ids, "grad": grads[t], "u": u, "s": s, "hp": hp, "clear": clear.copy(), "widen": widen,
+                  "ref_err": ref_err, "black": black, "live": live, "zeros": None,
+                  "slot_err": float((np.abs(new[1][li].astype(np.float64) - s64) / sbar).max()),
+                  "tables": [{"rows": rows[j].copy(), "rows32": new[j].astype(np.float64), "tol": tol[j].copy(),
+                              "metas": side.metas(j, keys), "counters": side.counters(j)} for j in range(2)]})
+  return {"batch": batch, "vinit": vinit, "sinits": sinits, "steps": steps}
+
+
+# ---- the sparse form: the same gradient rows, passed as segment gradients -----------------------------------------------------
+SPARSE_WEIGHTS = (0.5, 1.0, 2.0, 4.0)
+
+
+def has_sparse_form(D):
+  """kvhip.h kv_apply_sparse: the entry-list kernels' dims."""
+  return D % 4 == 0 and D <= 256
+
+
+def step_grad_rows(family, D, seed=OPT_SEED):
+  """The gradient rows of the trajectory's steps (what trajectory(family, D)["steps"][t]["grad"] holds), without the steps."""
+  return _setup(family, D, seed)[4]
+
+
+def sparse_form(family, D, t, grad):
+  """-> (seg_grad [num_segments, D], segment ids [n], weights [n], num_segments) that kv_apply_sparse with combiner "sum"
+  expands into `grad` (step t's rows) bit for bit: one position per segment, seg_grad[s_j] = grad_j / w_j with w_j a power
+  of two, so the one rounded multiply fl(w_j seg_grad[s_j]) the header defines is grad_j again.  The segment ids ascend with
+  gaps — about half of the segments are empty, some in front, some trailing; a segment's index never equals its position —
+  and are int32 at odd indices of DIMS, int64 at even ones.  The rows of empty segments hold NaN: they are never read."""
+  n = grad.shape[0]
+  rng = np.random.default_rng([OPT_SEED, D, ALL_FAMILIES.index(family), t, 5])
+  nseg = 2 * n + 8
+  seg = np.sort(rng.choice(np.arange(3, nseg - 4), n, replace=False))
+  w = rng.choice(SPARSE_WEIGHTS, n).astype(F)
+  seg_grad = np.full((nseg, D), np.nan, F)
+  seg_grad[seg] = grad / w[:, None]
+  return seg_grad, seg.astype(np.int32 if DIMS.index(D) % 2 else np.int64), w, nseg

@@ -15,6 +15,7 @@ import _reorder  # noqa: E402
 import _row_geometry as G  # noqa: E402
 import _shard_apply_sparse_ref as A  # noqa: E402
 import _sparse_grad_ref as R  # noqa: E402
+from _radam_ref import HP as RADAM_HP  # noqa: E402
 from tfplus_amd import _lib as L  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -26,9 +27,12 @@ FAM = {"group_adam_v4": ("group_adam", (0.05, 0.9, 0.999, 0.9, 0.999, 1e-8, 1e-3
        "adagrad": ("adagrad", (0.05, True)), "sparse_group_ftrl": ("sparse_group_ftrl", (0.1, 1e-3, 1e-2, 1e-3, 1e-2, -0.5)),
        "ftrl_v2": ("ftrl_v2", (0.1, 1e-3, 1e-2, 1e-2, -0.5)), "group_ftrl_v2": ("group_ftrl_v2", (0.1, 1e-3, 1e-2, 1e-2, -0.5)),
        "group_radam": ("group_rectified_adam", (0.1, 0.9, 0.999, 0.9, 0.999, 1e-7, 1e-3, 1e-2, 1e-3, 0.4, True, False, False)),
-       "adam": ("adam", (0.05,) + ADAM0[1:]), "plain_adam_v4": ("group_adam", ADAM0 + (0.0, 0.0, 0.0, 4))}
+       "adam": ("adam", (0.05,) + ADAM0[1:]), "plain_adam_v4": ("group_adam", ADAM0 + (0.0, 0.0, 0.0, 4)),
+       "radam": ("rectified_adam", RADAM_HP),
+       "group_amsgrad": ("group_amsgrad", (0.05, 0.9, 0.999, 0.9, 0.999, 1e-7, 1e-3, 0.01, 1e-3)),
+       "group_adabelief": ("group_adabelief", (0.05, 0.9, 0.999, 0.9, 0.999, 1e-7, 1e-3, 0.01, 1e-3))}
 CLASS_DIMS = sorted({min(d for d in range(4, 257, 4) if G.class_of("entry", d) == G.class_of("entry", D)) for D in range(4, 257, 4)})
-DET_CASES = [(f, 32, "mean", np.int64, True) for f in G.FAMILIES] + \
+DET_CASES = [(f, 32, "mean", np.int64, True) for f in G.ALL_FAMILIES] + \
             [(f, D, "mean", np.int64, True) for f in ("group_adam_v4", "adagrad", "adam") for D in CLASS_DIMS] + \
             [("adagrad", 32, c, t, w) for c in R.COMBINERS for t in (np.int32, np.int64) for w in (False, True)]
 

@@ -1,4 +1,4 @@
-"""The fused plain-RectifiedAdam op (kvhip.h kv_apply_rectified_adam and its forms) against radam_ref below, one restatement
+"""The fused plain-RectifiedAdam op (kvhip.h kv_apply_rectified_adam and its forms) against radam_ref (tests/_radam_ref.py), one restatement
 of the step's arithmetic, run on the table model of tests/_kv_model.py through the chain the reference composes
 (rectified_adam.py:68-96): gather_or_insert(opt) -> scatter_update(opt) [-> gather_or_insert(var)] -> scatter_sub(var)."""
 import itertools
@@ -13,49 +13,16 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _kv_model as M  # noqa: E402
 import _ranks  # noqa: E402
+from _radam_ref import HP, chain, radam_ref  # noqa: E402  (the scalars' order: _radam_ref.HP)
 
 F = np.float32
 DAY, SEED = 20000, 5
-# lr_t, beta1_power, beta2_power, beta1, beta2, epsilon, weight_decay, r_t, tractable, amsgrad, use_nesterov
-HP = (0.05, 0.81, 0.998, 0.9, 0.999, 1e-7, 0.01, 0.4, 1, 1, 1)
 FLAGS = list(itertools.product((0.0, 0.01), (0, 1), (0, 1), (0, 1)))        # weight_decay x tractable x amsgrad x use_nesterov
 DIMS_NS = [(D, n) for D in (4, 32, 256, 5, 260) for n in (1, 63, 2049)]     # entry-list classes, 5: the fallback; 2049: two tiles
 # The largest elementwise distance of radam_ref in float32 from radam_ref in float64 over every step of every case of
 # test_unique_ids, var and slot rows (on the CPU: max of |w32 - w64| over _unique_steps(D, n) for D, n in DIMS_NS):
 # 3.0833053e-08.  The GPU's sqrt and division are correctly rounded outside fast math and should add nothing: twice that.
 F64_BOUND = 2 * 3.0833053e-08
-
-
-def radam_ref(x, s, g, hp, dt):
-  """rectified_adam.py:76-96 on rows (x var, read for the decay term only; s slot = m | v | vhat; g the summed gradient), every
-  operation one rounding of dtype dt, the scalars the caller's float32 values.  -> (what scatter_sub takes off the var, slot rows)"""
-  lr_t, b1p, b2p, b1, b2, eps, wd, r_t, tract, ams, nest = [dt(F(v)) for v in hp]
-  D, one = g.shape[1], dt(1)
-  omb1, omb2, c1, c2 = one - b1, one - b2, one - b1p, one - b2p
-  x, g, m, v, h = [a.astype(dt) for a in (x, g, s[:, :D], s[:, D:2 * D], s[:, 2 * D:])]
-  with np.errstate(all="ignore"):
-    m1 = b1 * m + g * omb1
-    mu = g * omb1 + b1 * m1 if nest else m1
-    mc = mu / c1
-    v1 = b2 * v + (g * g) * omb2
-    h1 = np.maximum(v1, h) if ams else h
-    vc = np.sqrt((h1 if ams else v1) / c2)
-    upd = (r_t * mc) / (vc + eps) if tract else mc
-    if wd > 0:
-      upd = upd + wd * x
-    return upd * lr_t, np.concatenate([m1, v1, h1], axis=1)
-
-
-def chain(var, slot, ids, g, hp):
-  """One float32 step of the reference's chain on the models.  -> the (var, slot) rows it started from, their float64 step's"""
-  x0, s0 = [np.stack([t.rows[k].row if k in t.rows else t.init_row(k) for k in ids.tolist()]) for t in (var, slot)]
-  sg = slot.gather_or_insert(ids)                                 # (a blacklisted row: zeros)
-  xg = var.gather_or_insert(ids) if hp[6] > 0 else x0
-  step, s1 = radam_ref(xg, sg, g, hp, F)
-  slot.scatter_update(ids, s1, 0)
-  var.scatter_update(ids, step, 2)
-  step64, s64 = radam_ref(xg, sg, g, hp, np.float64)
-  return x0, s0, x0 - step64, s64
 
 
 def _unique_steps(D, n):

@@ -12,10 +12,14 @@ path.
                      operation: bit for bit (DIV: unique ids, rtol 1e-6);
   b. sparse lookups  kv_lookup_sparse (three combiners, with and without weights), its backward, kv_lookup_sparse_zeros:
                      the bounds of tests/_sparse_zeros_ref.py, the bits of tests/_sparse_grad_ref.py;
-  c. optimizers      eight families x every dim x every apply form the library offers for the dim (plain, with the lookup's
-                     token, unique; counted for the multiples of 4 up to 256; batched over two tables for every multiple of
-                     4), three steps with the state carried, regularizers on so that some rows blacklist (or zero) and
-                     some do not.  One reference trajectory per (family, dim) serves all forms (_row_geometry.trajectory);
+  c. optimizers      eleven families (G.ALL_FAMILIES) x every dim x every apply form the library offers for the dim (plain,
+                     with the lookup's token, unique; counted for the multiples of 4 up to 256; batched over two tables for
+                     every multiple of 4; for the multiples of 4 up to 256 also "sparse", straight from segment gradients
+                     through kv_variable_apply_sparse, and "multi_sparse", kv_multi_apply_sparse over two table sets of
+                     which the second passes plain rows), three steps with the state carried, regularizers on so that some
+                     rows blacklist (or zero) and some do not.  One reference trajectory per (family, dim) serves all forms
+                     (_row_geometry.trajectory): the sparse forms' segment gradients expand into the trajectory's gradient
+                     rows bit for bit (_row_geometry.sparse_form; tests/test_row_geometry.py holds that on the CPU);
   d. occurrence order  kv_set_deterministic(h, 2): the sorted pipeline with k_occ_sum at one dim per NC class and its edges;
                      the sums bit for bit;
   e. refused dims    which ops refuse a dim outside the fused kernels' range with KV_UNIMPLEMENTED and nothing changed,
@@ -37,6 +41,30 @@ matrix bites.  With the last k vector left out of the sum this module failed 317
 vector holds row elements (36, 60, 64, 65, 68, 124, 127, 128, 254, 255, 260, 508, 512, 1020, 1024); the rest of the suite
 noticed at dim 64 alone (16 cases).  With 1.0 added for every masked lane it failed 536 cases, at every dim of DIMS that is
 not its class's full width (3, 5, 7, 9, 12, ... 576, 1020); the rest of the suite noticed at dims 7 and 12 (19 cases).
+
+The three families that came after the matrix — plain RectifiedAdam (optimizer code 8), group AMSGrad / group AdaBelief
+(code 9, one kernel family) — and the segment-gradient apply (kv_apply_sparse / kv_multi_apply_sparse: k_papply_seg,
+k_papply_seg_multi) run here on the same batch.  What their own files run them on:
+  code 9            tests/test_gpu_group_adam4.py: distinct ids (300: one tile, no hot key, no tile sums) at dims 4, 7, 36,
+                    256, 1024, repeated ids at dim 32 only — k_apply / k_apply_fin had never summed a repeated key for code
+                    9 (dims 7, 1024, everything above 256), k_papply had run one row class of nine;
+  code 8            tests/test_gpu_radam.py: distinct ids at dims 4, 32, 256, 5, 260, repeated ids at dim 32; no masked
+                    class (12, 36, 60, 132, 252), nothing above 260;
+  kv_apply_sparse   tests/test_gpu_apply_sparse.py: against the composition it replaces (another GPU path) at dim 32 for every
+                    family and at the SMALLEST dim of each entry class (4, 8, 12, 20, 36, 68, 132) for three families; of
+                    DIMS, 16, 60, 64, 124, 128, 252 and 256 — the upper edge of every class from (4,4,1) on, 32 excepted —
+                    for no family; here against the CPU references, every family at all 15 multiples of 4 up to 256, int32
+                    and int64 segment ids, segments with gaps, NaN rows in the empty ones.
+Two more arithmetic-only edits, each built and run once, show where these additions bite:
+  1. opt_core's code-9 pass (kv_device.h): the accumulator block's maximum with its old value skipped for the last k vector.
+     This module failed 170 cases, all group_amsgrad, every form, at the 35 dims of DIMS whose last k vector holds row
+     elements (all but 129, 516, 572, 576).  tests/test_gpu_group_adam4.py noticed in 6 cases (its dims 4, 7, 36, 256, 1024
+     on distinct ids, and the variant test at dim 8); tests/test_gpu_radam.py and tests/test_gpu_apply_sparse.py in none.
+  2. the SEG row fetch of k_papply (kv_papply.h load_row): the scale multiply dropped for a row's last float4.  This module
+     failed 330 cases: all 11 families x 15 dims x {sparse, multi_sparse}.  tests/test_gpu_apply_sparse.py noticed in 51 cases
+     (its composition twin does not go through the SEG fetch) at dims 4, 8, 12, 20, 32, 36, 68, 100, 132; at 16,
+     60, 64, 124, 128, 252 and 256 it was noticed here alone; tests/test_gpu_radam.py in 2 (test_forms_agree,
+     dims 8 and 32); tests/test_gpu_group_adam4.py in none (its sparse form has no weights: the scale is 1).
 
 Bars: ids, flags, frequency words, counters exact; rows rtol 1e-6 with the atol of the family's own test file; a var that
 went through a group norm (1e-6 / scale) |x| + atol per row, rows whose scale is within 1e-4 of the threshold skipped (at
@@ -99,6 +127,53 @@ ref_err, the largest over a case's rows and its three steps, per dim (tests/test
    576       2.97           2.59           0.887           0.0233         0.311
   1020       3.21           3.65            1.26           0.0195         0.464
   1024       3.04           4.19            1.52           0.0184         0.262
+
+The later families.  group_amsgrad / group_adabelief: ref_err as above (their bar: tests/test_gpu_group_adam4.py's rtol 1e-6,
+the var's over scale, atol 1e-7, against the float64 step, for the var and all four slot blocks; the slot blocks' bar is
+never widened, and the float32 restatement stays below 0.26 of it).  radam: the largest |float32 chain - float64 chain|
+over the trajectory's var and slot rows; the rows must hold the float32 chain's bits (tests/test_gpu_radam.py
+test_unique_ids's bar) and lie within twice that distance of the float64 chain.
+
+  dim    group_amsgrad  group_adabelief  radam |float32 - float64|
+     1      0.107          0.126            1.49e-08
+     2      0.131          0.146            1.49e-08
+     3      0.125          0.155            1.49e-08
+     4      0.186          0.166            1.48e-08
+     5      0.143          0.153            1.48e-08
+     7       0.17          0.168            1.49e-08
+     8      0.164          0.164            1.51e-08
+     9      0.165          0.167            1.49e-08
+    12       0.19          0.141            1.48e-08
+    15      0.133          0.172            1.49e-08
+    16      0.151          0.157             1.5e-08
+    17      0.154          0.185             1.5e-08
+    20       0.17          0.171            1.53e-08
+    31      0.209          0.193             1.5e-08
+    32      0.164          0.179            1.51e-08
+    33      0.179          0.186            1.49e-08
+    36      0.187          0.184            1.56e-08
+    60      0.181          0.194            2.97e-08
+    63      0.185          0.173            1.51e-08
+    64      0.196          0.159             1.5e-08
+    65      0.199          0.178            1.51e-08
+    68       0.18          0.181            1.57e-08
+   124      0.194           0.19            1.54e-08
+   127      0.197          0.148            1.52e-08
+   128      0.185          0.198            1.55e-08
+   129      0.202           0.21            1.51e-08
+   132      0.175          0.195            1.53e-08
+   252        0.2          0.197            1.55e-08
+   254      0.199          0.196            2.89e-08
+   255      0.212          0.206            2.24e-08
+   256      0.196          0.196            2.71e-08
+   260      0.208          0.192            2.06e-08
+   508      0.183          0.204            1.67e-08
+   512      0.208          0.213            2.34e-08
+   516      0.194          0.223            1.54e-08
+   572      0.217          0.196            1.55e-08
+   576      0.208          0.222            2.51e-08
+  1020      0.207          0.199            2.98e-08
+  1024      0.215          0.232            2.49e-08
 """
 import os
 import sys
@@ -344,7 +419,9 @@ def _single(ops, family):
   return {"group_adam_v4": ops.kv_variable_group_sparse_apply_adam_v4, "group_adam_v3": ops.kv_variable_group_sparse_apply_adam_v3,
           "sparse_group_ftrl": ops.kv_variable_sparse_group_sparse_apply_ftrl_v2, "ftrl_v2": ops.kv_variable_sparse_apply_ftrl_v2,
           "group_ftrl_v2": ops.kv_variable_group_sparse_apply_ftrl_v2,
-          "group_radam": ops.kv_variable_group_sparse_apply_rectified_adam, "adam": ops.kv_variable_sparse_apply_adam}[family]
+          "group_radam": ops.kv_variable_group_sparse_apply_rectified_adam, "adam": ops.kv_variable_sparse_apply_adam,
+          "radam": ops.kv_variable_sparse_apply_rectified_adam, "group_amsgrad": ops.kv_variable_group_sparse_apply_amsgrad,
+          "group_adabelief": ops.kv_variable_group_sparse_apply_adabelief}[family]
 
 
 def _apply(ops, family, hs, grad, ids, hp, **kw):
@@ -364,8 +441,26 @@ def _apply_multi(ops, family, sets, grads, idl, hp):
     return ops.kv_multi_group_sparse_apply_adam(*roles, grads, idl, *hp[:9], version=hp[9])
   fn = {"sparse_group_ftrl": ops.kv_multi_sparse_group_sparse_apply_ftrl, "ftrl_v2": ops.kv_multi_sparse_apply_ftrl_v2,
         "group_ftrl_v2": ops.kv_multi_group_sparse_apply_ftrl_v2, "group_radam": ops.kv_multi_group_sparse_apply_rectified_adam,
-        "adam": ops.kv_multi_sparse_apply_adam}[family]
+        "adam": ops.kv_multi_sparse_apply_adam, "radam": ops.kv_multi_sparse_apply_rectified_adam,
+        "group_amsgrad": ops.kv_multi_group_sparse_apply_amsgrad, "group_adabelief": ops.kv_multi_group_sparse_apply_adabelief}[family]
   return fn(*roles, grads, idl, *hp)
+
+
+# the family's row of _lib.OPT_FAMILIES, which kv_variable_apply_sparse / kv_multi_apply_sparse name it by; the trajectory's
+# scalars are in that row's order (GroupAdam's with the version last)
+STEM = {"group_adam_v4": "group_adam", "group_adam_v3": "group_adam", "group_radam": "group_rectified_adam", "radam": "rectified_adam"}
+
+
+def _apply_sparse(ops, family, sets, st, D, t):
+  """One step straight from segment gradients (_row_geometry.sparse_form: they expand into the step's gradient rows bit for
+  bit).  One table set: kv_variable_apply_sparse; two: kv_multi_apply_sparse, the second set passing the plain rows."""
+  sg, seg, w, nseg = G.sparse_form(family, D, t, st["grad"])
+  stem = STEM.get(family, family)
+  if len(sets) == 1:
+    return ops.kv_variable_apply_sparse(stem, sets[0], st["hp"], sg, st["ids"], seg, w, nseg, "sum")
+  assert len(sets) == 2
+  ops.kv_multi_apply_sparse(stem, tuple(zip(*sets)), st["hp"], [sg, st["grad"]], [st["ids"]] * 2, [seg, None], [w, None],
+                            [nseg, 0], "sum")
 
 
 def _forms(D):
@@ -374,6 +469,8 @@ def _forms(D):
     f.append("counted")
   if D % 4 == 0:
     f.append("multi")
+  if G.has_sparse_form(D):
+    f += ["sparse", "multi_sparse"]
   return f
 
 
@@ -399,8 +496,20 @@ def _check_step(ops, hs, tr, t, tag):
       assert (ops.kv_variable_size_v2(h), ops.kv_variable_frequency(h)) == tb["counters"][1:], (tag, j)
 
 
+def _check_radam_bits(ops, hs, tr, t, tag):
+  """Plain RectifiedAdam beyond _check_step (whose tolerance is 0 here: numerically equal): var and slot rows hold the
+  float32 chain's BITS, and lie within twice the chain's own float32-to-float64 distance of its float64 step."""
+  keys = tr["batch"]["keys"]
+  for j, (h, tb) in enumerate(zip(hs, tr["steps"][t]["tables"])):
+    got = _np(ops.kv_variable_gather_or_zeros_v2(h, keys))
+    want = tb["rows32"].astype(F)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (tag, "table %d" % j, np.argwhere(got != want)[:5])
+    assert (np.abs(got.astype(np.float64) - tb["rows64"]) <= 2 * tr["f64_dist"]).all(), (tag, "table %d" % j)
+
+
 def _align(ops, hs, tr, t):
-  """GroupAdam between two steps: the rows just found within their bars of the reference's are set to the reference's own
+  """GroupAdam, group AMSGrad and group AdaBelief (G.ALIGNED_FAMILIES: linear' reads the var through a difference of two
+  square roots) between two steps: the rows just found within their bars of the reference's are set to the reference's own
   bits (scatter_update ASSIGN: no frequency word moves, a blacklisted row is left alone, the flags come from the same rows
   as the reference's).  The next step then starts from the reference's state, as the bars assume."""
   st, keys = tr["steps"][t], tr["batch"]["keys"]
@@ -409,7 +518,7 @@ def _align(ops, hs, tr, t):
     ops.kv_variable_scatter_update_v2(h, keys[there], tb["rows32"][there].astype(F))
 
 
-OPT_CASES = [(f, D, form) for f in G.FAMILIES for D in G.DIMS for form in _forms(D)]
+OPT_CASES = [(f, D, form) for f in G.ALL_FAMILIES for D in G.DIMS for form in _forms(D)]
 
 
 @pytest.mark.parametrize("family,D,form", OPT_CASES, ids=["%s-%d-%s" % c for c in OPT_CASES])
@@ -418,7 +527,7 @@ def test_optimizer_step(ops, family, D, form):
   b = tr["batch"]
   sdims = G.slot_dims(family, D)
   sets = []
-  for _ in range(2 if form == "multi" else 1):             # the batched form: two tables with the same history
+  for _ in range(2 if form in ("multi", "multi_sparse") else 1):      # the batched forms: two tables with the same history
     hs = [_table(ops, D, tr["vinit"], thr=G.ENTER, seed=G.OPT_SEED)] + \
          [_table(ops, d, init, seed=G.OPT_SEED) for d, init in zip(sdims, tr["sinits"])]
     ops.kv_variable_gather_or_insert_v2(hs[0], b["pre"])
@@ -430,6 +539,10 @@ def test_optimizer_step(ops, family, D, form):
       for hs in sets:
         ops.kv_variable_gather_or_insert_v2(hs[0], ids)
       _apply_multi(ops, family, sets, [grad] * 2, [ids] * 2, hp)
+    elif form in ("sparse", "multi_sparse"):               # straight from segment gradients; set 1 of the batched call: plain rows
+      for hs in sets:
+        ops.kv_variable_gather_or_insert_v2(hs[0], ids)
+      _apply_sparse(ops, family, sets, st, D, t)
     else:
       hs = sets[0]
       if form == "tok":                                    # the training lookup of a device tensor, then the very same object
@@ -452,7 +565,9 @@ def test_optimizer_step(ops, family, D, form):
       assert 0 < st["zeros"][0] < st["zeros"][1], tag
     for hs in sets:
       _check_step(ops, hs, tr, t, tag)
-      if family.startswith("group_adam") and t + 1 < G.STEPS:
+      if family == "radam":
+        _check_radam_bits(ops, hs, tr, t, tag)
+      if family in G.ALIGNED_FAMILIES and t + 1 < G.STEPS:
         _align(ops, hs, tr, t)
 
 
@@ -460,12 +575,13 @@ def test_optimizer_step(ops, family, D, form):
 OCC_DIMS = [64, 68, 128, 256, 260, 512, 516, 1024, 7, 63, 255]
 
 
-@pytest.mark.parametrize("family", ["adam", "group_ftrl_v2"])
+@pytest.mark.parametrize("family", ["adam", "group_ftrl_v2", "radam"])
 @pytest.mark.parametrize("D", OCC_DIMS)
 def test_occurrence_order(ops, D, family):
   """kv_set_deterministic(h, 2): every dim takes the sorted pipeline, a hot key's chain is k_occ_sum's.  Gradients with full
   mantissas: the sums must be TF-core's occurrence-order sums bit for bit, and with them the step the model's."""
   import _kv_model as M
+  import _radam_ref as RR
   assert D in G.DIMS
   rng = np.random.default_rng([D, 4])
   b = G.draw_batch(np.random.default_rng(G.SEEDS[1]))
@@ -490,22 +606,28 @@ def test_occurrence_order(ops, D, family):
     b1p, b2p = G.beta_pows(t)
     if family == "adam":
       hp = (0.05, b1p, b2p, 0.9, 0.999, 1e-8)
+    elif family == "radam":                                 # the two weight-decay steps of the matrix: nesterov, then amsgrad
+      hp = (0.05, b1p, b2p, 0.9, 0.999, 1e-7) + G.RADAM_FLAGS[1 + t][:1] + (0.4,) + G.RADAM_FLAGS[1 + t][1:]
     else:
       hp = lambda x, srows, g: (0.1, M.lasso_threshold(M.linear_norms(family, x, srows, g, (0.1, 0.0, 1e-2, 1e-2, -0.5))[0], rng),
                                 1e-2, 1e-2, -0.5)
-    res = M.apply_step(family, var, slots, u, s, hp, bar=family != "adam")
+    if family == "radam":                                   # the reference's chain on the models (tests/_radam_ref.py)
+      RR.chain(var, slots[0], u, s, hp)
+      res = {"hp": hp}
+    else:
+      res = M.apply_step(family, var, slots, u, s, hp, bar=family == "group_ftrl_v2")
     _apply(ops, family, hs, grad, ids, res["hp"])
     for j, (h, m) in enumerate(zip(hs, [var] + slots)):
       got = _np(ops.kv_variable_gather_or_zeros_v2(h, keys))
       want = m.gather_or_zeros(keys)
-      if family == "adam":                                  # the same sums, the same operations: the same bits
+      if family in ("adam", "radam"):                       # the same sums, the same operations: the same bits
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (D, t, j)
       else:
         assert (np.abs(got.astype(np.float64) - want) <= m.tols(keys)).all(), (D, t, j)
       assert ops.kv_get_meta(h, keys) == m.metas(keys), (D, t, j)
       assert (ops.kv_variable_shape_v2(h)[0], ops.kv_variable_size_v2(h), ops.kv_variable_frequency(h)) == \
           (m.map_size(), m.size(), m.sum_freq())
-    if family != "adam":
+    if family == "group_ftrl_v2":
       assert 0 < int((~res["updated"]).sum()) < len(res["keys"])
 
 
@@ -524,7 +646,9 @@ def _neutral_hps():
           "adagrad": (0.05, True), "sparse_group_ftrl": (0.1, 0.0, 0.0, 0.0, 0.0, -0.5), "ftrl_v2": (0.1, 0.0, 0.0, 0.0, -0.5),
           "group_ftrl_v2": (0.1, 0.0, 0.0, 0.0, -0.5),
           "group_radam": (0.1, b1p, b2p, 0.9, 0.999, 1e-7, 0.0, 0.0, 0.0, 0.4, False, False, False),
-          "adam": (0.05, b1p, b2p, 0.9, 0.999, 1e-8)}
+          "adam": (0.05, b1p, b2p, 0.9, 0.999, 1e-8), "radam": (0.05, b1p, b2p, 0.9, 0.999, 1e-7, 0.0, 0.4, 0, 0, 0),
+          "group_amsgrad": (0.05, b1p, b2p, 0.9, 0.999, 1e-7, 0.0, 0.0, 0.0),
+          "group_adabelief": (0.05, b1p, b2p, 0.9, 0.999, 1e-7, 0.0, 0.0, 0.0)}
 
 
 def _eq(got, want):
@@ -597,7 +721,7 @@ def _srv_lookup_sparse_grad(c):
 def _ref_optimizers(c):
   """every family: the op with the duplicate sum inside (_tok), the _unique op, the batched op over two tables"""
   hps = _neutral_hps()
-  for family in G.FAMILIES:
+  for family in G.ALL_FAMILIES:
     slots = [_table(c.ops, d, np.zeros((1, d), F), seed=6) for d in G.slot_dims(family, c.D)]
     slots2 = [_table(c.ops, d, np.zeros((1, d), F), seed=6) for d in G.slot_dims(family, c.D)]
     _refused(_apply, c.ops, family, [c.h] + slots, c.grad, c.ids, hps[family])
@@ -679,7 +803,7 @@ def test_batched_and_counted_forms_refuse_dims_that_are_no_multiple_of_4(ops, D)
   ids = b["ids"]
   grad = rng.standard_normal((ids.size, D)).astype(F)
   hps = _neutral_hps()
-  for family in G.FAMILIES:
+  for family in G.ALL_FAMILIES:
     sets = []
     for _ in range(2):
       h, _o = _pair(ops, D, seed=8)

@@ -284,5 +284,64 @@ def test_reference_trajectories_meet_their_conditions(family):
       for tb in st["tables"]:
         assert np.isfinite(tb["rows"]).all() and np.isfinite(tb["tol"]).all() and (tb["tol"] >= 0).all()
       worst = max(worst, st["ref_err"])
+      if family in G.ADAM4_FAMILIES:      # the slot rows' bar is never widened: a float32 evaluation must be able to meet it
+        assert st["slot_err"] < 1.0, (family, D, t, st["slot_err"])
     line.append("%d: %.3g" % (D, worst))
   print("%s ref_err per dim (units of the bar): %s" % (family, ", ".join(line)))
+
+
+def test_radam_trajectories_meet_their_conditions():
+  """Plain RectifiedAdam, every dim: the chain's float32 and float64 results are finite, the stored float64 distance is what
+  the rows say (printed per dim), and the weight-decay steps, and only those, move the var's frequency words and days."""
+  line = []
+  for D in G.DIMS:
+    tr = G.trajectory("radam", D)
+    dist = 0.0
+    for t, st in enumerate(tr["steps"]):
+      assert st["hp"][6:] == G.RADAM_FLAGS[t][:1] + (0.4,) + G.RADAM_FLAGS[t][1:] and st["live"].all() and st["clear"].all()
+      for tb in st["tables"]:
+        assert np.isfinite(tb["rows32"]).all() and np.isfinite(tb["rows64"]).all() and not tb["tol"].any()
+        assert np.array_equal(tb["rows"], tb["rows32"]) and np.array_equal(tb["rows32"].astype(np.float32), tb["rows32"])
+        dist = max(dist, float(np.abs(tb["rows32"] - tb["rows64"]).max()))
+      words = lambda ms: [(m["freq"], m["day"]) for m in ms]
+      hit = [(f + 1, G.DAY) for f, _ in words(st["pre_metas"])]
+      assert words(st["tables"][0]["metas"]) == (hit if st["hp"][6] > 0 else words(st["pre_metas"])), (D, t)
+      assert all(m["freq"] == t + 1 for m in st["tables"][1]["metas"]), (D, t)      # the slot row: one hit per step
+    assert [st["hp"][6] > 0 for st in tr["steps"]] == [False, True, True]
+    assert 0 < dist == tr["f64_dist"] < 1e-6, (D, dist, tr["f64_dist"])
+    line.append("%d: %.3g" % (D, dist))
+  print("radam largest |float32 chain - float64 chain| per dim: %s" % ", ".join(line))
+
+
+SPARSE_CASES = [(f, D) for f in G.ALL_FAMILIES for D in G.DIMS if G.has_sparse_form(D)]
+
+
+def test_sparse_form_inputs_expand_into_the_gradient_rows():
+  """The sparse form of tests/test_gpu_row_geometry.py, every (family, dim) that has it, every step: the segment gradients
+  expand (tests/_sparse_grad_ref.py, combiner "sum") into the step's gradient rows bit for bit; no segment gradient is
+  subnormal (the division by the weight was exact); at least a quarter of the segments are empty, some in front, some
+  trailing, their rows NaN; no segment's index is its position; both segment dtypes occur."""
+  import _sparse_grad_ref as GR
+  assert len(SPARSE_CASES) == 11 * 15          # DIMS holds 15 multiples of 4 up to 256
+  assert all(D <= 256 and G.class_of("entry", D) for _, D in SPARSE_CASES)
+  dtypes, weights = set(), set()
+  for family, D in SPARSE_CASES:
+    for t, grad in enumerate(G.step_grad_rows(family, D)):
+      sg, seg, w, nseg = G.sparse_form(family, D, t, grad)
+      n = grad.shape[0]
+      assert sg.shape == (nseg, D) and sg.dtype == np.float32 and seg.shape == w.shape == (n,)
+      assert seg.dtype == (np.int32 if G.DIMS.index(D) % 2 else np.int64)
+      assert (np.diff(seg) > 0).all() and seg[0] > 0 and seg[-1] < nseg - 1 and (seg != np.arange(n)).all()
+      empty = np.setdiff1d(np.arange(nseg), seg)
+      assert empty.size >= nseg / 4 and (np.diff(seg) > 1).any() and np.isnan(sg[empty]).all() and np.isfinite(sg[seg]).all()
+      assert GR.same_bits(GR.lookup_sparse_grad(sg, seg, w, nseg, "sum"), grad), (family, D, t)
+      assert not ((sg[seg] != 0) & (np.abs(sg[seg]) < np.finfo(np.float32).tiny)).any(), (family, D, t)
+      dtypes.add(seg.dtype.name)
+      weights.update(w.tolist())
+  assert dtypes == {"int32", "int64"} and weights == set(G.SPARSE_WEIGHTS)
+
+
+def test_sparse_form_gradients_are_the_trajectory_s():
+  for family, D in [("adagrad", 4), ("radam", 252), ("group_adabelief", 36)]:
+    for st, grad in zip(G.trajectory(family, D)["steps"], G.step_grad_rows(family, D)):
+      assert np.array_equal(st["grad"].view(np.uint32), grad.view(np.uint32))
