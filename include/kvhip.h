@@ -357,7 +357,7 @@ int kv_dedup_segment_sum_dev(kv_handle_t h, const void* ids, const float* grad, 
 /* kv_apply_<optimizer>_unique with the id count taken from the DEVICE: the op is applied to the first
  * min(n_max, *n_dev) ids and gradient rows, *n_dev (int64, device memory — kv_dedup_segment_sum_dev's or kv_unique's
  * num_unique_dev) being read by the kernel when it runs.  `optimizer`, `hp` and `slot1` are kv_shard_apply_serve's
- * codes and layouts (0 .. 9, below).  The same promise of unique ids, the same duplicate guard, checks, results and slot
+ * codes and layouts (0 .. 10, below).  The same promise of unique ids, the same duplicate guard, checks, results and slot
  * mirror handling as the _unique ops: the same bits.  `ids` [n_max] are KV_DT_INT64 or KV_DT_INT32 (ids_dtype) whatever
  * the table's key dtype — the dedup writes int64 ids for every table.  `grad` is [n_max, dim].
  * The host sizes everything by n_max: the tables' capacity (their row bounds advance by n_max per call, so a table
@@ -378,7 +378,7 @@ int kv_apply_unique_counted(kv_handle_t var, int optimizer, kv_handle_t slot0, k
  * those back to sum them per distinct id — writes and reads n * dim * 4 bytes that carry no information; here the tile sums and
  * the partition pass + update fetch a position's row from the segment gradients themselves, through per-position records
  * (segment, scale: 8 bytes a position) that a small pre-pass leaves in the var table's workspace.  The values buffer is never
- * allocated.  `optimizer`, `slot0`, `slot1` and `hp` are kv_shard_apply_serve's codes and layouts (0 .. 9, below), validated as
+ * allocated.  `optimizer`, `slot0`, `slot1` and `hp` are kv_shard_apply_serve's codes and layouts (0 .. 10, below), validated as
  * kv_apply_unique_counted validates them: the hyperparameter checks, their order and their wording are the named ops'.
  *   kv_apply_sparse        seg_grad [num_segments, dim], ids [n] of the table's key dtype, segment_ids [n] int32 or int64,
  *                          weights [n] or NULL: kv_lookup_sparse's arguments of the batch.  n == 0: a no-op, KV_OK.
@@ -825,6 +825,46 @@ int kv_multi_apply_group_adabelief_unique(int num_tables, const kv_handle_t* var
                                           float beta1_power, float beta2_power, float beta1, float beta2, float epsilon,
                                           float l1, float l2, float l21, kv_stream_t stream);
 
+/* Group LAMB: KvVariableGroupSparseApplyLamb (kernels/training_ops.cc:3400-3683; row math :3618-3661, COMPUTE_LAMB).  The
+ * reference keeps four slot variables beside the var; here `opt` is ONE slot table of dim 4 x the var's: [m | v | linear |
+ * accum], the block order of kv_apply_group_amsgrad's row, a row of zeros at first.  Per distinct id, g = the id's summed
+ * gradient row, every operation one fp32 rounding, in the reference's order:
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) (g g)
+ *   new_m = m / (1 - beta1_power);  new_accum = v / (1 - beta2_power);  r = new_m / (sqrt(new_accum) + epsilon)
+ *   r_norm = sqrt(sum r r);  var_norm = sqrt(sum var var)
+ *   ratio = var_norm / (r_norm + 1e-8) where r_norm > 0 and var_norm > 0, else 1: the row's trust ratio
+ *   linear = linear + (new_m ratio - ((sqrt(new_accum) - sqrt(accum)) / lr) var)
+ *   u = clamp(linear, -l1, l1) - linear;  norm = sqrt(sum u u)
+ *   norm > l21 sqrt(dim):  var = (u (1 - l21 sqrt(dim) / norm)) / ((sqrt(new_accum) + epsilon) / lr + 2 l2), CoverUpdate
+ *   else:                  the var is blacklisted (MarkBlacklist): it reads as zeros
+ *   accum = new_accum;  all four blocks are written on either branch
+ * A var row that is blacklisted enters the op as zeros, so its var_norm is 0 and its ratio 1.  The three sums are formed per
+ * row by the lanes that share it (lane partials, then a butterfly): their order is not the reference's left-to-right one.
+ * 1 - beta1_power and 1 - beta2_power are computed once on the host, in fp32.  Bookkeeping, checks (KV_INVALID_ARGUMENT for
+ * lr <= 0, negative l1 / l2 / l21, a beta power outside [0, 1), var == opt, "opt must be 4x", tables on different devices;
+ * KV_FAILED_PRECONDITION for an uninitialised table), dims, limits, graph capture, deterministic modes, fast math and delta
+ * tracking as kv_apply_group_amsgrad.  _unique / _tok and the batched forms: as kv_[multi_]apply_group_amsgrad[_unique|_tok]. */
+int kv_apply_group_lamb(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                        float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1, float l2,
+                        float l21, kv_stream_t stream);
+int kv_apply_group_lamb_tok(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                            float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1, float l2,
+                            float l21, kv_batch_token_t token, kv_stream_t stream);
+int kv_apply_group_lamb_unique(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                               float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1,
+                               float l2, float l21, kv_stream_t stream);
+int kv_multi_apply_group_lamb(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts, const float* const* grads,
+                              const void* const* ids, const int64_t* ns, float lr, float beta1_power, float beta2_power,
+                              float beta1, float beta2, float epsilon, float l1, float l2, float l21, kv_stream_t stream);
+int kv_multi_apply_group_lamb_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                  const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                  float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1,
+                                  float l2, float l21, const kv_batch_token_t* tokens, kv_stream_t stream);
+int kv_multi_apply_group_lamb_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                     const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                     float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1,
+                                     float l2, float l21, kv_stream_t stream);
+
 
 /* embedding_lookup_sparse on a KvVariable (python/ops/embedding_ops.py:279-441), fused: the
  * reference runs unique_with_counts -> GatherOrInsert[WithCounts] -> gather(idx) -> (x weights) ->
@@ -1076,6 +1116,8 @@ int kv_shard_apply_route(kv_shard_t shard, const float* grad, kv_stream_t stream
  * tractable, amsgrad, use_nesterov — the three flags as 0 / 1; slot0 = opt, slot1 unused),
  * 9 group AMSGrad / group AdaBelief (kv_apply_group_amsgrad / kv_apply_group_adabelief; hp = lr, beta1_power, beta2_power,
  * beta1, beta2, epsilon, l1, l2, l21, variant — 0 AMSGrad, 1 AdaBelief, anything else KV_INVALID_ARGUMENT; slot0 = opt,
+ * slot1 unused),
+ * 10 group LAMB (kv_apply_group_lamb; hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21; slot0 = opt,
  * slot1 unused) */
 int kv_shard_apply_serve(kv_shard_t shard, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp,
                          kv_stream_t stream);

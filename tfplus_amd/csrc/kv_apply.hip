@@ -1,6 +1,6 @@
 // kv_apply.hip — the optimizer layer of the C ABI on the table core (kv_host.h): one parser per optimizer family, the two
 // bodies (apply_one: one table; multi_apply: many tables, one launch per stage; the PartArgs of all their launches start
-// from opt_part_args), the 60 kv_apply_* / kv_multi_apply_* entry points, kv_[multi_]apply_sparse (the same bodies fed from
+// from opt_part_args), the 66 kv_apply_* / kv_multi_apply_* entry points, kv_[multi_]apply_sparse (the same bodies fed from
 // segment gradients) and kv_attach_slot.  It compiles no kernel: the
 // optimizers' kernels are reached through the typed launchers of kv_launch.h, the pipelines' through the core's.
 #include <hip/hip_runtime.h>
@@ -143,7 +143,7 @@ static WideSlotWords wide_slot_words(int opt) {
       return {"opt", "kv_variable and opt_shape do not have the same shape [%d] [%d] (opt must be 5x)", "", false};
     case OPT_ADAM: return {"m_v", "var and m_v do not have matching shapes [%d] [%d] (m_v must be 2x)", ": m_v must be 2x", true};
     case OPT_RADAM: return {"opt", "var and opt do not have matching shapes [%d] [%d] (opt must be 3x)", ": opt must be 3x", true};
-    case OPT_GROUP_ADAM4:
+    case OPT_GROUP_ADAM4: case OPT_GROUP_LAMB:
       return {"opt", "kv_variable and opt do not have the same shape [%d] [%d] (opt must be 4x)", ": opt must be 4x", true};
     default: return {"slot", "var and slot do not have matching shapes [%d] [%d]", "", false};
   }
@@ -584,6 +584,23 @@ static OptCall group_adam4_call(int variant, float lr, float b1p, float b2p, flo
 // the variant in the generic entries' float vector: 0 or 1 exactly; anything else goes on as -1, which the call refuses
 static int hp_variant(float f) { return f == 0.f ? GA4_AMSGRAD : f == 1.f ? GA4_ADABELIEF : -1; }
 
+// Group LAMB (training_ops.cc:3400-3683; row math :3618-3661): slot row = m | v | linear | accum.  Checks, order and wording
+// as group_adam4_call's; 1 - beta1_power and 1 - beta2_power once, in fp32
+static OptCall group_lamb_call(float lr, float b1p, float b2p, float b1, float b2, float eps, float l1, float l2, float l21) {
+  OptCall c;
+  c.opt = OPT_GROUP_LAMB;
+  c.slot_mult = slot0_blocks(OPT_GROUP_LAMB);
+  if ((c.status = check_hp(lr, l1, l2, l21, 0.f, 0.f))) return c;
+  if (!(b1p >= 0.f && b1p < 1.f)) { c.status = fail(KV_INVALID_ARGUMENT, "beta1_power is not in [0, 1): %g", b1p); return c; }
+  if (!(b2p >= 0.f && b2p < 1.f)) { c.status = fail(KV_INVALID_ARGUMENT, "beta2_power is not in [0, 1): %g", b2p); return c; }
+  OptArgs& a = c.a;
+  a.lr = lr; a.b1p = b1p; a.b2p = b2p; a.b1 = b1; a.b2 = b2; a.eps = eps;
+  a.l1 = l1; a.l2 = l2; a.l21 = l21;
+  lamb_c1(a) = 1.f - b1p;
+  lamb_c2(a) = 1.f - b2p;
+  return c;
+}
+
 // the one place where a runtime OPT_* becomes the template argument of the pipelines
 template <class F>
 static int with_opt(int opt, F&& f) {
@@ -598,6 +615,7 @@ static int with_opt(int opt, F&& f) {
     case OPT_ADAM: return f(std::integral_constant<int, OPT_ADAM>());
     case OPT_RADAM: return f(std::integral_constant<int, OPT_RADAM>());
     case OPT_GROUP_ADAM4: return f(std::integral_constant<int, OPT_GROUP_ADAM4>());
+    case OPT_GROUP_LAMB: return f(std::integral_constant<int, OPT_GROUP_LAMB>());
     default: return fail(KV_INTERNAL, "optimizer %d", opt);
   }
 }
@@ -615,7 +633,8 @@ namespace __attribute__((visibility("hidden"))) kvhip_internal {
 // 8 RectifiedAdam (hp = lr_t, beta1_power, beta2_power, beta1, beta2, epsilon, weight_decay, r_t, tractable, amsgrad,
 // use_nesterov; the three flags as 0 / 1; slot0 = opt),
 // 9 group AMSGrad / group AdaBelief (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, variant: 0 AMSGrad,
-// 1 AdaBelief; slot0 = opt)
+// 1 AdaBelief; slot0 = opt),
+// 10 group LAMB (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21; slot0 = opt)
 OptCall shard_opt_call(int optimizer, const float* hp) {
   switch (optimizer) {
     case OPT_ADAM_V4: case OPT_ADAM_V3:
@@ -631,6 +650,7 @@ OptCall shard_opt_call(int optimizer, const float* hp) {
       return radam_call(hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp_flag(hp[8]), hp_flag(hp[9]), hp_flag(hp[10]));
     case OPT_GROUP_ADAM4:
       return group_adam4_call(hp_variant(hp[9]), hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8]);
+    case OPT_GROUP_LAMB: return group_lamb_call(hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8]);
     default: return OptCall{};
   }
 }
@@ -858,43 +878,46 @@ int kv_multi_apply_rectified_adam_unique(int num_tables, const kv_handle_t* vars
 #undef KV_RADAM_PARAMS
 #undef KV_RADAM_CALL
 
-// group AMSGrad and group AdaBelief: the same six forms per stem, one OptCall apart in its variant
+// group AMSGrad, group AdaBelief and group LAMB: the same six forms per stem, one OptCall (CALL, over KV_GA4_HP) apart
 #define KV_GA4_PARAMS float lr, float b1p, float b2p, float b1, float b2, float eps, float l1, float l2, float l21
-#define KV_GA4_ENTRIES(stem, variant)                                                                                              \
+#define KV_GA4_ENTRIES(stem, CALL)                                                                                                 \
   int kv_apply_##stem(kv_handle_t v, kv_handle_t opt, const float* grad, const void* ids, int64_t n, KV_GA4_PARAMS,               \
                       kv_stream_t stream) {                                                                                        \
-    return apply_one(group_adam4_call(variant, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), v, opt, nullptr, grad, ids, n, 0, stream,  \
+    return apply_one(CALL, v, opt, nullptr, grad, ids, n, 0, stream,                                                               \
                      false);                                                                                                       \
   }                                                                                                                                \
   int kv_apply_##stem##_tok(kv_handle_t v, kv_handle_t opt, const float* grad, const void* ids, int64_t n, KV_GA4_PARAMS,         \
                             kv_batch_token_t token, kv_stream_t stream) {                                                          \
-    return apply_one(group_adam4_call(variant, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), v, opt, nullptr, grad, ids, n, token,      \
+    return apply_one(CALL, v, opt, nullptr, grad, ids, n, token,                                                                   \
                      stream, false);                                                                                               \
   }                                                                                                                                \
   int kv_apply_##stem##_unique(kv_handle_t v, kv_handle_t opt, const float* grad, const void* ids, int64_t n, KV_GA4_PARAMS,      \
                                kv_stream_t stream) {                                                                               \
-    return apply_one(group_adam4_call(variant, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), v, opt, nullptr, grad, ids, n, 0, stream,  \
+    return apply_one(CALL, v, opt, nullptr, grad, ids, n, 0, stream,                                                               \
                      true);                                                                                                        \
   }                                                                                                                                \
   int kv_multi_apply_##stem(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts, const float* const* grads,          \
                             const void* const* ids, const int64_t* ns, KV_GA4_PARAMS, kv_stream_t stream) {                        \
-    return multi_apply(group_adam4_call(variant, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), num_tables, vars, opts, nullptr, grads,  \
+    return multi_apply(CALL, num_tables, vars, opts, nullptr, grads,                                                               \
                        ids, ns, nullptr, stream, false);                                                                           \
   }                                                                                                                                \
   int kv_multi_apply_##stem##_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts, const float* const* grads,    \
                                   const void* const* ids, const int64_t* ns, KV_GA4_PARAMS, const kv_batch_token_t* tokens,        \
                                   kv_stream_t stream) {                                                                            \
-    return multi_apply(group_adam4_call(variant, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), num_tables, vars, opts, nullptr, grads,  \
+    return multi_apply(CALL, num_tables, vars, opts, nullptr, grads,                                                               \
                        ids, ns, tokens, stream, false);                                                                            \
   }                                                                                                                                \
   int kv_multi_apply_##stem##_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,                            \
                                      const float* const* grads, const void* const* ids, const int64_t* ns, KV_GA4_PARAMS,         \
                                      kv_stream_t stream) {                                                                         \
-    return multi_apply(group_adam4_call(variant, lr, b1p, b2p, b1, b2, eps, l1, l2, l21), num_tables, vars, opts, nullptr, grads,  \
+    return multi_apply(CALL, num_tables, vars, opts, nullptr, grads,                                                               \
                        ids, ns, nullptr, stream, true);                                                                            \
   }
-KV_GA4_ENTRIES(group_amsgrad, GA4_AMSGRAD)
-KV_GA4_ENTRIES(group_adabelief, GA4_ADABELIEF)
+#define KV_GA4_HP lr, b1p, b2p, b1, b2, eps, l1, l2, l21
+KV_GA4_ENTRIES(group_amsgrad, group_adam4_call(GA4_AMSGRAD, KV_GA4_HP))
+KV_GA4_ENTRIES(group_adabelief, group_adam4_call(GA4_ADABELIEF, KV_GA4_HP))
+KV_GA4_ENTRIES(group_lamb, group_lamb_call(KV_GA4_HP))
+#undef KV_GA4_HP
 #undef KV_GA4_ENTRIES
 #undef KV_GA4_PARAMS
 

@@ -410,6 +410,17 @@ __device__ __forceinline__ float group_sum(float v) {
   for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, W);
   return v;
 }
+// two sums in one butterfly: each step issues both shuffles before either add, so the two reductions share one chain of
+// log2(W) dependent cross-lane steps (group LAMB's trust ratio: sum r r and sum var var)
+template <int W>
+__device__ __forceinline__ void group_sum2(float& u, float& v) {
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) {
+    const float tu = __shfl_xor(u, o, W), tv = __shfl_xor(v, o, W);
+    u += tu;
+    v += tv;
+  }
+}
 template <int W>
 __device__ __forceinline__ bool group_any(bool p) {
   const unsigned long long m = __ballot(p);
@@ -437,7 +448,7 @@ struct PreRows {
 };
 // The row math and the stores of one key's update, on values the caller already holds: xin = the var row;
 // sin = GroupAdam m | v | z, group RectifiedAdam m | v | linear | vhat | vamsgrad, Adam m | v, Adagrad accum, FTRL accum | linear,
-// group AMSGrad / group AdaBelief m | v | linear | acc.
+// group AMSGrad / group AdaBelief m | v | linear | acc, group LAMB m | v | linear | accum (training_ops.cc:3618-3661).
 // Element e of a row lives at lane
 // (e / V) % LPR, step (e / V) / LPR.  All LPR lanes of every group of the wave call it (shuffles inside); `act`
 // masks groups without an update.  fvp / f0p / f1p = the flag bytes of the var / first / second slot row.
@@ -454,7 +465,7 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
                                          const OptArgs& a, int lane, const float (&xin)[K][V],
                                          const float (&sin)[state_blocks(OPT)][K][V], bool new1 = false, bool vblack = false,
                                          bool sblack = false) {
-  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_GROUP_ADAM4, "opt_core: unknown optimizer");
+  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_GROUP_LAMB, "opt_core: unknown optimizer");
   if (group_adam(OPT)) {
     // training_ops.cc:7166-7195 (V4) / :5895-5925 (V3); slot row = [m | v | z]
     float m[K][V], nv[K][V], sq[K][V], z[K][V], uu[K][V];
@@ -864,6 +875,100 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
     const bool anyx = group_any<LPR>(big), anys = group_any<LPR>(sbig);
     if (act && lane == 0) {
       // CoverUpdateUnsafe -> UpdateUnderThreshold, or MarkBlacklistUnsafe (:1755-1766 / :3202-3213)
+      *fvp = (unsigned char)(upd ? (anyx ? 0u : FLAG_UNDER) : (FLAG_BLACK | FLAG_UNDER));
+      *f0p = (unsigned char)(anys ? 0u : FLAG_UNDER);
+    }
+  } else if (OPT == OPT_GROUP_LAMB) {
+    // OPT_GROUP_LAMB: KvVariableGroupSparseApplyLamb (training_ops.cc:3618-3661, COMPUTE_LAMB); slot row =
+    // [m | v | linear | accum].  lamb_c1 / lamb_c2 = 1 - beta1_power / 1 - beta2_power (host, fp32).
+    // The row is coupled by THREE sums in two rounds: |r| and |var| make the trust ratio, the ratio enters linear, and linear
+    // feeds the l21 norm.  So linear cannot be stored in the first pass as OPT_GROUP_ADAM4 stores it.  Three stages:
+    //   1  m, v, accum are formed and stored (none depends on a norm); the partials of sum r r and sum var var go through
+    //      ONE butterfly, two values per shuffle step (group_sum2): one chain of dependent cross-lane steps, not two
+    //   2  across it live nm, t = ((sqrt(na) - sqrt(accum)) / lr) var, and y = (sqrt(na) + eps) / lr + 2 l2: 3 K V values
+    //      beside the old linear, which is still the caller's sin[2]; linear is formed from the group-uniform ratio and
+    //      stored, u takes nm's place, the second reduction runs
+    //   3  across that one only u and y live, 2 K V values as in OPT_GROUP_ADAM4; the var row or zeros, then the flags
+    float nm[K][V], tt[K][V], yy[K][V];
+    float pr = 0.f, px = 0.f;
+    const float omb1 = 1.f - a.b1, omb2 = 1.f - a.b2, c1 = lamb_c1(a), c2 = lamb_c2(a);
+    const float two_l2 = 2.f * a.l2;
+    const bool fm = KV_FASTM(a);
+    bool big = false, sbig = false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      const bool valid = act && e0 < D;
+      float mn[V], vn[V], na[V];
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        const float xo = valid ? xin[k][c] : 0.f, mo = valid ? sin[0][k][c] : 0.f, vo = valid ? sin[1][k][c] : 0.f;
+        const float ao = valid ? sin[3][k][c] : 0.f;
+        const float gg = gv[k][c];
+        mn[c] = a.b1 * mo + omb1 * gg;
+        vn[c] = a.b2 * vo + omb2 * (gg * gg);
+        nm[k][c] = kv_div(mn[c], c1, fm);
+        na[c] = kv_div(vn[c], c2, fm);
+        const float sq = kv_sqrt(na[c], fm);
+        const float den = sq + a.eps;
+        const float r = kv_div(nm[k][c], den, fm);
+        tt[k][c] = kv_div(sq - kv_sqrt(ao, fm), a.lr, fm) * xo;
+        yy[k][c] = kv_div(den, a.lr, fm) + two_l2;
+        if (valid) {   // (a masked lane adds nothing to either sum: its r may be 0 / 0)
+          pr += r * r;
+          px += xo * xo;
+          sbig |= fabsf(mn[c]) >= CUTOFF || fabsf(vn[c]) >= CUTOFF || fabsf(na[c]) >= CUTOFF;
+        }
+      }
+      if (valid) {
+        stv<V>(s0row + e0, mn);
+        stv<V>(s0row + e0 + D, vn);
+        stv<V>(s0row + e0 + 3 * D, na);   // accum = new_accum (:3653)
+      }
+    }
+    group_sum2<LPR>(pr, px);
+    const float rnorm = kv_sqrt(pr, fm), xnorm = kv_sqrt(px, fm);
+    // :3630-3633; uniform over the lane group
+    const float ratio = (rnorm > 0.f && xnorm > 0.f) ? kv_div(xnorm, rnorm + 1e-8f, fm) : 1.f;
+    float part = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      const bool valid = act && e0 < D;
+      float zn[V];
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        const float zo = valid ? sin[2][k][c] : 0.f;
+        zn[c] = zo + (nm[k][c] * ratio - tt[k][c]);
+        const float adj = fmaxf(fminf(zn[c], a.l1), -a.l1);
+        nm[k][c] = adj - zn[c];   // u
+        if (valid) {
+          part += nm[k][c] * nm[k][c];
+          sbig |= fabsf(zn[c]) >= CUTOFF;
+        }
+      }
+      if (valid) stv<V>(s0row + e0 + 2 * D, zn);
+    }
+    const float norm = kv_sqrt(group_sum<LPR>(part), fm);
+    const bool upd = norm > a.l21_norm;
+    const float scale = 1.f - kv_div(a.l21_norm, norm, fm);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      if (act && e0 < D) {
+        float xn[V];
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+          xn[c] = 0.f;  // blacklist: the row reads as zeros (table_manager.h:335-357)
+          if (upd) xn[c] = kv_div(nm[k][c] * scale, yy[k][c], fm);
+          big |= fabsf(xn[c]) >= CUTOFF;
+        }
+        stv<V>(xrow + e0, xn);
+      }
+    }
+    const bool anyx = group_any<LPR>(big), anys = group_any<LPR>(sbig);
+    if (act && lane == 0) {
+      // CoverUpdateUnsafe -> UpdateUnderThreshold, or MarkBlacklistUnsafe (:3647-3661)
       *fvp = (unsigned char)(upd ? (anyx ? 0u : FLAG_UNDER) : (FLAG_BLACK | FLAG_UNDER));
       *f0p = (unsigned char)(anys ? 0u : FLAG_UNDER);
     }

@@ -12,7 +12,7 @@ namespace __attribute__((visibility("hidden"))) kvhip_internal {
 enum Mode { MODE_LOOKUP = 0, MODE_APPLY = 1, MODE_DEDUP = 2, MODE_SCATTER = 3, MODE_MARK = 4, MODE_UNIQUE = 5,
             MODE_APPLYIDX = 6 };
 enum Opt { OPT_ADAM_V4 = 0, OPT_ADAM_V3 = 1, OPT_ADAGRAD = 2, OPT_FTRL = 3, OPT_FTRL_V2 = 4, OPT_GROUP_FTRL_V2 = 5,
-           OPT_GROUP_RADAM = 6, OPT_ADAM = 7, OPT_RADAM = 8, OPT_GROUP_ADAM4 = 9 };
+           OPT_GROUP_RADAM = 6, OPT_ADAM = 7, OPT_RADAM = 8, OPT_GROUP_ADAM4 = 9, OPT_GROUP_LAMB = 10 };
 // What the pipelines ask of an optimizer, in one place (a new OPT_* must answer each of them):
 // GroupAdam: one slot table of three dim-wide blocks (m | v | z)
 constexpr bool group_adam(int opt) { return opt == OPT_ADAM_V4 || opt == OPT_ADAM_V3; }
@@ -33,9 +33,10 @@ constexpr bool scatter_chain(int opt) { return opt == OPT_ADAM || opt == OPT_RAD
 constexpr bool chain_gathers_var(int opt) { return opt == OPT_RADAM; }
 // dim-wide blocks of the first slot row (group RectifiedAdam: m | v | linear | vhat | vamsgrad; Adam: m | v; RectifiedAdam:
 // m | v | vhat; group AMSGrad / group AdaBelief, OPT_GROUP_ADAM4: m | v | linear | acc — a group op like group
-// RectifiedAdam, so none of group_adam, two_slots, keeps_var_flags, scatter_chain)
+// RectifiedAdam, so none of group_adam, two_slots, keeps_var_flags, scatter_chain; group LAMB, OPT_GROUP_LAMB: m | v |
+// linear | accum, the same row and the same answers)
 constexpr int slot0_blocks(int opt) {
-  return opt == OPT_GROUP_RADAM ? 5 : opt == OPT_GROUP_ADAM4 ? 4 : (group_adam(opt) || opt == OPT_RADAM) ? 3 : opt == OPT_ADAM ? 2 : 1;
+  return opt == OPT_GROUP_RADAM ? 5 : (opt == OPT_GROUP_ADAM4 || opt == OPT_GROUP_LAMB) ? 4 : (group_adam(opt) || opt == OPT_RADAM) ? 3 : opt == OPT_ADAM ? 2 : 1;
 }
 // one wide slot table whose dim is a multiple of the var's (what the ops' initialisation and shape checks ask)
 constexpr bool wide_slot(int opt) { return slot0_blocks(opt) > 1; }
@@ -203,6 +204,11 @@ __host__ __device__ inline float& ga4_c2(OptArgs& a) { return a.alpha; }
 __host__ __device__ inline float ga4_c2(const OptArgs& a) { return a.alpha; }
 __host__ __device__ inline int& ga4_variant(OptArgs& a) { return a.update_slots; }
 __host__ __device__ inline int ga4_variant(const OptArgs& a) { return a.update_slots; }
+// ... and group LAMB's (OPT_GROUP_LAMB; lr, b1, b2, eps, l1, l2, l21 as named): 1 - beta1_power and 1 - beta2_power (host, fp32)
+__host__ __device__ inline float& lamb_c1(OptArgs& a) { return a.lr_power; }
+__host__ __device__ inline float lamb_c1(const OptArgs& a) { return a.lr_power; }
+__host__ __device__ inline float& lamb_c2(OptArgs& a) { return a.alpha; }
+__host__ __device__ inline float lamb_c2(const OptArgs& a) { return a.alpha; }
 // The vhat block (2) of RectifiedAdam's slot row takes part under amsgrad only: a wave-uniform test in front of its loads
 // and stores, so that the step without amsgrad moves two slot blocks.  Every other optimizer: all of its blocks, always
 // (the test folds away)

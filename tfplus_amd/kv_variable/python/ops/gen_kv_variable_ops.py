@@ -235,7 +235,7 @@ def _layout_args(stem, per, scalars):
 
 # floats the library reads from hp per optimizer code (kvhip.h kv_shard_apply_serve).  The C ABI takes a bare pointer, so the
 # length is checked here, where it is known: a vector in another family's layout is refused, not read past its end
-_HP_LEN = {0: 9, 1: 9, 2: 2, 3: 6, 4: 5, 5: 5, 6: 13, 7: 6, 8: 11, 9: 10}
+_HP_LEN = {0: 9, 1: 9, 2: 2, 3: 6, 4: 5, 5: 5, 6: 13, 7: 6, 8: 11, 9: 10, 10: 9}
 
 
 def _hp_array(hp, optimizer=None):
@@ -250,7 +250,7 @@ def _hp_array(hp, optimizer=None):
 # stem of an optimizer family + its scalars (the order of _lib.OPT_FAMILIES) -> the optimizer code and hp vector of the
 # generic entry points (the OPT_* codes below; GroupAdam's trailing scalar is its version)
 _COUNTED_CODE = {"adagrad": 2, "sparse_group_ftrl": 3, "ftrl_v2": 4, "group_ftrl_v2": 5, "group_rectified_adam": 6,
-                 "adam": 7, "rectified_adam": 8, "radam": 8}       # ("radam": the short name of OPT_RADAM's family)
+                 "adam": 7, "rectified_adam": 8, "radam": 8, "group_lamb": 10}       # ("radam": the short name of OPT_RADAM's family)
 # OPT_GROUP_ADAM4's two stems share code 9: the stem becomes the variant, the last float of hp
 _GROUP_ADAM4_VARIANT = {"group_amsgrad": 0, "group_adabelief": 1}
 
@@ -377,6 +377,16 @@ def kv_variable_group_sparse_apply_adabelief(var, opt, grad, indices, lr, beta1_
   """REGISTER_OP("KvVariableGroupSparseApplyAdaBelief") (kernels/training_ops.cc:2982-3251): `opt` is one slot table of dim
   4 x the var's, m | v | linear | accum (kvhip.h kv_apply_group_adabelief: group AMSGrad's kernels, a run-time flag apart)."""
   _apply("group_adabelief", (var, opt), grad, indices, (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21),
+         unique_indices, token, unique_count)
+
+
+def kv_variable_group_sparse_apply_lamb(var, opt, grad, indices, lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2,
+                                        l21, use_locking=False, name=None, unique_indices=False, token=None,
+                                        unique_count=None):
+  """REGISTER_OP("KvVariableGroupSparseApplyLamb") (kernels/training_ops.cc:3400-3683): the reference's four slot variables
+  are ONE slot table `opt` of dim 4 x the var's, m | v | linear | accum (kvhip.h kv_apply_group_lamb: the per-row trust
+  ratio |var| / |r| scales the step that enters linear).  token: as kv_variable_group_sparse_apply_rectified_adam's."""
+  _apply("group_lamb", (var, opt), grad, indices, (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21),
          unique_indices, token, unique_count)
 
 
@@ -841,6 +851,13 @@ def kv_multi_group_sparse_apply_adabelief(var_handles, opt_handles, grads, indic
                (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21), unique_indices)
 
 
+def kv_multi_group_sparse_apply_lamb(var_handles, opt_handles, grads, indices, lr, beta1_power, beta2_power, beta1, beta2,
+                                     epsilon, l1, l2, l21, unique_indices=False):
+  """KvVariableGroupSparseApplyLamb on many (var, opt) pairs with two kernel launches (one with unique_indices)."""
+  _multi_apply("group_lamb", "vars, opts, grads and indices", (var_handles, opt_handles), grads, indices,
+               (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21), unique_indices)
+
+
 def kv_multi_sparse_apply_adam(var_handles, m_v_handles, grads, indices, lr, beta1_power, beta2_power, beta1, beta2,
                                epsilon, unique_indices=False):
   """kv_variable_sparse_apply_adam on many (var, m_v) pairs with two kernel launches (one with unique_indices)."""
@@ -1178,6 +1195,7 @@ OPT_RADAM = 8  # slots = (opt,): m | v | vhat
 # group AMSGrad / group AdaBelief: hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, variant (0 AMSGrad,
 # 1 AdaBelief); slots = (opt,): m | v | linear | acc
 OPT_GROUP_ADAM4 = 9
+OPT_GROUP_LAMB = 10   # hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21; slots = (opt,): m | v | linear | accum
 
 
 class KvComm(object):
