@@ -357,7 +357,7 @@ int kv_dedup_segment_sum_dev(kv_handle_t h, const void* ids, const float* grad, 
 /* kv_apply_<optimizer>_unique with the id count taken from the DEVICE: the op is applied to the first
  * min(n_max, *n_dev) ids and gradient rows, *n_dev (int64, device memory — kv_dedup_segment_sum_dev's or kv_unique's
  * num_unique_dev) being read by the kernel when it runs.  `optimizer`, `hp` and `slot1` are kv_shard_apply_serve's
- * codes and layouts (0 .. 10, below).  The same promise of unique ids, the same duplicate guard, checks, results and slot
+ * codes and layouts (0 .. 11, below).  The same promise of unique ids, the same duplicate guard, checks, results and slot
  * mirror handling as the _unique ops: the same bits.  `ids` [n_max] are KV_DT_INT64 or KV_DT_INT32 (ids_dtype) whatever
  * the table's key dtype — the dedup writes int64 ids for every table.  `grad` is [n_max, dim].
  * The host sizes everything by n_max: the tables' capacity (their row bounds advance by n_max per call, so a table
@@ -378,7 +378,7 @@ int kv_apply_unique_counted(kv_handle_t var, int optimizer, kv_handle_t slot0, k
  * those back to sum them per distinct id — writes and reads n * dim * 4 bytes that carry no information; here the tile sums and
  * the partition pass + update fetch a position's row from the segment gradients themselves, through per-position records
  * (segment, scale: 8 bytes a position) that a small pre-pass leaves in the var table's workspace.  The values buffer is never
- * allocated.  `optimizer`, `slot0`, `slot1` and `hp` are kv_shard_apply_serve's codes and layouts (0 .. 10, below), validated as
+ * allocated.  `optimizer`, `slot0`, `slot1` and `hp` are kv_shard_apply_serve's codes and layouts (0 .. 11, below), validated as
  * kv_apply_unique_counted validates them: the hyperparameter checks, their order and their wording are the named ops'.
  *   kv_apply_sparse        seg_grad [num_segments, dim], ids [n] of the table's key dtype, segment_ids [n] int32 or int64,
  *                          weights [n] or NULL: kv_lookup_sparse's arguments of the batch.  n == 0: a no-op, KV_OK.
@@ -865,6 +865,76 @@ int kv_multi_apply_group_lamb_unique(int num_tables, const kv_handle_t* vars, co
                                      float beta1_power, float beta2_power, float beta1, float beta2, float epsilon, float l1,
                                      float l2, float l21, kv_stream_t stream);
 
+/* Group Momentum: KvVariableGroupSparseApplyMomentum (kernels/training_ops.cc:2274-2508; row math :2451-2482,
+ * COMPUTE_MOMENTUM).  The reference keeps three slot variables beside the var; here `opt` is ONE slot table of dim 3 x the
+ * var's: [accum | linear | m], a row of zeros at first.  Per distinct id, g = the id's summed gradient row, every operation
+ * one fp32 rounding, in the reference's order:
+ *   m = m momentum + g;  with use_nesterov: m = m momentum + g once more.  M = m
+ *   linear = linear + (M - ((1 - sqrt(accum)) / lr) var)            (new_accum is the constant 1)
+ *   u = clamp(linear, -l1, l1) - linear;  norm = sqrt(sum u u)
+ *   norm > l21 sqrt(dim):  var = (u (1 - l21 sqrt(dim) / norm)) / (1 / lr + 2 l2), CoverUpdate      (no epsilon)
+ *   else:                  the var is blacklisted (MarkBlacklist): it reads as zeros
+ *   accum = 1;  all three blocks are written on either branch
+ * M is the STORED m: the reference's `auto new_m = m;` (:2453) copies a TensorMap, not the values, so the nesterov line
+ * (:2455) writes through into the m slot — the m kept is the twice-updated one, and that same value enters linear.
+ * Bookkeeping as kv_apply_group_amsgrad: the var's enter-threshold filter, FindOrInsert on the slot row, CoverUpdate flags of
+ * the slot row from all three blocks, every id marked in both delta lists.
+ * KV_INVALID_ARGUMENT for lr <= 0, negative l1 / l2 / l21, a momentum outside [0, 1), a use_nesterov other than 0 or 1,
+ * var == opt, an opt dim other than 3 x the var's ("opt must be 3x") and tables on different devices;
+ * KV_FAILED_PRECONDITION for an uninitialised table.
+ * Dims, limits, graph capture, deterministic modes, fast math and delta tracking as kv_apply_group_adam.
+ * _unique / _tok: the forms of kv_apply_group_adam_unique / _tok. */
+int kv_apply_group_momentum(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                            float momentum, float l1, float l2, float l21, int use_nesterov, kv_stream_t stream);
+int kv_apply_group_momentum_tok(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                                float momentum, float l1, float l2, float l21, int use_nesterov, kv_batch_token_t token,
+                                kv_stream_t stream);
+int kv_apply_group_momentum_unique(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                                   float momentum, float l1, float l2, float l21, int use_nesterov, kv_stream_t stream);
+/* ... on many (var, opt) pairs of one dim, shaped like kv_multi_apply_group_amsgrad[_tok|_unique]. */
+int kv_multi_apply_group_momentum(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts, const float* const* grads,
+                                  const void* const* ids, const int64_t* ns, float lr, float momentum, float l1, float l2,
+                                  float l21, int use_nesterov, kv_stream_t stream);
+int kv_multi_apply_group_momentum_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                      const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                      float momentum, float l1, float l2, float l21, int use_nesterov,
+                                      const kv_batch_token_t* tokens, kv_stream_t stream);
+int kv_multi_apply_group_momentum_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                         const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                         float momentum, float l1, float l2, float l21, int use_nesterov, kv_stream_t stream);
+
+/* Group Adadelta: KvVariableGroupSparseApplyAdadelta (kernels/training_ops.cc:2005-2253; row math :2193-2226,
+ * COMPUTE_ADADELTA).  The same kernels as kv_apply_group_momentum's, a run-time variant apart; `opt` = [accum | linear |
+ * accum_update], a row of zeros at first.  The row math in front of the shared tail:
+ *   na = accum rho + (1 - rho) (g g)
+ *   M  = sqrt(accum_update + epsilon) g
+ *   linear = linear + (M - ((sqrt(na) - sqrt(accum)) / lr) var)
+ *   the tail as above with the denominator sqrt(na + epsilon) / lr + 2 l2
+ *   accum = na
+ *   na2 = na rho + (1 - rho) (g g)
+ *   accum_update = accum_update rho + ((1 - rho) (M M)) / (na2 + epsilon)
+ * The last denominator holds na2, the decay applied a SECOND time, not na: new_accum (:2194) is a lazy Eigen expression over
+ * the accum map, and :2220 reads it again after :2217 has assigned accum = new_accum.  1 - rho is computed once on the host,
+ * in fp32.  Everything else — bookkeeping, forms, and the checks with rho outside [0, 1) and epsilon <= 0 refused
+ * (KV_INVALID_ARGUMENT) in place of momentum and use_nesterov — as kv_apply_group_momentum. */
+int kv_apply_group_adadelta(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                            float rho, float epsilon, float l1, float l2, float l21, kv_stream_t stream);
+int kv_apply_group_adadelta_tok(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                                float rho, float epsilon, float l1, float l2, float l21, kv_batch_token_t token,
+                                kv_stream_t stream);
+int kv_apply_group_adadelta_unique(kv_handle_t var, kv_handle_t opt, const float* grad, const void* ids, int64_t n, float lr,
+                                   float rho, float epsilon, float l1, float l2, float l21, kv_stream_t stream);
+int kv_multi_apply_group_adadelta(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts, const float* const* grads,
+                                  const void* const* ids, const int64_t* ns, float lr, float rho, float epsilon, float l1,
+                                  float l2, float l21, kv_stream_t stream);
+int kv_multi_apply_group_adadelta_tok(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                      const float* const* grads, const void* const* ids, const int64_t* ns, float lr, float rho,
+                                      float epsilon, float l1, float l2, float l21, const kv_batch_token_t* tokens,
+                                      kv_stream_t stream);
+int kv_multi_apply_group_adadelta_unique(int num_tables, const kv_handle_t* vars, const kv_handle_t* opts,
+                                         const float* const* grads, const void* const* ids, const int64_t* ns, float lr,
+                                         float rho, float epsilon, float l1, float l2, float l21, kv_stream_t stream);
+
 
 /* embedding_lookup_sparse on a KvVariable (python/ops/embedding_ops.py:279-441), fused: the
  * reference runs unique_with_counts -> GatherOrInsert[WithCounts] -> gather(idx) -> (x weights) ->
@@ -1118,7 +1188,10 @@ int kv_shard_apply_route(kv_shard_t shard, const float* grad, kv_stream_t stream
  * beta1, beta2, epsilon, l1, l2, l21, variant — 0 AMSGrad, 1 AdaBelief, anything else KV_INVALID_ARGUMENT; slot0 = opt,
  * slot1 unused),
  * 10 group LAMB (kv_apply_group_lamb; hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21; slot0 = opt,
- * slot1 unused) */
+ * slot1 unused),
+ * 11 group Momentum / group Adadelta (kv_apply_group_momentum / kv_apply_group_adadelta; hp = lr, decay, epsilon, l1, l2,
+ * l21, variant — decay = momentum or rho; variant 0 Momentum, 1 Momentum with use_nesterov, 2 Adadelta, anything else
+ * KV_INVALID_ARGUMENT; Momentum ignores epsilon; slot0 = opt, slot1 unused) */
 int kv_shard_apply_serve(kv_shard_t shard, int optimizer, kv_handle_t slot0, kv_handle_t slot1, const float* hp,
                          kv_stream_t stream);
 int kv_shard_lookup(kv_shard_t shard, kv_comm_t comm, const void* ids, int64_t n, float* out, int join,

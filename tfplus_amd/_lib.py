@@ -154,6 +154,8 @@ OPT_FAMILIES = {
     "group_amsgrad": (2, "gin" + "f" * 9),                    # lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21
     "group_adabelief": (2, "gin" + "f" * 9),                  # (one kernel family, OPT_GROUP_ADAM4: the stem is the variant)
     "group_lamb": (2, "gin" + "f" * 9),                       # the same nine scalars (OPT_GROUP_LAMB)
+    "group_momentum": (2, "gin" + "f" * 5 + "b"),             # lr, momentum, l1, l2, l21, use_nesterov
+    "group_adadelta": (2, "gin" + "f" * 6),                   # lr, rho, epsilon, l1, l2, l21 (one kernel family, OPT_GROUP_ACC3)
 }
 _ARG = {"g": _vp, "i": _vp, "f": _f, "b": _i32}
 for _stem, (_handles, _layout) in OPT_FAMILIES.items():

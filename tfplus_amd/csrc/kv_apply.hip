@@ -1,6 +1,6 @@
 // kv_apply.hip — the optimizer layer of the C ABI on the table core (kv_host.h): one parser per optimizer family, the two
 // bodies (apply_one: one table; multi_apply: many tables, one launch per stage; the PartArgs of all their launches start
-// from opt_part_args), the 66 kv_apply_* / kv_multi_apply_* entry points, kv_[multi_]apply_sparse (the same bodies fed from
+// from opt_part_args), the 78 kv_apply_* / kv_multi_apply_* entry points, kv_[multi_]apply_sparse (the same bodies fed from
 // segment gradients) and kv_attach_slot.  It compiles no kernel: the
 // optimizers' kernels are reached through the typed launchers of kv_launch.h, the pipelines' through the core's.
 #include <hip/hip_runtime.h>
@@ -145,6 +145,8 @@ static WideSlotWords wide_slot_words(int opt) {
     case OPT_RADAM: return {"opt", "var and opt do not have matching shapes [%d] [%d] (opt must be 3x)", ": opt must be 3x", true};
     case OPT_GROUP_ADAM4: case OPT_GROUP_LAMB:
       return {"opt", "kv_variable and opt do not have the same shape [%d] [%d] (opt must be 4x)", ": opt must be 4x", true};
+    case OPT_GROUP_ACC3:
+      return {"opt", "kv_variable and opt do not have the same shape [%d] [%d] (opt must be 3x)", ": opt must be 3x", true};
     default: return {"slot", "var and slot do not have matching shapes [%d] [%d]", "", false};
   }
 }
@@ -601,6 +603,48 @@ static OptCall group_lamb_call(float lr, float b1p, float b2p, float b1, float b
   return c;
 }
 
+// Group Momentum (training_ops.cc:2274-2508; row math :2451-2482) and group Adadelta (:2005-2253; :2193-2226), one kernel
+// family: slot row = accum | linear | m / accum_update, `variant` (ACC3_*) the run-time value between them.  The reference
+// checks lr, l1, l2 and l21 (check_hp); a decay outside [0, 1) makes a growing average and Adadelta's epsilon <= 0 roots and
+// divides by zero on a new row, so they are refused here.  decay = momentum or rho; 1 - rho once, in fp32.  Momentum
+// ignores eps
+static OptCall group_acc3_call(int variant, float lr, float decay, float eps, float l1, float l2, float l21) {
+  OptCall c;
+  c.opt = OPT_GROUP_ACC3;
+  c.slot_mult = slot0_blocks(OPT_GROUP_ACC3);
+  if (variant != ACC3_MOMENTUM && variant != ACC3_NESTEROV && variant != ACC3_ADADELTA) {
+    c.status = fail(KV_INVALID_ARGUMENT, "variant %d: 0 (group Momentum), 1 (group Momentum, nesterov) or 2 (group Adadelta)", variant);
+    return c;
+  }
+  const bool adadelta = variant == ACC3_ADADELTA;
+  if ((c.status = check_hp(lr, l1, l2, l21, 0.f, 0.f))) return c;
+  if (!(decay >= 0.f && decay < 1.f)) {
+    c.status = fail(KV_INVALID_ARGUMENT, "%s is not in [0, 1): %g", adadelta ? "rho" : "momentum", decay);
+    return c;
+  }
+  if (adadelta && !(eps > 0.f)) { c.status = fail(KV_INVALID_ARGUMENT, "epsilon is not a positive scalar: %g", eps); return c; }
+  OptArgs& a = c.a;
+  a.lr = lr; a.eps = adadelta ? eps : 0.f;
+  a.l1 = l1; a.l2 = l2; a.l21 = l21;
+  acc3_decay(a) = decay;
+  acc3_omr(a) = 1.f - decay;
+  acc3_variant(a) = variant;
+  return c;
+}
+// use_nesterov of the named entries: 0 or 1; anything else goes on as variant -1 after its own message
+static OptCall group_momentum_call(float lr, float momentum, float l1, float l2, float l21, int use_nesterov) {
+  if (use_nesterov != 0 && use_nesterov != 1) {
+    OptCall c;
+    c.opt = OPT_GROUP_ACC3;
+    c.slot_mult = slot0_blocks(OPT_GROUP_ACC3);
+    c.status = fail(KV_INVALID_ARGUMENT, "use_nesterov %d: 0 or 1", use_nesterov);
+    return c;
+  }
+  return group_acc3_call(use_nesterov ? ACC3_NESTEROV : ACC3_MOMENTUM, lr, momentum, 0.f, l1, l2, l21);
+}
+// the variant in the generic entries' float vector: 0, 1 or 2 exactly; anything else goes on as -1, which the call refuses
+static int hp_acc3_variant(float f) { return f == 0.f ? ACC3_MOMENTUM : f == 1.f ? ACC3_NESTEROV : f == 2.f ? ACC3_ADADELTA : -1; }
+
 // the one place where a runtime OPT_* becomes the template argument of the pipelines
 template <class F>
 static int with_opt(int opt, F&& f) {
@@ -616,6 +660,7 @@ static int with_opt(int opt, F&& f) {
     case OPT_RADAM: return f(std::integral_constant<int, OPT_RADAM>());
     case OPT_GROUP_ADAM4: return f(std::integral_constant<int, OPT_GROUP_ADAM4>());
     case OPT_GROUP_LAMB: return f(std::integral_constant<int, OPT_GROUP_LAMB>());
+    case OPT_GROUP_ACC3: return f(std::integral_constant<int, OPT_GROUP_ACC3>());
     default: return fail(KV_INTERNAL, "optimizer %d", opt);
   }
 }
@@ -634,7 +679,9 @@ namespace __attribute__((visibility("hidden"))) kvhip_internal {
 // use_nesterov; the three flags as 0 / 1; slot0 = opt),
 // 9 group AMSGrad / group AdaBelief (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, variant: 0 AMSGrad,
 // 1 AdaBelief; slot0 = opt),
-// 10 group LAMB (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21; slot0 = opt)
+// 10 group LAMB (hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21; slot0 = opt),
+// 11 group Momentum / group Adadelta (hp = lr, decay, epsilon, l1, l2, l21, variant: 0 Momentum, 1 Momentum with nesterov,
+// 2 Adadelta; decay = momentum or rho; Momentum ignores epsilon; slot0 = opt)
 OptCall shard_opt_call(int optimizer, const float* hp) {
   switch (optimizer) {
     case OPT_ADAM_V4: case OPT_ADAM_V3:
@@ -651,6 +698,7 @@ OptCall shard_opt_call(int optimizer, const float* hp) {
     case OPT_GROUP_ADAM4:
       return group_adam4_call(hp_variant(hp[9]), hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8]);
     case OPT_GROUP_LAMB: return group_lamb_call(hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8]);
+    case OPT_GROUP_ACC3: return group_acc3_call(hp_acc3_variant(hp[6]), hp[0], hp[1], hp[2], hp[3], hp[4], hp[5]);
     default: return OptCall{};
   }
 }
@@ -918,6 +966,14 @@ KV_GA4_ENTRIES(group_amsgrad, group_adam4_call(GA4_AMSGRAD, KV_GA4_HP))
 KV_GA4_ENTRIES(group_adabelief, group_adam4_call(GA4_ADABELIEF, KV_GA4_HP))
 KV_GA4_ENTRIES(group_lamb, group_lamb_call(KV_GA4_HP))
 #undef KV_GA4_HP
+// group Momentum and group Adadelta: the same six forms over their own scalars (KV_GA4_PARAMS is read where the entries
+// expand, so it is redefined per stem)
+#undef KV_GA4_PARAMS
+#define KV_GA4_PARAMS float lr, float momentum, float l1, float l2, float l21, int use_nesterov
+KV_GA4_ENTRIES(group_momentum, group_momentum_call(lr, momentum, l1, l2, l21, use_nesterov))
+#undef KV_GA4_PARAMS
+#define KV_GA4_PARAMS float lr, float rho, float eps, float l1, float l2, float l21
+KV_GA4_ENTRIES(group_adadelta, group_acc3_call(ACC3_ADADELTA, lr, rho, eps, l1, l2, l21))
 #undef KV_GA4_ENTRIES
 #undef KV_GA4_PARAMS
 

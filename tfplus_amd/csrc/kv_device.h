@@ -448,7 +448,8 @@ struct PreRows {
 };
 // The row math and the stores of one key's update, on values the caller already holds: xin = the var row;
 // sin = GroupAdam m | v | z, group RectifiedAdam m | v | linear | vhat | vamsgrad, Adam m | v, Adagrad accum, FTRL accum | linear,
-// group AMSGrad / group AdaBelief m | v | linear | acc, group LAMB m | v | linear | accum (training_ops.cc:3618-3661).
+// group AMSGrad / group AdaBelief m | v | linear | acc, group LAMB m | v | linear | accum (training_ops.cc:3618-3661),
+// group Momentum accum | linear | m and group Adadelta accum | linear | accum_update (:2451-2482, :2193-2226).
 // Element e of a row lives at lane
 // (e / V) % LPR, step (e / V) / LPR.  All LPR lanes of every group of the wave call it (shuffles inside); `act`
 // masks groups without an update.  fvp / f0p / f1p = the flag bytes of the var / first / second slot row.
@@ -465,7 +466,7 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
                                          const OptArgs& a, int lane, const float (&xin)[K][V],
                                          const float (&sin)[state_blocks(OPT)][K][V], bool new1 = false, bool vblack = false,
                                          bool sblack = false) {
-  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_GROUP_LAMB, "opt_core: unknown optimizer");
+  static_assert(OPT >= OPT_ADAM_V4 && OPT <= OPT_GROUP_ACC3, "opt_core: unknown optimizer");
   if (group_adam(OPT)) {
     // training_ops.cc:7166-7195 (V4) / :5895-5925 (V3); slot row = [m | v | z]
     float m[K][V], nv[K][V], sq[K][V], z[K][V], uu[K][V];
@@ -969,6 +970,92 @@ __device__ __forceinline__ void opt_core(float* xrow, float* s0row, float* s1row
     const bool anyx = group_any<LPR>(big), anys = group_any<LPR>(sbig);
     if (act && lane == 0) {
       // CoverUpdateUnsafe -> UpdateUnderThreshold, or MarkBlacklistUnsafe (:3647-3661)
+      *fvp = (unsigned char)(upd ? (anyx ? 0u : FLAG_UNDER) : (FLAG_BLACK | FLAG_UNDER));
+      *f0p = (unsigned char)(anys ? 0u : FLAG_UNDER);
+    }
+  } else if (OPT == OPT_GROUP_ACC3) {
+    // OPT_GROUP_ACC3: KvVariableGroupSparseApplyMomentum (training_ops.cc:2451-2482, COMPUTE_MOMENTUM) and ...Adadelta
+    // (:2193-2226, COMPUTE_ADADELTA), one family: slot row = [accum | linear | third], third = m / accum_update.  Block 1 is
+    // linear in both, so the l1 / l21 tail is one piece of code; what differs sits behind the wave-uniform acc3_variant(a).
+    // acc3_decay = momentum / rho, acc3_omr = 1 - rho (host, fp32).  Two aliasing facts of the reference, restated here:
+    //   Momentum  `auto new_m = m;` copies the TensorMap, not the values: nesterov's second m mu + g writes through into the m
+    //             slot, so the STORED m is the twice-updated one and the same value enters linear
+    //   Adadelta  new_accum is a lazy expression over the accum map and is read again after `accum = new_accum`: the
+    //             denominator of accum_update's second term is the decay applied a second time, na2 = na rho + (1 - rho) g g
+    // Momentum's new_accum is the constant 1: sqrt(1) is 1, y = 1 / lr + 2 l2 is uniform, and its path has one root
+    // (sqrt(accum)), no epsilon and no per-element division but linear's.  Adadelta's has four roots and two divisions more.
+    // Two passes around the row norm, as OPT_GROUP_ADAM4: no slot block depends on the norm (the reference writes all three
+    // on both branches), so the first pass stores them as it forms them and only u and y, 2 K V values, cross the group_sum
+    float uu[K][V], yy[K][V];
+    float part = 0.f;
+    const float dec = acc3_decay(a), omr = acc3_omr(a);
+    const float two_l2 = 2.f * a.l2;
+    const bool fm = KV_FASTM(a);
+    const int variant = acc3_variant(a);
+    const bool adadelta = variant == ACC3_ADADELTA, nesterov = variant == ACC3_NESTEROV;
+    const float ym = kv_div(1.f, a.lr, fm) + two_l2;   // Momentum's denominator (:2467)
+    bool big = false, sbig = false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      const bool valid = act && e0 < D;
+      float an[V], zn[V], tn[V];
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        const float xo = valid ? xin[k][c] : 0.f, ao = valid ? sin[0][k][c] : 0.f, zo = valid ? sin[1][k][c] : 0.f;
+        const float to = valid ? sin[2][k][c] : 0.f;
+        const float gg = gv[k][c];
+        float mm, dsq;   // what enters linear: the step M and sqrt(new_accum) - sqrt(accum)
+        if (adadelta) {
+          const float t = omr * (gg * gg);
+          an[c] = ao * dec + t;
+          mm = kv_sqrt(to + a.eps, fm) * gg;
+          dsq = kv_sqrt(an[c], fm) - kv_sqrt(ao, fm);
+          yy[k][c] = kv_div(kv_sqrt(an[c] + a.eps, fm), a.lr, fm) + two_l2;
+          const float na2 = an[c] * dec + t;   // new_accum read after accum = new_accum (:2217-2220)
+          tn[c] = to * dec + kv_div(omr * (mm * mm), na2 + a.eps, fm);
+        } else {
+          mm = to * dec + gg;
+          if (nesterov) mm = mm * dec + gg;    // written through into m (:2453-2455)
+          an[c] = 1.f;
+          dsq = 1.f - kv_sqrt(ao, fm);
+          yy[k][c] = ym;
+          tn[c] = mm;
+        }
+        zn[c] = zo + (mm - kv_div(dsq, a.lr, fm) * xo);
+        const float adj = fmaxf(fminf(zn[c], a.l1), -a.l1);
+        uu[k][c] = adj - zn[c];
+        if (valid) {   // (a masked lane adds nothing)
+          part += uu[k][c] * uu[k][c];
+          sbig |= fabsf(an[c]) >= CUTOFF || fabsf(zn[c]) >= CUTOFF || fabsf(tn[c]) >= CUTOFF;
+        }
+      }
+      if (valid) {
+        stv<V>(s0row + e0, an);
+        stv<V>(s0row + e0 + D, zn);
+        stv<V>(s0row + e0 + 2 * D, tn);
+      }
+    }
+    const float norm = kv_sqrt(group_sum<LPR>(part), fm);
+    const bool upd = norm > a.l21_norm;
+    const float scale = 1.f - kv_div(a.l21_norm, norm, fm);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e0 = (lane + k * LPR) * V;
+      if (act && e0 < D) {
+        float xn[V];
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+          xn[c] = 0.f;  // blacklist: the row reads as zeros (table_manager.h:335-357)
+          if (upd) xn[c] = kv_div(uu[k][c] * scale, yy[k][c], fm);
+          big |= fabsf(xn[c]) >= CUTOFF;
+        }
+        stv<V>(xrow + e0, xn);
+      }
+    }
+    const bool anyx = group_any<LPR>(big), anys = group_any<LPR>(sbig);
+    if (act && lane == 0) {
+      // CoverUpdateUnsafe -> UpdateUnderThreshold, or MarkBlacklistUnsafe (:2469-2475 / :2210-2215)
       *fvp = (unsigned char)(upd ? (anyx ? 0u : FLAG_UNDER) : (FLAG_BLACK | FLAG_UNDER));
       *f0p = (unsigned char)(anys ? 0u : FLAG_UNDER);
     }

@@ -49,6 +49,7 @@ KV_OPT_LAUNCHERS(OPT_ADAM);            // kv_opt_adam.hip
 KV_OPT_LAUNCHERS(OPT_RADAM);           // kv_opt_radam.hip
 KV_OPT_LAUNCHERS(OPT_GROUP_ADAM4);     // kv_opt_group_adam4.hip
 KV_OPT_LAUNCHERS(OPT_GROUP_LAMB);      // kv_opt_group_lamb.hip
+KV_OPT_LAUNCHERS(OPT_GROUP_ACC3);      // kv_opt_group_acc3.hip
 
 // ---- optimizer-free (kv_sums.hip) --------------------------------------------------------------------------------------
 // k_tsum (kv_fused.h): the tile sums in front of k_papply

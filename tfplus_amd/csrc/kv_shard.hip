@@ -1005,7 +1005,7 @@ static int shards_apply(const char* what, bool single, const kv_shard_t* shards,
   for (const auto& grp : groups_of(ntab, [&](int k) {
          const kv_shard* sh = shards[k];
          const BatchIndex::Plan served = sh->table->batch.plan(sh->batch.serve_token(), shard_nrec(sh), fused_tab(sh->table));
-         return optimizer >= 0 && optimizer <= OPT_GROUP_LAMB && shard_owner_batchable(sh) && BatchIndex::takes_entries(served) && slot0[k] != nullptr &&
+         return optimizer >= 0 && optimizer <= OPT_GROUP_ACC3 && shard_owner_batchable(sh) && BatchIndex::takes_entries(served) && slot0[k] != nullptr &&
                         (!two_slots(optimizer) || (slot1 && slot1[k]))
                     ? sh->table->dim : -1; })) {
     const int m = (int)grp.size();

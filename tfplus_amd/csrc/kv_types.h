@@ -12,7 +12,8 @@ namespace __attribute__((visibility("hidden"))) kvhip_internal {
 enum Mode { MODE_LOOKUP = 0, MODE_APPLY = 1, MODE_DEDUP = 2, MODE_SCATTER = 3, MODE_MARK = 4, MODE_UNIQUE = 5,
             MODE_APPLYIDX = 6 };
 enum Opt { OPT_ADAM_V4 = 0, OPT_ADAM_V3 = 1, OPT_ADAGRAD = 2, OPT_FTRL = 3, OPT_FTRL_V2 = 4, OPT_GROUP_FTRL_V2 = 5,
-           OPT_GROUP_RADAM = 6, OPT_ADAM = 7, OPT_RADAM = 8, OPT_GROUP_ADAM4 = 9, OPT_GROUP_LAMB = 10 };
+           OPT_GROUP_RADAM = 6, OPT_ADAM = 7, OPT_RADAM = 8, OPT_GROUP_ADAM4 = 9, OPT_GROUP_LAMB = 10,
+           OPT_GROUP_ACC3 = 11 };
 // What the pipelines ask of an optimizer, in one place (a new OPT_* must answer each of them):
 // GroupAdam: one slot table of three dim-wide blocks (m | v | z)
 constexpr bool group_adam(int opt) { return opt == OPT_ADAM_V4 || opt == OPT_ADAM_V3; }
@@ -34,9 +35,10 @@ constexpr bool chain_gathers_var(int opt) { return opt == OPT_RADAM; }
 // dim-wide blocks of the first slot row (group RectifiedAdam: m | v | linear | vhat | vamsgrad; Adam: m | v; RectifiedAdam:
 // m | v | vhat; group AMSGrad / group AdaBelief, OPT_GROUP_ADAM4: m | v | linear | acc — a group op like group
 // RectifiedAdam, so none of group_adam, two_slots, keeps_var_flags, scatter_chain; group LAMB, OPT_GROUP_LAMB: m | v |
-// linear | accum, the same row and the same answers)
+// linear | accum, the same row and the same answers; group Momentum / group Adadelta, OPT_GROUP_ACC3: accum | linear | m
+// or accum | linear | accum_update — three blocks as GroupAdam's row, so state_blocks stays 3, and group LAMB's answers)
 constexpr int slot0_blocks(int opt) {
-  return opt == OPT_GROUP_RADAM ? 5 : (opt == OPT_GROUP_ADAM4 || opt == OPT_GROUP_LAMB) ? 4 : (group_adam(opt) || opt == OPT_RADAM) ? 3 : opt == OPT_ADAM ? 2 : 1;
+  return opt == OPT_GROUP_RADAM ? 5 : (opt == OPT_GROUP_ADAM4 || opt == OPT_GROUP_LAMB) ? 4 : (group_adam(opt) || opt == OPT_RADAM || opt == OPT_GROUP_ACC3) ? 3 : opt == OPT_ADAM ? 2 : 1;
 }
 // one wide slot table whose dim is a multiple of the var's (what the ops' initialisation and shape checks ask)
 constexpr bool wide_slot(int opt) { return slot0_blocks(opt) > 1; }
@@ -209,6 +211,15 @@ __host__ __device__ inline float& lamb_c1(OptArgs& a) { return a.lr_power; }
 __host__ __device__ inline float lamb_c1(const OptArgs& a) { return a.lr_power; }
 __host__ __device__ inline float& lamb_c2(OptArgs& a) { return a.alpha; }
 __host__ __device__ inline float lamb_c2(const OptArgs& a) { return a.alpha; }
+// ... and group Momentum / group Adadelta's (OPT_GROUP_ACC3; lr, eps, l1, l2, l21 as named): the decay scalar (momentum or
+// rho), 1 - rho (host, fp32; Adadelta only) and the variant, a wave-uniform run-time value: the two ops are one kernel family
+constexpr int ACC3_MOMENTUM = 0, ACC3_NESTEROV = 1, ACC3_ADADELTA = 2;
+__host__ __device__ inline float& acc3_decay(OptArgs& a) { return a.b1; }
+__host__ __device__ inline float acc3_decay(const OptArgs& a) { return a.b1; }
+__host__ __device__ inline float& acc3_omr(OptArgs& a) { return a.lr_power; }
+__host__ __device__ inline float acc3_omr(const OptArgs& a) { return a.lr_power; }
+__host__ __device__ inline int& acc3_variant(OptArgs& a) { return a.update_slots; }
+__host__ __device__ inline int acc3_variant(const OptArgs& a) { return a.update_slots; }
 // The vhat block (2) of RectifiedAdam's slot row takes part under amsgrad only: a wave-uniform test in front of its loads
 // and stores, so that the step without amsgrad moves two slot blocks.  Every other optimizer: all of its blocks, always
 // (the test folds away)

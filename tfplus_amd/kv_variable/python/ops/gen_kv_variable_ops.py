@@ -235,7 +235,7 @@ def _layout_args(stem, per, scalars):
 
 # floats the library reads from hp per optimizer code (kvhip.h kv_shard_apply_serve).  The C ABI takes a bare pointer, so the
 # length is checked here, where it is known: a vector in another family's layout is refused, not read past its end
-_HP_LEN = {0: 9, 1: 9, 2: 2, 3: 6, 4: 5, 5: 5, 6: 13, 7: 6, 8: 11, 9: 10, 10: 9}
+_HP_LEN = {0: 9, 1: 9, 2: 2, 3: 6, 4: 5, 5: 5, 6: 13, 7: 6, 8: 11, 9: 10, 10: 9, 11: 7}
 
 
 def _hp_array(hp, optimizer=None):
@@ -263,6 +263,14 @@ def _code_and_hp(stem, scalars):
     return (0 if int(scalars[-1]) == 4 else 1), sc[:-1]
   if stem in _GROUP_ADAM4_VARIANT:
     return 9, sc + [float(_GROUP_ADAM4_VARIANT[stem])]
+  # OPT_GROUP_ACC3's two stems share code 11 (hp = lr, decay, epsilon, l1, l2, l21, variant): the variant is appended —
+  # Momentum's from its trailing use_nesterov (0 / 1), with the epsilon it has no use for as 0; Adadelta's is 2
+  if stem == "group_momentum":
+    if int(scalars[-1]) not in (0, 1):
+      raise _lib.InvalidArgumentError("use_nesterov %d: 0 or 1" % int(scalars[-1]))
+    return 11, sc[:2] + [0.0] + sc[2:5] + [float(int(scalars[-1]))]
+  if stem == "group_adadelta":
+    return 11, sc + [2.0]
   return _COUNTED_CODE[stem], sc
 
 
@@ -388,6 +396,23 @@ def kv_variable_group_sparse_apply_lamb(var, opt, grad, indices, lr, beta1_power
   ratio |var| / |r| scales the step that enters linear).  token: as kv_variable_group_sparse_apply_rectified_adam's."""
   _apply("group_lamb", (var, opt), grad, indices, (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21),
          unique_indices, token, unique_count)
+
+
+def kv_variable_group_sparse_apply_momentum(var, opt, grad, indices, lr, momentum, l1, l2, l21, use_nesterov=False,
+                                            use_locking=False, name=None, unique_indices=False, token=None, unique_count=None):
+  """REGISTER_OP("KvVariableGroupSparseApplyMomentum") (kernels/training_ops.cc:2274-2508): the reference's three slot
+  variables are ONE slot table `opt` of dim 3 x the var's, accum | linear | m (kvhip.h kv_apply_group_momentum).  token: as
+  kv_variable_group_sparse_apply_rectified_adam's."""
+  _apply("group_momentum", (var, opt), grad, indices, (lr, momentum, l1, l2, l21, bool(use_nesterov)), unique_indices, token,
+         unique_count)
+
+
+def kv_variable_group_sparse_apply_adadelta(var, opt, grad, indices, lr, rho, epsilon, l1, l2, l21, use_locking=False,
+                                            name=None, unique_indices=False, token=None, unique_count=None):
+  """REGISTER_OP("KvVariableGroupSparseApplyAdadelta") (kernels/training_ops.cc:2005-2253): `opt` is one slot table of dim
+  3 x the var's, accum | linear | accum_update (kvhip.h kv_apply_group_adadelta: group Momentum's kernels, a run-time
+  variant apart)."""
+  _apply("group_adadelta", (var, opt), grad, indices, (lr, rho, epsilon, l1, l2, l21), unique_indices, token, unique_count)
 
 
 def kv_variable_sparse_apply_adam(var, m_v, grad, indices, lr, beta1_power, beta2_power, beta1, beta2, epsilon,
@@ -858,6 +883,20 @@ def kv_multi_group_sparse_apply_lamb(var_handles, opt_handles, grads, indices, l
                (lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21), unique_indices)
 
 
+def kv_multi_group_sparse_apply_momentum(var_handles, opt_handles, grads, indices, lr, momentum, l1, l2, l21,
+                                         use_nesterov=False, unique_indices=False):
+  """KvVariableGroupSparseApplyMomentum on many (var, opt) pairs with two kernel launches (one with unique_indices)."""
+  _multi_apply("group_momentum", "vars, opts, grads and indices", (var_handles, opt_handles), grads, indices,
+               (lr, momentum, l1, l2, l21, bool(use_nesterov)), unique_indices)
+
+
+def kv_multi_group_sparse_apply_adadelta(var_handles, opt_handles, grads, indices, lr, rho, epsilon, l1, l2, l21,
+                                         unique_indices=False):
+  """KvVariableGroupSparseApplyAdadelta on many (var, opt) pairs with two kernel launches (one with unique_indices)."""
+  _multi_apply("group_adadelta", "vars, opts, grads and indices", (var_handles, opt_handles), grads, indices,
+               (lr, rho, epsilon, l1, l2, l21), unique_indices)
+
+
 def kv_multi_sparse_apply_adam(var_handles, m_v_handles, grads, indices, lr, beta1_power, beta2_power, beta1, beta2,
                                epsilon, unique_indices=False):
   """kv_variable_sparse_apply_adam on many (var, m_v) pairs with two kernel launches (one with unique_indices)."""
@@ -1195,6 +1234,9 @@ OPT_RADAM = 8  # slots = (opt,): m | v | vhat
 # group AMSGrad / group AdaBelief: hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21, variant (0 AMSGrad,
 # 1 AdaBelief); slots = (opt,): m | v | linear | acc
 OPT_GROUP_ADAM4 = 9
+# group Momentum / group Adadelta: hp = lr, decay (momentum or rho), epsilon (Momentum: unused), l1, l2, l21, variant (0 Momentum,
+# 1 Momentum with use_nesterov, 2 Adadelta); slots = (opt,): accum | linear | m or accum | linear | accum_update
+OPT_GROUP_ACC3 = 11
 OPT_GROUP_LAMB = 10   # hp = lr, beta1_power, beta2_power, beta1, beta2, epsilon, l1, l2, l21; slots = (opt,): m | v | linear | accum
 
 
